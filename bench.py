@@ -181,6 +181,30 @@ def verify_on_gpu(mf, ctx, inst, proof):
     return ok
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 4242  # --dump-outputs: which statements' proofs are written whole (fixed, so that two builds write the same sample)
+
+
+def dump_proofs(out_dir, torch, proofs, nst, ct_limbs):
+    """--dump-outputs: what the timed path returned in its last step -- `nst` proofs of 5 ciphertexts of `ct_limbs` uint64 limbs each -- as float64 .npy files:
+    proof_ct_word_sums.npy  (nst, 5)           every ciphertext of every proof: the sum of its uint32 words (< 2^48, exact in float64);
+    proof_statements.npy    (k,)               the statement indices of the sample below (a fixed seeded choice, sorted; all statements when they fit);
+    proofs.npy              (k, 5, 2 ct_limbs) those proofs whole, one uint32 word per element (little-endian halves of the limbs, exact in float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = (proofs.view(torch.int32).view(nst, 5, 2 * ct_limbs).to(torch.int64) & 0xFFFFFFFF)
+    sums = words.sum(dim=2).cpu().numpy().astype(np.float64)
+    per_proof = 5 * 2 * ct_limbs * 8
+    k = min(nst, 32, (DUMP_LIMIT_BYTES - sums.nbytes - 32 * 8 - 3 * 4096) // per_proof)  # (4096: room for each file's .npy header)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nst, size=k, replace=False)) if k < nst else np.arange(nst)
+    sample = words[torch.from_numpy(idx).to(words.device)].cpu().numpy().astype(np.float64)
+    files = {"proof_ct_word_sums": sums, "proof_statements": idx.astype(np.float64), "proofs": sample}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in files)
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs wrote {total} bytes"
+    print(f"[bench] --dump-outputs: {', '.join(files)} ({total / 2 ** 20:.1f} MB; {k} of {nst} proofs whole) -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def usable_cores(cap=32):
     """cores this process may really use: the affinity mask, cut down to the cgroup CPU quota (a one-GPU box shares a big host)"""
     try:
@@ -289,7 +313,14 @@ def main():
                     help="default = benchmark_snark NDEBUG instance (the driver's workload); config4/config5 = BASELINE's 2^20-constraint "
                          "instance (M = 699050, generator-defined SSP) at logq 736 / 1472")
     ap.add_argument("--cpu-rows", type=int, default=20000, help="rows of the CPU baseline sample (~0.65 ms each on one core)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step returned (its proofs: per-ciphertext word sums of all, a fixed sample "
+                         "whole) as float64 .npy files into DIR (bench_outputs/<run> is git-ignored), at most 64 MB; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "default" and args.gpus > 1 and (args.mode or "single") == "batch":
+        ap.error("--dump-outputs: the row-sharded batch headline (config4/5, --mode batch, N > 1) does not return its proofs on one rank")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)  # no launcher: be one (before anything touches the GPU)
@@ -444,6 +475,8 @@ def main():
             proof = step()
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and mode == "single" and rank == 0:
+            dump_proofs(args.dump_outputs, torch, proof, 1, p.ct_limbs)
         ctx.set_timing(False)
         n2, ms2, rows2 = ctx.timing_drain("eval2")
         n1, ms1, rows1 = ctx.timing_drain("eval1")
@@ -662,6 +695,8 @@ def main():
         # headline: the CRS expanded once per call (= per step) into a transient image, streamed for every super-group of 255 proofs
         ctx.poly_exact_fallbacks()
         out_b, el_b, kt_b = run_batch()
+        if args.dump_outputs and rank == 0:
+            dump_proofs(args.dump_outputs, torch, out_b, nb, p.ct_limbs)
         recomputed_b = ctx.poly_exact_fallbacks()  # statements whose polynomial step fell back to Euclidean division, warm-up and timed calls (-1: no exact path for this t)
         ok_b = ctx.to_host(ctx.verify(d_ssp_b, inst["alpha"], inst["beta"], inst["s"], inst["sk"], out_b, nb))
         torch.cuda.synchronize()
