@@ -977,8 +977,13 @@ int mfh_poly_mul(mfh_ctx *c, const uint32_t *d_a, size_t la, const uint32_t *d_b
 }
 
 int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
-  if (c) c->ssp_frag_src = nullptr;  // a (new) SSP is being prepared: derived images are stale
-  if (!c || !d_t) return MFH_EINVAL;
+  if (!c) return MFH_EINVAL;
+  c->ssp_frag_src = nullptr;  // a (new) SSP is being prepared: derived images are stale
+  if (c->poly) {  // ... and so is the t prepared before: a call that fails below must not leave it in place for mfh_poly_h*
+    c->poly->have_t = false;
+    c->poly->cyc = false;
+  }
+  if (!d_t) return MFH_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t d = c->P.d;
   std::vector<uint32_t> t(d);

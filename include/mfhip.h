@@ -169,16 +169,21 @@ int mfh_ssp_prg_make_t(mfh_ctx *ctx, uint64_t seed, const uint8_t *h_witness_bit
 int mfh_ssp_prg_fill(mfh_ctx *ctx, uint64_t seed, size_t first_slot, size_t nslots, uint32_t *d_out);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
-/* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167). */
+/* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
+ * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
+ * transforms the context has prepared rebuilds them and forgets the prepared t: mfh_poly_h* then fail until mfh_poly_prepare_t is called again. */
 int mfh_poly_mul(mfh_ctx *ctx, const uint32_t *d_a, size_t la, const uint32_t *d_b, size_t lb, uint32_t *d_c);
 int mfh_poly_add(mfh_ctx *ctx, const uint32_t *d_a, const uint32_t *d_b, size_t count, uint32_t *d_out);
 /* Per-SSP precomputation for the quotient by t(x): power-series inverse of rev(t) (and its transform).
- * d_t = d coefficients (slot 0 of the device SSP).  Fails (MFH_EINVAL) for t = 0, where nmod_poly_div raises. */
+ * d_t = d coefficients (slot 0 of the device SSP).  Fails (MFH_EINVAL) for t = 0, where nmod_poly_div raises.
+ * Limit: 4 d - deg t <= 2^23, i.e. d <= 2 796 202 when deg t = d - 1 and d <= 2^21 when deg t is small; beyond it MFH_EUNSUPPORTED.
+ * A call that fails leaves no t prepared (mfh_poly_h* fail until a call succeeds). */
 int mfh_poly_prepare_t(mfh_ctx *ctx, const uint32_t *d_t);
 int mfh_ssp_prepare(mfh_ctx *ctx, const uint32_t *d_ssp); /* = mfh_poly_prepare_t(slot 0) */
 /* h = floor((v^2 - 1) / t), first d coefficients (nmod_poly_pow/sub/div, src/snark.c:166-169).  v: d coefficients. */
 int mfh_poly_h(mfh_ctx *ctx, const uint32_t *d_v, uint32_t *d_h);
-/* the same for nb polynomials side by side (v_k at d_v + k d, h_k at d_h + k d): one set of launches for the whole batch */
+/* the same for nb polynomials side by side (v_k at d_v + k d, h_k at d_h + k d): one set of launches for the whole batch.
+ * Limit: 1 <= nb <= 21845 (three grid rows per polynomial, 65535 at most); MFH_EINVAL outside. */
 int mfh_poly_h_multi(mfh_ctx *ctx, const uint32_t *d_v, uint32_t *d_h, uint32_t nb);
 /* A batch (nb >= 4) takes the exact-division path when the prepared t has degree d - 1 and is a unit modulo x^N - 1 (N = the power of two >= d): a prover with a valid
  * witness divides exactly (src/ssp.c:37-77), and then h = (v^2 - 1 mod x^N - 1) t^-1 mod x^N - 1 -- two cyclic products of length N instead of two linear ones of

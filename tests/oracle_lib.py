@@ -235,6 +235,72 @@ class Oracle:
         return int(self.lib.mfo_bench_encrypt(ctypes.byref(cp), ctypes.c_char_p(bytes(seed)), ctypes.c_size_t(count)))
 
 
+
+# ---- exact polynomial reference (oracle/poly_kron.c in libmf_gmpcheck.so): GMP products by Kronecker substitution, certified Euclidean quotients
+GMPCHECK_SO = os.path.join(ORACLE_DIR, "libmf_gmpcheck.so")
+
+
+def _u32(a) -> np.ndarray:
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.uint32:
+        assert a.size == 0 or int(a.max()) < 2**32
+        a = a.astype(np.uint32)
+    return a
+
+
+class PolyKron:
+    """F_p[x] at any length the GPU runs, exactly: c = a b (one mpz_mul), q = (v^2 - 1) div t (Newton on top of it) and the certificate
+    of a quotient.  Raises (never skips) when libmf_gmpcheck.so has not been built.  The calls release the GIL (ctypes.CDLL): check a batch on threads."""
+
+    def __init__(self):
+        if not os.path.exists(GMPCHECK_SO):
+            raise RuntimeError(f"{GMPCHECK_SO} is missing: build() makes it (oracle/Makefile, target gmpcheck; needs gmp.h)")
+        self.lib = ctypes.CDLL(GMPCHECK_SO)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        self.lib.pk_poly_mul_modp.argtypes = [vp, sz, vp, sz, vp]
+        self.lib.pk_poly_mul_modp.restype = ctypes.c_int
+        self.lib.pk_poly_div_certify.argtypes = [vp, sz, vp, sz, vp, sz]
+        self.lib.pk_poly_div_certify.restype = ctypes.c_int
+        self.lib.pk_poly_div.argtypes = [vp, sz, vp, sz, vp]
+        self.lib.pk_poly_div.restype = ctypes.c_long
+
+    def mul(self, a, b=None) -> np.ndarray:
+        """a b mod p, len(a) + len(b) - 1 coefficients (uint32); b = None: the square of a"""
+        a = _u32(a)
+        b = a if b is None else _u32(b)
+        out = np.zeros(len(a) + len(b) - 1, dtype=np.uint32)
+        assert self.lib.pk_poly_mul_modp(_p(a), len(a), _p(b), len(b), _p(out)) == 0
+        return out
+
+    def div_certify(self, v, t, q) -> bool:
+        """is q the Euclidean quotient of v^2 - 1 by t (nmod_poly_div's), trailing zeros aside?"""
+        v, t, q = _u32(v), _u32(t), _u32(q)
+        rc = self.lib.pk_poly_div_certify(_p(v), len(v), _p(t), len(t), _p(q), len(q))
+        assert rc >= 0, "t = 0 or out of memory"
+        return bool(rc)
+
+    def div(self, v, t) -> np.ndarray:
+        """the whole Euclidean quotient of v^2 - 1 by t (2 len(v) - 1 coefficients, zero above deg A - deg t), certified"""
+        v, t = _u32(v), _u32(t)
+        q = np.zeros(2 * len(v) - 1, dtype=np.uint32)
+        rc = self.lib.pk_poly_div(_p(v), len(v), _p(t), len(t), _p(q))
+        assert rc >= 0, f"pk_poly_div failed ({rc})"
+        return q
+
+
+def product_of_constants(ca: int, la: int, cb: int, lb: int) -> np.ndarray:
+    """(ca + ca x + ... + ca x^(la-1)) (cb + ... + cb x^(lb-1)) mod p: c_k = ca cb #{(i, j): i + j = k}, in O(la + lb)"""
+    k = np.arange(la + lb - 1, dtype=np.int64)
+    cnt = np.minimum(k, la - 1) - np.maximum(0, k - (lb - 1)) + 1
+    return ((cnt.astype(np.uint64) * np.uint64(ca * cb % P)) % np.uint64(P)).astype(np.uint32)
+
+
+def product_of_monomials(i: int, ca: int, la: int, j: int, cb: int, lb: int) -> np.ndarray:
+    """(ca x^i) (cb x^j) as la + lb - 1 coefficients mod p"""
+    out = np.zeros(la + lb - 1, dtype=np.uint32)
+    out[i + j] = ca * cb % P
+    return out
+
 def limbs_to_int(v) -> int:
     return int.from_bytes(np.ascontiguousarray(v, dtype=np.uint64).tobytes(), "little")
 

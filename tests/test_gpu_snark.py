@@ -95,8 +95,9 @@ def test_exact_division_path_is_checked_and_falls_back(gpu_ctx_factory, oracle, 
     """A batch of h = (v^2 - 1) / t goes through two CYCLIC products of length N = 2^ceil(log2 d) (the exact quotient of a valid witness is determined modulo x^N - 1),
     is checked on the device and recomputed by Euclidean division when one statement does not divide (src/snark.c:166-169 computes nmod_poly_div whatever the witness):
     (i) valid witnesses only: equal to the oracle's quotients, no statement recomputed; (ii) the same batch with two statements whose v does not belong to the SSP:
-    equal to the oracle's (Euclidean) quotients, those two counted; (iii) the same with the path switched off.  d = 1152: N = 2048 > d; 2048 / 4096: the register
-    kernels with one and two passes above the 2048-point blocks."""
+    equal to the oracle's (Euclidean) quotients, those two counted; (iii) the same with the path switched off.  d = 1152: N = 2048 > d; d = 2048: N = 2048, the generic cyclic
+    products (no register pass above the 2048-point blocks); d = 4096: the fused seam kernel with one register stage, k_exact_seam<1> (the other seam shapes
+    and the paths beyond them: test_gpu_poly_exact.py)."""
     p = mf.Params(logq=736, d=d, m=m)
     c = gpu_ctx_factory(p)
     rng = np.random.default_rng(d)
