@@ -97,6 +97,7 @@ EXPORTS = [
     "mfh_ssp_set_prg", "mfh_ssp_prg_make_t", "mfh_ssp_prg_fill",
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
+    "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
 ]
 
 
@@ -206,6 +207,11 @@ def load_library():
         "mfh_witness_poly_mm_cols": (i32, [vp, vp, u32, ctypes.c_char_p, sz, vp, u32, u32, vp, sz]),
         "mfh_prove_batch_partial": (i32, [vp, vp, u32, u32, u32, ctypes.c_char_p, sz, vp, vp, vp, sz, vp]),
         "mfh_prove_batch_finish": (i32, [vp, vp, u32, vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp]),
+        "mfh_setup_public": (i32, [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]),
+        "mfh_prove_public": (i32, [vp, vp, vp, u32, ctypes.c_char_p, u32, ctypes.c_char_p, sz, ctypes.c_char_p, vp]),
+        "mfh_prove_batch_public": (i32, [vp, vp, vp, u32, u32, ctypes.c_char_p, sz, vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp]),
+        "mfh_vk_derive": (i32, [vp, vp, u32, u32, vp]),
+        "mfh_verify_public": (i32, [vp, vp, u32, u32, u32, vp, vp, ctypes.c_char_p, sz, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -709,6 +715,55 @@ class Context:
         """verifier() (src/snark.c:192-250) for `count` proofs on the device; returns a uint8 tensor of accept bits"""
         ok = self.empty(count)
         self._chk(self.lib.mfh_verify(self._h, _ptr(d_ssp), alpha, beta, s, _ptr(d_sk), _ptr(d_proofs), count, _ptr(ok)))
+        return ok
+
+    # -- public inputs: bits [0, lu) of a statement's m - 1 input bits are public (include/mfhip.h; the reference fixes l_u = 0) ---------------------
+    def setup_public(self, d_ssp, alpha, beta, s, lu, d_sk, d_err, out=None, rows=None, image=False):
+        """setup() with rows v[0..lu) encrypting 0: returns the device CRS, or (CRS, expanded rows) with image=True"""
+        p = self.params
+        out = self.empty((2 * p.d + p.m) * p.ctb) if out is None else out
+        if image and rows is None:
+            rows = self.empty((2 * p.d + p.m) * self.resident_row_bytes())
+        self._chk(self.lib.mfh_setup_public(self._h, _ptr(d_ssp), alpha, beta, s, lu, _ptr(d_sk), _ptr(d_err), _ptr(out), _ptr(rows if image else None)))
+        return (out, rows) if image else out
+
+    def prove_public(self, d_crs, d_ssp, lu, bits: bytes, delta, smudge_mag: bytes, smudge_sign: bytes, maglen=80, out=None):
+        """one proof of the statement bits[0, lu) with the witness bits[lu, m - 1): 5 ciphertexts h | hat_h | hat_v | v_w | b_w"""
+        p = self.params
+        out = self.empty(5 * p.ct_limbs * 8) if out is None else out
+        assert len(smudge_mag) == 5 * maglen and len(smudge_sign) == 5
+        stride = (p.m + 6) // 8
+        self._chk(self.lib.mfh_prove_public(self._h, _ptr(d_crs), _ptr(d_ssp), lu, bytes(bits[:stride]).ljust(stride, b"\0"), delta, bytes(smudge_mag),
+                                            maglen, bytes(smudge_sign), _ptr(out)))
+        return out
+
+    def prove_batch_public(self, d_crs, d_ssp, lu, bits_list, deltas, smudge_mags, smudge_signs, maglen=80, out=None):
+        """prove_batch with a statement per proof (bits_list[b][0, lu)); proof b equals prove_public of statement b"""
+        p = self.params
+        nb = len(bits_list)
+        bits, stride = self._pack_bits(bits_list)
+        dl = (ctypes.c_uint32 * nb)(*[int(x) for x in deltas])
+        mags = b"".join(bytes(x) for x in smudge_mags)
+        signs = b"".join(bytes(x) for x in smudge_signs)
+        assert len(mags) == nb * 5 * maglen and len(signs) == nb * 5
+        out = self.empty(nb * 5 * p.ct_limbs * 8) if out is None else out
+        self._chk(self.lib.mfh_prove_batch_public(self._h, _ptr(d_crs), _ptr(d_ssp), lu, nb, bits, stride, ctypes.cast(dl, ctypes.c_void_p), mags,
+                                                  maglen, signs, _ptr(out)))
+        return out
+
+    def derive_vk(self, d_ssp, s, lu):
+        """the verification key [t(s), v_0(s), v_1(s) .. v_lu(s)] mod p: lu + 2 uint32 on the device"""
+        vk = self.empty((lu + 2) * 4)
+        self._chk(self.lib.mfh_vk_derive(self._h, _ptr(d_ssp), s, lu, _ptr(vk)))
+        return vk
+
+    def verify_public(self, d_vk, lu, alpha, beta, d_sk, d_proofs, statements, count=None):
+        """verifier() with statements (bytes each, bit i = u_i; bits lu and above ignored) from the verification key; a uint8 tensor of accept bits"""
+        count = len(statements) if count is None else count
+        ub = max(1, (lu + 7) // 8)
+        st = b"".join(bytes(u[:ub]).ljust(ub, b"\0") for u in statements)
+        ok = self.empty(count)
+        self._chk(self.lib.mfh_verify_public(self._h, _ptr(d_vk), lu, alpha, beta, _ptr(d_sk), _ptr(d_proofs), st, ub, count, _ptr(ok)))
         return ok
 
     # -- generator-defined SSP (BASELINE configs 4/5): pass d_ssp=None to the SSP-consuming calls afterwards ---------

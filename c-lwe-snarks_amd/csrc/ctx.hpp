@@ -125,6 +125,10 @@ struct mfh_ctx {
   int batch_merge = 1;     // the S and AS groups of a round in one streaming launch (0: two launches on two streams)
   uint32_t batch_ngl = 8;  // groups of 63 / 64 coefficient vectors per streaming launch and region (1..8; 8 = a super-group's S and AS regions in ONE launch)
   PinBuf pin_rows, pin_cw, pin_smudge;
+  // public inputs (mfh_prove_public / mfh_prove_batch_public): the statement bits, ceil(lu / 8) bytes per statement, staged and on the device
+  PinBuf pin_pub;
+  uint8_t *d_pub = nullptr;
+  size_t pub_bytes = 0;
   // the batch chain's witness staging (one per super-group of a call, evalmm.hip): a ring, so that queueing super-group k + 1 does not wait on the host for
   // super-group k's copy to have RUN (with one buffer mfh_prove_batch blocked its caller for half of the call's GPU time)
   PinBuf pin_wring[8];

@@ -1121,6 +1121,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   for (auto &b : c->pin_wring) pin_free(b);
   pin_free(c->pin_cw);
   pin_free(c->pin_smudge);
+  pin_free(c->pin_pub);
   if (c->side) hipStreamSynchronize(c->side);
   if (c->ws) hipFree(c->ws);
   if (c->wws) hipFree(c->wws);
@@ -1142,6 +1143,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   if (c->side2) hipStreamDestroy(c->side2);
   if (c->d_msg) hipFree(c->d_msg);
   if (c->d_prover) hipFree(c->d_prover);
+  if (c->d_pub) hipFree(c->d_pub);
   if (c->d_batch) hipFree(c->d_batch);
   if (c->batch_img) hipFree(c->batch_img);
   if (c->ssp_frag) hipFree(c->ssp_frag);

@@ -96,6 +96,41 @@ __global__ void k_add_slot_multi(const uint32_t *__restrict__ a, mf::SspSrc src,
   const size_t o = (size_t)blockIdx.y * d + k;
   out[o] = red_p32((uint64_t)a[o] + ssp_coef(src, slot, mf::ssp_prg_rowkey(src.seed, slot), d, k));
 }
+// Public inputs (src/lwe.h:26 GAMMA_LU; the reference fixes l_u = 0, src/snark.c:160): V = W + v_0 + sum_{i < lu, u_i = 1} v_{i+1} mod p for
+// `nstmt` statements side by side (W, V, extra strided by d).  Statement b's bits u_i are ubits[b * ustride + i / 8] bit i % 8.  A block owns 256 coefficients of
+// NB statements: public row i (slot i + 2) is read -- or generated -- once per block and only when one of its NB statements selects it, so the rows of a
+// super-group pass through L2 ceil(nstmt / NB) times (10 rows x 128 KiB at the default instance).  extra != nullptr: one more polynomial per statement is
+// added (the public sum formed by a second witness pass, for large lu).  Sums stay below 2^64 for lu < 2^31.
+template <int NB>
+__global__ __launch_bounds__(256) void k_add_public(const uint32_t *__restrict__ W, mf::SspSrc src, uint32_t d, uint32_t lu, const uint8_t *__restrict__ ubits,
+                                                    uint32_t ustride, uint32_t nstmt, const uint32_t *__restrict__ extra, uint32_t *__restrict__ V) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t b0 = blockIdx.y * NB;
+  if (k >= d || b0 >= nstmt) return;
+  const uint32_t nb = min((uint32_t)NB, nstmt - b0);
+  const uint32_t v0 = ssp_coef(src, 1, mf::ssp_prg_rowkey(src.seed, 1), d, k);
+  uint64_t acc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    const size_t o = (size_t)(b0 + j) * d + k;
+    acc[j] = (uint32_t)j < nb ? (uint64_t)W[o] + v0 + (extra ? extra[o] : 0u) : 0;
+  }
+  for (uint32_t i = 0; i < lu; i++) {
+    uint32_t sel = 0;  // (uniform across the block)
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+      if ((uint32_t)j < nb) sel |= (uint32_t)((ubits[(size_t)(b0 + j) * ustride + (i >> 3)] >> (i & 7)) & 1u) << j;
+    if (!sel) continue;
+    const uint32_t slot = i + 2;
+    const uint32_t x = ssp_coef(src, slot, mf::ssp_prg_rowkey(src.seed, slot), d, k);
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+      if ((sel >> j) & 1u) acc[j] += x;
+  }
+#pragma unroll
+  for (int j = 0; j < NB; j++)
+    if ((uint32_t)j < nb) V[(size_t)(b0 + j) * d + k] = red_p32(acc[j]);
+}
 // b_w of proof blockIdx.y += delta[blockIdx.y] * ct_t (ct_addmul_ui, src/lwe.c:141-149, for a batch: proofs are 5 ciphertexts apart)
 __global__ void k_bw_add_delta_ct(uint64_t *__restrict__ proofs, const uint64_t *__restrict__ ct_t, const uint32_t *__restrict__ delta, uint32_t nvalues,
                                   uint32_t L, uint32_t KW) {
@@ -145,7 +180,8 @@ __global__ void k_ct_from_lanes(const uint64_t *__restrict__ lanes, uint64_t nva
   for (uint32_t l = K; l < L; l++) o[l] = 0;  // modq: what exceeds 2^(64 K) is dropped
 }
 
-// scal[r] = <slot r, pw> mod p for r = 0 (t) and 1 (v_0): nmod_poly_evaluate_nmod of src/snark.c:201,213
+// scal[r] = <slot r, pw> mod p for r < gridDim.x: r = 0 (t) and 1 (v_0) for verifier() (nmod_poly_evaluate_nmod of src/snark.c:201,213); 0 .. lu + 1 for the
+// verification key of mfh_vk_derive (t, v_0, v_1 .. v_lu)
 __global__ __launch_bounds__(256) void k_eval_slots01(mf::SspSrc src, const uint32_t *__restrict__ pw, uint32_t d, uint32_t *__restrict__ scal) {
   __shared__ uint64_t red[4];
   const uint32_t slot = blockIdx.x;
@@ -161,19 +197,36 @@ __global__ __launch_bounds__(256) void k_eval_slots01(mf::SspSrc src, const uint
   __syncthreads();
   if (threadIdx.x == 0) scal[blockIdx.x] = red_p32(red[0] + red[1] + red[2] + red[3]);
 }
+// the four checks of verifier() (src/snark.c:219-235) on the decrypted values of one proof, v_s = v(s) already formed
+__device__ __forceinline__ bool verify_checks(uint32_t h_s, uint32_t hath_s, uint32_t hatv_s, uint32_t w_s, uint32_t b_s, uint32_t t_s, uint32_t v_s,
+                                              uint32_t alpha, uint32_t beta) {
+  bool good = mulmod(h_s, alpha) == hath_s;                                         // eq-pke
+  good = good && mulmod(v_s, alpha) == hatv_s;
+  good = good && red_p32((uint64_t)mulmod(v_s, v_s) + P32 - 1) == mulmod(h_s, t_s);  // eq-div
+  good = good && mulmod(w_s, beta) == b_s;                                          // eq-lin
+  return good;  // the reference's "test-error" bound (src/snark.c:238-241) can never reject
+}
 // the four checks of verifier() (src/snark.c:219-235) on decrypted values dec[5*i .. 5*i+5) = h, hat_h, hat_v, v_w, b_w
 __global__ void k_verify(const uint32_t *__restrict__ dec, const uint32_t *__restrict__ scal, uint32_t alpha, uint32_t beta, uint32_t count,
                          uint8_t *__restrict__ ok) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const uint32_t h_s = dec[5 * i], hath_s = dec[5 * i + 1], hatv_s = dec[5 * i + 2], w_s = dec[5 * i + 3], b_s = dec[5 * i + 4];
-  const uint32_t t_s = scal[0];
-  const uint32_t v_s = red_p32((uint64_t)scal[1] + w_s);
-  bool good = mulmod(h_s, alpha) == hath_s;                                         // eq-pke
-  good = good && mulmod(v_s, alpha) == hatv_s;
-  good = good && red_p32((uint64_t)mulmod(v_s, v_s) + P32 - 1) == mulmod(h_s, t_s);  // eq-div
-  good = good && mulmod(w_s, beta) == b_s;                                          // eq-lin
-  ok[i] = good ? 1 : 0;  // the reference's "test-error" bound (src/snark.c:238-241) can never reject
+  const uint32_t *x = dec + 5 * (size_t)i;
+  const uint32_t v_s = red_p32((uint64_t)scal[1] + x[3]);
+  ok[i] = verify_checks(x[0], x[1], x[2], x[3], x[4], scal[0], v_s, alpha, beta) ? 1 : 0;
+}
+// the same with a statement: v_s = v_0(s) + sum_{i < lu, u_i = 1} v_i(s) + w_s mod p from the verification key vk = [t(s), v_0(s), v_1(s) .. v_lu(s)]
+// (src/snark.c:213-217 with l_u public wires); proof i's statement bits are ubits[i * ustride ..], bits lu and above are not read
+__global__ void k_verify_public(const uint32_t *__restrict__ dec, const uint32_t *__restrict__ vk, uint32_t lu, const uint8_t *__restrict__ ubits,
+                                uint32_t ustride, uint32_t alpha, uint32_t beta, uint32_t count, uint8_t *__restrict__ ok) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t *x = dec + 5 * (size_t)i;
+  const uint8_t *u = ubits + (size_t)i * ustride;
+  uint32_t v_s = red_p32((uint64_t)vk[1] + x[3]);
+  for (uint32_t j = 0; j < lu; j++)
+    if ((u[j >> 3] >> (j & 7)) & 1) v_s = red_p32((uint64_t)v_s + vk[j + 2]);
+  ok[i] = verify_checks(x[0], x[1], x[2], x[3], x[4], vk[0], v_s, alpha, beta) ? 1 : 0;
 }
 
 inline dim3 g1(uint32_t n) { return dim3((n + 255) / 256); }
@@ -271,6 +324,75 @@ int mfh_verify(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta,
   return MFH_OK;
 }
 
+// ---- public inputs (src/lwe.h:26; the reference has l_u = 0, src/snark.c:160) -----------------------------------------------------------
+int mfh_setup_public(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, uint32_t lu, const uint64_t *d_sk, const uint64_t *d_err,
+                     uint8_t *d_crs_c8, void *d_rows_image) {
+  if (!c) return MFH_EINVAL;
+  if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  if (!lu) return mfh_setup_image(c, d_ssp, alpha, beta, s, d_sk, d_err, d_crs_c8, d_rows_image);
+  if (!d_sk || !d_err || !d_crs_c8) return MFH_EINVAL;
+  const size_t rows = (size_t)2 * c->P.d + c->P.m;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->d_msg || c->msg_rows < rows) {
+    if (c->d_msg) { hipStreamSynchronize(c->stream); hipFree(c->d_msg); c->d_msg = nullptr; }
+    HIP_TRY(c, hipMalloc(&c->d_msg, rows * 4));
+    c->msg_rows = rows;
+  }
+  int rc = mfh_setup_messages(c, d_ssp, alpha, beta, s, c->d_msg);
+  if (rc) return rc;
+  // rows v[0..lu) (messages 2d + 1 .. 2d + lu) encrypt 0 instead of beta v_i(s): same stream rows, same errors
+  HIP_TRY(c, hipMemsetAsync(c->d_msg + (size_t)2 * c->P.d + 1, 0, (size_t)lu * 4, c->stream));
+  rc = mfh_encrypt_rows(c, 0, rows, d_sk, c->d_msg, d_err, d_crs_c8);
+  if (rc || !d_rows_image) return rc;
+  return mfh_crs_expand(c, 0, rows, d_crs_c8, d_rows_image);
+}
+
+int mfh_vk_derive(mfh_ctx *c, const uint32_t *d_ssp, uint32_t s, uint32_t lu, uint32_t *d_vk) {
+  if (!c || !d_vk) return MFH_EINVAL;
+  if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  if (s >= P32) { c->err = "s must be < p"; return MFH_EINVAL; }
+  const uint32_t d = c->P.d;
+  HIP_TRY(c, hipSetDevice(c->device));
+  mf::SspSrc src;
+  int rc = ssp_src(c, d_ssp, src);
+  if (rc) return rc;
+  rc = aux_reserve(c, (size_t)d * 4);
+  if (rc) return rc;
+  uint32_t *pw = (uint32_t *)c->aux;
+  hipLaunchKernelGGL(k_powers, g1(d), dim3(256), 0, c->stream, s, d, pw);
+  hipLaunchKernelGGL(k_eval_slots01, dim3(lu + 2), dim3(256), 0, c->stream, src, pw, d, d_vk);  // slots 0 (t), 1 (v_0), 2 .. lu + 1 (v_1 .. v_lu)
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
+int mfh_verify_public(mfh_ctx *c, const uint32_t *d_vk, uint32_t lu, uint32_t alpha, uint32_t beta, const uint64_t *d_sk, const uint64_t *d_proofs,
+                      const uint8_t *h_statements, size_t stmt_stride, size_t count, uint8_t *d_ok) {
+  if (!c || !d_vk || !d_sk || (count && (!d_proofs || !d_ok))) return MFH_EINVAL;
+  if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  if (alpha >= P32 || beta >= P32) { c->err = "alpha, beta must be < p"; return MFH_EINVAL; }
+  const uint32_t ub = (lu + 7) / 8;
+  if (lu && count && (!h_statements || stmt_stride < ub)) { c->err = "statements: stmt_stride shorter than the lu statement bits"; return MFH_EINVAL; }
+  if (!count) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t dec_b = (count * 5 * 4 + 15) & ~(size_t)15;
+  int rc = aux_reserve(c, dec_b + count * ub + 16);
+  if (rc) return rc;
+  uint32_t *dec = (uint32_t *)c->aux;
+  uint8_t *ubits = (uint8_t *)c->aux + dec_b;
+  if (lu) {
+    uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_cw, count * ub);
+    if (!st) return MFH_ENOMEM;
+    for (size_t i = 0; i < count; i++) memcpy(st + i * ub, h_statements + i * stmt_stride, ub);
+    HIP_TRY(c, hipMemcpyAsync(ubits, st, count * ub, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_cw);
+  }
+  rc = mfh_decrypt(c, d_sk, d_proofs, 5 * count, dec);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_verify_public, g1((uint32_t)count), dim3(256), 0, c->stream, dec, d_vk, lu, ubits, ub, alpha, beta, (uint32_t)count, d_ok);
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
 uint32_t mfh_lanes_per_value(const mfh_ctx *c) { return c ? (64 * (c->P.logq / 64) + 55) / 56 : 0; }
 int mfh_ct_to_lanes(mfh_ctx *c, const uint64_t *d_cts, size_t count, uint64_t *d_lanes) {
   if (!c || !d_cts || !d_lanes) return MFH_EINVAL;
@@ -294,10 +416,19 @@ int mfh_ct_from_lanes(mfh_ctx *c, const uint64_t *d_lanes, size_t count, uint64_
   return MFH_OK;
 }
 
+// lu > 0 (mfh_prove_public; world == 1, no lanes): bits [0, lu) are the statement u -- left out of w and b_w, added into v -- the rest the witness
 static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, const uint8_t *h_witness_bits, uint32_t delta,
-                              uint32_t rank, uint32_t world, const uint64_t *d_wlanes, uint64_t *d_partial) {
+                              uint32_t rank, uint32_t world, const uint64_t *d_wlanes, uint64_t *d_partial, uint32_t lu = 0) {
   if (!c || !d_crs_c8 || !h_witness_bits || !d_partial || world == 0 || rank >= world) return MFH_EINVAL;
   if (delta >= P32) { c->err = "delta must be < p"; return MFH_EINVAL; }
+  if (lu && (lu >= c->P.m || world != 1 || d_wlanes)) { c->err = "public inputs: lu < m, single GPU"; return MFH_EINVAL; }
+  std::vector<uint8_t> priv;  // the witness bits with the statement's cleared
+  const uint8_t *const h_stmt = h_witness_bits;
+  if (lu) {
+    priv.assign(h_witness_bits, h_witness_bits + (c->P.m + 6) / 8);
+    for (uint32_t i = 0; i < lu; i++) priv[i >> 3] &= (uint8_t) ~(1u << (i & 7));
+    h_witness_bits = priv.data();
+  }
   mf::SspSrc src;
   {
     int rc0 = ssp_src(c, d_ssp, src);
@@ -307,13 +438,15 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
   const uint32_t L = (c->P.logq + 63) / 64, ctb = c->P.logq / 8;
   const size_t ctl = (size_t)(n + 1) * L;
   HIP_TRY(c, hipSetDevice(c->device));
-  // prover scratch: w, v, h (d each), cw (m)
-  if (!c->d_prover || c->prover_words < (size_t)3 * d + m) {
+  // prover scratch: w, v, h (d each), cw (m), the statement bits (lu < m bits)
+  const size_t pwords = (size_t)3 * d + m + (m + 31) / 32;
+  if (!c->d_prover || c->prover_words < pwords) {
     if (c->d_prover) { hipStreamSynchronize(c->stream); hipFree(c->d_prover); c->d_prover = nullptr; }
-    HIP_TRY(c, hipMalloc(&c->d_prover, ((size_t)3 * d + m) * 4));
-    c->prover_words = (size_t)3 * d + m;
+    HIP_TRY(c, hipMalloc(&c->d_prover, pwords * 4));
+    c->prover_words = pwords;
   }
   uint32_t *w = c->d_prover, *v = w + d, *h = v + d, *cw = h + d;
+  uint8_t *ubits = (uint8_t *)(cw + m);
   uint64_t *pi_h = d_partial, *pi_hat_h = d_partial + ctl, *pi_hat_v = d_partial + 2 * ctl, *pi_v_w = d_partial + 3 * ctl,
            *pi_b_w = d_partial + 4 * ctl;
   // this rank's contiguous share of each region's rows
@@ -382,8 +515,18 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
     // w(x) = delta t + sum_{bit} v_i   (src/snark.c:141,147-155); every rank needs all of w for the polynomial step
     int r = d_wlanes ? mfh_witness_from_lanes(c, d_ssp, d_wlanes, delta, w) : mfh_witness_poly(c, d_ssp, h_witness_bits, delta, w);
     if (r) return r;
-    // v = w + v_0 ; h = (v^2 - 1) / t   (src/snark.c:161-169)
-    hipLaunchKernelGGL(k_add_slot, g1(d), dim3(256), 0, c->stream, w, src, 1u, d, v);
+    // v = w + v_0 ; h = (v^2 - 1) / t   (src/snark.c:161-169); with public inputs v = w + v_0 + sum_{i <= lu, u_i} v_i
+    if (lu) {
+      const uint32_t ub = (lu + 7) / 8;
+      uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_pub, ub);
+      if (!st) return MFH_ENOMEM;
+      memcpy(st, h_stmt, ub);
+      HIP_TRY(c, hipMemcpyAsync(ubits, st, ub, hipMemcpyHostToDevice, c->stream));
+      pin_release(c, c->pin_pub);
+      hipLaunchKernelGGL(k_add_public<1>, g1(d), dim3(256), 0, c->stream, w, src, d, lu, ubits, ub, 1u, nullptr, v);
+    } else {
+      hipLaunchKernelGGL(k_add_slot, g1(d), dim3(256), 0, c->stream, w, src, 1u, d, v);
+    }
     HIP_TRY(c, hipGetLastError());
     r = mfh_poly_h(c, v, h);
     if (r) return r;
@@ -431,6 +574,15 @@ int mfh_prove_finish(mfh_ctx *c, uint64_t *d_proof, const uint8_t *h_smudge_mag,
   int rc = mfh_ct_smudge(c, d_proof, 4, h_smudge_mag, maglen, h_smudge_sign);
   if (rc) return rc;
   return mfh_ct_smudge(c, d_proof + 3 * ctl, 1, h_smudge_mag + 4 * maglen, maglen, h_smudge_sign + 4);
+}
+
+int mfh_prove_public(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t lu, const uint8_t *h_bits, uint32_t delta,
+                     const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign, uint64_t *d_proof) {
+  if (!c || !h_smudge_mag || !h_smudge_sign) return MFH_EINVAL;
+  if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  int rc = prove_partial_impl(c, d_crs_c8, d_ssp, h_bits, delta, 0, 1, nullptr, d_proof, lu);
+  if (rc) return rc;
+  return mfh_prove_finish(c, d_proof, h_smudge_mag, maglen, h_smudge_sign);
 }
 
 int mfh_prove(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, const uint8_t *h_witness_bits, uint32_t delta,
@@ -604,30 +756,65 @@ int batch_streams(mfh_ctx *c) {
   return MFH_OK;
 }
 
+// Public inputs of a batch call (mfh_prove_batch_public): the witness bits the call is handed have the statement bits cleared already (so the
+// witness GEMM and the b_w launches see the private witness only); the statements travel beside them.
+constexpr uint32_t kPubDirect = 64;  // up to this many public wires the V step reads the rows itself (k_add_public); above, a second witness pass forms their sum
+constexpr int kPubNB = 16;           // statements per k_add_public block
+struct PubBatch {
+  uint32_t lu;
+  const uint8_t *d_ubits;   // device: ub = ceil(lu / 8) statement bytes per statement of the call
+  uint32_t ub;
+  const uint8_t *h_pub;     // lu > kPubDirect: host bit strings (pub_stride bytes apart) holding the statement bits only
+  size_t pub_stride;
+  const uint32_t *h_zero;   // ... and zero deltas for that pass
+  PubBatch at(uint32_t s0) const {  // the same for the statements from s0 on
+    PubBatch p = *this;
+    p.d_ubits += (size_t)s0 * ub;
+    if (h_pub) p.h_pub += (size_t)s0 * pub_stride;
+    if (h_zero) p.h_zero += s0;
+    return p;
+  }
+};
+
 // The chain of sg <= BSG statements on c->stream: W = delta t + sum_bits v_i (src/snark.c:141,147-155), V = W + v_0, H = (V^2 - 1) / t
 // (src/snark.c:161-169); W, H, V are sg x d coefficients each.  The witness pass and the polynomial step have their own scratch (wws,
-// the poly buffers).
+// the poly buffers).  pub: public inputs, V = W + v_0 + sum_{i <= lu, u_i} v_i (pub->at(first statement) already applied).
 int batch_chain_launch(mfh_ctx *c, const mf::SspSrc &src, const uint32_t *d_ssp, uint32_t sg, const uint8_t *h_bits, size_t bits_stride,
-                       const uint32_t *h_delta, uint32_t *W, uint32_t *H, uint32_t *V, hipEvent_t ev_witness = nullptr) {
+                       const uint32_t *h_delta, uint32_t *W, uint32_t *H, uint32_t *V, hipEvent_t ev_witness = nullptr, const PubBatch *pub = nullptr) {
   const uint32_t d = c->P.d;
   int rc = MFH_OK;
   // d % 128 == 0: a GEMM on the matrix cores, one read (dense SSP) or one generation (generator-defined SSP) of the selected rows per
   // 124 statements; otherwise the VALU form, read or generated once per 12 statements
-  if (d % 128 == 0) {
-    // the whole super-group (up to 255 statements) in one read (dense SSP) or one generation (generator-defined SSP) of the rows: k_witness_mm8q / k_witness_mm8q_prg
-    const uint32_t per = c->witness_per ? c->witness_per : 256u;  // (mfh_set_witness_per: A/B knob; a super-group is at most BSG = 255 statements)
-    for (uint32_t b0 = 0; b0 < sg; b0 += per) {
-      rc = mfh_witness_poly_mm(c, d_ssp, std::min(per, sg - b0), h_bits + (size_t)b0 * bits_stride, bits_stride, h_delta + b0, W + (size_t)b0 * d);
-      if (rc) return rc;
+  auto witness_pass = [&](const uint8_t *bits, size_t stride, const uint32_t *delta, uint32_t *out) -> int {
+    if (d % 128 == 0) {
+      // the whole super-group (up to 255 statements) in one read (dense SSP) or one generation (generator-defined SSP) of the rows: k_witness_mm8q / k_witness_mm8q_prg
+      const uint32_t per = c->witness_per ? c->witness_per : 256u;  // (mfh_set_witness_per: A/B knob; a super-group is at most BSG = 255 statements)
+      for (uint32_t b0 = 0; b0 < sg; b0 += per) {
+        int r = mfh_witness_poly_mm(c, d_ssp, std::min(per, sg - b0), bits + (size_t)b0 * stride, stride, delta + b0, out + (size_t)b0 * d);
+        if (r) return r;
+      }
+    } else {
+      for (uint32_t b0 = 0; b0 < sg; b0 += 12) {
+        int r = mfh_witness_poly_multi(c, d_ssp, std::min(12u, sg - b0), bits + (size_t)b0 * stride, stride, delta + b0, out + (size_t)b0 * d);
+        if (r) return r;
+      }
     }
-  } else {
-    for (uint32_t b0 = 0; b0 < sg; b0 += 12) {
-      rc = mfh_witness_poly_multi(c, d_ssp, std::min(12u, sg - b0), h_bits + (size_t)b0 * bits_stride, bits_stride, h_delta + b0, W + (size_t)b0 * d);
-      if (rc) return rc;
-    }
+    return MFH_OK;
+  };
+  rc = witness_pass(h_bits, bits_stride, h_delta, W);
+  if (rc) return rc;
+  // many public wires: their sum by a second pass of the witness GEMM over the statement bits (delta = 0), into H (free until the polynomial step)
+  const bool pub_pass = pub && pub->lu > kPubDirect;
+  if (pub_pass) {
+    rc = witness_pass(pub->h_pub, pub->pub_stride, pub->h_zero, H);
+    if (rc) return rc;
   }
   if (ev_witness) HIP_TRY(c, hipEventRecord(ev_witness, c->stream));  // the HBM-bound part of the chain is over
-  hipLaunchKernelGGL(k_add_slot_multi, dim3((d + 255) / 256, sg), dim3(256), 0, c->stream, W, src, 1u, d, V);
+  if (pub)
+    hipLaunchKernelGGL(k_add_public<kPubNB>, dim3((d + 255) / 256, (sg + kPubNB - 1) / kPubNB), dim3(256), 0, c->stream, W, src, d, pub_pass ? 0u : pub->lu,
+                       pub->d_ubits, pub->ub, sg, pub_pass ? H : nullptr, V);
+  else
+    hipLaunchKernelGGL(k_add_slot_multi, dim3((d + 255) / 256, sg), dim3(256), 0, c->stream, W, src, 1u, d, V);
   HIP_TRY(c, hipGetLastError());
   return mfh_poly_h_multi(c, V, H, sg);  // one set of launches, sg times the work each
 }
@@ -870,13 +1057,10 @@ int batch_transient_image(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nproofs,
   return MFH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mfh_prove_batch(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
-                    size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
-                    uint64_t *d_proofs) {
+// mfh_prove_batch, and with pub != nullptr mfh_prove_batch_public (h_witness_bits then without the statement bits)
+int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
+                     size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
+                     uint64_t *d_proofs, const PubBatch *pub) {
   if (!c) return MFH_EINVAL;
   if (!nproofs) return MFH_OK;
   if (!d_crs_c8 || !h_witness_bits || !h_delta || !h_smudge_mag || !h_smudge_sign || !d_proofs) return MFH_EINVAL;
@@ -926,8 +1110,10 @@ int mfh_prove_batch(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, 
           const size_t ctl0 = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
           for (uint32_t s0 = 0; s0 < nproofs; s0 += (uint32_t)maxsg * SG) {
             const uint32_t cnt = std::min<uint32_t>((uint32_t)maxsg * SG, nproofs - s0);
-            int r = mfh_prove_batch(c, d_crs_c8, d_ssp, cnt, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0,
-                                    h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5, d_proofs + (size_t)s0 * 5 * ctl0);
+            const PubBatch sub = pub ? pub->at(s0) : PubBatch{};
+            int r = prove_batch_impl(c, d_crs_c8, d_ssp, cnt, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0,
+                                     h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5, d_proofs + (size_t)s0 * 5 * ctl0,
+                                     pub ? &sub : nullptr);
             if (r) return r;
           }
           c->last_batch_sg = 0;  // (several sub-calls: no per-super-group completion to hand out; a caller drains after mfh_sync)
@@ -971,7 +1157,9 @@ int mfh_prove_batch(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, 
     uint32_t *WALL, *HALL, *VALL;
     whv_of(sgi, WALL, HALL, VALL);
     OnStream chain(c, chain_stream);
-    int r = batch_chain_launch(c, src, d_ssp, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0, WALL, HALL, VALL, c->ev_wdone[sgi % nbuf]);
+    const PubBatch psg = pub ? pub->at(s0) : PubBatch{};
+    int r = batch_chain_launch(c, src, d_ssp, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0, WALL, HALL, VALL, c->ev_wdone[sgi % nbuf],
+                               pub ? &psg : nullptr);
     if (r) return r;
     HIP_TRY(c, hipEventRecord(c->ev_cdone[sgi % nbuf], chain_stream));
     return MFH_OK;
@@ -1115,6 +1303,62 @@ int mfh_prove_batch(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, 
   c->last_batch_sg = SG;
   c->last_batch_n = nproofs;
   return MFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_prove_batch(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
+                    size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
+                    uint64_t *d_proofs) {
+  return prove_batch_impl(c, d_crs_c8, d_ssp, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs, nullptr);
+}
+
+int mfh_prove_batch_public(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t lu, uint32_t nproofs, const uint8_t *h_bits,
+                           size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
+                           uint64_t *d_proofs) {
+  if (!c) return MFH_EINVAL;
+  if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  if (!lu) return mfh_prove_batch(c, d_crs_c8, d_ssp, nproofs, h_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs);
+  if (!nproofs) return MFH_OK;
+  if (!h_bits) return MFH_EINVAL;
+  const uint32_t m = c->P.m, bstride = (m + 6) / 8, ub = (lu + 7) / 8;
+  if (bits_stride < bstride) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  // the private witness (statement bits cleared): what the witness GEMM and the b_w launches see, staged as mfh_prove_batch stages its bits
+  std::vector<uint8_t> priv((size_t)nproofs * bstride), pubb;
+  std::vector<uint32_t> zero;
+  for (uint32_t b = 0; b < nproofs; b++) {
+    uint8_t *x = priv.data() + (size_t)b * bstride;
+    memcpy(x, h_bits + (size_t)b * bits_stride, bstride);
+    memset(x, 0, lu >> 3);
+    if (lu & 7) x[lu >> 3] &= (uint8_t)(0xffu << (lu & 7));
+  }
+  if (lu > kPubDirect) {  // the statement bits alone, for the second witness pass
+    pubb.assign((size_t)nproofs * bstride, 0);
+    zero.assign(nproofs, 0);
+    for (uint32_t b = 0; b < nproofs; b++) {
+      uint8_t *x = pubb.data() + (size_t)b * bstride;
+      memcpy(x, h_bits + (size_t)b * bits_stride, ub);
+      if (lu & 7) x[ub - 1] &= (uint8_t)((1u << (lu & 7)) - 1);
+    }
+  }
+  // the statements on the device, ub bytes each: queued on the caller's stream ahead of everything the call queues (the chain stream waits for it).  The
+  // previous call's chains have been joined into that stream, so none of them still reads the buffer.
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t need = (size_t)nproofs * ub;
+  if (c->pub_bytes < need) {
+    if (c->d_pub) { hipDeviceSynchronize(); hipFree(c->d_pub); c->d_pub = nullptr; c->pub_bytes = 0; }
+    HIP_TRY(c, hipMalloc(&c->d_pub, need));
+    c->pub_bytes = need;
+  }
+  uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_pub, need);
+  if (!st) return MFH_ENOMEM;
+  for (uint32_t b = 0; b < nproofs; b++) memcpy(st + (size_t)b * ub, h_bits + (size_t)b * bits_stride, ub);
+  HIP_TRY(c, hipMemcpyAsync(c->d_pub, st, need, hipMemcpyHostToDevice, c->stream));
+  pin_release(c, c->pin_pub);
+  const PubBatch pb{lu, c->d_pub, ub, lu > kPubDirect ? pubb.data() : nullptr, bstride, lu > kPubDirect ? zero.data() : nullptr};
+  return prove_batch_impl(c, d_crs_c8, d_ssp, nproofs, priv.data(), bstride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs, &pb);
 }
 
 uint32_t mfh_prove_batch_supergroup(const mfh_ctx *c) { return c ? c->last_batch_sg : 0; }

@@ -139,6 +139,16 @@ void mfuoco_gpu_invalidate(void);
 void mfuoco_prover_batch(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, size_t count);
 /* verifier() for `count` proofs under one SSP and key, on the device: ok[k] = 1 iff pis[k] is accepted (src/snark.c:192-250 per proof) */
 void mfuoco_verifier_batch(ssp_t ssp, vrs_t vrs, proof_t *pis, size_t count, uint8_t *ok);
+/* Public inputs (GAMMA_LU, src/lwe.h:26; the reference fixes l_u = 0, src/snark.c:160): the low lu bits of a random_ssp input are the public statement, the rest the
+ * witness.  Each call makes the OS-entropy draws of its counterpart in the same order (setup / prover / mfuoco_prover_batch / verifier draw nothing).  lu is a property
+ * of the CRS, kept by the caller as the reference keeps GAMMA_LU: a proof made or checked with another lu than the CRS was set up with is in general rejected (accepted
+ * only when the wires on which the two lu disagree are all zero).  lu must be < GAMMA_M.  mfuoco_setup_public: setup() with rows v[0..lu) encrypting 0.  The verifiers
+ * ignore statement bits at lu and above and derive the verification key [t(s), v_0(s) .. v_lu(s)] once per (SSP, s, lu), kept like the CRS image. */
+void mfuoco_setup_public(crs_t crs, vrs_t vrs, ssp_t ssp, uint32_t lu);
+void mfuoco_prover_public(proof_t pi, crs_t crs, ssp_t ssp, mpz_t input, uint32_t lu);
+void mfuoco_prover_batch_public(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *inputs, size_t count, uint32_t lu);
+bool mfuoco_verifier_public(ssp_t ssp, vrs_t vrs, proof_t pi, mpz_t statement, uint32_t lu);
+void mfuoco_verifier_batch_public(ssp_t ssp, vrs_t vrs, proof_t *pis, mpz_t *statements, size_t count, uint32_t lu, uint8_t *ok);
 /* regev_decrypt for `count` ciphertexts under one key (src/lwe.c:105-111 per ciphertext); ms[k] initialised by the caller */
 void mfuoco_decrypt_batch(mpz_t *ms, sk_t sk, ct_t *cts, size_t count);
 /* regev_encrypt + ct_export (src/lwe.c:78-97,115-119; the loops of src/benchmark_lwe.c:28-33 and src/snark.c:75-110) for `count` messages under one key: row k is

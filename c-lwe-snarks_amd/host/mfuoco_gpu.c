@@ -86,6 +86,13 @@ static struct {
   uint64_t staged_digest[2]; /* of the compressed CRS as last staged (mfuoco_gpu_stage_crs) */
   bool staged_digest_valid;
   int last_prover_path;      /* what the last prover() ran on: 0 regenerated keystream, 1 the resident rows (mfuoco_gpu_last_prover_path) */
+  uint64_t ssp_gen;          /* bumped by every upload of an SSP (ssp_resident) */
+  /* the verification key of the _public verifiers [t(s), v_0(s) .. v_lu(s)] (mfh_vk_derive), derived once per (SSP upload, s, lu) like the CRS image is kept */
+  uint32_t *d_vk;
+  size_t vk_cap;
+  bool vk_valid;
+  uint64_t vk_gen, vk_s;
+  uint32_t vk_lu;
 } G = { .device = -1, .resident_crs = -1 };
 
 static void die(const char *what)
@@ -213,6 +220,7 @@ void mfuoco_gpu_invalidate(void)
 {
   KEEP_ERRNO;
   G.ssp_host = NULL;
+  G.vk_valid = false;
   drop_image();
   /* ... and the batch calls' device scratch (720 MB per 1020 proofs), which otherwise stays for the next call */
   if (G.d_out) { (void)hipFree(G.d_out); G.d_out = NULL; G.out_cap = 0; }
@@ -902,6 +910,7 @@ static void ssp_resident(ssp_t ssp)
   CK(mfh_ssp_upload(G.ctx, ssp, G.d_ssp, 0, GAMMA_M + 3));
   CK(mfh_ssp_prepare(G.ctx, G.d_ssp));
   G.ssp_host = ssp;
+  G.ssp_gen++;
 }
 
 /* Everything a first prover() would otherwise pay for besides the proof itself -- the context's scratch (hipMalloc), the code objects of the prover's kernels (loaded
@@ -929,9 +938,9 @@ static void *setup_ssp_thread(void *ssp)
   ssp_resident((uint8_t *)ssp);
   return NULL;
 }
-void setup(crs_t crs, vrs_t vrs, ssp_t ssp)
+/* lu > 0: mfuoco_setup_public -- the same draws in the same order, rows v[0..lu) encrypt 0 (mfh_setup_public) */
+static void setup_impl(crs_t crs, vrs_t vrs, ssp_t ssp, uint32_t lu)
 {
-  KEEP_ERRNO;
   gpu();
   use_seed(crs->seed);
   /* the SSP (5.7 GB at the NDEBUG size) starts crossing PCIe at once, on a helper thread (mfh_ssp_upload has its own staging threads; this one only waits for them), while
@@ -978,7 +987,8 @@ void setup(crs_t crs, vrs_t vrs, ssp_t ssp)
   explicit_bzero(err, rows * L_LIMBS * 8); /* the encryption errors are part of the trapdoor: not left on the heap */
   free(err);
   sk_resident(vrs->sk);
-  CK(mfh_setup(G.ctx, G.d_ssp, (uint32_t)vrs->alpha, (uint32_t)vrs->beta, (uint32_t)vrs->s, G.d_sk, G.d_err, G.d_crs));
+  if (lu) CK(mfh_setup_public(G.ctx, G.d_ssp, (uint32_t)vrs->alpha, (uint32_t)vrs->beta, (uint32_t)vrs->s, lu, G.d_sk, G.d_err, G.d_crs, NULL));
+  else CK(mfh_setup(G.ctx, G.d_ssp, (uint32_t)vrs->alpha, (uint32_t)vrs->beta, (uint32_t)vrs->s, G.d_sk, G.d_err, G.d_crs));
   if (img) { /* the image's b column, behind the a parts (s2) and the encryptions (this stream) */
     HK(hipStreamWaitEvent(NULL, G.ev_img, 0));
     CK(mfh_crs_image_set_b(G.ctx, 0, rows, G.d_crs, img));
@@ -999,6 +1009,21 @@ void setup(crs_t crs, vrs_t vrs, ssp_t ssp)
   if (tracing())
     fprintf(stderr, "setup(): key + error draws %.2f ms (the SSP upload runs beside them), rest of the SSP upload (%.2f GB) + quotient precomputation %.2f, uploads + encryptions + CRS download %.2f (row image for prover(): %s, its a parts expanded beside the SSP upload), digest %.2f, prover warm-up %.2f\n",
             t_drawn - t_in, SSP_SIZE / 1e9, t_ssp - t_drawn, t_crs - t_ssp, img ? "written" : "not kept", t_img - t_crs, tnow() - t_img);
+}
+void setup(crs_t crs, vrs_t vrs, ssp_t ssp)
+{
+  KEEP_ERRNO;
+  setup_impl(crs, vrs, ssp, 0);
+}
+static void check_lu(uint32_t lu, const char *who)
+{
+  if (lu >= GAMMA_M) die(who); /* (the m - 1 wires of the SSP: lu <= M - 1) */
+}
+void mfuoco_setup_public(crs_t crs, vrs_t vrs, ssp_t ssp, uint32_t lu)
+{
+  KEEP_ERRNO;
+  check_lu(lu, "mfuoco_setup_public: lu must be < M");
+  setup_impl(crs, vrs, ssp, lu);
 }
 
 /* ---- pieces shared with the multi-GPU entry points (host/mfuoco_dist.c, libmfuoco_gpu_dist): not part of the reference interface ---- */
@@ -1343,9 +1368,8 @@ void mfuoco_gpu_prefetch_crs(crs_t crs)
 }
 int mfuoco_gpu_last_prover_path(void) { return G.last_prover_path; }
 
-void prover(proof_t pi, crs_t crs, ssp_t ssp, mpz_t witness)
+static void prover_impl(proof_t pi, crs_t crs, ssp_t ssp, mpz_t witness, uint32_t lu)
 {
-  KEEP_ERRNO;
   const double t_in = tnow();
   const uint8_t *d_crs = mfuoco_gpu_stage_crs(crs);
   const uint32_t *d_ssp = mfuoco_gpu_stage_ssp(ssp);
@@ -1357,7 +1381,8 @@ void prover(proof_t pi, crs_t crs, ssp_t ssp, mpz_t witness)
   mfuoco_gpu_prover_entropy(&delta, mag, sign);
   const void *rows = image_resident_rows(d_crs);
   if (rows) CK(mfh_crs_set_resident(G.ctx, rows));
-  int rc = mfh_prove(G.ctx, d_crs, d_ssp, bits, delta, mag, GAMMA_LOG_SMUDGING / 8, sign, G.d_proof);
+  int rc = lu ? mfh_prove_public(G.ctx, d_crs, d_ssp, lu, bits, delta, mag, GAMMA_LOG_SMUDGING / 8, sign, G.d_proof)
+              : mfh_prove(G.ctx, d_crs, d_ssp, bits, delta, mag, GAMMA_LOG_SMUDGING / 8, sign, G.d_proof);
   if (rows) CK(mfh_crs_set_resident(G.ctx, NULL)); /* (mfh_prove_batch must not find the single-proof image) */
   explicit_bzero(mag, sizeof mag);
   explicit_bzero(&delta, sizeof delta);
@@ -1373,13 +1398,24 @@ void prover(proof_t pi, crs_t crs, ssp_t ssp, mpz_t witness)
     fprintf(stderr, "prover(): stage CRS+SSP %.2f ms, image + queue %.2f, GPU %.2f, copy + mpz_t %.2f (%s)\n", t_staged - t_in, t_queued - t_staged, t_done - t_queued, tnow() - t_done,
             rows ? "resident rows" : "regenerated");
 }
+void prover(proof_t pi, crs_t crs, ssp_t ssp, mpz_t witness)
+{
+  KEEP_ERRNO;
+  prover_impl(pi, crs, ssp, witness, 0);
+}
+/* prover() with the low lu bits of `input` (the random_ssp input) as the public statement: the same draws as prover() */
+void mfuoco_prover_public(proof_t pi, crs_t crs, ssp_t ssp, mpz_t input, uint32_t lu)
+{
+  KEEP_ERRNO;
+  check_lu(lu, "mfuoco_prover_public: lu must be < M");
+  prover_impl(pi, crs, ssp, input, lu);
+}
 
 /* prover() for `count` statements under one CRS and SSP (not in the reference): the CRS rows are expanded once per group of proofs
  * and the multiply-accumulate runs on the matrix cores (mfh_prove_batch).  Entropy per proof as in prover(): delta, then 5 x
  * [80-byte magnitude, sign byte].  pis[k] must be initialised (proof_init). */
-void mfuoco_prover_batch(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, size_t count)
+static void prover_batch_impl(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, size_t count, uint32_t lu)
 {
-  KEEP_ERRNO;
   if (!count) return;
   const double t_in = tnow();
   const uint8_t *d_crs = mfuoco_gpu_stage_crs(crs);
@@ -1404,7 +1440,8 @@ void mfuoco_prover_batch(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, s
   if (tracing()) fprintf(stderr, "mfuoco_prover_batch(%zu) host inputs: buffers %.2f ms, witness bits %.2f, entropy %.2f\n", count, t_alloc - t_staged, t_bits - t_alloc, t_host - t_bits);
   image_resident_mm(d_crs, 0, 1, count > 31); /* (smaller calls do not expand an image at all; one kept from an earlier call is used if it still serves this CRS) */
   const double t_image = tnow();
-  int rc = mfh_prove_batch(G.ctx, d_crs, d_ssp, (uint32_t)count, bits, stride, delta, mag, maglen, sign, d_out);
+  int rc = lu ? mfh_prove_batch_public(G.ctx, d_crs, d_ssp, lu, (uint32_t)count, bits, stride, delta, mag, maglen, sign, d_out)
+              : mfh_prove_batch(G.ctx, d_crs, d_ssp, (uint32_t)count, bits, stride, delta, mag, maglen, sign, d_out);
   explicit_bzero(mag, count * 5 * maglen); /* the smudging terms and deltas are the proofs' zero-knowledge: not left on the heap */
   explicit_bzero(sign, count * 5);
   explicit_bzero(delta, count * 4);
@@ -1417,6 +1454,17 @@ void mfuoco_prover_batch(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, s
   if (tracing())
     fprintf(stderr, "mfuoco_prover_batch(%zu): stage CRS+SSP %.2f ms, witness bits + entropy %.2f, image %.2f, queue %.2f, drain (copy + mpz_t under the GPU work) %.2f\n", count,
             t_staged - t_in, t_host - t_staged, t_image - t_host, t_queued - t_image, tnow() - t_queued);
+}
+void mfuoco_prover_batch(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *witnesses, size_t count)
+{
+  KEEP_ERRNO;
+  prover_batch_impl(pis, crs, ssp, witnesses, count, 0);
+}
+void mfuoco_prover_batch_public(proof_t *pis, crs_t crs, ssp_t ssp, mpz_t *inputs, size_t count, uint32_t lu)
+{
+  KEEP_ERRNO;
+  check_lu(lu, "mfuoco_prover_batch_public: lu must be < M");
+  prover_batch_impl(pis, crs, ssp, inputs, count, lu);
 }
 
 static uint64_t horner_modp(const uint8_t *slot, uint64_t x)
@@ -1506,6 +1554,57 @@ void mfuoco_verifier_batch(ssp_t ssp, vrs_t vrs, proof_t *pis, size_t count, uin
   cts_upload(d_proofs, pis, NULL, count * 5);
   CK(mfh_verify(G.ctx, G.d_ssp, (uint32_t)vrs->alpha, (uint32_t)vrs->beta, (uint32_t)vrs->s, G.d_sk, d_proofs, count, d_ok));
   HK(hipMemcpy(ok, d_ok, count, hipMemcpyDeviceToHost));
+}
+
+/* the verification key of (resident SSP, s, lu) on the device: derived on first use, kept until the SSP, s or lu changes */
+static const uint32_t *vk_resident(uint64_t s, uint32_t lu)
+{
+  if (G.vk_valid && G.vk_gen == G.ssp_gen && G.vk_s == s && G.vk_lu == lu) return G.d_vk;
+  if (lu + 2 > G.vk_cap) {
+    if (G.d_vk) HK(hipFree(G.d_vk));
+    G.d_vk = NULL;
+    G.vk_cap = 0;
+    HK(hipMalloc((void **)&G.d_vk, (size_t)(lu + 2) * 4));
+    G.vk_cap = lu + 2;
+  }
+  CK(mfh_vk_derive(G.ctx, G.d_ssp, (uint32_t)s, lu, G.d_vk));
+  G.vk_valid = true;
+  G.vk_gen = G.ssp_gen;
+  G.vk_s = s;
+  G.vk_lu = lu;
+  return G.d_vk;
+}
+/* verifier() of `count` proofs against their statements (the low lu bits of statements[k]; bits lu and above are ignored), on the device from the cached
+ * verification key (mfh_verify_public) */
+void mfuoco_verifier_batch_public(ssp_t ssp, vrs_t vrs, proof_t *pis, mpz_t *statements, size_t count, uint32_t lu, uint8_t *ok)
+{
+  KEEP_ERRNO;
+  check_lu(lu, "mfuoco_verifier_batch_public: lu must be < M");
+  if (!count) return;
+  gpu();
+  ssp_resident(ssp);
+  sk_resident(vrs->sk);
+  const uint32_t *d_vk = vk_resident(vrs->s, lu);
+  const size_t ub = (lu + 7) / 8 ? (lu + 7) / 8 : 1;
+  uint8_t *st = xcalloc(count, ub);
+  for (size_t k = 0; k < count; k++) {
+    if (mpz_sgn(statements[k]) < 0) die("verifier: negative statement");
+    const size_t nl = mpz_size(statements[k]), nb = nl * sizeof(mp_limb_t);
+    memcpy(st + k * ub, mpz_limbs_read(statements[k]), nb < ub ? nb : ub); /* (little-endian bytes, as mfuoco_gpu_witness_bits) */
+  }
+  uint64_t *d_proofs = up_reserve(count * 5);
+  uint8_t *d_ok = (uint8_t *)(d_proofs + G.up_cap * CTL);
+  cts_upload(d_proofs, pis, NULL, count * 5);
+  CK(mfh_verify_public(G.ctx, d_vk, lu, (uint32_t)vrs->alpha, (uint32_t)vrs->beta, G.d_sk, d_proofs, st, ub, count, d_ok));
+  HK(hipMemcpy(ok, d_ok, count, hipMemcpyDeviceToHost));
+  free(st);
+}
+bool mfuoco_verifier_public(ssp_t ssp, vrs_t vrs, proof_t pi, mpz_t statement, uint32_t lu)
+{
+  KEEP_ERRNO;
+  uint8_t ok = 0;
+  mfuoco_verifier_batch_public(ssp, vrs, (proof_t *)pi, (mpz_t *)statement, 1, lu, &ok);
+  return ok != 0;
 }
 
 /* regev_decrypt (src/lwe.c:105-111) for `count` ciphertexts under one key: ms[k] initialised by the caller.  From 4096 ciphertexts the dot products run

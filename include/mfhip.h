@@ -227,6 +227,39 @@ int mfh_prove(mfh_ctx *ctx, const uint8_t *d_crs_c8, const uint32_t *d_ssp, cons
 int mfh_verify(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, const uint64_t *d_sk,
                const uint64_t *d_proofs, size_t count, uint8_t *d_ok);
 
+/* ---- public inputs: proofs bound to a statement of lu public wires ----------------------------------------------------------------
+ * The reference defines GAMMA_LU 10 (src/lwe.h:26) but fixes l_u = 0 ("Assume l_u = 0 . So v(x) = v_0(x) + w(x)", src/snark.c:160): its proofs carry no
+ * statement.  Here, with 0 <= lu <= m - 1, the m - 1 input bits of a statement are split: bits [0, lu) are the statement u (public), bits [lu, m - 1) the
+ * private witness.  lu is a property of the CRS: a proof made or checked with another lu than the CRS was set up with is in general rejected (accepted
+ * only when the wires on which the two lu disagree are all zero).  lu = 0 gives exactly the bytes of mfh_setup_image / mfh_prove / mfh_prove_batch /
+ * mfh_verify; lu >= m is MFH_EINVAL.  The row-sharded provers (mfh_prove_partial*, mfh_prove_batch_partial, mfh_batch_chain*) stay at lu = 0.
+ *
+ * mfh_setup_public: setup() (src/snark.c:100-108) with the messages of rows v[0..lu) zeroed -- they encrypt 0 instead of beta v_i(s), at the same stream
+ * rows with the same errors; the layout is that of mfh_setup.  Required for soundness: with Enc(beta v_i(s)) of a public wire in the CRS a prover could move
+ * (u - u') v_i into w and prove a false statement u'.  d_rows_image may be NULL; otherwise it receives the expanded rows as mfh_setup_image writes them. */
+int mfh_setup_public(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, uint32_t lu, const uint64_t *d_sk,
+                     const uint64_t *d_err, uint8_t *d_crs_c8, void *d_rows_image);
+/* prover() (src/snark.c:141-174) with a statement: h_bits as for mfh_prove (m - 1 bits, bits [0, lu) the statement):
+ *   w_priv = delta t + sum_{i > lu, bit} v_i,  v = v_0 + sum_{i <= lu, u_i} v_i + w_priv,  b_w = delta ct_t + sum_{i > lu, bit} ct_{v_i},
+ *   v_w = eval(S, w_priv), hat_v = eval(AS, v), h = (v^2 - 1) / t, hat_h, and the smudging of mfh_prove (src/snark.c:185-189).
+ * Equivalently: h, hat_h, hat_v are those of mfh_prove(bits); v_w, b_w those of mfh_prove(bits with [0, lu) cleared) (same delta and smudging). */
+int mfh_prove_public(mfh_ctx *ctx, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t lu, const uint8_t *h_bits, uint32_t delta,
+                     const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign, uint64_t *d_proof);
+/* mfh_prove_batch with a statement per proof (same layout, regimes and queue-only behaviour; proof b is bit-identical to mfh_prove_public of statement b).
+ * The witness GEMM and the b_w launches receive the bits with the statement cleared; the statements (ceil(lu / 8) bytes each) are staged beside them and the
+ * V = W + v_0 step adds the selected public rows (up to 64 public wires read once per 16 statements through L2; more by a second witness pass with delta 0). */
+int mfh_prove_batch_public(mfh_ctx *ctx, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t lu, uint32_t nproofs, const uint8_t *h_bits,
+                           size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
+                           uint64_t *d_proofs);
+/* The verification key: d_vk = [t(s), v_0(s), v_1(s) .. v_lu(s)] mod p, lu + 2 uint32 (the Horner values of src/snark.c:201,213 and of the public wires).
+ * With alpha, beta and sk it is all the verifier needs: no SSP on the device. */
+int mfh_vk_derive(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t s, uint32_t lu, uint32_t *d_vk);
+/* verifier() (src/snark.c:192-250) with statements: the 5 count decryptions of mfh_verify, then its four checks with
+ * v_s = v_0(s) + sum_{i <= lu, u_i} u_i v_i(s) + w_s mod p (src/snark.c:213-217).  Proof i's statement: h_statements + i * stmt_stride (stmt_stride >=
+ * ceil(lu / 8); bits lu and above are ignored).  d_ok[i] = 1 iff proof i is accepted. */
+int mfh_verify_public(mfh_ctx *ctx, const uint32_t *d_vk, uint32_t lu, uint32_t alpha, uint32_t beta, const uint64_t *d_sk, const uint64_t *d_proofs,
+                      const uint8_t *h_statements, size_t stmt_stride, size_t count, uint8_t *d_ok);
+
 /* The CRS expanded ONCE for the matrix-core path (the resident regime of the batch prover): mfh_crs_expand_mm writes the S, AS and
  * BT+BV regions in MFMA A-fragment order (mfh_crs_mm_image_bytes bytes: 11.3 GB at the default instance); while an image is
  * registered with mfh_crs_set_resident_mm (NULL clears it), mfh_eval_rows_multi over exactly one of those regions -- hence
