@@ -1034,7 +1034,7 @@ __device__ __forceinline__ void evalmm_finish_body(const int *__restrict__ part,
         }
         uint64_t t = 0;
 #pragma unroll
-        for (int w = 0; w < ND; w++) t += (uint64_t)(g[w] + 128 * sa + corr[w]) << (8 * w);  // each term is a true byte-product sum: >= 0, < 2^31
+        for (int w = 0; w < ND; w++) t += (uint64_t)(g[w] + 128 * sa + corr[w]) << (8 * w);  // each term is a true byte-product sum over all rows: 0 <= term <= 65025 nrows; t holds four of them shifted by up to 24 bits, which stays below 2^64 only while nrows < 2^64 / (65025 * 0x01010101), about 2^24 (16.9 M) rows
         val += (unsigned __int128)t << (8 * k);
       }
       sv[l][0][vl] = (uint32_t)val;

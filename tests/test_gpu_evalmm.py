@@ -302,7 +302,11 @@ def test_expansion_kernels_write_the_same_image(gpu_ctx_factory, logq, d, m):
 def test_row_chunks_stay_within_the_int32_bound(ctx, nrows, chunk_rows, nvec, cb):
     """a chunk of <= 131 071 rows rounded UP to whole 256-row stages could reach 131 072 (nrows = 2 x 131 071: two chunks of
     131 072).  The limit is now rounded DOWN to whole stages before dividing (three chunks here; 500 -> chunks of 256); both the
-    128-column (3 vectors) and the 256-column kernel (40 vectors), compared with the VALU path (k_eval) over the same rows."""
+    128-column (3 vectors) and the 256-column kernel (40 vectors), compared with the VALU path (k_eval) over the same rows.
+    These are AES rows, so the accumulators stay about 2^9 below the int32 limit and this test alone would not notice the chunk of
+    131 072 rows again.  test_gpu_operand_bounds.py::test_streaming_path_on_a_constant_image does: its constant image holds every
+    accumulator at exactly 2^30 under correct chunking, where that regression would put one at exactly 2^31 (and one region of 130 816
+    rows takes a single chunk to 2^31 - 2^22)."""
     p = ctx.params
     rng = np.random.default_rng(nrows + nvec)
     c8 = ctx.to_device(rng.integers(0, 256, size=nrows * p.ctb, dtype=np.uint8))
