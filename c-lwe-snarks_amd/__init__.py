@@ -98,6 +98,7 @@ EXPORTS = [
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
+    "mfh_ssp_from_rows",
 ]
 
 
@@ -212,6 +213,7 @@ def load_library():
         "mfh_prove_batch_public": (i32, [vp, vp, vp, u32, u32, ctypes.c_char_p, sz, vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp]),
         "mfh_vk_derive": (i32, [vp, vp, u32, u32, vp]),
         "mfh_verify_public": (i32, [vp, vp, u32, u32, u32, vp, vp, ctypes.c_char_p, sz, sz, vp]),
+        "mfh_ssp_from_rows": (i32, [vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -219,6 +221,24 @@ def load_library():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def rows_to_csr(rows):
+    """(row_ptr, wire, coef) as contiguous uint32 arrays, from a CSR triple or from a sequence of rows of (wire, coef) pairs (coefficients taken mod p)"""
+    if isinstance(rows, tuple) and len(rows) == 3 and all(isinstance(a, np.ndarray) for a in rows):
+        row_ptr, wire, coef = rows
+    else:
+        lens = [len(r) for r in rows]
+        row_ptr = np.zeros(len(lens) + 1, dtype=np.int64)
+        np.cumsum(lens, out=row_ptr[1:])
+        flat = [(int(w), int(a) % P) for r in rows for (w, a) in r]
+        wire = np.array([w for w, _ in flat], dtype=np.int64)
+        coef = np.array([a for _, a in flat], dtype=np.int64)
+    if len(row_ptr) == 0 or min(np.min(row_ptr), np.min(wire, initial=0), np.min(coef, initial=0)) < 0:
+        raise MfhError("rows: row_ptr needs nrows + 1 entries, and no entry may be negative")
+    if max(np.max(row_ptr), np.max(wire, initial=0), np.max(coef, initial=0)) > 0xFFFFFFFF:
+        raise MfhError("rows: entries must fit 32 bits")
+    return tuple(np.ascontiguousarray(a, dtype=np.uint32) for a in (row_ptr, wire, coef))
 
 
 def _ptr(t):
@@ -455,6 +475,22 @@ class Context:
         a = np.ascontiguousarray(ssp_host_u64)
         self._chk(self.lib.mfh_ssp_upload(self._h, ctypes.c_void_p(a.ctypes.data), _ptr(d_ssp), first_slot, nslots))
         return d_ssp
+
+    def ssp_from_rows(self, rows, d_ssp=None):
+        """the SSP of a constraint system given row by row (mfh_ssp_from_rows): rows = (row_ptr, wire, coef) arrays in CSR form, or a sequence of rows
+        each a sequence of (wire, coef) pairs; row j asks v_0(r_j) + sum_i a_i v_i(r_j) in {-1, +1} at r_j = j + 2.  Returns the device SSP (written in full)."""
+        p = self.params
+        row_ptr, wire, coef = rows_to_csr(rows)
+        if d_ssp is None:
+            d_ssp = self.empty((p.m + 3) * p.d * 4)
+        self._chk(self.lib.mfh_ssp_from_rows(self._h, len(row_ptr) - 1, ctypes.c_void_p(row_ptr.ctypes.data), ctypes.c_void_p(wire.ctypes.data),
+                                             ctypes.c_void_p(coef.ctypes.data), _ptr(d_ssp)))
+        return d_ssp
+
+    def ssp_to_host_u64(self, d_ssp):
+        """the device SSP in the reference's host layout: (m + 3) * d uint64 (files.ssp_write, the oracle, the shim's setup())"""
+        p = self.params
+        return self.to_host(d_ssp[: (p.m + 3) * p.d * 4], np.uint32).astype(np.uint64)
 
     def witness_poly(self, d_ssp, witness_bits: bytes, delta):
         out = self.empty(self.params.d * 4)

@@ -22,6 +22,7 @@
   } while (0)
 
 struct PolyState;
+struct SspInterp;
 
 // pinned host staging buffer whose previous async copy is awaited only when the buffer is reused
 struct PinBuf {
@@ -93,7 +94,8 @@ struct mfh_ctx {
   size_t mm_base[3] = {0, 0, 0};
   void *ssp_frag = nullptr;  // the dense SSP in MFMA B-fragment order (evalmm.hip: witness pass of the batch prover); built lazily
   size_t ssp_frag_bytes = 0;
-  const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload reset it
+  const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
+  SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): t, its seed table and the Lagrange weights, built on first use
   void *d_batch = nullptr;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
   size_t batch_bytes = 0;
   // mfh_prove_batch, more than one group of proofs and no image registered: the CRS is expanded ONCE PER CALL into this scratch in
@@ -210,6 +212,7 @@ inline int ssp_src(mfh_ctx *c, const uint32_t *d_ssp, mf::SspSrc &src) {
 }
 
 void mfh_poly_destroy(mfh_ctx *c);
+void ssp_interp_free(mfh_ctx *c);
 extern "C" int mfh_witness_poly_mm(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                                    uint32_t *d_w);
 extern "C" int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,

@@ -1114,6 +1114,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   mfh_poly_destroy(c);
+  ssp_interp_free(c);
   upload_free(c);
   if (c->sample_tmp) hipFree(c->sample_tmp);
   if (c->ev_sample) hipEventDestroy(c->ev_sample);
@@ -1265,6 +1266,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "mmstream_rounds")) return 10;  // the streaming launches that serve several groups (a subset of "evalmm_resident")
   if (!strcmp(which, "mmstream_rounds_persistent")) return 110;  // ... those of them that ran the persistent one-workgroup-per-CU grid (k_mmstream_p / k_mmstream_w)
   if (!strcmp(which, "mmstream_bw_persistent")) return 114;      // ... and of "mmstream_bw" (k_mmstream_pb)
+  if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
   return -1;
 }
 

@@ -168,6 +168,19 @@ int mfh_ssp_set_prg(mfh_ctx *ctx, uint64_t seed, const uint32_t *d_t);
 int mfh_ssp_prg_make_t(mfh_ctx *ctx, uint64_t seed, const uint8_t *h_witness_bits, uint32_t *d_t);
 int mfh_ssp_prg_fill(mfh_ctx *ctx, uint64_t seed, size_t first_slot, size_t nslots, uint32_t *d_out);
 
+/* A constraint system given row by row, written as the device SSP (the layout above) by interpolation on the device.
+ * Points: r_j = j + 2, j = 0 .. d - 2 (d - 1 of them).  Row j < nrows asks  v_0(r_j) + sum_i a_i v_i(r_j)  in {-1, +1}, where its entries
+ * (h_wire[e], h_coef[e]), e in [h_row_ptr[j], h_row_ptr[j + 1]), give the values v_i(r_j) = coef (wire 0 = the constant v_0; entries of one row with the same
+ * wire add; a wire absent from a row is 0 there).  Padding rows j >= nrows have v_0(r_j) = 1 and no wire: every input satisfies them.
+ * Written: slot 0 = t(x) = prod_j (x - r_j) (monic, degree d - 1; no root at +-1, so a satisfying batch takes the exact-division path of mfh_poly_h_multi),
+ * slot i + 1 = v_i, the interpolant of degree < d - 1 of its column (i = 0 .. m - 1), slots m + 1 and m + 2 = 0.
+ * Bits: input (witness) bit i - 1 is wire i (mfh_witness_poly); with public inputs, bits [0, lu) -- wires 1 .. lu -- are the statement.
+ * h_row_ptr: nrows + 1 entries (only [h_row_ptr[0], h_row_ptr[nrows]) of h_wire / h_coef is read); wires in [0, m), coefficients in [0, p).
+ * MFH_EINVAL, with nothing written, for nrows > d - 1, a wire >= m, a coefficient >= p or a decreasing h_row_ptr.  d_ssp is written in full, derived images
+ * of an earlier SSP are dropped as by mfh_ssp_upload; call mfh_ssp_prepare afterwards.  The first call of a context builds t and a table of
+ * (d - 1) * ceil(d / 32) words (134 MB at d = 2^15) that it keeps; the call synchronises the context's stream. */
+int mfh_ssp_from_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t *d_ssp);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
@@ -422,7 +435,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two
