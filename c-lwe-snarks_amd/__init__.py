@@ -98,7 +98,7 @@ EXPORTS = [
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
-    "mfh_ssp_from_rows",
+    "mfh_ssp_from_rows", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
 ]
 
 
@@ -214,6 +214,9 @@ def load_library():
         "mfh_vk_derive": (i32, [vp, vp, u32, u32, vp]),
         "mfh_verify_public": (i32, [vp, vp, u32, u32, u32, vp, vp, ctypes.c_char_p, sz, sz, vp]),
         "mfh_ssp_from_rows": (i32, [vp, u32, vp, vp, vp, vp]),
+        "mfh_circuit_create": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
+        "mfh_circuit_destroy": (None, [vp]),
+        "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -243,6 +246,24 @@ def rows_to_csr(rows):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+class CircuitProgram:
+    """a compiled circuit's gate program on the device (mfh_circuit): made by Context.circuit_load, used by Context.circuit_assign"""
+
+    def __init__(self, ctx, nin, ngates, handle):
+        self._ctx, self.nin, self.ngates, self._h = ctx, nin, ngates, handle
+
+    def close(self):
+        if self._h:
+            self._ctx.lib.mfh_circuit_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -486,6 +507,32 @@ class Context:
         self._chk(self.lib.mfh_ssp_from_rows(self._h, len(row_ptr) - 1, ctypes.c_void_p(row_ptr.ctypes.data), ctypes.c_void_p(wire.ctypes.data),
                                              ctypes.c_void_p(coef.ctypes.data), _ptr(d_ssp)))
         return d_ssp
+
+    def circuit_load(self, compiled):
+        """the gate program of circuit.Compiled on the device (mfh_circuit_create): levelised and uploaded once; close() frees it"""
+        gates = np.ascontiguousarray(compiled.gates, dtype=np.uint32).reshape(-1, 3)
+        asserts = np.ascontiguousarray(compiled.asserts, dtype=np.uint32).reshape(-1, 2)
+        nin = compiled.nwires - len(gates)
+        h = ctypes.c_void_p()
+        self._chk(self.lib.mfh_circuit_create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data),
+                                              ctypes.byref(h)))
+        return CircuitProgram(self, nin, len(gates), h)
+
+    def circuit_assign(self, prog, bits):
+        """witnesses of nb statements on the device (mfh_circuit_assign): bits = uint8 [nb, nin] of 0 / 1, public bits then private bits.
+        Returns (witness, holds): witness uint8 [nb, (m + 7) // 8], row b = Circuit.assign of statement b (prove_batch takes it as it is);
+        holds bool [nb] = Circuit.holds"""
+        bits = np.asarray(bits, dtype=np.uint8)
+        if bits.ndim != 2 or bits.shape[1] != prog.nin:
+            raise MfhError(f"circuit_assign: bits must be [nb, {prog.nin}] (public then private bits), got {bits.shape}")
+        nb = bits.shape[0]
+        packed = np.ascontiguousarray(np.packbits(bits & 1, axis=1, bitorder="little"))
+        stride = (self.params.m + 7) // 8
+        witness = np.zeros((nb, stride), dtype=np.uint8)
+        holds = np.zeros(nb, dtype=np.uint8)
+        self._chk(self.lib.mfh_circuit_assign(self._h, prog._h, nb, ctypes.c_void_p(packed.ctypes.data), packed.shape[1], ctypes.c_void_p(witness.ctypes.data),
+                                              stride, ctypes.c_void_p(holds.ctypes.data)))
+        return witness, holds.astype(bool)
 
     def ssp_to_host_u64(self, d_ssp):
         """the device SSP in the reference's host layout: (m + 3) * d uint64 (files.ssp_write, the oracle, the shim's setup())"""

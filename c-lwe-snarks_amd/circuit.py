@@ -18,15 +18,20 @@ Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py c
     cc = c.compile(mf.DEFAULT)                         # rows, lu, wire map
     d_ssp = ctx.ssp_from_rows(cc.rows)
     witness = c.assign(public_bits, private_bits)      # (m + 7) // 8 bytes for Context.prove / prove_batch
+    prog = ctx.circuit_load(cc)                        # ... or a whole batch on the device:
+    witness, holds = ctx.circuit_assign(prog, bits)    # bits [nb, nin] = public then private bits; witness [nb, (m + 7) // 8]
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
 P = 0xFFFFFFFB  # GAMMA_P
 _M1 = P - 1  # -1 mod p
+# gate ops of Compiled.gates: MFH_GATE_* of include/mfhip.h (mfh_circuit_create)
+GATE_XOR, GATE_AND, GATE_OR, GATE_NOT = 0, 1, 2, 3
+_OPS = {"xor": GATE_XOR, "and": GATE_AND, "or": GATE_OR, "not": GATE_NOT}
 
 
 class CircuitError(ValueError):
@@ -47,6 +52,10 @@ class Compiled:
     wires: tuple     # wires[node]: the SSP wire of each node (Wire.node)
     nrows: int
     nwires: int      # wires 1 .. nwires are used
+    # the gate program of Context.circuit_load (mfh_circuit_create), in SSP wire numbering: gate g = (op, a, b) writes wire nin + 1 + g (nin = nwires -
+    # len(gates)), operands in [1, nin + g], b = a for NOT; asserts[e] = (wire, value)
+    gates: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), dtype=np.uint32), compare=False)
+    asserts: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
 
     def wire(self, w: Wire) -> int:
         return self.wires[w.node]
@@ -151,8 +160,10 @@ class Circuit:
         np.cumsum([len(r) for r in rows], out=row_ptr[1:])
         wire = np.array([w for r in rows for w, _ in r], dtype=np.uint32)
         coef = np.array([x for r in rows for _, x in r], dtype=np.uint32)
+        gates = np.array([(_OPS[n[0]], wires[n[1]], wires[n[-1]]) for n in self._nodes if n[0] not in ("pub", "priv")], dtype=np.uint32).reshape(-1, 3)
+        asserts = np.array([(wires[node], value) for node, value in self._asserts], dtype=np.uint32).reshape(-1, 2)
         self._params = params
-        return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw)
+        return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw, gates=gates, asserts=asserts)
 
     # -- assignments ------------------------------------------------------------------------------------------------------
     def evaluate(self, public_bits, private_bits):

@@ -1,0 +1,229 @@
+// circuit_eval.hip -- mfh_circuit_create / mfh_circuit_assign: the witnesses of a Boolean circuit for a batch of statements, bitsliced on the device.
+//
+// One workgroup serves a block of 32 statements.  It keeps one uint32 word per wire in LDS, bit j = statement j of the block, so a gate is one word
+// operation (^ & | ~) for all 32 statements.  The gates are sorted by level on the host (inputs level 0, a gate one more than its highest operand); the
+// workgroup's threads evaluate one level at a time, with a barrier between levels, all levels in one launch (a ripple-carry chain has depth ~ ngates).
+// Both transposes go through wave ballots:
+//   in:  lanes 0..31 hold 32 input bits of statements 0..31, lanes 32..63 the next 32 bits: ballot t gives wire words of input bits t and t + 32;
+//   out: lane l holds the word of wire 64 q + 1 + l: ballot((word >> j) & 1) is bits [64 q, 64 q + 64) of statement j's witness -- 8 output bytes.
+// Assertions fold into one holds word per workgroup.
+#include <algorithm>
+#include <vector>
+
+#include "ctx.hpp"
+
+namespace {
+
+constexpr uint32_t CWG = 512;        // threads per workgroup (8 waves)
+constexpr uint32_t CSTMT = 32;       // statements per workgroup (bits of a wire word)
+constexpr uint32_t CCHUNK = 8192;    // statements per launch (256 workgroups); longer calls run several chunks
+constexpr uint32_t CWORDS = MFH_CIRCUIT_MAX_WIRES + 1;  // LDS wire words: wire 0 (unused) .. MFH_CIRCUIT_MAX_WIRES
+
+// gates[g] = {a | b << 16, out | op << 16}, sorted by level; level L is gates [lp[L], lp[L + 1]).  asserts[e] = {wire, value}.
+__global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
+                                                      const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
+                                                      const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt, uint8_t *__restrict__ out,
+                                                      size_t bits_stride, uint8_t *__restrict__ holds) {
+  __shared__ uint32_t st[CWORDS];
+  __shared__ uint32_t hw;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
+  const uint32_t s0 = blockIdx.x * CSTMT, j = lane & 31;
+  const bool live = s0 + j < nstmt;  // the tail block: statements past nstmt read zeros and write nothing
+  if (tid == 0) hw = ~0u;
+
+  // ---- inputs: statement rows -> wire words (wire k + 1 = input bit k)
+  const uint8_t *row = in + (size_t)(live ? s0 + j : 0) * in_stride;
+  for (uint32_t it = wave; it * 64 < nin; it += nwaves) {  // (wave-uniform trip count: every lane takes part in the ballots)
+    const uint32_t wd = 2 * it + (lane >> 5);
+    uint32_t word = 0;
+    if (live)
+      for (uint32_t u = 0; u < 4; u++) {
+        const size_t byte = (size_t)wd * 4 + u;
+        if (byte < in_stride) word |= (uint32_t)row[byte] << (8 * u);
+      }
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 32; t++) {
+      const uint64_t bm = __ballot((word >> t) & 1);
+      if (j == t) mine = lane < 32 ? (uint32_t)bm : (uint32_t)(bm >> 32);
+    }
+    const uint32_t k = wd * 32 + j;
+    if (k < nin) st[k + 1] = mine;
+  }
+  __syncthreads();
+
+  // ---- gates, level by level
+  uint32_t g1 = nlev ? lp[0] : 0;
+  for (uint32_t lv = 0; lv < nlev; lv++) {
+    const uint32_t g0 = g1;
+    g1 = lp[lv + 1];
+    for (uint32_t g = g0 + tid; g < g1; g += CWG) {
+      const uint2 r = gates[g];
+      const uint32_t x = st[r.x & 0xffff], y = st[r.x >> 16], op = r.y >> 16;
+      st[r.y & 0xffff] = op == MFH_GATE_XOR ? x ^ y : op == MFH_GATE_AND ? x & y : op == MFH_GATE_OR ? x | y : ~x;
+    }
+    __syncthreads();
+  }
+
+  // ---- assertions
+  uint32_t ok = ~0u;
+  for (uint32_t e = tid; e < nasserts; e += CWG) {
+    const uint2 a = asserts[e];
+    ok &= a.y ? st[a.x] : ~st[a.x];
+  }
+  if (ok != ~0u) atomicAnd(&hw, ok);
+
+  // ---- outputs: wire words -> statement rows, 8 bytes per statement and group of 64 wires; bytes [0, bits_stride) all written
+  const uint32_t nq = (uint32_t)((bits_stride + 7) / 8);
+  for (uint32_t q = wave; q < nq; q += nwaves) {
+    const uint32_t i = q * 64 + 1 + lane;
+    const uint32_t word = i <= nw ? st[i] : 0;
+    uint64_t mine = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 32; t++) {
+      const uint64_t bm = __ballot((word >> t) & 1);
+      if (lane == t) mine = bm;
+    }
+    if (lane < 32 && live) {
+      uint8_t *dst = out + (size_t)(s0 + lane) * bits_stride + (size_t)q * 8;
+      const size_t left = bits_stride - (size_t)q * 8;
+      if (left >= 8 && ((uintptr_t)dst & 7) == 0) {
+        *reinterpret_cast<uint64_t *>(dst) = mine;
+      } else {
+        for (uint32_t u = 0; u < 8 && u < left; u++) dst[u] = (uint8_t)(mine >> (8 * u));
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < CSTMT && s0 + tid < nstmt && holds) holds[s0 + tid] = (hw >> tid) & 1;
+}
+
+}  // namespace
+
+struct mfh_circuit {
+  int device = 0;
+  uint32_t nin = 0, ngates = 0, nasserts = 0, nlev = 0;
+  void *mem = nullptr;  // gates (uint2, by level) | asserts (uint2) | level_ptr (nlev + 1 words)
+  const uint2 *gates = nullptr, *asserts = nullptr;
+  const uint32_t *lp = nullptr;
+};
+
+extern "C" {
+
+int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                       mfh_circuit **out) {
+  if (!ctx || !out) return MFH_EINVAL;
+  *out = nullptr;
+  if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = "mfh_circuit_create: gates / assertions without their array"; return MFH_EINVAL; }
+  const uint64_t nw = (uint64_t)nin + ngates;
+  if (nw > ctx->P.m - 1) { ctx->err = "mfh_circuit_create: nin + ngates > m - 1"; return MFH_EINVAL; }
+  if (nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = "mfh_circuit_create: nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
+  std::vector<uint32_t> lvl(nw + 1, 0);
+  uint32_t nlev = 0;
+  for (uint32_t g = 0; g < ngates; g++) {
+    const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = h_gates[3 * g + 2], o = nin + 1 + g;
+    if (op > MFH_GATE_NOT) { ctx->err = "mfh_circuit_create: unknown gate op"; return MFH_EINVAL; }
+    if (a == 0 || a >= o || b == 0 || b >= o) { ctx->err = "mfh_circuit_create: a gate operand is 0 or not below the gate's output wire"; return MFH_EINVAL; }
+    lvl[o] = 1 + std::max(lvl[a], op == MFH_GATE_NOT ? lvl[a] : lvl[b]);
+    nlev = std::max(nlev, lvl[o]);
+  }
+  for (uint32_t e = 0; e < nasserts; e++) {
+    const uint32_t w = h_asserts[2 * e], v = h_asserts[2 * e + 1];
+    if (w == 0 || w > nw) { ctx->err = "mfh_circuit_create: an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
+    if (v > 1) { ctx->err = "mfh_circuit_create: an assertion value other than 0 / 1"; return MFH_EINVAL; }
+  }
+  // counting sort by level (stable: creation order within a level)
+  std::vector<uint32_t> lp(nlev + 1, 0);
+  for (uint32_t g = 0; g < ngates; g++) lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
+  for (uint32_t L = 0, acc = 0; L <= nlev; L++) { const uint32_t n = L < nlev ? lp[L + 1] : 0; lp[L] = acc; acc += n; }  // ... then lp[L] = first gate of level L + 1
+  std::vector<uint32_t> host((size_t)2 * ngates + 2 * nasserts + nlev + 1);
+  {
+    std::vector<uint32_t> pos(lp.begin(), lp.end());
+    for (uint32_t g = 0; g < ngates; g++) {
+      const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = op == MFH_GATE_NOT ? a : h_gates[3 * g + 2], o = nin + 1 + g;
+      const uint32_t q = pos[lvl[o] - 1]++;
+      host[2 * q] = a | b << 16;
+      host[2 * q + 1] = o | op << 16;
+    }
+    std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + 2 * ngates);
+    std::copy(lp.begin(), lp.end(), host.begin() + 2 * ngates + 2 * nasserts);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  mfh_circuit *c = new mfh_circuit();
+  c->device = ctx->device;
+  c->nin = nin;
+  c->ngates = ngates;
+  c->nasserts = nasserts;
+  c->nlev = nlev;
+  if (hipMalloc(&c->mem, host.size() * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    delete c;
+    ctx->err = "mfh_circuit_create: no memory for the gate program";
+    return MFH_ENOMEM;
+  }
+  if (hipMemcpy(c->mem, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(c->mem);
+    delete c;
+    ctx->err = "mfh_circuit_create: upload failed";
+    return MFH_EDEVICE;
+  }
+  c->gates = (const uint2 *)c->mem;
+  c->asserts = c->gates + ngates;
+  c->lp = (const uint32_t *)(c->asserts + nasserts);
+  *out = c;
+  return MFH_OK;
+}
+
+void mfh_circuit_destroy(mfh_circuit *c) {
+  if (!c) return;
+  hipSetDevice(c->device);
+  if (c->mem) hipFree(c->mem);
+  delete c;
+}
+
+int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const uint8_t *h_inputs, size_t in_stride, uint8_t *h_witness_bits,
+                       size_t bits_stride, uint8_t *h_holds) {
+  if (!ctx || !c) return MFH_EINVAL;
+  if (c->device != ctx->device) { ctx->err = "mfh_circuit_assign: the circuit belongs to another device"; return MFH_EINVAL; }
+  const uint64_t nw = (uint64_t)c->nin + c->ngates;
+  if (in_stride * 8 < c->nin) { ctx->err = "mfh_circuit_assign: in_stride * 8 < nin"; return MFH_EINVAL; }
+  if (bits_stride * 8 < nw) { ctx->err = "mfh_circuit_assign: bits_stride * 8 < nin + ngates"; return MFH_EINVAL; }
+  if (!nstmt) return MFH_OK;
+  if ((in_stride && !h_inputs) || (bits_stride && !h_witness_bits)) { ctx->err = "mfh_circuit_assign: null row buffer"; return MFH_EINVAL; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t ch = std::min(nstmt, CCHUNK);
+  const size_t in_b = (size_t)ch * in_stride, out_b = (size_t)ch * bits_stride, io_b = in_b + out_b + ch;
+  if (int rc = buf_reserve(ctx, ctx->circ_io, ctx->circ_io_bytes, io_b)) return rc;
+  uint8_t *pin_in = in_b ? (uint8_t *)pin_acquire(ctx, ctx->pin_rows, in_b) : nullptr;
+  uint8_t *pin_out = (uint8_t *)pin_acquire(ctx, ctx->pin_cw, out_b + ch);
+  if ((in_b && !pin_in) || !pin_out) return MFH_ENOMEM;
+  uint8_t *d_in = (uint8_t *)ctx->circ_io, *d_out = d_in + in_b, *d_holds = d_out + out_b;
+  int rc = MFH_OK;
+  for (uint32_t b0 = 0; b0 < nstmt && rc == MFH_OK; b0 += ch) {
+    const uint32_t n = std::min(ch, nstmt - b0);
+    if (in_b) {
+      memcpy(pin_in, h_inputs + (size_t)b0 * in_stride, (size_t)n * in_stride);
+      if (hipMemcpyAsync(d_in, pin_in, (size_t)n * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
+    }
+    {
+      Timer tm(ctx, 16, n);
+      hipLaunchKernelGGL(k_circuit_eval, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds);
+    }
+    if (hipGetLastError() != hipSuccess) { rc = MFH_EDEVICE; break; }
+    if (hipMemcpyAsync(pin_out, d_out, (size_t)n * bits_stride, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(pin_out + out_b, d_holds, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
+    if (bits_stride) memcpy(h_witness_bits + (size_t)b0 * bits_stride, pin_out, (size_t)n * bits_stride);
+    if (h_holds) memcpy(h_holds + b0, pin_out + out_b, n);
+  }
+  if (in_b) pin_release(ctx, ctx->pin_rows);
+  pin_release(ctx, ctx->pin_cw);
+  if (rc != MFH_OK) {
+    (void)hipGetLastError();
+    ctx->err = "mfh_circuit_assign: launch or copy failed";
+  }
+  return rc;
+}
+
+}  // extern "C"

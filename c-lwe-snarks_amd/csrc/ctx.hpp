@@ -96,6 +96,8 @@ struct mfh_ctx {
   size_t ssp_frag_bytes = 0;
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): t, its seed table and the Lagrange weights, built on first use
+  void *circ_io = nullptr;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
+  size_t circ_io_bytes = 0;
   void *d_batch = nullptr;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
   size_t batch_bytes = 0;
   // mfh_prove_batch, more than one group of proofs and no image registered: the CRS is expanded ONCE PER CALL into this scratch in

@@ -1147,6 +1147,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   if (c->d_pub) hipFree(c->d_pub);
   if (c->d_batch) hipFree(c->d_batch);
   if (c->batch_img) hipFree(c->batch_img);
+  if (c->circ_io) hipFree(c->circ_io);
   if (c->ssp_frag) hipFree(c->ssp_frag);
   if (c->d_t0) hipFree(c->d_t0);
   for (auto &t : c->timed) { hipEventDestroy(t.e0); hipEventDestroy(t.e1); }
@@ -1267,6 +1268,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "mmstream_rounds_persistent")) return 110;  // ... those of them that ran the persistent one-workgroup-per-CU grid (k_mmstream_p / k_mmstream_w)
   if (!strcmp(which, "mmstream_bw_persistent")) return 114;      // ... and of "mmstream_bw" (k_mmstream_pb)
   if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
+  if (!strcmp(which, "circuit_assign")) return 16;  // k_circuit_eval of mfh_circuit_assign
   return -1;
 }
 

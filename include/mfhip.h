@@ -181,6 +181,33 @@ int mfh_ssp_prg_fill(mfh_ctx *ctx, uint64_t seed, size_t first_slot, size_t nslo
  * (d - 1) * ceil(d / 32) words (134 MB at d = 2^15) that it keeps; the call synchronises the context's stream. */
 int mfh_ssp_from_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t *d_ssp);
 
+/* Witnesses of a Boolean circuit for a batch of statements, evaluated on the device.  What random_ssp(mpz_t input, ...) (src/ssp.c:37) is to a random SSP --
+ * the reference's only source of a witness -- this is to the SSP of mfh_ssp_from_rows: the input bits of mfh_prove / mfh_prove_batch for each statement.
+ * Wires (mfh_ssp_from_rows): wire 0 is the constant, wires 1 .. nin are the inputs (public first, then private), and gate g writes wire nin + 1 + g.
+ * h_gates: ngates records (op, a, b) of uint32, op one of MFH_GATE_*, operands in [1, nin + g] (below the gate's own output wire); for NOT, b = a.
+ * h_asserts: nasserts records (wire, value), wire in [1, nin + ngates], value 0 or 1.
+ * mfh_circuit_create validates the program, orders the gates by level (inputs are level 0, a gate one more than its highest operand) and uploads it once.
+ * MFH_EINVAL, with nothing allocated, for an unknown op, an operand of 0 or not below the gate's output wire, an assertion on wire 0 or above nin + ngates, an
+ * assertion value other than 0 / 1, nin + ngates > m - 1, or nin + ngates > MFH_CIRCUIT_MAX_WIRES: the kernel keeps one uint32 word per wire in LDS,
+ * (MFH_CIRCUIT_MAX_WIRES + 1) * 4 bytes = 128 KiB of the 160 KiB of a CU (every circuit of mf.DEFAULT, m - 1 = 21 844 wires, fits).
+ * The program belongs to ctx's device; destroy it before the context. */
+#define MFH_GATE_XOR 0u /* c = a ^ b */
+#define MFH_GATE_AND 1u /* c = a & b */
+#define MFH_GATE_OR 2u  /* c = a | b */
+#define MFH_GATE_NOT 3u /* c = 1 - a */
+#define MFH_CIRCUIT_MAX_WIRES 32767u
+typedef struct mfh_circuit mfh_circuit;
+int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                       mfh_circuit **out);
+void mfh_circuit_destroy(mfh_circuit *c);
+/* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
+ * (bits_stride bytes) becomes the witness bit string of statement b: bit i - 1 = wire i, bits >= nin + ngates zero -- the layout mfh_prove_batch reads.
+ * h_holds[b] = 1 if every assertion holds on statement b, else 0.  Bitsliced: one workgroup serves 32 statements, one LDS word per wire.
+ * MFH_EINVAL for in_stride * 8 < nin or bits_stride * 8 < nin + ngates; nstmt = 0 does nothing.  Staged through the context's pinned buffers
+ * (mfh_scrub_staging zeroes them); the call synchronises the context's stream. */
+int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const uint8_t *h_inputs, size_t in_stride, uint8_t *h_witness_bits,
+                       size_t bits_stride, uint8_t *h_holds);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
@@ -435,7 +462,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two
