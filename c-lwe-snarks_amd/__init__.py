@@ -98,7 +98,7 @@ EXPORTS = [
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
-    "mfh_ssp_from_rows", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
+    "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
 ]
 
 
@@ -214,6 +214,8 @@ def load_library():
         "mfh_vk_derive": (i32, [vp, vp, u32, u32, vp]),
         "mfh_verify_public": (i32, [vp, vp, u32, u32, u32, vp, vp, ctypes.c_char_p, sz, sz, vp]),
         "mfh_ssp_from_rows": (i32, [vp, u32, vp, vp, vp, vp]),
+        "mfh_ssp_set_rows": (i32, [vp, u32, vp, vp, vp, u32]),
+        "mfh_ssp_rows_fill": (i32, [vp, sz, sz, vp]),
         "mfh_circuit_create": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_destroy": (None, [vp]),
         "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
@@ -507,6 +509,22 @@ class Context:
         self._chk(self.lib.mfh_ssp_from_rows(self._h, len(row_ptr) - 1, ctypes.c_void_p(row_ptr.ctypes.data), ctypes.c_void_p(wire.ctypes.data),
                                              ctypes.c_void_p(coef.ctypes.data), _ptr(d_ssp)))
         return d_ssp
+
+    def ssp_set_rows(self, rows, lu_max=0):
+        """register the constraint system as its rows (mfh_ssp_set_rows): rows as for ssp_from_rows (e.g. circuit.Compiled.rows); afterwards d_ssp=None means
+        this SSP in the setup, prover and verifier calls (call ssp_prepare(None) first).  rows=None unregisters and frees."""
+        if rows is None:
+            self._chk(self.lib.mfh_ssp_set_rows(self._h, 0, None, None, None, 0))
+            return
+        row_ptr, wire, coef = rows_to_csr(rows)
+        self._chk(self.lib.mfh_ssp_set_rows(self._h, len(row_ptr) - 1, ctypes.c_void_p(row_ptr.ctypes.data), ctypes.c_void_p(wire.ctypes.data),
+                                            ctypes.c_void_p(coef.ctypes.data), int(lu_max)))
+
+    def ssp_rows_fill(self, first_slot, nslots):
+        """slots [first_slot, first_slot + nslots) of the registered row SSP in the dense layout (mfh_ssp_rows_fill): nslots * d uint32 on the device"""
+        out = self.empty(max(nslots, 1) * self.params.d * 4)
+        self._chk(self.lib.mfh_ssp_rows_fill(self._h, first_slot, nslots, _ptr(out)))
+        return out
 
     def circuit_load(self, compiled):
         """the gate program of circuit.Compiled on the device (mfh_circuit_create): levelised and uploaded once; close() frees it"""

@@ -20,6 +20,15 @@ Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py c
     witness = c.assign(public_bits, private_bits)      # (m + 7) // 8 bytes for Context.prove / prove_batch
     prog = ctx.circuit_load(cc)                        # ... or a whole batch on the device:
     witness, holds = ctx.circuit_assign(prog, bits)    # bits [nb, nin] = public then private bits; witness [nb, (m + 7) // 8]
+
+A circuit too large for the dense SSP (d = 2^20: about 500 000 gates) is registered as its rows instead (mfh_ssp_set_rows):
+
+    p = mf.Params(d=1 << 20, m=699050)
+    cc = c.compile(p)
+    ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)            # no dense SSP; d_ssp=None below means these rows
+    ctx.ssp_prepare(None)
+    crs = ctx.setup_public(None, alpha, beta, s, cc.lu, d_sk, d_err)
+    proofs = ctx.prove_batch_public(crs, None, cc.lu, [c.assign(u, x) for u, x in stmts], deltas, mags, signs)
 """
 from __future__ import annotations
 

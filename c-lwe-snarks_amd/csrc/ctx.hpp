@@ -23,6 +23,8 @@
 
 struct PolyState;
 struct SspInterp;
+struct SspRows;
+struct RowsTree;
 
 // pinned host staging buffer whose previous async copy is awaited only when the buffer is reused
 struct PinBuf {
@@ -145,6 +147,12 @@ struct mfh_ctx {
   bool prg_on = false;
   uint64_t prg_seed = 0;
   const uint32_t *prg_t = nullptr;
+  // row SSP (ssp_rows.hip, mfh_ssp_set_rows): used by the entry points that handle it when they are handed d_ssp == NULL; the dense prefix holds slots
+  // [0, rows_lu_max + 2) and nothing else of the dense layout exists
+  SspRows *rows = nullptr;
+  RowsTree *rows_tree = nullptr;  // the tree of t, its transforms, t and the Lagrange weights: d alone, kept across registrations
+  const uint32_t *rows_prefix = nullptr;
+  uint32_t rows_lu_max = 0;
   const uint8_t *resident_rows = nullptr;  // expanded CRS (mfh_crs_expand layout) or null: regenerate the keystream
   uint64_t resident_nrows = ~0ull;         // full image: rows [0, resident_nrows) in stream order are resident, the rest is regenerated
   bool resident_sharded = false;           // image holds only rank res_rank's shares: S share | AS share | BT+BV share
@@ -205,9 +213,16 @@ inline void pin_free(PinBuf &b) {
   b = PinBuf();
 }
 
-// resolves the d_ssp argument of an entry point: a dense image, or (NULL) the registered generator-defined SSP
-inline int ssp_src(mfh_ctx *c, const uint32_t *d_ssp, mf::SspSrc &src) {
+// resolves the d_ssp argument of an entry point: a dense image, or (NULL) the registered row SSP or generator-defined SSP.  The row SSP is only
+// handed to callers that say they handle it (rows_ok): its `dense` is the prefix of slots [0, prefix), and a kernel that reads further would run
+// past it -- everyone else gets MFH_EUNSUPPORTED.
+inline int ssp_src(mfh_ctx *c, const uint32_t *d_ssp, mf::SspSrc &src, bool rows_ok = false) {
   if (d_ssp) { src = mf::SspSrc{d_ssp, d_ssp, 0}; return MFH_OK; }
+  if (c->rows_prefix) {
+    if (!rows_ok) { c->err = "this entry point does not take the row SSP (mfh_ssp_set_rows): pass a dense d_ssp"; return MFH_EUNSUPPORTED; }
+    src = mf::SspSrc{c->rows_prefix, c->rows_prefix, 0, c->rows_lu_max + 2};
+    return MFH_OK;
+  }
   if (!c->prg_on || !c->prg_t) { c->err = "d_ssp is NULL and no generator-defined SSP is registered (mfh_ssp_set_prg)"; return MFH_EINVAL; }
   src = mf::SspSrc{nullptr, c->prg_t, c->prg_seed};
   return MFH_OK;
@@ -215,6 +230,16 @@ inline int ssp_src(mfh_ctx *c, const uint32_t *d_ssp, mf::SspSrc &src) {
 
 void mfh_poly_destroy(mfh_ctx *c);
 void ssp_interp_free(mfh_ctx *c);
+// ssp_rows.hip: drop the row SSP (and, tree, the per-context tree of t); row-mode witness polynomials; row-mode setup messages 2d .. 2d + m - 1
+void ssp_rows_free(mfh_ctx *c, bool tree);
+int ssp_rows_witness(mfh_ctx *c, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta, uint32_t *d_w, size_t w_stride);
+int ssp_rows_msg_evals(mfh_ctx *c, uint32_t s, uint32_t beta, uint32_t *d_msg_evals);
+// the row SSP is what d_ssp == NULL means; lu public wires need lu <= lu_max (its dense prefix)
+inline bool ssp_is_rows(const mfh_ctx *c, const uint32_t *d_ssp) { return !d_ssp && c->rows_prefix; }
+inline int ssp_rows_lu_check(mfh_ctx *c, const uint32_t *d_ssp, uint32_t lu) {
+  if (ssp_is_rows(c, d_ssp) && lu > c->rows_lu_max) { c->err = "lu exceeds the lu_max the row SSP was registered with (mfh_ssp_set_rows)"; return MFH_EINVAL; }
+  return MFH_OK;
+}
 extern "C" int mfh_witness_poly_mm(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                                    uint32_t *d_w);
 extern "C" int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,

@@ -2077,6 +2077,10 @@ int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, 
 int mfh_witness_poly_mm(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                         uint32_t *d_w) {
   if (!c) return MFH_EINVAL;
+  if (ssp_is_rows(c, d_ssp)) {  // the row SSP: one interpolation per statement (ssp_rows.hip)
+    if (!h_bits || !h_delta || !d_w || nstmt == 0 || nstmt > 256) return MFH_EINVAL;
+    return ssp_rows_witness(c, nstmt, h_bits, bits_stride, h_delta, d_w, c->P.d);
+  }
   return mfh_witness_poly_mm_cols(c, d_ssp, nstmt, h_bits, bits_stride, h_delta, 0, c->P.d, d_w, c->P.d);
 }
 

@@ -1115,6 +1115,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   mfh_poly_destroy(c);
   ssp_interp_free(c);
+  ssp_rows_free(c, true);
   upload_free(c);
   if (c->sample_tmp) hipFree(c->sample_tmp);
   if (c->ev_sample) hipEventDestroy(c->ev_sample);
@@ -1952,6 +1953,7 @@ static int witness_partials(mfh_ctx *c, const mf::SspSrc &src, const uint8_t *h_
 
 int mfh_ssp_set_prg(mfh_ctx *c, uint64_t seed, const uint32_t *d_t) {
   if (!c) return MFH_EINVAL;
+  if (d_t) ssp_rows_free(c, false);  // registering one kind replaces the other
   c->prg_on = d_t != nullptr;
   c->prg_seed = seed;
   c->prg_t = d_t;
@@ -1986,6 +1988,7 @@ int mfh_witness_poly(mfh_ctx *c, const uint32_t *d_ssp, const uint8_t *h_bits, u
   if (!c || !h_bits || !d_w) return MFH_EINVAL;
   if (delta >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
+  if (ssp_is_rows(c, d_ssp)) return ssp_rows_witness(c, 1, h_bits, (c->P.m + 6) / 8, &delta, d_w, c->P.d);
   mf::SspSrc src;
   int rc = ssp_src(c, d_ssp, src);
   if (rc) return rc;
@@ -2004,6 +2007,7 @@ int mfh_witness_poly_multi(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, co
                            uint32_t *d_w) {
   constexpr int NB = 12;
   if (!c || !h_bits || !h_delta || !d_w || nstmt == 0 || nstmt > NB) return MFH_EINVAL;
+  if (ssp_is_rows(c, d_ssp)) return ssp_rows_witness(c, nstmt, h_bits, bits_stride, h_delta, d_w, c->P.d);
   mf::SspSrc src;  // d_ssp == NULL: the registered generator-defined SSP
   {
     int rc0 = ssp_src(c, d_ssp, src);

@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "ntt.hpp"
 
 namespace {
 
@@ -30,24 +31,8 @@ constexpr uint32_t P32 = 0xfffffffbu;
 // workgroup returns at once.
 #define MF_NEEDED(need, vs) do { if ((need) && (vs) >= *(need)) return; } while (0)
 
-struct NttPrime {
-  uint32_t p, ninv, r2;  // modulus, -p^-1 mod 2^32, 2^64 mod p
-};
-struct Primes3 {
-  NttPrime q[3];
-};
+using namespace mf_ntt;  // NttPrime, Primes3, Crt, mont_mul, add_mod, sub_mod, red_p32, crt_coeff (ntt.hpp)
 
-__host__ __device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t ninv) {
-  uint64_t t = (uint64_t)a * b;
-  uint32_t m = (uint32_t)t * ninv;
-  uint32_t u = (uint32_t)((t + (uint64_t)m * p) >> 32);
-  return u >= p ? u - p : u;
-}
-__host__ __device__ __forceinline__ uint32_t add_mod(uint32_t a, uint32_t b, uint32_t p) {
-  uint32_t s = a + b;  // p < 2^31: no overflow
-  return s >= p ? s - p : s;
-}
-__host__ __device__ __forceinline__ uint32_t sub_mod(uint32_t a, uint32_t b, uint32_t p) { return a >= b ? a - b : a + p - b; }
 // Lazy forms for the stages a kernel runs in registers (round 6; the primes are below 2^30 for them): values in [0, 2p) between stages, so that the product needs no
 // final subtraction and the difference no comparison -- the three quarter-rate multiplies of a butterfly stay, five of the ten instructions around them go
 // (tools/ntt_lazy_ubench.hip: 15 - 20 % of k_ntt_lds_mul8).  Every kernel still reads and writes CANONICAL residues: lz_canon on the way out.
@@ -71,15 +56,6 @@ __device__ __forceinline__ void lz_dit(uint32_t &x, uint32_t &y, uint32_t w, uin
   const uint32_t u = x, z = lz_mont(y, w, p, ninv), d = u - z + 2 * p;
   x = lz_add(u, z, 2 * p);
   y = min(d, d - 2 * p);
-}
-
-// x mod (2^32 - 5) for x < 2^64:  2^32 = 5
-__host__ __device__ __forceinline__ uint32_t red_p32(uint64_t x) {
-  x = (x >> 32) * 5 + (uint32_t)x;  // < 5*2^32 + 2^32
-  x = (x >> 32) * 5 + (uint32_t)x;  // < 30 + 2^32
-  if (x >= P32) x -= P32;
-  if (x >= P32) x -= P32;
-  return (uint32_t)x;
 }
 
 uint64_t h_powmod(uint64_t a, uint64_t e, uint64_t p) {
@@ -437,27 +413,6 @@ __global__ void k_pointwise(uint32_t *__restrict__ a, const uint32_t *__restrict
   const NttPrime q = P.q[blockIdx.y % 3];
   size_t o = (size_t)blockIdx.y * N + i;
   a[o] = mont_mul(a[o], b[o], q.p, q.ninv);
-}
-struct Crt {
-  uint32_t ninv_std[3];  // N^-1 mod p_i (standard form): mont_mul(xR, ninv_std) = x / N in standard form
-  uint32_t inv_p1_p2, inv_p1_p3, inv_p2_p3;  // Montgomery form of p1^-1 mod p2, p1^-1 mod p3, p2^-1 mod p3
-  uint32_t p1_mod, p1p2_mod;                 // p1 mod p32, p1*p2 mod p32
-};
-// the three residues of one coefficient (Montgomery form, as an unscaled inverse transform leaves them) -> the coefficient mod p32
-__device__ __forceinline__ uint32_t crt_coeff(uint32_t a1, uint32_t a2, uint32_t a3, const Primes3 &P, const Crt &C) {
-  const NttPrime q1 = P.q[0], q2 = P.q[1], q3 = P.q[2];
-  uint32_t x1 = mont_mul(a1, C.ninv_std[0], q1.p, q1.ninv);
-  uint32_t r2 = mont_mul(a2, C.ninv_std[1], q2.p, q2.ninv);
-  uint32_t r3 = mont_mul(a3, C.ninv_std[2], q3.p, q3.ninv);
-  // Garner: X = x1 + x2 p1 + x3 p1 p2
-  uint32_t x1m2 = x1 >= q2.p ? x1 - q2.p : x1;  // x1 < p1 < 2 p2
-  uint32_t x2 = mont_mul(sub_mod(r2, x1m2, q2.p), C.inv_p1_p2, q2.p, q2.ninv);
-  uint32_t x1m3 = x1 >= q3.p ? x1 - q3.p : x1;
-  uint32_t x2m3 = x2 >= q3.p ? x2 - q3.p : x2;
-  uint32_t t3 = mont_mul(sub_mod(r3, x1m3, q3.p), C.inv_p1_p3, q3.p, q3.ninv);
-  uint32_t x3 = mont_mul(sub_mod(t3, x2m3, q3.p), C.inv_p2_p3, q3.p, q3.ninv);
-  uint64_t acc = (uint64_t)red_p32(x1) + red_p32((uint64_t)x2 * C.p1_mod) + red_p32((uint64_t)x3 * C.p1p2_mod);
-  return red_p32(acc);
 }
 // residues (Montgomery, unscaled inverse transform) -> coefficient mod p32: out[i] = coefficient i, i < count -- or, rev_top >= 0, coefficient rev_top - i where that
 // lies in [0, nsrc) and zero elsewhere (the reversals of the Euclidean path written by the kernel that produces the coefficients: rev(A)[:n], and the quotient
@@ -960,6 +915,51 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
 }
 
 }  // namespace
+
+// ---- blockwise transforms for ssp_rows.hip (ntt.hpp): the same kernels as the polynomial step, started at block length 2^logB instead of N --------------
+int ntt_reserve(mfh_ctx *c, uint32_t logmax) { return poly_init(c, std::max(logmax, 1u)); }
+const Primes3 &ntt_primes(const mfh_ctx *c) { return c->poly->P; }
+Crt ntt_crt_make(const mfh_ctx *c, uint32_t logB) { return make_crt(c->poly, logB); }
+void ntt_blocks_forward(mfh_ctx *c, uint32_t *buf, uint32_t N, uint32_t logB, uint32_t nb) {
+  PolyState *S = c->poly;
+  const uint32_t half_max = 1u << (S->logmax - 1), B = std::min(logB, 11u);
+  const uint32_t *nil = nullptr;
+  uint32_t top = logB - B, len = 1u << logB;
+  while (top) {  // k_ntt_dif_multi works on every block of length `len` of the buffer: a transform of length N is the case len = N
+    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;
+    dim3 g(((N >> k) + 255) / 256, 3 * nb);
+    switch (k) {
+      case 5: hipLaunchKernelGGL(k_ntt_dif_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
+      case 4: hipLaunchKernelGGL(k_ntt_dif_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
+      case 3: hipLaunchKernelGGL(k_ntt_dif_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
+      case 2: hipLaunchKernelGGL(k_ntt_dif_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
+      default: hipLaunchKernelGGL(k_ntt_dif_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
+    }
+    len >>= k;
+    top -= k;
+  }
+  hipLaunchKernelGGL(k_ntt_lds<false>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_tw, half_max, S->P);
+}
+void ntt_blocks_inverse(mfh_ctx *c, uint32_t *buf, uint32_t N, uint32_t logB, uint32_t nb) {
+  PolyState *S = c->poly;
+  const uint32_t half_max = 1u << (S->logmax - 1), B = std::min(logB, 11u);
+  hipLaunchKernelGGL(k_ntt_lds<true>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_twi, half_max, S->P);
+  uint32_t top = logB - B, len = 2u << B;
+  while (top) {
+    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;
+    dim3 g(((N >> k) + 255) / 256, 3 * nb);
+    const uint32_t *nil = nullptr;
+    switch (k) {
+      case 5: hipLaunchKernelGGL(k_ntt_dit_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
+      case 4: hipLaunchKernelGGL(k_ntt_dit_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
+      case 3: hipLaunchKernelGGL(k_ntt_dit_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
+      case 2: hipLaunchKernelGGL(k_ntt_dit_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
+      default: hipLaunchKernelGGL(k_ntt_dit_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
+    }
+    len <<= k;
+    top -= k;
+  }
+}
 
 void mfh_poly_destroy(mfh_ctx *c) {
   delete c->poly;

@@ -254,7 +254,7 @@ extern "C" {
 int mfh_ssp_prepare(mfh_ctx *c, const uint32_t *d_ssp) {
   if (!c) return MFH_EINVAL;
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);
   if (rc) return rc;
   return mfh_poly_prepare_t(c, src.t);  // slot 0 = t
 }
@@ -266,13 +266,17 @@ int mfh_setup_messages(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32
   if (d % 4) { c->err = "d must be a multiple of 4"; return MFH_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);
   if (rc) return rc;
   rc = aux_reserve(c, (size_t)d * 4);
   if (rc) return rc;
   uint32_t *pw = (uint32_t *)c->aux;
   hipLaunchKernelGGL(k_powers, g1(d), dim3(256), 0, c->stream, s, d, pw);
   hipLaunchKernelGGL(k_msg_powers, g1(d), dim3(256), 0, c->stream, pw, d, alpha, d_msg);
+  if (src.prefix) {  // the row SSP: v_r(s) from its rows, not from coefficients it does not store
+    HIP_TRY(c, hipGetLastError());
+    return ssp_rows_msg_evals(c, s, beta, d_msg + (size_t)2 * d);
+  }
   hipLaunchKernelGGL(k_msg_evals, dim3(m), dim3(256), 0, c->stream, src, pw, d, beta, d_msg);
   HIP_TRY(c, hipGetLastError());
   return MFH_OK;
@@ -309,7 +313,7 @@ int mfh_verify(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta,
   const uint32_t d = c->P.d;
   HIP_TRY(c, hipSetDevice(c->device));
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);  // (slots 0 and 1)
   if (rc) return rc;
   rc = aux_reserve(c, (size_t)d * 4 + 16 + count * 5 * 4);
   if (rc) return rc;
@@ -329,6 +333,7 @@ int mfh_setup_public(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t
                      uint8_t *d_crs_c8, void *d_rows_image) {
   if (!c) return MFH_EINVAL;
   if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
+  if (int rc0 = ssp_rows_lu_check(c, d_ssp, lu)) return rc0;
   if (!lu) return mfh_setup_image(c, d_ssp, alpha, beta, s, d_sk, d_err, d_crs_c8, d_rows_image);
   if (!d_sk || !d_err || !d_crs_c8) return MFH_EINVAL;
   const size_t rows = (size_t)2 * c->P.d + c->P.m;
@@ -354,8 +359,9 @@ int mfh_vk_derive(mfh_ctx *c, const uint32_t *d_ssp, uint32_t s, uint32_t lu, ui
   const uint32_t d = c->P.d;
   HIP_TRY(c, hipSetDevice(c->device));
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);  // (slots 0 .. lu + 1)
   if (rc) return rc;
+  if ((rc = ssp_rows_lu_check(c, d_ssp, lu))) return rc;
   rc = aux_reserve(c, (size_t)d * 4);
   if (rc) return rc;
   uint32_t *pw = (uint32_t *)c->aux;
@@ -431,8 +437,9 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
   }
   mf::SspSrc src;
   {
-    int rc0 = ssp_src(c, d_ssp, src);
+    int rc0 = ssp_src(c, d_ssp, src, world == 1 && !d_wlanes);  // (the row SSP: one GPU; its witness pass is mfh_witness_poly's)
     if (rc0) return rc0;
+    if ((rc0 = ssp_rows_lu_check(c, d_ssp, lu))) return rc0;
   }
   const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
   const uint32_t L = (c->P.logq + 63) / 64, ctb = c->P.logq / 8;
@@ -1068,8 +1075,9 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
   if (c->mm_image && c->mm_world != 1) { c->err = "mfh_prove_batch: the registered matrix-core image holds one rank's row shares (use mfh_prove_batch_partial)"; return MFH_EINVAL; }
   mf::SspSrc src;
   {
-    int rc0 = ssp_src(c, d_ssp, src);
+    int rc0 = ssp_src(c, d_ssp, src, true);  // (the row SSP: batch_chain_launch's witness pass interpolates)
     if (rc0) return rc0;
+    if (pub && (rc0 = ssp_rows_lu_check(c, d_ssp, pub->lu))) return rc0;
   }
   const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
   if (bits_stride < (m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
@@ -1377,7 +1385,7 @@ int mfh_batch_chain(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uin
   if (!nstmt) return MFH_OK;
   if (!h_witness_bits || !h_delta || !d_w || !d_h || !d_v) return MFH_EINVAL;
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);
   if (rc) return rc;
   const uint32_t d = c->P.d, m = c->P.m;
   if (bits_stride < (m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
@@ -1415,7 +1423,7 @@ int mfh_batch_chain_from_w(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, co
   if (!nstmt) return MFH_OK;
   if (!d_w || !d_h || !d_v) return MFH_EINVAL;
   mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
+  int rc = ssp_src(c, d_ssp, src, true);  // (slot 1)
   if (rc) return rc;
   const uint32_t d = c->P.d;
   HIP_TRY(c, hipSetDevice(c->device));

@@ -41,11 +41,12 @@ MF_HD uint32_t ssp_prg_coeff(uint32_t rowkey, uint32_t k) {
   return x >= 0xfffffffbu ? x - 0xfffffffbu : x;
 }
 
-// where a kernel takes its SSP coefficients from: a dense uint32 [(m+3)][d] image, or the generator (+ stored slot 0)
+// where a kernel takes its SSP coefficients from: a dense uint32 [(m+3)][d] image, the generator (+ stored slot 0), or the prefix of the row SSP
 struct SspSrc {
-  const uint32_t *dense;  // non-null: dense image
+  const uint32_t *dense;  // non-null: dense image (row SSP: its slots [0, prefix) only)
   const uint32_t *t;      // generator mode: slot 0
   uint64_t seed;
+  uint32_t prefix;        // 0: `dense` is a whole image; else the row SSP (ssp_rows.hip) and only slots below this exist
 };
 
 }  // namespace mf

@@ -181,6 +181,23 @@ int mfh_ssp_prg_fill(mfh_ctx *ctx, uint64_t seed, size_t first_slot, size_t nslo
  * (d - 1) * ceil(d / 32) words (134 MB at d = 2^15) that it keeps; the call synchronises the context's stream. */
 int mfh_ssp_from_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t *d_ssp);
 
+/* The same constraint system registered as its ROWS (the row SSP): no dense image exists, so circuits fill any d mfh_ssp_from_rows accepts up to 2^22,
+ * including d = 2^20 where the dense SSP would be 2.9 TB.  Input, points, padding rows and every MFH_EINVAL case as mfh_ssp_from_rows (an MFH_EINVAL leaves
+ * the previous registration in place); lu_max < m is the largest number of public wires the prover will be asked for.  Afterwards d_ssp == NULL means the row
+ * SSP in mfh_ssp_prepare, mfh_setup_messages, mfh_setup, mfh_setup_image, mfh_setup_public, mfh_vk_derive, mfh_verify, mfh_witness_poly, mfh_witness_poly_multi,
+ * mfh_witness_poly_mm, mfh_prove, mfh_prove_public, mfh_prove_batch, mfh_prove_batch_public and mfh_batch_chain, and every one of them returns exactly what it
+ * returns for the dense SSP mfh_ssp_from_rows writes from the same rows.  A public call with lu > lu_max returns MFH_EINVAL.  mfh_witness_lanes,
+ * mfh_witness_from_lanes, mfh_witness_poly_mm_cols, mfh_batch_witness_cols and mfh_prove_partial* with world > 1 return MFH_EUNSUPPORTED in row mode.
+ * The prover interpolates w - delta t from the statement's row sums by the subproduct tree of t (csrc/ssp_rows.hip); setup evaluates v_i(s) from the rows.
+ * Registering replaces a generator-defined SSP (and mfh_ssp_set_prg replaces the row SSP); mfh_ssp_set_rows(ctx, 0, NULL, NULL, NULL, 0) unregisters and frees.
+ * Derived images of an earlier SSP are dropped as by mfh_ssp_from_rows; call mfh_ssp_prepare(ctx, NULL) afterwards.  The call synchronises the stream.
+ * Device memory: per context (d alone, kept across registrations) the tree of t, (6 log2(Np / 64) + 1) Np + 2 d words with Np = 2^ceil(log2 d) -- 7.3 MB at
+ * d = 2^15, 0.37 GB at 2^20 -- plus the NTT tables of the polynomial step for length Np; per registration the rows (nrows + 1 + 2 nnz words), the dense
+ * prefix t, v_0 .. v_lu_max ((lu_max + 2) d words) and the interpolation scratch: 8 Np words per statement in flight, chunks of at most 128 MB.
+ * mfh_ssp_rows_fill writes slots [first_slot, first_slot + nslots) of the dense layout by interpolation (tests; slot 0 = t, slots m + 1, m + 2 = 0). */
+int mfh_ssp_set_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t lu_max);
+int mfh_ssp_rows_fill(mfh_ctx *ctx, size_t first_slot, size_t nslots, uint32_t *d_out);
+
 /* Witnesses of a Boolean circuit for a batch of statements, evaluated on the device.  What random_ssp(mpz_t input, ...) (src/ssp.c:37) is to a random SSP --
  * the reference's only source of a witness -- this is to the SSP of mfh_ssp_from_rows: the input bits of mfh_prove / mfh_prove_batch for each statement.
  * Wires (mfh_ssp_from_rows): wire 0 is the constant, wires 1 .. nin are the inputs (public first, then private), and gate g writes wire nin + 1 + g.
