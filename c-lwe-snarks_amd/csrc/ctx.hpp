@@ -97,7 +97,7 @@ struct mfh_ctx {
   void *ssp_frag = nullptr;  // the dense SSP in MFMA B-fragment order (evalmm.hip: witness pass of the batch prover); built lazily
   size_t ssp_frag_bytes = 0;
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
-  SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): t, its seed table and the Lagrange weights, built on first use
+  SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
   void *circ_io = nullptr;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
   size_t circ_io_bytes = 0;
   void *d_batch = nullptr;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
@@ -150,7 +150,7 @@ struct mfh_ctx {
   // row SSP (ssp_rows.hip, mfh_ssp_set_rows): used by the entry points that handle it when they are handed d_ssp == NULL; the dense prefix holds slots
   // [0, rows_lu_max + 2) and nothing else of the dense layout exists
   SspRows *rows = nullptr;
-  RowsTree *rows_tree = nullptr;  // the tree of t, its transforms, t and the Lagrange weights: d alone, kept across registrations
+  RowsTree *rows_tree = nullptr;  // the tree of t, its transforms, t and the Lagrange weights: d alone, kept across registrations; mfh_ssp_from_rows builds it too
   const uint32_t *rows_prefix = nullptr;
   uint32_t rows_lu_max = 0;
   const uint8_t *resident_rows = nullptr;  // expanded CRS (mfh_crs_expand layout) or null: regenerate the keystream
@@ -232,6 +232,11 @@ void mfh_poly_destroy(mfh_ctx *c);
 void ssp_interp_free(mfh_ctx *c);
 // ssp_rows.hip: drop the row SSP (and, tree, the per-context tree of t); row-mode witness polynomials; row-mode setup messages 2d .. 2d + m - 1
 void ssp_rows_free(mfh_ctx *c, bool tree);
+// ... the row format of mfh_ssp_from_rows and mfh_ssp_set_rows: MFH_EINVAL with c->err = "<who>: ..." unless it holds
+int ssp_rows_check(mfh_ctx *c, const char *who, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef);
+// ... the per-context tree of t, built unless it is there (MFH_EUNSUPPORTED for d > 2^22; c->err = "<who>: ..."): t on the device, d words zero-padded to a
+// multiple of 32, and the d - 1 Lagrange weights on the host, both valid until the tree is freed
+int ssp_rows_tree(mfh_ctx *c, const char *who, const uint32_t *&d_t, const uint32_t *&h_w);
 int ssp_rows_witness(mfh_ctx *c, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta, uint32_t *d_w, size_t w_stride);
 int ssp_rows_msg_evals(mfh_ctx *c, uint32_t s, uint32_t beta, uint32_t *d_msg_evals);
 // the row SSP is what d_ssp == NULL means; lu public wires need lu <= lu_max (its dense prefix)

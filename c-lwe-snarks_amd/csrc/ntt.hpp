@@ -5,11 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "p32.hpp"
+
 struct mfh_ctx;
 
 namespace mf_ntt {
-
-constexpr uint32_t kP32 = 0xfffffffbu;
 
 struct NttPrime {
   uint32_t p, ninv, r2;  // modulus, -p^-1 mod 2^32, 2^64 mod p
@@ -29,16 +29,6 @@ __host__ __device__ __forceinline__ uint32_t add_mod(uint32_t a, uint32_t b, uin
   return s >= p ? s - p : s;
 }
 __host__ __device__ __forceinline__ uint32_t sub_mod(uint32_t a, uint32_t b, uint32_t p) { return a >= b ? a - b : a + p - b; }
-
-// x mod (2^32 - 5) for x < 2^64:  2^32 = 5
-__host__ __device__ __forceinline__ uint32_t red_p32(uint64_t x) {
-  x = (x >> 32) * 5 + (uint32_t)x;  // < 5*2^32 + 2^32
-  x = (x >> 32) * 5 + (uint32_t)x;  // < 30 + 2^32
-  if (x >= kP32) x -= kP32;
-  if (x >= kP32) x -= kP32;
-  return (uint32_t)x;
-}
-
 
 struct Crt {
   uint32_t ninv_std[3];  // N^-1 mod p_i (standard form): mont_mul(xR, ninv_std) = x / N in standard form

@@ -23,15 +23,13 @@
 
 namespace {
 
-constexpr uint32_t P32 = 0xfffffffbu;
-
 // kernels of the Euclidean path take `need`: nullptr = every polynomial of the launch; else only the first *need ones -- the statements whose exact-division result
 // failed the check, compacted: polynomial vs of the launch is statement need[2 + vs] of the batch (k_exact_check), which matters where a launch reads the
 // batch's input or writes its output (`map` = need + 2 there); the transform and scratch buffers in between hold the compacted polynomials.  Nothing failed: every
 // workgroup returns at once.
 #define MF_NEEDED(need, vs) do { if ((need) && (vs) >= *(need)) return; } while (0)
 
-using namespace mf_ntt;  // NttPrime, Primes3, Crt, mont_mul, add_mod, sub_mod, red_p32, crt_coeff (ntt.hpp)
+using namespace mf_ntt;  // NttPrime, Primes3, Crt, mont_mul, add_mod, sub_mod, crt_coeff (ntt.hpp)
 
 // Lazy forms for the stages a kernel runs in registers (round 6; the primes are below 2^30 for them): values in [0, 2p) between stages, so that the product needs no
 // final subtraction and the difference no comparison -- the three quarter-rate multiplies of a butterfly stay, five of the ten instructions around them go
@@ -868,7 +866,7 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
   HIP_TRY(c, hipMemcpyAsync(&bottom, lev + off.back(), 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (!bottom) return MFH_OK;  // t shares a factor with x^Nc - 1 (probability about 2 / p for a random t)
-  const uint32_t binv = (uint32_t)h_powmod(bottom, (uint64_t)P32 - 2, P32);
+  const uint32_t binv = invp(bottom);
   HIP_TRY(c, hipMemcpyAsync(inv[0], &binv, 4, hipMemcpyHostToDevice, c->stream));
   int cur = 0;
   for (int k = (int)off.size() - 2; k >= 0; k--) {  // up: a_k^-1 = a_k(-x) a_{k+1}^-1(x^2)
@@ -1013,7 +1011,7 @@ int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
   HIP_TRY(c, hipMalloc(&S->d_f, (size_t)(dt + 1) * 4));
   hipLaunchKernelGGL(k_reverse, g1((uint32_t)dt + 1), dim3(256), 0, c->stream, d_t, dt, (uint32_t)dt + 1, S->d_f);  // f = rev(t)
   // Newton: g <- g (2 - f g) mod x^(2k)
-  uint32_t g0 = (uint32_t)h_powmod(t[dt], (uint64_t)P32 - 2, P32);
+  uint32_t g0 = invp(t[dt]);
   HIP_TRY(c, hipMemsetAsync(S->d_G, 0, (size_t)std::max(n, 2u) * 4 * 2, c->stream));
   HIP_TRY(c, hipMemcpyAsync(S->d_G, &g0, 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

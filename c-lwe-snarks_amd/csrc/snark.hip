@@ -10,19 +10,9 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "p32.hpp"
 
 namespace {
-
-constexpr uint32_t P32 = 0xfffffffbu;
-
-__device__ __forceinline__ uint32_t red_p32(uint64_t x) {
-  x = (x >> 32) * 5 + (uint32_t)x;
-  x = (x >> 32) * 5 + (uint32_t)x;
-  if (x >= P32) x -= P32;
-  if (x >= P32) x -= P32;
-  return (uint32_t)x;
-}
-__device__ __forceinline__ uint32_t mulmod(uint32_t a, uint32_t b) { return red_p32((uint64_t)a * b); }
 
 // coefficient k of SSP slot `slot` from either source (ssp_prg.hpp)
 __device__ __forceinline__ uint32_t ssp_coef(const mf::SspSrc &src, uint32_t slot, uint32_t rowkey, uint32_t d, uint32_t k) {
@@ -36,8 +26,8 @@ __global__ void k_powers(uint32_t s, uint32_t d, uint32_t *__restrict__ pw) {
   if (k >= d) return;
   uint32_t r = 1, b = s, e = k;
   while (e) {
-    if (e & 1) r = mulmod(r, b);
-    b = mulmod(b, b);
+    if (e & 1) r = mulp(r, b);
+    b = mulp(b, b);
     e >>= 1;
   }
   pw[k] = r;
@@ -47,7 +37,7 @@ __global__ void k_msg_powers(const uint32_t *__restrict__ pw, uint32_t d, uint32
   uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= d) return;
   msg[k] = pw[k];
-  msg[d + k] = mulmod(alpha, pw[k]);
+  msg[d + k] = mulp(alpha, pw[k]);
 }
 // msg[2d + r] = beta * <slot(r), pw>, slot(0) = t (slot 0), slot(r) = v_r (slot r+1) for r = 1..m-1: Horner's value
 // nmod_poly_evaluate_nmod(v_i, s) * beta (src/snark.c:97-98,105-106), computed as a dot product with the powers of s.
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(256) void k_msg_evals(mf::SspSrc src, const uint32_
   for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) msg[2 * d + r] = mulmod(red_p32(red[0] + red[1] + red[2] + red[3]), beta);
+  if (threadIdx.x == 0) msg[2 * d + r] = mulp(red_p32(red[0] + red[1] + red[2] + red[3]), beta);
 }
 
 // out = a + (slot `slot` of the SSP) mod p
@@ -200,10 +190,10 @@ __global__ __launch_bounds__(256) void k_eval_slots01(mf::SspSrc src, const uint
 // the four checks of verifier() (src/snark.c:219-235) on the decrypted values of one proof, v_s = v(s) already formed
 __device__ __forceinline__ bool verify_checks(uint32_t h_s, uint32_t hath_s, uint32_t hatv_s, uint32_t w_s, uint32_t b_s, uint32_t t_s, uint32_t v_s,
                                               uint32_t alpha, uint32_t beta) {
-  bool good = mulmod(h_s, alpha) == hath_s;                                         // eq-pke
-  good = good && mulmod(v_s, alpha) == hatv_s;
-  good = good && red_p32((uint64_t)mulmod(v_s, v_s) + P32 - 1) == mulmod(h_s, t_s);  // eq-div
-  good = good && mulmod(w_s, beta) == b_s;                                          // eq-lin
+  bool good = mulp(h_s, alpha) == hath_s;                                     // eq-pke
+  good = good && mulp(v_s, alpha) == hatv_s;
+  good = good && red_p32((uint64_t)mulp(v_s, v_s) + P32 - 1) == mulp(h_s, t_s);  // eq-div
+  good = good && mulp(w_s, beta) == b_s;                                      // eq-lin
   return good;  // the reference's "test-error" bound (src/snark.c:238-241) can never reject
 }
 // the four checks of verifier() (src/snark.c:219-235) on decrypted values dec[5*i .. 5*i+5) = h, hat_h, hat_v, v_w, b_w

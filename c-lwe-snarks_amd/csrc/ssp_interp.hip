@@ -6,7 +6,7 @@
 //     v_i(x) = sum_j V_ij w_j Q_j(x),     q_{j,d-1} = 0,  q_{j,k-1} = t_k + r_j q_{j,k}   (synthetic division of t by x - r_j).
 // So the SSP is a sparse (wires x rows) by dense (rows x coefficients) product mod p; the result is canonical residues, exact in any summation order.
 //
-// Per context (t and the weights depend on d alone, and d is fixed per context): t by a product tree on the device, the weights on the host, and a seed
+// Per context (t and the weights depend on d alone, and d is fixed per context): t and the weights from the tree of t of the row SSP (ssp_rows.hip), and a seed
 // table seeds[j][b] = q_{j, (b+1) G - 1}: the value of the recurrence at the top of every G-coefficient sub-tile, so that a thread regenerates one sub-tile's
 // q_{j,k} in registers from one load.  Per call: the rows are sorted into wire columns on the host (c_ij = V_ij w_j, O(nnz)), cut into parts of at most CH
 // nonzeros (load balance by nonzeros: v_0 carries every booleanity row, every gate row and the padding), and one launch writes every slot; parts of a cut
@@ -15,49 +15,14 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "p32.hpp"
 
 namespace {
 
-constexpr uint32_t P32 = 0xfffffffbu;
 constexpr int IG = 32;            // coefficients per thread (one sub-tile): 32 uint64 accumulators + 32 t words in registers
 constexpr uint32_t IWG = 256;     // threads per workgroup of the gather launch
 constexpr uint32_t CH_MIN = 256;  // nonzeros per part, at least (parts of a cut column go through scratch)
 constexpr uint32_t MAX_CUT = 512; // ... and more when nnz / CH_MIN would exceed this: scratch <= 2 * MAX_CUT * d words
-
-__device__ __forceinline__ uint32_t red_p32(uint64_t x) {  // (2^32 = 5 mod p)
-  x = (x >> 32) * 5 + (uint32_t)x;
-  x = (x >> 32) * 5 + (uint32_t)x;
-  if (x >= P32) x -= P32;
-  if (x >= P32) x -= P32;
-  return (uint32_t)x;
-}
-// a 64-bit product folded once: < 6 * 2^32, so 2^29 of them sum in a uint64
-__device__ __forceinline__ uint64_t fold1(uint64_t x) { return (x >> 32) * 5 + (uint32_t)x; }
-
-// ---- t by a product tree.  A node of degree L is stored as its L low coefficients (monic: the leading 1 is implicit); N leaves (x - r_j), padded
-// with factors x (r = 0) to the power of two N >= d, so the root is x^(N - n) t.
-__global__ void k_tree_leaves(uint32_t n, uint32_t N, uint32_t *__restrict__ a) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < N) a[j] = j < n ? P32 - (j + 2) : 0;
-}
-// node i of degree 2L = node 2i * node 2i+1 (degree L each): c_k = sum_{u+v=k, u,v<L} A_u B_v + [k >= L] (A_{k-L} + B_{k-L})
-__global__ __launch_bounds__(256) void k_tree_level(const uint32_t *__restrict__ a, uint32_t L, uint32_t N, uint32_t *__restrict__ out) {
-  const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= N) return;
-  const uint32_t i = o / (2 * L), k = o % (2 * L);
-  const uint32_t *A = a + (size_t)2 * i * L, *B = A + L;
-  uint64_t acc = 0;
-  const uint32_t lo = k >= L ? k - L + 1 : 0, hi = k < L ? k : L - 1;
-  for (uint32_t u = lo; u <= hi; u++) acc += fold1((uint64_t)A[u] * B[k - u]);
-  if (k >= L) acc += (uint64_t)A[k - L] + B[k - L];
-  out[o] = red_p32(acc);
-}
-// tpad[k] = t_k (k < d - 1), 1 (k = d - 1), 0 up to the padded length Dp
-__global__ void k_tree_finish(const uint32_t *__restrict__ root, uint32_t N, uint32_t n, uint32_t d, uint32_t Dp, uint32_t *__restrict__ tpad) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= Dp) return;
-  tpad[k] = k < n ? root[k + N - n] : k == n ? 1u : 0u;
-}
 
 // ---- seeds.  Over sub-tile b the recurrence is affine: q_{bG-1} = r^G q_{top(b)} + L_b, with L_b its G steps from 0 (top(b) = bG + G - 1).
 __global__ __launch_bounds__(256) void k_seed_local(const uint32_t *__restrict__ tpad, uint32_t n, uint32_t NB, uint32_t *__restrict__ seeds) {
@@ -145,22 +110,12 @@ __global__ __launch_bounds__(256) void k_interp_sum(const uint4 *__restrict__ sp
   ssp[(size_t)sp.x * d + k] = red_p32(acc);
 }
 
-uint32_t mulmod_h(uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % P32); }
-uint32_t powmod_h(uint32_t a, uint64_t e) {
-  uint32_t r = 1;
-  for (; e; e >>= 1, a = mulmod_h(a, a))
-    if (e & 1) r = mulmod_h(r, a);
-  return r;
-}
-
 }  // namespace
 
-// what mfh_ssp_from_rows keeps per context (t, seeds and weights depend on d alone)
+// what mfh_ssp_from_rows keeps per context (the seeds depend on d alone)
 struct SspInterp {
   uint32_t NB = 0;               // sub-tiles of G coefficients: Dp = NB * G >= d
-  uint32_t *tpad = nullptr;      // Dp words: t, zero-padded
   uint32_t *seeds = nullptr;     // n * NB words
-  std::vector<uint32_t> w;       // Lagrange weights, n words (host)
   void *buf = nullptr;           // per call: nonzeros | parts | splits
   size_t buf_bytes = 0;
   void *scratch = nullptr;       // per call: the parts of cut columns
@@ -170,7 +125,6 @@ struct SspInterp {
 void ssp_interp_free(mfh_ctx *c) {
   SspInterp *s = c->interp;
   if (!s) return;
-  if (s->tpad) hipFree(s->tpad);
   if (s->seeds) hipFree(s->seeds);
   if (s->buf) hipFree(s->buf);
   if (s->scratch) hipFree(s->scratch);
@@ -178,75 +132,42 @@ void ssp_interp_free(mfh_ctx *c) {
   c->interp = nullptr;
 }
 
-static int interp_prepare(mfh_ctx *c) {
+// the seed table from t (Dp words, zero-padded)
+static int interp_prepare(mfh_ctx *c, const uint32_t *tpad) {
   if (c->interp && c->interp->seeds) return MFH_OK;
   if (!c->interp) c->interp = new SspInterp();
   SspInterp *s = c->interp;
   const uint32_t d = c->P.d, n = d - 1;
-  uint32_t N = 1;
-  while (N < d) N <<= 1;
   s->NB = (d + IG - 1) / IG;
-  const uint32_t Dp = s->NB * IG;
-  uint32_t *tree = nullptr;
-  if (hipMalloc((void **)&tree, (size_t)2 * N * 4) != hipSuccess || hipMalloc((void **)&s->tpad, (size_t)Dp * 4) != hipSuccess ||
-      hipMalloc((void **)&s->seeds, (size_t)n * s->NB * 4) != hipSuccess) {
+  if (hipMalloc((void **)&s->seeds, (size_t)n * s->NB * 4) != hipSuccess) {
     (void)hipGetLastError();
-    if (tree) hipFree(tree);
-    if (s->tpad) hipFree(s->tpad);
-    s->tpad = s->seeds = nullptr;
-    c->err = "mfh_ssp_from_rows: no memory for t and its seed table";
+    s->seeds = nullptr;
+    c->err = "mfh_ssp_from_rows: no memory for the seed table";
     return MFH_ENOMEM;
   }
-  uint32_t *a = tree, *o = tree + N;
-  hipLaunchKernelGGL(k_tree_leaves, dim3((N + 255) / 256), dim3(256), 0, c->stream, n, N, a);
-  for (uint32_t L = 1; L < N; L <<= 1) {
-    hipLaunchKernelGGL(k_tree_level, dim3((N + 255) / 256), dim3(256), 0, c->stream, a, L, N, o);
-    std::swap(a, o);
-  }
-  hipLaunchKernelGGL(k_tree_finish, dim3((Dp + 255) / 256), dim3(256), 0, c->stream, a, N, n, d, Dp, s->tpad);
   const uint64_t nseed = (uint64_t)n * s->NB;
-  hipLaunchKernelGGL(k_seed_local, dim3((uint32_t)((nseed + 255) / 256)), dim3(256), 0, c->stream, s->tpad, n, s->NB, s->seeds);
+  hipLaunchKernelGGL(k_seed_local, dim3((uint32_t)((nseed + 255) / 256)), dim3(256), 0, c->stream, tpad, n, s->NB, s->seeds);
   hipLaunchKernelGGL(k_seed_scan, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, s->NB, s->seeds);
-  const hipError_t e = hipStreamSynchronize(c->stream);
-  hipFree(tree);
-  if (e != hipSuccess || hipGetLastError() != hipSuccess) {
-    hipFree(s->tpad);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     hipFree(s->seeds);
-    s->tpad = s->seeds = nullptr;
-    c->err = "mfh_ssp_from_rows: building t failed";
+    s->seeds = nullptr;
+    c->err = "mfh_ssp_from_rows: building the seed table failed";
     return MFH_EDEVICE;
-  }
-  // w_j = 1 / ((-1)^(n-1-j) j! (n-1-j)!)
-  std::vector<uint32_t> invf(n);
-  uint32_t f = 1;
-  for (uint32_t i = 1; i < n; i++) f = mulmod_h(f, i);
-  invf[n - 1] = powmod_h(f, P32 - 2);
-  for (uint32_t i = n - 1; i > 0; i--) invf[i - 1] = mulmod_h(invf[i], i);
-  s->w.resize(n);
-  for (uint32_t j = 0; j < n; j++) {
-    const uint32_t x = mulmod_h(invf[j], invf[n - 1 - j]);
-    s->w[j] = ((n - 1 - j) & 1) && x ? P32 - x : x;
   }
   return MFH_OK;
 }
 
 int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t *d_ssp) {
   if (!c || !h_row_ptr || !d_ssp) return MFH_EINVAL;
+  if (int rc = ssp_rows_check(c, "mfh_ssp_from_rows", nrows, h_row_ptr, h_wire, h_coef)) return rc;
   const uint32_t d = c->P.d, m = c->P.m, n = d - 1;
-  if (d < 2) { c->err = "mfh_ssp_from_rows: d < 2"; return MFH_EINVAL; }
-  if (nrows > n) { c->err = "mfh_ssp_from_rows: nrows > d - 1"; return MFH_EINVAL; }
-  for (uint32_t j = 0; j < nrows; j++)
-    if (h_row_ptr[j + 1] < h_row_ptr[j]) { c->err = "mfh_ssp_from_rows: row_ptr decreases"; return MFH_EINVAL; }
-  const uint32_t e0 = h_row_ptr[0], e1 = h_row_ptr[nrows];
-  if (e1 > e0 && (!h_wire || !h_coef)) { c->err = "mfh_ssp_from_rows: entries without h_wire / h_coef"; return MFH_EINVAL; }
   std::vector<uint32_t> cnt(m, 0);
-  for (uint32_t e = e0; e < e1; e++) {
-    if (h_wire[e] >= m) { c->err = "mfh_ssp_from_rows: wire >= m"; return MFH_EINVAL; }
-    if (h_coef[e] >= P32) { c->err = "mfh_ssp_from_rows: coefficient >= p"; return MFH_EINVAL; }
+  for (uint32_t e = h_row_ptr[0]; e < h_row_ptr[nrows]; e++)
     if (h_coef[e]) cnt[h_wire[e]]++;
-  }
   HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = interp_prepare(c)) return rc;
+  const uint32_t *tpad, *w;
+  if (int rc = ssp_rows_tree(c, "mfh_ssp_from_rows", tpad, w)) return rc;
+  if (int rc = interp_prepare(c, tpad)) return rc;
   SspInterp *s = c->interp;
   cnt[0] += n - nrows;  // padding rows: v_0(r_j) = 1
 
@@ -281,12 +202,12 @@ int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, con
         if (!h_coef[e]) continue;
         const uint64_t q = pos[h_wire[e]]++;
         host[2 * q] = j;
-        host[2 * q + 1] = mulmod_h(h_coef[e], s->w[j]);
+        host[2 * q + 1] = mulp(h_coef[e], w[j]);
       }
     for (uint32_t j = nrows; j < n; j++) {
       const uint64_t q = pos[0]++;
       host[2 * q] = j;
-      host[2 * q + 1] = s->w[j];
+      host[2 * q + 1] = w[j];
     }
   }
   std::copy(parts_h.begin(), parts_h.end(), host.begin() + nz_words);
@@ -299,14 +220,14 @@ int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, con
   HIP_TRY(c, hipMemcpyAsync(s->buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   const uint2 *d_nz = (const uint2 *)s->buf;
   const uint4 *d_parts = (const uint4 *)((uint32_t *)s->buf + nz_words), *d_splits = d_parts + nparts;
-  HIP_TRY(c, hipMemcpyAsync(d_ssp, s->tpad, (size_t)d * 4, hipMemcpyDeviceToDevice, c->stream));  // slot 0 = t
-  HIP_TRY(c, hipMemsetAsync(d_ssp + (size_t)(m + 1) * d, 0, (size_t)2 * d * 4, c->stream));      // slots m + 1, m + 2
+  HIP_TRY(c, hipMemcpyAsync(d_ssp, tpad, (size_t)d * 4, hipMemcpyDeviceToDevice, c->stream));  // slot 0 = t
+  HIP_TRY(c, hipMemsetAsync(d_ssp + (size_t)(m + 1) * d, 0, (size_t)2 * d * 4, c->stream));  // slots m + 1, m + 2
   {
     Timer tm(c, 15, nnz);
     const uint32_t wg_per_part = (s->NB + IWG - 1) / IWG;
     const int vec4 = d % 4 == 0 && ((uintptr_t)d_ssp & 15) == 0;
-    hipLaunchKernelGGL(k_interp, dim3(nparts * wg_per_part), dim3(IWG), 0, c->stream, d_nz, d_parts, wg_per_part, (const uint32_t *)s->seeds, s->NB,
-                       (const uint32_t *)s->tpad, d, vec4, d_ssp, (uint32_t *)s->scratch);
+    hipLaunchKernelGGL(k_interp, dim3(nparts * wg_per_part), dim3(IWG), 0, c->stream, d_nz, d_parts, wg_per_part, (const uint32_t *)s->seeds, s->NB, tpad, d,
+                       vec4, d_ssp, (uint32_t *)s->scratch);
     if (nsplit) hipLaunchKernelGGL(k_interp_sum, dim3((d + 255) / 256, nsplit), dim3(256), 0, c->stream, d_splits, (const uint32_t *)s->scratch, d, d_ssp);
   }
   // (host holds the staged rows: the copy must have run before it goes out of scope)

@@ -26,11 +26,8 @@ using namespace mf_ntt;
 
 namespace {
 
-constexpr uint32_t P32 = kP32;
 constexpr uint32_t kLeafMax = 64;               // leaves per bottom node
 constexpr size_t kChunkBytes = (size_t)128 << 20;  // interpolation scratch per chunk of statements: 8 words per padded point and statement
-
-__device__ __forceinline__ uint32_t mulp(uint32_t a, uint32_t b) { return red_p32((uint64_t)a * b); }
 
 // the bottom nodes of the tree of t: node k = prod_{l < G} (x - r_{kG + l}) (r = 0 past n), its G low coefficients.  One thread per node.
 __global__ __launch_bounds__(64) void k_rows_tree_bottom(uint32_t n, uint32_t G, uint32_t nodes, uint32_t *__restrict__ tb) {
@@ -134,13 +131,6 @@ __global__ void k_rows_root(const uint32_t *__restrict__ root, uint32_t Np, uint
   out[(size_t)s * out_stride + k] = delta ? red_p32((uint64_t)x + mulp(delta[s], t[k])) : x;
 }
 
-uint32_t mul_h(uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % P32); }
-uint32_t pow_h(uint32_t a, uint64_t e) {
-  uint32_t r = 1;
-  for (; e; e >>= 1, a = mul_h(a, a))
-    if (e & 1) r = mul_h(r, a);
-  return r;
-}
 inline dim3 g1(uint32_t n, uint32_t y = 1) { return dim3((n + 255) / 256, y); }
 
 }  // namespace
@@ -150,7 +140,7 @@ struct RowsTree {
   uint32_t d = 0, n = 0, Np = 0, logNp = 0, G = 0, logG = 0, nlev = 0;
   uint32_t *tb = nullptr;    // bottom nodes, Np words
   uint32_t *hats = nullptr;  // level lev (L = G 2^lev): [2][3][Np] transforms of [T_L', 0] | [T_R', 0]
-  uint32_t *d_t = nullptr;   // t, d words
+  uint32_t *d_t = nullptr;   // t, d words zero-padded to a multiple of 32 (the sub-tiles of k_interp and k_seed_local, ssp_interp.hip)
   uint32_t *d_w = nullptr;   // Lagrange weights, n words
   std::vector<uint32_t> h_t, h_w;
   ~RowsTree() {
@@ -207,9 +197,10 @@ void rows_level(mfh_ctx *c, const RowsTree *T, uint32_t lev, uint32_t ns, const 
   hipLaunchKernelGGL(k_rows_level_crt, g1(Np, ns), dim3(256), 0, c->stream, (const uint32_t *)cres, nv, L, Np, P, ntt_crt_make(c, logB), nout);
 }
 
-int rows_tree_build(mfh_ctx *c) {
+int rows_tree_build(mfh_ctx *c, const char *who) {
   const uint32_t d = c->P.d;
   if (c->rows_tree && c->rows_tree->d == d) return MFH_OK;
+  if (d > (1u << 22)) { c->err = std::string(who) + ": d above 2^22 exceeds the CRT bound of the tree"; return MFH_EUNSUPPORTED; }
   RowsTree *T = new RowsTree();
   struct Guard { RowsTree *&p; ~Guard() { delete p; } } guard{T};
   T->d = d;
@@ -219,16 +210,16 @@ int rows_tree_build(mfh_ctx *c) {
   T->G = std::min(kLeafMax, T->Np);
   while ((1u << T->logG) < T->G) T->logG++;
   T->nlev = T->logNp - T->logG;
-  const uint32_t Np = T->Np, n = T->n;
+  const uint32_t Np = T->Np, n = T->n, Dp = (d + 31) & ~31u;
   if (T->nlev) {
     if (int rc = ntt_reserve(c, T->logNp)) return rc;
   }
   uint32_t *scr = nullptr;  // one operand pair's products and two level vectors
-  if (hipMalloc(&T->tb, (size_t)Np * 4) != hipSuccess || hipMalloc(&T->d_t, (size_t)d * 4) != hipSuccess || hipMalloc(&T->d_w, (size_t)n * 4) != hipSuccess ||
+  if (hipMalloc(&T->tb, (size_t)Np * 4) != hipSuccess || hipMalloc(&T->d_t, (size_t)Dp * 4) != hipSuccess || hipMalloc(&T->d_w, (size_t)n * 4) != hipSuccess ||
       (T->nlev && hipMalloc(&T->hats, (size_t)T->nlev * 6 * Np * 4) != hipSuccess) || hipMalloc(&scr, (size_t)5 * Np * 4) != hipSuccess) {
     (void)hipGetLastError();
     if (scr) hipFree(scr);
-    c->err = "mfh_ssp_set_rows: no memory for the tree of t";
+    c->err = std::string(who) + ": no memory for the tree of t";
     return MFH_ENOMEM;
   }
   struct Free { uint32_t *p; ~Free() { hipFree(p); } } fscr{scr};
@@ -241,6 +232,7 @@ int rows_tree_build(mfh_ctx *c) {
     rows_level(c, T, lev, 1, lv[cur], T->hats + (size_t)lev * 6 * Np, nullptr, cres, lv[cur ^ 1]);
     cur ^= 1;
   }
+  HIP_TRY(c, hipMemsetAsync(T->d_t, 0, (size_t)Dp * 4, c->stream));  // (the words past d stay zero)
   hipLaunchKernelGGL(k_rows_root, g1(d), dim3(256), 0, c->stream, (const uint32_t *)lv[cur], Np, n, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 1, T->d_t,
                      (size_t)0);
   T->h_t.resize(d);
@@ -248,16 +240,16 @@ int rows_tree_build(mfh_ctx *c) {
   // w_j = 1 / ((-1)^(n-1-j) j! (n-1-j)!)
   std::vector<uint32_t> invf(n);
   uint32_t f = 1;
-  for (uint32_t i = 1; i < n; i++) f = mul_h(f, i);
-  invf[n - 1] = pow_h(f, P32 - 2);
-  for (uint32_t i = n - 1; i > 0; i--) invf[i - 1] = mul_h(invf[i], i);
+  for (uint32_t i = 1; i < n; i++) f = mulp(f, i);
+  invf[n - 1] = invp(f);
+  for (uint32_t i = n - 1; i > 0; i--) invf[i - 1] = mulp(invf[i], i);
   T->h_w.resize(n);
   for (uint32_t j = 0; j < n; j++) {
-    const uint32_t x = mul_h(invf[j], invf[n - 1 - j]);
+    const uint32_t x = mulp(invf[j], invf[n - 1 - j]);
     T->h_w[j] = ((n - 1 - j) & 1) && x ? P32 - x : x;
   }
   HIP_TRY(c, hipMemcpyAsync(T->d_w, T->h_w.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "mfh_ssp_set_rows: building the tree of t failed"; return MFH_EDEVICE; }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = std::string(who) + ": building the tree of t failed"; return MFH_EDEVICE; }
   delete c->rows_tree;
   c->rows_tree = T;
   T = nullptr;
@@ -293,6 +285,32 @@ int rows_interp(mfh_ctx *c, SspRows *R, uint32_t ns, const uint8_t *d_bits, uint
 }
 
 }  // namespace
+
+int ssp_rows_check(mfh_ctx *c, const char *who, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef) {
+  const uint32_t d = c->P.d, m = c->P.m;
+  auto fail = [&](const char *what) {
+    c->err = std::string(who) + ": " + what;
+    return MFH_EINVAL;
+  };
+  if (d < 2) return fail("d < 2");
+  if (nrows > d - 1) return fail("nrows > d - 1");
+  for (uint32_t j = 0; j < nrows; j++)
+    if (h_row_ptr[j + 1] < h_row_ptr[j]) return fail("row_ptr decreases");
+  const uint32_t e0 = h_row_ptr[0], e1 = h_row_ptr[nrows];
+  if (e1 > e0 && (!h_wire || !h_coef)) return fail("entries without h_wire / h_coef");
+  for (uint32_t e = e0; e < e1; e++) {
+    if (h_wire[e] >= m) return fail("wire >= m");
+    if (h_coef[e] >= P32) return fail("coefficient >= p");
+  }
+  return MFH_OK;
+}
+
+int ssp_rows_tree(mfh_ctx *c, const char *who, const uint32_t *&d_t, const uint32_t *&h_w) {
+  if (int rc = rows_tree_build(c, who)) return rc;
+  d_t = c->rows_tree->d_t;
+  h_w = c->rows_tree->h_w.data();
+  return MFH_OK;
+}
 
 // the witness polynomials of nstmt statements in row mode (mfh_witness_poly*, the batch chain): d_w + b * w_stride = delta_b t + sum_{bit} v_i
 int ssp_rows_witness(mfh_ctx *c, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta, uint32_t *d_w, size_t w_stride) {
@@ -332,21 +350,21 @@ int ssp_rows_msg_evals(mfh_ctx *c, uint32_t s, uint32_t beta, uint32_t *d_msg_ev
     uint32_t acc = 1;
     for (uint32_t j = 0; j < n; j++) {
       pre[j] = acc;
-      acc = mul_h(acc, (uint32_t)(((uint64_t)s + P32 - (j + 2)) % P32));
+      acc = mulp(acc, (uint32_t)(((uint64_t)s + P32 - (j + 2)) % P32));
     }
-    uint32_t inv = pow_h(acc, P32 - 2);
+    uint32_t inv = invp(acc);
     for (uint32_t j = n; j-- > 0;) {
       const uint32_t x = (uint32_t)(((uint64_t)s + P32 - (j + 2)) % P32);
-      lam[j] = mul_h(mul_h(inv, pre[j]), mul_h(T->h_w[j], ts));
-      inv = mul_h(inv, x);
+      lam[j] = mulp(mulp(inv, pre[j]), mulp(T->h_w[j], ts));
+      inv = mulp(inv, x);
     }
   }
   std::vector<uint64_t> acc(m, 0);  // each term < 2^32: 2^32 terms fit
   for (uint32_t j = 0; j < R->nrows; j++)
-    for (uint32_t e = R->h_ptr[j]; e < R->h_ptr[j + 1]; e++) acc[R->h_wire[e]] += mul_h(R->h_coef[e], lam[j]);
+    for (uint32_t e = R->h_ptr[j]; e < R->h_ptr[j + 1]; e++) acc[R->h_wire[e]] += mulp(R->h_coef[e], lam[j]);
   std::vector<uint32_t> msg(m);
-  msg[0] = mul_h(ts, beta);
-  for (uint32_t r = 1; r < m; r++) msg[r] = mul_h((uint32_t)(acc[r] % P32), beta);
+  msg[0] = mulp(ts, beta);
+  for (uint32_t r = 1; r < m; r++) msg[r] = mulp((uint32_t)(acc[r] % P32), beta);
   HIP_TRY(c, hipMemcpyAsync(d_msg_evals, msg.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (msg is on this stack)
   return MFH_OK;
@@ -362,22 +380,12 @@ int mfh_ssp_set_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, cons
     ssp_rows_free(c, true);  // unregister: the registration and the tree of t
     return MFH_OK;
   }
-  const uint32_t d = c->P.d, m = c->P.m, n = d - 1;
-  // the checks of mfh_ssp_from_rows, before anything changes
-  if (d < 2) { c->err = "mfh_ssp_set_rows: d < 2"; return MFH_EINVAL; }
-  if (nrows > n) { c->err = "mfh_ssp_set_rows: nrows > d - 1"; return MFH_EINVAL; }
-  for (uint32_t j = 0; j < nrows; j++)
-    if (h_row_ptr[j + 1] < h_row_ptr[j]) { c->err = "mfh_ssp_set_rows: row_ptr decreases"; return MFH_EINVAL; }
-  const uint32_t e0 = h_row_ptr[0], e1 = h_row_ptr[nrows];
-  if (e1 > e0 && (!h_wire || !h_coef)) { c->err = "mfh_ssp_set_rows: entries without h_wire / h_coef"; return MFH_EINVAL; }
-  for (uint32_t e = e0; e < e1; e++) {
-    if (h_wire[e] >= m) { c->err = "mfh_ssp_set_rows: wire >= m"; return MFH_EINVAL; }
-    if (h_coef[e] >= P32) { c->err = "mfh_ssp_set_rows: coefficient >= p"; return MFH_EINVAL; }
-  }
-  if (lu_max >= m) { c->err = "mfh_ssp_set_rows: lu_max must be < m"; return MFH_EINVAL; }
-  if (d > (1u << 22)) { c->err = "mfh_ssp_set_rows: d above 2^22 exceeds the CRT bound of the tree"; return MFH_EUNSUPPORTED; }
+  // before anything changes
+  if (int rc = ssp_rows_check(c, "mfh_ssp_set_rows", nrows, h_row_ptr, h_wire, h_coef)) return rc;
+  const uint32_t d = c->P.d, e0 = h_row_ptr[0], e1 = h_row_ptr[nrows];
+  if (lu_max >= c->P.m) { c->err = "mfh_ssp_set_rows: lu_max must be < m"; return MFH_EINVAL; }
   HIP_TRY(c, hipSetDevice(c->device));
-  if (int rc = rows_tree_build(c)) return rc;
+  if (int rc = rows_tree_build(c, "mfh_ssp_set_rows")) return rc;
   SspRows *R = new SspRows();
   struct Guard { SspRows *p; ~Guard() { delete p; } } guard{R};
   R->nrows = nrows;

@@ -176,9 +176,10 @@ int mfh_ssp_prg_fill(mfh_ctx *ctx, uint64_t seed, size_t first_slot, size_t nslo
  * slot i + 1 = v_i, the interpolant of degree < d - 1 of its column (i = 0 .. m - 1), slots m + 1 and m + 2 = 0.
  * Bits: input (witness) bit i - 1 is wire i (mfh_witness_poly); with public inputs, bits [0, lu) -- wires 1 .. lu -- are the statement.
  * h_row_ptr: nrows + 1 entries (only [h_row_ptr[0], h_row_ptr[nrows]) of h_wire / h_coef is read); wires in [0, m), coefficients in [0, p).
- * MFH_EINVAL, with nothing written, for nrows > d - 1, a wire >= m, a coefficient >= p or a decreasing h_row_ptr.  d_ssp is written in full, derived images
- * of an earlier SSP are dropped as by mfh_ssp_upload; call mfh_ssp_prepare afterwards.  The first call of a context builds t and a table of
- * (d - 1) * ceil(d / 32) words (134 MB at d = 2^15) that it keeps; the call synchronises the context's stream. */
+ * MFH_EINVAL, with nothing written, for nrows > d - 1, a wire >= m, a coefficient >= p or a decreasing h_row_ptr; then MFH_EUNSUPPORTED for d > 2^22.
+ * d_ssp is written in full, derived images of an earlier SSP are dropped as by mfh_ssp_upload; call mfh_ssp_prepare afterwards.  Per context the call keeps
+ * a seed table of (d - 1) * ceil(d / 32) words (134 MB at d = 2^15), built on its first call, and the tree of t of mfh_ssp_set_rows (below; 7.3 MB at
+ * d = 2^15), built when the context has none; the call synchronises the context's stream. */
 int mfh_ssp_from_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t *d_ssp);
 
 /* The same constraint system registered as its ROWS (the row SSP): no dense image exists, so circuits fill any d mfh_ssp_from_rows accepts up to 2^22,

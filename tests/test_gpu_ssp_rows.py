@@ -57,6 +57,8 @@ def test_fill_equals_dense_odd_shapes(gpu_ctx_factory, mf, d, m):
         dense = ctx.to_host(ctx.ssp_from_rows(rows), np.uint32).reshape(p.m + 3, p.d)
         ctx.ssp_set_rows(rows, lu_max=2)
         assert np.array_equal(_fill_all(ctx, p), dense)
+    ctx.ssp_set_rows(None)  # frees the tree of t that ssp_from_rows shares: the next call rebuilds it
+    assert np.array_equal(ctx.to_host(ctx.ssp_from_rows(rows), np.uint32).reshape(p.m + 3, p.d), dense)
 
 
 def test_fill_default_size_sample(gpu_ctx_factory, mf):

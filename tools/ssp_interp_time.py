@@ -23,7 +23,7 @@ from c_lwe_snarks_amd import circuit  # noqa: E402
 
 HBM_SPEC_GBS, HBM_ACHIEVABLE_GBS = 8000.0, 6290.0  # MI355X HBM3E: spec, and a measured float4 copy
 VALU_LANE_OPS = 256 * 4 * 16 * 2.4e9  # CUs x SIMDs x lanes per SIMD per clock x 2.4 GHz: full-rate VALU issue
-VALU_PER_MAC = 505 / 32  # k_interp's inner loop (gfx950 ISA): 505 VALU instructions per nonzero for 32 coefficients
+VALU_PER_MAC = 378 / 32  # k_interp's inner loop (gfx950 ISA): 378 VALU instructions per nonzero for 32 coefficients
 
 
 def random_circuit(rng, npub, npriv, ngates):
