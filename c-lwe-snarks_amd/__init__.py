@@ -99,6 +99,7 @@ EXPORTS = [
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
+    "mfh_circuit_create_global",
 ]
 
 
@@ -217,6 +218,7 @@ def load_library():
         "mfh_ssp_set_rows": (i32, [vp, u32, vp, vp, vp, u32]),
         "mfh_ssp_rows_fill": (i32, [vp, sz, sz, vp]),
         "mfh_circuit_create": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
+        "mfh_circuit_create_global": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_destroy": (None, [vp]),
         "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
     }
@@ -250,11 +252,15 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-class CircuitProgram:
-    """a compiled circuit's gate program on the device (mfh_circuit): made by Context.circuit_load, used by Context.circuit_assign"""
+CIRCUIT_MAX_WIRES = 32767  # MFH_CIRCUIT_MAX_WIRES: the most wires (nin + ngates) of a program whose wire state lives in LDS
 
-    def __init__(self, ctx, nin, ngates, handle):
-        self._ctx, self.nin, self.ngates, self._h = ctx, nin, ngates, handle
+
+class CircuitProgram:
+    """a compiled circuit's gate program on the device (mfh_circuit): made by Context.circuit_load, used by Context.circuit_assign.
+    state: "lds" (mfh_circuit_create, at most CIRCUIT_MAX_WIRES wires) or "global" (mfh_circuit_create_global, wire state in device memory)"""
+
+    def __init__(self, ctx, nin, ngates, handle, state="lds"):
+        self._ctx, self.nin, self.ngates, self._h, self.state = ctx, nin, ngates, handle, state
 
     def close(self):
         if self._h:
@@ -526,15 +532,21 @@ class Context:
         self._chk(self.lib.mfh_ssp_rows_fill(self._h, first_slot, nslots, _ptr(out)))
         return out
 
-    def circuit_load(self, compiled):
-        """the gate program of circuit.Compiled on the device (mfh_circuit_create): levelised and uploaded once; close() frees it"""
+    def circuit_load(self, compiled, state="lds"):
+        """the gate program of circuit.Compiled on the device: levelised and uploaded once; close() frees it.  state: "lds" (mfh_circuit_create: the
+        wire state in LDS, at most CIRCUIT_MAX_WIRES wires), "global" (mfh_circuit_create_global: in device memory, up to m - 1 wires) or "auto"
+        (lds up to CIRCUIT_MAX_WIRES wires, else global)"""
+        if state not in ("lds", "global", "auto"):
+            raise MfhError(f"circuit_load: state must be 'lds', 'global' or 'auto', got {state!r}")
         gates = np.ascontiguousarray(compiled.gates, dtype=np.uint32).reshape(-1, 3)
         asserts = np.ascontiguousarray(compiled.asserts, dtype=np.uint32).reshape(-1, 2)
         nin = compiled.nwires - len(gates)
+        if state == "auto":
+            state = "lds" if compiled.nwires <= CIRCUIT_MAX_WIRES else "global"
+        create = self.lib.mfh_circuit_create if state == "lds" else self.lib.mfh_circuit_create_global
         h = ctypes.c_void_p()
-        self._chk(self.lib.mfh_circuit_create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data),
-                                              ctypes.byref(h)))
-        return CircuitProgram(self, nin, len(gates), h)
+        self._chk(create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data), ctypes.byref(h)))
+        return CircuitProgram(self, nin, len(gates), h, state)
 
     def circuit_assign(self, prog, bits):
         """witnesses of nb statements on the device (mfh_circuit_assign): bits = uint8 [nb, nin] of 0 / 1, public bits then private bits.

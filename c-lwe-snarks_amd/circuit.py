@@ -28,7 +28,9 @@ A circuit too large for the dense SSP (d = 2^20: about 500 000 gates) is registe
     ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)            # no dense SSP; d_ssp=None below means these rows
     ctx.ssp_prepare(None)
     crs = ctx.setup_public(None, alpha, beta, s, cc.lu, d_sk, d_err)
-    proofs = ctx.prove_batch_public(crs, None, cc.lu, [c.assign(u, x) for u, x in stmts], deltas, mags, signs)
+    prog = ctx.circuit_load(cc, state="global")        # above 32 767 wires the wire state lives in device memory
+    witness, holds = ctx.circuit_assign(prog, bits)
+    proofs = ctx.prove_batch_public(crs, None, cc.lu, witness, deltas, mags, signs)
 """
 from __future__ import annotations
 

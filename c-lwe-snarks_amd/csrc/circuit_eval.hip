@@ -7,6 +7,10 @@
 //   in:  lanes 0..31 hold 32 input bits of statements 0..31, lanes 32..63 the next 32 bits: ballot t gives wire words of input bits t and t + 32;
 //   out: lane l holds the word of wire 64 q + 1 + l: ballot((word >> j) & 1) is bits [64 q, 64 q + 64) of statement j's witness -- 8 output bytes.
 // Assertions fold into one holds word per workgroup.
+//
+// mfh_circuit_create_global makes the second kind of program: k_circuit_eval_global is the same evaluation with the wire words in device memory
+// (ctx->circ_state), one column of nw + 1 words per block of 32 statements, read and written by that block's workgroup alone -- so the workgroup barrier
+// between levels orders everything, and the wire count is bounded by m - 1 instead of the LDS.  Gate records are 16 bytes {a, b, out, op}.
 #include <algorithm>
 #include <vector>
 
@@ -18,6 +22,10 @@ constexpr uint32_t CWG = 512;        // threads per workgroup (8 waves)
 constexpr uint32_t CSTMT = 32;       // statements per workgroup (bits of a wire word)
 constexpr uint32_t CCHUNK = 8192;    // statements per launch (256 workgroups); longer calls run several chunks
 constexpr uint32_t CWORDS = MFH_CIRCUIT_MAX_WIRES + 1;  // LDS wire words: wire 0 (unused) .. MFH_CIRCUIT_MAX_WIRES
+// the device-memory kind: a chunk of statements is bounded by bytes (include/mfhip.h, mfh_circuit_assign)
+constexpr size_t GPIN_BYTES = (size_t)64 << 20;     // pinned staging per chunk: statements x (in_stride + bits_stride + 1)
+constexpr size_t GSTATE_BYTES = (size_t)256 << 20;  // wire state per chunk: blocks x column bytes (at least one column)
+constexpr uint32_t GUNROLL = 4;                     // gates in flight per thread and level
 
 // gates[g] = {a | b << 16, out | op << 16}, sorted by level; level L is gates [lp[L], lp[L + 1]).  asserts[e] = {wire, value}.
 __global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
@@ -98,59 +106,160 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ 
   if (tid < CSTMT && s0 + tid < nstmt && holds) holds[s0 + tid] = (hw >> tid) & 1;
 }
 
+// The kernel above with the wire words in device memory: st = this block's column of colw words (wire i at st[i]), gates[g] = {a, b, out, op}.
+// A column is read and written by its own workgroup only; __syncthreads() (workgroup-scope release / acquire) orders the levels.
+__global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
+                                                             const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
+                                                             uint32_t *state, size_t colw, const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt,
+                                                             uint8_t *__restrict__ out, size_t bits_stride, uint8_t *__restrict__ holds) {
+  __shared__ uint32_t hw;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
+  const uint32_t s0 = blockIdx.x * CSTMT, j = lane & 31;
+  const bool live = s0 + j < nstmt;  // the tail block: statements past nstmt read zeros and write nothing
+  uint32_t *st = state + (size_t)blockIdx.x * colw;
+  if (tid == 0) hw = ~0u;
+
+  // ---- inputs: statement rows -> wire words (wire k + 1 = input bit k)
+  const uint8_t *row = in + (size_t)(live ? s0 + j : 0) * in_stride;
+  for (uint32_t it = wave; it * 64 < nin; it += nwaves) {  // (wave-uniform trip count: every lane takes part in the ballots)
+    const uint32_t wd = 2 * it + (lane >> 5);
+    uint32_t word = 0;
+    if (live)
+      for (uint32_t u = 0; u < 4; u++) {
+        const size_t byte = (size_t)wd * 4 + u;
+        if (byte < in_stride) word |= (uint32_t)row[byte] << (8 * u);
+      }
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 32; t++) {
+      const uint64_t bm = __ballot((word >> t) & 1);
+      if (j == t) mine = lane < 32 ? (uint32_t)bm : (uint32_t)(bm >> 32);
+    }
+    const uint32_t k = wd * 32 + j;
+    if (k < nin) st[k + 1] = mine;
+  }
+  __syncthreads();
+
+  // ---- gates, level by level; GUNROLL gates per thread in flight (no gate of a level reads another's output)
+  uint32_t g1 = nlev ? lp[0] : 0;
+  for (uint32_t lv = 0; lv < nlev; lv++) {
+    const uint32_t g0 = g1;
+    g1 = lp[lv + 1];
+    for (uint32_t g = g0 + tid; g < g1; g += GUNROLL * CWG) {
+      uint4 r[GUNROLL];
+      uint32_t x[GUNROLL], y[GUNROLL];
+#pragma unroll
+      for (uint32_t u = 0; u < GUNROLL; u++)
+        if (g + u * CWG < g1) r[u] = gates[g + u * CWG];
+#pragma unroll
+      for (uint32_t u = 0; u < GUNROLL; u++)
+        if (g + u * CWG < g1) { x[u] = st[r[u].x]; y[u] = st[r[u].y]; }
+#pragma unroll
+      for (uint32_t u = 0; u < GUNROLL; u++)
+        if (g + u * CWG < g1) {
+          const uint32_t op = r[u].w;
+          st[r[u].z] = op == MFH_GATE_XOR ? x[u] ^ y[u] : op == MFH_GATE_AND ? x[u] & y[u] : op == MFH_GATE_OR ? x[u] | y[u] : ~x[u];
+        }
+    }
+    __syncthreads();
+  }
+
+  // ---- assertions
+  uint32_t ok = ~0u;
+  for (uint32_t e = tid; e < nasserts; e += CWG) {
+    const uint2 a = asserts[e];
+    ok &= a.y ? st[a.x] : ~st[a.x];
+  }
+  if (ok != ~0u) atomicAnd(&hw, ok);
+
+  // ---- outputs: wire words -> statement rows, 8 bytes per statement and group of 64 wires; bytes [0, bits_stride) all written
+  const uint32_t nq = (uint32_t)((bits_stride + 7) / 8);
+  for (uint32_t q = wave; q < nq; q += nwaves) {
+    const uint32_t i = q * 64 + 1 + lane;
+    const uint32_t word = i <= nw ? st[i] : 0;
+    uint64_t mine = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 32; t++) {
+      const uint64_t bm = __ballot((word >> t) & 1);
+      if (lane == t) mine = bm;
+    }
+    if (lane < 32 && live) {
+      uint8_t *dst = out + (size_t)(s0 + lane) * bits_stride + (size_t)q * 8;
+      const size_t left = bits_stride - (size_t)q * 8;
+      if (left >= 8 && ((uintptr_t)dst & 7) == 0) {
+        *reinterpret_cast<uint64_t *>(dst) = mine;
+      } else {
+        for (uint32_t u = 0; u < 8 && u < left; u++) dst[u] = (uint8_t)(mine >> (8 * u));
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < CSTMT && s0 + tid < nstmt && holds) holds[s0 + tid] = (hw >> tid) & 1;
+}
+
 }  // namespace
 
 struct mfh_circuit {
   int device = 0;
+  bool global = false;  // false: mfh_circuit_create (k_circuit_eval, LDS); true: mfh_circuit_create_global (k_circuit_eval_global, ctx->circ_state)
   uint32_t nin = 0, ngates = 0, nasserts = 0, nlev = 0;
-  void *mem = nullptr;  // gates (uint2, by level) | asserts (uint2) | level_ptr (nlev + 1 words)
-  const uint2 *gates = nullptr, *asserts = nullptr;
+  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | level_ptr (nlev + 1 words)
+  const void *gates = nullptr;
+  const uint2 *asserts = nullptr;
   const uint32_t *lp = nullptr;
 };
 
-extern "C" {
+namespace {
 
-int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                       mfh_circuit **out) {
+// both kinds: validate, level, sort by level, upload.  LDS records {a | b << 16, out | op << 16}; global records {a, b, out, op}.
+int circuit_create(mfh_ctx *ctx, bool global, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                   mfh_circuit **out) {
   if (!ctx || !out) return MFH_EINVAL;
   *out = nullptr;
-  if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = "mfh_circuit_create: gates / assertions without their array"; return MFH_EINVAL; }
+  const std::string fn = global ? "mfh_circuit_create_global: " : "mfh_circuit_create: ";
+  if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = fn + "gates / assertions without their array"; return MFH_EINVAL; }
   const uint64_t nw = (uint64_t)nin + ngates;
-  if (nw > ctx->P.m - 1) { ctx->err = "mfh_circuit_create: nin + ngates > m - 1"; return MFH_EINVAL; }
-  if (nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = "mfh_circuit_create: nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
+  if (nw > ctx->P.m - 1) { ctx->err = fn + "nin + ngates > m - 1"; return MFH_EINVAL; }
+  if (!global && nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = fn + "nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
   std::vector<uint32_t> lvl(nw + 1, 0);
   uint32_t nlev = 0;
   for (uint32_t g = 0; g < ngates; g++) {
     const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = h_gates[3 * g + 2], o = nin + 1 + g;
-    if (op > MFH_GATE_NOT) { ctx->err = "mfh_circuit_create: unknown gate op"; return MFH_EINVAL; }
-    if (a == 0 || a >= o || b == 0 || b >= o) { ctx->err = "mfh_circuit_create: a gate operand is 0 or not below the gate's output wire"; return MFH_EINVAL; }
+    if (op > MFH_GATE_NOT) { ctx->err = fn + "unknown gate op"; return MFH_EINVAL; }
+    if (a == 0 || a >= o || b == 0 || b >= o) { ctx->err = fn + "a gate operand is 0 or not below the gate's output wire"; return MFH_EINVAL; }
     lvl[o] = 1 + std::max(lvl[a], op == MFH_GATE_NOT ? lvl[a] : lvl[b]);
     nlev = std::max(nlev, lvl[o]);
   }
   for (uint32_t e = 0; e < nasserts; e++) {
     const uint32_t w = h_asserts[2 * e], v = h_asserts[2 * e + 1];
-    if (w == 0 || w > nw) { ctx->err = "mfh_circuit_create: an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
-    if (v > 1) { ctx->err = "mfh_circuit_create: an assertion value other than 0 / 1"; return MFH_EINVAL; }
+    if (w == 0 || w > nw) { ctx->err = fn + "an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
+    if (v > 1) { ctx->err = fn + "an assertion value other than 0 / 1"; return MFH_EINVAL; }
   }
   // counting sort by level (stable: creation order within a level)
   std::vector<uint32_t> lp(nlev + 1, 0);
   for (uint32_t g = 0; g < ngates; g++) lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
   for (uint32_t L = 0, acc = 0; L <= nlev; L++) { const uint32_t n = L < nlev ? lp[L + 1] : 0; lp[L] = acc; acc += n; }  // ... then lp[L] = first gate of level L + 1
-  std::vector<uint32_t> host((size_t)2 * ngates + 2 * nasserts + nlev + 1);
+  const size_t rec = global ? 4 : 2;  // words per gate record
+  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + nlev + 1);
   {
     std::vector<uint32_t> pos(lp.begin(), lp.end());
     for (uint32_t g = 0; g < ngates; g++) {
       const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = op == MFH_GATE_NOT ? a : h_gates[3 * g + 2], o = nin + 1 + g;
-      const uint32_t q = pos[lvl[o] - 1]++;
-      host[2 * q] = a | b << 16;
-      host[2 * q + 1] = o | op << 16;
+      uint32_t *r = &host[rec * pos[lvl[o] - 1]++];
+      if (global) {
+        r[0] = a; r[1] = b; r[2] = o; r[3] = op;
+      } else {
+        r[0] = a | b << 16;
+        r[1] = o | op << 16;
+      }
     }
-    std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + 2 * ngates);
-    std::copy(lp.begin(), lp.end(), host.begin() + 2 * ngates + 2 * nasserts);
+    std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + rec * ngates);
+    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   mfh_circuit *c = new mfh_circuit();
   c->device = ctx->device;
+  c->global = global;
   c->nin = nin;
   c->ngates = ngates;
   c->nasserts = nasserts;
@@ -158,20 +267,34 @@ int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32
   if (hipMalloc(&c->mem, host.size() * 4) != hipSuccess) {
     (void)hipGetLastError();
     delete c;
-    ctx->err = "mfh_circuit_create: no memory for the gate program";
+    ctx->err = fn + "no memory for the gate program";
     return MFH_ENOMEM;
   }
   if (hipMemcpy(c->mem, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     hipFree(c->mem);
     delete c;
-    ctx->err = "mfh_circuit_create: upload failed";
+    ctx->err = fn + "upload failed";
     return MFH_EDEVICE;
   }
-  c->gates = (const uint2 *)c->mem;
-  c->asserts = c->gates + ngates;
+  c->gates = c->mem;
+  c->asserts = (const uint2 *)((const uint32_t *)c->mem + rec * ngates);
   c->lp = (const uint32_t *)(c->asserts + nasserts);
   *out = c;
   return MFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                       mfh_circuit **out) {
+  return circuit_create(ctx, false, nin, ngates, h_gates, nasserts, h_asserts, out);
+}
+
+int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                              mfh_circuit **out) {
+  return circuit_create(ctx, true, nin, ngates, h_gates, nasserts, h_asserts, out);
 }
 
 void mfh_circuit_destroy(mfh_circuit *c) {
@@ -191,9 +314,18 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
   if (!nstmt) return MFH_OK;
   if ((in_stride && !h_inputs) || (bits_stride && !h_witness_bits)) { ctx->err = "mfh_circuit_assign: null row buffer"; return MFH_EINVAL; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const uint32_t ch = std::min(nstmt, CCHUNK);
+  // statements per launch: the LDS kind CCHUNK; the global kind as many whole blocks as GPIN_BYTES of staging and GSTATE_BYTES of wire state hold (>= 1 block)
+  const size_t colw = (nw + 1 + 31) & ~(size_t)31;  // global kind: words per block's column (128-byte aligned columns)
+  uint32_t ch = std::min(nstmt, CCHUNK);
+  if (c->global) {
+    const size_t by_pin = GPIN_BYTES / (in_stride + bits_stride + 1) / CSTMT, by_state = GSTATE_BYTES / (colw * 4);
+    const size_t blocks = std::max<size_t>(1, std::min(by_pin, by_state));
+    ch = (uint32_t)std::min<size_t>(nstmt, blocks * CSTMT);
+  }
   const size_t in_b = (size_t)ch * in_stride, out_b = (size_t)ch * bits_stride, io_b = in_b + out_b + ch;
   if (int rc = buf_reserve(ctx, ctx->circ_io, ctx->circ_io_bytes, io_b)) return rc;
+  if (c->global)
+    if (int rc = buf_reserve(ctx, ctx->circ_state, ctx->circ_state_bytes, (size_t)(ch + CSTMT - 1) / CSTMT * colw * 4)) return rc;
   uint8_t *pin_in = in_b ? (uint8_t *)pin_acquire(ctx, ctx->pin_rows, in_b) : nullptr;
   uint8_t *pin_out = (uint8_t *)pin_acquire(ctx, ctx->pin_cw, out_b + ch);
   if ((in_b && !pin_in) || !pin_out) return MFH_ENOMEM;
@@ -205,10 +337,15 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
       memcpy(pin_in, h_inputs + (size_t)b0 * in_stride, (size_t)n * in_stride);
       if (hipMemcpyAsync(d_in, pin_in, (size_t)n * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
     }
-    {
+    if (c->global) {
+      Timer tm(ctx, 17, n);
+      hipLaunchKernelGGL(k_circuit_eval_global, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                         c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
+                         d_holds);
+    } else {
       Timer tm(ctx, 16, n);
-      hipLaunchKernelGGL(k_circuit_eval, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
-                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds);
+      hipLaunchKernelGGL(k_circuit_eval, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, (const uint2 *)c->gates, c->lp, c->nlev, c->asserts,
+                         c->nasserts, c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds);
     }
     if (hipGetLastError() != hipSuccess) { rc = MFH_EDEVICE; break; }
     if (hipMemcpyAsync(pin_out, d_out, (size_t)n * bits_stride, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

@@ -100,6 +100,8 @@ struct mfh_ctx {
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
   void *circ_io = nullptr;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
   size_t circ_io_bytes = 0;
+  void *circ_state = nullptr;  // mfh_circuit_assign of a mfh_circuit_create_global program: the wire words of one chunk, one column per 32 statements
+  size_t circ_state_bytes = 0;
   void *d_batch = nullptr;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
   size_t batch_bytes = 0;
   // mfh_prove_batch, more than one group of proofs and no image registered: the CRS is expanded ONCE PER CALL into this scratch in

@@ -1149,6 +1149,7 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   if (c->d_batch) hipFree(c->d_batch);
   if (c->batch_img) hipFree(c->batch_img);
   if (c->circ_io) hipFree(c->circ_io);
+  if (c->circ_state) hipFree(c->circ_state);
   if (c->ssp_frag) hipFree(c->ssp_frag);
   if (c->d_t0) hipFree(c->d_t0);
   for (auto &t : c->timed) { hipEventDestroy(t.e0); hipEventDestroy(t.e1); }
@@ -1270,6 +1271,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "mmstream_bw_persistent")) return 114;      // ... and of "mmstream_bw" (k_mmstream_pb)
   if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
   if (!strcmp(which, "circuit_assign")) return 16;  // k_circuit_eval of mfh_circuit_assign
+  if (!strcmp(which, "circuit_assign_global")) return 17;  // k_circuit_eval_global of mfh_circuit_assign (mfh_circuit_create_global programs)
   return -1;
 }
 

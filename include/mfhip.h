@@ -217,10 +217,21 @@ int mfh_ssp_rows_fill(mfh_ctx *ctx, size_t first_slot, size_t nslots, uint32_t *
 typedef struct mfh_circuit mfh_circuit;
 int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                        mfh_circuit **out);
+/* The same program with its wire state in device memory, for circuits above MFH_CIRCUIT_MAX_WIRES.  Same arguments, records and validation as
+ * mfh_circuit_create (the same MFH_EINVAL cases and texts, named after this function) except the LDS bound: the limit is nin + ngates <= m - 1 alone
+ * (699 049 wires at d = 2^20, m = 699 050; gate records are 16 bytes with 32-bit wire numbers, 7.5 MB for 470 000 gates).  mfh_circuit_assign evaluates it
+ * with one column of (nin + ngates + 1) words, rounded up to 32, per block of 32 statements in a context buffer reused across calls: one launch per
+ * chunk of statements whatever the circuit's depth; a chunk is the most whole blocks whose staging, chunk x (in_stride + bits_stride + 1) bytes, fits
+ * 64 MiB and whose columns fit 256 MiB, at least one block (736 statements at d = 2^20 with 2 508-byte input rows).  Witness rows and holds are byte for
+ * byte those of a mfh_circuit_create program of the same circuit.  Kernel timing kind "circuit_assign_global". */
+int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                              mfh_circuit **out);
+/* either kind of program */
 void mfh_circuit_destroy(mfh_circuit *c);
 /* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
  * (bits_stride bytes) becomes the witness bit string of statement b: bit i - 1 = wire i, bits >= nin + ngates zero -- the layout mfh_prove_batch reads.
- * h_holds[b] = 1 if every assertion holds on statement b, else 0.  Bitsliced: one workgroup serves 32 statements, one LDS word per wire.
+ * h_holds[b] = 1 if every assertion holds on statement b, else 0.  Bitsliced: one workgroup serves 32 statements, one word per wire (in LDS for a
+ * mfh_circuit_create program, in device memory for a mfh_circuit_create_global one).
  * MFH_EINVAL for in_stride * 8 < nin or bits_stride * 8 < nin + ngates; nstmt = 0 does nothing.  Staged through the context's pinned buffers
  * (mfh_scrub_staging zeroes them); the call synchronises the context's stream. */
 int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const uint8_t *h_inputs, size_t in_stride, uint8_t *h_witness_bits,
@@ -480,7 +491,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two

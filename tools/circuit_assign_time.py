@@ -1,17 +1,23 @@
-"""Same-box timing of Context.circuit_assign (mfh_circuit_assign) against Circuit.assign, default size (D = 2^15, M = 21 845).
-The circuit is the one of test_default_size_circuit_batch: 16 public inputs, 3 000 private inputs and 13 500 random AND / OR / XOR / NOT gates.
-Printed (one JSON line, also written to --out):
+"""Same-box timing of Context.circuit_assign (mfh_circuit_assign) against Circuit.assign.
+Legs (--leg, default all):
+  * default: D = 2^15, M = 21 845, the circuit of test_default_size_circuit_batch (16 public inputs, 3 000 private inputs, 13 500 random AND / OR /
+    XOR / NOT gates), LDS program (mfh_circuit_create), --nb statements;
+  * 2p20: D = 2^20, M = 699 050, the circuit of test_two_pow_20_circuit_proved_and_verified (64 public, 20 000 private inputs, 470 000 random gates),
+    device-memory program (circuit_load(state="global"), mfh_circuit_create_global), 255 and 1 020 statements;
+  * chain: a 60 000-gate XOR / NOT chain (depth 60 000) on 40 000 inputs, global program, 100 statements: its time and launch count.
+Printed per leg (one JSON line each, also appended to --out):
   * load: circuit_load once (levelising on the host, the upload);
-  * call: the median wall time of circuit_assign for --nb statements (packing the input bits, staging, the launch, the copies back; the call synchronises);
-  * kernel: k_circuit_eval alone (HIP events of mfh_set_timing, kind "circuit_assign");
-  * python: Circuit.assign for --py statements, scaled to --nb (the rows are checked equal).
-dev tool.  usage: python tools/circuit_assign_time.py [--nb 1020] [--reps 7] [--py 1020] [--out FILE]"""
+  * call: the median wall time of circuit_assign (packing the input bits, staging, the launches, the copies back; the call synchronises);
+  * kernel: the kernel launches alone (HIP events of mfh_set_timing, kind "circuit_assign" / "circuit_assign_global"), summed over a call's chunks;
+  * python: Circuit.assign for --py statements (--py2 at 2^20), scaled to the batch (the rows are checked equal).
+dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain] [--nb 1020] [--reps 7] [--py 1020] [--py2 4] [--out FILE]"""
 import argparse
 import json
 import os
 import statistics
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -32,13 +38,38 @@ def random_circuit(rng, npub, npriv, ngates):
     return c
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--nb", type=int, default=1020)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+def _time_calls(ctx, prog, bits, reps, kind):
+    ctx.circuit_assign(prog, bits)  # first call: staging buffers
+    call, kern, launches = [], [], 0
+    ctx.set_timing(True)
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        witness, holds = ctx.circuit_assign(prog, bits)
+        call.append((time.perf_counter() - t0) * 1e3)
+        n, tot, _ = ctx.timing_drain(kind)
+        kern.append(tot)
+        launches = n
+    ctx.set_timing(False)
+    return witness, holds, call, kern, launches
+
+
+def _depth(cc):
+    lvl = np.zeros(cc.nwires + 1, dtype=np.int64)
+    nin = cc.nwires - len(cc.gates)
+    for g, (op, x, y) in enumerate(cc.gates.tolist()):
+        lvl[nin + 1 + g] = 1 + max(lvl[x], lvl[y])
+    return int(lvl.max())
+
+
+def _emit(res, out):
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as f:
+            f.write(line + "\n")
+
+
+def leg_default(a):
     p = mf.DEFAULT
     npub, npriv, ngates = 16, 3000, 13500
     rng = np.random.default_rng(55)
@@ -50,39 +81,98 @@ def main():
     t0 = time.perf_counter()
     prog = ctx.circuit_load(cc)
     load_ms = (time.perf_counter() - t0) * 1e3
-    ctx.circuit_assign(prog, bits)  # first call: staging buffers
-    call, kern = [], []
-    ctx.set_timing(True)
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        witness, holds = ctx.circuit_assign(prog, bits)
-        call.append((time.perf_counter() - t0) * 1e3)
-        n, tot, _ = ctx.timing_drain("circuit_assign")
-        kern.append(tot)
-    ctx.set_timing(False)
+    witness, holds, call, kern, _ = _time_calls(ctx, prog, bits, a.reps, "circuit_assign")
     npy = min(a.py, a.nb)
     t0 = time.perf_counter()
     ref = [c.assign(bits[b, :npub].tolist(), bits[b, npub:].tolist()) for b in range(npy)]
     py_ms = (time.perf_counter() - t0) * 1e3 / npy
     same = all(witness[b].tobytes() == ref[b] for b in range(npy))
-    lvl = np.zeros(cc.nwires + 1, dtype=np.int64)
-    nin = cc.nwires - len(cc.gates)
-    for g, (op, x, y) in enumerate(cc.gates.tolist()):
-        lvl[nin + 1 + g] = 1 + max(lvl[x], lvl[y])
-    depth = int(lvl.max())
-    res = {"tool": "circuit_assign_time", "d": p.d, "m": p.m, "nb": a.nb, "npub": npub, "npriv": npriv, "ngates": ngates, "depth": depth,
+    res = {"tool": "circuit_assign_time", "d": p.d, "m": p.m, "nb": a.nb, "npub": npub, "npriv": npriv, "ngates": ngates, "depth": _depth(cc),
            "load_ms": round(load_ms, 3), "call_ms": round(statistics.median(call), 3), "call_ms_all": [round(x, 3) for x in call],
            "kernel_ms": round(statistics.median(kern), 3), "kernel_ms_all": [round(x, 3) for x in kern],
            "python_ms_per_statement": round(py_ms, 3), "python_statements_timed": npy, "python_ms_for_nb": round(py_ms * a.nb, 1),
            "python_over_call": round(py_ms * a.nb / statistics.median(call), 1), "rows_equal": bool(same), "holds_all": bool(holds.all())}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "a") as f:
-            f.write(line + "\n")
+    _emit(res, a.out)
     prog.close()
     ctx.close()
-    return 0 if same else 1
+    return same
+
+
+def leg_2p20(a):
+    p = mf.Params(d=1 << 20, m=699050)
+    npub, npriv, ngates = 64, 20000, 470000
+    rng = np.random.default_rng(2021)
+    c = random_circuit(rng, npub, npriv, ngates)
+    cc = c.compile(p)
+    depth = _depth(cc)
+    ctx = mf.Context(p, 0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    prog = ctx.circuit_load(cc, state="global")
+    load_ms = (time.perf_counter() - t0) * 1e3
+    ok = True
+    for nb in (255, 1020):
+        bits = rng.integers(0, 2, size=(nb, npub + npriv), dtype=np.uint8)
+        witness, holds, call, kern, launches = _time_calls(ctx, prog, bits, a.reps, "circuit_assign_global")
+        npy = min(a.py2, nb)
+        t0 = time.perf_counter()
+        ref = [c.assign(bits[b, :npub].tolist(), bits[b, npub:].tolist()) for b in range(npy)]
+        py_ms = (time.perf_counter() - t0) * 1e3 / npy
+        same = all(witness[b].tobytes() == ref[b] for b in range(npy))
+        ok = ok and same
+        res = {"tool": "circuit_assign_time", "leg": "2p20", "state": prog.state, "d": p.d, "m": p.m, "nb": nb, "npub": npub, "npriv": npriv,
+               "ngates": ngates, "depth": depth, "load_ms": round(load_ms, 3), "launches_per_call": launches,
+               "call_ms": round(statistics.median(call), 3), "call_ms_all": [round(x, 3) for x in call],
+               "kernel_ms": round(statistics.median(kern), 3), "kernel_ms_all": [round(x, 3) for x in kern],
+               "python_ms_per_statement": round(py_ms, 3), "python_statements_timed": npy, "python_ms_for_nb": round(py_ms * nb, 1),
+               "python_over_call": round(py_ms * nb / statistics.median(call), 1), "rows_equal": bool(same)}
+        _emit(res, a.out)
+    prog.close()
+    ctx.close()
+    return ok
+
+
+def leg_chain(a):
+    nin, ngates, nb = 40000, 60000, 100
+    p = mf.Params(d=256, m=nin + ngates + 1)
+    k = np.arange(ngates, dtype=np.int64)
+    prev = np.where(k == 0, 1, nin + k)
+    nots = k % 5 == 4
+    gates = np.stack([np.where(nots, 3, 0), prev, np.where(nots, prev, 1 + (k + 1) % nin)], axis=1).astype(np.uint32)
+    desc = SimpleNamespace(gates=gates, asserts=np.array([[nin + ngates, 1]], dtype=np.uint32), nwires=nin + ngates)
+    bits = np.random.default_rng(60).integers(0, 2, size=(nb, nin), dtype=np.uint8)
+    ctx = mf.Context(p, 0)
+    t0 = time.perf_counter()
+    prog = ctx.circuit_load(desc, state="global")
+    load_ms = (time.perf_counter() - t0) * 1e3
+    witness, holds, call, kern, launches = _time_calls(ctx, prog, bits, a.reps, "circuit_assign_global")
+    xs = np.where(nots[None, :], 0, bits[:, (k + 1) % nin])
+    last = bits[:, 0] ^ np.bitwise_xor.reduce(xs, axis=1) ^ (int(nots.sum()) & 1)
+    same = bool(np.array_equal(holds, last == 1))
+    res = {"tool": "circuit_assign_time", "leg": "chain", "state": prog.state, "d": p.d, "m": p.m, "nb": nb, "nin": nin, "ngates": ngates,
+           "depth": ngates, "load_ms": round(load_ms, 3), "launches_per_call": launches, "call_ms": round(statistics.median(call), 3),
+           "call_ms_all": [round(x, 3) for x in call], "kernel_ms": round(statistics.median(kern), 3), "kernel_ms_all": [round(x, 3) for x in kern],
+           "kernel_us_per_level": round(statistics.median(kern) * 1e3 / ngates, 3), "last_gate_equal": same}
+    _emit(res, a.out)
+    prog.close()
+    ctx.close()
+    return same
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain"])
+    ap.add_argument("--nb", type=int, default=1020)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign (default leg)")
+    ap.add_argument("--py2", type=int, default=4, help="statements timed through Circuit.assign (2p20 leg)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    ok = True
+    for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20)):
+        if a.leg in ("all", name):
+            ok = fn(a) and ok
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
