@@ -4,8 +4,8 @@
     child process, `force_collectives=True`: librccl is loaded, a communicator is created on the MI355X and int64 device tensors go
     through all_reduce, all_to_all_single (split lists) and reduce_scatter_tensor; proofs must equal mfh_prove / mfh_prove_batch bit
     for bit (which test_gpu_batch_sizes.py pins to the oracle).  Reference loops that shard: src/snark.c:147-155, :157-174.
-  * `python bench.py --gpus 2` with no launcher starts its own two ranks (here both on the one GPU, gloo host-staged collectives) and
-    prints ONE JSON line with n_gpus = 2; a rank-count mismatch under an external launcher is an error, not a note.
+  * `python bench.py --gpus 2 --full` with no launcher starts its own two ranks (here both on the one GPU, gloo host-staged collectives),
+    runs the row-sharded legs and prints ONE JSON line with n_gpus = 2; a rank-count mismatch under an external launcher is an error, not a note.
 """
 import json
 import os
@@ -44,9 +44,9 @@ def test_sharded_sequences_under_one_rank_rccl(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_starts_its_own_ranks(tmp_path):
-    """plain `python bench.py --gpus 2`: the parent only spawns, two fresh ranks share cuda:0 (gloo rehearsal backend)"""
+    """`python bench.py --gpus 2 --full` without a launcher: the parent only spawns, two fresh ranks share cuda:0 (gloo rehearsal backend)"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "62", "--sharded-batch", "62",
-                        "--no-resident", "--no-cpu-baseline"], env=_clean_env(MFUOCO_DIST_BACKEND="gloo", MFUOCO_SHARE_GPU="1"),
+                        "--full", "--no-resident", "--no-cpu-baseline"], env=_clean_env(MFUOCO_DIST_BACKEND="gloo", MFUOCO_SHARE_GPU="1"),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
