@@ -1,6 +1,7 @@
 """Boolean circuits as square span programs: the front end of mfh_ssp_from_rows (include/mfhip.h).
 
-A circuit is built from public and private input wires and AND / OR / XOR / NOT gates, with assertions that a wire is 0 or 1.  compile(params) turns it
+A circuit is built from public and private input wires and gates -- AND / OR / XOR / NOT, MAJ and its paired SUM3 (full_add), any two-input function
+(gate, NAND, NOR, XNOR, ANDN, ORN) and constants (const) -- with assertions that a wire is 0 or 1 and that two wires are equal.  compile(params) turns it
 into constraint rows, one row per constraint point r_j = j + 2.  Row j asks  v_0(r_j) + sum_i a_i v_i(r_j)  in {-1, +1}, where a_i is the bit on wire i.
 Context.ssp_from_rows interpolates the rows into the SSP on the device.
 
@@ -10,7 +11,16 @@ in creation order.  Witness bit i - 1 is wire i, so bits [0, lu) are the public 
 Rows, all values mod p: every wire w gets 2w - 1 (it is 0 or 1).  Then each gate and each assertion gets one row:
     c = a XOR b : a + b + c - 1          c = a AND b : 2a + 2b - 4c - 1          c = a OR b : -2a - 2b + 4c - 1
     c = NOT a   : a + c                  assert a = 1 : a                         assert a = 0 : 1 - a
-Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py checks all eight (a, b, c)).
+    k = MAJ(a, b, c)  : 2a + 2b + 2c - 4k - 1           s = SUM3(a, b, c) : 1 - a - b - c + 2k - s  (k = the MAJ gate just before, same operands)
+    c = CONST0 : 1 - c                   c = CONST1 : c                           assert_same(a, b) : 1 - a - b  (no wire)
+    c = LUT2(tt)(a, b) = (tt >> (a + 2b)) & 1, by the class of tt:
+        tt = 0 : 1 - c      tt = 15 : c      c = a : 1 - a - c      c = NOT a : a + c      c = b : 1 - b - c      c = NOT b : b + c
+        XOR (6) : a + b + c - 1      XNOR (9) : a + b - c
+        one 1, at (x, y)    : 2a' + 2b' - 4c - 1      (a' = a if x = 1 else 1 - a; b' likewise from y)
+        three 1s, 0 at (x, y): 2a' + 2b' + 4c - 5
+Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py checks all eight (a, b, c) of the first four gates,
+tests/test_circuit_gates_cpu.py every other row over all its inputs).  SUM3 is sound only because MAJ's row forces k, which is why full_add emits the
+two back to back.  Row order: the bit rows, one row per gate in creation order, the value assertions, then the equalities in creation order.
 
     c = Circuit()
     x = c.private(8); z = c.public()
@@ -42,7 +52,55 @@ P = 0xFFFFFFFB  # GAMMA_P
 _M1 = P - 1  # -1 mod p
 # gate ops of Compiled.gates: MFH_GATE_* of include/mfhip.h (mfh_circuit_create)
 GATE_XOR, GATE_AND, GATE_OR, GATE_NOT = 0, 1, 2, 3
-_OPS = {"xor": GATE_XOR, "and": GATE_AND, "or": GATE_OR, "not": GATE_NOT}
+# ... and of Compiled.program (mfh_circuit_create_ex)
+GATE_MAJ, GATE_SUM3, GATE_CONST0, GATE_CONST1 = 4, 5, 6, 7
+
+
+def GATE_LUT2(tt):
+    return 16 + tt
+
+
+_OPS = {"xor": GATE_XOR, "and": GATE_AND, "or": GATE_OR, "not": GATE_NOT, "maj": GATE_MAJ, "sum3": GATE_SUM3}
+# truth tables of the named two-input gates: bit (a + 2b) is the output on (a, b)
+TT_NAND, TT_NOR, TT_XNOR, TT_ANDN, TT_ORN = 0b0111, 0b0001, 0b1001, 0b0010, 0b1011  # ANDN = a AND NOT b, ORN = a OR NOT b
+
+
+def lut2_row(tt, a, b, c):
+    """the constraint row of c = LUT2(tt)(a, b) on SSP wires a, b, c: ([(wire, coef mod p)], constant mod p)"""
+    ones = [(x, y) for y in (0, 1) for x in (0, 1) if (tt >> (x + 2 * y)) & 1]
+    if tt == 0:
+        return [(c, -1)], 1
+    if tt == 15:
+        return [(c, 1)], 0
+    if tt == 0b1010:  # c = a
+        return [(a, -1), (c, -1)], 1
+    if tt == 0b0101:  # c = NOT a
+        return [(a, 1), (c, 1)], 0
+    if tt == 0b1100:  # c = b
+        return [(b, -1), (c, -1)], 1
+    if tt == 0b0011:  # c = NOT b
+        return [(b, 1), (c, 1)], 0
+    if tt == 0b0110:
+        return [(a, 1), (b, 1), (c, 1)], -1
+    if tt == 0b1001:
+        return [(a, 1), (b, 1), (c, -1)], 0
+    if len(ones) == 1:
+        (x, y), sign, const = ones[0], -4, -1
+    else:
+        assert len(ones) == 3
+        (x, y), = [(x, y) for y in (0, 1) for x in (0, 1) if not (tt >> (x + 2 * y)) & 1]
+        sign, const = 4, -5
+    # 2a' = 2a (x = 1) or 2 - 2a (x = 0)
+    const += (0 if x else 2) + (0 if y else 2)
+    return [(a, 2 if x else -2), (b, 2 if y else -2), (c, sign)], const
+
+
+def _modrow(terms, const):
+    """a row of (wire, coef) with coefficients mod p, the constant as wire 0 (omitted when 0)"""
+    row = [(w, x % P) for w, x in terms]
+    if const % P:
+        row.append((0, const % P))
+    return row
 
 
 class CircuitError(ValueError):
@@ -67,6 +125,10 @@ class Compiled:
     # len(gates)), operands in [1, nin + g], b = a for NOT; asserts[e] = (wire, value)
     gates: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), dtype=np.uint32), compare=False)
     asserts: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
+    # the same program with three operands (mfh_circuit_create_ex): program[g] = (op, a, b, c), c = 0 but for MAJ / SUM3, a = b = c = 0 for CONST;
+    # gates = program[:, :3].  equal[e] = (a, b): the wires of assert_same, in creation order
+    program: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), dtype=np.uint32), compare=False)
+    equal: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
 
     def wire(self, w: Wire) -> int:
         return self.wires[w.node]
@@ -74,8 +136,10 @@ class Compiled:
 
 class Circuit:
     def __init__(self):
-        self._nodes = []    # ("pub",) / ("priv",) / (gate, a, b) / ("not", a): operands are node indices
+        self._nodes = []    # ("pub",) / ("priv",) / (gate, a, b) / ("not", a) / ("maj" | "sum3", a, b, c) / ("lut", tt, a, b) / ("const", v): operands are node indices
         self._asserts = []  # (node, value)
+        self._equal = []    # (node, node) of assert_same
+        self._const = {}    # value -> node of the shared constant wire
         self._pub = []      # node indices of the public inputs, in declaration order
         self._priv = []
         self._params = None
@@ -119,6 +183,59 @@ class Circuit:
     def NOT(self, a: Wire) -> Wire:
         return self._new("not", a)
 
+    def MAJ(self, a: Wire, b: Wire, c: Wire) -> Wire:
+        """1 iff at least two of a, b, c are 1"""
+        return self._new("maj", a, b, c)
+
+    def full_add(self, a: Wire, b: Wire, c: Wire):
+        """(sum, carry) of a + b + c: a MAJ gate (the carry) and its SUM3 gate, back to back -- 2 wires, 4 rows"""
+        k = self.MAJ(a, b, c)
+        s = self._new("sum3", a, b, c)
+        return s, k
+
+    def gate(self, tt: int, a: Wire, b: Wire) -> Wire:
+        """any two-input function: the output on (a, b) is bit (a + 2b) of the truth table tt in [0, 16)"""
+        if not isinstance(tt, int) or not 0 <= tt < 16:
+            raise CircuitError("gate: the truth table must be an integer in [0, 16)")
+        for w in (a, b):
+            self._check(w)
+        self._nodes.append(("lut", tt, a.node, b.node))
+        return Wire(len(self._nodes) - 1)
+
+    def NAND(self, a: Wire, b: Wire) -> Wire:
+        return self.gate(TT_NAND, a, b)
+
+    def NOR(self, a: Wire, b: Wire) -> Wire:
+        return self.gate(TT_NOR, a, b)
+
+    def XNOR(self, a: Wire, b: Wire) -> Wire:
+        return self.gate(TT_XNOR, a, b)
+
+    def ANDN(self, a: Wire, b: Wire) -> Wire:
+        """a AND NOT b"""
+        return self.gate(TT_ANDN, a, b)
+
+    def ORN(self, a: Wire, b: Wire) -> Wire:
+        """a OR NOT b"""
+        return self.gate(TT_ORN, a, b)
+
+    def const(self, value: int) -> Wire:
+        """the wire that is always `value` (0 or 1): one shared wire per value and circuit, made on first use"""
+        if value not in (0, 1):
+            raise CircuitError("const: the value must be 0 or 1")
+        if value not in self._const:
+            self._nodes.append(("const", int(value)))
+            self._const[value] = len(self._nodes) - 1
+        return Wire(self._const[value])
+
+    def assert_same(self, a: Wire, b: Wire):
+        """assert that wires a and b carry the same bit: one row, no wire"""
+        self._check(a)
+        self._check(b)
+        if a.node == b.node:
+            raise CircuitError("assert_same: a wire is always equal to itself")
+        self._equal.append((a.node, b.node))
+
     def assert_equal(self, w: Wire, value: int):
         if value not in (0, 1):
             raise CircuitError("assert_equal: the value must be 0 or 1")
@@ -143,7 +260,7 @@ class Circuit:
         """the constraint rows for an SSP of params.d points and params.m wires; CircuitError if the circuit needs more than m - 1 wires or d - 1 rows"""
         wires, nw = self._layout()
         ngates = nw - len(self._pub) - len(self._priv)
-        nrows = nw + ngates + len(self._asserts)
+        nrows = nw + ngates + len(self._asserts) + len(self._equal)
         if nw > params.m - 1:
             raise CircuitError(f"the circuit needs {nw} wires, the SSP has {params.m - 1} (m - 1)")
         if nrows > params.d - 1:
@@ -153,9 +270,22 @@ class Circuit:
             kind, c = node[0], wires[i]
             if kind in ("pub", "priv"):
                 continue
+            if kind == "const":
+                rows.append([(c, 1)] if node[1] else [(c, _M1), (0, 1)])
+                continue
+            if kind == "lut":
+                rows.append(_modrow(*lut2_row(node[1], wires[node[2]], wires[node[3]], c)))
+                continue
             a = wires[node[1]]
             if kind == "not":
                 rows.append([(a, 1), (c, 1)])
+                continue
+            if kind in ("maj", "sum3"):
+                b, cc = wires[node[2]], wires[node[3]]
+                if kind == "maj":
+                    rows.append([(a, 2), (b, 2), (cc, 2), (c, P - 4), (0, _M1)])
+                else:  # the carry k is the MAJ gate's wire, created just before
+                    rows.append([(a, _M1), (b, _M1), (cc, _M1), (wires[i - 1], 2), (c, _M1), (0, 1)])
                 continue
             b = wires[node[2]]
             if kind == "xor":
@@ -166,15 +296,32 @@ class Circuit:
                 rows.append([(a, P - 2), (b, P - 2), (c, 4), (0, _M1)])
         for node, value in self._asserts:
             rows.append([(wires[node], 1)] if value else [(wires[node], _M1), (0, 1)])
+        for a, b in self._equal:
+            rows.append([(wires[a], _M1), (wires[b], _M1), (0, 1)])
         assert len(rows) == nrows
         row_ptr = np.zeros(nrows + 1, dtype=np.uint32)
         np.cumsum([len(r) for r in rows], out=row_ptr[1:])
         wire = np.array([w for r in rows for w, _ in r], dtype=np.uint32)
         coef = np.array([x for r in rows for _, x in r], dtype=np.uint32)
-        gates = np.array([(_OPS[n[0]], wires[n[1]], wires[n[-1]]) for n in self._nodes if n[0] not in ("pub", "priv")], dtype=np.uint32).reshape(-1, 3)
+        program = np.array([self._record(n, wires) for n in self._nodes if n[0] not in ("pub", "priv")], dtype=np.uint32).reshape(-1, 4)
+        gates = np.ascontiguousarray(program[:, :3])
         asserts = np.array([(wires[node], value) for node, value in self._asserts], dtype=np.uint32).reshape(-1, 2)
+        equal = np.array([(wires[a], wires[b]) for a, b in self._equal], dtype=np.uint32).reshape(-1, 2)
         self._params = params
-        return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw, gates=gates, asserts=asserts)
+        return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw, gates=gates, asserts=asserts,
+                        program=program, equal=equal)
+
+    @staticmethod
+    def _record(node, wires):
+        """(op, a, b, c) of one gate node in SSP wire numbering"""
+        kind = node[0]
+        if kind == "const":
+            return (GATE_CONST1 if node[1] else GATE_CONST0, 0, 0, 0)
+        if kind == "lut":
+            return (GATE_LUT2(node[1]), wires[node[2]], wires[node[3]], 0)
+        if kind in ("maj", "sum3"):
+            return (_OPS[kind], wires[node[1]], wires[node[2]], wires[node[3]])
+        return (_OPS[kind], wires[node[1]], wires[node[-1]], 0)
 
     # -- assignments ------------------------------------------------------------------------------------------------------
     def evaluate(self, public_bits, private_bits):
@@ -197,12 +344,20 @@ class Circuit:
                 val[i] = val[node[1]] & val[node[2]]
             elif kind == "or":
                 val[i] = val[node[1]] | val[node[2]]
+            elif kind == "maj":
+                val[i] = int(val[node[1]] + val[node[2]] + val[node[3]] >= 2)
+            elif kind == "sum3":
+                val[i] = val[node[1]] ^ val[node[2]] ^ val[node[3]]
+            elif kind == "lut":
+                val[i] = (node[1] >> (val[node[2]] + 2 * val[node[3]])) & 1
+            elif kind == "const":
+                val[i] = node[1]
         return val
 
     def holds(self, public_bits, private_bits) -> bool:
-        """every assertion holds on this input (then the witness of assign satisfies every row)"""
+        """every assertion and every equality holds on this input (then the witness of assign satisfies every row)"""
         val = self.evaluate(public_bits, private_bits)
-        return all(val[n] == v for n, v in self._asserts)
+        return all(val[n] == v for n, v in self._asserts) and all(val[a] == val[b] for a, b in self._equal)
 
     def assign(self, public_bits, private_bits, params=None) -> bytes:
         """the input bits of a proof: (m + 7) // 8 bytes, LSB first, bit i - 1 = wire i (m from params, else from the last compile)"""

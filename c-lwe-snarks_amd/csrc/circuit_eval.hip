@@ -11,7 +11,12 @@
 // mfh_circuit_create_global makes the second kind of program: k_circuit_eval_global is the same evaluation with the wire words in device memory
 // (ctx->circ_state), one column of nw + 1 words per block of 32 statements, read and written by that block's workgroup alone -- so the workgroup barrier
 // between levels orders everything, and the wire count is bounded by m - 1 instead of the LDS.  Gate records are 16 bytes {a, b, out, op}.
+//
+// mfh_circuit_create_ex makes extended programs of either kind (MAJ / SUM3 / CONST / LUT2 gates, equalities between wires): the EX = true instantiations
+// of both kernels, with 16-byte records {a, b, c, out | op << 24}.  The EX = false instantiations are the kernels of the two other creates.
 #include <algorithm>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ctx.hpp"
@@ -27,11 +32,33 @@ constexpr size_t GPIN_BYTES = (size_t)64 << 20;     // pinned staging per chunk:
 constexpr size_t GSTATE_BYTES = (size_t)256 << 20;  // wire state per chunk: blocks x column bytes (at least one column)
 constexpr uint32_t GUNROLL = 4;                     // gates in flight per thread and level
 
-// gates[g] = {a | b << 16, out | op << 16}, sorted by level; level L is gates [lp[L], lp[L + 1]).  asserts[e] = {wire, value}.
-__global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
-                                                      const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
+// the word of an extended gate (mfh_circuit_create_ex) from its operands' words; op = MFH_GATE_* (LUT2: 16 + tt)
+__device__ __forceinline__ uint32_t gate_ex(uint32_t op, uint32_t x, uint32_t y, uint32_t z) {
+  if (op >= 16) {
+    const uint32_t t0 = 0u - (op & 1), t1 = 0u - ((op >> 1) & 1), t2 = 0u - ((op >> 2) & 1), t3 = 0u - ((op >> 3) & 1);
+    return (~x & ~y & t0) | (x & ~y & t1) | (~x & y & t2) | (x & y & t3);
+  }
+  switch (op) {
+    case MFH_GATE_XOR: return x ^ y;
+    case MFH_GATE_AND: return x & y;
+    case MFH_GATE_OR: return x | y;
+    case MFH_GATE_NOT: return ~x;
+    case MFH_GATE_MAJ: return (x & y) | (z & (x | y));
+    case MFH_GATE_SUM3: return x ^ y ^ z;
+    case MFH_GATE_CONST0: return 0u;
+    default: return ~0u;  // MFH_GATE_CONST1
+  }
+}
+
+// Gate records sorted by level; level L is gates [lp[L], lp[L + 1]).  asserts[e] = {wire, value}.
+//   EX = false (mfh_circuit_create):    gates[g] = uint2 {a | b << 16, out | op << 16}, ops XOR / AND / OR / NOT; equal / nequal unused
+//   EX = true  (mfh_circuit_create_ex): gates[g] = uint4 {a, b, c, out | op << 24}, every op; equal[e] = {a, b} folds into holds with the assertions
+// The extra arguments come last, so the EX = false instantiation is the kernel as it was before extended programs existed, instruction for instruction.
+template <bool EX>
+__global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<EX, uint4, uint2> *__restrict__ gates, const uint32_t *__restrict__ lp,
+                                                      uint32_t nlev, const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                       const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt, uint8_t *__restrict__ out,
-                                                      size_t bits_stride, uint8_t *__restrict__ holds) {
+                                                      size_t bits_stride, uint8_t *__restrict__ holds, const uint2 *__restrict__ equal, uint32_t nequal) {
   __shared__ uint32_t st[CWORDS];
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
@@ -66,9 +93,13 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ 
     const uint32_t g0 = g1;
     g1 = lp[lv + 1];
     for (uint32_t g = g0 + tid; g < g1; g += CWG) {
-      const uint2 r = gates[g];
-      const uint32_t x = st[r.x & 0xffff], y = st[r.x >> 16], op = r.y >> 16;
-      st[r.y & 0xffff] = op == MFH_GATE_XOR ? x ^ y : op == MFH_GATE_AND ? x & y : op == MFH_GATE_OR ? x | y : ~x;
+      const auto r = gates[g];
+      if constexpr (EX) {
+        st[r.w & 0xffffff] = gate_ex(r.w >> 24, st[r.x], st[r.y], st[r.z]);
+      } else {
+        const uint32_t x = st[r.x & 0xffff], y = st[r.x >> 16], op = r.y >> 16;
+        st[r.y & 0xffff] = op == MFH_GATE_XOR ? x ^ y : op == MFH_GATE_AND ? x & y : op == MFH_GATE_OR ? x | y : ~x;
+      }
     }
     __syncthreads();
   }
@@ -79,6 +110,11 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ 
     const uint2 a = asserts[e];
     ok &= a.y ? st[a.x] : ~st[a.x];
   }
+  if constexpr (EX)
+    for (uint32_t e = tid; e < nequal; e += CWG) {
+      const uint2 q = equal[e];
+      ok &= ~(st[q.x] ^ st[q.y]);
+    }
   if (ok != ~0u) atomicAnd(&hw, ok);
 
   // ---- outputs: wire words -> statement rows, 8 bytes per statement and group of 64 wires; bytes [0, bits_stride) all written
@@ -106,12 +142,15 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const uint2 *__restrict__ 
   if (tid < CSTMT && s0 + tid < nstmt && holds) holds[s0 + tid] = (hw >> tid) & 1;
 }
 
-// The kernel above with the wire words in device memory: st = this block's column of colw words (wire i at st[i]), gates[g] = {a, b, out, op}.
-// A column is read and written by its own workgroup only; __syncthreads() (workgroup-scope release / acquire) orders the levels.
+// The kernel above with the wire words in device memory: st = this block's column of colw words (wire i at st[i]), gates[g] = {a, b, out, op}
+// (EX: {a, b, c, out | op << 24}, and equal / nequal as above).  A column is read and written by its own workgroup only; __syncthreads() (workgroup-scope
+// release / acquire) orders the levels.
+template <bool EX>
 __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
                                                              const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                              uint32_t *state, size_t colw, const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt,
-                                                             uint8_t *__restrict__ out, size_t bits_stride, uint8_t *__restrict__ holds) {
+                                                             uint8_t *__restrict__ out, size_t bits_stride, uint8_t *__restrict__ holds,
+                                                             const uint2 *__restrict__ equal, uint32_t nequal) {
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
   const uint32_t s0 = blockIdx.x * CSTMT, j = lane & 31;
@@ -147,18 +186,26 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__rest
     g1 = lp[lv + 1];
     for (uint32_t g = g0 + tid; g < g1; g += GUNROLL * CWG) {
       uint4 r[GUNROLL];
-      uint32_t x[GUNROLL], y[GUNROLL];
+      uint32_t x[GUNROLL], y[GUNROLL], z[GUNROLL];
 #pragma unroll
       for (uint32_t u = 0; u < GUNROLL; u++)
         if (g + u * CWG < g1) r[u] = gates[g + u * CWG];
 #pragma unroll
       for (uint32_t u = 0; u < GUNROLL; u++)
-        if (g + u * CWG < g1) { x[u] = st[r[u].x]; y[u] = st[r[u].y]; }
+        if (g + u * CWG < g1) {
+          x[u] = st[r[u].x];
+          y[u] = st[r[u].y];
+          if constexpr (EX) z[u] = st[r[u].z];
+        }
 #pragma unroll
       for (uint32_t u = 0; u < GUNROLL; u++)
         if (g + u * CWG < g1) {
-          const uint32_t op = r[u].w;
-          st[r[u].z] = op == MFH_GATE_XOR ? x[u] ^ y[u] : op == MFH_GATE_AND ? x[u] & y[u] : op == MFH_GATE_OR ? x[u] | y[u] : ~x[u];
+          if constexpr (EX) {
+            st[r[u].w & 0xffffff] = gate_ex(r[u].w >> 24, x[u], y[u], z[u]);
+          } else {
+            const uint32_t op = r[u].w;
+            st[r[u].z] = op == MFH_GATE_XOR ? x[u] ^ y[u] : op == MFH_GATE_AND ? x[u] & y[u] : op == MFH_GATE_OR ? x[u] | y[u] : ~x[u];
+          }
         }
     }
     __syncthreads();
@@ -170,6 +217,11 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__rest
     const uint2 a = asserts[e];
     ok &= a.y ? st[a.x] : ~st[a.x];
   }
+  if constexpr (EX)
+    for (uint32_t e = tid; e < nequal; e += CWG) {
+      const uint2 q = equal[e];
+      ok &= ~(st[q.x] ^ st[q.y]);
+    }
   if (ok != ~0u) atomicAnd(&hw, ok);
 
   // ---- outputs: wire words -> statement rows, 8 bytes per statement and group of 64 wires; bytes [0, bits_stride) all written
@@ -201,33 +253,64 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__rest
 
 struct mfh_circuit {
   int device = 0;
-  bool global = false;  // false: mfh_circuit_create (k_circuit_eval, LDS); true: mfh_circuit_create_global (k_circuit_eval_global, ctx->circ_state)
-  uint32_t nin = 0, ngates = 0, nasserts = 0, nlev = 0;
-  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | level_ptr (nlev + 1 words)
+  bool global = false;  // false: wire state in LDS (k_circuit_eval); true: mfh_circuit_create_global / MFH_CIRCUIT_GLOBAL (k_circuit_eval_global, ctx->circ_state)
+  bool ex = false;      // made by mfh_circuit_create_ex: 16-byte {a, b, c, out | op << 24} records and equalities, the EX = true kernels
+  uint32_t nin = 0, ngates = 0, nasserts = 0, nequal = 0, nlev = 0;
+  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | equal (uint2) | level_ptr (nlev + 1 words)
   const void *gates = nullptr;
   const uint2 *asserts = nullptr;
+  const uint2 *equal = nullptr;
   const uint32_t *lp = nullptr;
 };
 
 namespace {
 
-// both kinds: validate, level, sort by level, upload.  LDS records {a | b << 16, out | op << 16}; global records {a, b, out, op}.
-int circuit_create(mfh_ctx *ctx, bool global, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                   mfh_circuit **out) {
+// every kind: validate, level, sort by level, upload.  Records: mfh_circuit_create {a | b << 16, out | op << 16}; mfh_circuit_create_global {a, b, out, op};
+// mfh_circuit_create_ex {a, b, c, out | op << 24} in both kinds.  ex programs take 4-word gates (op, a, b, c), the others 3-word (op, a, b).
+int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts,
+                   const uint32_t *h_asserts, uint32_t nequal, const uint32_t *h_equal, mfh_circuit **out) {
   if (!ctx || !out) return MFH_EINVAL;
   *out = nullptr;
-  const std::string fn = global ? "mfh_circuit_create_global: " : "mfh_circuit_create: ";
+  const std::string fn = std::string(name) + ": ";
   if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = fn + "gates / assertions without their array"; return MFH_EINVAL; }
+  if (nequal && !h_equal) { ctx->err = fn + "equalities without their array"; return MFH_EINVAL; }
   const uint64_t nw = (uint64_t)nin + ngates;
   if (nw > ctx->P.m - 1) { ctx->err = fn + "nin + ngates > m - 1"; return MFH_EINVAL; }
   if (!global && nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = fn + "nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
+  if (ex && nw >= (1u << 24)) { ctx->err = fn + "nin + ngates >= 2^24 (the records' 24-bit wire field)"; return MFH_EINVAL; }
+  const size_t gw = ex ? 4 : 3;  // words per input gate record
   std::vector<uint32_t> lvl(nw + 1, 0);
   uint32_t nlev = 0;
   for (uint32_t g = 0; g < ngates; g++) {
-    const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = h_gates[3 * g + 2], o = nin + 1 + g;
-    if (op > MFH_GATE_NOT) { ctx->err = fn + "unknown gate op"; return MFH_EINVAL; }
-    if (a == 0 || a >= o || b == 0 || b >= o) { ctx->err = fn + "a gate operand is 0 or not below the gate's output wire"; return MFH_EINVAL; }
-    lvl[o] = 1 + std::max(lvl[a], op == MFH_GATE_NOT ? lvl[a] : lvl[b]);
+    const uint32_t *q = h_gates + gw * g;
+    const uint32_t op = q[0], a = q[1], b = q[2], o = nin + 1 + g;
+    if (!ex) {
+      if (op > MFH_GATE_NOT) { ctx->err = fn + "unknown gate op"; return MFH_EINVAL; }
+      if (a == 0 || a >= o || b == 0 || b >= o) { ctx->err = fn + "a gate operand is 0 or not below the gate's output wire"; return MFH_EINVAL; }
+      lvl[o] = 1 + std::max(lvl[a], op == MFH_GATE_NOT ? lvl[a] : lvl[b]);
+      nlev = std::max(nlev, lvl[o]);
+      continue;
+    }
+    const uint32_t c = q[3];
+    if ((op > MFH_GATE_CONST1 && op < 16) || op >= 32) { ctx->err = fn + "unknown gate op"; return MFH_EINVAL; }
+    if (op == MFH_GATE_CONST0 || op == MFH_GATE_CONST1) {
+      if (a | b | c) { ctx->err = fn + "a CONST gate with an operand other than 0"; return MFH_EINVAL; }
+      lvl[o] = 1;
+    } else {
+      const bool three = op == MFH_GATE_MAJ || op == MFH_GATE_SUM3;
+      if (a == 0 || a >= o || b == 0 || b >= o || (three && (c == 0 || c >= o))) {
+        ctx->err = fn + "a gate operand is 0 or not below the gate's output wire";
+        return MFH_EINVAL;
+      }
+      if (!three && c != 0) { ctx->err = fn + "a one- or two-input gate with a third operand c != 0"; return MFH_EINVAL; }
+      if (op == MFH_GATE_NOT && b != a) { ctx->err = fn + "a NOT gate with b != a"; return MFH_EINVAL; }
+      if (op == MFH_GATE_SUM3) {
+        const uint32_t *m = q - gw;  // gate g - 1
+        if (g == 0 || m[0] != MFH_GATE_MAJ) { ctx->err = fn + "a SUM3 gate not directly after a MAJ gate"; return MFH_EINVAL; }
+        if (m[1] != a || m[2] != b || m[3] != c) { ctx->err = fn + "a SUM3 gate whose operands differ from its MAJ's"; return MFH_EINVAL; }
+      }
+      lvl[o] = 1 + std::max(std::max(lvl[a], lvl[b]), three ? lvl[c] : 0u);
+    }
     nlev = std::max(nlev, lvl[o]);
   }
   for (uint32_t e = 0; e < nasserts; e++) {
@@ -235,18 +318,26 @@ int circuit_create(mfh_ctx *ctx, bool global, uint32_t nin, uint32_t ngates, con
     if (w == 0 || w > nw) { ctx->err = fn + "an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
     if (v > 1) { ctx->err = fn + "an assertion value other than 0 / 1"; return MFH_EINVAL; }
   }
+  for (uint32_t e = 0; e < nequal; e++) {
+    const uint32_t a = h_equal[2 * e], b = h_equal[2 * e + 1];
+    if (a == 0 || a > nw || b == 0 || b > nw) { ctx->err = fn + "an equality on wire 0 or above nin + ngates"; return MFH_EINVAL; }
+    if (a == b) { ctx->err = fn + "an equality of a wire with itself"; return MFH_EINVAL; }
+  }
   // counting sort by level (stable: creation order within a level)
   std::vector<uint32_t> lp(nlev + 1, 0);
   for (uint32_t g = 0; g < ngates; g++) lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
   for (uint32_t L = 0, acc = 0; L <= nlev; L++) { const uint32_t n = L < nlev ? lp[L + 1] : 0; lp[L] = acc; acc += n; }  // ... then lp[L] = first gate of level L + 1
-  const size_t rec = global ? 4 : 2;  // words per gate record
-  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + nlev + 1);
+  const size_t rec = global || ex ? 4 : 2;  // words per device gate record
+  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + 2 * (size_t)nequal + nlev + 1);
   {
     std::vector<uint32_t> pos(lp.begin(), lp.end());
     for (uint32_t g = 0; g < ngates; g++) {
-      const uint32_t op = h_gates[3 * g], a = h_gates[3 * g + 1], b = op == MFH_GATE_NOT ? a : h_gates[3 * g + 2], o = nin + 1 + g;
+      const uint32_t *q = h_gates + gw * g;
+      const uint32_t op = q[0], a = q[1], b = op == MFH_GATE_NOT ? a : q[2], o = nin + 1 + g;
       uint32_t *r = &host[rec * pos[lvl[o] - 1]++];
-      if (global) {
+      if (ex) {
+        r[0] = a; r[1] = b; r[2] = q[3]; r[3] = o | op << 24;
+      } else if (global) {
         r[0] = a; r[1] = b; r[2] = o; r[3] = op;
       } else {
         r[0] = a | b << 16;
@@ -254,15 +345,18 @@ int circuit_create(mfh_ctx *ctx, bool global, uint32_t nin, uint32_t ngates, con
       }
     }
     std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + rec * ngates);
-    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts);
+    std::copy(h_equal, h_equal + (size_t)2 * nequal, host.begin() + rec * ngates + 2 * nasserts);
+    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts + 2 * nequal);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   mfh_circuit *c = new mfh_circuit();
   c->device = ctx->device;
   c->global = global;
+  c->ex = ex;
   c->nin = nin;
   c->ngates = ngates;
   c->nasserts = nasserts;
+  c->nequal = nequal;
   c->nlev = nlev;
   if (hipMalloc(&c->mem, host.size() * 4) != hipSuccess) {
     (void)hipGetLastError();
@@ -278,7 +372,8 @@ int circuit_create(mfh_ctx *ctx, bool global, uint32_t nin, uint32_t ngates, con
   }
   c->gates = c->mem;
   c->asserts = (const uint2 *)((const uint32_t *)c->mem + rec * ngates);
-  c->lp = (const uint32_t *)(c->asserts + nasserts);
+  c->equal = c->asserts + nasserts;
+  c->lp = (const uint32_t *)(c->equal + nequal);
   *out = c;
   return MFH_OK;
 }
@@ -289,12 +384,24 @@ extern "C" {
 
 int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                        mfh_circuit **out) {
-  return circuit_create(ctx, false, nin, ngates, h_gates, nasserts, h_asserts, out);
+  return circuit_create(ctx, "mfh_circuit_create", false, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, out);
 }
 
 int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                               mfh_circuit **out) {
-  return circuit_create(ctx, true, nin, ngates, h_gates, nasserts, h_asserts, out);
+  return circuit_create(ctx, "mfh_circuit_create_global", true, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, out);
+}
+
+int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                          uint32_t nequal, const uint32_t *h_equal, uint32_t flags, mfh_circuit **out) {
+  if (!ctx || !out) return MFH_EINVAL;
+  if (flags & ~MFH_CIRCUIT_GLOBAL) {
+    *out = nullptr;
+    ctx->err = "mfh_circuit_create_ex: unknown flag bits";
+    return MFH_EINVAL;
+  }
+  return circuit_create(ctx, "mfh_circuit_create_ex", (flags & MFH_CIRCUIT_GLOBAL) != 0, true, nin, ngates, h_gates, nasserts, h_asserts, nequal, h_equal,
+                        out);
 }
 
 void mfh_circuit_destroy(mfh_circuit *c) {
@@ -337,15 +444,25 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
       memcpy(pin_in, h_inputs + (size_t)b0 * in_stride, (size_t)n * in_stride);
       if (hipMemcpyAsync(d_in, pin_in, (size_t)n * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
     }
-    if (c->global) {
+    const dim3 grid((n + CSTMT - 1) / CSTMT);
+    if (c->global && c->ex) {
+      Timer tm(ctx, 19, n);
+      hipLaunchKernelGGL(k_circuit_eval_global<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
+                         c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal,
+                         c->nequal);
+    } else if (c->global) {
       Timer tm(ctx, 17, n);
-      hipLaunchKernelGGL(k_circuit_eval_global, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
-                         c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
-                         d_holds);
+      hipLaunchKernelGGL(k_circuit_eval_global<false>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
+                         c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds,
+                         (const uint2 *)nullptr, 0u);
+    } else if (c->ex) {
+      Timer tm(ctx, 18, n);
+      hipLaunchKernelGGL(k_circuit_eval<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal);
     } else {
       Timer tm(ctx, 16, n);
-      hipLaunchKernelGGL(k_circuit_eval, dim3((n + CSTMT - 1) / CSTMT), dim3(CWG), 0, ctx->stream, (const uint2 *)c->gates, c->lp, c->nlev, c->asserts,
-                         c->nasserts, c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds);
+      hipLaunchKernelGGL(k_circuit_eval<false>, grid, dim3(CWG), 0, ctx->stream, (const uint2 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, (const uint2 *)nullptr, 0u);
     }
     if (hipGetLastError() != hipSuccess) { rc = MFH_EDEVICE; break; }
     if (hipMemcpyAsync(pin_out, d_out, (size_t)n * bits_stride, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

@@ -1272,6 +1272,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
   if (!strcmp(which, "circuit_assign")) return 16;  // k_circuit_eval of mfh_circuit_assign
   if (!strcmp(which, "circuit_assign_global")) return 17;  // k_circuit_eval_global of mfh_circuit_assign (mfh_circuit_create_global programs)
+  if (!strcmp(which, "circuit_assign_ex")) return 18;  // k_circuit_eval_ex of mfh_circuit_assign (mfh_circuit_create_ex programs, wires in LDS)
+  if (!strcmp(which, "circuit_assign_global_ex")) return 19;  // k_circuit_eval_global_ex (mfh_circuit_create_ex with MFH_CIRCUIT_GLOBAL)
   return -1;
 }
 

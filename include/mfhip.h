@@ -226,6 +226,30 @@ int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32
  * byte those of a mfh_circuit_create program of the same circuit.  Kernel timing kind "circuit_assign_global". */
 int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                               mfh_circuit **out);
+/* Extended programs: three-operand records, more gates, equalities.  h_gates: ngates records (op, a, b, c) of uint32, gate g writing wire nin + 1 + g;
+ * h_asserts as above; h_equal: nequal pairs (a, b) asserting wire a = wire b.  flags: 0 (wire state in LDS, nin + ngates <= MFH_CIRCUIT_MAX_WIRES) or
+ * MFH_CIRCUIT_GLOBAL (in device memory); in both kinds nin + ngates <= m - 1.  Every new gate and every equality adds one SSP row that is +-1 mod p exactly
+ * when its output is right, given bit operands (circuit.py compiles them; wire w keeps its bit row 2w - 1):
+ *   MAJ(a, b, c)     k = 1 iff a + b + c >= 2                          2a + 2b + 2c - 4k - 1
+ *   SUM3(a, b, c)    s = a ^ b ^ c (k = the wire of gate g - 1)         1 - a - b - c + 2k - s
+ *   CONST0 / CONST1  0 / 1                                              1 - c / c
+ *   LUT2(tt)(a, b)   c = (tt >> (a + 2b)) & 1                          by the class of tt (circuit.py); XOR, AND, OR, NOT rows for those functions
+ *   equality (a, b)  a = b (no wire)                                     1 - a - b
+ * SUM3 is sound only next to the MAJ that forces k, so gate g - 1 must be a MAJ with the same (a, b, c).
+ * Operands: XOR, AND, OR, LUT2: a, b in [1, nin + g], c = 0; NOT: a in [1, nin + g], b = a, c = 0; MAJ, SUM3: a, b, c in [1, nin + g]; CONST: a = b = c
+ * = 0.  Equality wires in [1, nin + ngates] with a != b.  MFH_EINVAL, with its own mfh_last_error text and nothing allocated, for each violation, for ops
+ * 8 .. 15 and >= 32 and for unknown flag bits, besides the cases of mfh_circuit_create.  Levels: a gate is 1 + the highest level of the operands it
+ * uses (CONST: 1; SUM3 shares its MAJ's level).  holds = every value assertion and every equality holds.  mfh_circuit_assign runs these programs in
+ * k_circuit_eval_ex / k_circuit_eval_global_ex (16-byte records {a, b, c, out | op << 24}), timing kinds "circuit_assign_ex" and
+ * "circuit_assign_global_ex"; the chunking, witness rows and holds layout are those of the kind named by flags. */
+#define MFH_GATE_MAJ 4u    /* out = maj(a, b, c) */
+#define MFH_GATE_SUM3 5u   /* out = a ^ b ^ c; gate g - 1 must be MFH_GATE_MAJ with the same (a, b, c) */
+#define MFH_GATE_CONST0 6u /* a = b = c = 0 */
+#define MFH_GATE_CONST1 7u
+#define MFH_GATE_LUT2(tt) (16u + (tt)) /* out = (tt >> (a + 2b)) & 1, tt in [0, 16) */
+#define MFH_CIRCUIT_GLOBAL 1u
+int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                          uint32_t nequal, const uint32_t *h_equal, uint32_t flags, mfh_circuit **out);
 /* either kind of program */
 void mfh_circuit_destroy(mfh_circuit *c);
 /* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
@@ -491,7 +515,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two

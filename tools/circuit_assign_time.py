@@ -4,13 +4,17 @@ Legs (--leg, default all):
     XOR / NOT gates), LDS program (mfh_circuit_create), --nb statements;
   * 2p20: D = 2^20, M = 699 050, the circuit of test_two_pow_20_circuit_proved_and_verified (64 public, 20 000 private inputs, 470 000 random gates),
     device-memory program (circuit_load(state="global"), mfh_circuit_create_global), 255 and 1 020 statements;
-  * chain: a 60 000-gate XOR / NOT chain (depth 60 000) on 40 000 inputs, global program, 100 statements: its time and launch count.
+  * chain: a 60 000-gate XOR / NOT chain (depth 60 000) on 40 000 inputs, global program, 100 statements: its time and launch count;
+  * chacha: the ChaCha20 block statement (words.ChaCha20Block: 896 inputs, 31 746 gates, 512 equalities) at D = 2^16, M = 43 690, --nb statements,
+    both kinds of mfh_circuit_create_ex program (kinds "circuit_assign_ex" / "circuit_assign_global_ex");
+  * chacha_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^16 (median of --reps calls after one warm-up).
 Printed per leg (one JSON line each, also appended to --out):
   * load: circuit_load once (levelising on the host, the upload);
   * call: the median wall time of circuit_assign (packing the input bits, staging, the launches, the copies back; the call synchronises);
   * kernel: the kernel launches alone (HIP events of mfh_set_timing, kind "circuit_assign" / "circuit_assign_global"), summed over a call's chunks;
   * python: Circuit.assign for --py statements (--py2 at 2^20), scaled to the batch (the rows are checked equal).
-dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain] [--nb 1020] [--reps 7] [--py 1020] [--py2 4] [--out FILE]"""
+dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
+[--out FILE]"""
 import argparse
 import json
 import os
@@ -59,6 +63,31 @@ def _depth(cc):
     for g, (op, x, y) in enumerate(cc.gates.tolist()):
         lvl[nin + 1 + g] = 1 + max(lvl[x], lvl[y])
     return int(lvl.max())
+
+
+def _depth_ex(cc):
+    """levels of an extended program (Compiled.program): CONST gates are level 1, a gate 1 + the highest level of the operands it reads"""
+    lvl = np.zeros(cc.nwires + 1, dtype=np.int64)
+    nin = cc.nwires - len(cc.program)
+    for g, (op, x, y, z) in enumerate(cc.program.tolist()):
+        lvl[nin + 1 + g] = 1 if op in (circuit.GATE_CONST0, circuit.GATE_CONST1) else 1 + max(lvl[x], lvl[y], lvl[z] if z else 0)
+    return int(lvl.max())
+
+
+def _chacha_statements(st, rng, nb):
+    from c_lwe_snarks_amd import words
+
+    rows = []
+    for _ in range(nb):
+        key = bytes(rng.integers(0, 256, size=32, dtype=np.uint8).tolist())
+        counter = int(rng.integers(0, 1 << 32, dtype=np.uint64))
+        nonce = bytes(rng.integers(0, 256, size=12, dtype=np.uint8).tolist())
+        # the public block from the circuit itself: evaluate with a zero block, read the computed words back
+        bits = st.bits(key, counter, nonce, bytes(64))
+        val = st.circuit.evaluate(bits[:640], bits[640:])
+        block = b"".join(words.unpack(np.array([val[b.node] for b in w], dtype=np.uint8))[0].to_bytes(4, "little") for w in st.out)
+        rows.append(st.bits(key, counter, nonce, block))
+    return np.stack(rows)
 
 
 def _emit(res, out):
@@ -159,17 +188,99 @@ def leg_chain(a):
     return same
 
 
+def leg_chacha(a):
+    from c_lwe_snarks_amd import words
+
+    p = mf.Params(d=1 << 16, m=43690)
+    st = words.ChaCha20Block()
+    cc = st.circuit.compile(p)
+    depth = _depth_ex(cc)
+    rng = np.random.default_rng(8439)
+    bits = _chacha_statements(st, rng, a.nb)
+    ctx = mf.Context(p, 0)
+    ok = True
+    outs = {}
+    for state, kind in (("lds", "circuit_assign_ex"), ("global", "circuit_assign_global_ex")):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        prog = ctx.circuit_load(cc, state=state)
+        load_ms = (time.perf_counter() - t0) * 1e3
+        witness, holds, call, kern, launches = _time_calls(ctx, prog, bits, a.reps, kind)
+        outs[state] = witness
+        npy = min(a.py2, a.nb)
+        t0 = time.perf_counter()
+        ref = [st.circuit.assign(bits[b, :640], bits[b, 640:], p) for b in range(npy)]
+        py_ms = (time.perf_counter() - t0) * 1e3 / npy
+        same = all(witness[b].tobytes() == ref[b] for b in range(npy)) and bool(holds.all())
+        ok = ok and same
+        res = {"tool": "circuit_assign_time", "leg": "chacha", "state": state, "d": p.d, "m": p.m, "nb": a.nb, "npub": cc.lu, "npriv": 256,
+               "ngates": len(cc.program), "nequal": len(cc.equal), "depth": depth, "load_ms": round(load_ms, 3), "launches_per_call": launches,
+               "call_ms": round(statistics.median(call), 3), "call_ms_all": [round(x, 3) for x in call],
+               "kernel_ms": round(statistics.median(kern), 3), "kernel_ms_all": [round(x, 3) for x in kern],
+               "kernel_us_per_level": round(statistics.median(kern) * 1e3 / depth, 3),
+               "python_ms_per_statement": round(py_ms, 3), "python_statements_timed": npy, "python_ms_for_nb": round(py_ms * a.nb, 1),
+               "python_over_call": round(py_ms * a.nb / statistics.median(call), 1), "rows_equal": bool(same)}
+        _emit(res, a.out)
+        prog.close()
+    ok = ok and bool(np.array_equal(outs["lds"], outs["global"]))
+    ctx.close()
+    return ok
+
+
+def leg_chacha_prove(a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+    from c_lwe_snarks_amd import words
+
+    p = mf.Params(d=1 << 16, m=43690)
+    st = words.ChaCha20Block()
+    cc = st.circuit.compile(p)
+    nb = 255
+    rng = np.random.default_rng(8440)
+    bits = _chacha_statements(st, rng, nb)
+    ctx = mf.Context(p, 0)
+    prog = ctx.circuit_load(cc)
+    witness, holds = ctx.circuit_assign(prog, bits)
+    prog.close()
+    ctx.set_seed(bytes(range(40)))
+    ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)
+    ctx.ssp_prepare(None)
+    alpha, beta, s = (int(x) for x in rng.integers(1, circuit.P, size=3, dtype=np.uint64))
+    d_sk = ctx.to_device(ol.rand_values(rng, p.n, p.L, p.logq))
+    d_err = ctx.to_device(ol.rand_values(rng, 2 * p.d + p.m, p.L, 559))
+    d_crs = ctx.setup_public(None, alpha, beta, s, cc.lu, d_sk, d_err).clone()
+    stmts = [witness[b].tobytes() for b in range(nb)]
+    deltas = [int(x) for x in rng.integers(0, circuit.P, size=nb, dtype=np.uint64)]
+    mags = [rng.integers(0, 256, size=400, dtype=np.uint8).tobytes() for _ in range(nb)]
+    signs = [bytes(rng.integers(0, 2, size=5, dtype=np.uint8).tolist()) for _ in range(nb)]
+    times = []
+    for _ in range(a.reps + 1):
+        ctx.sync()
+        t0 = time.perf_counter()
+        proofs = ctx.prove_batch_public(d_crs, None, cc.lu, stmts, deltas, mags, signs)
+        ctx.sync()
+        times.append((time.perf_counter() - t0) * 1e3)
+    vk = ctx.derive_vk(None, s, cc.lu)
+    ok = bool(ctx.to_host(ctx.verify_public(vk, cc.lu, alpha, beta, d_sk, proofs, stmts), np.uint8).all())
+    res = {"tool": "circuit_assign_time", "leg": "chacha_prove", "d": p.d, "m": p.m, "nb": nb, "lu": cc.lu, "nrows": cc.nrows,
+           "prove_batch_public_ms": round(statistics.median(times[1:]), 3), "prove_ms_all": [round(x, 3) for x in times],
+           "holds_all": bool(holds.all()), "verified_all": ok}
+    _emit(res, a.out)
+    ctx.close()
+    return ok and bool(holds.all())
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain"])
+    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove"])
     ap.add_argument("--nb", type=int, default=1020)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign (default leg)")
-    ap.add_argument("--py2", type=int, default=4, help="statements timed through Circuit.assign (2p20 leg)")
+    ap.add_argument("--py2", type=int, default=4, help="statements timed through Circuit.assign (2p20 and chacha legs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ok = True
-    for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20)):
+    for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20), ("chacha", leg_chacha), ("chacha_prove", leg_chacha_prove)):
         if a.leg in ("all", name):
             ok = fn(a) and ok
     return 0 if ok else 1
