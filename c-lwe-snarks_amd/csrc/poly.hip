@@ -13,9 +13,14 @@
 // T' = t^-1 in F_p[x] / (x^N - 1) -- two CYCLIC products of length N instead of two linear ones of length 2N: half the transform work (2^15 points instead of 2^16 at the
 // default size) and no reversals.  T' is computed once per SSP by the norm recursion a^-1 = a(-x) [a(x) a(-x)]^-1, the bracket being a polynomial in x^2, i.e. an
 // element of the ring of half the length (log N levels down to a scalar).  Whether the division WAS exact is not assumed: the batch's results are checked on the device
-// (h(r) t(r) = v(r)^2 - 1 at four points r: a wrong h of ANY origin survives with probability <= (2d / p)^4 < 2^-64), and when one statement fails the Euclidean path above
-// recomputes the statements that failed -- its kernels are queued behind the check, sized for the whole batch, and each workgroup returns at once unless the list
-// of failed statements reaches it: nothing waits for the host, and a batch with k such statements pays the Euclidean path for k.
+// (h(r) t(r) = v(r)^2 - 1 at four points r drawn per preparation from the kernel's entropy: a wrong h of ANY origin, for a v chosen without knowledge of the points,
+// survives with probability <= (2d / p)^4 < 2^-64), and when one statement fails the Euclidean path above recomputes the statements that failed -- its kernels
+// are queued behind the check, sized for the whole batch, and each workgroup returns at once unless the list of failed statements reaches it: nothing waits for the
+// host, and a batch with k such statements pays the Euclidean path for k.
+#include <errno.h>
+#include <sys/syscall.h>
+#include <unistd.h>
+
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -623,6 +628,7 @@ struct PolyState {
   uint32_t logNc = 0;            // Nc = 2^logNc >= d
   uint32_t *d_That = nullptr;    // [3][Nc] forward transform of t^-1 mod (x^Nc - 1)
   uint32_t *d_chk = nullptr;     // [4][Nc] powers of the four check points
+  uint32_t chk_r[4]{};           // the check points (drawn per preparation, or pinned: mfh_set_poly_exact_points)
   uint32_t chk_t[4]{};           // t at the check points
   uint32_t *d_need = nullptr;    // [0] statements of the batch that failed the check, [1] the same since the last reset, [2 ..] which ones (k_exact_check)
   uint32_t *h_seen = nullptr;    // pinned host word the check sets when a statement fails: read (never waited for) by later calls
@@ -828,6 +834,21 @@ int poly_mul(mfh_ctx *c, const uint32_t *a, uint32_t la, const uint32_t *b, uint
   return MFH_OK;
 }
 
+// one check point from the kernel's entropy, uniform in [2, p - 1): not 0 and not +-1, where r^Nc = 1 and the check cannot see the cyclic wrap.  Through the system
+// call itself, not the getrandom symbol: the reference-driver tests interpose that symbol with deterministic tapes, and a draw here would shift the bytes they predict.
+// false: no entropy to be had.
+bool draw_point(uint32_t *r) {
+  uint64_t z = 0;
+  for (size_t got = 0; got < sizeof z;) {
+    const long k = syscall(SYS_getrandom, (char *)&z + got, sizeof z - got, 0);
+    if (k < 0 && errno == EINTR) continue;
+    if (k <= 0) return false;
+    got += (size_t)k;
+  }
+  *r = (uint32_t)(2 + z % (P32 - 3));  // (bias below 2^-31)
+  return true;
+}
+
 // T' = t^-1 in F_p[x] / (x^Nc - 1) by the norm recursion, its transform, and the check points: everything the exact-division path of mfh_poly_h_multi needs.
 // Leaves S->cyc false (and the Euclidean path in charge) when deg t < d - 1 or t is not a unit of that ring.
 int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &t) {
@@ -888,20 +909,25 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
   hipLaunchKernelGGL(k_ntt_load, dim3((Nc + 255) / 256, 3), dim3(256), 0, c->stream, inv[cur], Nc, Nc, S->P, S->d_That, (size_t)0, (const uint32_t *)nullptr,
                      (const uint32_t *)nullptr);
   forward(c, S->d_That, logNc);
-  // the check points: fixed, odd, spread over F_p (splitmix64 of 1..4); their powers and t at them
+  // the check points, drawn here -- for every t prepared -- unless the caller has pinned them; their powers and t at them.  Points fixed in advance (public constants)
+  // would let a crafted v whose defect vanishes there pass the check (tests/exact_defect_ref.py builds one): the bound (2d / p)^4 holds for points drawn independently
+  // of the input.  A drawn point that repeats an earlier one or is a root of t is drawn again.
   std::vector<uint32_t> pw((size_t)4 * Nc);
-  for (int j = 0; j < 4; j++) {
-    uint64_t z = 0x9e3779b97f4a7c15ull * (uint64_t)(j + 1);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    const uint64_t r = 2 + (z ^ (z >> 31)) % (P32 - 2);
+  for (int j = 0, draws = 0; j < 4;) {
+    uint32_t r = c->poly_pts[j];
+    if (!c->poly_pts_pinned) {
+      if (++draws > 64 || !draw_point(&r)) return MFH_OK;  // no entropy: the Euclidean path stays in charge
+      if (std::find(S->chk_r, S->chk_r + j, r) != S->chk_r + j) continue;
+    }
     uint64_t x = 1, tv = 0;
     for (uint32_t i = 0; i < Nc; i++) {
       pw[(size_t)j * Nc + i] = (uint32_t)x;
       if (i < d) tv = (tv + x * t[i]) % P32;
       x = x * r % P32;
     }
-    S->chk_t[j] = (uint32_t)tv;
+    if (!tv && !c->poly_pts_pinned) continue;
+    S->chk_r[j] = r;
+    S->chk_t[j++] = (uint32_t)tv;
   }
   HIP_TRY(c, hipMalloc(&S->d_chk, pw.size() * 4));
   HIP_TRY(c, hipMemcpyAsync(S->d_chk, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1146,6 +1172,25 @@ long mfh_poly_exact_fallbacks(mfh_ctx *c) {
       hipMemsetAsync(c->poly->d_need + 1, 0, 4, c->stream) != hipSuccess)
     return -1;
   return (long)w[1];
+}
+// the four points of the prepared t's check
+int mfh_poly_exact_points(mfh_ctx *c, uint32_t *out) {
+  if (!c || !out || !c->poly || !c->poly->have_t || !c->poly->cyc) return MFH_EINVAL;
+  std::copy(c->poly->chk_r, c->poly->chk_r + 4, out);
+  return MFH_OK;
+}
+// pin the check points from the next mfh_poly_prepare_t on (four distinct values in [2, p - 1)); nullptr: draw them again
+int mfh_set_poly_exact_points(mfh_ctx *c, const uint32_t *pts) {
+  if (!c) return MFH_EINVAL;
+  if (!pts) {
+    c->poly_pts_pinned = false;
+    return MFH_OK;
+  }
+  for (int j = 0; j < 4; j++)
+    if (pts[j] < 2 || pts[j] >= P32 - 1 || std::find(pts, pts + j, pts[j]) != pts + j) return MFH_EINVAL;
+  std::copy(pts, pts + 4, c->poly_pts);
+  c->poly_pts_pinned = true;
+  return MFH_OK;
 }
 int mfh_poly_h(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h) { return mfh_poly_h_multi(c, d_v, d_h, 1); }
 

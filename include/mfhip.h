@@ -280,15 +280,21 @@ int mfh_poly_h(mfh_ctx *ctx, const uint32_t *d_v, uint32_t *d_h);
 int mfh_poly_h_multi(mfh_ctx *ctx, const uint32_t *d_v, uint32_t *d_h, uint32_t nb);
 /* A batch (nb >= 4) takes the exact-division path when the prepared t has degree d - 1 and is a unit modulo x^N - 1 (N = the power of two >= d): a prover with a valid
  * witness divides exactly (src/ssp.c:37-77), and then h = (v^2 - 1 mod x^N - 1) t^-1 mod x^N - 1 -- two cyclic products of length N instead of two linear ones of
- * length 2N.  Every result is CHECKED on the device (h(r) t(r) = v(r)^2 - 1 at four points); the statements that fail -- a witness that does not satisfy the SSP
+ * length 2N.  Every result is CHECKED on the device (h(r) t(r) = v(r)^2 - 1 at four points drawn per preparation from the kernel's entropy, so that a wrong h for a
+ * v chosen without knowledge of them survives with probability <= (2d / p)^4 < 2^-64); the statements that fail -- a witness that does not satisfy the SSP
  * -- are recomputed by the Euclidean division above, by kernels queued behind the check (no host round trip; a batch with k such statements pays that path for k):
- * the output is nmod_poly_div's in every case.  mode 1 (the default): as described, except that after a batch in which the check has failed the next 64 batches take
- * the Euclidean path alone before the exact path is tried again (a caller whose statements do not satisfy the SSP would pay both; the failure is noticed through a
- * word in host memory whenever the device gets there -- a hint, nothing is waited for).  mode 2: every batch tries the exact path (A/B, tests).  mode 0: never.
- * Setting a mode forgets what earlier batches have taught. */
+ * the output is nmod_poly_div's but for that probability.  mode 1 (the default): as described, except that after a batch in which the check has failed the next
+ * 64 batches take the Euclidean path alone before the exact path is tried again (a caller whose statements do not satisfy the SSP would pay both; the failure is
+ * noticed through a word in host memory whenever the device gets there -- a hint, nothing is waited for).  mode 2: every batch tries the exact path (A/B, tests).
+ * mode 0: never.  Setting a mode forgets what earlier batches have taught.  The points: mfh_poly_exact_points, mfh_set_poly_exact_points below. */
 int mfh_set_poly_exact(mfh_ctx *ctx, int mode);
 /* statements that failed that check (and were recomputed) since the last call; waits for the stream.  -1: the prepared t has no exact-division path */
 long mfh_poly_exact_fallbacks(mfh_ctx *ctx);
+/* the four points of that check for the prepared t (out[4]).  MFH_EINVAL: no t prepared, or it has no exact-division path. */
+int mfh_poly_exact_points(mfh_ctx *ctx, uint32_t *out);
+/* pin the check points (tests, reproducible runs): pts = four distinct values in [2, p - 1), used from the next mfh_poly_prepare_t on until unpinned; pts = NULL
+ * unpins (the next preparation draws them again).  MFH_EINVAL for a value out of range or a repeated one (and the setting is left as it was). */
+int mfh_set_poly_exact_points(mfh_ctx *ctx, const uint32_t *pts);
 
 /* The 2d+m plaintexts setup() encrypts, in stream order: s^i | alpha s^i | beta t(s) | beta v_i(s), i=1..m-1
  * (src/snark.c:73-110; the Horner values nmod_poly_evaluate_nmod are computed as dot products with the powers of s). */
