@@ -99,7 +99,7 @@ EXPORTS = [
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
-    "mfh_circuit_create_global", "mfh_circuit_create_ex",
+    "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out",
 ]
 
 
@@ -222,6 +222,7 @@ def load_library():
         "mfh_circuit_create": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_create_global": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_create_ex": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
+        "mfh_circuit_create_out": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
         "mfh_circuit_destroy": (None, [vp]),
         "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
     }
@@ -262,10 +263,12 @@ CIRCUIT_GLOBAL = 1  # MFH_CIRCUIT_GLOBAL: mfh_circuit_create_ex flag, wire state
 class CircuitProgram:
     """a compiled circuit's gate program on the device (mfh_circuit): made by Context.circuit_load, used by Context.circuit_assign.
     state: "lds" (mfh_circuit_create, at most CIRCUIT_MAX_WIRES wires) or "global" (mfh_circuit_create_global, wire state in device memory);
-    extended: made by mfh_circuit_create_ex (the circuit has a gate beyond XOR / AND / OR / NOT or an equality), in the kind `state` names"""
+    extended: made by mfh_circuit_create_ex (the circuit has a gate beyond XOR / AND / OR / NOT or an equality), in the kind `state` names;
+    outputs: the number of computed public outputs (Circuit.output): above 0 the program was made by mfh_circuit_create_out, in the kind `state` names,
+    and circuit_assign writes the computed statement into bits [0, lu) of every witness row"""
 
-    def __init__(self, ctx, nin, ngates, handle, state="lds", extended=False):
-        self._ctx, self.nin, self.ngates, self._h, self.state, self.extended = ctx, nin, ngates, handle, state, extended
+    def __init__(self, ctx, nin, ngates, handle, state="lds", extended=False, outputs=0):
+        self._ctx, self.nin, self.ngates, self._h, self.state, self.extended, self.outputs = ctx, nin, ngates, handle, state, extended, outputs
 
     def close(self):
         if self._h:
@@ -557,7 +560,8 @@ class Context:
         """the gate program of circuit.Compiled on the device: levelised and uploaded once; close() frees it.  state: "lds" (mfh_circuit_create: the
         wire state in LDS, at most CIRCUIT_MAX_WIRES wires), "global" (mfh_circuit_create_global: in device memory, up to m - 1 wires) or "auto"
         (lds up to CIRCUIT_MAX_WIRES wires, else global).  A circuit with a MAJ / SUM3 / CONST / LUT2 gate or an equality (Compiled.program, Compiled.equal)
-        goes through mfh_circuit_create_ex in the same kind; the others through the two creates above."""
+        goes through mfh_circuit_create_ex in the same kind; the others through the two creates above.  A circuit with computed public outputs
+        (Circuit.output, Compiled.outputs) goes through mfh_circuit_create_out; one without them loads exactly as before."""
         if state not in ("lds", "global", "auto"):
             raise MfhError(f"circuit_load: state must be 'lds', 'global' or 'auto', got {state!r}")
         gates = np.ascontiguousarray(compiled.gates, dtype=np.uint32).reshape(-1, 3)
@@ -565,22 +569,28 @@ class Context:
         # a program description without program / equal (gates, asserts, nwires alone) is one of the four original ops
         program = np.ascontiguousarray(getattr(compiled, "program", np.zeros((0, 4))), dtype=np.uint32).reshape(-1, 4)
         equal = np.ascontiguousarray(getattr(compiled, "equal", np.zeros((0, 2))), dtype=np.uint32).reshape(-1, 2)
-        extended = len(equal) > 0 or bool((program[:, 0] > 3).any())
+        outputs = np.ascontiguousarray(getattr(compiled, "outputs", np.zeros((0, 2))), dtype=np.uint32).reshape(-1, 2)
+        extended = len(equal) > 0 or len(outputs) > 0 or bool((program[:, 0] > 3).any())
         nin = compiled.nwires - len(gates)
         if state == "auto":
             state = "lds" if compiled.nwires <= CIRCUIT_MAX_WIRES else "global"
         h = ctypes.c_void_p()
-        if extended:
+        if len(outputs):
+            self._chk(self.lib.mfh_circuit_create_out(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
+                                                      ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data), len(outputs),
+                                                      ctypes.c_void_p(outputs.ctypes.data), CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
+        elif extended:
             self._chk(self.lib.mfh_circuit_create_ex(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
                                                      ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data),
                                                      CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
         else:
             create = self.lib.mfh_circuit_create if state == "lds" else self.lib.mfh_circuit_create_global
             self._chk(create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data), ctypes.byref(h)))
-        return CircuitProgram(self, nin, len(gates), h, state, extended)
+        return CircuitProgram(self, nin, len(gates), h, state, extended, len(outputs))
 
     def circuit_assign(self, prog, bits):
-        """witnesses of nb statements on the device (mfh_circuit_assign): bits = uint8 [nb, nin] of 0 / 1, public bits then private bits.
+        """witnesses of nb statements on the device (mfh_circuit_assign): bits = uint8 [nb, nin] of 0 / 1, public bits then private bits (whatever stands
+        at the position of a computed public output is ignored: the witness row carries the computed bit there).
         Returns (witness, holds): witness uint8 [nb, (m + 7) // 8], row b = Circuit.assign of statement b (prove_batch takes it as it is);
         holds bool [nb] = Circuit.holds"""
         bits = np.asarray(bits, dtype=np.uint8)

@@ -8,6 +8,12 @@ Context.ssp_from_rows interpolates the rows into the SSP on the device.
 Wire layout: wire 0 is the constant v_0.  Public inputs take wires 1 .. lu in the order they were declared.  Private inputs follow, then the gate outputs
 in creation order.  Witness bit i - 1 is wire i, so bits [0, lu) are the public statement (Context.prove_batch_public / verify_public with this lu).
 
+Computed public outputs: p = c.output(w) declares a public wire p whose value is DEFINED as that of wire w.  In the layout p is a public input like any
+other (wires 1 .. lu in declaration order, public() and output() interleaved as declared) and it costs one equality row 1 - p - w, in the equalities'
+place in the row order; Compiled.outputs records (p, w).  evaluate / assign / holds ignore what the caller put at p's input position and use w's value,
+and so does Context.circuit_assign, so the caller gives the inputs and reads the statement back: outputs_of(witness_row).  Nothing may read an output
+wire (no gate, assertion or equality takes it as an operand): its value exists only once the whole circuit has been evaluated.
+
 Rows, all values mod p: every wire w gets 2w - 1 (it is 0 or 1).  Then each gate and each assertion gets one row:
     c = a XOR b : a + b + c - 1          c = a AND b : 2a + 2b - 4c - 1          c = a OR b : -2a - 2b + 4c - 1
     c = NOT a   : a + c                  assert a = 1 : a                         assert a = 0 : 1 - a
@@ -129,6 +135,8 @@ class Compiled:
     # gates = program[:, :3].  equal[e] = (a, b): the wires of assert_same, in creation order
     program: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), dtype=np.uint32), compare=False)
     equal: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
+    # computed public outputs (mfh_circuit_create_out): outputs[e] = (p, w), public wire p defined as wire w, in declaration order; each pair is also in equal
+    outputs: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
 
     def wire(self, w: Wire) -> int:
         return self.wires[w.node]
@@ -136,11 +144,12 @@ class Compiled:
 
 class Circuit:
     def __init__(self):
-        self._nodes = []    # ("pub",) / ("priv",) / (gate, a, b) / ("not", a) / ("maj" | "sum3", a, b, c) / ("lut", tt, a, b) / ("const", v): operands are node indices
+        self._nodes = []    # ("pub",) / ("priv",) / ("out", w) / (gate, a, b) / ("not", a) / ("maj" | "sum3", a, b, c) / ("lut", tt, a, b) / ("const", v): operands are node indices
         self._asserts = []  # (node, value)
         self._equal = []    # (node, node) of assert_same
         self._const = {}    # value -> node of the shared constant wire
-        self._pub = []      # node indices of the public inputs, in declaration order
+        self._pub = []      # node indices of the public inputs, in declaration order (computed outputs among them)
+        self._outputs = []  # (node of the output wire p, node w) of output
         self._priv = []
         self._params = None
 
@@ -148,6 +157,8 @@ class Circuit:
     def _check(self, w):
         if not isinstance(w, Wire) or not 0 <= w.node < len(self._nodes):
             raise CircuitError(f"{w!r} is not a wire of this circuit")
+        if self._nodes[w.node][0] == "out":
+            raise CircuitError(f"{w!r} is a computed public output: nothing may read it")
 
     def _new(self, kind, *ops):
         for w in ops:
@@ -162,6 +173,16 @@ class Circuit:
         w = self._new("pub")
         self._pub.append(w.node)
         return w
+
+    def output(self, w: Wire) -> Wire:
+        """a public wire whose value is defined as that of wire w (a computed public output): a public input in the wire layout, one equality row
+        1 - p - w, and a pair in Compiled.outputs.  The returned wire only names the position in the statement: nothing may read it."""
+        self._check(w)
+        p = self._new("out", w)
+        self._pub.append(p.node)
+        self._equal.append((p.node, w.node))
+        self._outputs.append((p.node, w.node))
+        return p
 
     def private(self, count=None):
         """one private input wire, or a list of `count` of them"""
@@ -250,7 +271,7 @@ class Circuit:
     def _layout(self):
         wires = [0] * len(self._nodes)
         nxt = 1
-        for group in (self._pub, self._priv, [i for i, n in enumerate(self._nodes) if n[0] not in ("pub", "priv")]):
+        for group in (self._pub, self._priv, [i for i, n in enumerate(self._nodes) if n[0] not in ("pub", "priv", "out")]):
             for i in group:
                 wires[i] = nxt
                 nxt += 1
@@ -268,7 +289,7 @@ class Circuit:
         rows = [[(w, 2), (0, _M1)] for w in range(1, nw + 1)]  # every wire is a bit
         for i, node in enumerate(self._nodes):
             kind, c = node[0], wires[i]
-            if kind in ("pub", "priv"):
+            if kind in ("pub", "priv", "out"):
                 continue
             if kind == "const":
                 rows.append([(c, 1)] if node[1] else [(c, _M1), (0, 1)])
@@ -303,13 +324,14 @@ class Circuit:
         np.cumsum([len(r) for r in rows], out=row_ptr[1:])
         wire = np.array([w for r in rows for w, _ in r], dtype=np.uint32)
         coef = np.array([x for r in rows for _, x in r], dtype=np.uint32)
-        program = np.array([self._record(n, wires) for n in self._nodes if n[0] not in ("pub", "priv")], dtype=np.uint32).reshape(-1, 4)
+        program = np.array([self._record(n, wires) for n in self._nodes if n[0] not in ("pub", "priv", "out")], dtype=np.uint32).reshape(-1, 4)
         gates = np.ascontiguousarray(program[:, :3])
         asserts = np.array([(wires[node], value) for node, value in self._asserts], dtype=np.uint32).reshape(-1, 2)
         equal = np.array([(wires[a], wires[b]) for a, b in self._equal], dtype=np.uint32).reshape(-1, 2)
+        outputs = np.array([(wires[p], wires[w]) for p, w in self._outputs], dtype=np.uint32).reshape(-1, 2)
         self._params = params
         return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw, gates=gates, asserts=asserts,
-                        program=program, equal=equal)
+                        program=program, equal=equal, outputs=outputs)
 
     @staticmethod
     def _record(node, wires):
@@ -325,7 +347,8 @@ class Circuit:
 
     # -- assignments ------------------------------------------------------------------------------------------------------
     def evaluate(self, public_bits, private_bits):
-        """the bit on every node (Wire.node order)"""
+        """the bit on every node (Wire.node order).  public_bits has one entry per public wire, computed outputs included: what stands at an output's
+        position is ignored, the node takes the value of the wire it is defined as"""
         public_bits, private_bits = list(public_bits), list(private_bits)
         if len(public_bits) != len(self._pub) or len(private_bits) != len(self._priv):
             raise CircuitError(f"the circuit has {len(self._pub)} public and {len(self._priv)} private inputs")
@@ -352,6 +375,8 @@ class Circuit:
                 val[i] = (node[1] >> (val[node[2]] + 2 * val[node[3]])) & 1
             elif kind == "const":
                 val[i] = node[1]
+            elif kind == "out":
+                val[i] = val[node[1]]
         return val
 
     def holds(self, public_bits, private_bits) -> bool:
@@ -374,8 +399,22 @@ class Circuit:
                 out[(wires[i] - 1) >> 3] |= 1 << ((wires[i] - 1) & 7)
         return bytes(out)
 
+    def outputs_of(self, witness_bits) -> bytes:
+        """the public statement u read back from a witness row (bytes of assign, or a row of Context.circuit_assign): bits [0, lu), LSB first, as
+        Context.verify_public takes it -- with computed outputs, the statement the circuit arrived at"""
+        lu = len(self._pub)
+        row = bytes(bytearray(witness_bits)[: (lu + 7) // 8])
+        if len(row) * 8 < lu:
+            raise CircuitError(f"outputs_of: the witness row has fewer than {lu} bits")
+        out = bytearray(max(1, (lu + 7) // 8))
+        out[: len(row)] = row
+        if lu & 7:
+            out[lu >> 3] &= (1 << (lu & 7)) - 1
+        return bytes(out)
+
     def statement(self, public_bits) -> bytes:
-        """the public statement u (bits [0, lu) of the input, LSB first) as Context.verify_public takes it"""
+        """the public statement u (bits [0, lu) of the input, LSB first) as Context.verify_public takes it (the bits as given: for a circuit with
+        computed outputs read the statement from the witness, outputs_of)"""
         public_bits = list(public_bits)
         if len(public_bits) != len(self._pub):
             raise CircuitError(f"the circuit has {len(self._pub)} public inputs")

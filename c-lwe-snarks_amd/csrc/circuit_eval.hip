@@ -14,6 +14,10 @@
 //
 // mfh_circuit_create_ex makes extended programs of either kind (MAJ / SUM3 / CONST / LUT2 gates, equalities between wires): the EX = true instantiations
 // of both kernels, with 16-byte records {a, b, c, out | op << 24}.  The EX = false instantiations are the kernels of the two other creates.
+//
+// mfh_circuit_create_out adds computed public outputs to an extended program: pairs (p, w) of an input wire p whose value is defined as that of wire w.
+// The OUT = true instantiations (EX = true only) copy st[w] to st[p] for every pair after the last level, before the assertions and equalities are
+// folded and the witness is written: bits [0, lu) of a witness row then carry the computed statement, whatever the caller put at p's input position.
 #include <algorithm>
 #include <string>
 #include <type_traits>
@@ -54,11 +58,15 @@ __device__ __forceinline__ uint32_t gate_ex(uint32_t op, uint32_t x, uint32_t y,
 //   EX = false (mfh_circuit_create):    gates[g] = uint2 {a | b << 16, out | op << 16}, ops XOR / AND / OR / NOT; equal / nequal unused
 //   EX = true  (mfh_circuit_create_ex): gates[g] = uint4 {a, b, c, out | op << 24}, every op; equal[e] = {a, b} folds into holds with the assertions
 // The extra arguments come last, so the EX = false instantiation is the kernel as it was before extended programs existed, instruction for instruction.
-template <bool EX>
+//   OUT = true (mfh_circuit_create_out, nout > 0): outputs[e] = {p, w}: st[p] = st[w] after the last level (no w is a p, every p once: no order among pairs).
+// outputs / nout come last again, and the OUT = false instantiations never read them: their code is what it was before outputs existed.
+template <bool EX, bool OUT = false>
 __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<EX, uint4, uint2> *__restrict__ gates, const uint32_t *__restrict__ lp,
                                                       uint32_t nlev, const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                       const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt, uint8_t *__restrict__ out,
-                                                      size_t bits_stride, uint8_t *__restrict__ holds, const uint2 *__restrict__ equal, uint32_t nequal) {
+                                                      size_t bits_stride, uint8_t *__restrict__ holds, const uint2 *__restrict__ equal, uint32_t nequal,
+                                                      const uint2 *__restrict__ outputs, uint32_t nout) {
+  static_assert(EX || !OUT, "outputs belong to extended programs");
   __shared__ uint32_t st[CWORDS];
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
@@ -104,6 +112,15 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<E
     __syncthreads();
   }
 
+  // ---- computed public outputs: the input wire p takes the value of wire w
+  if constexpr (OUT) {
+    for (uint32_t e = tid; e < nout; e += CWG) {
+      const uint2 o = outputs[e];
+      st[o.x] = st[o.y];
+    }
+    __syncthreads();
+  }
+
   // ---- assertions
   uint32_t ok = ~0u;
   for (uint32_t e = tid; e < nasserts; e += CWG) {
@@ -144,13 +161,15 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<E
 
 // The kernel above with the wire words in device memory: st = this block's column of colw words (wire i at st[i]), gates[g] = {a, b, out, op}
 // (EX: {a, b, c, out | op << 24}, and equal / nequal as above).  A column is read and written by its own workgroup only; __syncthreads() (workgroup-scope
-// release / acquire) orders the levels.
-template <bool EX>
+// release / acquire) orders the levels, and the output pass after them.
+template <bool EX, bool OUT = false>
 __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
                                                              const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                              uint32_t *state, size_t colw, const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt,
                                                              uint8_t *__restrict__ out, size_t bits_stride, uint8_t *__restrict__ holds,
-                                                             const uint2 *__restrict__ equal, uint32_t nequal) {
+                                                             const uint2 *__restrict__ equal, uint32_t nequal, const uint2 *__restrict__ outputs,
+                                                             uint32_t nout) {
+  static_assert(EX || !OUT, "outputs belong to extended programs");
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
   const uint32_t s0 = blockIdx.x * CSTMT, j = lane & 31;
@@ -211,6 +230,15 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__rest
     __syncthreads();
   }
 
+  // ---- computed public outputs: the input wire p takes the value of wire w
+  if constexpr (OUT) {
+    for (uint32_t e = tid; e < nout; e += CWG) {
+      const uint2 o = outputs[e];
+      st[o.x] = st[o.y];
+    }
+    __syncthreads();
+  }
+
   // ---- assertions
   uint32_t ok = ~0u;
   for (uint32_t e = tid; e < nasserts; e += CWG) {
@@ -255,11 +283,12 @@ struct mfh_circuit {
   int device = 0;
   bool global = false;  // false: wire state in LDS (k_circuit_eval); true: mfh_circuit_create_global / MFH_CIRCUIT_GLOBAL (k_circuit_eval_global, ctx->circ_state)
   bool ex = false;      // made by mfh_circuit_create_ex: 16-byte {a, b, c, out | op << 24} records and equalities, the EX = true kernels
-  uint32_t nin = 0, ngates = 0, nasserts = 0, nequal = 0, nlev = 0;
-  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | equal (uint2) | level_ptr (nlev + 1 words)
+  uint32_t nin = 0, ngates = 0, nasserts = 0, nequal = 0, nout = 0, nlev = 0;  // nout > 0: mfh_circuit_create_out with outputs, the OUT = true kernels
+  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | equal (uint2) | outputs (uint2) | level_ptr (nlev + 1 words)
   const void *gates = nullptr;
   const uint2 *asserts = nullptr;
   const uint2 *equal = nullptr;
+  const uint2 *outputs = nullptr;
   const uint32_t *lp = nullptr;
 };
 
@@ -267,18 +296,36 @@ namespace {
 
 // every kind: validate, level, sort by level, upload.  Records: mfh_circuit_create {a | b << 16, out | op << 16}; mfh_circuit_create_global {a, b, out, op};
 // mfh_circuit_create_ex {a, b, c, out | op << 24} in both kinds.  ex programs take 4-word gates (op, a, b, c), the others 3-word (op, a, b).
+// h_outputs: nout pairs (p, w) of mfh_circuit_create_out (ex programs only).
 int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts,
-                   const uint32_t *h_asserts, uint32_t nequal, const uint32_t *h_equal, mfh_circuit **out) {
+                   const uint32_t *h_asserts, uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, mfh_circuit **out) {
   if (!ctx || !out) return MFH_EINVAL;
   *out = nullptr;
   const std::string fn = std::string(name) + ": ";
   if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = fn + "gates / assertions without their array"; return MFH_EINVAL; }
   if (nequal && !h_equal) { ctx->err = fn + "equalities without their array"; return MFH_EINVAL; }
+  if (nout && !h_outputs) { ctx->err = fn + "outputs without their array"; return MFH_EINVAL; }
   const uint64_t nw = (uint64_t)nin + ngates;
   if (nw > ctx->P.m - 1) { ctx->err = fn + "nin + ngates > m - 1"; return MFH_EINVAL; }
   if (!global && nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = fn + "nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
   if (ex && nw >= (1u << 24)) { ctx->err = fn + "nin + ngates >= 2^24 (the records' 24-bit wire field)"; return MFH_EINVAL; }
   const size_t gw = ex ? 4 : 3;  // words per input gate record
+  // output pairs (p, w): source[p] = w for an output wire p, else 0.  An output wire has no value until the end of the evaluation, so nothing reads it
+  // but its own pair's equality
+  std::vector<uint32_t> source(nout ? (size_t)nin + 1 : 0, 0);
+  for (uint32_t e = 0; e < nout; e++) {
+    const uint32_t p = h_outputs[2 * e], w = h_outputs[2 * e + 1];
+    if (p == 0 || p > nin) { ctx->err = fn + "an output wire p that is not an input wire (1 .. nin)"; return MFH_EINVAL; }
+    if (w == 0 || w > nw) { ctx->err = fn + "an output's source wire w is 0 or above nin + ngates"; return MFH_EINVAL; }
+    if (w == p) { ctx->err = fn + "an output wire defined as itself"; return MFH_EINVAL; }
+    if (source[p]) { ctx->err = fn + "an output wire p given twice"; return MFH_EINVAL; }
+    source[p] = w;
+  }
+  for (uint32_t e = 0; e < nout; e++) {
+    const uint32_t w = h_outputs[2 * e + 1];
+    if (w <= nin && source[w]) { ctx->err = fn + "an output's source wire w is itself an output wire"; return MFH_EINVAL; }
+  }
+  const auto is_out = [&](uint32_t w) { return nout && w <= nin && source[w] != 0; };
   std::vector<uint32_t> lvl(nw + 1, 0);
   uint32_t nlev = 0;
   for (uint32_t g = 0; g < ngates; g++) {
@@ -304,6 +351,7 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
       }
       if (!three && c != 0) { ctx->err = fn + "a one- or two-input gate with a third operand c != 0"; return MFH_EINVAL; }
       if (op == MFH_GATE_NOT && b != a) { ctx->err = fn + "a NOT gate with b != a"; return MFH_EINVAL; }
+      if (is_out(a) || is_out(b) || (three && is_out(c))) { ctx->err = fn + "a gate reads an output wire"; return MFH_EINVAL; }
       if (op == MFH_GATE_SUM3) {
         const uint32_t *m = q - gw;  // gate g - 1
         if (g == 0 || m[0] != MFH_GATE_MAJ) { ctx->err = fn + "a SUM3 gate not directly after a MAJ gate"; return MFH_EINVAL; }
@@ -317,18 +365,23 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
     const uint32_t w = h_asserts[2 * e], v = h_asserts[2 * e + 1];
     if (w == 0 || w > nw) { ctx->err = fn + "an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
     if (v > 1) { ctx->err = fn + "an assertion value other than 0 / 1"; return MFH_EINVAL; }
+    if (is_out(w)) { ctx->err = fn + "an assertion on an output wire"; return MFH_EINVAL; }
   }
   for (uint32_t e = 0; e < nequal; e++) {
     const uint32_t a = h_equal[2 * e], b = h_equal[2 * e + 1];
     if (a == 0 || a > nw || b == 0 || b > nw) { ctx->err = fn + "an equality on wire 0 or above nin + ngates"; return MFH_EINVAL; }
     if (a == b) { ctx->err = fn + "an equality of a wire with itself"; return MFH_EINVAL; }
+    if ((is_out(a) && source[a] != b) || (is_out(b) && source[b] != a)) {
+      ctx->err = fn + "an equality on an output wire other than its own pair's";
+      return MFH_EINVAL;
+    }
   }
   // counting sort by level (stable: creation order within a level)
   std::vector<uint32_t> lp(nlev + 1, 0);
   for (uint32_t g = 0; g < ngates; g++) lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
   for (uint32_t L = 0, acc = 0; L <= nlev; L++) { const uint32_t n = L < nlev ? lp[L + 1] : 0; lp[L] = acc; acc += n; }  // ... then lp[L] = first gate of level L + 1
   const size_t rec = global || ex ? 4 : 2;  // words per device gate record
-  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + 2 * (size_t)nequal + nlev + 1);
+  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + 2 * (size_t)nequal + 2 * (size_t)nout + nlev + 1);
   {
     std::vector<uint32_t> pos(lp.begin(), lp.end());
     for (uint32_t g = 0; g < ngates; g++) {
@@ -346,7 +399,8 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
     }
     std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + rec * ngates);
     std::copy(h_equal, h_equal + (size_t)2 * nequal, host.begin() + rec * ngates + 2 * nasserts);
-    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts + 2 * nequal);
+    std::copy(h_outputs, h_outputs + (size_t)2 * nout, host.begin() + rec * ngates + 2 * nasserts + 2 * nequal);
+    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts + 2 * nequal + 2 * nout);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   mfh_circuit *c = new mfh_circuit();
@@ -357,6 +411,7 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
   c->ngates = ngates;
   c->nasserts = nasserts;
   c->nequal = nequal;
+  c->nout = nout;
   c->nlev = nlev;
   if (hipMalloc(&c->mem, host.size() * 4) != hipSuccess) {
     (void)hipGetLastError();
@@ -373,7 +428,8 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
   c->gates = c->mem;
   c->asserts = (const uint2 *)((const uint32_t *)c->mem + rec * ngates);
   c->equal = c->asserts + nasserts;
-  c->lp = (const uint32_t *)(c->equal + nequal);
+  c->outputs = c->equal + nequal;
+  c->lp = (const uint32_t *)(c->outputs + nout);
   *out = c;
   return MFH_OK;
 }
@@ -384,12 +440,12 @@ extern "C" {
 
 int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                        mfh_circuit **out) {
-  return circuit_create(ctx, "mfh_circuit_create", false, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, out);
+  return circuit_create(ctx, "mfh_circuit_create", false, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, 0, nullptr, out);
 }
 
 int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                               mfh_circuit **out) {
-  return circuit_create(ctx, "mfh_circuit_create_global", true, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, out);
+  return circuit_create(ctx, "mfh_circuit_create_global", true, false, nin, ngates, h_gates, nasserts, h_asserts, 0, nullptr, 0, nullptr, out);
 }
 
 int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
@@ -401,7 +457,19 @@ int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uin
     return MFH_EINVAL;
   }
   return circuit_create(ctx, "mfh_circuit_create_ex", (flags & MFH_CIRCUIT_GLOBAL) != 0, true, nin, ngates, h_gates, nasserts, h_asserts, nequal, h_equal,
-                        out);
+                        0, nullptr, out);
+}
+
+int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t flags, mfh_circuit **out) {
+  if (!ctx || !out) return MFH_EINVAL;
+  if (flags & ~MFH_CIRCUIT_GLOBAL) {
+    *out = nullptr;
+    ctx->err = "mfh_circuit_create_out: unknown flag bits";
+    return MFH_EINVAL;
+  }
+  return circuit_create(ctx, "mfh_circuit_create_out", (flags & MFH_CIRCUIT_GLOBAL) != 0, true, nin, ngates, h_gates, nasserts, h_asserts, nequal, h_equal,
+                        nout, h_outputs, out);
 }
 
 void mfh_circuit_destroy(mfh_circuit *c) {
@@ -445,24 +513,33 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
       if (hipMemcpyAsync(d_in, pin_in, (size_t)n * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
     }
     const dim3 grid((n + CSTMT - 1) / CSTMT);
-    if (c->global && c->ex) {
+    if (c->global && c->nout) {
+      Timer tm(ctx, 21, n);
+      hipLaunchKernelGGL((k_circuit_eval_global<true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                         c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
+                         d_holds, c->equal, c->nequal, c->outputs, c->nout);
+    } else if (c->nout) {
+      Timer tm(ctx, 20, n);
+      hipLaunchKernelGGL((k_circuit_eval<true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
+                         c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, c->outputs, c->nout);
+    } else if (c->global && c->ex) {
       Timer tm(ctx, 19, n);
       hipLaunchKernelGGL(k_circuit_eval_global<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
                          c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal,
-                         c->nequal);
+                         c->nequal, (const uint2 *)nullptr, 0u);
     } else if (c->global) {
       Timer tm(ctx, 17, n);
       hipLaunchKernelGGL(k_circuit_eval_global<false>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
                          c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds,
-                         (const uint2 *)nullptr, 0u);
+                         (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u);
     } else if (c->ex) {
       Timer tm(ctx, 18, n);
       hipLaunchKernelGGL(k_circuit_eval<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
-                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal);
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, (const uint2 *)nullptr, 0u);
     } else {
       Timer tm(ctx, 16, n);
       hipLaunchKernelGGL(k_circuit_eval<false>, grid, dim3(CWG), 0, ctx->stream, (const uint2 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
-                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, (const uint2 *)nullptr, 0u);
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u);
     }
     if (hipGetLastError() != hipSuccess) { rc = MFH_EDEVICE; break; }
     if (hipMemcpyAsync(pin_out, d_out, (size_t)n * bits_stride, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

@@ -1274,6 +1274,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "circuit_assign_global")) return 17;  // k_circuit_eval_global of mfh_circuit_assign (mfh_circuit_create_global programs)
   if (!strcmp(which, "circuit_assign_ex")) return 18;  // k_circuit_eval_ex of mfh_circuit_assign (mfh_circuit_create_ex programs, wires in LDS)
   if (!strcmp(which, "circuit_assign_global_ex")) return 19;  // k_circuit_eval_global_ex (mfh_circuit_create_ex with MFH_CIRCUIT_GLOBAL)
+  if (!strcmp(which, "circuit_assign_out")) return 20;  // k_circuit_eval<true, true> (mfh_circuit_create_out programs with outputs, wires in LDS)
+  if (!strcmp(which, "circuit_assign_global_out")) return 21;  // k_circuit_eval_global<true, true> (... with MFH_CIRCUIT_GLOBAL)
   return -1;
 }
 

@@ -1,4 +1,4 @@
-"""32-bit words over one circuit.Circuit, and the ChaCha20 block function (RFC 8439) written with them.
+"""32-bit words over one circuit.Circuit, and the ChaCha20 block function (RFC 8439) and the SHA-256 compression function (FIPS 180-4) written with them.
 
 A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wires (each also one SSP row besides the wire's bit row):
     add          64   bit 0 a half adder (XOR, AND), bits 1 .. 31 a full adder each (MAJ + SUM3; the last carry is unused)
@@ -10,6 +10,7 @@ A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wire
     const         0   the shared zero and one wires (at most 2 for the whole circuit)
     assert_u32        32 value assertions (rows, no wires)
     assert_same_u32   32 equalities (rows, no wires)
+    output            32 computed public outputs (Circuit.output): 32 public wires and 32 equality rows
 
     w = Words()
     x, y = w.public(), w.private()
@@ -18,6 +19,8 @@ A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wire
     bits = np.concatenate([pack([x_value]), pack([y_value])], axis=1)   # public words, then private words, as Context.circuit_assign takes them
 
 The ChaCha20 block statement (ChaCha20Block) takes 32 642 wires and 64 900 rows: it fits d = 2^16 (m = 43 690) and the LDS kernel.
+The SHA-256 compression statement (Sha256Compress) takes 61 698 wires and 122 884 rows (61 954 and 123 140 with a public chaining value): it fits
+d = 2^17 (m = 87 381), above the LDS kernel's wire limit, so its witnesses come from the device-memory kernel and its SSP is the row SSP.
 """
 from __future__ import annotations
 
@@ -63,6 +66,10 @@ class Words:
         if count is not None:
             return [self.private() for _ in range(count)]
         return tuple(self.c.private(32))
+
+    def output(self, x):
+        """a public word whose value is defined as that of x (32 computed public outputs, Circuit.output): the statement's position of x"""
+        return tuple(self.c.output(a) for a in x)
 
     def const(self, value: int):
         """the word `value`: the circuit's shared constant wires, no new wire beyond them"""
@@ -200,3 +207,110 @@ class ChaCha20Block:
     def bits(self, key: bytes, counter: int, nonce: bytes, block: bytes):
         """one statement's 896 input bits, public then private (a row of Context.circuit_assign's input)"""
         return np.concatenate([self.public_bits(counter, nonce, block), self.private_bits(key)])
+
+
+# ---------------------------------------------------------------------------------------------------------------------- SHA-256 (FIPS 180-4)
+SHA256_IV = (0x6A09E667, 0xBB67AE85, 0x3C6EF372, 0xA54FF53A, 0x510E527F, 0x9B05688C, 0x1F83D9AB, 0x5BE0CD19)
+SHA256_K = (
+    0x428A2F98, 0x71374491, 0xB5C0FBCF, 0xE9B5DBA5, 0x3956C25B, 0x59F111F1, 0x923F82A4, 0xAB1C5ED5, 0xD807AA98, 0x12835B01, 0x243185BE, 0x550C7DC3,
+    0x72BE5D74, 0x80DEB1FE, 0x9BDC06A7, 0xC19BF174, 0xE49B69C1, 0xEFBE4786, 0x0FC19DC6, 0x240CA1CC, 0x2DE92C6F, 0x4A7484AA, 0x5CB0A9DC, 0x76F988DA,
+    0x983E5152, 0xA831C66D, 0xB00327C8, 0xBF597FC7, 0xC6E00BF3, 0xD5A79147, 0x06CA6351, 0x14292967, 0x27B70A85, 0x2E1B2138, 0x4D2C6DFC, 0x53380D13,
+    0x650A7354, 0x766A0ABB, 0x81C2C92E, 0x92722C85, 0xA2BFE8A1, 0xA81A664B, 0xC24B8B70, 0xC76C51A3, 0xD192E819, 0xD6990624, 0xF40E3585, 0x106AA070,
+    0x19A4C116, 0x1E376C08, 0x2748774C, 0x34B0BCB5, 0x391C0CB3, 0x4ED8AA4A, 0x5B9CCA4F, 0x682E6FF3, 0x748F82EE, 0x78A5636F, 0x84C87814, 0x8CC70208,
+    0x90BEFFFA, 0xA4506CEB, 0xBEF9A3F7, 0xC67178F2,
+)
+
+
+def _xor3(w: Words, x, y, z):
+    return w.xor(w.xor(x, y), z)
+
+
+def sha256_compress(w: Words, H, M):
+    """the 8 words of the SHA-256 compression function (FIPS 180-4 6.2.2): H = the 8 words of the incoming hash value, M = the 16 words of one block
+    (big-endian words of the bytes, be_words).  48 schedule words of 2 x 2 xors and 3 adds, 64 rounds of 4 xors, Ch, Maj and 7 adds, 8 final adds:
+    600 adds, 448 xors, 64 Ch, 64 Maj -- 60 928 gate wires, and the circuit's two constant wires.  The adds of a round are ordered so that the words
+    that are ready early (h, K_t, W_t, then Ch and Sigma_1) are summed first and the ripple carries of consecutive adds overlap."""
+    H, W = list(H), list(M)
+    if len(H) != 8 or len(W) != 16:
+        raise CircuitError("sha256_compress: H is 8 words and M 16")
+    for t in range(16, 64):
+        s0 = _xor3(w, w.rotr(W[t - 15], 7), w.rotr(W[t - 15], 18), w.shr(W[t - 15], 3))
+        s1 = _xor3(w, w.rotr(W[t - 2], 17), w.rotr(W[t - 2], 19), w.shr(W[t - 2], 10))
+        W.append(w.add(w.add(W[t - 16], s0), w.add(W[t - 7], s1)))
+    a, b, c, d, e, f, g, h = H
+    for t in range(64):
+        S1 = _xor3(w, w.rotr(e, 6), w.rotr(e, 11), w.rotr(e, 25))
+        S0 = _xor3(w, w.rotr(a, 2), w.rotr(a, 13), w.rotr(a, 22))
+        t1 = w.add(w.add(w.add(h, w.add(w.const(SHA256_K[t]), W[t])), w.ch(e, f, g)), S1)
+        t2 = w.add(S0, w.maj(a, b, c))
+        a, b, c, d, e, f, g, h = w.add(t1, t2), a, b, c, w.add(d, t1), e, f, g
+    return [w.add(x, y) for x, y in zip(H, (a, b, c, d, e, f, g, h))]
+
+
+def be_words(data: bytes):
+    """big-endian 32-bit words of a byte string (FIPS 180-4's convention)"""
+    if len(data) % 4:
+        raise CircuitError("be_words: the length must be a multiple of 4")
+    return [int.from_bytes(data[i: i + 4], "big") for i in range(0, len(data), 4)]
+
+
+def sha256_pad(message: bytes) -> bytes:
+    """the message padded to whole 64-byte blocks (FIPS 180-4 5.1.1): 0x80, zeros, the bit length as 8 big-endian bytes"""
+    message = bytes(message)
+    return message + b"\x80" + bytes((55 - len(message)) % 64) + (8 * len(message)).to_bytes(8, "big")
+
+
+class Sha256Compress:
+    """The statement "I know a 64-byte block whose SHA-256 compression, from this chaining value, is this value".
+
+    chaining="iv": the chaining value is the constant SHA256_IV, so the statement is the digest of a one-block padded message: lu = 256, the eight result
+    words as computed public outputs; 61 698 wires (768 inputs, 2 constants, 60 928 gates) and 122 884 rows.
+    chaining="public": the incoming chaining value is public too, ahead of the result (lu = 512: bits [0, 256) the chaining value, [256, 512) the
+    result) -- what a caller hashing several blocks, or a Merkle path, chains from statement to statement; 61 954 wires and 123 140 rows.
+    The block is private (512 bits).  Both fit Params(d=1 << 17, m=87381).  The result is computed, not given: bits() leaves its positions zero,
+    Circuit.assign / Context.circuit_assign write it into the witness row, and digest_of reads the 32 bytes back."""
+
+    def __init__(self, chaining="iv"):
+        if chaining not in ("iv", "public"):
+            raise CircuitError("Sha256Compress: chaining is 'iv' or 'public'")
+        self.chaining = chaining
+        self.w = w = Words()
+        self.h_in = w.public(8) if chaining == "public" else [w.const(v) for v in SHA256_IV]
+        self.block = w.private(16)
+        self.out = sha256_compress(w, self.h_in, self.block)
+        self.digest = [w.output(x) for x in self.out]
+        self.digest_at = 256 if chaining == "public" else 0  # the result's first bit in the statement
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return self.digest_at + 256
+
+    def public_bits(self, chaining: bytes | None = None):
+        """the lu public bits: the 32-byte chaining value (chaining="public" only), then 256 zeros where the result is computed"""
+        if (chaining is not None) != (self.chaining == "public"):
+            raise CircuitError("Sha256Compress: a chaining value goes with chaining='public', and only with it")
+        if chaining is not None and len(chaining) != 32:
+            raise CircuitError("Sha256Compress: the chaining value is 32 bytes")
+        head = pack(be_words(chaining)) if chaining is not None else np.zeros(0, dtype=np.uint8)
+        return np.concatenate([head, np.zeros(256, dtype=np.uint8)])
+
+    @staticmethod
+    def private_bits(block: bytes):
+        """the 512 private bits of a 64-byte block"""
+        if len(block) != 64:
+            raise CircuitError("Sha256Compress: the block is 64 bytes")
+        return pack(be_words(block))
+
+    def bits(self, block: bytes, chaining: bytes | None = None):
+        """one statement's input bits, public then private (a row of Context.circuit_assign's input), the result's positions zero"""
+        return np.concatenate([self.public_bits(chaining), self.private_bits(block)])
+
+    def digest_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed result, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        row = np.frombuffer(bytes(bytearray(witness_row)[: self.lu // 8]), dtype=np.uint8)
+        bits = np.unpackbits(row, bitorder="little")[self.digest_at: self.digest_at + 256]
+        return b"".join(v.to_bytes(4, "big") for v in unpack(bits))

@@ -250,7 +250,18 @@ int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const
 #define MFH_CIRCUIT_GLOBAL 1u
 int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                           uint32_t nequal, const uint32_t *h_equal, uint32_t flags, mfh_circuit **out);
-/* either kind of program */
+/* Extended programs with computed public outputs.  The arguments of mfh_circuit_create_ex plus h_outputs: nout pairs (p, w) of uint32.  Output wire p is
+ * an input wire (a public input of the statement, wires 1 .. lu) whose value is DEFINED as that of wire w: mfh_circuit_assign ignores input bit p - 1 of
+ * every statement and, after the last level and before the assertions and equalities are folded, writes wire w's value onto wire p, so bits [0, lu) of a
+ * witness row carry the computed statement (circuit.py adds the row 1 - p - w, an equality, for each pair: list it in h_equal and it holds by
+ * construction).  MFH_EINVAL, with its own mfh_last_error text and nothing allocated, besides the cases of mfh_circuit_create_ex (named after this
+ * function): p = 0 or p > nin; w = 0 or w > nin + ngates; w = p; a p given twice; a w that is the p of another pair; a gate operand or an assertion on
+ * an output wire (it has no value until the end); an equality touching an output wire other than (p, w) / (w, p) of its own pair; nout > 0 with
+ * h_outputs null.  nout = 0 gives exactly the program of mfh_circuit_create_ex (the same kernels and timing kinds).  With nout > 0 mfh_circuit_assign
+ * runs k_circuit_eval<true, true> / k_circuit_eval_global<true, true>, timing kinds "circuit_assign_out" and "circuit_assign_global_out". */
+int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t flags, mfh_circuit **out);
+/* every kind of program */
 void mfh_circuit_destroy(mfh_circuit *c);
 /* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
  * (bits_stride bytes) becomes the witness bit string of statement b: bit i - 1 = wire i, bits >= nin + ngates zero -- the layout mfh_prove_batch reads.
@@ -521,7 +532,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two

@@ -7,13 +7,19 @@ Legs (--leg, default all):
   * chain: a 60 000-gate XOR / NOT chain (depth 60 000) on 40 000 inputs, global program, 100 statements: its time and launch count;
   * chacha: the ChaCha20 block statement (words.ChaCha20Block: 896 inputs, 31 746 gates, 512 equalities) at D = 2^16, M = 43 690, --nb statements,
     both kinds of mfh_circuit_create_ex program (kinds "circuit_assign_ex" / "circuit_assign_global_ex");
-  * chacha_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^16 (median of --reps calls after one warm-up).
+  * chacha_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^16 (median of --reps calls after one warm-up);
+  * chacha_out: is the output pass free?  The ChaCha20 block statement (k_circuit_eval<true>) against the same circuit with its 512 block bits as
+    computed outputs (k_circuit_eval<true, true>), the two programs called in turn in one process, --reps calls each; then the same comparison on a
+    chain of 200 adds x += rotl(x, 1) (depth 6 400, 32 outputs), which tells a cost per output from a cost per level;
+  * sha256: the SHA-256 compression statement (words.Sha256Compress, chaining value = IV: 768 inputs, 60 930 gates, 256 outputs) at D = 2^17,
+    M = 87 381, device-memory program (kind "circuit_assign_global_out"), 255 and 1 020 statements;
+  * sha256_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^17.
 Printed per leg (one JSON line each, also appended to --out):
   * load: circuit_load once (levelising on the host, the upload);
   * call: the median wall time of circuit_assign (packing the input bits, staging, the launches, the copies back; the call synchronises);
   * kernel: the kernel launches alone (HIP events of mfh_set_timing, kind "circuit_assign" / "circuit_assign_global"), summed over a call's chunks;
   * python: Circuit.assign for --py statements (--py2 at 2^20), scaled to the batch (the rows are checked equal).
-dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
+dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove|chacha_out|sha256|sha256_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
 [--out FILE]"""
 import argparse
 import json
@@ -270,17 +276,189 @@ def leg_chacha_prove(a):
     return ok and bool(holds.all())
 
 
+def leg_chacha_out(a):
+    from c_lwe_snarks_amd import words
+
+    p = mf.Params(d=1 << 16, m=43690)
+    st = words.ChaCha20Block()
+    cc = st.circuit.compile(p)
+    # the same statement with the block computed: counter and nonce public, the 16 block words outputs (the same wires 1 .. 640), the key private
+    w = words.Words()
+    counter, nonce = w.public(), w.public(3)
+    key = w.private(8)
+    block = [w.output(x) for x in words.chacha20_block(w, key, counter, nonce)]
+    # (outputs are declared after the private key here, but the layout puts every public wire first: wires 129 .. 640, as in ChaCha20Block)
+    co = w.c.compile(p)
+    assert co.lu == cc.lu == 640 and co.nwires == cc.nwires and co.nrows == cc.nrows and np.array_equal(co.program, cc.program)
+    assert len(co.outputs) == 512 and co.wire(block[0][0]) == 129
+    rng = np.random.default_rng(8439)
+    bits = _chacha_statements(st, rng, a.nb)
+    ok = _alternate(a, p, "chacha20 block", cc, co, bits)
+    # a second pair with three times the depth and a sixteenth of the outputs: 200 adds x += rotl(x, 1), each waiting for the top bit of the one
+    # before, the result tied to a public word by equalities or declared an output.  A cost of the pass itself would follow nout; a difference in the level loop follows the depth.
+    p2 = mf.DEFAULT
+    pair = []
+    for out in (False, True):
+        w = words.Words()
+        r = None if out else w.public()
+        acc = w.private()
+        for _ in range(200):
+            acc = w.add(acc, w.rotl(acc, 1))
+        if out:
+            w.output(acc)
+        else:
+            w.assert_same_u32(acc, r)
+        pair.append(w.c.compile(p2))
+    assert np.array_equal(pair[0].program, pair[1].program) and len(pair[1].outputs) == 32
+    xv = rng.integers(0, 1 << 32, size=a.nb, dtype=np.uint64)
+    rv = xv.copy()
+    for _ in range(200):
+        rv = (rv + ((rv << np.uint64(1)) | (rv >> np.uint64(31)))) & np.uint64(0xFFFFFFFF)
+    bits2 = np.concatenate([words.pack(rv[:, None]), words.pack(xv[:, None])], axis=1)
+    return _alternate(a, p2, "200 adds x += rotl(x, 1)", pair[0], pair[1], bits2) and ok
+
+
+def _alternate(a, p, what, cc, co, bits):
+    """the LDS programs of cc (no outputs, k_circuit_eval<true>) and co (the same gates with outputs, k_circuit_eval<true, true>) called in turn"""
+    ctx = mf.Context(p, 0)
+    progs = {"circuit_assign_ex": ctx.circuit_load(cc, state="lds"), "circuit_assign_out": ctx.circuit_load(co, state="lds")}
+    for prog in progs.values():
+        ctx.circuit_assign(prog, bits)  # first calls: staging buffers
+    kern = {k: [] for k in progs}
+    outs = {}
+    ctx.set_timing(True)
+    for _ in range(a.reps):
+        for kind, prog in progs.items():
+            outs[kind], holds = ctx.circuit_assign(prog, bits)
+            kern[kind].append(ctx.timing_drain(kind)[1])
+    ctx.set_timing(False)
+    same = bool(np.array_equal(outs["circuit_assign_ex"], outs["circuit_assign_out"]))
+    med = {k: statistics.median(v) for k, v in kern.items()}
+    depth = _depth_ex(cc)
+    res = {"tool": "circuit_assign_time", "leg": "chacha_out", "circuit": what, "d": p.d, "m": p.m, "nb": len(bits), "nout": len(co.outputs),
+           "depth": depth, "reps": a.reps,
+           "kernel_ms_ex": round(med["circuit_assign_ex"], 4), "kernel_ms_ex_all": [round(x, 4) for x in kern["circuit_assign_ex"]],
+           "kernel_ms_out": round(med["circuit_assign_out"], 4), "kernel_ms_out_all": [round(x, 4) for x in kern["circuit_assign_out"]],
+           "out_minus_ex_us": round((med["circuit_assign_out"] - med["circuit_assign_ex"]) * 1e3, 2),
+           "out_minus_ex_ns_per_level": round((med["circuit_assign_out"] - med["circuit_assign_ex"]) * 1e6 / depth, 2),
+           "spread_ex_us": round((max(kern["circuit_assign_ex"]) - min(kern["circuit_assign_ex"])) * 1e3, 2), "rows_equal": same}
+    _emit(res, a.out)
+    for prog in progs.values():
+        prog.close()
+    ctx.close()
+    return same
+
+
+def _sha256_statements(st, rng, nb):
+    from c_lwe_snarks_amd import words
+
+    msgs = [bytes(rng.integers(0, 256, size=int(rng.integers(0, 56)), dtype=np.uint8).tolist()) for _ in range(nb)]
+    return msgs, np.stack([st.bits(words.sha256_pad(m)) for m in msgs])
+
+
+def leg_sha256(a):
+    import hashlib
+
+    from c_lwe_snarks_amd import words
+
+    p = mf.Params(d=1 << 17, m=87381)
+    st = words.Sha256Compress("iv")
+    t0 = time.perf_counter()
+    cc = st.circuit.compile(p)
+    compile_ms = (time.perf_counter() - t0) * 1e3
+    depth = _depth_ex(cc)
+    ctx = mf.Context(p, 0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    prog = ctx.circuit_load(cc, state="auto")
+    load_ms = (time.perf_counter() - t0) * 1e3
+    ok = prog.state == "global"
+    rng = np.random.default_rng(1802)
+    for nb in (255, 1020):
+        msgs, bits = _sha256_statements(st, rng, nb)
+        witness, holds, call, kern, launches = _time_calls(ctx, prog, bits, a.reps, "circuit_assign_global_out")
+        digests = all(st.digest_of(witness[b]) == hashlib.sha256(msgs[b]).digest() for b in range(nb))
+        npy = min(a.py2, nb)
+        t0 = time.perf_counter()
+        ref = [st.circuit.assign(bits[b, :256], bits[b, 256:], p) for b in range(npy)]
+        py_ms = (time.perf_counter() - t0) * 1e3 / npy
+        same = all(witness[b].tobytes() == ref[b] for b in range(npy)) and bool(holds.all()) and digests
+        ok = ok and same
+        res = {"tool": "circuit_assign_time", "leg": "sha256", "state": prog.state, "d": p.d, "m": p.m, "nb": nb, "npub": cc.lu, "npriv": 512,
+               "ngates": len(cc.program), "nout": len(cc.outputs), "depth": depth, "compile_ms": round(compile_ms, 1), "load_ms": round(load_ms, 3),
+               "launches_per_call": launches, "call_ms": round(statistics.median(call), 3), "call_ms_all": [round(x, 3) for x in call],
+               "kernel_ms": round(statistics.median(kern), 3), "kernel_ms_all": [round(x, 3) for x in kern],
+               "kernel_us_per_level": round(statistics.median(kern) * 1e3 / depth / max(launches, 1), 3),
+               "python_ms_per_statement": round(py_ms, 3), "python_statements_timed": npy, "python_ms_for_nb": round(py_ms * nb, 1),
+               "python_over_call": round(py_ms * nb / statistics.median(call), 1), "rows_equal": bool(same), "digests_equal_hashlib": bool(digests)}
+        _emit(res, a.out)
+    prog.close()
+    ctx.close()
+    return ok
+
+
+def leg_sha256_prove(a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+    from c_lwe_snarks_amd import words
+
+    p = mf.Params(d=1 << 17, m=87381)
+    st = words.Sha256Compress("iv")
+    cc = st.circuit.compile(p)
+    nb = 255
+    rng = np.random.default_rng(1803)
+    _, bits = _sha256_statements(st, rng, nb)
+    ctx = mf.Context(p, 0)
+    prog = ctx.circuit_load(cc, state="auto")
+    witness, holds = ctx.circuit_assign(prog, bits)
+    prog.close()
+    ctx.set_seed(bytes(range(40)))
+    t0 = time.perf_counter()
+    ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)
+    ctx.ssp_prepare(None)
+    ctx.sync()
+    rows_ms = (time.perf_counter() - t0) * 1e3
+    alpha, beta, s = (int(x) for x in rng.integers(1, circuit.P, size=3, dtype=np.uint64))
+    d_sk = ctx.to_device(ol.rand_values(rng, p.n, p.L, p.logq))
+    d_err = ctx.to_device(ol.rand_values(rng, 2 * p.d + p.m, p.L, 559))
+    t0 = time.perf_counter()
+    d_crs = ctx.setup_public(None, alpha, beta, s, cc.lu, d_sk, d_err).clone()
+    ctx.sync()
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    stmts = [witness[b].tobytes() for b in range(nb)]
+    deltas = [int(x) for x in rng.integers(0, circuit.P, size=nb, dtype=np.uint64)]
+    mags = [rng.integers(0, 256, size=400, dtype=np.uint8).tobytes() for _ in range(nb)]
+    signs = [bytes(rng.integers(0, 2, size=5, dtype=np.uint8).tolist()) for _ in range(nb)]
+    times = []
+    for _ in range(a.reps + 1):
+        ctx.sync()
+        t0 = time.perf_counter()
+        proofs = ctx.prove_batch_public(d_crs, None, cc.lu, stmts, deltas, mags, signs)
+        ctx.sync()
+        times.append((time.perf_counter() - t0) * 1e3)
+    vk = ctx.derive_vk(None, s, cc.lu)
+    ok = bool(ctx.to_host(ctx.verify_public(vk, cc.lu, alpha, beta, d_sk, proofs, stmts), np.uint8).all())
+    res = {"tool": "circuit_assign_time", "leg": "sha256_prove", "d": p.d, "m": p.m, "nb": nb, "lu": cc.lu, "nrows": cc.nrows,
+           "ssp_set_rows_prepare_ms": round(rows_ms, 1), "setup_public_ms": round(setup_ms, 1),
+           "prove_batch_public_ms": round(statistics.median(times[1:]), 3), "prove_ms_all": [round(x, 3) for x in times],
+           "holds_all": bool(holds.all()), "verified_all": ok}
+    _emit(res, a.out)
+    ctx.close()
+    return ok and bool(holds.all())
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove"])
+    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove", "chacha_out", "sha256", "sha256_prove"])
     ap.add_argument("--nb", type=int, default=1020)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign (default leg)")
-    ap.add_argument("--py2", type=int, default=4, help="statements timed through Circuit.assign (2p20 and chacha legs)")
+    ap.add_argument("--py2", type=int, default=4, help="statements timed through Circuit.assign (2p20, chacha and sha256 legs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ok = True
-    for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20), ("chacha", leg_chacha), ("chacha_prove", leg_chacha_prove)):
+    for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20), ("chacha", leg_chacha), ("chacha_prove", leg_chacha_prove),
+                     ("chacha_out", leg_chacha_out), ("sha256", leg_sha256), ("sha256_prove", leg_sha256_prove)):
         if a.leg in ("all", name):
             ok = fn(a) and ok
     return 0 if ok else 1
