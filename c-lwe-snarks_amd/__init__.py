@@ -99,7 +99,7 @@ EXPORTS = [
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
-    "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out",
+    "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
 ]
 
 
@@ -223,6 +223,7 @@ def load_library():
         "mfh_circuit_create_global": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_create_ex": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
         "mfh_circuit_create_out": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
+        "mfh_circuit_create_sum": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
         "mfh_circuit_destroy": (None, [vp]),
         "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
     }
@@ -265,10 +266,12 @@ class CircuitProgram:
     state: "lds" (mfh_circuit_create, at most CIRCUIT_MAX_WIRES wires) or "global" (mfh_circuit_create_global, wire state in device memory);
     extended: made by mfh_circuit_create_ex (the circuit has a gate beyond XOR / AND / OR / NOT or an equality), in the kind `state` names;
     outputs: the number of computed public outputs (Circuit.output): above 0 the program was made by mfh_circuit_create_out, in the kind `state` names,
-    and circuit_assign writes the computed statement into bits [0, lu) of every witness row"""
+    and circuit_assign writes the computed statement into bits [0, lu) of every witness row;
+    sums: the circuit has a weighted-sum gate (Circuit.wsum) and the program was made by mfh_circuit_create_sum, in the kind `state` names"""
 
-    def __init__(self, ctx, nin, ngates, handle, state="lds", extended=False, outputs=0):
+    def __init__(self, ctx, nin, ngates, handle, state="lds", extended=False, outputs=0, sums=False):
         self._ctx, self.nin, self.ngates, self._h, self.state, self.extended, self.outputs = ctx, nin, ngates, handle, state, extended, outputs
+        self.sums = sums
 
     def close(self):
         if self._h:
@@ -561,7 +564,8 @@ class Context:
         wire state in LDS, at most CIRCUIT_MAX_WIRES wires), "global" (mfh_circuit_create_global: in device memory, up to m - 1 wires) or "auto"
         (lds up to CIRCUIT_MAX_WIRES wires, else global).  A circuit with a MAJ / SUM3 / CONST / LUT2 gate or an equality (Compiled.program, Compiled.equal)
         goes through mfh_circuit_create_ex in the same kind; the others through the two creates above.  A circuit with computed public outputs
-        (Circuit.output, Compiled.outputs) goes through mfh_circuit_create_out; one without them loads exactly as before."""
+        (Circuit.output, Compiled.outputs) goes through mfh_circuit_create_out; one without them loads exactly as before.  A circuit with a weighted-sum
+        gate (Circuit.wsum, Compiled.terms) goes through mfh_circuit_create_sum, and only such a circuit."""
         if state not in ("lds", "global", "auto"):
             raise MfhError(f"circuit_load: state must be 'lds', 'global' or 'auto', got {state!r}")
         gates = np.ascontiguousarray(compiled.gates, dtype=np.uint32).reshape(-1, 3)
@@ -570,12 +574,19 @@ class Context:
         program = np.ascontiguousarray(getattr(compiled, "program", np.zeros((0, 4))), dtype=np.uint32).reshape(-1, 4)
         equal = np.ascontiguousarray(getattr(compiled, "equal", np.zeros((0, 2))), dtype=np.uint32).reshape(-1, 2)
         outputs = np.ascontiguousarray(getattr(compiled, "outputs", np.zeros((0, 2))), dtype=np.uint32).reshape(-1, 2)
+        terms = np.ascontiguousarray(getattr(compiled, "terms", np.zeros((0, 2))), dtype=np.uint32).reshape(-1, 2)
+        sums = bool((program[:, 0] == 8).any())  # MFH_GATE_WSUM
         extended = len(equal) > 0 or len(outputs) > 0 or bool((program[:, 0] > 3).any())
         nin = compiled.nwires - len(gates)
         if state == "auto":
             state = "lds" if compiled.nwires <= CIRCUIT_MAX_WIRES else "global"
         h = ctypes.c_void_p()
-        if len(outputs):
+        if sums:
+            self._chk(self.lib.mfh_circuit_create_sum(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
+                                                      ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data), len(outputs),
+                                                      ctypes.c_void_p(outputs.ctypes.data), len(terms), ctypes.c_void_p(terms.ctypes.data),
+                                                      CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
+        elif len(outputs):
             self._chk(self.lib.mfh_circuit_create_out(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
                                                       ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data), len(outputs),
                                                       ctypes.c_void_p(outputs.ctypes.data), CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
@@ -586,7 +597,7 @@ class Context:
         else:
             create = self.lib.mfh_circuit_create if state == "lds" else self.lib.mfh_circuit_create_global
             self._chk(create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data), ctypes.byref(h)))
-        return CircuitProgram(self, nin, len(gates), h, state, extended, len(outputs))
+        return CircuitProgram(self, nin, len(gates), h, state, extended, len(outputs), sums)
 
     def circuit_assign(self, prog, bits):
         """witnesses of nb statements on the device (mfh_circuit_assign): bits = uint8 [nb, nin] of 0 / 1, public bits then private bits (whatever stands

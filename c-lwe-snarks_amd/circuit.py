@@ -1,7 +1,7 @@
 """Boolean circuits as square span programs: the front end of mfh_ssp_from_rows (include/mfhip.h).
 
 A circuit is built from public and private input wires and gates -- AND / OR / XOR / NOT, MAJ and its paired SUM3 (full_add), any two-input function
-(gate, NAND, NOR, XNOR, ANDN, ORN) and constants (const) -- with assertions that a wire is 0 or 1 and that two wires are equal.  compile(params) turns it
+(gate, NAND, NOR, XNOR, ANDN, ORN), constants (const) and weighted sums (wsum) -- with assertions that a wire is 0 or 1 and that two wires are equal.  compile(params) turns it
 into constraint rows, one row per constraint point r_j = j + 2.  Row j asks  v_0(r_j) + sum_i a_i v_i(r_j)  in {-1, +1}, where a_i is the bit on wire i.
 Context.ssp_from_rows interpolates the rows into the SSP on the device.
 
@@ -24,9 +24,14 @@ Rows, all values mod p: every wire w gets 2w - 1 (it is 0 or 1).  Then each gate
         XOR (6) : a + b + c - 1      XNOR (9) : a + b - c
         one 1, at (x, y)    : 2a' + 2b' - 4c - 1      (a' = a if x = 1 else 1 - a; b' likewise from y)
         three 1s, 0 at (x, y): 2a' + 2b' + 4c - 5
+    o_0 .. o_{n-1} = WSUM(terms), terms = (x_e, shift_e), n = bitlength(sum_e 2^shift_e) <= 24: TWO rows for the n output wires together,
+        2X - 1  and  2X + 1,   X = sum_e 2^shift_e x_e - sum_i 2^i o_i
+    The first is +-1 iff X in {0, 1} mod p, the second iff X in {0, -1}: together X = 0 mod p.  Operands and outputs are bits (their bit rows), so
+    |X| < 2^n <= 2^24 < p and X = 0 over the integers: the o_i are the binary expansion of the sum.  A wire may occur in several terms.
 Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py checks all eight (a, b, c) of the first four gates,
 tests/test_circuit_gates_cpu.py every other row over all its inputs).  SUM3 is sound only because MAJ's row forces k, which is why full_add emits the
-two back to back.  Row order: the bit rows, one row per gate in creation order, the value assertions, then the equalities in creation order.
+two back to back.  Row order: the bit rows, one row per gate in creation order (a wsum's two rows at the place of its first output wire, none for
+its other output wires), the value assertions, then the equalities in creation order.
 
     c = Circuit()
     x = c.private(8); z = c.public()
@@ -60,6 +65,9 @@ _M1 = P - 1  # -1 mod p
 GATE_XOR, GATE_AND, GATE_OR, GATE_NOT = 0, 1, 2, 3
 # ... and of Compiled.program (mfh_circuit_create_ex)
 GATE_MAJ, GATE_SUM3, GATE_CONST0, GATE_CONST1 = 4, 5, 6, 7
+# ... and of the programs of mfh_circuit_create_sum: a head (GATE_WSUM, first_term, nterms, nbits), then nbits - 1 records (GATE_WSUM_BIT, i, 0, 0)
+GATE_WSUM, GATE_WSUM_BIT = 8, 9
+WSUM_MAX_BITS = 24  # the most output wires of one wsum gate: |X| < 2^24 keeps the two rows sound mod p
 
 
 def GATE_LUT2(tt):
@@ -137,6 +145,8 @@ class Compiled:
     equal: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
     # computed public outputs (mfh_circuit_create_out): outputs[e] = (p, w), public wire p defined as wire w, in declaration order; each pair is also in equal
     outputs: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
+    # the terms of the wsum gates (mfh_circuit_create_sum): terms[e] = (wire, shift); a head record of program names its slice, sorted by shift
+    terms: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), dtype=np.uint32), compare=False)
 
     def wire(self, w: Wire) -> int:
         return self.wires[w.node]
@@ -144,7 +154,9 @@ class Compiled:
 
 class Circuit:
     def __init__(self):
-        self._nodes = []    # ("pub",) / ("priv",) / ("out", w) / (gate, a, b) / ("not", a) / ("maj" | "sum3", a, b, c) / ("lut", tt, a, b) / ("const", v): operands are node indices
+        # ("pub",) / ("priv",) / ("out", w) / (gate, a, b) / ("not", a) / ("maj" | "sum3", a, b, c) / ("lut", tt, a, b) / ("const", v) /
+        # ("wsum", nbits, ((a, shift), ...)) / ("wsumbit", i, head): operands are node indices
+        self._nodes = []
         self._asserts = []  # (node, value)
         self._equal = []    # (node, node) of assert_same
         self._const = {}    # value -> node of the shared constant wire
@@ -240,6 +252,26 @@ class Circuit:
         """a OR NOT b"""
         return self.gate(TT_ORN, a, b)
 
+    def wsum(self, terms):
+        """the binary expansion of sum_e 2^shift_e * x_e for terms = [(wire x_e, shift_e), ...], a wire as often as wanted: nbits = bitlength(sum_e
+        2^shift_e) output wires, least significant first, and two rows for all of them.  The terms are kept sorted by shift (stable)."""
+        terms = list(terms)
+        if not terms:
+            raise CircuitError("wsum: no terms")
+        for w, sh in terms:
+            self._check(w)
+            if not isinstance(sh, (int, np.integer)) or sh < 0:
+                raise CircuitError("wsum: a shift must be a non-negative integer")
+        terms.sort(key=lambda t: t[1])
+        nbits = sum(1 << int(sh) for _, sh in terms).bit_length()
+        if nbits > WSUM_MAX_BITS:
+            raise CircuitError(f"wsum: the sum needs {nbits} bits, a gate has at most {WSUM_MAX_BITS}")
+        self._nodes.append(("wsum", nbits, tuple((w.node, int(sh)) for w, sh in terms)))
+        head = len(self._nodes) - 1
+        for i in range(1, nbits):
+            self._nodes.append(("wsumbit", i, head))
+        return [Wire(head + i) for i in range(nbits)]
+
     def const(self, value: int) -> Wire:
         """the wire that is always `value` (0 or 1): one shared wire per value and circuit, made on first use"""
         if value not in (0, 1):
@@ -248,6 +280,12 @@ class Circuit:
             self._nodes.append(("const", int(value)))
             self._const[value] = len(self._nodes) - 1
         return Wire(self._const[value])
+
+    def const_value(self, w: Wire):
+        """0 or 1 if w is one of the circuit's constant wires (const), else None"""
+        self._check(w)
+        node = self._nodes[w.node]
+        return node[1] if node[0] == "const" else None
 
     def assert_same(self, a: Wire, b: Wire):
         """assert that wires a and b carry the same bit: one row, no wire"""
@@ -281,7 +319,8 @@ class Circuit:
         """the constraint rows for an SSP of params.d points and params.m wires; CircuitError if the circuit needs more than m - 1 wires or d - 1 rows"""
         wires, nw = self._layout()
         ngates = nw - len(self._pub) - len(self._priv)
-        nrows = nw + ngates + len(self._asserts) + len(self._equal)
+        # one row per gate wire, but two for the nbits wires of a wsum
+        nrows = nw + ngates - sum(n[1] - 2 for n in self._nodes if n[0] == "wsum") + len(self._asserts) + len(self._equal)
         if nw > params.m - 1:
             raise CircuitError(f"the circuit needs {nw} wires, the SSP has {params.m - 1} (m - 1)")
         if nrows > params.d - 1:
@@ -296,6 +335,13 @@ class Circuit:
                 continue
             if kind == "lut":
                 rows.append(_modrow(*lut2_row(node[1], wires[node[2]], wires[node[3]], c)))
+                continue
+            if kind == "wsumbit":
+                continue
+            if kind == "wsum":  # 2X - 1 and 2X + 1, X = sum 2^shift x - sum 2^i o_i
+                x2 = [(wires[a], 2 << sh) for a, sh in node[2]] + [(c + k, P - (2 << k)) for k in range(node[1])]
+                rows.append(x2 + [(0, _M1)])
+                rows.append(x2 + [(0, 1)])
                 continue
             a = wires[node[1]]
             if kind == "not":
@@ -325,13 +371,17 @@ class Circuit:
         wire = np.array([w for r in rows for w, _ in r], dtype=np.uint32)
         coef = np.array([x for r in rows for _, x in r], dtype=np.uint32)
         program = np.array([self._record(n, wires) for n in self._nodes if n[0] not in ("pub", "priv", "out")], dtype=np.uint32).reshape(-1, 4)
-        gates = np.ascontiguousarray(program[:, :3])
         asserts = np.array([(wires[node], value) for node, value in self._asserts], dtype=np.uint32).reshape(-1, 2)
         equal = np.array([(wires[a], wires[b]) for a, b in self._equal], dtype=np.uint32).reshape(-1, 2)
         outputs = np.array([(wires[p], wires[w]) for p, w in self._outputs], dtype=np.uint32).reshape(-1, 2)
+        terms = np.array([(wires[a], sh) for n in self._nodes if n[0] == "wsum" for a, sh in n[2]], dtype=np.uint32).reshape(-1, 2)
+        first = np.cumsum([0] + [len(n[2]) for n in self._nodes if n[0] == "wsum"])  # a head's first_term: the heads' slices follow each other
+        heads = np.flatnonzero(program[:, 0] == GATE_WSUM)
+        program[heads, 1] = first[:-1]
+        gates = np.ascontiguousarray(program[:, :3])
         self._params = params
         return Compiled(rows=(row_ptr, wire, coef), lu=len(self._pub), wires=tuple(wires), nrows=nrows, nwires=nw, gates=gates, asserts=asserts,
-                        program=program, equal=equal, outputs=outputs)
+                        program=program, equal=equal, outputs=outputs, terms=terms)
 
     @staticmethod
     def _record(node, wires):
@@ -341,6 +391,10 @@ class Circuit:
             return (GATE_CONST1 if node[1] else GATE_CONST0, 0, 0, 0)
         if kind == "lut":
             return (GATE_LUT2(node[1]), wires[node[2]], wires[node[3]], 0)
+        if kind == "wsum":  # first_term is filled in by compile
+            return (GATE_WSUM, 0, len(node[2]), node[1])
+        if kind == "wsumbit":
+            return (GATE_WSUM_BIT, node[1], 0, 0)
         if kind in ("maj", "sum3"):
             return (_OPS[kind], wires[node[1]], wires[node[2]], wires[node[3]])
         return (_OPS[kind], wires[node[1]], wires[node[-1]], 0)
@@ -377,6 +431,10 @@ class Circuit:
                 val[i] = node[1]
             elif kind == "out":
                 val[i] = val[node[1]]
+            elif kind == "wsum":
+                total = sum(val[a] << sh for a, sh in node[2])
+                for k in range(node[1]):
+                    val[i + k] = (total >> k) & 1
         return val
 
     def holds(self, public_bits, private_bits) -> bool:

@@ -18,6 +18,14 @@
 // mfh_circuit_create_out adds computed public outputs to an extended program: pairs (p, w) of an input wire p whose value is defined as that of wire w.
 // The OUT = true instantiations (EX = true only) copy st[w] to st[p] for every pair after the last level, before the assertions and equalities are
 // folded and the witness is written: bits [0, lu) of a witness row then carry the computed statement, whatever the caller put at p's input position.
+//
+// mfh_circuit_create_sum adds weighted-sum gates (MFH_GATE_WSUM): the SUM = true instantiations (EX = true only).  A head is served by one wave, the other
+// way round from every other gate: lane j holds STATEMENT j's sum T_j = sum_e (bit j of term e's word) << shift_e as an ordinary integer (T < 2^24), and
+// output wire i's word is the ballot of bit i of T over the lanes -- the transposes this file already does at both ends of a launch.  The wave first
+// gathers up to 64 terms, one per lane (the term record and its wire word: one memory latency for 64 terms, in LDS or device memory alike), then walks them
+// with v_readlane: four register instructions per term, no memory access in the loop, no counter array.  Within a level the heads come first in the gate
+// order and go to the waves from the last one down, while the level's one-word gates fill the threads from the first wave up: a level of the SHA-256
+// statement (2 - 4 heads, a few hundred cheap gates at most) then has no wave that does both.
 #include <algorithm>
 #include <string>
 #include <type_traits>
@@ -54,19 +62,47 @@ __device__ __forceinline__ uint32_t gate_ex(uint32_t op, uint32_t x, uint32_t y,
   }
 }
 
+// One WSUM head, by one whole wave (every argument but lane is wave-uniform): terms[first .. first + nterms) = wire | shift << 24 in non-decreasing shift
+// order, output wire i (i < nbits <= 24) = o + i.  Both halves of the wave compute the same 32 sums (j = lane & 31): the term walk is uniform.
+__device__ __forceinline__ void wsum_head(uint32_t *st, const uint32_t *__restrict__ terms, uint32_t first, uint32_t nterms, uint32_t nbits, uint32_t o,
+                                          uint32_t lane) {
+  const uint32_t j = lane & 31;
+  uint32_t T = 0;
+  uint32_t next = lane < nterms ? terms[first + lane] : 0;  // the term records one gather ahead: their latency hides behind the walk
+  for (uint32_t e0 = 0; e0 < nterms; e0 += 64) {
+    const uint32_t n = min(64u, nterms - e0), t = next;
+    next = e0 + 64 + lane < nterms ? terms[first + e0 + 64 + lane] : 0;
+    const uint32_t word = lane < n ? st[t & 0xffffff] : 0, sh = t >> 24;
+    for (uint32_t t = 0; t < n; t++) {
+      const uint32_t w = __builtin_amdgcn_readlane(word, t), s = __builtin_amdgcn_readlane(sh, t);
+      T += ((w >> j) & 1) << s;
+    }
+  }
+  uint32_t mine = 0;
+  for (uint32_t i = 0; i < nbits; i++) {
+    const uint64_t bm = __ballot((T >> i) & 1);
+    if (lane == i) mine = (uint32_t)bm;
+  }
+  if (lane < nbits) st[o + lane] = mine;
+}
+
 // Gate records sorted by level; level L is gates [lp[L], lp[L + 1]).  asserts[e] = {wire, value}.
 //   EX = false (mfh_circuit_create):    gates[g] = uint2 {a | b << 16, out | op << 16}, ops XOR / AND / OR / NOT; equal / nequal unused
 //   EX = true  (mfh_circuit_create_ex): gates[g] = uint4 {a, b, c, out | op << 24}, every op; equal[e] = {a, b} folds into holds with the assertions
 // The extra arguments come last, so the EX = false instantiation is the kernel as it was before extended programs existed, instruction for instruction.
 //   OUT = true (mfh_circuit_create_out, nout > 0): outputs[e] = {p, w}: st[p] = st[w] after the last level (no w is a p, every p once: no order among pairs).
 // outputs / nout come last again, and the OUT = false instantiations never read them: their code is what it was before outputs existed.
-template <bool EX, bool OUT = false>
+//   SUM = true (mfh_circuit_create_sum with a WSUM gate): heads {first_term, nterms, nbits, out | MFH_GATE_WSUM << 24} are the first records of their
+// level, [lp[L], hp[L]); WSUM_BIT records have no device record.  terms / hp come last, and the SUM = false instantiations never read them.
+template <bool EX, bool OUT = false, bool SUM = false>
 __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<EX, uint4, uint2> *__restrict__ gates, const uint32_t *__restrict__ lp,
                                                       uint32_t nlev, const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                       const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt, uint8_t *__restrict__ out,
                                                       size_t bits_stride, uint8_t *__restrict__ holds, const uint2 *__restrict__ equal, uint32_t nequal,
-                                                      const uint2 *__restrict__ outputs, uint32_t nout) {
+                                                      const uint2 *__restrict__ outputs, uint32_t nout, const uint32_t *__restrict__ terms,
+                                                      const uint32_t *__restrict__ hp) {
   static_assert(EX || !OUT, "outputs belong to extended programs");
+  static_assert(EX || !SUM, "weighted sums belong to extended programs");
   __shared__ uint32_t st[CWORDS];
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
@@ -98,8 +134,17 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<E
   // ---- gates, level by level
   uint32_t g1 = nlev ? lp[0] : 0;
   for (uint32_t lv = 0; lv < nlev; lv++) {
-    const uint32_t g0 = g1;
+    uint32_t g0 = g1;
     g1 = lp[lv + 1];
+    if constexpr (SUM) {  // the level's heads, one wave each, from the last wave down
+      const uint32_t h1 = hp[lv], uw = __builtin_amdgcn_readfirstlane(nwaves - 1 - wave);
+      for (uint32_t h = g0 + uw; h < h1; h += nwaves) {
+        const uint4 r = gates[h];
+        wsum_head(st, terms, __builtin_amdgcn_readfirstlane(r.x), __builtin_amdgcn_readfirstlane(r.y), __builtin_amdgcn_readfirstlane(r.z),
+                  __builtin_amdgcn_readfirstlane(r.w & 0xffffff), lane);
+      }
+      g0 = h1;
+    }
     for (uint32_t g = g0 + tid; g < g1; g += CWG) {
       const auto r = gates[g];
       if constexpr (EX) {
@@ -162,14 +207,15 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval(const std::conditional_t<E
 // The kernel above with the wire words in device memory: st = this block's column of colw words (wire i at st[i]), gates[g] = {a, b, out, op}
 // (EX: {a, b, c, out | op << 24}, and equal / nequal as above).  A column is read and written by its own workgroup only; __syncthreads() (workgroup-scope
 // release / acquire) orders the levels, and the output pass after them.
-template <bool EX, bool OUT = false>
+template <bool EX, bool OUT = false, bool SUM = false>
 __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__restrict__ gates, const uint32_t *__restrict__ lp, uint32_t nlev,
                                                              const uint2 *__restrict__ asserts, uint32_t nasserts, uint32_t nin, uint32_t nw,
                                                              uint32_t *state, size_t colw, const uint8_t *__restrict__ in, size_t in_stride, uint32_t nstmt,
                                                              uint8_t *__restrict__ out, size_t bits_stride, uint8_t *__restrict__ holds,
                                                              const uint2 *__restrict__ equal, uint32_t nequal, const uint2 *__restrict__ outputs,
-                                                             uint32_t nout) {
+                                                             uint32_t nout, const uint32_t *__restrict__ terms, const uint32_t *__restrict__ hp) {
   static_assert(EX || !OUT, "outputs belong to extended programs");
+  static_assert(EX || !SUM, "weighted sums belong to extended programs");
   __shared__ uint32_t hw;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CWG / 64;
   const uint32_t s0 = blockIdx.x * CSTMT, j = lane & 31;
@@ -201,8 +247,17 @@ __global__ __launch_bounds__(CWG) void k_circuit_eval_global(const uint4 *__rest
   // ---- gates, level by level; GUNROLL gates per thread in flight (no gate of a level reads another's output)
   uint32_t g1 = nlev ? lp[0] : 0;
   for (uint32_t lv = 0; lv < nlev; lv++) {
-    const uint32_t g0 = g1;
+    uint32_t g0 = g1;
     g1 = lp[lv + 1];
+    if constexpr (SUM) {  // the level's heads, one wave each, from the last wave down
+      const uint32_t h1 = hp[lv], uw = __builtin_amdgcn_readfirstlane(nwaves - 1 - wave);
+      for (uint32_t h = g0 + uw; h < h1; h += nwaves) {
+        const uint4 r = gates[h];
+        wsum_head(st, terms, __builtin_amdgcn_readfirstlane(r.x), __builtin_amdgcn_readfirstlane(r.y), __builtin_amdgcn_readfirstlane(r.z),
+                  __builtin_amdgcn_readfirstlane(r.w & 0xffffff), lane);
+      }
+      g0 = h1;
+    }
     for (uint32_t g = g0 + tid; g < g1; g += GUNROLL * CWG) {
       uint4 r[GUNROLL];
       uint32_t x[GUNROLL], y[GUNROLL], z[GUNROLL];
@@ -284,27 +339,34 @@ struct mfh_circuit {
   bool global = false;  // false: wire state in LDS (k_circuit_eval); true: mfh_circuit_create_global / MFH_CIRCUIT_GLOBAL (k_circuit_eval_global, ctx->circ_state)
   bool ex = false;      // made by mfh_circuit_create_ex: 16-byte {a, b, c, out | op << 24} records and equalities, the EX = true kernels
   uint32_t nin = 0, ngates = 0, nasserts = 0, nequal = 0, nout = 0, nlev = 0;  // nout > 0: mfh_circuit_create_out with outputs, the OUT = true kernels
-  void *mem = nullptr;  // gates (uint2 or uint4 records, by level) | asserts (uint2) | equal (uint2) | outputs (uint2) | level_ptr (nlev + 1 words)
+  bool sum = false;  // mfh_circuit_create_sum with a WSUM gate: the SUM = true kernels (ngates counts the WSUM_BIT records, which have no device record)
+  // gates (uint2 or uint4 records, by level) | asserts (uint2) | equal (uint2) | outputs (uint2) | level_ptr (nlev + 1 words) | sum: head_end (nlev words) | terms
+  void *mem = nullptr;
   const void *gates = nullptr;
   const uint2 *asserts = nullptr;
   const uint2 *equal = nullptr;
   const uint2 *outputs = nullptr;
   const uint32_t *lp = nullptr;
+  const uint32_t *hp = nullptr;     // sum: hp[L] = the end of the heads of level L + 1, which are its first records
+  const uint32_t *terms = nullptr;  // sum: wire | shift << 24
 };
 
 namespace {
 
 // every kind: validate, level, sort by level, upload.  Records: mfh_circuit_create {a | b << 16, out | op << 16}; mfh_circuit_create_global {a, b, out, op};
 // mfh_circuit_create_ex {a, b, c, out | op << 24} in both kinds.  ex programs take 4-word gates (op, a, b, c), the others 3-word (op, a, b).
-// h_outputs: nout pairs (p, w) of mfh_circuit_create_out (ex programs only).
+// h_outputs: nout pairs (p, w) of mfh_circuit_create_out (ex programs only).  wsum: mfh_circuit_create_sum, which alone accepts WSUM / WSUM_BIT records
+// and their nterms pairs (wire, shift) in h_terms; a program without a WSUM gate comes out as that of mfh_circuit_create_out.
 int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts,
-                   const uint32_t *h_asserts, uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, mfh_circuit **out) {
+                   const uint32_t *h_asserts, uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, mfh_circuit **out,
+                   bool wsum = false, uint32_t nterms = 0, const uint32_t *h_terms = nullptr) {
   if (!ctx || !out) return MFH_EINVAL;
   *out = nullptr;
   const std::string fn = std::string(name) + ": ";
   if ((ngates && !h_gates) || (nasserts && !h_asserts)) { ctx->err = fn + "gates / assertions without their array"; return MFH_EINVAL; }
   if (nequal && !h_equal) { ctx->err = fn + "equalities without their array"; return MFH_EINVAL; }
   if (nout && !h_outputs) { ctx->err = fn + "outputs without their array"; return MFH_EINVAL; }
+  if (nterms && !h_terms) { ctx->err = fn + "terms without their array"; return MFH_EINVAL; }
   const uint64_t nw = (uint64_t)nin + ngates;
   if (nw > ctx->P.m - 1) { ctx->err = fn + "nin + ngates > m - 1"; return MFH_EINVAL; }
   if (!global && nw > MFH_CIRCUIT_MAX_WIRES) { ctx->err = fn + "nin + ngates > MFH_CIRCUIT_MAX_WIRES (the wire state must fit 128 KiB of LDS)"; return MFH_EINVAL; }
@@ -327,7 +389,8 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
   }
   const auto is_out = [&](uint32_t w) { return nout && w <= nin && source[w] != 0; };
   std::vector<uint32_t> lvl(nw + 1, 0);
-  uint32_t nlev = 0;
+  uint32_t nlev = 0, nheads = 0, nbitrec = 0;
+  uint32_t run_o = 0, run_n = 0, run_i = 0;  // inside a head's run of WSUM_BIT records: the head's output wire, its nbits, the next i
   for (uint32_t g = 0; g < ngates; g++) {
     const uint32_t *q = h_gates + gw * g;
     const uint32_t op = q[0], a = q[1], b = q[2], o = nin + 1 + g;
@@ -339,6 +402,40 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
       continue;
     }
     const uint32_t c = q[3];
+    if (wsum && run_i < run_n) {  // the records after a head
+      if (op != MFH_GATE_WSUM_BIT || a != run_i || b != 0 || c != 0) { ctx->err = fn + "a WSUM head not followed by its WSUM_BIT records in order"; return MFH_EINVAL; }
+      lvl[o] = lvl[run_o];
+      run_i++;
+      nbitrec++;
+      continue;
+    }
+    if (wsum && op == MFH_GATE_WSUM_BIT) { ctx->err = fn + "a WSUM_BIT record without a head"; return MFH_EINVAL; }
+    if (wsum && op == MFH_GATE_WSUM) {  // (first_term, nterms, nbits) = (a, b, c)
+      if (b == 0) { ctx->err = fn + "a WSUM gate with nterms = 0"; return MFH_EINVAL; }
+      if ((uint64_t)a + b > nterms) { ctx->err = fn + "a WSUM gate's term range lies outside the term array"; return MFH_EINVAL; }
+      if (c > 24) { ctx->err = fn + "a WSUM gate with nbits > 24"; return MFH_EINVAL; }
+      uint64_t tmax = 0;
+      uint32_t top = 0, prev = 0;
+      for (uint32_t e = 0; e < b; e++) {
+        const uint32_t w = h_terms[2 * ((size_t)a + e)], sh = h_terms[2 * ((size_t)a + e) + 1];
+        if (w == 0 || w >= o) { ctx->err = fn + "a WSUM term wire is 0 or not below the head's output wire"; return MFH_EINVAL; }
+        if (is_out(w)) { ctx->err = fn + "a WSUM term reads an output wire"; return MFH_EINVAL; }
+        if (sh >= c) { ctx->err = fn + "a WSUM term with shift >= nbits"; return MFH_EINVAL; }
+        if (sh < prev) { ctx->err = fn + "WSUM terms not in non-decreasing shift order"; return MFH_EINVAL; }
+        prev = sh;
+        tmax += (uint64_t)1 << sh;
+        top = std::max(top, lvl[w]);
+      }
+      uint32_t len = 0;
+      while (tmax >> len) len++;
+      if (len != c) { ctx->err = fn + "a WSUM gate whose nbits is not the bit length of the sum of 2^shift"; return MFH_EINVAL; }
+      if ((uint64_t)g + c > ngates) { ctx->err = fn + "a WSUM head not followed by its WSUM_BIT records in order"; return MFH_EINVAL; }
+      lvl[o] = 1 + top;
+      nlev = std::max(nlev, lvl[o]);
+      run_o = o; run_n = c; run_i = 1;
+      nheads++;
+      continue;
+    }
     if ((op > MFH_GATE_CONST1 && op < 16) || op >= 32) { ctx->err = fn + "unknown gate op"; return MFH_EINVAL; }
     if (op == MFH_GATE_CONST0 || op == MFH_GATE_CONST1) {
       if (a | b | c) { ctx->err = fn + "a CONST gate with an operand other than 0"; return MFH_EINVAL; }
@@ -361,6 +458,7 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
     }
     nlev = std::max(nlev, lvl[o]);
   }
+  if (run_i < run_n) { ctx->err = fn + "a WSUM head not followed by its WSUM_BIT records in order"; return MFH_EINVAL; }
   for (uint32_t e = 0; e < nasserts; e++) {
     const uint32_t w = h_asserts[2 * e], v = h_asserts[2 * e + 1];
     if (w == 0 || w > nw) { ctx->err = fn + "an assertion on wire 0 or above nin + ngates"; return MFH_EINVAL; }
@@ -376,18 +474,30 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
       return MFH_EINVAL;
     }
   }
-  // counting sort by level (stable: creation order within a level)
-  std::vector<uint32_t> lp(nlev + 1, 0);
-  for (uint32_t g = 0; g < ngates; g++) lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
+  // counting sort by level (stable: creation order within a level; with WSUM gates a level's heads come first, and WSUM_BIT records are dropped)
+  const bool sum = nheads != 0;
+  const auto opof = [&](uint32_t g) { return h_gates[gw * g]; };
+  const auto is_head = [&](uint32_t g) { return sum && opof(g) == MFH_GATE_WSUM; };
+  const auto is_bit = [&](uint32_t g) { return sum && opof(g) == MFH_GATE_WSUM_BIT; };
+  const uint32_t nrec = ngates - nbitrec;  // device records
+  std::vector<uint32_t> lp(nlev + 1, 0), hp(sum ? nlev : 0, 0);
+  for (uint32_t g = 0; g < ngates; g++) {
+    if (is_bit(g)) continue;
+    lp[lvl[nin + 1 + g]]++;  // lp[L] = gates of level L (L >= 1) ...
+    if (is_head(g)) hp[lvl[nin + 1 + g] - 1]++;  // hp[L] = heads of level L + 1 ...
+  }
   for (uint32_t L = 0, acc = 0; L <= nlev; L++) { const uint32_t n = L < nlev ? lp[L + 1] : 0; lp[L] = acc; acc += n; }  // ... then lp[L] = first gate of level L + 1
+  for (uint32_t L = 0; sum && L < nlev; L++) hp[L] += lp[L];                                                           // ... and hp[L] = the end of its heads
   const size_t rec = global || ex ? 4 : 2;  // words per device gate record
-  std::vector<uint32_t> host(rec * ngates + 2 * (size_t)nasserts + 2 * (size_t)nequal + 2 * (size_t)nout + nlev + 1);
+  const size_t tail_at = rec * nrec + 2 * (size_t)nasserts + 2 * (size_t)nequal + 2 * (size_t)nout + nlev + 1;
+  std::vector<uint32_t> host(tail_at + (sum ? (size_t)nlev + nterms : 0));
   {
-    std::vector<uint32_t> pos(lp.begin(), lp.end());
+    std::vector<uint32_t> pos(lp.begin(), lp.end()), cpos(hp.begin(), hp.end());  // next slot of a level: heads from lp[L], the others from hp[L]
     for (uint32_t g = 0; g < ngates; g++) {
+      if (is_bit(g)) continue;
       const uint32_t *q = h_gates + gw * g;
       const uint32_t op = q[0], a = q[1], b = op == MFH_GATE_NOT ? a : q[2], o = nin + 1 + g;
-      uint32_t *r = &host[rec * pos[lvl[o] - 1]++];
+      uint32_t *r = &host[rec * (sum && !is_head(g) ? cpos : pos)[lvl[o] - 1]++];
       if (ex) {
         r[0] = a; r[1] = b; r[2] = q[3]; r[3] = o | op << 24;
       } else if (global) {
@@ -397,10 +507,14 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
         r[1] = o | op << 16;
       }
     }
-    std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + rec * ngates);
-    std::copy(h_equal, h_equal + (size_t)2 * nequal, host.begin() + rec * ngates + 2 * nasserts);
-    std::copy(h_outputs, h_outputs + (size_t)2 * nout, host.begin() + rec * ngates + 2 * nasserts + 2 * nequal);
-    std::copy(lp.begin(), lp.end(), host.begin() + rec * ngates + 2 * nasserts + 2 * nequal + 2 * nout);
+    std::copy(h_asserts, h_asserts + (size_t)2 * nasserts, host.begin() + rec * nrec);
+    std::copy(h_equal, h_equal + (size_t)2 * nequal, host.begin() + rec * nrec + 2 * nasserts);
+    std::copy(h_outputs, h_outputs + (size_t)2 * nout, host.begin() + rec * nrec + 2 * nasserts + 2 * nequal);
+    std::copy(lp.begin(), lp.end(), host.begin() + rec * nrec + 2 * nasserts + 2 * nequal + 2 * nout);
+    if (sum) {
+      std::copy(hp.begin(), hp.end(), host.begin() + tail_at);
+      for (uint32_t e = 0; e < nterms; e++) host[tail_at + nlev + e] = h_terms[2 * (size_t)e] | h_terms[2 * (size_t)e + 1] << 24;
+    }
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   mfh_circuit *c = new mfh_circuit();
@@ -413,6 +527,7 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
   c->nequal = nequal;
   c->nout = nout;
   c->nlev = nlev;
+  c->sum = sum;
   if (hipMalloc(&c->mem, host.size() * 4) != hipSuccess) {
     (void)hipGetLastError();
     delete c;
@@ -426,10 +541,14 @@ int circuit_create(mfh_ctx *ctx, const char *name, bool global, bool ex, uint32_
     return MFH_EDEVICE;
   }
   c->gates = c->mem;
-  c->asserts = (const uint2 *)((const uint32_t *)c->mem + rec * ngates);
+  c->asserts = (const uint2 *)((const uint32_t *)c->mem + rec * nrec);
   c->equal = c->asserts + nasserts;
   c->outputs = c->equal + nequal;
   c->lp = (const uint32_t *)(c->outputs + nout);
+  if (sum) {
+    c->hp = (const uint32_t *)c->mem + tail_at;
+    c->terms = c->hp + nlev;
+  }
   *out = c;
   return MFH_OK;
 }
@@ -470,6 +589,19 @@ int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const ui
   }
   return circuit_create(ctx, "mfh_circuit_create_out", (flags & MFH_CIRCUIT_GLOBAL) != 0, true, nin, ngates, h_gates, nasserts, h_asserts, nequal, h_equal,
                         nout, h_outputs, out);
+}
+
+int mfh_circuit_create_sum(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t nterms_total,
+                           const uint32_t *h_terms, uint32_t flags, mfh_circuit **out) {
+  if (!ctx || !out) return MFH_EINVAL;
+  if (flags & ~MFH_CIRCUIT_GLOBAL) {
+    *out = nullptr;
+    ctx->err = "mfh_circuit_create_sum: unknown flag bits";
+    return MFH_EINVAL;
+  }
+  return circuit_create(ctx, "mfh_circuit_create_sum", (flags & MFH_CIRCUIT_GLOBAL) != 0, true, nin, ngates, h_gates, nasserts, h_asserts, nequal, h_equal,
+                        nout, h_outputs, out, true, nterms_total, h_terms);
 }
 
 void mfh_circuit_destroy(mfh_circuit *c) {
@@ -513,33 +645,57 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
       if (hipMemcpyAsync(d_in, pin_in, (size_t)n * in_stride, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = MFH_EDEVICE; break; }
     }
     const dim3 grid((n + CSTMT - 1) / CSTMT);
-    if (c->global && c->nout) {
+    const uint32_t *const no_terms = nullptr;
+    if (c->sum && c->global) {
+      Timer tm(ctx, 23, n);
+      if (c->nout)
+        hipLaunchKernelGGL((k_circuit_eval_global<true, true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                           c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
+                           d_holds, c->equal, c->nequal, c->outputs, c->nout, c->terms, c->hp);
+      else
+        hipLaunchKernelGGL((k_circuit_eval_global<true, false, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                           c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
+                           d_holds, c->equal, c->nequal, (const uint2 *)nullptr, 0u, c->terms, c->hp);
+    } else if (c->sum) {
+      Timer tm(ctx, 22, n);
+      if (c->nout)
+        hipLaunchKernelGGL((k_circuit_eval<true, true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                           c->nasserts, c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal,
+                           c->outputs, c->nout, c->terms, c->hp);
+      else
+        hipLaunchKernelGGL((k_circuit_eval<true, false, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
+                           c->nasserts, c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal,
+                           (const uint2 *)nullptr, 0u, c->terms, c->hp);
+    } else if (c->global && c->nout) {
       Timer tm(ctx, 21, n);
       hipLaunchKernelGGL((k_circuit_eval_global<true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts,
                          c->nasserts, c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride,
-                         d_holds, c->equal, c->nequal, c->outputs, c->nout);
+                         d_holds, c->equal, c->nequal, c->outputs, c->nout, no_terms, no_terms);
     } else if (c->nout) {
       Timer tm(ctx, 20, n);
       hipLaunchKernelGGL((k_circuit_eval<true, true>), grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
-                         c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, c->outputs, c->nout);
+                         c->nin, (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, c->outputs, c->nout, no_terms,
+                         no_terms);
     } else if (c->global && c->ex) {
       Timer tm(ctx, 19, n);
       hipLaunchKernelGGL(k_circuit_eval_global<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
                          c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal,
-                         c->nequal, (const uint2 *)nullptr, 0u);
+                         c->nequal, (const uint2 *)nullptr, 0u, no_terms, no_terms);
     } else if (c->global) {
       Timer tm(ctx, 17, n);
       hipLaunchKernelGGL(k_circuit_eval_global<false>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts,
                          c->nin, (uint32_t)nw, (uint32_t *)ctx->circ_state, colw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds,
-                         (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u);
+                         (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u, no_terms, no_terms);
     } else if (c->ex) {
       Timer tm(ctx, 18, n);
       hipLaunchKernelGGL(k_circuit_eval<true>, grid, dim3(CWG), 0, ctx->stream, (const uint4 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
-                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, (const uint2 *)nullptr, 0u);
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, c->equal, c->nequal, (const uint2 *)nullptr, 0u, no_terms,
+                         no_terms);
     } else {
       Timer tm(ctx, 16, n);
       hipLaunchKernelGGL(k_circuit_eval<false>, grid, dim3(CWG), 0, ctx->stream, (const uint2 *)c->gates, c->lp, c->nlev, c->asserts, c->nasserts, c->nin,
-                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u);
+                         (uint32_t)nw, (const uint8_t *)d_in, in_stride, n, d_out, bits_stride, d_holds, (const uint2 *)nullptr, 0u, (const uint2 *)nullptr, 0u,
+                         no_terms, no_terms);
     }
     if (hipGetLastError() != hipSuccess) { rc = MFH_EDEVICE; break; }
     if (hipMemcpyAsync(pin_out, d_out, (size_t)n * bits_stride, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

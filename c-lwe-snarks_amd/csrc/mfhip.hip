@@ -1276,6 +1276,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "circuit_assign_global_ex")) return 19;  // k_circuit_eval_global_ex (mfh_circuit_create_ex with MFH_CIRCUIT_GLOBAL)
   if (!strcmp(which, "circuit_assign_out")) return 20;  // k_circuit_eval<true, true> (mfh_circuit_create_out programs with outputs, wires in LDS)
   if (!strcmp(which, "circuit_assign_global_out")) return 21;  // k_circuit_eval_global<true, true> (... with MFH_CIRCUIT_GLOBAL)
+  if (!strcmp(which, "circuit_assign_sum")) return 22;  // k_circuit_eval<true, OUT, true> (mfh_circuit_create_sum programs with a WSUM gate, wires in LDS)
+  if (!strcmp(which, "circuit_assign_global_sum")) return 23;  // k_circuit_eval_global<true, OUT, true> (... with MFH_CIRCUIT_GLOBAL)
   return -1;
 }
 

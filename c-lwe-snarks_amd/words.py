@@ -2,6 +2,8 @@
 
 A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wires (each also one SSP row besides the wire's bit row):
     add          64   bit 0 a half adder (XOR, AND), bits 1 .. 31 a full adder each (MAJ + SUM3; the last carry is unused)
+    sum          34 .. 38 wires and 4 more rows than wires, for k words at once: two weighted-sum gates (Circuit.wsum) on 16-bit limbs.
+                      k = 2: 34 wires / 38 rows; k = 3, 4: 36 / 40; k = 5 .. 8: 38 / 42 (an add is 64 wires / 128 rows for every two words)
     xor / and_ / or_ / not_   32
     ch           96   z ^ (x & (y ^ z))
     maj          32   one MAJ per bit
@@ -21,6 +23,8 @@ A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wire
 The ChaCha20 block statement (ChaCha20Block) takes 32 642 wires and 64 900 rows: it fits d = 2^16 (m = 43 690) and the LDS kernel.
 The SHA-256 compression statement (Sha256Compress) takes 61 698 wires and 122 884 rows (61 954 and 123 140 with a public chaining value): it fits
 d = 2^17 (m = 87 381), above the LDS kernel's wire limit, so its witnesses come from the device-memory kernel and its SSP is the row SSP.
+Written with sums (Sha256Compress(adds="sum")) it takes 28 114 wires and 49 588 rows (28 370 and 49 844 with a public chaining value): it fits
+d = 2^16 (m = 43 690) and the LDS kernel.
 """
 from __future__ import annotations
 
@@ -84,6 +88,26 @@ class Words:
             s, carry = self.c.full_add(x[i], y[i], carry)
             out.append(s)
         return tuple(out)
+
+    def sum(self, xs):
+        """the sum of the k >= 1 words xs mod 2^32 through two weighted-sum gates on 16-bit limbs (a single 32-bit limb would be unsound: p is about
+        2^32).  lo sums the low halves at shifts 0 .. 15; its output bits 16 and up are the carry count.  hi sums the high halves at shifts 0 .. 15 and
+        lo's carry bits at shifts 0, 1, ..; its output bits 16 and up are discarded wires.  A constant operand (const) costs nothing: its zero bits are
+        left out and its one bits are terms on the shared one wire.  CircuitError when k is so large that a gate would need more than 24 bits."""
+        xs = [tuple(x) for x in xs]
+        if not xs or any(len(x) != 32 for x in xs):
+            raise CircuitError("sum: one or more words of 32 wires")
+        if (len(xs) * 0xFFFF + len(xs)).bit_length() > 24:  # hi's largest sum: k limbs and a carry count below k
+            raise CircuitError(f"sum: {len(xs)} words need a gate of more than 24 bits")
+
+        def limb(bits, carries):
+            terms = [(x[i], i % 16) for x in xs for i in bits if self.c.const_value(x[i]) != 0] + [(k, i) for i, k in enumerate(carries)]
+            out = self.c.wsum(terms) if terms else []
+            return [out[i] if i < len(out) else self.c.const(0) for i in range(16)], out[16:]
+
+        lo, carries = limb(range(16), [])
+        hi, _ = limb(range(16, 32), carries)
+        return tuple(lo + hi)
 
     def xor(self, x, y):
         return tuple(self.c.XOR(a, b) for a, b in zip(x, y))
@@ -247,6 +271,29 @@ def sha256_compress(w: Words, H, M):
     return [w.add(x, y) for x, y in zip(H, (a, b, c, d, e, f, g, h))]
 
 
+def sha256_compress_sum(w: Words, H, M):
+    """sha256_compress with every addition a Words.sum: per round a' = sum(h, K_t, W_t, e & f, ~e & g, Sigma_1, Sigma_0, Maj) and
+    e' = sum(d, h, K_t, W_t, e & f, ~e & g, Sigma_1) -- Ch = (e & f) + (~e & g), the two addends being disjoint, one AND and one ANDN per bit -- the
+    schedule word sum(W[t - 16], sigma_0, W[t - 7], sigma_1) and the eight final sum(H_i, x_i).  184 sums, 448 xors, 64 x (AND, ANDN, MAJ):
+    27 344 gate wires, and the circuit's two constant wires; about 4 levels per round."""
+    H, W = list(H), list(M)
+    if len(H) != 8 or len(W) != 16:
+        raise CircuitError("sha256_compress_sum: H is 8 words and M 16")
+    for t in range(16, 64):
+        s0 = _xor3(w, w.rotr(W[t - 15], 7), w.rotr(W[t - 15], 18), w.shr(W[t - 15], 3))
+        s1 = _xor3(w, w.rotr(W[t - 2], 17), w.rotr(W[t - 2], 19), w.shr(W[t - 2], 10))
+        W.append(w.sum([W[t - 16], s0, W[t - 7], s1]))
+    a, b, c, d, e, f, g, h = H
+    for t in range(64):
+        S1 = _xor3(w, w.rotr(e, 6), w.rotr(e, 11), w.rotr(e, 25))
+        S0 = _xor3(w, w.rotr(a, 2), w.rotr(a, 13), w.rotr(a, 22))
+        ef = w.and_(e, f)
+        neg = tuple(w.c.ANDN(y, x) for x, y in zip(e, g))  # ~e & g
+        t1 = [h, w.const(SHA256_K[t]), W[t], ef, neg, S1]
+        a, b, c, d, e, f, g, h = w.sum(t1 + [S0, w.maj(a, b, c)]), a, b, c, w.sum([d] + t1), e, f, g
+    return [w.sum([x, y]) for x, y in zip(H, (a, b, c, d, e, f, g, h))]
+
+
 def be_words(data: bytes):
     """big-endian 32-bit words of a byte string (FIPS 180-4's convention)"""
     if len(data) % 4:
@@ -268,16 +315,22 @@ class Sha256Compress:
     chaining="public": the incoming chaining value is public too, ahead of the result (lu = 512: bits [0, 256) the chaining value, [256, 512) the
     result) -- what a caller hashing several blocks, or a Merkle path, chains from statement to statement; 61 954 wires and 123 140 rows.
     The block is private (512 bits).  Both fit Params(d=1 << 17, m=87381).  The result is computed, not given: bits() leaves its positions zero,
-    Circuit.assign / Context.circuit_assign write it into the witness row, and digest_of reads the 32 bytes back."""
+    Circuit.assign / Context.circuit_assign write it into the witness row, and digest_of reads the 32 bytes back.
+    adds="ripple" (the default) is the circuit above, every addition a Words.add.  adds="sum" writes the additions as Words.sum
+    (sha256_compress_sum): the same statement in 28 114 wires and 49 588 rows ("iv"; 28 370 and 49 844 for "public"), which fits
+    Params(d=1 << 16, m=43690) and the LDS witness kernel."""
 
-    def __init__(self, chaining="iv"):
+    def __init__(self, chaining="iv", adds="ripple"):
         if chaining not in ("iv", "public"):
             raise CircuitError("Sha256Compress: chaining is 'iv' or 'public'")
+        if adds not in ("ripple", "sum"):
+            raise CircuitError("Sha256Compress: adds is 'ripple' or 'sum'")
         self.chaining = chaining
+        self.adds = adds
         self.w = w = Words()
         self.h_in = w.public(8) if chaining == "public" else [w.const(v) for v in SHA256_IV]
         self.block = w.private(16)
-        self.out = sha256_compress(w, self.h_in, self.block)
+        self.out = (sha256_compress_sum if adds == "sum" else sha256_compress)(w, self.h_in, self.block)
         self.digest = [w.output(x) for x in self.out]
         self.digest_at = 256 if chaining == "public" else 0  # the result's first bit in the statement
 

@@ -261,6 +261,25 @@ int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uin
  * runs k_circuit_eval<true, true> / k_circuit_eval_global<true, true>, timing kinds "circuit_assign_out" and "circuit_assign_global_out". */
 int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                            uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t flags, mfh_circuit **out);
+/* Extended programs with weighted-sum gates.  The arguments of mfh_circuit_create_out plus h_terms: nterms_total pairs (wire, shift) of uint32.
+ * WSUM(terms) has nbits = bitlength(sum_e 2^shift_e) output wires; output wire i carries bit i of T = sum_e 2^shift_e * x_e, where x_e is the bit on term
+ * e's wire (a wire may occur in several terms).  Its two constraint rows are 2X - 1 and 2X + 1 with X = T - sum_i 2^i o_i: the first is +-1 mod p iff
+ * X in {0, 1}, the second iff X in {0, -1}, so X = 0 mod p, and with nbits <= 24 and every operand and output wire a bit, |X| < 2^24 < p gives O = T over
+ * the integers (circuit.py compiles the rows).  The rule "gate g writes wire nin + 1 + g" stays: a head record (MFH_GATE_WSUM, first_term, nterms, nbits)
+ * at gate g is followed by exactly nbits - 1 records (MFH_GATE_WSUM_BIT, i, 0, 0), i = 1 .. nbits - 1, and the head writes wires nin + 1 + g ..
+ * nin + g + nbits, all at the head's level (1 + the highest level of its terms); its terms are h_terms[first_term .. first_term + nterms).
+ * MFH_EINVAL, with its own mfh_last_error text and nothing allocated, besides the cases of mfh_circuit_create_out (named after this function): a term
+ * range outside the array; nterms = 0; a term wire that is 0, not below the head's output wire, or an output wire; a shift >= nbits; terms not in
+ * non-decreasing shift order; nbits other than the bit length of sum 2^shift; nbits > 24; a head not followed by its WSUM_BIT records in order; a
+ * WSUM_BIT record without a head; nterms_total > 0 with h_terms null.  mfh_circuit_create_ex / _out keep rejecting ops 8 .. 15.  A program without a
+ * WSUM gate is exactly the program of mfh_circuit_create_out (the same kernels and timing kinds).  With one, mfh_circuit_assign runs
+ * k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>, timing kinds "circuit_assign_sum" and "circuit_assign_global_sum": a head is
+ * evaluated by one wave, lane j summing statement j's terms as an integer, the output words formed by ballots. */
+#define MFH_GATE_WSUM 8u     /* head: (a, b, c) = (first_term, nterms, nbits) */
+#define MFH_GATE_WSUM_BIT 9u /* (a, b, c) = (i, 0, 0): output bit i of the head i records before */
+int mfh_circuit_create_sum(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t nterms_total,
+                           const uint32_t *h_terms, uint32_t flags, mfh_circuit **out);
 /* every kind of program */
 void mfh_circuit_destroy(mfh_circuit *c);
 /* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
@@ -532,7 +551,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two

@@ -13,13 +13,19 @@ Legs (--leg, default all):
     chain of 200 adds x += rotl(x, 1) (depth 6 400, 32 outputs), which tells a cost per output from a cost per level;
   * sha256: the SHA-256 compression statement (words.Sha256Compress, chaining value = IV: 768 inputs, 60 930 gates, 256 outputs) at D = 2^17,
     M = 87 381, device-memory program (kind "circuit_assign_global_out"), 255 and 1 020 statements;
-  * sha256_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^17.
+  * sha256_prove: prove_batch_public for 255 of those statements through the row SSP at D = 2^17;
+  * sha256_sum: the same statement written with weighted sums (words.Sha256Compress(adds="sum"): 27 346 gate wires, 368 WSUM heads) at D = 2^16,
+    M = 43 690, LDS program (kind "circuit_assign_sum"), against the sha256 leg's circuit at D = 2^17: the two programs called in turn in one process,
+    255 and 1 020 statements;
+  * sha256_sum_prove: for 255 statements of each of the two, in one process: ssp_set_rows + ssp_prepare (the registration of the rows: up to 151 entries
+    a row with sums, 3 - 6 without), one witness_poly call through the row SSP (its witness pass), setup_public, and prove_batch_public called in turn
+    (median of min(--reps, 5) calls after one warm-up); "witness_plus_prove_ms" = the circuit_assign call + the batch proof.
 Printed per leg (one JSON line each, also appended to --out):
   * load: circuit_load once (levelising on the host, the upload);
   * call: the median wall time of circuit_assign (packing the input bits, staging, the launches, the copies back; the call synchronises);
   * kernel: the kernel launches alone (HIP events of mfh_set_timing, kind "circuit_assign" / "circuit_assign_global"), summed over a call's chunks;
   * python: Circuit.assign for --py statements (--py2 at 2^20), scaled to the batch (the rows are checked equal).
-dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove|chacha_out|sha256|sha256_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
+dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove|chacha_out|sha256|sha256_prove|sha256_sum|sha256_sum_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
 [--out FILE]"""
 import argparse
 import json
@@ -447,9 +453,154 @@ def leg_sha256_prove(a):
     return ok and bool(holds.all())
 
 
+def _sha256_variants():
+    """(name, Params, statement, compiled, timing kind) of the ripple-carry statement at d = 2^17 and of the statement with sums at d = 2^16"""
+    from c_lwe_snarks_amd import words
+
+    out = []
+    for name, p, adds, kind in (("ripple", mf.Params(d=1 << 17, m=87381), "ripple", "circuit_assign_global_out"),
+                                ("sum", mf.Params(d=1 << 16, m=43690), "sum", "circuit_assign_sum")):
+        st = words.Sha256Compress("iv", adds=adds)
+        out.append(SimpleNamespace(name=name, p=p, st=st, cc=st.circuit.compile(p), kind=kind))
+    return out
+
+
+def _depth_sum(cc):
+    """levels of a program with WSUM gates: a head and its bit records 1 + the highest level of its terms"""
+    lvl = np.zeros(cc.nwires + 1, dtype=np.int64)
+    nin = cc.nwires - len(cc.program)
+    head = 0
+    for g, (op, x, y, z) in enumerate(cc.program.tolist()):
+        o = nin + 1 + g
+        if op == circuit.GATE_WSUM:
+            head = o
+            lvl[o] = 1 + int(lvl[cc.terms[x: x + y, 0]].max())
+        elif op == circuit.GATE_WSUM_BIT:
+            lvl[o] = lvl[head]
+        else:
+            lvl[o] = 1 if op in (circuit.GATE_CONST0, circuit.GATE_CONST1) else 1 + max(lvl[x], lvl[y], lvl[z] if z else 0)
+    return int(lvl.max())
+
+
+def leg_sha256_sum(a):
+    import hashlib
+
+    vs = _sha256_variants()
+    ok = True
+    for v in vs:
+        v.ctx = mf.Context(v.p, 0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        v.prog = v.ctx.circuit_load(v.cc, state="auto")
+        v.load_ms = (time.perf_counter() - t0) * 1e3
+        v.depth = _depth_sum(v.cc)
+    ok = ok and vs[0].prog.state == "global" and vs[1].prog.state == "lds" and vs[1].prog.sums
+    rng = np.random.default_rng(1806)
+    for nb in (255, 1020):
+        msgs, bits = _sha256_statements(vs[0].st, rng, nb)
+        for v in vs:
+            v.ctx.circuit_assign(v.prog, bits)  # first call: staging buffers
+            v.call, v.kern = [], []
+        for _ in range(a.reps):  # in turn
+            for v in vs:
+                v.ctx.set_timing(True)
+                t0 = time.perf_counter()
+                v.witness, v.holds = v.ctx.circuit_assign(v.prog, bits)
+                v.call.append((time.perf_counter() - t0) * 1e3)
+                v.launches, tot, _ = v.ctx.timing_drain(v.kind)
+                v.kern.append(tot)
+                v.ctx.set_timing(False)
+        for v in vs:
+            digests = all(v.st.digest_of(v.witness[b]) == hashlib.sha256(msgs[b]).digest() for b in range(nb))
+            same = all(v.witness[b].tobytes() == v.st.circuit.assign(bits[b, :256], bits[b, 256:], v.p) for b in range(min(a.py2, nb)))
+            ok = ok and digests and same and bool(v.holds.all())
+            heads = int((v.cc.program[:, 0] == circuit.GATE_WSUM).sum())
+            _emit({"tool": "circuit_assign_time", "leg": "sha256_sum", "adds": v.name, "state": v.prog.state, "d": v.p.d, "m": v.p.m, "nb": nb,
+                   "nwires": v.cc.nwires, "nrows": v.cc.nrows, "heads": heads, "terms": len(v.cc.terms), "depth": v.depth,
+                   "load_ms": round(v.load_ms, 3), "launches_per_call": v.launches, "call_ms": round(statistics.median(v.call), 3),
+                   "call_ms_all": [round(x, 3) for x in v.call], "kernel_ms": round(statistics.median(v.kern), 3),
+                   "kernel_ms_all": [round(x, 3) for x in v.kern],
+                   "kernel_us_per_level": round(statistics.median(v.kern) * 1e3 / v.depth / max(v.launches, 1), 3),
+                   "rows_equal": bool(same), "digests_equal_hashlib": bool(digests)}, a.out)
+    for v in vs:
+        v.prog.close()
+        v.ctx.close()
+    return ok
+
+
+def leg_sha256_sum_prove(a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+
+    vs = _sha256_variants()
+    nb, reps = 255, min(a.reps, 5)
+    rng = np.random.default_rng(1807)
+    _, bits = _sha256_statements(vs[0].st, rng, nb)
+    deltas = [int(x) for x in rng.integers(0, circuit.P, size=nb, dtype=np.uint64)]
+    mags = [rng.integers(0, 256, size=400, dtype=np.uint8).tobytes() for _ in range(nb)]
+    signs = [bytes(rng.integers(0, 2, size=5, dtype=np.uint8).tolist()) for _ in range(nb)]
+    for v in vs:
+        p, cc = v.p, v.cc
+        v.ctx = ctx = mf.Context(p, 0)
+        v.prog = ctx.circuit_load(cc, state="auto")
+        ctx.circuit_assign(v.prog, bits)
+        ctx.set_seed(bytes(range(40)))
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)
+        ctx.ssp_prepare(None)
+        ctx.sync()
+        v.rows_ms = (time.perf_counter() - t0) * 1e3
+        v.alpha, v.beta, v.s = (int(x) for x in rng.integers(1, circuit.P, size=3, dtype=np.uint64))
+        v.d_sk = ctx.to_device(ol.rand_values(rng, p.n, p.L, p.logq))
+        d_err = ctx.to_device(ol.rand_values(rng, 2 * p.d + p.m, p.L, 559))
+        t0 = time.perf_counter()
+        v.d_crs = ctx.setup_public(None, v.alpha, v.beta, v.s, cc.lu, v.d_sk, d_err).clone()
+        ctx.sync()
+        v.setup_ms = (time.perf_counter() - t0) * 1e3
+        v.assign, v.wpoly, v.prove = [], [], []
+    for r in range(reps + 1):  # in turn; the first round warms up
+        for v in vs:
+            ctx = v.ctx
+            ctx.sync()
+            t0 = time.perf_counter()
+            v.witness, v.holds = ctx.circuit_assign(v.prog, bits)
+            t1 = time.perf_counter()
+            v.stmts = [v.witness[b].tobytes() for b in range(nb)]
+            ctx.sync()
+            t2 = time.perf_counter()
+            ctx.witness_poly(None, v.stmts[0], deltas[0])
+            ctx.sync()
+            t3 = time.perf_counter()
+            v.proofs = ctx.prove_batch_public(v.d_crs, None, v.cc.lu, v.stmts, deltas, mags, signs)
+            ctx.sync()
+            t4 = time.perf_counter()
+            if r:
+                v.assign.append((t1 - t0) * 1e3)
+                v.wpoly.append((t3 - t2) * 1e3)
+                v.prove.append((t4 - t3) * 1e3)
+    ok = True
+    for v in vs:
+        vk = v.ctx.derive_vk(None, v.s, v.cc.lu)
+        good = bool(v.ctx.to_host(v.ctx.verify_public(vk, v.cc.lu, v.alpha, v.beta, v.d_sk, v.proofs, v.stmts), np.uint8).all()) and bool(v.holds.all())
+        ok = ok and good
+        lens = np.diff(v.cc.rows[0].astype(np.int64))
+        _emit({"tool": "circuit_assign_time", "leg": "sha256_sum_prove", "adds": v.name, "d": v.p.d, "m": v.p.m, "nb": nb, "lu": v.cc.lu,
+               "nwires": v.cc.nwires, "nrows": v.cc.nrows, "row_entries": int(lens.sum()), "longest_row": int(lens.max()),
+               "ssp_set_rows_prepare_ms": round(v.rows_ms, 1), "setup_public_ms": round(v.setup_ms, 1),
+               "witness_poly_ms": round(statistics.median(v.wpoly), 3), "circuit_assign_call_ms": round(statistics.median(v.assign), 3),
+               "prove_batch_public_ms": round(statistics.median(v.prove), 3), "prove_ms_all": [round(x, 3) for x in v.prove],
+               "witness_plus_prove_ms": round(statistics.median(v.assign) + statistics.median(v.prove), 3), "verified_all": good}, a.out)
+    for v in vs:
+        v.prog.close()
+        v.ctx.close()
+    return ok and statistics.median(vs[1].assign) + statistics.median(vs[1].prove) < statistics.median(vs[0].assign) + statistics.median(vs[0].prove)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove", "chacha_out", "sha256", "sha256_prove"])
+    ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove", "chacha_out", "sha256", "sha256_prove", "sha256_sum",
+                                                      "sha256_sum_prove"])
     ap.add_argument("--nb", type=int, default=1020)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign (default leg)")
@@ -458,7 +609,8 @@ def main():
     a = ap.parse_args()
     ok = True
     for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20), ("chacha", leg_chacha), ("chacha_prove", leg_chacha_prove),
-                     ("chacha_out", leg_chacha_out), ("sha256", leg_sha256), ("sha256_prove", leg_sha256_prove)):
+                     ("chacha_out", leg_chacha_out), ("sha256", leg_sha256), ("sha256_prove", leg_sha256_prove), ("sha256_sum", leg_sha256_sum),
+                     ("sha256_sum_prove", leg_sha256_sum_prove)):
         if a.leg in ("all", name):
             ok = fn(a) and ok
     return 0 if ok else 1
