@@ -263,11 +263,11 @@ CIRCUIT_GLOBAL = 1  # MFH_CIRCUIT_GLOBAL: mfh_circuit_create_ex flag, wire state
 
 class CircuitProgram:
     """a compiled circuit's gate program on the device (mfh_circuit): made by Context.circuit_load, used by Context.circuit_assign.
-    state: "lds" (mfh_circuit_create, at most CIRCUIT_MAX_WIRES wires) or "global" (mfh_circuit_create_global, wire state in device memory);
-    extended: made by mfh_circuit_create_ex (the circuit has a gate beyond XOR / AND / OR / NOT or an equality), in the kind `state` names;
-    outputs: the number of computed public outputs (Circuit.output): above 0 the program was made by mfh_circuit_create_out, in the kind `state` names,
-    and circuit_assign writes the computed statement into bits [0, lu) of every witness row;
-    sums: the circuit has a weighted-sum gate (Circuit.wsum) and the program was made by mfh_circuit_create_sum, in the kind `state` names"""
+    state: "lds" (wire state in LDS, at most CIRCUIT_MAX_WIRES wires) or "global" (wire state in device memory);
+    extended: the circuit has a gate beyond XOR / AND / OR / NOT, an equality or an output (a mfh_circuit_create_ex / _out / _sum program);
+    outputs: the number of computed public outputs (Circuit.output): above 0 circuit_assign writes the computed statement into bits [0, lu) of every
+    witness row (mfh_circuit_create_out, or _sum);
+    sums: the circuit has a weighted-sum gate (Circuit.wsum; mfh_circuit_create_sum)"""
 
     def __init__(self, ctx, nin, ngates, handle, state="lds", extended=False, outputs=0, sums=False):
         self._ctx, self.nin, self.ngates, self._h, self.state, self.extended, self.outputs = ctx, nin, ngates, handle, state, extended, outputs
@@ -560,12 +560,13 @@ class Context:
         return out
 
     def circuit_load(self, compiled, state="lds"):
-        """the gate program of circuit.Compiled on the device: levelised and uploaded once; close() frees it.  state: "lds" (mfh_circuit_create: the
-        wire state in LDS, at most CIRCUIT_MAX_WIRES wires), "global" (mfh_circuit_create_global: in device memory, up to m - 1 wires) or "auto"
-        (lds up to CIRCUIT_MAX_WIRES wires, else global).  A circuit with a MAJ / SUM3 / CONST / LUT2 gate or an equality (Compiled.program, Compiled.equal)
-        goes through mfh_circuit_create_ex in the same kind; the others through the two creates above.  A circuit with computed public outputs
-        (Circuit.output, Compiled.outputs) goes through mfh_circuit_create_out; one without them loads exactly as before.  A circuit with a weighted-sum
-        gate (Circuit.wsum, Compiled.terms) goes through mfh_circuit_create_sum, and only such a circuit."""
+        """the gate program of circuit.Compiled on the device: levelised and uploaded once; close() frees it.  state: "lds" (the wire state in LDS, at
+        most CIRCUIT_MAX_WIRES wires), "global" (in device memory, up to m - 1 wires) or "auto" (lds up to CIRCUIT_MAX_WIRES wires, else global).
+        The entry point, by what the circuit holds, the first that applies, each in the kind `state` names:
+          a weighted-sum gate (Circuit.wsum, Compiled.terms)                                        mfh_circuit_create_sum
+          computed public outputs (Circuit.output, Compiled.outputs)                                mfh_circuit_create_out
+          a MAJ / SUM3 / CONST / LUT2 gate or an equality (Compiled.program, Compiled.equal)        mfh_circuit_create_ex
+          XOR / AND / OR / NOT gates and assertions alone                                           mfh_circuit_create ("lds"), mfh_circuit_create_global"""
         if state not in ("lds", "global", "auto"):
             raise MfhError(f"circuit_load: state must be 'lds', 'global' or 'auto', got {state!r}")
         gates = np.ascontiguousarray(compiled.gates, dtype=np.uint32).reshape(-1, 3)
@@ -581,22 +582,21 @@ class Context:
         if state == "auto":
             state = "lds" if compiled.nwires <= CIRCUIT_MAX_WIRES else "global"
         h = ctypes.c_void_p()
+
+        def arr(x):
+            return ctypes.c_void_p(x.ctypes.data)
+
+        flags = CIRCUIT_GLOBAL if state == "global" else 0
+        ex = [self._h, nin, len(program), arr(program), len(asserts), arr(asserts), len(equal), arr(equal)]
         if sums:
-            self._chk(self.lib.mfh_circuit_create_sum(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
-                                                      ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data), len(outputs),
-                                                      ctypes.c_void_p(outputs.ctypes.data), len(terms), ctypes.c_void_p(terms.ctypes.data),
-                                                      CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
+            self._chk(self.lib.mfh_circuit_create_sum(*ex, len(outputs), arr(outputs), len(terms), arr(terms), flags, ctypes.byref(h)))
         elif len(outputs):
-            self._chk(self.lib.mfh_circuit_create_out(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
-                                                      ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data), len(outputs),
-                                                      ctypes.c_void_p(outputs.ctypes.data), CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
+            self._chk(self.lib.mfh_circuit_create_out(*ex, len(outputs), arr(outputs), flags, ctypes.byref(h)))
         elif extended:
-            self._chk(self.lib.mfh_circuit_create_ex(self._h, nin, len(program), ctypes.c_void_p(program.ctypes.data), len(asserts),
-                                                     ctypes.c_void_p(asserts.ctypes.data), len(equal), ctypes.c_void_p(equal.ctypes.data),
-                                                     CIRCUIT_GLOBAL if state == "global" else 0, ctypes.byref(h)))
+            self._chk(self.lib.mfh_circuit_create_ex(*ex, flags, ctypes.byref(h)))
         else:
             create = self.lib.mfh_circuit_create if state == "lds" else self.lib.mfh_circuit_create_global
-            self._chk(create(self._h, nin, len(gates), ctypes.c_void_p(gates.ctypes.data), len(asserts), ctypes.c_void_p(asserts.ctypes.data), ctypes.byref(h)))
+            self._chk(create(self._h, nin, len(gates), arr(gates), len(asserts), arr(asserts), ctypes.byref(h)))
         return CircuitProgram(self, nin, len(gates), h, state, extended, len(outputs), sums)
 
     def circuit_assign(self, prog, bits):

@@ -1270,10 +1270,12 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "mmstream_rounds_persistent")) return 110;  // ... those of them that ran the persistent one-workgroup-per-CU grid (k_mmstream_p / k_mmstream_w)
   if (!strcmp(which, "mmstream_bw_persistent")) return 114;      // ... and of "mmstream_bw" (k_mmstream_pb)
   if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
+  // mfh_circuit_assign (circuit_eval.hip): 16 + 2 * tier + global; tier 0 not extended, 1 extended, 2 with outputs, 3 with a WSUM gate; global = wire state in
+  // device memory (k_circuit_eval_global) instead of LDS (k_circuit_eval)
   if (!strcmp(which, "circuit_assign")) return 16;  // k_circuit_eval of mfh_circuit_assign
   if (!strcmp(which, "circuit_assign_global")) return 17;  // k_circuit_eval_global of mfh_circuit_assign (mfh_circuit_create_global programs)
-  if (!strcmp(which, "circuit_assign_ex")) return 18;  // k_circuit_eval_ex of mfh_circuit_assign (mfh_circuit_create_ex programs, wires in LDS)
-  if (!strcmp(which, "circuit_assign_global_ex")) return 19;  // k_circuit_eval_global_ex (mfh_circuit_create_ex with MFH_CIRCUIT_GLOBAL)
+  if (!strcmp(which, "circuit_assign_ex")) return 18;  // k_circuit_eval<true> (mfh_circuit_create_ex programs, wires in LDS)
+  if (!strcmp(which, "circuit_assign_global_ex")) return 19;  // k_circuit_eval_global<true> (... with MFH_CIRCUIT_GLOBAL)
   if (!strcmp(which, "circuit_assign_out")) return 20;  // k_circuit_eval<true, true> (mfh_circuit_create_out programs with outputs, wires in LDS)
   if (!strcmp(which, "circuit_assign_global_out")) return 21;  // k_circuit_eval_global<true, true> (... with MFH_CIRCUIT_GLOBAL)
   if (!strcmp(which, "circuit_assign_sum")) return 22;  // k_circuit_eval<true, OUT, true> (mfh_circuit_create_sum programs with a WSUM gate, wires in LDS)

@@ -202,90 +202,102 @@ int mfh_ssp_rows_fill(mfh_ctx *ctx, size_t first_slot, size_t nslots, uint32_t *
 /* Witnesses of a Boolean circuit for a batch of statements, evaluated on the device.  What random_ssp(mpz_t input, ...) (src/ssp.c:37) is to a random SSP --
  * the reference's only source of a witness -- this is to the SSP of mfh_ssp_from_rows: the input bits of mfh_prove / mfh_prove_batch for each statement.
  * Wires (mfh_ssp_from_rows): wire 0 is the constant, wires 1 .. nin are the inputs (public first, then private), and gate g writes wire nin + 1 + g.
- * h_gates: ngates records (op, a, b) of uint32, op one of MFH_GATE_*, operands in [1, nin + g] (below the gate's own output wire); for NOT, b = a.
- * h_asserts: nasserts records (wire, value), wire in [1, nin + ngates], value 0 or 1.
- * mfh_circuit_create validates the program, orders the gates by level (inputs are level 0, a gate one more than its highest operand) and uploads it once.
- * MFH_EINVAL, with nothing allocated, for an unknown op, an operand of 0 or not below the gate's output wire, an assertion on wire 0 or above nin + ngates, an
- * assertion value other than 0 / 1, nin + ngates > m - 1, or nin + ngates > MFH_CIRCUIT_MAX_WIRES: the kernel keeps one uint32 word per wire in LDS,
- * (MFH_CIRCUIT_MAX_WIRES + 1) * 4 bytes = 128 KiB of the 160 KiB of a CU (every circuit of mf.DEFAULT, m - 1 = 21 844 wires, fits).
- * The program belongs to ctx's device; destroy it before the context. */
-#define MFH_GATE_XOR 0u /* c = a ^ b */
-#define MFH_GATE_AND 1u /* c = a & b */
-#define MFH_GATE_OR 2u  /* c = a | b */
-#define MFH_GATE_NOT 3u /* c = 1 - a */
-#define MFH_CIRCUIT_MAX_WIRES 32767u
-typedef struct mfh_circuit mfh_circuit;
-int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                       mfh_circuit **out);
-/* The same program with its wire state in device memory, for circuits above MFH_CIRCUIT_MAX_WIRES.  Same arguments, records and validation as
- * mfh_circuit_create (the same MFH_EINVAL cases and texts, named after this function) except the LDS bound: the limit is nin + ngates <= m - 1 alone
- * (699 049 wires at d = 2^20, m = 699 050; gate records are 16 bytes with 32-bit wire numbers, 7.5 MB for 470 000 gates).  mfh_circuit_assign evaluates it
- * with one column of (nin + ngates + 1) words, rounded up to 32, per block of 32 statements in a context buffer reused across calls: one launch per
- * chunk of statements whatever the circuit's depth; a chunk is the most whole blocks whose staging, chunk x (in_stride + bits_stride + 1) bytes, fits
- * 64 MiB and whose columns fit 256 MiB, at least one block (736 statements at d = 2^20 with 2 508-byte input rows).  Witness rows and holds are byte for
- * byte those of a mfh_circuit_create program of the same circuit.  Kernel timing kind "circuit_assign_global". */
-int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                              mfh_circuit **out);
-/* Extended programs: three-operand records, more gates, equalities.  h_gates: ngates records (op, a, b, c) of uint32, gate g writing wire nin + 1 + g;
- * h_asserts as above; h_equal: nequal pairs (a, b) asserting wire a = wire b.  flags: 0 (wire state in LDS, nin + ngates <= MFH_CIRCUIT_MAX_WIRES) or
- * MFH_CIRCUIT_GLOBAL (in device memory); in both kinds nin + ngates <= m - 1.  Every new gate and every equality adds one SSP row that is +-1 mod p exactly
- * when its output is right, given bit operands (circuit.py compiles them; wire w keeps its bit row 2w - 1):
+ * A program is validated, ordered by level (inputs are level 0, a gate one more than the highest level of the operands it uses; CONST: 1; SUM3 shares its
+ * MAJ's level; a WSUM head and its WSUM_BIT records: 1 + the highest level of its terms) and uploaded once by one of five entry points; it belongs to
+ * ctx's device; destroy it (mfh_circuit_destroy, every kind) before the context.
+ *
+ * Arguments.
+ *   h_gates    ngates records of uint32: (op, a, b) for mfh_circuit_create / _global, (op, a, b, c) for _ex / _out / _sum (extended programs)
+ *   h_asserts  nasserts records (wire, value): wire in [1, nin + ngates], value 0 or 1
+ *   h_equal    nequal pairs (a, b) asserting wire a = wire b                                                       (_ex, _out, _sum)
+ *   h_outputs  nout pairs (p, w): the input wire p (a public input of the statement, wires 1 .. lu) is DEFINED as wire w   (_out, _sum)
+ *   h_terms    nterms_total pairs (wire, shift), the terms of the WSUM gates                                         (_sum)
+ *   flags      0: wire state in LDS; MFH_CIRCUIT_GLOBAL: in device memory                                           (_ex, _out, _sum)
+ * The wire state.  LDS (mfh_circuit_create, flags 0): one uint32 word per wire, (MFH_CIRCUIT_MAX_WIRES + 1) * 4 bytes = 128 KiB of the 160 KiB of a CU,
+ * so nin + ngates <= MFH_CIRCUIT_MAX_WIRES (every circuit of mf.DEFAULT, m - 1 = 21 844 wires, fits).  Device memory (mfh_circuit_create_global,
+ * MFH_CIRCUIT_GLOBAL): nin + ngates <= m - 1 alone (699 049 wires at d = 2^20, m = 699 050; gate records are 16 bytes with 32-bit wire numbers, 7.5 MB for
+ * 470 000 gates); one column of (nin + ngates + 1) words, rounded up to 32, per block of 32 statements in a context buffer reused across calls.  Witness
+ * rows and holds are byte for byte the same in both kinds.
+ *
+ * Gates and their operands (g = the gate's index; extended programs only below the line; c = 0 where it is not named).
+ *   XOR, AND, OR          a, b in [1, nin + g]
+ *   NOT                   a in [1, nin + g], b = a
+ *   ------------------------------------------------------------------------------------------------------------------------------------------------
+ *   LUT2(tt)              a, b in [1, nin + g]: out = (tt >> (a + 2b)) & 1
+ *   MAJ, SUM3             a, b, c in [1, nin + g]; SUM3 is sound only next to the MAJ that forces its carry k: gate g - 1 must be a MAJ with the same (a, b, c)
+ *   CONST0, CONST1        a = b = c = 0
+ *   WSUM (_sum only)      (a, b, c) = (first_term, nterms, nbits): its terms are h_terms[first_term .. first_term + nterms), and it has nbits =
+ *                         bitlength(sum_e 2^shift_e) output wires; output wire i carries bit i of T = sum_e 2^shift_e * x_e, x_e the bit on term e's wire (a
+ *                         wire may occur in several terms).  The rule "gate g writes wire nin + 1 + g" stays: the head at gate g is followed by exactly
+ *                         nbits - 1 records (MFH_GATE_WSUM_BIT, i, 0, 0), i = 1 .. nbits - 1, and writes wires nin + 1 + g .. nin + g + nbits.
+ * Every extended gate and every equality adds one SSP row that is +-1 mod p exactly when its output is right, given bit operands (circuit.py compiles them;
+ * wire w keeps its bit row 2w - 1):
  *   MAJ(a, b, c)     k = 1 iff a + b + c >= 2                          2a + 2b + 2c - 4k - 1
  *   SUM3(a, b, c)    s = a ^ b ^ c (k = the wire of gate g - 1)         1 - a - b - c + 2k - s
  *   CONST0 / CONST1  0 / 1                                              1 - c / c
  *   LUT2(tt)(a, b)   c = (tt >> (a + 2b)) & 1                          by the class of tt (circuit.py); XOR, AND, OR, NOT rows for those functions
  *   equality (a, b)  a = b (no wire)                                     1 - a - b
- * SUM3 is sound only next to the MAJ that forces k, so gate g - 1 must be a MAJ with the same (a, b, c).
- * Operands: XOR, AND, OR, LUT2: a, b in [1, nin + g], c = 0; NOT: a in [1, nin + g], b = a, c = 0; MAJ, SUM3: a, b, c in [1, nin + g]; CONST: a = b = c
- * = 0.  Equality wires in [1, nin + ngates] with a != b.  MFH_EINVAL, with its own mfh_last_error text and nothing allocated, for each violation, for ops
- * 8 .. 15 and >= 32 and for unknown flag bits, besides the cases of mfh_circuit_create.  Levels: a gate is 1 + the highest level of the operands it
- * uses (CONST: 1; SUM3 shares its MAJ's level).  holds = every value assertion and every equality holds.  mfh_circuit_assign runs these programs in
- * k_circuit_eval_ex / k_circuit_eval_global_ex (16-byte records {a, b, c, out | op << 24}), timing kinds "circuit_assign_ex" and
- * "circuit_assign_global_ex"; the chunking, witness rows and holds layout are those of the kind named by flags. */
+ *   output (p, w)    p = w                                               1 - p - w, an equality: list it in h_equal and it holds by construction
+ *   WSUM             two rows 2X - 1 and 2X + 1 with X = T - sum_i 2^i o_i: the first is +-1 mod p iff X in {0, 1}, the second iff X in {0, -1}, so X = 0
+ *                    mod p, and with nbits <= 24 and every operand and output wire a bit, |X| < 2^24 < p gives O = T over the integers
+ *
+ * MFH_EINVAL, with its own mfh_last_error text (named after the function called) and nothing allocated:
+ *   every entry point     nin + ngates > m - 1; in the LDS kind nin + ngates > MFH_CIRCUIT_MAX_WIRES; an unknown op (not extended: above NOT; _ex, _out:
+ *                         8 .. 15 and >= 32; _sum: 10 .. 15 and >= 32); an operand of 0 or not below the gate's output wire; an assertion on wire 0 or above
+ *                         nin + ngates; an assertion value other than 0 / 1; a count > 0 with its array null
+ *   _ex, _out, _sum       unknown flag bits; nin + ngates >= 2^24; a violation of the operand table above (a third operand c != 0 on a one- or two-input
+ *                         gate, NOT with b != a, CONST with an operand, SUM3 not directly after its MAJ or with other operands); an equality on wire 0 or
+ *                         above nin + ngates, or with a = b
+ *   _out, _sum            p = 0 or p > nin; w = 0 or w > nin + ngates; w = p; a p given twice; a w that is the p of another pair; a gate operand or an
+ *                         assertion on an output wire (it has no value until the end); an equality touching an output wire other than (p, w) / (w, p) of
+ *                         its own pair
+ *   _sum                  a term range outside the array; nterms = 0; a term wire that is 0, not below the head's output wire, or an output wire; a
+ *                         shift >= nbits; terms not in non-decreasing shift order; nbits other than the bit length of sum 2^shift; nbits > 24; a head not
+ *                         followed by its WSUM_BIT records in order; a WSUM_BIT record without a head
+ *
+ * What mfh_circuit_assign runs: circuit_eval.hip's k_circuit_eval<EX, OUT, SUM> (LDS) or k_circuit_eval_global<EX, OUT, SUM> (device memory), by what the
+ * program holds, whichever entry point made it (so nout = 0 gives exactly the program of mfh_circuit_create_ex, and a _sum program without a WSUM gate
+ * exactly that of mfh_circuit_create_out).  Kernel timing kinds (mfh_timing_kind):
+ *   not extended (mfh_circuit_create / _global)          <false>             "circuit_assign"      / "circuit_assign_global"
+ *   extended, no outputs, no WSUM gate                   <true>              "circuit_assign_ex"   / "circuit_assign_global_ex"
+ *   extended with outputs (nout > 0), no WSUM gate       <true, true>        "circuit_assign_out"  / "circuit_assign_global_out"
+ *   with a WSUM gate, outputs or none                    <true, OUT, true>   "circuit_assign_sum"  / "circuit_assign_global_sum"
+ * Device gate records are 8 bytes {a | b << 16, out | op << 16} for LDS programs that are not extended, 16 bytes {a, b, out, op} for device-memory ones,
+ * 16 bytes {a, b, c, out | op << 24} for extended programs of either kind.  A WSUM head is evaluated by one wave, lane j summing statement j's terms as an
+ * integer, the output words formed by ballots. */
+#define MFH_GATE_XOR 0u /* c = a ^ b */
+#define MFH_GATE_AND 1u /* c = a & b */
+#define MFH_GATE_OR 2u  /* c = a | b */
+#define MFH_GATE_NOT 3u /* c = 1 - a */
 #define MFH_GATE_MAJ 4u    /* out = maj(a, b, c) */
 #define MFH_GATE_SUM3 5u   /* out = a ^ b ^ c; gate g - 1 must be MFH_GATE_MAJ with the same (a, b, c) */
 #define MFH_GATE_CONST0 6u /* a = b = c = 0 */
 #define MFH_GATE_CONST1 7u
-#define MFH_GATE_LUT2(tt) (16u + (tt)) /* out = (tt >> (a + 2b)) & 1, tt in [0, 16) */
-#define MFH_CIRCUIT_GLOBAL 1u
-int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                          uint32_t nequal, const uint32_t *h_equal, uint32_t flags, mfh_circuit **out);
-/* Extended programs with computed public outputs.  The arguments of mfh_circuit_create_ex plus h_outputs: nout pairs (p, w) of uint32.  Output wire p is
- * an input wire (a public input of the statement, wires 1 .. lu) whose value is DEFINED as that of wire w: mfh_circuit_assign ignores input bit p - 1 of
- * every statement and, after the last level and before the assertions and equalities are folded, writes wire w's value onto wire p, so bits [0, lu) of a
- * witness row carry the computed statement (circuit.py adds the row 1 - p - w, an equality, for each pair: list it in h_equal and it holds by
- * construction).  MFH_EINVAL, with its own mfh_last_error text and nothing allocated, besides the cases of mfh_circuit_create_ex (named after this
- * function): p = 0 or p > nin; w = 0 or w > nin + ngates; w = p; a p given twice; a w that is the p of another pair; a gate operand or an assertion on
- * an output wire (it has no value until the end); an equality touching an output wire other than (p, w) / (w, p) of its own pair; nout > 0 with
- * h_outputs null.  nout = 0 gives exactly the program of mfh_circuit_create_ex (the same kernels and timing kinds).  With nout > 0 mfh_circuit_assign
- * runs k_circuit_eval<true, true> / k_circuit_eval_global<true, true>, timing kinds "circuit_assign_out" and "circuit_assign_global_out". */
-int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
-                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t flags, mfh_circuit **out);
-/* Extended programs with weighted-sum gates.  The arguments of mfh_circuit_create_out plus h_terms: nterms_total pairs (wire, shift) of uint32.
- * WSUM(terms) has nbits = bitlength(sum_e 2^shift_e) output wires; output wire i carries bit i of T = sum_e 2^shift_e * x_e, where x_e is the bit on term
- * e's wire (a wire may occur in several terms).  Its two constraint rows are 2X - 1 and 2X + 1 with X = T - sum_i 2^i o_i: the first is +-1 mod p iff
- * X in {0, 1}, the second iff X in {0, -1}, so X = 0 mod p, and with nbits <= 24 and every operand and output wire a bit, |X| < 2^24 < p gives O = T over
- * the integers (circuit.py compiles the rows).  The rule "gate g writes wire nin + 1 + g" stays: a head record (MFH_GATE_WSUM, first_term, nterms, nbits)
- * at gate g is followed by exactly nbits - 1 records (MFH_GATE_WSUM_BIT, i, 0, 0), i = 1 .. nbits - 1, and the head writes wires nin + 1 + g ..
- * nin + g + nbits, all at the head's level (1 + the highest level of its terms); its terms are h_terms[first_term .. first_term + nterms).
- * MFH_EINVAL, with its own mfh_last_error text and nothing allocated, besides the cases of mfh_circuit_create_out (named after this function): a term
- * range outside the array; nterms = 0; a term wire that is 0, not below the head's output wire, or an output wire; a shift >= nbits; terms not in
- * non-decreasing shift order; nbits other than the bit length of sum 2^shift; nbits > 24; a head not followed by its WSUM_BIT records in order; a
- * WSUM_BIT record without a head; nterms_total > 0 with h_terms null.  mfh_circuit_create_ex / _out keep rejecting ops 8 .. 15.  A program without a
- * WSUM gate is exactly the program of mfh_circuit_create_out (the same kernels and timing kinds).  With one, mfh_circuit_assign runs
- * k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>, timing kinds "circuit_assign_sum" and "circuit_assign_global_sum": a head is
- * evaluated by one wave, lane j summing statement j's terms as an integer, the output words formed by ballots. */
 #define MFH_GATE_WSUM 8u     /* head: (a, b, c) = (first_term, nterms, nbits) */
 #define MFH_GATE_WSUM_BIT 9u /* (a, b, c) = (i, 0, 0): output bit i of the head i records before */
+#define MFH_GATE_LUT2(tt) (16u + (tt)) /* out = (tt >> (a + 2b)) & 1, tt in [0, 16) */
+#define MFH_CIRCUIT_MAX_WIRES 32767u
+#define MFH_CIRCUIT_GLOBAL 1u
+typedef struct mfh_circuit mfh_circuit;
+int mfh_circuit_create(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                       mfh_circuit **out);
+int mfh_circuit_create_global(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                              mfh_circuit **out);
+int mfh_circuit_create_ex(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                          uint32_t nequal, const uint32_t *h_equal, uint32_t flags, mfh_circuit **out);
+int mfh_circuit_create_out(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
+                           uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t flags, mfh_circuit **out);
 int mfh_circuit_create_sum(mfh_ctx *ctx, uint32_t nin, uint32_t ngates, const uint32_t *h_gates, uint32_t nasserts, const uint32_t *h_asserts,
                            uint32_t nequal, const uint32_t *h_equal, uint32_t nout, const uint32_t *h_outputs, uint32_t nterms_total,
                            const uint32_t *h_terms, uint32_t flags, mfh_circuit **out);
-/* every kind of program */
 void mfh_circuit_destroy(mfh_circuit *c);
-/* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored).  Row b of h_witness_bits
- * (bits_stride bytes) becomes the witness bit string of statement b: bit i - 1 = wire i, bits >= nin + ngates zero -- the layout mfh_prove_batch reads.
- * h_holds[b] = 1 if every assertion holds on statement b, else 0.  Bitsliced: one workgroup serves 32 statements, one word per wire (in LDS for a
- * mfh_circuit_create program, in device memory for a mfh_circuit_create_global one).
+/* nstmt statements: row b of h_inputs (in_stride bytes) holds the nin input bits, LSB first (bits >= nin are ignored, and so is input bit p - 1 of an
+ * output wire p).  Row b of h_witness_bits (bits_stride bytes) becomes the witness bit string of statement b: bit i - 1 = wire i, bits >= nin + ngates
+ * zero -- the layout mfh_prove_batch reads; after the last level and before the assertions and equalities are folded, wire w's value is written onto
+ * wire p for every output pair, so bits [0, lu) of a witness row carry the computed statement.  h_holds[b] = 1 if every value assertion and every
+ * equality holds on statement b, else 0.  Bitsliced: one workgroup serves 32 statements, one word per wire; one launch per chunk of statements whatever the
+ * circuit's depth.  A chunk is 8 192 statements in the LDS kind; in the device-memory kind the most whole blocks whose staging, chunk x (in_stride +
+ * bits_stride + 1) bytes, fits 64 MiB and whose columns fit 256 MiB, at least one block (736 statements at d = 2^20 with 2 508-byte input rows).
  * MFH_EINVAL for in_stride * 8 < nin or bits_stride * 8 < nin + ngates; nstmt = 0 does nothing.  Staged through the context's pinned buffers
  * (mfh_scrub_staging zeroes them); the call synchronises the context's stream. */
 int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const uint8_t *h_inputs, size_t in_stride, uint8_t *h_witness_bits,
