@@ -505,7 +505,7 @@ void launch(mfh_ctx *ctx, const mfh_circuit *c, const Chunk &k) {
   const dim3 grid((k.n + CSTMT - 1) / CSTMT);
   const Program &p = c->p;
   if constexpr (GLOBAL)
-    hipLaunchKernelGGL((k_circuit_eval_global<EX, OUT, SUM>), grid, dim3(CWG), 0, ctx->stream, p.gates, p.lp, p.nlev, p.asserts, p.nasserts, p.nin, p.nw, (uint32_t *)ctx->circ_state, k.colw, k.in, k.in_stride,
+    hipLaunchKernelGGL((k_circuit_eval_global<EX, OUT, SUM>), grid, dim3(CWG), 0, ctx->stream, p.gates, p.lp, p.nlev, p.asserts, p.nasserts, p.nin, p.nw, ctx->circ_state.as<uint32_t>(), k.colw, k.in, k.in_stride,
                        k.n, k.out, k.bits_stride, k.holds, p.equal, p.nequal, p.outputs, p.nout, p.terms, p.hp);
   else
     hipLaunchKernelGGL((k_circuit_eval<EX, OUT, SUM>), grid, dim3(CWG), 0, ctx->stream, p.gates, p.lp, p.nlev, p.asserts, p.nasserts, p.nin, p.nw, k.in, k.in_stride, k.n, k.out, k.bits_stride, k.holds, p.equal, p.nequal, p.outputs, p.nout, p.terms, p.hp);
@@ -576,13 +576,13 @@ int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const
     ch = (uint32_t)std::min<size_t>(nstmt, blocks * CSTMT);
   }
   const size_t in_b = (size_t)ch * in_stride, out_b = (size_t)ch * bits_stride, io_b = in_b + out_b + ch;
-  if (int rc = buf_reserve(ctx, ctx->circ_io, ctx->circ_io_bytes, io_b)) return rc;
+  if (int rc = work_reserve(ctx, ctx->circ_io, io_b)) return rc;
   if (c->global)
-    if (int rc = buf_reserve(ctx, ctx->circ_state, ctx->circ_state_bytes, (size_t)(ch + CSTMT - 1) / CSTMT * colw * 4)) return rc;
+    if (int rc = work_reserve(ctx, ctx->circ_state, (size_t)(ch + CSTMT - 1) / CSTMT * colw * 4)) return rc;
   uint8_t *pin_in = in_b ? (uint8_t *)pin_acquire(ctx, ctx->pin_rows, in_b) : nullptr;
   uint8_t *pin_out = (uint8_t *)pin_acquire(ctx, ctx->pin_cw, out_b + ch);
   if ((in_b && !pin_in) || !pin_out) return MFH_ENOMEM;
-  uint8_t *d_in = (uint8_t *)ctx->circ_io, *d_out = d_in + in_b, *d_holds = d_out + out_b;
+  uint8_t *d_in = ctx->circ_io.as<uint8_t>(), *d_out = d_in + in_b, *d_holds = d_out + out_b;
   int rc = MFH_OK;
   for (uint32_t b0 = 0; b0 < nstmt && rc == MFH_OK; b0 += ch) {
     const uint32_t n = std::min(ch, nstmt - b0);

@@ -35,6 +35,13 @@ struct PinBuf {
   size_t used = 0;  // bytes the last user asked for: what pin_scrub zeroes
 };
 
+// grow-only device scratch: dev_reserve / dev_free below
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;  // bytes
+  template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
 struct mfh_ctx {
   mfh_params P{};
   int device = 0;
@@ -43,24 +50,19 @@ struct mfh_ctx {
   mf::AesKey key{};
   bool have_seed = false;
   uint32_t *d_t0 = nullptr;  // 256 words
-  void *ws = nullptr;        // scratch (partials etc.)
-  size_t ws_bytes = 0;
-  void *ws2 = nullptr;       // second scratch of mfh_eval_rows_multi: the launch in flight on the side stream (mfh_prove_batch)
-  size_t ws2_bytes = 0;
+  DevBuf ws;                 // scratch (partials etc.)
+  DevBuf ws2;                // second scratch of mfh_eval_rows_multi: the launch in flight on the side stream (mfh_prove_batch)
   int mm_ws_sel = 0;         // 0: ws, 1: ws2
-  void *ws3 = nullptr;       // mfh_prove_batch, streaming regime: digit fragments and partial products of all rounds of a super-group
-  size_t ws3_bytes = 0;
+  DevBuf ws3;                // mfh_prove_batch, streaming regime: digit fragments and partial products of all rounds of a super-group
   std::vector<hipEvent_t> ev_cdone, ev_rdone, ev_wdone;  // mfh_prove_batch: chain of super-group k done / its w | h | v area read / its witness pass done (per area)
   std::vector<hipEvent_t> ev_round;  // one per round: its streaming launch has finished
   std::vector<hipEvent_t> ev_sgdone;  // mfh_prove_batch: super-group k's proofs are final in d_proofs (mfh_prove_batch_stream_wait)
   uint32_t last_batch_sg = 0, last_batch_n = 0;  // super-group size and statement count of the last mfh_prove_batch call
-  void *wws = nullptr;       // scratch of the witness pass (its own buffer: the pass may run beside an eval launch that owns `ws`)
-  size_t wws_bytes = 0;
-  // lazy-carry image (one u64 per accumulator word and coordinate) + active-row counter of the eval launches.  Invariant: all
-  // zero between launches (k_eval_reduce_carry clears what it reads), so no memset is queued per evaluation.
-  uint64_t *lazy = nullptr;
+  DevBuf wws;                // scratch of the witness pass (its own buffer: the pass may run beside an eval launch that owns `ws`)
+  // lazy-carry image (one u64 per accumulator word and coordinate) + active-row counter of the eval launches (the buffer's last 256 bytes).
+  // Invariant: all zero between launches (k_eval_reduce_carry clears what it reads), so no memset is queued per evaluation.
+  DevBuf lazy;
   uint32_t *lazy_cnt = nullptr;
-  size_t lazy_bytes = 0;
   bool eval_dense = false;  // caller's hint: the coefficient vectors have (practically) no zero entry, skip the row compaction
   // prover overlap: witness pass + polynomial step on `side` while b_w's rows are evaluated on `stream` (snark.hip)
   bool overlap = true;
@@ -83,31 +85,23 @@ struct mfh_ctx {
   uint64_t last_work_rows = 0;
   std::vector<hipEvent_t> ev_pool;
   PolyState *poly = nullptr;  // NTT tables and per-SSP precomputation (poly.hip)
-  void *aux = nullptr;        // small scratch that must survive an eval/encrypt launch (snark.hip)
-  size_t aux_bytes = 0;
-  uint32_t *d_msg = nullptr;  // setup messages
-  size_t msg_rows = 0;
-  uint32_t *d_prover = nullptr;  // prover polynomials w, v, h and the b_w coefficient vector
-  size_t prover_words = 0;
+  DevBuf aux;                 // small scratch that must survive an eval/encrypt launch
+  DevBuf d_msg;               // setup messages
+  DevBuf d_prover;            // prover polynomials w, v, h and the b_w coefficient vector
   std::vector<uint32_t> h_cw;
   const uint8_t *mm_image = nullptr;  // CRS expanded for the matrix-core path (mfh_crs_expand_mm): S | AS | BT+BV regions
   uint32_t mm_rank = 0, mm_world = 1;  // whose row shares the image holds (mfh_crs_set_resident_mm_share)
   uint64_t mm_off[3] = {0, 0, 0}, mm_rows[3] = {0, 0, 0};
   size_t mm_base[3] = {0, 0, 0};
-  void *ssp_frag = nullptr;  // the dense SSP in MFMA B-fragment order (evalmm.hip: witness pass of the batch prover); built lazily
-  size_t ssp_frag_bytes = 0;
+  DevBuf ssp_frag;  // the dense SSP in MFMA B-fragment order (evalmm.hip: witness pass of the batch prover); built lazily
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
-  void *circ_io = nullptr;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
-  size_t circ_io_bytes = 0;
-  void *circ_state = nullptr;  // mfh_circuit_assign of a mfh_circuit_create_global program: the wire words of one chunk, one column per 32 statements
-  size_t circ_state_bytes = 0;
-  void *d_batch = nullptr;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
-  size_t batch_bytes = 0;
+  DevBuf circ_io;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
+  DevBuf circ_state;  // mfh_circuit_assign of a mfh_circuit_create_global program: the wire words of one chunk, one column per 32 statements
+  DevBuf d_batch;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
   // mfh_prove_batch, more than one group of proofs and no image registered: the CRS is expanded ONCE PER CALL into this scratch in
   // MFMA A-fragment order and streamed for every group (k_mmstream) instead of running AES again per group (mfh_set_batch_image)
-  void *batch_img = nullptr;
-  size_t batch_img_bytes = 0;
+  DevBuf batch_img;
   int batch_image = 1;
   // k_mmstream launches with several groups (mfh_set_mm_stream): slot -> (group, tile group) map, persistent grid, rendezvous of the sharers
   int mm_map = 1;
@@ -137,15 +131,13 @@ struct mfh_ctx {
   PinBuf pin_rows, pin_cw, pin_smudge;
   // public inputs (mfh_prove_public / mfh_prove_batch_public): the statement bits, ceil(lu / 8) bytes per statement, staged and on the device
   PinBuf pin_pub;
-  uint8_t *d_pub = nullptr;
-  size_t pub_bytes = 0;
+  DevBuf d_pub;
   // the batch chain's witness staging (one per super-group of a call, evalmm.hip): a ring, so that queueing super-group k + 1 does not wait on the host for
   // super-group k's copy to have RUN (with one buffer mfh_prove_batch blocked its caller for half of the call's GPU time)
   PinBuf pin_wring[8];
   uint32_t pin_wnext = 0;
   hipEvent_t ev_sample = nullptr;  // ... recorded behind the last reader of sample_tmp: the next call (on whatever stream) waits for it before it overwrites the buffer
-  void *sample_tmp = nullptr;  // mfh_sample_rows: the rows' raw stream bytes (small requests; kept so that the call neither allocates nor waits)
-  size_t sample_bytes = 0;
+  DevBuf sample_tmp;  // mfh_sample_rows: the rows' raw stream bytes (small requests; kept so that the call neither allocates nor waits)
   void *uploader = nullptr;  // mfh_ssp_upload: per-thread pinned / device staging pairs and streams (mfhip.hip), made on the first large upload
   // generator-defined SSP (ssp_prg.hpp): used by every entry point that is handed d_ssp == NULL
   bool prg_on = false;
@@ -217,6 +209,62 @@ inline void pin_free(PinBuf &b) {
   b = PinBuf();
 }
 
+// What a grow waits for before it frees the old block: the caller's stream, or -- buffers that side streams read -- the whole device.
+enum class DevWait { stream, device };
+inline void dev_free(DevBuf &b) {  // (no wait: a caller that needs one does it first)
+  if (b.p) hipFree(b.p);
+  b = DevBuf();
+}
+// allocates into an EMPTY buffer; false, and the buffer stays empty, when there is no room.  (No c->err: the batch prover's transient image is taken
+// only "if it fits", and a miss there is no error.)
+inline bool dev_alloc(DevBuf &b, size_t bytes) {
+  if (hipMalloc(&b.p, bytes) != hipSuccess) {
+    b = DevBuf();
+    return false;
+  }
+  b.cap = bytes;
+  return true;
+}
+// bytes <= capacity: nothing.  Else wait, free and allocate bytes rounded up to a multiple of gran (a power of two); MFH_ENOMEM leaves the buffer empty.
+inline int dev_reserve(mfh_ctx *c, DevBuf &b, size_t bytes, DevWait wait = DevWait::stream, size_t gran = 1) {
+  if (bytes <= b.cap) return MFH_OK;
+  if (b.p) {
+    if (wait == DevWait::device) hipDeviceSynchronize();
+    else hipStreamSynchronize(c->stream);
+    dev_free(b);
+  }
+  if (!dev_alloc(b, (bytes + gran - 1) & ~(gran - 1))) {
+    c->err = "hipMalloc(device scratch) failed";
+    return MFH_ENOMEM;
+  }
+  return MFH_OK;
+}
+// the batch prover's transient CRS image leaves (side streams read it: the whole device is awaited first).  The block is freed whatever the wait
+// returns; a failed wait is reported to the one caller that looks (mfh_set_batch_image).
+inline int batch_img_drop(mfh_ctx *c) {
+  if (!c->batch_img.p) return MFH_OK;
+  const hipError_t e = hipDeviceSynchronize();
+  dev_free(c->batch_img);
+  if (e != hipSuccess) {
+    c->err = std::string("hipDeviceSynchronize(): ") + hipGetErrorString(e);
+    return MFH_EDEVICE;
+  }
+  return MFH_OK;
+}
+inline int work_reserve(mfh_ctx *c, DevBuf &b, size_t bytes) { return dev_reserve(c, b, bytes, DevWait::stream, (size_t)1 << 20); }  // workspaces: 1 MiB steps
+inline int lazy_reserve(mfh_ctx *c, size_t bytes) {
+  if (bytes + 256 <= c->lazy.cap || !bytes) return MFH_OK;
+  bytes = ((bytes + 255) & ~(size_t)255) + 256;  // (+ the counter's 256 bytes)
+  if (int rc = dev_reserve(c, c->lazy, bytes)) return rc;
+  if (hipMemsetAsync(c->lazy.p, 0, bytes, c->stream) != hipSuccess) return MFH_EDEVICE;
+  c->lazy_cnt = reinterpret_cast<uint32_t *>(c->lazy.as<uint8_t>() + bytes - 256);
+  return MFH_OK;
+}
+inline int ws_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->ws, bytes); }
+inline int wws_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->wws, bytes); }
+inline int ws2_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->ws2, bytes); }
+inline int aux_reserve(mfh_ctx *c, size_t bytes) { return dev_reserve(c, c->aux, bytes); }
+
 // resolves the d_ssp argument of an entry point: a dense image, or (NULL) the registered row SSP or generator-defined SSP.  The row SSP is only
 // handed to callers that say they handle it (rows_ok): its `dense` is the prefix of slots [0, prefix), and a kernel that reads further would run
 // past it -- everyone else gets MFH_EUNSUPPORTED.
@@ -254,7 +302,6 @@ extern "C" int mfh_witness_poly_mm(mfh_ctx *c, const uint32_t *d_ssp, uint32_t n
 extern "C" int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                                         uint32_t col0, uint32_t ncols, uint32_t *d_w, size_t w_stride);
 extern "C" int mfh_poly_h_multi(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h, uint32_t nb);
-int aux_reserve(mfh_ctx *c, size_t bytes);
 // expandmm.hip: one region of the matrix-core CRS image (rows at stream offset off, their compressed ciphertexts c8), barrier-free writer
 int expand_mm_region(mfh_ctx *c, uint64_t off, uint32_t nrows, const uint8_t *c8, uint8_t *image);
 // encmm.hip: mfh_encrypt_rows with <sk, a> on the matrix cores (off and the row length multiples of 8)
@@ -316,42 +363,3 @@ void mms_bind(MmsPlan &P, void *ws);              // the launch's digit fragment
 int mms_digits(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs);
 int mms_stream(mfh_ctx *c, const MmsPlan &P);
 int mms_finish(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs, int accumulate);
-
-inline int buf_reserve(mfh_ctx *c, void *&buf, size_t &have, size_t bytes) {
-  if (bytes <= have) return MFH_OK;
-  if (buf) {
-    hipStreamSynchronize(c->stream);
-    hipFree(buf);
-    buf = nullptr;
-    have = 0;
-  }
-  bytes = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
-  if (hipMalloc(&buf, bytes) != hipSuccess) {
-    c->err = "hipMalloc(workspace) failed";
-    return MFH_ENOMEM;
-  }
-  have = bytes;
-  return MFH_OK;
-}
-inline int lazy_reserve(mfh_ctx *c, size_t bytes) {
-  if (bytes <= c->lazy_bytes) return MFH_OK;
-  if (c->lazy) {
-    hipStreamSynchronize(c->stream);
-    hipFree(c->lazy);
-    c->lazy = nullptr;
-    c->lazy_bytes = 0;
-  }
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (hipMalloc((void **)&c->lazy, bytes + 256) != hipSuccess) {
-    c->err = "hipMalloc(lazy image) failed";
-    return MFH_ENOMEM;
-  }
-  if (hipMemsetAsync(c->lazy, 0, bytes + 256, c->stream) != hipSuccess) return MFH_EDEVICE;
-  c->lazy_cnt = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(c->lazy) + bytes);
-  c->lazy_bytes = bytes;
-  return MFH_OK;
-}
-inline int ws_reserve(mfh_ctx *c, size_t bytes) { return buf_reserve(c, c->ws, c->ws_bytes, bytes); }
-inline int wws_reserve(mfh_ctx *c, size_t bytes) { return buf_reserve(c, c->wws, c->wws_bytes, bytes); }
-inline int ws2_reserve(mfh_ctx *c, size_t bytes) { return buf_reserve(c, c->ws2, c->ws2_bytes, bytes); }
-

@@ -416,7 +416,7 @@ int key_operands(mfh_ctx *c, const uint64_t *sk, uint32_t ctb, uint32_t rowlen, 
   const size_t bf_b = (size_t)nheads * ksteps * G::NQ * 1024;
   int rc = ws_reserve(c, sb_b + ps_b + bf_b + part_b);
   if (rc) return rc;
-  K.w = (uint8_t *)c->ws;
+  K.w = c->ws.as<uint8_t>();
   K.sb = (int8_t *)K.w;
   K.ps = (int64_t *)(K.w + sb_b);
   K.bf = (v4i *)(K.w + sb_b + ps_b);

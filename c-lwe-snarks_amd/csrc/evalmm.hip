@@ -1651,7 +1651,7 @@ int eval_rows_multi_io(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t *d_
   const size_t part_bytes = (size_t)nchunks * ntiles * mb * N * 4;
   int rc = c->mm_ws_sel ? ws2_reserve(c, cd_bytes + sc_bytes + part_bytes) : ws_reserve(c, cd_bytes + sc_bytes + part_bytes);
   if (rc) return rc;
-  uint8_t *wsp = (uint8_t *)(c->mm_ws_sel ? c->ws2 : c->ws);  // the launch on the side stream of mfh_prove_batch has its own scratch
+  uint8_t *wsp = (c->mm_ws_sel ? c->ws2 : c->ws).as<uint8_t>();  // the launch on the side stream of mfh_prove_batch has its own scratch
   int8_t *cd = (int8_t *)wsp;
   int64_t *sc = io.sc_zeroed ? io.sc_zeroed : (int64_t *)(wsp + cd_bytes);
   int *part = (int *)(wsp + cd_bytes + sc_bytes);
@@ -1851,7 +1851,7 @@ int eval_rows_multi_io_regions(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, 
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = c->mm_ws_sel ? ws2_reserve(c, mms_ws_bytes(P)) : ws_reserve(c, mms_ws_bytes(P));
   if (rc) return rc;
-  mms_bind(P, c->mm_ws_sel ? c->ws2 : c->ws);
+  mms_bind(P, (c->mm_ws_sel ? c->ws2 : c->ws).p);
   rc = mms_digits(c, P, ios, nvecs);
   if (!rc) rc = mms_stream(c, P);
   if (!rc) rc = mms_finish(c, P, ios, nvecs, accumulate);
@@ -2006,14 +2006,10 @@ int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, 
   const uint32_t nchunks = fused ? 1u : std::min(ksteps, 4u), kpc = (ksteps + nchunks - 1) / nchunks;
   // the SSP in B-fragment order: built on first use per SSP (mfh_ssp_prepare invalidates it), kept beside the uint32 image
   const size_t sfrag_b = (size_t)ksteps * 32 * d * 4;
-  if (src.dense && (c->ssp_frag_src != d_ssp || c->ssp_frag_bytes < sfrag_b)) {
-    if (c->ssp_frag_bytes < sfrag_b) {
-      if (c->ssp_frag) { hipStreamSynchronize(c->stream); hipFree(c->ssp_frag); c->ssp_frag = nullptr; c->ssp_frag_bytes = 0; }
-      HIP_TRY(c, hipMalloc(&c->ssp_frag, sfrag_b));
-      c->ssp_frag_bytes = sfrag_b;
-    }
+  if (src.dense && (c->ssp_frag_src != d_ssp || c->ssp_frag.cap < sfrag_b)) {
+    if (int rc0 = dev_reserve(c, c->ssp_frag, sfrag_b)) return rc0;
     const uint64_t nthreads = (uint64_t)ksteps * (d / 32) * 256;
-    hipLaunchKernelGGL(k_ssp_frag, dim3((uint32_t)((nthreads + 255) / 256)), dim3(256), 0, c->stream, d_ssp, nrowsel, d, (uint32_t *)c->ssp_frag);
+    hipLaunchKernelGGL(k_ssp_frag, dim3((uint32_t)((nthreads + 255) / 256)), dim3(256), 0, c->stream, d_ssp, nrowsel, d, c->ssp_frag.as<uint32_t>());
     HIP_TRY(c, hipGetLastError());
     c->ssp_frag_src = d_ssp;
   }
@@ -2036,7 +2032,7 @@ int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, 
     cd[2 * b] = cnt;
     cd[2 * b + 1] = h_delta[b];
   }
-  uint8_t *dev = (uint8_t *)c->wws;
+  uint8_t *dev = c->wws.as<uint8_t>();
   HIP_TRY(c, hipMemcpyAsync(dev, stage, head_b, hipMemcpyHostToDevice, c->stream));
   pin_release(c, wpin);
   const uint32_t *d_cd = (const uint32_t *)(dev + packed + ((8 - packed % 8) % 8));
@@ -2053,20 +2049,20 @@ int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, 
     else if (MT == 2) hipLaunchKernelGGL(k_witness_mm_prg<2>, grid, dim3(256), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
     else hipLaunchKernelGGL(k_witness_mm_prg<4>, grid, dim3(256), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
   } else if (MT == 8) {
-    hipLaunchKernelGGL(k_witness_mm8q, dim3(nc / 64, (ksteps + kpc - 1) / kpc), dim3(512), 0, c->stream, (const v4i *)c->ssp_frag, (const v4i *)d_frag, nrowsel, kpc, nc,
+    hipLaunchKernelGGL(k_witness_mm8q, dim3(nc / 64, (ksteps + kpc - 1) / kpc), dim3(512), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag, nrowsel, kpc, nc,
                        fused ? (int *)nullptr : d_part, tpoly, d_cd, nstmt, d_w, wc);
     if (fused) {
       HIP_TRY(c, hipGetLastError());
       return MFH_OK;
     }
   } else if (MT == 1)
-    hipLaunchKernelGGL(k_witness_mm<1>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, (const v4i *)c->ssp_frag, (const v4i *)d_frag,
+    hipLaunchKernelGGL(k_witness_mm<1>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
                        nrowsel, kpc, nc, d_part, wc);
   else if (MT == 2)
-    hipLaunchKernelGGL(k_witness_mm<2>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, (const v4i *)c->ssp_frag, (const v4i *)d_frag,
+    hipLaunchKernelGGL(k_witness_mm<2>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
                        nrowsel, kpc, nc, d_part, wc);
   else
-    hipLaunchKernelGGL(k_witness_mm<4>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, (const v4i *)c->ssp_frag, (const v4i *)d_frag,
+    hipLaunchKernelGGL(k_witness_mm<4>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
                        nrowsel, kpc, nc, d_part, wc);
   hipLaunchKernelGGL(k_witness_mm_finish, dim3((nc + 255) / 256, nstmt), dim3(256), 0, c->stream, d_part, (ksteps + kpc - 1) / kpc, tpoly, d_cd, nstmt, 32 * MT,
                      nc, d_w, (uint64_t)w_stride);

@@ -1117,7 +1117,6 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   ssp_interp_free(c);
   ssp_rows_free(c, true);
   upload_free(c);
-  if (c->sample_tmp) hipFree(c->sample_tmp);
   if (c->ev_sample) hipEventDestroy(c->ev_sample);
   pin_free(c->pin_rows);
   for (auto &b : c->pin_wring) pin_free(b);
@@ -1125,32 +1124,22 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   pin_free(c->pin_smudge);
   pin_free(c->pin_pub);
   if (c->side) hipStreamSynchronize(c->side);
-  if (c->ws) hipFree(c->ws);
-  if (c->wws) hipFree(c->wws);
-  if (c->ws2) hipFree(c->ws2);
-  if (c->ws3) hipFree(c->ws3);
   if (c->mm_sync) hipFree(c->mm_sync);
   for (hipEvent_t e : c->ev_round) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_sgdone) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_cdone) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_rdone) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_wdone) hipEventDestroy(e);
-  if (c->lazy) hipFree(c->lazy);
-  if (c->aux) hipFree(c->aux);
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_join) hipEventDestroy(c->ev_join);
   if (c->ev_chain) hipEventDestroy(c->ev_chain);
   if (c->ev_chain_done) hipEventDestroy(c->ev_chain_done);
   if (c->side) hipStreamDestroy(c->side);
   if (c->side2) hipStreamDestroy(c->side2);
-  if (c->d_msg) hipFree(c->d_msg);
-  if (c->d_prover) hipFree(c->d_prover);
-  if (c->d_pub) hipFree(c->d_pub);
-  if (c->d_batch) hipFree(c->d_batch);
-  if (c->batch_img) hipFree(c->batch_img);
-  if (c->circ_io) hipFree(c->circ_io);
-  if (c->circ_state) hipFree(c->circ_state);
-  if (c->ssp_frag) hipFree(c->ssp_frag);
+  // every grow-only scratch, in one place: behind all the waits above and the side streams' end, so none goes earlier than it used to
+  for (DevBuf *b : {&c->ws, &c->ws2, &c->ws3, &c->wws, &c->lazy, &c->aux, &c->d_msg, &c->d_prover, &c->d_pub, &c->d_batch, &c->batch_img, &c->circ_io,
+                    &c->circ_state, &c->ssp_frag, &c->sample_tmp})
+    dev_free(*b);
   if (c->d_t0) hipFree(c->d_t0);
   for (auto &t : c->timed) { hipEventDestroy(t.e0); hipEventDestroy(t.e1); }
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -1180,7 +1169,7 @@ int mfh_scrub_staging(mfh_ctx *c) {
 }
 
 const char *mfh_last_error(const mfh_ctx *c) { return c ? c->err.c_str() : "null context"; }
-size_t mfh_workspace_bytes(const mfh_ctx *c) { return c ? c->ws_bytes : 0; }
+size_t mfh_workspace_bytes(const mfh_ctx *c) { return c ? c->ws.cap : 0; }
 int mfh_set_overlap(mfh_ctx *c, int en) {
   if (!c) return MFH_EINVAL;
   c->overlap = en != 0;
@@ -1237,13 +1226,7 @@ int mfh_set_batch_bw(mfh_ctx *c, int merged) {
 int mfh_set_batch_image(mfh_ctx *c, int en) {
   if (!c) return MFH_EINVAL;
   c->batch_image = en != 0;
-  if (!en && c->batch_img) {
-    HIP_TRY(c, hipDeviceSynchronize());
-    hipFree(c->batch_img);
-    c->batch_img = nullptr;
-    c->batch_img_bytes = 0;
-  }
-  return MFH_OK;
+  return en ? MFH_OK : batch_img_drop(c);
 }
 
 int mfh_set_timing(mfh_ctx *c, int en) {
@@ -1369,12 +1352,12 @@ int mfh_digest128(mfh_ctx *c, const void *d_buf, size_t nbytes, uint64_t h_diges
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = aux_reserve(c, 16);
   if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->aux, 0, 16, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->aux.p, 0, 16, c->stream));
   const uint64_t nwords = (nbytes + 3) / 4;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (nwords + 255) / 256);
-  if (grid) hipLaunchKernelGGL(k_digest128, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)d_buf, (uint64_t)nbytes, (unsigned long long *)c->aux);
+  if (grid) hipLaunchKernelGGL(k_digest128, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)d_buf, (uint64_t)nbytes, c->aux.as<unsigned long long>());
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(h_digest, c->aux, 16, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_digest, c->aux.p, 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MFH_OK;
 }
@@ -1406,12 +1389,8 @@ int mfh_sample_rows(mfh_ctx *c, uint64_t off, size_t nrows, uint64_t *d_out) {
   const bool kept = bytes <= ((uint64_t)16 << 20);
   void *tmp = nullptr;
   if (kept) {
-    if (c->sample_bytes < bytes) {
-      if (c->sample_tmp) { hipDeviceSynchronize(); hipFree(c->sample_tmp); c->sample_tmp = nullptr; c->sample_bytes = 0; }
-      HIP_TRY(c, hipMalloc(&c->sample_tmp, bytes));
-      c->sample_bytes = bytes;
-    }
-    tmp = c->sample_tmp;
+    if (int rc0 = dev_reserve(c, c->sample_tmp, bytes, DevWait::device)) return rc0;
+    tmp = c->sample_tmp.p;
     // the buffer is the context's, the stream is whatever the caller set for THIS call: a previous call on another stream may still be repacking out of it
     if (!c->ev_sample) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_sample, hipEventDisableTiming));
     else HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_sample, 0));
@@ -1496,12 +1475,12 @@ static int eval_rows(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t *c8, 
   if (rc) return rc;
   rc = lazy_reserve(c, (size_t)nacc * S::KW * (size_t)std::max(NJ, ntiles * S::TILE) * 8);
   if (rc) return rc;
-  uint32_t *part = (uint32_t *)c->ws;
-  uint64_t *lazy = c->lazy;
+  uint32_t *part = c->ws.as<uint32_t>();
+  uint64_t *lazy = c->lazy.as<uint64_t>();
   uint32_t *cnt = c->lazy_cnt;
   uint32_t *idx = nullptr;
   if (!c->eval_dense) {  // drop the rows whose coefficients are all zero (the reference expands them only to advance its stream)
-    idx = (uint32_t *)((uint8_t *)c->ws + part_bytes);
+    idx = (uint32_t *)(c->ws.as<uint8_t>() + part_bytes);
     hipLaunchKernelGGL(k_compact_rows, dim3(((uint32_t)nrows + 255) / 256), dim3(256), 0, c->stream, c0, c1, (uint32_t)nrows, idx, cnt);
     HIP_TRY(c, hipGetLastError());
   }
@@ -1563,12 +1542,12 @@ static int eval_rows_resident(mfh_ctx *c, const uint8_t *rows, size_t row_base, 
   if (rc) return rc;
   rc = lazy_reserve(c, (size_t)nacc * S::KW * NJ * 8);
   if (rc) return rc;
-  uint32_t *part = (uint32_t *)c->ws;
-  uint64_t *lazy = c->lazy;
+  uint32_t *part = c->ws.as<uint32_t>();
+  uint64_t *lazy = c->lazy.as<uint64_t>();
   uint32_t *cnt = c->lazy_cnt;
   uint32_t *idx = nullptr;
   if (!c->eval_dense) {
-    idx = (uint32_t *)((uint8_t *)c->ws + part_bytes);
+    idx = (uint32_t *)(c->ws.as<uint8_t>() + part_bytes);
     hipLaunchKernelGGL(k_compact_rows, dim3(((uint32_t)nrows + 255) / 256), dim3(256), 0, c->stream, c0, c1, (uint32_t)nrows, idx, cnt);
     HIP_TRY(c, hipGetLastError());
   }
@@ -1720,7 +1699,7 @@ static int encrypt_rows(mfh_ctx *c, uint64_t off, size_t nrows, const uint64_t *
   const size_t pb_bytes = (size_t)nrows * ntiles * S::KW * 4;
   int rc = ws_reserve(c, pb_bytes);
   if (rc) return rc;
-  uint32_t *pb = (uint32_t *)c->ws;
+  uint32_t *pb = c->ws.as<uint32_t>();
   {
     Timer t(c, 3, nrows);
     hipLaunchKernelGGL(k_encrypt<LOGQ>, dim3(ntiles, gy), dim3(S::THREADS), 0, c->stream, c->key, c->d_t0, off, n, (uint32_t)nrows, rpc, sk, pb);
@@ -1814,12 +1793,12 @@ int mfh_ct_smudge(mfh_ctx *c, uint64_t *d_cts, size_t count, const uint8_t *h_ma
   memcpy(stage + ub, h_sign, count);
   int rc = aux_reserve(c, ub + count);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->aux, stage, ub + count, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->aux.p, stage, ub + count, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_smudge);
-  DISPATCH_LOGQ(c, hipLaunchKernelGGL(k_smudge<736>, dim3(((uint32_t)count + 63) / 64), dim3(64), 0, c->stream, d_cts, c->P.n, (const uint32_t *)c->aux,
-                                      (const uint8_t *)c->aux + ub, (uint32_t)count),
-                hipLaunchKernelGGL(k_smudge<1472>, dim3(((uint32_t)count + 63) / 64), dim3(64), 0, c->stream, d_cts, c->P.n, (const uint32_t *)c->aux,
-                                   (const uint8_t *)c->aux + ub, (uint32_t)count));
+  DISPATCH_LOGQ(c, hipLaunchKernelGGL(k_smudge<736>, dim3(((uint32_t)count + 63) / 64), dim3(64), 0, c->stream, d_cts, c->P.n, c->aux.as<uint32_t>(),
+                                      c->aux.as<uint8_t>() + ub, (uint32_t)count),
+                hipLaunchKernelGGL(k_smudge<1472>, dim3(((uint32_t)count + 63) / 64), dim3(64), 0, c->stream, d_cts, c->P.n, c->aux.as<uint32_t>(),
+                                   c->aux.as<uint8_t>() + ub, (uint32_t)count));
   HIP_TRY(c, hipGetLastError());
   return MFH_OK;
 }
@@ -1947,8 +1926,8 @@ static int witness_partials(mfh_ctx *c, const mf::SspSrc &src, const uint8_t *h_
   const size_t rows_b = ((size_t)m * 4 + 255) & ~(size_t)255;
   int rc = wws_reserve(c, rows_b + (size_t)G * d * 8);
   if (rc) return rc;
-  uint32_t *d_rows = (uint32_t *)c->wws;
-  uint64_t *partial = (uint64_t *)((uint8_t *)c->wws + rows_b);
+  uint32_t *d_rows = c->wws.as<uint32_t>();
+  uint64_t *partial = (uint64_t *)(c->wws.as<uint8_t>() + rows_b);
   if (nsel) HIP_TRY(c, hipMemcpyAsync(d_rows, rows + lo, (size_t)nsel * 4, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_rows);
   if (src.dense)
@@ -2040,8 +2019,8 @@ int mfh_witness_poly_multi(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, co
   const size_t list_b = ((size_t)m * 8 + 255) & ~(size_t)255;
   int rc = wws_reserve(c, list_b + (size_t)NB * G * d * 8);
   if (rc) return rc;
-  uint2 *d_list = (uint2 *)c->wws;
-  uint64_t *partial = (uint64_t *)((uint8_t *)c->wws + list_b);
+  uint2 *d_list = c->wws.as<uint2>();
+  uint64_t *partial = (uint64_t *)(c->wws.as<uint8_t>() + list_b);
   if (nsel) HIP_TRY(c, hipMemcpyAsync(d_list, list, (size_t)nsel * 8, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_rows);
   if (src.dense)

@@ -223,22 +223,6 @@ inline dim3 g1(uint32_t n) { return dim3((n + 255) / 256); }
 
 }  // namespace
 
-int aux_reserve(mfh_ctx *c, size_t bytes) {
-  if (bytes <= c->aux_bytes) return MFH_OK;
-  if (c->aux) {
-    hipStreamSynchronize(c->stream);
-    hipFree(c->aux);
-    c->aux = nullptr;
-    c->aux_bytes = 0;
-  }
-  if (hipMalloc(&c->aux, bytes) != hipSuccess) {
-    c->err = "hipMalloc(aux) failed";
-    return MFH_ENOMEM;
-  }
-  c->aux_bytes = bytes;
-  return MFH_OK;
-}
-
 extern "C" {
 
 int mfh_ssp_prepare(mfh_ctx *c, const uint32_t *d_ssp) {
@@ -260,7 +244,7 @@ int mfh_setup_messages(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32
   if (rc) return rc;
   rc = aux_reserve(c, (size_t)d * 4);
   if (rc) return rc;
-  uint32_t *pw = (uint32_t *)c->aux;
+  uint32_t *pw = c->aux.as<uint32_t>();
   hipLaunchKernelGGL(k_powers, g1(d), dim3(256), 0, c->stream, s, d, pw);
   hipLaunchKernelGGL(k_msg_powers, g1(d), dim3(256), 0, c->stream, pw, d, alpha, d_msg);
   if (src.prefix) {  // the row SSP: v_r(s) from its rows, not from coefficients it does not store
@@ -272,27 +256,33 @@ int mfh_setup_messages(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32
   return MFH_OK;
 }
 
-int mfh_setup(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, const uint64_t *d_sk, const uint64_t *d_err,
-              uint8_t *d_crs_c8) {
+// mfh_setup / mfh_setup_image / mfh_setup_public: the 2d + m messages, encrypted; lu > 0: rows v[0..lu) encrypt 0; d_rows_image != NULL: the rows expanded too
+static int setup_impl(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, uint32_t lu, const uint64_t *d_sk, const uint64_t *d_err,
+                      uint8_t *d_crs_c8, void *d_rows_image) {
   if (!c || !d_sk || !d_err || !d_crs_c8) return MFH_EINVAL;
   const size_t rows = (size_t)2 * c->P.d + c->P.m;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->d_msg || c->msg_rows < rows) {
-    if (c->d_msg) { hipStreamSynchronize(c->stream); hipFree(c->d_msg); c->d_msg = nullptr; }
-    HIP_TRY(c, hipMalloc(&c->d_msg, rows * 4));
-    c->msg_rows = rows;
-  }
-  int rc = mfh_setup_messages(c, d_ssp, alpha, beta, s, c->d_msg);
+  int rc = dev_reserve(c, c->d_msg, rows * 4);
   if (rc) return rc;
+  uint32_t *msg = c->d_msg.as<uint32_t>();
+  rc = mfh_setup_messages(c, d_ssp, alpha, beta, s, msg);
+  if (rc) return rc;
+  // rows v[0..lu) (messages 2d + 1 .. 2d + lu) encrypt 0 instead of beta v_i(s): same stream rows, same errors
+  if (lu) HIP_TRY(c, hipMemsetAsync(msg + (size_t)2 * c->P.d + 1, 0, (size_t)lu * 4, c->stream));
   // all 2d+m encryptions are consecutive rows of the stream starting at CTR_S = 0 (src/snark.c:75-110)
-  return mfh_encrypt_rows(c, 0, rows, d_sk, c->d_msg, d_err, d_crs_c8);
+  rc = mfh_encrypt_rows(c, 0, rows, d_sk, msg, d_err, d_crs_c8);
+  if (rc || !d_rows_image) return rc;
+  return mfh_crs_expand(c, 0, rows, d_crs_c8, d_rows_image);  // (same stream: behind the encryptions that write d_crs_c8)
+}
+
+int mfh_setup(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, const uint64_t *d_sk, const uint64_t *d_err,
+              uint8_t *d_crs_c8) {
+  return setup_impl(c, d_ssp, alpha, beta, s, 0, d_sk, d_err, d_crs_c8, nullptr);
 }
 
 int mfh_setup_image(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, const uint64_t *d_sk, const uint64_t *d_err,
                     uint8_t *d_crs_c8, void *d_rows_image) {
-  int rc = mfh_setup(c, d_ssp, alpha, beta, s, d_sk, d_err, d_crs_c8);
-  if (rc || !d_rows_image) return rc;
-  return mfh_crs_expand(c, 0, (size_t)2 * c->P.d + c->P.m, d_crs_c8, d_rows_image);  // (same stream: behind the encryptions that write d_crs_c8)
+  return setup_impl(c, d_ssp, alpha, beta, s, 0, d_sk, d_err, d_crs_c8, d_rows_image);
 }
 
 int mfh_verify(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta, uint32_t s, const uint64_t *d_sk, const uint64_t *d_proofs,
@@ -307,7 +297,7 @@ int mfh_verify(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t beta,
   if (rc) return rc;
   rc = aux_reserve(c, (size_t)d * 4 + 16 + count * 5 * 4);
   if (rc) return rc;
-  uint32_t *pw = (uint32_t *)c->aux, *scal = pw + d, *dec = scal + 4;
+  uint32_t *pw = c->aux.as<uint32_t>(), *scal = pw + d, *dec = scal + 4;
   hipLaunchKernelGGL(k_powers, g1(d), dim3(256), 0, c->stream, s, d, pw);
   hipLaunchKernelGGL(k_eval_slots01, dim3(2), dim3(256), 0, c->stream, src, pw, d, scal);
   HIP_TRY(c, hipGetLastError());
@@ -324,22 +314,7 @@ int mfh_setup_public(mfh_ctx *c, const uint32_t *d_ssp, uint32_t alpha, uint32_t
   if (!c) return MFH_EINVAL;
   if (lu >= c->P.m) { c->err = "lu must be < m (the m - 1 wires of the SSP)"; return MFH_EINVAL; }
   if (int rc0 = ssp_rows_lu_check(c, d_ssp, lu)) return rc0;
-  if (!lu) return mfh_setup_image(c, d_ssp, alpha, beta, s, d_sk, d_err, d_crs_c8, d_rows_image);
-  if (!d_sk || !d_err || !d_crs_c8) return MFH_EINVAL;
-  const size_t rows = (size_t)2 * c->P.d + c->P.m;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->d_msg || c->msg_rows < rows) {
-    if (c->d_msg) { hipStreamSynchronize(c->stream); hipFree(c->d_msg); c->d_msg = nullptr; }
-    HIP_TRY(c, hipMalloc(&c->d_msg, rows * 4));
-    c->msg_rows = rows;
-  }
-  int rc = mfh_setup_messages(c, d_ssp, alpha, beta, s, c->d_msg);
-  if (rc) return rc;
-  // rows v[0..lu) (messages 2d + 1 .. 2d + lu) encrypt 0 instead of beta v_i(s): same stream rows, same errors
-  HIP_TRY(c, hipMemsetAsync(c->d_msg + (size_t)2 * c->P.d + 1, 0, (size_t)lu * 4, c->stream));
-  rc = mfh_encrypt_rows(c, 0, rows, d_sk, c->d_msg, d_err, d_crs_c8);
-  if (rc || !d_rows_image) return rc;
-  return mfh_crs_expand(c, 0, rows, d_crs_c8, d_rows_image);
+  return setup_impl(c, d_ssp, alpha, beta, s, lu, d_sk, d_err, d_crs_c8, d_rows_image);
 }
 
 int mfh_vk_derive(mfh_ctx *c, const uint32_t *d_ssp, uint32_t s, uint32_t lu, uint32_t *d_vk) {
@@ -354,7 +329,7 @@ int mfh_vk_derive(mfh_ctx *c, const uint32_t *d_ssp, uint32_t s, uint32_t lu, ui
   if ((rc = ssp_rows_lu_check(c, d_ssp, lu))) return rc;
   rc = aux_reserve(c, (size_t)d * 4);
   if (rc) return rc;
-  uint32_t *pw = (uint32_t *)c->aux;
+  uint32_t *pw = c->aux.as<uint32_t>();
   hipLaunchKernelGGL(k_powers, g1(d), dim3(256), 0, c->stream, s, d, pw);
   hipLaunchKernelGGL(k_eval_slots01, dim3(lu + 2), dim3(256), 0, c->stream, src, pw, d, d_vk);  // slots 0 (t), 1 (v_0), 2 .. lu + 1 (v_1 .. v_lu)
   HIP_TRY(c, hipGetLastError());
@@ -373,8 +348,8 @@ int mfh_verify_public(mfh_ctx *c, const uint32_t *d_vk, uint32_t lu, uint32_t al
   const size_t dec_b = (count * 5 * 4 + 15) & ~(size_t)15;
   int rc = aux_reserve(c, dec_b + count * ub + 16);
   if (rc) return rc;
-  uint32_t *dec = (uint32_t *)c->aux;
-  uint8_t *ubits = (uint8_t *)c->aux + dec_b;
+  uint32_t *dec = c->aux.as<uint32_t>();
+  uint8_t *ubits = c->aux.as<uint8_t>() + dec_b;
   if (lu) {
     uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_cw, count * ub);
     if (!st) return MFH_ENOMEM;
@@ -437,12 +412,8 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
   HIP_TRY(c, hipSetDevice(c->device));
   // prover scratch: w, v, h (d each), cw (m), the statement bits (lu < m bits)
   const size_t pwords = (size_t)3 * d + m + (m + 31) / 32;
-  if (!c->d_prover || c->prover_words < pwords) {
-    if (c->d_prover) { hipStreamSynchronize(c->stream); hipFree(c->d_prover); c->d_prover = nullptr; }
-    HIP_TRY(c, hipMalloc(&c->d_prover, pwords * 4));
-    c->prover_words = pwords;
-  }
-  uint32_t *w = c->d_prover, *v = w + d, *h = v + d, *cw = h + d;
+  if (int rc0 = dev_reserve(c, c->d_prover, pwords * 4)) return rc0;
+  uint32_t *w = c->d_prover.as<uint32_t>(), *v = w + d, *h = v + d, *cw = h + d;
   uint8_t *ubits = (uint8_t *)(cw + m);
   uint64_t *pi_h = d_partial, *pi_hat_h = d_partial + ctl, *pi_hat_v = d_partial + 2 * ctl, *pi_v_w = d_partial + 3 * ctl,
            *pi_b_w = d_partial + 4 * ctl;
@@ -652,12 +623,8 @@ int batch_scratch(mfh_ctx *c, uint32_t nproofs, uint32_t whv /* w | h | v areas 
   const size_t KW = 2 * (c->P.logq / 64);
   const size_t sm_b = ((size_t)nsmudge * 5 * (KW * 4 + 1) + 255) & ~(size_t)255;
   const size_t need = whv_b + cw_pad * ncw + sm_b + 256 + ctl * 8 + B.nslots * 2048;
-  if (c->batch_bytes < need) {
-    if (c->d_batch) { hipDeviceSynchronize(); hipFree(c->d_batch); c->d_batch = nullptr; c->batch_bytes = 0; }
-    HIP_TRY(c, hipMalloc(&c->d_batch, need));
-    c->batch_bytes = need;
-  }
-  uint8_t *base = (uint8_t *)c->d_batch;
+  if (int rc = dev_reserve(c, c->d_batch, need, DevWait::device)) return rc;
+  uint8_t *base = c->d_batch.as<uint8_t>();
   B.WHV = (uint32_t *)base;
   B.CW = base + whv_b;
   B.cw_stride = cw_pad;
@@ -937,11 +904,11 @@ int batch_rows_supergroup(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, ui
       if (ws_slot != 0) { c->err = "early chain: a later super-group needs more scratch than the call's first"; return MFH_EINVAL; }
       c->early_ws_half = ws_need;
     }
-    rc = buf_reserve(c, c->ws3, c->ws3_bytes, early ? 2 * c->early_ws_half : ws_need);
+    rc = work_reserve(c, c->ws3, early ? 2 * c->early_ws_half : ws_need);
     if (rc) return rc;
     size_t wo = early ? (size_t)(ws_slot & 1) * c->early_ws_half : 0;
     for (uint32_t r = 0; r < R; r++) {
-      mms_bind(plan[r], (uint8_t *)c->ws3 + wo);
+      mms_bind(plan[r], c->ws3.as<uint8_t>() + wo);
       wo += (mms_ws_bytes(plan[r]) + 255) & ~(size_t)255;
       rc = mms_digits(c, plan[r], io[r], nv[r]);
       if (rc) return rc;
@@ -1038,18 +1005,17 @@ int batch_transient_image(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nproofs,
   const uint32_t ctb = c->P.logq / 8;
   if (c->mm_image || !c->batch_image || nproofs <= BG || (((uint64_t)c->P.n * ctb) & 7)) return MFH_OK;
   const size_t ib = mfh_crs_mm_share_bytes(c, rank, world);
-  if (c->batch_img_bytes < ib) {
-    if (c->batch_img) { hipDeviceSynchronize(); hipFree(c->batch_img); c->batch_img = nullptr; c->batch_img_bytes = 0; }
+  if (c->batch_img.cap < ib) {
+    (void)batch_img_drop(c);
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = 0;
     // no room (the rest of the call and the caller need memory too): the groups regenerate the keystream
-    if (ib <= mem_free / 4 * 3 && hipMalloc(&c->batch_img, ib) == hipSuccess) c->batch_img_bytes = ib;
-    else { c->batch_img = nullptr; (void)hipGetLastError(); }
+    if (ib > mem_free / 4 * 3 || !dev_alloc(c->batch_img, ib)) (void)hipGetLastError();
   }
-  if (!c->batch_img) return MFH_OK;
-  int rc = mfh_crs_expand_mm_share(c, d_crs_c8, rank, world, (uint8_t *)c->batch_img);
+  if (!c->batch_img.p) return MFH_OK;
+  int rc = mfh_crs_expand_mm_share(c, d_crs_c8, rank, world, c->batch_img.as<uint8_t>());
   if (rc) return rc;
-  mfh_crs_set_resident_mm_share(c, (const uint8_t *)c->batch_img, rank, world);
+  mfh_crs_set_resident_mm_share(c, c->batch_img.as<uint8_t>(), rank, world);
   guard.on = true;
   return MFH_OK;
 }
@@ -1099,7 +1065,7 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
   else if (slabs_ok) {
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-      const size_t ib = mfh_crs_mm_image_bytes(c), avail = mem_free + c->batch_img_bytes + c->batch_bytes;  // (what the context holds is re-used)
+      const size_t ib = mfh_crs_mm_image_bytes(c), avail = mem_free + c->batch_img.cap + c->d_batch.cap;  // (what the context holds is re-used)
       if (ib > avail / 4 * 3) {
         const size_t budget = std::max<size_t>(avail / 3, (size_t)1 << 30);
         nsl = (uint32_t)std::min<size_t>(256, (ib + budget - 1) / budget);
@@ -1176,12 +1142,11 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     for (;;) {
       size_t ib = 0;
       for (uint32_t r = 0; r < nsl; r++) ib = std::max(ib, mfh_crs_mm_share_bytes(c, r, nsl));
-      if (c->batch_img_bytes >= ib) break;
-      if (c->batch_img) { hipDeviceSynchronize(); hipFree(c->batch_img); c->batch_img = nullptr; c->batch_img_bytes = 0; }
+      if (c->batch_img.cap >= ib) break;
+      (void)batch_img_drop(c);
       size_t mem_free = 0, mem_total = 0;
       const bool fits = hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || ib + ((size_t)8 << 30) <= mem_free;  // (leave room for the launches' workspaces)
-      if (fits && hipMalloc(&c->batch_img, ib) == hipSuccess) { c->batch_img_bytes = ib; break; }
-      c->batch_img = nullptr;
+      if (fits && dev_alloc(c->batch_img, ib)) break;
       (void)hipGetLastError();
       const uint32_t cap = std::min<uint32_t>(256u, std::max(1u, std::min(d, m)));
       if (nsl >= cap || c->batch_slabs) { c->err = "mfh_prove_batch: no room for a row slab of the CRS image"; return MFH_ENOMEM; }
@@ -1191,9 +1156,9 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     if (rc) return rc;
     ImageGuard slab{c, true};
     for (uint32_t r = 0; r < nsl; r++) {
-      rc = mfh_crs_expand_mm_share(c, d_crs_c8, r, nsl, (uint8_t *)c->batch_img);  // (queued behind the previous slab's launches on the caller's stream)
+      rc = mfh_crs_expand_mm_share(c, d_crs_c8, r, nsl, c->batch_img.as<uint8_t>());  // (queued behind the previous slab's launches on the caller's stream)
       if (rc) return rc;
-      mfh_crs_set_resident_mm_share(c, (const uint8_t *)c->batch_img, r, nsl);
+      mfh_crs_set_resident_mm_share(c, c->batch_img.as<uint8_t>(), r, nsl);
       HIP_TRY(c, hipMemsetAsync(B.SCZ, 0, B.nslots * 2048, c->stream));
       slot = 0;
       const uint32_t loS = (uint32_t)((uint64_t)d * r / nsl);
@@ -1345,17 +1310,13 @@ int mfh_prove_batch_public(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *
   // previous call's chains have been joined into that stream, so none of them still reads the buffer.
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t need = (size_t)nproofs * ub;
-  if (c->pub_bytes < need) {
-    if (c->d_pub) { hipDeviceSynchronize(); hipFree(c->d_pub); c->d_pub = nullptr; c->pub_bytes = 0; }
-    HIP_TRY(c, hipMalloc(&c->d_pub, need));
-    c->pub_bytes = need;
-  }
+  if (int rc = dev_reserve(c, c->d_pub, need, DevWait::device)) return rc;
   uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_pub, need);
   if (!st) return MFH_ENOMEM;
   for (uint32_t b = 0; b < nproofs; b++) memcpy(st + (size_t)b * ub, h_bits + (size_t)b * bits_stride, ub);
-  HIP_TRY(c, hipMemcpyAsync(c->d_pub, st, need, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_pub.p, st, need, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_pub);
-  const PubBatch pb{lu, c->d_pub, ub, lu > kPubDirect ? pubb.data() : nullptr, bstride, lu > kPubDirect ? zero.data() : nullptr};
+  const PubBatch pb{lu, c->d_pub.as<uint8_t>(), ub, lu > kPubDirect ? pubb.data() : nullptr, bstride, lu > kPubDirect ? zero.data() : nullptr};
   return prove_batch_impl(c, d_crs_c8, d_ssp, nproofs, priv.data(), bstride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs, &pb);
 }
 

@@ -116,18 +116,16 @@ __global__ __launch_bounds__(256) void k_interp_sum(const uint4 *__restrict__ sp
 struct SspInterp {
   uint32_t NB = 0;               // sub-tiles of G coefficients: Dp = NB * G >= d
   uint32_t *seeds = nullptr;     // n * NB words
-  void *buf = nullptr;           // per call: nonzeros | parts | splits
-  size_t buf_bytes = 0;
-  void *scratch = nullptr;       // per call: the parts of cut columns
-  size_t scratch_bytes = 0;
+  DevBuf buf;                    // per call: nonzeros | parts | splits
+  DevBuf scratch;                // per call: the parts of cut columns
 };
 
 void ssp_interp_free(mfh_ctx *c) {
   SspInterp *s = c->interp;
   if (!s) return;
   if (s->seeds) hipFree(s->seeds);
-  if (s->buf) hipFree(s->buf);
-  if (s->scratch) hipFree(s->scratch);
+  dev_free(s->buf);
+  dev_free(s->scratch);
   delete s;
   c->interp = nullptr;
 }
@@ -212,14 +210,14 @@ int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, con
   }
   std::copy(parts_h.begin(), parts_h.end(), host.begin() + nz_words);
   std::copy(splits_h.begin(), splits_h.end(), host.begin() + nz_words + parts_h.size());
-  if (int rc = buf_reserve(c, s->buf, s->buf_bytes, std::max<size_t>(bytes, 16))) return rc;
+  if (int rc = work_reserve(c, s->buf, std::max<size_t>(bytes, 16))) return rc;
   if (ncut)
-    if (int rc = buf_reserve(c, s->scratch, s->scratch_bytes, (size_t)ncut * d * 4)) return rc;
+    if (int rc = work_reserve(c, s->scratch, (size_t)ncut * d * 4)) return rc;
 
   c->ssp_frag_src = nullptr;  // derived images of the SSP are stale
-  HIP_TRY(c, hipMemcpyAsync(s->buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
-  const uint2 *d_nz = (const uint2 *)s->buf;
-  const uint4 *d_parts = (const uint4 *)((uint32_t *)s->buf + nz_words), *d_splits = d_parts + nparts;
+  HIP_TRY(c, hipMemcpyAsync(s->buf.p, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  const uint2 *d_nz = s->buf.as<const uint2>();
+  const uint4 *d_parts = (const uint4 *)(s->buf.as<uint32_t>() + nz_words), *d_splits = d_parts + nparts;
   HIP_TRY(c, hipMemcpyAsync(d_ssp, tpad, (size_t)d * 4, hipMemcpyDeviceToDevice, c->stream));  // slot 0 = t
   HIP_TRY(c, hipMemsetAsync(d_ssp + (size_t)(m + 1) * d, 0, (size_t)2 * d * 4, c->stream));  // slots m + 1, m + 2
   {
@@ -227,8 +225,8 @@ int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, con
     const uint32_t wg_per_part = (s->NB + IWG - 1) / IWG;
     const int vec4 = d % 4 == 0 && ((uintptr_t)d_ssp & 15) == 0;
     hipLaunchKernelGGL(k_interp, dim3(nparts * wg_per_part), dim3(IWG), 0, c->stream, d_nz, d_parts, wg_per_part, (const uint32_t *)s->seeds, s->NB, tpad, d,
-                       vec4, d_ssp, (uint32_t *)s->scratch);
-    if (nsplit) hipLaunchKernelGGL(k_interp_sum, dim3((d + 255) / 256, nsplit), dim3(256), 0, c->stream, d_splits, (const uint32_t *)s->scratch, d, d_ssp);
+                       vec4, d_ssp, s->scratch.as<uint32_t>());
+    if (nsplit) hipLaunchKernelGGL(k_interp_sum, dim3((d + 255) / 256, nsplit), dim3(256), 0, c->stream, d_splits, s->scratch.as<const uint32_t>(), d, d_ssp);
   }
   // (host holds the staged rows: the copy must have run before it goes out of scope)
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "mfh_ssp_from_rows: launch failed"; return MFH_EDEVICE; }

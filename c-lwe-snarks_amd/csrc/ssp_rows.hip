@@ -154,12 +154,11 @@ struct SspRows {
   uint32_t *d_rows = nullptr;  // row_ptr (nrows + 1, from 0) | wire (nnz) | coef (nnz)
   uint32_t *d_prefix = nullptr;  // slots [0, lu_max + 2) in the dense layout
   std::vector<uint32_t> h_ptr, h_wire, h_coef;
-  void *ws = nullptr;  // interpolation scratch
-  size_t ws_bytes = 0;
+  DevBuf ws;  // interpolation scratch
   ~SspRows() {
     if (d_rows) hipFree(d_rows);
     if (d_prefix) hipFree(d_prefix);
-    if (ws) hipFree(ws);
+    dev_free(ws);
   }
   const uint32_t *row_ptr() const { return d_rows; }
   const uint32_t *wire() const { return d_rows + nrows + 1; }
@@ -265,8 +264,8 @@ int rows_interp(mfh_ctx *c, SspRows *R, uint32_t ns, const uint8_t *d_bits, uint
   const size_t per = (size_t)8 * Np * 4;
   // (the transforms launch grid.y = 6 ch: at most 65535)
   const uint32_t ch = (uint32_t)std::min<size_t>({(size_t)ns, std::max<size_t>(1, kChunkBytes / per), (size_t)(65535 / 6)});
-  if (int rc = buf_reserve(c, R->ws, R->ws_bytes, ch * per)) return rc;
-  uint32_t *ab = (uint32_t *)R->ws, *cres = ab, *lv[2] = {ab + (size_t)6 * ch * Np, ab + (size_t)7 * ch * Np};
+  if (int rc = work_reserve(c, R->ws, ch * per)) return rc;
+  uint32_t *ab = R->ws.as<uint32_t>(), *cres = ab, *lv[2] = {ab + (size_t)6 * ch * Np, ab + (size_t)7 * ch * Np};
   // (cres reuses the A operands: k_rows_level_mul reads A and B at the same index and writes C there)
   for (uint32_t s0 = 0; s0 < ns; s0 += ch) {
     const uint32_t k = std::min(ch, ns - s0);
@@ -329,9 +328,9 @@ int ssp_rows_witness(mfh_ctx *c, uint32_t nstmt, const uint8_t *h_bits, size_t b
   memcpy(st, h_delta, (size_t)nstmt * 4);
   for (uint32_t b = 0; b < nstmt; b++) memcpy(st + db + (size_t)b * bs, h_bits + (size_t)b * bits_stride, bs);
   if (int rc = wws_reserve(c, db + bb)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->wws, st, db + bb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->wws.p, st, db + bb, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_rows);
-  return rows_interp(c, R, nstmt, (const uint8_t *)c->wws + db, bs, 0, (const uint32_t *)c->wws, d_w, w_stride);
+  return rows_interp(c, R, nstmt, c->wws.as<const uint8_t>() + db, bs, 0, c->wws.as<const uint32_t>(), d_w, w_stride);
 }
 
 // setup messages 2d .. 2d + m - 1 in row mode: beta t(s), beta v_r(s) for r = 1 .. m - 1, from lambda_j(s) (host, O(nnz + d))
