@@ -287,9 +287,11 @@ class CircuitProgram:
 
 class Context:
     """One prover context on one GPU (one process per GPU).  Mirrors the reference's implicit global state:
-    an `rng_t` seeded from the CRS seed (src/snark.c:59,119) plus the parameter macros."""
+    an `rng_t` seeded from the CRS seed (src/snark.c:59,119) plus the parameter macros.
+    own_stream=True keeps the library on the non-blocking stream the context creates for itself (what a C caller gets who never calls mfh_set_stream):
+    nothing then orders its work against torch's streams but sync() and the caller's own waits."""
 
-    def __init__(self, params: Params = DEFAULT, device: int = 0):
+    def __init__(self, params: Params = DEFAULT, device: int = 0, own_stream: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -303,8 +305,9 @@ class Context:
         rc = self.lib.mfh_ctx_create(ctypes.byref(self._h), device, ctypes.byref(cp))
         if rc != 0:
             raise MfhError(f"mfh_ctx_create failed ({rc})")
-        # run on torch's current stream so torch allocations/copies and our kernels are ordered
-        self._chk(self.lib.mfh_set_stream(self._h, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        if not own_stream:
+            # run on torch's current stream so torch allocations/copies and our kernels are ordered
+            self.set_stream(torch.cuda.current_stream(self.device))
 
     def close(self):
         if self._h:
@@ -343,6 +346,21 @@ class Context:
 
     def sync(self):
         self._chk(self.lib.mfh_sync(self._h))
+
+    def set_stream(self, stream):
+        """run the calls that follow on `stream` (mfh_set_stream): a torch.cuda.Stream, or None for HIP's null stream.  The caller waits for the context's
+        work (sync()) before it switches; sample_rows alone may be followed by a switch at once (include/mfhip.h)."""
+        self._chk(self.lib.mfh_set_stream(self._h, ctypes.c_void_p(stream.cuda_stream if stream is not None else 0)))
+
+    def scrub_staging(self):
+        """wait for the copies out of the context's pinned staging (witness bits, deltas, smudging terms) and zero it (mfh_scrub_staging); returns 0"""
+        rc = self.lib.mfh_scrub_staging(self._h)
+        self._chk(rc)
+        return rc
+
+    def workspace_bytes(self):
+        """capacity of the context's main device workspace in bytes (mfh_workspace_bytes): grow-only, in 1 MiB steps"""
+        return int(self.lib.mfh_workspace_bytes(self._h))
 
     def set_timing(self, on=True):
         self._chk(self.lib.mfh_set_timing(self._h, 1 if on else 0))

@@ -57,7 +57,10 @@ typedef struct mfh_ctx mfh_ctx;
 int mfh_ctx_create(mfh_ctx **out, int device, const mfh_params *P);
 void mfh_ctx_destroy(mfh_ctx *ctx);
 /* run on an existing hipStream_t (e.g. torch's current stream).  NULL means HIP's default (null) stream,
- * NOT the context's own stream (a fresh context runs on its own non-blocking stream until this is called). */
+ * NOT the context's own stream (a fresh context runs on its own non-blocking stream until this is called).
+ * Switching rule: the context's scratch, pinned staging and side-stream events are ordered by the stream the previous calls ran on, so the caller
+ * waits for the context's work (mfh_sync, or its own wait on the old stream) BEFORE it switches; calls queued on the new stream otherwise race the
+ * ones still running on the old.  The one exception is mfh_sample_rows, which orders its kept buffer across streams itself: a switch may follow it at once. */
 int mfh_set_stream(mfh_ctx *ctx, void *hip_stream);
 int mfh_sync(mfh_ctx *ctx);
 /* The prover entry points stage what the host contributes -- witness bits, deltas (src/snark.c:140) and the smudging terms u p (src/lwe.c:65-76) -- in pinned host
