@@ -93,7 +93,7 @@ struct mfh_ctx {
   uint32_t mm_rank = 0, mm_world = 1;  // whose row shares the image holds (mfh_crs_set_resident_mm_share)
   uint64_t mm_off[3] = {0, 0, 0}, mm_rows[3] = {0, 0, 0};
   size_t mm_base[3] = {0, 0, 0};
-  DevBuf ssp_frag;  // the dense SSP in MFMA B-fragment order (evalmm.hip: witness pass of the batch prover); built lazily
+  DevBuf ssp_frag;  // the dense SSP in MFMA B-fragment order (witness.hip: witness pass of the batch prover); built lazily
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
   DevBuf circ_io;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements
@@ -132,7 +132,7 @@ struct mfh_ctx {
   // public inputs (mfh_prove_public / mfh_prove_batch_public): the statement bits, ceil(lu / 8) bytes per statement, staged and on the device
   PinBuf pin_pub;
   DevBuf d_pub;
-  // the batch chain's witness staging (one per super-group of a call, evalmm.hip): a ring, so that queueing super-group k + 1 does not wait on the host for
+  // the batch chain's witness staging (one per super-group of a call, witness.hip): a ring, so that queueing super-group k + 1 does not wait on the host for
   // super-group k's copy to have RUN (with one buffer mfh_prove_batch blocked its caller for half of the call's GPU time)
   PinBuf pin_wring[8];
   uint32_t pin_wnext = 0;

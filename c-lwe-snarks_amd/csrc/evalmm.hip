@@ -21,8 +21,8 @@
 //   k_evalmm16<0>    256 digit columns (v_mfma_i32_16x16x64_i8, 2-coordinate column tiles): 31 proofs' vector pairs per expansion
 //   k_evalmm16<1>    expansion only: the rows written to HBM in MFMA A-fragment order (the resident image of the batch prover)
 //   k_mmstream       the same GEMM streamed from that image: no AES, HBM / matrix-core bound
-//   k_witness_mm     the witness pass of up to 128 statements as a GEMM of witness bits x SSP bytes (one read of the SSP)
-//   k_mm_digits / k_evalmm_finish, k_ssp_frag / k_witness_bits / k_witness_mm_finish: operand preparation and epilogues
+//   k_mm_digits / k_evalmm_finish: operand preparation and epilogues
+// (The other GEMM of the batch prover, the witness pass as witness bits x SSP bytes, is witness.hip.)
 //
 // k_evalmm: workgroup = 1024 threads, one column tile of CT = 4 coordinates (352 byte positions = 11 MFMA row tiles) x one row chunk.
 // Per unit of RT = 128 rows: (1) all 16 waves expand the 128 x 368-byte row segments into a row-major LDS tile (23-24 AES blocks
@@ -1095,482 +1095,6 @@ __global__ __launch_bounds__(256) void k_evalmm_finish_groups(const int *__restr
                                   part + lender * part_stride, ND * A.nvec[lender]);
 }
 
-// ---- the witness pass of up to 32 statements as a GEMM over the SSP rows (one read of the SSP) ---------------------------------------
-//   sum_b[k] = sum_i bit_b[i] * v_i[k]:   A = the statements' witness bits (0/1), B = the bytes of v_i[k] (offset by 128), K = rows.
-// The SSP is row-major (v_i[k], k fastest) but the MFMA wants 16 consecutive ROWS per lane, so a second image of the SSP in B-fragment
-// order is built once per SSP (k_ssp_frag, same size as the uint32 SSP): for row step K (32 rows), coefficient tile kt (32
-// coefficients), byte w and lane (k = 32 kt + (l & 31), h = l >> 5): the 16 bytes [byte w of v_{32K+16h+e+1}[k]] ^ 0x80, e = 0..15, at
-// frag[(((kt * KS + K) * 4 + w) * 64 + l) * 16 + e] (KS row steps: a coefficient tile's fragments are contiguous, so a wave reads one
-// sequential stream -- with the row step outermost, 8 KiB pieces 4 MiB apart, the pass ran at 3.75 TB/s).  The pass is then a pure stream: four 16-byte loads and four 32x32x32 MFMAs
-// (M = 32 statements) per wave and row step.
-__global__ void k_ssp_frag(const uint32_t *__restrict__ ssp, uint32_t nrowsel, uint32_t d, uint32_t *__restrict__ frag) {
-  // one thread = 4 rows x 1 coefficient -> one dword of each of the four byte columns
-  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t KT = d / 32;
-  const uint32_t lane = gid & 63, eg = (gid >> 6) & 3;
-  const uint64_t tile = gid >> 8;  // K * KT + kt
-  const uint32_t kt = (uint32_t)(tile % KT), K = (uint32_t)(tile / KT);
-  const uint32_t KSt = (nrowsel + 31) / 32;
-  if (K >= KSt) return;
-  const uint32_t k = kt * 32 + (lane & 31), rb = K * 32 + 16 * (lane >> 5) + 4 * eg;
-  uint32_t x[4];
-#pragma unroll
-  for (int e = 0; e < 4; e++) x[e] = rb + e < nrowsel ? ssp[(uint64_t)(rb + e + 2) * d + k] ^ 0x80808080u : 0u;  // row r = v_{r+1} = slot r + 2
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const uint32_t lo = __builtin_amdgcn_perm(x[1], x[0], 0x0c0c0400u + 0x00000101u * w);  // {x0.bw, x1.bw, 0, 0}
-    const uint32_t hi = __builtin_amdgcn_perm(x[3], x[2], 0x04000c0cu + 0x01010000u * w);  // {0, 0, x2.bw, x3.bw}
-    frag[(((((uint64_t)kt * KSt + K) * 4 + w) * 64 + lane) << 2) + eg] = lo | hi;
-  }
-}
-// The witness kernels work on a RANGE of coefficients [col0, col0 + d) of the polynomials (the whole polynomial: col0 = 0, d = the SSP's
-// d; a rank of the row-sharded batch prover computes its slice of every statement's w: mfh_witness_poly_mm_cols): `d` below is the width
-// of the range (and of the partial arrays), WCols carries where it starts.
-struct WCols {
-  uint32_t kt0;      // col0 / 32: first 32-coefficient tile
-  uint32_t KS;       // row steps of the whole SSP (the fragment image's tile stride)
-  uint64_t wstride;  // coefficients between consecutive statements of the output
-};
-// grid = (d / 128, row chunks); block = 4 waves, one 32-coefficient tile each; MT = 1, 2 or 4 tiles of 32 statements (the SSP is read
-// once per 32 MT statements).  part[((chunk * 4 + w) * 32 MT + stmt) * d + k].
-template <int MT>
-__global__ __launch_bounds__(256) void k_witness_mm(const v4i *__restrict__ sspfrag, const v4i *__restrict__ bitfrag, uint32_t nrowsel /* m - 1 */,
-                                                    uint32_t ksteps_per_chunk, uint32_t d, int *__restrict__ part, WCols wc) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t r32 = lane & 31, h = lane >> 5;
-  const uint32_t ktl = blockIdx.x * 4 + wave, kt = wc.kt0 + ktl;
-  const uint32_t k = ktl * 32 + r32;  // (within the range)
-  const uint32_t K0 = blockIdx.y * ksteps_per_chunk, K1 = min((nrowsel + 31) / 32, K0 + ksteps_per_chunk);
-  v16i acc[MT][4];
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[t][w][e] = 0;
-  if (K0 >= K1) return;  // (uniform)
-  // PF row steps of fragments in flight per wave (MT = 4 holds 256 accumulator registers: one wave per SIMD, so the stream has to be
-  // kept ahead by hand); loads past the chunk re-read its last step
-  constexpr int PF = 3;
-  v4i bq[PF][4], aq[PF][MT];
-  auto fetch = [&](int slot, uint32_t K) {
-    K = min(K, K1 - 1);
-    const v4i *src = sspfrag + (((uint64_t)kt * wc.KS + K) * 4) * 64 + lane;
-#pragma unroll
-    for (int w = 0; w < 4; w++) bq[slot][w] = src[64 * w];
-#pragma unroll
-    for (int t = 0; t < MT; t++) aq[slot][t] = bitfrag[((uint64_t)K * MT + t) * 64 + lane];
-  };
-#pragma unroll
-  for (int i = 0; i < PF; i++) fetch(i, K0 + i);
-  for (uint32_t K = K0; K < K1; K += PF) {
-#pragma unroll
-    for (int i = 0; i < PF; i++) {
-      if (K + i < K1) {
-#pragma unroll
-        for (int t = 0; t < MT; t++)
-#pragma unroll
-          for (int w = 0; w < 4; w++) acc[t][w] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aq[i][t], bq[i][w], acc[t][w], 0, 0, 0);
-        fetch(i, K + i + PF);
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const uint32_t stmt = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
-        part[(((uint64_t)blockIdx.y * 4 + w) * (32 * MT) + stmt) * d + k] = acc[t][w][e];
-      }
-}
-// The same pass over a GENERATOR-DEFINED SSP (csrc/ssp_prg.hpp; BASELINE configs 3/4, where the dense SSP would be 5.9 TB): the B
-// fragments are not loaded but generated -- lane (coefficient k, row half h) hashes its 16 (row, k) pairs (9 integer operations each; the
-// un-reduced 32-bit hash: sums of raw values and sums of coefficients agree mod p) and picks the four byte planes with v_perm -- so that a
-// selected row is generated once per 32 MT statements instead of once per 12 (the VALU form, k_witness_partial_multi_prg): at 2^20
-// constraints the witness pass of a statement drops from 19 ms to about 2.  rowkeys[r] = ssp_prg_rowkey(seed, slot r + 2), padded to a
-// multiple of 32 rows.
-__global__ void k_prg_rowkeys(uint64_t seed, uint32_t nrows_pad, uint32_t *__restrict__ rk) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < nrows_pad) rk[r] = mf::ssp_prg_rowkey(seed, r + 2);
-}
-template <int MT>
-__global__ __launch_bounds__(256) void k_witness_mm_prg(const uint32_t *__restrict__ rowkeys, const v4i *__restrict__ bitfrag, uint32_t nrowsel /* m - 1 */,
-                                                        uint32_t ksteps_per_chunk, uint32_t d, int *__restrict__ part, WCols wc) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t r32 = lane & 31, h = lane >> 5;
-  const uint32_t kt = blockIdx.x * 4 + wave;
-  const uint32_t k = kt * 32 + r32;  // (within the range)
-  const uint32_t K0 = blockIdx.y * ksteps_per_chunk, K1 = min((nrowsel + 31) / 32, K0 + ksteps_per_chunk);
-  v16i acc[MT][4];
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[t][w][e] = 0;
-  if (K0 >= K1) return;  // (uniform)
-  const uint32_t kc = wc.kt0 * 32 + k + 0x632BE5ABu;
-  // the bit fragments and the row keys of a step are loaded two steps ahead (consumed in the step that issues them, the loads cost their
-  // whole latency every step: 0.85 us per step against 0.35 of arithmetic); loads past the chunk re-read its last step
-  constexpr int PF = 2;
-  v4i aqr[PF][MT];
-  uint4 rkr[PF][4];
-  auto fetch = [&](uint32_t K, int slot) {
-    K = min(K, K1 - 1);
-#pragma unroll
-    for (int t = 0; t < MT; t++) aqr[slot][t] = bitfrag[((uint64_t)K * MT + t) * 64 + lane];
-    const uint4 *rk4 = reinterpret_cast<const uint4 *>(rowkeys + 32 * (uint64_t)K + 16 * h);
-#pragma unroll
-    for (int q = 0; q < 4; q++) rkr[slot][q] = rk4[q];
-  };
-  fetch(K0, 0);
-  fetch(K0 + 1, 1);
-  auto step = [&](uint32_t K, int slot) {
-    v4i aq[MT];
-#pragma unroll
-    for (int t = 0; t < MT; t++) aq[t] = aqr[slot][t];
-    uint32_t x[16];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const uint4 r = rkr[slot][q];
-      x[4 * q] = r.x; x[4 * q + 1] = r.y; x[4 * q + 2] = r.z; x[4 * q + 3] = r.w;
-    }
-    fetch(K + PF, slot);
-#pragma unroll
-    for (int e = 0; e < 16; e++) {  // mf::ssp_prg_raw(rowkey, k)
-      uint32_t y = kc * x[e];
-      y ^= y >> 16;
-      y *= 0x7FEB352Du;
-      y ^= y >> 15;
-      y *= 0x846CA68Bu;
-      y ^= y >> 16;
-      x[e] = y;
-    }
-    v4i bq[4];
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t lo = __builtin_amdgcn_perm(x[4 * j + 1], x[4 * j], 0x0c0c0400u + 0x00000101u * w);  // {x0.bw, x1.bw, 0, 0}
-        const uint32_t hi = __builtin_amdgcn_perm(x[4 * j + 3], x[4 * j + 2], 0x04000c0cu + 0x01010000u * w);  // {0, 0, x2.bw, x3.bw}
-        bq[w][j] = (int)((lo | hi) ^ 0x80808080u);
-      }
-#pragma unroll
-    for (int t = 0; t < MT; t++)
-#pragma unroll
-      for (int w = 0; w < 4; w++) acc[t][w] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aq[t], bq[w], acc[t][w], 0, 0, 0);
-  };
-  uint32_t K = K0;
-  for (; K + 2 <= K1; K += 2) {
-    step(K, 0);
-    step(K + 1, 1);
-  }
-  if (K < K1) step(K, 0);
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const uint32_t stmt = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
-        part[(((uint64_t)blockIdx.y * 4 + w) * (32 * MT) + stmt) * d + k] = acc[t][w][e];
-      }
-}
-// 256 statements per generation with TWO waves per SIMD.  The 8 statement tiles x 4 byte planes of a 32-coefficient tile (512 accumulator registers) go to
-// four waves, 4 statement tiles x 2 planes each (128 registers; round 4 -- rounds 2-3 gave a wave all 8 statement tiles of ONE plane: 8 KiB of bit fragments
-// + 1 KiB of coefficient bytes read from LDS per wave and 32-row step, 72 KiB per CU = 576 clk of the LDS pipe against 512 clk of MFMAs per SIMD: the pass was
-// LDS-bound, a build without the MFMAs ran no faster; 4 + 2 KiB per wave are 384 clk).  The four waves SHARE the hashes four ways -- wave j hashes rows
-// 4 j .. 4 j + 3 of a lane's 16 and publishes dword j of all four planes' fragments through LDS (a three-slot ring: the hashes of step K + 2 are issued between
-// the MFMAs of step K, the fragments of step K + 1 are read during step K; the row keys are loaded four steps ahead), wave (sh, pp) reads the fragments of
-// planes 2 pp and 2 pp + 1 with two 16-byte loads and the bit fragments of statement tiles 4 sh .. 4 sh + 3.  4 hashes and 8 MFMAs per wave and step, and
-// with two waves per SIMD one wave's hashes run under the other's MFMAs.
-// Chunk partials only (k_witness_mm_finish).  grid = (d / 64, row chunks), block = 8 waves = 2 coefficient tiles x (2 statement halves x 2 plane pairs).
-__global__ __launch_bounds__(512) void k_witness_mm8q_prg(const uint32_t *__restrict__ rowkeys, const v4i *__restrict__ bitfrag, uint32_t nrowsel /* m - 1 */,
-                                                          uint32_t ksteps_per_chunk, uint32_t d, int *__restrict__ part, WCols wc) {
-  constexpr int MT = 8, RING = 4;
-  __shared__ v4i bits[RING][MT][64];
-  __shared__ uint32_t xch[3][2][4][64][4];  // [step % 3][tile][plane][lane][hashing wave]
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t r32 = lane & 31, h = lane >> 5;
-  const uint32_t tile = wave >> 2, pl = wave & 3;
-  const uint32_t sh = pl >> 1, pp = pl & 1;        // the wave's statement half (tiles 4 sh ..) and plane pair (planes 2 pp, 2 pp + 1)
-  // which 4 of a lane's 16 rows this wave hashes = which dword of the lane's fragments it publishes: rotated by the lane's 16-lane group, so that the 64
-  // lanes of a ds_write_b32 into the [lane][4 dwords] slots hit 64 different banks (with pos = pl for every lane the addresses are 16 bytes apart: 16
-  // distinct banks, every publish a 4-way conflict -- PMC: SQ_LDS_BANK_CONFLICT was 37 % of the LDS cycles of the pass)
-  const uint32_t pos = (pl + (lane >> 4)) & 3;
-  const uint32_t ktl = blockIdx.x * 2 + tile, kt = wc.kt0 + ktl;
-  const uint32_t kc = kt * 32 + r32 + 0x632BE5ABu;
-  const uint32_t K0 = blockIdx.y * ksteps_per_chunk, K1 = min((nrowsel + 31) / 32, K0 + ksteps_per_chunk);
-  v16i acc[4][2];
-#pragma unroll
-  for (int t = 0; t < 4; t++)
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[t][q][e] = 0;
-  if (K0 >= K1) return;  // (uniform)
-  auto bits_load = [&](uint32_t K) -> v4i { return bitfrag[(uint64_t)min(K, K1 - 1) * MT * 64 + tid]; };  // 512 elements per step: one per thread
-  auto bits_store = [&](uint32_t K, v4i st) { (&bits[K % RING][0][0])[tid] = st; };
-  auto rk_load = [&](uint32_t K) -> uint4 { return *reinterpret_cast<const uint4 *>(rowkeys + 32 * (uint64_t)min(K, K1 - 1) + 16 * h + 4 * pos); };
-  auto hash1 = [&](uint32_t rowkey) -> uint32_t {  // mf::ssp_prg_raw(rowkey, k)
-#ifdef WPRG_NOHASH  // timing-only build (wrong results): what the kernel costs without the generator's arithmetic
-    return kc ^ rowkey;
-#endif
-    uint32_t y = kc * rowkey;
-    y ^= y >> 16;
-    y *= 0x7FEB352Du;
-    y ^= y >> 15;
-    y *= 0x846CA68Bu;
-    y ^= y >> 16;
-    return y;
-  };
-  auto publish = [&](uint32_t K, const uint32_t (&x)[4]) {  // dword `pos` of the four planes' fragments of step K
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      const uint32_t lo = __builtin_amdgcn_perm(x[1], x[0], 0x0c0c0400u + 0x00000101u * w);  // {x0.bw, x1.bw, 0, 0}
-      const uint32_t hi = __builtin_amdgcn_perm(x[3], x[2], 0x04000c0cu + 0x01010000u * w);  // {0, 0, x2.bw, x3.bw}
-      xch[K % 3][tile][w][lane][pos] = (lo | hi) ^ 0x80808080u;
-    }
-  };
-  auto fragment = [&](uint32_t K, uint32_t q) -> v4i { return *reinterpret_cast<const v4i *>(&xch[K % 3][tile][2 * pp + q][lane][0]); };
-  uint4 rkr[4];  // the row keys of steps K + 2 .. K + 5
-  v4i sta, stb;  // the bit fragments of steps K + 1 / K + 2 on their way to the ring
-  sta = bits_load(K0);
-  bits_store(K0, sta);
-  sta = bits_load(K0 + 1);
-  stb = bits_load(K0 + 2);
-  {
-    const uint4 r0 = rk_load(K0), r1 = rk_load(K0 + 1);
-    const uint32_t x0[4] = {hash1(r0.x), hash1(r0.y), hash1(r0.z), hash1(r0.w)};
-    const uint32_t x1[4] = {hash1(r1.x), hash1(r1.y), hash1(r1.z), hash1(r1.w)};
-    publish(K0, x0);
-    publish(K0 + 1, x1);
-  }
-#pragma unroll
-  for (int i = 2; i <= 5; i++) rkr[i & 3] = rk_load(K0 + i);
-  __syncthreads();
-  v4i bq0 = fragment(K0, 0), bq1 = fragment(K0, 1);
-  uint32_t K = K0;
-  auto step = [&](int slot, v4i &st) {  // st: the bit fragment of step K + 1 (loaded two steps ago); refilled with that of step K + 3
-    const v4i bn0 = fragment(K + 1, 0), bn1 = fragment(K + 1, 1);  // (published a step ago, before the barrier)
-    const uint4 rk = rkr[(slot + 2) & 3];  // step K + 2
-    const uint32_t hr[4] = {rk.x, rk.y, rk.z, rk.w};
-    uint32_t hx[4];
-    bits_store(K + 1, st);
-    const v4i *aq = &bits[K % RING][4 * sh][lane];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-      const v4i a = aq[t * 64];
-#ifdef WPRG_NOMFMA  // timing-only build (wrong results): the generation, its LDS exchange and the barriers without the matrix cores
-      acc[t][0][0] += a[0] ^ bq0[t];
-      acc[t][1][0] += a[1] ^ bq1[t];
-#else
-      acc[t][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq0, acc[t][0], 0, 0, 0);
-      acc[t][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq1, acc[t][1], 0, 0, 0);
-#endif
-      hx[t] = hash1(hr[t]);
-    }
-    publish(K + 2, hx);  // (slot last read during step K - 2, two barriers ago)
-    rkr[(slot + 2) & 3] = rk_load(K + 6);
-    bq0 = bn0;
-    bq1 = bn1;
-    st = bits_load(K + 3);
-#ifndef WPRG_NOSYNC  // (timing-only build without it: wrong results -- what the step barrier costs)
-    __syncthreads();
-#endif
-    K++;
-  };
-  while (K + 4 <= K1) {  // (K advances inside step)
-    step(0, sta);
-    step(1, stb);
-    step(2, sta);
-    step(3, stb);
-  }
-  if (K < K1) step(0, sta);
-  if (K < K1) step(1, stb);
-  if (K < K1) step(2, sta);
-  uint32_t dd = d;
-  asm volatile("" : "+s"(dd));  // (keeps the store addresses from being computed ahead of the loop)
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    int *dst = part + (((uint64_t)blockIdx.y * 4 + 2 * pp + q) * (32 * MT) + 128 * sh) * dd + ktl * 32 + r32 + (uint64_t)(4 * h) * dd;
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) dst[(uint64_t)((e & 3) + 8 * (e >> 2)) * dd] = acc[t][q][e];
-      dst += (uint64_t)32 * dd;
-    }
-  }
-}
-// 256 statements (a whole super-group of 248) in ONE read of the dense SSP.  8 statement tiles x 4 byte planes are 512 accumulator
-// registers per 32-coefficient tile: the four planes go to four waves (128 registers each, two waves per SIMD; a workgroup = 2
-// coefficient tiles x 4 planes), the eight bit fragments of a row step -- 8 KiB, the same for all eight waves -- go through a four-slot
-// LDS ring (fetched straight from L2 by every wave they made a first version L1-bound: 2.26 ms against 2 x 0.59 for two 124-statement
-// passes) and are read from it a step ahead, under the previous step's MFMAs.  Vector-memory operations complete in issue order, so
-// EVERY load of the loop is consumed exactly PF steps after its issue (the plane's fragment of step K + PF, the bit fragment of step
-// K + 2 + PF, staged in registers and stored to the ring two steps ahead of its use), and the prologue issues its loads in the order
-// the loop does, pinned: s_waitcnt vmcnt(n) is a static count of younger loads and the compiler takes the minimum over the paths into
-// the loop (with the bit fragments staged two steps ahead, or all of them loaded first, it emitted vmcnt(4..9) where the steady state
-// allows 12: the stream was awaited one or two steps after its issue whatever PF).  Timing-only builds split the pass: the stream
-// alone 0.53 ms per 248 statements (5.4 TB/s), MFMAs + LDS alone 0.54, together 0.77 -- with one wave per SIMD (wave pairs, two
-// planes each: the first version) as with two; the chip does not hold its clock under both.
-// part == nullptr (one row chunk, m < 2^16): the four waves exchange their plane sums through LDS, one statement tile per round, and the
-// tile's owner writes w_b[k] = delta_b t[k] + the byte sum mod p (what k_witness_mm_finish does from chunk partials: 0.5 GB written and
-// read back per 248 statements otherwise).  grid = (d / 64, row chunks), block = 8 waves.
-__global__ __launch_bounds__(512) void k_witness_mm8q(const v4i *__restrict__ sspfrag, const v4i *__restrict__ bitfrag, uint32_t nrowsel /* m - 1 */,
-                                                      uint32_t ksteps_per_chunk, uint32_t d, int *__restrict__ part, const uint32_t *__restrict__ tpoly /* + col0 */,
-                                                      const uint32_t *__restrict__ cnt_delta, uint32_t nstmt, uint32_t *__restrict__ w_out, WCols wc) {
-  constexpr int MT = 8, RING = 4, PF = 4;
-  __shared__ v4i bits[RING][MT][64];      // 32 KiB
-  __shared__ uint32_t xch[2][3][16][64];  // the epilogue's exchange: [coefficient tile][sending wave (owner skipped)][e][lane], 24 KiB
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t r32 = lane & 31, h = lane >> 5;
-  const uint32_t tile = wave >> 2, pl = wave & 3;
-  const uint32_t ktl = blockIdx.x * 2 + tile, kt = wc.kt0 + ktl;
-  const uint32_t K0 = blockIdx.y * ksteps_per_chunk, K1 = min((nrowsel + 31) / 32, K0 + ksteps_per_chunk);
-  v16i acc[MT];
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[t][e] = 0;
-  if (K0 >= K1) return;  // (uniform)
-  auto bits_load = [&](uint32_t K) -> v4i { return bitfrag[(uint64_t)min(K, K1 - 1) * MT * 64 + tid]; };  // 512 elements per step: one per thread
-  auto bits_store = [&](uint32_t K, v4i st) { (&bits[K % RING][0][0])[tid] = st; };
-  auto ssp_load = [&](uint32_t K) -> v4i { return sspfrag[(((uint64_t)kt * wc.KS + min(K, K1 - 1)) * 4 + pl) * 64 + lane]; };
-  v4i stg[PF], bq[PF];
-  {
-    const v4i s0 = bits_load(K0), s1 = bits_load(K0 + 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < PF; i++) {  // (in the order the loop issues them)
-      bq[i] = ssp_load(K0 + i);
-      stg[i] = bits_load(K0 + 2 + i);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    bits_store(K0, s0);
-    bits_store(K0 + 1, s1);
-  }
-  __syncthreads();
-  v4i acur[MT];
-#pragma unroll
-  for (int t = 0; t < MT; t++) acur[t] = bits[K0 % RING][t][lane];
-  uint32_t K = K0;
-  auto step = [&](int slot) {
-    bits_store(K + 2, stg[slot]);
-    v4i anext[MT];
-    const v4i *aq = &bits[(K + 1) % RING][0][lane];
-#pragma unroll
-    for (int t = 0; t < MT; t++) anext[t] = aq[t * 64];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int t = 0; t < MT; t++) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(acur[t], bq[slot], acc[t], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    bq[slot] = ssp_load(K + PF);
-    stg[slot] = bits_load(K + 2 + PF);
-#pragma unroll
-    for (int t = 0; t < MT; t++) acur[t] = anext[t];
-    __syncthreads();
-    K++;
-  };
-  while (K + PF <= K1) {  // (K advances inside step)
-#pragma unroll
-    for (int i = 0; i < PF; i++) step(i);
-  }
-#pragma unroll
-  for (int i = 0; i + 1 < PF; i++)
-    if (K < K1) step(i);
-  uint32_t dd = d;
-  asm volatile("" : "+s"(dd));  // (keeps the store addresses from being computed ahead of the loop)
-  if (part) {
-    int *dst = part + ((uint64_t)blockIdx.y * 4 + pl) * (32 * MT) * dd + ktl * 32 + r32 + (uint64_t)(4 * h) * dd;
-#pragma unroll
-    for (int t = 0; t < MT; t++) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) dst[(uint64_t)((e & 3) + 8 * (e >> 2)) * dd] = acc[t][e];
-      dst += (uint64_t)32 * dd;
-    }
-    return;
-  }
-  // statement tile t is finished by wave t >> 1 of the coefficient tile: the other three hand over their plane sums (acc + 128 cnt_b:
-  // the true byte sum, < 2^24 for m < 2^16), one statement tile per round
-  asm volatile("" : "+s"(cnt_delta), "+s"(tpoly));
-  const uint32_t k = ktl * 32 + r32;
-  const uint64_t tk = tpoly[k], ws = wc.wstride, P = MFH_P;
-#pragma unroll
-  for (int t = 0; t < MT; t++) {
-    const uint32_t owner = t >> 1;
-    uint32_t mine[16];
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const uint32_t b = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
-      mine[e] = (uint32_t)acc[t][e] + (b < nstmt ? 128u * cnt_delta[2 * b] : 0u);
-    }
-    if (pl != owner) {  // (wave-uniform)
-      const uint32_t sidx = pl - (pl > owner);
-#pragma unroll
-      for (int e = 0; e < 16; e++) xch[tile][sidx][e][lane] = mine[e];
-    }
-    __syncthreads();
-    if (pl == owner) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const uint32_t b = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (b < nstmt) {
-          uint64_t val = (uint64_t)mine[e] << (8 * owner);
-#pragma unroll
-          for (int o = 0; o < 4; o++)
-            if (o != (int)owner) val += (uint64_t)xch[tile][o - (o > (int)owner)][e][lane] << (8 * o);
-          w_out[(uint64_t)b * ws + k] = (uint32_t)((val % P + tk * cnt_delta[2 * b + 1] % P) % P);
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-// bits of nstmt statements (packed, bits_stride bytes apart) -> A fragments: bitfrag[K][t][lane (stmt = 32 t + (l & 31), h)][e] = bit
-// (32 K + 16 h + e) of that statement
-// (one thread per lane's 16 bytes: two bytes of the statement's bit string in, one 16-byte store out)
-__global__ void k_witness_bits(const uint8_t *__restrict__ bits, size_t bits_stride, uint32_t nstmt, uint32_t nrowsel, uint32_t ksteps, uint32_t MT,
-                               int8_t *__restrict__ bitfrag) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // one lane of one fragment: 16 output bytes
-  if (i >= ksteps * MT * 64) return;
-  const uint32_t lane = i & 63, t = (i >> 6) % MT, K = (i >> 6) / MT, stmt = 32 * t + (lane & 31), h = lane >> 5;
-  const uint32_t r0 = K * 32 + 16 * h;  // rows r0 .. r0 + 15: bits of two consecutive bytes (r0 is a multiple of 16)
-  uint32_t w = 0;
-  if (stmt < nstmt && r0 < nrowsel) {
-    const uint8_t *b = bits + (size_t)stmt * bits_stride + (r0 >> 3);
-    w = b[0];
-    if (r0 + 8 < nrowsel) w |= (uint32_t)b[1] << 8;
-    if (nrowsel - r0 < 16) w &= (1u << (nrowsel - r0)) - 1;  // rows beyond the last selected one contribute nothing
-  }
-  uint32_t o[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const uint32_t n4 = (w >> (4 * q)) & 15;  // four bits -> four bytes of 0 / 1
-    o[q] = (n4 & 1) | ((n4 & 2) << 7) | ((n4 & 4) << 14) | ((n4 & 8) << 21);
-  }
-  reinterpret_cast<uint4 *>(bitfrag)[i] = uint4{o[0], o[1], o[2], o[3]};
-}
-// w_b[k] = delta_b t[k] + sum_i bit_b[i] v_i[k] mod p from the chunk partials: sum_w 256^w (G'_w + 128 cnt_b)
-__global__ void k_witness_mm_finish(const int *__restrict__ part, uint32_t nchunks, const uint32_t *__restrict__ t, const uint32_t *__restrict__ cnt_delta,
-                                    uint32_t nstmt, uint32_t mrows /* 32 MT */, uint32_t d, uint32_t *__restrict__ w_out, uint64_t wstride) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (k >= d || b >= nstmt) return;
-  const uint64_t corr = 128ull * cnt_delta[2 * b];
-  const uint32_t delta = cnt_delta[2 * b + 1];
-  uint64_t val = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    int64_t g = 0;
-    for (uint32_t ch = 0; ch < nchunks; ch++) g += part[(((uint64_t)ch * 4 + w) * mrows + b) * d + k];
-    val += (uint64_t)(g + (int64_t)corr) << (8 * w);  // the true byte sum: >= 0
-  }
-  const uint64_t P = MFH_P;
-  w_out[(uint64_t)b * wstride + k] = (uint32_t)((val % P + (uint64_t)t[k] * delta % P) % P);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1976,108 +1500,5 @@ int mfh_crs_set_resident_mm_share(mfh_ctx *c, const uint8_t *d_image, uint32_t r
   return MFH_OK;
 }
 int mfh_crs_set_resident_mm(mfh_ctx *c, const uint8_t *d_image) { return mfh_crs_set_resident_mm_share(c, d_image, 0, 1); }
-
-// mfh_witness_poly for up to 256 statements in ONE read (dense SSP) or one generation (generator-defined SSP) of the selected rows, on the
-// matrix cores, restricted to the coefficients [col0, col0 + ncols): d_w[b * w_stride + (k - col0)]
-int mfh_witness_poly_mm_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
-                             uint32_t col0, uint32_t ncols, uint32_t *d_w, size_t w_stride) {
-  if (!c || !h_bits || !h_delta || !d_w || nstmt == 0 || nstmt > 256) return MFH_EINVAL;
-  mf::SspSrc src;  // d_ssp == NULL: the registered generator-defined SSP (B fragments generated in the kernel)
-  {
-    int rc0 = ssp_src(c, d_ssp, src);
-    if (rc0) return rc0;
-  }
-  const uint32_t MT = nstmt > 128 ? 8 : nstmt > 64 ? 4 : nstmt > 32 ? 2 : 1;
-  const uint32_t d = c->P.d, m = c->P.m;
-  if (d % 128 || m < 2) { c->err = "mfh_witness_poly_mm: d must be a multiple of 128"; return MFH_EUNSUPPORTED; }
-  if ((uint64_t)col0 + ncols > d || w_stride < ncols) return MFH_EINVAL;
-  if (ncols == 0) return MFH_OK;
-  if (col0 % 128 || ncols % 128) { c->err = "mfh_witness_poly_mm_cols: the coefficient range must start and end at multiples of 128"; return MFH_EUNSUPPORTED; }
-  const uint32_t nc = ncols;
-  const WCols wc = {col0 / 32, (m - 1 + 31) / 32, (uint64_t)w_stride};
-  const uint32_t *tpoly = src.t + col0;
-  for (uint32_t b = 0; b < nstmt; b++)
-    if (h_delta[b] >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t nrowsel = m - 1, ksteps = (nrowsel + 31) / 32;
-  // (the 256-statement pass has d / 64 workgroups of one wave per SIMD: one row chunk fills the chip at d >= 2^14, and with one chunk --
-  // and byte sums that fit 32 bits per plane pair -- it finishes in the kernel)
-  const bool fused = MT == 8 && src.dense && m < 65536 && (nc >= 16384 || ksteps <= 64);  // (small instances: nothing to fill either way)
-  const uint32_t nchunks = fused ? 1u : std::min(ksteps, 4u), kpc = (ksteps + nchunks - 1) / nchunks;
-  // the SSP in B-fragment order: built on first use per SSP (mfh_ssp_prepare invalidates it), kept beside the uint32 image
-  const size_t sfrag_b = (size_t)ksteps * 32 * d * 4;
-  if (src.dense && (c->ssp_frag_src != d_ssp || c->ssp_frag.cap < sfrag_b)) {
-    if (int rc0 = dev_reserve(c, c->ssp_frag, sfrag_b)) return rc0;
-    const uint64_t nthreads = (uint64_t)ksteps * (d / 32) * 256;
-    hipLaunchKernelGGL(k_ssp_frag, dim3((uint32_t)((nthreads + 255) / 256)), dim3(256), 0, c->stream, d_ssp, nrowsel, d, c->ssp_frag.as<uint32_t>());
-    HIP_TRY(c, hipGetLastError());
-    c->ssp_frag_src = d_ssp;
-  }
-  const size_t packed = (size_t)nstmt * bits_stride, head_b = ((packed + 8 + 256 * 8 + 255) & ~(size_t)255);
-  const size_t frag_b = (size_t)ksteps * MT * 1024, part_b = (size_t)nchunks * 4 * 32 * MT * nc * 4;
-  const size_t rk_b = src.dense ? 0 : (((size_t)ksteps * 32 * 4 + 255) & ~(size_t)255);
-  int rc = wws_reserve(c, head_b + frag_b + part_b + rk_b);
-  if (rc) return rc;
-  // staged: packed bits, then (count of selected rows, delta) per statement
-  PinBuf &wpin = c->pin_wring[c->pin_wnext++ % 8];
-  uint8_t *stage = (uint8_t *)pin_acquire(c, wpin, head_b);
-  if (!stage) return MFH_ENOMEM;
-  memcpy(stage, h_bits, packed);
-  uint32_t *cd = (uint32_t *)(stage + packed + ((8 - packed % 8) % 8));
-  for (uint32_t b = 0; b < nstmt; b++) {
-    uint32_t cnt = 0;
-    const uint8_t *hb = h_bits + (size_t)b * bits_stride;
-    for (uint32_t r = 0; r + 8 <= nrowsel; r += 8) cnt += (uint32_t)__builtin_popcount(hb[r >> 3]);
-    for (uint32_t r = nrowsel & ~7u; r < nrowsel; r++) cnt += (hb[r >> 3] >> (r & 7)) & 1;
-    cd[2 * b] = cnt;
-    cd[2 * b + 1] = h_delta[b];
-  }
-  uint8_t *dev = c->wws.as<uint8_t>();
-  HIP_TRY(c, hipMemcpyAsync(dev, stage, head_b, hipMemcpyHostToDevice, c->stream));
-  pin_release(c, wpin);
-  const uint32_t *d_cd = (const uint32_t *)(dev + packed + ((8 - packed % 8) % 8));
-  int8_t *d_frag = (int8_t *)(dev + head_b);
-  int *d_part = (int *)(dev + head_b + frag_b);
-  hipLaunchKernelGGL(k_witness_bits, dim3((uint32_t)((frag_b / 16 + 255) / 256)), dim3(256), 0, c->stream, dev, bits_stride, nstmt, nrowsel, ksteps, MT, d_frag);
-  if (!src.dense) {
-    uint32_t *d_rk = (uint32_t *)(dev + head_b + frag_b + part_b);
-    const dim3 grid(nc / 128, (ksteps + kpc - 1) / kpc);
-    hipLaunchKernelGGL(k_prg_rowkeys, dim3((ksteps * 32 + 255) / 256), dim3(256), 0, c->stream, src.seed, ksteps * 32, d_rk);
-    if (MT == 8)
-      hipLaunchKernelGGL(k_witness_mm8q_prg, dim3(nc / 64, (ksteps + kpc - 1) / kpc), dim3(512), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
-    else if (MT == 1) hipLaunchKernelGGL(k_witness_mm_prg<1>, grid, dim3(256), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
-    else if (MT == 2) hipLaunchKernelGGL(k_witness_mm_prg<2>, grid, dim3(256), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
-    else hipLaunchKernelGGL(k_witness_mm_prg<4>, grid, dim3(256), 0, c->stream, d_rk, (const v4i *)d_frag, nrowsel, kpc, nc, d_part, wc);
-  } else if (MT == 8) {
-    hipLaunchKernelGGL(k_witness_mm8q, dim3(nc / 64, (ksteps + kpc - 1) / kpc), dim3(512), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag, nrowsel, kpc, nc,
-                       fused ? (int *)nullptr : d_part, tpoly, d_cd, nstmt, d_w, wc);
-    if (fused) {
-      HIP_TRY(c, hipGetLastError());
-      return MFH_OK;
-    }
-  } else if (MT == 1)
-    hipLaunchKernelGGL(k_witness_mm<1>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
-                       nrowsel, kpc, nc, d_part, wc);
-  else if (MT == 2)
-    hipLaunchKernelGGL(k_witness_mm<2>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
-                       nrowsel, kpc, nc, d_part, wc);
-  else
-    hipLaunchKernelGGL(k_witness_mm<4>, dim3(nc / 128, (ksteps + kpc - 1) / kpc), dim3(256), 0, c->stream, c->ssp_frag.as<const v4i>(), (const v4i *)d_frag,
-                       nrowsel, kpc, nc, d_part, wc);
-  hipLaunchKernelGGL(k_witness_mm_finish, dim3((nc + 255) / 256, nstmt), dim3(256), 0, c->stream, d_part, (ksteps + kpc - 1) / kpc, tpoly, d_cd, nstmt, 32 * MT,
-                     nc, d_w, (uint64_t)w_stride);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-int mfh_witness_poly_mm(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
-                        uint32_t *d_w) {
-  if (!c) return MFH_EINVAL;
-  if (ssp_is_rows(c, d_ssp)) {  // the row SSP: one interpolation per statement (ssp_rows.hip)
-    if (!h_bits || !h_delta || !d_w || nstmt == 0 || nstmt > 256) return MFH_EINVAL;
-    return ssp_rows_witness(c, nstmt, h_bits, bits_stride, h_delta, d_w, c->P.d);
-  }
-  return mfh_witness_poly_mm_cols(c, d_ssp, nstmt, h_bits, bits_stride, h_delta, 0, c->P.d, d_w, c->P.d);
-}
 
 }  // extern "C"

@@ -938,137 +938,11 @@ __global__ void k_smudge(uint64_t *cts, uint32_t n, const uint32_t *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------------
-// SSP: layout conversion and the witness polynomial (src/ssp.c:28-34, src/snark.c:141,147-155)
+// SSP: layout conversion (src/ssp.c:28-34; the witness polynomial is witness.hip)
 // ------------------------------------------------------------------------------------------------------
 __global__ void k_ssp_reduce(const uint64_t *__restrict__ in, uint32_t *__restrict__ out, uint64_t ncoef) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ncoef; i += (uint64_t)gridDim.x * blockDim.x)
     out[i] = (uint32_t)(in[i] % MFH_P);
-}
-
-// partial[g][k] = sum over the g-th share of selected rows of v_row[k]   (uint64, no reduction needed: < 2^32 * rows)
-__global__ __launch_bounds__(256) void k_witness_partial(const uint32_t *__restrict__ ssp, const uint32_t *__restrict__ rows, uint32_t nsel,
-                                                         uint32_t d, uint64_t *__restrict__ partial) {
-  const uint32_t k4 = blockIdx.x * blockDim.x + threadIdx.x;  // group of 4 coefficients
-  if (k4 * 4 >= d) return;
-  const uint32_t G = gridDim.y, g = blockIdx.y;
-  uint64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  for (uint32_t i = g; i < nsel; i += G) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(ssp + (uint64_t)rows[i] * d + (uint64_t)k4 * 4);
-    s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
-  }
-  uint64_t *o = partial + (uint64_t)g * d + (uint64_t)k4 * 4;
-  o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
-}
-
-// the same partial sums with generator-defined rows: every thread makes 4 consecutive coefficients of each selected row
-__global__ __launch_bounds__(256) void k_witness_partial_prg(uint64_t seed, const uint32_t *__restrict__ rows, uint32_t nsel, uint32_t d,
-                                                             uint64_t *__restrict__ partial) {
-  const uint32_t k4 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k4 * 4 >= d) return;
-  const uint32_t G = gridDim.y, g = blockIdx.y;
-  const uint32_t k = k4 * 4;
-  uint64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  for (uint32_t i = g; i < nsel; i += G) {
-    const uint32_t rk = mf::ssp_prg_rowkey(seed, rows[i]);
-    s0 += mf::ssp_prg_raw(rk, k);  // raw values: congruent to the coefficients mod p, the sums are reduced by the finish kernels
-    s1 += mf::ssp_prg_raw(rk, k + 1);
-    s2 += mf::ssp_prg_raw(rk, k + 2);
-    s3 += mf::ssp_prg_raw(rk, k + 3);
-  }
-  uint64_t *o = partial + (uint64_t)g * d + k;
-  o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
-}
-// The witness pass for NB statements at once: every selected SSP row is read ONCE and added into the accumulators of the statements
-// whose bit selects it.  list[i] = {slot, mask}: bit b of mask = statement b selects the row (uniform per row: scalar branches).
-// partial[(b * G + g) * d + k]: the per-statement layout k_witness_finish reads.
-template <int NB>
-__global__ __launch_bounds__(256) void k_witness_partial_multi(const uint32_t *__restrict__ ssp, const uint2 *__restrict__ list, uint32_t nsel,
-                                                               uint32_t d, uint64_t *__restrict__ partial) {
-  const uint32_t k4 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k4 * 4 >= d) return;
-  const uint32_t G = gridDim.y, g = blockIdx.y;
-  uint64_t acc[NB][4];
-#pragma unroll
-  for (int b = 0; b < NB; b++) acc[b][0] = acc[b][1] = acc[b][2] = acc[b][3] = 0;
-  auto add = [&](const uint4 &v, uint32_t mask) {
-#pragma unroll
-    for (int b = 0; b < NB; b++)
-      if ((mask >> b) & 1) { acc[b][0] += v.x; acc[b][1] += v.y; acc[b][2] += v.z; acc[b][3] += v.w; }
-  };
-  const uint32_t *col = ssp + (uint64_t)k4 * 4;
-  uint32_t i = g;
-  for (; i + 3 * G < nsel; i += 4 * G) {  // four rows in flight
-    const uint2 e0 = list[i], e1 = list[i + G], e2 = list[i + 2 * G], e3 = list[i + 3 * G];
-    const uint4 v0 = *reinterpret_cast<const uint4 *>(col + (uint64_t)e0.x * d), v1 = *reinterpret_cast<const uint4 *>(col + (uint64_t)e1.x * d);
-    const uint4 v2 = *reinterpret_cast<const uint4 *>(col + (uint64_t)e2.x * d), v3 = *reinterpret_cast<const uint4 *>(col + (uint64_t)e3.x * d);
-    add(v0, e0.y); add(v1, e1.y); add(v2, e2.y); add(v3, e3.y);
-  }
-  for (; i < nsel; i += G) {
-    const uint2 e = list[i];
-    add(*reinterpret_cast<const uint4 *>(col + (uint64_t)e.x * d), e.y);
-  }
-#pragma unroll
-  for (int b = 0; b < NB; b++) {
-    uint64_t *o = partial + ((uint64_t)b * G + g) * d + (uint64_t)k4 * 4;
-    o[0] = acc[b][0]; o[1] = acc[b][1]; o[2] = acc[b][2]; o[3] = acc[b][3];
-  }
-}
-// the same with generator-defined rows (csrc/ssp_prg.hpp): every selected row is GENERATED once per NB statements
-template <int NB>
-__global__ __launch_bounds__(256) void k_witness_partial_multi_prg(uint64_t seed, const uint2 *__restrict__ list, uint32_t nsel, uint32_t d,
-                                                                   uint64_t *__restrict__ partial) {
-  const uint32_t k4 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k4 * 4 >= d) return;
-  const uint32_t G = gridDim.y, g = blockIdx.y, k = k4 * 4;
-  uint64_t acc[NB][4];
-#pragma unroll
-  for (int b = 0; b < NB; b++) acc[b][0] = acc[b][1] = acc[b][2] = acc[b][3] = 0;
-  for (uint32_t i = g; i < nsel; i += G) {
-    const uint2 e = list[i];
-    const uint32_t rk = mf::ssp_prg_rowkey(seed, e.x);
-    const uint32_t v0 = mf::ssp_prg_raw(rk, k), v1 = mf::ssp_prg_raw(rk, k + 1), v2 = mf::ssp_prg_raw(rk, k + 2), v3 = mf::ssp_prg_raw(rk, k + 3);
-#pragma unroll
-    for (int b = 0; b < NB; b++)
-      if ((e.y >> b) & 1) { acc[b][0] += v0; acc[b][1] += v1; acc[b][2] += v2; acc[b][3] += v3; }
-  }
-#pragma unroll
-  for (int b = 0; b < NB; b++) {
-    uint64_t *o = partial + ((uint64_t)b * G + g) * d + k;
-    o[0] = acc[b][0]; o[1] = acc[b][1]; o[2] = acc[b][2]; o[3] = acc[b][3];
-  }
-}
-// materialise generator-defined slots [first, first+nslots) as a dense uint32 image (tests; small instances)
-__global__ void k_ssp_prg_fill(uint64_t seed, uint32_t first_slot, uint32_t d, uint64_t total, uint32_t *__restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t slot = first_slot + (uint32_t)(i / d), k = (uint32_t)(i % d);
-    out[i] = mf::ssp_prg_coeff(mf::ssp_prg_rowkey(seed, slot), k);
-  }
-}
-// t = v_0 + (summed selected rows) - 1: random_ssp's definition (src/ssp.c:59-71), for a generator-defined SSP
-__global__ void k_ssp_prg_make_t(uint64_t seed, const uint64_t *__restrict__ partial, uint32_t G, uint32_t d, uint32_t *__restrict__ t) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= d) return;
-  uint64_t s = mf::ssp_prg_coeff(mf::ssp_prg_rowkey(seed, 1), k);  // v_0 = slot 1
-  for (uint32_t g = 0; g < G; g++) s = (s + partial[(uint64_t)g * d + k] % MFH_P) % MFH_P;
-  if (k == 0) s = (s + MFH_P - 1) % MFH_P;
-  t[k] = (uint32_t)s;
-}
-
-__global__ void k_witness_finish(const uint32_t *__restrict__ ssp, const uint64_t *__restrict__ partial, uint32_t G, uint32_t d, uint32_t delta,
-                                 uint32_t *__restrict__ w) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= d) return;
-  uint64_t s = ((uint64_t)ssp[k] * delta) % MFH_P;  // slot 0 = t
-  for (uint32_t g = 0; g < G; g++) s = (s + partial[(uint64_t)g * d + k] % MFH_P) % MFH_P;
-  w[k] = (uint32_t)s;
-}
-
-__global__ void k_witness_lanes(const uint64_t *__restrict__ partial, uint32_t G, uint32_t d, uint64_t *__restrict__ lanes) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= d) return;
-  uint64_t s = 0;
-  for (uint32_t g = 0; g < G; g++) s = (s + partial[(uint64_t)g * d + k] % MFH_P) % MFH_P;
-  lanes[k] = s;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1906,161 +1780,6 @@ int mfh_ssp_upload(mfh_ctx *c, const void *h_ssp_u64, uint32_t *d_ssp, size_t fi
   for (int t = 1; t <= started; t++) th[t].join();
   for (int t = 0; t < NT; t++)
     if (failed[t] || hipGetLastError() != hipSuccess) { c->err = "ssp upload failed"; return MFH_EDEVICE; }
-  return MFH_OK;
-}
-
-// shared body: partial[g][k] sums over this rank's share of the selected SSP rows
-static int witness_partials(mfh_ctx *c, const mf::SspSrc &src, const uint8_t *h_bits, uint32_t rank, uint32_t world, uint32_t *G_out,
-                            uint64_t **partial_out) {
-  const uint32_t d = c->P.d, m = c->P.m;
-  if (d % 4) { c->err = "d must be a multiple of 4"; return MFH_EINVAL; }
-  uint32_t *rows = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)m * 4 + 4);
-  if (!rows) return MFH_ENOMEM;
-  uint32_t nall = 0;
-  for (uint32_t i = 1; i < m; i++)
-    if ((h_bits[(i - 1) >> 3] >> ((i - 1) & 7)) & 1) rows[nall++] = i + 1;  // slot of v_i
-  // contiguous share of the selected rows
-  const uint32_t lo = (uint32_t)((uint64_t)nall * rank / world), hi = (uint32_t)((uint64_t)nall * (rank + 1) / world);
-  const uint32_t nsel = hi - lo;
-  const uint32_t G = std::max(1u, std::min(64u, nsel / 8 + 1));
-  const size_t rows_b = ((size_t)m * 4 + 255) & ~(size_t)255;
-  int rc = wws_reserve(c, rows_b + (size_t)G * d * 8);
-  if (rc) return rc;
-  uint32_t *d_rows = c->wws.as<uint32_t>();
-  uint64_t *partial = (uint64_t *)(c->wws.as<uint8_t>() + rows_b);
-  if (nsel) HIP_TRY(c, hipMemcpyAsync(d_rows, rows + lo, (size_t)nsel * 4, hipMemcpyHostToDevice, c->stream));
-  pin_release(c, c->pin_rows);
-  if (src.dense)
-    hipLaunchKernelGGL(k_witness_partial, dim3((d / 4 + 255) / 256, G), dim3(256), 0, c->stream, src.dense, d_rows, nsel, d, partial);
-  else
-    hipLaunchKernelGGL(k_witness_partial_prg, dim3((d / 4 + 255) / 256, G), dim3(256), 0, c->stream, src.seed, d_rows, nsel, d, partial);
-  HIP_TRY(c, hipGetLastError());
-  *G_out = G;
-  *partial_out = partial;
-  return MFH_OK;
-}
-
-int mfh_ssp_set_prg(mfh_ctx *c, uint64_t seed, const uint32_t *d_t) {
-  if (!c) return MFH_EINVAL;
-  if (d_t) ssp_rows_free(c, false);  // registering one kind replaces the other
-  c->prg_on = d_t != nullptr;
-  c->prg_seed = seed;
-  c->prg_t = d_t;
-  return MFH_OK;
-}
-
-int mfh_ssp_prg_fill(mfh_ctx *c, uint64_t seed, size_t first_slot, size_t nslots, uint32_t *d_out) {
-  if (!c || !d_out) return MFH_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t total = (uint64_t)nslots * c->P.d;
-  if (!total) return MFH_OK;
-  hipLaunchKernelGGL(k_ssp_prg_fill, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096)), dim3(256), 0, c->stream, seed, (uint32_t)first_slot,
-                     c->P.d, total, d_out);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-int mfh_ssp_prg_make_t(mfh_ctx *c, uint64_t seed, const uint8_t *h_bits, uint32_t *d_t) {
-  if (!c || !h_bits || !d_t) return MFH_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  mf::SspSrc src{nullptr, d_t, seed};
-  uint32_t G;
-  uint64_t *partial;
-  int rc = witness_partials(c, src, h_bits, 0, 1, &G, &partial);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ssp_prg_make_t, dim3((c->P.d + 255) / 256), dim3(256), 0, c->stream, seed, partial, G, c->P.d, d_t);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-int mfh_witness_poly(mfh_ctx *c, const uint32_t *d_ssp, const uint8_t *h_bits, uint32_t delta, uint32_t *d_w) {
-  if (!c || !h_bits || !d_w) return MFH_EINVAL;
-  if (delta >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (ssp_is_rows(c, d_ssp)) return ssp_rows_witness(c, 1, h_bits, (c->P.m + 6) / 8, &delta, d_w, c->P.d);
-  mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
-  if (rc) return rc;
-  uint32_t G;
-  uint64_t *partial;
-  rc = witness_partials(c, src, h_bits, 0, 1, &G, &partial);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_witness_finish, dim3((c->P.d + 255) / 256), dim3(256), 0, c->stream, src.t, partial, G, c->P.d, delta, d_w);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-// mfh_witness_poly for up to 12 statements in one pass over the SSP (d_ssp == NULL: the rows are generated once per pass): d_w = nstmt
-// polynomials of d coefficients
-int mfh_witness_poly_multi(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
-                           uint32_t *d_w) {
-  constexpr int NB = 12;
-  if (!c || !h_bits || !h_delta || !d_w || nstmt == 0 || nstmt > NB) return MFH_EINVAL;
-  if (ssp_is_rows(c, d_ssp)) return ssp_rows_witness(c, nstmt, h_bits, bits_stride, h_delta, d_w, c->P.d);
-  mf::SspSrc src;  // d_ssp == NULL: the registered generator-defined SSP
-  {
-    int rc0 = ssp_src(c, d_ssp, src);
-    if (rc0) return rc0;
-  }
-  const uint32_t d = c->P.d, m = c->P.m;
-  if (d % 4) { c->err = "d must be a multiple of 4"; return MFH_EINVAL; }
-  for (uint32_t b = 0; b < nstmt; b++)
-    if (h_delta[b] >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  uint2 *list = (uint2 *)pin_acquire(c, c->pin_rows, (size_t)m * 8 + 8);
-  if (!list) return MFH_ENOMEM;
-  uint32_t nsel = 0;
-  for (uint32_t i = 1; i < m; i++) {
-    uint32_t mask = 0;
-    for (uint32_t b = 0; b < nstmt; b++) mask |= (uint32_t)((h_bits[b * bits_stride + ((i - 1) >> 3)] >> ((i - 1) & 7)) & 1) << b;
-    if (mask) list[nsel++] = make_uint2(i + 1, mask);  // slot of v_i
-  }
-  const uint32_t G = std::max(1u, std::min(16u, nsel / 8 + 1));
-  const size_t list_b = ((size_t)m * 8 + 255) & ~(size_t)255;
-  int rc = wws_reserve(c, list_b + (size_t)NB * G * d * 8);
-  if (rc) return rc;
-  uint2 *d_list = c->wws.as<uint2>();
-  uint64_t *partial = (uint64_t *)(c->wws.as<uint8_t>() + list_b);
-  if (nsel) HIP_TRY(c, hipMemcpyAsync(d_list, list, (size_t)nsel * 8, hipMemcpyHostToDevice, c->stream));
-  pin_release(c, c->pin_rows);
-  if (src.dense)
-    hipLaunchKernelGGL(k_witness_partial_multi<NB>, dim3((d / 4 + 255) / 256, G), dim3(256), 0, c->stream, src.dense, d_list, nsel, d, partial);
-  else
-    hipLaunchKernelGGL(k_witness_partial_multi_prg<NB>, dim3((d / 4 + 255) / 256, G), dim3(256), 0, c->stream, src.seed, d_list, nsel, d, partial);
-  HIP_TRY(c, hipGetLastError());
-  for (uint32_t b = 0; b < nstmt; b++)
-    hipLaunchKernelGGL(k_witness_finish, dim3((d + 255) / 256), dim3(256), 0, c->stream, src.t, partial + (size_t)b * G * d, G, d, h_delta[b],
-                       d_w + (size_t)b * d);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-// rank's share of sum_{bit} v_i as d uint64 lanes, each already reduced mod p (so `world` of them sum without overflow)
-int mfh_witness_lanes(mfh_ctx *c, const uint32_t *d_ssp, const uint8_t *h_bits, uint32_t rank, uint32_t world, uint64_t *d_lanes) {
-  if (!c || !h_bits || !d_lanes || world == 0 || rank >= world) return MFH_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  mf::SspSrc src;
-  int rc = ssp_src(c, d_ssp, src);
-  if (rc) return rc;
-  uint32_t G;
-  uint64_t *partial;
-  rc = witness_partials(c, src, h_bits, rank, world, &G, &partial);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_witness_lanes, dim3((c->P.d + 255) / 256), dim3(256), 0, c->stream, partial, G, c->P.d, d_lanes);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
-}
-
-// w = delta*t + (summed lanes) mod p
-int mfh_witness_from_lanes(mfh_ctx *c, const uint32_t *d_ssp, const uint64_t *d_lanes, uint32_t delta, uint32_t *d_w) {
-  if (!c || !d_lanes || !d_w) return MFH_EINVAL;
-  if (delta >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  mf::SspSrc src;
-  int rc0 = ssp_src(c, d_ssp, src);
-  if (rc0) return rc0;
-  hipLaunchKernelGGL(k_witness_finish, dim3((c->P.d + 255) / 256), dim3(256), 0, c->stream, src.t, d_lanes, 1u, c->P.d, delta, d_w);
-  HIP_TRY(c, hipGetLastError());
   return MFH_OK;
 }
 

@@ -26,9 +26,9 @@ MF_HD uint32_t ssp_prg_rowkey(uint64_t seed, uint32_t slot) {  // per-row part, 
   return r | 1u;
 }
 // the un-reduced 32-bit hash; coefficient = raw mod p.  Sums of coefficients may be formed from the raw values and reduced once:
-// raw and coefficient differ by a multiple of p (0 or p).
-MF_HD uint32_t ssp_prg_raw(uint32_t rowkey, uint32_t k) {
-  uint32_t x = (k + 0x632BE5ABu) * rowkey;
+// raw and coefficient differ by a multiple of p (0 or p).  A thread that keeps one k across many rows hoists k + SSP_PRG_K0 and mixes itself (witness.hip).
+constexpr uint32_t SSP_PRG_K0 = 0x632BE5ABu;
+MF_HD uint32_t ssp_prg_mix(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7FEB352Du;
   x ^= x >> 15;
@@ -36,6 +36,7 @@ MF_HD uint32_t ssp_prg_raw(uint32_t rowkey, uint32_t k) {
   x ^= x >> 16;
   return x;
 }
+MF_HD uint32_t ssp_prg_raw(uint32_t rowkey, uint32_t k) { return ssp_prg_mix((k + SSP_PRG_K0) * rowkey); }
 MF_HD uint32_t ssp_prg_coeff(uint32_t rowkey, uint32_t k) {
   const uint32_t x = ssp_prg_raw(rowkey, k);
   return x >= 0xfffffffbu ? x - 0xfffffffbu : x;

@@ -210,7 +210,7 @@ def test_witness_pass_on_the_matrix_cores(gpu_ctx_factory, nstmt):
     wits = [rng.integers(0, 256, size=nbytes, dtype=np.uint8).tobytes() for _ in range(nstmt)]
     wits[0] = bytes(nbytes)
     if nstmt > 1:
-        wits[1] = b"\\xff" * nbytes
+        wits[1] = b"\xff" * nbytes
     deltas = [int(x) for x in rng.integers(0, ol.P, size=nstmt, dtype=np.uint64)]
     deltas[0] = 0
     got_mm = c.to_host(c.witness_poly_many(d_ssp, wits, deltas, mm=True), np.uint32).reshape(nstmt, p.d)

@@ -105,12 +105,17 @@ def _mfma_loop(body, min_mfma):
     return best
 
 
-def test_witness_gemm_loads_are_awaited_four_steps_after_issue(asm_evalmm):
+@pytest.fixture(scope="module")
+def asm_witness(tmp_path_factory):
+    return _asm_of(tmp_path_factory, "witness")
+
+
+def test_witness_gemm_loads_are_awaited_four_steps_after_issue(asm_witness):
     """k_witness_mm8q: per step a wave issues one SSP fragment load and one bit fragment load, both consumed four steps later, so the
     only vector-memory waits of the loop are s_waitcnt vmcnt(6) / vmcnt(7) (two loads per step x 3 younger steps, + the step's own);
     smaller counts mean the compiler fell back to awaiting the stream a step or two after its issue (0.76 ms per 248 statements whatever
     the prefetch depth).  And nothing of the loop lives in scratch."""
-    loop = _mfma_loop(_kernel(asm_evalmm, "_ZN12_GLOBAL__N_114k_witness_mm8qE"), 32)
+    loop = _mfma_loop(_kernel(asm_witness, "_ZN12_GLOBAL__N_114k_witness_mm8qE"), 32)
     waits = [int(m.group(1)) for x in loop for m in [re.search(r"s_waitcnt vmcnt\((\d+)\)", x)] if m]
     assert waits and min(waits) >= 6, waits
     assert not any(x.startswith("scratch_") for x in loop)
