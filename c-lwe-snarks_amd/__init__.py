@@ -98,7 +98,7 @@ EXPORTS = [
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
     "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
-    "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
+    "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
 ]
 
@@ -219,6 +219,7 @@ def load_library():
         "mfh_ssp_from_rows": (i32, [vp, u32, vp, vp, vp, vp]),
         "mfh_ssp_set_rows": (i32, [vp, u32, vp, vp, vp, u32]),
         "mfh_ssp_rows_fill": (i32, [vp, sz, sz, vp]),
+        "mfh_ssp_rows_violations": (i32, [vp, u32, vp, sz, vp, vp]),
         "mfh_circuit_create": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_create_global": (i32, [vp, u32, u32, vp, u32, vp, ctypes.POINTER(vp)]),
         "mfh_circuit_create_ex": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
@@ -576,6 +577,16 @@ class Context:
         out = self.empty(max(nslots, 1) * self.params.d * 4)
         self._chk(self.lib.mfh_ssp_rows_fill(self._h, first_slot, nslots, _ptr(out)))
         return out
+
+    def ssp_rows_violations(self, witness_bits_list):
+        """the row check (mfh_ssp_rows_violations): for each statement's witness bits (rows of circuit_assign, or bytes as prove_batch takes them) the number of
+        rows of the registered row SSP it violates and the smallest violated row index (0xFFFFFFFF when there is none) -> (count, first), np.uint32 arrays.
+        circuit.Compiled.row_source names a reported row."""
+        nb = len(witness_bits_list)
+        count, first = np.zeros(nb, dtype=np.uint32), np.full(nb, 0xFFFFFFFF, dtype=np.uint32)
+        bits, stride = self._pack_bits(witness_bits_list)
+        self._chk(self.lib.mfh_ssp_rows_violations(self._h, nb, bits if nb else None, stride, ctypes.c_void_p(count.ctypes.data), ctypes.c_void_p(first.ctypes.data)))
+        return count, first
 
     def circuit_load(self, compiled, state="lds"):
         """the gate program of circuit.Compiled on the device: levelised and uploaded once; close() frees it.  state: "lds" (the wire state in LDS, at

@@ -31,7 +31,8 @@ Rows, all values mod p: every wire w gets 2w - 1 (it is 0 or 1).  Then each gate
 Each row is +-1 exactly when c is the gate's output (tests/test_circuit_cpu.py checks all eight (a, b, c) of the first four gates,
 tests/test_circuit_gates_cpu.py every other row over all its inputs).  SUM3 is sound only because MAJ's row forces k, which is why full_add emits the
 two back to back.  Row order: the bit rows, one row per gate in creation order (a wsum's two rows at the place of its first output wire, none for
-its other output wires), the value assertions, then the equalities in creation order.
+its other output wires), the value assertions, then the equalities in creation order.  Compiled.row_source(j) maps a row index back to its wire, gate record,
+assertion or equality (Context.ssp_rows_violations reports row indices).
 
     c = Circuit()
     x = c.private(8); z = c.public()
@@ -150,6 +151,26 @@ class Compiled:
 
     def wire(self, w: Wire) -> int:
         return self.wires[w.node]
+
+    def row_source(self, j: int):
+        """what row j of rows constrains, by compile's row order: ("bit", wire) -- the bit row of that SSP wire; ("gate", g) -- a row of program[g] (both rows
+        of a WSUM head map to the head; a WSUM_BIT record has no row); ("assert", e) -- asserts[e]; ("equal", e) -- equal[e].  Names a row that
+        Context.ssp_rows_violations reports."""
+        j = int(j)
+        if not 0 <= j < self.nrows:
+            raise CircuitError(f"row_source: row {j} is not one of the {self.nrows} rows")
+        if j < self.nwires:
+            return ("bit", j + 1)
+        k = j - self.nwires
+        op = self.program[:, 0]
+        ends = np.cumsum(np.where(op == GATE_WSUM, 2, np.where(op == GATE_WSUM_BIT, 0, 1)))  # ends[g]: gate rows up to and including program[g]
+        ngate = int(ends[-1]) if len(ends) else 0
+        if k < ngate:
+            return ("gate", int(np.searchsorted(ends, k, side="right")))
+        k -= ngate
+        if k < len(self.asserts):
+            return ("assert", k)
+        return ("equal", k - len(self.asserts))
 
 
 class Circuit:

@@ -16,6 +16,9 @@
 // rows (device, row-major; host copy for setup) and the dense prefix of slots [0, lu_max + 2) -- t, v_0, v_1 .. v_lu_max -- which is all that
 // k_add_slot / k_add_public / k_eval_slots01 ever read.  Setup evaluates v_i(s) = sum_j V_ij lambda_j(s), lambda_j(s) = w_j t(s) / (s - r_j)
 // (the indicator [j = k] at s = r_k) on the host: O(nnz + d) once per setup.
+//
+// The row check (mfh_ssp_rows_violations, k_rows_violations): the same row sums E_j, wire 0 included, compared with +-1 per statement -- the number of
+// violated rows and the first of them, without the tree.
 #include <algorithm>
 #include <vector>
 
@@ -28,6 +31,7 @@ namespace {
 
 constexpr uint32_t kLeafMax = 64;               // leaves per bottom node
 constexpr size_t kChunkBytes = (size_t)128 << 20;  // interpolation scratch per chunk of statements: 8 words per padded point and statement
+constexpr size_t kViolStageBytes = (size_t)64 << 20;  // mfh_ssp_rows_violations: staged witness bits per chunk of statements (at least one statement)
 
 // the bottom nodes of the tree of t: node k = prod_{l < G} (x - r_{kG + l}) (r = 0 past n), its G low coefficients.  One thread per node.
 __global__ __launch_bounds__(64) void k_rows_tree_bottom(uint32_t n, uint32_t G, uint32_t nodes, uint32_t *__restrict__ tb) {
@@ -129,6 +133,32 @@ __global__ void k_rows_root(const uint32_t *__restrict__ root, uint32_t Np, uint
   if (k > n) return;
   const uint32_t x = k < n ? root[(size_t)s * Np + k + Np - n] : (t_mode ? 1u : 0u);
   out[(size_t)s * out_stride + k] = delta ? red_p32((uint64_t)x + mulp(delta[s], t[k])) : x;
+}
+
+// The row check (mfh_ssp_rows_violations): thread (j, s) forms E_j of statement s = blockIdx.y as k_rows_leaf does, from the packed bits, but WITH the
+// wire-0 entries (k_rows_leaf leaves them to delta t), and row j is violated unless E_j is 1 or p - 1.  Each wave ballots its violations; the lowest
+// violating lane adds their number to count[s] and lowers first[s] to its own row (the lowest of the wave).  Add and min commute: the result does not
+// depend on the order the waves arrive in.  A wave without a violation issues no atomic.
+__global__ __launch_bounds__(256) void k_rows_violations(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ wire, const uint32_t *__restrict__ coef,
+                                                         uint32_t nrows, const uint8_t *__restrict__ bits, uint32_t stride, uint32_t *__restrict__ count,
+                                                         uint32_t *__restrict__ first) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  bool bad = false;
+  if (j < nrows) {
+    const uint8_t *b = bits + (size_t)s * stride;
+    uint64_t acc = 0;  // each term < 2^32: 2^32 terms fit
+    for (uint32_t e = row_ptr[j], e1 = row_ptr[j + 1]; e < e1; e++) {
+      const uint32_t wi = wire[e];
+      if (wi == 0 || ((b[(wi - 1) >> 3] >> ((wi - 1) & 7)) & 1)) acc += coef[e];
+    }
+    const uint32_t E = red_p32(acc);
+    bad = E != 1 && E != P32 - 1;
+  }
+  const unsigned long long mask = __ballot(bad);  // 64 lanes; the lanes past nrows vote 0
+  if (mask && (threadIdx.x & 63) == (uint32_t)__ffsll(mask) - 1) {
+    atomicAdd(count + s, (uint32_t)__popcll(mask));
+    atomicMin(first + s, j);
+  }
 }
 
 inline dim3 g1(uint32_t n, uint32_t y = 1) { return dim3((n + 255) / 256, y); }
@@ -442,6 +472,43 @@ int mfh_ssp_rows_fill(mfh_ctx *c, size_t first_slot, size_t nslots, uint32_t *d_
     }
   }
   HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
+int mfh_ssp_rows_violations(mfh_ctx *c, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, uint32_t *h_count, uint32_t *h_first) {
+  if (!c) return MFH_EINVAL;
+  const SspRows *R = c->rows;
+  if (!R) { c->err = "mfh_ssp_rows_violations: no row SSP registered (mfh_ssp_set_rows)"; return MFH_EINVAL; }
+  const uint32_t bs = (c->P.m + 6) / 8;
+  if (bits_stride < bs) { c->err = "mfh_ssp_rows_violations: bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  if (nstmt && (!h_bits || !h_count)) { c->err = "mfh_ssp_rows_violations: statements without h_bits / h_count"; return MFH_EINVAL; }
+  if (!nstmt) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // staged as ssp_rows_witness stages them: compacted to bs bytes per statement in pin_rows (mfh_scrub_staging covers it), on the device in the witness
+  // scratch: bits | count | first of one chunk of statements
+  const uint32_t ch = (uint32_t)std::min<size_t>({(size_t)nstmt, std::max<size_t>(1, kViolStageBytes / bs), (size_t)65535});  // (grid.y <= 65535)
+  const size_t bb = ((size_t)ch * bs + 255) & ~(size_t)255;
+  if (int rc = wws_reserve(c, bb + (size_t)ch * 8)) return rc;
+  const uint8_t *d_bits = c->wws.as<const uint8_t>();
+  uint32_t *d_count = reinterpret_cast<uint32_t *>(c->wws.as<uint8_t>() + bb), *d_first = d_count + ch;
+  for (uint32_t s0 = 0; s0 < nstmt; s0 += ch) {
+    const uint32_t k = std::min(ch, nstmt - s0);
+    uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_rows, (size_t)k * bs);
+    if (!st) return MFH_ENOMEM;
+    for (uint32_t b = 0; b < k; b++) memcpy(st + (size_t)b * bs, h_bits + (size_t)(s0 + b) * bits_stride, bs);
+    HIP_TRY(c, hipMemcpyAsync(c->wws.p, st, (size_t)k * bs, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, (size_t)k * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_first, 0xFF, (size_t)k * 4, c->stream));
+    if (R->nrows) {
+      Timer tm(c, 24, (uint64_t)R->nrows * k);  // "ssp_rows_violations" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_rows_violations, g1(R->nrows, k), dim3(256), 0, c->stream, R->row_ptr(), R->wire(), R->coef(), R->nrows, d_bits, bs, d_count, d_first);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(h_count + s0, d_count, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_first) HIP_TRY(c, hipMemcpyAsync(h_first + s0, d_first, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MFH_OK;
 }
 

@@ -25,6 +25,16 @@ The SHA-256 compression statement (Sha256Compress) takes 61 698 wires and 122 88
 d = 2^17 (m = 87 381), above the LDS kernel's wire limit, so its witnesses come from the device-memory kernel and its SSP is the row SSP.
 Written with sums (Sha256Compress(adds="sum")) it takes 28 114 wires and 49 588 rows (28 370 and 49 844 with a public chaining value): it fits
 d = 2^16 (m = 43 690) and the LDS kernel.
+
+Whole statements built from that compression, the result 256 computed public outputs (lu = 256) in both:
+    Sha256Message(length)   "I know a `length`-byte message with this digest": the padding of FIPS 180-4 5.1.1 is constant wires, part of the statement.
+                            length -> (wires, rows): 0 -> (27 588, 49 062), 55 -> (28 042, 49 516): one block, d = 2^16 and the LDS kernel;
+                            56 -> (55 382, 98 072), 100 -> (55 746, 98 436), 119 -> (55 898, 98 588): two blocks, d = 2^17 (m = 87 381);
+                            120 -> (83 238, 147 144): three blocks.
+    MerklePath(depth)       "I know a leaf and a path of `depth` siblings to this root", parent = compress(IV, left || right) (one compression, no
+                            padding block).  28 625 depth + 514 wires, 50 865 depth + 772 rows: depth 1 -> (29 139, 51 637), 2 -> (57 764, 102 502),
+                            3 -> (86 389, 153 367); depth 20 -> (573 014, 1 018 072) fits d = 2^20 (m = 699 050) and the device-memory kernel.
+Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
 
@@ -367,3 +377,124 @@ class Sha256Compress:
         row = np.frombuffer(bytes(bytearray(witness_row)[: self.lu // 8]), dtype=np.uint8)
         bits = np.unpackbits(row, bitorder="little")[self.digest_at: self.digest_at + 256]
         return b"".join(v.to_bytes(4, "big") for v in unpack(bits))
+
+
+def _digest_from_row(witness_row, at: int) -> bytes:
+    """the 32 bytes of the eight computed words at statement bits [at, at + 256) of a witness row"""
+    row = np.frombuffer(bytes(bytearray(witness_row)[: (at + 256) // 8]), dtype=np.uint8)
+    bits = np.unpackbits(row, bitorder="little")[at: at + 256]
+    return b"".join(v.to_bytes(4, "big") for v in unpack(bits))
+
+
+class Sha256Message:
+    """The statement "I know a `length`-byte message whose SHA-256 digest is this value".
+
+    Private inputs: the 8 * length message bits, byte k's bit b (LSB first) at private index 8 k + b -- np.unpackbits(message, bitorder="little").  The
+    padding of FIPS 180-4 5.1.1 (sha256_pad: 0x80, zeros, the bit length) is constant wires: it costs nothing and it is part of the statement, so a proof
+    says the digest is that of a message of exactly `length` bytes (Sha256Compress leaves the padding to the caller).  len(sha256_pad) / 64 compressions
+    (sha256_compress_sum) are chained from the constant SHA256_IV; the digest is 256 computed public outputs (lu = 256).  bits() leaves the digest's
+    positions zero, Circuit.assign / Context.circuit_assign write them, digest_of reads the 32 bytes back.  Sizes: SHA256_MESSAGE_SIZES."""
+
+    def __init__(self, length: int):
+        if not isinstance(length, (int, np.integer)) or length < 0:
+            raise CircuitError("Sha256Message: the length is a non-negative number of bytes")
+        self.length = length = int(length)
+        self.w = w = Words()
+        self.message = w.c.private(8 * length)
+        tail = sha256_pad(bytes(length))[length:]  # the padding depends on the length alone
+        self.blocks = (length + len(tail)) // 64
+
+        def byte(k):  # the 8 wires of padded byte k, LSB first
+            if k < length:
+                return self.message[8 * k: 8 * k + 8]
+            return [w.c.const((tail[k - length] >> b) & 1) for b in range(8)]
+
+        h = [w.const(v) for v in SHA256_IV]
+        for blk in range(self.blocks):
+            # big-endian words: bit i of word t is bit i % 8 of byte 4 t + 3 - i // 8
+            M = [tuple(byte(64 * blk + 4 * t + 3 - i // 8)[i % 8] for i in range(32)) for t in range(16)]
+            h = sha256_compress_sum(w, h, M)
+        self.out = h
+        self.digest = [w.output(x) for x in h]
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 256
+
+    def bits(self, message: bytes):
+        """one statement's input bits, public then private (a row of Context.circuit_assign's input): 256 zeros where the digest is computed, then the message"""
+        message = bytes(message)
+        if len(message) != self.length:
+            raise CircuitError(f"Sha256Message: the message is {self.length} bytes")
+        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(message, dtype=np.uint8), bitorder="little")])
+
+    def digest_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed digest, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0)
+
+
+class MerklePath:
+    """The statement "I know a leaf and an authentication path of `depth` siblings to this root".
+
+    The node function is parent = compress(IV, left || right): ONE SHA-256 compression of the 64-byte concatenation from the constant SHA256_IV, with no
+    padding block -- the usual 2-to-1 compression tree, not SHA-256 of a 64-byte message (which would be two compressions).
+    Private inputs, in this order: the leaf (8 words, big-endian words of its 32 bytes), then per level its sibling (8 words), then `depth` direction
+    bits, bit l = 1 meaning the current node is the RIGHT child at level l (level 0 is the leaf's: bit l of the leaf's index).  Per level a conditional
+    swap, four gates a bit -- t = AND(dir, XOR(cur, sib)), L = XOR(cur, t), R = XOR(sib, t) -- then sha256_compress_sum.  The root is 256 computed
+    public outputs (lu = 256).  28 625 depth + 514 wires and 50 865 depth + 772 rows (MERKLE_PATH_SIZES): depth 20 is 573 014 wires and 1 018 072 rows,
+    which fits Params(d=1 << 20, m=699050)."""
+
+    def __init__(self, depth: int):
+        if not isinstance(depth, (int, np.integer)) or depth < 1:
+            raise CircuitError("MerklePath: the depth is at least 1")
+        self.depth = depth = int(depth)
+        self.w = w = Words()
+        self.leaf = w.private(8)
+        self.siblings = [w.private(8) for _ in range(depth)]
+        self.dirs = w.c.private(depth)
+        iv = [w.const(v) for v in SHA256_IV]
+        cur = self.leaf
+        for sib, d in zip(self.siblings, self.dirs):
+            left, right = [], []
+            for x, y in zip(cur, sib):
+                t = tuple(w.c.AND(d, a) for a in w.xor(x, y))
+                left.append(w.xor(x, t))
+                right.append(w.xor(y, t))
+            cur = sha256_compress_sum(w, iv, left + right)
+        self.out = cur
+        self.root = [w.output(x) for x in cur]
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 256
+
+    def bits(self, leaf: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 256 zeros where the root is computed, the leaf, the siblings from the leaf's level up, then
+        the direction bits = the bits of the leaf's index, least significant first"""
+        siblings = [bytes(s) for s in siblings]
+        if len(leaf) != 32 or len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+            raise CircuitError(f"MerklePath: a 32-byte leaf and {self.depth} siblings of 32 bytes")
+        if not 0 <= index < 1 << self.depth:
+            raise CircuitError(f"MerklePath: the index is in [0, 2^{self.depth})")
+        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
+        return np.concatenate([np.zeros(256, dtype=np.uint8), pack(be_words(bytes(leaf) + b"".join(siblings))), dirs])
+
+    def root_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0)
+
+
+# (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
+# witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
+# (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
+SHA256_MESSAGE_SIZES = {0: (27588, 49062), 55: (28042, 49516), 56: (55382, 98072), 100: (55746, 98436), 119: (55898, 98588), 120: (83238, 147144)}
+# ... and of MerklePath by depth: 28 625 depth + 514 wires, 50 865 depth + 772 rows
+MERKLE_PATH_SIZES = {1: (29139, 51637), 2: (57764, 102502), 3: (86389, 153367), 20: (573014, 1018072)}

@@ -202,6 +202,19 @@ int mfh_ssp_from_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, c
 int mfh_ssp_set_rows(mfh_ctx *ctx, uint32_t nrows, const uint32_t *h_row_ptr, const uint32_t *h_wire, const uint32_t *h_coef, uint32_t lu_max);
 int mfh_ssp_rows_fill(mfh_ctx *ctx, size_t first_slot, size_t nslots, uint32_t *d_out);
 
+/* The row check: which rows of the registered row SSP does a witness violate?  What a prover otherwise learns only from a rejected proof, with no location.
+ * Statement b is h_bits + b * bits_stride in the layout of mfh_prove_batch: bit i - 1 is wire i (with public inputs the statement is bits [0, lu)).
+ * Row j < nrows has  E_j = (the coefficients of its wire-0 entries) + sum of coef(e) over its entries e whose wire i >= 1 has its bit set,  mod p; entries of
+ * one row on one wire add.  The row is satisfied iff E_j is 1 or p - 1.  h_count[b] = the number of violated rows of statement b; h_first[b] (h_first may
+ * be NULL) = the smallest violated row index, 0xFFFFFFFF when there is none.  Padding rows j >= nrows hold for every input and are not examined; an empty
+ * row has E_j = 0 and counts as violated.  A witness with h_count[b] = 0 is one the prover's h = (v^2 - 1) / t is exact for.
+ * One thread per (row, statement) (k_rows_violations, csrc/ssp_rows.hip) reads the packed bits as the prover's bottom level does; the bits are staged like
+ * the prover's, compacted to (m + 6) / 8 bytes per statement in pinned memory that mfh_scrub_staging zeroes, in chunks of statements of at most 64 MiB
+ * (at least one statement), their device copy in the witness scratch.  The call synchronises the stream.
+ * MFH_EINVAL, each with its own text and nothing written: no row SSP registered; bits_stride < (m + 6) / 8; nstmt > 0 with h_bits or h_count NULL.
+ * nstmt = 0 does nothing. */
+int mfh_ssp_rows_violations(mfh_ctx *ctx, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, uint32_t *h_count, uint32_t *h_first);
+
 /* Witnesses of a Boolean circuit for a batch of statements, evaluated on the device.  What random_ssp(mpz_t input, ...) (src/ssp.c:37) is to a random SSP --
  * the reference's only source of a witness -- this is to the SSP of mfh_ssp_from_rows: the input bits of mfh_prove / mfh_prove_batch for each statement.
  * Wires (mfh_ssp_from_rows): wire 0 is the constant, wires 1 .. nin are the inputs (public first, then private), and gate g writes wire nin + 1 + g.
@@ -566,7 +579,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs), "ssp_rows_violations" (k_rows_violations of mfh_ssp_rows_violations; total_rows = rows x statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two

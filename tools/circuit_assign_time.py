@@ -20,12 +20,17 @@ Legs (--leg, default all):
   * sha256_sum_prove: for 255 statements of each of the two, in one process: ssp_set_rows + ssp_prepare (the registration of the rows: up to 151 entries
     a row with sums, 3 - 6 without), one witness_poly call through the row SSP (its witness pass), setup_public, and prove_batch_public called in turn
     (median of min(--reps, 5) calls after one warm-up); "witness_plus_prove_ms" = the circuit_assign call + the batch proof.
+  * merkle: the two whole statements, 255 statements each, every step once in one process: words.Sha256Message(100) at D = 2^17, M = 87 381, then
+    words.MerklePath(20) (573 014 wires, 1 018 072 rows) at D = 2^20, M = 699 050 -- Circuit build and compile, circuit_load, circuit_assign,
+    ssp_set_rows + ssp_prepare, the row check (ssp_rows_violations) against witness_poly_many through the row SSP on the same statements (calls
+    alternated, median of 5 after one warm-up each; also the row check's kernel alone, kind "ssp_rows_violations"), setup_public,
+    prove_batch_public (first call and a second) and verify_public; digests / roots checked against hashlib / tests/sha256_ref.py.
 Printed per leg (one JSON line each, also appended to --out):
   * load: circuit_load once (levelising on the host, the upload);
   * call: the median wall time of circuit_assign (packing the input bits, staging, the launches, the copies back; the call synchronises);
   * kernel: the kernel launches alone (HIP events of mfh_set_timing, kind "circuit_assign" / "circuit_assign_global"), summed over a call's chunks;
   * python: Circuit.assign for --py statements (--py2 at 2^20), scaled to the batch (the rows are checked equal).
-dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove|chacha_out|sha256|sha256_prove|sha256_sum|sha256_sum_prove] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
+dev tool.  usage: python tools/circuit_assign_time.py [--leg all|default|2p20|chain|chacha|chacha_prove|chacha_out|sha256|sha256_prove|sha256_sum|sha256_sum_prove|merkle] [--nb 1020] [--reps 7] [--py 1020] [--py2 4]
 [--out FILE]"""
 import argparse
 import json
@@ -596,11 +601,128 @@ def leg_sha256_sum_prove(a):
         v.ctx.close()
     return ok and statistics.median(vs[1].assign) + statistics.median(vs[1].prove) < statistics.median(vs[0].assign) + statistics.median(vs[0].prove)
 
+def _whole_statement(a, name, p, build, make_bits, result_of, expected):
+    """every step of one statement class at p for 255 statements, one JSON record; True when the results are right, no row is violated and every proof verifies"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+
+    nb = 255
+    rng = np.random.default_rng(2025)
+    t0 = time.perf_counter()
+    st = build()
+    build_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    cc = st.circuit.compile(p)
+    compile_ms = (time.perf_counter() - t0) * 1e3
+    cases = [make_bits(st, rng) for _ in range(nb)]
+    bits = np.stack([b for b, _ in cases])
+    ctx = mf.Context(p, 0)
+    ctx.set_seed(bytes(range(40)))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    prog = ctx.circuit_load(cc, state="auto")
+    load_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    witness, holds = ctx.circuit_assign(prog, bits)
+    assign_first_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    witness, holds = ctx.circuit_assign(prog, bits)
+    assign_ms = (time.perf_counter() - t0) * 1e3
+    state = prog.state
+    prog.close()
+    right = all(result_of(st, witness[b]) == expected(key) for b, (_, key) in enumerate(cases)) and bool(holds.all())
+    t0 = time.perf_counter()
+    ctx.ssp_set_rows(cc.rows, lu_max=cc.lu)
+    ctx.ssp_prepare(None)
+    ctx.sync()
+    rows_ms = (time.perf_counter() - t0) * 1e3
+    stmts = [witness[b].tobytes() for b in range(nb)]
+    deltas = [int(x) for x in rng.integers(0, circuit.P, size=nb, dtype=np.uint64)]
+    # the row check against the witness pass of the row SSP: the same statements, calls alternated, the first round warms up
+    check, wpoly, kern = [], [], []
+    ctx.set_timing(True)
+    for r in range(6):
+        ctx.sync()
+        t0 = time.perf_counter()
+        count, first = ctx.ssp_rows_violations(witness)
+        t1 = time.perf_counter()
+        kern_ms = ctx.timing_drain("ssp_rows_violations")[1]
+        ctx.sync()
+        t2 = time.perf_counter()
+        w = ctx.witness_poly_many(None, stmts, deltas)
+        ctx.sync()
+        t3 = time.perf_counter()
+        del w
+        if r:
+            check.append((t1 - t0) * 1e3)
+            kern.append(kern_ms)
+            wpoly.append((t3 - t2) * 1e3)
+    ctx.set_timing(False)
+    clean = not count.any()
+    alpha, beta, s = (int(x) for x in rng.integers(1, circuit.P, size=3, dtype=np.uint64))
+    d_sk = ctx.to_device(ol.rand_values(rng, p.n, p.L, p.logq))
+    d_err = ctx.to_device(ol.rand_values(rng, 2 * p.d + p.m, p.L, 559))
+    ctx.sync()
+    t0 = time.perf_counter()
+    d_crs = ctx.setup_public(None, alpha, beta, s, cc.lu, d_sk, d_err).clone()
+    ctx.sync()
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    del d_err
+    mags = [rng.integers(0, 256, size=400, dtype=np.uint8).tobytes() for _ in range(nb)]
+    signs = [bytes(rng.integers(0, 2, size=5, dtype=np.uint8).tolist()) for _ in range(nb)]
+    prove = []
+    for _ in range(2):
+        ctx.sync()
+        t0 = time.perf_counter()
+        proofs = ctx.prove_batch_public(d_crs, None, cc.lu, stmts, deltas, mags, signs)
+        ctx.sync()
+        prove.append((time.perf_counter() - t0) * 1e3)
+    vk = ctx.derive_vk(None, s, cc.lu)
+    ctx.sync()
+    t0 = time.perf_counter()
+    ok = ctx.to_host(ctx.verify_public(vk, cc.lu, alpha, beta, d_sk, proofs, stmts), np.uint8)
+    verify_ms = (time.perf_counter() - t0) * 1e3
+    verified = bool(ok.all())
+    lens = np.diff(cc.rows[0].astype(np.int64))
+    _emit({"tool": "circuit_assign_time", "leg": "merkle", "statement": name, "d": p.d, "m": p.m, "nb": nb, "lu": cc.lu, "state": state,
+           "nwires": cc.nwires, "nrows": cc.nrows, "row_entries": int(lens.sum()), "longest_row": int(lens.max()),
+           "build_ms": round(build_ms, 1), "compile_ms": round(compile_ms, 1), "circuit_load_ms": round(load_ms, 1),
+           "circuit_assign_first_ms": round(assign_first_ms, 2), "circuit_assign_ms": round(assign_ms, 2),
+           "ssp_set_rows_prepare_ms": round(rows_ms, 1),
+           "rows_violations_ms": round(statistics.median(check), 3), "rows_violations_ms_all": [round(x, 3) for x in check],
+           "rows_violations_kernel_ms": round(statistics.median(kern), 3),
+           "witness_poly_many_ms": round(statistics.median(wpoly), 3), "witness_poly_many_ms_all": [round(x, 3) for x in wpoly],
+           "setup_public_ms": round(setup_ms, 1), "prove_batch_public_ms_all": [round(x, 2) for x in prove], "verify_public_ms": round(verify_ms, 2),
+           "results_right": bool(right), "violations": int(count.sum()), "verified_all": verified}, a.out)
+    ctx.close()
+    return right and clean and verified
+
+
+def leg_merkle(a):
+    import hashlib
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sha256_ref
+    from c_lwe_snarks_amd import words
+
+    def message_bits(st, rng):
+        m = rng.bytes(100)
+        return st.bits(m), m
+
+    def path_bits(st, rng):
+        leaf, sibs, index = rng.bytes(32), [rng.bytes(32) for _ in range(st.depth)], int(rng.integers(0, 1 << st.depth))
+        return st.bits(leaf, sibs, index), (leaf, sibs, index)
+
+    ok = _whole_statement(a, "Sha256Message(100)", mf.Params(d=1 << 17, m=87381), lambda: words.Sha256Message(100), message_bits,
+                          lambda st, row: st.digest_of(row), lambda m: hashlib.sha256(m).digest())
+    return _whole_statement(a, "MerklePath(20)", mf.Params(d=1 << 20, m=699050), lambda: words.MerklePath(20), path_bits,
+                            lambda st, row: st.root_of(row), lambda k: sha256_ref.merkle_root(*k)) and ok
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", default="all", choices=["all", "default", "2p20", "chain", "chacha", "chacha_prove", "chacha_out", "sha256", "sha256_prove", "sha256_sum",
-                                                      "sha256_sum_prove"])
+                                                      "sha256_sum_prove", "merkle"])
     ap.add_argument("--nb", type=int, default=1020)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--py", type=int, default=1020, help="statements timed through Circuit.assign (default leg)")
@@ -610,7 +732,7 @@ def main():
     ok = True
     for name, fn in (("default", leg_default), ("chain", leg_chain), ("2p20", leg_2p20), ("chacha", leg_chacha), ("chacha_prove", leg_chacha_prove),
                      ("chacha_out", leg_chacha_out), ("sha256", leg_sha256), ("sha256_prove", leg_sha256_prove), ("sha256_sum", leg_sha256_sum),
-                     ("sha256_sum_prove", leg_sha256_sum_prove)):
+                     ("sha256_sum_prove", leg_sha256_sum_prove), ("merkle", leg_merkle)):
         if a.leg in ("all", name):
             ok = fn(a) and ok
     return 0 if ok else 1
