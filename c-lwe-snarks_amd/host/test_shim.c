@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "mfuoco/mangiafuoco_api.h"
+#include "test_vc.h"
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
@@ -295,6 +296,31 @@ static void t_snark(void)
     for (int k = 0; k < NP; k++) { proof_clear(pb[k]); mpz_clear(wit[k]); }
     mpz_clear(one);
     free(cts); free(dec); free(pb); free(wit);
+  }
+  { /* all 16 sets of failing checks at w_s = 777 and at w_s = -v_0(s) (v_s = 0: v_s^2 - 1 = p - 1): verifier() on each proof, mfuoco_verifier_batch on all 32 */
+    enum { NV = 32 };
+    const uint64_t t_s = vc_horner(ssp + ssp_t_offset, vrs->s), v0_s = vc_horner(ssp + ssp_v_offset(0), vrs->s);
+    CHECK(t_s != 0);
+    const uint64_t ws[2] = { 777, (GAMMA_P - v0_s) % GAMMA_P };
+    proof_t *pv = malloc(NV * sizeof *pv);
+    uint8_t want[NV], okv[NV];
+    for (int k = 0; k < NV; k++) {
+      const int fail = k & 15;
+      const uint64_t w_s = ws[k >> 4], v_s = (v0_s + w_s) % GAMMA_P;
+      uint64_t x[5];
+      vc_values(x, fail, w_s, v_s, t_s, vrs->alpha, vrs->beta);
+      want[k] = (uint8_t)vc_expect(x, v_s, t_s, vrs->alpha, vrs->beta);
+      CHECK(want[k] == (fail == 0));
+      proof_init(pv[k]);
+      vc_proof(pv[k], x, 5 * (uint64_t)k);
+      CHECK(verifier(ssp, vrs, pv[k]) == (want[k] != 0));
+    }
+    memset(okv, 9, sizeof okv);
+    mfuoco_verifier_batch(ssp, vrs, pv, NV, okv);
+    for (int k = 0; k < NV; k++) CHECK(okv[k] == want[k]);
+    for (int k = 0; k < NV; k++) proof_clear(pv[k]);
+    free(pv);
+    puts("verifier checks ok");
   }
   proof_clear(pi);
   crs_clear(crs);

@@ -16,6 +16,7 @@
 #include <unistd.h>
 
 #include "mfuoco/mangiafuoco_api.h"
+#include "test_vc.h"
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
 
@@ -182,6 +183,46 @@ int main(void)
   for (int k = 0; k < NB; k++) mpz_init_set(same[k], input);
   mfuoco_verifier_batch_public(ssp, vq, bp, same, NB, lu, ok);
   for (int k = 0; k < NB; k++) CHECK(ok[k] == (k % 3 != 1));
+
+  /* ---- the checks of the public verifiers on crafted proofs: for the all-zero statement, all lu bits and one bit, v_s = v_0(s) + the statement's v_i(s) + w_s from
+   * verification-key values computed here by Horner; all 16 sets of failing checks at w_s = 777 and at the w_s that makes v_s = 0 */
+  {
+    enum { NS = 3, NV = NS * 32 };
+    uint64_t vk[2 + 10];
+    CHECK(lu <= 10);
+    vk[0] = vc_horner(ssp + ssp_t_offset, vq->s);
+    for (uint32_t i = 0; i <= lu; i++) vk[1 + i] = vc_horner(ssp + ssp_v_offset(i), vq->s);
+    CHECK(vk[0] != 0);
+    const uint64_t sbits[NS] = { 0, (1u << lu) - 1, 1u << 3 };
+    proof_t *pv = malloc(NV * sizeof *pv);
+    mpz_t *st = malloc(NV * sizeof *st);
+    uint8_t want[NV], okv[NV];
+    for (int k = 0; k < NV; k++) {
+      const int fail = k & 15;
+      const uint64_t u = sbits[k >> 5];
+      uint64_t base = vk[1];
+      for (uint32_t i = 0; i < lu; i++)
+        if ((u >> i) & 1) base = (base + vk[2 + i]) % GAMMA_P;
+      const uint64_t w_s = (k >> 4) & 1 ? (GAMMA_P - base) % GAMMA_P : 777, v_s = (base + w_s) % GAMMA_P;
+      uint64_t x[5];
+      vc_values(x, fail, w_s, v_s, vk[0], vq->alpha, vq->beta);
+      want[k] = (uint8_t)vc_expect(x, v_s, vk[0], vq->alpha, vq->beta);
+      CHECK(want[k] == (fail == 0));
+      proof_init(pv[k]);
+      vc_proof(pv[k], x, 5 * (uint64_t)k);
+      mpz_init_set_ui(st[k], u);
+      CHECK(mfuoco_verifier_public(ssp, vq, pv[k], st[k], lu) == (want[k] != 0));
+    }
+    memset(okv, 9, sizeof okv);
+    mfuoco_verifier_batch_public(ssp, vq, pv, st, NV, lu, okv);
+    for (int k = 0; k < NV; k++) CHECK(okv[k] == want[k]);
+    /* the accepted proof of each statement under another one: the sums differ (v_4(s) != 0), the second eq-pke line and eq-div fail */
+    CHECK(vk[2 + 3] != 0);
+    CHECK(!mfuoco_verifier_public(ssp, vq, pv[0], st[64], lu) && !mfuoco_verifier_public(ssp, vq, pv[64], st[0], lu));
+    for (int k = 0; k < NV; k++) { proof_clear(pv[k]); mpz_clear(st[k]); }
+    free(pv); free(st);
+    puts("public verifier checks ok");
+  }
 
   for (int k = 0; k < NB; k++) {
     proof_clear(bp[k]);

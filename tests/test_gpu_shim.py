@@ -17,6 +17,7 @@ def test_c_shim_properties():
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "encrypt batch ok" in r.stdout and "snark ok" in r.stdout and "files ok" in r.stdout
+    assert "verifier checks ok" in r.stdout  # verifier() and mfuoco_verifier_batch on constructed proofs: every subset of failing checks
 
 
 def _sharded_exe():

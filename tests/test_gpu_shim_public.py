@@ -18,3 +18,4 @@ def test_c_shim_public_inputs():
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "test_shim_public: ok" in r.stdout
+    assert "public verifier checks ok" in r.stdout  # both _public verifiers on constructed proofs: every subset of failing checks
