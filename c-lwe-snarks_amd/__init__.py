@@ -100,6 +100,7 @@ EXPORTS = [
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
+    "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
 ]
 
 
@@ -227,6 +228,12 @@ def load_library():
         "mfh_circuit_create_sum": (i32, [vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(vp)]),
         "mfh_circuit_destroy": (None, [vp]),
         "mfh_circuit_assign": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
+        "mfh_merkle_create": (i32, [vp, u32, ctypes.POINTER(vp)]),
+        "mfh_merkle_destroy": (None, [vp]),
+        "mfh_merkle_set_leaves": (i32, [vp, vp, u32, u32, vp]),
+        "mfh_merkle_root": (i32, [vp, vp, vp]),
+        "mfh_merkle_nodes": (i32, [vp, u32, ctypes.POINTER(vp)]),
+        "mfh_merkle_paths": (i32, [vp, vp, u32, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -284,6 +291,86 @@ class CircuitProgram:
             self.close()
         except Exception:
             pass
+
+
+class _DeviceBytes:
+    """n x 32 bytes of device memory that something else owns, as torch takes them without a copy (torch.as_tensor reads __cuda_array_interface__ and
+    keeps this object, and with it `owner`, alive as long as the tensor)"""
+
+    def __init__(self, ptr, n, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (n, 32), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
+
+
+class MerkleTree:
+    """a SHA-256 Merkle tree of 2^depth leaves of 32 bytes in device memory (mfh_merkle): made by Context.merkle_tree, all leaves zero at first.
+    parent = compress(IV, left || right), the node function of words.MerklePath; path_bits gives that statement's input rows for leaves of this tree."""
+
+    def __init__(self, ctx, depth, handle):
+        self._ctx, self.depth, self._h = ctx, depth, handle
+        self.nin = 256 + 256 * (depth + 1) + depth  # input bits of words.MerklePath(depth)
+        self._keep = []  # host leaves on their way: set_leaves only queues, the copies live until a call that waits for the stream
+
+    def close(self):
+        """frees the nodes: tensors that nodes() returned must not be used afterwards"""
+        if self._h:
+            self._ctx.lib.mfh_merkle_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_leaves(self, first, leaves):
+        """leaves [first, first + n) <- leaves: bytes-like of 32 n bytes, a numpy uint8 [n, 32], or a torch uint8 tensor on the context's device, which is
+        read in place when the context's stream reaches the call (mfh_merkle_set_leaves: queue-only); their ancestors are recomputed"""
+        c = self._ctx
+        if isinstance(leaves, c.torch.Tensor):
+            t = leaves
+            if t.dtype != c.torch.uint8 or t.device != c.device or not t.is_contiguous():
+                raise MfhError("set_leaves: a device tensor of leaves is contiguous uint8 on the context's device")
+        else:
+            a = np.frombuffer(leaves, dtype=np.uint8) if isinstance(leaves, (bytes, bytearray, memoryview)) else np.asarray(leaves)
+            if a.dtype != np.uint8:
+                raise MfhError("set_leaves: leaves are bytes or uint8")
+            t = c.to_device(a)
+            self._keep.append(t)
+        if t.numel() % 32:
+            raise MfhError("set_leaves: leaves are 32 bytes each")
+        c._chk(c.lib.mfh_merkle_set_leaves(c._h, self._h, int(first), t.numel() // 32, _ptr(t)))
+
+    def root(self):
+        """the root's 32 bytes (mfh_merkle_root; waits for the stream)"""
+        out = (ctypes.c_uint8 * 32)()
+        self._ctx._chk(self._ctx.lib.mfh_merkle_root(self._ctx._h, self._h, out))
+        self._keep = []
+        return bytes(out)
+
+    def nodes(self, level):
+        """level `level` (0 = the leaves, depth = the root) as a torch uint8 [2^(depth - level), 32] view of the tree's memory: no copy, and ordered behind
+        the tree's updates only on the context's stream"""
+        p = ctypes.c_void_p()
+        self._ctx._chk(self._ctx.lib.mfh_merkle_nodes(self._h, int(level), ctypes.byref(p)))
+        return self._ctx.torch.as_tensor(_DeviceBytes(p.value, 1 << (self.depth - level), self), device=self._ctx.device)
+
+    def path_rows(self, indices):
+        """np.uint8 [nb, ceil(nin / 8)]: the packed input rows of words.MerklePath(depth) for the leaves at `indices` (mfh_merkle_paths; indices may repeat)"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise MfhError("path_rows: indices are in [0, 2^depth)")
+        idx = idx.astype(np.uint32)
+        rows = np.zeros((len(idx), (self.nin + 7) // 8), dtype=np.uint8)
+        self._ctx._chk(self._ctx.lib.mfh_merkle_paths(self._ctx._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(rows.ctypes.data),
+                                                      rows.shape[1]))
+        self._keep = []
+        return rows
+
+    def path_bits(self, indices):
+        """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerklePath(depth)"""
+        return np.unpackbits(self.path_rows(indices), axis=1, bitorder="little")[:, : self.nin]
 
 
 class Context:
@@ -644,6 +731,12 @@ class Context:
         self._chk(self.lib.mfh_circuit_assign(self._h, prog._h, nb, ctypes.c_void_p(packed.ctypes.data), packed.shape[1], ctypes.c_void_p(witness.ctypes.data),
                                               stride, ctypes.c_void_p(holds.ctypes.data)))
         return witness, holds.astype(bool)
+
+    def merkle_tree(self, depth):
+        """a MerkleTree of 2^depth zero leaves on this context's device (mfh_merkle_create: 1 <= depth <= 24); close() frees it, before the context"""
+        h = ctypes.c_void_p()
+        self._chk(self.lib.mfh_merkle_create(self._h, int(depth), ctypes.byref(h)))
+        return MerkleTree(self, int(depth), h)
 
     def ssp_to_host_u64(self, d_ssp):
         """the device SSP in the reference's host layout: (m + 3) * d uint64 (files.ssp_write, the oracle, the shim's setup())"""

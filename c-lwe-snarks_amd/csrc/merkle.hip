@@ -1,0 +1,206 @@
+// merkle.hip -- a SHA-256 Merkle tree in device memory (mfh_merkle): built and updated level by level, and read as the input rows of words.MerklePath.
+//
+// The tree.  One allocation of 2^(depth + 1) nodes of 32 bytes in heap order: node 1 is the root, the children of node k are 2k and 2k + 1, slot 0 is
+// unused; node j of level l (0 = the leaves) is heap index 2^(depth - l) + j.  A node is its 32 digest BYTES (the big-endian words of FIPS 180-4, what
+// hashlib prints), so leaves are copied in as they are and every level reads as digests; the kernels swap the bytes of a word on load and store (one
+// v_perm_b32 each).  The two children of a parent are 64 contiguous, 64-byte aligned bytes: four 16-byte loads in, two 16-byte stores out.
+// The node function is parent = compress(IV, left || right) (sha256_dev.hpp): one compression, no padding block -- words.MerklePath's.
+//
+// k_merkle_level: one thread per parent of a contiguous range of one level.  A build or an update is one launch per level from the leaves' parents up
+// to the root, in order on the context's stream: the leaves [first, first + count) change parents [first >> l, (first + count - 1) >> l] of level l and
+// nothing else (a parent at the edge of the range has one changed and one unchanged child: heap indexing makes that no special case).  The narrow top
+// levels are launches like the others -- no second kernel body that walks several levels in one workgroup (DESIGN.md 4.8.6 has what they cost).
+// k_merkle_paths: one workgroup per statement writes the packed input row of MerklePath(depth) -- 32 zero bytes where the root is computed, the leaf's 8
+// words, the 8 words of the sibling of every level (heap node ((2^depth + i) >> l) ^ 1), each word a native uint32 holding its value, then the
+// ceil(depth / 8) bytes of the index i, whose bit l is direction bit l.
+#include <algorithm>
+
+#include "ctx.hpp"
+#include "sha256_dev.hpp"
+
+namespace {
+
+constexpr uint32_t kMaxDepth = 24;                      // 2^25 nodes: 1 GiB
+constexpr size_t kPathStageBytes = (size_t)64 << 20;    // mfh_merkle_paths: rows per chunk of statements (at least one statement)
+
+__device__ __forceinline__ uint4 bswap4(uint4 v) { return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w)); }
+
+// parents [p0, p0 + n) in heap order (one level): nodes = the heap as 16-byte units, node k = units 2k, 2k + 1
+__global__ __launch_bounds__(256) void k_merkle_level(uint4 *nodes, uint32_t p0, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t k = (size_t)p0 + i;
+  const uint4 *ch = nodes + 4 * k;  // children 2k, 2k + 1: units 4k .. 4k + 3
+  const uint4 c0 = bswap4(ch[0]), c1 = bswap4(ch[1]), c2 = bswap4(ch[2]), c3 = bswap4(ch[3]);
+  uint32_t w[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+  uint32_t h[8] = MF_SHA256_IV;
+  mf::sha256_compress(h, w);
+  nodes[2 * k] = bswap4(make_uint4(h[0], h[1], h[2], h[3]));
+  nodes[2 * k + 1] = bswap4(make_uint4(h[4], h[5], h[6], h[7]));
+}
+
+// statement b = blockIdx.x with leaf index idx[b]: row words [0, 8) zero, word 8 + 8 j + e = word e of the leaf (j = 0) or of the sibling of level j - 1,
+// then one word holding the index (its ceil(depth / 8) low bytes are the row's last bytes; the rest lies inside the row's 16-byte padded stride)
+__global__ __launch_bounds__(64) void k_merkle_paths(const uint32_t *__restrict__ nodes, uint32_t depth, const uint32_t *__restrict__ idx,
+                                                     uint32_t *__restrict__ rows, uint32_t stride_words) {
+  const uint32_t b = blockIdx.x, i = idx[b], leaf = (1u << depth) + i, nw = 8 * (depth + 2);
+  uint32_t *row = rows + (size_t)b * stride_words;
+  for (uint32_t w = threadIdx.x; w < nw; w += 64) {
+    uint32_t v = 0;
+    if (w >= 8) {
+      const uint32_t j = (w - 8) >> 3, e = w & 7;
+      const uint32_t node = j ? ((leaf >> (j - 1)) ^ 1u) : leaf;
+      v = __builtin_bswap32(nodes[(size_t)node * 8 + e]);
+    }
+    row[w] = v;
+  }
+  if (threadIdx.x == 0) row[nw] = i;
+}
+
+inline size_t path_row_bytes(uint32_t depth) { return 32 + (size_t)32 * (depth + 1) + (depth + 7) / 8; }
+
+}  // namespace
+
+struct mfh_merkle {
+  mfh_ctx *owner = nullptr;  // the creating context: mfh_merkle_nodes, which is handed none, leaves its error text there
+  int device = 0;
+  uint32_t depth = 0;
+  uint8_t *mem = nullptr;  // 2^(depth + 1) nodes
+  uint8_t *level(uint32_t l) const { return mem + ((size_t)32 << (depth - l)); }
+};
+
+namespace {
+
+int fail(mfh_ctx *c, const char *who, const char *what) {
+  c->err = std::string(who) + ": " + what;
+  return MFH_EINVAL;
+}
+
+// the ancestors of leaves [first, first + count), level by level on the context's stream
+int merkle_update(mfh_ctx *c, const mfh_merkle *t, uint32_t first, uint32_t count) {
+  const uint64_t last = (uint64_t)first + count - 1;
+  for (uint32_t l = 1; l <= t->depth; l++) {
+    const uint32_t lo = first >> l, n = (uint32_t)(last >> l) - lo + 1;
+    Timer tm(c, 25, n);  // "merkle_level" (mfhip.hip: timing_kind)
+    hipLaunchKernelGGL(k_merkle_level, dim3((n + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<uint4 *>(t->mem), (1u << (t->depth - l)) + lo, n);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_create(mfh_ctx *c, uint32_t depth, mfh_merkle **out) {
+  if (!c) return MFH_EINVAL;
+  if (!out) return fail(c, "mfh_merkle_create", "out is null");
+  if (depth < 1 || depth > kMaxDepth) return fail(c, "mfh_merkle_create", "depth must be in [1, 24]");
+  HIP_TRY(c, hipSetDevice(c->device));
+  mfh_merkle *t = new mfh_merkle();
+  t->owner = c;
+  t->device = c->device;
+  t->depth = depth;
+  const size_t bytes = (size_t)64 << depth;
+  if (hipMalloc(&t->mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete t;
+    c->err = "mfh_merkle_create: no memory for the nodes";
+    return MFH_ENOMEM;
+  }
+  // all-zero leaves with every level computed: every later state is well defined
+  int rc = hipMemsetAsync(t->mem, 0, bytes, c->stream) == hipSuccess ? merkle_update(c, t, 0, 1u << depth) : MFH_EDEVICE;
+  if (rc == MFH_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = MFH_EDEVICE;
+  if (rc != MFH_OK) {
+    (void)hipGetLastError();
+    hipFree(t->mem);
+    delete t;
+    c->err = "mfh_merkle_create: building the tree of zero leaves failed";
+    return rc;
+  }
+  *out = t;
+  return MFH_OK;
+}
+
+void mfh_merkle_destroy(mfh_merkle *t) {
+  if (!t) return;
+  hipSetDevice(t->device);
+  if (t->mem) hipFree(t->mem);
+  delete t;
+}
+
+int mfh_merkle_set_leaves(mfh_ctx *c, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_leaves) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, "mfh_merkle_set_leaves", "the tree is null");
+  if (t->device != c->device) return fail(c, "mfh_merkle_set_leaves", "the tree belongs to another device");
+  if ((uint64_t)first + count > (1ull << t->depth)) return fail(c, "mfh_merkle_set_leaves", "first + count exceeds the 2^depth leaves");
+  if (!count) return MFH_OK;
+  if (!d_leaves) return fail(c, "mfh_merkle_set_leaves", "leaves without d_leaves");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(t->level(0) + (size_t)32 * first, d_leaves, (size_t)32 * count, hipMemcpyDeviceToDevice, c->stream));
+  return merkle_update(c, t, first, count);
+}
+
+int mfh_merkle_root(mfh_ctx *c, const mfh_merkle *t, uint8_t h_root[32]) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, "mfh_merkle_root", "the tree is null");
+  if (!h_root) return fail(c, "mfh_merkle_root", "h_root is null");
+  if (t->device != c->device) return fail(c, "mfh_merkle_root", "the tree belongs to another device");
+  HIP_TRY(c, hipSetDevice(c->device));
+  uint8_t *pin = (uint8_t *)pin_acquire(c, c->pin_cw, 32);
+  if (!pin) return MFH_ENOMEM;
+  HIP_TRY(c, hipMemcpyAsync(pin, t->level(t->depth), 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(h_root, pin, 32);
+  return MFH_OK;
+}
+
+int mfh_merkle_nodes(const mfh_merkle *t, uint32_t level, const uint8_t **d_nodes) {
+  if (!t) return MFH_EINVAL;
+  if (!d_nodes) return fail(t->owner, "mfh_merkle_nodes", "d_nodes is null");
+  if (level > t->depth) return fail(t->owner, "mfh_merkle_nodes", "level above the depth");
+  *d_nodes = t->level(level);
+  return MFH_OK;
+}
+
+int mfh_merkle_paths(mfh_ctx *c, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint8_t *h_inputs, size_t in_stride) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, "mfh_merkle_paths", "the tree is null");
+  if (t->device != c->device) return fail(c, "mfh_merkle_paths", "the tree belongs to another device");
+  const size_t rowb = path_row_bytes(t->depth);
+  if (in_stride < rowb) return fail(c, "mfh_merkle_paths", "in_stride shorter than the row's ceil(nin / 8) bytes");
+  if (nstmt && !h_index) return fail(c, "mfh_merkle_paths", "statements without h_index");
+  if (nstmt && !h_inputs) return fail(c, "mfh_merkle_paths", "statements without h_inputs");
+  for (uint32_t b = 0; b < nstmt; b++)
+    if (h_index[b] >> t->depth) return fail(c, "mfh_merkle_paths", "an index is not below 2^depth");
+  if (!nstmt) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // a chunk: the most statements whose rows fit kPathStageBytes (mfh_ssp_rows_violations chunks its bits the same way).  On the device, in the scratch of
+  // mfh_circuit_assign (these are its input rows; that call leaves nothing in flight): rows at a stride of 16 bytes' multiple | indices
+  const size_t rs = (rowb + 15) & ~(size_t)15;
+  const uint32_t ch = (uint32_t)std::min<size_t>(nstmt, std::max<size_t>(1, kPathStageBytes / rowb));
+  if (int rc = work_reserve(c, c->circ_io, (size_t)ch * rs + (size_t)ch * 4)) return rc;
+  uint32_t *d_rows = c->circ_io.as<uint32_t>(), *d_idx = d_rows + (size_t)ch * rs / 4;
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * rs);
+  if (!pin_out) return MFH_ENOMEM;
+  for (uint32_t b0 = 0; b0 < nstmt; b0 += ch) {
+    const uint32_t k = std::min(ch, nstmt - b0);
+    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)k * 4);
+    if (!pin_idx) return MFH_ENOMEM;
+    memcpy(pin_idx, h_index + b0, (size_t)k * 4);
+    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    {
+      Timer tm(c, 26, k);  // "merkle_paths"
+      hipLaunchKernelGGL(k_merkle_paths, dim3(k), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(t->mem), t->depth, (const uint32_t *)d_idx, d_rows,
+                         (uint32_t)(rs / 4));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
+  }
+  return MFH_OK;
+}
+
+}  // extern "C"

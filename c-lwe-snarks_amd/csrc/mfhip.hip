@@ -1138,6 +1138,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "circuit_assign_sum")) return 22;  // k_circuit_eval<true, OUT, true> (mfh_circuit_create_sum programs with a WSUM gate, wires in LDS)
   if (!strcmp(which, "circuit_assign_global_sum")) return 23;  // k_circuit_eval_global<true, OUT, true> (... with MFH_CIRCUIT_GLOBAL)
   if (!strcmp(which, "ssp_rows_violations")) return 24;  // k_rows_violations of mfh_ssp_rows_violations (ssp_rows.hip); rows = rows x statements
+  if (!strcmp(which, "merkle_level")) return 25;  // k_merkle_level (merkle.hip): one per level of a build or update; rows = parents computed
+  if (!strcmp(which, "merkle_paths")) return 26;  // k_merkle_paths of mfh_merkle_paths; rows = statements
   return -1;
 }
 

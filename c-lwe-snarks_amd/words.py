@@ -491,6 +491,15 @@ class MerklePath:
         """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
         return _digest_from_row(witness_row, 0)
 
+    @staticmethod
+    def statement(root: bytes) -> bytes:
+        """the 32 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the root is `root`": each word's 4 bytes reversed, the
+        inverse of root_of -- a verifier checks a proof against a root it knows without a witness row"""
+        root = bytes(root)
+        if len(root) != 32:
+            raise CircuitError("MerklePath: the root is 32 bytes")
+        return b"".join(root[i: i + 4][::-1] for i in range(0, 32, 4))
+
 
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter

@@ -319,6 +319,38 @@ void mfh_circuit_destroy(mfh_circuit *c);
 int mfh_circuit_assign(mfh_ctx *ctx, const mfh_circuit *c, uint32_t nstmt, const uint8_t *h_inputs, size_t in_stride, uint8_t *h_witness_bits,
                        size_t bits_stride, uint8_t *h_holds);
 
+/* ---- Merkle trees (merkle.hip): what words.MerklePath(depth) proves membership in, kept in device memory ------------------------------
+ * The node function is parent = compress(IV, left || right): ONE SHA-256 compression of the 64 bytes from the constant initial hash value, no padding
+ * block.  The tree is one device allocation of 2^(depth + 1) nodes of 32 bytes in heap order: node 1 is the root, the children of node k are 2k and
+ * 2k + 1, slot 0 is unused; node j of level l (0 = the leaves, depth = the root) is heap index 2^(depth - l) + j.  A node is stored as its 32 digest
+ * bytes (the big-endian words of FIPS 180-4, what hashlib prints).  The tree belongs to ctx's device and may be used by every context of that device;
+ * its memory is its own (hipMalloc at create).  Destroy it before the context that created it.
+ *   create      1 <= depth <= 24 (1 GiB of nodes at 24).  The tree of all-zero leaves with every level computed; waits for the stream.
+ *   set_leaves  d_leaves = count x 32 bytes ON THE DEVICE, copied to leaves [first, first + count); then parents [first >> l, (first + count - 1) >> l] of
+ *               level l = 1 .. depth are recomputed, one launch of k_merkle_level per level, and nothing else.  Queue-only on the context's stream (no
+ *               host wait): d_leaves must stay valid until the stream has passed the call.  count = 0 does nothing.
+ *   root        the root's 32 bytes to the host; synchronises the stream.
+ *   nodes       the device pointer of level `level`'s first node (2^(depth - level) nodes of 32 bytes follow), 0 <= level <= depth; touches no stream:
+ *               the caller orders its reads behind the context's stream.  Its error text goes to the creating context.
+ *   paths       row b of h_inputs (in_stride bytes) becomes the packed input row of MerklePath(depth) for the leaf of index h_index[b] -- what
+ *               mfh_circuit_assign takes: 32 zero bytes where the root is computed; the leaf's 8 words; for l = 0 .. depth - 1 the 8 words of the sibling,
+ *               heap node ((2^depth + index) >> l) ^ 1; each word a little-endian uint32 holding the word's value (the node's 4 bytes reversed); then
+ *               ceil(depth / 8) bytes holding the index, little-endian (direction bit l = bit l of the index).  nin = 256 + 256 (depth + 1) + depth bits;
+ *               exactly ceil(nin / 8) bytes of a row are written, the rest of a wider row is left alone.  Indices may repeat.  One launch of
+ *               k_merkle_paths per chunk of statements, a chunk being the most statements whose rows fit 64 MiB (at least one); staged through the
+ *               context's pinned buffers (mfh_scrub_staging zeroes them); synchronises the stream.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing allocated, queued or written: depth 0 or above 24; a null tree or a null
+ * required pointer; a tree of another device; first + count > 2^depth; an index >= 2^depth; in_stride < ceil(nin / 8); level > depth.
+ * Kernel timing kinds: "merkle_level" (total_rows = parents computed, one count per launch: depth launches and 2^depth - 1 rows for a full build) and
+ * "merkle_paths" (total_rows = statements). */
+typedef struct mfh_merkle mfh_merkle;
+int mfh_merkle_create(mfh_ctx *ctx, uint32_t depth, mfh_merkle **out);
+void mfh_merkle_destroy(mfh_merkle *t);
+int mfh_merkle_set_leaves(mfh_ctx *ctx, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_leaves);
+int mfh_merkle_root(mfh_ctx *ctx, const mfh_merkle *t, uint8_t h_root[32]);
+int mfh_merkle_nodes(const mfh_merkle *t, uint32_t level, const uint8_t **d_nodes);
+int mfh_merkle_paths(mfh_ctx *ctx, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint8_t *h_inputs, size_t in_stride);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
@@ -579,7 +611,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs), "ssp_rows_violations" (k_rows_violations of mfh_ssp_rows_violations; total_rows = rows x statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs), "ssp_rows_violations" (k_rows_violations of mfh_ssp_rows_violations; total_rows = rows x statements), "merkle_level" / "merkle_paths" (k_merkle_level / k_merkle_paths of the Merkle tree calls; total_rows = parents computed / statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two
