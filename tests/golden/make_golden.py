@@ -35,6 +35,13 @@ def ref_stream():
             buf = ctypes.create_string_buffer(n)
             lib.ref_keystream(ctypes.c_char_p(s), ctypes.c_uint64(off), buf, ctypes.c_size_t(n))
             out["stateless"].append({"seed": s.hex(), "off": off, "n": n, "out": buf.raw.hex()})
+    # windows that straddle stream byte 2^36 = counter block 2^32, where the counter's high word changes (appended: the cases above keep their places)
+    b36 = 1 << 36
+    for s in seeds:
+        for off, n in [(b36 - 16, 32), (b36 - 3, 40), (b36 - 4096 - 8, 4096 + 24), (b36, 16), (b36 - 1, 1), (b36 - 92 * 3 - 5, 92 * 6)]:
+            buf = ctypes.create_string_buffer(n)
+            lib.ref_keystream(ctypes.c_char_p(s), ctypes.c_uint64(off), buf, ctypes.c_size_t(n))
+            out["stateless"].append({"seed": s.hex(), "off": off, "n": n, "out": buf.raw.hex()})
     seqs = [[92] * 5, [1, 5, 32, 40, 65, 64, 92, 94], [16, 16, 3, 13, 92, 7], [8, 69, 1, 80, 1], [15, 1, 16, 17]]
     for s in seeds[:2]:
         for off in (0, 512, 135240 + 7):
@@ -45,6 +52,15 @@ def ref_stream():
                 ctr, rem = ctypes.c_uint64(), ctypes.c_uint64()
                 lib.ref_state_after(ctypes.c_char_p(s), ctypes.c_uint64(off), arr, ctypes.c_size_t(len(sizes)), ctypes.byref(ctr), ctypes.byref(rem))
                 out["stateful"].append({"seed": s.hex(), "off": off, "sizes": sizes, "out": buf.raw.hex(), "ctr": ctr.value, "rem": rem.value})
+    # ... and reads in pieces across it: the state after them has a counter above 2^32
+    for s in seeds[:2]:
+        for off, sizes in [(b36 - 100, [92, 92, 92]), (b36 - 16, [16, 1, 15, 8]), (b36 - 8, [3, 5, 16, 7])]:
+            arr = (ctypes.c_uint32 * len(sizes))(*sizes)
+            buf = ctypes.create_string_buffer(sum(sizes))
+            lib.ref_gen_sequence(ctypes.c_char_p(s), ctypes.c_uint64(off), arr, ctypes.c_size_t(len(sizes)), buf)
+            ctr, rem = ctypes.c_uint64(), ctypes.c_uint64()
+            lib.ref_state_after(ctypes.c_char_p(s), ctypes.c_uint64(off), arr, ctypes.c_size_t(len(sizes)), ctypes.byref(ctr), ctypes.byref(rem))
+            out["stateful"].append({"seed": s.hex(), "off": off, "sizes": sizes, "out": buf.raw.hex(), "ctr": ctr.value, "rem": rem.value})
     # widths exercised by src/test_entropy.c:24-78 plus the parameter sets' widths
     for nbits in [64, 1, 5, 32, 40, 520, 512, 700] + list(range(736, 752)) + [1472]:
         limbs = (nbits + 63) // 64
