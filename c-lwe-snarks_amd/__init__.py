@@ -101,6 +101,7 @@ EXPORTS = [
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
+    "mfh_sha256_records", "mfh_merkle_set_records",
 ]
 
 
@@ -234,6 +235,8 @@ def load_library():
         "mfh_merkle_root": (i32, [vp, vp, vp]),
         "mfh_merkle_nodes": (i32, [vp, u32, ctypes.POINTER(vp)]),
         "mfh_merkle_paths": (i32, [vp, vp, u32, vp, vp, sz]),
+        "mfh_sha256_records": (i32, [vp, vp, sz, u32, u32, vp]),
+        "mfh_merkle_set_records": (i32, [vp, vp, u32, u32, vp, sz, u32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -302,6 +305,24 @@ class _DeviceBytes:
         self.__cuda_array_interface__ = {"shape": (n, 32), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
 
 
+def _records(ctx, records, who):
+    """(tensor, stride, length, n, host) of records as the device calls take them: a numpy uint8 [n, length], uploaded (host = True), or a torch uint8
+    tensor on the context's device with stride(1) == 1 and stride(0) >= length, read in place (a column slice of a wider table is no copy)"""
+    if isinstance(records, ctx.torch.Tensor):
+        t = records
+        if t.dtype != ctx.torch.uint8 or t.device != ctx.device or t.dim() != 2:
+            raise MfhError(f"{who}: a device tensor of records is uint8 [n, length] on the context's device")
+        n, length = int(t.shape[0]), int(t.shape[1])
+        if (length > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < length):
+            raise MfhError(f"{who}: a device tensor of records has stride(1) == 1 and stride(0) >= length")
+        return t, (int(t.stride(0)) if n > 1 else length), length, n, False
+    a = np.asarray(records)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise MfhError(f"{who}: records are a uint8 array [n, length]")
+    n, length = a.shape
+    return ctx.to_device(a).reshape(n, length), length, length, n, True
+
+
 class MerkleTree:
     """a SHA-256 Merkle tree of 2^depth leaves of 32 bytes in device memory (mfh_merkle): made by Context.merkle_tree, all leaves zero at first.
     parent = compress(IV, left || right), the node function of words.MerklePath; path_bits gives that statement's input rows for leaves of this tree."""
@@ -342,6 +363,16 @@ class MerkleTree:
             raise MfhError("set_leaves: leaves are 32 bytes each")
         c._chk(c.lib.mfh_merkle_set_leaves(c._h, self._h, int(first), t.numel() // 32, _ptr(t)))
 
+    def set_records(self, first, records):
+        """leaves [first, first + n) <- SHA-256 of the n records, hashed on the device straight into the leaves; their ancestors are recomputed
+        (mfh_merkle_set_records: queue-only).  records: a numpy uint8 [n, length], uploaded, or a torch uint8 tensor [n, length] on the context's device
+        with stride(1) == 1 and stride(0) >= length, read in place when the context's stream reaches the call"""
+        c = self._ctx
+        t, stride, length, n, host = _records(c, records, "set_records")
+        if host:
+            self._keep.append(t)
+        c._chk(c.lib.mfh_merkle_set_records(c._h, self._h, int(first), n, _ptr(t), stride, length))
+
     def root(self):
         """the root's 32 bytes (mfh_merkle_root; waits for the stream)"""
         out = (ctypes.c_uint8 * 32)()
@@ -367,6 +398,28 @@ class MerkleTree:
                                                       rows.shape[1]))
         self._keep = []
         return rows
+
+    def record_rows(self, records, indices):
+        """np.uint8 [nb, ceil(nin / 8)]: the packed input rows of words.MerkleRecord(length, depth), records[i] (a uint8 [nb, length] array, or nb
+        bytes-likes of one length) being the record at leaf indices[i]: 32 zero bytes where the root is computed, the record's bytes, then the siblings
+        and the index bytes of path_rows(indices).  That the record hashes to that leaf is not checked here: the root circuit_assign computes shows it."""
+        paths = self.path_rows(indices)
+        if isinstance(records, np.ndarray):
+            rec = records
+        else:
+            rec = [np.frombuffer(bytes(r), dtype=np.uint8) for r in records]
+            if len({len(r) for r in rec}) > 1:
+                raise MfhError("record_rows: the records are of one length")
+            rec = np.stack(rec) if rec else np.zeros((0, 0), dtype=np.uint8)
+        if rec.dtype != np.uint8 or rec.ndim != 2 or len(rec) != len(paths):
+            raise MfhError("record_rows: records are uint8 [nb, length], one per index")
+        return np.concatenate([np.zeros((len(paths), 32), dtype=np.uint8), rec, paths[:, 64:]], axis=1)
+
+    def record_bits(self, records, indices):
+        """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerkleRecord(length, depth)"""
+        rows = self.record_rows(records, indices)
+        length = rows.shape[1] - 32 - 32 * self.depth - (self.depth + 7) // 8
+        return np.unpackbits(rows, axis=1, bitorder="little")[:, : 256 + 8 * length + 257 * self.depth]
 
     def path_bits(self, indices):
         """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerklePath(depth)"""
@@ -731,6 +784,18 @@ class Context:
         self._chk(self.lib.mfh_circuit_assign(self._h, prog._h, nb, ctypes.c_void_p(packed.ctypes.data), packed.shape[1], ctypes.c_void_p(witness.ctypes.data),
                                               stride, ctypes.c_void_p(holds.ctypes.data)))
         return witness, holds.astype(bool)
+
+    def sha256_records(self, records):
+        """torch uint8 [n, 32] on the device: SHA-256 of each of n records of one length, what hashlib.sha256(record).digest() gives
+        (mfh_sha256_records: one launch of k_sha256_records, queue-only).  records: a numpy uint8 [n, length], uploaded (the call then waits for the
+        stream, the upload being its own), or a torch uint8 tensor [n, length] on the context's device with stride(1) == 1 and stride(0) >= length, read
+        in place when the context's stream reaches the call: a column slice of a wider table is no copy."""
+        t, stride, length, n, host = _records(self, records, "sha256_records")
+        out = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.device)
+        self._chk(self.lib.mfh_sha256_records(self._h, _ptr(t), stride, length, n, _ptr(out)))
+        if host:
+            self.sync()
+        return out
 
     def merkle_tree(self, depth):
         """a MerkleTree of 2^depth zero leaves on this context's device (mfh_merkle_create: 1 <= depth <= 24); close() frees it, before the context"""

@@ -13,6 +13,8 @@
 // k_merkle_paths: one workgroup per statement writes the packed input row of MerklePath(depth) -- 32 zero bytes where the root is computed, the leaf's 8
 // words, the 8 words of the sibling of every level (heap node ((2^depth + i) >> l) ^ 1), each word a native uint32 holding its value, then the
 // ceil(depth / 8) bytes of the index i, whose bit l is direction bit l.
+// k_sha256_records: SHA-256 of whole records, one thread per record, for mfh_sha256_records and mfh_merkle_set_records, which hashes records straight
+// into the leaves (its load plan and LDS image: above the kernel).
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -59,6 +61,79 @@ __global__ __launch_bounds__(64) void k_merkle_paths(const uint32_t *__restrict_
 
 inline size_t path_row_bytes(uint32_t depth) { return 32 + (size_t)32 * (depth + 1) + (depth + 7) / 8; }
 
+// ---- k_sha256_records: SHA-256 of `count` whole messages of `length` bytes each, record r at rec + r * stride (stride >= length; any byte alignment of
+// rec and stride), its digest's 32 bytes at dig + 2 r (16-byte units).  One thread per record, 256 a workgroup; the state and the rolling schedule stay
+// in registers over sha256_blocks(length) calls of mf::sha256_compress; the padding is sha256_pad_word's, from `length` alone.
+//
+// Loads.  A thread walking its own record would put a stride between the lanes of every load, so each 64-byte block of the workgroup's 256 records goes
+// through LDS: in four passes lanes 4 r .. 4 r + 3 of a wave take the four 16-byte units of record r's current block (64 contiguous bytes a record, and
+// one contiguous run over the wave when the records are packed).  Misalignment is per record and is taken out HERE: a lane loads the five dwords
+// at and after the unit's address rounded down to 4 and funnel-shifts them by (address & 3) bytes (v_alignbyte_b32), so the LDS image holds every
+// block from its row's byte 0.  A dword that lies wholly inside the span [rec, rec + (count - 1) * stride + length) is one load (all five: a 16-byte
+// and a 4-byte load); one that crosses the span's head or tail -- only in the first and the last record -- is put together from the byte loads of its
+// bytes inside the span; dwords holding no byte of the unit's part of the record are not loaded.  Nothing outside the span is read, whatever count % 256.
+// A byte of the span outside the record (a gap, a neighbour) may be loaded; sha256_pad_word masks it.
+//
+// The LDS image: row r = the 64 bytes of record r's block at a pitch of 80 bytes = 20 dwords (256 rows: 20 480 bytes, 8 workgroups a CU).  ds_read_b128
+// is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32), bank = (address / 4) mod 64, 4 banks a lane.  Lane
+// r reading unit u of its row starts at bank (20 r + 4 u) mod 64 = 4 ((5 r + u) mod 16); every group holds each residue of r mod 16 once and 5 is odd,
+// so its 16 lanes start at the 16 multiples of 4 and cover the 64 banks once: no conflict (any pitch of 16 x odd bytes does this; 80 is the smallest
+// above 64).  The stores (ds_write_b128: 8 contiguous lanes a group = two rows, banks mod 32) overlap by 4 banks between the two rows of a group: one
+// extra LDS cycle under an instruction whose register transfer takes 13.
+constexpr uint32_t kRecPitch = 80;
+
+// the dword at rec + p (a 4-byte aligned address; p may be below 0), of which only the bytes at offsets inside [0, span) are read: the others come out zero
+__device__ __forceinline__ uint32_t load_dword_within(const uint8_t *__restrict__ rec, int64_t p, int64_t span) {
+  if (p >= 0 && p + 4 <= span) return *reinterpret_cast<const uint32_t *>(rec + p);
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (p + k >= 0 && p + k < span) v |= (uint32_t)rec[p + k] << (8 * k);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_sha256_records(const uint8_t *__restrict__ rec, size_t stride, uint32_t length, uint32_t count, uint4 *__restrict__ dig) {
+  __shared__ uint4 image[256 * kRecPitch / 16];
+  const uint64_t r0 = (uint64_t)blockIdx.x * 256, mine = r0 + threadIdx.x;  // (64 bits: count may be near 2^32)
+  const int64_t span = (int64_t)((size_t)(count - 1) * stride + length);  // the records' bytes are offsets [0, span) from rec
+  const uint32_t blocks = mf::sha256_blocks(length);
+  uint32_t h[8] = MF_SHA256_IV;
+  for (uint32_t b = 0; b < blocks; b++) {
+    if (b) __syncthreads();  // every thread has read block b - 1 out of the image
+#pragma unroll
+    for (uint32_t pass = 0; pass < 4; pass++) {
+      const uint32_t slot = pass * 256 + threadIdx.x, r = slot >> 2, u = slot & 3;
+      const uint32_t off = 64 * b + 16 * u;  // of the unit in its record (length <= 2^20)
+      if (r0 + r < count && off < length) {
+        const int64_t a = (int64_t)((size_t)(r0 + r) * stride + off), end = a + min(16u, length - off);
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(rec) + (uint64_t)a) & 3;
+        const int64_t p = a - sh;
+        uint32_t d[5];
+        if (p >= 0 && p + 20 <= span) {
+          __builtin_memcpy(d, reinterpret_cast<const uint32_t *>(rec + p), 16);
+          d[4] = reinterpret_cast<const uint32_t *>(rec + p)[4];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 5; k++) d[k] = p + 4 * k < end ? load_dword_within(rec, p + 4 * k, span) : 0u;
+        }
+        image[r * (kRecPitch / 16) + u] = make_uint4(__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh),
+                                                     __builtin_amdgcn_alignbyte(d[3], d[2], sh), __builtin_amdgcn_alignbyte(d[4], d[3], sh));
+      }
+    }
+    __syncthreads();
+    const uint4 *row = image + threadIdx.x * (kRecPitch / 16);
+    const uint4 c0 = bswap4(row[0]), c1 = bswap4(row[1]), c2 = bswap4(row[2]), c3 = bswap4(row[3]);  // (units past the record's end: stale, masked below)
+    uint32_t w[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+#pragma unroll
+    for (uint32_t t = 0; t < 16; t++) w[t] = mf::sha256_pad_word(w[t], length, b, t);
+    mf::sha256_compress(h, w);
+  }
+  if (mine < count) {
+    dig[2 * (size_t)mine] = bswap4(make_uint4(h[0], h[1], h[2], h[3]));
+    dig[2 * (size_t)mine + 1] = bswap4(make_uint4(h[4], h[5], h[6], h[7]));
+  }
+}
+
 }  // namespace
 
 struct mfh_merkle {
@@ -74,6 +149,26 @@ namespace {
 int fail(mfh_ctx *c, const char *who, const char *what) {
   c->err = std::string(who) + ": " + what;
   return MFH_EINVAL;
+}
+
+constexpr uint32_t kMaxRecordLength = 1u << 20;
+
+// what mfh_sha256_records and mfh_merkle_set_records ask of their records; 0 when they are fine
+const char *records_refused(const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count) {
+  if (length > kMaxRecordLength) return "length above 2^20 bytes";
+  if (stride < length) return "stride shorter than length";
+  if (count && length && !d_records) return "records without d_records";
+  return nullptr;
+}
+
+// digests of records [0, count) to d_digests (16-byte aligned), one launch on the context's stream; count > 0
+int sha256_records(mfh_ctx *c, const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count, uint8_t *d_digests) {
+  {
+    Timer tm(c, 27, count);  // "sha256_records" (mfhip.hip: timing_kind)
+    hipLaunchKernelGGL(k_sha256_records, dim3((uint32_t)(((uint64_t)count + 255) / 256)), dim3(256), 0, c->stream, d_records, stride, length, count, reinterpret_cast<uint4 *>(d_digests));
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
 }
 
 // the ancestors of leaves [first, first + count), level by level on the context's stream
@@ -138,6 +233,28 @@ int mfh_merkle_set_leaves(mfh_ctx *c, mfh_merkle *t, uint32_t first, uint32_t co
   if (!d_leaves) return fail(c, "mfh_merkle_set_leaves", "leaves without d_leaves");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemcpyAsync(t->level(0) + (size_t)32 * first, d_leaves, (size_t)32 * count, hipMemcpyDeviceToDevice, c->stream));
+  return merkle_update(c, t, first, count);
+}
+
+int mfh_sha256_records(mfh_ctx *c, const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count, uint8_t *d_digests) {
+  if (!c) return MFH_EINVAL;
+  if (const char *what = records_refused(d_records, stride, length, count)) return fail(c, "mfh_sha256_records", what);
+  if (count && !d_digests) return fail(c, "mfh_sha256_records", "records without d_digests");
+  if (reinterpret_cast<uintptr_t>(d_digests) & 15) return fail(c, "mfh_sha256_records", "d_digests is not 16-byte aligned");
+  if (!count) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return sha256_records(c, d_records, stride, length, count, d_digests);
+}
+
+int mfh_merkle_set_records(mfh_ctx *c, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_records, size_t stride, uint32_t length) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, "mfh_merkle_set_records", "the tree is null");
+  if (t->device != c->device) return fail(c, "mfh_merkle_set_records", "the tree belongs to another device");
+  if ((uint64_t)first + count > (1ull << t->depth)) return fail(c, "mfh_merkle_set_records", "first + count exceeds the 2^depth leaves");
+  if (const char *what = records_refused(d_records, stride, length, count)) return fail(c, "mfh_merkle_set_records", what);
+  if (!count) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = sha256_records(c, d_records, stride, length, count, t->level(0) + (size_t)32 * first)) return rc;  // straight into the leaves
   return merkle_update(c, t, first, count);
 }
 

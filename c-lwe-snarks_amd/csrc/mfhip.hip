@@ -1140,6 +1140,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "ssp_rows_violations")) return 24;  // k_rows_violations of mfh_ssp_rows_violations (ssp_rows.hip); rows = rows x statements
   if (!strcmp(which, "merkle_level")) return 25;  // k_merkle_level (merkle.hip): one per level of a build or update; rows = parents computed
   if (!strcmp(which, "merkle_paths")) return 26;  // k_merkle_paths of mfh_merkle_paths; rows = statements
+  if (!strcmp(which, "sha256_records")) return 27;  // k_sha256_records of mfh_sha256_records / mfh_merkle_set_records (merkle.hip); rows = records
   return -1;
 }
 

@@ -1,4 +1,4 @@
-// sha256_dev.hpp -- one SHA-256 compression (FIPS 180-4 6.2.2) for the Merkle kernels of merkle.hip.
+// sha256_dev.hpp -- one SHA-256 compression (FIPS 180-4 6.2.2) and the padded blocks of a whole message (5.1.1) for the kernels of merkle.hip.
 //
 // sha256_compress is host and device code: a plain C++ compiler takes this header as it stands (tests/sha256_host_check.cpp), so the rounds, the
 // message schedule and the constants are checked on a CPU.  The device pass writes the rotations as v_alignbit_b32 and the three-input Boolean
@@ -79,6 +79,40 @@ MF_SHA_HD void sha256_compress(uint32_t state[8], uint32_t w[16]) {
   MF_SHA_8(56, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u);
 #undef MF_SHA_W
   state[0] += a; state[1] += b; state[2] += c; state[3] += d; state[4] += e; state[5] += f; state[6] += g; state[7] += h;
+}
+
+// ---- whole messages: the padded blocks of FIPS 180-4 5.1.1 (message, 0x80, zeros, the bit length as 8 big-endian bytes), one word at a time.  Host and
+// device code like sha256_compress; tests/sha256_records_host_check.cpp runs the host pass on exact-fit heap messages under ASan, which is the bound on
+// what sha256_block_word reads.  length < 2^32 bytes (the kernel of merkle.hip takes at most 2^20).
+
+// the number of 64-byte blocks of a padded `length`-byte message
+MF_SHA_HD uint32_t sha256_blocks(uint32_t length) { return (uint32_t)(((uint64_t)length + 9 + 63) / 64); }
+
+// word t of padded block b, given `data` = the big-endian word of the four bytes at message offset 64 b + 4 t: the bytes of `data` at offsets >= length
+// are ignored (whatever they hold), so the padding comes from `length` alone
+MF_SHA_HD uint32_t sha256_pad_word(uint32_t data, uint32_t length, uint32_t b, uint32_t t) {
+  const uint64_t off = (uint64_t)64 * b + 4 * t;
+  uint32_t v = 0;
+  if (off + 4 <= length) {
+    v = data;
+  } else if (off <= length) {  // k = 0 .. 3 message bytes, then 0x80
+    const uint32_t k = (uint32_t)(length - off);
+    v = (k ? data & (0xFFFFFFFFu << (32 - 8 * k)) : 0u) | (0x80u << (24 - 8 * k));
+  }
+  if (b + 1 == sha256_blocks(length)) {  // the last block ends with the bit length; 0x80 lies before its word 14
+    if (t == 14) v |= length >> 29;
+    if (t == 15) v |= length << 3;
+  }
+  return v;
+}
+
+// word t of padded block b of the `length`-byte message at msg: reads no byte outside [msg, msg + length)
+MF_SHA_HD uint32_t sha256_block_word(const uint8_t *msg, uint32_t length, uint32_t b, uint32_t t) {
+  const uint64_t off = (uint64_t)64 * b + 4 * t;
+  uint32_t data = 0;
+  for (uint32_t k = 0; k < 4; k++)
+    if (off + k < length) data |= (uint32_t)msg[off + k] << (24 - 8 * k);
+  return sha256_pad_word(data, length, b, t);
 }
 
 #undef MF_SHA_8

@@ -34,6 +34,9 @@ Whole statements built from that compression, the result 256 computed public out
     MerklePath(depth)       "I know a leaf and a path of `depth` siblings to this root", parent = compress(IV, left || right) (one compression, no
                             padding block).  28 625 depth + 514 wires, 50 865 depth + 772 rows: depth 1 -> (29 139, 51 637), 2 -> (57 764, 102 502),
                             3 -> (86 389, 153 367); depth 20 -> (573 014, 1 018 072) fits d = 2^20 (m = 699 050) and the device-memory kernel.
+    MerkleRecord(length, depth)   "I know a `length`-byte record and a path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with this
+                            root": Sha256Message's chain into MerklePath's levels.  Sha256Message(length)'s sizes plus 28 625 depth wires and 50 865 depth
+                            rows: (55, 1) -> (56 667, 100 381); at d = 2^20 (m = 699 050) records up to 55 bytes reach depth 19, up to 119 bytes depth 18.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
@@ -386,6 +389,47 @@ def _digest_from_row(witness_row, at: int) -> bytes:
     return b"".join(v.to_bytes(4, "big") for v in unpack(bits))
 
 
+def _message_chain(w: Words, message, length: int):
+    """(the eight words of SHA-256 of the `length`-byte message whose 8 * length bit wires are `message`, the number of blocks): the padding of FIPS 180-4
+    5.1.1 as constant wires, the compressions (sha256_compress_sum) chained from the constant SHA256_IV -- the body of Sha256Message and MerkleRecord"""
+    tail = sha256_pad(bytes(length))[length:]  # the padding depends on the length alone
+    blocks = (length + len(tail)) // 64
+
+    def byte(k):  # the 8 wires of padded byte k, LSB first
+        if k < length:
+            return message[8 * k: 8 * k + 8]
+        return [w.c.const((tail[k - length] >> b) & 1) for b in range(8)]
+
+    h = [w.const(v) for v in SHA256_IV]
+    for blk in range(blocks):
+        # big-endian words: bit i of word t is bit i % 8 of byte 4 t + 3 - i // 8
+        M = [tuple(byte(64 * blk + 4 * t + 3 - i // 8)[i % 8] for i in range(32)) for t in range(16)]
+        h = sha256_compress_sum(w, h, M)
+    return h, blocks
+
+
+def _merkle_levels(w: Words, cur, siblings, dirs):
+    """the eight words of the root above the node `cur` (8 words): per level a conditional swap, four gates a bit -- t = AND(dir, XOR(cur, sib)),
+    L = XOR(cur, t), R = XOR(sib, t) -- then parent = sha256_compress_sum(IV, L || R) -- the body of MerklePath and MerkleRecord"""
+    iv = [w.const(v) for v in SHA256_IV]
+    for sib, d in zip(siblings, dirs):
+        left, right = [], []
+        for x, y in zip(cur, sib):
+            t = tuple(w.c.AND(d, a) for a in w.xor(x, y))
+            left.append(w.xor(x, t))
+            right.append(w.xor(y, t))
+        cur = sha256_compress_sum(w, iv, left + right)
+    return cur
+
+
+def _statement_of(digest: bytes, who: str) -> bytes:
+    """the 32 statement bytes (bits [0, 256) of a witness row) of eight computed words whose big-endian bytes are `digest`: each word's 4 bytes reversed"""
+    digest = bytes(digest)
+    if len(digest) != 32:
+        raise CircuitError(f"{who} is 32 bytes")
+    return b"".join(digest[i: i + 4][::-1] for i in range(0, 32, 4))
+
+
 class Sha256Message:
     """The statement "I know a `length`-byte message whose SHA-256 digest is this value".
 
@@ -401,19 +445,7 @@ class Sha256Message:
         self.length = length = int(length)
         self.w = w = Words()
         self.message = w.c.private(8 * length)
-        tail = sha256_pad(bytes(length))[length:]  # the padding depends on the length alone
-        self.blocks = (length + len(tail)) // 64
-
-        def byte(k):  # the 8 wires of padded byte k, LSB first
-            if k < length:
-                return self.message[8 * k: 8 * k + 8]
-            return [w.c.const((tail[k - length] >> b) & 1) for b in range(8)]
-
-        h = [w.const(v) for v in SHA256_IV]
-        for blk in range(self.blocks):
-            # big-endian words: bit i of word t is bit i % 8 of byte 4 t + 3 - i // 8
-            M = [tuple(byte(64 * blk + 4 * t + 3 - i // 8)[i % 8] for i in range(32)) for t in range(16)]
-            h = sha256_compress_sum(w, h, M)
+        h, self.blocks = _message_chain(w, self.message, length)
         self.out = h
         self.digest = [w.output(x) for x in h]
 
@@ -436,6 +468,13 @@ class Sha256Message:
         """the 32 bytes of the computed digest, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
         return _digest_from_row(witness_row, 0)
 
+    @staticmethod
+    def statement(digest: bytes) -> bytes:
+        """the 32 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the digest is `digest`": each word's 4 bytes reversed,
+        the inverse of digest_of, as MerklePath.statement -- a verifier checks a proof against a digest it knows (one of Context.sha256_records, say)
+        without a witness row"""
+        return _statement_of(digest, "Sha256Message: the digest")
+
 
 class MerklePath:
     """The statement "I know a leaf and an authentication path of `depth` siblings to this root".
@@ -456,16 +495,7 @@ class MerklePath:
         self.leaf = w.private(8)
         self.siblings = [w.private(8) for _ in range(depth)]
         self.dirs = w.c.private(depth)
-        iv = [w.const(v) for v in SHA256_IV]
-        cur = self.leaf
-        for sib, d in zip(self.siblings, self.dirs):
-            left, right = [], []
-            for x, y in zip(cur, sib):
-                t = tuple(w.c.AND(d, a) for a in w.xor(x, y))
-                left.append(w.xor(x, t))
-                right.append(w.xor(y, t))
-            cur = sha256_compress_sum(w, iv, left + right)
-        self.out = cur
+        self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
         self.root = [w.output(x) for x in cur]
 
     @property
@@ -495,10 +525,65 @@ class MerklePath:
     def statement(root: bytes) -> bytes:
         """the 32 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the root is `root`": each word's 4 bytes reversed, the
         inverse of root_of -- a verifier checks a proof against a root it knows without a witness row"""
-        root = bytes(root)
-        if len(root) != 32:
-            raise CircuitError("MerklePath: the root is 32 bytes")
-        return b"".join(root[i: i + 4][::-1] for i in range(0, 32, 4))
+        return _statement_of(root, "MerklePath: the root")
+
+
+class MerkleRecord:
+    """The statement "I know a `length`-byte record and an authentication path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with
+    this root": Sha256Message's block chain over the private record bits (the padding constant wires, part of the statement), its eight output words
+    fed, in place of MerklePath's private leaf, into MerklePath's levels (the same conditional swap and parent = compress(IV, left || right)).  It ties a
+    membership proof to the data: the tree is the one Context.merkle_tree keeps, its leaves made by MerkleTree.set_records.
+    Private inputs, in this order: the 8 * length record bits, byte k's bit b (LSB first) at 8 k + b; `depth` siblings of 8 words each (big-endian words
+    of their 32 bytes), from the leaf's level up; `depth` direction bits, bit l of the leaf's index.  The root is 256 computed public outputs (lu = 256),
+    and statement(root) is MerklePath.statement's bytes.  MerkleTree.record_rows / record_bits give the input rows for records of a device tree.
+    Sizes (MERKLE_RECORD_SIZES): exactly those of Sha256Message(length) plus 28 625 depth wires and 50 865 depth rows.  At Params(d=1 << 20, m=699050)
+    records of up to 55 bytes (one block) reach depth 19 (571 917 wires, 1 015 951 rows) and records of up to 119 bytes (two blocks) depth 18 (571 148
+    wires, 1 014 158 rows); (55, 20) does not fit: 1 066 816 rows."""
+
+    def __init__(self, length: int, depth: int):
+        if not isinstance(length, (int, np.integer)) or length < 0:
+            raise CircuitError("MerkleRecord: the length is a non-negative number of bytes")
+        if not isinstance(depth, (int, np.integer)) or depth < 1:
+            raise CircuitError("MerkleRecord: the depth is at least 1")
+        self.length, self.depth = length, depth = int(length), int(depth)
+        self.w = w = Words()
+        self.record = w.c.private(8 * length)
+        self.siblings = [w.private(8) for _ in range(depth)]
+        self.dirs = w.c.private(depth)
+        self.leaf, self.blocks = _message_chain(w, self.record, length)
+        self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
+        self.root = [w.output(x) for x in cur]
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 256
+
+    def bits(self, record: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 256 zeros where the root is computed, the record's bits, the siblings from the leaf's level
+        up, then the direction bits = the bits of the leaf's index, least significant first"""
+        record, siblings = bytes(record), [bytes(s) for s in siblings]
+        if len(record) != self.length:
+            raise CircuitError(f"MerkleRecord: the record is {self.length} bytes")
+        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+            raise CircuitError(f"MerkleRecord: {self.depth} siblings of 32 bytes")
+        if not 0 <= index < 1 << self.depth:
+            raise CircuitError(f"MerkleRecord: the index is in [0, 2^{self.depth})")
+        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
+        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(record, dtype=np.uint8), bitorder="little"),
+                               pack(be_words(b"".join(siblings))), dirs])
+
+    def root_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0)
+
+    @staticmethod
+    def statement(root: bytes) -> bytes:
+        """the 32 statement bytes that say "the root is `root`": MerklePath.statement's"""
+        return _statement_of(root, "MerkleRecord: the root")
 
 
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
@@ -507,3 +592,6 @@ class MerklePath:
 SHA256_MESSAGE_SIZES = {0: (27588, 49062), 55: (28042, 49516), 56: (55382, 98072), 100: (55746, 98436), 119: (55898, 98588), 120: (83238, 147144)}
 # ... and of MerklePath by depth: 28 625 depth + 514 wires, 50 865 depth + 772 rows
 MERKLE_PATH_SIZES = {1: (29139, 51637), 2: (57764, 102502), 3: (86389, 153367), 20: (573014, 1018072)}
+# ... and of MerkleRecord by (length, depth): those of Sha256Message(length) plus 28 625 depth wires and 50 865 depth rows
+MERKLE_RECORD_SIZES = {(0, 1): (56213, 99927), (55, 1): (56667, 100381), (56, 1): (84007, 148937), (119, 1): (84523, 149453), (120, 1): (111863, 198009),
+                       (3, 2): (84865, 150819), (55, 2): (85292, 151246), (56, 2): (112632, 199802), (55, 19): (571917, 1015951), (119, 18): (571148, 1014158)}

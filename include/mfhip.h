@@ -351,6 +351,22 @@ int mfh_merkle_root(mfh_ctx *ctx, const mfh_merkle *t, uint8_t h_root[32]);
 int mfh_merkle_nodes(const mfh_merkle *t, uint32_t level, const uint8_t **d_nodes);
 int mfh_merkle_paths(mfh_ctx *ctx, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint8_t *h_inputs, size_t in_stride);
 
+/* ---- SHA-256 of whole records (merkle.hip: k_sha256_records): the leaves of a tree from the data they stand for --------------------------------
+ * A record is `length` bytes ON THE DEVICE at d_records + r * stride, stride >= length, any byte alignment of d_records and of stride; length <= 2^20.
+ * Its digest is SHA-256 of exactly those bytes with the padding of FIPS 180-4 5.1.1 (0x80, zeros, the 64-bit big-endian bit length), which is made
+ * from `length` alone and never read: what hashlib.sha256(record).digest() gives and what words.Sha256Message(length) states.  Nothing outside
+ * [d_records, d_records + (count - 1) * stride + length) is read; a byte of a gap between two records may be read and enters no digest.
+ *   sha256_records   d_digests[32 r, 32 r + 32) <- the digest of record r, r < count; d_digests is 16-byte aligned device memory of 32 count bytes.
+ *   set_records      leaves [first, first + count) of the tree <- the digests of the records, hashed straight into the tree's leaves (no buffer in
+ *                    between); then their ancestors are recomputed as by mfh_merkle_set_leaves (one launch of k_merkle_level per level).
+ * Both are queue-only on the context's stream (no host wait): d_records must stay valid until the stream has passed the call.  count = 0 does nothing.
+ * One launch of k_sha256_records, one thread per record.  The range arithmetic is done in 64 bits.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued or written: a null tree; a null d_digests, or a null d_records
+ * with length > 0 (count > 0); stride < length; length > 2^20; first + count > 2^depth; a tree of another device; d_digests not 16-byte aligned.
+ * Kernel timing kind: "sha256_records" (total_rows = records, one count per launch). */
+int mfh_sha256_records(mfh_ctx *ctx, const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count, uint8_t *d_digests);
+int mfh_merkle_set_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_records, size_t stride, uint32_t length);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
@@ -611,7 +627,7 @@ int mfh_eval_rows_multi(mfh_ctx *ctx, uint64_t off, size_t nrows, const uint8_t 
 /* Kernel timing for the roofline leg of bench.py.  With timing enabled every launch of a hot kernel is bracketed by
  * HIP events on the context's stream (no synchronisation is added).  mfh_timing_drain waits for the stream, then
  * reports and forgets the launches of kind `which`: "eval2" / "eval1" (k_eval with 2 / 1 coefficient vectors),
- * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs), "ssp_rows_violations" (k_rows_violations of mfh_ssp_rows_violations; total_rows = rows x statements), "merkle_level" / "merkle_paths" (k_merkle_level / k_merkle_paths of the Merkle tree calls; total_rows = parents computed / statements).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
+ * "eval" (both), "encrypt", "keystream", "expand", "mac2" / "mac1" (resident MAC), "evalmm" / "evalmm_resident" (mfh_eval_rows_multi from the seed / from the image), "mmstream_rounds" (those of "evalmm_resident" that serve several groups of a batch: the S / AS rounds of mfh_prove_batch; drain it first), "mmstream_bw" (b_w of several super-groups in one launch), "mmstream_rounds_persistent" / "mmstream_bw_persistent" (those of the two that ran the persistent one-workgroup-per-CU grid; drain them before their supersets), "expandmm" (mfh_crs_expand_mm, one launch per region), "ssp_interp" (the gather launches of mfh_ssp_from_rows; total_rows = nonzeros), "circuit_assign" (k_circuit_eval of mfh_circuit_assign; total_rows = statements), "circuit_assign_global" (k_circuit_eval_global of mfh_circuit_assign on a mfh_circuit_create_global program; total_rows = statements), "circuit_assign_ex" / "circuit_assign_global_ex" (k_circuit_eval_ex / k_circuit_eval_global_ex: mfh_circuit_create_ex programs of either kind; total_rows = statements), "circuit_assign_out" / "circuit_assign_global_out" (the same for mfh_circuit_create_out programs with outputs), "circuit_assign_sum" / "circuit_assign_global_sum" (k_circuit_eval<true, OUT, true> / k_circuit_eval_global<true, OUT, true>: mfh_circuit_create_sum programs with a WSUM gate, with or without outputs), "ssp_rows_violations" (k_rows_violations of mfh_ssp_rows_violations; total_rows = rows x statements), "merkle_level" / "merkle_paths" (k_merkle_level / k_merkle_paths of the Merkle tree calls; total_rows = parents computed / statements).  "sha256_records" (k_sha256_records of mfh_sha256_records and mfh_merkle_set_records; total_rows = records).  total_rows = rows handed to those launches (AES blocks for "keystream"). */
 int mfh_set_timing(mfh_ctx *ctx, int enabled);
 /* prover scheduling: mfh_prove* run the witness pass + polynomial step on an internal stream beside the evaluation of
  * b_w's rows and join before the S / AS regions; results are identical in every mode.  0 = one stream, 1 (default) = two
