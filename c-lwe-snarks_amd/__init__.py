@@ -101,7 +101,7 @@ EXPORTS = [
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
-    "mfh_sha256_records", "mfh_merkle_set_records",
+    "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows",
 ]
 
 
@@ -237,6 +237,7 @@ def load_library():
         "mfh_merkle_paths": (i32, [vp, vp, u32, vp, vp, sz]),
         "mfh_sha256_records": (i32, [vp, vp, sz, u32, u32, vp]),
         "mfh_merkle_set_records": (i32, [vp, vp, u32, u32, vp, sz, u32]),
+        "mfh_merkle_update_rows": (i32, [vp, vp, u32, vp, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -424,6 +425,46 @@ class MerkleTree:
     def path_bits(self, indices):
         """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerklePath(depth)"""
         return np.unpackbits(self.path_rows(indices), axis=1, bitorder="little")[:, : self.nin]
+
+    def update_rows(self, indices, new_leaves, roots=False):
+        """n sequential one-leaf updates, leaf indices[k] <- new_leaves[k] in order (mfh_merkle_update_rows: depth + 1 launches for the batch; waits for the
+        stream).  Returns np.uint8 [n, 128 + 32 depth + ceil(depth / 8)]: row k is the packed input row of words.MerkleUpdate(depth) taken from the tree
+        as it stood before update k -- indices may repeat, and update k sees what updates 0 .. k - 1 did.  With roots=True a pair whose second element
+        is np.uint8 [n + 1, 32], the roots R_0 .. R_n: statement k is MerkleUpdate.statement(R_k, R_k+1).
+        new_leaves: bytes-like of 32 n bytes, a numpy uint8 [n, 32], or a torch uint8 tensor on the context's device (contiguous; copied when it is not
+        16-byte aligned), read when the context's stream reaches the call -- the digests Context.sha256_records returns feed straight in."""
+        c = self._ctx
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise MfhError("update_rows: indices are in [0, 2^depth)")
+        idx = idx.astype(np.uint32)
+        if isinstance(new_leaves, c.torch.Tensor):
+            t = new_leaves
+            if t.dtype != c.torch.uint8 or t.device != c.device or not t.is_contiguous():
+                raise MfhError("update_rows: a device tensor of leaves is contiguous uint8 on the context's device")
+            if t.data_ptr() & 15:
+                t = t.clone()  # (a fresh allocation: aligned; queued on torch's current stream, the context's)
+        else:
+            a = np.frombuffer(new_leaves, dtype=np.uint8) if isinstance(new_leaves, (bytes, bytearray, memoryview)) else np.asarray(new_leaves)
+            if a.dtype != np.uint8:
+                raise MfhError("update_rows: leaves are bytes or uint8")
+            t = c.to_device(a)
+        if t.numel() != 32 * len(idx):
+            raise MfhError("update_rows: one leaf of 32 bytes per index")
+        rows = np.zeros((len(idx), 128 + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
+        r = np.zeros((len(idx) + 1, 32), dtype=np.uint8) if roots else None
+        c._chk(c.lib.mfh_merkle_update_rows(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(t) if len(idx) else None,
+                                            ctypes.c_void_p(rows.ctypes.data), rows.shape[1], ctypes.c_void_p(r.ctypes.data) if roots else None))
+        self._keep = []
+        if roots and not len(idx):
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        return (rows, r) if roots else rows
+
+    def update_bits(self, indices, new_leaves, roots=False):
+        """update_rows as np.uint8 [n, 1024 + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerkleUpdate(depth)"""
+        out = self.update_rows(indices, new_leaves, roots)
+        bits = np.unpackbits(out[0] if roots else out, axis=1, bitorder="little")[:, : 1024 + 257 * self.depth]
+        return (bits, out[1]) if roots else bits
 
 
 class Context:

@@ -15,9 +15,12 @@
 // ceil(depth / 8) bytes of the index i, whose bit l is direction bit l.
 // k_sha256_records: SHA-256 of whole records, one thread per record, for mfh_sha256_records and mfh_merkle_set_records, which hashes records straight
 // into the leaves (its load plan and LDS image: above the kernel).
+// k_merkle_update_level, k_merkle_update_store: a batch of sequential one-leaf updates in depth + 1 launches, every update's words.MerkleUpdate input row
+// written on the way (mfh_merkle_update_rows; the recurrence: above the kernels, the host's schedule: merkle_sched.hpp).
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "merkle_sched.hpp"
 #include "sha256_dev.hpp"
 
 namespace {
@@ -133,6 +136,66 @@ __global__ __launch_bounds__(256) void k_sha256_records(const uint8_t *__restric
     dig[2 * (size_t)mine + 1] = bswap4(make_uint4(h[4], h[5], h[6], h[7]));
   }
 }
+
+// ---- mfh_merkle_update_rows: a batch of n sequential one-leaf updates, level by level.  V[l][k] = the value of node idx[k] >> l right after update k:
+// V[0] is the caller's new leaves, read in place; V[l], l = 1 .. depth, is slot l - 1 of the scratch `v` (n_cap nodes a slot).  All as 16-byte units,
+// node k of a slot = units 2k, 2k + 1, in digest byte order like the tree's nodes.
+//
+// k_merkle_update_level, one launch per level l = 0 .. depth - 1, one thread per update k: the sibling is V[l][sib[k]] when an earlier update of the batch
+// touched that node (merkle_sched.hpp), else the tree's stored node; it goes into the row as words, and V[l + 1][k] = compress(IV, left || right).  Level
+// 0 also writes the head of the row: 64 zero bytes, the old leaf (V[0][same0[k]] or the stored leaf), the new leaf, and the index behind the siblings.
+// The launch writes nothing it or a concurrent thread reads: the tree is not touched, V[l + 1] is the next launch's input.
+// Row k: units [0, 4) zero, 4-5 the old leaf, 6-7 the new leaf, 8 + 2 l and 9 + 2 l the sibling of level l, 8 + 2 depth the index (one unit: the row's
+// stride is its bytes rounded up to 16, which is at least 13 bytes more than the index's).
+__global__ __launch_bounds__(256) void k_merkle_update_level(const uint4 *__restrict__ nodes, uint32_t depth, uint32_t l, uint32_t n,
+                                                             const uint32_t *__restrict__ idx, const int32_t *__restrict__ sib,
+                                                             const int32_t *__restrict__ same0, const uint4 *__restrict__ cur, uint4 *__restrict__ next,
+                                                             uint4 *__restrict__ rows, uint32_t stride_units) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t i = idx[k], node = i >> l;
+  const size_t heap = ((size_t)1 << (depth - l)) + node;
+  const int32_t js = sib[k];
+  const uint4 *sp = js >= 0 ? cur + 2 * (size_t)js : nodes + 2 * (heap ^ 1);
+  const uint4 a0 = bswap4(cur[2 * (size_t)k]), a1 = bswap4(cur[2 * (size_t)k + 1]), s0 = bswap4(sp[0]), s1 = bswap4(sp[1]);
+  uint4 *row = rows + (size_t)k * stride_units;
+  if (l == 0) {
+    const int32_t jo = same0[k];
+    const uint4 *op = jo >= 0 ? cur + 2 * (size_t)jo : nodes + 2 * heap;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    row[0] = zero; row[1] = zero; row[2] = zero; row[3] = zero;
+    row[4] = bswap4(op[0]);
+    row[5] = bswap4(op[1]);
+    row[6] = a0;
+    row[7] = a1;
+    row[8 + 2 * depth] = make_uint4(i, 0, 0, 0);
+  }
+  row[8 + 2 * l] = s0;
+  row[9 + 2 * l] = s1;
+  const bool right = node & 1;  // this node is the right child: the sibling goes first
+  const uint4 c0 = right ? s0 : a0, c1 = right ? s1 : a1, c2 = right ? a0 : s0, c3 = right ? a1 : s1;
+  uint32_t w[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+  uint32_t h[8] = MF_SHA256_IV;
+  mf::sha256_compress(h, w);
+  next[2 * (size_t)k] = bswap4(make_uint4(h[0], h[1], h[2], h[3]));
+  next[2 * (size_t)k + 1] = bswap4(make_uint4(h[4], h[5], h[6], h[7]));
+}
+
+// k_merkle_update_store, ONE launch behind the levels, one thread per update and level l = blockIdx.y <= depth: where update k is the last of the batch at
+// node idx[k] >> l (bit l of last[k]), the tree's node <- V[l][k].  Every read of the stored nodes is over by then, and a node has one last update: no
+// two threads write the same node.
+__global__ __launch_bounds__(256) void k_merkle_update_store(uint4 *__restrict__ nodes, uint32_t depth, uint32_t n, const uint32_t *__restrict__ idx,
+                                                             const uint32_t *__restrict__ last, const uint4 *__restrict__ leaves,
+                                                             const uint4 *__restrict__ v, size_t slot_units) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (k >= n || !((last[k] >> l) & 1)) return;
+  const uint4 *src = (l ? v + (size_t)(l - 1) * slot_units : leaves) + 2 * (size_t)k;
+  const size_t heap = ((size_t)1 << (depth - l)) + (idx[k] >> l);
+  nodes[2 * heap] = src[0];
+  nodes[2 * heap + 1] = src[1];
+}
+
+inline size_t update_row_bytes(uint32_t depth) { return 128 + (size_t)32 * depth + (depth + 7) / 8; }
 
 }  // namespace
 
@@ -316,6 +379,65 @@ int mfh_merkle_paths(mfh_ctx *c, const mfh_merkle *t, uint32_t nstmt, const uint
     HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
+  }
+  return MFH_OK;
+}
+
+int mfh_merkle_update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_inputs, size_t in_stride,
+                           uint8_t *h_roots) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, "mfh_merkle_update_rows", "the tree is null");
+  if (t->device != c->device) return fail(c, "mfh_merkle_update_rows", "the tree belongs to another device");
+  const uint32_t depth = t->depth;
+  const size_t rowb = update_row_bytes(depth);
+  if (in_stride < rowb) return fail(c, "mfh_merkle_update_rows", "in_stride shorter than the row's 128 + 32 depth + ceil(depth / 8) bytes");
+  if (nupd && !h_index) return fail(c, "mfh_merkle_update_rows", "updates without h_index");
+  if (nupd && !d_new_leaves) return fail(c, "mfh_merkle_update_rows", "updates without d_new_leaves");
+  if (nupd && !h_inputs) return fail(c, "mfh_merkle_update_rows", "updates without h_inputs");
+  if (reinterpret_cast<uintptr_t>(d_new_leaves) & 15) return fail(c, "mfh_merkle_update_rows", "d_new_leaves is not 16-byte aligned");
+  for (uint32_t k = 0; k < nupd; k++)
+    if (h_index[k] >> depth) return fail(c, "mfh_merkle_update_rows", "an index is not below 2^depth");
+  if (!nupd) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // a chunk: the most updates whose rows fit kPathStageBytes, as mfh_merkle_paths counts it.  On the device, in the scratch of mfh_circuit_assign (these are
+  // its input rows): V[1 .. depth] (depth slots of ch nodes) | rows at a stride of 16 bytes' multiple | the schedule (idx | last | same0 | sib[depth])
+  const size_t rs = (rowb + 15) & ~(size_t)15;
+  const uint32_t ch = (uint32_t)std::min<size_t>(nupd, std::max<size_t>(1, kPathStageBytes / rowb));
+  const size_t slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
+  if (int rc = work_reserve(c, c->circ_io, depth * slot + (size_t)ch * rs + sched_words * 4)) return rc;
+  uint4 *d_v = c->circ_io.as<uint4>(), *d_rows = d_v + depth * slot / 16;
+  uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_rows + (size_t)ch * rs / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * rs + ((size_t)ch + 1) * 32);
+  if (!pin_out) return MFH_ENOMEM;
+  uint8_t *pin_roots = pin_out + (size_t)ch * rs;  // R_b0 | the chunk's new roots
+  uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
+  if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
+  for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
+    const uint32_t k = std::min(ch, nupd - b0);
+    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
+    if (!pin_sched) return MFH_ENOMEM;
+    memcpy(pin_sched, h_index + b0, (size_t)k * 4);
+    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
+    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    const uint32_t *d_idx = d_sched, *d_last = d_sched + k;
+    const int32_t *d_same0 = (const int32_t *)d_sched + 2 * (size_t)k, *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
+    const uint4 *d_leaves = reinterpret_cast<const uint4 *>(d_new_leaves + (size_t)32 * b0);
+    for (uint32_t l = 0; l < depth; l++) {
+      Timer tm(c, 28, k);  // "merkle_updates" (mfhip.hip: timing_kind): k compressions
+      hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, d_idx, d_sib + (size_t)l * k, d_same0,
+                         l ? (const uint4 *)(d_v + (size_t)(l - 1) * slot / 16) : d_leaves, d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
+    }
+    {
+      Timer tm(c, 28, 0);  // ... the write-back: no compression
+      hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, d_idx, d_last, d_leaves, (const uint4 *)d_v, slot / 16);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
+    if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
+    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
   }
   return MFH_OK;
 }

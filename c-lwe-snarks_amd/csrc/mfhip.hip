@@ -1141,6 +1141,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_level")) return 25;  // k_merkle_level (merkle.hip): one per level of a build or update; rows = parents computed
   if (!strcmp(which, "merkle_paths")) return 26;  // k_merkle_paths of mfh_merkle_paths; rows = statements
   if (!strcmp(which, "sha256_records")) return 27;  // k_sha256_records of mfh_sha256_records / mfh_merkle_set_records (merkle.hip); rows = records
+  if (!strcmp(which, "merkle_updates")) return 28;  // k_merkle_update_level / _store of mfh_merkle_update_rows: depth + 1 per chunk; rows = compressions
   return -1;
 }
 

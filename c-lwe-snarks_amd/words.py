@@ -26,7 +26,7 @@ d = 2^17 (m = 87 381), above the LDS kernel's wire limit, so its witnesses come 
 Written with sums (Sha256Compress(adds="sum")) it takes 28 114 wires and 49 588 rows (28 370 and 49 844 with a public chaining value): it fits
 d = 2^16 (m = 43 690) and the LDS kernel.
 
-Whole statements built from that compression, the result 256 computed public outputs (lu = 256) in both:
+Whole statements built from that compression, the result 256 computed public outputs (lu = 256; MerkleUpdate has two results, lu = 512):
     Sha256Message(length)   "I know a `length`-byte message with this digest": the padding of FIPS 180-4 5.1.1 is constant wires, part of the statement.
                             length -> (wires, rows): 0 -> (27 588, 49 062), 55 -> (28 042, 49 516): one block, d = 2^16 and the LDS kernel;
                             56 -> (55 382, 98 072), 100 -> (55 746, 98 436), 119 -> (55 898, 98 588): two blocks, d = 2^17 (m = 87 381);
@@ -37,6 +37,9 @@ Whole statements built from that compression, the result 256 computed public out
     MerkleRecord(length, depth)   "I know a `length`-byte record and a path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with this
                             root": Sha256Message's chain into MerklePath's levels.  Sha256Message(length)'s sizes plus 28 625 depth wires and 50 865 depth
                             rows: (55, 1) -> (56 667, 100 381); at d = 2^20 (m = 699 050) records up to 55 bytes reach depth 19, up to 119 bytes depth 18.
+    MerkleUpdate(depth)     "I know an old leaf, a new leaf and a path of `depth` siblings that takes the old leaf to old_root and the new leaf to
+                            new_root" (lu = 512): MerklePath's levels twice over shared siblings and directions.  56 993 depth + 1 026 wires, 101 473
+                            depth + 1 540 rows: depth 1 -> (58 019, 103 013), 2 -> (115 012, 204 486); depth 10 -> (570 956, 1 016 270) fits d = 2^20.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
@@ -586,6 +589,63 @@ class MerkleRecord:
         return _statement_of(root, "MerkleRecord: the root")
 
 
+class MerkleUpdate:
+    """The statement "I know an old leaf, a new leaf, `depth` siblings and an index such that the path from the old leaf gives old_root and the SAME
+    siblings and directions from the new leaf give new_root": one leaf changed, and that change alone takes the tree from old_root to new_root.
+
+    Private inputs, in this order: the old leaf (8 words, big-endian words of its 32 bytes, as MerklePath), the new leaf (8 words), `depth` siblings of 8
+    words from the leaf's level up, `depth` direction bits (bit l of the index).  The body is MerklePath's levels (_merkle_levels) twice over the shared
+    sibling and direction wires.  Public outputs (lu = 512): the old root's 8 words at statement bits [0, 256), the new root's at [256, 512), all computed.
+    MerkleTree.update_rows / update_bits give the input rows of a batch of sequential updates of a device tree, and statement k is (R_k, R_k+1).
+    Sizes (MERKLE_UPDATE_SIZES): 56 993 depth + 1 026 wires and 101 473 depth + 1 540 rows, i.e. twice MerklePath's less the 257 wires and bit rows a level
+    that are shared (and the two shared constant wires); nwires - len(program) = 1024 + 257 depth inputs.  Depth 10 is 570 956 wires and 1 016 270 rows,
+    which fits Params(d=1 << 20, m=699050); depth 11 (1 117 743 rows) does not.  Depth 1 fits Params(d=1 << 17, m=87381), depth 2
+    Params(d=1 << 18, m=174762)."""
+
+    def __init__(self, depth: int):
+        if not isinstance(depth, (int, np.integer)) or depth < 1:
+            raise CircuitError("MerkleUpdate: the depth is at least 1")
+        self.depth = depth = int(depth)
+        self.w = w = Words()
+        self.old_leaf = w.private(8)
+        self.new_leaf = w.private(8)
+        self.siblings = [w.private(8) for _ in range(depth)]
+        self.dirs = w.c.private(depth)
+        self.out_old = _merkle_levels(w, self.old_leaf, self.siblings, self.dirs)
+        self.out_new = _merkle_levels(w, self.new_leaf, self.siblings, self.dirs)
+        self.old_root = [w.output(x) for x in self.out_old]
+        self.new_root = [w.output(x) for x in self.out_new]
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 512
+
+    def bits(self, old_leaf: bytes, new_leaf: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed, the old leaf, the new leaf, the siblings from the
+        leaf's level up, then the direction bits = the bits of the leaf's index, least significant first"""
+        siblings = [bytes(s) for s in siblings]
+        if len(old_leaf) != 32 or len(new_leaf) != 32 or len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+            raise CircuitError(f"MerkleUpdate: two 32-byte leaves and {self.depth} siblings of 32 bytes")
+        if not 0 <= index < 1 << self.depth:
+            raise CircuitError(f"MerkleUpdate: the index is in [0, 2^{self.depth})")
+        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
+        return np.concatenate([np.zeros(512, dtype=np.uint8), pack(be_words(bytes(old_leaf) + bytes(new_leaf) + b"".join(siblings))), dirs])
+
+    def roots_of(self, witness_row):
+        """(old_root, new_root), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0), _digest_from_row(witness_row, 256)
+
+    @staticmethod
+    def statement(old_root: bytes, new_root: bytes) -> bytes:
+        """the 64 statement bytes (what verify_public takes, bits [0, 512) of a witness row) that say "old_root became new_root": the inverse of
+        roots_of, each half MerklePath.statement's bytes"""
+        return _statement_of(old_root, "MerkleUpdate: the old root") + _statement_of(new_root, "MerkleUpdate: the new root")
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -595,3 +655,5 @@ MERKLE_PATH_SIZES = {1: (29139, 51637), 2: (57764, 102502), 3: (86389, 153367), 
 # ... and of MerkleRecord by (length, depth): those of Sha256Message(length) plus 28 625 depth wires and 50 865 depth rows
 MERKLE_RECORD_SIZES = {(0, 1): (56213, 99927), (55, 1): (56667, 100381), (56, 1): (84007, 148937), (119, 1): (84523, 149453), (120, 1): (111863, 198009),
                        (3, 2): (84865, 150819), (55, 2): (85292, 151246), (56, 2): (112632, 199802), (55, 19): (571917, 1015951), (119, 18): (571148, 1014158)}
+# ... and of MerkleUpdate by depth: 56 993 depth + 1 026 wires, 101 473 depth + 1 540 rows
+MERKLE_UPDATE_SIZES = {1: (58019, 103013), 2: (115012, 204486), 3: (172005, 305959), 10: (570956, 1016270)}

@@ -367,6 +367,31 @@ int mfh_merkle_paths(mfh_ctx *ctx, const mfh_merkle *t, uint32_t nstmt, const ui
 int mfh_sha256_records(mfh_ctx *ctx, const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count, uint8_t *d_digests);
 int mfh_merkle_set_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_records, size_t stride, uint32_t length);
 
+/* ---- Sequential updates of a tree as statements (merkle.hip: k_merkle_update_level, k_merkle_update_store): what words.MerkleUpdate(depth) proves --
+ * "I changed one leaf, and that change alone takes the tree from root R to root R'".  For k = 0 .. nupd - 1 IN ORDER: row k of h_inputs (in_stride bytes)
+ * becomes the packed input row of MerkleUpdate(depth) taken from the tree as it stands before update k; then leaf h_index[k] becomes
+ * d_new_leaves[32 k, 32 k + 32) (ON THE DEVICE, 16-byte aligned) and its ancestors are recomputed.  Indices may repeat, and later updates may be the
+ * siblings, cousins or the same leaf as earlier ones: update k sees everything updates 0 .. k - 1 did.  Afterwards the tree is what nupd one-leaf
+ * mfh_merkle_set_leaves calls would have left.
+ *   roots    h_roots is NULL or (nupd + 1) x 32 bytes: the roots R_0 .. R_nupd; statement k is (R_k, R_k+1), MerkleUpdate.statement's bytes.
+ *   rows     64 zero bytes where the two roots are computed; the 8 words of the old leaf; the 8 words of the new leaf; for l = 0 .. depth - 1 the 8 words
+ *            of the sibling at level l; each word a little-endian uint32 holding the word's value (mfh_merkle_paths' convention); then ceil(depth / 8)
+ *            bytes holding the index.  nin = 512 + 512 + 256 depth + depth bits; exactly 128 + 32 depth + ceil(depth / 8) bytes of a row are written,
+ *            the rest of a wider row is left alone.
+ *   how      level-synchronous, not a loop over updates: the host makes, in O(nupd log nupd + nupd depth), the tables "the last earlier update at my
+ *            leaf / at my sibling of level l" and "I am the last update at this node" (merkle_sched.hpp); then one launch of k_merkle_update_level per
+ *            level, one thread per update, computes every update's value of its node from its own value and its sibling's below -- an earlier update's
+ *            value or the tree's stored node -- and writes the sibling into the row; one launch of k_merkle_update_store then writes each touched node's
+ *            last value into the tree, after every read of the stored nodes.  depth + 1 launches per chunk of updates, a chunk being the most updates
+ *            whose rows fit 64 MiB (at least one); chunks run in order.  Rows, roots and tables are staged through the context's pinned buffers
+ *            (mfh_scrub_staging zeroes them); d_new_leaves is read in place and in stream order (it must not overlap the tree's own nodes); the call
+ *            synchronises the stream.  nupd = 0 does nothing.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued, written or changed in the tree: a null tree; a tree of another
+ * device; nupd > 0 with h_index, d_new_leaves or h_inputs null; an index >= 2^depth; in_stride below the row's bytes; d_new_leaves not 16-byte aligned.
+ * Kernel timing kind: "merkle_updates" (one count per launch: depth + 1 per chunk; total_rows = compressions, nupd x depth over the call). */
+int mfh_merkle_update_rows(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_inputs, size_t in_stride,
+                           uint8_t *h_roots);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
