@@ -101,7 +101,7 @@ EXPORTS = [
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
-    "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows",
+    "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
 ]
 
 
@@ -238,6 +238,7 @@ def load_library():
         "mfh_sha256_records": (i32, [vp, vp, sz, u32, u32, vp]),
         "mfh_merkle_set_records": (i32, [vp, vp, u32, u32, vp, sz, u32]),
         "mfh_merkle_update_rows": (i32, [vp, vp, u32, vp, vp, vp, sz, vp]),
+        "mfh_merkle_update_records": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -464,6 +465,49 @@ class MerkleTree:
         """update_rows as np.uint8 [n, 1024 + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerkleUpdate(depth)"""
         out = self.update_rows(indices, new_leaves, roots)
         bits = np.unpackbits(out[0] if roots else out, axis=1, bitorder="little")[:, : 1024 + 257 * self.depth]
+        return (bits, out[1]) if roots else bits
+
+    def update_records(self, table, indices, new_records, roots=False):
+        """n sequential one-record updates of a table of records and this tree, record indices[k] <- new_records[k] in order (mfh_merkle_update_records: one
+        hash launch, two copy launches and depth + 1 tree launches for the batch; waits for the stream).  Returns np.uint8 [n, 64 + 2 length + 32 depth +
+        ceil(depth / 8)]: row k is the packed input row of words.MerkleRecordUpdate(length, depth) taken from the table and the tree as they stood before
+        update k -- indices may repeat, and update k sees what updates 0 .. k - 1 did.  With roots=True a pair whose second element is np.uint8 [n + 1, 32],
+        the roots R_0 .. R_n: statement k is MerkleRecordUpdate.statement(R_k, R_k+1).
+        table: a torch uint8 [2^depth, length] tensor on the context's device with stride(1) == 1 and stride(0) >= length (a column slice of a wider table
+        is used in place), MODIFIED IN PLACE: afterwards it holds each touched record's last new value.  Leaf i of the tree must be SHA-256 of table[i]
+        (the state after set_records(0, table)); that is not checked, the old root circuit_assign computes from a row shows it.
+        new_records: a numpy uint8 [n, length], uploaded, or a device tensor under the table's rules, read when the context's stream reaches the call; it
+        must not overlap the table."""
+        c = self._ctx
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise MfhError("update_records: indices are in [0, 2^depth)")
+        idx = idx.astype(np.uint32)
+        if not isinstance(table, c.torch.Tensor):
+            raise MfhError("update_records: the table is a torch uint8 [2^depth, length] tensor on the context's device")
+        tab, tstride, length, nrec, _ = _records(c, table, "update_records")
+        if nrec != 1 << self.depth:
+            raise MfhError("update_records: the table has one record per leaf, 2^depth of them")
+        new, nstride, nlength, n, _ = _records(c, new_records, "update_records")
+        if n != len(idx) or nlength != length:
+            raise MfhError("update_records: one new record of the table's length per index")
+        rows = np.zeros((len(idx), 64 + 2 * length + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
+        r = np.zeros((len(idx) + 1, 32), dtype=np.uint8) if roots else None
+        c._chk(c.lib.mfh_merkle_update_records(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(tab), tstride, length,
+                                               _ptr(new) if len(idx) else None, nstride, ctypes.c_void_p(rows.ctypes.data),
+                                               rows.shape[1], ctypes.c_void_p(r.ctypes.data) if roots else None))
+        self._keep = []
+        if roots and not len(idx):
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        return (rows, r) if roots else rows
+
+    def update_record_bits(self, table, indices, new_records, roots=False):
+        """update_records as np.uint8 [n, 512 + 16 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
+        words.MerkleRecordUpdate(length, depth)"""
+        out = self.update_records(table, indices, new_records, roots)
+        rows = out[0] if roots else out
+        length = (rows.shape[1] - 64 - 32 * self.depth - (self.depth + 7) // 8) // 2
+        bits = np.unpackbits(rows, axis=1, bitorder="little")[:, : 512 + 16 * length + 257 * self.depth]
         return (bits, out[1]) if roots else bits
 
 

@@ -17,9 +17,13 @@
 // into the leaves (its load plan and LDS image: above the kernel).
 // k_merkle_update_level, k_merkle_update_store: a batch of sequential one-leaf updates in depth + 1 launches, every update's words.MerkleUpdate input row
 // written on the way (mfh_merkle_update_rows; the recurrence: above the kernels, the host's schedule: merkle_sched.hpp).
+// k_record_gather, k_record_store: the byte-granular copies of mfh_merkle_update_records, which applies a batch of sequential RECORD updates to a table of
+// records and its tree and writes every update's words.MerkleRecordUpdate input row: old and new records into the row heads before the level launches,
+// the last new record of each leaf into the table behind them (the host's splice of heads and siblings: merkle_record_row.hpp).
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "merkle_record_row.hpp"
 #include "merkle_sched.hpp"
 #include "sha256_dev.hpp"
 
@@ -95,6 +99,24 @@ __device__ __forceinline__ uint32_t load_dword_within(const uint8_t *__restrict_
   return v;
 }
 
+// the 16 bytes at rec + a (any alignment; a may be below 0), funnel-shifted out of the five dwords at and after that address rounded down to 4: all five in
+// a 16-byte and a 4-byte load when they lie inside [0, span), else dword by dword, those at or past `end` not at all (zero) and one that crosses the span's
+// head or tail from the byte loads of its bytes inside.  Nothing outside [0, span) is read; bytes of the result at or past `end` are unspecified.
+__device__ __forceinline__ uint4 load_unit_within(const uint8_t *__restrict__ rec, int64_t a, int64_t end, int64_t span) {
+  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(rec) + (uint64_t)a) & 3;
+  const int64_t p = a - sh;
+  uint32_t d[5];
+  if (p >= 0 && p + 20 <= span) {
+    __builtin_memcpy(d, reinterpret_cast<const uint32_t *>(rec + p), 16);
+    d[4] = reinterpret_cast<const uint32_t *>(rec + p)[4];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 5; k++) d[k] = p + 4 * k < end ? load_dword_within(rec, p + 4 * k, span) : 0u;
+  }
+  return make_uint4(__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh), __builtin_amdgcn_alignbyte(d[3], d[2], sh),
+                    __builtin_amdgcn_alignbyte(d[4], d[3], sh));
+}
+
 __global__ __launch_bounds__(256) void k_sha256_records(const uint8_t *__restrict__ rec, size_t stride, uint32_t length, uint32_t count, uint4 *__restrict__ dig) {
   __shared__ uint4 image[256 * kRecPitch / 16];
   const uint64_t r0 = (uint64_t)blockIdx.x * 256, mine = r0 + threadIdx.x;  // (64 bits: count may be near 2^32)
@@ -108,19 +130,8 @@ __global__ __launch_bounds__(256) void k_sha256_records(const uint8_t *__restric
       const uint32_t slot = pass * 256 + threadIdx.x, r = slot >> 2, u = slot & 3;
       const uint32_t off = 64 * b + 16 * u;  // of the unit in its record (length <= 2^20)
       if (r0 + r < count && off < length) {
-        const int64_t a = (int64_t)((size_t)(r0 + r) * stride + off), end = a + min(16u, length - off);
-        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(rec) + (uint64_t)a) & 3;
-        const int64_t p = a - sh;
-        uint32_t d[5];
-        if (p >= 0 && p + 20 <= span) {
-          __builtin_memcpy(d, reinterpret_cast<const uint32_t *>(rec + p), 16);
-          d[4] = reinterpret_cast<const uint32_t *>(rec + p)[4];
-        } else {
-#pragma unroll
-          for (int k = 0; k < 5; k++) d[k] = p + 4 * k < end ? load_dword_within(rec, p + 4 * k, span) : 0u;
-        }
-        image[r * (kRecPitch / 16) + u] = make_uint4(__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh),
-                                                     __builtin_amdgcn_alignbyte(d[3], d[2], sh), __builtin_amdgcn_alignbyte(d[4], d[3], sh));
+        const int64_t a = (int64_t)((size_t)(r0 + r) * stride + off);
+        image[r * (kRecPitch / 16) + u] = load_unit_within(rec, a, a + min(16u, length - off), span);
       }
     }
     __syncthreads();
@@ -195,7 +206,61 @@ __global__ __launch_bounds__(256) void k_merkle_update_store(uint4 *__restrict__
   nodes[2 * heap + 1] = src[1];
 }
 
-inline size_t update_row_bytes(uint32_t depth) { return 128 + (size_t)32 * depth + (depth + 7) / 8; }
+// ---- mfh_merkle_update_records: the two byte-granular copies around the level launches.  Records have any byte alignment (base and stride), so both
+// kernels load through load_unit_within: 4-byte aligned dwords, funnel-shifted.  A work item is one 16-byte unit of one record, items in record order: the
+// lanes of a wave cover consecutive units of a record (coalesced), and a record shorter than a wave's 1 024 bytes shares its wave with its neighbours.
+//
+// k_record_gather, one item per update k < n, side (0 = old, 1 = new) and unit u < ceil(length / 16): heads[k] (a slot of 2 pitch units, pitch =
+// ceil(length / 16)) <- the old record at unit 0 and the new record at unit pitch.  The new record is fresh + (first + k) * new_stride; the old one is the
+// new record of update same0[k] of this chunk when that is >= 0 (merkle_sched.hpp), else the table's record idx[k].
+// Reads: nothing outside [table, table + table_span) and [fresh, fresh + fresh_span), table_span = (2^depth - 1) * table_stride + length and fresh_span =
+// (nupd - 1) * new_stride + length over the WHOLE batch.  Writes: whole units of heads, all 16-byte aligned; the bytes of a record's last unit past
+// `length` are unspecified (the host's splice copies `length` bytes).  The table is only read: the launch is ordered before k_record_store by the stream.
+__global__ __launch_bounds__(256) void k_record_gather(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ fresh,
+                                                       size_t new_stride, int64_t fresh_span, uint32_t first, uint32_t length, uint32_t n,
+                                                       const uint32_t *__restrict__ idx, const int32_t *__restrict__ same0, uint4 *__restrict__ heads) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (n * 2 * units < 2^32: a chunk's rows fit 64 MiB, or n = 1)
+  if (g >= n * 2 * units) return;
+  const uint32_t k = g / (2 * units), r = g - k * 2 * units, side = r >= units, u = r - side * units, off = 16 * u;
+  const int32_t jo = side ? (int32_t)k : same0[k];
+  const uint8_t *src = jo >= 0 ? fresh : table;
+  const int64_t a = (int64_t)(jo >= 0 ? (size_t)(first + (uint32_t)jo) * new_stride : (size_t)idx[k] * table_stride) + off;
+  heads[((size_t)2 * k + side) * units + u] = load_unit_within(src, a, a + min(16u, length - off), jo >= 0 ? fresh_span : table_span);
+}
+
+// k_record_store, behind the levels: where update k is the last of the chunk at its leaf (bit 0 of last[k]), the table's record idx[k] <- its new record.
+// The destination has any alignment too, so the items of a record are the 16-byte windows of the DESTINATION's dword grid: with dst = the record's address
+// and a0 = dst & 3, window u holds the record's bytes [16 u - a0, 16 u - a0 + 16) cut to [0, length); u < ceil((length + 3) / 16) covers every a0.  A
+// window's four dwords are 4-byte aligned in the table: one that lies inside the record is a dword store, one across the record's head or tail is the byte
+// stores of its bytes inside.
+// Reads: nothing outside [fresh, fresh + fresh_span) (as above).  Writes: the `length` bytes of the records idx[k] with bit 0 of last[k] set and nothing
+// else -- no gap byte of a wider stride, nothing before the table or behind its last record.  One leaf has one last update: no two threads write one byte.
+__global__ __launch_bounds__(256) void k_record_store(uint8_t *__restrict__ table, size_t table_stride, const uint8_t *__restrict__ fresh, size_t new_stride,
+                                                      int64_t fresh_span, uint32_t first, uint32_t length, uint32_t n, const uint32_t *__restrict__ idx,
+                                                      const uint32_t *__restrict__ last) {
+  const uint32_t units = (length + 18) / 16, g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n * units) return;
+  const uint32_t k = g / units, u = g - k * units;
+  if (!(last[k] & 1)) return;
+  uint8_t *dst = table + (size_t)idx[k] * table_stride;
+  const int64_t s = (int64_t)16 * u - (int64_t)(reinterpret_cast<uintptr_t>(dst) & 3);  // the window's first byte, as an offset in the record
+  const int64_t hi = min(s + 16, (int64_t)length);
+  if (hi <= max(s, (int64_t)0)) return;
+  const int64_t a = (int64_t)((size_t)(first + k) * new_stride);
+  const uint4 v = load_unit_within(fresh, a + s, a + hi, fresh_span);
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int64_t o = s + 4 * j;
+    if (o >= 0 && o + 4 <= (int64_t)length) {
+      *reinterpret_cast<uint32_t *>(dst + o) = w[j];
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+        if (o + b >= 0 && o + b < (int64_t)length) dst[o + b] = (uint8_t)(w[j] >> (8 * b));
+    }
+  }
+}
 
 }  // namespace
 
@@ -389,7 +454,7 @@ int mfh_merkle_update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint3
   if (!t) return fail(c, "mfh_merkle_update_rows", "the tree is null");
   if (t->device != c->device) return fail(c, "mfh_merkle_update_rows", "the tree belongs to another device");
   const uint32_t depth = t->depth;
-  const size_t rowb = update_row_bytes(depth);
+  const size_t rowb = mf::update_row_bytes(depth);
   if (in_stride < rowb) return fail(c, "mfh_merkle_update_rows", "in_stride shorter than the row's 128 + 32 depth + ceil(depth / 8) bytes");
   if (nupd && !h_index) return fail(c, "mfh_merkle_update_rows", "updates without h_index");
   if (nupd && !d_new_leaves) return fail(c, "mfh_merkle_update_rows", "updates without d_new_leaves");
@@ -437,6 +502,85 @@ int mfh_merkle_update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint3
     if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
+    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
+  }
+  return MFH_OK;
+}
+
+int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                              const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots) {
+  const char *who = "mfh_merkle_update_records";
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, who, "the tree is null");
+  if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  const uint32_t depth = t->depth;
+  if (length > kMaxRecordLength) return fail(c, who, "length above 2^20 bytes");
+  if (table_stride < length) return fail(c, who, "table_stride shorter than length");
+  if (new_stride < length) return fail(c, who, "new_stride shorter than length");
+  const size_t rowb = mf::record_update_row_bytes(length, depth);
+  if (in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + 2 length + 32 depth + ceil(depth / 8) bytes");
+  if (nupd && !h_index) return fail(c, who, "updates without h_index");
+  if (nupd && !h_inputs) return fail(c, who, "updates without h_inputs");
+  if (nupd && !d_table) return fail(c, who, "updates without d_table");
+  if (nupd && length && !d_new_records) return fail(c, who, "updates without d_new_records");
+  for (uint32_t k = 0; k < nupd; k++)
+    if (h_index[k] >> depth) return fail(c, who, "an index is not below 2^depth");
+  if (!nupd) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // a chunk: the most updates whose rows fit kPathStageBytes.  On the device, in the scratch of mfh_circuit_assign: V[0 .. depth] (depth + 1 slots of ch
+  // nodes; V[0] = the digests of the chunk's new records) | the level rows of mfh_merkle_update_rows at their stride | the heads (merkle_record_row.hpp) | the
+  // schedule (idx | last | same0 | sib[depth])
+  const size_t lrb = mf::update_row_bytes(depth), rs = (lrb + 15) & ~(size_t)15, hs = 2 * mf::record_head_pitch(length);
+  const uint32_t ch = mf::update_chunk(nupd, rowb, kPathStageBytes);
+  const size_t slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
+  if (int rc = work_reserve(c, c->circ_io, (depth + 1) * slot + (size_t)ch * (rs + hs) + sched_words * 4)) return rc;
+  uint4 *d_leaves = c->circ_io.as<uint4>(), *d_v = d_leaves + slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
+  uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32);
+  if (!pin_out) return MFH_ENOMEM;
+  uint8_t *pin_heads = pin_out + (size_t)ch * rs, *pin_roots = pin_heads + (size_t)ch * hs;  // level rows | heads | R_b0, the chunk's new roots
+  uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
+  const int64_t table_span = (int64_t)((((size_t)1 << depth) - 1) * table_stride + length), fresh_span = (int64_t)((size_t)(nupd - 1) * new_stride + length);
+  if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
+  for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
+    const uint32_t k = std::min(ch, nupd - b0);
+    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
+    if (!pin_sched) return MFH_ENOMEM;
+    memcpy(pin_sched, h_index + b0, (size_t)k * 4);
+    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
+    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    const uint32_t *d_idx = d_sched, *d_last = d_sched + k;
+    const int32_t *d_same0 = (const int32_t *)d_sched + 2 * (size_t)k, *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
+    if (int rc = sha256_records(c, d_new_records + (size_t)b0 * new_stride, new_stride, length, k, reinterpret_cast<uint8_t *>(d_leaves))) return rc;
+    {
+      Timer tm(c, 29, k);  // "merkle_record_rows" (mfhip.hip: timing_kind): the gather
+      const uint32_t items = k * 2 * (uint32_t)(hs / 32);
+      hipLaunchKernelGGL(k_record_gather, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, table_span, d_new_records,
+                         new_stride, fresh_span, b0, length, k, d_idx, d_same0, d_heads);
+    }
+    for (uint32_t l = 0; l < depth; l++) {
+      Timer tm(c, 28, k);  // "merkle_updates": k compressions
+      hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, d_idx, d_sib + (size_t)l * k, d_same0,
+                         (const uint4 *)(d_leaves + (size_t)l * slot / 16), d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
+    }
+    {
+      Timer tm(c, 28, 0);  // ... the tree's write-back: no compression
+      hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, d_idx, d_last, (const uint4 *)d_leaves,
+                         (const uint4 *)d_v, slot / 16);
+    }
+    {
+      Timer tm(c, 29, 0);  // ... and the table's, behind the gather's reads of it
+      const uint32_t items = k * ((length + 18) / 16);
+      hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_new_records, new_stride, fresh_span, b0,
+                         length, k, d_idx, d_last);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
+    if (hs) HIP_TRY(c, hipMemcpyAsync(pin_heads, d_heads, (size_t)k * hs, hipMemcpyDeviceToHost, c->stream));
+    if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t b = 0; b < k; b++) mf::record_update_row(h_inputs + (size_t)(b0 + b) * in_stride, pin_heads + (size_t)b * hs, pin_out + (size_t)b * rs, length, depth);
     if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
   }
   return MFH_OK;

@@ -1142,6 +1142,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_paths")) return 26;  // k_merkle_paths of mfh_merkle_paths; rows = statements
   if (!strcmp(which, "sha256_records")) return 27;  // k_sha256_records of mfh_sha256_records / mfh_merkle_set_records (merkle.hip); rows = records
   if (!strcmp(which, "merkle_updates")) return 28;  // k_merkle_update_level / _store of mfh_merkle_update_rows: depth + 1 per chunk; rows = compressions
+  if (!strcmp(which, "merkle_record_rows")) return 29;  // k_record_gather / k_record_store of mfh_merkle_update_records: 2 per chunk; rows = updates gathered
   return -1;
 }
 

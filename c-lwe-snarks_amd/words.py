@@ -40,6 +40,10 @@ Whole statements built from that compression, the result 256 computed public out
     MerkleUpdate(depth)     "I know an old leaf, a new leaf and a path of `depth` siblings that takes the old leaf to old_root and the new leaf to
                             new_root" (lu = 512): MerklePath's levels twice over shared siblings and directions.  56 993 depth + 1 026 wires, 101 473
                             depth + 1 540 rows: depth 1 -> (58 019, 103 013), 2 -> (115 012, 204 486); depth 10 -> (570 956, 1 016 270) fits d = 2^20.
+    MerkleRecordUpdate(length, depth, frozen=None)   "I know an old and a new `length`-byte record and a path of `depth` siblings that takes SHA-256(old
+                            record) to old_root and SHA-256(new record) to new_root" (lu = 512); frozen=(lo, hi) adds "bytes [lo, hi) did not change".
+                            MerkleUpdate(depth)'s sizes plus twice Sha256Message(length)'s less (1 028, 1 544): (55, 1) -> (113 075, 200 501) fits
+                            d = 2^18; at d = 2^20 records up to 55 bytes reach depth 9, up to 119 bytes depth 8.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
@@ -646,6 +650,83 @@ class MerkleUpdate:
         return _statement_of(old_root, "MerkleUpdate: the old root") + _statement_of(new_root, "MerkleUpdate: the new root")
 
 
+class MerkleRecordUpdate:
+    """The statement "I know an old record and a new record of `length` bytes, `depth` siblings and an index such that the path from SHA-256(old record)
+    gives old_root and the SAME siblings and directions from SHA-256(new record) give new_root": MerkleUpdate about the data behind the leaf.
+
+    Private inputs, in this order: the 8 * length bits of the old record, byte k's bit b (LSB first) at 8 k + b, as MerkleRecord; the 8 * length bits of
+    the new record; `depth` siblings of 8 words from the leaf's level up; `depth` direction bits (bit l of the index).  The body is Sha256Message's block
+    chain (_message_chain) once per record and MerklePath's levels (_merkle_levels) twice over the shared sibling and direction wires, as MerkleUpdate
+    shares them.  Public outputs (lu = 512): the old root at statement bits [0, 256), the new root at [256, 512), both computed; statement(R, R') is
+    MerkleUpdate.statement's 64 bytes.
+    frozen=(lo, hi), 0 <= lo <= hi <= length: bytes [lo, hi) of the new record equal the old record's (assert_same on the 8 (hi - lo) bit pairs: that
+    many rows, no wire) -- "the key did not change, only the value did".  It is part of the circuit, and therefore of the CRS.
+    MerkleTree.update_records / update_record_bits give the input rows of a batch of sequential record updates of a device table and its tree.
+    Sizes (MERKLE_RECORD_UPDATE_SIZES): those of MerkleUpdate(depth) plus twice Sha256Message(length)'s, less 1 028 wires and 1 544 rows (the 512 leaf
+    inputs and their bit rows, the chains' outputs and constants counted once); nwires - len(program) = 512 + 16 length + 257 depth inputs.  (55, 1)
+    fits Params(d=1 << 18, m=174762).  At Params(d=1 << 20, m=699050) one-block records (up to 55 bytes) reach depth 9 (569 019 wires, 1 012 285
+    rows; depth 10 would be 1 113 758 rows) and two-block records (up to 119 bytes) depth 8."""
+
+    def __init__(self, length: int, depth: int, frozen=None):
+        if not isinstance(length, (int, np.integer)) or length < 0:
+            raise CircuitError("MerkleRecordUpdate: the length is a non-negative number of bytes")
+        if not isinstance(depth, (int, np.integer)) or depth < 1:
+            raise CircuitError("MerkleRecordUpdate: the depth is at least 1")
+        self.length, self.depth = length, depth = int(length), int(depth)
+        if frozen is not None:
+            lo, hi = frozen
+            if not all(isinstance(x, (int, np.integer)) for x in (lo, hi)) or not 0 <= lo <= hi <= length:
+                raise CircuitError("MerkleRecordUpdate: frozen is (lo, hi) with 0 <= lo <= hi <= length")
+            frozen = (int(lo), int(hi))
+        self.frozen = frozen
+        self.w = w = Words()
+        self.old_record = w.c.private(8 * length)
+        self.new_record = w.c.private(8 * length)
+        self.siblings = [w.private(8) for _ in range(depth)]
+        self.dirs = w.c.private(depth)
+        self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
+        self.new_leaf, _ = _message_chain(w, self.new_record, length)
+        self.out_old = _merkle_levels(w, self.old_leaf, self.siblings, self.dirs)
+        self.out_new = _merkle_levels(w, self.new_leaf, self.siblings, self.dirs)
+        self.old_root = [w.output(x) for x in self.out_old]
+        self.new_root = [w.output(x) for x in self.out_new]
+        if frozen:
+            for a, b in zip(self.old_record[8 * frozen[0]: 8 * frozen[1]], self.new_record[8 * frozen[0]: 8 * frozen[1]]):
+                w.c.assert_same(a, b)
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 512
+
+    def bits(self, old_record: bytes, new_record: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed, the old record's bits, the new record's, the
+        siblings from the leaf's level up, then the direction bits = the bits of the leaf's index, least significant first.  (A new record that breaks
+        `frozen` is not refused here: Circuit.holds / circuit_assign say so.)"""
+        old_record, new_record, siblings = bytes(old_record), bytes(new_record), [bytes(s) for s in siblings]
+        if len(old_record) != self.length or len(new_record) != self.length:
+            raise CircuitError(f"MerkleRecordUpdate: the records are {self.length} bytes")
+        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+            raise CircuitError(f"MerkleRecordUpdate: {self.depth} siblings of 32 bytes")
+        if not 0 <= index < 1 << self.depth:
+            raise CircuitError(f"MerkleRecordUpdate: the index is in [0, 2^{self.depth})")
+        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
+        return np.concatenate([np.zeros(512, dtype=np.uint8), np.unpackbits(np.frombuffer(old_record + new_record, dtype=np.uint8), bitorder="little"),
+                               pack(be_words(b"".join(siblings))), dirs])
+
+    def roots_of(self, witness_row):
+        """(old_root, new_root), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0), _digest_from_row(witness_row, 256)
+
+    @staticmethod
+    def statement(old_root: bytes, new_root: bytes) -> bytes:
+        """the 64 statement bytes that say "old_root became new_root": MerkleUpdate.statement's"""
+        return _statement_of(old_root, "MerkleRecordUpdate: the old root") + _statement_of(new_root, "MerkleRecordUpdate: the new root")
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -657,3 +738,7 @@ MERKLE_RECORD_SIZES = {(0, 1): (56213, 99927), (55, 1): (56667, 100381), (56, 1)
                        (3, 2): (84865, 150819), (55, 2): (85292, 151246), (56, 2): (112632, 199802), (55, 19): (571917, 1015951), (119, 18): (571148, 1014158)}
 # ... and of MerkleUpdate by depth: 56 993 depth + 1 026 wires, 101 473 depth + 1 540 rows
 MERKLE_UPDATE_SIZES = {1: (58019, 103013), 2: (115012, 204486), 3: (172005, 305959), 10: (570956, 1016270)}
+# ... and of MerkleRecordUpdate by (length, depth): MERKLE_UPDATE_SIZES[depth] + 2 x SHA256_MESSAGE_SIZES[length] - (1 028, 1 544); frozen=(lo, hi) adds
+# 8 (hi - lo) rows and no wire.  (55, 9) and (119, 8) are the deepest that fit Params(d=1 << 20, m=699050): (55, 10) would be 1 113 758 rows, (119, 9) 1 110 429
+MERKLE_RECORD_UPDATE_SIZES = {(8, 1): (112309, 199735), (55, 1): (113075, 200501), (56, 1): (167755, 297613), (55, 2): (170068, 301974),
+                              (55, 9): (569019, 1012285), (119, 8): (567738, 1008956)}

@@ -392,6 +392,35 @@ int mfh_merkle_set_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t first, uint32_t
 int mfh_merkle_update_rows(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_inputs, size_t in_stride,
                            uint8_t *h_roots);
 
+/* ---- Sequential updates of a table of records and its tree as statements (merkle.hip: k_sha256_records, k_record_gather, the level and store kernels of
+ * mfh_merkle_update_rows, k_record_store): what words.MerkleRecordUpdate(length, depth) proves -- "I changed one record, and that change alone takes the tree
+ * from root R to root R'".  d_table holds the 2^depth records of the tree ON THE DEVICE, record i at d_table + i * table_stride (table_stride >= length; any
+ * byte alignment of base and stride, as mfh_sha256_records takes them).  PRECONDITION, NOT CHECKED: leaf i of the tree is SHA-256 of record i -- the state
+ * after mfh_merkle_set_records(ctx, t, 0, 2^depth, d_table, table_stride, length).  Where table and tree disagree, the old root mfh_circuit_assign computes
+ * from a row is not R_k.
+ * For k = 0 .. nupd - 1 IN ORDER: row k of h_inputs becomes the packed input row of MerkleRecordUpdate(length, depth) taken from the table and the tree as
+ * they stand before update k; then record h_index[k] becomes the `length` bytes at d_new_records + k * new_stride (on the device, any alignment) and its leaf
+ * and the leaf's ancestors are recomputed.  Indices may repeat: the old record of update k is then the new record of the last earlier update at that index.
+ *   rows     64 zero bytes where the two roots are computed; the old record's `length` bytes; the new record's; for l = 0 .. depth - 1 the 8 words of the
+ *            sibling at level l, each a little-endian uint32 holding the word's value (mfh_merkle_update_rows' order); ceil(depth / 8) bytes holding the
+ *            index.  Exactly 64 + 2 length + 32 depth + ceil(depth / 8) bytes of a row are written, the rest of a wider row is left alone.
+ *   after    the table holds each touched record's last new value and nothing outside a touched record's `length` bytes was written (the gap bytes of a
+ *            wider stride stay); the tree holds the final nodes; h_roots, when not NULL, the (nupd + 1) x 32 bytes R_0 .. R_nupd.
+ *   how      per chunk, on the context's stream: one launch of k_sha256_records hashes the chunk's new records; k_record_gather copies every update's old
+ *            record -- out of the table, or out of d_new_records where the schedule of merkle_sched.hpp names an earlier update at that leaf -- and new
+ *            record into the row heads; the depth + 1 launches of mfh_merkle_update_rows run on the digests; k_record_store writes the new record of the
+ *            last update at each leaf into the table, behind the gather's reads.  A chunk is the most updates whose rows fit 64 MiB (at least one); chunks
+ *            run in order, a later chunk reads the table and the tree the earlier ones stored.  Rows, roots and tables are staged through the context's
+ *            pinned buffers (mfh_scrub_staging zeroes them), the host splices the heads and the siblings into the rows; the call synchronises the stream.
+ *            d_new_records must not overlap the table, and neither may overlap the tree's nodes (not checked).  nupd = 0 does nothing.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued, written or changed in tree or table: a null tree; a tree of another
+ * device; nupd > 0 with h_index, h_inputs or d_table null, or d_new_records null with length > 0; an index >= 2^depth; table_stride or new_stride below
+ * length; length > 2^20; in_stride below the row's bytes.
+ * Kernel timing kinds: "sha256_records" (1 per chunk, rows = the chunk's updates), "merkle_record_rows" (2 per chunk: the gather with rows = the chunk's
+ * updates, the table store with 0), "merkle_updates" (depth + 1 per chunk, as mfh_merkle_update_rows). */
+int mfh_merkle_update_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                              const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
