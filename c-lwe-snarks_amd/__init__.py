@@ -102,6 +102,7 @@ EXPORTS = [
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
+    "mfh_merkle_absent_rows",
 ]
 
 
@@ -239,6 +240,7 @@ def load_library():
         "mfh_merkle_set_records": (i32, [vp, vp, u32, u32, vp, sz, u32]),
         "mfh_merkle_update_rows": (i32, [vp, vp, u32, vp, vp, vp, sz, vp]),
         "mfh_merkle_update_records": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, vp, sz, vp]),
+        "mfh_merkle_absent_rows": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -509,6 +511,50 @@ class MerkleTree:
         length = (rows.shape[1] - 64 - 32 * self.depth - (self.depth + 7) // 8) // 2
         bits = np.unpackbits(rows, axis=1, bitorder="little")[:, : 512 + 16 * length + 257 * self.depth]
         return (bits, out[1]) if roots else bits
+
+    def _absent(self, table, keys, who, want_rows):
+        c = self._ctx
+        if not isinstance(table, c.torch.Tensor):
+            raise MfhError(f"{who}: the table is a torch uint8 [2^depth, length] tensor on the context's device")
+        tab, tstride, length, nrec, _ = _records(c, table, who)
+        if nrec != 1 << self.depth:
+            raise MfhError(f"{who}: the table has one record per leaf, 2^depth of them")
+        k = np.ascontiguousarray(keys)
+        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
+            raise MfhError(f"{who}: keys are uint8 [nq, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        nq, kb = k.shape
+        index = np.zeros(nq, dtype=np.uint32)
+        status = np.zeros(nq, dtype=np.uint8)
+        rows = np.zeros((nq, 32 + kb + length + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8) if want_rows else None
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_absent_rows(c._h, self._h, _ptr(tab), tstride, length, kb, nq, vp(k.ctypes.data), kb, vp(rows.ctypes.data) if want_rows else None,
+                                            rows.shape[1] if want_rows else 0, vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nq:
+            self._keep = []  # (the call waited for the stream)
+        return rows, index, status
+
+    def locate_keys(self, table, keys):
+        """(index uint32 [nq], status uint8 [nq]): for every key the record of the INDEXED table (words.MerkleAbsent has the data model) that decides it
+        -- status 0, absent: the record with lo < key < hi; 1, present: the record whose own key it is; 2, no record (only in a malformed table), index
+        0xFFFFFFFF.  mfh_merkle_absent_rows with no rows: one launch that streams the table's keys, whatever nq; waits for the stream.
+        table: a torch uint8 [2^depth, length] tensor on the context's device under update_records' rules, only read; the records may stand in any
+        order.  keys: np.uint8 [nq, key_bytes], in any order, repeats allowed, neither all-zero nor all-0xFF."""
+        _, index, status = self._absent(table, keys, "locate_keys", False)
+        return index, status
+
+    def absent_rows(self, table, keys):
+        """(rows, index, status): locate_keys, and np.uint8 [nq, 32 + key_bytes + length + 32 depth + ceil(depth / 8)] rows: row k is the packed input
+        row of words.MerkleAbsent(key_bytes, length, depth) for keys[k] and the located record (mfh_merkle_absent_rows).  The row of a present key
+        (status 1) is complete and does not hold; the row of status 2 has the key alone."""
+        return self._absent(table, keys, "absent_rows", True)
+
+    def absent_bits(self, table, keys):
+        """absent_rows with the rows as np.uint8 [nq, 256 + 8 key_bytes + 8 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes
+        for words.MerkleAbsent(key_bytes, length, depth)"""
+        rows, index, status = self._absent(table, keys, "absent_bits", True)
+        kb = np.ascontiguousarray(keys).shape[1]
+        length = rows.shape[1] - 32 - kb - 32 * self.depth - (self.depth + 7) // 8
+        return np.unpackbits(rows, axis=1, bitorder="little")[:, : 256 + 8 * kb + 8 * length + 257 * self.depth], index, status
 
 
 class Context:

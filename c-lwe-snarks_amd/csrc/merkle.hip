@@ -20,9 +20,14 @@
 // k_record_gather, k_record_store: the byte-granular copies of mfh_merkle_update_records, which applies a batch of sequential RECORD updates to a table of
 // records and its tree and writes every update's words.MerkleRecordUpdate input row: old and new records into the row heads before the level launches,
 // the last new record of each leaf into the table behind them (the host's splice of heads and siblings: merkle_record_row.hpp).
+// k_key_locate, k_absent_gather: mfh_merkle_absent_rows, which finds for every query key the record of an indexed table whose range (lo, hi) holds it, or
+// whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp, the splice:
+// merkle_absent_row.hpp).
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "merkle_absent_row.hpp"
+#include "merkle_keys.hpp"
 #include "merkle_record_row.hpp"
 #include "merkle_sched.hpp"
 #include "sha256_dev.hpp"
@@ -260,6 +265,108 @@ __global__ __launch_bounds__(256) void k_record_store(uint8_t *__restrict__ tabl
         if (o + b >= 0 && o + b < (int64_t)length) dst[o + b] = (uint8_t)(w[j] >> (8 * b));
     }
   }
+}
+
+// ---- mfh_merkle_absent_rows: where a key is NOT in an indexed table (include/mfhip.h has the data model).  Record i = (lo | hi | payload), lo and hi of
+// key_bytes bytes each, big-endian; a record is live when lo < hi, and the open ranges (lo, hi) of the live records of a well-formed table partition the
+// keys that are neither members nor sentinels.  The records are in ANY order, so the table is streamed once and every record looks its range up among the
+// queries -- not the other way round.
+//
+// k_key_locate<KW>, ONE launch per call, one thread per record, KW = ceil(key_bytes / 4).  A thread loads lo and hi through load_unit_within (any
+// alignment; nothing outside the table's span is read) as KW words each, byte 0 in the top bits of word 0, a last partial word masked to its key bytes
+// (merkle_keys.hpp: the same words the host made of the queries), and binary-searches the nu sorted unique queries qw (nu x KW words, a query's words
+// contiguous) for a = the first query > lo and b = the first query >= hi.  Queries [a, b) lie inside this record's range: range[u] <- min(range[u], i).
+// The query a - 1, when it equals lo, is this record's own key: present[u] <- min(present[u], i).  Both result arrays start at 0xFFFFFFFF; the atomic
+// minimum makes the answer on a malformed table (ranges that overlap) the lowest index, whatever the order the threads run in.
+// Almost every record of a large table holds no query (2^20 records, 1 020 queries), so b is first tried at a: one probe instead of a second search.
+// A range of more than one query is not filled by its own thread alone: the wave ballots its lanes with such ranges, and for each in turn all 64 lanes
+// take that lane's (a, b, i) by shuffle and stride over [a, b) together -- every query in ONE range costs nu / 64 steps of one wave, not nu of one lane.
+// No thread returns before that loop: a lane that has left the wave could not help.
+// The queries are searched through the vector L1 and L2, not staged in LDS: a search touches 2 + log2(nu) of them, the first probes are the same few for
+// every thread (L1 hits), and staging nu x KW words per workgroup of 256 records would move more bytes than the records themselves (1 020 queries of 16
+// bytes = 16 KB against 4 KB of packed 16-byte records), besides bounding nu by the LDS.
+template <int KW>
+__device__ __forceinline__ bool key_less(const uint32_t *a, const uint32_t *b) {
+#pragma unroll
+  for (int j = 0; j < KW; j++)
+    if (a[j] != b[j]) return a[j] < b[j];
+  return false;
+}
+
+// the KW words of the key_bytes bytes at offset a of the table
+template <int KW>
+__device__ __forceinline__ void load_key_words(const uint8_t *__restrict__ table, int64_t a, uint32_t key_bytes, int64_t span, uint32_t *w) {
+#pragma unroll
+  for (int u = 0; u < (KW + 3) / 4; u++) {
+    const uint4 v = load_unit_within(table, a + 16 * u, a + min(16u * u + 16u, key_bytes), span);
+    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      if (4 * u + e < KW) w[4 * u + e] = __builtin_bswap32(d[e]);
+  }
+  if (key_bytes & 3) w[KW - 1] &= ~0u << (8 * (4 - (key_bytes & 3)));
+}
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_key_locate(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t n,
+                                                    const uint32_t *__restrict__ qw, uint32_t nu, uint32_t *__restrict__ range, uint32_t *__restrict__ present) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  uint32_t a = 0, b = 0;
+  if (i < n) {
+    uint32_t lo[KW], hi[KW], q[KW];
+    const int64_t at = (int64_t)((size_t)i * stride);
+    load_key_words<KW>(table, at, key_bytes, span, lo);
+    load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
+    if (key_less<KW>(lo, hi)) {
+      uint32_t l = 0, r = nu;  // a: the first query > lo
+      while (l < r) {
+        const uint32_t m = l + (r - l) / 2;
+#pragma unroll
+        for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
+        if (key_less<KW>(lo, q)) r = m; else l = m + 1;
+      }
+      a = b = l;
+      if (a > 0) {
+#pragma unroll
+        for (int j = 0; j < KW; j++) q[j] = qw[(size_t)(a - 1) * KW + j];
+        if (!key_less<KW>(q, lo)) atomicMin(present + (a - 1), i);  // (q <= lo by the search: equal)
+      }
+      if (a < nu) {
+#pragma unroll
+        for (int j = 0; j < KW; j++) q[j] = qw[(size_t)a * KW + j];
+        if (key_less<KW>(q, hi)) {  // b: the first query >= hi, above a
+          l = a + 1, r = nu;
+          while (l < r) {
+            const uint32_t m = l + (r - l) / 2;
+#pragma unroll
+            for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
+            if (key_less<KW>(q, hi)) l = m + 1; else r = m;
+          }
+          b = l;
+        }
+      }
+      if (b == a + 1) atomicMin(range + a, i);
+    }
+  }
+  unsigned long long wide = __ballot(b > a + 1);
+  while (wide) {
+    const int src = __ffsll(wide) - 1;
+    wide &= wide - 1;
+    const uint32_t wa = __shfl(a, src), wb = __shfl(b, src), wi = __shfl(i, src);
+    for (uint32_t u = wa + lane; u < wb; u += 64) atomicMin(range + u, wi);
+  }
+}
+
+// k_absent_gather: one item per query k < n of the chunk and 16-byte unit u < ceil(length / 16): heads[k] (a slot of ceil(length / 16) units) <- the
+// table's record idx[k], through load_unit_within as k_record_gather.  Reads nothing outside [table, table + span); the bytes of a record's last unit past
+// `length` are unspecified (the host's splice copies `length` bytes).
+__global__ __launch_bounds__(256) void k_absent_gather(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t length, uint32_t n,
+                                                       const uint32_t *__restrict__ idx, uint4 *__restrict__ heads) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (n * units < 2^32: a chunk's rows fit 64 MiB, or n = 1)
+  if (g >= n * units) return;
+  const uint32_t k = g / units, off = 16 * (g - k * units);
+  const int64_t a = (int64_t)((size_t)idx[k] * stride) + off;
+  heads[g] = load_unit_within(table, a, a + min(16u, length - off), span);
 }
 
 }  // namespace
@@ -582,6 +689,99 @@ int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const ui
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (uint32_t b = 0; b < k; b++) mf::record_update_row(h_inputs + (size_t)(b0 + b) * in_stride, pin_heads + (size_t)b * hs, pin_out + (size_t)b * rs, length, depth);
     if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
+  }
+  return MFH_OK;
+}
+
+int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
+                           const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_absent_rows";
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, who, "the tree is null");
+  if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  const uint32_t depth = t->depth;
+  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
+  if (length > kMaxRecordLength) return fail(c, who, "length above 2^20 bytes");
+  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
+  if (table_stride < length) return fail(c, who, "table_stride shorter than length");
+  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
+  const size_t rowb = mf::absent_row_bytes(key_bytes, length, depth);
+  if (h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 32 + key_bytes + length + 32 depth + ceil(depth / 8) bytes");
+  if (nq && !d_table) return fail(c, who, "queries without d_table");
+  if (nq && !h_keys) return fail(c, who, "queries without h_keys");
+  if (nq && !h_index) return fail(c, who, "queries without h_index");
+  if (nq && !h_status) return fail(c, who, "queries without h_status");
+  for (uint32_t k = 0; k < nq; k++)
+    if (mf::key_is_sentinel(h_keys + (size_t)k * key_stride, key_bytes)) return fail(c, who, "a query is the all-zero or the all-0xFF key");
+  if (!nq) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  mf::KeyPlan plan;
+  mf::keys_prepare(h_keys, key_stride, key_bytes, nq, plan);
+  const uint32_t nu = plan.nu, kw = mf::key_words(key_bytes), n = 1u << depth;
+  // On the device, in the scratch of mfh_circuit_assign.  The search: the unique queries' words | range[nu] | present[nu].  Then, per chunk (the most queries
+  // whose rows fit kPathStageBytes): the path rows of k_merkle_paths at their stride | the heads (merkle_absent_row.hpp) | the chunk's indices -- over the
+  // search's bytes, whose results are on the host by then.
+  const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
+  const size_t prb = mf::absent_path_row_bytes(depth), rs = (prb + 15) & ~(size_t)15, hp = mf::record_head_pitch(length);
+  const uint32_t ch = mf::update_chunk(nq, rowb, kPathStageBytes);
+  const size_t rows_bytes = h_inputs ? (size_t)ch * (rs + hp + 4) : 0;
+  if (int rc = work_reserve(c, c->circ_io, std::max(words_bytes + res_bytes, rows_bytes))) return rc;
+  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
+  {
+    uint32_t *d_qw = c->circ_io.as<uint32_t>(), *d_res = d_qw + (size_t)nu * kw;
+    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
+    if (!pin_qw) return MFH_ENOMEM;
+    memcpy(pin_qw, plan.words.data(), words_bytes);
+    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
+    {
+      Timer tm(c, 30, n);  // "merkle_locate" (mfhip.hip: timing_kind)
+      const dim3 grid((n + 255) / 256), block(256);
+#define MF_LOCATE(KW) \
+  case KW: hipLaunchKernelGGL(k_key_locate<KW>, grid, block, 0, c->stream, d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nu, d_res, d_res + nu); break
+      switch (kw) {
+        MF_LOCATE(1); MF_LOCATE(2); MF_LOCATE(3); MF_LOCATE(4); MF_LOCATE(5); MF_LOCATE(6); MF_LOCATE(7); MF_LOCATE(8);
+      }
+#undef MF_LOCATE
+    }
+    HIP_TRY(c, hipGetLastError());
+    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
+    if (!pin_res) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    mf::keys_scatter(plan, nq, pin_res, h_index, h_status);
+  }
+  if (!h_inputs) return MFH_OK;
+  uint4 *d_rows = c->circ_io.as<uint4>(), *d_heads = d_rows + (size_t)ch * rs / 16;
+  uint32_t *d_idx = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hp / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hp));
+  if (!pin_out) return MFH_ENOMEM;
+  uint8_t *pin_heads = pin_out + (size_t)ch * rs;  // path rows | heads
+  for (uint32_t b0 = 0; b0 < nq; b0 += ch) {
+    const uint32_t k = std::min(ch, nq - b0);
+    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)k * 4);
+    if (!pin_idx) return MFH_ENOMEM;
+    for (uint32_t b = 0; b < k; b++) pin_idx[b] = h_status[b0 + b] == 2 ? 0u : h_index[b0 + b];  // (no record: a stand-in, its staged pieces are not read)
+    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    {
+      Timer tm(c, 26, k);  // "merkle_paths"
+      hipLaunchKernelGGL(k_merkle_paths, dim3(k), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(t->mem), depth, (const uint32_t *)d_idx,
+                         reinterpret_cast<uint32_t *>(d_rows), (uint32_t)(rs / 4));
+    }
+    {
+      Timer tm(c, 31, k);  // "merkle_absent_rows" (mfhip.hip: timing_kind): the gather
+      const uint32_t items = k * (uint32_t)(hp / 16);
+      hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, span, length, k, (const uint32_t *)d_idx, d_heads);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pin_heads, d_heads, (size_t)k * hp, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t b = 0; b < k; b++)
+      mf::absent_row(h_inputs + (size_t)(b0 + b) * in_stride, h_keys + (size_t)(b0 + b) * key_stride, pin_heads + (size_t)b * hp, pin_out + (size_t)b * rs, key_bytes,
+                     length, depth, h_status[b0 + b] != 2);
   }
   return MFH_OK;
 }

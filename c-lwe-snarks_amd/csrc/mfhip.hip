@@ -1143,6 +1143,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "sha256_records")) return 27;  // k_sha256_records of mfh_sha256_records / mfh_merkle_set_records (merkle.hip); rows = records
   if (!strcmp(which, "merkle_updates")) return 28;  // k_merkle_update_level / _store of mfh_merkle_update_rows: depth + 1 per chunk; rows = compressions
   if (!strcmp(which, "merkle_record_rows")) return 29;  // k_record_gather / k_record_store of mfh_merkle_update_records: 2 per chunk; rows = updates gathered
+  if (!strcmp(which, "merkle_locate")) return 30;  // k_key_locate of mfh_merkle_absent_rows (merkle.hip): one per call; rows = the table's 2^depth records
+  if (!strcmp(which, "merkle_absent_rows")) return 31;  // k_absent_gather of mfh_merkle_absent_rows: one per chunk; rows = the chunk's queries
   return -1;
 }
 

@@ -7,6 +7,7 @@ A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wire
     xor / and_ / or_ / not_   32
     ch           96   z ^ (x & (y ^ z))
     maj          32   one MAJ per bit
+    less_than     2 n   for two n-bit operands: a NOT and a MAJ a bit (the borrow chain of a - b); 4 n rows
     rotl / rotr   0   rewiring only
     shr           0   the vacated bits are the circuit's shared zero wire (1 wire for the whole circuit)
     const         0   the shared zero and one wires (at most 2 for the whole circuit)
@@ -44,6 +45,10 @@ Whole statements built from that compression, the result 256 computed public out
                             record) to old_root and SHA-256(new record) to new_root" (lu = 512); frozen=(lo, hi) adds "bytes [lo, hi) did not change".
                             MerkleUpdate(depth)'s sizes plus twice Sha256Message(length)'s less (1 028, 1 544): (55, 1) -> (113 075, 200 501) fits
                             d = 2^18; at d = 2^20 records up to 55 bytes reach depth 9, up to 119 bytes depth 8.
+    MerkleAbsent(key_bytes, length, depth)   "the key q is not in the set behind this root" for an indexed table of records (lo | hi | payload): MerkleRecord's
+                            body plus "lo < q < hi" (two Words.less_than), q public (lu = 256 + 8 key_bytes).  MerkleRecord(length, depth)'s sizes plus 40
+                            key_bytes wires and 72 key_bytes + 2 rows: (4, 8, 1) -> (56 444, 100 288) fits d = 2^17; (8, 55, 19) fits d = 2^20.  Sound
+                            relative to the table's invariant (the class has it); indexed_records / indexed_insert make and extend such tables.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
@@ -148,6 +153,17 @@ class Words:
     def maj(self, x, y, z):
         """bitwise majority (SHA-2's Maj)"""
         return tuple(self.c.MAJ(a, b, d) for a, b, d in zip(x, y, z))
+
+    def less_than(self, a_bits, b_bits):
+        """the wire "a < b" for two equal-length lists of wires, least significant first, read as unsigned integers: the final borrow of a - b,
+        borrow' = MAJ(NOT a_i, b_i, borrow) from const(0).  Two wires (a NOT and a MAJ) and four rows a bit."""
+        a_bits, b_bits = list(a_bits), list(b_bits)
+        if not a_bits or len(a_bits) != len(b_bits):
+            raise CircuitError("less_than: two lists of wires of one length, at least 1")
+        borrow = self.c.const(0)
+        for a, b in zip(a_bits, b_bits):
+            borrow = self.c.MAJ(self.c.NOT(a), b, borrow)
+        return borrow
 
     # -- rewiring -------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -727,6 +743,165 @@ class MerkleRecordUpdate:
         return _statement_of(old_root, "MerkleRecordUpdate: the old root") + _statement_of(new_root, "MerkleRecordUpdate: the new root")
 
 
+def _key_bits_lsb_first(bits, key_bytes: int):
+    """the 8 * key_bytes wires of a key (byte k's bit b at 8 k + b) as an unsigned big-endian integer, least significant wire first: byte 0 is the most
+    significant byte, and bit 7 of a byte stands above its bit 0"""
+    return [bits[8 * k + b] for k in range(key_bytes - 1, -1, -1) for b in range(8)]
+
+
+def _is_sentinel(key: bytes) -> bool:
+    return key == bytes(len(key)) or key == b"\xff" * len(key)
+
+
+class MerkleAbsent:
+    """The statement "the key q is NOT in the set behind this root", for a set kept as an indexed Merkle tree: I know a `length`-byte record (lo | hi |
+    payload) and an authentication path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with this root and lo < q < hi.
+
+    The data model.  A key is key_bytes bytes, 1 <= key_bytes <= 32, compared as a big-endian unsigned integer (memcmp order); the all-zero and the
+    all-0xFF key are sentinels, never members and never queries.  A record is length >= 2 key_bytes bytes: its own key lo at [0, K), the next larger key
+    of the set hi at [K, 2K), an opaque payload behind them.  A well-formed table of 2^depth records holds, in any positions, the sentinel record
+    (0...0, k_1), one record (k_i, k_i+1) per member, the last with hi = FF...FF, and in every other slot lo >= hi: the open ranges (lo, hi) of the live
+    records then partition the keys that are neither members nor sentinels, so exactly one record shows a key absent and none does for a member.
+    SOUNDNESS IS RELATIVE TO THAT INVARIANT: whoever accepts a root accepts that the table behind it is well formed; the circuit proves membership of
+    ONE record with lo < q < hi and nothing about the other records (indexed_records makes such a table, indexed_insert the two updates of an insert).
+    Public wires, in this order: the root as 256 computed outputs (statement bits [0, 256), as MerkleRecord), then the 8 key_bytes given bits of q,
+    byte k's bit b (LSB first) at 256 + 8 k + b; lu = 256 + 8 key_bytes.  Private inputs, in MerkleRecord's order: the 8 * length record bits, `depth`
+    siblings of 8 words, `depth` direction bits.  The body is MerkleRecord's (_message_chain, _merkle_levels) and two comparators (Words.less_than)
+    asserted to 1.  MerkleTree.absent_rows / absent_bits find the record and give the input rows for queries against a device table.
+    Sizes (MERKLE_ABSENT_SIZES): those of MerkleRecord(length, depth) plus 40 key_bytes wires and 72 key_bytes + 2 rows -- the 8 key_bytes public wires of
+    q and their bit rows, and per comparison 16 key_bytes wires (a NOT and a MAJ a bit), 32 key_bytes rows and the assertion's row.  It keeps
+    MerkleRecord's depth range: (8, 55, 19) fits Params(d=1 << 20, m=699050)."""
+
+    def __init__(self, key_bytes: int, length: int, depth: int):
+        if not isinstance(key_bytes, (int, np.integer)) or not 1 <= key_bytes <= 32:
+            raise CircuitError("MerkleAbsent: key_bytes is in [1, 32]")
+        if not isinstance(length, (int, np.integer)) or length < 2 * key_bytes:
+            raise CircuitError("MerkleAbsent: the length is at least 2 key_bytes bytes")
+        if not isinstance(depth, (int, np.integer)) or depth < 1:
+            raise CircuitError("MerkleAbsent: the depth is at least 1")
+        self.key_bytes, self.length, self.depth = K, length, depth = int(key_bytes), int(length), int(depth)
+        self.w = w = Words()
+        self.record = w.c.private(8 * length)
+        self.siblings = [w.private(8) for _ in range(depth)]
+        self.dirs = w.c.private(depth)
+        self.leaf, self.blocks = _message_chain(w, self.record, length)
+        self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
+        self.root = [w.output(x) for x in cur]
+        self.key = w.c.public(8 * K)
+        lo, hi, q = (_key_bits_lsb_first(bits, K) for bits in (self.record[: 8 * K], self.record[8 * K: 16 * K], self.key))
+        w.c.assert_equal(w.less_than(lo, q), 1)
+        w.c.assert_equal(w.less_than(q, hi), 1)
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def lu(self) -> int:
+        return 256 + 8 * self.key_bytes
+
+    def _query(self, key) -> bytes:
+        key = bytes(key)
+        if len(key) != self.key_bytes:
+            raise CircuitError(f"MerkleAbsent: the key is {self.key_bytes} bytes")
+        if _is_sentinel(key):
+            raise CircuitError("MerkleAbsent: the all-zero and the all-0xFF key are sentinels, never queries")
+        return key
+
+    def bits(self, key: bytes, record: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 256 zeros where the root is computed, the query's bits, the record's bits, the siblings from
+        the leaf's level up, then the direction bits = the bits of the leaf's index, least significant first.  (A record whose range does not hold the
+        key is not refused here: Circuit.holds / circuit_assign say so.)"""
+        key, record, siblings = self._query(key), bytes(record), [bytes(s) for s in siblings]
+        if len(record) != self.length:
+            raise CircuitError(f"MerkleAbsent: the record is {self.length} bytes")
+        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+            raise CircuitError(f"MerkleAbsent: {self.depth} siblings of 32 bytes")
+        if not 0 <= index < 1 << self.depth:
+            raise CircuitError(f"MerkleAbsent: the index is in [0, 2^{self.depth})")
+        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
+        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(key + record, dtype=np.uint8), bitorder="little"),
+                               pack(be_words(b"".join(siblings))), dirs])
+
+    def root_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0)
+
+    def statement(self, root: bytes, key: bytes) -> bytes:
+        """the 32 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "`key` is not in the set with root
+        `root`": MerklePath.statement's bytes, then the key"""
+        return _statement_of(root, "MerkleAbsent: the root") + self._query(key)
+
+
+def _keys_array(keys, who: str):
+    """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
+    if isinstance(keys, np.ndarray):
+        a = keys
+    else:
+        keys = [bytes(k) for k in keys]
+        if not keys:
+            raise CircuitError(f"{who}: an empty set of keys is a uint8 array [0, key_bytes] (a list does not say key_bytes)")
+        if len({len(k) for k in keys}) > 1:
+            raise CircuitError(f"{who}: the keys are of one length")
+        a = np.frombuffer(b"".join(keys), dtype=np.uint8).reshape(len(keys), len(keys[0]))
+    if a.dtype != np.uint8 or a.ndim != 2 or not 1 <= a.shape[1] <= 32:
+        raise CircuitError(f"{who}: keys are uint8 [n, key_bytes], key_bytes in [1, 32]")
+    return a
+
+
+def indexed_records(keys, depth: int, length=None, payloads=None):
+    """np.uint8 [2^depth, length]: a well-formed indexed table (MerkleAbsent) of the set `keys` -- record 0 the sentinel record (0...0, smallest key),
+    then one record (key, next larger key) per member in ascending order, the last with hi = FF...FF, the unused slots all zero (lo >= hi: inert).
+    keys: n bytes-likes of one length K, or a uint8 array [n, K] (the only way to say K for the empty set), in any order.  length defaults to 2 K.
+    payloads: one bytes-like per key, in the order of `keys`, at most length - 2 K bytes each, zero-padded; the sentinel record's payload is zero.
+    CircuitError for duplicates, sentinel keys, or more than 2^depth - 1 members."""
+    a = _keys_array(keys, "indexed_records")
+    n, K = a.shape
+    length = 2 * K if length is None else int(length)
+    if length < 2 * K:
+        raise CircuitError("indexed_records: the length is at least 2 key_bytes bytes")
+    if not isinstance(depth, (int, np.integer)) or depth < 1 or n > (1 << depth) - 1:
+        raise CircuitError("indexed_records: a depth >= 1 and at most 2^depth - 1 members")
+    members = [k.tobytes() for k in a]
+    if any(_is_sentinel(k) for k in members):
+        raise CircuitError("indexed_records: the all-zero and the all-0xFF key are sentinels, never members")
+    if len(set(members)) != n:
+        raise CircuitError("indexed_records: a key is given twice")
+    if payloads is None:
+        payloads = [b""] * n
+    payloads = [bytes(p) for p in payloads]
+    if len(payloads) != n or any(len(p) > length - 2 * K for p in payloads):
+        raise CircuitError("indexed_records: one payload of at most length - 2 key_bytes bytes per key")
+    order = sorted(range(n), key=lambda i: members[i])
+    los = [bytes(K)] + [members[i] for i in order]
+    pay = [b""] + [payloads[i] for i in order]
+    table = np.zeros((1 << depth, length), dtype=np.uint8)
+    for r, (lo, p) in enumerate(zip(los, pay)):
+        hi = los[r + 1] if r + 1 < len(los) else b"\xff" * K
+        table[r, : 2 * K + len(p)] = np.frombuffer(lo + hi + p, dtype=np.uint8)
+    return table
+
+
+def indexed_insert(record_p, p: int, key: bytes, free_slot: int, payload: bytes = b""):
+    """(indices, new_records): the two updates that insert `key` into an indexed table, in the order MerkleTree.update_records takes them.  record_p is
+    record p of the table, the one whose range holds the key (lo < key < hi: what MerkleTree.locate_keys reports with status 0); free_slot is any inert
+    slot.  Update 0 is record p with hi <- key (lo and payload kept), update 1 the record (key, the old hi, payload zero-padded) into free_slot.
+    key_bytes is len(key).  CircuitError when the key is not inside record p's range."""
+    record_p, key, payload = bytes(record_p), bytes(key), bytes(payload)
+    K, length = len(key), len(record_p)
+    if not 1 <= K <= 32 or length < 2 * K or len(payload) > length - 2 * K:
+        raise CircuitError("indexed_insert: a key of 1 .. 32 bytes, a record of at least 2 key_bytes bytes, a payload that fits behind the keys")
+    lo, hi = record_p[:K], record_p[K: 2 * K]
+    if not lo < key < hi:
+        raise CircuitError("indexed_insert: the key is not inside record p's range (lo < key < hi)")
+    if p == free_slot or p < 0 or free_slot < 0:
+        raise CircuitError("indexed_insert: p and free_slot are two different slots")
+    new = np.zeros((2, length), dtype=np.uint8)
+    new[0] = np.frombuffer(lo + key + record_p[2 * K:], dtype=np.uint8)
+    new[1, : 2 * K + len(payload)] = np.frombuffer(key + hi + payload, dtype=np.uint8)
+    return [int(p), int(free_slot)], new
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -742,3 +917,8 @@ MERKLE_UPDATE_SIZES = {1: (58019, 103013), 2: (115012, 204486), 3: (172005, 3059
 # 8 (hi - lo) rows and no wire.  (55, 9) and (119, 8) are the deepest that fit Params(d=1 << 20, m=699050): (55, 10) would be 1 113 758 rows, (119, 9) 1 110 429
 MERKLE_RECORD_UPDATE_SIZES = {(8, 1): (112309, 199735), (55, 1): (113075, 200501), (56, 1): (167755, 297613), (55, 2): (170068, 301974),
                               (55, 9): (569019, 1012285), (119, 8): (567738, 1008956)}
+# ... and of MerkleAbsent by (key_bytes, length, depth): those of MerkleRecord(length, depth) plus 40 key_bytes wires and 72 key_bytes + 2 rows (a comparison
+# is 16 key_bytes wires and 32 key_bytes + 1 rows; q is 8 key_bytes public wires and their bit rows).  (4, 8, 1) and (8, 16, 1) fit Params(d=1 << 17,
+# m=87381), (32, 64, 1) (two blocks) Params(d=1 << 18, m=174762); (8, 55, 19) is the deepest one-block statement that fits Params(d=1 << 20, m=699050):
+# (8, 55, 20) would be 1 067 394 rows
+MERKLE_ABSENT_SIZES = {(4, 8, 1): (56444, 100288), (8, 16, 1): (56672, 100644), (32, 64, 1): (85352, 151308), (8, 55, 19): (572237, 1016529)}

@@ -420,6 +420,38 @@ int mfh_merkle_update_rows(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uin
  * updates, the table store with 0), "merkle_updates" (depth + 1 per chunk, as mfh_merkle_update_rows). */
 int mfh_merkle_update_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
                               const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots);
+/* Non-membership in an INDEXED table: for every query key the record whose range holds it, and the packed input row of words.MerkleAbsent(key_bytes, length,
+ * depth) -- "this key is not in the set behind this root".
+ *   layout     a key is key_bytes bytes, 1 <= key_bytes <= 32, compared as a big-endian unsigned integer (memcmp order); the all-zero and the all-0xFF key
+ *              are sentinels, never members and never queries.  Record i of the table (at d_table + i * table_stride, any byte alignment of base and
+ *              stride, as mfh_merkle_update_records takes it) is length >= 2 key_bytes bytes: lo = its own key at [0, key_bytes) | hi = the next larger
+ *              key of the set at [key_bytes, 2 key_bytes) | an opaque payload.
+ *   invariant  NOT CHECKED, and the statement is sound relative to it: the 2^depth records hold, in ANY positions, the sentinel record (0...0, k_1), one
+ *              record (k_i, k_i+1) per member k_1 < k_2 < ..., the last of them with hi = FF...FF, and in every other slot lo >= hi (an all-zero slot
+ *              qualifies), which makes the slot inert.  The open ranges (lo, hi) of the live records then partition the keys that are neither members
+ *              nor sentinels.  Inserting k into the range of record p is two updates of mfh_merkle_update_records: record p with hi <- k, and the record
+ *              (k, the old hi) into any inert slot.  Leaf i of the tree is SHA-256 of record i (the state after mfh_merkle_set_records), not checked
+ *              either: the root mfh_circuit_assign computes from a row shows it.
+ *   results    query j is the key_bytes bytes at h_keys + j * key_stride.  h_status[j] = 0, absent, with h_index[j] = the record with lo < q < hi; 1,
+ *              present, with the record whose lo == q; 2, no record (only in a malformed table), with 0xFFFFFFFF.  Where several records of a malformed
+ *              table qualify, the lowest index is reported.
+ *   rows       h_inputs = NULL means locate only: no row work is launched.  Else row j (at h_inputs + j * in_stride): 32 zero bytes where the root is
+ *              computed | q | the record's `length` bytes | the 32 depth sibling bytes in mfh_merkle_paths' word convention | ceil(depth / 8) index bytes.
+ *              Exactly 32 + key_bytes + length + 32 depth + ceil(depth / 8) bytes of a row are written, the rest of a wider row is left alone.  A status 1
+ *              row is written in full (its witness violates the statement's lo < q); a status 2 row gets the 32 zero bytes and q only.
+ *   how        the host sorts the queries, drops duplicates and turns them into big-endian words; ONE launch of k_key_locate, one thread per record
+ *              whatever nq, binary-searches them for the record's range (a range holding several queries is filled in by the whole wave) and leaves
+ *              the lowest record per query by atomic minimum; the results come back through the sort's permutation.  Then per chunk (the most queries
+ *              whose rows fit 64 MiB, at least one) k_merkle_paths runs on the located indices and k_absent_gather copies the located records; the host
+ *              splices q, record and siblings.  Staging goes through the context's pinned buffers (mfh_scrub_staging zeroes them); the call synchronises
+ *              the stream.  Neither the tree nor the table is modified.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued or written: a null tree; a tree of another device; key_bytes 0 or above
+ * 32; length < 2 key_bytes or length > 2^20; table_stride < length; key_stride < key_bytes; nq > 0 with d_table, h_keys, h_index or h_status null; in_stride
+ * below the row's bytes when h_inputs is given; a query that is all-zero or all-0xFF.  nq = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call, rows = 2^depth), "merkle_absent_rows" (1 per chunk: the gather, rows = the chunk's queries),
+ * "merkle_paths" (1 per chunk, as mfh_merkle_paths). */
+int mfh_merkle_absent_rows(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
+                           const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint32_t *h_index, uint8_t *h_status);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
