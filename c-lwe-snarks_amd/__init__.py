@@ -349,19 +349,62 @@ class MerkleTree:
         except Exception:
             pass
 
+    def _row_bytes(self, zeros, head):
+        """a statement's packed input row (csrc/merkle_rows.hpp): zero bytes where the root(s) are computed | head | depth siblings | ceil(depth / 8) index bytes"""
+        return zeros + head + 32 * self.depth + (self.depth + 7) // 8
+
+    def _unpack(self, rows, zeros, head):
+        return np.unpackbits(rows, axis=1, bitorder="little")[:, : 8 * (zeros + head) + 257 * self.depth]
+
+    @staticmethod
+    def _indices(indices, who):
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise MfhError(f"{who}: indices are in [0, 2^depth)")
+        return idx.astype(np.uint32)
+
+    def _leaves(self, leaves, who, aligned=False):
+        """(tensor, host = it was uploaded); aligned: a device tensor that is not 16-byte aligned is copied"""
+        c = self._ctx
+        if isinstance(leaves, c.torch.Tensor):
+            if leaves.dtype != c.torch.uint8 or leaves.device != c.device or not leaves.is_contiguous():
+                raise MfhError(f"{who}: a device tensor of leaves is contiguous uint8 on the context's device")
+            # (a clone is a fresh allocation: aligned; queued on torch's current stream, the context's)
+            return (leaves.clone() if aligned and leaves.data_ptr() & 15 else leaves), False
+        a = np.frombuffer(leaves, dtype=np.uint8) if isinstance(leaves, (bytes, bytearray, memoryview)) else np.asarray(leaves)
+        if a.dtype != np.uint8:
+            raise MfhError(f"{who}: leaves are bytes or uint8")
+        return c.to_device(a), True
+
+    def _table(self, table, who):
+        """(tensor, stride, length) of a table of one record per leaf, used in place"""
+        if not isinstance(table, self._ctx.torch.Tensor):
+            raise MfhError(f"{who}: the table is a torch uint8 [2^depth, length] tensor on the context's device")
+        tab, tstride, length, nrec, _ = _records(self._ctx, table, who)
+        if nrec != 1 << self.depth:
+            raise MfhError(f"{who}: the table has one record per leaf, 2^depth of them")
+        return tab, tstride, length
+
+    def _updates(self, n, head, roots, call):
+        """the rows (and with roots=True the n + 1 roots) of n updates: call(rows, in_stride, roots or None) is the C call"""
+        rows = np.zeros((n, self._row_bytes(64, head)), dtype=np.uint8)
+        r = np.zeros((n + 1, 32), dtype=np.uint8) if roots else None
+        self._ctx._chk(call(ctypes.c_void_p(rows.ctypes.data), rows.shape[1], ctypes.c_void_p(r.ctypes.data) if roots else None))
+        self._keep = []
+        if roots and not n:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        return (rows, r) if roots else rows
+
+    def _update_bits(self, out, head, roots):
+        bits = self._unpack(out[0] if roots else out, 64, head)
+        return (bits, out[1]) if roots else bits
+
     def set_leaves(self, first, leaves):
         """leaves [first, first + n) <- leaves: bytes-like of 32 n bytes, a numpy uint8 [n, 32], or a torch uint8 tensor on the context's device, which is
         read in place when the context's stream reaches the call (mfh_merkle_set_leaves: queue-only); their ancestors are recomputed"""
         c = self._ctx
-        if isinstance(leaves, c.torch.Tensor):
-            t = leaves
-            if t.dtype != c.torch.uint8 or t.device != c.device or not t.is_contiguous():
-                raise MfhError("set_leaves: a device tensor of leaves is contiguous uint8 on the context's device")
-        else:
-            a = np.frombuffer(leaves, dtype=np.uint8) if isinstance(leaves, (bytes, bytearray, memoryview)) else np.asarray(leaves)
-            if a.dtype != np.uint8:
-                raise MfhError("set_leaves: leaves are bytes or uint8")
-            t = c.to_device(a)
+        t, host = self._leaves(leaves, "set_leaves")
+        if host:
             self._keep.append(t)
         if t.numel() % 32:
             raise MfhError("set_leaves: leaves are 32 bytes each")
@@ -393,20 +436,14 @@ class MerkleTree:
 
     def path_rows(self, indices):
         """np.uint8 [nb, ceil(nin / 8)]: the packed input rows of words.MerklePath(depth) for the leaves at `indices` (mfh_merkle_paths; indices may repeat)"""
-        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
-            raise MfhError("path_rows: indices are in [0, 2^depth)")
-        idx = idx.astype(np.uint32)
-        rows = np.zeros((len(idx), (self.nin + 7) // 8), dtype=np.uint8)
+        idx = self._indices(indices, "path_rows")
+        rows = np.zeros((len(idx), self._row_bytes(32, 32)), dtype=np.uint8)
         self._ctx._chk(self._ctx.lib.mfh_merkle_paths(self._ctx._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(rows.ctypes.data),
                                                       rows.shape[1]))
         self._keep = []
         return rows
 
-    def record_rows(self, records, indices):
-        """np.uint8 [nb, ceil(nin / 8)]: the packed input rows of words.MerkleRecord(length, depth), records[i] (a uint8 [nb, length] array, or nb
-        bytes-likes of one length) being the record at leaf indices[i]: 32 zero bytes where the root is computed, the record's bytes, then the siblings
-        and the index bytes of path_rows(indices).  That the record hashes to that leaf is not checked here: the root circuit_assign computes shows it."""
+    def _record_rows(self, records, indices):
         paths = self.path_rows(indices)
         if isinstance(records, np.ndarray):
             rec = records
@@ -417,17 +454,22 @@ class MerkleTree:
             rec = np.stack(rec) if rec else np.zeros((0, 0), dtype=np.uint8)
         if rec.dtype != np.uint8 or rec.ndim != 2 or len(rec) != len(paths):
             raise MfhError("record_rows: records are uint8 [nb, length], one per index")
-        return np.concatenate([np.zeros((len(paths), 32), dtype=np.uint8), rec, paths[:, 64:]], axis=1)
+        return np.concatenate([np.zeros((len(paths), 32), dtype=np.uint8), rec, paths[:, 64:]], axis=1), rec.shape[1]
+
+    def record_rows(self, records, indices):
+        """np.uint8 [nb, ceil(nin / 8)]: the packed input rows of words.MerkleRecord(length, depth), records[i] (a uint8 [nb, length] array, or nb
+        bytes-likes of one length) being the record at leaf indices[i]: 32 zero bytes where the root is computed, the record's bytes, then the siblings
+        and the index bytes of path_rows(indices).  That the record hashes to that leaf is not checked here: the root circuit_assign computes shows it."""
+        return self._record_rows(records, indices)[0]
 
     def record_bits(self, records, indices):
         """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerkleRecord(length, depth)"""
-        rows = self.record_rows(records, indices)
-        length = rows.shape[1] - 32 - 32 * self.depth - (self.depth + 7) // 8
-        return np.unpackbits(rows, axis=1, bitorder="little")[:, : 256 + 8 * length + 257 * self.depth]
+        rows, length = self._record_rows(records, indices)
+        return self._unpack(rows, 32, length)
 
     def path_bits(self, indices):
         """np.uint8 [nb, nin] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerklePath(depth)"""
-        return np.unpackbits(self.path_rows(indices), axis=1, bitorder="little")[:, : self.nin]
+        return self._unpack(self.path_rows(indices), 32, 32)
 
     def update_rows(self, indices, new_leaves, roots=False):
         """n sequential one-leaf updates, leaf indices[k] <- new_leaves[k] in order (mfh_merkle_update_rows: depth + 1 launches for the batch; waits for the
@@ -437,37 +479,16 @@ class MerkleTree:
         new_leaves: bytes-like of 32 n bytes, a numpy uint8 [n, 32], or a torch uint8 tensor on the context's device (contiguous; copied when it is not
         16-byte aligned), read when the context's stream reaches the call -- the digests Context.sha256_records returns feed straight in."""
         c = self._ctx
-        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
-            raise MfhError("update_rows: indices are in [0, 2^depth)")
-        idx = idx.astype(np.uint32)
-        if isinstance(new_leaves, c.torch.Tensor):
-            t = new_leaves
-            if t.dtype != c.torch.uint8 or t.device != c.device or not t.is_contiguous():
-                raise MfhError("update_rows: a device tensor of leaves is contiguous uint8 on the context's device")
-            if t.data_ptr() & 15:
-                t = t.clone()  # (a fresh allocation: aligned; queued on torch's current stream, the context's)
-        else:
-            a = np.frombuffer(new_leaves, dtype=np.uint8) if isinstance(new_leaves, (bytes, bytearray, memoryview)) else np.asarray(new_leaves)
-            if a.dtype != np.uint8:
-                raise MfhError("update_rows: leaves are bytes or uint8")
-            t = c.to_device(a)
+        idx = self._indices(indices, "update_rows")
+        t, _ = self._leaves(new_leaves, "update_rows", aligned=True)
         if t.numel() != 32 * len(idx):
             raise MfhError("update_rows: one leaf of 32 bytes per index")
-        rows = np.zeros((len(idx), 128 + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
-        r = np.zeros((len(idx) + 1, 32), dtype=np.uint8) if roots else None
-        c._chk(c.lib.mfh_merkle_update_rows(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(t) if len(idx) else None,
-                                            ctypes.c_void_p(rows.ctypes.data), rows.shape[1], ctypes.c_void_p(r.ctypes.data) if roots else None))
-        self._keep = []
-        if roots and not len(idx):
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        return (rows, r) if roots else rows
+        return self._updates(len(idx), 64, roots, lambda rows, stride, r: c.lib.mfh_merkle_update_rows(
+            c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(t) if len(idx) else None, rows, stride, r))
 
     def update_bits(self, indices, new_leaves, roots=False):
         """update_rows as np.uint8 [n, 1024 + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for words.MerkleUpdate(depth)"""
-        out = self.update_rows(indices, new_leaves, roots)
-        bits = np.unpackbits(out[0] if roots else out, axis=1, bitorder="little")[:, : 1024 + 257 * self.depth]
-        return (bits, out[1]) if roots else bits
+        return self._update_bits(self.update_rows(indices, new_leaves, roots), 64, roots)
 
     def update_records(self, table, indices, new_records, roots=False):
         """n sequential one-record updates of a table of records and this tree, record indices[k] <- new_records[k] in order (mfh_merkle_update_records: one
@@ -481,51 +502,29 @@ class MerkleTree:
         new_records: a numpy uint8 [n, length], uploaded, or a device tensor under the table's rules, read when the context's stream reaches the call; it
         must not overlap the table."""
         c = self._ctx
-        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
-            raise MfhError("update_records: indices are in [0, 2^depth)")
-        idx = idx.astype(np.uint32)
-        if not isinstance(table, c.torch.Tensor):
-            raise MfhError("update_records: the table is a torch uint8 [2^depth, length] tensor on the context's device")
-        tab, tstride, length, nrec, _ = _records(c, table, "update_records")
-        if nrec != 1 << self.depth:
-            raise MfhError("update_records: the table has one record per leaf, 2^depth of them")
+        idx = self._indices(indices, "update_records")
+        tab, tstride, length = self._table(table, "update_records")
         new, nstride, nlength, n, _ = _records(c, new_records, "update_records")
         if n != len(idx) or nlength != length:
             raise MfhError("update_records: one new record of the table's length per index")
-        rows = np.zeros((len(idx), 64 + 2 * length + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
-        r = np.zeros((len(idx) + 1, 32), dtype=np.uint8) if roots else None
-        c._chk(c.lib.mfh_merkle_update_records(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(tab), tstride, length,
-                                               _ptr(new) if len(idx) else None, nstride, ctypes.c_void_p(rows.ctypes.data),
-                                               rows.shape[1], ctypes.c_void_p(r.ctypes.data) if roots else None))
-        self._keep = []
-        if roots and not len(idx):
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        return (rows, r) if roots else rows
+        return self._updates(len(idx), 2 * length, roots, lambda rows, stride, r: c.lib.mfh_merkle_update_records(
+            c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(tab), tstride, length, _ptr(new) if len(idx) else None, nstride, rows, stride, r))
 
     def update_record_bits(self, table, indices, new_records, roots=False):
         """update_records as np.uint8 [n, 512 + 16 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
         words.MerkleRecordUpdate(length, depth)"""
-        out = self.update_records(table, indices, new_records, roots)
-        rows = out[0] if roots else out
-        length = (rows.shape[1] - 64 - 32 * self.depth - (self.depth + 7) // 8) // 2
-        bits = np.unpackbits(rows, axis=1, bitorder="little")[:, : 512 + 16 * length + 257 * self.depth]
-        return (bits, out[1]) if roots else bits
+        return self._update_bits(self.update_records(table, indices, new_records, roots), 2 * int(table.shape[1]), roots)
 
     def _absent(self, table, keys, who, want_rows):
         c = self._ctx
-        if not isinstance(table, c.torch.Tensor):
-            raise MfhError(f"{who}: the table is a torch uint8 [2^depth, length] tensor on the context's device")
-        tab, tstride, length, nrec, _ = _records(c, table, who)
-        if nrec != 1 << self.depth:
-            raise MfhError(f"{who}: the table has one record per leaf, 2^depth of them")
+        tab, tstride, length = self._table(table, who)
         k = np.ascontiguousarray(keys)
         if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
             raise MfhError(f"{who}: keys are uint8 [nq, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
         nq, kb = k.shape
         index = np.zeros(nq, dtype=np.uint32)
         status = np.zeros(nq, dtype=np.uint8)
-        rows = np.zeros((nq, 32 + kb + length + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8) if want_rows else None
+        rows = np.zeros((nq, self._row_bytes(32, kb + length)), dtype=np.uint8) if want_rows else None
         vp = ctypes.c_void_p
         c._chk(c.lib.mfh_merkle_absent_rows(c._h, self._h, _ptr(tab), tstride, length, kb, nq, vp(k.ctypes.data), kb, vp(rows.ctypes.data) if want_rows else None,
                                             rows.shape[1] if want_rows else 0, vp(index.ctypes.data), vp(status.ctypes.data)))
@@ -552,9 +551,7 @@ class MerkleTree:
         """absent_rows with the rows as np.uint8 [nq, 256 + 8 key_bytes + 8 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes
         for words.MerkleAbsent(key_bytes, length, depth)"""
         rows, index, status = self._absent(table, keys, "absent_bits", True)
-        kb = np.ascontiguousarray(keys).shape[1]
-        length = rows.shape[1] - 32 - kb - 32 * self.depth - (self.depth + 7) // 8
-        return np.unpackbits(rows, axis=1, bitorder="little")[:, : 256 + 8 * kb + 8 * length + 257 * self.depth], index, status
+        return self._unpack(rows, 32, np.ascontiguousarray(keys).shape[1] + int(table.shape[1])), index, status
 
 
 class Context:

@@ -19,16 +19,16 @@
 // written on the way (mfh_merkle_update_rows; the recurrence: above the kernels, the host's schedule: merkle_sched.hpp).
 // k_record_gather, k_record_store: the byte-granular copies of mfh_merkle_update_records, which applies a batch of sequential RECORD updates to a table of
 // records and its tree and writes every update's words.MerkleRecordUpdate input row: old and new records into the row heads before the level launches,
-// the last new record of each leaf into the table behind them (the host's splice of heads and siblings: merkle_record_row.hpp).
+// the last new record of each leaf into the table behind them.
 // k_key_locate, k_absent_gather: mfh_merkle_absent_rows, which finds for every query key the record of an indexed table whose range (lo, hi) holds it, or
-// whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp, the splice:
-// merkle_absent_row.hpp).
+// whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp).
+// The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
+#include <functional>
 
 #include "ctx.hpp"
-#include "merkle_absent_row.hpp"
 #include "merkle_keys.hpp"
-#include "merkle_record_row.hpp"
+#include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
 #include "sha256_dev.hpp"
 
@@ -70,8 +70,6 @@ __global__ __launch_bounds__(64) void k_merkle_paths(const uint32_t *__restrict_
   }
   if (threadIdx.x == 0) row[nw] = i;
 }
-
-inline size_t path_row_bytes(uint32_t depth) { return 32 + (size_t)32 * (depth + 1) + (depth + 7) / 8; }
 
 // ---- k_sha256_records: SHA-256 of `count` whole messages of `length` bytes each, record r at rec + r * stride (stride >= length; any byte alignment of
 // rec and stride), its digest's 32 bytes at dig + 2 r (16-byte units).  One thread per record, 256 a workgroup; the state and the rolling schedule stay
@@ -386,12 +384,26 @@ int fail(mfh_ctx *c, const char *who, const char *what) {
   return MFH_EINVAL;
 }
 
+// the preamble of a call on a tree: MFH_OK when there is a context and a tree of its device
+int tree_refused(mfh_ctx *c, const mfh_merkle *t, const char *who) {
+  if (!c) return MFH_EINVAL;
+  if (!t) return fail(c, who, "the tree is null");
+  if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  return MFH_OK;
+}
+
+const char *indices_refused(const uint32_t *h_index, uint32_t n, uint32_t depth) {
+  for (uint32_t k = 0; k < n; k++)
+    if (h_index[k] >> depth) return "an index is not below 2^depth";
+  return nullptr;
+}
+
 constexpr uint32_t kMaxRecordLength = 1u << 20;
 
-// what mfh_sha256_records and mfh_merkle_set_records ask of their records; 0 when they are fine
-const char *records_refused(const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count) {
+// what every call asks of its records of `length` bytes at `stride`; 0 when they are fine (count = 0: the caller checks the pointer itself)
+const char *records_refused(const uint8_t *d_records, size_t stride, uint32_t length, uint32_t count, const char *short_stride = "stride shorter than length") {
   if (length > kMaxRecordLength) return "length above 2^20 bytes";
-  if (stride < length) return "stride shorter than length";
+  if (stride < length) return short_stride;
   if (count && length && !d_records) return "records without d_records";
   return nullptr;
 }
@@ -415,6 +427,113 @@ int merkle_update(mfh_ctx *c, const mfh_merkle *t, uint32_t first, uint32_t coun
     hipLaunchKernelGGL(k_merkle_level, dim3((n + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<uint4 *>(t->mem), (1u << (t->depth - l)) + lo, n);
   }
   HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
+// ---- the row calls.  A batch goes in chunks of the most rows that fit kPathStageBytes (mfh_ssp_rows_violations chunks its bits the same way).  A chunk is
+// staged on the device in the scratch of mfh_circuit_assign (these are its input rows; that call leaves nothing in flight) and comes back through pin_cw;
+// what goes up (indices, the schedule) goes through pin_rows, released once its copy is queued.
+
+// A chunk as the two drivers' call-backs see it: rows [b0, b0 + k) of the batch.  On the device their indices (updates: the schedule, merkle_sched.hpp), the
+// kernels' rows (path rows or level rows: merkle_rows.hpp) at a stride of rs bytes and per row a slot of hs bytes for gathered records (hs = 0: none); in the
+// pinned buffer, once the chunk is back, the same rows and heads
+struct Chunk {
+  uint32_t b0, k;
+  const uint32_t *d_idx, *d_last;
+  const int32_t *d_same0;
+  uint4 *d_own_leaves;  // V[0], a slot of k nodes, when the call makes the new leaves itself (else null)
+  uint4 *d_rows, *d_heads;
+  size_t rs, hs;
+  uint8_t *pin_rows, *pin_heads;
+};
+using ChunkFn = std::function<void(const Chunk &)>;
+
+// what the chunk's launches said, then its rows and heads on their way to the pinned buffer
+int stage_out(mfh_ctx *c, const Chunk &u) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(u.pin_rows, u.d_rows, (size_t)u.k * u.rs, hipMemcpyDeviceToHost, c->stream));
+  if (u.hs) HIP_TRY(c, hipMemcpyAsync(u.pin_heads, u.d_heads, (size_t)u.k * u.hs, hipMemcpyDeviceToHost, c->stream));
+  return MFH_OK;
+}
+
+// n path rows of the leaves h_index (where h_status, if any, is 2 there is no record: leaf 0 stands in), chunked by the caller's row of rowb bytes.  Per
+// chunk: the indices go up, k_merkle_paths writes the rows, `gather` (if any) launches what fills the heads, both come back, and `rows_out` takes them from
+// the pinned buffer with the stream idle.  On the device: rows | heads | indices
+int path_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_index, const uint8_t *h_status, size_t rowb, size_t hs, const ChunkFn &gather,
+              const ChunkFn &rows_out) {
+  const size_t rs = mf::staged_stride(mf::row_bytes(32, 32, t->depth));
+  const uint32_t ch = mf::update_chunk(n, rowb, kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, (size_t)ch * (rs + hs + 4))) return rc;
+  uint4 *d_rows = c->circ_io.as<uint4>(), *d_heads = d_rows + (size_t)ch * rs / 16;
+  uint32_t *d_idx = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs));
+  if (!pin_out) return MFH_ENOMEM;
+  for (uint32_t b0 = 0; b0 < n; b0 += ch) {
+    const Chunk u{b0, std::min(ch, n - b0), d_idx, nullptr, nullptr, nullptr, d_rows, d_heads, rs, hs, pin_out, pin_out + (size_t)ch * rs};
+    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)u.k * 4);
+    if (!pin_idx) return MFH_ENOMEM;
+    for (uint32_t b = 0; b < u.k; b++) pin_idx[b] = h_status && h_status[b0 + b] == 2 ? 0u : h_index[b0 + b];
+    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)u.k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    {
+      Timer tm(c, 26, u.k);  // "merkle_paths"
+      hipLaunchKernelGGL(k_merkle_paths, dim3(u.k), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(t->mem), t->depth, (const uint32_t *)d_idx,
+                         reinterpret_cast<uint32_t *>(d_rows), (uint32_t)(rs / 4));
+    }
+    if (gather) gather(u);
+    if (int rc = stage_out(c, u)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rows_out(u);
+  }
+  return MFH_OK;
+}
+
+// nupd sequential updates of the leaves h_index, chunked by the caller's row of rowb bytes; the new leaves are d_new_leaves or, if that is null, what `before`
+// writes to the chunk's d_own_leaves.  Per chunk: the schedule goes up, `before` (if any) queues what the levels need, depth launches of
+// k_merkle_update_level and the tree's write-back, `after` (if any) queues what has to follow that, the level rows, the heads and the roots come back, and
+// `rows_out` takes them from the pinned buffer with the stream idle.  On the device: V[0] (own leaves only) | V[1 .. depth], slots of ch nodes | level rows |
+// heads | the schedule (idx | last | same0 | sib[depth]).  Pinned: level rows | heads | R_b0, the chunk's new roots
+int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_roots, size_t rowb, size_t hs,
+                const std::function<int(const Chunk &)> &before, const ChunkFn &after, const ChunkFn &rows_out) {
+  const uint32_t depth = t->depth, ch = mf::update_chunk(nupd, rowb, kPathStageBytes), own = !d_new_leaves;
+  const size_t rs = mf::staged_stride(mf::row_bytes(64, 64, depth)), slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
+  if (int rc = work_reserve(c, c->circ_io, (depth + own) * slot + (size_t)ch * (rs + hs) + sched_words * 4)) return rc;
+  uint4 *d_own = c->circ_io.as<uint4>(), *d_v = d_own + own * slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
+  uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32);
+  if (!pin_out) return MFH_ENOMEM;
+  uint8_t *pin_roots = pin_out + (size_t)ch * (rs + hs);
+  uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
+  if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
+  for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
+    const uint32_t k = std::min(ch, nupd - b0);
+    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
+    if (!pin_sched) return MFH_ENOMEM;
+    memcpy(pin_sched, h_index + b0, (size_t)k * 4);
+    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
+    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    const int32_t *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
+    const Chunk u{b0, k, d_sched, d_sched + k, (const int32_t *)d_sched + 2 * (size_t)k, own ? d_own : nullptr, d_rows, d_heads, rs, hs, pin_out, pin_out + (size_t)ch * rs};
+    const uint4 *d_leaves = own ? d_own : reinterpret_cast<const uint4 *>(d_new_leaves + (size_t)32 * b0);
+    if (before)
+      if (int rc = before(u)) return rc;
+    for (uint32_t l = 0; l < depth; l++) {
+      Timer tm(c, 28, k);  // "merkle_updates" (mfhip.hip: timing_kind): k compressions
+      hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, u.d_idx, d_sib + (size_t)l * k, u.d_same0,
+                         l ? (const uint4 *)(d_v + (size_t)(l - 1) * slot / 16) : d_leaves, d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
+    }
+    {
+      Timer tm(c, 28, 0);  // ... the write-back: no compression
+      hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, u.d_idx, u.d_last, d_leaves, (const uint4 *)d_v, slot / 16);
+    }
+    if (after) after(u);
+    if (int rc = stage_out(c, u)) return rc;
+    if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rows_out(u);
+    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
+  }
   return MFH_OK;
 }
 
@@ -460,9 +579,7 @@ void mfh_merkle_destroy(mfh_merkle *t) {
 }
 
 int mfh_merkle_set_leaves(mfh_ctx *c, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_leaves) {
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, "mfh_merkle_set_leaves", "the tree is null");
-  if (t->device != c->device) return fail(c, "mfh_merkle_set_leaves", "the tree belongs to another device");
+  if (int rc = tree_refused(c, t, "mfh_merkle_set_leaves")) return rc;
   if ((uint64_t)first + count > (1ull << t->depth)) return fail(c, "mfh_merkle_set_leaves", "first + count exceeds the 2^depth leaves");
   if (!count) return MFH_OK;
   if (!d_leaves) return fail(c, "mfh_merkle_set_leaves", "leaves without d_leaves");
@@ -482,9 +599,7 @@ int mfh_sha256_records(mfh_ctx *c, const uint8_t *d_records, size_t stride, uint
 }
 
 int mfh_merkle_set_records(mfh_ctx *c, mfh_merkle *t, uint32_t first, uint32_t count, const uint8_t *d_records, size_t stride, uint32_t length) {
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, "mfh_merkle_set_records", "the tree is null");
-  if (t->device != c->device) return fail(c, "mfh_merkle_set_records", "the tree belongs to another device");
+  if (int rc = tree_refused(c, t, "mfh_merkle_set_records")) return rc;
   if ((uint64_t)first + count > (1ull << t->depth)) return fail(c, "mfh_merkle_set_records", "first + count exceeds the 2^depth leaves");
   if (const char *what = records_refused(d_records, stride, length, count)) return fail(c, "mfh_merkle_set_records", what);
   if (!count) return MFH_OK;
@@ -516,196 +631,89 @@ int mfh_merkle_nodes(const mfh_merkle *t, uint32_t level, const uint8_t **d_node
 }
 
 int mfh_merkle_paths(mfh_ctx *c, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint8_t *h_inputs, size_t in_stride) {
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, "mfh_merkle_paths", "the tree is null");
-  if (t->device != c->device) return fail(c, "mfh_merkle_paths", "the tree belongs to another device");
-  const size_t rowb = path_row_bytes(t->depth);
-  if (in_stride < rowb) return fail(c, "mfh_merkle_paths", "in_stride shorter than the row's ceil(nin / 8) bytes");
-  if (nstmt && !h_index) return fail(c, "mfh_merkle_paths", "statements without h_index");
-  if (nstmt && !h_inputs) return fail(c, "mfh_merkle_paths", "statements without h_inputs");
-  for (uint32_t b = 0; b < nstmt; b++)
-    if (h_index[b] >> t->depth) return fail(c, "mfh_merkle_paths", "an index is not below 2^depth");
+  const char *who = "mfh_merkle_paths";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const size_t rowb = mf::row_bytes(32, 32, t->depth);
+  if (in_stride < rowb) return fail(c, who, "in_stride shorter than the row's ceil(nin / 8) bytes");
+  if (nstmt && !h_index) return fail(c, who, "statements without h_index");
+  if (nstmt && !h_inputs) return fail(c, who, "statements without h_inputs");
+  if (const char *what = indices_refused(h_index, nstmt, t->depth)) return fail(c, who, what);
   if (!nstmt) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  // a chunk: the most statements whose rows fit kPathStageBytes (mfh_ssp_rows_violations chunks its bits the same way).  On the device, in the scratch of
-  // mfh_circuit_assign (these are its input rows; that call leaves nothing in flight): rows at a stride of 16 bytes' multiple | indices
-  const size_t rs = (rowb + 15) & ~(size_t)15;
-  const uint32_t ch = (uint32_t)std::min<size_t>(nstmt, std::max<size_t>(1, kPathStageBytes / rowb));
-  if (int rc = work_reserve(c, c->circ_io, (size_t)ch * rs + (size_t)ch * 4)) return rc;
-  uint32_t *d_rows = c->circ_io.as<uint32_t>(), *d_idx = d_rows + (size_t)ch * rs / 4;
-  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * rs);
-  if (!pin_out) return MFH_ENOMEM;
-  for (uint32_t b0 = 0; b0 < nstmt; b0 += ch) {
-    const uint32_t k = std::min(ch, nstmt - b0);
-    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)k * 4);
-    if (!pin_idx) return MFH_ENOMEM;
-    memcpy(pin_idx, h_index + b0, (size_t)k * 4);
-    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    {
-      Timer tm(c, 26, k);  // "merkle_paths"
-      hipLaunchKernelGGL(k_merkle_paths, dim3(k), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(t->mem), t->depth, (const uint32_t *)d_idx, d_rows,
-                         (uint32_t)(rs / 4));
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
-  }
-  return MFH_OK;
+  return path_rows(c, t, nstmt, h_index, nullptr, rowb, 0, nullptr, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) memcpy(h_inputs + (size_t)(u.b0 + b) * in_stride, u.pin_rows + (size_t)b * u.rs, rowb);
+  });
 }
 
 int mfh_merkle_update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_inputs, size_t in_stride,
                            uint8_t *h_roots) {
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, "mfh_merkle_update_rows", "the tree is null");
-  if (t->device != c->device) return fail(c, "mfh_merkle_update_rows", "the tree belongs to another device");
-  const uint32_t depth = t->depth;
-  const size_t rowb = mf::update_row_bytes(depth);
-  if (in_stride < rowb) return fail(c, "mfh_merkle_update_rows", "in_stride shorter than the row's 128 + 32 depth + ceil(depth / 8) bytes");
-  if (nupd && !h_index) return fail(c, "mfh_merkle_update_rows", "updates without h_index");
-  if (nupd && !d_new_leaves) return fail(c, "mfh_merkle_update_rows", "updates without d_new_leaves");
-  if (nupd && !h_inputs) return fail(c, "mfh_merkle_update_rows", "updates without h_inputs");
-  if (reinterpret_cast<uintptr_t>(d_new_leaves) & 15) return fail(c, "mfh_merkle_update_rows", "d_new_leaves is not 16-byte aligned");
-  for (uint32_t k = 0; k < nupd; k++)
-    if (h_index[k] >> depth) return fail(c, "mfh_merkle_update_rows", "an index is not below 2^depth");
+  const char *who = "mfh_merkle_update_rows";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const size_t rowb = mf::row_bytes(64, 64, t->depth);
+  if (in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 128 + 32 depth + ceil(depth / 8) bytes");
+  if (nupd && !h_index) return fail(c, who, "updates without h_index");
+  if (nupd && !d_new_leaves) return fail(c, who, "updates without d_new_leaves");
+  if (nupd && !h_inputs) return fail(c, who, "updates without h_inputs");
+  if (reinterpret_cast<uintptr_t>(d_new_leaves) & 15) return fail(c, who, "d_new_leaves is not 16-byte aligned");
+  if (const char *what = indices_refused(h_index, nupd, t->depth)) return fail(c, who, what);
   if (!nupd) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  // a chunk: the most updates whose rows fit kPathStageBytes, as mfh_merkle_paths counts it.  On the device, in the scratch of mfh_circuit_assign (these are
-  // its input rows): V[1 .. depth] (depth slots of ch nodes) | rows at a stride of 16 bytes' multiple | the schedule (idx | last | same0 | sib[depth])
-  const size_t rs = (rowb + 15) & ~(size_t)15;
-  const uint32_t ch = (uint32_t)std::min<size_t>(nupd, std::max<size_t>(1, kPathStageBytes / rowb));
-  const size_t slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
-  if (int rc = work_reserve(c, c->circ_io, depth * slot + (size_t)ch * rs + sched_words * 4)) return rc;
-  uint4 *d_v = c->circ_io.as<uint4>(), *d_rows = d_v + depth * slot / 16;
-  uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_rows + (size_t)ch * rs / 16);
-  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * rs + ((size_t)ch + 1) * 32);
-  if (!pin_out) return MFH_ENOMEM;
-  uint8_t *pin_roots = pin_out + (size_t)ch * rs;  // R_b0 | the chunk's new roots
-  uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
-  if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
-  for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
-    const uint32_t k = std::min(ch, nupd - b0);
-    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
-    if (!pin_sched) return MFH_ENOMEM;
-    memcpy(pin_sched, h_index + b0, (size_t)k * 4);
-    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
-    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    const uint32_t *d_idx = d_sched, *d_last = d_sched + k;
-    const int32_t *d_same0 = (const int32_t *)d_sched + 2 * (size_t)k, *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
-    const uint4 *d_leaves = reinterpret_cast<const uint4 *>(d_new_leaves + (size_t)32 * b0);
-    for (uint32_t l = 0; l < depth; l++) {
-      Timer tm(c, 28, k);  // "merkle_updates" (mfhip.hip: timing_kind): k compressions
-      hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, d_idx, d_sib + (size_t)l * k, d_same0,
-                         l ? (const uint4 *)(d_v + (size_t)(l - 1) * slot / 16) : d_leaves, d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
-    }
-    {
-      Timer tm(c, 28, 0);  // ... the write-back: no compression
-      hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, d_idx, d_last, d_leaves, (const uint4 *)d_v, slot / 16);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
-    if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t b = 0; b < k; b++) memcpy(h_inputs + (size_t)(b0 + b) * in_stride, pin_out + (size_t)b * rs, rowb);
-    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
-  }
-  return MFH_OK;
+  return update_rows(c, t, nupd, h_index, d_new_leaves, h_roots, rowb, 0, nullptr, nullptr, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) memcpy(h_inputs + (size_t)(u.b0 + b) * in_stride, u.pin_rows + (size_t)b * u.rs, rowb);
+  });
 }
 
 int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
                               const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots) {
   const char *who = "mfh_merkle_update_records";
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, who, "the tree is null");
-  if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  if (int rc = tree_refused(c, t, who)) return rc;
   const uint32_t depth = t->depth;
-  if (length > kMaxRecordLength) return fail(c, who, "length above 2^20 bytes");
-  if (table_stride < length) return fail(c, who, "table_stride shorter than length");
+  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
   if (new_stride < length) return fail(c, who, "new_stride shorter than length");
-  const size_t rowb = mf::record_update_row_bytes(length, depth);
+  const size_t rowb = mf::row_bytes(64, 2 * (size_t)length, depth);
   if (in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + 2 length + 32 depth + ceil(depth / 8) bytes");
   if (nupd && !h_index) return fail(c, who, "updates without h_index");
   if (nupd && !h_inputs) return fail(c, who, "updates without h_inputs");
   if (nupd && !d_table) return fail(c, who, "updates without d_table");
   if (nupd && length && !d_new_records) return fail(c, who, "updates without d_new_records");
-  for (uint32_t k = 0; k < nupd; k++)
-    if (h_index[k] >> depth) return fail(c, who, "an index is not below 2^depth");
+  if (const char *what = indices_refused(h_index, nupd, depth)) return fail(c, who, what);
   if (!nupd) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  // a chunk: the most updates whose rows fit kPathStageBytes.  On the device, in the scratch of mfh_circuit_assign: V[0 .. depth] (depth + 1 slots of ch
-  // nodes; V[0] = the digests of the chunk's new records) | the level rows of mfh_merkle_update_rows at their stride | the heads (merkle_record_row.hpp) | the
-  // schedule (idx | last | same0 | sib[depth])
-  const size_t lrb = mf::update_row_bytes(depth), rs = (lrb + 15) & ~(size_t)15, hs = 2 * mf::record_head_pitch(length);
-  const uint32_t ch = mf::update_chunk(nupd, rowb, kPathStageBytes);
-  const size_t slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
-  if (int rc = work_reserve(c, c->circ_io, (depth + 1) * slot + (size_t)ch * (rs + hs) + sched_words * 4)) return rc;
-  uint4 *d_leaves = c->circ_io.as<uint4>(), *d_v = d_leaves + slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
-  uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
-  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32);
-  if (!pin_out) return MFH_ENOMEM;
-  uint8_t *pin_heads = pin_out + (size_t)ch * rs, *pin_roots = pin_heads + (size_t)ch * hs;  // level rows | heads | R_b0, the chunk's new roots
-  uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
+  // the new leaves = the digests of the chunk's new records; a head = the old record | the new record, a pitch each
+  const size_t hp = mf::record_head_pitch(length);
   const int64_t table_span = (int64_t)((((size_t)1 << depth) - 1) * table_stride + length), fresh_span = (int64_t)((size_t)(nupd - 1) * new_stride + length);
-  if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
-  for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
-    const uint32_t k = std::min(ch, nupd - b0);
-    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
-    if (!pin_sched) return MFH_ENOMEM;
-    memcpy(pin_sched, h_index + b0, (size_t)k * 4);
-    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
-    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    const uint32_t *d_idx = d_sched, *d_last = d_sched + k;
-    const int32_t *d_same0 = (const int32_t *)d_sched + 2 * (size_t)k, *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
-    if (int rc = sha256_records(c, d_new_records + (size_t)b0 * new_stride, new_stride, length, k, reinterpret_cast<uint8_t *>(d_leaves))) return rc;
-    {
-      Timer tm(c, 29, k);  // "merkle_record_rows" (mfhip.hip: timing_kind): the gather
-      const uint32_t items = k * 2 * (uint32_t)(hs / 32);
-      hipLaunchKernelGGL(k_record_gather, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, table_span, d_new_records,
-                         new_stride, fresh_span, b0, length, k, d_idx, d_same0, d_heads);
+  auto hash_and_gather = [&](const Chunk &u) -> int {
+    if (int rc = sha256_records(c, d_new_records + (size_t)u.b0 * new_stride, new_stride, length, u.k, reinterpret_cast<uint8_t *>(u.d_own_leaves))) return rc;
+    Timer tm(c, 29, u.k);  // "merkle_record_rows" (mfhip.hip: timing_kind): the gather
+    const uint32_t items = u.k * 2 * (uint32_t)(hp / 16);
+    hipLaunchKernelGGL(k_record_gather, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, table_span, d_new_records,
+                       new_stride, fresh_span, u.b0, length, u.k, u.d_idx, u.d_same0, u.d_heads);
+    return MFH_OK;
+  };
+  auto store_table = [&](const Chunk &u) {
+    Timer tm(c, 29, 0);  // ... and the table's write-back, behind the gather's reads of it
+    const uint32_t items = u.k * ((length + 18) / 16);
+    hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_new_records, new_stride, fresh_span, u.b0,
+                       length, u.k, u.d_idx, u.d_last);
+  };
+  return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) {
+      const uint8_t *head = u.pin_heads + (size_t)b * u.hs;
+      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 64, {{head, length}, {head + hp, length}}, u.pin_rows + (size_t)b * u.rs, 128, depth);
     }
-    for (uint32_t l = 0; l < depth; l++) {
-      Timer tm(c, 28, k);  // "merkle_updates": k compressions
-      hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, d_idx, d_sib + (size_t)l * k, d_same0,
-                         (const uint4 *)(d_leaves + (size_t)l * slot / 16), d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
-    }
-    {
-      Timer tm(c, 28, 0);  // ... the tree's write-back: no compression
-      hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, d_idx, d_last, (const uint4 *)d_leaves,
-                         (const uint4 *)d_v, slot / 16);
-    }
-    {
-      Timer tm(c, 29, 0);  // ... and the table's, behind the gather's reads of it
-      const uint32_t items = k * ((length + 18) / 16);
-      hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_new_records, new_stride, fresh_span, b0,
-                         length, k, d_idx, d_last);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
-    if (hs) HIP_TRY(c, hipMemcpyAsync(pin_heads, d_heads, (size_t)k * hs, hipMemcpyDeviceToHost, c->stream));
-    if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t b = 0; b < k; b++) mf::record_update_row(h_inputs + (size_t)(b0 + b) * in_stride, pin_heads + (size_t)b * hs, pin_out + (size_t)b * rs, length, depth);
-    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
-  }
-  return MFH_OK;
+  });
 }
 
 int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
                            const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint32_t *h_index, uint8_t *h_status) {
   const char *who = "mfh_merkle_absent_rows";
-  if (!c) return MFH_EINVAL;
-  if (!t) return fail(c, who, "the tree is null");
-  if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  if (int rc = tree_refused(c, t, who)) return rc;
   const uint32_t depth = t->depth;
   if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
-  if (length > kMaxRecordLength) return fail(c, who, "length above 2^20 bytes");
-  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
-  if (table_stride < length) return fail(c, who, "table_stride shorter than length");
+  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");  // (at most 64: never also above 2^20)
+  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
   if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
-  const size_t rowb = mf::absent_row_bytes(key_bytes, length, depth);
+  const size_t rowb = mf::row_bytes(32, (size_t)key_bytes + length, depth);
   if (h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 32 + key_bytes + length + 32 depth + ceil(depth / 8) bytes");
   if (nq && !d_table) return fail(c, who, "queries without d_table");
   if (nq && !h_keys) return fail(c, who, "queries without h_keys");
@@ -718,13 +726,11 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
   mf::KeyPlan plan;
   mf::keys_prepare(h_keys, key_stride, key_bytes, nq, plan);
   const uint32_t nu = plan.nu, kw = mf::key_words(key_bytes), n = 1u << depth;
-  // On the device, in the scratch of mfh_circuit_assign.  The search: the unique queries' words | range[nu] | present[nu].  Then, per chunk (the most queries
-  // whose rows fit kPathStageBytes): the path rows of k_merkle_paths at their stride | the heads (merkle_absent_row.hpp) | the chunk's indices -- over the
-  // search's bytes, whose results are on the host by then.
+  // On the device.  The search: the unique queries' words | range[nu] | present[nu].  Then, per chunk: the path rows | the heads (a record each, k_absent_gather)
+  // | the chunk's indices -- over the search's bytes, whose results are on the host by then.
   const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
-  const size_t prb = mf::absent_path_row_bytes(depth), rs = (prb + 15) & ~(size_t)15, hp = mf::record_head_pitch(length);
-  const uint32_t ch = mf::update_chunk(nq, rowb, kPathStageBytes);
-  const size_t rows_bytes = h_inputs ? (size_t)ch * (rs + hp + 4) : 0;
+  const size_t hp = mf::record_head_pitch(length);
+  const size_t rows_bytes = h_inputs ? mf::update_chunk(nq, rowb, kPathStageBytes) * (mf::staged_stride(mf::row_bytes(32, 32, depth)) + hp + 4) : 0;  // path_rows'
   if (int rc = work_reserve(c, c->circ_io, std::max(words_bytes + res_bytes, rows_bytes))) return rc;
   const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
   {
@@ -753,37 +759,18 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
     mf::keys_scatter(plan, nq, pin_res, h_index, h_status);
   }
   if (!h_inputs) return MFH_OK;
-  uint4 *d_rows = c->circ_io.as<uint4>(), *d_heads = d_rows + (size_t)ch * rs / 16;
-  uint32_t *d_idx = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hp / 16);
-  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hp));
-  if (!pin_out) return MFH_ENOMEM;
-  uint8_t *pin_heads = pin_out + (size_t)ch * rs;  // path rows | heads
-  for (uint32_t b0 = 0; b0 < nq; b0 += ch) {
-    const uint32_t k = std::min(ch, nq - b0);
-    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)k * 4);
-    if (!pin_idx) return MFH_ENOMEM;
-    for (uint32_t b = 0; b < k; b++) pin_idx[b] = h_status[b0 + b] == 2 ? 0u : h_index[b0 + b];  // (no record: a stand-in, its staged pieces are not read)
-    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    {
-      Timer tm(c, 26, k);  // "merkle_paths"
-      hipLaunchKernelGGL(k_merkle_paths, dim3(k), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(t->mem), depth, (const uint32_t *)d_idx,
-                         reinterpret_cast<uint32_t *>(d_rows), (uint32_t)(rs / 4));
+  auto gather = [&](const Chunk &u) {
+    Timer tm(c, 31, u.k);  // "merkle_absent_rows" (mfhip.hip: timing_kind)
+    const uint32_t items = u.k * (uint32_t)(hp / 16);
+    hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, span, length, u.k, u.d_idx, u.d_heads);
+  };
+  return path_rows(c, t, nq, h_index, h_status, rowb, hp, gather, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) {
+      const bool found = h_status[u.b0 + b] != 2;  // (else the zero bytes and the key alone: the staged pieces are a stand-in's)
+      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 32, {{h_keys + (size_t)(u.b0 + b) * key_stride, key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
+                     found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, depth);
     }
-    {
-      Timer tm(c, 31, k);  // "merkle_absent_rows" (mfhip.hip: timing_kind): the gather
-      const uint32_t items = k * (uint32_t)(hp / 16);
-      hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, span, length, k, (const uint32_t *)d_idx, d_heads);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * rs, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(pin_heads, d_heads, (size_t)k * hp, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t b = 0; b < k; b++)
-      mf::absent_row(h_inputs + (size_t)(b0 + b) * in_stride, h_keys + (size_t)(b0 + b) * key_stride, pin_heads + (size_t)b * hp, pin_out + (size_t)b * rs, key_bytes,
-                     length, depth, h_status[b0 + b] != 2);
-  }
-  return MFH_OK;
+  });
 }
 
 }  // extern "C"

@@ -453,7 +453,114 @@ def _statement_of(digest: bytes, who: str) -> bytes:
     return b"".join(digest[i: i + 4][::-1] for i in range(0, 32, 4))
 
 
-class Sha256Message:
+class _Statement:
+    """Private base of Sha256Message and the Merkle statements: the argument checks and the pieces of bits() they share, every refusal under the public
+    class's own name.  A statement's nin input bits, public then private, packed eight to a byte (least significant first) are its packed input row, one
+    layout for all of them (MerkleTree's *_rows write it on the device; csrc/merkle_rows.hpp): 32 or 64 zero bytes where the root(s) are computed
+    (MerkleAbsent: and the key) | the head (leaves as words, records as bytes) | depth siblings of 32 bytes as words | ceil(depth / 8) index bytes."""
+
+    def _arg(self, value, lo, hi, what):
+        if not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
+            raise CircuitError(f"{type(self).__name__}: {what}")
+        return int(value)
+
+    def _length_arg(self, length):
+        return self._arg(length, 0, None, "the length is a non-negative number of bytes")
+
+    def _depth_arg(self, depth):
+        return self._arg(depth, 1, None, "the depth is at least 1")
+
+    def _tail_wires(self):
+        """the private wires behind the head: `depth` siblings of 8 words from the leaf's level up, then `depth` direction bits"""
+        self.siblings = [self.w.private(8) for _ in range(self.depth)]
+        self.dirs = self.w.c.private(self.depth)
+
+    @property
+    def circuit(self) -> Circuit:
+        return self.w.c
+
+    @property
+    def nin(self) -> int:
+        """the input bits, public then private: len(bits(...)), and nwires - len(program) of the compiled circuit"""
+        return self.w.c.lu + len(self.w.c._priv)
+
+    @property
+    def row_bytes(self) -> int:
+        """the bytes of the packed input row: ceil(nin / 8)"""
+        return (self.nin + 7) // 8
+
+
+# The pieces of the statements' bits().  Functions of the sizes, not methods: bits() reads self.depth and self.length alone, so it also serves a stand-in that
+# has only those (a model of a statement too deep to build); `who` is the public class's name, for the refusals.
+def _input_bits(computed: int, *parts):
+    """`computed` zeros where the public outputs are computed, then the given bits"""
+    return np.concatenate([np.zeros(computed, dtype=np.uint8), *parts])
+
+
+def _record_bits(who: str, length: int, *records, what="the record is"):
+    """the bits of byte strings of `length` bytes each, byte k's bit b (LSB first) at 8 k + b"""
+    records = [bytes(r) for r in records]
+    if any(len(r) != length for r in records):
+        raise CircuitError(f"{who}: {what} {length} bytes")
+    return np.unpackbits(np.frombuffer(b"".join(records), dtype=np.uint8), bitorder="little")
+
+
+def _tail_bits(who: str, depth: int, siblings, index: int, leaves=(), what=""):
+    """the bits of `leaves` (32-byte heads, refused together with the siblings: `what` names them) and of the `depth` siblings, as big-endian words, then the
+    direction bits = the bits of the leaf's index, least significant first"""
+    leaves, siblings = [bytes(x) for x in leaves], [bytes(s) for s in siblings]
+    if len(siblings) != depth or any(len(x) != 32 for x in leaves + siblings):
+        raise CircuitError(f"{who}: {what}{depth} siblings of 32 bytes")
+    if not 0 <= index < 1 << depth:
+        raise CircuitError(f"{who}: the index is in [0, 2^{depth})")
+    dirs = np.array([(index >> l) & 1 for l in range(depth)], dtype=np.uint8)
+    return np.concatenate([pack(be_words(b"".join(leaves + siblings))), dirs])
+
+
+class _OneRoot(_Statement):
+    """a statement whose public outputs are one root, at statement bits [0, 256)"""
+
+    @property
+    def lu(self) -> int:
+        return 256
+
+    def root_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0)
+
+    @classmethod
+    def statement(cls, root: bytes) -> bytes:
+        """the 32 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the root is `root`": each word's 4 bytes reversed, the
+        inverse of root_of -- a verifier checks a proof against a root it knows without a witness row"""
+        return _statement_of(root, f"{cls.__name__}: the root")
+
+
+class _TwoRoots(_Statement):
+    """a statement whose public outputs are the old root at statement bits [0, 256) and the new root at [256, 512)"""
+
+    @property
+    def lu(self) -> int:
+        return 512
+
+    def _root_outputs(self, old_leaf, new_leaf):
+        """MerklePath's levels twice over the shared sibling and direction wires, then the two roots' outputs"""
+        self.out_old = _merkle_levels(self.w, old_leaf, self.siblings, self.dirs)
+        self.out_new = _merkle_levels(self.w, new_leaf, self.siblings, self.dirs)
+        self.old_root = [self.w.output(x) for x in self.out_old]
+        self.new_root = [self.w.output(x) for x in self.out_new]
+
+    def roots_of(self, witness_row):
+        """(old_root, new_root), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 0), _digest_from_row(witness_row, 256)
+
+    @classmethod
+    def statement(cls, old_root: bytes, new_root: bytes) -> bytes:
+        """the 64 statement bytes (what verify_public takes, bits [0, 512) of a witness row) that say "old_root became new_root": the inverse of
+        roots_of, each half MerklePath.statement's bytes"""
+        return _statement_of(old_root, f"{cls.__name__}: the old root") + _statement_of(new_root, f"{cls.__name__}: the new root")
+
+
+class Sha256Message(_Statement):
     """The statement "I know a `length`-byte message whose SHA-256 digest is this value".
 
     Private inputs: the 8 * length message bits, byte k's bit b (LSB first) at private index 8 k + b -- np.unpackbits(message, bitorder="little").  The
@@ -463,9 +570,7 @@ class Sha256Message:
     positions zero, Circuit.assign / Context.circuit_assign write them, digest_of reads the 32 bytes back.  Sizes: SHA256_MESSAGE_SIZES."""
 
     def __init__(self, length: int):
-        if not isinstance(length, (int, np.integer)) or length < 0:
-            raise CircuitError("Sha256Message: the length is a non-negative number of bytes")
-        self.length = length = int(length)
+        self.length = length = self._length_arg(length)
         self.w = w = Words()
         self.message = w.c.private(8 * length)
         h, self.blocks = _message_chain(w, self.message, length)
@@ -473,19 +578,12 @@ class Sha256Message:
         self.digest = [w.output(x) for x in h]
 
     @property
-    def circuit(self) -> Circuit:
-        return self.w.c
-
-    @property
     def lu(self) -> int:
         return 256
 
     def bits(self, message: bytes):
         """one statement's input bits, public then private (a row of Context.circuit_assign's input): 256 zeros where the digest is computed, then the message"""
-        message = bytes(message)
-        if len(message) != self.length:
-            raise CircuitError(f"Sha256Message: the message is {self.length} bytes")
-        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(message, dtype=np.uint8), bitorder="little")])
+        return _input_bits(256, _record_bits("Sha256Message", self.length, message, what="the message is"))
 
     def digest_of(self, witness_row) -> bytes:
         """the 32 bytes of the computed digest, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
@@ -499,7 +597,7 @@ class Sha256Message:
         return _statement_of(digest, "Sha256Message: the digest")
 
 
-class MerklePath:
+class MerklePath(_OneRoot):
     """The statement "I know a leaf and an authentication path of `depth` siblings to this root".
 
     The node function is parent = compress(IV, left || right): ONE SHA-256 compression of the 64-byte concatenation from the constant SHA256_IV, with no
@@ -511,47 +609,20 @@ class MerklePath:
     which fits Params(d=1 << 20, m=699050)."""
 
     def __init__(self, depth: int):
-        if not isinstance(depth, (int, np.integer)) or depth < 1:
-            raise CircuitError("MerklePath: the depth is at least 1")
-        self.depth = depth = int(depth)
+        self.depth = self._depth_arg(depth)
         self.w = w = Words()
         self.leaf = w.private(8)
-        self.siblings = [w.private(8) for _ in range(depth)]
-        self.dirs = w.c.private(depth)
+        self._tail_wires()
         self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
         self.root = [w.output(x) for x in cur]
-
-    @property
-    def circuit(self) -> Circuit:
-        return self.w.c
-
-    @property
-    def lu(self) -> int:
-        return 256
 
     def bits(self, leaf: bytes, siblings, index: int):
         """one statement's input bits, public then private: 256 zeros where the root is computed, the leaf, the siblings from the leaf's level up, then
         the direction bits = the bits of the leaf's index, least significant first"""
-        siblings = [bytes(s) for s in siblings]
-        if len(leaf) != 32 or len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
-            raise CircuitError(f"MerklePath: a 32-byte leaf and {self.depth} siblings of 32 bytes")
-        if not 0 <= index < 1 << self.depth:
-            raise CircuitError(f"MerklePath: the index is in [0, 2^{self.depth})")
-        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
-        return np.concatenate([np.zeros(256, dtype=np.uint8), pack(be_words(bytes(leaf) + b"".join(siblings))), dirs])
-
-    def root_of(self, witness_row) -> bytes:
-        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
-        return _digest_from_row(witness_row, 0)
-
-    @staticmethod
-    def statement(root: bytes) -> bytes:
-        """the 32 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the root is `root`": each word's 4 bytes reversed, the
-        inverse of root_of -- a verifier checks a proof against a root it knows without a witness row"""
-        return _statement_of(root, "MerklePath: the root")
+        return _input_bits(256, _tail_bits("MerklePath", self.depth, siblings, index, (leaf,), "a 32-byte leaf and "))
 
 
-class MerkleRecord:
+class MerkleRecord(_OneRoot):
     """The statement "I know a `length`-byte record and an authentication path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with
     this root": Sha256Message's block chain over the private record bits (the padding constant wires, part of the statement), its eight output words
     fed, in place of MerklePath's private leaf, into MerklePath's levels (the same conditional swap and parent = compress(IV, left || right)).  It ties a
@@ -564,52 +635,21 @@ class MerkleRecord:
     wires, 1 014 158 rows); (55, 20) does not fit: 1 066 816 rows."""
 
     def __init__(self, length: int, depth: int):
-        if not isinstance(length, (int, np.integer)) or length < 0:
-            raise CircuitError("MerkleRecord: the length is a non-negative number of bytes")
-        if not isinstance(depth, (int, np.integer)) or depth < 1:
-            raise CircuitError("MerkleRecord: the depth is at least 1")
-        self.length, self.depth = length, depth = int(length), int(depth)
+        self.length, self.depth = length, depth = self._length_arg(length), self._depth_arg(depth)
         self.w = w = Words()
         self.record = w.c.private(8 * length)
-        self.siblings = [w.private(8) for _ in range(depth)]
-        self.dirs = w.c.private(depth)
+        self._tail_wires()
         self.leaf, self.blocks = _message_chain(w, self.record, length)
         self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
         self.root = [w.output(x) for x in cur]
 
-    @property
-    def circuit(self) -> Circuit:
-        return self.w.c
-
-    @property
-    def lu(self) -> int:
-        return 256
-
     def bits(self, record: bytes, siblings, index: int):
         """one statement's input bits, public then private: 256 zeros where the root is computed, the record's bits, the siblings from the leaf's level
         up, then the direction bits = the bits of the leaf's index, least significant first"""
-        record, siblings = bytes(record), [bytes(s) for s in siblings]
-        if len(record) != self.length:
-            raise CircuitError(f"MerkleRecord: the record is {self.length} bytes")
-        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
-            raise CircuitError(f"MerkleRecord: {self.depth} siblings of 32 bytes")
-        if not 0 <= index < 1 << self.depth:
-            raise CircuitError(f"MerkleRecord: the index is in [0, 2^{self.depth})")
-        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
-        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(record, dtype=np.uint8), bitorder="little"),
-                               pack(be_words(b"".join(siblings))), dirs])
-
-    def root_of(self, witness_row) -> bytes:
-        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
-        return _digest_from_row(witness_row, 0)
-
-    @staticmethod
-    def statement(root: bytes) -> bytes:
-        """the 32 statement bytes that say "the root is `root`": MerklePath.statement's"""
-        return _statement_of(root, "MerkleRecord: the root")
+        return _input_bits(256, _record_bits("MerkleRecord", self.length, record), _tail_bits("MerkleRecord", self.depth, siblings, index))
 
 
-class MerkleUpdate:
+class MerkleUpdate(_TwoRoots):
     """The statement "I know an old leaf, a new leaf, `depth` siblings and an index such that the path from the old leaf gives old_root and the SAME
     siblings and directions from the new leaf give new_root": one leaf changed, and that change alone takes the tree from old_root to new_root.
 
@@ -623,50 +663,20 @@ class MerkleUpdate:
     Params(d=1 << 18, m=174762)."""
 
     def __init__(self, depth: int):
-        if not isinstance(depth, (int, np.integer)) or depth < 1:
-            raise CircuitError("MerkleUpdate: the depth is at least 1")
-        self.depth = depth = int(depth)
+        self.depth = self._depth_arg(depth)
         self.w = w = Words()
         self.old_leaf = w.private(8)
         self.new_leaf = w.private(8)
-        self.siblings = [w.private(8) for _ in range(depth)]
-        self.dirs = w.c.private(depth)
-        self.out_old = _merkle_levels(w, self.old_leaf, self.siblings, self.dirs)
-        self.out_new = _merkle_levels(w, self.new_leaf, self.siblings, self.dirs)
-        self.old_root = [w.output(x) for x in self.out_old]
-        self.new_root = [w.output(x) for x in self.out_new]
-
-    @property
-    def circuit(self) -> Circuit:
-        return self.w.c
-
-    @property
-    def lu(self) -> int:
-        return 512
+        self._tail_wires()
+        self._root_outputs(self.old_leaf, self.new_leaf)
 
     def bits(self, old_leaf: bytes, new_leaf: bytes, siblings, index: int):
         """one statement's input bits, public then private: 512 zeros where the two roots are computed, the old leaf, the new leaf, the siblings from the
         leaf's level up, then the direction bits = the bits of the leaf's index, least significant first"""
-        siblings = [bytes(s) for s in siblings]
-        if len(old_leaf) != 32 or len(new_leaf) != 32 or len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
-            raise CircuitError(f"MerkleUpdate: two 32-byte leaves and {self.depth} siblings of 32 bytes")
-        if not 0 <= index < 1 << self.depth:
-            raise CircuitError(f"MerkleUpdate: the index is in [0, 2^{self.depth})")
-        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
-        return np.concatenate([np.zeros(512, dtype=np.uint8), pack(be_words(bytes(old_leaf) + bytes(new_leaf) + b"".join(siblings))), dirs])
-
-    def roots_of(self, witness_row):
-        """(old_root, new_root), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
-        return _digest_from_row(witness_row, 0), _digest_from_row(witness_row, 256)
-
-    @staticmethod
-    def statement(old_root: bytes, new_root: bytes) -> bytes:
-        """the 64 statement bytes (what verify_public takes, bits [0, 512) of a witness row) that say "old_root became new_root": the inverse of
-        roots_of, each half MerklePath.statement's bytes"""
-        return _statement_of(old_root, "MerkleUpdate: the old root") + _statement_of(new_root, "MerkleUpdate: the new root")
+        return _input_bits(512, _tail_bits("MerkleUpdate", self.depth, siblings, index, (old_leaf, new_leaf), "two 32-byte leaves and "))
 
 
-class MerkleRecordUpdate:
+class MerkleRecordUpdate(_TwoRoots):
     """The statement "I know an old record and a new record of `length` bytes, `depth` siblings and an index such that the path from SHA-256(old record)
     gives old_root and the SAME siblings and directions from SHA-256(new record) give new_root": MerkleUpdate about the data behind the leaf.
 
@@ -684,11 +694,7 @@ class MerkleRecordUpdate:
     rows; depth 10 would be 1 113 758 rows) and two-block records (up to 119 bytes) depth 8."""
 
     def __init__(self, length: int, depth: int, frozen=None):
-        if not isinstance(length, (int, np.integer)) or length < 0:
-            raise CircuitError("MerkleRecordUpdate: the length is a non-negative number of bytes")
-        if not isinstance(depth, (int, np.integer)) or depth < 1:
-            raise CircuitError("MerkleRecordUpdate: the depth is at least 1")
-        self.length, self.depth = length, depth = int(length), int(depth)
+        self.length, self.depth = length, depth = self._length_arg(length), self._depth_arg(depth)
         if frozen is not None:
             lo, hi = frozen
             if not all(isinstance(x, (int, np.integer)) for x in (lo, hi)) or not 0 <= lo <= hi <= length:
@@ -698,49 +704,20 @@ class MerkleRecordUpdate:
         self.w = w = Words()
         self.old_record = w.c.private(8 * length)
         self.new_record = w.c.private(8 * length)
-        self.siblings = [w.private(8) for _ in range(depth)]
-        self.dirs = w.c.private(depth)
+        self._tail_wires()
         self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
         self.new_leaf, _ = _message_chain(w, self.new_record, length)
-        self.out_old = _merkle_levels(w, self.old_leaf, self.siblings, self.dirs)
-        self.out_new = _merkle_levels(w, self.new_leaf, self.siblings, self.dirs)
-        self.old_root = [w.output(x) for x in self.out_old]
-        self.new_root = [w.output(x) for x in self.out_new]
+        self._root_outputs(self.old_leaf, self.new_leaf)
         if frozen:
             for a, b in zip(self.old_record[8 * frozen[0]: 8 * frozen[1]], self.new_record[8 * frozen[0]: 8 * frozen[1]]):
                 w.c.assert_same(a, b)
-
-    @property
-    def circuit(self) -> Circuit:
-        return self.w.c
-
-    @property
-    def lu(self) -> int:
-        return 512
 
     def bits(self, old_record: bytes, new_record: bytes, siblings, index: int):
         """one statement's input bits, public then private: 512 zeros where the two roots are computed, the old record's bits, the new record's, the
         siblings from the leaf's level up, then the direction bits = the bits of the leaf's index, least significant first.  (A new record that breaks
         `frozen` is not refused here: Circuit.holds / circuit_assign say so.)"""
-        old_record, new_record, siblings = bytes(old_record), bytes(new_record), [bytes(s) for s in siblings]
-        if len(old_record) != self.length or len(new_record) != self.length:
-            raise CircuitError(f"MerkleRecordUpdate: the records are {self.length} bytes")
-        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
-            raise CircuitError(f"MerkleRecordUpdate: {self.depth} siblings of 32 bytes")
-        if not 0 <= index < 1 << self.depth:
-            raise CircuitError(f"MerkleRecordUpdate: the index is in [0, 2^{self.depth})")
-        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
-        return np.concatenate([np.zeros(512, dtype=np.uint8), np.unpackbits(np.frombuffer(old_record + new_record, dtype=np.uint8), bitorder="little"),
-                               pack(be_words(b"".join(siblings))), dirs])
-
-    def roots_of(self, witness_row):
-        """(old_root, new_root), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
-        return _digest_from_row(witness_row, 0), _digest_from_row(witness_row, 256)
-
-    @staticmethod
-    def statement(old_root: bytes, new_root: bytes) -> bytes:
-        """the 64 statement bytes that say "old_root became new_root": MerkleUpdate.statement's"""
-        return _statement_of(old_root, "MerkleRecordUpdate: the old root") + _statement_of(new_root, "MerkleRecordUpdate: the new root")
+        who = "MerkleRecordUpdate"
+        return _input_bits(512, _record_bits(who, self.length, old_record, new_record, what="the records are"), _tail_bits(who, self.depth, siblings, index))
 
 
 def _key_bits_lsb_first(bits, key_bytes: int):
@@ -753,7 +730,7 @@ def _is_sentinel(key: bytes) -> bool:
     return key == bytes(len(key)) or key == b"\xff" * len(key)
 
 
-class MerkleAbsent:
+class MerkleAbsent(_OneRoot):
     """The statement "the key q is NOT in the set behind this root", for a set kept as an indexed Merkle tree: I know a `length`-byte record (lo | hi |
     payload) and an authentication path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with this root and lo < q < hi.
 
@@ -773,17 +750,12 @@ class MerkleAbsent:
     MerkleRecord's depth range: (8, 55, 19) fits Params(d=1 << 20, m=699050)."""
 
     def __init__(self, key_bytes: int, length: int, depth: int):
-        if not isinstance(key_bytes, (int, np.integer)) or not 1 <= key_bytes <= 32:
-            raise CircuitError("MerkleAbsent: key_bytes is in [1, 32]")
-        if not isinstance(length, (int, np.integer)) or length < 2 * key_bytes:
-            raise CircuitError("MerkleAbsent: the length is at least 2 key_bytes bytes")
-        if not isinstance(depth, (int, np.integer)) or depth < 1:
-            raise CircuitError("MerkleAbsent: the depth is at least 1")
-        self.key_bytes, self.length, self.depth = K, length, depth = int(key_bytes), int(length), int(depth)
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
+        self.depth = self._depth_arg(depth)
         self.w = w = Words()
         self.record = w.c.private(8 * length)
-        self.siblings = [w.private(8) for _ in range(depth)]
-        self.dirs = w.c.private(depth)
+        self._tail_wires()
         self.leaf, self.blocks = _message_chain(w, self.record, length)
         self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
         self.root = [w.output(x) for x in cur]
@@ -791,10 +763,6 @@ class MerkleAbsent:
         lo, hi, q = (_key_bits_lsb_first(bits, K) for bits in (self.record[: 8 * K], self.record[8 * K: 16 * K], self.key))
         w.c.assert_equal(w.less_than(lo, q), 1)
         w.c.assert_equal(w.less_than(q, hi), 1)
-
-    @property
-    def circuit(self) -> Circuit:
-        return self.w.c
 
     @property
     def lu(self) -> int:
@@ -812,20 +780,8 @@ class MerkleAbsent:
         """one statement's input bits, public then private: 256 zeros where the root is computed, the query's bits, the record's bits, the siblings from
         the leaf's level up, then the direction bits = the bits of the leaf's index, least significant first.  (A record whose range does not hold the
         key is not refused here: Circuit.holds / circuit_assign say so.)"""
-        key, record, siblings = self._query(key), bytes(record), [bytes(s) for s in siblings]
-        if len(record) != self.length:
-            raise CircuitError(f"MerkleAbsent: the record is {self.length} bytes")
-        if len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
-            raise CircuitError(f"MerkleAbsent: {self.depth} siblings of 32 bytes")
-        if not 0 <= index < 1 << self.depth:
-            raise CircuitError(f"MerkleAbsent: the index is in [0, 2^{self.depth})")
-        dirs = np.array([(index >> l) & 1 for l in range(self.depth)], dtype=np.uint8)
-        return np.concatenate([np.zeros(256, dtype=np.uint8), np.unpackbits(np.frombuffer(key + record, dtype=np.uint8), bitorder="little"),
-                               pack(be_words(b"".join(siblings))), dirs])
-
-    def root_of(self, witness_row) -> bytes:
-        """the 32 bytes of the computed root, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
-        return _digest_from_row(witness_row, 0)
+        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
+        return _input_bits(256, key, _record_bits("MerkleAbsent", self.length, record), _tail_bits("MerkleAbsent", self.depth, siblings, index))
 
     def statement(self, root: bytes, key: bytes) -> bytes:
         """the 32 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "`key` is not in the set with root

@@ -9,6 +9,8 @@ Sources of truth:
     Covers aesctr_prg / rng_seek / rng_gen (stateless and stateful, incl. the ctr/rem state) and mpz2_urandomb.
   * gmp_lwe.json -- LWE arithmetic vectors produced by oracle/gmp_check.c, i.e. by the same libgmp 6.2.1 calls the
     reference's lwe.c makes (lwe.c itself cannot be compiled here: FLINT is absent).  NOT reference output.
+  * merkle_programs.json -- SHA-256 digests of the compiled Merkle statements and Sha256Message (tests/test_merkle_programs_cpu.py says what is
+    hashed); made by this project's own words.py and circuit.py.  NOT reference output.
 Only data is stored (inputs and expected outputs); no reference source text.
 """
 import ctypes
@@ -125,7 +127,16 @@ def gmp_lwe():
     return out
 
 
+def merkle_programs():
+    """digests of the compiled Merkle statements (tests/test_merkle_programs_cpu.py: what is hashed, and for which statements); needs no reference"""
+    sys.path.insert(0, ROOT)
+    from test_merkle_programs_cpu import program_digests
+
+    return program_digests()
+
+
 if __name__ == "__main__":
+    json.dump(merkle_programs(), open(os.path.join(HERE, "merkle_programs.json"), "w"), indent=0)
     json.dump(ref_stream(), open(os.path.join(HERE, "reference_stream.json"), "w"), indent=0)
     json.dump(gmp_lwe(), open(os.path.join(HERE, "gmp_lwe.json"), "w"), indent=0)
     print("wrote", os.listdir(HERE))

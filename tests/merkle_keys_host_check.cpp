@@ -1,5 +1,5 @@
 // The host side of mfh_merkle_absent_rows (csrc/merkle_keys.hpp: the queries sorted, de-duplicated, turned into words, the results scattered back through
-// the permutation; csrc/merkle_absent_row.hpp: the row's size and splice) as a program of its own (tests/test_merkle_keys_host_cpu.py builds it with the
+// the permutation; csrc/merkle_rows.hpp: the row's size and splice) as a program of its own (tests/test_merkle_keys_host_cpu.py builds it with the
 // address and undefined-behaviour sanitizers and runs it).  Every line of standard input is
 //   <key_bytes> <nq> <pool> <extra> <seed>
 // nq queries are drawn from a pool of `pool` random non-sentinel keys (pool < nq forces duplicates; the pool's keys share their first key_bytes - 1 bytes in
@@ -20,8 +20,8 @@
 
 #include <vector>
 
-#include "merkle_absent_row.hpp"
 #include "merkle_keys.hpp"
+#include "merkle_rows.hpp"
 
 static uint64_t rng_state;
 static uint8_t rnd() {  // xorshift64*
@@ -127,7 +127,7 @@ int main() {
     }
     // the splice
     const uint32_t length = 2 * kb + extra, depth = 1 + (uint32_t)(seed % 24);
-    const size_t idxb = (depth + 7) / 8, rowb = mf::absent_row_bytes(kb, length, depth), prb = mf::absent_path_row_bytes(depth), in_stride = rowb + extra;
+    const size_t idxb = (depth + 7) / 8, rowb = mf::row_bytes(32, (size_t)kb + length, depth), prb = mf::row_bytes(32, 32, depth), in_stride = rowb + extra;
     CHECK(rowb == 32 + (size_t)kb + length + 32 * (size_t)depth + idxb && prb == 64 + 32 * (size_t)depth + idxb, "the sizes differ");
     const unsigned nr = nq < 3 ? nq : 3;
     if (nr) {
@@ -148,7 +148,8 @@ int main() {
           for (size_t i = 64; i < prb; i++) w[at++] = path[i];
           CHECK(at == rowb, "the row's size");
         }
-        mf::absent_row(out + k * in_stride, keys + k * stride, found ? head : nullptr, found ? path : nullptr, kb, length, depth, found);
+        if (found) mf::splice_row(out + k * in_stride, 32, {{keys + k * stride, kb}, {head, length}}, path, 64, depth);
+        else mf::splice_row(out + k * in_stride, 32, {{keys + k * stride, kb}}, nullptr, 64, depth);
       }
       const bool same = !memcmp(out, want, out_bytes);
       free(head);

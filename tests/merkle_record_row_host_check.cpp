@@ -1,10 +1,10 @@
-// The host arithmetic of mfh_merkle_update_records (csrc/merkle_record_row.hpp: the row's size, the chunk size, the splice of a staged head and a staged
+// The host arithmetic of mfh_merkle_update_records (csrc/merkle_rows.hpp: the row's size, the chunk size, the splice of a staged head and a staged
 // level row into the packed input row of words.MerkleRecordUpdate) as a program of its own (tests/test_merkle_record_row_host_cpu.py builds it with the
 // address and undefined-behaviour sanitizers and runs it).  Every line of standard input is
 //   <length> <depth> <extra> <n> <seed>
-// n rows of record_update_row_bytes(length, depth) + extra bytes (the in_stride) are spliced from n heads and n level rows.  The heads, the level rows and
+// n rows of row_bytes(64, 2 length, depth) + extra bytes (the in_stride) are spliced from n heads and n level rows.  The heads, the level rows and
 // the output live in heap allocations of exactly their sizes: the heads n x 2 x head_pitch bytes less the last slot's unused tail (the splice reads
-// `length` bytes of each half), the level rows n x update_row_bytes(depth) at that exact stride, the output (n - 1) x in_stride + the row's bytes -- so a
+// `length` bytes of each half), the level rows n x row_bytes(64, 64, depth) at that exact stride, the output (n - 1) x in_stride + the row's bytes -- so a
 // read or write one byte outside them is a heap overflow the address sanitizer reports.  The expected row is put together here byte by byte.
 // Prints "ok <length> <depth> <extra> <n> <row bytes> <chunk of 1000000 updates at 64 MiB>".
 #include <stdint.h>
@@ -12,7 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "merkle_record_row.hpp"
+#include "merkle_rows.hpp"
 
 static uint64_t rng_state;
 static uint8_t rnd() {  // xorshift64*
@@ -38,7 +38,7 @@ int main() {
       return 2;
     }
     rng_state = seed * 0x9E3779B97F4A7C15ull + 1;
-    const size_t rowb = mf::record_update_row_bytes(length, depth), lrb = mf::update_row_bytes(depth), hp = mf::record_head_pitch(length), stride = rowb + extra;
+    const size_t rowb = mf::row_bytes(64, 2 * (size_t)length, depth), lrb = mf::row_bytes(64, 64, depth), hp = mf::record_head_pitch(length), stride = rowb + extra;
     const size_t idxb = (depth + 7) / 8;
     if (rowb != 64 + 2 * (size_t)length + 32 * (size_t)depth + idxb || lrb != 128 + 32 * (size_t)depth + idxb || hp < length || hp % 16 || hp >= (size_t)length + 16) {
       fprintf(stderr, "merkle_record_row_host_check: the sizes differ\n");
@@ -57,7 +57,8 @@ int main() {
       for (unsigned i = 0; i < length; i++) w[at++] = heads[(size_t)k * 2 * hp + hp + i];
       for (size_t i = 128; i < lrb; i++) w[at++] = levels[(size_t)k * lrb + i];
       if (at != rowb) return 1;
-      mf::record_update_row(out + (size_t)k * stride, heads + (size_t)k * 2 * hp, levels + (size_t)k * lrb, length, depth);
+      const uint8_t *head = heads + (size_t)k * 2 * hp;
+      mf::splice_row(out + (size_t)k * stride, 64, {{head, length}, {head + hp, length}}, levels + (size_t)k * lrb, 128, depth);
     }
     const bool ok = !memcmp(out, want, out_bytes);
     // the chunk: the most rows that fit, at least one, at most what there is

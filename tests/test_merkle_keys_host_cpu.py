@@ -1,5 +1,5 @@
 """CPU: the host side of mfh_merkle_absent_rows -- csrc/merkle_keys.hpp (the queries sorted with their permutation, de-duplicated, turned into big-endian
-words; the results scattered back) and csrc/merkle_absent_row.hpp (the row's size and splice).
+words; the results scattered back) and csrc/merkle_rows.hpp (the row's size and splice).
 
 tests/merkle_keys_host_check.cpp (a program with its own main that includes the two headers) is compiled with g++ -O1 -fsanitize=address,undefined and
 run as a program: nothing is loaded into Python.  For key_bytes 1, 3, 4, 5, 8, 20 and 32 and nq 0, 1 and 257 -- drawn from pools of 1, 40 and 4 096 keys,

@@ -1,4 +1,4 @@
-"""CPU: the host arithmetic of mfh_merkle_update_records in csrc/merkle_record_row.hpp -- the row's size, the chunk size, and the splice of the staged
+"""CPU: the host arithmetic of mfh_merkle_update_records in csrc/merkle_rows.hpp -- the row's size, the chunk size, and the splice of the staged
 record heads and level rows into the packed input row of words.MerkleRecordUpdate.
 
 tests/merkle_record_row_host_check.cpp (a program with its own main that includes the header) is compiled with g++ -O1 -fsanitize=address,undefined and
