@@ -56,6 +56,7 @@ __device__ __forceinline__ uint32_t crt_coeff(uint32_t a1, uint32_t a2, uint32_t
 
 // ---- blockwise transforms over buffers [nb][3][N] (poly.hip): every contiguous 2^logB block of every prime's row independently, in place.
 // Forward leaves Montgomery residues in bit-reversed order; inverse takes them back unscaled (x 2^logB), which ntt_crt_make's constants undo.
+// (One plan of passes serves these and the polynomial step's own transforms -- poly.hip: ntt_top_passes; logB = log N is a whole transform per polynomial.)
 int ntt_reserve(mfh_ctx *c, uint32_t logmax);  // twiddle tables for lengths up to 2^logmax (poly_init; never shrinks)
 const mf_ntt::Primes3 &ntt_primes(const mfh_ctx *c);
 mf_ntt::Crt ntt_crt_make(const mfh_ctx *c, uint32_t logB);

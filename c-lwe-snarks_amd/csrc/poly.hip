@@ -17,11 +17,14 @@
 // survives with probability <= (2d / p)^4 < 2^-64), and when one statement fails the Euclidean path above recomputes the statements that failed -- its kernels
 // are queued behind the check, sized for the whole batch, and each workgroup returns at once unless the list of failed statements reaches it: nothing waits for the
 // host, and a batch with k such statements pays the Euclidean path for k.
+// The host half (one pass plan, one product routine, the batch quotient in three parts): DESIGN.md 4.6.
+#include <assert.h>
 #include <errno.h>
 #include <sys/syscall.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "ctx.hpp"
 #include "ntt.hpp"
@@ -86,34 +89,6 @@ __global__ void k_ntt_load(const uint32_t *__restrict__ in, uint32_t len, uint32
   out[(size_t)blockIdx.y * N + i] = mont_mul(x, q.r2, q.p, q.ninv);  // x * R mod p (x < 2^32, r2 < p: product < p * 2^32)
 }
 
-// decimation-in-frequency stage (natural -> bit-reversed order overall)
-__global__ void k_ntt_dif(uint32_t *__restrict__ a, uint32_t N, uint32_t len, const uint32_t *__restrict__ tw, uint32_t tw_stride_n, Primes3 P) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N / 2) return;
-  const NttPrime q = P.q[blockIdx.y % 3];
-  const uint32_t half = len >> 1;
-  const uint32_t j = i & (half - 1);
-  const uint32_t s = (i - j) * 2;
-  uint32_t *x = a + (size_t)blockIdx.y * N + s + j;
-  const uint32_t w = tw[(size_t)(blockIdx.y % 3) * tw_stride_n + (size_t)j * (tw_stride_n * 2 / len)];
-  uint32_t u = x[0], v = x[half];
-  x[0] = add_mod(u, v, q.p);
-  x[half] = mont_mul(sub_mod(u, v, q.p), w, q.p, q.ninv);
-}
-// decimation-in-time stage with inverse twiddles (bit-reversed -> natural)
-__global__ void k_ntt_dit(uint32_t *__restrict__ a, uint32_t N, uint32_t len, const uint32_t *__restrict__ tw, uint32_t tw_stride_n, Primes3 P) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N / 2) return;
-  const NttPrime q = P.q[blockIdx.y % 3];
-  const uint32_t half = len >> 1;
-  const uint32_t j = i & (half - 1);
-  const uint32_t s = (i - j) * 2;
-  uint32_t *x = a + (size_t)blockIdx.y * N + s + j;
-  const uint32_t w = tw[(size_t)(blockIdx.y % 3) * tw_stride_n + (size_t)j * (tw_stride_n * 2 / len)];
-  uint32_t u = x[0], v = mont_mul(x[half], w, q.p, q.ninv);
-  x[0] = add_mod(u, v, q.p);
-  x[half] = sub_mod(u, v, q.p);
-}
 // ---- fused stages ---------------------------------------------------------------------------------------------
 // K consecutive DIF stages (block lengths len, len/2, ..., len>>(K-1)) in registers: a thread owns the 2^K elements
 // {s + j + m*q}, q = len >> K.  grid = (N >> K) threads x 3 primes.
@@ -410,13 +385,6 @@ __global__ __launch_bounds__(256) void k_ntt_lds_mul8(uint32_t *__restrict__ a, 
   for (int m = 0; m < 8; m++) a[base + i1 + 256 * m] = lz_canon(v[m], q.p);
 }
 
-__global__ void k_pointwise(uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t N, Primes3 P) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const NttPrime q = P.q[blockIdx.y % 3];
-  size_t o = (size_t)blockIdx.y * N + i;
-  a[o] = mont_mul(a[o], b[o], q.p, q.ninv);
-}
 // residues (Montgomery, unscaled inverse transform) -> coefficient mod p32: out[i] = coefficient i, i < count -- or, rev_top >= 0, coefficient rev_top - i where that
 // lies in [0, nsrc) and zero elsewhere (the reversals of the Euclidean path written by the kernel that produces the coefficients: rev(A)[:n], and the quotient
 // turned back and padded); map: see MF_NEEDED
@@ -608,34 +576,34 @@ inline dim3 g1(uint32_t n) { return dim3((n + 255) / 256); }
 }  // namespace
 
 struct PolyState {
+  struct Words : DevBuf {  // a DevBuf of 32-bit words: grown with dev_reserve, read as the pointer it holds
+    operator uint32_t *() const { return as<uint32_t>(); }
+  };
   Primes3 P{};
-  uint32_t root[3]{};  // generator of the 2^logmax subgroup is derived from these primitive roots
-  uint32_t logmax = 0;
-  uint32_t *d_tw = nullptr;   // [3][Nmax/2] forward twiddles (Montgomery)
-  uint32_t *d_twi = nullptr;  // [3][Nmax/2] inverse twiddles
-  uint32_t *d_bufA = nullptr, *d_bufB = nullptr;  // [3][Nmax] transform buffers
-  uint32_t *d_tmp = nullptr;  // Nmax coefficients
-  uint32_t *d_tmp2 = nullptr;
-  uint32_t nb_cap = 1;  // polynomials the buffers above hold side by side (poly_batch_reserve)
-  // per-SSP quotient precomputation
+  uint32_t logmax = 0, half_max = 0;  // tables for transforms of up to 2^logmax points; half_max = 2^(logmax - 1) twiddles per prime
+  Words d_tw, d_twi;                  // [3][half_max] forward / inverse twiddles (Montgomery)
+  Words d_bufA, d_bufB;               // [nb_cap][3][Nmax] transform buffers
+  Words d_tmp, d_tmp2;                // [nb_cap][Nmax] coefficients
+  uint32_t nb_cap = 0;  // polynomials the four buffers above hold side by side (poly_batch_reserve)
+  // per-SSP quotient precomputation.  Its buffers only grow: a context keeps the largest preparation it has seen, and have_t / cyc alone say whether
+  // their contents belong to the t in charge (every preparation rewrites all it will read)
   bool have_t = false;
   uint32_t d = 0, dt = 0, n = 0, logN2 = 0;
-  uint32_t *d_G = nullptr;     // n coefficients of rev(t)^-1
-  uint32_t *d_Ghat = nullptr;  // [3][N2] forward transform of G
-  uint32_t *d_f = nullptr;     // rev(t), dt+1 coefficients
+  Words d_G;     // n coefficients of rev(t)^-1
+  Words d_Ghat;  // [3][N2] forward transform of G
+  Words d_f;     // rev(t), dt+1 coefficients
   // ... and the exact-division path (when deg t = d - 1 and t is a unit modulo x^Nc - 1)
   bool cyc = false;
   uint32_t logNc = 0;            // Nc = 2^logNc >= d
-  uint32_t *d_That = nullptr;    // [3][Nc] forward transform of t^-1 mod (x^Nc - 1)
-  uint32_t *d_chk = nullptr;     // [4][Nc] powers of the four check points
+  Words d_That;                  // [3][Nc] forward transform of t^-1 mod (x^Nc - 1)
+  Words d_chk;                   // [4][Nc] powers of the four check points
   uint32_t chk_r[4]{};           // the check points (drawn per preparation, or pinned: mfh_set_poly_exact_points)
   uint32_t chk_t[4]{};           // t at the check points
-  uint32_t *d_need = nullptr;    // [0] statements of the batch that failed the check, [1] the same since the last reset, [2 ..] which ones (k_exact_check)
+  Words d_need;                  // [0] statements of the batch that failed the check, [1] the same since the last reset, [2 ..] which ones (k_exact_check)
   uint32_t *h_seen = nullptr;    // pinned host word the check sets when a statement fails: read (never waited for) by later calls
   uint32_t rest = 0;             // batches left on the Euclidean path alone after such a mark (poly_exact == 1)
   ~PolyState() {
-    for (uint32_t *p : {d_tw, d_twi, d_bufA, d_bufB, d_tmp, d_tmp2, d_G, d_Ghat, d_f, d_That, d_chk, d_need})
-      if (p) hipFree(p);
+    for (Words *b : {&d_tw, &d_twi, &d_bufA, &d_bufB, &d_tmp, &d_tmp2, &d_G, &d_Ghat, &d_f, &d_That, &d_chk, &d_need}) dev_free(*b);
     if (h_seen) hipHostFree(h_seen);
   }
 };
@@ -649,8 +617,29 @@ constexpr uint32_t kMaxBatch = 21845;  // polynomials side by side: 3 per polyno
 
 uint32_t to_mont(uint64_t x, const NttPrime &q) { return (uint32_t)(((unsigned __int128)(x % q.p) << 32) % q.p); }
 
+// the transform / scratch buffers for nb polynomials side by side ([nb][3][Nmax] and [nb][Nmax]); grows only, and waits once for the stream before the old blocks go.
+// A growth that fails leaves nb_cap = 0, so that the next call (poly_init included) tries again instead of using what is left
+int poly_batch_reserve(mfh_ctx *c, PolyState *S, uint32_t nb) {
+  if (nb <= S->nb_cap) return MFH_OK;
+  const size_t bytes = (size_t)nb * 4 << S->logmax;  // nb polynomials of Nmax words
+  if (S->d_bufA.p) hipStreamSynchronize(c->stream);  // (a new state's buffers are empty: nothing reads them)
+  S->nb_cap = 0;
+  for (PolyState::Words *b : {&S->d_bufA, &S->d_bufB, &S->d_tmp, &S->d_tmp2}) dev_free(*b);
+  int rc = MFH_OK;
+  for (PolyState::Words *b : {&S->d_bufA, &S->d_bufB})
+    if (!rc) rc = dev_reserve(c, *b, 3 * bytes);
+  for (PolyState::Words *b : {&S->d_tmp, &S->d_tmp2})
+    if (!rc) rc = dev_reserve(c, *b, bytes);
+  if (rc) {
+    c->err = "poly_batch_reserve: device allocation failed";
+    return rc;
+  }
+  S->nb_cap = nb;
+  return MFH_OK;
+}
+
 int poly_init(mfh_ctx *c, uint32_t logmax) {
-  if (c->poly && c->poly->logmax >= logmax) return MFH_OK;
+  if (c->poly && c->poly->logmax >= logmax) return poly_batch_reserve(c, c->poly, 1);
   if (logmax > 23) {
     c->err = "polynomial too long for the NTT primes (max 2^23)";
     return MFH_EUNSUPPORTED;
@@ -659,6 +648,7 @@ int poly_init(mfh_ctx *c, uint32_t logmax) {
   c->poly = nullptr;
   PolyState *S = new PolyState();
   S->logmax = logmax;
+  S->half_max = 1u << (logmax - 1);
   const size_t Nmax = (size_t)1 << logmax;
   for (int k = 0; k < 3; k++) {
     NttPrime &q = S->P.q[k];
@@ -688,38 +678,18 @@ int poly_init(mfh_ctx *c, uint32_t logmax) {
       b = b * wi % q.p;
     }
   }
-  bool ok = hipMalloc(&S->d_tw, tw.size() * 4) == hipSuccess && hipMalloc(&S->d_twi, twi.size() * 4) == hipSuccess &&
-            hipMalloc(&S->d_bufA, 3 * Nmax * 4) == hipSuccess && hipMalloc(&S->d_bufB, 3 * Nmax * 4) == hipSuccess &&
-            hipMalloc(&S->d_tmp, Nmax * 4) == hipSuccess && hipMalloc(&S->d_tmp2, Nmax * 4) == hipSuccess &&
-            hipMemcpy(S->d_tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(S->d_twi, twi.data(), twi.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
+  int rc = dev_reserve(c, S->d_tw, tw.size() * 4);
+  if (!rc) rc = dev_reserve(c, S->d_twi, twi.size() * 4);
+  if (!rc) rc = poly_batch_reserve(c, S, 1);
+  if (!rc && (hipMemcpy(S->d_tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(S->d_twi, twi.data(), twi.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
+    rc = MFH_ENOMEM;
+  if (rc) {
     delete S;
     c->err = "poly_init: device allocation failed";
     return MFH_ENOMEM;
   }
   c->poly = S;
-  return MFH_OK;
-}
-
-// grow the transform / scratch buffers to hold nb polynomials side by side ([nb][3][Nmax] and [nb][Nmax])
-int poly_batch_reserve(mfh_ctx *c, uint32_t nb) {
-  PolyState *S = c->poly;
-  if (nb <= S->nb_cap) return MFH_OK;
-  const size_t Nmax = (size_t)1 << S->logmax;
-  hipStreamSynchronize(c->stream);
-  for (uint32_t **p : {&S->d_bufA, &S->d_bufB, &S->d_tmp, &S->d_tmp2}) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
-  S->nb_cap = 1;
-  bool ok = hipMalloc(&S->d_bufA, (size_t)nb * 3 * Nmax * 4) == hipSuccess && hipMalloc(&S->d_bufB, (size_t)nb * 3 * Nmax * 4) == hipSuccess &&
-            hipMalloc(&S->d_tmp, (size_t)nb * Nmax * 4) == hipSuccess && hipMalloc(&S->d_tmp2, (size_t)nb * Nmax * 4) == hipSuccess;
-  if (!ok) {
-    c->err = "poly_batch_reserve: device allocation failed";
-    return MFH_ENOMEM;
-  }
-  S->nb_cap = nb;
   return MFH_OK;
 }
 
@@ -729,57 +699,57 @@ uint32_t ceil_log2(size_t x) {
   return l;
 }
 
-// the top (register) stages of a forward / inverse transform; the low B = min(logN, 11) stages run in LDS
-// (up to five stages per pass: 32 elements per thread; 2^16 -> one pass of 5, 2^21 -> two.  `in`: the coefficients to load in the first
-// pass instead of a separate k_ntt_load; returns false when there is no register pass to fuse the load into)
-bool forward_top(mfh_ctx *c, uint32_t *buf, uint32_t logN, uint32_t nb = 1, const uint32_t *in = nullptr, uint32_t in_len = 0, size_t in_stride = 0,
-                 const uint32_t *need = nullptr, const uint32_t *map = nullptr) {
-  PolyState *S = c->poly;
-  const uint32_t N = 1u << logN, half_max = 1u << (S->logmax - 1);
-  uint32_t top = logN - std::min(logN, 11u), len = N;
-  if (!top) return false;
-  while (top) {
-    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;  // never leave a pass of fewer than three stages behind a full one
-    dim3 g(((N >> k) + 255) / 256, 3 * nb);
-    switch (k) {
-      case 5: hipLaunchKernelGGL(k_ntt_dif_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, in, in_len, in_stride, need, map); break;
-      case 4: hipLaunchKernelGGL(k_ntt_dif_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, in, in_len, in_stride, need, map); break;
-      case 3: hipLaunchKernelGGL(k_ntt_dif_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, in, in_len, in_stride, need, map); break;
-      case 2: hipLaunchKernelGGL(k_ntt_dif_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, in, in_len, in_stride, need, map); break;
-      default: hipLaunchKernelGGL(k_ntt_dif_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, in, in_len, in_stride, need, map); break;
-    }
-    in = nullptr;
-    map = nullptr;
-    len >>= k;
-    top -= k;
+// calls f with k as a compile-time constant (std::integral_constant): the one place where a run-time stage count picks a kernel instantiation.  k in 1 .. 5 --
+// the pass plan and the seams' 12 <= logNc <= 16 give nothing else.  Any other k is a bug in this file, and the assert stops the process on it on purpose: falling
+// back to some instantiation would run a transform with the wrong number of stages and hand back a wrong polynomial
+template <class F>
+void with_stages(uint32_t k, F &&f) {
+  assert(k >= 1 && k <= 5);
+  switch (k) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+  }
+}
+
+// coefficients on their way into a transform buffer: `len` per polynomial (mod p32, zero padded), polynomial k of the launch at in + (map ? map[k] : k) stride
+struct NttLoad {
+  const uint32_t *in = nullptr; uint32_t len = 0; size_t stride = 0;
+  const uint32_t *map = nullptr;
+};
+// ... as a pass of their own: buf[nb][3][N] <- their Montgomery residues
+void ntt_load(mfh_ctx *c, uint32_t *buf, uint32_t N, uint32_t nb, const NttLoad &ld, const uint32_t *need = nullptr) {
+  hipLaunchKernelGGL(k_ntt_load, dim3((N + 255) / 256, 3 * nb), dim3(256), 0, c->stream, ld.in, ld.len, N, c->poly->P, buf, ld.stride, need, ld.map);
+}
+
+// The register passes of a transform made of blocks of length 2^logB, over a buffer of N points per prime and nb polynomials (logB = log N: one whole transform per
+// polynomial; k_ntt_dif_multi / k_ntt_dit_multi work on every block of length `len` of the buffer).  They are the stages above the 2048-point blocks, whose own 11
+// stages run in LDS: none when logB <= 11 (returns false).  A pass takes up to five stages (32 elements per thread: 2^16 -> one pass of 5, 2^21 -> two), and never
+// leaves a pass of fewer than three stages behind a full one.  Forward walks the block length down from 2^logB, inverse up from 2^12.
+// ld (forward only): the coefficients the first pass loads instead of reading the buffer -- a separate ntt_load saved.
+enum class Ntt { forward, inverse };
+bool ntt_top_passes(mfh_ctx *c, Ntt dir, uint32_t *buf, uint32_t N, uint32_t logB, uint32_t nb, const uint32_t *need = nullptr, NttLoad ld = {}) {
+  const PolyState *S = c->poly;
+  if (logB <= 11) return false;
+  const bool fwd = dir == Ntt::forward;
+  uint32_t len = fwd ? 1u << logB : 2u << 11;
+  for (uint32_t top = logB - 11, k; top; top -= k) {
+    k = top > 5 ? std::min(top - 3, 5u) : top;
+    const dim3 g(((N >> k) + 255) / 256, 3 * nb);
+    with_stages(k, [&](auto K) {
+      if (fwd)
+        hipLaunchKernelGGL(k_ntt_dif_multi<K()>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, S->half_max, S->P, ld.in, ld.len, ld.stride, need, ld.map);
+      else
+        hipLaunchKernelGGL(k_ntt_dit_multi<K()>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, S->half_max, S->P, need);
+    });
+    ld.in = ld.map = nullptr;
+    len = fwd ? len >> k : len << k;
   }
   return true;
 }
-void inverse_top(mfh_ctx *c, uint32_t *buf, uint32_t logN, uint32_t nb = 1, const uint32_t *need = nullptr) {
-  PolyState *S = c->poly;
-  const uint32_t N = 1u << logN, half_max = 1u << (S->logmax - 1);
-  const uint32_t B = std::min(logN, 11u);
-  uint32_t top = logN - B, len = 2u << B;
-  while (top) {
-    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;
-    dim3 g(((N >> k) + 255) / 256, 3 * nb);
-    switch (k) {
-      case 5: hipLaunchKernelGGL(k_ntt_dit_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, need); break;
-      case 4: hipLaunchKernelGGL(k_ntt_dit_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, need); break;
-      case 3: hipLaunchKernelGGL(k_ntt_dit_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, need); break;
-      case 2: hipLaunchKernelGGL(k_ntt_dit_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, need); break;
-      default: hipLaunchKernelGGL(k_ntt_dit_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, need); break;
-    }
-    len <<= k;
-    top -= k;
-  }
-}
-void forward(mfh_ctx *c, uint32_t *buf, uint32_t logN) {  // complete forward transform (used for the cached G^)
-  PolyState *S = c->poly;
-  const uint32_t N = 1u << logN, half_max = 1u << (S->logmax - 1), B = std::min(logN, 11u);
-  forward_top(c, buf, logN);
-  hipLaunchKernelGGL(k_ntt_lds<false>, dim3(N >> B, 3), dim3(256), 0, c->stream, buf, N, B, S->d_tw, half_max, S->P);
-}
+
 Crt make_crt(const PolyState *S, uint32_t logN) {
   Crt C{};
   const NttPrime *q = S->P.q;
@@ -792,44 +762,45 @@ Crt make_crt(const PolyState *S, uint32_t logN) {
   return C;
 }
 
-// c[0..keep) = (a * b)[0..keep) mod p32.  bhat != null: use that precomputed forward transform (size 2^logN) instead of b.
-// nb > 1: nb products side by side, polynomial k at a + k a_stride (and b + k a_stride), result at out + k out_stride.
-// log_cyc != 0: the product in F_p[x] / (x^N - 1), N = 2^log_cyc >= la, lb (the transform of that length IS the cyclic product).  need, a_map (which polynomial at `a`
-// product k reads): see MF_NEEDED.  rev_top, nsrc, out_map: the output written reversed / into the statements of the batch (k_crt).
-int poly_mul(mfh_ctx *c, const uint32_t *a, uint32_t la, const uint32_t *b, uint32_t lb, const uint32_t *bhat, uint32_t logN_hat,
-             uint32_t *out, uint32_t keep, uint32_t nb = 1, size_t a_stride = 0, size_t out_stride = 0, const uint32_t *need = nullptr, uint32_t log_cyc = 0,
-             const uint32_t *a_map = nullptr, int64_t rev_top = -1, uint32_t nsrc = 0, const uint32_t *out_map = nullptr) {
+// One product, or nb of them side by side: out[0 .. keep) = (a * b)[0 .. keep) mod p32.
+struct PolyMul {
+  const uint32_t *a = nullptr; uint32_t la = 0;  // left operand: la coefficients
+  const uint32_t *b = nullptr; uint32_t lb = 0;  // right operand: lb coefficients (b == a and lb == la: a square) ...
+  const uint32_t *bhat = nullptr; uint32_t log_hat = 0;  // ... or, instead of b, its cached forward transform of 2^log_hat points, shared by the batch
+  uint32_t *out = nullptr; uint32_t keep = 0;
+  uint32_t nb = 1; size_t in_stride = 0, out_stride = 0;  // product k reads a + k in_stride (and b + k in_stride) and writes out + k out_stride
+  uint32_t log_cyc = 0;            // != 0: the product in F_p[x] / (x^N - 1), N = 2^log_cyc >= la, lb (the transform of that length IS the cyclic product)
+  const uint32_t *need = nullptr;  // see MF_NEEDED ...
+  const uint32_t *a_map = nullptr, *out_map = nullptr;  // ... which statement of the batch product k reads at `a` / writes at `out`
+  int64_t rev_top = -1; uint32_t nsrc = 0;  // rev_top >= 0: out[i] = coefficient rev_top - i where that lies in [0, nsrc), else zero (k_crt's reversal)
+};
+int poly_mul(mfh_ctx *c, const PolyMul &m) {
   PolyState *S = c->poly;
-  uint32_t logN = log_cyc ? log_cyc : bhat ? logN_hat : ceil_log2((size_t)la + lb - 1);
-  if (logN < 1) logN = 1;
-  if (logN > S->logmax || (log_cyc ? std::max(la, lb) : (size_t)la + lb - 1) > ((size_t)1 << logN) || (bhat && logN != logN_hat)) {
+  const uint32_t logN = std::max(m.log_cyc ? m.log_cyc : m.bhat ? m.log_hat : ceil_log2((size_t)m.la + m.lb - 1), 1u), nb = m.nb;
+  if (logN > S->logmax || (m.log_cyc ? std::max(m.la, m.lb) : (size_t)m.la + m.lb - 1) > ((size_t)1 << logN) || (m.bhat && logN != m.log_hat)) {
     c->err = "poly_mul: size exceeds the prepared NTT length";
     return MFH_EINVAL;
   }
-  const uint32_t N = 1u << logN, half_max = 1u << (S->logmax - 1), B = std::min(logN, 11u);
-  if (!forward_top(c, S->d_bufA, logN, nb, a, la, a_stride, need, a_map)) {  // (no register pass at this size: load on its own)
-    hipLaunchKernelGGL(k_ntt_load, dim3((N + 255) / 256, 3 * nb), dim3(256), 0, c->stream, a, la, N, S->P, S->d_bufA, a_stride, need, a_map);
-  }
-  const uint32_t *rhs = bhat;  // already fully transformed
-  int is_hat = 1;
-  if (!bhat) {
-    is_hat = 0;
-    if (b == a && lb == la) {
-      rhs = nullptr;  // square
-    } else {
-      if (!forward_top(c, S->d_bufB, logN, nb, b, lb, a_stride, need))
-        hipLaunchKernelGGL(k_ntt_load, dim3((N + 255) / 256, 3 * nb), dim3(256), 0, c->stream, b, lb, N, S->P, S->d_bufB, a_stride, need, (const uint32_t *)nullptr);
-      rhs = S->d_bufB;
-    }
+  const uint32_t N = 1u << logN, B = std::min(logN, 11u);
+  // an operand's coefficients go in with the first register pass, or on their own where the size has none
+  auto load_top = [&](uint32_t *buf, const NttLoad &ld) {
+    if (!ntt_top_passes(c, Ntt::forward, buf, N, logN, nb, m.need, ld)) ntt_load(c, buf, N, nb, ld, m.need);
+  };
+  load_top(S->d_bufA, {m.a, m.la, m.in_stride, m.a_map});
+  const uint32_t *rhs = m.bhat;  // already fully transformed
+  if (!m.bhat && !(m.b == m.a && m.lb == m.la)) {  // (else rhs stays null: a square)
+    load_top(S->d_bufB, {m.b, m.lb, m.in_stride});
+    rhs = S->d_bufB;
   }
   // low forward stages of both operands, pointwise product, low inverse stages: one kernel, the block never leaves LDS
-  if (B == 11 && (rhs == nullptr || is_hat))
-    hipLaunchKernelGGL(k_ntt_lds_mul8, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, S->d_bufA, rhs, N, S->d_tw, S->d_twi, half_max, S->P, need);
+  if (B == 11 && (!rhs || m.bhat))
+    hipLaunchKernelGGL(k_ntt_lds_mul8, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, S->d_bufA, rhs, N, S->d_tw, S->d_twi, S->half_max, S->P, m.need);
   else
-    hipLaunchKernelGGL(k_ntt_lds_mul, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, S->d_bufA, rhs, is_hat, N, B, S->d_tw, S->d_twi, half_max, S->P, need);
-  inverse_top(c, S->d_bufA, logN, nb, need);
-  hipLaunchKernelGGL(k_crt, dim3((keep + 255) / 256, nb), dim3(256), 0, c->stream, S->d_bufA, N, keep, S->P, make_crt(S, logN), out, out_stride, need, rev_top, nsrc,
-                     out_map);
+    hipLaunchKernelGGL(k_ntt_lds_mul, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, S->d_bufA, rhs, m.bhat ? 1 : 0, N, B, S->d_tw, S->d_twi, S->half_max, S->P,
+                       m.need);
+  ntt_top_passes(c, Ntt::inverse, S->d_bufA, N, logN, nb, m.need);
+  hipLaunchKernelGGL(k_crt, dim3((m.keep + 255) / 256, nb), dim3(256), 0, c->stream, S->d_bufA, N, m.keep, S->P, make_crt(S, logN), m.out, m.out_stride, m.need,
+                     m.rev_top, m.nsrc, m.out_map);
   HIP_TRY(c, hipGetLastError());
   return MFH_OK;
 }
@@ -854,15 +825,14 @@ bool draw_point(uint32_t *r) {
 int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &t) {
   PolyState *S = c->poly;
   S->cyc = false;
-  for (uint32_t **p : {&S->d_That, &S->d_chk})
-    if (*p) { hipFree(*p); *p = nullptr; }
   const uint32_t d = S->d;
   if (S->dt != d - 1 || d < 2) return MFH_OK;
   const uint32_t logNc = ceil_log2(d), Nc = 1u << logNc;
   if (logNc + 1 > S->logmax) return MFH_OK;  // (the linear products below have 2 Nc - 1 coefficients)
   if (!S->h_seen) HIP_TRY(c, hipHostMalloc(&S->h_seen, 64, hipHostMallocDefault));
-  if (!S->d_need) {
-    HIP_TRY(c, hipMalloc(&S->d_need, (size_t)(2 + kMaxBatch) * 4));
+  int rc;
+  if (!S->d_need.p) {
+    if ((rc = dev_reserve(c, S->d_need, (size_t)(2 + kMaxBatch) * 4))) return rc;
     HIP_TRY(c, hipMemsetAsync(S->d_need, 0, 8, c->stream));
   }
   *S->h_seen = 0;
@@ -875,11 +845,13 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
   HIP_TRY(c, hipMemsetAsync(lev, 0, (size_t)Nc * 4, c->stream));
   HIP_TRY(c, hipMemcpyAsync(lev, d_t, (size_t)d * 4, hipMemcpyDeviceToDevice, c->stream));
   std::vector<size_t> off{0};
-  int rc;
+  auto mul_tmp = [&](const uint32_t *a, const uint32_t *b, uint32_t n) {  // d_tmp <- the 2n - 1 coefficients of the linear product of two ring elements
+    return poly_mul(c, {.a = a, .la = n, .b = b, .lb = n, .out = S->d_tmp, .keep = 2 * n - 1});
+  };
   for (uint32_t n = Nc; n > 1; n >>= 1) {  // down: a_{k+1}(x^2) = a_k(x) a_k(-x)
     uint32_t *a = lev + off.back();
     hipLaunchKernelGGL(k_conj, g1(n), dim3(256), 0, c->stream, a, n, cj);
-    if ((rc = poly_mul(c, a, n, cj, n, nullptr, 0, S->d_tmp, 2 * n - 1))) return rc;
+    if ((rc = mul_tmp(a, cj, n))) return rc;
     off.push_back(off.back() + n);
     hipLaunchKernelGGL(k_fold_even, g1(n / 2), dim3(256), 0, c->stream, S->d_tmp, n, lev + off.back());
   }
@@ -894,21 +866,20 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
     const uint32_t n = Nc >> k;
     hipLaunchKernelGGL(k_conj, g1(n), dim3(256), 0, c->stream, lev + off[k], n, cj);
     hipLaunchKernelGGL(k_spread2, g1(n), dim3(256), 0, c->stream, inv[cur], n, sp);
-    if ((rc = poly_mul(c, cj, n, sp, n, nullptr, 0, S->d_tmp, 2 * n - 1))) return rc;
+    if ((rc = mul_tmp(cj, sp, n))) return rc;
     hipLaunchKernelGGL(k_fold, g1(n), dim3(256), 0, c->stream, S->d_tmp, n, inv[cur ^ 1]);
     cur ^= 1;
   }
   // t T' = 1 in the ring?  (checked, not assumed: one more product and Nc words to the host, once per SSP)
-  if ((rc = poly_mul(c, lev, Nc, inv[cur], Nc, nullptr, 0, S->d_tmp, 2 * Nc - 1))) return rc;
+  if ((rc = mul_tmp(lev, inv[cur], Nc))) return rc;
   hipLaunchKernelGGL(k_fold, g1(Nc), dim3(256), 0, c->stream, S->d_tmp, Nc, sp);
   std::vector<uint32_t> one(Nc);
   HIP_TRY(c, hipMemcpyAsync(one.data(), sp, (size_t)Nc * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (one[0] != 1 || std::any_of(one.begin() + 1, one.end(), [](uint32_t x) { return x != 0; })) return MFH_OK;
-  HIP_TRY(c, hipMalloc(&S->d_That, (size_t)3 * Nc * 4));
-  hipLaunchKernelGGL(k_ntt_load, dim3((Nc + 255) / 256, 3), dim3(256), 0, c->stream, inv[cur], Nc, Nc, S->P, S->d_That, (size_t)0, (const uint32_t *)nullptr,
-                     (const uint32_t *)nullptr);
-  forward(c, S->d_That, logNc);
+  if ((rc = dev_reserve(c, S->d_That, (size_t)3 * Nc * 4))) return rc;
+  ntt_load(c, S->d_That, Nc, 1, {inv[cur], Nc});
+  ntt_blocks_forward(c, S->d_That, Nc, logNc, 1);
   // the check points, drawn here -- for every t prepared -- unless the caller has pinned them; their powers and t at them.  Points fixed in advance (public constants)
   // would let a crafted v whose defect vanishes there pass the check (tests/exact_defect_ref.py builds one): the bound (2d / p)^4 holds for points drawn independently
   // of the input.  A drawn point that repeats an earlier one or is a root of t is drawn again.
@@ -929,7 +900,7 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
     S->chk_r[j] = r;
     S->chk_t[j++] = (uint32_t)tv;
   }
-  HIP_TRY(c, hipMalloc(&S->d_chk, pw.size() * 4));
+  if ((rc = dev_reserve(c, S->d_chk, pw.size() * 4))) return rc;
   HIP_TRY(c, hipMemcpyAsync(S->d_chk, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -940,55 +911,140 @@ int prepare_exact(mfh_ctx *c, const uint32_t *d_t, const std::vector<uint32_t> &
 
 }  // namespace
 
-// ---- blockwise transforms for ssp_rows.hip (ntt.hpp): the same kernels as the polynomial step, started at block length 2^logB instead of N --------------
+// ---- blockwise transforms (ntt.hpp): for ssp_rows.hip, and -- one block of length N per polynomial -- the cached transforms G^ and T'^ of the polynomial step --------------
 int ntt_reserve(mfh_ctx *c, uint32_t logmax) { return poly_init(c, std::max(logmax, 1u)); }
 const Primes3 &ntt_primes(const mfh_ctx *c) { return c->poly->P; }
 Crt ntt_crt_make(const mfh_ctx *c, uint32_t logB) { return make_crt(c->poly, logB); }
 void ntt_blocks_forward(mfh_ctx *c, uint32_t *buf, uint32_t N, uint32_t logB, uint32_t nb) {
-  PolyState *S = c->poly;
-  const uint32_t half_max = 1u << (S->logmax - 1), B = std::min(logB, 11u);
-  const uint32_t *nil = nullptr;
-  uint32_t top = logB - B, len = 1u << logB;
-  while (top) {  // k_ntt_dif_multi works on every block of length `len` of the buffer: a transform of length N is the case len = N
-    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;
-    dim3 g(((N >> k) + 255) / 256, 3 * nb);
-    switch (k) {
-      case 5: hipLaunchKernelGGL(k_ntt_dif_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
-      case 4: hipLaunchKernelGGL(k_ntt_dif_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
-      case 3: hipLaunchKernelGGL(k_ntt_dif_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
-      case 2: hipLaunchKernelGGL(k_ntt_dif_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
-      default: hipLaunchKernelGGL(k_ntt_dif_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_tw, half_max, S->P, nil, 0u, (size_t)0, nil, nil); break;
-    }
-    len >>= k;
-    top -= k;
-  }
-  hipLaunchKernelGGL(k_ntt_lds<false>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_tw, half_max, S->P);
+  const PolyState *S = c->poly;
+  const uint32_t B = std::min(logB, 11u);
+  ntt_top_passes(c, Ntt::forward, buf, N, logB, nb);
+  hipLaunchKernelGGL(k_ntt_lds<false>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_tw, S->half_max, S->P);
 }
 void ntt_blocks_inverse(mfh_ctx *c, uint32_t *buf, uint32_t N, uint32_t logB, uint32_t nb) {
-  PolyState *S = c->poly;
-  const uint32_t half_max = 1u << (S->logmax - 1), B = std::min(logB, 11u);
-  hipLaunchKernelGGL(k_ntt_lds<true>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_twi, half_max, S->P);
-  uint32_t top = logB - B, len = 2u << B;
-  while (top) {
-    const uint32_t k = top > 5 ? std::min(top - 3, 5u) : top;
-    dim3 g(((N >> k) + 255) / 256, 3 * nb);
-    const uint32_t *nil = nullptr;
-    switch (k) {
-      case 5: hipLaunchKernelGGL(k_ntt_dit_multi<5>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
-      case 4: hipLaunchKernelGGL(k_ntt_dit_multi<4>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
-      case 3: hipLaunchKernelGGL(k_ntt_dit_multi<3>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
-      case 2: hipLaunchKernelGGL(k_ntt_dit_multi<2>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
-      default: hipLaunchKernelGGL(k_ntt_dit_multi<1>, g, dim3(256), 0, c->stream, buf, N, len, S->d_twi, half_max, S->P, nil); break;
-    }
-    len <<= k;
-    top -= k;
-  }
+  const PolyState *S = c->poly;
+  const uint32_t B = std::min(logB, 11u);
+  hipLaunchKernelGGL(k_ntt_lds<true>, dim3(N >> B, 3 * nb), dim3(256), 0, c->stream, buf, N, B, S->d_twi, S->half_max, S->P);
+  ntt_top_passes(c, Ntt::inverse, buf, N, logB, nb);
 }
 
 void mfh_poly_destroy(mfh_ctx *c) {
   delete c->poly;
   c->poly = nullptr;
 }
+
+namespace {
+
+// G = rev(t)^-1 mod x^n by Newton iteration, g <- g (2 - f g) mod x^(2k), from g0 = the inverse of t's leading coefficient; f = rev(t) is in d_f
+int newton_inverse(mfh_ctx *c, uint32_t g0) {
+  PolyState *S = c->poly;
+  const uint32_t n = S->n, lt = S->dt + 1;
+  HIP_TRY(c, hipMemsetAsync(S->d_G, 0, (size_t)std::max(n, 2u) * 4 * 2, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(S->d_G, &g0, 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (uint32_t k = 1; k < n;) {
+    const uint32_t k2 = std::min(2 * k, n), lf = std::min(k2, lt), le = std::min(k2, lf + k - 1);
+    int rc = poly_mul(c, {.a = S->d_f, .la = lf, .b = S->d_G, .lb = k, .out = S->d_tmp, .keep = le});  // e = f g mod x^k2
+    if (rc) return rc;
+    if (le < k2) HIP_TRY(c, hipMemsetAsync(S->d_tmp + le, 0, (size_t)(k2 - le) * 4, c->stream));
+    hipLaunchKernelGGL(k_two_minus, g1(k2), dim3(256), 0, c->stream, S->d_tmp, k2);
+    rc = poly_mul(c, {.a = S->d_G, .la = k, .b = S->d_tmp, .lb = k2, .out = S->d_tmp2, .keep = k2});  // g (2 - e) mod x^k2
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(S->d_G, S->d_tmp2, (size_t)k2 * 4, hipMemcpyDeviceToDevice, c->stream));
+    k = k2;
+  }
+  return MFH_OK;
+}
+
+// ---- h = floor((v^2 - 1) / t) for a batch: the policy, the exact path, the Euclidean path (mfh_poly_h_multi) ----------------------------------------------
+// Does this batch try the exact-division path?  It needs a prepared T' and a batch: for one polynomial its launches are latency, not work.
+bool exact_policy(mfh_ctx *c, uint32_t nb) {
+  PolyState *S = c->poly;
+  if (!S->cyc || !c->poly_exact || nb < 4) return false;
+  if (c->poly_exact != 1) return true;
+  // a caller whose statements do NOT satisfy the SSP pays the cyclic products on top of the Euclidean division: after a batch in which the check has failed (seen
+  // whenever the device gets there: this is a hint, nothing is waited for) the next 64 batches take the Euclidean path alone, then the exact path is tried again
+  if (*(volatile uint32_t *)S->h_seen) {
+    *(volatile uint32_t *)S->h_seen = 0;
+    S->rest = 64;
+  }
+  if (!S->rest) return true;
+  S->rest--;
+  return false;
+}
+
+// The exact path: two cyclic products of length Nc and the check, which lists in d_need the statements whose h the Euclidean path behind has to recompute.
+int h_exact(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h, uint32_t nb) {
+  PolyState *S = c->poly;
+  const uint32_t d = S->d, logNc = S->logNc, Nc = 1u << logNc;
+  const size_t Nmax = (size_t)1 << S->logmax;
+  HIP_TRY(c, hipMemsetAsync(S->d_need, 0, 4, c->stream));
+  if (logNc >= 12 && logNc <= 16) {  // five launches: the seams between and behind the two products are fused (k_exact_seam)
+    const Crt C = make_crt(S, logNc);
+    const uint32_t K = logNc - 11;  // stages above the 2048-point blocks: one register pass, inside the seams
+    const dim3 gs(((Nc >> K) + 255) / 256, nb), gl(Nc >> 11, 3 * nb);
+    auto product = [&](const uint32_t *bhat) {
+      hipLaunchKernelGGL(k_ntt_lds_mul8, gl, dim3(256), 0, c->stream, S->d_bufA, bhat, Nc, S->d_tw, S->d_twi, S->half_max, S->P, (const uint32_t *)nullptr);
+    };
+    auto seam = [&](auto last, uint32_t *out, uint32_t keep, size_t stride) {
+      with_stages(K, [&](auto k) {
+        hipLaunchKernelGGL((k_exact_seam<k(), last()>), gs, dim3(256), 0, c->stream, S->d_bufA, Nc, S->d_tw, S->d_twi, S->half_max, S->P, C, out, keep, stride);
+      });
+    };
+    ntt_top_passes(c, Ntt::forward, S->d_bufA, Nc, logNc, nb, nullptr, {d_v, d, d});
+    product(nullptr);
+    seam(std::false_type{}, nullptr, 0, 0);  // v^2 mod x^Nc - 1, minus 1, on its way into the second transform
+    product(S->d_That);
+    seam(std::true_type{}, d_h, d, d);  // times t^-1 in the ring: h when t | v^2 - 1
+  } else {
+    int rc = poly_mul(c, {.a = d_v, .la = d, .b = d_v, .lb = d, .out = S->d_tmp, .keep = Nc, .nb = nb, .in_stride = d, .out_stride = Nmax,
+                          .log_cyc = logNc});  // v^2 mod x^Nc - 1
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sub_const0, dim3(nb), dim3(64), 0, c->stream, S->d_tmp, 1u, Nmax, (const uint32_t *)nullptr);
+    rc = poly_mul(c, {.a = S->d_tmp, .la = Nc, .lb = Nc, .bhat = S->d_That, .log_hat = logNc, .out = d_h, .keep = d, .nb = nb, .in_stride = Nmax, .out_stride = d,
+                      .log_cyc = logNc});  // times t^-1 in the ring: h when t | v^2 - 1
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_exact_check, dim3(nb), dim3(1024), 0, c->stream, d_v, d_h, d, S->d_chk, Nc, uint4{S->chk_t[0], S->chk_t[1], S->chk_t[2], S->chk_t[3]},
+                     S->d_need, S->h_seen);
+  return MFH_OK;
+}
+
+// The Euclidean path: q = rev( rev(A)[:n] * G mod x^n ), A = v^2 - 1.  need: nullptr = every statement of the batch, else the list the exact path's check left
+int h_euclid(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h, uint32_t nb, const uint32_t *need) {
+  PolyState *S = c->poly;
+  const uint32_t d = S->d, n = S->n;
+  const size_t Nmax = (size_t)1 << S->logmax;
+  const uint32_t *map = need ? need + 2 : nullptr;
+  int rc;
+  if (S->dt >= 1) {
+    // rev(A)[:n] (2d - 1 coefficients, nominal degree 2d - 2): coefficients dt .. 2d - 2 of the square, written reversed by the kernel that produces them
+    // (the "- 1" sits at coefficient 0, which the quotient does not see when deg t >= 1)
+    rc = poly_mul(c, {.a = d_v, .la = d, .b = d_v, .lb = d, .out = S->d_tmp2, .keep = n, .nb = nb, .in_stride = d, .out_stride = Nmax, .need = need, .a_map = map,
+                      .rev_top = (int64_t)(2 * d - 2), .nsrc = 2 * d - 1});
+    if (rc) return rc;
+    // qrev = rev(A)[:n] * G mod x^n, turned back: h[i] = qrev[n - 1 - i] for i < min(n, d), zero above
+    rc = poly_mul(c, {.a = S->d_tmp2, .la = n, .lb = n, .bhat = S->d_Ghat, .log_hat = S->logN2, .out = d_h, .keep = d, .nb = nb, .in_stride = Nmax, .out_stride = d,
+                      .need = need, .out_map = map, .rev_top = (int64_t)n - 1, .nsrc = n});
+    if (rc) return rc;
+  } else {  // deg t = 0 (division by a constant): the general sequence
+    rc = poly_mul(c, {.a = d_v, .la = d, .b = d_v, .lb = d, .out = S->d_tmp, .keep = 2 * d - 1, .nb = nb, .in_stride = d, .out_stride = Nmax, .need = need,
+                      .a_map = map});
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sub_const0, dim3(nb), dim3(64), 0, c->stream, S->d_tmp, 1u, Nmax, need);
+    // rev(A)[:n]
+    hipLaunchKernelGGL(k_reverse, dim3((n + 255) / 256, nb), dim3(256), 0, c->stream, S->d_tmp, (int64_t)(2 * d - 2), n, S->d_tmp2, Nmax, Nmax, need);
+    // qrev = rev(A)[:n] * G mod x^n
+    rc = poly_mul(c, {.a = S->d_tmp2, .la = n, .lb = n, .bhat = S->d_Ghat, .log_hat = S->logN2, .out = S->d_tmp, .keep = n, .nb = nb, .in_stride = Nmax,
+                      .out_stride = Nmax, .need = need});
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_unreverse_pad, dim3((d + 255) / 256, nb), dim3(256), 0, c->stream, S->d_tmp, n, d, d_h, Nmax, (size_t)d, need, map);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -997,7 +1053,7 @@ int mfh_poly_mul(mfh_ctx *c, const uint32_t *d_a, size_t la, const uint32_t *d_b
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = poly_init(c, std::max(ceil_log2(la + lb - 1), 1u));
   if (rc) return rc;
-  return poly_mul(c, d_a, (uint32_t)la, d_b, (uint32_t)lb, nullptr, 0, d_c, (uint32_t)(la + lb - 1));
+  return poly_mul(c, {.a = d_a, .la = (uint32_t)la, .b = d_b, .lb = (uint32_t)lb, .out = d_c, .keep = (uint32_t)(la + lb - 1)});
 }
 
 int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
@@ -1026,37 +1082,18 @@ int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
   int rc = poly_init(c, logmax);
   if (rc) return rc;
   PolyState *S = c->poly;
-  for (uint32_t **p : {&S->d_G, &S->d_Ghat, &S->d_f})
-    if (*p) { hipFree(*p); *p = nullptr; }
   S->have_t = false;
   S->d = d; S->dt = (uint32_t)dt; S->n = n;
   S->logN2 = std::max(ceil_log2((size_t)2 * n - 1), 1u);
   const uint32_t N2 = 1u << S->logN2;
-  HIP_TRY(c, hipMalloc(&S->d_G, (size_t)std::max(n, 2u) * 4 * 2));
-  HIP_TRY(c, hipMalloc(&S->d_Ghat, (size_t)3 * N2 * 4));
-  HIP_TRY(c, hipMalloc(&S->d_f, (size_t)(dt + 1) * 4));
+  if ((rc = dev_reserve(c, S->d_G, (size_t)std::max(n, 2u) * 4 * 2))) return rc;
+  if ((rc = dev_reserve(c, S->d_Ghat, (size_t)3 * N2 * 4))) return rc;
+  if ((rc = dev_reserve(c, S->d_f, (size_t)(dt + 1) * 4))) return rc;
   hipLaunchKernelGGL(k_reverse, g1((uint32_t)dt + 1), dim3(256), 0, c->stream, d_t, dt, (uint32_t)dt + 1, S->d_f);  // f = rev(t)
-  // Newton: g <- g (2 - f g) mod x^(2k)
-  uint32_t g0 = invp(t[dt]);
-  HIP_TRY(c, hipMemsetAsync(S->d_G, 0, (size_t)std::max(n, 2u) * 4 * 2, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(S->d_G, &g0, 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (uint32_t k = 1; k < n;) {
-    const uint32_t k2 = std::min(2 * k, n);
-    const uint32_t lf = std::min(k2, (uint32_t)dt + 1);
-    rc = poly_mul(c, S->d_f, lf, S->d_G, k, nullptr, 0, S->d_tmp, std::min(k2, lf + k - 1));  // e = f g mod x^k2
-    if (rc) return rc;
-    if (lf + k - 1 < k2) HIP_TRY(c, hipMemsetAsync(S->d_tmp + (lf + k - 1), 0, (size_t)(k2 - (lf + k - 1)) * 4, c->stream));
-    hipLaunchKernelGGL(k_two_minus, g1(k2), dim3(256), 0, c->stream, S->d_tmp, k2);
-    rc = poly_mul(c, S->d_G, k, S->d_tmp, k2, nullptr, 0, S->d_tmp2, k2);  // g (2 - e) mod x^k2
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(S->d_G, S->d_tmp2, (size_t)k2 * 4, hipMemcpyDeviceToDevice, c->stream));
-    k = k2;
-  }
+  if ((rc = newton_inverse(c, invp(t[dt])))) return rc;
   // forward transform of G at the size used per proof
-  hipLaunchKernelGGL(k_ntt_load, dim3((N2 + 255) / 256, 3), dim3(256), 0, c->stream, S->d_G, n, N2, S->P, S->d_Ghat, (size_t)0, (const uint32_t *)nullptr,
-                     (const uint32_t *)nullptr);
-  forward(c, S->d_Ghat, S->logN2);
+  ntt_load(c, S->d_Ghat, N2, 1, {S->d_G, n});
+  ntt_blocks_forward(c, S->d_Ghat, N2, S->logN2, 1);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if ((rc = prepare_exact(c, d_t, t))) return rc;
@@ -1065,7 +1102,7 @@ int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
 }
 
 // h_k = floor((v_k^2 - 1) / t) for nb polynomials side by side (v_k = d_v + k d, h_k = d_h + k d): the same launches as for one, nb times
-// the work each
+// the work each.  The exact path's check leaves the statements that failed it to the Euclidean kernels queued behind: none, as a rule
 int mfh_poly_h_multi(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h, uint32_t nb) {
   if (!c || !d_v || !d_h || !nb || nb > kMaxBatch) return MFH_EINVAL;
   PolyState *S = c->poly;
@@ -1074,84 +1111,11 @@ int mfh_poly_h_multi(mfh_ctx *c, const uint32_t *d_v, uint32_t *d_h, uint32_t nb
     return MFH_EINVAL;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = poly_batch_reserve(c, nb);
+  int rc = poly_batch_reserve(c, S, nb);
   if (rc) return rc;
-  const uint32_t d = S->d, n = S->n;
-  const size_t Nmax = (size_t)1 << S->logmax;
-  // the exact-division path (a batch: for one polynomial the launches below are latency, not work): two cyclic products of length Nc and the check
-  const uint32_t *need = nullptr;
-  bool exact = S->cyc && c->poly_exact && nb >= 4;
-  if (exact && c->poly_exact == 1) {
-    // a caller whose statements do NOT satisfy the SSP pays the cyclic products on top of the Euclidean division: after a batch in which the check has failed (seen
-    // whenever the device gets there: this is a hint, nothing is waited for) the next 64 batches take the Euclidean path alone, then the exact path is tried again
-    if (*(volatile uint32_t *)S->h_seen) {
-      *(volatile uint32_t *)S->h_seen = 0;
-      S->rest = 64;
-    }
-    if (S->rest) {
-      S->rest--;
-      exact = false;
-    }
-  }
-  if (exact) {
-    const uint32_t Nc = 1u << S->logNc;
-    HIP_TRY(c, hipMemsetAsync(S->d_need, 0, 4, c->stream));
-    if (S->logNc >= 12 && S->logNc <= 16) {  // five launches: the seams between and behind the two products are fused (k_exact_seam)
-      const uint32_t half_max = 1u << (S->logmax - 1), K = S->logNc - 11;
-      const Crt C = make_crt(S, S->logNc);
-      const dim3 gs(((Nc >> K) + 255) / 256, nb), gl(Nc >> 11, 3 * nb);
-      forward_top(c, S->d_bufA, S->logNc, nb, d_v, d, d);
-      hipLaunchKernelGGL(k_ntt_lds_mul8, gl, dim3(256), 0, c->stream, S->d_bufA, (const uint32_t *)nullptr, Nc, S->d_tw, S->d_twi, half_max, S->P, (const uint32_t *)nullptr);
-#define MF_SEAM(K_, LAST_, out_, keep_, stride_) \
-  hipLaunchKernelGGL((k_exact_seam<K_, LAST_>), gs, dim3(256), 0, c->stream, S->d_bufA, Nc, S->d_tw, S->d_twi, half_max, S->P, C, out_, keep_, stride_)
-#define MF_SEAM_K(LAST_, out_, keep_, stride_)                  \
-  switch (K) {                                                  \
-    case 1: MF_SEAM(1, LAST_, out_, keep_, stride_); break;     \
-    case 2: MF_SEAM(2, LAST_, out_, keep_, stride_); break;     \
-    case 3: MF_SEAM(3, LAST_, out_, keep_, stride_); break;     \
-    case 4: MF_SEAM(4, LAST_, out_, keep_, stride_); break;     \
-    default: MF_SEAM(5, LAST_, out_, keep_, stride_); break;    \
-  }
-      MF_SEAM_K(false, (uint32_t *)nullptr, 0u, (size_t)0)  // v^2 mod x^Nc - 1, minus 1, on its way into the second transform
-      hipLaunchKernelGGL(k_ntt_lds_mul8, gl, dim3(256), 0, c->stream, S->d_bufA, (const uint32_t *)S->d_That, Nc, S->d_tw, S->d_twi, half_max, S->P, (const uint32_t *)nullptr);
-      MF_SEAM_K(true, d_h, d, (size_t)d)  // times t^-1 in the ring: h when t | v^2 - 1
-#undef MF_SEAM_K
-#undef MF_SEAM
-    } else {
-      rc = poly_mul(c, d_v, d, d_v, d, nullptr, 0, S->d_tmp, Nc, nb, d, Nmax, nullptr, S->logNc);  // v^2 mod x^Nc - 1
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_sub_const0, dim3(nb), dim3(64), 0, c->stream, S->d_tmp, 1u, Nmax, (const uint32_t *)nullptr);
-      rc = poly_mul(c, S->d_tmp, Nc, nullptr, Nc, S->d_That, S->logNc, d_h, d, nb, Nmax, d, nullptr, S->logNc);  // times t^-1 in the ring: h when t | v^2 - 1
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_exact_check, dim3(nb), dim3(1024), 0, c->stream, d_v, d_h, d, S->d_chk, Nc, uint4{S->chk_t[0], S->chk_t[1], S->chk_t[2], S->chk_t[3]},
-                       S->d_need, S->h_seen);
-    need = S->d_need;  // the Euclidean kernels below work through the statements that failed the check: none, as a rule
-  }
-  const uint32_t *map = need ? need + 2 : nullptr;
-  if (S->dt >= 1) {
-    // rev(A)[:n], A = v^2 - 1 (2d - 1 coefficients, nominal degree 2d - 2): coefficients dt .. 2d - 2 of the square, written reversed by the kernel that produces them
-    // (the "- 1" sits at coefficient 0, which the quotient does not see when deg t >= 1)
-    rc = poly_mul(c, d_v, d, d_v, d, nullptr, 0, S->d_tmp2, n, nb, d, Nmax, need, 0, map, (int64_t)(2 * d - 2), 2 * d - 1);
-    if (rc) return rc;
-    // qrev = rev(A)[:n] * G mod x^n, turned back: h[i] = qrev[n - 1 - i] for i < min(n, d), zero above
-    rc = poly_mul(c, S->d_tmp2, n, nullptr, n, S->d_Ghat, S->logN2, d_h, d, nb, Nmax, d, need, 0, nullptr, (int64_t)n - 1, n, map);
-    if (rc) return rc;
-    HIP_TRY(c, hipGetLastError());
-    return MFH_OK;
-  }
-  // deg t = 0 (division by a constant): the general sequence
-  rc = poly_mul(c, d_v, d, d_v, d, nullptr, 0, S->d_tmp, 2 * d - 1, nb, d, Nmax, need, 0, map);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_sub_const0, dim3(nb), dim3(64), 0, c->stream, S->d_tmp, 1u, Nmax, need);
-  // rev(A)[:n]
-  hipLaunchKernelGGL(k_reverse, dim3((n + 255) / 256, nb), dim3(256), 0, c->stream, S->d_tmp, (int64_t)(2 * d - 2), n, S->d_tmp2, Nmax, Nmax, need);
-  // qrev = rev(A)[:n] * G mod x^n
-  rc = poly_mul(c, S->d_tmp2, n, nullptr, n, S->d_Ghat, S->logN2, S->d_tmp, n, nb, Nmax, Nmax, need);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_unreverse_pad, dim3((d + 255) / 256, nb), dim3(256), 0, c->stream, S->d_tmp, n, d, d_h, Nmax, (size_t)d, need, map);
-  HIP_TRY(c, hipGetLastError());
-  return MFH_OK;
+  const bool exact = exact_policy(c, nb);
+  if (exact && (rc = h_exact(c, d_v, d_h, nb))) return rc;
+  return h_euclid(c, d_v, d_h, nb, exact ? (const uint32_t *)S->d_need : nullptr);
 }
 int mfh_set_poly_exact(mfh_ctx *c, int mode) {
   if (!c || mode < 0 || mode > 2) return MFH_EINVAL;

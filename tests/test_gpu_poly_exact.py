@@ -74,7 +74,7 @@ def _mul(c, a, b=None):
 @pytest.mark.parametrize("k", range(1, MAX_LOG + 1))
 def test_poly_mul_at_every_transform_length(ctx, kron, pool, k):
     """la + lb - 1 = 2^k exactly and 2^k + 1 (the padding step to the next length), distinct operands (k_ntt_lds_mul) and squares (k_ntt_lds_mul8 at 2^11 points
-    and up): random coefficients against GMP, and at every k constant and monomial operands against closed forms.  This walks every forward_top / inverse_top
+    and up): random coefficients against GMP, and at every k constant and monomial operands against closed forms.  This walks every ntt_top_passes
     split of the register passes (one pass of 1..5 stages, 4 + 3, 5 + 3, 3 + 3, 5 + 5, 5 + 3 + 3, 5 + 4 + 3)."""
     n = 1 << k
     rng = np.random.default_rng(7000 + k)
@@ -348,6 +348,40 @@ def test_growing_poly_mul_after_prepare_t(gpu_ctx_factory, oracle, kron, mf):
     c.poly_prepare_t(_dev(c, t))
     assert np.array_equal(_host(c, c.poly_h_many(d_v, nb), (nb, d)), exp)
     assert c.poly_exact_fallbacks() == 0
+    c.close()
+
+
+def test_prepared_t_across_preparations_in_one_context(gpu_ctx_factory, oracle, kron, mf):
+    """The per-SSP buffers of a context only grow, so a preparation finds the buffers of the one before it: nothing of an earlier t may be read.  d = 4100 is the
+    smallest shape that takes the fused seam (logNc = 13, K = 2).  A poly_mul of 2^15 coefficients comes first: it sizes the NTT tables for all that follows (the
+    degree-3 t needs 2^15, the dense ones 2^14), so no preparation rebuilds the state and the buffers do carry over.  Then a dense t; a t of degree 3 (no exact path,
+    a longer quotient and G; the transform of t^-1 and the check powers of step 1 stay behind, unused); another dense t, which writes its own over them and feeds them
+    to k_exact_seam / k_exact_check; and a fourth, dense again, over step 3's -- every quotient against GMP's division."""
+    d, nb = 4100, 6
+    rng = np.random.default_rng(4100)
+    p = mf.Params(d=d, m=3)
+    c = gpu_ctx_factory(p)
+    c.set_poly_exact(2)
+    a, b = _rand(rng, 1 << 14), _rand(rng, (1 << 14) + 1)
+    assert np.array_equal(_mul(c, a, b), kron.mul(a, b))
+    points = []
+    for step, seed in ((1, 11), (2, None), (3, 33), (4, 44)):
+        if seed is None:  # step 2: deg t = 3, statements that do not divide
+            t = np.zeros(d, np.uint32)
+            t[:4] = _rand(rng, 4)
+            V = np.stack([_rand(rng, d) for _ in range(nb)])
+        else:
+            _, t, v_ok = _ssp(oracle, mf, d, 3, np.random.default_rng(seed))
+            V = _valid(v_ok, t, rng.integers(0, P, size=nb, dtype=np.uint64))
+        exp = np.stack([kron.div(v, t)[:d] for v in V])
+        c.poly_prepare_t(_dev(c, t))
+        assert c.poly_exact_fallbacks() == (-1 if seed is None else 0), step
+        assert np.array_equal(_host(c, c.poly_h_many(_dev(c, V), nb), (nb, d)), exp), step
+        assert np.array_equal(_host(c, c.poly_h(_dev(c, V[-1]))), exp[-1]), step
+        assert c.poly_exact_fallbacks() == (-1 if seed is None else 0), step
+        if seed is not None:
+            points.append(c.exact_points())
+    assert points[0] != points[1] and points[1] != points[2]  # drawn per preparation
     c.close()
 
 
