@@ -102,7 +102,7 @@ EXPORTS = [
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
-    "mfh_merkle_absent_rows",
+    "mfh_merkle_absent_rows", "mfh_merkle_insert_keys",
 ]
 
 
@@ -241,6 +241,7 @@ def load_library():
         "mfh_merkle_update_rows": (i32, [vp, vp, u32, vp, vp, vp, sz, vp]),
         "mfh_merkle_update_records": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, vp, sz, vp]),
         "mfh_merkle_absent_rows": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, vp]),
+        "mfh_merkle_insert_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -552,6 +553,49 @@ class MerkleTree:
         for words.MerkleAbsent(key_bytes, length, depth)"""
         rows, index, status = self._absent(table, keys, "absent_bits", True)
         return self._unpack(rows, 32, np.ascontiguousarray(keys).shape[1] + int(table.shape[1])), index, status
+
+    def insert_keys(self, table, keys, payloads=None, roots=False):
+        """(rows, index): nk sequential key inserts into an INDEXED table (words.MerkleAbsent has the data model) and this tree in one call
+        (mfh_merkle_insert_keys; waits for the stream).  Insert j changes the hi of the record whose range holds keys[j] and writes the record (keys[j] | the old
+        hi | payloads[j]) into the lowest inert slot; a later key may fall into a range an earlier one has split.  rows is np.uint8 [nk, 64 + key_bytes + 3
+        length + 64 depth + ceil(2 depth / 8)]: row j is the packed input row of words.MerkleInsert(key_bytes, length, depth) taken from table and tree as
+        they stood before insert j.  index is np.uint32 [nk, 2]: (the slot whose hi changed, the slot that received the new record).  With roots=True a
+        triple whose last element is np.uint8 [nk + 1, 32], the roots R_0 .. R_nk: statement j is MerkleInsert.statement(R_j, R_j+1, keys[j]).
+        table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, all different.  payloads: None (all
+        zero) or np.uint8 [nk, length - 2 key_bytes].  MfhError with the library's text, table and tree untouched, when a key is a member already, no record
+        holds a key, or the table has fewer than nk inert slots."""
+        c = self._ctx
+        tab, tstride, length = self._table(table, "insert_keys")
+        k = np.ascontiguousarray(keys)
+        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
+            raise MfhError("insert_keys: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        nk, kb = k.shape
+        pay = None
+        if payloads is not None:
+            pay = np.ascontiguousarray(payloads)
+            if pay.dtype != np.uint8 or pay.shape != (nk, length - 2 * kb):
+                raise MfhError("insert_keys: payloads are uint8 [nk, length - 2 key_bytes]")
+        rows = np.zeros((nk, 64 + kb + 3 * length + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
+        index = np.zeros((nk, 2), dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots else None
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_insert_keys(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(pay.ctypes.data) if pay is not None else None,
+                                            length - 2 * kb, vp(rows.ctypes.data), rows.shape[1], vp(r.ctypes.data) if roots else None, vp(index.ctypes.data),
+                                            vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif roots:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        return (rows, index, r) if roots else (rows, index)
+
+    def insert_bits(self, table, keys, payloads=None, roots=False):
+        """insert_keys with the rows as np.uint8 [nk, 512 + 8 key_bytes + 24 length + 514 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
+        words.MerkleInsert(key_bytes, length, depth)"""
+        out = self.insert_keys(table, keys, payloads, roots)
+        head = 64 + np.ascontiguousarray(keys).shape[1] + 3 * int(table.shape[1])
+        bits = np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth]
+        return (bits,) + tuple(out[1:])
 
 
 class Context:

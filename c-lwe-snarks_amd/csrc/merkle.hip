@@ -22,11 +22,14 @@
 // the last new record of each leaf into the table behind them.
 // k_key_locate, k_absent_gather: mfh_merkle_absent_rows, which finds for every query key the record of an indexed table whose range (lo, hi) holds it, or
 // whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp).
+// k_inert_flags, k_inert_scan, k_inert_select, k_insert_records: mfh_merkle_insert_keys, a batch of sequential key inserts into an indexed table in one call --
+// the lowest inert slots found on the device, all new records built in one launch, then the record updates above (the host's plan: merkle_insert.hpp).
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
 #include <functional>
 
 #include "ctx.hpp"
+#include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
 #include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
@@ -367,6 +370,136 @@ __global__ __launch_bounds__(256) void k_absent_gather(const uint8_t *__restrict
   heads[g] = load_unit_within(table, a, a + min(16u, length - off), span);
 }
 
+// ---- mfh_merkle_insert_keys: the lowest nk inert slots of an indexed table, ascending, and the 2 nk new records of a batch of inserts.
+//
+// The inert search, three launches, none of which depends on the order in which threads or workgroups run (no atomics):
+//   k_inert_flags<KW>  one thread per record i < n, 256 a workgroup: lo and hi through load_key_words as k_key_locate loads them (any alignment, nothing outside
+//                      the table's span), inert = !(lo < hi); a wave's ballot is 64 flags at once -- lane 0 stores it as mask[i / 64] (threads past n: flag
+//                      0), and the workgroup's four popcounts meet in LDS (16 bytes) as count[blockIdx].  The masks stay on the device: 2^depth / 8 bytes.
+//   k_inert_scan       ONE workgroup of 256 threads: count[0 .. nb) <- its exclusive prefix sums, and total[0] <- the number of inert slots.  Thread t sums
+//                      the contiguous segment [t seg, (t + 1) seg), seg = ceil(nb / 256); the 256 segment sums are scanned in LDS (1 KiB, Hillis-Steele,
+//                      8 steps), then every thread writes its segment's running prefix.  nb <= 2^16 (depth <= 24): seg <= 256.
+//   k_inert_select     one thread per mask word g: its first inert slot has rank count[g / 4] + the popcounts of the workgroup's earlier words; the set bits
+//                      of ranks below nk go to slots[rank] = 64 g + bit.  A word whose base rank is not below nk does nothing: with nk far below the number
+//                      of inert slots almost every thread leaves after one load.  Every rank below min(nk, total) is written exactly once.
+template <int KW>
+__global__ __launch_bounds__(256) void k_inert_flags(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t n,
+                                                     unsigned long long *__restrict__ mask, uint32_t *__restrict__ count) {
+  __shared__ uint32_t part[4];
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool inert = false;
+  if (i < n) {
+    uint32_t lo[KW], hi[KW];
+    const int64_t at = (int64_t)((size_t)i * stride);
+    load_key_words<KW>(table, at, key_bytes, span, lo);
+    load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
+    inert = !key_less<KW>(lo, hi);
+  }
+  const unsigned long long flags = __ballot(inert);
+  if (lane == 0) {
+    mask[blockIdx.x * 4 + wave] = flags;  // (the mask array has 4 words a workgroup: words past n / 64 are zero)
+    part[wave] = (uint32_t)__popcll(flags);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) count[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+__global__ __launch_bounds__(256) void k_inert_scan(uint32_t *__restrict__ count, uint32_t nb, uint32_t *__restrict__ total) {
+  __shared__ uint32_t sums[256];
+  const uint32_t t = threadIdx.x, seg = (nb + 255) / 256, b0 = min(t * seg, nb), b1 = min(b0 + seg, nb);
+  uint32_t mine = 0;
+  for (uint32_t b = b0; b < b1; b++) mine += count[b];
+  sums[t] = mine;
+  __syncthreads();
+  for (uint32_t step = 1; step < 256; step <<= 1) {
+    const uint32_t below = t >= step ? sums[t - step] : 0u;
+    __syncthreads();
+    sums[t] += below;
+    __syncthreads();
+  }
+  uint32_t run = sums[t] - mine;  // exclusive
+  for (uint32_t b = b0; b < b1; b++) {
+    const uint32_t c = count[b];
+    count[b] = run;
+    run += c;
+  }
+  if (t == 255) total[0] = sums[255];
+}
+
+__global__ __launch_bounds__(256) void k_inert_select(const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ count, uint32_t nwords, uint32_t nk,
+                                                      uint32_t *__restrict__ slots) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= nwords) return;
+  uint32_t rank = count[g >> 2];
+  if (rank >= nk) return;
+  for (uint32_t w = g & ~3u; w < g; w++) rank += (uint32_t)__popcll(mask[w]);
+  unsigned long long m = mask[g];
+  while (m && rank < nk) {
+    slots[rank++] = 64 * g + (uint32_t)(__ffsll(m) - 1);
+    m &= m - 1;
+  }
+}
+
+// k_insert_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
+// aligned).  One item per record r and 16-byte unit u; the store is the whole unit.  With (p, pred, succ) = plan[3 j ..] of insert j (merkle_insert.hpp):
+//   record 2 j      the predecessor with hi <- key_j: the table's record p with bytes [K, 2K) replaced (pred < 0), else key_pred | key_j | payload_pred
+//   record 2 j + 1  key_j | (succ < 0 ? the hi of the table's record p : key_succ) | payload_j, zero-padded to `length`
+// No record of the batch depends on another: a predecessor's lo and payload never change during the batch (an insert rewrites only the hi of an existing
+// record), and with succ < 0 no earlier insert of the batch lies between key_j and the table's hi, so every source is the table as it stood BEFORE the
+// batch, the keys, or the payloads -- one launch, no ordering among the items, and the table is only read.
+// A record is three byte ranges, lo [0, K), hi [K, 2K) and the payload [2K, length), each with its own source; K need not be a multiple of 4 and the
+// table sits at any byte alignment, so a unit may straddle the ranges anywhere.  Per range that meets the unit, load_unit_within fetches the 16 bytes of its
+// source that line up with the unit (source offset = unit offset - the range's start + the source's start; it may be negative, bytes outside the source's
+// span come out zero and are masked away), and the unit is the three loads merged under per-dword byte masks.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [keys, keys + nk K) and [pay, pay + nk (length - 2K)) (pay = null: zero payloads).
+__device__ __forceinline__ uint32_t bytes_in(int64_t o, int64_t lo, int64_t hi) {  // mask of the bytes o .. o + 3 that lie in [lo, hi)
+  uint32_t m = 0;
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+    if (o + b >= lo && o + b < hi) m |= 0xFFu << (8 * b);
+  return m;
+}
+
+__device__ __forceinline__ uint4 merge_unit(uint4 acc, uint4 v, int64_t o, int64_t lo, int64_t hi) {
+  const uint32_t m0 = bytes_in(o, lo, hi), m1 = bytes_in(o + 4, lo, hi), m2 = bytes_in(o + 8, lo, hi), m3 = bytes_in(o + 12, lo, hi);
+  return make_uint4(acc.x | (v.x & m0), acc.y | (v.y & m1), acc.z | (v.z & m2), acc.w | (v.w & m3));
+}
+
+__global__ __launch_bounds__(256) void k_insert_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ keys,
+                                                        const uint8_t *__restrict__ pay, const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t length,
+                                                        uint32_t nk, uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (2 nk units < 2^32: checked by the host)
+  if (g >= 2 * nk * units) return;
+  const uint32_t r = g / units, u = g - r * units, j = r >> 1, side = r & 1;
+  const int64_t o = 16 * (int64_t)u, K = key_bytes, plen = (int64_t)length - 2 * K;
+  const int64_t keys_span = (int64_t)nk * K, pay_span = (int64_t)nk * plen;
+  const uint32_t p = (uint32_t)plan[3 * j];
+  const int32_t pred = plan[3 * j + 1], succ = plan[3 * j + 2];
+  const int64_t rec_p = (int64_t)((size_t)p * table_stride);  // the table's record p, as an offset
+  // the source of each range: `key` >= 0 = that insert's key / payload, -1 = the table's record p, in place
+  const int32_t lo_key = side ? (int32_t)j : pred, hi_key = side ? succ : (int32_t)j, pay_key = side ? (int32_t)j : pred;
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (o < K) {  // lo
+    const int64_t e = min(o + 16, K);
+    const uint4 v = lo_key >= 0 ? load_unit_within(keys, lo_key * K + o, lo_key * K + e, keys_span) : load_unit_within(table, rec_p + o, rec_p + e, table_span);
+    out = merge_unit(out, v, o, 0, K);
+  }
+  if (o < 2 * K && o + 16 > K) {  // hi
+    const int64_t e = min(o + 16, 2 * K);
+    const uint4 v = hi_key >= 0 ? load_unit_within(keys, hi_key * K + o - K, hi_key * K + e - K, keys_span) : load_unit_within(table, rec_p + o, rec_p + e, table_span);
+    out = merge_unit(out, v, o, K, 2 * K);
+  }
+  if (o + 16 > 2 * K && plen > 0) {  // the payload
+    const int64_t e = min(o + 16, (int64_t)length);
+    if (pay_key < 0) {
+      out = merge_unit(out, load_unit_within(table, rec_p + o, rec_p + e, table_span), o, 2 * K, length);
+    } else if (pay) {
+      out = merge_unit(out, load_unit_within(pay, pay_key * plen + o - 2 * K, pay_key * plen + e - 2 * K, pay_span), o, 2 * K, length);
+    }
+  }
+  fresh[g] = out;
+}
+
 }  // namespace
 
 struct mfh_merkle {
@@ -493,12 +626,24 @@ int path_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_ind
 // k_merkle_update_level and the tree's write-back, `after` (if any) queues what has to follow that, the level rows, the heads and the roots come back, and
 // `rows_out` takes them from the pinned buffer with the stream idle.  On the device: V[0] (own leaves only) | V[1 .. depth], slots of ch nodes | level rows |
 // heads | the schedule (idx | last | same0 | sib[depth]).  Pinned: level rows | heads | R_b0, the chunk's new roots
+// A batch of inserts (mfh_merkle_insert_keys) drives the same body with `pairs`: chunks of whole inserts (mf::insert_chunk: an even number of updates), the first
+// `skip` bytes of the scratch (a multiple of 16, reserved by the caller with update_rows_bytes behind them) left to the caller, h_roots given every second root,
+// and rows_out = null for "no rows": then nothing but the roots comes back.
+struct Pairs {
+  uint32_t ch;  // updates a chunk
+  size_t skip;
+};
+
+size_t update_rows_bytes(uint32_t depth, uint32_t ch, size_t hs, uint32_t own) {
+  return (size_t)(depth + own) * ch * 32 + (size_t)ch * (mf::staged_stride(mf::row_bytes(64, 64, depth)) + hs) + (size_t)(depth + 3) * ch * 4;
+}
+
 int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_roots, size_t rowb, size_t hs,
-                const std::function<int(const Chunk &)> &before, const ChunkFn &after, const ChunkFn &rows_out) {
-  const uint32_t depth = t->depth, ch = mf::update_chunk(nupd, rowb, kPathStageBytes), own = !d_new_leaves;
-  const size_t rs = mf::staged_stride(mf::row_bytes(64, 64, depth)), slot = (size_t)ch * 32, sched_words = (size_t)(depth + 3) * ch;
-  if (int rc = work_reserve(c, c->circ_io, (depth + own) * slot + (size_t)ch * (rs + hs) + sched_words * 4)) return rc;
-  uint4 *d_own = c->circ_io.as<uint4>(), *d_v = d_own + own * slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
+                const std::function<int(const Chunk &)> &before, const ChunkFn &after, const ChunkFn &rows_out, const Pairs *pairs = nullptr) {
+  const uint32_t depth = t->depth, ch = pairs ? pairs->ch : mf::update_chunk(nupd, rowb, kPathStageBytes), own = !d_new_leaves, step = pairs ? 2 : 1;
+  const size_t rs = mf::staged_stride(mf::row_bytes(64, 64, depth)), slot = (size_t)ch * 32, skip = pairs ? pairs->skip : 0;
+  if (int rc = work_reserve(c, c->circ_io, skip + update_rows_bytes(depth, ch, hs, own))) return rc;
+  uint4 *d_own = reinterpret_cast<uint4 *>(c->circ_io.as<uint8_t>() + skip), *d_v = d_own + own * slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
   uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
   uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32);
   if (!pin_out) return MFH_ENOMEM;
@@ -528,13 +673,47 @@ int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_inde
       hipLaunchKernelGGL(k_merkle_update_store, dim3((k + 255) / 256, depth + 1), dim3(256), 0, c->stream, nodes, depth, k, u.d_idx, u.d_last, d_leaves, (const uint4 *)d_v, slot / 16);
     }
     if (after) after(u);
-    if (int rc = stage_out(c, u)) return rc;
+    if (rows_out) {
+      if (int rc = stage_out(c, u)) return rc;
+    } else {
+      HIP_TRY(c, hipGetLastError());
+    }
     if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    rows_out(u);
-    if (h_roots) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
+    if (rows_out) rows_out(u);
+    if (h_roots && step == 1) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
+    if (h_roots && step == 2) {  // (b0 and k are even) R_0, then the root behind every insert's second update
+      if (!b0) memcpy(h_roots, pin_roots, 32);
+      for (uint32_t b = 1; b < k; b += 2) memcpy(h_roots + (size_t)32 * ((b0 + b + 1) / 2), pin_roots + (size_t)32 * (b + 1), 32);
+    }
   }
   return MFH_OK;
+}
+
+// nupd sequential record updates, records h_index[k] of the table <- the records at d_fresh + k * new_stride (device memory, whoever wrote it: the caller's new
+// records, or what k_insert_records built), through update_rows: per chunk the new leaves = the digests of the chunk's new records, a head = the old record | the
+// new record at a pitch of record_head_pitch(length) each, and the table's write-back behind the levels.  rows_out = null: no gather, nothing staged out.
+int record_updates(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length, const uint8_t *d_fresh,
+                   size_t new_stride, uint8_t *h_roots, size_t rowb, const Pairs *pairs, const ChunkFn &rows_out) {
+  const uint32_t depth = t->depth;
+  const size_t hp = mf::record_head_pitch(length);
+  const int64_t table_span = (int64_t)((((size_t)1 << depth) - 1) * table_stride + length), fresh_span = (int64_t)((size_t)(nupd - 1) * new_stride + length);
+  auto hash_and_gather = [&](const Chunk &u) -> int {
+    if (int rc = sha256_records(c, d_fresh + (size_t)u.b0 * new_stride, new_stride, length, u.k, reinterpret_cast<uint8_t *>(u.d_own_leaves))) return rc;
+    if (!rows_out) return MFH_OK;
+    Timer tm(c, 29, u.k);  // "merkle_record_rows" (mfhip.hip: timing_kind): the gather
+    const uint32_t items = u.k * 2 * (uint32_t)(hp / 16);
+    hipLaunchKernelGGL(k_record_gather, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, table_span, d_fresh,
+                       new_stride, fresh_span, u.b0, length, u.k, u.d_idx, u.d_same0, u.d_heads);
+    return MFH_OK;
+  };
+  auto store_table = [&](const Chunk &u) {
+    Timer tm(c, 29, 0);  // ... and the table's write-back, behind the gather's reads of it
+    const uint32_t items = u.k * ((length + 18) / 16);
+    hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_fresh, new_stride, fresh_span, u.b0,
+                       length, u.k, u.d_idx, u.d_last);
+  };
+  return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, rows_out, pairs);
 }
 
 }  // namespace
@@ -679,24 +858,8 @@ int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const ui
   if (const char *what = indices_refused(h_index, nupd, depth)) return fail(c, who, what);
   if (!nupd) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  // the new leaves = the digests of the chunk's new records; a head = the old record | the new record, a pitch each
   const size_t hp = mf::record_head_pitch(length);
-  const int64_t table_span = (int64_t)((((size_t)1 << depth) - 1) * table_stride + length), fresh_span = (int64_t)((size_t)(nupd - 1) * new_stride + length);
-  auto hash_and_gather = [&](const Chunk &u) -> int {
-    if (int rc = sha256_records(c, d_new_records + (size_t)u.b0 * new_stride, new_stride, length, u.k, reinterpret_cast<uint8_t *>(u.d_own_leaves))) return rc;
-    Timer tm(c, 29, u.k);  // "merkle_record_rows" (mfhip.hip: timing_kind): the gather
-    const uint32_t items = u.k * 2 * (uint32_t)(hp / 16);
-    hipLaunchKernelGGL(k_record_gather, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, table_span, d_new_records,
-                       new_stride, fresh_span, u.b0, length, u.k, u.d_idx, u.d_same0, u.d_heads);
-    return MFH_OK;
-  };
-  auto store_table = [&](const Chunk &u) {
-    Timer tm(c, 29, 0);  // ... and the table's write-back, behind the gather's reads of it
-    const uint32_t items = u.k * ((length + 18) / 16);
-    hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_new_records, new_stride, fresh_span, u.b0,
-                       length, u.k, u.d_idx, u.d_last);
-  };
-  return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, [&](const Chunk &u) {
+  return record_updates(c, t, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_roots, rowb, nullptr, [&](const Chunk &u) {
     for (uint32_t b = 0; b < u.k; b++) {
       const uint8_t *head = u.pin_heads + (size_t)b * u.hs;
       mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 64, {{head, length}, {head + hp, length}}, u.pin_rows + (size_t)b * u.rs, 128, depth);
@@ -771,6 +934,153 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
                      found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, depth);
     }
   });
+}
+
+int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                           size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
+                           uint8_t *h_status) {
+  const char *who = "mfh_merkle_insert_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const uint32_t depth = t->depth;
+  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
+  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
+  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
+  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
+  const uint32_t plen = length - 2 * key_bytes;
+  if (h_payloads && payload_stride < plen) return fail(c, who, "payload_stride shorter than the payload's length - 2 key_bytes bytes");
+  const size_t rowb = mf::insert_row_bytes(key_bytes, length, depth);
+  if (h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
+  if (nk && !d_table) return fail(c, who, "inserts without d_table");
+  if (nk && !h_keys) return fail(c, who, "inserts without h_keys");
+  if (nk && !h_index) return fail(c, who, "inserts without h_index");
+  if (nk && !h_status) return fail(c, who, "inserts without h_status");
+  const uint32_t n = 1u << depth;
+  if (nk > n) return fail(c, who, "more inserts than the table has slots");
+  if ((uint64_t)2 * nk * ((length + 15) / 16) >> 32) return fail(c, who, "the batch's 2 nk new records exceed 2^32 units of 16 bytes");
+  for (uint32_t j = 0; j < nk; j++)
+    if (mf::key_is_sentinel(h_keys + (size_t)j * key_stride, key_bytes)) return fail(c, who, "a key is the all-zero or the all-0xFF key");
+  if (!nk) return MFH_OK;
+  mf::KeyPlan keys;
+  mf::keys_prepare(h_keys, key_stride, key_bytes, nk, keys);
+  if (keys.nu != nk) return fail(c, who, "a key is given twice");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t kw = mf::key_words(key_bytes), nb = (n + 255) / 256, nupd = 2 * nk;
+  const size_t hp = mf::record_head_pitch(length);
+  const uint32_t pair_ch = mf::insert_chunk(nk, rowb, kPathStageBytes);  // updates a chunk: whole inserts
+  // On the device.  Kept for the whole call: fresh = the 2 nk new records at a pitch of hp | the plan (p, pred, succ an insert) | the keys | the payloads.  Behind
+  // them, one after the other: the search (the keys' words | range[nk] | present[nk]), the inert search (mask words | count[nb] | total | slots[nk]), and per
+  // chunk update_rows' scratch.
+  const size_t fresh_bytes = (size_t)nupd * hp, plan_bytes = (size_t)nk * 12, keys_bytes = (size_t)nk * key_bytes, pay_bytes = h_payloads ? (size_t)nk * plen : 0;
+  const size_t up_bytes = plan_bytes + keys_bytes + pay_bytes, skip = (fresh_bytes + up_bytes + 15) & ~(size_t)15;
+  const size_t words_bytes = (size_t)nk * kw * 4, res_bytes = (size_t)2 * nk * 4, mask_bytes = (size_t)nb * 4 * 8, inert_bytes = mask_bytes + ((size_t)nb + 1 + nk) * 4;
+  if (int rc = work_reserve(c, c->circ_io, skip + std::max(std::max(words_bytes + res_bytes, inert_bytes), update_rows_bytes(depth, pair_ch, 2 * hp, 1)))) return rc;
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_keys = d_plan + plan_bytes, *d_pay = h_payloads ? d_keys + keys_bytes : nullptr;
+  uint8_t *d_work = d_fresh + skip;
+  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
+  std::vector<uint32_t> located(nk), slots(nk);
+  {  // a. the search: mfh_merkle_absent_rows', against the table before the batch
+    uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nk * kw;
+    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
+    if (!pin_qw) return MFH_ENOMEM;
+    memcpy(pin_qw, keys.words.data(), words_bytes);
+    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
+    {
+      Timer tm(c, 30, n);  // "merkle_locate" (mfhip.hip: timing_kind)
+      const dim3 grid(nb), block(256);
+#define MF_LOCATE(KW) \
+  case KW: hipLaunchKernelGGL(k_key_locate<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nk, d_res, d_res + nk); break
+      switch (kw) {
+        MF_LOCATE(1); MF_LOCATE(2); MF_LOCATE(3); MF_LOCATE(4); MF_LOCATE(5); MF_LOCATE(6); MF_LOCATE(7); MF_LOCATE(8);
+      }
+#undef MF_LOCATE
+    }
+    HIP_TRY(c, hipGetLastError());
+    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
+    if (!pin_res) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    mf::keys_scatter(keys, nk, pin_res, located.data(), h_status);
+    bool member = false, missing = false;
+    for (uint32_t j = 0; j < nk; j++) {
+      h_index[2 * (size_t)j] = located[j];
+      member = member || h_status[j] == 1;
+      missing = missing || h_status[j] == 2;
+    }
+    if (member) return fail(c, who, "a key is already a member of the set (h_status 1)");
+    if (missing) return fail(c, who, "no record's range holds a key (h_status 2): the table is malformed");
+  }
+  {  // b. the lowest nk inert slots
+    unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(d_work);
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_work + mask_bytes), *d_total = d_count + nb, *d_slots = d_total + 1;
+    {
+      Timer tm(c, 32, n);  // "merkle_inert" (mfhip.hip: timing_kind): the flags ...
+      const dim3 grid(nb), block(256);
+#define MF_INERT(KW) \
+  case KW: hipLaunchKernelGGL(k_inert_flags<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, d_mask, d_count); break
+      switch (kw) {
+        MF_INERT(1); MF_INERT(2); MF_INERT(3); MF_INERT(4); MF_INERT(5); MF_INERT(6); MF_INERT(7); MF_INERT(8);
+      }
+#undef MF_INERT
+    }
+    {
+      Timer tm(c, 32, 0);  // ... the scan of the workgroups' counts ...
+      hipLaunchKernelGGL(k_inert_scan, dim3(1), dim3(256), 0, c->stream, d_count, nb, d_total);
+    }
+    {
+      Timer tm(c, 32, 0);  // ... and the slots of the ranks below nk
+      hipLaunchKernelGGL(k_inert_select, dim3((4 * nb + 255) / 256), dim3(256), 0, c->stream, (const unsigned long long *)d_mask, (const uint32_t *)d_count, 4 * nb, nk, d_slots);
+    }
+    HIP_TRY(c, hipGetLastError());
+    uint32_t *pin_slots = (uint32_t *)pin_acquire(c, c->pin_cw, ((size_t)nk + 1) * 4);  // total | slots: O(nk) bytes
+    if (!pin_slots) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin_slots, d_total, ((size_t)nk + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (pin_slots[0] < nk) return fail(c, who, "the table has fewer inert slots than keys to insert");
+    memcpy(slots.data(), pin_slots + 1, (size_t)nk * 4);
+  }
+  // c. the plan, and what k_insert_records reads: (p, pred, succ) an insert | the keys, packed | the payloads, packed
+  mf::InsertPlan plan;
+  mf::insert_plan(h_keys, key_stride, key_bytes, nk, located.data(), slots.data(), plan);
+  for (uint32_t j = 0; j < nk; j++) {  // (p, s): the slot whose hi changes -- an earlier insert's where that split the range first -- and the new record's
+    h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];
+    h_index[2 * (size_t)j + 1] = slots[j];
+  }
+  {
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, up_bytes);
+    if (!pin_up) return MFH_ENOMEM;
+    int32_t *w = reinterpret_cast<int32_t *>(pin_up);
+    for (uint32_t j = 0; j < nk; j++) {
+      w[3 * (size_t)j] = (int32_t)located[j];
+      w[3 * (size_t)j + 1] = plan.pred[j];
+      w[3 * (size_t)j + 2] = plan.succ[j];
+      memcpy(pin_up + plan_bytes + (size_t)j * key_bytes, h_keys + (size_t)j * key_stride, key_bytes);
+      if (h_payloads && plen) memcpy(pin_up + plan_bytes + keys_bytes + (size_t)j * plen, h_payloads + (size_t)j * payload_stride, plen);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, up_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {  // d. the 2 nk new records
+    Timer tm(c, 33, nupd);  // "merkle_insert_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nupd * (hp / 16);
+    hipLaunchKernelGGL(k_insert_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, span, (const uint8_t *)d_keys,
+                       (const uint8_t *)d_pay, (const int32_t *)d_plan, key_bytes, length, nk, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  // e. the 2 nk record updates, a chunk of whole inserts at a time; row b of a chunk out of the heads and the level rows of its updates 2 b and 2 b + 1
+  const Pairs chunks{pair_ch, skip};
+  ChunkFn rows_out;
+  if (h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
+        const uint32_t j = (u.b0 + b) / 2;
+        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
+        mf::splice_insert_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, hp, length, staged_p, staged_p + u.rs, depth,
+                              h_index[2 * (size_t)j], h_index[2 * (size_t)j + 1]);
+      }
+    };
+  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out);
 }
 
 }  // extern "C"

@@ -7,11 +7,15 @@
 //   words.MerkleUpdate(depth)                     Z = 64, head = old leaf | new leaf                 row_bytes(64, 64, depth)
 //   words.MerkleRecordUpdate(length, depth)       Z = 64, head = old record | new record             row_bytes(64, 2 length, depth)
 //   words.MerkleAbsent(key_bytes, length, depth)  Z = 32, head = the query's key | the located record   row_bytes(32, key_bytes + length, depth)
+//   words.MerkleInsert(key_bytes, length, depth)  Z = 64, head = the key | old record of p | old record of s | new record of s, and TWO tails' siblings:
+//                                                 depth siblings of p | depth siblings of s | ceil(2 depth / 8) index bytes, bit l < depth = bit l of p,
+//                                                 bit depth + l = bit l of s                      insert_row_bytes(key_bytes, length, depth)
 // The kernels write whole rows where the tail lands on a 16-byte unit: k_merkle_paths the path row (tail at byte 64), k_merkle_update_level the level row
 // (tail at byte 128), both staged at staged_stride of their bytes.  A head of records puts the tail anywhere, so for those statements the device stages two
 // pieces per row and the host splices them while it copies out of the pinned buffer (splice_row):
 //   the staged row  a path row or a level row; only its tail is read
 //   the heads       what k_record_gather / k_absent_gather write: each record at the start of a slot of record_head_pitch(length) bytes (whole-unit stores)
+// An insert is two record updates: its row is spliced out of the heads and the level rows of both (splice_insert_row), the index bits written by the host.
 // An absent query for which no record was found (status 2) gets the zero bytes and its key alone: its staged pieces come from a stand-in index and are not read.
 #pragma once
 #include <stddef.h>
@@ -33,6 +37,14 @@ inline uint32_t update_chunk(uint32_t nupd, size_t row_bytes, size_t stage_bytes
   return (uint32_t)(fit < 1 ? 1 : fit < nupd ? fit : nupd);
 }
 
+inline size_t insert_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth) {
+  return (size_t)64 + key_bytes + (size_t)3 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
+}
+
+// the updates of one chunk of a batch of nk inserts (nk > 0): the most INSERTS whose rows of row_bytes fit the stage, at least one, two updates each -- always
+// even, so both updates of an insert are in one chunk even when one row alone exceeds the stage
+inline uint32_t insert_chunk(uint32_t nk, size_t row_bytes, size_t stage_bytes) { return 2 * update_chunk(nk, row_bytes, stage_bytes); }
+
 struct RowPiece {
   const uint8_t *p;
   size_t bytes;
@@ -48,6 +60,28 @@ inline void splice_row(uint8_t *row, size_t zeros, std::initializer_list<RowPiec
     row += h.bytes;
   }
   if (staged) memcpy(row, staged + tail_at, row_tail_bytes(depth));
+}
+
+// row <- the input row of words.MerkleInsert for the insert whose updates are (record p: head_p = old | new at a pitch of hp; slot s: head_s likewise) and
+// whose level rows are staged_p and staged_s (tails at byte 128): 64 zero bytes | key | old_p | old_s | new_s | p's siblings | s's siblings | the index bytes of
+// (p, s).  Reads key_bytes, length and 32 depth bytes of its sources, writes insert_row_bytes(key_bytes, length, depth) bytes and nothing behind them.
+inline void splice_insert_row(uint8_t *row, const uint8_t *key, uint32_t key_bytes, const uint8_t *head_p, const uint8_t *head_s, size_t hp, uint32_t length,
+                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s) {
+  memset(row, 0, 64);
+  row += 64;
+  memcpy(row, key, key_bytes);
+  row += key_bytes;
+  if (length) {
+    memcpy(row, head_p, length);
+    memcpy(row + length, head_s, length);
+    memcpy(row + 2 * (size_t)length, head_s + hp, length);
+  }
+  row += 3 * (size_t)length;
+  memcpy(row, staged_p + 128, (size_t)32 * depth);
+  memcpy(row + (size_t)32 * depth, staged_s + 128, (size_t)32 * depth);
+  row += (size_t)64 * depth;
+  const uint64_t bits = (uint64_t)p | (uint64_t)s << depth;  // (depth <= 24: 48 bits)
+  for (uint32_t b = 0; b < (2 * depth + 7) / 8; b++) row[b] = (uint8_t)(bits >> (8 * b));
 }
 
 }  // namespace mf

@@ -1145,6 +1145,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_record_rows")) return 29;  // k_record_gather / k_record_store of mfh_merkle_update_records: 2 per chunk; rows = updates gathered
   if (!strcmp(which, "merkle_locate")) return 30;  // k_key_locate of mfh_merkle_absent_rows (merkle.hip): one per call; rows = the table's 2^depth records
   if (!strcmp(which, "merkle_absent_rows")) return 31;  // k_absent_gather of mfh_merkle_absent_rows: one per chunk; rows = the chunk's queries
+  if (!strcmp(which, "merkle_inert")) return 32;  // k_inert_flags / _scan / _select of mfh_merkle_insert_keys (merkle.hip): 3 per call; rows = the table's 2^depth records
+  if (!strcmp(which, "merkle_insert_records")) return 33;  // k_insert_records of mfh_merkle_insert_keys: one per call; rows = the 2 nk new records
   return -1;
 }
 

@@ -457,7 +457,9 @@ class _Statement:
     """Private base of Sha256Message and the Merkle statements: the argument checks and the pieces of bits() they share, every refusal under the public
     class's own name.  A statement's nin input bits, public then private, packed eight to a byte (least significant first) are its packed input row, one
     layout for all of them (MerkleTree's *_rows write it on the device; csrc/merkle_rows.hpp): 32 or 64 zero bytes where the root(s) are computed
-    (MerkleAbsent: and the key) | the head (leaves as words, records as bytes) | depth siblings of 32 bytes as words | ceil(depth / 8) index bytes."""
+    (MerkleAbsent: and the key) | the head (leaves as words, records as bytes) | depth siblings of 32 bytes as words | ceil(depth / 8) index bytes.
+    MerkleInsert's row has two paths: 64 zero bytes | the key | old_p | old_s | new_s | depth siblings of p | depth siblings of s | ceil(2 depth / 8) index
+    bytes, bit l < depth = bit l of p, bit depth + l = bit l of s: 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes."""
 
     def _arg(self, value, lo, hi, what):
         if not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
@@ -789,6 +791,89 @@ class MerkleAbsent(_OneRoot):
         return _statement_of(root, "MerkleAbsent: the root") + self._query(key)
 
 
+class MerkleInsert(_TwoRoots):
+    """The statement "the key k was inserted into the indexed table (MerkleAbsent has the data model), and that alone takes the tree from root R to root
+    R'": the two record updates of an insert (indexed_insert) under ONE pair of roots.  Record p, whose range held k (lo_p < k < hi_p), gets hi <- k; the
+    record (k, the old hi_p, a payload) goes into a slot s that was inert (lo_s >= hi_s).  A chain of such steps from the root of an indexed_records table
+    keeps the invariant MerkleAbsent's soundness rests on, so a verifier who has seen every step's proof accepts absence proofs against the last root.
+
+    Public wires, in this order: R as 256 computed outputs at statement bits [0, 256), R' at [256, 512), then the 8 key_bytes given bits of k, byte j's
+    bit b (LSB first) at 512 + 8 j + b, as MerkleAbsent places q; lu = 512 + 8 key_bytes.  statement(R, R', k) is MerkleUpdate.statement's 64 bytes, then k.
+    Private inputs, in this order: the old record of slot p (8 * length bits, byte j's bit b at 8 j + b), the old record of slot s, the new record of slot
+    s; `depth` siblings of 8 words for p, from the leaf's level up; `depth` siblings for s, taken from the tree AFTER p's update; `depth` direction bits
+    of p; `depth` direction bits of s.
+    The body.  The new record of p is no input: it is old_p's wires with those of bytes [K, 2K) replaced by new_s's bytes [0, K), so lo and payload of p
+    cannot change.  Four record chains (_message_chain: old_p, new_p, old_s, new_s) and four level chains (_merkle_levels: old_p and new_p over p's siblings
+    and directions, old_s and new_s over s's).  R is the root of the first chain, R' that of the last; the two middle roots -- the private intermediate
+    root, the tree after p's update -- are tied by 256 assert_same.  Further assert_same: k = new_s[0, K); old_p[K, 2K) = new_s[K, 2K) (the new record
+    inherits the old hi).  Comparators (Words.less_than): lo_p < k and k < hi_p asserted to 1, lo_s < hi_s asserted to 0 (the slot was inert).
+    p != s needs no constraint of its own: the siblings of s open the tree AFTER p's update, in which slot p holds the live record (lo_p, k), lo_p < k,
+    so with s = p the record old_s would have to be that live record and could not pass the inert check.
+    What it does not cover: the payload of the new record is free (bytes [2K, length) of new_s are unconstrained; constrain them in a wrapping circuit if
+    they matter), and, like MerkleAbsent, it says nothing about the records it does not open.
+    MerkleTree.insert_keys / insert_bits perform a batch of inserts on a device table and give the input rows; statement j is (R_j, R_j+1, key_j).
+    Sizes (MERKLE_INSERT_SIZES): four level chains cost about 203 000 rows a level, so (8, 55, 4) is the deepest one-block statement that fits
+    Params(d=1 << 20, m=699050); depth 5 (about 1 212 000 rows) does not.  Depth 1 fits Params(d=1 << 19, m=349525)."""
+
+    def __init__(self, key_bytes: int, length: int, depth: int):
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
+        self.depth = depth = self._depth_arg(depth)
+        self.w = w = Words()
+        self.old_p, self.old_s, self.new_s = (w.c.private(8 * length) for _ in range(3))
+        self.siblings_p = [w.private(8) for _ in range(depth)]
+        self.siblings_s = [w.private(8) for _ in range(depth)]
+        self.dirs_p = w.c.private(depth)
+        self.dirs_s = w.c.private(depth)
+        self.new_p = self.old_p[: 8 * K] + self.new_s[: 8 * K] + self.old_p[16 * K:]
+        leaves = [_message_chain(w, rec, length) for rec in (self.old_p, self.new_p, self.old_s, self.new_s)]
+        self.blocks = leaves[0][1]
+        tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
+        self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for (leaf, _), (sibs, dirs) in zip(leaves, tails))
+        self.old_root = [w.output(x) for x in self.out_old]
+        self.new_root = [w.output(x) for x in self.out_new]
+        self.key = w.c.public(8 * K)
+        for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
+            w.assert_same_u32(x, y)
+        for a, b in zip(self.key, self.new_s[: 8 * K]):
+            w.c.assert_same(a, b)
+        for a, b in zip(self.old_p[8 * K: 16 * K], self.new_s[8 * K: 16 * K]):
+            w.c.assert_same(a, b)
+        lo_p, hi_p, lo_s, hi_s, k = (_key_bits_lsb_first(bits, K) for bits in (self.old_p[: 8 * K], self.old_p[8 * K: 16 * K], self.old_s[: 8 * K],
+                                                                              self.old_s[8 * K: 16 * K], self.key))
+        w.c.assert_equal(w.less_than(lo_p, k), 1)
+        w.c.assert_equal(w.less_than(k, hi_p), 1)
+        w.c.assert_equal(w.less_than(lo_s, hi_s), 0)
+
+    @property
+    def lu(self) -> int:
+        return 512 + 8 * self.key_bytes
+
+    def _query(self, key) -> bytes:
+        key = bytes(key)
+        if len(key) != self.key_bytes:
+            raise CircuitError(f"MerkleInsert: the key is {self.key_bytes} bytes")
+        if _is_sentinel(key):
+            raise CircuitError("MerkleInsert: the all-zero and the all-0xFF key are sentinels, never members")
+        return key
+
+    def bits(self, key: bytes, old_p: bytes, old_s: bytes, new_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed, the key's bits, the three records' bits, p's
+        siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A witness that breaks a
+        constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
+        who = "MerkleInsert"
+        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
+        tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
+        nsib = 256 * self.depth
+        return _input_bits(512, key, _record_bits(who, self.length, old_p, old_s, new_s, what="the records are"), tail_p[:nsib], tail_s[:nsib], tail_p[nsib:],
+                           tail_s[nsib:])
+
+    def statement(self, old_root: bytes, new_root: bytes, key: bytes) -> bytes:
+        """the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "inserting `key` took old_root to
+        new_root": MerkleUpdate.statement's bytes, then the key"""
+        return super().statement(old_root, new_root) + self._query(key)
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):
@@ -878,3 +963,9 @@ MERKLE_RECORD_UPDATE_SIZES = {(8, 1): (112309, 199735), (55, 1): (113075, 200501
 # m=87381), (32, 64, 1) (two blocks) Params(d=1 << 18, m=174762); (8, 55, 19) is the deepest one-block statement that fits Params(d=1 << 20, m=699050):
 # (8, 55, 20) would be 1 067 394 rows
 MERKLE_ABSENT_SIZES = {(4, 8, 1): (56444, 100288), (8, 16, 1): (56672, 100644), (32, 64, 1): (85352, 151308), (8, 55, 19): (572237, 1016529)}
+# ... and of MerkleInsert by (key_bytes, length, depth): twice MerkleRecordUpdate(length, depth)'s, less 8 length - 56 key_bytes + 514 wires and 8 length - 120
+# key_bytes + 769 rows -- the new record of p is no input (8 length wires and bit rows), the roots are output once, not twice (512 wires, 1 024 rows), the two
+# constant wires are shared; k is 8 key_bytes public wires and bit rows, three comparisons are 16 key_bytes wires and 32 key_bytes + 1 rows each, and 256 + 16
+# key_bytes equalities tie the middle roots, k and the inherited hi.  A level costs 113 986 wires and 202 946 rows (twice MerkleUpdate's).  Depth 1 fits
+# Params(d=1 << 19, m=349525); (8, 55, 4) is the deepest one-block statement that fits Params(d=1 << 20, m=699050): (8, 55, 5) would be 1 212 537 rows
+MERKLE_INSERT_SIZES = {(4, 8, 1): (224264, 399117), (8, 55, 1): (225644, 400753), (8, 16, 4): (566654, 1008643), (8, 55, 4): (567602, 1009591)}

@@ -452,6 +452,33 @@ int mfh_merkle_update_records(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const 
  * "merkle_paths" (1 per chunk, as mfh_merkle_paths). */
 int mfh_merkle_absent_rows(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
                            const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint32_t *h_index, uint8_t *h_status);
+/* nk sequential key inserts into an INDEXED table (the data model: mfh_merkle_absent_rows) and its tree in ONE call, and the packed input row of
+ * words.MerkleInsert(key_bytes, length, depth) of every insert -- "key j was inserted, and that alone takes the tree from R_j to R_j+1".
+ *   semantics  byte for byte what this gives, run once per key in order: mfh_merkle_absent_rows (locate) for the record p whose range holds the key; the two
+ *              updates of an insert -- record p with hi <- key, and (key | the old hi | payload, zero-padded) into the LOWEST inert slot s of the table as it
+ *              then stands -- through mfh_merkle_update_records.  That covers the table in place, every node of the tree, the roots and row j, which describes
+ *              table and tree as they stood before insert j.  A later key may fall into a range an earlier key of the batch has split: it is resolved in order.
+ *   arguments  key j is the key_bytes bytes at h_keys + j * key_stride; its payload the length - 2 key_bytes bytes at h_payloads + j * payload_stride, or all
+ *              zero with h_payloads = NULL.  h_inputs = NULL: insert, no rows.  h_roots (may be NULL) receives the nk + 1 roots R_0 .. R_nk.  h_index
+ *              receives nk pairs (p, s): the slot whose hi changed and the slot that received the new record.  h_status receives the status of each key
+ *              against the table BEFORE the batch (mfh_merkle_absent_rows').
+ *   rows       row j (at h_inputs + j * in_stride): 64 zero bytes where the roots are computed | the key | the old record of p | the old record of s | the new
+ *              record of s | the 32 depth sibling bytes of p | those of s, from the tree after p's update | ceil(2 depth / 8) index bytes, bit l < depth =
+ *              bit l of p, bit depth + l = bit l of s.  Exactly 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes are written.
+ *   how        k_key_locate as mfh_merkle_absent_rows runs it; three launches (k_inert_flags, k_inert_scan, k_inert_select) find the lowest nk inert slots
+ *              and their total on the device, and nk + 1 words come back; the host plans predecessors and successors within the batch (merkle_insert.hpp);
+ *              ONE launch of k_insert_records builds the 2 nk new records; they go through mfh_merkle_update_records' machinery in chunks of whole inserts
+ *              (the most whose rows fit 64 MiB, at least one).  The call synchronises the stream behind the search, the inert search and every chunk.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: a null tree; a tree of another device; key_bytes 0 or above 32; length
+ * < 2 key_bytes or > 2^20; table_stride < length; key_stride < key_bytes; payload_stride < length - 2 key_bytes with h_payloads given; nk > 0 with d_table,
+ * h_keys, h_index or h_status null; nk > 2^depth; in_stride below the row's bytes when h_inputs is given; a sentinel key; a key given twice.
+ * MFH_EINVAL after the search, with h_status and the first element of every pair of h_index (the located record) filled, table and tree unwritten: a key that
+ * is already a member (status 1); a key that no record holds (status 2); fewer inert slots than nk.  The call is all or nothing.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call), "merkle_inert" (3 per call, rows = 2^depth), "merkle_insert_records" (1 per call, rows = 2 nk), then per
+ * chunk of 2 k updates "sha256_records" (1), "merkle_record_rows" (2; 1 without rows) and "merkle_updates" (depth + 1). */
+int mfh_merkle_insert_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
+                           const uint8_t *h_keys, size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride,
+                           uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
