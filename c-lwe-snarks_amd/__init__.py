@@ -102,7 +102,7 @@ EXPORTS = [
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
-    "mfh_merkle_absent_rows", "mfh_merkle_insert_keys",
+    "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
 ]
 
 
@@ -242,6 +242,9 @@ def load_library():
         "mfh_merkle_update_records": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, vp, sz, vp]),
         "mfh_merkle_absent_rows": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, vp]),
         "mfh_merkle_insert_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+        "mfh_merkle_update_rows_cut": (i32, [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp]),
+        "mfh_merkle_update_records_cut": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, u32, vp, vp, vp, vp]),
+        "mfh_merkle_insert_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -596,6 +599,125 @@ class MerkleTree:
         head = 64 + np.ascontiguousarray(keys).shape[1] + 3 * int(table.shape[1])
         bits = np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth]
         return (bits,) + tuple(out[1:])
+
+    # ---- the path cut into level ranges (words.MerkleSegment): one row array a segment, and the published node pairs
+    def _cut(self, cuts, who, n0, row0, nupper):
+        """(the row arrays: n0 rows of row0 bytes for segment 0, nupper rows a MerkleSegment, the C arguments ncuts, h_cuts, h_rows, h_strides)"""
+        from .words import CircuitError, segment_levels
+
+        try:
+            ranges = segment_levels(self.depth, [int(x) for x in cuts])
+        except (CircuitError, TypeError, ValueError):
+            raise MfhError(f"{who}: cuts are 1 <= c_0 < .. < c_G-1 < depth, at least one") from None
+        rows = [np.zeros((n0, row0(ranges[0][1])), dtype=np.uint8)]
+        rows += [np.zeros((nupper, 128 + 32 * (hi - lo) + (hi - lo + 7) // 8), dtype=np.uint8) for lo, hi in ranges[1:]]
+        c_cuts = np.array([lo for lo, _ in ranges[1:]], dtype=np.uint32)
+        ptrs = (ctypes.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
+        strides = (ctypes.c_size_t * len(rows))(*[r.shape[1] for r in rows])
+        return rows, (len(c_cuts), ctypes.c_void_p(c_cuts.ctypes.data), ptrs, strides), c_cuts
+
+    def _cut_nodes(self, rows, r):
+        """np.uint8 [n, G + 1, 2, 32], the published pairs (X_g, X_g') of every update in digest byte order: the heads of its upper segments' rows, then (R_k, R_k+1)"""
+        n, G = len(r) - 1, len(rows) - 1
+        nodes = np.zeros((n, G + 1, 2, 32), dtype=np.uint8)
+        for g in range(G):
+            nodes[:, g] = rows[g + 1][:, :64].reshape(n, 2, 8, 4)[..., ::-1].reshape(n, 2, 32)
+        nodes[:, G, 0], nodes[:, G, 1] = r[:-1], r[1:]
+        return nodes
+
+    def _cut_unpack(self, rows, cuts, head0):
+        edges = [0] + [int(x) for x in cuts] + [self.depth]
+        levels = [hi - lo for lo, hi in zip(edges, edges[1:])]
+        per = head0(levels[0])
+        return [np.unpackbits(r, axis=1, bitorder="little")[:, : per if g == 0 else 1024 + 257 * levels[g]] for g, r in enumerate(rows)]
+
+    def update_segments(self, indices, new_leaves, cuts, roots=False):
+        """update_rows with the path cut at levels `cuts` (words.segment_levels; mfh_merkle_update_rows_cut: one more launch a chunk).  Returns (rows, nodes):
+        rows is a list of G + 1 arrays, rows[0][k] the packed input row of words.MerkleUpdate(c_0) of update k -- over the subtree of height c_0 that holds
+        the leaf -- and rows[g][k], g >= 1, that of words.MerkleSegment(c_g - c_g-1); nodes is np.uint8 [n, G + 1, 2, 32], the published pairs (X_g, X_g') of
+        every update in digest byte order, (X_G, X_G') = (R_k, R_k+1): MerkleUpdate.statement(*nodes[k, 0]) and MerkleSegment.chain(nodes[k]) are the G + 1
+        statements of update k.  With roots=True a triple whose last element is the n + 1 roots."""
+        c = self._ctx
+        idx = self._indices(indices, "update_segments")
+        t, _ = self._leaves(new_leaves, "update_segments", aligned=True)
+        if t.numel() != 32 * len(idx):
+            raise MfhError("update_segments: one leaf of 32 bytes per index")
+        rows, cargs, keep = self._cut(cuts, "update_segments", len(idx), lambda c0: 128 + 32 * c0 + (c0 + 7) // 8, len(idx))
+        r = np.zeros((len(idx) + 1, 32), dtype=np.uint8)
+        c._chk(c.lib.mfh_merkle_update_rows_cut(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), _ptr(t) if len(idx) else None, *cargs,
+                                                ctypes.c_void_p(r.ctypes.data)))
+        self._keep = []
+        if not len(idx):
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        nodes = self._cut_nodes(rows, r)
+        return (rows, nodes, r) if roots else (rows, nodes)
+
+    def update_segment_bits(self, indices, new_leaves, cuts, roots=False):
+        """update_segments with every segment's rows as 0 / 1 arrays: what Context.circuit_assign takes for MerkleUpdate(c_0) and the MerkleSegments"""
+        out = self.update_segments(indices, new_leaves, cuts, roots)
+        return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 257 * c0),) + tuple(out[1:])
+
+    def update_record_segments(self, table, indices, new_records, cuts, roots=False):
+        """update_records with the path cut at levels `cuts` (mfh_merkle_update_records_cut): as update_segments, rows[0][k] being the packed input row of
+        words.MerkleRecordUpdate(length, c_0)"""
+        c = self._ctx
+        idx = self._indices(indices, "update_record_segments")
+        tab, tstride, length = self._table(table, "update_record_segments")
+        new, nstride, nlength, n, _ = _records(c, new_records, "update_record_segments")
+        if n != len(idx) or nlength != length:
+            raise MfhError("update_record_segments: one new record of the table's length per index")
+        rows, cargs, keep = self._cut(cuts, "update_record_segments", n, lambda c0: 64 + 2 * length + 32 * c0 + (c0 + 7) // 8, n)
+        r = np.zeros((n + 1, 32), dtype=np.uint8)
+        c._chk(c.lib.mfh_merkle_update_records_cut(c._h, self._h, n, ctypes.c_void_p(idx.ctypes.data), _ptr(tab), tstride, length, _ptr(new) if n else None, nstride,
+                                                   *cargs, ctypes.c_void_p(r.ctypes.data)))
+        self._keep = []
+        if not n:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        nodes = self._cut_nodes(rows, r)
+        return (rows, nodes, r) if roots else (rows, nodes)
+
+    def update_record_segment_bits(self, table, indices, new_records, cuts, roots=False):
+        """update_record_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.update_record_segments(table, indices, new_records, cuts, roots)
+        length = int(table.shape[1])
+        return (self._cut_unpack(out[0], cuts, lambda c0: 512 + 16 * length + 257 * c0),) + tuple(out[1:])
+
+    def insert_key_segments(self, table, keys, cuts, payloads=None):
+        """insert_keys with the path cut at levels `cuts` (mfh_merkle_insert_keys_cut).  Returns (rows, nodes_p, nodes_s, index): rows[0][j] is the packed input
+        row of words.MerkleInsert(key_bytes, length, c_0, joined=False) of insert j; rows[g], g >= 1, holds one words.MerkleSegment row per UPDATE, row 2 j that
+        of p's update of insert j and row 2 j + 1 that of s's; nodes_p and nodes_s are np.uint8 [nk, G + 1, 2, 32], the published pairs of the two updates:
+        segment 0's statement is statement(*nodes_p[j, 0], *nodes_s[j, 0], keys[j]), the upper ones MerkleSegment.chain(nodes_p[j]) and chain(nodes_s[j]), and
+        nodes_p[j, G, 1] == nodes_s[j, G, 0] is the root between the two updates, which becomes public.  index as insert_keys gives it."""
+        c = self._ctx
+        tab, tstride, length = self._table(table, "insert_key_segments")
+        k = np.ascontiguousarray(keys)
+        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
+            raise MfhError("insert_key_segments: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        nk, kb = k.shape
+        pay = None
+        if payloads is not None:
+            pay = np.ascontiguousarray(payloads)
+            if pay.dtype != np.uint8 or pay.shape != (nk, length - 2 * kb):
+                raise MfhError("insert_key_segments: payloads are uint8 [nk, length - 2 key_bytes]")
+        rows, cargs, keep = self._cut(cuts, "insert_key_segments", nk, lambda c0: 128 + kb + 3 * length + 64 * c0 + (2 * c0 + 7) // 8, 2 * nk)
+        index = np.zeros((nk, 2), dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        r = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_insert_keys_cut(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(pay.ctypes.data) if pay is not None else None,
+                                                length - 2 * kb, *cargs, vp(r.ctypes.data), vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        else:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        nodes = self._cut_nodes(rows, r)
+        return rows, nodes[0::2], nodes[1::2], index
+
+    def insert_key_segment_bits(self, table, keys, cuts, payloads=None):
+        """insert_key_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.insert_key_segments(table, keys, cuts, payloads)
+        kb, length = np.ascontiguousarray(keys).shape[1], int(table.shape[1])
+        return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 8 * kb + 24 * length + 514 * c0),) + tuple(out[1:])
 
 
 class Context:

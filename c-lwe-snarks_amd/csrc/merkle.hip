@@ -17,6 +17,8 @@
 // into the leaves (its load plan and LDS image: above the kernel).
 // k_merkle_update_level, k_merkle_update_store: a batch of sequential one-leaf updates in depth + 1 launches, every update's words.MerkleUpdate input row
 // written on the way (mfh_merkle_update_rows; the recurrence: above the kernels, the host's schedule: merkle_sched.hpp).
+// k_merkle_cut_rows: a path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) -- the words.MerkleSegment input rows of every update's upper
+// segments, one launch a chunk between the level launches and the write-back.
 // k_record_gather, k_record_store: the byte-granular copies of mfh_merkle_update_records, which applies a batch of sequential RECORD updates to a table of
 // records and its tree and writes every update's words.MerkleRecordUpdate input row: old and new records into the row heads before the level launches,
 // the last new record of each leaf into the table behind them.
@@ -210,6 +212,49 @@ __global__ __launch_bounds__(256) void k_merkle_update_store(uint4 *__restrict__
   const size_t heap = ((size_t)1 << (depth - l)) + (idx[k] >> l);
   nodes[2 * heap] = src[0];
   nodes[2 * heap + 1] = src[1];
+}
+
+// ---- the mfh_merkle_*_cut calls: a path cut at levels c_0 < .. < c_G-1 gives every update G more rows, segment g = 1 .. G the packed input row of
+// words.MerkleSegment(c_g - c_g-1) (c_G = depth; merkle_rows.hpp has the row).  CutPlan, by value: per segment its lower level lo = c_g-1, its levels and
+// the 16-byte unit at which its n rows of 9 + 2 levels units start in the stage.
+//
+// k_merkle_cut_rows, ONE launch per chunk, behind the last k_merkle_update_level and BEFORE k_merkle_update_store: it reads stored nodes that the write-back
+// may replace.  A work item is (update k, segment blockIdx.y + 1, unit u) of that segment's staged row:
+//   units 0 - 1   the old node of level lo on update k's path, as words: V[lo][j] with j = same_cut[g * n + k] when an earlier update of the chunk touched
+//                 that node (merkle_sched.hpp), else the tree's stored node idx[k] >> lo of that level -- the recurrence of the old leaf, at level lo
+//   units 2 - 3   the new node V[lo][k], as words
+//   units 4 - 7   zero: where the two tops are computed
+//   then          the siblings of levels [lo, lo + levels), copied from level row k (they are words already)
+//   last          (idx[k] >> lo) mod 2^levels, in one unit
+// Reads: the schedule's n entries, V[lo] (lo >= 1: a slot of v), stored nodes of level lo, units [8 + 2 lo, 8 + 2 (lo + levels)) of level row k -- all
+// written by earlier launches.  Writes: whole units of its own segment's rows, each by one item; nothing outside base + n (9 + 2 levels) units.
+struct CutPlan {
+  uint32_t nseg;
+  uint32_t lo[kMaxDepth], levels[kMaxDepth], base[kMaxDepth];
+};
+
+__global__ __launch_bounds__(256) void k_merkle_cut_rows(const uint4 *__restrict__ nodes, uint32_t depth, uint32_t n, const uint32_t *__restrict__ idx,
+                                                         const int32_t *__restrict__ same_cut, const uint4 *__restrict__ v, size_t slot_units,
+                                                         const uint4 *__restrict__ level_rows, uint32_t level_stride_units, uint4 *__restrict__ seg_rows,
+                                                         const CutPlan plan) {
+  const uint32_t g = blockIdx.y, lo = plan.lo[g], levels = plan.levels[g], units = 9 + 2 * levels;
+  const uint32_t item = blockIdx.x * 256 + threadIdx.x;  // (n * units < 2^32: a chunk's rows fit 64 MiB, or n = 1)
+  if (g >= plan.nseg || item >= n * units) return;
+  const uint32_t k = item / units, u = item - k * units, i = idx[k];
+  const uint4 *vlo = v + (size_t)(lo - 1) * slot_units;
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (u < 2) {
+    const int32_t js = same_cut[(size_t)g * n + k];
+    const uint4 *op = js >= 0 ? vlo + 2 * (size_t)js : nodes + 2 * (((size_t)1 << (depth - lo)) + (i >> lo));
+    out = bswap4(op[u]);
+  } else if (u < 4) {
+    out = bswap4(vlo[2 * (size_t)k + (u - 2)]);
+  } else if (u >= 8 && u < 8 + 2 * levels) {
+    out = level_rows[(size_t)k * level_stride_units + 2 * lo + u];
+  } else if (u == 8 + 2 * levels) {
+    out.x = (i >> lo) & (uint32_t)(((uint64_t)1 << levels) - 1);
+  }
+  seg_rows[(size_t)plan.base[g] + item] = out;
 }
 
 // ---- mfh_merkle_update_records: the two byte-granular copies around the level launches.  Records have any byte alignment (base and stride), so both
@@ -578,6 +623,8 @@ struct Chunk {
   uint4 *d_rows, *d_heads;
   size_t rs, hs;
   uint8_t *pin_rows, *pin_heads;
+  const CutPlan *plan = nullptr;      // a cut call: the chunk's upper segments ...
+  const uint8_t *pin_segs = nullptr;  // ... and their staged rows in the pinned buffer, segment g + 1 at 16 plan->base[g] bytes
 };
 using ChunkFn = std::function<void(const Chunk &)>;
 
@@ -629,37 +676,66 @@ int path_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_ind
 // A batch of inserts (mfh_merkle_insert_keys) drives the same body with `pairs`: chunks of whole inserts (mf::insert_chunk: an even number of updates), the first
 // `skip` bytes of the scratch (a multiple of 16, reserved by the caller with update_rows_bytes behind them) left to the caller, h_roots given every second root,
 // and rows_out = null for "no rows": then nothing but the roots comes back.
+// A cut call (mfh_merkle_*_cut) drives the same body with `cuts`: the schedule carries same_cut behind sib, k_merkle_cut_rows runs between the last level and the
+// write-back, the upper segments' staged rows (behind the schedule on the device, behind the roots in the pinned buffer) come back with the chunk, and once
+// rows_out has made the caller's segment-0 rows out of level rows and heads, row b0 + b of segment g >= 1 goes to h_rows[g] + (b0 + b) * strides[g].
 struct Pairs {
   uint32_t ch;  // updates a chunk
   size_t skip;
+  bool all_roots = false;  // h_roots gets the root behind EVERY update
 };
 
-size_t update_rows_bytes(uint32_t depth, uint32_t ch, size_t hs, uint32_t own) {
-  return (size_t)(depth + own) * ch * 32 + (size_t)ch * (mf::staged_stride(mf::row_bytes(64, 64, depth)) + hs) + (size_t)(depth + 3) * ch * 4;
+struct Cuts {
+  uint32_t ncuts;
+  const uint32_t *cuts;
+  uint8_t *const *h_rows;  // ncuts + 1 arrays: [0] is segment 0's, the caller's own business
+  const size_t *strides;
+  uint32_t levels(uint32_t g, uint32_t depth) const { return (g + 1 < ncuts ? cuts[g + 1] : depth) - cuts[g]; }  // of segment g + 1
+};
+
+size_t update_rows_bytes(uint32_t depth, uint32_t ch, size_t hs, uint32_t own, const Cuts *cuts = nullptr) {
+  const size_t uncut = (size_t)(depth + own) * ch * 32 + (size_t)ch * (mf::staged_stride(mf::row_bytes(64, 64, depth)) + hs) + (size_t)(depth + 3) * ch * 4;
+  return cuts ? uncut + (size_t)cuts->ncuts * ch * 4 + 16 + (size_t)ch * mf::cut_staged_bytes(depth, cuts->ncuts, cuts->cuts) : uncut;
 }
 
 int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint8_t *h_roots, size_t rowb, size_t hs,
-                const std::function<int(const Chunk &)> &before, const ChunkFn &after, const ChunkFn &rows_out, const Pairs *pairs = nullptr) {
-  const uint32_t depth = t->depth, ch = pairs ? pairs->ch : mf::update_chunk(nupd, rowb, kPathStageBytes), own = !d_new_leaves, step = pairs ? 2 : 1;
+                const std::function<int(const Chunk &)> &before, const ChunkFn &after, const ChunkFn &rows_out, const Pairs *pairs = nullptr,
+                const Cuts *cuts = nullptr) {
+  const uint32_t depth = t->depth, ch = pairs ? pairs->ch : mf::update_chunk(nupd, rowb, kPathStageBytes), own = !d_new_leaves;
+  const uint32_t step = pairs && !pairs->all_roots ? 2 : 1, ncuts = cuts ? cuts->ncuts : 0, sw = depth + 3 + ncuts;  // sw: the schedule's words an update
   const size_t rs = mf::staged_stride(mf::row_bytes(64, 64, depth)), slot = (size_t)ch * 32, skip = pairs ? pairs->skip : 0;
-  if (int rc = work_reserve(c, c->circ_io, skip + update_rows_bytes(depth, ch, hs, own))) return rc;
+  const size_t seg_bytes = cuts ? mf::cut_staged_bytes(depth, ncuts, cuts->cuts) : 0;  // an update's upper segments, staged
+  if (int rc = work_reserve(c, c->circ_io, skip + update_rows_bytes(depth, ch, hs, own, cuts))) return rc;
   uint4 *d_own = reinterpret_cast<uint4 *>(c->circ_io.as<uint8_t>() + skip), *d_v = d_own + own * slot / 16, *d_rows = d_v + depth * slot / 16, *d_heads = d_rows + (size_t)ch * rs / 16;
   uint32_t *d_sched = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
-  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32);
+  uint4 *d_segs = reinterpret_cast<uint4 *>(d_sched) + ((size_t)sw * ch * 4 + 15) / 16;
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (rs + hs) + ((size_t)ch + 1) * 32 + (size_t)ch * seg_bytes);
   if (!pin_out) return MFH_ENOMEM;
-  uint8_t *pin_roots = pin_out + (size_t)ch * (rs + hs);
+  uint8_t *pin_roots = pin_out + (size_t)ch * (rs + hs), *pin_segs = pin_roots + ((size_t)ch + 1) * 32;
   uint4 *nodes = reinterpret_cast<uint4 *>(t->mem);
   if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
   for (uint32_t b0 = 0; b0 < nupd; b0 += ch) {
     const uint32_t k = std::min(ch, nupd - b0);
-    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)(depth + 3) * k * 4);
+    uint32_t *pin_sched = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)sw * k * 4);
     if (!pin_sched) return MFH_ENOMEM;
     memcpy(pin_sched, h_index + b0, (size_t)k * 4);
-    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k);
-    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)(depth + 3) * k * 4, hipMemcpyHostToDevice, c->stream));
+    mf::merkle_schedule(depth, k, h_index + b0, (int32_t *)pin_sched + 2 * (size_t)k, (int32_t *)pin_sched + 3 * (size_t)k, pin_sched + k, ncuts, cuts ? cuts->cuts : nullptr,
+                        (int32_t *)pin_sched + (size_t)(depth + 3) * k);
+    HIP_TRY(c, hipMemcpyAsync(d_sched, pin_sched, (size_t)sw * k * 4, hipMemcpyHostToDevice, c->stream));
     pin_release(c, c->pin_rows);
     const int32_t *d_sib = (const int32_t *)d_sched + 3 * (size_t)k;
-    const Chunk u{b0, k, d_sched, d_sched + k, (const int32_t *)d_sched + 2 * (size_t)k, own ? d_own : nullptr, d_rows, d_heads, rs, hs, pin_out, pin_out + (size_t)ch * rs};
+    CutPlan plan{};  // the chunk's upper segments: k rows each, one behind the other
+    uint32_t seg_units = 0, widest = 0;
+    for (uint32_t g = 0; g < ncuts; g++) {
+      plan.lo[g] = cuts->cuts[g];
+      plan.levels[g] = cuts->levels(g, depth);
+      plan.base[g] = seg_units;
+      seg_units += k * mf::segment_row_units(plan.levels[g]);
+      widest = std::max(widest, mf::segment_row_units(plan.levels[g]));
+    }
+    plan.nseg = ncuts;
+    const Chunk u{b0, k, d_sched, d_sched + k, (const int32_t *)d_sched + 2 * (size_t)k, own ? d_own : nullptr, d_rows, d_heads, rs, hs, pin_out, pin_out + (size_t)ch * rs,
+                  cuts ? &plan : nullptr, cuts ? pin_segs : nullptr};
     const uint4 *d_leaves = own ? d_own : reinterpret_cast<const uint4 *>(d_new_leaves + (size_t)32 * b0);
     if (before)
       if (int rc = before(u)) return rc;
@@ -667,6 +743,11 @@ int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_inde
       Timer tm(c, 28, k);  // "merkle_updates" (mfhip.hip: timing_kind): k compressions
       hipLaunchKernelGGL(k_merkle_update_level, dim3((k + 255) / 256), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, l, k, u.d_idx, d_sib + (size_t)l * k, u.d_same0,
                          l ? (const uint4 *)(d_v + (size_t)(l - 1) * slot / 16) : d_leaves, d_v + (size_t)l * slot / 16, d_rows, (uint32_t)(rs / 16));
+    }
+    if (cuts) {  // behind the last level, before the write-back: the old nodes of the cut levels are still the stored ones
+      Timer tm(c, 34, (uint64_t)k * ncuts);  // "merkle_segments" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_merkle_cut_rows, dim3((k * widest + 255) / 256, ncuts), dim3(256), 0, c->stream, (const uint4 *)nodes, depth, k, u.d_idx,
+                         (const int32_t *)d_sched + (size_t)(depth + 3) * k, (const uint4 *)d_v, slot / 16, (const uint4 *)d_rows, (uint32_t)(rs / 16), d_segs, plan);
     }
     {
       Timer tm(c, 28, 0);  // ... the write-back: no compression
@@ -678,9 +759,14 @@ int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_inde
     } else {
       HIP_TRY(c, hipGetLastError());
     }
+    if (cuts) HIP_TRY(c, hipMemcpyAsync(pin_segs, d_segs, (size_t)seg_units * 16, hipMemcpyDeviceToHost, c->stream));
     if (h_roots) HIP_TRY(c, hipMemcpyAsync(pin_roots + 32, d_v + (size_t)(depth - 1) * slot / 16, (size_t)k * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (rows_out) rows_out(u);
+    for (uint32_t g = 0; g < ncuts; g++) {
+      const size_t rowb_g = mf::segment_row_bytes(plan.levels[g]), units = mf::segment_row_units(plan.levels[g]);
+      for (uint32_t b = 0; b < k; b++) memcpy(cuts->h_rows[g + 1] + (size_t)(b0 + b) * cuts->strides[g + 1], pin_segs + ((size_t)plan.base[g] + b * units) * 16, rowb_g);
+    }
     if (h_roots && step == 1) memcpy(h_roots + (b0 ? (size_t)32 * (b0 + 1) : 0), pin_roots + (b0 ? 32 : 0), (size_t)32 * (k + (b0 ? 0 : 1)));
     if (h_roots && step == 2) {  // (b0 and k are even) R_0, then the root behind every insert's second update
       if (!b0) memcpy(h_roots, pin_roots, 32);
@@ -694,7 +780,7 @@ int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_inde
 // records, or what k_insert_records built), through update_rows: per chunk the new leaves = the digests of the chunk's new records, a head = the old record | the
 // new record at a pitch of record_head_pitch(length) each, and the table's write-back behind the levels.  rows_out = null: no gather, nothing staged out.
 int record_updates(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length, const uint8_t *d_fresh,
-                   size_t new_stride, uint8_t *h_roots, size_t rowb, const Pairs *pairs, const ChunkFn &rows_out) {
+                   size_t new_stride, uint8_t *h_roots, size_t rowb, const Pairs *pairs, const ChunkFn &rows_out, const Cuts *cuts = nullptr) {
   const uint32_t depth = t->depth;
   const size_t hp = mf::record_head_pitch(length);
   const int64_t table_span = (int64_t)((((size_t)1 << depth) - 1) * table_stride + length), fresh_span = (int64_t)((size_t)(nupd - 1) * new_stride + length);
@@ -713,7 +799,21 @@ int record_updates(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_i
     hipLaunchKernelGGL(k_record_store, dim3(std::max(1u, (items + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, d_fresh, new_stride, fresh_span, u.b0,
                        length, u.k, u.d_idx, u.d_last);
   };
-  return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, rows_out, pairs);
+  return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, rows_out, pairs, cuts);
+}
+
+// what a cut call asks of its cuts and of the ncuts + 1 row arrays of n rows each, segment 0's row being rowb0 bytes; 0 when they are fine
+const char *cuts_refused(uint32_t n, uint32_t ncuts, const uint32_t *h_cuts, uint32_t depth, uint8_t *const *h_rows, const size_t *h_strides, size_t rowb0) {
+  if (!ncuts || !h_cuts) return "no cuts (ncuts >= 1 and h_cuts)";
+  for (uint32_t g = 0; g < ncuts; g++)
+    if (h_cuts[g] < 1 || h_cuts[g] >= depth || (g && h_cuts[g] <= h_cuts[g - 1])) return "the cuts are not 1 <= c_0 < .. < c_G-1 < depth";
+  if (!h_rows || !h_strides) return "h_rows or h_strides is null";
+  for (uint32_t g = 0; g <= ncuts; g++) {
+    if (n && !h_rows[g]) return "a segment without its rows (a null pointer in h_rows)";
+    const size_t rowb = g ? mf::segment_row_bytes((g < ncuts ? h_cuts[g] : depth) - h_cuts[g - 1]) : rowb0;
+    if (h_strides[g] < rowb) return "a segment's stride shorter than its row's bytes";
+  }
+  return nullptr;
 }
 
 }  // namespace
@@ -842,15 +942,44 @@ int mfh_merkle_update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint3
   });
 }
 
-int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
-                              const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots) {
-  const char *who = "mfh_merkle_update_records";
+int mfh_merkle_update_rows_cut(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint32_t ncuts, const uint32_t *h_cuts,
+                               uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots) {
+  const char *who = "mfh_merkle_update_rows_cut";
   if (int rc = tree_refused(c, t, who)) return rc;
   const uint32_t depth = t->depth;
+  const size_t rowb0 = ncuts && h_cuts ? mf::row_bytes(64, 64, h_cuts[0]) : 0;
+  if (const char *what = cuts_refused(nupd, ncuts, h_cuts, depth, h_rows, h_strides, rowb0)) return fail(c, who, what);
+  if (nupd && !h_index) return fail(c, who, "updates without h_index");
+  if (nupd && !d_new_leaves) return fail(c, who, "updates without d_new_leaves");
+  if (reinterpret_cast<uintptr_t>(d_new_leaves) & 15) return fail(c, who, "d_new_leaves is not 16-byte aligned");
+  if (const char *what = indices_refused(h_index, nupd, depth)) return fail(c, who, what);
+  if (!nupd) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  const uint32_t c0 = h_cuts[0];
+  return update_rows(c, t, nupd, h_index, d_new_leaves, h_roots, rowb0 + mf::cut_rows_bytes(depth, ncuts, h_cuts), 0, nullptr, nullptr, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) {  // segment 0: the level row's head, its first c_0 siblings, the index mod 2^c_0
+      uint8_t *row = h_rows[0] + (size_t)(u.b0 + b) * h_strides[0];
+      memcpy(row, u.pin_rows + (size_t)b * u.rs, 128);
+      mf::splice_cut_tail(row + 128, u.pin_rows + (size_t)b * u.rs, c0, h_index[u.b0 + b]);
+    }
+  }, nullptr, &cuts);
+}
+
+}  // extern "C"
+
+namespace {
+
+// mfh_merkle_update_records (cuts = null: rows of the whole depth to h_inputs) and mfh_merkle_update_records_cut (segment 0's rows to cuts->h_rows[0])
+int update_records(mfh_ctx *c, mfh_merkle *t, const char *who, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                   const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, const Cuts *cuts) {
+  const uint32_t depth = t->depth, d0 = cuts ? cuts->cuts[0] : depth;  // d0: the levels of the caller's own row
   if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
   if (new_stride < length) return fail(c, who, "new_stride shorter than length");
-  const size_t rowb = mf::row_bytes(64, 2 * (size_t)length, depth);
-  if (in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + 2 length + 32 depth + ceil(depth / 8) bytes");
+  const size_t rowb = mf::row_bytes(64, 2 * (size_t)length, d0);
+  if (!cuts && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + 2 length + 32 depth + ceil(depth / 8) bytes");
+  if (cuts)
+    if (const char *what = cuts_refused(nupd, cuts->ncuts, cuts->cuts, depth, cuts->h_rows, cuts->strides, rowb)) return fail(c, who, what);
   if (nupd && !h_index) return fail(c, who, "updates without h_index");
   if (nupd && !h_inputs) return fail(c, who, "updates without h_inputs");
   if (nupd && !d_table) return fail(c, who, "updates without d_table");
@@ -859,12 +988,36 @@ int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const ui
   if (!nupd) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t hp = mf::record_head_pitch(length);
-  return record_updates(c, t, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_roots, rowb, nullptr, [&](const Chunk &u) {
+  return record_updates(c, t, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_roots, rowb + (cuts ? mf::cut_rows_bytes(depth, cuts->ncuts, cuts->cuts) : 0),
+                        nullptr, [&](const Chunk &u) {
     for (uint32_t b = 0; b < u.k; b++) {
-      const uint8_t *head = u.pin_heads + (size_t)b * u.hs;
-      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 64, {{head, length}, {head + hp, length}}, u.pin_rows + (size_t)b * u.rs, 128, depth);
+      const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs;
+      uint8_t *row = h_inputs + (size_t)(u.b0 + b) * in_stride;
+      mf::splice_row(row, 64, {{head, length}, {head + hp, length}}, cuts ? nullptr : staged, 128, depth);
+      if (cuts) mf::splice_cut_tail(row + 64 + 2 * (size_t)length, staged, d0, h_index[u.b0 + b]);
     }
-  });
+  }, cuts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_update_records_cut(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                                  const uint8_t *d_new_records, size_t new_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides,
+                                  uint8_t *h_roots) {
+  const char *who = "mfh_merkle_update_records_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nupd, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return update_records(c, t, who, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_rows[0], h_strides[0], h_roots, &cuts);
+}
+
+int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                              const uint8_t *d_new_records, size_t new_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots) {
+  const char *who = "mfh_merkle_update_records";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return update_records(c, t, who, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_inputs, in_stride, h_roots, nullptr);
 }
 
 int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
@@ -936,20 +1089,26 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
   });
 }
 
-int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
-                           size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
-                           uint8_t *h_status) {
-  const char *who = "mfh_merkle_insert_keys";
-  if (int rc = tree_refused(c, t, who)) return rc;
-  const uint32_t depth = t->depth;
+}  // extern "C"
+
+namespace {
+
+// mfh_merkle_insert_keys (cuts = null: one row of the whole depth an insert, nk + 1 roots) and mfh_merkle_insert_keys_cut (segment 0's row an insert to
+// cuts->h_rows[0] = h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots)
+int insert_keys(mfh_ctx *c, mfh_merkle *t, const char *who, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
+                uint8_t *h_status, const Cuts *cuts) {
+  const uint32_t depth = t->depth, d0 = cuts ? cuts->cuts[0] : depth;  // d0: the levels of the insert's own row
   if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
   if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
   if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
   if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
   const uint32_t plen = length - 2 * key_bytes;
   if (h_payloads && payload_stride < plen) return fail(c, who, "payload_stride shorter than the payload's length - 2 key_bytes bytes");
-  const size_t rowb = mf::insert_row_bytes(key_bytes, length, depth);
-  if (h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
+  const size_t rowb = mf::insert_row_bytes(key_bytes, length, d0, cuts ? 128 : 64);
+  if (!cuts && h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
+  if (cuts)  // (segment 0 has nk rows, the upper segments 2 nk: a null pointer is refused for either count)
+    if (const char *what = cuts_refused(nk, cuts->ncuts, cuts->cuts, depth, cuts->h_rows, cuts->strides, rowb)) return fail(c, who, what);
   if (nk && !d_table) return fail(c, who, "inserts without d_table");
   if (nk && !h_keys) return fail(c, who, "inserts without h_keys");
   if (nk && !h_index) return fail(c, who, "inserts without h_index");
@@ -966,14 +1125,15 @@ int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t t
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t kw = mf::key_words(key_bytes), nb = (n + 255) / 256, nupd = 2 * nk;
   const size_t hp = mf::record_head_pitch(length);
-  const uint32_t pair_ch = mf::insert_chunk(nk, rowb, kPathStageBytes);  // updates a chunk: whole inserts
+  // updates a chunk: whole inserts, all segments' rows together
+  const uint32_t pair_ch = mf::insert_chunk(nk, rowb + (cuts ? 2 * mf::cut_rows_bytes(depth, cuts->ncuts, cuts->cuts) : 0), kPathStageBytes);
   // On the device.  Kept for the whole call: fresh = the 2 nk new records at a pitch of hp | the plan (p, pred, succ an insert) | the keys | the payloads.  Behind
   // them, one after the other: the search (the keys' words | range[nk] | present[nk]), the inert search (mask words | count[nb] | total | slots[nk]), and per
   // chunk update_rows' scratch.
   const size_t fresh_bytes = (size_t)nupd * hp, plan_bytes = (size_t)nk * 12, keys_bytes = (size_t)nk * key_bytes, pay_bytes = h_payloads ? (size_t)nk * plen : 0;
   const size_t up_bytes = plan_bytes + keys_bytes + pay_bytes, skip = (fresh_bytes + up_bytes + 15) & ~(size_t)15;
   const size_t words_bytes = (size_t)nk * kw * 4, res_bytes = (size_t)2 * nk * 4, mask_bytes = (size_t)nb * 4 * 8, inert_bytes = mask_bytes + ((size_t)nb + 1 + nk) * 4;
-  if (int rc = work_reserve(c, c->circ_io, skip + std::max(std::max(words_bytes + res_bytes, inert_bytes), update_rows_bytes(depth, pair_ch, 2 * hp, 1)))) return rc;
+  if (int rc = work_reserve(c, c->circ_io, skip + std::max(std::max(words_bytes + res_bytes, inert_bytes), update_rows_bytes(depth, pair_ch, 2 * hp, 1, cuts)))) return rc;
   uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_keys = d_plan + plan_bytes, *d_pay = h_payloads ? d_keys + keys_bytes : nullptr;
   uint8_t *d_work = d_fresh + skip;
   const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
@@ -1069,18 +1229,41 @@ int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t t
   }
   HIP_TRY(c, hipGetLastError());
   // e. the 2 nk record updates, a chunk of whole inserts at a time; row b of a chunk out of the heads and the level rows of its updates 2 b and 2 b + 1
-  const Pairs chunks{pair_ch, skip};
+  const Pairs chunks{pair_ch, skip, cuts != nullptr};
+  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
   ChunkFn rows_out;
   if (h_inputs)
     rows_out = [&](const Chunk &u) {
       for (uint32_t b = 0; b + 1 < u.k; b += 2) {
         const uint32_t j = (u.b0 + b) / 2;
         const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
-        mf::splice_insert_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, hp, length, staged_p, staged_p + u.rs, depth,
-                              h_index[2 * (size_t)j], h_index[2 * (size_t)j + 1]);
+        mf::splice_insert_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, hp, length, staged_p, staged_p + u.rs, d0,
+                              h_index[2 * (size_t)j] & low, h_index[2 * (size_t)j + 1] & low, cuts ? 128 : 64);
       }
     };
-  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out);
+  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out, cuts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                           size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
+                           uint8_t *h_status) {
+  const char *who = "mfh_merkle_insert_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return insert_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_payloads, payload_stride, h_inputs, in_stride, h_roots, h_index, h_status, nullptr);
+}
+
+int mfh_merkle_insert_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                               size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                               const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_insert_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return insert_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_payloads, payload_stride, h_rows[0], h_strides[0], h_roots, h_index, h_status, &cuts);
 }
 
 }  // extern "C"

@@ -10,6 +10,12 @@
 //   words.MerkleInsert(key_bytes, length, depth)  Z = 64, head = the key | old record of p | old record of s | new record of s, and TWO tails' siblings:
 //                                                 depth siblings of p | depth siblings of s | ceil(2 depth / 8) index bytes, bit l < depth = bit l of p,
 //                                                 bit depth + l = bit l of s                      insert_row_bytes(key_bytes, length, depth)
+//   words.MerkleInsert(.., joined=False)          the same behind Z = 128 (four tops)                insert_row_bytes(key_bytes, length, depth, 128)
+//   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
+//                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
+// A path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) gives G + 1 rows an update: segment 0 is the statement's own row over the subtree of
+// height c_0 -- the head, the first c_0 siblings of the level row, the index masked to c_0 bits (splice_cut_tail) -- and segment g >= 1 a MerkleSegment row
+// of c_g - c_g-1 levels (c_G = depth), which k_merkle_cut_rows writes whole: its tail too starts at byte 128.
 // The kernels write whole rows where the tail lands on a 16-byte unit: k_merkle_paths the path row (tail at byte 64), k_merkle_update_level the level row
 // (tail at byte 128), both staged at staged_stride of their bytes.  A head of records puts the tail anywhere, so for those statements the device stages two
 // pieces per row and the host splices them while it copies out of the pinned buffer (splice_row):
@@ -37,8 +43,24 @@ inline uint32_t update_chunk(uint32_t nupd, size_t row_bytes, size_t stage_bytes
   return (uint32_t)(fit < 1 ? 1 : fit < nupd ? fit : nupd);
 }
 
-inline size_t insert_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth) {
-  return (size_t)64 + key_bytes + (size_t)3 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
+inline size_t insert_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth, size_t zeros = 64) {
+  return zeros + key_bytes + (size_t)3 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
+}
+
+inline size_t segment_row_bytes(uint32_t levels) { return row_bytes(64, 64, levels); }
+// the 16-byte units of a staged segment row: 8 of nodes and zeros, 2 a sibling, 1 for the index
+inline uint32_t segment_row_units(uint32_t levels) { return 9 + 2 * levels; }
+// the staged bytes of the upper segments of ONE update of a path of `depth` levels cut at cuts[0 .. ncuts)
+inline size_t cut_staged_bytes(uint32_t depth, uint32_t ncuts, const uint32_t *cuts) {
+  size_t units = 0;
+  for (uint32_t g = 0; g < ncuts; g++) units += segment_row_units((g + 1 < ncuts ? cuts[g + 1] : depth) - cuts[g]);
+  return units * 16;
+}
+// ... and the bytes of their rows as the caller gets them
+inline size_t cut_rows_bytes(uint32_t depth, uint32_t ncuts, const uint32_t *cuts) {
+  size_t bytes = 0;
+  for (uint32_t g = 0; g < ncuts; g++) bytes += segment_row_bytes((g + 1 < ncuts ? cuts[g + 1] : depth) - cuts[g]);
+  return bytes;
 }
 
 // the updates of one chunk of a batch of nk inserts (nk > 0): the most INSERTS whose rows of row_bytes fit the stage, at least one, two updates each -- always
@@ -62,13 +84,21 @@ inline void splice_row(uint8_t *row, size_t zeros, std::initializer_list<RowPiec
   if (staged) memcpy(row, staged + tail_at, row_tail_bytes(depth));
 }
 
+// at <- the tail of a segment-0 row: the first c0 siblings of the level row `staged` (tail at byte 128), then the ceil(c0 / 8) bytes of index mod 2^c0
+inline void splice_cut_tail(uint8_t *at, const uint8_t *staged, uint32_t c0, uint32_t index) {
+  memcpy(at, staged + 128, (size_t)32 * c0);
+  const uint32_t low = index & (uint32_t)(((uint64_t)1 << c0) - 1);
+  for (uint32_t b = 0; b < (c0 + 7) / 8; b++) at[(size_t)32 * c0 + b] = (uint8_t)(low >> (8 * b));
+}
+
 // row <- the input row of words.MerkleInsert for the insert whose updates are (record p: head_p = old | new at a pitch of hp; slot s: head_s likewise) and
 // whose level rows are staged_p and staged_s (tails at byte 128): 64 zero bytes | key | old_p | old_s | new_s | p's siblings | s's siblings | the index bytes of
 // (p, s).  Reads key_bytes, length and 32 depth bytes of its sources, writes insert_row_bytes(key_bytes, length, depth) bytes and nothing behind them.
+// Segment 0 of a cut insert (joined=False): zeros = 128, depth = c_0 -- the first c_0 siblings of each level row -- and p, s already reduced mod 2^c_0.
 inline void splice_insert_row(uint8_t *row, const uint8_t *key, uint32_t key_bytes, const uint8_t *head_p, const uint8_t *head_s, size_t hp, uint32_t length,
-                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s) {
-  memset(row, 0, 64);
-  row += 64;
+                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s, size_t zeros = 64) {
+  memset(row, 0, zeros);
+  row += zeros;
   memcpy(row, key, key_bytes);
   row += key_bytes;
   if (length) {

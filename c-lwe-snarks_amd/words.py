@@ -49,6 +49,11 @@ Whole statements built from that compression, the result 256 computed public out
                             body plus "lo < q < hi" (two Words.less_than), q public (lu = 256 + 8 key_bytes).  MerkleRecord(length, depth)'s sizes plus 40
                             key_bytes wires and 72 key_bytes + 2 rows: (4, 8, 1) -> (56 444, 100 288) fits d = 2^17; (8, 55, 19) fits d = 2^20.  Sound
                             relative to the table's invariant (the class has it); indexed_records / indexed_insert make and extend such tables.
+    MerkleInsert(key_bytes, length, depth, joined=True)   "key k was inserted into the indexed table, and that alone takes the tree from R to R'"; joined=False
+                            outputs all four chain tops (lu = 1024 + 8 key_bytes): segment 0 of an insert into a tree deeper than one circuit.
+    MerkleSegment(levels)   "one node changed from X to X', and that alone takes its ancestor `levels` levels up from Y to Y'" (lu = 1024, the two nodes
+                            given, the two tops computed): one level range of a path cut by segment_levels(depth, cuts); MerkleUpdate's sizes, 10 levels
+                            fit d = 2^20.  chain(nodes) turns the published node pairs of a transition into the upper segments' statements.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
@@ -678,6 +683,77 @@ class MerkleUpdate(_TwoRoots):
         return _input_bits(512, _tail_bits("MerkleUpdate", self.depth, siblings, index, (old_leaf, new_leaf), "two 32-byte leaves and "))
 
 
+class MerkleSegment(_Statement):
+    """The statement "one node changed from X to X', and that change alone takes its ancestor `levels` levels up from Y to Y'": MerkleUpdate's body with the
+    two leaves made PUBLIC -- one level range of a path that is too deep for one circuit (segment_levels cuts it).
+
+    A deep transition R -> R' is proved per level range.  With cuts c_0 < .. < c_G-1 segment 0 is an existing statement (MerkleUpdate, MerkleRecordUpdate,
+    MerkleInsert(joined=False)) over the subtree of height c_0 that holds the leaf, its "roots" the old and new value of the level-c_0 node on the path, and
+    segment g >= 1 is MerkleSegment(c_g - c_g-1) (c_G = the depth).  The prover publishes the node pairs (X_g, X_g'), g = 0 .. G, (X_G, X_G') = (R, R'); the
+    verifier builds every segment's statement bytes from that ONE list (chain), so adjacent segments agree by construction, and checks one proof a segment.
+    Soundness is MerkleUpdate's applied G + 1 times: within a segment the old and the new pass share siblings and directions, so nothing but the lower node
+    changed below its top.  A segment's private index bits need not be consistent with its neighbours'.
+    WHAT BECOMES PUBLIC: the intermediate nodes (X_g, X_g'), 0 <= g < G.  They are hashes; nothing else is revealed.
+    Public wires, in this order (public wires are laid out in declaration order, so the given ones come first): the old node as 8 given words at statement bits
+    [0, 256), the new node at [256, 512), the old top as 256 computed outputs at [512, 768), the new top at [768, 1024); lu = 1024.  Private inputs: `levels`
+    siblings of 8 words from the node's level up, then `levels` direction bits.  The packed row (csrc/merkle_rows.hpp): old node as words | new node as words
+    | 64 zero bytes | the siblings as words | ceil(levels / 8) index bytes -- the tail starts at byte 128, as in MerkleUpdate's row.
+    MerkleTree.update_segments / update_record_segments / insert_key_segments give every segment's rows and the published nodes for a device tree.
+    Sizes (MERKLE_SEGMENT_SIZES): exactly MerkleUpdate's, 56 993 levels + 1 026 wires and 101 473 levels + 1 540 rows; levels = 10 is the most that fits
+    Params(d=1 << 20, m=699050), levels = 1 fits Params(d=1 << 17, m=87381)."""
+
+    def __init__(self, levels: int):
+        self.levels = self.depth = self._arg(levels, 1, None, "levels is at least 1")
+        self.w = w = Words()
+        self.old_node = w.public(8)
+        self.new_node = w.public(8)
+        self._tail_wires()
+        self.out_old = _merkle_levels(w, self.old_node, self.siblings, self.dirs)
+        self.out_new = _merkle_levels(w, self.new_node, self.siblings, self.dirs)
+        self.old_top = [w.output(x) for x in self.out_old]
+        self.new_top = [w.output(x) for x in self.out_new]
+
+    @property
+    def lu(self) -> int:
+        return 1024
+
+    def bits(self, old_node: bytes, new_node: bytes, siblings, index: int):
+        """one statement's input bits, public then private: the old node, the new node, 512 zeros where the two tops are computed, the siblings from the node's
+        level up, then the direction bits = the bits of the node's index inside the segment's subtree, least significant first"""
+        tail = _tail_bits("MerkleSegment", self.levels, siblings, index, (old_node, new_node), "two 32-byte nodes and ")
+        return np.concatenate([tail[:512], np.zeros(512, dtype=np.uint8), tail[512:]])
+
+    def tops_of(self, witness_row):
+        """(old_top, new_top), 32 bytes each, as computed: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 512), _digest_from_row(witness_row, 768)
+
+    @staticmethod
+    def statement(old_node: bytes, new_node: bytes, old_top: bytes, new_top: bytes) -> bytes:
+        """the 128 statement bytes (what verify_public takes, bits [0, 1024) of a witness row) that say "old_node -> new_node takes old_top to new_top": each
+        quarter MerklePath.statement's bytes"""
+        return b"".join(_statement_of(x, f"MerkleSegment: {what}") for x, what in ((old_node, "the old node"), (new_node, "the new node"),
+                                                                                  (old_top, "the old top"), (new_top, "the new top")))
+
+    @classmethod
+    def chain(cls, nodes):
+        """the G upper statements of one transition from its published list [(X_0, X_0'), .., (X_G, X_G')], (X_G, X_G') = (R, R'): statement g - 1 of the result
+        is segment g's, statement(X_g-1, X_g-1', X_g, X_g').  Segment 0's statement is its own class's, over (X_0, X_0')."""
+        nodes = [(bytes(a), bytes(b)) for a, b in nodes]
+        if len(nodes) < 2:
+            raise CircuitError("MerkleSegment: a chain is at least two node pairs")
+        return [cls.statement(*nodes[g - 1], *nodes[g]) for g in range(1, len(nodes))]
+
+
+def segment_levels(depth: int, cuts):
+    """[(0, c_0), (c_0, c_1), .., (c_G-1, depth)]: the level ranges of a path of `depth` levels cut at `cuts`; CircuitError unless 1 <= c_0 < .. < c_G-1 < depth"""
+    cuts = list(cuts)
+    if (not isinstance(depth, (int, np.integer)) or not cuts or not all(isinstance(c, (int, np.integer)) for c in cuts) or cuts[0] < 1 or cuts[-1] >= depth
+            or any(a >= b for a, b in zip(cuts, cuts[1:]))):
+        raise CircuitError("segment_levels: cuts are 1 <= c_0 < .. < c_G-1 < depth, at least one")
+    edges = [0] + [int(c) for c in cuts] + [int(depth)]
+    return list(zip(edges, edges[1:]))
+
+
 class MerkleRecordUpdate(_TwoRoots):
     """The statement "I know an old record and a new record of `length` bytes, `depth` siblings and an index such that the path from SHA-256(old record)
     gives old_root and the SAME siblings and directions from SHA-256(new record) give new_root": MerkleUpdate about the data behind the leaf.
@@ -813,9 +889,17 @@ class MerkleInsert(_TwoRoots):
     they matter), and, like MerkleAbsent, it says nothing about the records it does not open.
     MerkleTree.insert_keys / insert_bits perform a batch of inserts on a device table and give the input rows; statement j is (R_j, R_j+1, key_j).
     Sizes (MERKLE_INSERT_SIZES): four level chains cost about 203 000 rows a level, so (8, 55, 4) is the deepest one-block statement that fits
-    Params(d=1 << 20, m=699050); depth 5 (about 1 212 000 rows) does not.  Depth 1 fits Params(d=1 << 19, m=349525)."""
+    Params(d=1 << 20, m=699050); depth 5 (about 1 212 000 rows) does not.  Depth 1 fits Params(d=1 << 19, m=349525).
+    joined=False is segment 0 of an insert into a deeper tree (MerkleSegment): the 256 assert_same on the middle roots are dropped and all four chain tops are
+    outputs, so p and s may lie in different height-`depth` subtrees.  Public wires then: X_p at [0, 256), X_p' at [256, 512), X_s at [512, 768), X_s' at
+    [768, 1024), the key's bits from 1024; lu = 1024 + 8 key_bytes; statement(X_p, X_p', X_s, X_s', key); tops_of(row) reads the four back; the packed row is
+    the joined one with 128 zero bytes in front in place of 64.  X_s is opened in the tree after p's update, so the p != s argument above still holds; the upper
+    chain of s starts from the root after p's update, which thereby becomes public.  Sizes (MERKLE_INSERT_SPLIT_SIZES): the joined ones plus 512 wires and 768
+    rows; (8, 55, 4) still fits Params(d=1 << 20, m=699050)."""
 
-    def __init__(self, key_bytes: int, length: int, depth: int):
+    joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
+
+    def __init__(self, key_bytes: int, length: int, depth: int, joined=True):
         self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
         self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
         self.depth = depth = self._depth_arg(depth)
@@ -830,11 +914,16 @@ class MerkleInsert(_TwoRoots):
         self.blocks = leaves[0][1]
         tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
         self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for (leaf, _), (sibs, dirs) in zip(leaves, tails))
+        self.joined = bool(joined)
         self.old_root = [w.output(x) for x in self.out_old]
+        if not self.joined:  # every chain top is public: X_p, X_p', X_s, X_s'
+            self.top_mid_p = [w.output(x) for x in self.mid_p]
+            self.top_mid_s = [w.output(x) for x in self.mid_s]
         self.new_root = [w.output(x) for x in self.out_new]
         self.key = w.c.public(8 * K)
-        for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
-            w.assert_same_u32(x, y)
+        if self.joined:
+            for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
+                w.assert_same_u32(x, y)
         for a, b in zip(self.key, self.new_s[: 8 * K]):
             w.c.assert_same(a, b)
         for a, b in zip(self.old_p[8 * K: 16 * K], self.new_s[8 * K: 16 * K]):
@@ -847,7 +936,7 @@ class MerkleInsert(_TwoRoots):
 
     @property
     def lu(self) -> int:
-        return 512 + 8 * self.key_bytes
+        return (512 if self.joined else 1024) + 8 * self.key_bytes
 
     def _query(self, key) -> bytes:
         key = bytes(key)
@@ -858,20 +947,30 @@ class MerkleInsert(_TwoRoots):
         return key
 
     def bits(self, key: bytes, old_p: bytes, old_s: bytes, new_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
-        """one statement's input bits, public then private: 512 zeros where the two roots are computed, the key's bits, the three records' bits, p's
-        siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A witness that breaks a
-        constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits,
+        the three records' bits, p's siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A
+        witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
         who = "MerkleInsert"
         key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
         tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
         nsib = 256 * self.depth
-        return _input_bits(512, key, _record_bits(who, self.length, old_p, old_s, new_s, what="the records are"), tail_p[:nsib], tail_s[:nsib], tail_p[nsib:],
-                           tail_s[nsib:])
+        return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, old_p, old_s, new_s, what="the records are"), tail_p[:nsib],
+                           tail_s[:nsib], tail_p[nsib:], tail_s[nsib:])
 
-    def statement(self, old_root: bytes, new_root: bytes, key: bytes) -> bytes:
-        """the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "inserting `key` took old_root to
-        new_root": MerkleUpdate.statement's bytes, then the key"""
-        return super().statement(old_root, new_root) + self._query(key)
+    def statement(self, *tops_and_key) -> bytes:
+        """statement(old_root, new_root, key): the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "inserting
+        `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 + key_bytes
+        bytes: "inserting `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
+        *tops, key = tops_and_key
+        if len(tops) != (2 if self.joined else 4):
+            raise CircuitError("MerkleInsert: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
+        return b"".join(_statement_of(x, "MerkleInsert: a top") for x in tops) + self._query(key)
+
+    def tops_of(self, witness_row):
+        """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
+        if self.joined:
+            raise CircuitError("MerkleInsert: tops_of is for joined=False (roots_of reads the two roots)")
+        return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
 
 
 def _keys_array(keys, who: str):
@@ -969,3 +1068,9 @@ MERKLE_ABSENT_SIZES = {(4, 8, 1): (56444, 100288), (8, 16, 1): (56672, 100644), 
 # key_bytes equalities tie the middle roots, k and the inherited hi.  A level costs 113 986 wires and 202 946 rows (twice MerkleUpdate's).  Depth 1 fits
 # Params(d=1 << 19, m=349525); (8, 55, 4) is the deepest one-block statement that fits Params(d=1 << 20, m=699050): (8, 55, 5) would be 1 212 537 rows
 MERKLE_INSERT_SIZES = {(4, 8, 1): (224264, 399117), (8, 55, 1): (225644, 400753), (8, 16, 4): (566654, 1008643), (8, 55, 4): (567602, 1009591)}
+# ... and of MerkleInsert(joined=False): the joined sizes plus 512 wires (two more tops are outputs) and 768 rows (their 512 bit rows and 512 equality rows, less
+# the 256 equalities on the middle roots); (8, 55, 4) still fits Params(d=1 << 20, m=699050)
+MERKLE_INSERT_SPLIT_SIZES = {(4, 8, 1): (224776, 399885), (8, 55, 1): (226156, 401521), (8, 55, 4): (568114, 1010359)}
+# ... and of MerkleSegment by levels: MerkleUpdate's, 56 993 levels + 1 026 wires and 101 473 levels + 1 540 rows (the two nodes are public inputs where
+# MerkleUpdate's leaves are private ones); 10 levels fit Params(d=1 << 20, m=699050), 11 (1 117 743 rows) do not
+MERKLE_SEGMENT_SIZES = {1: (58019, 103013), 2: (115012, 204486), 10: (570956, 1016270)}

@@ -479,6 +479,36 @@ int mfh_merkle_absent_rows(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_t
 int mfh_merkle_insert_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
                            const uint8_t *h_keys, size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride,
                            uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+/* ---- The three update calls above with the PATH CUT into level ranges, for trees deeper than one circuit: what words.MerkleSegment proves per range.
+ * h_cuts holds ncuts >= 1 levels 1 <= c_0 < c_1 < .. < c_G-1 < depth (G = ncuts); segment 0 covers levels [0, c_0), segment g >= 1 levels [c_g-1, c_g) with
+ * c_G = depth.  In place of (h_inputs, in_stride) the calls take h_rows and h_strides, arrays of ncuts + 1 row pointers and strides, one per segment:
+ *   segment 0   the parent call's row over the subtree of height c_0 that holds the leaf: the same head, the first c_0 siblings, ceil(c_0 / 8) bytes holding
+ *               the index mod 2^c_0 -- the packed input row of MerkleUpdate(c_0) (mfh_merkle_update_rows_cut: 128 + 32 c_0 + ceil(c_0 / 8) bytes), of
+ *               MerkleRecordUpdate(length, c_0) (mfh_merkle_update_records_cut: 64 + 2 length + ..) or, ONE ROW PER INSERT, of MerkleInsert(key_bytes, length, c_0,
+ *               joined=False) (mfh_merkle_insert_keys_cut: 128 zero bytes | key | old p | old s | new s | c_0 siblings of p | c_0 of s | ceil(2 c_0 / 8) index
+ *               bytes of p mod 2^c_0 and s mod 2^c_0).  The values its circuit computes are the old and new node of level c_0 on the path.
+ *   segment g   the packed input row of MerkleSegment(levels = c_g - c_g-1), ONE ROW PER UPDATE (an insert is two updates: 2 nk rows, p's then s's of each
+ *               insert): the old node of level c_g-1 on the update's path as 8 words | the new node as 8 words | 64 zero bytes where the two tops are computed
+ *               | the siblings of levels c_g-1 .. c_g - 1 in mfh_merkle_paths' word convention | ceil(levels / 8) bytes holding (index >> c_g-1) mod
+ *               2^levels.  Exactly 128 + 32 levels + ceil(levels / 8) bytes of a row are written, the rest of a wider row is left alone.
+ * The published node pairs of an update are the heads of its rows: (X_g, X_g') for g < G are bytes [0, 64) of its segment g + 1 row (words: swap each
+ * word's bytes for the digest), (X_G, X_G') = (R_k, R_k+1) from h_roots.  mfh_merkle_insert_keys_cut writes ALL 2 nk + 1 roots to h_roots, so the root
+ * between an insert's two updates, from which the upper chain of s starts, is there.  Tree, table, h_index, h_status and the order of events are the
+ * parent call's; so are its kernels, with ONE more launch per chunk, k_merkle_cut_rows, behind the last k_merkle_update_level and before the write-back
+ * (it reads stored nodes of the cut levels that the write-back may replace).  A chunk is the most updates (or whole inserts) whose rows, all segments
+ * together, fit 64 MiB, at least one.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued, written or changed: everything the parent call refuses, and ncuts = 0
+ * or h_cuts null; cuts that are not 1 <= c_0 < .. < c_G-1 < depth; h_rows or h_strides null; a null pointer in h_rows with rows to write; a stride below
+ * its segment's row bytes.  mfh_merkle_insert_keys_cut has no "no rows" mode.
+ * Kernel timing kinds: the parent call's, and "merkle_segments" (1 per chunk, rows = the chunk's updates x ncuts). */
+int mfh_merkle_update_rows_cut(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, const uint8_t *d_new_leaves, uint32_t ncuts,
+                               const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots);
+int mfh_merkle_update_records_cut(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length,
+                                  const uint8_t *d_new_records, size_t new_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                                  const size_t *h_strides, uint8_t *h_roots);
+int mfh_merkle_insert_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
+                               const uint8_t *h_keys, size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint32_t ncuts, const uint32_t *h_cuts,
+                               uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
