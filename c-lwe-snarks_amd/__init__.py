@@ -103,6 +103,7 @@ EXPORTS = [
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
+    "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut",
 ]
 
 
@@ -245,6 +246,8 @@ def load_library():
         "mfh_merkle_update_rows_cut": (i32, [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp]),
         "mfh_merkle_update_records_cut": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, sz, u32, vp, vp, vp, vp]),
         "mfh_merkle_insert_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_remove_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, vp, vp]),
+        "mfh_merkle_remove_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -718,6 +721,77 @@ class MerkleTree:
         out = self.insert_key_segments(table, keys, cuts, payloads)
         kb, length = np.ascontiguousarray(keys).shape[1], int(table.shape[1])
         return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 8 * kb + 24 * length + 514 * c0),) + tuple(out[1:])
+
+    # ---- removes: the inverse of insert_keys
+    def _remove_keys(self, table, keys, who):
+        tab, tstride, length = self._table(table, who)
+        k = np.ascontiguousarray(keys)
+        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
+            raise MfhError(f"{who}: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        return tab, tstride, length, k
+
+    def remove_keys(self, table, keys, roots=False):
+        """(rows, index): nk sequential key removes from an INDEXED table (words.MerkleAbsent has the data model) and this tree in one call
+        (mfh_merkle_remove_keys; waits for the stream).  Remove j zeroes the live record whose own key is keys[j] (it becomes inert, as indexed_records leaves
+        unused slots) and hands its hi to the live record whose hi was keys[j]; an earlier remove of the batch may have taken a neighbour already.  rows is
+        np.uint8 [nk, 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8)]: row j is the packed input row of words.MerkleRemove(key_bytes, length, depth)
+        taken from table and tree as they stood before remove j.  index is np.uint32 [nk, 2]: (the slot whose hi changed, the slot that was zeroed).  With
+        roots=True a triple whose last element is np.uint8 [nk + 1, 32], the roots R_0 .. R_nk: statement j is MerkleRemove.statement(R_j, R_j+1, keys[j]).
+        table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, all different.  MfhError with the
+        library's text, table and tree untouched, when a key is not a member or no live record has a member as its hi.  With all-zero inert slots,
+        insert_keys of a batch followed by remove_keys of the same keys restores the table's bytes and the root."""
+        c = self._ctx
+        tab, tstride, length, k = self._remove_keys(table, keys, "remove_keys")
+        nk, kb = k.shape
+        rows = np.zeros((nk, 64 + kb + 2 * length + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
+        index = np.zeros((nk, 2), dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots else None
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_remove_keys(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(rows.ctypes.data), rows.shape[1],
+                                            vp(r.ctypes.data) if roots else None, vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif roots:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        return (rows, index, r) if roots else (rows, index)
+
+    def remove_bits(self, table, keys, roots=False):
+        """remove_keys with the rows as np.uint8 [nk, 512 + 8 key_bytes + 16 length + 514 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
+        words.MerkleRemove(key_bytes, length, depth)"""
+        out = self.remove_keys(table, keys, roots)
+        head = 64 + np.ascontiguousarray(keys).shape[1] + 2 * int(table.shape[1])
+        bits = np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth]
+        return (bits,) + tuple(out[1:])
+
+    def remove_key_segments(self, table, keys, cuts):
+        """remove_keys with the path cut at levels `cuts` (mfh_merkle_remove_keys_cut).  Returns (rows, nodes_p, nodes_s, index): rows[0][j] is the packed input
+        row of words.MerkleRemove(key_bytes, length, c_0, joined=False) of remove j; rows[g], g >= 1, holds one words.MerkleSegment row per UPDATE, row 2 j that
+        of p's update of remove j and row 2 j + 1 that of s's; nodes_p and nodes_s are np.uint8 [nk, G + 1, 2, 32], the published pairs of the two updates:
+        segment 0's statement is statement(*nodes_p[j, 0], *nodes_s[j, 0], keys[j]), the upper ones MerkleSegment.chain(nodes_p[j]) and chain(nodes_s[j]), and
+        nodes_p[j, G, 1] == nodes_s[j, G, 0] is the root between the two updates, which becomes public.  index as remove_keys gives it."""
+        c = self._ctx
+        tab, tstride, length, k = self._remove_keys(table, keys, "remove_key_segments")
+        nk, kb = k.shape
+        rows, cargs, keep = self._cut(cuts, "remove_key_segments", nk, lambda c0: 128 + kb + 2 * length + 64 * c0 + (2 * c0 + 7) // 8, 2 * nk)
+        index = np.zeros((nk, 2), dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        r = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_remove_keys_cut(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, *cargs, vp(r.ctypes.data),
+                                                vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        else:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        nodes = self._cut_nodes(rows, r)
+        return rows, nodes[0::2], nodes[1::2], index
+
+    def remove_key_segment_bits(self, table, keys, cuts):
+        """remove_key_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.remove_key_segments(table, keys, cuts)
+        kb, length = np.ascontiguousarray(keys).shape[1], int(table.shape[1])
+        return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 8 * kb + 16 * length + 514 * c0),) + tuple(out[1:])
 
 
 class Context:

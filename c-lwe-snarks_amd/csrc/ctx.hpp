@@ -96,7 +96,7 @@ struct mfh_ctx {
   DevBuf ssp_frag;  // the dense SSP in MFMA B-fragment order (witness.hip: witness pass of the batch prover); built lazily
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
-  DevBuf circ_io;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements; mfh_merkle_paths (merkle.hip): rows | indices of one chunk; mfh_merkle_update_rows: node values | rows | schedule of one chunk; mfh_merkle_absent_rows: query words | results, then path rows | heads | indices of one chunk; mfh_merkle_insert_keys: new records | plan | keys | payloads, then the search's and mfh_merkle_update_rows' scratch
+  DevBuf circ_io;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements; mfh_merkle_paths (merkle.hip): rows | indices of one chunk; mfh_merkle_update_rows: node values | rows | schedule of one chunk; mfh_merkle_absent_rows: query words | results, then path rows | heads | indices of one chunk; mfh_merkle_insert_keys: new records | plan | keys | payloads, then the search's and mfh_merkle_update_rows' scratch; mfh_merkle_remove_keys: new records | plan | keys, then the same
   DevBuf circ_state;  // mfh_circuit_assign of a mfh_circuit_create_global program: the wire words of one chunk, one column per 32 statements
   DevBuf d_batch;  // mfh_prove_batch group scratch: W | H | V | CW | ONE | CT_T
   // mfh_prove_batch, more than one group of proofs and no image registered: the CRS is expanded ONCE PER CALL into this scratch in

@@ -26,6 +26,8 @@
 // whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp).
 // k_inert_flags, k_inert_scan, k_inert_select, k_insert_records: mfh_merkle_insert_keys, a batch of sequential key inserts into an indexed table in one call --
 // the lowest inert slots found on the device, all new records built in one launch, then the record updates above (the host's plan: merkle_insert.hpp).
+// k_key_owners, k_remove_records: mfh_merkle_remove_keys, a batch of sequential key removes from an indexed table in one call -- every key's own record and
+// predecessor found in one pass, all new records built in one launch, then the record updates above (the host's plan: merkle_remove.hpp).
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
 #include <functional>
@@ -33,6 +35,7 @@
 #include "ctx.hpp"
 #include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
+#include "merkle_remove.hpp"
 #include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
 #include "sha256_dev.hpp"
@@ -540,6 +543,85 @@ __global__ __launch_bounds__(256) void k_insert_records(const uint8_t *__restric
       out = merge_unit(out, load_unit_within(table, rec_p + o, rec_p + e, table_span), o, 2 * K, length);
     } else if (pay) {
       out = merge_unit(out, load_unit_within(pay, pay_key * plen + o - 2 * K, pay_key * plen + e - 2 * K, pay_span), o, 2 * K, length);
+    }
+  }
+  fresh[g] = out;
+}
+
+// ---- mfh_merkle_remove_keys: where the keys of a batch of removes stand in an indexed table, and the 2 nk new records of the batch.
+//
+// k_key_owners<KW>, ONE launch per call whatever nk, one thread per record, KW = ceil(key_bytes / 4).  A thread loads lo and hi through load_key_words as
+// k_key_locate does (any alignment; nothing outside the table's span is read); an inert record (!(lo < hi)) does nothing.  It binary-searches the nu sorted
+// unique queries qw for the first query >= lo: where that query equals lo this record is the query's own, own[u] <- min(own[u], i).  Then it searches for the
+// first query >= hi, from the first query above lo on (hi > lo): where that equals hi this record is the query's predecessor, prev[u] <- min(prev[u], i).
+// Both result arrays start at 0xFFFFFFFF; the atomic minimum makes the answer on a malformed table (two live records with one lo, or one hi) the lowest
+// index, whatever order the threads run in.  A thread makes at most two single atomics: no range to fill, no wave cooperation, every thread may leave early.
+// The queries are searched through the vector L1 and L2, not staged in LDS, for k_key_locate's reasons.
+template <int KW>
+__device__ __forceinline__ uint32_t first_query_not_below(const uint32_t *__restrict__ qw, uint32_t l, uint32_t r, const uint32_t *key) {
+  uint32_t q[KW];
+  while (l < r) {
+    const uint32_t m = l + (r - l) / 2;
+#pragma unroll
+    for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
+    if (key_less<KW>(q, key)) l = m + 1; else r = m;
+  }
+  return l;
+}
+
+template <int KW>
+__device__ __forceinline__ bool query_equals(const uint32_t *__restrict__ qw, uint32_t u, const uint32_t *key) {
+  bool same = true;
+#pragma unroll
+  for (int j = 0; j < KW; j++) same = same && qw[(size_t)u * KW + j] == key[j];
+  return same;
+}
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_key_owners(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t n,
+                                                    const uint32_t *__restrict__ qw, uint32_t nu, uint32_t *__restrict__ own, uint32_t *__restrict__ prev) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t lo[KW], hi[KW];
+  const int64_t at = (int64_t)((size_t)i * stride);
+  load_key_words<KW>(table, at, key_bytes, span, lo);
+  load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
+  if (!key_less<KW>(lo, hi)) return;
+  uint32_t u = first_query_not_below<KW>(qw, 0, nu, lo);
+  if (u < nu && query_equals<KW>(qw, u, lo)) {
+    atomicMin(own + u, i);
+    u++;  // the first query above lo
+  }
+  if (u >= nu) return;
+  u = first_query_not_below<KW>(qw, u, nu, hi);
+  if (u < nu && query_equals<KW>(qw, u, hi)) atomicMin(prev + u, i);
+}
+
+// k_remove_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
+// aligned).  One item per record r and 16-byte unit u; the store is the whole unit.  With (P, hi_key, hi_rec) = plan[3 j ..] of remove j (merkle_remove.hpp):
+//   record 2 j      the table's record P with bytes [K, 2K) replaced: by key hi_key of the batch (hi_key >= 0), else by bytes [K, 2K) of the table's record hi_rec
+//   record 2 j + 1  all zero: the inert record
+// No record of the batch depends on another (merkle_remove.hpp): every source is the table as it stood BEFORE the batch or a key -- one launch, no ordering
+// among the items, and the table is only read.  K need not be a multiple of 4 and the table sits at any byte alignment, so a unit may straddle the three
+// ranges anywhere: as in k_insert_records, load_unit_within fetches the 16 bytes of a source that line up with the unit and merge_unit takes each range's
+// bytes under per-dword byte masks.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [keys, keys + nk K) and the plan.
+__global__ __launch_bounds__(256) void k_remove_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ keys,
+                                                        const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t length, uint32_t nk, uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (2 nk units < 2^32: checked by the host)
+  if (g >= 2 * nk * units) return;
+  const uint32_t r = g / units, u = g - r * units, j = r >> 1;
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (!(r & 1)) {
+    const int64_t o = 16 * (int64_t)u, K = key_bytes, keys_span = (int64_t)nk * K;
+    const int32_t hi_key = plan[3 * j + 1];
+    const int64_t rec_p = (int64_t)((size_t)(uint32_t)plan[3 * j] * table_stride), rec_h = (int64_t)((size_t)(uint32_t)plan[3 * j + 2] * table_stride);
+    const uint4 v = load_unit_within(table, rec_p + o, rec_p + min(o + 16, (int64_t)length), table_span);  // lo and the payload
+    out = merge_unit(merge_unit(out, v, o, 0, K), v, o, 2 * K, length);
+    if (o < 2 * K && o + 16 > K) {  // hi
+      const int64_t e = min(o + 16, 2 * K);
+      const uint4 h = hi_key >= 0 ? load_unit_within(keys, hi_key * K + o - K, hi_key * K + e - K, keys_span) : load_unit_within(table, rec_h + o, rec_h + e, table_span);
+      out = merge_unit(out, h, o, K, 2 * K);
     }
   }
   fresh[g] = out;
@@ -1264,6 +1346,149 @@ int mfh_merkle_insert_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size
   if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
   const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
   return insert_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_payloads, payload_stride, h_rows[0], h_strides[0], h_roots, h_index, h_status, &cuts);
+}
+
+}  // extern "C"
+
+namespace {
+
+// mfh_merkle_remove_keys (cuts = null: one row of the whole depth a remove, nk + 1 roots) and mfh_merkle_remove_keys_cut (segment 0's row a remove to
+// cuts->h_rows[0] = h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots): insert_keys' driver without the inert search, the search and the build
+// kernels swapped
+int remove_keys(mfh_ctx *c, mfh_merkle *t, const char *who, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status, const Cuts *cuts) {
+  const uint32_t depth = t->depth, d0 = cuts ? cuts->cuts[0] : depth;  // d0: the levels of the remove's own row
+  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
+  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
+  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
+  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
+  const size_t rowb = mf::remove_row_bytes(key_bytes, length, d0, cuts ? 128 : 64);
+  if (!cuts && h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
+  if (cuts)  // (segment 0 has nk rows, the upper segments 2 nk: a null pointer is refused for either count)
+    if (const char *what = cuts_refused(nk, cuts->ncuts, cuts->cuts, depth, cuts->h_rows, cuts->strides, rowb)) return fail(c, who, what);
+  if (nk && !d_table) return fail(c, who, "removes without d_table");
+  if (nk && !h_keys) return fail(c, who, "removes without h_keys");
+  if (nk && !h_index) return fail(c, who, "removes without h_index");
+  if (nk && !h_status) return fail(c, who, "removes without h_status");
+  const uint32_t n = 1u << depth;
+  if (nk > n) return fail(c, who, "more removes than the table has slots");
+  if ((uint64_t)2 * nk * ((length + 15) / 16) >> 32) return fail(c, who, "the batch's 2 nk new records exceed 2^32 units of 16 bytes");
+  for (uint32_t j = 0; j < nk; j++)
+    if (mf::key_is_sentinel(h_keys + (size_t)j * key_stride, key_bytes)) return fail(c, who, "a key is the all-zero or the all-0xFF key");
+  if (!nk) return MFH_OK;
+  mf::KeyPlan keys;
+  mf::keys_prepare(h_keys, key_stride, key_bytes, nk, keys);
+  if (keys.nu != nk) return fail(c, who, "a key is given twice");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t kw = mf::key_words(key_bytes), nupd = 2 * nk;
+  const size_t hp = mf::record_head_pitch(length);
+  // updates a chunk: whole removes, all segments' rows together
+  const uint32_t pair_ch = mf::insert_chunk(nk, rowb + (cuts ? 2 * mf::cut_rows_bytes(depth, cuts->ncuts, cuts->cuts) : 0), kPathStageBytes);
+  // On the device.  Kept for the whole call: fresh = the 2 nk new records at a pitch of hp | the plan (P, hi_key, hi_rec a remove) | the keys.  Behind them, one
+  // after the other: the search (the keys' words | own[nk] | prev[nk]) and per chunk update_rows' scratch.
+  const size_t fresh_bytes = (size_t)nupd * hp, plan_bytes = (size_t)nk * 12, keys_bytes = (size_t)nk * key_bytes;
+  const size_t up_bytes = plan_bytes + keys_bytes, skip = (fresh_bytes + up_bytes + 15) & ~(size_t)15;
+  const size_t words_bytes = (size_t)nk * kw * 4, res_bytes = (size_t)2 * nk * 4;
+  if (int rc = work_reserve(c, c->circ_io, skip + std::max(words_bytes + res_bytes, update_rows_bytes(depth, pair_ch, 2 * hp, 1, cuts)))) return rc;
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_keys = d_plan + plan_bytes;
+  uint8_t *d_work = d_fresh + skip;
+  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
+  std::vector<uint32_t> own(nk), prev(nk);
+  {  // a. the search, against the table before the batch
+    uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nk * kw;
+    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
+    if (!pin_qw) return MFH_ENOMEM;
+    memcpy(pin_qw, keys.words.data(), words_bytes);
+    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
+    {
+      Timer tm(c, 35, n);  // "merkle_owners" (mfhip.hip: timing_kind)
+      const dim3 grid((n + 255) / 256), block(256);
+#define MF_OWNERS(KW) \
+  case KW: hipLaunchKernelGGL(k_key_owners<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nk, d_res, d_res + nk); break
+      switch (kw) {
+        MF_OWNERS(1); MF_OWNERS(2); MF_OWNERS(3); MF_OWNERS(4); MF_OWNERS(5); MF_OWNERS(6); MF_OWNERS(7); MF_OWNERS(8);
+      }
+#undef MF_OWNERS
+    }
+    HIP_TRY(c, hipGetLastError());
+    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
+    if (!pin_res) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bool absent = false, loose = false;
+    for (uint32_t j = 0; j < nk; j++) {  // (own | prev per UNIQUE sorted key, back to the caller's order)
+      own[j] = pin_res[keys.slot[j]];
+      prev[j] = pin_res[nk + keys.slot[j]];
+      h_index[2 * (size_t)j] = prev[j];
+      h_index[2 * (size_t)j + 1] = own[j];
+      h_status[j] = own[j] == mf::kNoRecord ? 0 : prev[j] == mf::kNoRecord ? 2 : 1;
+      absent = absent || h_status[j] == 0;
+      loose = loose || h_status[j] == 2;
+    }
+    if (absent) return fail(c, who, "a key is not a member of the set (h_status 0)");
+    if (loose) return fail(c, who, "no live record has a member as its hi (h_status 2): the table is malformed");
+  }
+  // b. the plan, and what k_remove_records reads: (P, hi_key, hi_rec) a remove | the keys, packed
+  mf::RemovePlan plan;
+  mf::remove_plan(h_keys, key_stride, key_bytes, nk, own.data(), prev.data(), plan);
+  for (uint32_t j = 0; j < nk; j++) h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];  // (P, s): the slot whose hi changes -- further left where earlier removes took the ones between
+  {
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, up_bytes);
+    if (!pin_up) return MFH_ENOMEM;
+    int32_t *w = reinterpret_cast<int32_t *>(pin_up);
+    for (uint32_t j = 0; j < nk; j++) {
+      w[3 * (size_t)j] = (int32_t)plan.idx[2 * (size_t)j];
+      w[3 * (size_t)j + 1] = plan.hi_key[j];
+      w[3 * (size_t)j + 2] = (int32_t)plan.hi_rec[j];
+      memcpy(pin_up + plan_bytes + (size_t)j * key_bytes, h_keys + (size_t)j * key_stride, key_bytes);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, up_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {  // c. the 2 nk new records
+    Timer tm(c, 36, nupd);  // "merkle_remove_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nupd * (hp / 16);
+    hipLaunchKernelGGL(k_remove_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, span, (const uint8_t *)d_keys,
+                       (const int32_t *)d_plan, key_bytes, length, nk, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  // d. the 2 nk record updates, a chunk of whole removes at a time; row b of a chunk out of the heads and the level rows of its updates 2 b and 2 b + 1
+  const Pairs chunks{pair_ch, skip, cuts != nullptr};
+  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
+  ChunkFn rows_out;
+  if (h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
+        const uint32_t j = (u.b0 + b) / 2;
+        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
+        mf::splice_remove_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, length, staged_p, staged_p + u.rs, d0,
+                              h_index[2 * (size_t)j] & low, h_index[2 * (size_t)j + 1] & low, cuts ? 128 : 64);
+      }
+    };
+  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out, cuts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_remove_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                           size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_remove_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return remove_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_roots, h_index, h_status, nullptr);
+}
+
+int mfh_merkle_remove_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
+                               size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots,
+                               uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_remove_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return remove_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_roots, h_index, h_status, &cuts);
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 //                                                 depth siblings of p | depth siblings of s | ceil(2 depth / 8) index bytes, bit l < depth = bit l of p,
 //                                                 bit depth + l = bit l of s                      insert_row_bytes(key_bytes, length, depth)
 //   words.MerkleInsert(.., joined=False)          the same behind Z = 128 (four tops)                insert_row_bytes(key_bytes, length, depth, 128)
+//   words.MerkleRemove(key_bytes, length, depth)  the insert's row without a new record of s: Z = 64 (128 with joined=False), head = the key | old record of
+//                                                 p | old record of s, the two tails as the insert's  remove_row_bytes(key_bytes, length, depth)
 //   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
 //                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
 // A path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) gives G + 1 rows an update: segment 0 is the statement's own row over the subtree of
@@ -107,6 +109,33 @@ inline void splice_insert_row(uint8_t *row, const uint8_t *key, uint32_t key_byt
     memcpy(row + 2 * (size_t)length, head_s + hp, length);
   }
   row += 3 * (size_t)length;
+  memcpy(row, staged_p + 128, (size_t)32 * depth);
+  memcpy(row + (size_t)32 * depth, staged_s + 128, (size_t)32 * depth);
+  row += (size_t)64 * depth;
+  const uint64_t bits = (uint64_t)p | (uint64_t)s << depth;  // (depth <= 24: 48 bits)
+  for (uint32_t b = 0; b < (2 * depth + 7) / 8; b++) row[b] = (uint8_t)(bits >> (8 * b));
+}
+
+// words.MerkleRemove(key_bytes, length, depth): the insert's row without a new record of s -- zeros | the key | old record of p | old record of s | depth
+// siblings of p | depth siblings of s | the index bytes of (p, s), as the insert's; zeros = 128 with joined=False
+inline size_t remove_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth, size_t zeros = 64) {
+  return zeros + key_bytes + (size_t)2 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
+}
+
+// row <- the input row of words.MerkleRemove for the remove whose updates are (record p: head_p = its old record; slot s: head_s likewise, as it stands after
+// p's update) and whose level rows are staged_p and staged_s (tails at byte 128).  Reads key_bytes, length and 32 depth bytes of its sources, writes
+// remove_row_bytes(key_bytes, length, depth, zeros) bytes and nothing behind them.  Segment 0 of a cut remove: zeros = 128, depth = c_0, p and s mod 2^c_0.
+inline void splice_remove_row(uint8_t *row, const uint8_t *key, uint32_t key_bytes, const uint8_t *head_p, const uint8_t *head_s, uint32_t length,
+                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s, size_t zeros = 64) {
+  memset(row, 0, zeros);
+  row += zeros;
+  memcpy(row, key, key_bytes);
+  row += key_bytes;
+  if (length) {
+    memcpy(row, head_p, length);
+    memcpy(row + length, head_s, length);
+  }
+  row += 2 * (size_t)length;
   memcpy(row, staged_p + 128, (size_t)32 * depth);
   memcpy(row + (size_t)32 * depth, staged_s + 128, (size_t)32 * depth);
   row += (size_t)64 * depth;

@@ -1148,6 +1148,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_inert")) return 32;  // k_inert_flags / _scan / _select of mfh_merkle_insert_keys (merkle.hip): 3 per call; rows = the table's 2^depth records
   if (!strcmp(which, "merkle_insert_records")) return 33;  // k_insert_records of mfh_merkle_insert_keys: one per call; rows = the 2 nk new records
   if (!strcmp(which, "merkle_segments")) return 34;  // k_merkle_cut_rows of the mfh_merkle_*_cut calls: one per chunk; rows = the chunk's updates x upper segments
+  if (!strcmp(which, "merkle_owners")) return 35;  // k_key_owners of mfh_merkle_remove_keys (merkle.hip): one per call; rows = the table's 2^depth records
+  if (!strcmp(which, "merkle_remove_records")) return 36;  // k_remove_records of mfh_merkle_remove_keys: one per call; rows = the 2 nk new records
   return -1;
 }
 

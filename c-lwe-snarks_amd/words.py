@@ -51,12 +51,16 @@ Whole statements built from that compression, the result 256 computed public out
                             relative to the table's invariant (the class has it); indexed_records / indexed_insert make and extend such tables.
     MerkleInsert(key_bytes, length, depth, joined=True)   "key k was inserted into the indexed table, and that alone takes the tree from R to R'"; joined=False
                             outputs all four chain tops (lu = 1024 + 8 key_bytes): segment 0 of an insert into a tree deeper than one circuit.
+    MerkleRemove(key_bytes, length, depth, joined=True)   "key k was removed from the indexed table, and that alone takes the tree from R to R'": the
+                            inverse step, three record chains and a constant inert leaf; the same public wires and joined=False form as MerkleInsert.
     MerkleSegment(levels)   "one node changed from X to X', and that alone takes its ancestor `levels` levels up from Y to Y'" (lu = 1024, the two nodes
                             given, the two tops computed): one level range of a path cut by segment_levels(depth, cuts); MerkleUpdate's sizes, 10 levels
                             fit d = 2^20.  chain(nodes) turns the published node pairs of a transition into the upper segments' statements.
 Context.ssp_rows_violations(witness) tells which rows of the registered statement a witness violates, Compiled.row_source(j) what row j constrains.
 """
 from __future__ import annotations
+
+import hashlib
 
 import numpy as np
 
@@ -464,7 +468,8 @@ class _Statement:
     layout for all of them (MerkleTree's *_rows write it on the device; csrc/merkle_rows.hpp): 32 or 64 zero bytes where the root(s) are computed
     (MerkleAbsent: and the key) | the head (leaves as words, records as bytes) | depth siblings of 32 bytes as words | ceil(depth / 8) index bytes.
     MerkleInsert's row has two paths: 64 zero bytes | the key | old_p | old_s | new_s | depth siblings of p | depth siblings of s | ceil(2 depth / 8) index
-    bytes, bit l < depth = bit l of p, bit depth + l = bit l of s: 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes."""
+    bytes, bit l < depth = bit l of p, bit depth + l = bit l of s: 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes.  MerkleRemove's row is
+    that without new_s: 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes."""
 
     def _arg(self, value, lo, hi, what):
         if not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
@@ -973,6 +978,113 @@ class MerkleInsert(_TwoRoots):
         return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
 
 
+class MerkleRemove(_TwoRoots):
+    """The statement "the key k was removed from the indexed table (MerkleAbsent has the data model), and that alone takes the tree from root R to root
+    R'": the two record updates of a removal (indexed_remove) under ONE pair of roots.  Record s is the one whose own key is k (lo_s = k): it becomes the
+    all-zero record, which is inert and is what indexed_records leaves in unused slots.  Record p is the live record whose hi is k: it gets hi <- hi_s, its
+    lo and payload kept.  The inverse of MerkleInsert's step: a chain of inserts and removes from the root of an indexed_records table keeps the invariant
+    MerkleAbsent's soundness rests on.
+
+    Public wires, in this order: R as 256 computed outputs at statement bits [0, 256), R' at [256, 512), then the 8 key_bytes given bits of k, byte j's
+    bit b (LSB first) at 512 + 8 j + b, as MerkleInsert places it; lu = 512 + 8 key_bytes.  statement(R, R', k) is MerkleUpdate.statement's 64 bytes, then k.
+    Private inputs, in this order: the old record of slot p (8 * length bits, byte j's bit b at 8 j + b), the old record of slot s; `depth` siblings of 8
+    words for p, from the leaf's level up; `depth` siblings for s, taken from the tree AFTER p's update; `depth` direction bits of p; `depth` direction
+    bits of s.  nin = 512 + 8 key_bytes + 16 length + 514 depth.
+    The body.  Neither new record is an input: new_p is old_p's wires with those of bytes [K, 2K) replaced by old_s's bytes [K, 2K), so lo and payload of p
+    cannot change, and the new leaf of s is the CONSTANT digest SHA-256(bytes(length)) as eight Words.const words.  Three record chains (_message_chain:
+    old_p, new_p, old_s; MerkleInsert has four) and four level chains (_merkle_levels: old_p and new_p over p's siblings and directions, old_s and the
+    constant leaf over s's).  R is the root of the first chain, R' that of the last; the two middle roots -- the private intermediate root, the tree after
+    p's update -- are tied by 256 assert_same.  Further assert_same: k = old_p[K, 2K) and k = old_s[0, K).  Comparators (Words.less_than): lo_p < k and
+    k < hi_s asserted to 1.
+    Soundness.  p and s are records under R (s under the root after p's update, which differs from R in slot p alone).  After the step p's range is
+    (lo_p, hi_s) with lo_p < k < hi_s and s is inert: the live ranges partition the keys again, and k is the lo of none of them.  p != s needs no
+    constraint of its own: the siblings of s open the tree AFTER p's update, in which slot p holds a record with lo = lo_p < k, so it cannot be a record
+    with lo = k.
+    What it does not cover: the removed record's payload is discarded unseen, and, like MerkleInsert, it says nothing about the records it does not open.
+    MerkleTree.remove_keys / remove_bits perform a batch of removes on a device table and give the input rows; statement j is (R_j, R_j+1, key_j).
+    Sizes (MERKLE_REMOVE_SIZES): a level costs what MerkleInsert's does, so (8, 55, 4) is the deepest one-block statement that fits Params(d=1 << 20,
+    m=699050); depth 5 does not.  Depth 1 fits Params(d=1 << 19, m=349525).
+    joined=False is segment 0 of a removal from a deeper tree (MerkleSegment), exactly as MerkleInsert's: the 256 assert_same on the middle roots are
+    dropped and all four chain tops are outputs, so p and s may lie in different height-`depth` subtrees.  Public wires then: X_p at [0, 256), X_p' at
+    [256, 512), X_s at [512, 768), X_s' at [768, 1024), the key's bits from 1024; lu = 1024 + 8 key_bytes; statement(X_p, X_p', X_s, X_s', key);
+    tops_of(row) reads the four back; the packed row is the joined one with 128 zero bytes in front in place of 64 (MERKLE_REMOVE_SPLIT_SIZES)."""
+
+    joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
+
+    def __init__(self, key_bytes: int, length: int, depth: int, joined=True):
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
+        self.depth = depth = self._depth_arg(depth)
+        self.w = w = Words()
+        self.old_p, self.old_s = (w.c.private(8 * length) for _ in range(2))
+        self.siblings_p = [w.private(8) for _ in range(depth)]
+        self.siblings_s = [w.private(8) for _ in range(depth)]
+        self.dirs_p = w.c.private(depth)
+        self.dirs_s = w.c.private(depth)
+        self.new_p = self.old_p[: 8 * K] + self.old_s[8 * K: 16 * K] + self.old_p[16 * K:]
+        chains = [_message_chain(w, rec, length) for rec in (self.old_p, self.new_p, self.old_s)]
+        self.blocks = chains[0][1]
+        self.inert_leaf = [w.const(v) for v in be_words(hashlib.sha256(bytes(length)).digest())]  # the all-zero record's leaf
+        leaves = [leaf for leaf, _ in chains] + [self.inert_leaf]
+        tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
+        self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for leaf, (sibs, dirs) in zip(leaves, tails))
+        self.joined = bool(joined)
+        self.old_root = [w.output(x) for x in self.out_old]
+        if not self.joined:  # every chain top is public: X_p, X_p', X_s, X_s'
+            self.top_mid_p = [w.output(x) for x in self.mid_p]
+            self.top_mid_s = [w.output(x) for x in self.mid_s]
+        self.new_root = [w.output(x) for x in self.out_new]
+        self.key = w.c.public(8 * K)
+        if self.joined:
+            for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
+                w.assert_same_u32(x, y)
+        for a, b in zip(self.key, self.old_p[8 * K: 16 * K]):
+            w.c.assert_same(a, b)
+        for a, b in zip(self.key, self.old_s[: 8 * K]):
+            w.c.assert_same(a, b)
+        lo_p, hi_s, k = (_key_bits_lsb_first(bits, K) for bits in (self.old_p[: 8 * K], self.old_s[8 * K: 16 * K], self.key))
+        w.c.assert_equal(w.less_than(lo_p, k), 1)
+        w.c.assert_equal(w.less_than(k, hi_s), 1)
+
+    @property
+    def lu(self) -> int:
+        return (512 if self.joined else 1024) + 8 * self.key_bytes
+
+    def _query(self, key) -> bytes:
+        key = bytes(key)
+        if len(key) != self.key_bytes:
+            raise CircuitError(f"MerkleRemove: the key is {self.key_bytes} bytes")
+        if _is_sentinel(key):
+            raise CircuitError("MerkleRemove: the all-zero and the all-0xFF key are sentinels, never members")
+        return key
+
+    def bits(self, key: bytes, old_p: bytes, old_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits,
+        the two records' bits, p's siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A
+        witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
+        who = "MerkleRemove"
+        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
+        tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
+        nsib = 256 * self.depth
+        return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, old_p, old_s, what="the records are"), tail_p[:nsib],
+                           tail_s[:nsib], tail_p[nsib:], tail_s[nsib:])
+
+    def statement(self, *tops_and_key) -> bytes:
+        """statement(old_root, new_root, key): the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "removing
+        `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 + key_bytes
+        bytes: "removing `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
+        *tops, key = tops_and_key
+        if len(tops) != (2 if self.joined else 4):
+            raise CircuitError("MerkleRemove: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
+        return b"".join(_statement_of(x, "MerkleRemove: a top") for x in tops) + self._query(key)
+
+    def tops_of(self, witness_row):
+        """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
+        if self.joined:
+            raise CircuitError("MerkleRemove: tops_of is for joined=False (roots_of reads the two roots)")
+        return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):
@@ -1042,6 +1154,28 @@ def indexed_insert(record_p, p: int, key: bytes, free_slot: int, payload: bytes 
     return [int(p), int(free_slot)], new
 
 
+def indexed_remove(record_p, p: int, record_s, s: int, key_bytes=None):
+    """(indices, new_records): the two updates that remove a key from an indexed table, in the order MerkleTree.update_records takes them, p first.
+    record_s is record s of the table, the live record whose own key (lo) is the key to remove; record_p is record p, the live record whose hi is that
+    key.  Update 0 is record p with hi <- record s's hi (lo and payload kept), update 1 the all-zero record into slot s (inert, as indexed_records
+    leaves unused slots).  key_bytes defaults to half the records' length, indexed_records' default layout; say it for records with payloads.
+    CircuitError when record_p[K:2K] != record_s[:K], when either record is not live (lo < hi), or when p == s."""
+    record_p, record_s = bytes(record_p), bytes(record_s)
+    length = len(record_p)
+    K = length // 2 if key_bytes is None else key_bytes
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= 32 or length < 2 * K or len(record_s) != length:
+        raise CircuitError("indexed_remove: two records of one length, at least 2 key_bytes bytes, key_bytes in [1, 32]")
+    if record_p[K: 2 * K] != record_s[:K]:
+        raise CircuitError("indexed_remove: record p's hi is not record s's key (record_p[K:2K] != record_s[:K])")
+    if not record_p[:K] < record_p[K: 2 * K] or not record_s[:K] < record_s[K: 2 * K]:
+        raise CircuitError("indexed_remove: a record is not live (lo < hi)")
+    if p == s or p < 0 or s < 0:
+        raise CircuitError("indexed_remove: p and s are two different slots")
+    new = np.zeros((2, length), dtype=np.uint8)
+    new[0] = np.frombuffer(record_p[:K] + record_s[K: 2 * K] + record_p[2 * K:], dtype=np.uint8)
+    return [int(p), int(s)], new
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -1074,3 +1208,10 @@ MERKLE_INSERT_SPLIT_SIZES = {(4, 8, 1): (224776, 399885), (8, 55, 1): (226156, 4
 # ... and of MerkleSegment by levels: MerkleUpdate's, 56 993 levels + 1 026 wires and 101 473 levels + 1 540 rows (the two nodes are public inputs where
 # MerkleUpdate's leaves are private ones); 10 levels fit Params(d=1 << 20, m=699050), 11 (1 117 743 rows) do not
 MERKLE_SEGMENT_SIZES = {1: (58019, 103013), 2: (115012, 204486), 10: (570956, 1016270)}
+# ... and of MerkleRemove by (key_bytes, length, depth): MerkleInsert's less one record chain (the new leaf of s is a constant), 8 length input wires and their
+# bit rows (no new record of s) and one comparison (no inert check), with 16 key_bytes equalities on k as the insert has on k and the inherited hi.  A level
+# costs 113 986 wires and 202 946 rows, MerkleInsert's.  (4, 8, 1) fits Params(d=1 << 19, m=349525) and not d = 2^18; (8, 55, 4) is the deepest one-block
+# statement that fits Params(d=1 << 20, m=699050): (8, 55, 5) would be 1 163 280 rows
+MERKLE_REMOVE_SIZES = {(4, 8, 1): (196799, 350371), (4, 8, 2): (310785, 553317), (8, 55, 1): (197732, 351496), (8, 55, 4): (539690, 960334)}
+# ... and of MerkleRemove(joined=False): the joined sizes plus 512 wires and 768 rows, as MERKLE_INSERT_SPLIT_SIZES
+MERKLE_REMOVE_SPLIT_SIZES = {(4, 8, 1): (197311, 351139), (8, 55, 1): (198244, 352264), (8, 55, 4): (540202, 961102)}

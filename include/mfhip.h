@@ -509,6 +509,40 @@ int mfh_merkle_update_records_cut(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, co
 int mfh_merkle_insert_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
                                const uint8_t *h_keys, size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint32_t ncuts, const uint32_t *h_cuts,
                                uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+/* nk sequential key REMOVES from an indexed table (the data model: mfh_merkle_absent_rows) and its tree in ONE call, and the packed input row of
+ * words.MerkleRemove(key_bytes, length, depth) of every remove -- "key j was removed, and that alone takes the tree from R_j to R_j+1".  The inverse of
+ * mfh_merkle_insert_keys: with all-zero inert slots, inserting a batch and removing the same keys restores the table's bytes and the root.
+ *   semantics  byte for byte what this gives, run once per key in order: find s, the lowest live record whose own key (lo) is the key, and P, the lowest live
+ *              record whose hi is the key, in the table as it then stands; the two updates of a remove -- record P with hi <- the hi of record s, then the
+ *              all-zero record into slot s -- through mfh_merkle_update_records.  That covers the table in place, every node of the tree, the roots and row
+ *              j, which describes table and tree as they stood before remove j.  Adjacent members may both be in the batch: resolved in order.
+ *   arguments  key j is the key_bytes bytes at h_keys + j * key_stride.  h_inputs = NULL: remove, no rows.  h_roots (may be NULL) receives the nk + 1 roots
+ *              R_0 .. R_nk.  h_index receives nk pairs (P, s): the slot whose hi changed and the slot that was zeroed.  h_status receives the status of each
+ *              key against the table BEFORE the batch: 1 = a member, both records found; 0 = no live record has this key as its own, it is not a member; 2 =
+ *              a member, but no live record has it as hi: the table is malformed.
+ *   rows       row j (at h_inputs + j * in_stride): 64 zero bytes where the roots are computed | the key | the old record of P | the old record of s | the 32
+ *              depth sibling bytes of P | those of s, from the tree after P's update | ceil(2 depth / 8) index bytes, bit l < depth = bit l of P, bit depth +
+ *              l = bit l of s.  Exactly 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes are written.
+ *   how        ONE launch of k_key_owners (one thread per record, at most two atomic minima each: the lowest index wins on a malformed table) finds own and
+ *              prev of every key, and 2 nk words come back; the host plans the slots and the inherited hi within the batch (merkle_remove.hpp); ONE launch
+ *              of k_remove_records builds the 2 nk new records; they go through mfh_merkle_update_records' machinery in chunks of whole removes (the most
+ *              whose rows fit 64 MiB, at least one).  The call synchronises the stream behind the search and every chunk.
+ * mfh_merkle_remove_keys_cut is the same with the path cut (above): segment 0's row, ONE PER REMOVE, is that of MerkleRemove(key_bytes, length, c_0,
+ * joined=False) -- 128 zero bytes | key | old P | old s | c_0 siblings of P | c_0 of s | ceil(2 c_0 / 8) index bytes of P mod 2^c_0 and s mod 2^c_0 -- the upper
+ * segments have one MerkleSegment row per UPDATE (2 nk), and h_roots receives ALL 2 nk + 1 roots; it has no "no rows" mode.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: a null tree; a tree of another device; key_bytes 0 or above 32; length
+ * < 2 key_bytes or > 2^20; table_stride < length; key_stride < key_bytes; nk > 0 with d_table, h_keys, h_index or h_status null; nk > 2^depth; in_stride
+ * below the row's bytes when h_inputs is given; a sentinel key; a key given twice; for the cut call, what the cut calls above refuse.
+ * MFH_EINVAL after the search, with h_status and h_index (the located P and s of the table before the batch, 0xFFFFFFFF = none) filled, table and tree
+ * unwritten and no record or tree kernel launched: any key of status 0 or 2.  The call is all or nothing.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_owners" (1 per call, rows = 2^depth), "merkle_remove_records" (1 per call, rows = 2 nk), then per chunk of 2 k updates
+ * "sha256_records" (1), "merkle_record_rows" (2; 1 without rows) and "merkle_updates" (depth + 1), the cut call also "merkle_segments" (1). */
+int mfh_merkle_remove_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
+                           const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
+                           uint8_t *h_status);
+int mfh_merkle_remove_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
+                               const uint8_t *h_keys, size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                               const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
