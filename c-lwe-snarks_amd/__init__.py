@@ -522,12 +522,71 @@ class MerkleTree:
         words.MerkleRecordUpdate(length, depth)"""
         return self._update_bits(self.update_records(table, indices, new_records, roots), 2 * int(table.shape[1]), roots)
 
-    def _absent(self, table, keys, who, want_rows):
-        c = self._ctx
+    # ---- the key calls on an indexed table: what their arguments share
+    def _keys(self, table, keys, who, count="nk"):
+        """(the table's tensor, its stride, its length, the keys as a contiguous np.uint8 [n, key_bytes]) of a key call"""
         tab, tstride, length = self._table(table, who)
         k = np.ascontiguousarray(keys)
         if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
-            raise MfhError(f"{who}: keys are uint8 [nq, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+            raise MfhError(f"{who}: keys are uint8 [{count}, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        return tab, tstride, length, k
+
+    @staticmethod
+    def _payloads(payloads, nk, plen, who):
+        """None, or the payloads as a contiguous np.uint8 [nk, plen]"""
+        if payloads is None:
+            return None
+        pay = np.ascontiguousarray(payloads)
+        if pay.dtype != np.uint8 or pay.shape != (nk, plen):
+            raise MfhError(f"{who}: payloads are uint8 [nk, length - 2 key_bytes]")
+        return pay
+
+    @staticmethod
+    def _step_head(table, keys, nrec, zeros):
+        """the bytes in front of the two tails in the row of a key step with nrec records: the zeros where the tops are computed, the key, the records"""
+        return zeros + np.ascontiguousarray(keys).shape[1] + nrec * int(table.shape[1])
+
+    def _key_steps(self, who, step, table, keys, payloads=None, roots=False, cut=False, cuts=None):
+        """the body of insert_keys, remove_keys and, with cut=True, their *_segments forms (whatever `cuts` is then, _cut judges it): mfh_merkle_<step>_keys[_cut] with the rows of a statement of three
+        (insert) or two (remove) records, index, status and roots allocated here.  Uncut: (rows, index) and with roots=True the nk + 1 roots; cut: (rows,
+        nodes_p, nodes_s, index), from the 2 nk + 1 roots"""
+        c = self._ctx
+        tab, tstride, length, k = self._keys(table, keys, who)
+        nk, kb = k.shape
+        vp = ctypes.c_void_p
+        nrec, extra = 2, ()
+        if step == "insert":
+            pay = self._payloads(payloads, nk, length - 2 * kb, who)
+            nrec, extra = 3, (vp(pay.ctypes.data) if pay is not None else None, length - 2 * kb)
+        head = self._step_head(table, keys, nrec, 128 if cut else 64)
+        if not cut:
+            rows = np.zeros((nk, head + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
+            out = (vp(rows.ctypes.data), rows.shape[1])
+            r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots else None
+        else:
+            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 64 * c0 + (2 * c0 + 7) // 8, 2 * nk)
+            r = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
+        index = np.zeros((nk, 2), dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        call = getattr(c.lib, f"mfh_merkle_{step}_keys" + ("_cut" if cut else ""))
+        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, *extra, *out, vp(r.ctypes.data) if r is not None else None,
+                    vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif r is not None:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        if not cut:
+            return (rows, index, r) if roots else (rows, index)
+        nodes = self._cut_nodes(rows, r)
+        return rows, nodes[0::2], nodes[1::2], index
+
+    def _key_step_bits(self, out, head):
+        """the uncut rows of a key step as 0 / 1"""
+        return (np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth],) + tuple(out[1:])
+
+    def _absent(self, table, keys, who, want_rows):
+        c = self._ctx
+        tab, tstride, length, k = self._keys(table, keys, who, "nq")
         nq, kb = k.shape
         index = np.zeros(nq, dtype=np.uint32)
         status = np.zeros(nq, dtype=np.uint8)
@@ -570,38 +629,12 @@ class MerkleTree:
         table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, all different.  payloads: None (all
         zero) or np.uint8 [nk, length - 2 key_bytes].  MfhError with the library's text, table and tree untouched, when a key is a member already, no record
         holds a key, or the table has fewer than nk inert slots."""
-        c = self._ctx
-        tab, tstride, length = self._table(table, "insert_keys")
-        k = np.ascontiguousarray(keys)
-        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
-            raise MfhError("insert_keys: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
-        nk, kb = k.shape
-        pay = None
-        if payloads is not None:
-            pay = np.ascontiguousarray(payloads)
-            if pay.dtype != np.uint8 or pay.shape != (nk, length - 2 * kb):
-                raise MfhError("insert_keys: payloads are uint8 [nk, length - 2 key_bytes]")
-        rows = np.zeros((nk, 64 + kb + 3 * length + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
-        index = np.zeros((nk, 2), dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots else None
-        vp = ctypes.c_void_p
-        c._chk(c.lib.mfh_merkle_insert_keys(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(pay.ctypes.data) if pay is not None else None,
-                                            length - 2 * kb, vp(rows.ctypes.data), rows.shape[1], vp(r.ctypes.data) if roots else None, vp(index.ctypes.data),
-                                            vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        elif roots:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        return (rows, index, r) if roots else (rows, index)
+        return self._key_steps("insert_keys", "insert", table, keys, payloads, roots)
 
     def insert_bits(self, table, keys, payloads=None, roots=False):
         """insert_keys with the rows as np.uint8 [nk, 512 + 8 key_bytes + 24 length + 514 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
         words.MerkleInsert(key_bytes, length, depth)"""
-        out = self.insert_keys(table, keys, payloads, roots)
-        head = 64 + np.ascontiguousarray(keys).shape[1] + 3 * int(table.shape[1])
-        bits = np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth]
-        return (bits,) + tuple(out[1:])
+        return self._key_step_bits(self.insert_keys(table, keys, payloads, roots), self._step_head(table, keys, 3, 64))
 
     # ---- the path cut into level ranges (words.MerkleSegment): one row array a segment, and the published node pairs
     def _cut(self, cuts, who, n0, row0, nupper):
@@ -691,45 +724,15 @@ class MerkleTree:
         of p's update of insert j and row 2 j + 1 that of s's; nodes_p and nodes_s are np.uint8 [nk, G + 1, 2, 32], the published pairs of the two updates:
         segment 0's statement is statement(*nodes_p[j, 0], *nodes_s[j, 0], keys[j]), the upper ones MerkleSegment.chain(nodes_p[j]) and chain(nodes_s[j]), and
         nodes_p[j, G, 1] == nodes_s[j, G, 0] is the root between the two updates, which becomes public.  index as insert_keys gives it."""
-        c = self._ctx
-        tab, tstride, length = self._table(table, "insert_key_segments")
-        k = np.ascontiguousarray(keys)
-        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
-            raise MfhError("insert_key_segments: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
-        nk, kb = k.shape
-        pay = None
-        if payloads is not None:
-            pay = np.ascontiguousarray(payloads)
-            if pay.dtype != np.uint8 or pay.shape != (nk, length - 2 * kb):
-                raise MfhError("insert_key_segments: payloads are uint8 [nk, length - 2 key_bytes]")
-        rows, cargs, keep = self._cut(cuts, "insert_key_segments", nk, lambda c0: 128 + kb + 3 * length + 64 * c0 + (2 * c0 + 7) // 8, 2 * nk)
-        index = np.zeros((nk, 2), dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        r = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
-        vp = ctypes.c_void_p
-        c._chk(c.lib.mfh_merkle_insert_keys_cut(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(pay.ctypes.data) if pay is not None else None,
-                                                length - 2 * kb, *cargs, vp(r.ctypes.data), vp(index.ctypes.data), vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        else:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        nodes = self._cut_nodes(rows, r)
-        return rows, nodes[0::2], nodes[1::2], index
+        return self._key_steps("insert_key_segments", "insert", table, keys, payloads, cut=True, cuts=cuts)
 
     def insert_key_segment_bits(self, table, keys, cuts, payloads=None):
         """insert_key_segments with every segment's rows as 0 / 1 arrays"""
         out = self.insert_key_segments(table, keys, cuts, payloads)
-        kb, length = np.ascontiguousarray(keys).shape[1], int(table.shape[1])
-        return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 8 * kb + 24 * length + 514 * c0),) + tuple(out[1:])
+        head = self._step_head(table, keys, 3, 128)
+        return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
 
     # ---- removes: the inverse of insert_keys
-    def _remove_keys(self, table, keys, who):
-        tab, tstride, length = self._table(table, who)
-        k = np.ascontiguousarray(keys)
-        if k.dtype != np.uint8 or k.ndim != 2 or not 1 <= k.shape[1] <= 32 or length < 2 * k.shape[1]:
-            raise MfhError(f"{who}: keys are uint8 [nk, key_bytes], 1 <= key_bytes <= 32 and 2 key_bytes <= length")
-        return tab, tstride, length, k
-
     def remove_keys(self, table, keys, roots=False):
         """(rows, index): nk sequential key removes from an INDEXED table (words.MerkleAbsent has the data model) and this tree in one call
         (mfh_merkle_remove_keys; waits for the stream).  Remove j zeroes the live record whose own key is keys[j] (it becomes inert, as indexed_records leaves
@@ -740,29 +743,12 @@ class MerkleTree:
         table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, all different.  MfhError with the
         library's text, table and tree untouched, when a key is not a member or no live record has a member as its hi.  With all-zero inert slots,
         insert_keys of a batch followed by remove_keys of the same keys restores the table's bytes and the root."""
-        c = self._ctx
-        tab, tstride, length, k = self._remove_keys(table, keys, "remove_keys")
-        nk, kb = k.shape
-        rows = np.zeros((nk, 64 + kb + 2 * length + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
-        index = np.zeros((nk, 2), dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots else None
-        vp = ctypes.c_void_p
-        c._chk(c.lib.mfh_merkle_remove_keys(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, vp(rows.ctypes.data), rows.shape[1],
-                                            vp(r.ctypes.data) if roots else None, vp(index.ctypes.data), vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        elif roots:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        return (rows, index, r) if roots else (rows, index)
+        return self._key_steps("remove_keys", "remove", table, keys, roots=roots)
 
     def remove_bits(self, table, keys, roots=False):
         """remove_keys with the rows as np.uint8 [nk, 512 + 8 key_bytes + 16 length + 514 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
         words.MerkleRemove(key_bytes, length, depth)"""
-        out = self.remove_keys(table, keys, roots)
-        head = 64 + np.ascontiguousarray(keys).shape[1] + 2 * int(table.shape[1])
-        bits = np.unpackbits(out[0], axis=1, bitorder="little")[:, : 8 * head + 514 * self.depth]
-        return (bits,) + tuple(out[1:])
+        return self._key_step_bits(self.remove_keys(table, keys, roots), self._step_head(table, keys, 2, 64))
 
     def remove_key_segments(self, table, keys, cuts):
         """remove_keys with the path cut at levels `cuts` (mfh_merkle_remove_keys_cut).  Returns (rows, nodes_p, nodes_s, index): rows[0][j] is the packed input
@@ -770,28 +756,13 @@ class MerkleTree:
         of p's update of remove j and row 2 j + 1 that of s's; nodes_p and nodes_s are np.uint8 [nk, G + 1, 2, 32], the published pairs of the two updates:
         segment 0's statement is statement(*nodes_p[j, 0], *nodes_s[j, 0], keys[j]), the upper ones MerkleSegment.chain(nodes_p[j]) and chain(nodes_s[j]), and
         nodes_p[j, G, 1] == nodes_s[j, G, 0] is the root between the two updates, which becomes public.  index as remove_keys gives it."""
-        c = self._ctx
-        tab, tstride, length, k = self._remove_keys(table, keys, "remove_key_segments")
-        nk, kb = k.shape
-        rows, cargs, keep = self._cut(cuts, "remove_key_segments", nk, lambda c0: 128 + kb + 2 * length + 64 * c0 + (2 * c0 + 7) // 8, 2 * nk)
-        index = np.zeros((nk, 2), dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        r = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
-        vp = ctypes.c_void_p
-        c._chk(c.lib.mfh_merkle_remove_keys_cut(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, *cargs, vp(r.ctypes.data),
-                                                vp(index.ctypes.data), vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        else:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        nodes = self._cut_nodes(rows, r)
-        return rows, nodes[0::2], nodes[1::2], index
+        return self._key_steps("remove_key_segments", "remove", table, keys, cut=True, cuts=cuts)
 
     def remove_key_segment_bits(self, table, keys, cuts):
         """remove_key_segments with every segment's rows as 0 / 1 arrays"""
         out = self.remove_key_segments(table, keys, cuts)
-        kb, length = np.ascontiguousarray(keys).shape[1], int(table.shape[1])
-        return (self._cut_unpack(out[0], cuts, lambda c0: 1024 + 8 * kb + 16 * length + 514 * c0),) + tuple(out[1:])
+        head = self._step_head(table, keys, 2, 128)
+        return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
 
 
 class Context:

@@ -24,13 +24,20 @@
 // the last new record of each leaf into the table behind them.
 // k_key_locate, k_absent_gather: mfh_merkle_absent_rows, which finds for every query key the record of an indexed table whose range (lo, hi) holds it, or
 // whose key it is, in one pass over the table, and writes the words.MerkleAbsent input rows (the queries' host side: merkle_keys.hpp).
-// k_inert_flags, k_inert_scan, k_inert_select, k_insert_records: mfh_merkle_insert_keys, a batch of sequential key inserts into an indexed table in one call --
-// the lowest inert slots found on the device, all new records built in one launch, then the record updates above (the host's plan: merkle_insert.hpp).
-// k_key_owners, k_remove_records: mfh_merkle_remove_keys, a batch of sequential key removes from an indexed table in one call -- every key's own record and
-// predecessor found in one pass, all new records built in one launch, then the record updates above (the host's plan: merkle_remove.hpp).
+// k_inert_flags, k_inert_scan, k_inert_select: mfh_merkle_insert_keys, a batch of sequential key inserts into an indexed table in one call -- the keys located
+// as above, the lowest inert slots found on the device, then the steps below (the host's plan: merkle_insert.hpp).
+// k_key_owners: mfh_merkle_remove_keys, a batch of sequential key removes from an indexed table in one call -- every key's own record and predecessor found in
+// one pass, then the steps below (the host's plan: merkle_remove.hpp).
+// k_insert_records, k_remove_records: what a batch of key steps (inserts, removes) ends with -- all 2 nk new records built in one launch from the step's plan,
+// then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
+// (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
 #include <functional>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "ctx.hpp"
 #include "merkle_insert.hpp"
@@ -356,6 +363,28 @@ __device__ __forceinline__ void load_key_words(const uint8_t *__restrict__ table
   if (key_bytes & 3) w[KW - 1] &= ~0u << (8 * (4 - (key_bytes & 3)));
 }
 
+// lo and hi of record i as words; true when the record is live (lo < hi)
+template <int KW>
+__device__ __forceinline__ bool load_record_keys(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t i, uint32_t *lo, uint32_t *hi) {
+  const int64_t at = (int64_t)((size_t)i * stride);
+  load_key_words<KW>(table, at, key_bytes, span, lo);
+  load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
+  return key_less<KW>(lo, hi);
+}
+
+// the first of the sorted queries [l, r) that is not below `key` (r when all are)
+template <int KW>
+__device__ __forceinline__ uint32_t first_query_not_below(const uint32_t *__restrict__ qw, uint32_t l, uint32_t r, const uint32_t *key) {
+  uint32_t q[KW];
+  while (l < r) {
+    const uint32_t m = l + (r - l) / 2;
+#pragma unroll
+    for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
+    if (key_less<KW>(q, key)) l = m + 1; else r = m;
+  }
+  return l;
+}
+
 template <int KW>
 __global__ __launch_bounds__(256) void k_key_locate(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t n,
                                                     const uint32_t *__restrict__ qw, uint32_t nu, uint32_t *__restrict__ range, uint32_t *__restrict__ present) {
@@ -363,10 +392,7 @@ __global__ __launch_bounds__(256) void k_key_locate(const uint8_t *__restrict__ 
   uint32_t a = 0, b = 0;
   if (i < n) {
     uint32_t lo[KW], hi[KW], q[KW];
-    const int64_t at = (int64_t)((size_t)i * stride);
-    load_key_words<KW>(table, at, key_bytes, span, lo);
-    load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
-    if (key_less<KW>(lo, hi)) {
+    if (load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi)) {
       uint32_t l = 0, r = nu;  // a: the first query > lo
       while (l < r) {
         const uint32_t m = l + (r - l) / 2;
@@ -383,16 +409,7 @@ __global__ __launch_bounds__(256) void k_key_locate(const uint8_t *__restrict__ 
       if (a < nu) {
 #pragma unroll
         for (int j = 0; j < KW; j++) q[j] = qw[(size_t)a * KW + j];
-        if (key_less<KW>(q, hi)) {  // b: the first query >= hi, above a
-          l = a + 1, r = nu;
-          while (l < r) {
-            const uint32_t m = l + (r - l) / 2;
-#pragma unroll
-            for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
-            if (key_less<KW>(q, hi)) l = m + 1; else r = m;
-          }
-          b = l;
-        }
+        if (key_less<KW>(q, hi)) b = first_query_not_below<KW>(qw, a + 1, nu, hi);  // b: the first query >= hi, above a
       }
       if (b == a + 1) atomicMin(range + a, i);
     }
@@ -438,10 +455,7 @@ __global__ __launch_bounds__(256) void k_inert_flags(const uint8_t *__restrict__
   bool inert = false;
   if (i < n) {
     uint32_t lo[KW], hi[KW];
-    const int64_t at = (int64_t)((size_t)i * stride);
-    load_key_words<KW>(table, at, key_bytes, span, lo);
-    load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
-    inert = !key_less<KW>(lo, hi);
+    inert = !load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi);
   }
   const unsigned long long flags = __ballot(inert);
   if (lane == 0) {
@@ -558,18 +572,6 @@ __global__ __launch_bounds__(256) void k_insert_records(const uint8_t *__restric
 // index, whatever order the threads run in.  A thread makes at most two single atomics: no range to fill, no wave cooperation, every thread may leave early.
 // The queries are searched through the vector L1 and L2, not staged in LDS, for k_key_locate's reasons.
 template <int KW>
-__device__ __forceinline__ uint32_t first_query_not_below(const uint32_t *__restrict__ qw, uint32_t l, uint32_t r, const uint32_t *key) {
-  uint32_t q[KW];
-  while (l < r) {
-    const uint32_t m = l + (r - l) / 2;
-#pragma unroll
-    for (int j = 0; j < KW; j++) q[j] = qw[(size_t)m * KW + j];
-    if (key_less<KW>(q, key)) l = m + 1; else r = m;
-  }
-  return l;
-}
-
-template <int KW>
 __device__ __forceinline__ bool query_equals(const uint32_t *__restrict__ qw, uint32_t u, const uint32_t *key) {
   bool same = true;
 #pragma unroll
@@ -583,10 +585,7 @@ __global__ __launch_bounds__(256) void k_key_owners(const uint8_t *__restrict__ 
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   uint32_t lo[KW], hi[KW];
-  const int64_t at = (int64_t)((size_t)i * stride);
-  load_key_words<KW>(table, at, key_bytes, span, lo);
-  load_key_words<KW>(table, at + key_bytes, key_bytes, span, hi);
-  if (!key_less<KW>(lo, hi)) return;
+  if (!load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi)) return;
   uint32_t u = first_query_not_below<KW>(qw, 0, nu, lo);
   if (u < nu && query_equals<KW>(qw, u, lo)) {
     atomicMin(own + u, i);
@@ -755,7 +754,7 @@ int path_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_ind
 // k_merkle_update_level and the tree's write-back, `after` (if any) queues what has to follow that, the level rows, the heads and the roots come back, and
 // `rows_out` takes them from the pinned buffer with the stream idle.  On the device: V[0] (own leaves only) | V[1 .. depth], slots of ch nodes | level rows |
 // heads | the schedule (idx | last | same0 | sib[depth]).  Pinned: level rows | heads | R_b0, the chunk's new roots
-// A batch of inserts (mfh_merkle_insert_keys) drives the same body with `pairs`: chunks of whole inserts (mf::insert_chunk: an even number of updates), the first
+// A batch of key steps (pair_updates) drives the same body with `pairs`: chunks of whole steps (mf::pair_chunk: an even number of updates), the first
 // `skip` bytes of the scratch (a multiple of 16, reserved by the caller with update_rows_bytes behind them) left to the caller, h_roots given every second root,
 // and rows_out = null for "no rows": then nothing but the roots comes back.
 // A cut call (mfh_merkle_*_cut) drives the same body with `cuts`: the schedule carries same_cut behind sib, k_merkle_cut_rows runs between the last level and the
@@ -859,7 +858,7 @@ int update_rows(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_inde
 }
 
 // nupd sequential record updates, records h_index[k] of the table <- the records at d_fresh + k * new_stride (device memory, whoever wrote it: the caller's new
-// records, or what k_insert_records built), through update_rows: per chunk the new leaves = the digests of the chunk's new records, a head = the old record | the
+// records, or what k_insert_records / k_remove_records built), through update_rows: per chunk the new leaves = the digests of the chunk's new records, a head = the old record | the
 // new record at a pitch of record_head_pitch(length) each, and the table's write-back behind the levels.  rows_out = null: no gather, nothing staged out.
 int record_updates(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_index, uint8_t *d_table, size_t table_stride, uint32_t length, const uint8_t *d_fresh,
                    size_t new_stride, uint8_t *h_roots, size_t rowb, const Pairs *pairs, const ChunkFn &rows_out, const Cuts *cuts = nullptr) {
@@ -1102,70 +1101,210 @@ int mfh_merkle_update_records(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const ui
   return update_records(c, t, who, nupd, h_index, d_table, table_stride, length, d_new_records, new_stride, h_inputs, in_stride, h_roots, nullptr);
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- the key calls: mfh_merkle_absent_rows and the two batches of key steps, mfh_merkle_insert_keys and mfh_merkle_remove_keys, with their _cut forms.
+
+// the arguments the key calls share (include/mfhip.h says what each is).  The table is only read through this: a batch's write-back is handed its own pointer.
+// Absent queries have no roots and no cuts
+struct KeyCall {
+  const char *who;
+  const uint8_t *d_table;
+  size_t table_stride;
+  uint32_t length, key_bytes, nk;
+  const uint8_t *h_keys;
+  size_t key_stride;
+  uint8_t *h_inputs;
+  size_t in_stride;
+  uint32_t *h_index;
+  uint8_t *h_status;
+  uint8_t *h_roots;
+  const Cuts *cuts;
+  const uint8_t *key(uint32_t j) const { return h_keys + (size_t)j * key_stride; }
+  int64_t span(uint32_t depth) const { return (int64_t)((((size_t)1 << depth) - 1) * table_stride + length); }  // the table's bytes
+};
+
+// what the three key calls ask of their arguments, in the order each call has always checked them; empty when they are fine.  `noun`: the call's "queries",
+// "inserts" or "removes".  `own`: the caller's checks of what only it has (the strides of payloads and rows, the cuts), whose place is between the keys' shape
+// and the pointers.  `steps`: a batch of key steps, which builds 2 nk records and needs as many slots as keys
+std::string keys_refused(const KeyCall &k, uint32_t depth, const char *noun, bool steps, const std::function<const char *()> &own) {
+  if (k.key_bytes < 1 || k.key_bytes > mf::kMaxKeyBytes) return "key_bytes must be in [1, 32]";
+  if (k.length < 2 * k.key_bytes) return "length shorter than the two keys' 2 key_bytes bytes";  // (at most 64: never also above 2^20)
+  if (const char *what = records_refused(nullptr, k.table_stride, k.length, 0, "table_stride shorter than length")) return what;
+  if (k.key_stride < k.key_bytes) return "key_stride shorter than key_bytes";
+  if (const char *what = own()) return what;
+  const std::pair<const void *, const char *> needed[] = {{k.d_table, "d_table"}, {k.h_keys, "h_keys"}, {k.h_index, "h_index"}, {k.h_status, "h_status"}};
+  for (const auto &p : needed)
+    if (k.nk && !p.first) return std::string(noun) + " without " + p.second;
+  if (steps && k.nk > 1u << depth) return std::string("more ") + noun + " than the table has slots";
+  if (steps && (uint64_t)2 * k.nk * ((k.length + 15) / 16) >> 32) return "the batch's 2 nk new records exceed 2^32 units of 16 bytes";
+  for (uint32_t j = 0; j < k.nk; j++)
+    if (mf::key_is_sentinel(k.key(j), k.key_bytes)) return std::string(steps ? "a key" : "a query") + " is the all-zero or the all-0xFF key";
+  return {};
+}
+
+// f(std::integral_constant<int, KW>) for the runtime kw = 1 .. 8 (key_words of 1 .. 32 key bytes): the kernels that compare keys take KW at compile time
+template <class F>
+void with_key_words(uint32_t kw, F &&f) {
+  switch (kw) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// The search of a call's sorted unique keys against the table as it stands, ONE launch, one thread per record: k_key_locate (range | present) or k_key_owners
+// (own | prev).  The value is the launch's timing kind, "merkle_locate" and "merkle_owners" (mfhip.hip: timing_kind)
+enum KeySearch { kLocate = 30, kOwners = 35 };
+using KeyKernel = void (*)(const uint8_t *, size_t, int64_t, uint32_t, uint32_t, const uint32_t *, uint32_t, uint32_t *, uint32_t *);
+
+size_t key_search_bytes(uint32_t nu, uint32_t key_bytes) { return (size_t)nu * (mf::key_words(key_bytes) + 2) * 4; }
+
+// At d_work (key_search_bytes, reserved by the caller): the keys' words | 2 nu result words, all 0xFF before the launch.  *res <- the results in pin_cw with the
+// stream idle: good until pin_cw is next acquired
+int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch which, uint32_t depth, uint8_t *d_work, const uint32_t **res) {
+  const uint32_t nu = keys.nu, kw = mf::key_words(k.key_bytes), n = 1u << depth;
+  const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
+  uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nu * kw;
+  uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
+  if (!pin_qw) return MFH_ENOMEM;
+  memcpy(pin_qw, keys.words.data(), words_bytes);
+  HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
+  pin_release(c, c->pin_rows);
+  HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
+  KeyKernel kernel = nullptr;
+  with_key_words(kw, [&](auto KW) { kernel = which == kOwners ? k_key_owners<decltype(KW)::value> : k_key_locate<decltype(KW)::value>; });
+  {
+    Timer tm(c, which, n);
+    hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.key_bytes, n, (const uint32_t *)d_qw, nu, d_res,
+                       d_res + nu);
+  }
+  HIP_TRY(c, hipGetLastError());
+  uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
+  if (!pin_res) return MFH_ENOMEM;
+  HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *res = pin_res;
+  return MFH_OK;
+}
+
+// What a batch of nk key steps keeps at the front of the scratch for the whole call: fresh = the 2 nk new records at a pitch of record_head_pitch(length) | the
+// plan, three words a step (its build kernel says which) | the keys, packed | the payloads, packed.  skip = their bytes rounded up to 16: behind them, one after the
+// other, the call's searches and per chunk update_rows' scratch.  ch: the updates a chunk -- whole steps, all segments' rows together
+struct PairScratch {
+  size_t fresh_bytes, plan_bytes, keys_bytes, pay_bytes, skip, rowb;
+  uint32_t ch;
+  size_t up_bytes() const { return plan_bytes + keys_bytes + pay_bytes; }
+};
+
+// lays that scratch out for rows of rowb bytes and payloads of plen bytes (0: none go up) and reserves it, with the larger of search_bytes -- the most any of
+// the caller's searches needs -- and update_rows' scratch behind the front
+int pair_reserve(mfh_ctx *c, const KeyCall &k, uint32_t depth, size_t rowb, size_t plen, size_t search_bytes, PairScratch &s) {
+  s.fresh_bytes = (size_t)2 * k.nk * mf::record_head_pitch(k.length);
+  s.plan_bytes = (size_t)k.nk * 3 * 4;
+  s.keys_bytes = (size_t)k.nk * k.key_bytes;
+  s.pay_bytes = (size_t)k.nk * plen;
+  s.skip = (s.fresh_bytes + s.up_bytes() + 15) & ~(size_t)15;
+  s.rowb = rowb;
+  s.ch = mf::pair_chunk(k.nk, rowb + (k.cuts ? 2 * mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
+  return work_reserve(c, c->circ_io, s.skip + std::max(search_bytes, update_rows_bytes(depth, s.ch, 2 * mf::record_head_pitch(k.length), 1, k.cuts)));
+}
+
+// the caller's splice of step j's row out of the pinned buffer: the heads (old | new record at a pitch of record_head_pitch) and the level rows of its updates p, s
+using PairSplice = std::function<void(uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s)>;
+
+// the caller's build kernel, launched on the context's stream over `grid` workgroups of 256: the 2 nk new records into d_fresh from the plan, the packed keys
+// and payloads (d_pay = null: none went up) and the table before the batch
+using PairBuild = std::function<void(dim3 grid, const int32_t *d_plan, const uint8_t *d_keys, const uint8_t *d_pay, uint4 *d_fresh)>;
+
+// What follows the plan in a batch of key steps.  The plan (three words a step), the keys and the payloads go up packed; the caller's build kernel, ONE launch
+// under the caller's timing kind, builds the 2 nk new records from the table before the batch; then the 2 nk record updates idx, a chunk of whole steps at a
+// time, row b of a chunk spliced out of the heads and the level rows of its updates 2 b and 2 b + 1
+int pair_updates(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const PairScratch &s, int build_kind, const PairBuild &build,
+                 const std::vector<int32_t> &plan, const std::vector<uint32_t> &idx, const uint8_t *h_payloads, size_t payload_stride, const PairSplice &splice) {
+  const uint32_t nk = k.nk, nupd = 2 * nk;
+  const size_t hp = mf::record_head_pitch(k.length), plen = s.pay_bytes / nk;
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + s.fresh_bytes, *d_keys = d_plan + s.plan_bytes, *d_pay = s.pay_bytes ? d_keys + s.keys_bytes : nullptr;
+  {
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, s.up_bytes());
+    if (!pin_up) return MFH_ENOMEM;
+    memcpy(pin_up, plan.data(), s.plan_bytes);
+    for (uint32_t j = 0; j < nk; j++) {
+      memcpy(pin_up + s.plan_bytes + (size_t)j * k.key_bytes, k.key(j), k.key_bytes);
+      if (plen) memcpy(pin_up + s.plan_bytes + s.keys_bytes + (size_t)j * plen, h_payloads + (size_t)j * payload_stride, plen);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, s.up_bytes(), hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {
+    Timer tm(c, build_kind, nupd);  // "merkle_insert_records" or "merkle_remove_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nupd * (hp / 16);
+    build(dim3((uint32_t)((items + 255) / 256)), (const int32_t *)d_plan, d_keys, d_pay, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  const Pairs chunks{s.ch, s.skip, k.cuts != nullptr};
+  ChunkFn rows_out;
+  if (k.h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
+        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
+        splice((u.b0 + b) / 2, head_p, head_p + u.hs, staged_p, staged_p + u.rs);
+      }
+    };
+  return record_updates(c, t, nupd, idx.data(), d_table, k.table_stride, k.length, d_fresh, hp, k.h_roots, s.rowb, &chunks, rows_out, k.cuts);
+}
+
+// the two refusals a batch of key steps shares behind keys_refused: the caller's own row checks, uncut (in_stride, with its text) or cut (segment 0 has nk
+// rows, the upper segments 2 nk: a null pointer is refused for either count)
+const char *pair_rows_refused(const KeyCall &k, uint32_t depth, size_t rowb, const char *short_stride) {
+  if (k.cuts) return cuts_refused(k.nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
+  return k.h_inputs && k.in_stride < rowb ? short_stride : nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
 int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
                            const uint8_t *h_keys, size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint32_t *h_index, uint8_t *h_status) {
   const char *who = "mfh_merkle_absent_rows";
   if (int rc = tree_refused(c, t, who)) return rc;
   const uint32_t depth = t->depth;
-  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
-  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");  // (at most 64: never also above 2^20)
-  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
-  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
+  const KeyCall k{who, d_table, table_stride, length, key_bytes, nq, h_keys, key_stride, h_inputs, in_stride, h_index, h_status, nullptr, nullptr};
   const size_t rowb = mf::row_bytes(32, (size_t)key_bytes + length, depth);
-  if (h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 32 + key_bytes + length + 32 depth + ceil(depth / 8) bytes");
-  if (nq && !d_table) return fail(c, who, "queries without d_table");
-  if (nq && !h_keys) return fail(c, who, "queries without h_keys");
-  if (nq && !h_index) return fail(c, who, "queries without h_index");
-  if (nq && !h_status) return fail(c, who, "queries without h_status");
-  for (uint32_t k = 0; k < nq; k++)
-    if (mf::key_is_sentinel(h_keys + (size_t)k * key_stride, key_bytes)) return fail(c, who, "a query is the all-zero or the all-0xFF key");
+  const std::string what = keys_refused(k, depth, "queries", false, [&]() -> const char * {
+    return h_inputs && in_stride < rowb ? "in_stride shorter than the row's 32 + key_bytes + length + 32 depth + ceil(depth / 8) bytes" : nullptr;
+  });
+  if (!what.empty()) return fail(c, who, what.c_str());
   if (!nq) return MFH_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   mf::KeyPlan plan;
   mf::keys_prepare(h_keys, key_stride, key_bytes, nq, plan);
-  const uint32_t nu = plan.nu, kw = mf::key_words(key_bytes), n = 1u << depth;
-  // On the device.  The search: the unique queries' words | range[nu] | present[nu].  Then, per chunk: the path rows | the heads (a record each, k_absent_gather)
-  // | the chunk's indices -- over the search's bytes, whose results are on the host by then.
-  const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
+  // On the device.  The search.  Then, per chunk: the path rows | the heads (a record each, k_absent_gather) | the chunk's indices -- over the search's bytes,
+  // whose results are on the host by then.
   const size_t hp = mf::record_head_pitch(length);
   const size_t rows_bytes = h_inputs ? mf::update_chunk(nq, rowb, kPathStageBytes) * (mf::staged_stride(mf::row_bytes(32, 32, depth)) + hp + 4) : 0;  // path_rows'
-  if (int rc = work_reserve(c, c->circ_io, std::max(words_bytes + res_bytes, rows_bytes))) return rc;
-  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
-  {
-    uint32_t *d_qw = c->circ_io.as<uint32_t>(), *d_res = d_qw + (size_t)nu * kw;
-    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
-    if (!pin_qw) return MFH_ENOMEM;
-    memcpy(pin_qw, plan.words.data(), words_bytes);
-    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
-    {
-      Timer tm(c, 30, n);  // "merkle_locate" (mfhip.hip: timing_kind)
-      const dim3 grid((n + 255) / 256), block(256);
-#define MF_LOCATE(KW) \
-  case KW: hipLaunchKernelGGL(k_key_locate<KW>, grid, block, 0, c->stream, d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nu, d_res, d_res + nu); break
-      switch (kw) {
-        MF_LOCATE(1); MF_LOCATE(2); MF_LOCATE(3); MF_LOCATE(4); MF_LOCATE(5); MF_LOCATE(6); MF_LOCATE(7); MF_LOCATE(8);
-      }
-#undef MF_LOCATE
-    }
-    HIP_TRY(c, hipGetLastError());
-    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
-    if (!pin_res) return MFH_ENOMEM;
-    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    mf::keys_scatter(plan, nq, pin_res, h_index, h_status);
-  }
+  if (int rc = work_reserve(c, c->circ_io, std::max(key_search_bytes(plan.nu, key_bytes), rows_bytes))) return rc;
+  const uint32_t *res;
+  if (int rc = key_search(c, k, plan, kLocate, depth, c->circ_io.as<uint8_t>(), &res)) return rc;
+  mf::keys_scatter(plan, nq, res, h_index, h_status);
   if (!h_inputs) return MFH_OK;
   auto gather = [&](const Chunk &u) {
     Timer tm(c, 31, u.k);  // "merkle_absent_rows" (mfhip.hip: timing_kind)
     const uint32_t items = u.k * (uint32_t)(hp / 16);
-    hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, span, length, u.k, u.d_idx, u.d_heads);
+    hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, k.span(depth), length, u.k, u.d_idx, u.d_heads);
   };
   return path_rows(c, t, nq, h_index, h_status, rowb, hp, gather, [&](const Chunk &u) {
     for (uint32_t b = 0; b < u.k; b++) {
       const bool found = h_status[u.b0 + b] != 2;  // (else the zero bytes and the key alone: the staged pieces are a stand-in's)
-      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 32, {{h_keys + (size_t)(u.b0 + b) * key_stride, key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
+      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 32, {{k.key(u.b0 + b), key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
                      found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, depth);
     }
   });
@@ -1175,96 +1314,49 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
 
 namespace {
 
-// mfh_merkle_insert_keys (cuts = null: one row of the whole depth an insert, nk + 1 roots) and mfh_merkle_insert_keys_cut (segment 0's row an insert to
-// cuts->h_rows[0] = h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots)
-int insert_keys(mfh_ctx *c, mfh_merkle *t, const char *who, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
-                size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
-                uint8_t *h_status, const Cuts *cuts) {
-  const uint32_t depth = t->depth, d0 = cuts ? cuts->cuts[0] : depth;  // d0: the levels of the insert's own row
-  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
-  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
-  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
-  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
-  const uint32_t plen = length - 2 * key_bytes;
-  if (h_payloads && payload_stride < plen) return fail(c, who, "payload_stride shorter than the payload's length - 2 key_bytes bytes");
-  const size_t rowb = mf::insert_row_bytes(key_bytes, length, d0, cuts ? 128 : 64);
-  if (!cuts && h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
-  if (cuts)  // (segment 0 has nk rows, the upper segments 2 nk: a null pointer is refused for either count)
-    if (const char *what = cuts_refused(nk, cuts->ncuts, cuts->cuts, depth, cuts->h_rows, cuts->strides, rowb)) return fail(c, who, what);
-  if (nk && !d_table) return fail(c, who, "inserts without d_table");
-  if (nk && !h_keys) return fail(c, who, "inserts without h_keys");
-  if (nk && !h_index) return fail(c, who, "inserts without h_index");
-  if (nk && !h_status) return fail(c, who, "inserts without h_status");
-  const uint32_t n = 1u << depth;
-  if (nk > n) return fail(c, who, "more inserts than the table has slots");
-  if ((uint64_t)2 * nk * ((length + 15) / 16) >> 32) return fail(c, who, "the batch's 2 nk new records exceed 2^32 units of 16 bytes");
-  for (uint32_t j = 0; j < nk; j++)
-    if (mf::key_is_sentinel(h_keys + (size_t)j * key_stride, key_bytes)) return fail(c, who, "a key is the all-zero or the all-0xFF key");
+// mfh_merkle_insert_keys (k.cuts = null: one row of the whole depth an insert, nk + 1 roots) and mfh_merkle_insert_keys_cut (segment 0's row an insert to
+// cuts->h_rows[0] = k.h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots)
+int insert_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const uint8_t *h_payloads, size_t payload_stride) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length;  // d0: the levels of the insert's own row
+  const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(k.key_bytes, 3, length, d0, zeros);
+  const std::string what = keys_refused(k, depth, "inserts", true, [&]() -> const char * {
+    if (h_payloads && payload_stride < length - 2 * k.key_bytes) return "payload_stride shorter than the payload's length - 2 key_bytes bytes";
+    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
+  });
+  if (!what.empty()) return fail(c, k.who, what.c_str());
   if (!nk) return MFH_OK;
   mf::KeyPlan keys;
-  mf::keys_prepare(h_keys, key_stride, key_bytes, nk, keys);
-  if (keys.nu != nk) return fail(c, who, "a key is given twice");
+  mf::keys_prepare(k.h_keys, k.key_stride, k.key_bytes, nk, keys);
+  if (keys.nu != nk) return fail(c, k.who, "a key is given twice");
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t kw = mf::key_words(key_bytes), nb = (n + 255) / 256, nupd = 2 * nk;
-  const size_t hp = mf::record_head_pitch(length);
-  // updates a chunk: whole inserts, all segments' rows together
-  const uint32_t pair_ch = mf::insert_chunk(nk, rowb + (cuts ? 2 * mf::cut_rows_bytes(depth, cuts->ncuts, cuts->cuts) : 0), kPathStageBytes);
-  // On the device.  Kept for the whole call: fresh = the 2 nk new records at a pitch of hp | the plan (p, pred, succ an insert) | the keys | the payloads.  Behind
-  // them, one after the other: the search (the keys' words | range[nk] | present[nk]), the inert search (mask words | count[nb] | total | slots[nk]), and per
-  // chunk update_rows' scratch.
-  const size_t fresh_bytes = (size_t)nupd * hp, plan_bytes = (size_t)nk * 12, keys_bytes = (size_t)nk * key_bytes, pay_bytes = h_payloads ? (size_t)nk * plen : 0;
-  const size_t up_bytes = plan_bytes + keys_bytes + pay_bytes, skip = (fresh_bytes + up_bytes + 15) & ~(size_t)15;
-  const size_t words_bytes = (size_t)nk * kw * 4, res_bytes = (size_t)2 * nk * 4, mask_bytes = (size_t)nb * 4 * 8, inert_bytes = mask_bytes + ((size_t)nb + 1 + nk) * 4;
-  if (int rc = work_reserve(c, c->circ_io, skip + std::max(std::max(words_bytes + res_bytes, inert_bytes), update_rows_bytes(depth, pair_ch, 2 * hp, 1, cuts)))) return rc;
-  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_keys = d_plan + plan_bytes, *d_pay = h_payloads ? d_keys + keys_bytes : nullptr;
-  uint8_t *d_work = d_fresh + skip;
-  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
+  // behind the batch's front, one after the other: the search, the inert search (mask words | count[nb] | total | slots[nk]), update_rows' scratch
+  const uint32_t n = 1u << depth, nb = (n + 255) / 256;
+  const size_t mask_bytes = (size_t)nb * 4 * 8, inert_bytes = mask_bytes + ((size_t)nb + 1 + nk) * 4;
+  PairScratch s;
+  if (int rc = pair_reserve(c, k, depth, rowb, h_payloads ? length - 2 * k.key_bytes : 0, std::max(key_search_bytes(nk, k.key_bytes), inert_bytes), s)) return rc;
+  uint8_t *d_work = c->circ_io.as<uint8_t>() + s.skip;
   std::vector<uint32_t> located(nk), slots(nk);
   {  // a. the search: mfh_merkle_absent_rows', against the table before the batch
-    uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nk * kw;
-    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
-    if (!pin_qw) return MFH_ENOMEM;
-    memcpy(pin_qw, keys.words.data(), words_bytes);
-    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
-    {
-      Timer tm(c, 30, n);  // "merkle_locate" (mfhip.hip: timing_kind)
-      const dim3 grid(nb), block(256);
-#define MF_LOCATE(KW) \
-  case KW: hipLaunchKernelGGL(k_key_locate<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nk, d_res, d_res + nk); break
-      switch (kw) {
-        MF_LOCATE(1); MF_LOCATE(2); MF_LOCATE(3); MF_LOCATE(4); MF_LOCATE(5); MF_LOCATE(6); MF_LOCATE(7); MF_LOCATE(8);
-      }
-#undef MF_LOCATE
-    }
-    HIP_TRY(c, hipGetLastError());
-    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
-    if (!pin_res) return MFH_ENOMEM;
-    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    mf::keys_scatter(keys, nk, pin_res, located.data(), h_status);
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kLocate, depth, d_work, &res)) return rc;
+    mf::keys_scatter(keys, nk, res, located.data(), k.h_status);
     bool member = false, missing = false;
     for (uint32_t j = 0; j < nk; j++) {
-      h_index[2 * (size_t)j] = located[j];
-      member = member || h_status[j] == 1;
-      missing = missing || h_status[j] == 2;
+      k.h_index[2 * (size_t)j] = located[j];
+      member = member || k.h_status[j] == 1;
+      missing = missing || k.h_status[j] == 2;
     }
-    if (member) return fail(c, who, "a key is already a member of the set (h_status 1)");
-    if (missing) return fail(c, who, "no record's range holds a key (h_status 2): the table is malformed");
+    if (member) return fail(c, k.who, "a key is already a member of the set (h_status 1)");
+    if (missing) return fail(c, k.who, "no record's range holds a key (h_status 2): the table is malformed");
   }
   {  // b. the lowest nk inert slots
     unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(d_work);
     uint32_t *d_count = reinterpret_cast<uint32_t *>(d_work + mask_bytes), *d_total = d_count + nb, *d_slots = d_total + 1;
     {
       Timer tm(c, 32, n);  // "merkle_inert" (mfhip.hip: timing_kind): the flags ...
-      const dim3 grid(nb), block(256);
-#define MF_INERT(KW) \
-  case KW: hipLaunchKernelGGL(k_inert_flags<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, d_mask, d_count); break
-      switch (kw) {
-        MF_INERT(1); MF_INERT(2); MF_INERT(3); MF_INERT(4); MF_INERT(5); MF_INERT(6); MF_INERT(7); MF_INERT(8);
-      }
-#undef MF_INERT
+      with_key_words(mf::key_words(k.key_bytes), [&](auto KW) {
+        hipLaunchKernelGGL(k_inert_flags<decltype(KW)::value>, dim3(nb), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.key_bytes, n, d_mask, d_count);
+      });
     }
     {
       Timer tm(c, 32, 0);  // ... the scan of the workgroups' counts ...
@@ -1279,51 +1371,88 @@ int insert_keys(mfh_ctx *c, mfh_merkle *t, const char *who, uint8_t *d_table, si
     if (!pin_slots) return MFH_ENOMEM;
     HIP_TRY(c, hipMemcpyAsync(pin_slots, d_total, ((size_t)nk + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (pin_slots[0] < nk) return fail(c, who, "the table has fewer inert slots than keys to insert");
+    if (pin_slots[0] < nk) return fail(c, k.who, "the table has fewer inert slots than keys to insert");
     memcpy(slots.data(), pin_slots + 1, (size_t)nk * 4);
   }
-  // c. the plan, and what k_insert_records reads: (p, pred, succ) an insert | the keys, packed | the payloads, packed
+  // c. the plan: (p, s) of every insert -- p the slot whose hi changes, an earlier insert's where that split the range first, s the new record's -- and what
+  // k_insert_records reads, (p, pred, succ) an insert
   mf::InsertPlan plan;
-  mf::insert_plan(h_keys, key_stride, key_bytes, nk, located.data(), slots.data(), plan);
-  for (uint32_t j = 0; j < nk; j++) {  // (p, s): the slot whose hi changes -- an earlier insert's where that split the range first -- and the new record's
-    h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];
-    h_index[2 * (size_t)j + 1] = slots[j];
+  mf::insert_plan(k.h_keys, k.key_stride, k.key_bytes, nk, located.data(), slots.data(), plan);
+  std::vector<int32_t> words((size_t)3 * nk);
+  for (uint32_t j = 0; j < nk; j++) {
+    k.h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];
+    k.h_index[2 * (size_t)j + 1] = slots[j];
+    words[3 * (size_t)j] = (int32_t)located[j];
+    words[3 * (size_t)j + 1] = plan.pred[j];
+    words[3 * (size_t)j + 2] = plan.succ[j];
   }
-  {
-    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, up_bytes);
-    if (!pin_up) return MFH_ENOMEM;
-    int32_t *w = reinterpret_cast<int32_t *>(pin_up);
-    for (uint32_t j = 0; j < nk; j++) {
-      w[3 * (size_t)j] = (int32_t)located[j];
-      w[3 * (size_t)j + 1] = plan.pred[j];
-      w[3 * (size_t)j + 2] = plan.succ[j];
-      memcpy(pin_up + plan_bytes + (size_t)j * key_bytes, h_keys + (size_t)j * key_stride, key_bytes);
-      if (h_payloads && plen) memcpy(pin_up + plan_bytes + keys_bytes + (size_t)j * plen, h_payloads + (size_t)j * payload_stride, plen);
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, up_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-  }
-  {  // d. the 2 nk new records
-    Timer tm(c, 33, nupd);  // "merkle_insert_records" (mfhip.hip: timing_kind)
-    const uint64_t items = (uint64_t)nupd * (hp / 16);
-    hipLaunchKernelGGL(k_insert_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, span, (const uint8_t *)d_keys,
-                       (const uint8_t *)d_pay, (const int32_t *)d_plan, key_bytes, length, nk, reinterpret_cast<uint4 *>(d_fresh));
-  }
-  HIP_TRY(c, hipGetLastError());
-  // e. the 2 nk record updates, a chunk of whole inserts at a time; row b of a chunk out of the heads and the level rows of its updates 2 b and 2 b + 1
-  const Pairs chunks{pair_ch, skip, cuts != nullptr};
+  auto build = [&](dim3 grid, const int32_t *d_plan, const uint8_t *d_keys, const uint8_t *d_pay, uint4 *d_fresh) {
+    hipLaunchKernelGGL(k_insert_records, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), d_keys, d_pay, d_plan, k.key_bytes, length, nk, d_fresh);
+  };
+  // d. the 2 nk new records and their updates; a row: the key | old record of p | old record of s | new record of s
+  const size_t hp = mf::record_head_pitch(length);
   const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
-  ChunkFn rows_out;
-  if (h_inputs)
-    rows_out = [&](const Chunk &u) {
-      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
-        const uint32_t j = (u.b0 + b) / 2;
-        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
-        mf::splice_insert_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, hp, length, staged_p, staged_p + u.rs, d0,
-                              h_index[2 * (size_t)j] & low, h_index[2 * (size_t)j + 1] & low, cuts ? 128 : 64);
-      }
-    };
-  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out, cuts);
+  return pair_updates(c, t, k, d_table, s, 33, build, words, plan.idx, h_payloads, payload_stride,
+                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
+    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros, {{k.key(j), k.key_bytes}, {head_p, length}, {head_s, length}, {head_s + hp, length}}, staged_p, staged_s, d0,
+                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  });
+}
+
+// mfh_merkle_remove_keys (k.cuts = null: one row of the whole depth a remove, nk + 1 roots) and mfh_merkle_remove_keys_cut (segment 0's row a remove to
+// cuts->h_rows[0] = k.h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots)
+int remove_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length;  // d0: the levels of the remove's own row
+  const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(k.key_bytes, 2, length, d0, zeros);
+  const std::string what = keys_refused(k, depth, "removes", true, [&] {
+    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
+  });
+  if (!what.empty()) return fail(c, k.who, what.c_str());
+  if (!nk) return MFH_OK;
+  mf::KeyPlan keys;
+  mf::keys_prepare(k.h_keys, k.key_stride, k.key_bytes, nk, keys);
+  if (keys.nu != nk) return fail(c, k.who, "a key is given twice");
+  HIP_TRY(c, hipSetDevice(c->device));
+  PairScratch s;  // behind the batch's front: the search, then update_rows' scratch
+  if (int rc = pair_reserve(c, k, depth, rowb, 0, key_search_bytes(nk, k.key_bytes), s)) return rc;
+  std::vector<uint32_t> own(nk), prev(nk);
+  {  // a. the search, against the table before the batch: own | prev per UNIQUE sorted key, back to the caller's order
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kOwners, depth, c->circ_io.as<uint8_t>() + s.skip, &res)) return rc;
+    bool absent = false, loose = false;
+    for (uint32_t j = 0; j < nk; j++) {
+      own[j] = res[keys.slot[j]];
+      prev[j] = res[nk + keys.slot[j]];
+      k.h_index[2 * (size_t)j] = prev[j];
+      k.h_index[2 * (size_t)j + 1] = own[j];
+      k.h_status[j] = own[j] == mf::kNoRecord ? 0 : prev[j] == mf::kNoRecord ? 2 : 1;
+      absent = absent || k.h_status[j] == 0;
+      loose = loose || k.h_status[j] == 2;
+    }
+    if (absent) return fail(c, k.who, "a key is not a member of the set (h_status 0)");
+    if (loose) return fail(c, k.who, "no live record has a member as its hi (h_status 2): the table is malformed");
+  }
+  // b. the plan: (P, s) of every remove -- P the slot whose hi changes, further left where earlier removes took the ones between -- and what k_remove_records
+  // reads, (P, hi_key, hi_rec) a remove
+  mf::RemovePlan plan;
+  mf::remove_plan(k.h_keys, k.key_stride, k.key_bytes, nk, own.data(), prev.data(), plan);
+  std::vector<int32_t> words((size_t)3 * nk);
+  for (uint32_t j = 0; j < nk; j++) {
+    k.h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];
+    words[3 * (size_t)j] = (int32_t)plan.idx[2 * (size_t)j];
+    words[3 * (size_t)j + 1] = plan.hi_key[j];
+    words[3 * (size_t)j + 2] = (int32_t)plan.hi_rec[j];
+  }
+  auto build = [&](dim3 grid, const int32_t *d_plan, const uint8_t *d_keys, const uint8_t *, uint4 *d_fresh) {
+    hipLaunchKernelGGL(k_remove_records, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), d_keys, d_plan, k.key_bytes, length, nk, d_fresh);
+  };
+  // c. the 2 nk new records and their updates; a row: the key | old record of P | old record of s
+  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
+  return pair_updates(c, t, k, d_table, s, 36, build, words, plan.idx, nullptr, 0,
+                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
+    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros, {{k.key(j), k.key_bytes}, {head_p, length}, {head_s, length}}, staged_p, staged_s, d0,
+                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  });
 }
 
 }  // namespace
@@ -1335,7 +1464,8 @@ int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t t
                            uint8_t *h_status) {
   const char *who = "mfh_merkle_insert_keys";
   if (int rc = tree_refused(c, t, who)) return rc;
-  return insert_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_payloads, payload_stride, h_inputs, in_stride, h_roots, h_index, h_status, nullptr);
+  return insert_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_index, h_status, h_roots, nullptr}, d_table, h_payloads,
+                     payload_stride);
 }
 
 int mfh_merkle_insert_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
@@ -1345,140 +1475,15 @@ int mfh_merkle_insert_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size
   if (int rc = tree_refused(c, t, who)) return rc;
   if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
   const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
-  return insert_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_payloads, payload_stride, h_rows[0], h_strides[0], h_roots, h_index, h_status, &cuts);
+  return insert_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table, h_payloads,
+                     payload_stride);
 }
-
-}  // extern "C"
-
-namespace {
-
-// mfh_merkle_remove_keys (cuts = null: one row of the whole depth a remove, nk + 1 roots) and mfh_merkle_remove_keys_cut (segment 0's row a remove to
-// cuts->h_rows[0] = h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots): insert_keys' driver without the inert search, the search and the build
-// kernels swapped
-int remove_keys(mfh_ctx *c, mfh_merkle *t, const char *who, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
-                size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status, const Cuts *cuts) {
-  const uint32_t depth = t->depth, d0 = cuts ? cuts->cuts[0] : depth;  // d0: the levels of the remove's own row
-  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
-  if (length < 2 * key_bytes) return fail(c, who, "length shorter than the two keys' 2 key_bytes bytes");
-  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
-  if (key_stride < key_bytes) return fail(c, who, "key_stride shorter than key_bytes");
-  const size_t rowb = mf::remove_row_bytes(key_bytes, length, d0, cuts ? 128 : 64);
-  if (!cuts && h_inputs && in_stride < rowb) return fail(c, who, "in_stride shorter than the row's 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
-  if (cuts)  // (segment 0 has nk rows, the upper segments 2 nk: a null pointer is refused for either count)
-    if (const char *what = cuts_refused(nk, cuts->ncuts, cuts->cuts, depth, cuts->h_rows, cuts->strides, rowb)) return fail(c, who, what);
-  if (nk && !d_table) return fail(c, who, "removes without d_table");
-  if (nk && !h_keys) return fail(c, who, "removes without h_keys");
-  if (nk && !h_index) return fail(c, who, "removes without h_index");
-  if (nk && !h_status) return fail(c, who, "removes without h_status");
-  const uint32_t n = 1u << depth;
-  if (nk > n) return fail(c, who, "more removes than the table has slots");
-  if ((uint64_t)2 * nk * ((length + 15) / 16) >> 32) return fail(c, who, "the batch's 2 nk new records exceed 2^32 units of 16 bytes");
-  for (uint32_t j = 0; j < nk; j++)
-    if (mf::key_is_sentinel(h_keys + (size_t)j * key_stride, key_bytes)) return fail(c, who, "a key is the all-zero or the all-0xFF key");
-  if (!nk) return MFH_OK;
-  mf::KeyPlan keys;
-  mf::keys_prepare(h_keys, key_stride, key_bytes, nk, keys);
-  if (keys.nu != nk) return fail(c, who, "a key is given twice");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t kw = mf::key_words(key_bytes), nupd = 2 * nk;
-  const size_t hp = mf::record_head_pitch(length);
-  // updates a chunk: whole removes, all segments' rows together
-  const uint32_t pair_ch = mf::insert_chunk(nk, rowb + (cuts ? 2 * mf::cut_rows_bytes(depth, cuts->ncuts, cuts->cuts) : 0), kPathStageBytes);
-  // On the device.  Kept for the whole call: fresh = the 2 nk new records at a pitch of hp | the plan (P, hi_key, hi_rec a remove) | the keys.  Behind them, one
-  // after the other: the search (the keys' words | own[nk] | prev[nk]) and per chunk update_rows' scratch.
-  const size_t fresh_bytes = (size_t)nupd * hp, plan_bytes = (size_t)nk * 12, keys_bytes = (size_t)nk * key_bytes;
-  const size_t up_bytes = plan_bytes + keys_bytes, skip = (fresh_bytes + up_bytes + 15) & ~(size_t)15;
-  const size_t words_bytes = (size_t)nk * kw * 4, res_bytes = (size_t)2 * nk * 4;
-  if (int rc = work_reserve(c, c->circ_io, skip + std::max(words_bytes + res_bytes, update_rows_bytes(depth, pair_ch, 2 * hp, 1, cuts)))) return rc;
-  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_keys = d_plan + plan_bytes;
-  uint8_t *d_work = d_fresh + skip;
-  const int64_t span = (int64_t)((size_t)(n - 1) * table_stride + length);
-  std::vector<uint32_t> own(nk), prev(nk);
-  {  // a. the search, against the table before the batch
-    uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nk * kw;
-    uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
-    if (!pin_qw) return MFH_ENOMEM;
-    memcpy(pin_qw, keys.words.data(), words_bytes);
-    HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-    HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
-    {
-      Timer tm(c, 35, n);  // "merkle_owners" (mfhip.hip: timing_kind)
-      const dim3 grid((n + 255) / 256), block(256);
-#define MF_OWNERS(KW) \
-  case KW: hipLaunchKernelGGL(k_key_owners<KW>, grid, block, 0, c->stream, (const uint8_t *)d_table, table_stride, span, key_bytes, n, (const uint32_t *)d_qw, nk, d_res, d_res + nk); break
-      switch (kw) {
-        MF_OWNERS(1); MF_OWNERS(2); MF_OWNERS(3); MF_OWNERS(4); MF_OWNERS(5); MF_OWNERS(6); MF_OWNERS(7); MF_OWNERS(8);
-      }
-#undef MF_OWNERS
-    }
-    HIP_TRY(c, hipGetLastError());
-    uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
-    if (!pin_res) return MFH_ENOMEM;
-    HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    bool absent = false, loose = false;
-    for (uint32_t j = 0; j < nk; j++) {  // (own | prev per UNIQUE sorted key, back to the caller's order)
-      own[j] = pin_res[keys.slot[j]];
-      prev[j] = pin_res[nk + keys.slot[j]];
-      h_index[2 * (size_t)j] = prev[j];
-      h_index[2 * (size_t)j + 1] = own[j];
-      h_status[j] = own[j] == mf::kNoRecord ? 0 : prev[j] == mf::kNoRecord ? 2 : 1;
-      absent = absent || h_status[j] == 0;
-      loose = loose || h_status[j] == 2;
-    }
-    if (absent) return fail(c, who, "a key is not a member of the set (h_status 0)");
-    if (loose) return fail(c, who, "no live record has a member as its hi (h_status 2): the table is malformed");
-  }
-  // b. the plan, and what k_remove_records reads: (P, hi_key, hi_rec) a remove | the keys, packed
-  mf::RemovePlan plan;
-  mf::remove_plan(h_keys, key_stride, key_bytes, nk, own.data(), prev.data(), plan);
-  for (uint32_t j = 0; j < nk; j++) h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];  // (P, s): the slot whose hi changes -- further left where earlier removes took the ones between
-  {
-    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, up_bytes);
-    if (!pin_up) return MFH_ENOMEM;
-    int32_t *w = reinterpret_cast<int32_t *>(pin_up);
-    for (uint32_t j = 0; j < nk; j++) {
-      w[3 * (size_t)j] = (int32_t)plan.idx[2 * (size_t)j];
-      w[3 * (size_t)j + 1] = plan.hi_key[j];
-      w[3 * (size_t)j + 2] = (int32_t)plan.hi_rec[j];
-      memcpy(pin_up + plan_bytes + (size_t)j * key_bytes, h_keys + (size_t)j * key_stride, key_bytes);
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, up_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-  }
-  {  // c. the 2 nk new records
-    Timer tm(c, 36, nupd);  // "merkle_remove_records" (mfhip.hip: timing_kind)
-    const uint64_t items = (uint64_t)nupd * (hp / 16);
-    hipLaunchKernelGGL(k_remove_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_table, table_stride, span, (const uint8_t *)d_keys,
-                       (const int32_t *)d_plan, key_bytes, length, nk, reinterpret_cast<uint4 *>(d_fresh));
-  }
-  HIP_TRY(c, hipGetLastError());
-  // d. the 2 nk record updates, a chunk of whole removes at a time; row b of a chunk out of the heads and the level rows of its updates 2 b and 2 b + 1
-  const Pairs chunks{pair_ch, skip, cuts != nullptr};
-  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
-  ChunkFn rows_out;
-  if (h_inputs)
-    rows_out = [&](const Chunk &u) {
-      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
-        const uint32_t j = (u.b0 + b) / 2;
-        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
-        mf::splice_remove_row(h_inputs + (size_t)j * in_stride, h_keys + (size_t)j * key_stride, key_bytes, head_p, head_p + u.hs, length, staged_p, staged_p + u.rs, d0,
-                              h_index[2 * (size_t)j] & low, h_index[2 * (size_t)j + 1] & low, cuts ? 128 : 64);
-      }
-    };
-  return record_updates(c, t, nupd, plan.idx.data(), d_table, table_stride, length, d_fresh, hp, h_roots, rowb, &chunks, rows_out, cuts);
-}
-
-}  // namespace
-
-extern "C" {
 
 int mfh_merkle_remove_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
                            size_t key_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
   const char *who = "mfh_merkle_remove_keys";
   if (int rc = tree_refused(c, t, who)) return rc;
-  return remove_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_roots, h_index, h_status, nullptr);
+  return remove_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_index, h_status, h_roots, nullptr}, d_table);
 }
 
 int mfh_merkle_remove_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
@@ -1488,7 +1493,7 @@ int mfh_merkle_remove_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size
   if (int rc = tree_refused(c, t, who)) return rc;
   if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
   const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
-  return remove_keys(c, t, who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_roots, h_index, h_status, &cuts);
+  return remove_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table);
 }
 
 }  // extern "C"

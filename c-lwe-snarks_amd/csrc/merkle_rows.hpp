@@ -9,10 +9,10 @@
 //   words.MerkleAbsent(key_bytes, length, depth)  Z = 32, head = the query's key | the located record   row_bytes(32, key_bytes + length, depth)
 //   words.MerkleInsert(key_bytes, length, depth)  Z = 64, head = the key | old record of p | old record of s | new record of s, and TWO tails' siblings:
 //                                                 depth siblings of p | depth siblings of s | ceil(2 depth / 8) index bytes, bit l < depth = bit l of p,
-//                                                 bit depth + l = bit l of s                      insert_row_bytes(key_bytes, length, depth)
-//   words.MerkleInsert(.., joined=False)          the same behind Z = 128 (four tops)                insert_row_bytes(key_bytes, length, depth, 128)
+//                                                 bit depth + l = bit l of s                      pair_row_bytes(key_bytes, 3, length, depth)
+//   words.MerkleInsert(.., joined=False)          the same behind Z = 128 (four tops)                pair_row_bytes(key_bytes, 3, length, depth, 128)
 //   words.MerkleRemove(key_bytes, length, depth)  the insert's row without a new record of s: Z = 64 (128 with joined=False), head = the key | old record of
-//                                                 p | old record of s, the two tails as the insert's  remove_row_bytes(key_bytes, length, depth)
+//                                                 p | old record of s, the two tails as the insert's  pair_row_bytes(key_bytes, 2, length, depth)
 //   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
 //                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
 // A path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) gives G + 1 rows an update: segment 0 is the statement's own row over the subtree of
@@ -23,7 +23,8 @@
 // pieces per row and the host splices them while it copies out of the pinned buffer (splice_row):
 //   the staged row  a path row or a level row; only its tail is read
 //   the heads       what k_record_gather / k_absent_gather write: each record at the start of a slot of record_head_pitch(length) bytes (whole-unit stores)
-// An insert is two record updates: its row is spliced out of the heads and the level rows of both (splice_insert_row), the index bits written by the host.
+// A key step (insert, remove) is two record updates: its row is spliced out of the heads and the level rows of both (splice_pair_row), the index bits written
+// by the host.
 // An absent query for which no record was found (status 2) gets the zero bytes and its key alone: its staged pieces come from a stand-in index and are not read.
 #pragma once
 #include <stddef.h>
@@ -45,8 +46,9 @@ inline uint32_t update_chunk(uint32_t nupd, size_t row_bytes, size_t stage_bytes
   return (uint32_t)(fit < 1 ? 1 : fit < nupd ? fit : nupd);
 }
 
-inline size_t insert_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth, size_t zeros = 64) {
-  return zeros + key_bytes + (size_t)3 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
+// the row of a key step, two record updates (p, s) under one pair of roots: the key and nrec records in its head, then TWO tails' siblings and both indices' bits
+inline size_t pair_row_bytes(uint32_t key_bytes, uint32_t nrec, uint32_t length, uint32_t depth, size_t zeros = 64) {
+  return zeros + key_bytes + (size_t)nrec * length + (size_t)64 * depth + (2 * depth + 7) / 8;
 }
 
 inline size_t segment_row_bytes(uint32_t levels) { return row_bytes(64, 64, levels); }
@@ -65,9 +67,9 @@ inline size_t cut_rows_bytes(uint32_t depth, uint32_t ncuts, const uint32_t *cut
   return bytes;
 }
 
-// the updates of one chunk of a batch of nk inserts (nk > 0): the most INSERTS whose rows of row_bytes fit the stage, at least one, two updates each -- always
-// even, so both updates of an insert are in one chunk even when one row alone exceeds the stage
-inline uint32_t insert_chunk(uint32_t nk, size_t row_bytes, size_t stage_bytes) { return 2 * update_chunk(nk, row_bytes, stage_bytes); }
+// the updates of one chunk of a batch of nk key steps (nk > 0): the most STEPS whose rows of row_bytes fit the stage, at least one, two updates each -- always
+// even, so both updates of a step are in one chunk even when one row alone exceeds the stage
+inline uint32_t pair_chunk(uint32_t nk, size_t row_bytes, size_t stage_bytes) { return 2 * update_chunk(nk, row_bytes, stage_bytes); }
 
 struct RowPiece {
   const uint8_t *p;
@@ -93,49 +95,15 @@ inline void splice_cut_tail(uint8_t *at, const uint8_t *staged, uint32_t c0, uin
   for (uint32_t b = 0; b < (c0 + 7) / 8; b++) at[(size_t)32 * c0 + b] = (uint8_t)(low >> (8 * b));
 }
 
-// row <- the input row of words.MerkleInsert for the insert whose updates are (record p: head_p = old | new at a pitch of hp; slot s: head_s likewise) and
-// whose level rows are staged_p and staged_s (tails at byte 128): 64 zero bytes | key | old_p | old_s | new_s | p's siblings | s's siblings | the index bytes of
-// (p, s).  Reads key_bytes, length and 32 depth bytes of its sources, writes insert_row_bytes(key_bytes, length, depth) bytes and nothing behind them.
-// Segment 0 of a cut insert (joined=False): zeros = 128, depth = c_0 -- the first c_0 siblings of each level row -- and p, s already reduced mod 2^c_0.
-inline void splice_insert_row(uint8_t *row, const uint8_t *key, uint32_t key_bytes, const uint8_t *head_p, const uint8_t *head_s, size_t hp, uint32_t length,
-                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s, size_t zeros = 64) {
-  memset(row, 0, zeros);
+// row <- the input row of a key step whose two updates' level rows are staged_p and staged_s (tails at byte 128): `zeros` zero bytes | the head's pieces, in
+// order (the key, then the step's records out of the two updates' heads) | p's siblings | s's siblings | the index bytes of (p, s).  Reads the pieces' bytes --
+// key_bytes and `length` each -- and 32 depth bytes of each level row; writes pair_row_bytes(key_bytes, nrec, length, depth, zeros) bytes and nothing behind
+// them.  Segment 0 of a cut step (joined=False): zeros = 128, depth = c_0 -- the first c_0 siblings of each level row -- and p, s already reduced mod 2^c_0.
+inline void splice_pair_row(uint8_t *row, size_t zeros, std::initializer_list<RowPiece> head, const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth,
+                            uint32_t p, uint32_t s) {
+  splice_row(row, zeros, head, nullptr, 0, 0);
   row += zeros;
-  memcpy(row, key, key_bytes);
-  row += key_bytes;
-  if (length) {
-    memcpy(row, head_p, length);
-    memcpy(row + length, head_s, length);
-    memcpy(row + 2 * (size_t)length, head_s + hp, length);
-  }
-  row += 3 * (size_t)length;
-  memcpy(row, staged_p + 128, (size_t)32 * depth);
-  memcpy(row + (size_t)32 * depth, staged_s + 128, (size_t)32 * depth);
-  row += (size_t)64 * depth;
-  const uint64_t bits = (uint64_t)p | (uint64_t)s << depth;  // (depth <= 24: 48 bits)
-  for (uint32_t b = 0; b < (2 * depth + 7) / 8; b++) row[b] = (uint8_t)(bits >> (8 * b));
-}
-
-// words.MerkleRemove(key_bytes, length, depth): the insert's row without a new record of s -- zeros | the key | old record of p | old record of s | depth
-// siblings of p | depth siblings of s | the index bytes of (p, s), as the insert's; zeros = 128 with joined=False
-inline size_t remove_row_bytes(uint32_t key_bytes, uint32_t length, uint32_t depth, size_t zeros = 64) {
-  return zeros + key_bytes + (size_t)2 * length + (size_t)64 * depth + (2 * depth + 7) / 8;
-}
-
-// row <- the input row of words.MerkleRemove for the remove whose updates are (record p: head_p = its old record; slot s: head_s likewise, as it stands after
-// p's update) and whose level rows are staged_p and staged_s (tails at byte 128).  Reads key_bytes, length and 32 depth bytes of its sources, writes
-// remove_row_bytes(key_bytes, length, depth, zeros) bytes and nothing behind them.  Segment 0 of a cut remove: zeros = 128, depth = c_0, p and s mod 2^c_0.
-inline void splice_remove_row(uint8_t *row, const uint8_t *key, uint32_t key_bytes, const uint8_t *head_p, const uint8_t *head_s, uint32_t length,
-                              const uint8_t *staged_p, const uint8_t *staged_s, uint32_t depth, uint32_t p, uint32_t s, size_t zeros = 64) {
-  memset(row, 0, zeros);
-  row += zeros;
-  memcpy(row, key, key_bytes);
-  row += key_bytes;
-  if (length) {
-    memcpy(row, head_p, length);
-    memcpy(row + length, head_s, length);
-  }
-  row += 2 * (size_t)length;
+  for (const RowPiece &h : head) row += h.bytes;
   memcpy(row, staged_p + 128, (size_t)32 * depth);
   memcpy(row + (size_t)32 * depth, staged_s + 128, (size_t)32 * depth);
   row += (size_t)64 * depth;

@@ -813,6 +813,16 @@ def _is_sentinel(key: bytes) -> bool:
     return key == bytes(len(key)) or key == b"\xff" * len(key)
 
 
+def _checked_key(who: str, key_bytes: int, key, never: str) -> bytes:
+    """the key as bytes; refused when it is not key_bytes bytes or a sentinel, which is `never` ("queries", "members") what the statement takes"""
+    key = bytes(key)
+    if len(key) != key_bytes:
+        raise CircuitError(f"{who}: the key is {key_bytes} bytes")
+    if _is_sentinel(key):
+        raise CircuitError(f"{who}: the all-zero and the all-0xFF key are sentinels, never {never}")
+    return key
+
+
 class MerkleAbsent(_OneRoot):
     """The statement "the key q is NOT in the set behind this root", for a set kept as an indexed Merkle tree: I know a `length`-byte record (lo | hi |
     payload) and an authentication path of `depth` siblings, such that SHA-256(record) is a leaf of the tree with this root and lo < q < hi.
@@ -852,12 +862,7 @@ class MerkleAbsent(_OneRoot):
         return 256 + 8 * self.key_bytes
 
     def _query(self, key) -> bytes:
-        key = bytes(key)
-        if len(key) != self.key_bytes:
-            raise CircuitError(f"MerkleAbsent: the key is {self.key_bytes} bytes")
-        if _is_sentinel(key):
-            raise CircuitError("MerkleAbsent: the all-zero and the all-0xFF key are sentinels, never queries")
-        return key
+        return _checked_key("MerkleAbsent", self.key_bytes, key, "queries")
 
     def bits(self, key: bytes, record: bytes, siblings, index: int):
         """one statement's input bits, public then private: 256 zeros where the root is computed, the query's bits, the record's bits, the siblings from
@@ -872,7 +877,82 @@ class MerkleAbsent(_OneRoot):
         return _statement_of(root, "MerkleAbsent: the root") + self._query(key)
 
 
-class MerkleInsert(_TwoRoots):
+class _KeyStep(_TwoRoots):
+    """Private base of MerkleInsert and MerkleRemove: a key step, the two record updates of slots p and s under ONE pair of roots, with the key as public
+    wires behind the roots.  It holds what the two share -- the argument checks, the two tails' wires, the four level chains over (p, p, s, s), the wiring of
+    their tops (joined or not), the key's wires, lu, statement, tops_of and the tail half of bits.  A subclass states its private records, how new_p is
+    composed, its four leaves, its assert_same and comparator lines and the record arguments of bits: its __init__ is _open, its own records and leaves,
+    _close, its own assertions -- in that order, which is the order of the wires and gates of the compiled program."""
+
+    joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
+
+    def _open(self, key_bytes, length, depth, nrec: int):
+        """the argument checks, then the private wires in their order: nrec records of 8 * length bits (returned), `depth` siblings of p, `depth` siblings of
+        s, the direction bits of p, those of s"""
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
+        self.depth = depth = self._depth_arg(depth)
+        self.w = w = Words()
+        records = [w.c.private(8 * length) for _ in range(nrec)]
+        self.siblings_p = [w.private(8) for _ in range(depth)]
+        self.siblings_s = [w.private(8) for _ in range(depth)]
+        self.dirs_p = w.c.private(depth)
+        self.dirs_s = w.c.private(depth)
+        return records
+
+    def _close(self, leaves, joined):
+        """the level chains of the four leaves (old p, new p, old s, new s), the first two over p's tail and the last two over s's; the old root's outputs,
+        with joined=False the two middle tops', the new root's; the key's public wires; joined: the 256 assert_same that tie the middle tops, the private
+        intermediate root"""
+        w = self.w
+        tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
+        self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for leaf, (sibs, dirs) in zip(leaves, tails))
+        self.joined = bool(joined)
+        self.old_root = [w.output(x) for x in self.out_old]
+        if not self.joined:  # every chain top is public: X_p, X_p', X_s, X_s'
+            self.top_mid_p = [w.output(x) for x in self.mid_p]
+            self.top_mid_s = [w.output(x) for x in self.mid_s]
+        self.new_root = [w.output(x) for x in self.out_new]
+        self.key = w.c.public(8 * self.key_bytes)
+        if self.joined:
+            for x, y in zip(self.mid_p, self.mid_s):
+                w.assert_same_u32(x, y)
+
+    @property
+    def lu(self) -> int:
+        return (512 if self.joined else 1024) + 8 * self.key_bytes
+
+    def _query(self, key) -> bytes:
+        return _checked_key(type(self).__name__, self.key_bytes, key, "members")
+
+    def _step_bits(self, key, records, siblings_p, index_p, siblings_s, index_s):
+        """512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits, the records' bits, p's siblings and s's as
+        big-endian words, then the direction bits of p and of s"""
+        who = type(self).__name__
+        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
+        tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
+        nsib = 256 * self.depth
+        return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, *records, what="the records are"), tail_p[:nsib], tail_s[:nsib],
+                           tail_p[nsib:], tail_s[nsib:])
+
+    def statement(self, *tops_and_key) -> bytes:
+        """statement(old_root, new_root, key): the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the step
+        with `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 +
+        key_bytes bytes: "the step with `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
+        who = type(self).__name__
+        *tops, key = tops_and_key
+        if len(tops) != (2 if self.joined else 4):
+            raise CircuitError(f"{who}: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
+        return b"".join(_statement_of(x, f"{who}: a top") for x in tops) + self._query(key)
+
+    def tops_of(self, witness_row):
+        """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
+        if self.joined:
+            raise CircuitError(f"{type(self).__name__}: tops_of is for joined=False (roots_of reads the two roots)")
+        return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
+
+
+class MerkleInsert(_KeyStep):
     """The statement "the key k was inserted into the indexed table (MerkleAbsent has the data model), and that alone takes the tree from root R to root
     R'": the two record updates of an insert (indexed_insert) under ONE pair of roots.  Record p, whose range held k (lo_p < k < hi_p), gets hi <- k; the
     record (k, the old hi_p, a payload) goes into a slot s that was inert (lo_s >= hi_s).  A chain of such steps from the root of an indexed_records table
@@ -902,33 +982,13 @@ class MerkleInsert(_TwoRoots):
     chain of s starts from the root after p's update, which thereby becomes public.  Sizes (MERKLE_INSERT_SPLIT_SIZES): the joined ones plus 512 wires and 768
     rows; (8, 55, 4) still fits Params(d=1 << 20, m=699050)."""
 
-    joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
-
     def __init__(self, key_bytes: int, length: int, depth: int, joined=True):
-        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
-        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
-        self.depth = depth = self._depth_arg(depth)
-        self.w = w = Words()
-        self.old_p, self.old_s, self.new_s = (w.c.private(8 * length) for _ in range(3))
-        self.siblings_p = [w.private(8) for _ in range(depth)]
-        self.siblings_s = [w.private(8) for _ in range(depth)]
-        self.dirs_p = w.c.private(depth)
-        self.dirs_s = w.c.private(depth)
+        self.old_p, self.old_s, self.new_s = self._open(key_bytes, length, depth, 3)
+        w, K = self.w, self.key_bytes
         self.new_p = self.old_p[: 8 * K] + self.new_s[: 8 * K] + self.old_p[16 * K:]
-        leaves = [_message_chain(w, rec, length) for rec in (self.old_p, self.new_p, self.old_s, self.new_s)]
-        self.blocks = leaves[0][1]
-        tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
-        self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for (leaf, _), (sibs, dirs) in zip(leaves, tails))
-        self.joined = bool(joined)
-        self.old_root = [w.output(x) for x in self.out_old]
-        if not self.joined:  # every chain top is public: X_p, X_p', X_s, X_s'
-            self.top_mid_p = [w.output(x) for x in self.mid_p]
-            self.top_mid_s = [w.output(x) for x in self.mid_s]
-        self.new_root = [w.output(x) for x in self.out_new]
-        self.key = w.c.public(8 * K)
-        if self.joined:
-            for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
-                w.assert_same_u32(x, y)
+        chains = [_message_chain(w, rec, self.length) for rec in (self.old_p, self.new_p, self.old_s, self.new_s)]
+        self.blocks = chains[0][1]
+        self._close([leaf for leaf, _ in chains], joined)
         for a, b in zip(self.key, self.new_s[: 8 * K]):
             w.c.assert_same(a, b)
         for a, b in zip(self.old_p[8 * K: 16 * K], self.new_s[8 * K: 16 * K]):
@@ -939,46 +999,14 @@ class MerkleInsert(_TwoRoots):
         w.c.assert_equal(w.less_than(k, hi_p), 1)
         w.c.assert_equal(w.less_than(lo_s, hi_s), 0)
 
-    @property
-    def lu(self) -> int:
-        return (512 if self.joined else 1024) + 8 * self.key_bytes
-
-    def _query(self, key) -> bytes:
-        key = bytes(key)
-        if len(key) != self.key_bytes:
-            raise CircuitError(f"MerkleInsert: the key is {self.key_bytes} bytes")
-        if _is_sentinel(key):
-            raise CircuitError("MerkleInsert: the all-zero and the all-0xFF key are sentinels, never members")
-        return key
-
     def bits(self, key: bytes, old_p: bytes, old_s: bytes, new_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
         """one statement's input bits, public then private: 512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits,
         the three records' bits, p's siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A
         witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
-        who = "MerkleInsert"
-        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
-        tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
-        nsib = 256 * self.depth
-        return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, old_p, old_s, new_s, what="the records are"), tail_p[:nsib],
-                           tail_s[:nsib], tail_p[nsib:], tail_s[nsib:])
-
-    def statement(self, *tops_and_key) -> bytes:
-        """statement(old_root, new_root, key): the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "inserting
-        `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 + key_bytes
-        bytes: "inserting `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
-        *tops, key = tops_and_key
-        if len(tops) != (2 if self.joined else 4):
-            raise CircuitError("MerkleInsert: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
-        return b"".join(_statement_of(x, "MerkleInsert: a top") for x in tops) + self._query(key)
-
-    def tops_of(self, witness_row):
-        """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
-        if self.joined:
-            raise CircuitError("MerkleInsert: tops_of is for joined=False (roots_of reads the two roots)")
-        return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
+        return self._step_bits(key, (old_p, old_s, new_s), siblings_p, index_p, siblings_s, index_s)
 
 
-class MerkleRemove(_TwoRoots):
+class MerkleRemove(_KeyStep):
     """The statement "the key k was removed from the indexed table (MerkleAbsent has the data model), and that alone takes the tree from root R to root
     R'": the two record updates of a removal (indexed_remove) under ONE pair of roots.  Record s is the one whose own key is k (lo_s = k): it becomes the
     all-zero record, which is inert and is what indexed_records leaves in unused slots.  Record p is the live record whose hi is k: it gets hi <- hi_s, its
@@ -1009,35 +1037,14 @@ class MerkleRemove(_TwoRoots):
     [256, 512), X_s at [512, 768), X_s' at [768, 1024), the key's bits from 1024; lu = 1024 + 8 key_bytes; statement(X_p, X_p', X_s, X_s', key);
     tops_of(row) reads the four back; the packed row is the joined one with 128 zero bytes in front in place of 64 (MERKLE_REMOVE_SPLIT_SIZES)."""
 
-    joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
-
     def __init__(self, key_bytes: int, length: int, depth: int, joined=True):
-        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
-        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
-        self.depth = depth = self._depth_arg(depth)
-        self.w = w = Words()
-        self.old_p, self.old_s = (w.c.private(8 * length) for _ in range(2))
-        self.siblings_p = [w.private(8) for _ in range(depth)]
-        self.siblings_s = [w.private(8) for _ in range(depth)]
-        self.dirs_p = w.c.private(depth)
-        self.dirs_s = w.c.private(depth)
+        self.old_p, self.old_s = self._open(key_bytes, length, depth, 2)
+        w, K = self.w, self.key_bytes
         self.new_p = self.old_p[: 8 * K] + self.old_s[8 * K: 16 * K] + self.old_p[16 * K:]
-        chains = [_message_chain(w, rec, length) for rec in (self.old_p, self.new_p, self.old_s)]
+        chains = [_message_chain(w, rec, self.length) for rec in (self.old_p, self.new_p, self.old_s)]
         self.blocks = chains[0][1]
-        self.inert_leaf = [w.const(v) for v in be_words(hashlib.sha256(bytes(length)).digest())]  # the all-zero record's leaf
-        leaves = [leaf for leaf, _ in chains] + [self.inert_leaf]
-        tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
-        self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for leaf, (sibs, dirs) in zip(leaves, tails))
-        self.joined = bool(joined)
-        self.old_root = [w.output(x) for x in self.out_old]
-        if not self.joined:  # every chain top is public: X_p, X_p', X_s, X_s'
-            self.top_mid_p = [w.output(x) for x in self.mid_p]
-            self.top_mid_s = [w.output(x) for x in self.mid_s]
-        self.new_root = [w.output(x) for x in self.out_new]
-        self.key = w.c.public(8 * K)
-        if self.joined:
-            for x, y in zip(self.mid_p, self.mid_s):  # the private intermediate root
-                w.assert_same_u32(x, y)
+        self.inert_leaf = [w.const(v) for v in be_words(hashlib.sha256(bytes(self.length)).digest())]  # the all-zero record's leaf
+        self._close([leaf for leaf, _ in chains] + [self.inert_leaf], joined)
         for a, b in zip(self.key, self.old_p[8 * K: 16 * K]):
             w.c.assert_same(a, b)
         for a, b in zip(self.key, self.old_s[: 8 * K]):
@@ -1046,43 +1053,11 @@ class MerkleRemove(_TwoRoots):
         w.c.assert_equal(w.less_than(lo_p, k), 1)
         w.c.assert_equal(w.less_than(k, hi_s), 1)
 
-    @property
-    def lu(self) -> int:
-        return (512 if self.joined else 1024) + 8 * self.key_bytes
-
-    def _query(self, key) -> bytes:
-        key = bytes(key)
-        if len(key) != self.key_bytes:
-            raise CircuitError(f"MerkleRemove: the key is {self.key_bytes} bytes")
-        if _is_sentinel(key):
-            raise CircuitError("MerkleRemove: the all-zero and the all-0xFF key are sentinels, never members")
-        return key
-
     def bits(self, key: bytes, old_p: bytes, old_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
         """one statement's input bits, public then private: 512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits,
         the two records' bits, p's siblings and s's (those from the tree after p's update) as big-endian words, then the direction bits of p and of s.  (A
         witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
-        who = "MerkleRemove"
-        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
-        tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
-        nsib = 256 * self.depth
-        return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, old_p, old_s, what="the records are"), tail_p[:nsib],
-                           tail_s[:nsib], tail_p[nsib:], tail_s[nsib:])
-
-    def statement(self, *tops_and_key) -> bytes:
-        """statement(old_root, new_root, key): the 64 + key_bytes statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "removing
-        `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 + key_bytes
-        bytes: "removing `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
-        *tops, key = tops_and_key
-        if len(tops) != (2 if self.joined else 4):
-            raise CircuitError("MerkleRemove: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
-        return b"".join(_statement_of(x, "MerkleRemove: a top") for x in tops) + self._query(key)
-
-    def tops_of(self, witness_row):
-        """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
-        if self.joined:
-            raise CircuitError("MerkleRemove: tops_of is for joined=False (roots_of reads the two roots)")
-        return tuple(_digest_from_row(witness_row, at) for at in (0, 256, 512, 768))
+        return self._step_bits(key, (old_p, old_s), siblings_p, index_p, siblings_s, index_s)
 
 
 def _keys_array(keys, who: str):

@@ -1,5 +1,5 @@
 // The host side of mfh_merkle_insert_keys (csrc/merkle_insert.hpp: predecessor, successor and the 2 nk update indices of a batch of sequential key inserts;
-// csrc/merkle_rows.hpp: the insert row's size, its splice and the chunk of whole inserts) as a program of its own (tests/test_merkle_insert_host_cpu.py
+// csrc/merkle_rows.hpp: the key step's row size with three records, its splice and the chunk of whole steps) as a program of its own (tests/test_merkle_insert_host_cpu.py
 // builds it with the address and undefined-behaviour sanitizers and runs it).  Every line of standard input is
 //   <key_bytes> <nk> <mode> <extra> <seed>
 // A set of random non-sentinel keys is split into members and the batch -- mode 0, 1, 2: the batch is a run of neighbours in key order, so every key falls
@@ -12,7 +12,7 @@
 //                batch and the keys alone) are the model's two new records of insert j
 //   the splice   (length = 2 key_bytes + extra) at depth 1 + seed % 24, 3 and 4 -- 2 depth is and is not a multiple of 8 -- two rows at in_stride = row bytes +
 //                extra out of heap arrays of exactly the bytes the splice may read, the rest of the output untouched, the index bits set one by one
-//   the chunk    insert_chunk is even, at least 2, at most 2 nk, and twice the inserts whose rows fit, whatever the stage
+//   the chunk    pair_chunk is even, at least 2, at most 2 nk, and twice the inserts whose rows fit, whatever the stage
 // Prints "ok <key_bytes> <nk> <mode> <distinct located records> <row bytes>".
 #include <stdint.h>
 #include <stdio.h>
@@ -156,7 +156,7 @@ int main() {
     const size_t hp = mf::record_head_pitch(length);
     size_t rowb_seed = 0;
     for (uint32_t depth : {1 + (uint32_t)(seed % 24), 3u, 4u}) {
-      const size_t idxb = (2 * depth + 7) / 8, rowb = mf::insert_row_bytes(kb, length, depth), in_stride = rowb + extra;
+      const size_t idxb = (2 * depth + 7) / 8, rowb = mf::pair_row_bytes(kb, 3, length, depth), in_stride = rowb + extra;
       if (!rowb_seed) rowb_seed = rowb;
       CHECK(rowb == 64 + (size_t)kb + 3 * (size_t)length + 64 * (size_t)depth + idxb && hp % 16 == 0 && hp >= length && hp < (size_t)length + 16, "the sizes differ");
       const unsigned nr = nk < 2 ? nk : 2;
@@ -185,7 +185,7 @@ int main() {
           if ((s >> l) & 1) w[at + (depth + l) / 8] |= (uint8_t)(1u << ((depth + l) % 8));
         }
         CHECK(at + idxb == rowb, "the row's size");
-        mf::splice_insert_row(out + k * in_stride, keys + k * stride, kb, head_p, head_s, hp, length, staged_p, staged_s, depth, p, s);
+        mf::splice_pair_row(out + k * in_stride, 64, {{keys + k * stride, kb}, {head_p, length}, {head_s, length}, {head_s + hp, length}}, staged_p, staged_s, depth, p, s);
       }
       const bool same = !memcmp(out, want, out_bytes);
       free(head_p); free(head_s); free(staged_p); free(staged_s); free(out); free(want);
@@ -194,7 +194,7 @@ int main() {
     // the chunk of whole inserts
     if (nk) {
       for (size_t stage : {(size_t)1, rowb_seed - 1, rowb_seed, 2 * rowb_seed + 1, (size_t)nk * rowb_seed - 1, (size_t)nk * rowb_seed, (size_t)64 << 20}) {
-        const uint32_t ch = mf::insert_chunk(nk, rowb_seed, stage);
+        const uint32_t ch = mf::pair_chunk(nk, rowb_seed, stage);
         const size_t fit = stage / rowb_seed, want = fit < 1 ? 1 : fit < nk ? fit : nk;
         CHECK(ch % 2 == 0 && ch >= 2 && ch <= 2 * nk && ch == 2 * want, "the chunk is not whole inserts");
       }

@@ -1,5 +1,5 @@
 // The host side of mfh_merkle_remove_keys (csrc/merkle_remove.hpp: the slot whose hi changes, the hi it receives and the 2 nk update indices of a batch of
-// sequential key removes; csrc/merkle_rows.hpp: the remove row's size and its splice) as a program of its own (tests/test_merkle_remove_host_cpu.py builds
+// sequential key removes; csrc/merkle_rows.hpp: the key step's row size with two records and its splice) as a program of its own (tests/test_merkle_remove_host_cpu.py builds
 // it with the address and undefined-behaviour sanitizers and runs it).  Every line of standard input is
 //   <key_bytes> <nk> <mode> <extra> <seed>
 // A set of random non-sentinel keys makes a well-formed indexed table in shuffled positions, its inert slots all zero, lo == hi or lo > hi.  The batches:
@@ -205,9 +205,9 @@ int main() {
     for (unsigned b = 0; b < kb; b++) key[b] = rnd();
     for (uint32_t depth : {1 + (uint32_t)(seed % 24), 3u, 4u})
       for (size_t zeros : {(size_t)64, (size_t)128}) {
-        const size_t idxb = (2 * depth + 7) / 8, rowb = mf::remove_row_bytes(kb, length, depth, zeros), in_stride = rowb + extra;
+        const size_t idxb = (2 * depth + 7) / 8, rowb = mf::pair_row_bytes(kb, 2, length, depth, zeros), in_stride = rowb + extra;
         if (!rowb_seed) rowb_seed = rowb;
-        CHECK(rowb == zeros + (size_t)kb + 2 * (size_t)length + 64 * (size_t)depth + idxb && mf::remove_row_bytes(kb, length, depth) == rowb - zeros + 64, "the sizes differ");
+        CHECK(rowb == zeros + (size_t)kb + 2 * (size_t)length + 64 * (size_t)depth + idxb && mf::pair_row_bytes(kb, 2, length, depth) == rowb - zeros + 64, "the sizes differ");
         const unsigned nr = 2;
         const size_t out_bytes = (size_t)(nr - 1) * in_stride + rowb, staged_bytes = 128 + (size_t)32 * depth;
         uint8_t *head_p = exact(length), *head_s = exact(length), *staged_p = exact(staged_bytes), *staged_s = exact(staged_bytes), *out = exact(out_bytes), *want = exact(out_bytes);
@@ -233,11 +233,7 @@ int main() {
             if ((s >> l) & 1) w[at + (depth + l) / 8] |= (uint8_t)(1u << ((depth + l) % 8));
           }
           CHECK(at + idxb == rowb, "the row's size");
-          if (zeros == 64 && k == 0) {
-            mf::splice_remove_row(out + k * in_stride, k_exact, kb, head_p, head_s, length, staged_p, staged_s, depth, p, s);  // (the default: 64)
-          } else {
-            mf::splice_remove_row(out + k * in_stride, k_exact, kb, head_p, head_s, length, staged_p, staged_s, depth, p, s, zeros);
-          }
+          mf::splice_pair_row(out + k * in_stride, zeros, {{k_exact, kb}, {head_p, length}, {head_s, length}}, staged_p, staged_s, depth, p, s);
         }
         const bool same = !memcmp(out, want, out_bytes);
         free(head_p); free(head_s); free(staged_p); free(staged_s); free(out); free(want); free(k_exact);

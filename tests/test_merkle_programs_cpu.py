@@ -12,7 +12,8 @@ import c_lwe_snarks_amd as mf
 from c_lwe_snarks_amd import words as W
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "merkle_programs.json")
-P18 = mf.Params(d=1 << 18, m=174762)  # the largest below, MerkleRecordUpdate(8, 1), is 199 735 rows
+P18 = mf.Params(d=1 << 18, m=174762)  # the largest of the older statements, MerkleRecordUpdate(8, 1), is 199 735 rows
+P19 = mf.Params(d=1 << 19, m=349525)  # the key steps and MerkleSegment: MerkleInsert(4, 8, 1, joined=False) is 399 885 rows
 
 STATEMENTS = {
     "MerklePath(1)": lambda: W.MerklePath(1),
@@ -27,10 +28,19 @@ STATEMENTS = {
     "Sha256Message(0)": lambda: W.Sha256Message(0),
     "Sha256Message(56)": lambda: W.Sha256Message(56),
 }
+# compiled against P19; the entries above stay on P18, so their digests do not move
+STATEMENTS_P19 = {
+    "MerkleInsert(4, 8, 1)": lambda: W.MerkleInsert(4, 8, 1),
+    "MerkleInsert(4, 8, 1, joined=False)": lambda: W.MerkleInsert(4, 8, 1, joined=False),
+    "MerkleRemove(4, 8, 1)": lambda: W.MerkleRemove(4, 8, 1),
+    "MerkleRemove(5, 11, 1, joined=False)": lambda: W.MerkleRemove(5, 11, 1, joined=False),
+    "MerkleSegment(2)": lambda: W.MerkleSegment(2),
+}
+STATEMENTS.update(STATEMENTS_P19)
 
 
-def program_digest(statement) -> str:
-    cc = statement.circuit.compile(P18)
+def program_digest(statement, params=P18) -> str:
+    cc = statement.circuit.compile(params)
     h = hashlib.sha256(f"nrows {cc.nrows} nwires {cc.nwires} lu {cc.lu} statement lu {statement.lu}".encode())
     arrays = dict(zip(("row_ptr", "wire", "coef"), cc.rows), gates=cc.gates, asserts=cc.asserts, program=cc.program, equal=cc.equal, outputs=cc.outputs,
                   terms=cc.terms, wires=np.array(cc.wires, dtype=np.uint32))
@@ -41,7 +51,7 @@ def program_digest(statement) -> str:
 
 
 def program_digests():
-    return {name: program_digest(make()) for name, make in STATEMENTS.items()}
+    return {name: program_digest(make(), P19 if name in STATEMENTS_P19 else P18) for name, make in STATEMENTS.items()}
 
 
 def test_compiled_programs_are_the_recorded_ones():
