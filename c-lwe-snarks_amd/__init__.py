@@ -103,7 +103,7 @@ EXPORTS = [
     "mfh_merkle_create", "mfh_merkle_destroy", "mfh_merkle_set_leaves", "mfh_merkle_root", "mfh_merkle_nodes", "mfh_merkle_paths",
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
-    "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut",
+    "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
 ]
 
 
@@ -248,6 +248,8 @@ def load_library():
         "mfh_merkle_insert_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_remove_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, vp, sz, vp, vp, vp]),
         "mfh_merkle_remove_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_transfer_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, vp, sz, vp, vp, vp]),
+        "mfh_merkle_transfer_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, u32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -546,19 +548,36 @@ class MerkleTree:
         """the bytes in front of the two tails in the row of a key step with nrec records: the zeros where the tops are computed, the key, the records"""
         return zeros + np.ascontiguousarray(keys).shape[1] + nrec * int(table.shape[1])
 
-    def _key_steps(self, who, step, table, keys, payloads=None, roots=False, cut=False, cuts=None):
-        """the body of insert_keys, remove_keys and, with cut=True, their *_segments forms (whatever `cuts` is then, _cut judges it): mfh_merkle_<step>_keys[_cut] with the rows of a statement of three
-        (insert) or two (remove) records, index, status and roots allocated here.  Uncut: (rows, index) and with roots=True the nk + 1 roots; cut: (rows,
-        nodes_p, nodes_s, index), from the 2 nk + 1 roots"""
+    def _key_steps(self, who, step, table, keys, payloads=None, roots=False, cut=False, cuts=None, transfer=None):
+        """the body of insert_keys, remove_keys, transfer_keys and, with cut=True, their *_segments forms (whatever `cuts` is then, _cut judges it): mfh_merkle_<step>_keys[_cut] with the rows of a statement of three
+        (insert) or two (remove, transfer) records, index, status and roots allocated here.  Uncut: (rows, index) and with roots=True the nk + 1 roots; cut: (rows,
+        nodes_p, nodes_s, index), from the 2 nk + 1 roots.  transfer = (to_keys, amounts, amount_bytes): `keys` are then the senders'"""
         c = self._ctx
         tab, tstride, length, k = self._keys(table, keys, who)
         nk, kb = k.shape
         vp = ctypes.c_void_p
-        nrec, extra = 2, ()
+        nrec, extra, more = 2, (), 0
+        keys_args = (kb, nk, vp(k.ctypes.data), kb)
         if step == "insert":
             pay = self._payloads(payloads, nk, length - 2 * kb, who)
             nrec, extra = 3, (vp(pay.ctypes.data) if pay is not None else None, length - 2 * kb)
-        head = self._step_head(table, keys, nrec, 128 if cut else 64)
+        if step == "transfer":
+            to, amounts, ab = transfer
+            to = np.ascontiguousarray(to)
+            if to.dtype != np.uint8 or to.shape != k.shape:
+                raise MfhError(f"{who}: from_keys and to_keys are uint8 [nk, key_bytes], one pair a transfer")
+            if not isinstance(ab, (int, np.integer)) or not 1 <= ab <= 8 or length < 2 * kb + ab:
+                raise MfhError(f"{who}: 1 <= amount_bytes <= 8 and 2 key_bytes + amount_bytes <= length")
+            try:
+                values = [int(a) for a in amounts]
+            except (TypeError, ValueError):
+                values = None
+            if values is None or len(values) != nk or any(not 0 <= a < 1 << 64 for a in values):
+                raise MfhError(f"{who}: amounts are nk integers in [0, 2^64), one a transfer")
+            amt = np.array(values, dtype=np.uint64).reshape(nk)
+            more = kb + int(ab)  # the row has k_from | k_to | the amount where the other steps' rows have the key
+            keys_args = (kb, int(ab), nk, vp(k.ctypes.data), vp(to.ctypes.data), kb, vp(amt.ctypes.data))
+        head = self._step_head(table, keys, nrec, 128 if cut else 64) + more
         if not cut:
             rows = np.zeros((nk, head + 64 * self.depth + (2 * self.depth + 7) // 8), dtype=np.uint8)
             out = (vp(rows.ctypes.data), rows.shape[1])
@@ -569,7 +588,7 @@ class MerkleTree:
         index = np.zeros((nk, 2), dtype=np.uint32)
         status = np.zeros(nk, dtype=np.uint8)
         call = getattr(c.lib, f"mfh_merkle_{step}_keys" + ("_cut" if cut else ""))
-        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, nk, vp(k.ctypes.data), kb, *extra, *out, vp(r.ctypes.data) if r is not None else None,
+        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, *keys_args, *extra, *out, vp(r.ctypes.data) if r is not None else None,
                     vp(index.ctypes.data), vp(status.ctypes.data)))
         if nk:
             self._keep = []  # (the call waited for the stream)
@@ -762,6 +781,41 @@ class MerkleTree:
         """remove_key_segments with every segment's rows as 0 / 1 arrays"""
         out = self.remove_key_segments(table, keys, cuts)
         head = self._step_head(table, keys, 2, 128)
+        return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
+
+    # ---- transfers: a ledger on the indexed table, a balance in the payload
+    def transfer_keys(self, table, from_keys, to_keys, amounts, amount_bytes=8, roots=False):
+        """(rows, index): nk sequential transfers between the accounts of an INDEXED table whose records carry a balance (words.MerkleTransfer has the data
+        model: bytes [2 key_bytes, 2 key_bytes + amount_bytes) of a record, big-endian) and this tree in one call (mfh_merkle_transfer_keys; waits for the
+        stream).  Transfer j takes amounts[j] from the record whose own key is from_keys[j] and adds it to the record whose own key is to_keys[j]; an account
+        may occur in any number of steps and may spend what an earlier step of the batch delivered.  rows is np.uint8 [nk, 64 + 2 key_bytes + amount_bytes +
+        2 length + 64 depth + ceil(2 depth / 8)]: row j is the packed input row of words.MerkleTransfer(key_bytes, length, depth, amount_bytes) taken from
+        table and tree as they stood before transfer j.  index is np.uint32 [nk, 2]: (the sender's slot, the receiver's).  With roots=True a triple whose last
+        element is np.uint8 [nk + 1, 32], the roots R_0 .. R_nk: statement j is MerkleTransfer.statement(R_j, R_j+1, from_keys[j], to_keys[j], amounts[j]).
+        table: under update_records' rules, MODIFIED IN PLACE.  from_keys, to_keys: np.uint8 [nk, key_bytes] under locate_keys' rules, from_keys[j] !=
+        to_keys[j].  amounts: nk integers below 2^(8 amount_bytes).  MfhError with the library's text, table and tree untouched, when a sender or a receiver
+        is not a member, a step overdraws its sender or takes its receiver past 2^(8 amount_bytes) - 1."""
+        return self._key_steps("transfer_keys", "transfer", table, from_keys, roots=roots, transfer=(to_keys, amounts, amount_bytes))
+
+    def transfer_bits(self, table, from_keys, to_keys, amounts, amount_bytes=8, roots=False):
+        """transfer_keys with the rows as np.uint8 [nk, 512 + 16 key_bytes + 8 amount_bytes + 16 length + 514 depth] of 0 / 1: what
+        Context.circuit_assign(prog, bits) takes for words.MerkleTransfer(key_bytes, length, depth, amount_bytes)"""
+        head = self._step_head(table, from_keys, 2, 64) + np.ascontiguousarray(from_keys).shape[1] + int(amount_bytes)
+        return self._key_step_bits(self.transfer_keys(table, from_keys, to_keys, amounts, amount_bytes, roots), head)
+
+    def transfer_key_segments(self, table, from_keys, to_keys, amounts, cuts, amount_bytes=8):
+        """transfer_keys with the path cut at levels `cuts` (mfh_merkle_transfer_keys_cut).  Returns (rows, nodes_p, nodes_s, index): rows[0][j] is the packed
+        input row of words.MerkleTransfer(key_bytes, length, c_0, amount_bytes, joined=False) of transfer j; rows[g], g >= 1, holds one words.MerkleSegment
+        row per UPDATE, row 2 j that of p's update of transfer j and row 2 j + 1 that of s's; nodes_p and nodes_s are np.uint8 [nk, G + 1, 2, 32], the
+        published pairs of the two updates: segment 0's statement is statement(*nodes_p[j, 0], *nodes_s[j, 0], from_keys[j], to_keys[j], amounts[j]), the
+        upper ones MerkleSegment.chain(nodes_p[j]) and chain(nodes_s[j]), and nodes_p[j, G, 1] == nodes_s[j, G, 0] is the root between the two updates,
+        which becomes public.  index as transfer_keys gives it."""
+        return self._key_steps("transfer_key_segments", "transfer", table, from_keys, cut=True, cuts=cuts, transfer=(to_keys, amounts, amount_bytes))
+
+    def transfer_key_segment_bits(self, table, from_keys, to_keys, amounts, cuts, amount_bytes=8):
+        """transfer_key_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.transfer_key_segments(table, from_keys, to_keys, amounts, cuts, amount_bytes)
+        head = self._step_head(table, from_keys, 2, 128) + np.ascontiguousarray(from_keys).shape[1] + int(amount_bytes)
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
 
 

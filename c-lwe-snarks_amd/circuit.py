@@ -207,6 +207,19 @@ class Circuit:
         self._pub.append(w.node)
         return w
 
+    def public_last(self, wires):
+        """move the public input wires `wires`, in the order given, behind every public wire declared so far.  Public wires are laid out in declaration
+        order, and a gate reads only wires made before it: an input that the computed outputs depend on is declared early, and this puts it behind
+        the outputs in the statement all the same.  It changes the layout alone, no node."""
+        wires = list(wires)
+        nodes = [w.node for w in wires]
+        for w in wires:
+            self._check(w)
+        if len(set(nodes)) != len(nodes) or any(self._nodes[n][0] != "pub" for n in nodes):
+            raise CircuitError("public_last: distinct public input wires of this circuit")
+        moved = set(nodes)
+        self._pub = [n for n in self._pub if n not in moved] + nodes
+
     def output(self, w: Wire) -> Wire:
         """a public wire whose value is defined as that of wire w (a computed public output): a public input in the wire layout, one equality row
         1 - p - w, and a pair in Compiled.outputs.  The returned wire only names the position in the statement: nothing may read it."""

@@ -28,7 +28,9 @@
 // as above, the lowest inert slots found on the device, then the steps below (the host's plan: merkle_insert.hpp).
 // k_key_owners: mfh_merkle_remove_keys, a batch of sequential key removes from an indexed table in one call -- every key's own record and predecessor found in
 // one pass, then the steps below (the host's plan: merkle_remove.hpp).
-// k_insert_records, k_remove_records: what a batch of key steps (inserts, removes) ends with -- all 2 nk new records built in one launch from the step's plan,
+// k_balance_gather: mfh_merkle_transfer_keys, a batch of sequential transfers between the accounts of an indexed table in one call -- the keys located as above,
+// the located records' balances read behind the search, then the steps below (the host's plan: merkle_transfer.hpp).
+// k_insert_records, k_remove_records, k_transfer_records: what a batch of key steps ends with -- all 2 nk new records built in one launch from the step's plan,
 // then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
 // (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
@@ -45,6 +47,7 @@
 #include "merkle_remove.hpp"
 #include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
+#include "merkle_transfer.hpp"
 #include "sha256_dev.hpp"
 
 namespace {
@@ -626,6 +629,55 @@ __global__ __launch_bounds__(256) void k_remove_records(const uint8_t *__restric
   fresh[g] = out;
 }
 
+// ---- mfh_merkle_transfer_keys: the balances of a batch's accounts before the batch, and the 2 nk new records of the batch.  A record's balance is its bytes
+// [2K, 2K + A), an unsigned big-endian integer, A = amount_bytes in [1, 8] (merkle_transfer.hpp).
+//
+// k_balance_gather, ONE launch per call behind k_key_locate on the same stream, one thread per UNIQUE key u < nu: present[u] is the search's result word on the
+// device, the record whose own key is key u (0xFFFFFFFF: not a member).  The A balance bytes come through load_unit_within -- any alignment of the table, any
+// stride, the field anywhere across a 16-byte unit; nothing outside the table's span is read -- and balance[u] <- their value as one uint64, 0 for a key that
+// is not a member (or a record index that is not below n, which the search never leaves).
+__global__ __launch_bounds__(256) void k_balance_gather(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t amount_bytes,
+                                                        uint32_t n, const uint32_t *__restrict__ present, uint32_t nu, unsigned long long *__restrict__ balance) {
+  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= nu) return;
+  const uint32_t rec = present[u];
+  unsigned long long value = 0;
+  if (rec < n) {
+    const int64_t a = (int64_t)((size_t)rec * stride) + 2 * (int64_t)key_bytes;
+    const uint4 v = load_unit_within(table, a, a + amount_bytes, span);
+    const unsigned long long be = (unsigned long long)__builtin_bswap32(v.x) << 32 | __builtin_bswap32(v.y);  // byte 0 in the top 8 bits
+    value = be >> (8 * (8 - amount_bytes));  // (the bytes at and past A, unspecified, leave here)
+  }
+  balance[u] = value;
+}
+
+// k_transfer_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
+// aligned).  One item per record r and 16-byte unit u; the store is the whole unit.  With (p, s, spare) = plan[3 j ..] of transfer j (merkle_transfer.hpp):
+//   record 2 j      the table's record p as it stood before the batch, with bytes [2K, 2K + A) <- the sender's new balance, bal[2 j A ..]
+//   record 2 j + 1  the table's record s, with those bytes <- the receiver's new balance, bal[(2 j + 1) A ..]
+// The new balances are the host's (the plan's running balances, big-endian), and a transfer changes nothing else of a record, so every source is the table as
+// it stood BEFORE the batch or the uploaded balances -- one launch, no ordering among the items, and the table is only read, even where an account occurs in
+// many steps.  K and A are any, the table sits at any byte alignment, so a unit may straddle the three ranges anywhere: as in k_insert_records,
+// load_unit_within fetches the 16 bytes of a source that line up with the unit and merge_unit takes each range's bytes under per-dword byte masks.  Bytes at
+// or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [bal, bal + 2 nk A) and the plan.
+__global__ __launch_bounds__(256) void k_transfer_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ bal,
+                                                          const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t nk,
+                                                          uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (2 nk units < 2^32: checked by the host)
+  if (g >= 2 * nk * units) return;
+  const uint32_t r = g / units, u = g - r * units;
+  const int64_t o = 16 * (int64_t)u, f0 = 2 * (int64_t)key_bytes, f1 = f0 + amount_bytes, bal_span = (int64_t)2 * nk * amount_bytes;
+  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[3 * (r >> 1) + (r & 1)] * table_stride);
+  const uint4 v = load_unit_within(table, rec + o, rec + min(o + 16, (int64_t)length), table_span);  // the keys and the payload behind the balance
+  uint4 out = merge_unit(merge_unit(make_uint4(0, 0, 0, 0), v, o, 0, f0), v, o, f1, length);
+  if (o < f1 && o + 16 > f0) {  // the balance
+    const int64_t at = (int64_t)r * amount_bytes - f0;  // the record's byte x is bal's byte at + x
+    out = merge_unit(out, load_unit_within(bal, at + o, at + min(o + 16, f1), bal_span), o, f0, f1);
+  }
+  fresh[g] = out;
+}
+
 }  // namespace
 
 struct mfh_merkle {
@@ -1128,8 +1180,9 @@ struct KeyCall {
 
 // what the three key calls ask of their arguments, in the order each call has always checked them; empty when they are fine.  `noun`: the call's "queries",
 // "inserts" or "removes".  `own`: the caller's checks of what only it has (the strides of payloads and rows, the cuts), whose place is between the keys' shape
-// and the pointers.  `steps`: a batch of key steps, which builds 2 nk records and needs as many slots as keys
-std::string keys_refused(const KeyCall &k, uint32_t depth, const char *noun, bool steps, const std::function<const char *()> &own) {
+// and the pointers.  `steps`: a batch of key steps, which builds 2 nk records and, its keys being `distinct` (all but the transfers', whose accounts repeat),
+// needs as many slots as keys
+std::string keys_refused(const KeyCall &k, uint32_t depth, const char *noun, bool steps, const std::function<const char *()> &own, bool distinct = true) {
   if (k.key_bytes < 1 || k.key_bytes > mf::kMaxKeyBytes) return "key_bytes must be in [1, 32]";
   if (k.length < 2 * k.key_bytes) return "length shorter than the two keys' 2 key_bytes bytes";  // (at most 64: never also above 2^20)
   if (const char *what = records_refused(nullptr, k.table_stride, k.length, 0, "table_stride shorter than length")) return what;
@@ -1138,7 +1191,7 @@ std::string keys_refused(const KeyCall &k, uint32_t depth, const char *noun, boo
   const std::pair<const void *, const char *> needed[] = {{k.d_table, "d_table"}, {k.h_keys, "h_keys"}, {k.h_index, "h_index"}, {k.h_status, "h_status"}};
   for (const auto &p : needed)
     if (k.nk && !p.first) return std::string(noun) + " without " + p.second;
-  if (steps && k.nk > 1u << depth) return std::string("more ") + noun + " than the table has slots";
+  if (steps && distinct && k.nk > 1u << depth) return std::string("more ") + noun + " than the table has slots";
   if (steps && (uint64_t)2 * k.nk * ((k.length + 15) / 16) >> 32) return "the batch's 2 nk new records exceed 2^32 units of 16 bytes";
   for (uint32_t j = 0; j < k.nk; j++)
     if (mf::key_is_sentinel(k.key(j), k.key_bytes)) return std::string(steps ? "a key" : "a query") + " is the all-zero or the all-0xFF key";
@@ -1167,9 +1220,20 @@ using KeyKernel = void (*)(const uint8_t *, size_t, int64_t, uint32_t, uint32_t,
 
 size_t key_search_bytes(uint32_t nu, uint32_t key_bytes) { return (size_t)nu * (mf::key_words(key_bytes) + 2) * 4; }
 
+// An optional second kernel behind the search, on the same stream and under the same wait: launch(d_res, d_out) reads the search's 2 nu result words on the
+// device and writes `bytes` bytes at d_out = d_work + key_search_bytes rounded up to 16 (the caller reserves both); they come back behind the results, at
+// *res + 2 nu words.  A call without one queues and waits for exactly what it always has
+struct SearchTail {
+  size_t bytes;
+  std::function<void(const uint32_t *d_res, uint8_t *d_out)> launch;
+};
+
+size_t key_search_tail_at(uint32_t nu, uint32_t key_bytes) { return (key_search_bytes(nu, key_bytes) + 15) & ~(size_t)15; }
+
 // At d_work (key_search_bytes, reserved by the caller): the keys' words | 2 nu result words, all 0xFF before the launch.  *res <- the results in pin_cw with the
 // stream idle: good until pin_cw is next acquired
-int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch which, uint32_t depth, uint8_t *d_work, const uint32_t **res) {
+int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch which, uint32_t depth, uint8_t *d_work, const uint32_t **res,
+               const SearchTail *tail = nullptr) {
   const uint32_t nu = keys.nu, kw = mf::key_words(k.key_bytes), n = 1u << depth;
   const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
   uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nu * kw;
@@ -1187,9 +1251,15 @@ int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch 
                        d_res + nu);
   }
   HIP_TRY(c, hipGetLastError());
-  uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes);
+  uint8_t *d_tail = tail ? d_work + key_search_tail_at(nu, k.key_bytes) : nullptr;
+  if (tail) {
+    tail->launch(d_res, d_tail);
+    HIP_TRY(c, hipGetLastError());
+  }
+  uint32_t *pin_res = (uint32_t *)pin_acquire(c, c->pin_cw, res_bytes + (tail ? tail->bytes : 0));
   if (!pin_res) return MFH_ENOMEM;
   HIP_TRY(c, hipMemcpyAsync(pin_res, d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (tail) HIP_TRY(c, hipMemcpyAsync(pin_res + (size_t)2 * nu, d_tail, tail->bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *res = pin_res;
   return MFH_OK;
@@ -1244,7 +1314,7 @@ int pair_updates(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, 
     pin_release(c, c->pin_rows);
   }
   {
-    Timer tm(c, build_kind, nupd);  // "merkle_insert_records" or "merkle_remove_records" (mfhip.hip: timing_kind)
+    Timer tm(c, build_kind, nupd);  // "merkle_insert_records", "merkle_remove_records" or "merkle_transfer_records" (mfhip.hip: timing_kind)
     const uint64_t items = (uint64_t)nupd * (hp / 16);
     build(dim3((uint32_t)((items + 255) / 256)), (const int32_t *)d_plan, d_keys, d_pay, reinterpret_cast<uint4 *>(d_fresh));
   }
@@ -1455,9 +1525,117 @@ int remove_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table) {
   });
 }
 
+// mfh_merkle_transfer_keys (k.cuts = null: one row of the whole depth a transfer, nk + 1 roots) and mfh_merkle_transfer_keys_cut (segment 0's row a transfer to
+// cuts->h_rows[0] = k.h_inputs, the upper segments' rows an UPDATE, 2 nk + 1 roots).  k.h_keys are the senders' keys, h_to the receivers' at the same stride
+int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const uint8_t *h_to, const uint64_t *h_amounts, uint32_t amount_bytes) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes, A = amount_bytes;  // d0: the levels of the transfer's own row
+  const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(2 * K + A, 2, length, d0, zeros);
+  const std::string what = keys_refused(k, depth, "transfers", true, [&]() -> const char * {
+    if (A < 1 || A > mf::kMaxAmountBytes) return "amount_bytes must be in [1, 8]";
+    if (length < 2 * K + A) return "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes";
+    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + 2 key_bytes + amount_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
+  }, false);  // (2 nk below 2^32 by the check of the new records' units)
+  if (!what.empty()) return fail(c, k.who, what.c_str());
+  if (nk && (!h_to || !h_amounts)) return fail(c, k.who, !h_to ? "transfers without h_to" : "transfers without h_amounts");
+  for (uint32_t j = 0; j < nk; j++) {
+    const uint8_t *to = h_to + (size_t)j * k.key_stride;
+    if (mf::key_is_sentinel(to, K)) return fail(c, k.who, "a key is the all-zero or the all-0xFF key");
+    if (!memcmp(k.key(j), to, K)) return fail(c, k.who, "a transfer from an account to itself");
+    if (h_amounts[j] > mf::balance_limit(A)) return fail(c, k.who, "an amount does not fit amount_bytes bytes");
+  }
+  if (!nk) return MFH_OK;
+  // the accounts: the unique keys of all 2 nk senders and receivers.  A key may occur in many steps
+  std::vector<uint8_t> both((size_t)2 * nk * K), amounts((size_t)nk * A);
+  for (uint32_t j = 0; j < nk; j++) {
+    memcpy(both.data() + (size_t)2 * j * K, k.key(j), K);
+    memcpy(both.data() + ((size_t)2 * j + 1) * K, h_to + (size_t)j * k.key_stride, K);
+    mf::balance_bytes(h_amounts[j], A, amounts.data() + (size_t)j * A);
+  }
+  mf::KeyPlan keys;
+  mf::keys_prepare(both.data(), K, K, 2 * nk, keys);
+  const uint32_t nu = keys.nu, n = 1u << depth;
+  HIP_TRY(c, hipSetDevice(c->device));
+  PairScratch s;  // behind the batch's front: the search and the nu balances behind it, then update_rows' scratch
+  if (int rc = pair_reserve(c, k, depth, rowb, 2 * A, key_search_tail_at(nu, K) + (size_t)nu * 8, s)) return rc;
+  std::vector<uint32_t> rec(nu), from(nk), to(nk);
+  std::vector<uint64_t> balance(nu);
+  {  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
+    const SearchTail gather{(size_t)nu * 8, [&](const uint32_t *d_res, uint8_t *d_out) {
+      Timer tm(c, 37, nu);  // "merkle_balances" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_balance_gather, dim3((nu + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), K, A, n, d_res + nu, nu,
+                         reinterpret_cast<unsigned long long *>(d_out));
+    }};
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + s.skip, &res, &gather)) return rc;
+    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
+    memcpy(balance.data(), res + (size_t)2 * nu, (size_t)nu * 8);
+  }
+  // b. the plan: the running balance of every account through the steps in order -- (p, s) and the two new balances of every transfer, its status
+  for (uint32_t j = 0; j < nk; j++) {
+    from[j] = keys.slot[2 * (size_t)j];
+    to[j] = keys.slot[2 * (size_t)j + 1];
+  }
+  mf::TransferPlan plan;
+  mf::transfer_plan(nk, from.data(), to.data(), h_amounts, A, rec.data(), balance.data(), plan);
+  uint32_t first = nk;
+  for (uint32_t j = 0; j < nk; j++) {
+    k.h_index[2 * (size_t)j] = plan.idx[2 * (size_t)j];
+    k.h_index[2 * (size_t)j + 1] = plan.idx[2 * (size_t)j + 1];
+    k.h_status[j] = plan.status[j];
+    if (plan.status[j] && first == nk) first = j;
+  }
+  if (first != nk) {
+    static const char *const why[] = {"", "a sender is not a member of the set (h_status 1)", "a receiver is not a member of the set (h_status 2)",
+                                      "a transfer overdraws its sender's balance at that step (h_status 3)",
+                                      "a transfer takes its receiver's balance past 2^(8 amount_bytes) - 1 (h_status 4)"};
+    return fail(c, k.who, why[plan.status[first]]);
+  }
+  // what k_transfer_records reads: (p, s, spare) a transfer, and in the payloads' place the two new balances, A big-endian bytes each
+  std::vector<int32_t> words((size_t)3 * nk);
+  std::vector<uint8_t> fresh((size_t)2 * nk * A);
+  for (uint32_t j = 0; j < nk; j++) {
+    words[3 * (size_t)j] = (int32_t)plan.idx[2 * (size_t)j];
+    words[3 * (size_t)j + 1] = (int32_t)plan.idx[2 * (size_t)j + 1];
+    words[3 * (size_t)j + 2] = 0;
+    mf::balance_bytes(plan.fresh[2 * (size_t)j], A, fresh.data() + (size_t)2 * j * A);
+    mf::balance_bytes(plan.fresh[2 * (size_t)j + 1], A, fresh.data() + ((size_t)2 * j + 1) * A);
+  }
+  auto build = [&](dim3 grid, const int32_t *d_plan, const uint8_t *, const uint8_t *d_pay, uint4 *d_fresh) {
+    hipLaunchKernelGGL(k_transfer_records, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), d_pay, d_plan, K, A, length, nk, d_fresh);
+  };
+  // c. the 2 nk new records and their updates; a row: k_from | k_to | v | old record of p | old record of s
+  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
+  return pair_updates(c, t, k, d_table, s, 38, build, words, plan.idx, fresh.data(), (size_t)2 * A,
+                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
+    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros,
+                        {{k.key(j), K}, {h_to + (size_t)j * k.key_stride, K}, {amounts.data() + (size_t)j * A, A}, {head_p, length}, {head_s, length}}, staged_p, staged_s, d0,
+                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int mfh_merkle_transfer_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                             const uint8_t *h_from, const uint8_t *h_to, size_t key_stride, const uint64_t *h_amounts, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots,
+                             uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_transfer_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return transfer_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_from, key_stride, h_inputs, in_stride, h_index, h_status, h_roots, nullptr}, d_table, h_to,
+                       h_amounts, amount_bytes);
+}
+
+int mfh_merkle_transfer_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                                 const uint8_t *h_from, const uint8_t *h_to, size_t key_stride, const uint64_t *h_amounts, uint32_t ncuts, const uint32_t *h_cuts,
+                                 uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_transfer_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return transfer_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_from, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table, h_to,
+                       h_amounts, amount_bytes);
+}
 
 int mfh_merkle_insert_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *h_keys,
                            size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,

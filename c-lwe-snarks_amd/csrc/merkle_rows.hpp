@@ -13,6 +13,9 @@
 //   words.MerkleInsert(.., joined=False)          the same behind Z = 128 (four tops)                pair_row_bytes(key_bytes, 3, length, depth, 128)
 //   words.MerkleRemove(key_bytes, length, depth)  the insert's row without a new record of s: Z = 64 (128 with joined=False), head = the key | old record of
 //                                                 p | old record of s, the two tails as the insert's  pair_row_bytes(key_bytes, 2, length, depth)
+//   words.MerkleTransfer(key_bytes, length, depth, amount_bytes)   the remove's row with three public pieces where it has the key: Z = 64 (128 with joined=False),
+//                                                 head = k_from | k_to | the amount as amount_bytes big-endian bytes | old record of p | old record of s, the two
+//                                                 tails as the insert's                           pair_row_bytes(2 key_bytes + amount_bytes, 2, length, depth)
 //   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
 //                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
 // A path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) gives G + 1 rows an update: segment 0 is the statement's own row over the subtree of

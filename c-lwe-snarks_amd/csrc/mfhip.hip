@@ -1150,6 +1150,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_segments")) return 34;  // k_merkle_cut_rows of the mfh_merkle_*_cut calls: one per chunk; rows = the chunk's updates x upper segments
   if (!strcmp(which, "merkle_owners")) return 35;  // k_key_owners of mfh_merkle_remove_keys (merkle.hip): one per call; rows = the table's 2^depth records
   if (!strcmp(which, "merkle_remove_records")) return 36;  // k_remove_records of mfh_merkle_remove_keys: one per call; rows = the 2 nk new records
+  if (!strcmp(which, "merkle_balances")) return 37;  // k_balance_gather of mfh_merkle_transfer_keys (merkle.hip): one per call; rows = the batch's unique keys
+  if (!strcmp(which, "merkle_transfer_records")) return 38;  // k_transfer_records of mfh_merkle_transfer_keys: one per call; rows = the 2 nk new records
   return -1;
 }
 

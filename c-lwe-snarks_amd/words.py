@@ -8,6 +8,7 @@ A word is a tuple of 32 wires, least significant bit first.  Costs, in gate wire
     ch           96   z ^ (x & (y ^ z))
     maj          32   one MAJ per bit
     less_than     2 n   for two n-bit operands: a NOT and a MAJ a bit (the borrow chain of a - b); 4 n rows
+    ripple        2 n   for two n-bit operands of any width: a full adder a bit, the carry out returned; subtract=True 3 n + 1 (a NOT a bit, the borrow out)
     rotl / rotr   0   rewiring only
     shr           0   the vacated bits are the circuit's shared zero wire (1 wire for the whole circuit)
     const         0   the shared zero and one wires (at most 2 for the whole circuit)
@@ -53,6 +54,9 @@ Whole statements built from that compression, the result 256 computed public out
                             outputs all four chain tops (lu = 1024 + 8 key_bytes): segment 0 of an insert into a tree deeper than one circuit.
     MerkleRemove(key_bytes, length, depth, joined=True)   "key k was removed from the indexed table, and that alone takes the tree from R to R'": the
                             inverse step, three record chains and a constant inert leaf; the same public wires and joined=False form as MerkleInsert.
+    MerkleTransfer(key_bytes, length, depth, amount_bytes=8, joined=True)   "v moved from the account k_from to the account k_to, and that alone takes the
+                            tree from R to R'": two live records whose balances (bytes [2K, 2K + A), big-endian) become b_p - v and b_s + v with no borrow
+                            and no carry; lu = 512 + 16 key_bytes + 8 amount_bytes; the same joined=False form.
     MerkleSegment(levels)   "one node changed from X to X', and that alone takes its ancestor `levels` levels up from Y to Y'" (lu = 1024, the two nodes
                             given, the two tops computed): one level range of a path cut by segment_levels(depth, cuts); MerkleUpdate's sizes, 10 levels
                             fit d = 2^20.  chain(nodes) turns the published node pairs of a transition into the upper segments' statements.
@@ -173,6 +177,20 @@ class Words:
         for a, b in zip(a_bits, b_bits):
             borrow = self.c.MAJ(self.c.NOT(a), b, borrow)
         return borrow
+
+    def ripple(self, a_bits, b_bits, subtract=False):
+        """(the n wires of a + b mod 2^n, the carry out) for two equal-length lists of wires of ANY width n >= 1, least significant first, read as unsigned
+        integers: one full adder a bit (Circuit.full_add: MAJ + SUM3) from the carry const(0) -- 2 n wires, 4 n rows.  subtract=True: (the n wires of
+        a - b mod 2^n, the BORROW out, 1 when a < b) as a + NOT b + 1, the carry from const(1), the borrow the NOT of the last carry -- 3 n + 1 wires, 6 n + 2
+        rows.  (add stays the 32-bit modular word addition.)"""
+        a_bits, b_bits = list(a_bits), list(b_bits)
+        if not a_bits or len(a_bits) != len(b_bits):
+            raise CircuitError("ripple: two lists of wires of one length, at least 1")
+        out, carry = [], self.c.const(1 if subtract else 0)
+        for a, b in zip(a_bits, b_bits):
+            s, carry = self.c.full_add(a, self.c.NOT(b) if subtract else b, carry)
+            out.append(s)
+        return out, self.c.NOT(carry) if subtract else carry
 
     # -- rewiring -------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -886,11 +904,11 @@ class _KeyStep(_TwoRoots):
 
     joined = True  # (on the class too: bits() reads the sizes and this alone, so it still serves a stand-in that has only the sizes)
 
-    def _open(self, key_bytes, length, depth, nrec: int):
+    def _open(self, key_bytes, length, depth, nrec: int, field=0):
         """the argument checks, then the private wires in their order: nrec records of 8 * length bits (returned), `depth` siblings of p, `depth` siblings of
-        s, the direction bits of p, those of s"""
+        s, the direction bits of p, those of s.  field: the bytes of a field the statement reads behind the two keys (MerkleTransfer's balance)"""
         self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
-        self.length = length = self._arg(length, 2 * K, None, "the length is at least 2 key_bytes bytes")
+        self.length = length = self._arg(length, 2 * K + field, None, "the length is at least 2 key_bytes" + (f" + {field}" if field else "") + " bytes")
         self.depth = depth = self._depth_arg(depth)
         self.w = w = Words()
         records = [w.c.private(8 * length) for _ in range(nrec)]
@@ -900,10 +918,12 @@ class _KeyStep(_TwoRoots):
         self.dirs_s = w.c.private(depth)
         return records
 
-    def _close(self, leaves, joined):
+    def _close(self, leaves, joined, pieces=None):
         """the level chains of the four leaves (old p, new p, old s, new s), the first two over p's tail and the last two over s's; the old root's outputs,
         with joined=False the two middle tops', the new root's; the key's public wires; joined: the 256 assert_same that tie the middle tops, the private
-        intermediate root"""
+        intermediate root.  pieces: the statement's public pieces behind the tops where the key is not the only one (self._piece_bytes says their bytes) --
+        lists of public wires that the subclass declared BEFORE its leaves, because its leaves depend on them; they are moved behind the tops here
+        (Circuit.public_last), the key first"""
         w = self.w
         tails = ((self.siblings_p, self.dirs_p), (self.siblings_p, self.dirs_p), (self.siblings_s, self.dirs_s), (self.siblings_s, self.dirs_s))
         self.out_old, self.mid_p, self.mid_s, self.out_new = (_merkle_levels(w, leaf, sibs, dirs) for leaf, (sibs, dirs) in zip(leaves, tails))
@@ -913,23 +933,35 @@ class _KeyStep(_TwoRoots):
             self.top_mid_p = [w.output(x) for x in self.mid_p]
             self.top_mid_s = [w.output(x) for x in self.mid_s]
         self.new_root = [w.output(x) for x in self.out_new]
-        self.key = w.c.public(8 * self.key_bytes)
+        if pieces is None:
+            self.key = w.c.public(8 * self.key_bytes)
+        else:
+            self.key = pieces[0]
+            w.c.public_last([x for piece in pieces for x in piece])
         if self.joined:
             for x, y in zip(self.mid_p, self.mid_s):
                 w.assert_same_u32(x, y)
 
+    def _piece_bytes(self):
+        """the bytes of the public pieces behind the tops, in their order: the key's, then whatever else the step's statement names"""
+        return (self.key_bytes,)
+
     @property
     def lu(self) -> int:
-        return (512 if self.joined else 1024) + 8 * self.key_bytes
+        return (512 if self.joined else 1024) + 8 * sum(self._piece_bytes())
 
     def _query(self, key) -> bytes:
         return _checked_key(type(self).__name__, self.key_bytes, key, "members")
 
-    def _step_bits(self, key, records, siblings_p, index_p, siblings_s, index_s):
-        """512 zeros where the two roots are computed (1024 with joined=False: the four tops), the key's bits, the records' bits, p's siblings and s's as
-        big-endian words, then the direction bits of p and of s"""
+    def _public(self, *pieces) -> bytes:
+        """the checked bytes of the public pieces behind the tops, as the statement has them: one value per entry of _piece_bytes"""
+        return self._query(*pieces)
+
+    def _step_bits(self, pieces, records, siblings_p, index_p, siblings_s, index_s):
+        """512 zeros where the two roots are computed (1024 with joined=False: the four tops), the bits of the public pieces (the key: one value, or a tuple
+        of one value a piece), the records' bits, p's siblings and s's as big-endian words, then the direction bits of p and of s"""
         who = type(self).__name__
-        key = np.unpackbits(np.frombuffer(self._query(key), dtype=np.uint8), bitorder="little")
+        key = np.unpackbits(np.frombuffer(self._public(*(pieces if isinstance(pieces, tuple) else (pieces,))), dtype=np.uint8), bitorder="little")
         tail_p, tail_s = (_tail_bits(who, self.depth, sibs, index) for sibs, index in ((siblings_p, index_p), (siblings_s, index_s)))
         nsib = 256 * self.depth
         return _input_bits(512 if self.joined else 1024, key, _record_bits(who, self.length, *records, what="the records are"), tail_p[:nsib], tail_s[:nsib],
@@ -940,10 +972,12 @@ class _KeyStep(_TwoRoots):
         with `key` took old_root to new_root": MerkleUpdate.statement's bytes, then the key.  With joined=False statement(X_p, X_p', X_s, X_s', key), 128 +
         key_bytes bytes: "the step with `key` took p's top from X_p to X_p' and then s's top from X_s to X_s'"."""
         who = type(self).__name__
-        *tops, key = tops_and_key
-        if len(tops) != (2 if self.joined else 4):
-            raise CircuitError(f"{who}: statement takes (old_root, new_root, key), or with joined=False (X_p, X_p', X_s, X_s', key)")
-        return b"".join(_statement_of(x, f"{who}: a top") for x in tops) + self._query(key)
+        npieces = len(self._piece_bytes())
+        tops, pieces = tops_and_key[: -npieces], tops_and_key[-npieces:]
+        if len(tops_and_key) != (2 if self.joined else 4) + npieces:
+            what = "key" if npieces == 1 else f"the {npieces} public pieces"
+            raise CircuitError(f"{who}: statement takes (old_root, new_root, {what}), or with joined=False (X_p, X_p', X_s, X_s', {what})")
+        return b"".join(_statement_of(x, f"{who}: a top") for x in tops) + self._public(*pieces)
 
     def tops_of(self, witness_row):
         """joined=False: (X_p, X_p', X_s, X_s'), 32 bytes each, as computed, from a witness row"""
@@ -1060,6 +1094,93 @@ class MerkleRemove(_KeyStep):
         return self._step_bits(key, (old_p, old_s), siblings_p, index_p, siblings_s, index_s)
 
 
+class MerkleTransfer(_KeyStep):
+    """The statement "the amount v moved from the account with key k_from to the account with key k_to, and that alone takes the tree from root R to root
+    R'": the two record updates of a transfer (indexed_transfer) under ONE pair of roots -- the first statement over the indexed table (MerkleAbsent has
+    the data model) that does arithmetic on the payload.
+
+    The data model.  amount_bytes = A, 1 <= A <= 8.  A record's BALANCE is its bytes [2K, 2K + A), an unsigned big-endian integer, so length >= 2K + A;
+    a transfer touches nothing else of a record (lo, hi and the payload bytes from 2K + A on).  Record p is the live record whose own key is k_from: its
+    balance becomes b_p - v.  Record s is the live record whose own key is k_to, opened in the tree AFTER p's update: its balance becomes b_s + v.
+    Public wires, in this order: R as 256 computed outputs at statement bits [0, 256), R' at [256, 512), the 8K given bits of k_from, the 8K of k_to, the 8A
+    of v -- v as A big-endian bytes, byte j's bit b (LSB first) at 8 j + b, as the keys are placed; lu = 512 + 16K + 8A.  statement(R, R', k_from, k_to, v)
+    is MerkleUpdate.statement's 64 bytes, then the two keys, then v as A bytes.
+    Private inputs, in this order: the old record of p (8 * length bits, byte j's bit b at 8 j + b), the old record of s; `depth` siblings of 8 words for p,
+    from the leaf's level up; `depth` siblings for s, taken from the tree AFTER p's update; `depth` direction bits of p; `depth` direction bits of s.
+    nin = 512 + 16K + 8A + 16 length + 514 depth.
+    The body.  Neither new record is an input: new_p is old_p's wires with the 8A balance wires replaced by the difference b_p - v, new_s is old_s's wires
+    with them replaced by the sum b_s + v (Words.ripple, a full adder a bit), so keys and the rest of the payload cannot change.  The final BORROW of the
+    subtraction is asserted 0 (no overdraft) and the final CARRY of the addition is asserted 0 (no overflow past 2^(8A) - 1).  Four record chains
+    (_message_chain: old_p, new_p, old_s, new_s) and four level chains (_merkle_levels) as MerkleInsert's; the two middle roots tied by 256 assert_same.
+    Further assert_same: k_from = old_p[0, K), k_to = old_s[0, K).  Comparators: less_than(lo_p, hi_p) = 1 and less_than(lo_s, hi_s) = 1 -- both records
+    are live.  The sentinel keys are refused as for members.
+    Soundness.  A transfer CONSERVES b_p + b_s: with no borrow and no carry the two new balances are the integers b_p - v and b_s + v.  It keeps the
+    table's invariant, because no key changes: every record's lo and hi are the wires they were.  By the invariant a key is the lo of at most one live
+    record, so p and s are the accounts of k_from and k_to and no others.
+    k_from = k_to.  The statement needs no constraint against it.  With k_from = k_to the invariant makes s the slot p, and s is opened in the tree after
+    p's update, so old_s is new_p, balance b_p - v; the step then leaves the slot at (b_p - v) + v = b_p: R' = R and the sum of all balances is what it
+    was.  A transfer to oneself is a no-op that still demands v <= b_p, nothing is created -- so the circuit allows it, and MerkleTree.transfer_keys,
+    which has nothing to do for it, refuses it.
+    What it does not cover: like MerkleInsert, the records it does not open.
+    MerkleTree.transfer_keys / transfer_bits perform a batch of transfers on a device table and give the input rows; statement j is (R_j, R_j+1,
+    from_j, to_j, v_j).  An account may occur in many steps of a batch, and may spend what an earlier step delivered.
+    Sizes (MERKLE_TRANSFER_SIZES): MerkleInsert's four chains and four level chains, so a level costs 113 986 wires and 202 946 rows; (8, 55, 4, 8) fits
+    Params(d=1 << 20, m=699050), depth 5 does not; (4, 16, 1, 8) fits Params(d=1 << 19, m=349525).
+    joined=False is segment 0 of a cut transfer (MerkleSegment), exactly as MerkleInsert's: the 256 assert_same on the middle roots are dropped and all four
+    chain tops are outputs, X_p at [0, 256), X_p' at [256, 512), X_s at [512, 768), X_s' at [768, 1024); the keys and the amount follow from bit 1024;
+    lu = 1024 + 16K + 8A; statement(X_p, X_p', X_s, X_s', k_from, k_to, v); tops_of(row) reads the four back; the packed row is the joined one with 128
+    zero bytes in front in place of 64 (MERKLE_TRANSFER_SPLIT_SIZES)."""
+
+    amount_bytes = 8
+
+    def __init__(self, key_bytes: int, length: int, depth: int, amount_bytes=8, joined=True):
+        self.amount_bytes = A = self._arg(amount_bytes, 1, 8, "amount_bytes is in [1, 8]")
+        self.old_p, self.old_s = self._open(key_bytes, length, depth, 2, field=A)
+        w, K = self.w, self.key_bytes
+        # the public pieces are read by the two balances' gates, so they are declared here; _close moves them behind the tops
+        self.key, self.key_to, self.amount = w.c.public(8 * K), w.c.public(8 * K), w.c.public(8 * A)
+        field = slice(16 * K, 16 * K + 8 * A)
+        v, b_p, b_s = (_key_bits_lsb_first(bits, A) for bits in (self.amount, self.old_p[field], self.old_s[field]))
+        diff, self.borrow = w.ripple(b_p, v, subtract=True)
+        total, self.carry = w.ripple(b_s, v)
+
+        def with_balance(record, bits):  # `bits` least significant first, back into the record's byte order
+            return record[: field.start] + [bits[8 * (A - 1 - j) + b] for j in range(A) for b in range(8)] + record[field.stop:]
+
+        self.new_p, self.new_s = with_balance(self.old_p, diff), with_balance(self.old_s, total)
+        chains = [_message_chain(w, rec, self.length) for rec in (self.old_p, self.new_p, self.old_s, self.new_s)]
+        self.blocks = chains[0][1]
+        self._close([leaf for leaf, _ in chains], joined, pieces=(self.key, self.key_to, self.amount))
+        w.c.assert_equal(self.borrow, 0)
+        w.c.assert_equal(self.carry, 0)
+        for a, b in zip(self.key, self.old_p[: 8 * K]):
+            w.c.assert_same(a, b)
+        for a, b in zip(self.key_to, self.old_s[: 8 * K]):
+            w.c.assert_same(a, b)
+        lo_p, hi_p, lo_s, hi_s = (_key_bits_lsb_first(bits, K) for bits in (self.old_p[: 8 * K], self.old_p[8 * K: 16 * K], self.old_s[: 8 * K],
+                                                                           self.old_s[8 * K: 16 * K]))
+        w.c.assert_equal(w.less_than(lo_p, hi_p), 1)
+        w.c.assert_equal(w.less_than(lo_s, hi_s), 1)
+
+    def _piece_bytes(self):
+        return (self.key_bytes, self.key_bytes, self.amount_bytes)
+
+    def _public(self, *pieces) -> bytes:
+        if len(pieces) != 3:
+            raise CircuitError("MerkleTransfer: the public pieces are (k_from, k_to, v)")
+        k_from, k_to, v = pieces
+        if not isinstance(v, (int, np.integer)) or not 0 <= v < 1 << (8 * self.amount_bytes):
+            raise CircuitError(f"MerkleTransfer: the amount is an integer in [0, 2^{8 * self.amount_bytes})")
+        return self._query(k_from) + self._query(k_to) + int(v).to_bytes(self.amount_bytes, "big")
+
+    def bits(self, k_from: bytes, k_to: bytes, amount: int, old_p: bytes, old_s: bytes, siblings_p, index_p: int, siblings_s, index_s: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed (1024 with joined=False: the four tops), the bits of
+        k_from, of k_to and of the amount's A big-endian bytes, the two records' bits, p's siblings and s's (those from the tree after p's update) as
+        big-endian words, then the direction bits of p and of s.  (A witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign
+        say so.)"""
+        return self._step_bits((k_from, k_to, amount), (old_p, old_s), siblings_p, index_p, siblings_s, index_s)
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):
@@ -1151,6 +1272,33 @@ def indexed_remove(record_p, p: int, record_s, s: int, key_bytes=None):
     return [int(p), int(s)], new
 
 
+def indexed_transfer(record_p, p: int, record_s, s: int, amount: int, key_bytes: int, amount_bytes=8):
+    """(indices, new_records): the two updates that move `amount` from the account in slot p to the account in slot s of an indexed table whose records
+    carry a balance (MerkleTransfer has the data model), in the order MerkleTree.update_records takes them, p first.  record_p and record_s are the two
+    live records as they stand; update 0 is record p with its balance, bytes [2K, 2K + A) big-endian, less the amount, update 1 record s with its
+    balance plus the amount; nothing else of either changes.  CircuitError on an overdraft (amount > p's balance), an overflow (s's balance + amount
+    >= 2^(8A)), p == s, or a record that is not live (lo < hi)."""
+    record_p, record_s = bytes(record_p), bytes(record_s)
+    K, A, length = key_bytes, amount_bytes, len(record_p)
+    if (not all(isinstance(x, (int, np.integer)) for x in (K, A)) or not 1 <= K <= 32 or not 1 <= A <= 8 or length < 2 * K + A or len(record_s) != length):
+        raise CircuitError("indexed_transfer: two records of one length, at least 2 key_bytes + amount_bytes bytes, key_bytes in [1, 32], amount_bytes in [1, 8]")
+    if not isinstance(amount, (int, np.integer)) or not 0 <= amount < 1 << (8 * A):
+        raise CircuitError(f"indexed_transfer: the amount is an integer in [0, 2^{8 * A})")
+    if not record_p[:K] < record_p[K: 2 * K] or not record_s[:K] < record_s[K: 2 * K]:
+        raise CircuitError("indexed_transfer: a record is not live (lo < hi)")
+    if p == s or p < 0 or s < 0:
+        raise CircuitError("indexed_transfer: p and s are two different slots")
+    b_p, b_s = (int.from_bytes(r[2 * K: 2 * K + A], "big") for r in (record_p, record_s))
+    if amount > b_p:
+        raise CircuitError(f"indexed_transfer: an overdraft, the sender has {b_p}")
+    if b_s + amount >= 1 << (8 * A):
+        raise CircuitError(f"indexed_transfer: the receiver's balance would exceed 2^{8 * A} - 1")
+    new = np.zeros((2, length), dtype=np.uint8)
+    new[0] = np.frombuffer(record_p[: 2 * K] + (b_p - int(amount)).to_bytes(A, "big") + record_p[2 * K + A:], dtype=np.uint8)
+    new[1] = np.frombuffer(record_s[: 2 * K] + (b_s + int(amount)).to_bytes(A, "big") + record_s[2 * K + A:], dtype=np.uint8)
+    return [int(p), int(s)], new
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -1190,3 +1338,12 @@ MERKLE_SEGMENT_SIZES = {1: (58019, 103013), 2: (115012, 204486), 10: (570956, 10
 MERKLE_REMOVE_SIZES = {(4, 8, 1): (196799, 350371), (4, 8, 2): (310785, 553317), (8, 55, 1): (197732, 351496), (8, 55, 4): (539690, 960334)}
 # ... and of MerkleRemove(joined=False): the joined sizes plus 512 wires and 768 rows, as MERKLE_INSERT_SPLIT_SIZES
 MERKLE_REMOVE_SPLIT_SIZES = {(4, 8, 1): (197311, 351139), (8, 55, 1): (198244, 352264), (8, 55, 4): (540202, 961102)}
+# ... and of MerkleTransfer by (key_bytes, length, depth, amount_bytes): MerkleInsert's four record chains and four level chains, one input record fewer (neither
+# new record is an input), 16 key_bytes + 8 amount_bytes public wires, two comparisons, 16 key_bytes equalities on the keys, and the two ripples: 5 amount_bytes
+# x 8 + 1 wires and 10 amount_bytes x 8 + 4 rows with their two assertions (an amount byte costs 48 wires and 88 rows: (4, 16, 1, 3) less (4, 16, 1, 1) is twice
+# that).  A level costs 113 986 wires and 202 946 rows, MerkleInsert's.  (4, 16, 1, 8) fits Params(d=1 << 19, m=349525), (4, 16, 2, 8) does not; (8, 55, 4, 8)
+# is the deepest one-block statement that fits Params(d=1 << 20, m=699050): (8, 55, 5, 8) would be 1 212 612 rows
+MERKLE_TRANSFER_SIZES = {(4, 16, 1, 8): (224697, 399808), (4, 16, 2, 8): (338683, 602754), (4, 16, 1, 1): (224361, 399192), (4, 16, 1, 3): (224457, 399368),
+                         (8, 55, 1, 8): (225525, 400828), (8, 55, 4, 8): (567483, 1009666)}
+# ... and of MerkleTransfer(joined=False): the joined sizes plus 512 wires and 768 rows, as MERKLE_INSERT_SPLIT_SIZES
+MERKLE_TRANSFER_SPLIT_SIZES = {(4, 16, 1, 8): (225209, 400576), (8, 55, 1, 8): (226037, 401596), (8, 55, 4, 8): (567995, 1010434)}

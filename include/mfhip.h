@@ -543,6 +543,51 @@ int mfh_merkle_remove_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t
 int mfh_merkle_remove_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
                                const uint8_t *h_keys, size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
                                const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+/* nk sequential TRANSFERS between the accounts of an indexed table (the data model: mfh_merkle_absent_rows) and its tree in ONE call, and the packed input row
+ * of words.MerkleTransfer(key_bytes, length, depth, amount_bytes) of every transfer -- "amount j moved from the account with key from_j to the account with key
+ * to_j, and that alone takes the tree from R_j to R_j+1".  A record's BALANCE is its bytes [2 key_bytes, 2 key_bytes + amount_bytes), an unsigned big-endian
+ * integer, 1 <= amount_bytes <= 8; a transfer changes nothing else of a record.
+ *   semantics  byte for byte what this gives, run once per transfer in order: find p, the lowest live record whose own key (lo) is from_j, and s, that of
+ *              to_j; record p with its balance less the amount, then record s with its balance plus the amount, through mfh_merkle_update_records.  That
+ *              covers the table in place, every node of the tree, the roots and row j, which describes table and tree as they stood before transfer j.  An
+ *              account may occur in ANY number of steps, as sender and as receiver -- the one batch in which a key may be given many times -- and a step sees
+ *              the balances the earlier steps left: it may spend what an earlier step of the batch delivered.
+ *   arguments  sender j is the key_bytes bytes at h_from + j * key_stride, receiver j those at h_to + j * key_stride, h_amounts[j] the amount, below
+ *              2^(8 amount_bytes).  h_inputs = NULL: transfer, no rows.  h_roots (may be NULL) receives the nk + 1 roots R_0 .. R_nk.  h_index receives nk
+ *              pairs (p, s), 0xFFFFFFFF for a key that is no member.  h_status receives per step the first that applies: 0 = fine; 1 = the sender is not a
+ *              member; 2 = the receiver is not a member; 3 = an overdraft, the amount exceeds the sender's balance AT THAT STEP; 4 = an overflow, the
+ *              receiver's balance at that step plus the amount exceeds 2^(8 amount_bytes) - 1.  A step with a status is left out of the balances the later
+ *              steps are judged by.
+ *   rows       row j (at h_inputs + j * in_stride): 64 zero bytes where the roots are computed | from_j | to_j | the amount as amount_bytes big-endian bytes |
+ *              the old record of p | the old record of s | the 32 depth sibling bytes of p | those of s, from the tree after p's update | ceil(2 depth / 8)
+ *              index bytes, bit l < depth = bit l of p, bit depth + l = bit l of s.  Exactly 64 + 2 key_bytes + amount_bytes + 2 length + 64 depth +
+ *              ceil(2 depth / 8) bytes are written.
+ *   how        ONE launch of k_key_locate over the sorted unique keys of all 2 nk senders and receivers and, behind it on the stream, ONE launch of
+ *              k_balance_gather (one thread per unique key: the located record's balance as a uint64); 2 words and one balance per unique key come back under
+ *              ONE wait.  The host walks the steps in order over a running balance per account (merkle_transfer.hpp); ONE launch of k_transfer_records
+ *              builds the 2 nk new records from the table before the batch and the uploaded new balances; they go through mfh_merkle_update_records'
+ *              machinery in chunks of whole transfers (the most whose rows fit 64 MiB, at least one).  The call synchronises the stream behind the search
+ *              and every chunk.
+ * mfh_merkle_transfer_keys_cut is the same with the path cut (above): segment 0's row, ONE PER TRANSFER, is that of MerkleTransfer(key_bytes, length, c_0,
+ * amount_bytes, joined=False) -- 128 zero bytes | from | to | amount | old p | old s | c_0 siblings of p | c_0 of s | ceil(2 c_0 / 8) index bytes of p mod
+ * 2^c_0 and s mod 2^c_0 -- the upper segments have one MerkleSegment row per UPDATE (2 nk), and h_roots receives ALL 2 nk + 1 roots; it has no "no rows" mode.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: a null tree; a tree of another device; key_bytes 0 or above 32;
+ * amount_bytes 0 or above 8; length < 2 key_bytes + amount_bytes or > 2^20; table_stride < length; key_stride < key_bytes; nk > 0 with d_table, h_from, h_to,
+ * h_amounts, h_index or h_status null (nk may exceed 2^depth: accounts repeat); in_stride below the row's bytes when h_inputs is given; a sentinel key as sender or receiver; a transfer
+ * from an account to itself (from_j == to_j: a no-op, which the statement allows and the call has nothing to do for); an amount of 2^(8 amount_bytes) or more;
+ * for the cut call, what the cut calls above refuse.
+ * MFH_EINVAL after the search, with h_status and h_index filled, table and tree unwritten and no record or tree kernel launched: any step with a status
+ * other than 0.  The call is all or nothing.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call, rows = 2^depth), "merkle_balances" (1 per call, rows = the unique keys), "merkle_transfer_records" (1 per
+ * call, rows = 2 nk), then per chunk of 2 k updates "sha256_records" (1), "merkle_record_rows" (2; 1 without rows) and "merkle_updates" (depth + 1), the
+ * cut call also "merkle_segments" (1). */
+int mfh_merkle_transfer_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                             uint32_t nk, const uint8_t *h_from, const uint8_t *h_to, size_t key_stride, const uint64_t *h_amounts, uint8_t *h_inputs,
+                             size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+int mfh_merkle_transfer_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                                 uint32_t nk, const uint8_t *h_from, const uint8_t *h_to, size_t key_stride, const uint64_t *h_amounts, uint32_t ncuts,
+                                 const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index,
+                                 uint8_t *h_status);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
