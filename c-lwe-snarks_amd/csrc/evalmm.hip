@@ -660,8 +660,9 @@ __device__ __forceinline__ void mmstream_body(const MmsImages &imgs, uint32_t mt
   };
   v4i a[RQ][KSN];
   // Vector-memory operations complete in issue order (s_waitcnt vmcnt), so every load of the loop is used exactly one stage after it was
-  // issued: the A fragments of stage s+1 and the digit fragments of stage s+2 (kept in registers for a stage, then written to the LDS
-  // buffer stage s has just finished with) are issued in k-step ks of stage s and waited for in k-step ks of stage s+1.
+  // issued: the A fragments of stage s+1 and the digit fragments of stage s+2 (kept in registers for a stage, then written to the other
+  // LDS buffer) are issued in k-step ks of stage s and waited for in k-step ks of stage s+1 -- the digit fragments at its head (their
+  // ds_writes follow its first MFMAs and their registers are loaded again right behind), the A fragments at its end.
   v4i bnr[KSN][BPK];
   auto b_load = [&](uint32_t u0, int ks, int i) -> v4i {
     const v4i *bp = cdv + (uint64_t)(u0 >> 6) * NQ2 * 64 + (uint64_t)ks * NQ2 * 64 + SW * 64 * i;  // scalar
@@ -679,9 +680,9 @@ __device__ __forceinline__ void mmstream_body(const MmsImages &imgs, uint32_t mt
 #pragma unroll
   for (int ks = 0; ks < KSN; ks++) {
 #pragma unroll
-    for (int t = 0; t < RQ; t++) a[t][ks] = a_load(t, r0, ks);
-#pragma unroll
     for (int i = 0; i < BPK; i++) bnr[ks][i] = b_load(min(r0 + RT2, ulast), ks, i);
+#pragma unroll
+    for (int t = 0; t < RQ; t++) a[t][ks] = a_load(t, r0, ks);
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
@@ -690,26 +691,40 @@ __device__ __forceinline__ void mmstream_body(const MmsImages &imgs, uint32_t mt
 #elif defined(MMS_PRIO_OLD)
   if (wave < SW / 2) __builtin_amdgcn_s_setprio(1);
 #endif
+  // A ring of DEPTH digit fragments keeps the LDS reads ahead of the MFMAs that use them.  It NEVER drains inside an item: slot `it` of a stage (one
+  // fragment, RQ MFMAs; NF = KSN CH slots per stage, CH per k-step) first issues the read of fragment it + DEPTH -- past the stage's end that is fragment
+  // it + DEPTH - NF of the OTHER buffer, which the next stage starts with -- and then uses fragment it.
+  [[maybe_unused]] constexpr int NF = KSN * CH;
+  [[maybe_unused]] constexpr int BSLOT = 2 * CH + CH - 1 - DEPTH;  // the slot the stage's one barrier follows: the one whose read is the LAST read of LDS unit [2] (see there)
+  static_assert(DEPTH >= 1 && DEPTH + BPK <= CH && 2 * BPK <= CH, "the stage barrier follows the ds_writes of its k-step and that k-step's last ring read");
+  static_assert(CH - DEPTH - BPK <= 15, "lgkmcnt is a 4-bit count");
+  v4i ring[DEPTH];
+#pragma unroll
+  for (int i = 0; i < DEPTH; i++) {
+    ring[i] = bfrag[0][i / CH][ch * CH + i % CH][lane];
+    // (in the loop's order, oldest fragment first: s_waitcnt lgkmcnt(n) at the head of a stage is the minimum over the paths into it as well -- filled in
+    // any other order the ring was drained there once per stage, lgkmcnt(0))
+    __builtin_amdgcn_sched_barrier(0);
+  }
   uint32_t buf = 0;
   for (uint32_t u0 = r0; u0 < r1; u0 += RT2) {
     const uint32_t un1 = min(u0 + RT2, ulast), un2 = min(u0 + 2 * RT2, ulast);
-    const v4i *bcur = &bfrag[buf][0][ch * CH][lane];  // this wave's fragment (ks, q) at bcur[(ks * NQ2 + q) * 64]
+    [[maybe_unused]] const v4i *bcur = &bfrag[buf][0][ch * CH][lane];  // this wave's fragment (ks, q) at bcur[(ks * NQ2 + q) * 64]
+    [[maybe_unused]] const v4i *bnxt = &bfrag[buf ^ 1][0][ch * CH][lane];
     v4i *bnext = &bfrag[buf ^ 1][0][0][0];
-    // a ring of DEPTH digit fragments keeps the LDS reads ahead of the MFMAs that use them
-    v4i ring[DEPTH];
-#pragma unroll
-    for (int i = 0; i < DEPTH; i++) ring[i] = bcur[((i / CH) * NQ2 + i % CH) * 64];
 #pragma unroll
     for (int ks = 0; ks < KSN; ks++) {
-#ifdef MMS_LOADS_ONLY  // timing-only build (wrong results): the HBM stream and the staging of the digit fragments without the matrix core
-#pragma unroll
-      for (int t = 0; t < RQ; t++) acc[t][ks][0] += a[t][ks][0] ^ a[t][ks][3];
-#else
 #pragma unroll
       for (int q = 0; q < CH; q++) {
-        const int it = ks * CH + q;
+#ifdef MMS_LOADS_ONLY  // timing-only build (wrong results): the HBM stream and the staging of the digit fragments without the matrix core
+        if (q == 0) {
+#pragma unroll
+          for (int t = 0; t < RQ; t++) acc[t][ks][0] += a[t][ks][0] ^ a[t][ks][3];
+        }
+#else
+        const int it = ks * CH + q, nx = it + DEPTH;
         const v4i b = ring[it % DEPTH];
-        if (it + DEPTH < KSN * CH) ring[it % DEPTH] = bcur[(((it + DEPTH) / CH) * NQ2 + (it + DEPTH) % CH) * 64];
+        ring[it % DEPTH] = nx < NF ? bcur[((nx / CH) * NQ2 + nx % CH) * 64] : bnxt[(((nx - NF) / CH) * NQ2 + (nx - NF) % CH) * 64];
 #pragma unroll
         for (int t = 0; t < RQ; t++) {
 #ifdef MMS_ACC_ASM  // accumulators pinned to AccVGPRs (one wave per SIMD, 256 of them: MMS_SW=4 MMS_RQ=4): the compiler's own placement shuttles them through arch VGPRs and spills
@@ -718,23 +733,49 @@ __device__ __forceinline__ void mmstream_body(const MmsImages &imgs, uint32_t mt
           acc[t][q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t][ks], b, acc[t][q], 0, 0, 0);
 #endif
         }
-        __builtin_amdgcn_sched_barrier(0);  // keep [refill one ring slot, RQ MFMAs] as written: the reads stay DEPTH fragments ahead
-      }
 #endif
-      // this k-step's share of the next stage's digit fragments (loaded a stage ago) -> the other LDS buffer; the A fragments of this
-      // k-step are spent: their registers take the next stage's
-#pragma unroll
-      for (int i = 0; i < BPK; i++) bnext[ks * NQ2 * 64 + tid + SW * 64 * i] = bnr[ks][i];
+        // Behind the k-step's first slots: its share of the next stage's digit fragments (loaded a stage ago) -> unit [ks] of the other LDS buffer, one
+        // ds_write per slot, and then the same registers take the stage after's.
+        if (q < BPK) bnext[ks * NQ2 * 64 + tid + SW * 64 * q] = bnr[ks][q];
+        else if (q < 2 * BPK) bnr[ks][q - BPK] = b_load(un2, ks, q - BPK);
+#ifndef MMS_NOSYNC  // (timing-only build without it: wrong results -- what the stage barrier costs)
+        if (ks * CH + q == BSLOT) {
+          // The stage's ONE barrier.  Call this stage's buffer X, the other one Y, and unit [k] the fragments of k-step k.  Times are slots; s is this stage.
+          //   Y[k] is WRITTEN in slots k CH .. k CH + BPK - 1 of s (above), READ for stage s + 1 by reads issued from slot k CH - DEPTH of s + 1 (k = 0: from slot
+          //   NF - DEPTH of s, the ring running on) to slot k CH + CH - 1 - DEPTH of s + 1, and written again two stages after s.  This barrier sits behind slot
+          //   BSLOT = 2 CH + CH - 1 - DEPTH, after that slot's read.
+          //   (i) a unit is read only after every wave has written it: the writes of Y[0], Y[1], Y[2] precede this barrier (k CH + BPK - 1 <= BSLOT: the static_assert)
+          //       and their first reads follow it (NF - DEPTH, NF + CH - DEPTH, NF + 2 CH - DEPTH > BSLOT); Y[3] is written behind it, in slots 3 CH .. of s, and
+          //       first read in slot 3 CH - DEPTH of s + 1, which is the slot right behind the barrier of s + 1.
+          //   (ii) a unit is overwritten only after every wave has issued its last read of it: X[0], X[1], X[2] are last read in slots <= BSLOT of s, before this barrier
+          //       (X[2]'s last read IS slot BSLOT's), and overwritten in s + 1; X[3] is last read in slot NF - 1 - DEPTH of s and overwritten from slot 3 CH of s + 1,
+          //       with the barrier of s + 1 between the two.
+          //   "Issued", not "returned": up to DEPTH reads are in flight whenever the ring is full, so no barrier position can have them all back without draining
+          //   the ring.  The LDS executes a CU's instructions in the order the waves issued them, and a write that follows a barrier is issued after every read that
+          //   preceded it (the same argument as in k_mmstream_w).
+          // Only the wave's own ds_writes have to have landed: the CH - DEPTH - BPK ring reads issued behind the last of them may stay in flight (the LDS returns in
+          // order, so the count is exact), and 2 (CH - DEPTH - BPK) MFMAs lie between that ds_write and the barrier, so its latency is not waited for either.
+          asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" ::"n"(CH - DEPTH - BPK) : "memory");
+        }
+#endif
+        __builtin_amdgcn_sched_barrier(0);  // keep [refill one ring slot, RQ MFMAs, at most one more memory operation] as written: the reads stay DEPTH fragments ahead
+      }
+      // the A fragments of this k-step are spent: their registers take the next stage's
 #pragma unroll
       for (int t = 0; t < RQ; t++) a[t][ks] = a_load(t, un1, ks);
-#pragma unroll
-      for (int i = 0; i < BPK; i++) bnr[ks][i] = b_load(un2, ks, i);
     }
-#ifndef MMS_NOSYNC  // (timing-only build without it: wrong results -- what the stage barrier costs)
-    __syncthreads();  // the other buffer is complete; everyone is done with this one
+#ifndef MMS_LOADS_ONLY
+    if (NF % DEPTH) {  // (the next stage expects its fragment j in ring[j]: a renaming, the loop is unrolled over the slots)
+      v4i turned[DEPTH];
+#pragma unroll
+      for (int j = 0; j < DEPTH; j++) turned[j] = ring[(NF + j) % DEPTH];
+#pragma unroll
+      for (int j = 0; j < DEPTH; j++) ring[j] = turned[j];
+    }
 #endif
     buf ^= 1;
   }
+  __syncthreads();  // (every wave is out of the item's last stage before a persistent workgroup's next item refills buffer 0)
   const uint64_t Mtot = (uint64_t)mtiles * 16;
 #ifdef MMS_ACC_ASM
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // (the hazard recogniser does not see inside the asm MFMAs: their last results must have landed before they are read)
