@@ -104,6 +104,7 @@ EXPORTS = [
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
+    "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut",
 ]
 
 
@@ -250,6 +251,8 @@ def load_library():
         "mfh_merkle_remove_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_transfer_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, vp, sz, vp, vp, vp]),
         "mfh_merkle_transfer_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_paths_cut": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
+        "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -452,17 +455,23 @@ class MerkleTree:
         self._keep = []
         return rows
 
-    def _record_rows(self, records, indices):
-        paths = self.path_rows(indices)
+    @staticmethod
+    def _record_array(records, nb, who):
+        """the records of record_rows / record_segments as np.uint8 [nb, length]: an array of that shape, or nb bytes-likes of one length"""
         if isinstance(records, np.ndarray):
             rec = records
         else:
             rec = [np.frombuffer(bytes(r), dtype=np.uint8) for r in records]
             if len({len(r) for r in rec}) > 1:
-                raise MfhError("record_rows: the records are of one length")
+                raise MfhError(f"{who}: the records are of one length")
             rec = np.stack(rec) if rec else np.zeros((0, 0), dtype=np.uint8)
-        if rec.dtype != np.uint8 or rec.ndim != 2 or len(rec) != len(paths):
-            raise MfhError("record_rows: records are uint8 [nb, length], one per index")
+        if rec.dtype != np.uint8 or rec.ndim != 2 or len(rec) != nb:
+            raise MfhError(f"{who}: records are uint8 [nb, length], one per index")
+        return rec
+
+    def _record_rows(self, records, indices):
+        paths = self.path_rows(indices)
+        rec = self._record_array(records, len(paths), "record_rows")
         return np.concatenate([np.zeros((len(paths), 32), dtype=np.uint8), rec, paths[:, 64:]], axis=1), rec.shape[1]
 
     def record_rows(self, records, indices):
@@ -656,8 +665,9 @@ class MerkleTree:
         return self._key_step_bits(self.insert_keys(table, keys, payloads, roots), self._step_head(table, keys, 3, 64))
 
     # ---- the path cut into level ranges (words.MerkleSegment): one row array a segment, and the published node pairs
-    def _cut(self, cuts, who, n0, row0, nupper):
-        """(the row arrays: n0 rows of row0 bytes for segment 0, nupper rows a MerkleSegment, the C arguments ncuts, h_cuts, h_rows, h_strides)"""
+    def _cut(self, cuts, who, n0, row0, nupper, upper=128):
+        """(the row arrays: n0 rows of row0 bytes for segment 0, nupper rows a MerkleSegment -- upper=64: a MerkleClimb, whose tail starts at byte 64 --, the C
+        arguments ncuts, h_cuts, h_rows, h_strides)"""
         from .words import CircuitError, segment_levels
 
         try:
@@ -665,7 +675,7 @@ class MerkleTree:
         except (CircuitError, TypeError, ValueError):
             raise MfhError(f"{who}: cuts are 1 <= c_0 < .. < c_G-1 < depth, at least one") from None
         rows = [np.zeros((n0, row0(ranges[0][1])), dtype=np.uint8)]
-        rows += [np.zeros((nupper, 128 + 32 * (hi - lo) + (hi - lo + 7) // 8), dtype=np.uint8) for lo, hi in ranges[1:]]
+        rows += [np.zeros((nupper, upper + 32 * (hi - lo) + (hi - lo + 7) // 8), dtype=np.uint8) for lo, hi in ranges[1:]]
         c_cuts = np.array([lo for lo, _ in ranges[1:]], dtype=np.uint32)
         ptrs = (ctypes.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
         strides = (ctypes.c_size_t * len(rows))(*[r.shape[1] for r in rows])
@@ -750,6 +760,81 @@ class MerkleTree:
         out = self.insert_key_segments(table, keys, cuts, payloads)
         head = self._step_head(table, keys, 3, 128)
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
+
+    # ---- the READ path cut into level ranges (words.MerkleClimb): one row array a segment, and the published nodes
+    def _climb_nodes(self, rows):
+        """np.uint8 [n, G + 1, 32], the published nodes X_g of every statement in digest byte order: the heads of its upper segments' rows, then the root"""
+        n, G = len(rows[0]), len(rows) - 1
+        nodes = np.zeros((n, G + 1, 32), dtype=np.uint8)
+        for g in range(G):
+            nodes[:, g] = rows[g + 1][:, :32].reshape(n, 8, 4)[..., ::-1].reshape(n, 32)
+        nodes[:, G] = np.frombuffer(self.root(), dtype=np.uint8)
+        return nodes
+
+    def _climb_unpack(self, rows, cuts, head0):
+        edges = [0] + [int(x) for x in cuts] + [self.depth]
+        levels = [hi - lo for lo, hi in zip(edges, edges[1:])]
+        return [np.unpackbits(r, axis=1, bitorder="little")[:, : (head0 if g == 0 else 512) + 257 * levels[g]] for g, r in enumerate(rows)]
+
+    def path_segments(self, indices, cuts):
+        """path_rows with the path cut at levels `cuts` (words.segment_levels; mfh_merkle_paths_cut: ONE launch a chunk, straight from the tree's nodes).
+        Returns (rows, nodes): rows is a list of G + 1 arrays, rows[0][k] the packed input row of words.MerklePath(c_0) of statement k -- over the subtree of
+        height c_0 that holds the leaf -- and rows[g][k], g >= 1, that of words.MerkleClimb(c_g - c_g-1); nodes is np.uint8 [n, G + 1, 32], the published nodes
+        X_g of every statement in digest byte order, nodes[:, G] the root: MerklePath.statement(nodes[k, 0]) and MerkleClimb.chain(nodes[k]) are the G + 1
+        statements of statement k.  The tree is only read; waits for the stream."""
+        return self._path_segments(indices, cuts, "path_segments")
+
+    def _path_segments(self, indices, cuts, who):
+        c = self._ctx
+        idx = self._indices(indices, who)
+        rows, cargs, keep = self._cut(cuts, who, len(idx), lambda c0: 64 + 32 * c0 + (c0 + 7) // 8, len(idx), upper=64)
+        c._chk(c.lib.mfh_merkle_paths_cut(c._h, self._h, len(idx), ctypes.c_void_p(idx.ctypes.data), *cargs))
+        self._keep = []
+        return rows, self._climb_nodes(rows)
+
+    def path_segment_bits(self, indices, cuts):
+        """path_segments with every segment's rows as 0 / 1 arrays: what Context.circuit_assign takes for MerklePath(c_0) and the MerkleClimbs"""
+        rows, nodes = self.path_segments(indices, cuts)
+        return self._climb_unpack(rows, cuts, 512), nodes
+
+    def _record_segments(self, records, indices, cuts):
+        rows, nodes = self._path_segments(indices, cuts, "record_segments")
+        rec = self._record_array(records, len(rows[0]), "record_segments")
+        rows[0] = np.concatenate([np.zeros((len(rec), 32), dtype=np.uint8), rec, rows[0][:, 64:]], axis=1)
+        return rows, nodes, rec.shape[1]
+
+    def record_segments(self, records, indices, cuts):
+        """record_rows with the path cut at levels `cuts`: as path_segments, rows[0][k] being the packed input row of words.MerkleRecord(length, c_0) -- the
+        record spliced on the host in place of the leaf, as record_rows does -- and segment 0's statement MerkleRecord.statement(nodes[k, 0])"""
+        return self._record_segments(records, indices, cuts)[:2]
+
+    def record_segment_bits(self, records, indices, cuts):
+        """record_segments with every segment's rows as 0 / 1 arrays"""
+        rows, nodes, length = self._record_segments(records, indices, cuts)
+        return self._climb_unpack(rows, cuts, 256 + 8 * length), nodes
+
+    def absent_segments(self, table, keys, cuts):
+        """absent_rows with the path cut at levels `cuts` (mfh_merkle_absent_rows_cut).  Returns (rows, nodes, index, status): rows and nodes as path_segments
+        gives them, rows[0][k] being the packed input row of words.MerkleAbsent(key_bytes, length, c_0) for keys[k] and the located record, and segment 0's
+        statement MerkleAbsent(..).statement(nodes[k, 0], keys[k]); index and status as locate_keys gives them.  The row set of a present key (status 1) is
+        complete and segment 0 does not hold; a query of status 2 has the key alone in segment 0, all-zero rows above it and all-zero nodes below the root."""
+        c = self._ctx
+        tab, tstride, length, k = self._keys(table, keys, "absent_segments", "nq")
+        nq, kb = k.shape
+        index = np.zeros(nq, dtype=np.uint32)
+        status = np.zeros(nq, dtype=np.uint8)
+        rows, cargs, keep = self._cut(cuts, "absent_segments", nq, lambda c0: 32 + kb + length + 32 * c0 + (c0 + 7) // 8, nq, upper=64)
+        vp = ctypes.c_void_p
+        c._chk(c.lib.mfh_merkle_absent_rows_cut(c._h, self._h, _ptr(tab), tstride, length, kb, nq, vp(k.ctypes.data), kb, *cargs, vp(index.ctypes.data),
+                                                vp(status.ctypes.data)))
+        self._keep = []
+        return rows, self._climb_nodes(rows), index, status
+
+    def absent_segment_bits(self, table, keys, cuts):
+        """absent_segments with every segment's rows as 0 / 1 arrays"""
+        rows, nodes, index, status = self.absent_segments(table, keys, cuts)
+        head0 = 256 + 8 * (np.ascontiguousarray(keys).shape[1] + int(table.shape[1]))
+        return self._climb_unpack(rows, cuts, head0), nodes, index, status
 
     # ---- removes: the inverse of insert_keys
     def remove_keys(self, table, keys, roots=False):

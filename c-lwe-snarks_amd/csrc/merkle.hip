@@ -19,6 +19,8 @@
 // written on the way (mfh_merkle_update_rows; the recurrence: above the kernels, the host's schedule: merkle_sched.hpp).
 // k_merkle_cut_rows: a path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) -- the words.MerkleSegment input rows of every update's upper
 // segments, one launch a chunk between the level launches and the write-back.
+// k_merkle_climb_rows: a READ path cut the same way (mfh_merkle_paths_cut, mfh_merkle_absent_rows_cut) -- every segment's staged row of every statement of a
+// chunk, segment 0 the call's own and the words.MerkleClimb input rows above it, in one launch straight from the tree's nodes.
 // k_record_gather, k_record_store: the byte-granular copies of mfh_merkle_update_records, which applies a batch of sequential RECORD updates to a table of
 // records and its tree and writes every update's words.MerkleRecordUpdate input row: old and new records into the row heads before the level launches,
 // the last new record of each leaf into the table behind them.
@@ -265,6 +267,38 @@ __global__ __launch_bounds__(256) void k_merkle_cut_rows(const uint4 *__restrict
   } else if (u >= 8 && u < 8 + 2 * levels) {
     out = level_rows[(size_t)k * level_stride_units + 2 * lo + u];
   } else if (u == 8 + 2 * levels) {
+    out.x = (i >> lo) & (uint32_t)(((uint64_t)1 << levels) - 1);
+  }
+  seg_rows[(size_t)plan.base[g] + item] = out;
+}
+
+// ---- the cut READS, mfh_merkle_paths_cut and mfh_merkle_absent_rows_cut: a read path cut at levels c_0 < .. < c_G-1 gives every statement G + 1 rows, segment
+// 0 the call's own row over the subtree of height c_0 and segment g >= 1 the packed input row of words.MerkleClimb(c_g - c_g-1) (merkle_rows.hpp has the rows
+// and mf::ClimbPlan).  The tree is only read: no schedule, no same_cut, no k_merkle_paths and no staged full path.
+//
+// k_merkle_climb_rows, ONE launch per chunk, writes ALL segments' staged rows straight from the tree's nodes.  A work item is (statement k, segment g =
+// blockIdx.y, unit u) of that segment's staged row of 5 + 2 levels units, lo = the segment's lowest level:
+//   units 0 - 3   zero, but for the two units at plan.head[g] (if any): the stored node idx[k] >> lo of level lo, as words -- units 2 - 3 of segment 0 in a call
+//                 of paths (the leaf behind the 32 zero bytes where the top is computed), units 0 - 1 of segment g >= 1 (the given node X_g-1 in front of them)
+//   then          the siblings of levels [lo, lo + levels): node (idx[k] >> l) ^ 1 of level l, as words
+//   last          (idx[k] >> lo) mod 2^levels, in one unit
+// Reads: the chunk's n indices (all below 2^depth: the host checked) and nodes of levels [0, depth) -- heap index 2^(depth - l) + (i >> l) or its sibling,
+// both below 2^(depth - l + 1).  Writes: whole units of its own segment's rows, each by one item; nothing outside base + n (5 + 2 levels) units.
+__global__ __launch_bounds__(256) void k_merkle_climb_rows(const uint4 *__restrict__ nodes, uint32_t depth, uint32_t n, const uint32_t *__restrict__ idx,
+                                                           uint4 *__restrict__ seg_rows, const mf::ClimbPlan plan) {
+  const uint32_t g = blockIdx.y;
+  if (g >= plan.nseg) return;
+  const uint32_t lo = plan.lo[g], levels = plan.levels[g], head = plan.head[g], units = 5 + 2 * levels;
+  const uint32_t item = blockIdx.x * 256 + threadIdx.x;  // (n * units < 2^32: a chunk's rows fit 64 MiB, or n = 1)
+  if (item >= n * units) return;
+  const uint32_t k = item / units, u = item - k * units, i = idx[k];
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (u < 4) {
+    if (u - head < 2) out = bswap4(nodes[2 * (((size_t)1 << (depth - lo)) + (i >> lo)) + (u - head)]);  // (unsigned: u < head wraps; head = kClimbNoHead = 4: never)
+  } else if (u < 4 + 2 * levels) {
+    const uint32_t l = lo + ((u - 4) >> 1);
+    out = bswap4(nodes[2 * ((((size_t)1 << (depth - l)) + (i >> l)) ^ 1) + (u & 1)]);
+  } else {
     out.x = (i >> lo) & (uint32_t)(((uint64_t)1 << levels) - 1);
   }
   seg_rows[(size_t)plan.base[g] + item] = out;
@@ -935,18 +969,75 @@ int record_updates(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const uint32_t *h_i
   return update_rows(c, t, nupd, h_index, nullptr, h_roots, rowb, 2 * hp, hash_and_gather, store_table, rows_out, pairs, cuts);
 }
 
-// what a cut call asks of its cuts and of the ncuts + 1 row arrays of n rows each, segment 0's row being rowb0 bytes; 0 when they are fine
-const char *cuts_refused(uint32_t n, uint32_t ncuts, const uint32_t *h_cuts, uint32_t depth, uint8_t *const *h_rows, const size_t *h_strides, size_t rowb0) {
+// what a cut call asks of its cuts and of the ncuts + 1 row arrays of n rows each, segment 0's row being rowb0 bytes and an upper segment's
+// upper_row_bytes(its levels) -- a MerkleSegment's, or a cut read's MerkleClimb's; 0 when they are fine
+const char *cuts_refused(uint32_t n, uint32_t ncuts, const uint32_t *h_cuts, uint32_t depth, uint8_t *const *h_rows, const size_t *h_strides, size_t rowb0,
+                         size_t (*upper_row_bytes)(uint32_t) = mf::segment_row_bytes) {
   if (!ncuts || !h_cuts) return "no cuts (ncuts >= 1 and h_cuts)";
   for (uint32_t g = 0; g < ncuts; g++)
     if (h_cuts[g] < 1 || h_cuts[g] >= depth || (g && h_cuts[g] <= h_cuts[g - 1])) return "the cuts are not 1 <= c_0 < .. < c_G-1 < depth";
   if (!h_rows || !h_strides) return "h_rows or h_strides is null";
   for (uint32_t g = 0; g <= ncuts; g++) {
     if (n && !h_rows[g]) return "a segment without its rows (a null pointer in h_rows)";
-    const size_t rowb = g ? mf::segment_row_bytes((g < ncuts ? h_cuts[g] : depth) - h_cuts[g - 1]) : rowb0;
+    const size_t rowb = g ? upper_row_bytes((g < ncuts ? h_cuts[g] : depth) - h_cuts[g - 1]) : rowb0;
     if (h_strides[g] < rowb) return "a segment's stride shorter than its row's bytes";
   }
   return nullptr;
+}
+
+static_assert(mf::kClimbMaxSegments == kMaxDepth, "a ClimbPlan holds the most segments a tree can have");
+
+size_t climb_rows_scratch(uint32_t depth, uint32_t ch, size_t hs, const Cuts &cuts) {
+  return (size_t)ch * (mf::climb_staged_units(depth, cuts.ncuts, cuts.cuts) * 16 + hs + 4);
+}
+
+// The cut reads' driver: every segment's rows of n statements about the leaves h_index (where h_status, if any, is 2 there is no record: leaf 0 stands in),
+// chunked by the caller's rows of rowb0 bytes in segment 0 and a MerkleClimb's above.  Per chunk: the indices go up, ONE launch of k_merkle_climb_rows stages
+// all ncuts + 1 segments, `gather` (if any) launches what fills the heads, both come back, `rows0_out` makes the caller's segment-0 rows out of the pinned buffer
+// with the stream idle (u.pin_rows at u.rs: segment 0's staged rows, tail at byte 64), and row b0 + b of segment g >= 1 goes to h_rows[g] + (b0 + b) *
+// strides[g] -- all zero where the status is 2.  leaf_head: segment 0's staged row carries the leaf (a path row whole).  On the device: segment 0's k rows |
+// .. | segment G's | (at ch rows' distance) the heads | the indices; pinned: the same without the indices.  The tree is only read.
+int climb_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_index, const uint8_t *h_status, const Cuts &cuts, bool leaf_head, size_t rowb0, size_t hs,
+               const ChunkFn &gather, const ChunkFn &rows0_out) {
+  const uint32_t depth = t->depth, ncuts = cuts.ncuts;
+  const size_t su = mf::climb_staged_units(depth, ncuts, cuts.cuts);  // a statement's staged units, all segments
+  const uint32_t ch = mf::climb_chunk(n, rowb0, depth, ncuts, cuts.cuts, kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, climb_rows_scratch(depth, ch, hs, cuts))) return rc;
+  uint4 *d_rows = c->circ_io.as<uint4>(), *d_heads = d_rows + (size_t)ch * su;
+  uint32_t *d_idx = reinterpret_cast<uint32_t *>(d_heads + (size_t)ch * hs / 16);
+  uint8_t *pin_out = (uint8_t *)pin_acquire(c, c->pin_cw, (size_t)ch * (su * 16 + hs));
+  if (!pin_out) return MFH_ENOMEM;
+  uint8_t *pin_heads = pin_out + (size_t)ch * su * 16;
+  for (uint32_t b0 = 0; b0 < n; b0 += ch) {
+    const uint32_t k = std::min(ch, n - b0);
+    uint32_t widest = 0;
+    const mf::ClimbPlan plan = mf::climb_plan(depth, ncuts, cuts.cuts, k, leaf_head, &widest);
+    const Chunk u{b0, k, d_idx, nullptr, nullptr, nullptr, d_rows, d_heads, (size_t)16 * mf::climb_row_units(plan.levels[0]), hs, pin_out, pin_heads};
+    uint32_t *pin_idx = (uint32_t *)pin_acquire(c, c->pin_rows, (size_t)k * 4);
+    if (!pin_idx) return MFH_ENOMEM;
+    for (uint32_t b = 0; b < k; b++) pin_idx[b] = h_status && h_status[b0 + b] == 2 ? 0u : h_index[b0 + b];
+    HIP_TRY(c, hipMemcpyAsync(d_idx, pin_idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+    {
+      Timer tm(c, 39, (uint64_t)k * plan.nseg);  // "merkle_climb_rows" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_merkle_climb_rows, dim3((k * widest + 255) / 256, plan.nseg), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(t->mem), depth, k,
+                         (const uint32_t *)d_idx, d_rows, plan);
+    }
+    if (gather) gather(u);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pin_out, d_rows, (size_t)k * su * 16, hipMemcpyDeviceToHost, c->stream));
+    if (hs) HIP_TRY(c, hipMemcpyAsync(pin_heads, d_heads, (size_t)k * hs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rows0_out(u);
+    for (uint32_t g = 1; g <= ncuts; g++) {
+      const size_t units = mf::climb_row_units(plan.levels[g]);
+      for (uint32_t b = 0; b < k; b++) {
+        const bool found = !h_status || h_status[b0 + b] != 2;
+        mf::splice_climb_row(cuts.h_rows[g] + (size_t)(b0 + b) * cuts.strides[g], found ? pin_out + ((size_t)plan.base[g] + b * units) * 16 : nullptr, plan.levels[g]);
+      }
+    }
+  }
+  return MFH_OK;
 }
 
 }  // namespace
@@ -1097,6 +1188,22 @@ int mfh_merkle_update_rows_cut(mfh_ctx *c, mfh_merkle *t, uint32_t nupd, const u
       mf::splice_cut_tail(row + 128, u.pin_rows + (size_t)b * u.rs, c0, h_index[u.b0 + b]);
     }
   }, nullptr, &cuts);
+}
+
+int mfh_merkle_paths_cut(mfh_ctx *c, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                         const size_t *h_strides) {
+  const char *who = "mfh_merkle_paths_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const size_t rowb0 = ncuts && h_cuts ? mf::climb_row_bytes(h_cuts[0]) : 0;  // MerklePath(c_0)'s row
+  if (const char *what = cuts_refused(nstmt, ncuts, h_cuts, t->depth, h_rows, h_strides, rowb0, mf::climb_row_bytes)) return fail(c, who, what);
+  if (nstmt && !h_index) return fail(c, who, "statements without h_index");
+  if (const char *what = indices_refused(h_index, nstmt, t->depth)) return fail(c, who, what);
+  if (!nstmt) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return climb_rows(c, t, nstmt, h_index, nullptr, cuts, true, rowb0, 0, nullptr, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) mf::splice_climb_row(h_rows[0] + (size_t)(u.b0 + b) * h_strides[0], u.pin_rows + (size_t)b * u.rs, h_cuts[0]);
+  });
 }
 
 }  // extern "C"
@@ -1338,6 +1445,15 @@ const char *pair_rows_refused(const KeyCall &k, uint32_t depth, size_t rowb, con
   return k.h_inputs && k.in_stride < rowb ? short_stride : nullptr;
 }
 
+// the gather of the absent calls, cut or not: per chunk ONE launch of k_absent_gather copies the located records into the chunk's heads
+ChunkFn absent_gather(mfh_ctx *c, const KeyCall &k, uint32_t depth) {
+  return [c, &k, depth](const Chunk &u) {
+    Timer tm(c, 31, u.k);  // "merkle_absent_rows" (mfhip.hip: timing_kind)
+    const uint32_t items = u.k * (uint32_t)(mf::record_head_pitch(k.length) / 16);
+    hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.length, u.k, u.d_idx, u.d_heads);
+  };
+}
+
 }  // namespace
 
 extern "C" {
@@ -1366,16 +1482,47 @@ int mfh_merkle_absent_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
   if (int rc = key_search(c, k, plan, kLocate, depth, c->circ_io.as<uint8_t>(), &res)) return rc;
   mf::keys_scatter(plan, nq, res, h_index, h_status);
   if (!h_inputs) return MFH_OK;
-  auto gather = [&](const Chunk &u) {
-    Timer tm(c, 31, u.k);  // "merkle_absent_rows" (mfhip.hip: timing_kind)
-    const uint32_t items = u.k * (uint32_t)(hp / 16);
-    hipLaunchKernelGGL(k_absent_gather, dim3((items + 255) / 256), dim3(256), 0, c->stream, d_table, table_stride, k.span(depth), length, u.k, u.d_idx, u.d_heads);
-  };
+  const ChunkFn gather = absent_gather(c, k, depth);
   return path_rows(c, t, nq, h_index, h_status, rowb, hp, gather, [&](const Chunk &u) {
     for (uint32_t b = 0; b < u.k; b++) {
       const bool found = h_status[u.b0 + b] != 2;  // (else the zero bytes and the key alone: the staged pieces are a stand-in's)
       mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 32, {{k.key(u.b0 + b), key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
                      found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, depth);
+    }
+  });
+}
+
+int mfh_merkle_absent_rows_cut(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
+                               const uint8_t *h_keys, size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides,
+                               uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_absent_rows_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const uint32_t depth = t->depth;
+  const KeyCall k{who, d_table, table_stride, length, key_bytes, nq, h_keys, key_stride, nullptr, 0, h_index, h_status, nullptr, nullptr};
+  const size_t rowb0 = ncuts && h_cuts ? mf::row_bytes(32, (size_t)key_bytes + length, h_cuts[0]) : 0;  // MerkleAbsent(key_bytes, length, c_0)'s row
+  const std::string what = keys_refused(k, depth, "queries", false, [&]() -> const char * {
+    return cuts_refused(nq, ncuts, h_cuts, depth, h_rows, h_strides, rowb0, mf::climb_row_bytes);
+  });
+  if (!what.empty()) return fail(c, who, what.c_str());
+  if (!nq) return MFH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  mf::KeyPlan plan;
+  mf::keys_prepare(h_keys, key_stride, key_bytes, nq, plan);
+  // On the device.  The search, exactly mfh_merkle_absent_rows'.  Then, per chunk: all segments' staged rows | the heads (a record each, k_absent_gather) | the
+  // chunk's indices -- over the search's bytes, whose results are on the host by then.
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  const size_t hp = mf::record_head_pitch(length);
+  const uint32_t c0 = h_cuts[0], ch = mf::climb_chunk(nq, rowb0, depth, ncuts, h_cuts, kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, std::max(key_search_bytes(plan.nu, key_bytes), climb_rows_scratch(depth, ch, hp, cuts)))) return rc;
+  const uint32_t *res;
+  if (int rc = key_search(c, k, plan, kLocate, depth, c->circ_io.as<uint8_t>(), &res)) return rc;
+  mf::keys_scatter(plan, nq, res, h_index, h_status);
+  const ChunkFn gather = absent_gather(c, k, depth);
+  return climb_rows(c, t, nq, h_index, h_status, cuts, false, rowb0, hp, gather, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++) {  // segment 0: today's row with c_0 siblings and the low index bits, which the staged row's tail holds
+      const bool found = h_status[u.b0 + b] != 2;  // (else the zero bytes and the key alone: the staged pieces are a stand-in's)
+      mf::splice_row(h_rows[0] + (size_t)(u.b0 + b) * h_strides[0], 32, {{k.key(u.b0 + b), key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
+                     found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, c0);
     }
   });
 }

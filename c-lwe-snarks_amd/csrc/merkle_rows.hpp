@@ -18,9 +18,14 @@
 //                                                 tails as the insert's                           pair_row_bytes(2 key_bytes + amount_bytes, 2, length, depth)
 //   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
 //                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
+//   words.MerkleClimb(levels)                     the GIVEN node stands in front of the computed top: the node as words | 32 zero bytes | levels siblings as
+//                                                 words | ceil(levels / 8) index bytes            climb_row_bytes(levels) = row_bytes(32, 32, levels)
 // A path cut at levels c_0 < .. < c_G-1 (the mfh_merkle_*_cut calls) gives G + 1 rows an update: segment 0 is the statement's own row over the subtree of
 // height c_0 -- the head, the first c_0 siblings of the level row, the index masked to c_0 bits (splice_cut_tail) -- and segment g >= 1 a MerkleSegment row
 // of c_g - c_g-1 levels (c_G = depth), which k_merkle_cut_rows writes whole: its tail too starts at byte 128.
+// A cut READ (mfh_merkle_paths_cut, mfh_merkle_absent_rows_cut) gives G + 1 rows a statement, all staged by ONE launch of k_merkle_climb_rows in one layout
+// of 5 + 2 levels units, the tail at byte 64 as in a path row: segment 0 is the statement's own row over the subtree of height c_0 (a path row whole; under a
+// head of records its tail alone is read, splice_row with depth = c_0) and segment g >= 1 a MerkleClimb row whole (ClimbPlan, climb_plan, climb_chunk).
 // The kernels write whole rows where the tail lands on a 16-byte unit: k_merkle_paths the path row (tail at byte 64), k_merkle_update_level the level row
 // (tail at byte 128), both staged at staged_stride of their bytes.  A head of records puts the tail anywhere, so for those statements the device stages two
 // pieces per row and the host splices them while it copies out of the pinned buffer (splice_row):
@@ -70,6 +75,57 @@ inline size_t cut_rows_bytes(uint32_t depth, uint32_t ncuts, const uint32_t *cut
   return bytes;
 }
 
+// ---- cut reads.  Every segment of a read path is staged as 5 + 2 levels units of 16 bytes: 4 of node and zeros (a path row: zeros and leaf), 2 a sibling,
+// 1 for the index.  The staged row's first climb_row_bytes(levels) bytes ARE the caller's row (the index unit's low bytes are its last bytes).
+inline size_t climb_row_bytes(uint32_t levels) { return row_bytes(32, 32, levels); }
+inline uint32_t climb_row_units(uint32_t levels) { return 5 + 2 * levels; }
+// the levels of segment g = 0 .. ncuts of a path of `depth` levels cut at cuts[0 .. ncuts), and the level at which it starts
+inline uint32_t climb_lo(uint32_t g, const uint32_t *cuts) { return g ? cuts[g - 1] : 0; }
+inline uint32_t climb_levels(uint32_t g, uint32_t depth, uint32_t ncuts, const uint32_t *cuts) { return (g < ncuts ? cuts[g] : depth) - climb_lo(g, cuts); }
+// the staged units of ALL ncuts + 1 segments of ONE statement
+inline size_t climb_staged_units(uint32_t depth, uint32_t ncuts, const uint32_t *cuts) {
+  size_t units = 0;
+  for (uint32_t g = 0; g <= ncuts; g++) units += climb_row_units(climb_levels(g, depth, ncuts, cuts));
+  return units;
+}
+// ... and the bytes of its UPPER segments' rows as the caller gets them (segment 0's row is the call's own)
+inline size_t climb_rows_bytes(uint32_t depth, uint32_t ncuts, const uint32_t *cuts) {
+  size_t bytes = 0;
+  for (uint32_t g = 1; g <= ncuts; g++) bytes += climb_row_bytes(climb_levels(g, depth, ncuts, cuts));
+  return bytes;
+}
+// the statements of one chunk of a cut read of n statements (n > 0) whose segment 0 row is rowb0 bytes: the most whose rows of ALL segments fit the stage
+inline uint32_t climb_chunk(uint32_t n, size_t rowb0, uint32_t depth, uint32_t ncuts, const uint32_t *cuts, size_t stage_bytes) {
+  return update_chunk(n, rowb0 + climb_rows_bytes(depth, ncuts, cuts), stage_bytes);
+}
+
+// The plan of k_merkle_climb_rows, handed to it by value: segment g covers levels [lo, lo + levels) and its k staged rows start at unit `base` of the stage, one
+// segment behind the other; `head` is the unit of a row at which the stored node idx >> lo of level lo goes -- 2 in segment 0 (the leaf of a path row), 0 above
+// it (the given node of a MerkleClimb row) -- or kClimbNoHead, the first unit behind the head, where the host splices a head of records and the four head units
+// stay zero.
+constexpr uint32_t kClimbMaxSegments = 24;  // cuts lie below the depth, and that is at most 24
+constexpr uint32_t kClimbNoHead = 4;
+struct ClimbPlan {
+  uint32_t nseg;
+  uint32_t lo[kClimbMaxSegments], levels[kClimbMaxSegments], base[kClimbMaxSegments], head[kClimbMaxSegments];
+};
+// (1 <= cuts[0] < .. < cuts[ncuts - 1] < depth <= 24, k > 0.)  *widest <- the most units of a row of any segment: the launch's items a statement
+inline ClimbPlan climb_plan(uint32_t depth, uint32_t ncuts, const uint32_t *cuts, uint32_t k, bool leaf_head, uint32_t *widest) {
+  ClimbPlan plan{};
+  uint32_t units = 0, wide = 0;
+  for (uint32_t g = 0; g <= ncuts; g++) {
+    plan.lo[g] = climb_lo(g, cuts);
+    plan.levels[g] = climb_levels(g, depth, ncuts, cuts);
+    plan.base[g] = units;
+    plan.head[g] = g ? 0 : leaf_head ? 2 : kClimbNoHead;
+    units += k * climb_row_units(plan.levels[g]);
+    if (climb_row_units(plan.levels[g]) > wide) wide = climb_row_units(plan.levels[g]);
+  }
+  plan.nseg = ncuts + 1;
+  if (widest) *widest = wide;
+  return plan;
+}
+
 // the updates of one chunk of a batch of nk key steps (nk > 0): the most STEPS whose rows of row_bytes fit the stage, at least one, two updates each -- always
 // even, so both updates of a step are in one chunk even when one row alone exceeds the stage
 inline uint32_t pair_chunk(uint32_t nk, size_t row_bytes, size_t stage_bytes) { return 2 * update_chunk(nk, row_bytes, stage_bytes); }
@@ -96,6 +152,12 @@ inline void splice_cut_tail(uint8_t *at, const uint8_t *staged, uint32_t c0, uin
   memcpy(at, staged + 128, (size_t)32 * c0);
   const uint32_t low = index & (uint32_t)(((uint64_t)1 << c0) - 1);
   for (uint32_t b = 0; b < (c0 + 7) / 8; b++) at[(size_t)32 * c0 + b] = (uint8_t)(low >> (8 * b));
+}
+
+// row <- the climb_row_bytes(levels) bytes of a segment's row of a cut read out of its staged row; staged = nullptr (an absent query with no record): all zero
+inline void splice_climb_row(uint8_t *row, const uint8_t *staged, uint32_t levels) {
+  if (staged) memcpy(row, staged, climb_row_bytes(levels));
+  else memset(row, 0, climb_row_bytes(levels));
 }
 
 // row <- the input row of a key step whose two updates' level rows are staged_p and staged_s (tails at byte 128): `zeros` zero bytes | the head's pieces, in

@@ -1152,6 +1152,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_remove_records")) return 36;  // k_remove_records of mfh_merkle_remove_keys: one per call; rows = the 2 nk new records
   if (!strcmp(which, "merkle_balances")) return 37;  // k_balance_gather of mfh_merkle_transfer_keys (merkle.hip): one per call; rows = the batch's unique keys
   if (!strcmp(which, "merkle_transfer_records")) return 38;  // k_transfer_records of mfh_merkle_transfer_keys: one per call; rows = the 2 nk new records
+  if (!strcmp(which, "merkle_climb_rows")) return 39;  // k_merkle_climb_rows of the cut reads (mfh_merkle_paths_cut, mfh_merkle_absent_rows_cut): one per chunk; rows = the chunk's statements x segments
   return -1;
 }
 

@@ -662,7 +662,8 @@ class MerkleRecord(_OneRoot):
     and statement(root) is MerklePath.statement's bytes.  MerkleTree.record_rows / record_bits give the input rows for records of a device tree.
     Sizes (MERKLE_RECORD_SIZES): exactly those of Sha256Message(length) plus 28 625 depth wires and 50 865 depth rows.  At Params(d=1 << 20, m=699050)
     records of up to 55 bytes (one block) reach depth 19 (571 917 wires, 1 015 951 rows) and records of up to 119 bytes (two blocks) depth 18 (571 148
-    wires, 1 014 158 rows); (55, 20) does not fit: 1 066 816 rows."""
+    wires, 1 014 158 rows); (55, 20) does not fit: 1 066 816 rows.  A deeper tree is read with the path cut (segment_levels): MerkleRecord(length, c_0) over
+    the leaf's subtree, MerkleClimb above it (MerkleTree.record_segments)."""
 
     def __init__(self, length: int, depth: int):
         self.length, self.depth = length, depth = self._length_arg(length), self._depth_arg(depth)
@@ -777,6 +778,68 @@ def segment_levels(depth: int, cuts):
     return list(zip(edges, edges[1:]))
 
 
+class MerkleClimb(_Statement):
+    """The statement "the node X lies `levels` levels below the node Y": MerklePath's body with the leaf made PUBLIC -- one level range of a READ path that is
+    too deep for one circuit (segment_levels cuts it), at half of MerkleSegment's cost a level.
+
+    A deep read -- "this leaf / record is in the tree with root R", "this key is not in the table under R" -- is proved per level range.  With cuts c_0 < ..
+    < c_G-1 segment 0 is an existing statement (MerklePath(c_0), MerkleRecord(length, c_0), MerkleAbsent(key_bytes, length, c_0)) over the subtree of height
+    c_0 that holds the leaf, its computed "root" X_0 the level-c_0 node on the path, and segment g >= 1 is MerkleClimb(c_g - c_g-1) (c_G = the depth).  The
+    prover publishes the nodes X_0 .. X_G, X_G = R; the verifier builds every upper statement's bytes from that ONE list (chain), so adjacent statements share
+    a node by construction, and checks one proof a segment.
+    Soundness is MerklePath's applied G + 1 times: each proof says its lower node hashes up to its top through SOME siblings and directions, and the shared
+    nodes tie the tops to the next segment's lower node, so the leaf's subtree top X_0 lies depth - c_0 levels below R.  A segment's private index bits need
+    not agree with its neighbours'.
+    WHAT BECOMES PUBLIC: the intermediate nodes X_g, g < G.  They are hashes; to someone who holds the tree they reveal which level-c_g subtree the leaf lies
+    in, that is the high bits of the index.  That matters for MerklePath and MerkleRecord, which hide the leaf; for MerkleAbsent the key is public already.
+    Public wires, in this order (public wires are laid out in declaration order, so the given ones come first): X as 8 given words at statement bits [0, 256),
+    Y as 256 computed outputs at [256, 512); lu = 512.  Private inputs: `levels` siblings of 8 words from X's level up, then `levels` direction bits; nin =
+    512 + 257 levels.  The packed row (csrc/merkle_rows.hpp): X as words | 32 zero bytes | the siblings as words | ceil(levels / 8) index bytes -- the tail
+    starts at byte 64, as in MerklePath's row.
+    MerkleTree.path_segments / record_segments / absent_segments give every segment's rows and the published nodes for a device tree.
+    Sizes (MERKLE_CLIMB_SIZES): exactly MerklePath's, 28 625 levels + 514 wires and 50 865 levels + 772 rows; levels = 20 is the most that fits
+    Params(d=1 << 20, m=699050), levels = 10 fits d = 2^19 and levels = 2 is the most that fits Params(d=1 << 17, m=87381)."""
+
+    def __init__(self, levels: int):
+        self.levels = self.depth = self._arg(levels, 1, None, "levels is at least 1")
+        self.w = w = Words()
+        self.node = w.public(8)
+        self._tail_wires()
+        self.out = _merkle_levels(w, self.node, self.siblings, self.dirs)
+        self.top = [w.output(x) for x in self.out]
+
+    @property
+    def lu(self) -> int:
+        return 512
+
+    def bits(self, node: bytes, siblings, index: int):
+        """one statement's input bits, public then private: the node, 256 zeros where the top is computed, the siblings from the node's level up, then the
+        direction bits = the bits of the node's index inside the segment's subtree, least significant first"""
+        tail = _tail_bits("MerkleClimb", self.levels, siblings, index, (node,), "a 32-byte node and ")
+        return np.concatenate([tail[:256], np.zeros(256, dtype=np.uint8), tail[256:]])
+
+    def top_of(self, witness_row) -> bytes:
+        """the 32 bytes of the computed top: from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return _digest_from_row(witness_row, 256)
+
+    @staticmethod
+    def statement(node: bytes, top: bytes) -> bytes:
+        """the 64 statement bytes (what verify_public takes, bits [0, 512) of a witness row) that say "node lies below top": each half
+        MerklePath.statement's bytes"""
+        return _statement_of(node, "MerkleClimb: the node") + _statement_of(top, "MerkleClimb: the top")
+
+    @classmethod
+    def chain(cls, nodes):
+        """the G upper statements of one read from its published list [X_0, .., X_G], X_G = R: statement g - 1 of the result is segment g's,
+        statement(X_g-1, X_g).  Segment 0's statement is its own class's, over X_0."""
+        nodes = [bytes(x) for x in nodes]
+        if len(nodes) < 2:
+            raise CircuitError("MerkleClimb: a chain is at least two nodes")
+        if any(len(x) != 32 for x in nodes):
+            raise CircuitError("MerkleClimb: a node of a chain is 32 bytes")
+        return [cls.statement(nodes[g - 1], nodes[g]) for g in range(1, len(nodes))]
+
+
 class MerkleRecordUpdate(_TwoRoots):
     """The statement "I know an old record and a new record of `length` bytes, `depth` siblings and an index such that the path from SHA-256(old record)
     gives old_root and the SAME siblings and directions from SHA-256(new record) give new_root": MerkleUpdate about the data behind the leaf.
@@ -858,7 +921,8 @@ class MerkleAbsent(_OneRoot):
     asserted to 1.  MerkleTree.absent_rows / absent_bits find the record and give the input rows for queries against a device table.
     Sizes (MERKLE_ABSENT_SIZES): those of MerkleRecord(length, depth) plus 40 key_bytes wires and 72 key_bytes + 2 rows -- the 8 key_bytes public wires of
     q and their bit rows, and per comparison 16 key_bytes wires (a NOT and a MAJ a bit), 32 key_bytes rows and the assertion's row.  It keeps
-    MerkleRecord's depth range: (8, 55, 19) fits Params(d=1 << 20, m=699050)."""
+    MerkleRecord's depth range: (8, 55, 19) fits Params(d=1 << 20, m=699050).  A deeper table is read with the path cut (segment_levels):
+    MerkleAbsent(key_bytes, length, c_0) over the record's subtree, MerkleClimb above it (MerkleTree.absent_segments)."""
 
     def __init__(self, key_bytes: int, length: int, depth: int):
         self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
@@ -1331,6 +1395,10 @@ MERKLE_INSERT_SPLIT_SIZES = {(4, 8, 1): (224776, 399885), (8, 55, 1): (226156, 4
 # ... and of MerkleSegment by levels: MerkleUpdate's, 56 993 levels + 1 026 wires and 101 473 levels + 1 540 rows (the two nodes are public inputs where
 # MerkleUpdate's leaves are private ones); 10 levels fit Params(d=1 << 20, m=699050), 11 (1 117 743 rows) do not
 MERKLE_SEGMENT_SIZES = {1: (58019, 103013), 2: (115012, 204486), 10: (570956, 1016270)}
+# ... and of MerkleClimb by levels: MerklePath's, 28 625 levels + 514 wires and 50 865 levels + 772 rows (the node is 256 public inputs where MerklePath's leaf is
+# 256 private ones), every entry compiled; 20 levels (573 014 wires, 1 018 072 rows) fit Params(d=1 << 20, m=699050) and 21 (1 068 937 rows) do not, 10 fit
+# d = 2^19, and 2 fit Params(d=1 << 17, m=87381) where 3 do not
+MERKLE_CLIMB_SIZES = {1: (29139, 51637), 2: (57764, 102502), 3: (86389, 153367)}
 # ... and of MerkleRemove by (key_bytes, length, depth): MerkleInsert's less one record chain (the new leaf of s is a constant), 8 length input wires and their
 # bit rows (no new record of s) and one comparison (no inert check), with 16 key_bytes equalities on k as the insert has on k and the inherited hi.  A level
 # costs 113 986 wires and 202 946 rows, MerkleInsert's.  (4, 8, 1) fits Params(d=1 << 19, m=349525) and not d = 2^18; (8, 55, 4) is the deepest one-block

@@ -509,6 +509,37 @@ int mfh_merkle_update_records_cut(mfh_ctx *ctx, mfh_merkle *t, uint32_t nupd, co
 int mfh_merkle_insert_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
                                const uint8_t *h_keys, size_t key_stride, const uint8_t *h_payloads, size_t payload_stride, uint32_t ncuts, const uint32_t *h_cuts,
                                uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+/* ---- The two READ calls with the path cut into level ranges: what words.MerkleClimb proves per range.  h_cuts, h_rows and h_strides follow the conventions of
+ * the mfh_merkle_*_cut calls above (ncuts >= 1 levels 1 <= c_0 < .. < c_G-1 < depth; ncuts + 1 row pointers and strides, nstmt or nq rows a segment).
+ *   segment 0   the parent call's row over the subtree of height c_0 that holds the leaf: the same head, the first c_0 siblings, ceil(c_0 / 8) bytes holding
+ *               the index mod 2^c_0 -- the packed input row of MerklePath(c_0) (mfh_merkle_paths_cut: 64 + 32 c_0 + ceil(c_0 / 8) bytes) or of
+ *               MerkleAbsent(key_bytes, length, c_0) (mfh_merkle_absent_rows_cut: 32 + key_bytes + length + 32 c_0 + ceil(c_0 / 8) bytes).  The value its
+ *               circuit computes is X_0, the node of level c_0 on the path.
+ *   segment g   the packed input row of MerkleClimb(levels = c_g - c_g-1), c_G = depth: the stored node X_g-1 of level c_g-1 on the path as 8 words | 32 zero
+ *               bytes where the top X_g is computed | the siblings of levels c_g-1 .. c_g - 1 in mfh_merkle_paths' word convention | ceil(levels / 8) bytes
+ *               holding (index >> c_g-1) mod 2^levels.  Exactly 64 + 32 levels + ceil(levels / 8) bytes of a row are written, the rest of a wider row is left
+ *               alone.
+ * The published nodes of a statement are the heads of its rows: X_g for g < G is bytes [0, 32) of its segment g + 1 row (words: swap each word's bytes for the
+ * digest), X_G the root (mfh_merkle_root).
+ * mfh_merkle_absent_rows_cut: the search, the gather of the located records, h_index and h_status are exactly mfh_merkle_absent_rows'.  A status 1 row set is
+ * written in full (segment 0 does not hold); a status 2 query gets the 32 zero bytes and its key alone in segment 0 and all-zero rows above it.  There is
+ * no "locate only" mode: mfh_merkle_absent_rows has it.
+ *   how        per chunk (the most statements whose rows of ALL segments fit 64 MiB, at least one) the indices go up and ONE launch of k_merkle_climb_rows
+ *              writes every segment's staged rows straight from the tree's nodes -- no k_merkle_paths, no staged full path; mfh_merkle_absent_rows_cut adds
+ *              k_absent_gather, and the host splices key and record into segment 0.  Staging goes through the context's pinned buffers; the calls run on
+ *              the context's stream, synchronise it, and modify neither the tree nor the table.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued or written: everything the uncut call refuses but its in_stride (a null
+ * tree; a tree of another device; statements without h_index; an index not below 2^depth; for the absent call key_bytes 0 or above 32, length < 2 key_bytes or
+ * > 2^20, table_stride < length, key_stride < key_bytes, nq > 0 with d_table, h_keys, h_index or h_status null, a sentinel query), and ncuts = 0 or h_cuts
+ * null; cuts that are not 1 <= c_0 < .. < c_G-1 < depth; h_rows or h_strides null; a null pointer in h_rows with rows to write; a stride below its
+ * segment's row bytes.  nstmt = 0 or nq = 0 does nothing.
+ * Kernel timing kinds: "merkle_climb_rows" (1 per chunk, rows = the chunk's statements x (ncuts + 1)); the absent call also "merkle_locate" (1 per call) and
+ * "merkle_absent_rows" (1 per chunk).  Neither launches "merkle_paths". */
+int mfh_merkle_paths_cut(mfh_ctx *ctx, const mfh_merkle *t, uint32_t nstmt, const uint32_t *h_index, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                         const size_t *h_strides);
+int mfh_merkle_absent_rows_cut(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
+                               const uint8_t *h_keys, size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides,
+                               uint32_t *h_index, uint8_t *h_status);
 /* nk sequential key REMOVES from an indexed table (the data model: mfh_merkle_absent_rows) and its tree in ONE call, and the packed input row of
  * words.MerkleRemove(key_bytes, length, depth) of every remove -- "key j was removed, and that alone takes the tree from R_j to R_j+1".  The inverse of
  * mfh_merkle_insert_keys: with all-zero inert slots, inserting a batch and removing the same keys restores the table's bytes and the root.
