@@ -104,7 +104,7 @@ EXPORTS = [
     "mfh_sha256_records", "mfh_merkle_set_records", "mfh_merkle_update_rows", "mfh_merkle_update_records",
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
-    "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut",
+    "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
 ]
 
 
@@ -253,6 +253,8 @@ def load_library():
         "mfh_merkle_transfer_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_paths_cut": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
         "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
+        "mfh_merkle_range_rows": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
+        "mfh_merkle_range_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
@@ -835,6 +837,89 @@ class MerkleTree:
         rows, nodes, index, status = self.absent_segments(table, keys, cuts)
         head0 = 256 + 8 * (np.ascontiguousarray(keys).shape[1] + int(table.shape[1]))
         return self._climb_unpack(rows, cuts, head0), nodes, index, status
+
+    # ---- range reads (words.MerkleLink): the records of a key range in key order, their rows, and the same with the path cut
+    def _range(self, table, lo, hi, who, max_links, cut=False, cuts=None, want_rows=True):
+        """the body of count_range, range_rows and range_segments (cut=True, whatever `cuts` is then: _cut judges it): mfh_merkle_range_rows[_cut] with count,
+        index, keys, status and rows allocated here.  Returns (rows or the list of row arrays, index, keys, status, count); rows are cut to the links written (none unless the status is 0)"""
+        c = self._ctx
+        tab, tstride, length = self._table(table, who)
+        lo, hi = bytes(lo), bytes(hi)
+        kb = len(lo)
+        if len(hi) != kb or not 1 <= kb <= 32 or length < 2 * kb:
+            raise MfhError(f"{who}: lo and hi are key_bytes bytes each, 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        vp = ctypes.c_void_p
+        a, b = np.frombuffer(lo, dtype=np.uint8), np.frombuffer(hi, dtype=np.uint8)
+        count = ctypes.c_uint32(0)
+        status = np.zeros(1, dtype=np.uint8)
+
+        def call(m, index, keys, rows_args):
+            fn = c.lib.mfh_merkle_range_rows_cut if cut else c.lib.mfh_merkle_range_rows
+            c._chk(fn(c._h, self._h, _ptr(tab), tstride, length, kb, vp(a.ctypes.data), vp(b.ctypes.data), m, ctypes.byref(count),
+                      vp(index.ctypes.data) if index is not None else None, vp(keys.ctypes.data) if keys is not None else None, *rows_args, vp(status.ctypes.data)))
+            self._keep = []  # (the call waited for the stream)
+
+        if max_links is None or not want_rows:  # the count query: flags and scan alone
+            c._chk(c.lib.mfh_merkle_range_rows(c._h, self._h, _ptr(tab), tstride, length, kb, vp(a.ctypes.data), vp(b.ctypes.data), 0, ctypes.byref(count), None, None,
+                                               None, 0, vp(status.ctypes.data)))
+            self._keep = []
+            if not want_rows:
+                return None, None, None, int(status[0]), int(count.value)
+            max_links = int(count.value)
+        if not isinstance(max_links, (int, np.integer)) or max_links < 0 or max_links > 0xFFFFFFFF:
+            raise MfhError(f"{who}: max_links is a number of links, or None to ask for the count first")
+        m = int(max_links)
+        index = np.zeros(m, dtype=np.uint32)
+        keys = np.zeros((m, 2, kb), dtype=np.uint8)
+        if not cut:
+            rows = np.zeros((m, self._row_bytes(32, length)), dtype=np.uint8)
+            call(m, index, keys, (vp(rows.ctypes.data), rows.shape[1]))
+        else:
+            rows, cargs, keep = self._cut(cuts, who, m, lambda c0: 32 + length + 32 * c0 + (c0 + 7) // 8, m, upper=64)
+            call(m, index, keys, cargs)
+        st, n = int(status[0]), int(count.value)
+        wrote = n if st != 1 else 0  # index and keys
+        nrows = n if st == 0 else 0
+        rows = [r[:nrows] for r in rows] if cut else rows[:nrows]
+        return rows, index[:wrote], keys[:wrote], st, n
+
+    def count_range(self, table, lo, hi):
+        """the number of links of the key range [lo, hi] of an INDEXED table (words.MerkleLink; words.MerkleAbsent has the data model): the live records with
+        record.hi >= lo and record.lo <= hi -- in a well-formed table the members inside [lo, hi] plus one.  mfh_merkle_range_rows with max_links = 0: two
+        launches that stream the table's keys once; waits for the stream.  table: under locate_keys' rules, only read.  lo, hi: key_bytes bytes each, lo <= hi,
+        neither all-zero nor all-0xFF."""
+        return self._range(table, lo, hi, "count_range", None, want_rows=False)[4]
+
+    def range_rows(self, table, lo, hi, max_links=None):
+        """(rows, index, keys, status): the links of the key range [lo, hi] in key order (mfh_merkle_range_rows; waits for the stream).  keys is np.uint8 [n, 2,
+        key_bytes], link i's (lo, hi): with members k_1 < .. < k_n-1 inside the range, (p, k_1), (k_1, k_2), .., (k_n-1, s) -- keys[1:, 0] are exactly the
+        members of the set inside [lo, hi].  index is np.uint32 [n], their slots; rows is np.uint8 [n, 32 + length + 32 depth + ceil(depth / 8)], row i the
+        packed input row of words.MerkleLink(key_bytes, length, depth, reveal) of link i for any `reveal`.
+        status 0: the links chain across the range.  1: more than max_links links; everything comes back empty (count_range says how many).  2: the selected
+        records do not chain, the table is malformed; index and keys are given, no rows.  max_links = None asks for the count first (one more pass over the
+        table's keys); at most 2^16 links a call.
+        A present-key lookup is the range [k, k]: link 1 is (k, its successor), its row's record carries k's payload -- and link 0 publishes k's predecessor,
+        link 1 its successor, to whoever gets the statements."""
+        return self._range(table, lo, hi, "range_rows", max_links)[:4]
+
+    def range_bits(self, table, lo, hi, max_links=None):
+        """range_rows with the rows as np.uint8 [n, 256 + 8 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits) takes for
+        words.MerkleLink(key_bytes, length, depth, reveal)"""
+        rows, index, keys, status = self.range_rows(table, lo, hi, max_links)
+        return self._unpack(rows, 32, int(table.shape[1])), index, keys, status
+
+    def range_segments(self, table, lo, hi, cuts, max_links=None):
+        """range_rows with the path cut at levels `cuts` (mfh_merkle_range_rows_cut).  Returns (rows, nodes, index, keys, status): rows and nodes as
+        path_segments gives them, rows[0][i] being the packed input row of words.MerkleLink(key_bytes, length, c_0, reveal) of link i; a verifier builds segment
+        0's statements with MerkleLink.chain_cut(nodes[:, 0], lo, hi, keys, shown) and link i's upper ones with MerkleClimb.chain(nodes[i]).  The published
+        nodes reveal which subtrees hold the links' records."""
+        rows, index, keys, status, _ = self._range(table, lo, hi, "range_segments", max_links, cut=True, cuts=cuts)
+        return rows, self._climb_nodes(rows), index, keys, status
+
+    def range_segment_bits(self, table, lo, hi, cuts, max_links=None):
+        """range_segments with every segment's rows as 0 / 1 arrays"""
+        rows, nodes, index, keys, status = self.range_segments(table, lo, hi, cuts, max_links)
+        return self._climb_unpack(rows, cuts, 256 + 8 * int(table.shape[1])), nodes, index, keys, status
 
     # ---- removes: the inverse of insert_keys
     def remove_keys(self, table, keys, roots=False):

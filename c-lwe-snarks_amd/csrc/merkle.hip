@@ -46,6 +46,7 @@
 #include "ctx.hpp"
 #include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
+#include "merkle_range.hpp"
 #include "merkle_remove.hpp"
 #include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
@@ -537,6 +538,96 @@ __global__ __launch_bounds__(256) void k_inert_select(const unsigned long long *
     slots[rank++] = 64 * g + (uint32_t)(__ffsll(m) - 1);
     m &= m - 1;
   }
+}
+
+// ---- mfh_merkle_range_rows: the links of a key range [a, b], the live records with hi >= a and lo <= b, in KEY order (merkle_range.hpp has the host side and
+// the scratch).  Records stand in any positions: the table is streamed once, the matching slots are compacted in table order and then ranked by key.  No
+// atomics; no result depends on the order in which threads or workgroups run.
+//   k_range_flags<KW>  k_inert_flags with another predicate and the same output: one thread per record i < n, 256 a workgroup, lo and hi through
+//                      load_record_keys (any alignment and stride, nothing outside the span), flag = live && !(hi < a) && !(b < lo); the wave's ballot is
+//                      mask[i / 64], the workgroup's four popcounts are count[blockIdx].  k_inert_scan and k_inert_select run on that unchanged: total <- the
+//                      number of links, slots[r] <- the r-th matching slot in table order for r < min(total, max_links).
+//   k_range_keys<KW>   one thread per selected slot r < n, n = min(total, max_links) read from the device: dense[r] <- lo | hi of record slots[r], 2 KW words.
+//   k_range_order<KW>  one thread per selected slot r: rank(r) = #{ j < n : (lo_j, j) < (lo_r, r) } over tiles of 256 keys staged in LDS (256 KW words, at
+//                      most 8 KiB; every lane reads the SAME tile entry at a time, a broadcast: no bank conflicts), then order[rank] <- slots[r] and
+//                      okeys[rank] <- lo_r | hi_r.  Ties on lo (a malformed table) break by position r, so rank is a permutation of [0, n) and every output
+//                      word below n is written exactly once.  O(n^2) key compares: the host refuses max_links above 2^16 (mf::kMaxRangeLinks).
+// The grids of the last two are sized from max_links, which the host knows; n comes from `total` on the device.  When total > max_links the call reports
+// status 1 and reads none of slots, dense, order and okeys: the kernels then work on the first max_links matches, inside their arrays of max_links entries.
+struct RangeBounds {
+  uint32_t a[8], b[8];  // key_to_words of the bounds, KW words used
+};
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_range_flags(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t n,
+                                                     const RangeBounds bounds, unsigned long long *__restrict__ mask, uint32_t *__restrict__ count) {
+  __shared__ uint32_t part[4];
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool link = false;
+  if (i < n) {
+    uint32_t lo[KW], hi[KW];
+    link = load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi) && !key_less<KW>(hi, bounds.a) && !key_less<KW>(bounds.b, lo);
+  }
+  const unsigned long long flags = __ballot(link);
+  if (lane == 0) {
+    mask[blockIdx.x * 4 + wave] = flags;  // (the mask array has 4 words a workgroup: words past n / 64 are zero)
+    part[wave] = (uint32_t)__popcll(flags);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) count[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// Reads total[0], slots[r] for r < n = min(total, max_links) -- each below 2^depth, a set bit of the mask -- and that record's keys; writes dense[r], r < n.
+template <int KW>
+__global__ __launch_bounds__(256) void k_range_keys(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes,
+                                                    const uint32_t *__restrict__ total, uint32_t max_links, const uint32_t *__restrict__ slots,
+                                                    uint32_t *__restrict__ dense) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x, n = min(total[0], max_links);
+  if (r >= n) return;
+  uint32_t lo[KW], hi[KW];
+  load_record_keys<KW>(table, stride, span, key_bytes, slots[r], lo, hi);
+#pragma unroll
+  for (int j = 0; j < KW; j++) {
+    dense[(size_t)r * 2 * KW + j] = lo[j];
+    dense[(size_t)r * 2 * KW + KW + j] = hi[j];
+  }
+}
+
+// BARRIERS: a thread with r >= n takes part in every tile's load and in both __syncthreads of every tile and only skips the stores at the end; an early
+// `return` in front of a barrier would hang the workgroup.  Only a workgroup that lies ENTIRELY past n returns, under a test that is the same for all its
+// threads (blockIdx and n alone).  The tile loop's bounds are functions of n alone, so every thread of a workgroup makes the same number of rounds.
+// Reads dense[j] and slots[j] for j < n; writes order[q] and okeys[q] for q < n (rank < n: at most n - 1 entries lie below any entry).
+template <int KW>
+__global__ __launch_bounds__(256) void k_range_order(const uint32_t *__restrict__ dense, const uint32_t *__restrict__ total, uint32_t max_links,
+                                                     const uint32_t *__restrict__ slots, uint32_t *__restrict__ order, uint32_t *__restrict__ okeys) {
+  __shared__ uint32_t tile[256 * KW];
+  const uint32_t n = min(total[0], max_links), r = blockIdx.x * 256 + threadIdx.x;
+  if (blockIdx.x * 256 >= n) return;  // workgroup-uniform: the whole workgroup lies past n
+  const bool mine = r < n;
+  uint32_t lo[KW];
+#pragma unroll
+  for (int j = 0; j < KW; j++) lo[j] = mine ? dense[(size_t)r * 2 * KW + j] : 0u;
+  uint32_t rank = 0;
+  for (uint32_t t0 = 0; t0 < n; t0 += 256) {
+    const uint32_t j = t0 + threadIdx.x, fill = min(256u, n - t0);
+    if (j < n) {
+#pragma unroll
+      for (int w = 0; w < KW; w++) tile[threadIdx.x * KW + w] = dense[(size_t)j * 2 * KW + w];
+    }
+    __syncthreads();
+    for (uint32_t e = 0; e < fill; e++) {
+      uint32_t other[KW];
+#pragma unroll
+      for (int w = 0; w < KW; w++) other[w] = tile[e * KW + w];
+      const bool below = key_less<KW>(other, lo) || (!key_less<KW>(lo, other) && t0 + e < r);  // (lo_j, j) < (lo_r, r)
+      rank += below ? 1u : 0u;
+    }
+    __syncthreads();
+  }
+  if (!mine) return;  // (behind the last barrier)
+  order[rank] = slots[r];
+#pragma unroll
+  for (int j = 0; j < 2 * KW; j++) okeys[(size_t)rank * 2 * KW + j] = dense[(size_t)r * 2 * KW + j];
 }
 
 // k_insert_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
@@ -1524,6 +1615,164 @@ int mfh_merkle_absent_rows_cut(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d
       mf::splice_row(h_rows[0] + (size_t)(u.b0 + b) * h_strides[0], 32, {{k.key(u.b0 + b), key_bytes}, {u.pin_heads + (size_t)b * hp, found ? length : 0}},
                      found ? u.pin_rows + (size_t)b * u.rs : nullptr, 64, c0);
     }
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- the range reads, mfh_merkle_range_rows and mfh_merkle_range_rows_cut (k_range_flags has the kernels, merkle_range.hpp the host side)
+
+// the outputs of a range read next to its KeyCall (whose keys are unused: the bounds are the call's keys)
+struct RangeCall {
+  const uint8_t *h_lo, *h_hi;
+  uint32_t max_links;
+  uint32_t *h_count;
+  uint8_t *h_keys;
+};
+
+// what the two range reads ask of their arguments: mfh_merkle_absent_rows' checks of table and keys in its order, `own` (the rows' stride, or the cuts) in its
+// place between the shapes and the pointers, then the bounds; empty when they are fine
+std::string range_refused(const KeyCall &k, const RangeCall &r, const std::function<const char *()> &own) {
+  if (k.key_bytes < 1 || k.key_bytes > mf::kMaxKeyBytes) return "key_bytes must be in [1, 32]";
+  if (k.length < 2 * k.key_bytes) return "length shorter than the two keys' 2 key_bytes bytes";
+  if (const char *what = records_refused(nullptr, k.table_stride, k.length, 0, "table_stride shorter than length")) return what;
+  if (r.max_links > mf::kMaxRangeLinks) return "max_links above 2^16 (the order kernel is quadratic in the links)";
+  if (const char *what = own()) return what;
+  const std::pair<const void *, const char *> needed[] = {{k.d_table, "d_table"}, {r.h_lo, "h_lo"}, {r.h_hi, "h_hi"}, {r.h_count, "h_count"}, {k.h_status, "h_status"}};
+  for (const auto &p : needed)
+    if (!p.first) return std::string("a range without ") + p.second;
+  if (r.max_links && !k.h_index) return "links (max_links > 0) without h_index";
+  if (mf::key_is_sentinel(r.h_lo, k.key_bytes) || mf::key_is_sentinel(r.h_hi, k.key_bytes)) return "a bound is the all-zero or the all-0xFF key";
+  if (memcmp(r.h_lo, r.h_hi, k.key_bytes) > 0) return "the range is empty (lo > hi)";
+  return {};
+}
+
+// The search of a range read on the table as it stands: flags, scan and -- with max_links > 0 -- select, keys and order, then total | order | okeys back in
+// ONE copy under ONE wait.  Reserves the larger of its own scratch and rows_bytes, what the caller's row driver takes afterwards over the same bytes (the
+// results are on the host by then).  *h_count <- the table's total, always.  total > max_links: status 1 and nothing else written.  Else h_index and h_keys
+// (if any) <- the links in key order and status 0 or 2 (mf::range_status).  *n <- the rows to write: the links on status 0, else 0.
+int range_links(mfh_ctx *c, const KeyCall &k, const RangeCall &r, uint32_t depth, size_t rows_bytes, uint32_t *n) {
+  const uint32_t records = 1u << depth, kw = mf::key_words(k.key_bytes), max_links = r.max_links;
+  const mf::RangeScratch s = mf::range_scratch(depth, max_links, k.key_bytes);
+  if (int rc = work_reserve(c, c->circ_io, std::max(s.bytes, rows_bytes))) return rc;
+  uint8_t *d_work = c->circ_io.as<uint8_t>();
+  unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(d_work + s.mask_at);
+  auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_work + at); };
+  uint32_t *d_count = words(s.count_at), *d_slots = words(s.slots_at), *d_dense = words(s.dense_at), *d_total = words(s.total_at), *d_order = words(s.order_at),
+           *d_okeys = words(s.okeys_at);
+  RangeBounds bounds{};
+  mf::key_to_words(r.h_lo, k.key_bytes, bounds.a);
+  mf::key_to_words(r.h_hi, k.key_bytes, bounds.b);
+  with_key_words(kw, [&](auto KW) {
+    constexpr int W = decltype(KW)::value;
+    {
+      Timer tm(c, 40, records);  // "merkle_range" (mfhip.hip: timing_kind): the flags ...
+      hipLaunchKernelGGL(k_range_flags<W>, dim3(s.nb), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.key_bytes, records, bounds, d_mask, d_count);
+    }
+    {
+      Timer tm(c, 40, 0);  // ... the scan of the workgroups' counts ...
+      hipLaunchKernelGGL(k_inert_scan, dim3(1), dim3(256), 0, c->stream, d_count, s.nb, d_total);
+    }
+    if (!max_links) return;  // the count query
+    {
+      Timer tm(c, 40, 0);  // ... and the slots of the ranks below max_links
+      hipLaunchKernelGGL(k_inert_select, dim3((4 * s.nb + 255) / 256), dim3(256), 0, c->stream, (const unsigned long long *)d_mask, (const uint32_t *)d_count, 4 * s.nb,
+                         max_links, d_slots);
+    }
+    const dim3 grid((max_links + 255) / 256);
+    {
+      Timer tm(c, 41, max_links);  // "merkle_range_order": the links' keys ...
+      hipLaunchKernelGGL(k_range_keys<W>, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.key_bytes, (const uint32_t *)d_total, max_links,
+                         (const uint32_t *)d_slots, d_dense);
+    }
+    {
+      Timer tm(c, 41, max_links);  // ... and their ranks
+      hipLaunchKernelGGL(k_range_order<W>, grid, dim3(256), 0, c->stream, (const uint32_t *)d_dense, (const uint32_t *)d_total, max_links, (const uint32_t *)d_slots,
+                         d_order, d_okeys);
+    }
+  });
+  HIP_TRY(c, hipGetLastError());
+  const size_t back = max_links ? mf::range_result_bytes(max_links, k.key_bytes) : 4;
+  uint32_t *pin = (uint32_t *)pin_acquire(c, c->pin_cw, back);  // total | order | okeys
+  if (!pin) return MFH_ENOMEM;
+  HIP_TRY(c, hipMemcpyAsync(pin, d_total, back, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t total = pin[0];
+  *r.h_count = total;
+  *n = 0;
+  if (total > max_links) {
+    *k.h_status = 1;
+    return MFH_OK;
+  }
+  const uint32_t *order = pin + 1, *okeys = order + max_links;
+  for (uint32_t i = 0; i < total; i++) {
+    k.h_index[i] = order[i];
+    if (r.h_keys) {
+      mf::words_to_key(okeys + (size_t)2 * i * kw, k.key_bytes, r.h_keys + (size_t)2 * i * k.key_bytes);
+      mf::words_to_key(okeys + ((size_t)2 * i + 1) * kw, k.key_bytes, r.h_keys + ((size_t)2 * i + 1) * k.key_bytes);
+    }
+  }
+  *k.h_status = (uint8_t)mf::range_status(okeys, total, kw, bounds.a, bounds.b);
+  if (*k.h_status == 0) *n = total;
+  return MFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_range_rows(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, const uint8_t *h_lo,
+                          const uint8_t *h_hi, uint32_t max_links, uint32_t *h_count, uint32_t *h_index, uint8_t *h_keys, uint8_t *h_inputs, size_t in_stride,
+                          uint8_t *h_status) {
+  const char *who = "mfh_merkle_range_rows";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const uint32_t depth = t->depth;
+  const KeyCall k{who, d_table, table_stride, length, key_bytes, 0, nullptr, 0, h_inputs, in_stride, h_index, h_status, nullptr, nullptr};
+  const RangeCall r{h_lo, h_hi, max_links, h_count, h_keys};
+  const size_t rowb = mf::row_bytes(32, length, depth);  // MerkleLink(key_bytes, length, depth)'s row, MerkleRecord's
+  const std::string what = range_refused(k, r, [&]() -> const char * {
+    return h_inputs && in_stride < rowb ? "in_stride shorter than the row's 32 + length + 32 depth + ceil(depth / 8) bytes" : nullptr;
+  });
+  if (!what.empty()) return fail(c, who, what.c_str());
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hp = mf::record_head_pitch(length);
+  const bool rows = h_inputs && max_links;
+  const size_t rows_bytes = rows ? mf::update_chunk(max_links, rowb, kPathStageBytes) * (mf::staged_stride(mf::row_bytes(32, 32, depth)) + hp + 4) : 0;  // path_rows'
+  uint32_t n = 0;
+  if (int rc = range_links(c, k, r, depth, rows_bytes, &n)) return rc;
+  if (!rows || !n) return MFH_OK;
+  const ChunkFn gather = absent_gather(c, k, depth);
+  return path_rows(c, t, n, h_index, nullptr, rowb, hp, gather, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++)
+      mf::splice_row(h_inputs + (size_t)(u.b0 + b) * in_stride, 32, {{u.pin_heads + (size_t)b * hp, length}}, u.pin_rows + (size_t)b * u.rs, 64, depth);
+  });
+}
+
+int mfh_merkle_range_rows_cut(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, const uint8_t *h_lo,
+                              const uint8_t *h_hi, uint32_t max_links, uint32_t *h_count, uint32_t *h_index, uint8_t *h_keys, uint32_t ncuts, const uint32_t *h_cuts,
+                              uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_status) {
+  const char *who = "mfh_merkle_range_rows_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const uint32_t depth = t->depth;
+  const KeyCall k{who, d_table, table_stride, length, key_bytes, 0, nullptr, 0, nullptr, 0, h_index, h_status, nullptr, nullptr};
+  const RangeCall r{h_lo, h_hi, max_links, h_count, h_keys};
+  const size_t rowb0 = ncuts && h_cuts ? mf::row_bytes(32, length, h_cuts[0]) : 0;  // MerkleLink(key_bytes, length, c_0)'s row
+  const std::string what = range_refused(k, r, [&]() -> const char * { return cuts_refused(max_links, ncuts, h_cuts, depth, h_rows, h_strides, rowb0, mf::climb_row_bytes); });
+  if (!what.empty()) return fail(c, who, what.c_str());
+  HIP_TRY(c, hipSetDevice(c->device));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  const size_t hp = mf::record_head_pitch(length);
+  const uint32_t c0 = h_cuts[0];
+  const size_t rows_bytes = max_links ? climb_rows_scratch(depth, mf::climb_chunk(max_links, rowb0, depth, ncuts, h_cuts, kPathStageBytes), hp, cuts) : 0;
+  uint32_t n = 0;
+  if (int rc = range_links(c, k, r, depth, rows_bytes, &n)) return rc;
+  if (!n) return MFH_OK;
+  const ChunkFn gather = absent_gather(c, k, depth);
+  return climb_rows(c, t, n, h_index, nullptr, cuts, false, rowb0, hp, gather, [&](const Chunk &u) {
+    for (uint32_t b = 0; b < u.k; b++)  // segment 0: the uncut row with c_0 siblings and the low index bits, which the staged row's tail holds
+      mf::splice_row(h_rows[0] + (size_t)(u.b0 + b) * h_strides[0], 32, {{u.pin_heads + (size_t)b * hp, length}}, u.pin_rows + (size_t)b * u.rs, 64, c0);
   });
 }
 

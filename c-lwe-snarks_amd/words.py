@@ -959,6 +959,124 @@ class MerkleAbsent(_OneRoot):
         return _statement_of(root, "MerkleAbsent: the root") + self._query(key)
 
 
+class MerkleLink(_OneRoot):
+    """The statement "the set behind this root has a record whose first P = 2 key_bytes + reveal bytes are these", for a set kept as an indexed Merkle
+    tree (MerkleAbsent has the data model).  Read as (k | k' | the first `reveal` payload bytes) it says: k and k' are ADJACENT in the set -- no member lies
+    strictly between them -- and k's payload begins with these bytes.  With reveal = amount_bytes it publishes a MerkleTransfer balance.
+
+    One statement gives the two reads that MerkleRecord (which hides the record) and MerkleAbsent cannot: "k IS a member, and its payload begins with v" is
+    one link (k, successor); "the members inside [a, b] are exactly k_1 < .. < k_n" is the n + 1 links (p, k_1), (k_1, k_2), .., (k_n, s) with p < a and
+    b < s, which `chain` checks in the clear -- completeness of a range scan, n + 1 proofs of ONE circuit under one CRS (Context.prove_batch_public).
+    SOUNDNESS IS RELATIVE TO THE TABLE INVARIANT, as MerkleAbsent's: whoever accepts a root accepts that the table behind it is well formed; the circuit
+    proves membership of ONE record with this prefix and nothing about the other records.  In a well-formed table a live record (k, k') exists exactly
+    when k is a member or the lower sentinel and k' is the next larger member or the upper sentinel.
+    The circuit is MerkleRecord's body unchanged (_message_chain, _merkle_levels); the first 8 P record bits are PUBLIC GIVEN wires instead of private ones,
+    declared before the leaf and moved behind the root (Circuit.public_last).  No comparator and no equality row: the verifier checks k < k' in the clear
+    (statement refuses anything else).
+    Public wires: the root as 256 computed outputs at statement bits [0, 256), then the 8 P prefix bits, byte j's bit b (LSB first) at 256 + 8 j + b; lu =
+    256 + 8 P.  Private inputs: the remaining 8 (length - P) record bits, `depth` siblings of 8 words, `depth` direction bits.  The input bits, and so the
+    packed row, are MerkleRecord's: 32 zero bytes | record | siblings as words | index bytes.  MerkleTree.range_rows / range_segments find the records of a
+    key range and give the rows for a device table.
+    Sizes (MERKLE_LINK_SIZES): MerkleRecord(length, depth)'s, wire for wire and row for row -- a public input costs what a private one does -- and its depth
+    range: (8, 55, 19) fits Params(d=1 << 20, m=699050), depth 20 needs a cut (MerkleClimb above MerkleLink(.., c_0), chain_cut)."""
+
+    def __init__(self, key_bytes: int, length: int, depth: int, reveal=0):
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.reveal = reveal = self._arg(reveal, 0, None, "reveal is a non-negative number of payload bytes")
+        self.length = length = self._arg(length, 2 * K + reveal, None, "the length is at least 2 key_bytes + reveal bytes")
+        self.depth = self._depth_arg(depth)
+        self.shown_bytes = P = 2 * K + reveal
+        self.w = w = Words()
+        # the public prefix is read by the leaf's gates, so it is declared here and moved behind the root below
+        self.shown = w.c.public(8 * P)
+        self.hidden = w.c.private(8 * (length - P))
+        self.record = list(self.shown) + list(self.hidden)
+        self._tail_wires()
+        self.leaf, self.blocks = _message_chain(w, self.record, length)
+        self.out = cur = _merkle_levels(w, self.leaf, self.siblings, self.dirs)
+        self.root = [w.output(x) for x in cur]
+        w.c.public_last(self.shown)
+
+    @property
+    def lu(self) -> int:
+        return 256 + 8 * self.shown_bytes
+
+    def bits(self, record: bytes, siblings, index: int):
+        """one statement's input bits, public then private: MerkleRecord.bits(record, siblings, index) unchanged -- 256 zeros where the root is computed, the
+        record's bits (the first 8 P of them public), the siblings from the leaf's level up, then the direction bits"""
+        return _input_bits(256, _record_bits("MerkleLink", self.length, record), _tail_bits("MerkleLink", self.depth, siblings, index))
+
+    def shown_of(self, witness_row) -> bytes:
+        """the P public prefix bytes, from a witness row (Circuit.assign's bytes or a row of Context.circuit_assign)"""
+        return bytes(bytearray(witness_row)[32: 32 + self.shown_bytes])
+
+    def _shown(self, shown) -> bytes:
+        shown, K = bytes(shown), self.key_bytes
+        if len(shown) != self.shown_bytes:
+            raise CircuitError(f"MerkleLink: the shown prefix is 2 key_bytes + reveal = {self.shown_bytes} bytes")
+        if shown[:K] >= shown[K: 2 * K]:
+            raise CircuitError("MerkleLink: not a live record (lo < hi)")
+        return shown
+
+    def statement(self, root: bytes, shown: bytes) -> bytes:
+        """the 32 + P statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "a record of the set with root `root` begins with
+        `shown`" = (k | k' | reveal payload bytes): MerklePath.statement's bytes, then the prefix.  Refused unless k < k': an inert slot is no link."""
+        return _statement_of(root, "MerkleLink: the root") + self._shown(shown)
+
+    def _links(self, lo, hi, keys, shown):
+        """the n + 1 prefixes of a range read, after the checks on which the claim "exactly these members" rests"""
+        K = self.key_bytes
+        lo, hi, keys = bytes(lo), bytes(hi), [bytes(k) for k in keys]
+        if len(lo) != K or len(hi) != K or any(len(k) != K for k in keys):
+            raise CircuitError(f"MerkleLink: the bounds and the keys are {K} bytes")
+        if len(keys) < 2:
+            raise CircuitError("MerkleLink: a chain is at least the two keys p and s around the range")
+        if self.reveal:
+            if shown is None or len(shown) != len(keys) - 1:
+                raise CircuitError("MerkleLink: with reveal > 0 a chain takes one shown payload prefix per link: those of p, k_1, .., k_n")
+            shown = [bytes(v) for v in shown]
+            if any(len(v) != self.reveal for v in shown):
+                raise CircuitError(f"MerkleLink: a shown payload prefix is reveal = {self.reveal} bytes")
+        else:
+            if shown is not None and len(shown):
+                raise CircuitError("MerkleLink: with reveal = 0 a chain takes no shown bytes")
+            shown = [b""] * (len(keys) - 1)
+        p, members, s = keys[0], keys[1:-1], keys[-1]
+        if not lo <= hi:
+            raise CircuitError("MerkleLink: the range is lo <= hi")
+        if not p < lo:
+            raise CircuitError("MerkleLink: the first key is not below lo (p < lo)")
+        if not hi < s:
+            raise CircuitError("MerkleLink: the last key is not above hi (hi < s)")
+        if members and not lo <= members[0]:
+            raise CircuitError("MerkleLink: a member below lo (lo <= k_1)")
+        if members and not members[-1] <= hi:
+            raise CircuitError("MerkleLink: a member above hi (k_n <= hi)")
+        if any(not a < b for a, b in zip(members, members[1:])):
+            raise CircuitError("MerkleLink: the members are strictly ascending (k_1 < .. < k_n)")
+        return [keys[i] + keys[i + 1] + shown[i] for i in range(len(keys) - 1)]
+
+    def chain(self, root: bytes, lo: bytes, hi: bytes, keys, shown=None):
+        """the verifier's side of a range read: the n + 1 statements statement(root, keys[i] | keys[i + 1] | shown[i]) of the claim "the members of the set
+        inside [lo, hi] are exactly k_1 < .. < k_n", keys = [p, k_1, .., k_n, s] (n + 2 keys) and shown the n + 1 payload prefixes of `reveal` bytes of p,
+        k_1, .., k_n (required exactly when reveal > 0).  CircuitError unless p < lo <= k_1 < .. < k_n <= hi < s; with n = 0 that is p < lo <= hi < s, the
+        absence of a whole interval.
+        THE CLAIM "EXACTLY THESE MEMBERS" RESTS ON THIS CHECK together with the n + 1 proofs: every link shares a key with the next, so the links tile
+        (p, s) without a gap, and (p, s) covers [lo, hi].  A list that omits a member passes the check -- it is consistent on its face -- but then one of its
+        links is not a record of the table, and no proof verifies against that statement."""
+        return [self.statement(root, link) for link in self._links(lo, hi, keys, shown)]
+
+    def chain_cut(self, nodes_0, lo: bytes, hi: bytes, keys, shown=None):
+        """chain for a path cut at c_0 (this statement being MerkleLink(.., depth = c_0)): nodes_0 is one published level-c_0 node per link, statement i is
+        statement(nodes_0[i], ..) over the subtree that holds link i's record.  The upper statements of link i come from MerkleClimb.chain(nodes[i]) over its
+        whole published list (MerkleTree.range_segments' nodes)."""
+        links = self._links(lo, hi, keys, shown)
+        nodes_0 = [bytes(x) for x in nodes_0]
+        if len(nodes_0) != len(links):
+            raise CircuitError("MerkleLink: one level-c_0 node per link")
+        return [self.statement(node, link) for node, link in zip(nodes_0, links)]
+
+
 class _KeyStep(_TwoRoots):
     """Private base of MerkleInsert and MerkleRemove: a key step, the two record updates of slots p and s under ONE pair of roots, with the key as public
     wires behind the roots.  It holds what the two share -- the argument checks, the two tails' wires, the four level chains over (p, p, s, s), the wiring of
@@ -1363,6 +1481,31 @@ def indexed_transfer(record_p, p: int, record_s, s: int, amount: int, key_bytes:
     return [int(p), int(s)], new
 
 
+def indexed_range(table, key_bytes: int, lo: bytes, hi: bytes):
+    """the ordered slots of the links of the key range [lo, hi] in an indexed table (a uint8 array [n, length]; MerkleLink has the read): the live records
+    with record.hi >= lo and record.lo <= hi, sorted by (record.lo, slot) -- in a well-formed table the records (p, k_1), (k_1, k_2), .., (k_n, s) around
+    and between the members k_1 .. k_n of [lo, hi].  The host reference of MerkleTree.range_rows.  CircuitError for bounds that are not key_bytes bytes,
+    a sentinel bound, or lo > hi."""
+    table = np.asarray(table)
+    K = key_bytes
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= 32 or table.dtype != np.uint8 or table.ndim != 2 or table.shape[1] < 2 * K:
+        raise CircuitError("indexed_range: a uint8 table [n, length], length at least 2 key_bytes, key_bytes in [1, 32]")
+    lo, hi = _checked_key("indexed_range", K, lo, "bounds"), _checked_key("indexed_range", K, hi, "bounds")
+    if lo > hi:
+        raise CircuitError("indexed_range: the range is lo <= hi")
+    def less(a, b):  # a < b per row, big-endian: the first byte that differs decides
+        res, open_ = np.zeros(len(table), dtype=bool), np.ones(len(table), dtype=bool)
+        for j in range(K):
+            res |= open_ & (a[:, j] < b[:, j])
+            open_ &= a[:, j] == b[:, j]
+        return res
+
+    rlo, rhi = table[:, :K], table[:, K: 2 * K]
+    a, b = (np.broadcast_to(np.frombuffer(x, dtype=np.uint8), rlo.shape) for x in (lo, hi))
+    slots = np.flatnonzero(less(rlo, rhi) & ~less(rhi, a) & ~less(b, rlo))
+    return [int(s) for _, s in sorted((rlo[s].tobytes(), int(s)) for s in slots)]
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.
@@ -1372,6 +1515,9 @@ MERKLE_PATH_SIZES = {1: (29139, 51637), 2: (57764, 102502), 3: (86389, 153367), 
 # ... and of MerkleRecord by (length, depth): those of Sha256Message(length) plus 28 625 depth wires and 50 865 depth rows
 MERKLE_RECORD_SIZES = {(0, 1): (56213, 99927), (55, 1): (56667, 100381), (56, 1): (84007, 148937), (119, 1): (84523, 149453), (120, 1): (111863, 198009),
                        (3, 2): (84865, 150819), (55, 2): (85292, 151246), (56, 2): (112632, 199802), (55, 19): (571917, 1015951), (119, 18): (571148, 1014158)}
+# ... and of MerkleLink by (key_bytes, length, depth, reveal): MerkleRecord(length, depth)'s, wire for wire and row for row (the shown prefix is 8 P public
+# inputs where MerkleRecord's record bits are private ones), every entry compiled; it keeps MerkleRecord's depth range
+MERKLE_LINK_SIZES = {(4, 8, 1, 0): (56284, 99998), (8, 55, 1, 8): (56667, 100381), (4, 9, 1, 1): (56292, 100006), (4, 8, 2, 0): (84909, 150863)}
 # ... and of MerkleUpdate by depth: 56 993 depth + 1 026 wires, 101 473 depth + 1 540 rows
 MERKLE_UPDATE_SIZES = {1: (58019, 103013), 2: (115012, 204486), 3: (172005, 305959), 10: (570956, 1016270)}
 # ... and of MerkleRecordUpdate by (length, depth): MERKLE_UPDATE_SIZES[depth] + 2 x SHA256_MESSAGE_SIZES[length] - (1 028, 1 544); frozen=(lo, hi) adds

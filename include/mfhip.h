@@ -540,6 +540,43 @@ int mfh_merkle_paths_cut(mfh_ctx *ctx, const mfh_merkle *t, uint32_t nstmt, cons
 int mfh_merkle_absent_rows_cut(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nq,
                                const uint8_t *h_keys, size_t key_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides,
                                uint32_t *h_index, uint8_t *h_status);
+/* ---- RANGE reads of an indexed table (the data model: mfh_merkle_absent_rows): the links of the key range [lo, hi] in key order, and the packed input row of
+ * words.MerkleLink(key_bytes, length, depth) -- MerkleRecord's row: 32 zero bytes | the record | depth siblings as words | ceil(depth / 8) index bytes -- of
+ * every link.  A LINK of [lo, hi] is a live record (record.lo < record.hi) with record.hi >= lo and record.lo <= hi.  In a well-formed table the links are
+ * (p, k_1), (k_1, k_2), .., (k_n, s), where k_1 < .. < k_n are exactly the members inside [lo, hi], p is the largest key below lo (a member or the all-zero
+ * sentinel) and s the smallest key above hi: n + 1 links, at least one.  A present-key lookup is the range [k, k]: link 1 is (k, successor) with k's payload.
+ *   h_lo, h_hi  the bounds, key_bytes bytes each, lo <= hi, neither a sentinel
+ *   max_links   the most links the caller has room for, at most 2^16 (the ordering is quadratic in the links).  0 with null outputs is the COUNT query
+ *   *h_count    always the number of links of the whole table
+ *   *h_status   0: count <= max_links and the links chain across the range (link 0's lo < lo, every link's hi is the next link's lo, the last link's hi >
+ *               hi) -- h_index, h_keys and the rows are written, count entries each.  1: count > max_links, nothing but *h_count is written.  2: the
+ *               selected records do not chain (or there is none): the table is malformed; h_index and h_keys are written, the rows are not.
+ *   h_index     max_links slots: the links' slots, ordered by (record.lo, slot)
+ *   h_keys      max_links x 2 key_bytes bytes, or null: lo | hi of every link, in that order
+ *   h_inputs    max_links rows at in_stride, or null for no rows: row i the MerkleLink row of link i (its first 2 key_bytes + reveal record bytes are the
+ *               statement's public prefix, whatever `reveal` the statement was built with: the row does not depend on it)
+ *   how         three launches select the links in table order (flags and popcounts per workgroup, one-workgroup scan, select: the inert search of
+ *               mfh_merkle_insert_keys with another predicate), two put them into key order on the device (a dense array of their keys, then every link's
+ *               rank among all of them); count | slots | keys come back in one copy under one wait; the host checks the chain; on status 0 the rows are
+ *               mfh_merkle_absent_rows' -- per chunk k_merkle_paths and the gather of the records, spliced on the host.  No atomics: the result does not depend
+ *               on the order in which threads run.  Both calls run on the context's stream, synchronise it, stage through the context's pinned buffers
+ *               (mfh_scrub_staging covers them) and modify neither the tree nor the table.  One range a call.
+ * mfh_merkle_range_rows_cut: the same with the path cut (the conventions of the cut reads above): segment 0's row i, to h_rows[0], is the packed input row of
+ * MerkleLink(key_bytes, length, c_0) of link i, 32 + length + 32 c_0 + ceil(c_0 / 8) bytes, and segment g >= 1 a MerkleClimb row; max_links rows a segment.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued or written: a null tree; a tree of another device; key_bytes 0 or above
+ * 32; length < 2 key_bytes or > 2^20; table_stride < length; max_links > 2^16; in_stride below the row's bytes (with h_inputs), or for the cut call what the
+ * cut conventions refuse (ncuts = 0 or h_cuts null; cuts that are not 1 <= c_0 < .. < c_G-1 < depth; h_rows or h_strides null; a null pointer in h_rows with
+ * max_links > 0; a stride below its segment's row bytes); d_table, h_lo, h_hi, h_count or h_status null; max_links > 0 with h_index null; a bound that is the
+ * all-zero or the all-0xFF key; lo > hi.
+ * Kernel timing kinds: "merkle_range" (flags, scan, select: 3 per call, 2 for the count query; rows = 2^depth on the first), "merkle_range_order" (keys and
+ * order: 2 per call with max_links > 0; rows = max_links), then per chunk "merkle_paths" and "merkle_absent_rows", or for the cut call "merkle_climb_rows" and
+ * "merkle_absent_rows" and no "merkle_paths". */
+int mfh_merkle_range_rows(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, const uint8_t *h_lo,
+                          const uint8_t *h_hi, uint32_t max_links, uint32_t *h_count, uint32_t *h_index, uint8_t *h_keys, uint8_t *h_inputs, size_t in_stride,
+                          uint8_t *h_status);
+int mfh_merkle_range_rows_cut(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes,
+                              const uint8_t *h_lo, const uint8_t *h_hi, uint32_t max_links, uint32_t *h_count, uint32_t *h_index, uint8_t *h_keys, uint32_t ncuts,
+                              const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_status);
 /* nk sequential key REMOVES from an indexed table (the data model: mfh_merkle_absent_rows) and its tree in ONE call, and the packed input row of
  * words.MerkleRemove(key_bytes, length, depth) of every remove -- "key j was removed, and that alone takes the tree from R_j to R_j+1".  The inverse of
  * mfh_merkle_insert_keys: with all-zero inert slots, inserting a batch and removing the same keys restores the table's bytes and the root.
