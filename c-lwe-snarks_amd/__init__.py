@@ -251,6 +251,9 @@ def load_library():
         "mfh_merkle_remove_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_transfer_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, vp, sz, vp, vp, vp]),
         "mfh_merkle_transfer_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, sz, vp, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_adjust_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+        "mfh_merkle_adjust_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, sz, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_balance_sum": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, vp]),
         "mfh_merkle_paths_cut": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
         "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
         "mfh_merkle_range_rows": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
@@ -987,6 +990,99 @@ class MerkleTree:
         out = self.transfer_key_segments(table, from_keys, to_keys, amounts, cuts, amount_bytes)
         head = self._step_head(table, from_keys, 2, 128) + np.ascontiguousarray(from_keys).shape[1] + int(amount_bytes)
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
+
+    # ---- deposits and withdrawals: what funds and drains the ledger, and its supply
+    def _adjust(self, who, table, keys, amounts, sides, amount_bytes, roots=False, cut=False, cuts=None):
+        """the body of adjust_keys and, with cut=True, adjust_key_segments: mfh_merkle_adjust_keys[_cut] with rows, index, status and roots allocated here"""
+        c = self._ctx
+        tab, tstride, length, k = self._keys(table, keys, who)
+        nk, kb = k.shape
+        vp = ctypes.c_void_p
+        ab = amount_bytes
+        if not isinstance(ab, (int, np.integer)) or not 1 <= ab <= 8 or length < 2 * kb + ab:
+            raise MfhError(f"{who}: 1 <= amount_bytes <= 8 and 2 key_bytes + amount_bytes <= length")
+        try:
+            values = [int(a) for a in amounts]
+            dirs = [0] * nk if sides is None else [int(x) for x in sides]
+        except (TypeError, ValueError):
+            values = dirs = None
+        if values is None or len(values) != nk or any(not 0 <= a < 1 << 64 for a in values):
+            raise MfhError(f"{who}: amounts are nk integers in [0, 2^64), one a step")
+        if len(dirs) != nk or any(x not in (0, 1) for x in dirs):
+            raise MfhError(f"{who}: sides are nk values 0 (a deposit) or 1 (a withdrawal), one a step")
+        amt = np.array(values, dtype=np.uint64).reshape(nk)
+        side = np.array(dirs, dtype=np.uint8).reshape(nk)
+        head = 64 + kb + int(ab) + 1 + length
+        if not cut:
+            rows = np.zeros((nk, head + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
+            out = (vp(rows.ctypes.data), rows.shape[1])
+        else:
+            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 32 * c0 + (c0 + 7) // 8, nk)
+        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots or cut else None
+        index = np.zeros(nk, dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        call = c.lib.mfh_merkle_adjust_keys_cut if cut else c.lib.mfh_merkle_adjust_keys
+        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, int(ab), nk, vp(k.ctypes.data), kb, vp(amt.ctypes.data), vp(side.ctypes.data) if sides is not None else None,
+                    *out, vp(r.ctypes.data) if r is not None else None, vp(index.ctypes.data), vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif r is not None:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        if not cut:
+            return (rows, index, r) if roots else (rows, index)
+        return rows, self._cut_nodes(rows, r), index
+
+    def adjust_keys(self, table, keys, amounts, sides=None, amount_bytes=8, roots=False):
+        """(rows, index): nk sequential DEPOSITS and WITHDRAWALS on the accounts of an INDEXED table whose records carry a balance (words.MerkleTransfer has the
+        data model: bytes [2 key_bytes, 2 key_bytes + amount_bytes) of a record, big-endian) and this tree in one call (mfh_merkle_adjust_keys; waits for the
+        stream).  Step j adds amounts[j] to the balance of the record whose own key is keys[j] (sides[j] = 0, a deposit) or takes it off (sides[j] = 1, a
+        withdrawal); sides=None: all deposits.  An account may occur in any number of steps, and a withdrawal may spend what an earlier deposit of the batch
+        delivered.  rows is np.uint8 [nk, 64 + key_bytes + amount_bytes + 1 + length + 32 depth + ceil(depth / 8)]: row j is the packed input row of
+        words.MerkleAdjust(key_bytes, length, depth, amount_bytes) taken from table and tree as they stood before step j.  index is np.uint32 [nk]: the
+        account's slot.  With roots=True a triple whose last element is np.uint8 [nk + 1, 32], the roots R_0 .. R_nk: statement j is
+        MerkleAdjust.statement(R_j, R_j+1, keys[j], amounts[j], sides[j]).
+        table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, repeats allowed.  amounts: nk integers
+        below 2^(8 amount_bytes).  MfhError with the library's text, table and tree untouched, when a key is not a member, a withdrawal overdraws its account
+        or a deposit takes it past 2^(8 amount_bytes) - 1."""
+        return self._adjust("adjust_keys", table, keys, amounts, sides, amount_bytes, roots)
+
+    def adjust_bits(self, table, keys, amounts, sides=None, amount_bytes=8, roots=False):
+        """adjust_keys with the rows as np.uint8 [nk, 512 + 8 (key_bytes + amount_bytes + 1) + 8 length + 257 depth] of 0 / 1: what
+        Context.circuit_assign(prog, bits) takes for words.MerkleAdjust(key_bytes, length, depth, amount_bytes)"""
+        out = self.adjust_keys(table, keys, amounts, sides, amount_bytes, roots)
+        head = np.ascontiguousarray(keys).shape[1] + int(amount_bytes) + 1 + int(table.shape[1])
+        return (self._unpack(out[0], 64, head),) + tuple(out[1:])
+
+    def adjust_key_segments(self, table, keys, amounts, cuts, sides=None, amount_bytes=8):
+        """adjust_keys with the path cut at levels `cuts` (mfh_merkle_adjust_keys_cut).  Returns (rows, nodes, index), rows and nodes shaped as
+        update_record_segments returns them: rows[0][j] is the packed input row of words.MerkleAdjust(key_bytes, length, c_0, amount_bytes) of step j --
+        the statement itself over the subtree of height c_0, it has one pair of tops -- and rows[g][j], g >= 1, that of words.MerkleSegment(c_g - c_g-1);
+        nodes is np.uint8 [nk, G + 1, 2, 32], the published pairs of every step, (X_G, X_G') = (R_j, R_j+1): segment 0's statement is
+        MerkleAdjust.statement(*nodes[j, 0], keys[j], amounts[j], sides[j]), the upper ones MerkleSegment.chain(nodes[j]).  index as adjust_keys gives it."""
+        return self._adjust("adjust_key_segments", table, keys, amounts, sides, amount_bytes, cut=True, cuts=cuts)
+
+    def adjust_key_segment_bits(self, table, keys, amounts, cuts, sides=None, amount_bytes=8):
+        """adjust_key_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.adjust_key_segments(table, keys, amounts, cuts, sides, amount_bytes)
+        head = 64 + np.ascontiguousarray(keys).shape[1] + int(amount_bytes) + 1 + int(table.shape[1])
+        return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 257 * c0),) + tuple(out[1:])
+
+    def total_balance(self, table, key_bytes, amount_bytes=8):
+        """(sum, live): the SUPPLY of an indexed table whose records carry a balance -- the sum, a Python int, of the balances (bytes [2 key_bytes, 2 key_bytes
+        + amount_bytes), big-endian) of all live records (lo < hi), and their number (mfh_merkle_balance_sum: two launches, a 128-bit sum, no atomics; waits
+        for the stream).  What stands in the balance bytes of a slot that is not live does not count.  transfer_keys leaves the sum as it is; adjust_keys
+        changes it by the batch's deposits less its withdrawals.  table: under update_records' rules, only read."""
+        c = self._ctx
+        who = "total_balance"
+        tab, tstride, length = self._table(table, who)
+        if not all(isinstance(x, (int, np.integer)) for x in (key_bytes, amount_bytes)) or not 1 <= key_bytes <= 32 or not 1 <= amount_bytes <= 8 \
+                or length < 2 * key_bytes + amount_bytes:
+            raise MfhError(f"{who}: 1 <= key_bytes <= 32, 1 <= amount_bytes <= 8 and 2 key_bytes + amount_bytes <= length")
+        total = (ctypes.c_uint64 * 2)()
+        live = ctypes.c_uint32()
+        c._chk(c.lib.mfh_merkle_balance_sum(c._h, self._h, _ptr(tab), tstride, length, int(key_bytes), int(amount_bytes), total, ctypes.byref(live)))
+        self._keep = []
+        return int(total[0]) | int(total[1]) << 64, int(live.value)
 
 
 class Context:

@@ -32,6 +32,8 @@
 // one pass, then the steps below (the host's plan: merkle_remove.hpp).
 // k_balance_gather: mfh_merkle_transfer_keys, a batch of sequential transfers between the accounts of an indexed table in one call -- the keys located as above,
 // the located records' balances read behind the search, then the steps below (the host's plan: merkle_transfer.hpp).
+// k_adjust_records: mfh_merkle_adjust_keys, a batch of sequential deposits and withdrawals in one call -- the search and the balances as for the transfers, ONE
+// new record a step (the host's plan: merkle_adjust.hpp), then the record updates above.  k_balance_sum, k_balance_fold: mfh_merkle_balance_sum, the supply.
 // k_insert_records, k_remove_records, k_transfer_records: what a batch of key steps ends with -- all 2 nk new records built in one launch from the step's plan,
 // then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
 // (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
@@ -44,6 +46,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "merkle_adjust.hpp"
 #include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
 #include "merkle_range.hpp"
@@ -776,6 +779,21 @@ __global__ __launch_bounds__(256) void k_balance_gather(const uint8_t *__restric
   balance[u] = value;
 }
 
+// unit u of a new record that differs from a table record in its balance alone (k_transfer_records, k_adjust_records): the record at byte `rec` of the table
+// as it stood before the batch, with bytes [2K, 2K + A) <- the A bytes of slot `slot` of the uploaded balances `bal` (bal_span bytes).  Bytes at or past
+// `length`: zero
+__device__ __forceinline__ uint4 rebalanced_unit(const uint8_t *__restrict__ table, int64_t rec, int64_t table_span, const uint8_t *__restrict__ bal, int64_t slot,
+                                                 int64_t bal_span, uint32_t u, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length) {
+  const int64_t o = 16 * (int64_t)u, f0 = 2 * (int64_t)key_bytes, f1 = f0 + amount_bytes;
+  const uint4 v = load_unit_within(table, rec + o, rec + min(o + 16, (int64_t)length), table_span);  // the keys and the payload behind the balance
+  uint4 out = merge_unit(merge_unit(make_uint4(0, 0, 0, 0), v, o, 0, f0), v, o, f1, length);
+  if (o < f1 && o + 16 > f0) {  // the balance
+    const int64_t at = slot * amount_bytes - f0;  // the record's byte x is bal's byte at + x
+    out = merge_unit(out, load_unit_within(bal, at + o, at + min(o + 16, f1), bal_span), o, f0, f1);
+  }
+  return out;
+}
+
 // k_transfer_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
 // aligned).  One item per record r and 16-byte unit u; the store is the whole unit.  With (p, s, spare) = plan[3 j ..] of transfer j (merkle_transfer.hpp):
 //   record 2 j      the table's record p as it stood before the batch, with bytes [2K, 2K + A) <- the sender's new balance, bal[2 j A ..]
@@ -792,15 +810,95 @@ __global__ __launch_bounds__(256) void k_transfer_records(const uint8_t *__restr
   const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (2 nk units < 2^32: checked by the host)
   if (g >= 2 * nk * units) return;
   const uint32_t r = g / units, u = g - r * units;
-  const int64_t o = 16 * (int64_t)u, f0 = 2 * (int64_t)key_bytes, f1 = f0 + amount_bytes, bal_span = (int64_t)2 * nk * amount_bytes;
   const int64_t rec = (int64_t)((size_t)(uint32_t)plan[3 * (r >> 1) + (r & 1)] * table_stride);
-  const uint4 v = load_unit_within(table, rec + o, rec + min(o + 16, (int64_t)length), table_span);  // the keys and the payload behind the balance
-  uint4 out = merge_unit(merge_unit(make_uint4(0, 0, 0, 0), v, o, 0, f0), v, o, f1, length);
-  if (o < f1 && o + 16 > f0) {  // the balance
-    const int64_t at = (int64_t)r * amount_bytes - f0;  // the record's byte x is bal's byte at + x
-    out = merge_unit(out, load_unit_within(bal, at + o, at + min(o + 16, f1), bal_span), o, f0, f1);
+  fresh[g] = rebalanced_unit(table, rec, table_span, bal, r, (int64_t)2 * nk * amount_bytes, u, key_bytes, amount_bytes, length);
+}
+
+// ---- mfh_merkle_adjust_keys: the nk new records of a batch of deposits and withdrawals (merkle_adjust.hpp), and mfh_merkle_balance_sum: the table's supply.
+//
+// k_adjust_records, ONE launch per call: all nk new records of the batch into `fresh`, record j at j * pitch bytes (pitch = ceil(length / 16) units, 16-byte
+// aligned).  One item per record j and 16-byte unit u; the store is the whole unit.  Record j is the table's record plan[j] as it stood before the batch, with
+// bytes [2K, 2K + A) <- the account's balance right after step j, bal[j A ..] (the plan's running balance, big-endian).  An adjust changes nothing else of a
+// record, so every source is the table as it stood BEFORE the batch or the uploaded balances -- one launch, no ordering among the items, and the table is only
+// read, even where an account occurs in many steps.  The unit is k_transfer_records' (rebalanced_unit): load_unit_within fetches the 16 bytes of a source that
+// line up with the unit, merge_unit takes each range's bytes under per-dword byte masks, for any alignment, stride, K and A.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [bal, bal + nk A) and the plan.
+__global__ __launch_bounds__(256) void k_adjust_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ bal,
+                                                        const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t nk,
+                                                        uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nk units < 2^32: checked by the host)
+  if (g >= nk * units) return;
+  const uint32_t r = g / units, u = g - r * units;
+  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[r] * table_stride);
+  fresh[g] = rebalanced_unit(table, rec, table_span, bal, r, (int64_t)nk * amount_bytes, u, key_bytes, amount_bytes, length);
+}
+
+// The supply: the sum of the balances of all LIVE records and their number, two launches, no atomics (integer addition: the result does not depend on the
+// order anyway).  The sum is 128 bits, two 64-bit words with the carry out of the low word: 2^depth balances below 2^64 stay below 2^(64 + depth) <= 2^88.
+//   k_balance_sum<KW>  one thread per record i < n, 256 a workgroup: lo | hi through load_record_keys (any alignment and stride, nothing outside the table's span),
+//                      live = lo < hi; the A balance bytes as k_balance_gather reads them, 0 for a record that is not live (whatever its bytes) or past n.  A
+//                      wave reduces (lo, hi, live) with lane shuffles, the workgroup's four waves meet in LDS (96 bytes), thread 0 writes part[3 blockIdx ..].
+//   k_balance_fold     ONE workgroup of 256 threads: thread t adds the partials t, t + 256, ..., then the same reduction; out <- sum lo | sum hi | live.
+struct Supply {
+  unsigned long long lo, hi, live;
+};
+
+__device__ __forceinline__ void supply_add(Supply &a, unsigned long long lo, unsigned long long hi, unsigned long long live) {
+  a.lo += lo;
+  a.hi += hi + (a.lo < lo);  // the carry out of the low word
+  a.live += live;
+}
+
+// the workgroup's sum in thread 0 (256 threads, all of them call); sh: 12 words of LDS
+__device__ __forceinline__ Supply supply_reduce(Supply s, unsigned long long *sh) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) supply_add(s, __shfl_down(s.lo, off), __shfl_down(s.hi, off), __shfl_down(s.live, off));
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh[3 * wave] = s.lo;
+    sh[3 * wave + 1] = s.hi;
+    sh[3 * wave + 2] = s.live;
   }
-  fresh[g] = out;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (uint32_t w = 1; w < 4; w++) supply_add(s, sh[3 * w], sh[3 * w + 1], sh[3 * w + 2]);
+  return s;
+}
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_balance_sum(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t amount_bytes, uint32_t n,
+                                                     unsigned long long *__restrict__ part) {
+  __shared__ unsigned long long sh[12];
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  Supply s{0, 0, 0};
+  if (i < n) {
+    uint32_t lo[KW], hi[KW];
+    if (load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi)) {
+      const int64_t a = (int64_t)((size_t)i * stride) + 2 * (int64_t)key_bytes;
+      const uint4 v = load_unit_within(table, a, a + amount_bytes, span);
+      const unsigned long long be = (unsigned long long)__builtin_bswap32(v.x) << 32 | __builtin_bswap32(v.y);  // byte 0 in the top 8 bits
+      s.lo = be >> (8 * (8 - amount_bytes));
+      s.live = 1;
+    }
+  }
+  s = supply_reduce(s, sh);
+  if (threadIdx.x == 0) {
+    part[3 * (size_t)blockIdx.x] = s.lo;
+    part[3 * (size_t)blockIdx.x + 1] = s.hi;
+    part[3 * (size_t)blockIdx.x + 2] = s.live;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_balance_fold(const unsigned long long *__restrict__ part, uint32_t nb, unsigned long long *__restrict__ out) {
+  __shared__ unsigned long long sh[12];
+  Supply s{0, 0, 0};
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) supply_add(s, part[3 * (size_t)b], part[3 * (size_t)b + 1], part[3 * (size_t)b + 2]);
+  s = supply_reduce(s, sh);
+  if (threadIdx.x == 0) {
+    out[0] = s.lo;
+    out[1] = s.hi;
+    out[2] = s.live;  // (at most 2^24: the caller reads its low word)
+  }
 }
 
 }  // namespace
@@ -2009,9 +2107,156 @@ int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table,
   });
 }
 
+// mfh_merkle_adjust_keys (k.cuts = null: one row of the whole depth a step) and mfh_merkle_adjust_keys_cut (segment 0's row an adjust over c_0 levels to
+// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  A step is ONE record update, so this is the
+// one-record driver beside pair_reserve / pair_updates, whose scratch, chunks and launches stay what they are.  The front of the scratch, kept for the whole
+// call: fresh = the nk new records at a pitch of record_head_pitch(length) | the plan, one word a step | the nk new balances, A bytes each; behind its bytes
+// rounded up to 16 the search with the nu balances behind it, then per chunk update_rows' scratch.
+int adjust_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const uint64_t *h_amounts, const uint8_t *h_sides, uint32_t amount_bytes) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes, A = amount_bytes;  // d0: the levels of the adjust's own row
+  const size_t rowb = mf::row_bytes(64, (size_t)K + A + 1 + length, d0);
+  const std::string what = keys_refused(k, depth, "adjusts", true, [&]() -> const char * {
+    if (A < 1 || A > mf::kMaxAmountBytes) return "amount_bytes must be in [1, 8]";
+    if (length < 2 * K + A) return "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes";
+    if (k.cuts) return cuts_refused(nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
+    return k.h_inputs && k.in_stride < rowb ? "in_stride shorter than the row's 64 + key_bytes + amount_bytes + 1 + length + 32 depth + ceil(depth / 8) bytes" : nullptr;
+  }, false);
+  if (!what.empty()) return fail(c, k.who, what.c_str());
+  if (nk && !h_amounts) return fail(c, k.who, "adjusts without h_amounts");
+  for (uint32_t j = 0; j < nk; j++) {
+    if (h_sides && h_sides[j] > 1) return fail(c, k.who, "a side is neither 0 (a deposit) nor 1 (a withdrawal)");
+    if (h_amounts[j] > mf::balance_limit(A)) return fail(c, k.who, "an amount does not fit amount_bytes bytes");
+  }
+  if (!nk) return MFH_OK;
+  mf::KeyPlan keys;
+  mf::keys_prepare(k.h_keys, k.key_stride, K, nk, keys);
+  const uint32_t nu = keys.nu, n = 1u << depth;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hp = mf::record_head_pitch(length), fresh_bytes = (size_t)nk * hp, plan_bytes = (size_t)nk * 4, bal_bytes = (size_t)nk * A;
+  const size_t skip = (fresh_bytes + plan_bytes + bal_bytes + 15) & ~(size_t)15;
+  const uint32_t ch = mf::update_chunk(nk, rowb + (k.cuts ? mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, skip + std::max(key_search_tail_at(nu, K) + (size_t)nu * 8, update_rows_bytes(depth, ch, 2 * hp, 1, k.cuts)))) return rc;
+  std::vector<uint32_t> rec(nu);
+  std::vector<uint64_t> balance(nu);
+  {  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
+    const SearchTail gather{(size_t)nu * 8, [&](const uint32_t *d_res, uint8_t *d_out) {
+      Timer tm(c, 37, nu);  // "merkle_balances" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_balance_gather, dim3((nu + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), K, A, n, d_res + nu, nu,
+                         reinterpret_cast<unsigned long long *>(d_out));
+    }};
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + skip, &res, &gather)) return rc;
+    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
+    memcpy(balance.data(), res + (size_t)2 * nu, (size_t)nu * 8);
+  }
+  // b. the plan: the running balance of every account through the steps in order
+  mf::AdjustPlan plan;
+  mf::adjust_plan(nk, keys.slot.data(), h_amounts, h_sides, A, rec.data(), balance.data(), plan);
+  memcpy(k.h_index, plan.idx.data(), (size_t)nk * 4);
+  memcpy(k.h_status, plan.status.data(), nk);
+  if (plan.failed) {
+    static const char *const why[] = {"", "a key is not a member of the set (h_status 1)", "", "a withdrawal overdraws its account's balance at that step (h_status 3)",
+                                      "a deposit takes its account's balance past 2^(8 amount_bytes) - 1 (h_status 4)"};
+    uint32_t first = 0;
+    while (!plan.status[first]) first++;
+    return fail(c, k.who, why[plan.status[first]]);
+  }
+  // c. the plan's words and the nk new balances go up; ONE launch builds the nk new records
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_bal = d_plan + plan_bytes;
+  std::vector<uint8_t> amounts((size_t)nk * A);
+  {
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, plan_bytes + bal_bytes);
+    if (!pin_up) return MFH_ENOMEM;
+    memcpy(pin_up, plan.idx.data(), plan_bytes);
+    for (uint32_t j = 0; j < nk; j++) {
+      mf::balance_bytes(plan.fresh[j], A, pin_up + plan_bytes + (size_t)j * A);
+      mf::balance_bytes(h_amounts[j], A, amounts.data() + (size_t)j * A);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, plan_bytes + bal_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {
+    Timer tm(c, 42, nk);  // "merkle_adjust_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nk * (hp / 16);
+    hipLaunchKernelGGL(k_adjust_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), (const uint8_t *)d_bal,
+                       (const int32_t *)d_plan, K, A, length, nk, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  // d. the nk record updates; a row: k | v | side | the old record
+  const Pairs chunks{ch, skip, true};
+  ChunkFn rows_out;
+  if (k.h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b < u.k; b++) {
+        const uint32_t j = u.b0 + b;
+        const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs, side = h_sides ? h_sides[j] : (uint8_t)0;
+        uint8_t *row = k.h_inputs + (size_t)j * k.in_stride;
+        mf::splice_row(row, 64, {{k.key(j), K}, {amounts.data() + (size_t)j * A, A}, {&side, 1}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
+        if (k.cuts) mf::splice_cut_tail(row + 64 + K + A + 1 + (size_t)length, staged, d0, k.h_index[j]);
+      }
+    };
+  return record_updates(c, t, nk, k.h_index, d_table, k.table_stride, length, d_fresh, hp, k.h_roots, rowb, &chunks, rows_out, k.cuts);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mfh_merkle_adjust_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                           const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots,
+                           uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_adjust_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return adjust_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_index, h_status, h_roots, nullptr}, d_table, h_amounts,
+                     h_sides, amount_bytes);
+}
+
+int mfh_merkle_adjust_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                               const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint32_t ncuts, const uint32_t *h_cuts,
+                               uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_adjust_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return adjust_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table, h_amounts,
+                     h_sides, amount_bytes);
+}
+
+int mfh_merkle_balance_sum(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                           uint64_t h_sum[2], uint32_t *h_live) {
+  const char *who = "mfh_merkle_balance_sum";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
+  if (amount_bytes < 1 || amount_bytes > mf::kMaxAmountBytes) return fail(c, who, "amount_bytes must be in [1, 8]");
+  if (length < 2 * key_bytes + amount_bytes) return fail(c, who, "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes");
+  if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
+  if (!d_table) return fail(c, who, "a sum without d_table");
+  if (!h_sum) return fail(c, who, "a sum without h_sum");
+  const uint32_t n = 1u << t->depth, nb = (n + 255) / 256;
+  const int64_t span = (int64_t)(((size_t)n - 1) * table_stride + length);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = work_reserve(c, c->circ_io, ((size_t)nb + 1) * 24)) return rc;  // the workgroups' partials | the result
+  unsigned long long *d_part = c->circ_io.as<unsigned long long>(), *d_out = d_part + (size_t)3 * nb;
+  void (*kernel)(const uint8_t *, size_t, int64_t, uint32_t, uint32_t, uint32_t, unsigned long long *) = nullptr;
+  with_key_words(mf::key_words(key_bytes), [&](auto KW) { kernel = k_balance_sum<decltype(KW)::value>; });
+  {
+    Timer tm(c, 43, n);  // "merkle_balance_sum" (mfhip.hip: timing_kind)
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, c->stream, d_table, table_stride, span, key_bytes, amount_bytes, n, d_part);
+  }
+  {
+    Timer tm(c, 43, 0);  // ... the fold: no record
+    hipLaunchKernelGGL(k_balance_fold, dim3(1), dim3(256), 0, c->stream, (const unsigned long long *)d_part, nb, d_out);
+  }
+  HIP_TRY(c, hipGetLastError());
+  uint64_t *pin = (uint64_t *)pin_acquire(c, c->pin_cw, 20);
+  if (!pin) return MFH_ENOMEM;
+  HIP_TRY(c, hipMemcpyAsync(pin, d_out, 20, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  h_sum[0] = pin[0];
+  h_sum[1] = pin[1];
+  if (h_live) memcpy(h_live, pin + 2, 4);
+  return MFH_OK;
+}
 
 int mfh_merkle_transfer_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
                              const uint8_t *h_from, const uint8_t *h_to, size_t key_stride, const uint64_t *h_amounts, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots,

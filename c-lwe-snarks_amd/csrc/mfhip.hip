@@ -1155,6 +1155,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_climb_rows")) return 39;  // k_merkle_climb_rows of the cut reads (mfh_merkle_paths_cut, mfh_merkle_absent_rows_cut): one per chunk; rows = the chunk's statements x segments
   if (!strcmp(which, "merkle_range")) return 40;  // k_range_flags, k_inert_scan, k_inert_select of the range reads (mfh_merkle_range_rows, _cut): three per call, two for the count query; rows = the table's 2^depth records on the first
   if (!strcmp(which, "merkle_range_order")) return 41;  // k_range_keys, k_range_order of the range reads: two per call with max_links > 0; rows = max_links, the grids' bound (the links n are on the device at launch; n when the count was asked first)
+  if (!strcmp(which, "merkle_adjust_records")) return 42;  // k_adjust_records of mfh_merkle_adjust_keys (merkle.hip): one per call; rows = the nk new records
+  if (!strcmp(which, "merkle_balance_sum")) return 43;  // k_balance_sum, k_balance_fold of mfh_merkle_balance_sum: two per call; rows = the table's 2^depth records on the first, 0 on the fold
   return -1;
 }
 

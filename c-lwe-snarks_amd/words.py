@@ -57,6 +57,10 @@ Whole statements built from that compression, the result 256 computed public out
     MerkleTransfer(key_bytes, length, depth, amount_bytes=8, joined=True)   "v moved from the account k_from to the account k_to, and that alone takes the
                             tree from R to R'": two live records whose balances (bytes [2K, 2K + A), big-endian) become b_p - v and b_s + v with no borrow
                             and no carry; lu = 512 + 16 key_bytes + 8 amount_bytes; the same joined=False form.
+    MerkleAdjust(key_bytes, length, depth, amount_bytes=8)   "the balance of the account k went up by v (side 0, a deposit) or down by v (side 1, a
+                            withdrawal), and that alone takes the tree from R to R'": ONE live record whose balance becomes b + v or b - v through one ripple
+                            with the side as carry in, the carry out tied to the side; lu = 512 + 8 (key_bytes + amount_bytes + 1); MerkleRecordUpdate's
+                            depth range, (8, 55, 9, 8) fits d = 2^20.
     MerkleSegment(levels)   "one node changed from X to X', and that alone takes its ancestor `levels` levels up from Y to Y'" (lu = 1024, the two nodes
                             given, the two tops computed): one level range of a path cut by segment_levels(depth, cuts); MerkleUpdate's sizes, 10 levels
                             fit d = 2^20.  chain(nodes) turns the published node pairs of a transition into the upper segments' statements.
@@ -1363,6 +1367,99 @@ class MerkleTransfer(_KeyStep):
         return self._step_bits((k_from, k_to, amount), (old_p, old_s), siblings_p, index_p, siblings_s, index_s)
 
 
+class MerkleAdjust(_TwoRoots):
+    """The statement "the balance of the account with key k went up by v (side 0, a deposit) or down by v (side 1, a withdrawal), and that alone takes the
+    tree from root R to root R'": ONE record update of the indexed table with balances -- what funds and drains the ledger that MerkleTransfer moves
+    value within.
+
+    The data model is MerkleTransfer's.  amount_bytes = A, 1 <= A <= 8; the BALANCE of a record is its bytes [2K, 2K + A), an unsigned big-endian
+    integer, so length >= 2K + A; an adjust touches nothing else of the record.
+    Public wires, in this order: R as 256 computed outputs at statement bits [0, 256), R' at [256, 512), the 8K given bits of k, the 8A of v -- v as A
+    big-endian bytes, byte j's bit b (LSB first) at 8 j + b, as MerkleTransfer places its amount -- and one byte `side`: its bit 0 is the direction, its
+    bits 1 .. 7 are asserted 0.  lu = 512 + 8 (K + A + 1).  statement(R, R', k, v, side) is MerkleUpdate.statement's 64 bytes, then k, v as A bytes and
+    the side byte.
+    Private inputs, in this order: the old record (8 * length bits, byte j's bit b at 8 j + b); `depth` siblings of 8 words from the leaf's level up;
+    `depth` direction bits -- _tail_wires, as MerkleRecordUpdate has them.  nin = 512 + 8 (K + A + 1) + 8 length + 257 depth.  The packed row: 64 zero
+    bytes | k | v | side | old record | depth siblings as words | ceil(depth / 8) index bytes.
+    The body.  The new record is not an input: it is the old record's wires with the 8A balance wires replaced by b + (v XOR side) + side -- ONE ripple of
+    full adders whose carry in is the side wire and whose second operand is v_i XOR side (an XOR a bit): b + v for side 0, b + NOT v + 1 = b - v mod
+    2^(8A) for side 1.  The carry out is tied to the side wire (assert_same).  Two record chains (_message_chain) and MerkleUpdate's two level chains over
+    the shared tail (_root_outputs).  Further assert_same: k = old[0, K).  One comparator: less_than(lo, hi) = 1, the record is live.  The sentinel keys
+    are refused as for members.
+    Soundness.  Keys and the rest of the payload are the old record's wires, so every record's lo and hi are what they were: the table's invariant
+    (MerkleAbsent) is kept.  By the invariant k is the lo of at most one live record, so the record opened is the account of k and no other.  With
+    carry = side the new balance is the INTEGER b + v or b - v: a deposit's carry out must be 0, so b + v <= 2^(8A) - 1, no overflow; a withdrawal's
+    carry out of b + (2^(8A) - 1 - v) + 1 must be 1, which is b >= v, no borrow, so no overdraft.  v = 0 is a no-op with R' = R in either direction
+    (b + 0 carries 0; b + (2^(8A) - 1) + 1 = b + 2^(8A) carries 1).  The sum of all live balances therefore changes by exactly +v or -v.
+    What it does not cover: like MerkleInsert, the records it does not open.
+    MerkleTree.adjust_keys / adjust_bits perform a batch of adjusts on a device table and give the input rows; statement j is (R_j, R_j+1, k_j, v_j,
+    side_j).  An account may occur in many steps of a batch, and a withdrawal may spend what an earlier deposit delivered.
+    Sizes (MERKLE_ADJUST_SIZES): MerkleRecordUpdate(length, depth)'s two record chains and two level chains with one input record fewer; (8, 55, 9, 8)
+    fits Params(d=1 << 20, m=699050), depth 10 does not; (4, 16, 1, 8) fits Params(d=1 << 18, m=174762).
+    Cut form.  There is no `joined` parameter: the statement has one pair of tops, so segment 0 of a cut adjust (segment_levels) is MerkleAdjust(K,
+    length, c_0, A) itself over the record's subtree of height c_0, and the upper ranges are MerkleSegment rows, exactly as
+    MerkleTree.update_record_segments has them (MerkleTree.adjust_key_segments)."""
+
+    def __init__(self, key_bytes: int, length: int, depth: int, amount_bytes=8):
+        self.amount_bytes = A = self._arg(amount_bytes, 1, 8, "amount_bytes is in [1, 8]")
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K + A, None, f"the length is at least 2 key_bytes + {A} bytes")
+        self.depth = self._depth_arg(depth)
+        self.w = w = Words()
+        self.old_record = w.c.private(8 * length)
+        self._tail_wires()
+        # the public pieces are read by the balance's gates, so they are declared here and moved behind the roots below
+        self.key, self.amount, self.side = w.c.public(8 * K), w.c.public(8 * A), w.c.public(8)
+        field = slice(16 * K, 16 * K + 8 * A)
+        v, b = _key_bits_lsb_first(self.amount, A), _key_bits_lsb_first(self.old_record[field], A)
+        side = self.side[0]
+        bits, carry = [], side
+        for x, y in zip(b, v):  # b + (v XOR side) + side: Words.ripple's full adders with the side as carry in
+            s, carry = w.c.full_add(x, w.c.XOR(y, side), carry)
+            bits.append(s)
+        self.carry = carry
+        # `bits` least significant first, back into the record's byte order
+        self.new_record = self.old_record[: field.start] + [bits[8 * (A - 1 - j) + i] for j in range(A) for i in range(8)] + self.old_record[field.stop:]
+        self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
+        self.new_leaf, _ = _message_chain(w, self.new_record, length)
+        self._root_outputs(self.old_leaf, self.new_leaf)
+        w.c.public_last(self.key + self.amount + self.side)
+        w.c.assert_same(self.carry, side)
+        for x in self.side[1:]:
+            w.c.assert_equal(x, 0)
+        for x, y in zip(self.key, self.old_record[: 8 * K]):
+            w.c.assert_same(x, y)
+        lo, hi = (_key_bits_lsb_first(part, K) for part in (self.old_record[: 8 * K], self.old_record[8 * K: 16 * K]))
+        w.c.assert_equal(w.less_than(lo, hi), 1)
+
+    @property
+    def lu(self) -> int:
+        return 512 + 8 * (self.key_bytes + self.amount_bytes + 1)
+
+    def _public(self, key, amount, side) -> bytes:
+        """the checked K + A + 1 bytes of the public pieces behind the roots"""
+        A = self.amount_bytes
+        if not isinstance(amount, (int, np.integer)) or not 0 <= amount < 1 << (8 * A):
+            raise CircuitError(f"MerkleAdjust: the amount is an integer in [0, 2^{8 * A})")
+        if not isinstance(side, (int, np.integer)) or side not in (0, 1):
+            raise CircuitError("MerkleAdjust: the side is 0 (a deposit) or 1 (a withdrawal)")
+        return _checked_key("MerkleAdjust", self.key_bytes, key, "members") + int(amount).to_bytes(A, "big") + bytes([int(side)])
+
+    def bits(self, key: bytes, amount: int, side: int, old_record: bytes, siblings, index: int):
+        """one statement's input bits, public then private: 512 zeros where the two roots are computed, the bits of k, of the amount's A big-endian bytes
+        and of the side byte, the old record's bits, the siblings from the leaf's level up, then the direction bits.  (A witness that breaks a constraint
+        is not refused here: Circuit.holds / circuit_assign say so.)"""
+        who = "MerkleAdjust"
+        public = np.unpackbits(np.frombuffer(self._public(key, amount, side), dtype=np.uint8), bitorder="little")
+        return _input_bits(512, public, _record_bits(who, self.length, old_record), _tail_bits(who, self.depth, siblings, index))
+
+    def statement(self, old_root: bytes, new_root: bytes, key: bytes, amount: int, side: int) -> bytes:
+        """the 64 + K + A + 1 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the adjust of `key` by `amount` in the
+        direction `side` took old_root to new_root": MerkleUpdate.statement's bytes, then the key, the amount as A big-endian bytes, the side byte"""
+        return (_statement_of(old_root, "MerkleAdjust: the old root") + _statement_of(new_root, "MerkleAdjust: the new root")
+                + self._public(key, amount, side))
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):
@@ -1481,6 +1578,29 @@ def indexed_transfer(record_p, p: int, record_s, s: int, amount: int, key_bytes:
     return [int(p), int(s)], new
 
 
+def indexed_adjust(record, amount: int, side: int, key_bytes: int, amount_bytes=8):
+    """the new record, np.uint8 [length]: `record`, a live record of an indexed table whose records carry a balance (MerkleTransfer has the data model),
+    with its balance, bytes [2K, 2K + A) big-endian, plus the amount (side 0, a deposit) or less the amount (side 1, a withdrawal); nothing else of it
+    changes.  CircuitError on a record that is not live (lo < hi), an overdraft (amount > the balance) or an overflow (balance + amount >= 2^(8A))."""
+    record = bytes(record)
+    K, A, length = key_bytes, amount_bytes, len(record)
+    if not all(isinstance(x, (int, np.integer)) for x in (K, A)) or not 1 <= K <= 32 or not 1 <= A <= 8 or length < 2 * K + A:
+        raise CircuitError("indexed_adjust: a record of at least 2 key_bytes + amount_bytes bytes, key_bytes in [1, 32], amount_bytes in [1, 8]")
+    if not isinstance(amount, (int, np.integer)) or not 0 <= amount < 1 << (8 * A):
+        raise CircuitError(f"indexed_adjust: the amount is an integer in [0, 2^{8 * A})")
+    if not isinstance(side, (int, np.integer)) or side not in (0, 1):
+        raise CircuitError("indexed_adjust: the side is 0 (a deposit) or 1 (a withdrawal)")
+    if not record[:K] < record[K: 2 * K]:
+        raise CircuitError("indexed_adjust: the record is not live (lo < hi)")
+    b = int.from_bytes(record[2 * K: 2 * K + A], "big")
+    if side and amount > b:
+        raise CircuitError(f"indexed_adjust: an overdraft, the account has {b}")
+    if not side and b + amount >= 1 << (8 * A):
+        raise CircuitError(f"indexed_adjust: the balance would exceed 2^{8 * A} - 1")
+    fresh = b - int(amount) if side else b + int(amount)
+    return np.frombuffer(record[: 2 * K] + fresh.to_bytes(A, "big") + record[2 * K + A:], dtype=np.uint8).copy()
+
+
 def indexed_range(table, key_bytes: int, lo: bytes, hi: bytes):
     """the ordered slots of the links of the key range [lo, hi] in an indexed table (a uint8 array [n, length]; MerkleLink has the read): the live records
     with record.hi >= lo and record.lo <= hi, sorted by (record.lo, slot) -- in a well-formed table the records (p, k_1), (k_1, k_2), .., (k_n, s) around
@@ -1561,3 +1681,10 @@ MERKLE_TRANSFER_SIZES = {(4, 16, 1, 8): (224697, 399808), (4, 16, 2, 8): (338683
                          (8, 55, 1, 8): (225525, 400828), (8, 55, 4, 8): (567483, 1009666)}
 # ... and of MerkleTransfer(joined=False): the joined sizes plus 512 wires and 768 rows, as MERKLE_INSERT_SPLIT_SIZES
 MERKLE_TRANSFER_SPLIT_SIZES = {(4, 16, 1, 8): (225209, 400576), (8, 55, 1, 8): (226037, 401596), (8, 55, 4, 8): (567995, 1010434)}
+# ... and of MerkleAdjust by (key_bytes, length, depth, amount_bytes): MerkleRecordUpdate(length, depth)'s two record chains and two level chains with ONE input
+# record (the new record is not an input), 8 (key_bytes + amount_bytes + 1) public wires, one comparison, 8 key_bytes equalities on the key, the carry's
+# equality, the side byte's seven assertions, and the ripple: 4 wires and 7 rows an amount bit (an XOR and a full adder; (4, 16, 1, 3) less (4, 16, 1, 1) is
+# (64, 112)).  A level costs 56 993 wires and 101 473 rows, MerkleUpdate's.  (8, 55, 1, 8) is 16 wires and 409 rows above MerkleRecordUpdate(55, 1); (4, 16, 1, 8)
+# fits Params(d=1 << 18, m=174762); (8, 55, 9, 8) is the deepest one-block statement that fits Params(d=1 << 20, m=699050): (8, 55, 10, 8) would be 1 114 167 rows
+MERKLE_ADJUST_SIZES = {(4, 16, 1, 8): (112677, 200400), (4, 16, 1, 1): (112453, 200008), (4, 16, 1, 3): (112517, 200120), (8, 55, 1, 8): (113091, 200910),
+                       (4, 16, 2, 8): (169670, 301873), (8, 55, 9, 8): (569035, 1012694)}

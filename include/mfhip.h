@@ -657,6 +657,59 @@ int mfh_merkle_transfer_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, 
                                  const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index,
                                  uint8_t *h_status);
 
+/* nk sequential DEPOSITS and WITHDRAWALS on the accounts of an indexed table whose records carry a balance (the data model: mfh_merkle_transfer_keys) and its
+ * tree in ONE call, and the packed input row of words.MerkleAdjust(key_bytes, length, depth, amount_bytes) of every step -- "the balance of the account with key
+ * k_j went up (side 0) or down (side 1) by amount j, and that alone takes the tree from R_j to R_j+1".  What funds and drains the ledger that the transfers
+ * move value within; an adjust changes nothing of a record but its balance.
+ *   semantics  byte for byte what this gives, run once per step in order: find the lowest live record whose own key (lo) is k_j; that record with its balance
+ *              plus or less the amount, through mfh_merkle_update_records.  That covers the table in place, every node of the tree, the roots and row j, which
+ *              describes table and tree as they stood before step j.  A key may occur in ANY number of steps, and a step sees the balance the earlier steps
+ *              left: a withdrawal may spend what an earlier deposit of the batch delivered.
+ *   arguments  key j is the key_bytes bytes at h_keys + j * key_stride, h_amounts[j] the amount, below 2^(8 amount_bytes), h_sides[j] the direction, 0 = deposit,
+ *              1 = withdrawal; h_sides = NULL: all deposits.  h_inputs = NULL: adjust, no rows.  h_roots (may be NULL) receives the nk + 1 roots R_0 .. R_nk.
+ *              h_index receives the nk records, 0xFFFFFFFF for a key that is no member.  h_status receives per step the first that applies: 0 = fine; 1 = the
+ *              key is not a member; 3 = an overdraft, a withdrawal above the account's balance AT THAT STEP; 4 = an overflow, a deposit that takes the balance
+ *              at that step past 2^(8 amount_bytes) - 1 (2 is unused: the numbers mean what mfh_merkle_transfer_keys' mean).  A step with a status is left
+ *              out of the balances the later steps are judged by.
+ *   rows       row j (at h_inputs + j * in_stride): 64 zero bytes where the roots are computed | k_j | the amount as amount_bytes big-endian bytes | the side
+ *              byte | the old record | the 32 depth sibling bytes | ceil(depth / 8) index bytes.  Exactly 64 + key_bytes + amount_bytes + 1 + length +
+ *              32 depth + ceil(depth / 8) bytes are written.
+ *   how        ONE launch of k_key_locate over the sorted unique keys and, behind it on the stream, ONE launch of k_balance_gather; 2 words and one balance
+ *              per unique key come back under ONE wait.  The host walks the steps in order over a running balance per account (merkle_adjust.hpp); ONE launch
+ *              of k_adjust_records builds the nk new records from the table before the batch and the uploaded new balances; they go through
+ *              mfh_merkle_update_records' machinery in its chunks (the most updates whose rows fit 64 MiB, at least one).  The call synchronises the stream
+ *              behind the search and every chunk.
+ * mfh_merkle_adjust_keys_cut is the same with the path cut (above), exactly as mfh_merkle_update_records_cut for nk updates: segment 0's row is that of
+ * MerkleAdjust(key_bytes, length, c_0, amount_bytes) -- 64 zero bytes | k | amount | side | old record | c_0 siblings | ceil(c_0 / 8) index bytes of the record
+ * mod 2^c_0 -- every upper segment has ONE MerkleSegment row per step, and h_roots (may be NULL) receives the nk + 1 roots; it has no "no rows" mode.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: a null tree; a tree of another device; key_bytes 0 or above 32;
+ * amount_bytes 0 or above 8; length < 2 key_bytes + amount_bytes or > 2^20; table_stride < length; key_stride < key_bytes; nk > 0 with d_table, h_keys,
+ * h_amounts, h_index or h_status null (nk may exceed 2^depth: keys repeat); in_stride below the row's bytes when h_inputs is given; a sentinel key; a side
+ * above 1; an amount of 2^(8 amount_bytes) or more; for the cut call, what the cut calls above refuse.
+ * MFH_EINVAL after the search, with h_status and h_index filled, table and tree unwritten and no record or tree kernel launched: any step with a status
+ * other than 0.  The call is all or nothing.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call, rows = 2^depth), "merkle_balances" (1 per call, rows = the unique keys), "merkle_adjust_records" (1 per
+ * call, rows = nk), then per chunk of k updates "sha256_records" (1), "merkle_record_rows" (2; 1 without rows) and "merkle_updates" (depth + 1), the cut call
+ * also "merkle_segments" (1). */
+int mfh_merkle_adjust_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                           uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint8_t *h_inputs,
+                           size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+int mfh_merkle_adjust_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                               uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint32_t ncuts,
+                               const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index,
+                               uint8_t *h_status);
+/* The SUPPLY of such a table: h_sum[0] | h_sum[1] << 64 = the sum of the balances (bytes [2 key_bytes, 2 key_bytes + amount_bytes), big-endian) of all LIVE
+ * records (lo < hi) of the 2^depth records at d_table, *h_live (may be NULL) their number.  What is in the balance bytes of a record that is not live does
+ * not count.  The table is only read; the tree is used for its depth alone.  Transfers leave the sum as it is, a batch of adjusts changes it by its deposits
+ * less its withdrawals.
+ *   how        ONE launch of k_balance_sum (one thread per record, a 128-bit sum reduced per wave by shuffles and per workgroup through LDS, one partial a
+ *              workgroup) and ONE of k_balance_fold (one workgroup), no atomics; 20 bytes come back under ONE wait.
+ * MFH_EINVAL with the function's name in mfh_last_error: a null tree; a tree of another device; key_bytes 0 or above 32; amount_bytes 0 or above 8; length <
+ * 2 key_bytes + amount_bytes or > 2^20; table_stride < length; d_table or h_sum null.
+ * Kernel timing kind: "merkle_balance_sum" (2 per call, rows = 2^depth on the first and 0 on the fold). */
+int mfh_merkle_balance_sum(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes,
+                           uint32_t amount_bytes, uint64_t h_sum[2], uint32_t *h_live);
+
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
  * Limit: la + lb - 1 <= 2^23 (the NTT primes have 2-adicity 23); longer products fail with MFH_EUNSUPPORTED.  A product longer than the
