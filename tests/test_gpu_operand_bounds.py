@@ -6,6 +6,7 @@ with the modq wrap at 2^(64 K), 56-bit lanes with 8 bits of headroom for 256 ran
 (A' = A - 128 averages zero), so the operands here are crafted: constant matrix-core images, all-ones limb planes, coefficients chosen
 from the signs of the keystream bytes.  Expected values are closed forms or exact numpy byte sums recombined with Python integers,
 never another GPU kernel alone.  Each test's docstring says which bound it reaches and how close it gets.
+(The witness GEMM's offset-by-128 bytes and its 128 cnt_b correction: tests/test_gpu_witness_exact.py, part B.)
 """
 import numpy as np
 import pytest
