@@ -96,7 +96,7 @@ EXPORTS = [
     "mfh_witness_lanes", "mfh_witness_from_lanes", "mfh_prove_partial_w", "mfh_verify",
     "mfh_ssp_set_prg", "mfh_ssp_prg_make_t", "mfh_ssp_prg_fill",
     "mfh_resident_share_rows", "mfh_crs_expand_share", "mfh_crs_set_resident_share", "mfh_crs_set_resident_prefix",
-    "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width",
+    "mfh_prove_batch_supergroup", "mfh_prove_batch_stream_wait", "mfh_set_mm_width", "mfh_set_mm_queue", "mfh_set_mm_claim_log", "mfh_mm_claim_log_launches",
     "mfh_setup_public", "mfh_prove_public", "mfh_prove_batch_public", "mfh_vk_derive", "mfh_verify_public",
     "mfh_ssp_from_rows", "mfh_ssp_set_rows", "mfh_ssp_rows_fill", "mfh_ssp_rows_violations", "mfh_circuit_create", "mfh_circuit_destroy", "mfh_circuit_assign",
     "mfh_circuit_create_global", "mfh_circuit_create_ex", "mfh_circuit_create_out", "mfh_circuit_create_sum",
@@ -106,6 +106,16 @@ EXPORTS = [
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
     "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
 ]
+
+
+# Entry points a library may lack and still load (calling one then raises AttributeError).  Each needs a reason: everything else is required of every library.
+OPTIONAL_EXPORTS = {
+    # tuning / test knobs of the persistent grid's item queues: no proof depends on them, and $MFHIP_LIB exists to time an older build of the same ABI (one that walks
+    # fixed lists only) against this one through the same bench.py.  build() still requires them of the tree's own library (EXPORTS).
+    "mfh_set_mm_queue": "tuning knob; older builds walk fixed lists",
+    "mfh_set_mm_claim_log": "test instrumentation of mfh_set_mm_queue",
+    "mfh_mm_claim_log_launches": "test instrumentation of mfh_set_mm_queue",
+}
 
 
 def load_library():
@@ -152,6 +162,9 @@ def load_library():
         "mfh_prove_batch": (i32, [vp, vp, vp, u32, ctypes.c_char_p, sz, vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp]),
         "mfh_prove_batch_supergroup": (u32, [vp]),
         "mfh_set_mm_width": (i32, [vp, u32, i32]),
+        "mfh_set_mm_queue": (i32, [vp, i32, u32, i32]),
+        "mfh_set_mm_claim_log": (i32, [vp, vp, sz]),
+        "mfh_mm_claim_log_launches": (u32, [vp, ctypes.POINTER(u32), u32]),
         "mfh_prove_batch_stream_wait": (i32, [vp, u32, vp]),
         "mfh_poly_mul": (i32, [vp, vp, sz, vp, sz, vp]),
         "mfh_poly_add": (i32, [vp, vp, vp, sz, vp]),
@@ -260,6 +273,8 @@ def load_library():
         "mfh_merkle_range_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
+        if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
@@ -1212,6 +1227,25 @@ class Context:
     def set_mm_width(self, per_xcd=32, early_chain=False):
         """workgroups per XCD of the persistent S / AS launch (32 = every CU); early_chain: chain / epilogues queued beside the streaming launches"""
         self._chk(self.lib.mfh_set_mm_width(self._h, int(per_xcd), 1 if early_chain else 0))
+
+    def set_mm_queue(self, mode=1, start_shift=0, prefix=-8):
+        """persistent grid: 0 = every workgroup walks its fixed list of items, 1 = workgroups claim items from per-XCD queues and steal from the other XCDs' at the end.
+        prefix: rounds of the fixed list run before the first claim (< 0: all but the last -prefix); start_shift (tests): begin in the queue of XCD x + start_shift"""
+        self._chk(self.lib.mfh_set_mm_queue(self._h, int(mode), int(start_shift), int(prefix)))
+
+    def set_mm_claim_log(self, log):
+        """tests: a zeroed uint32 device tensor in which the persistent launches of the following calls record who ran which item; None: no log"""
+        if log is None:
+            self._chk(self.lib.mfh_set_mm_claim_log(self._h, None, 0))
+        else:
+            self._chk(self.lib.mfh_set_mm_claim_log(self._h, log.data_ptr(), log.numel()))
+
+    def mm_claim_log_launches(self):
+        """one dict per persistent launch recorded in the claim log since set_mm_claim_log: where its section starts and the shape that indexes it"""
+        out = (ctypes.c_uint32 * (16 * 12))()
+        n = int(self.lib.mfh_mm_claim_log_launches(self._h, out, 16))
+        keys = ("offset", "nchunks", "nblk", "ngt", "ngr", "map", "tgs", "width", "coeff_bytes", "queue", "prefix", "shift")
+        return [dict(zip(keys, (int(x) for x in out[12 * i:12 * i + 12]))) for i in range(n)]
 
     def set_mm_pack(self, on=True):
         """streaming kernels hand their partial products to the epilogue recombined (default) or as int32 (rounds 1 - 5): same results"""

@@ -111,7 +111,9 @@ struct mfh_ctx {
   uint32_t mm_width = 32;  // workgroups per XCD of the persistent S / AS launch (mfh_set_mm_width): 32 = every CU
   size_t early_ws_half = 0;        // early chain: distance of the two halves of ws3 = the scratch of the call's first (largest) super-group
   bool batch_early_chain = false;  // mfh_prove_batch: chain of super-group k + 1 and epilogue of k queued BESIDE the streaming launch of k / k + 1 (for the CUs a narrower grid leaves free)
-  uint32_t *mm_sync = nullptr;  // 8 x 32 counters of the persistent grid's rendezvous
+  uint32_t *mm_sync = nullptr;  // 8 x 32 counters of the persistent grid's rendezvous, then 8 counters of its item queues per workspace (mm_ws_sel)
+  uint32_t mm_queue = 1, mm_queue_shift = 0; int mm_queue_prefix = -8;  // mfh_set_mm_queue: workgroups of the persistent grid claim their items from per-XCD queues (evalmm.hip)
+  uint32_t *mm_log = nullptr; size_t mm_log_words = 0, mm_log_used = 0; uint32_t mm_log_n = 0, mm_log_desc[16][12];  // mfh_set_mm_claim_log (tests): who ran which item
   int poly_exact = 1;  // batches of h = (v^2 - 1) / t try the exact-division path first: 0 never, 1 unless recent batches failed its check, 2 always (poly.hip; mfh_set_poly_exact)
   bool poly_pts_pinned = false;  // the exact path's check points: drawn per preparation, or these four (mfh_set_poly_exact_points; tests)
   uint32_t poly_pts[4] = {0, 0, 0, 0};

@@ -35,6 +35,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
+#include "mms_slots.hpp"
 
 namespace {
 
@@ -575,22 +576,7 @@ constexpr int CH = NQ2 / CG;      // column tiles per wave
 // same 16 row tiles for consecutive groups, so the second one's A fragments come out of that XCD's L2 (or the Infinity Cache) instead
 // of HBM: the image is read from HBM once per ng groups.  grid.x = 8 ng ceil(tile groups / 8).
 struct MmsImages { const v4i *image[16]; };  // the region image each group of a launch streams (S and AS groups share one launch)
-// Which (group, tile group) the slot-th workgroup of an XCD takes.  `ngt` groups in the launch, `ngr` of them per region (ngt / ngr regions).
-//   map 0: slot -> (slot % ngt, slot / ngt): the 32 workgroups an XCD runs at a time are 32 / ngt tile groups x all groups of BOTH regions -- an image's
-//          fragments are shared by ngr workgroups, a group's digit fragments by 32 / ngt of them;
-//   map 1: 32 consecutive slots are 32 / ngr tile groups x the ngr groups of ONE region (regions alternate per 32 slots): the fragments are shared by ngr
-//          workgroups as before, a group's digit fragments by 32 / ngr -- the digit fragments are as many bytes per workgroup as the image's, so with two
-//          regions this halves their share of the L2 misses.  Needs ngr | 32; the host picks map 0 otherwise.
-__device__ __forceinline__ void mms_item(uint32_t xcd, uint32_t slot, uint32_t ngt, uint32_t ngr, uint32_t map, uint32_t &grp, uint32_t &tg) {
-  if (map == 0) {
-    grp = slot % ngt;
-    tg = (slot / ngt) * 8 + xcd;
-  } else {
-    const uint32_t blk = slot >> 5, i = slot & 31, nreg = ngt / ngr, tpb = 32 / ngr;
-    grp = (blk % nreg) * ngr + i % ngr;
-    tg = ((blk / nreg) * tpb + i / ngr) * 8 + xcd;
-  }
-}
+// Which (group, tile group) the slot-th workgroup of an XCD takes: mms_item (mms_slots.hpp, shared with the host and the queue of the persistent grid).
 // ---- packed partial products (round 6) ------------------------------------------------------------------------------------------------------------------
 // A lane of the streaming kernels ends an item with, per row tile and column tile, the int32 sums of FOUR consecutive byte positions (rows 4 g4 + e of the tile) of ONE
 // digit column (16 q + c16).  Written as they are that is 1 KiB per byte position and group -- 2.1 GB per super-group launch, written by the kernel and read back by the
@@ -824,16 +810,58 @@ __global__ __launch_bounds__(SW * 64) void k_mmstream1(MmsImages imgs, uint32_t 
 // every wave reaches the end of the grid whatever the counters hold.  sync: 8 x 32 counters zeroed before the launch.
 // (`width`: workgroups per XCD = grid / 8, 32 by default -- every CU --; fewer leave CUs of every XCD to other streams' kernels, and the workgroup then strides
 // over its XCD's slots by `width` (mfh_set_mm_width: the round-5 experiment on the power finding, EXPERIMENTS.md); the rendezvous needs width == 32)
+//
+// ITEM QUEUES (mfh_set_mm_queue; q.mode 1, sync_mode 0).  The static walk fixes every workgroup's list, so the launch ends when the slowest CU has finished ITS list; with the
+// queues a workgroup draws its items instead.  Every XCD has one 32-bit counter over the flat index of its slots (mms_slots.hpp: chunk outermost, then the 32-slot blocks, so
+// the 32 workgroups that claim consecutive indices share fragments in that XCD's L2 as the static walk's do).  A workgroup first runs `q.prefix` rounds of its static list
+// without any claim -- flat indices below q.prefix x width, the host makes sure they are exactly those rounds -- and then thread 0 claims index q.prefix x width + fetch_add
+// of its XCD's counter (agent scope, relaxed: nothing but the index is handed over), skips the indices whose tile group does not exist, and hands the index to the workgroup
+// through one LDS word behind a barrier.  When a queue is exhausted the workgroup goes on to the queue of XCD x + 1, x + 2, ... (mod 8) and runs that XCD's items (mms_item
+// gets the QUEUE's XCD); after eight exhausted queues it returns.  Nothing waits for another workgroup: a counter only grows, so a workgroup makes at most
+// 8 x (indices of a queue + 1) claims whatever the others do (every claim but a queue's last gives it an index of its own).
+// q.shift (tests): the workgroups of XCD x begin in the queue of XCD x + shift.
+// q.log (tests; null otherwise): two words per (chunk, XCD, slot) -- how often the item was taken, and by whom: blockIdx.x + 1 | the ordinal of the queue it came from << 16
+// (0 = the workgroup's first queue, 0xff = its static list).
+struct MmsQueue {
+  uint32_t *ctr;   // 8 counters, zero before the launch
+  uint32_t *log;   // claim log or null
+  uint32_t mode, shift, prefix, tgs;
+};
+#ifdef MMS_ITEM_STAMPS  // diagnostic build (never the default, never timed for a headline): wave 0 of every workgroup stamps s_memrealtime (100 MHz) at the entry of its first
+                        // item, when it leaves its last item (stores issued) and when those stores have landed, and counts its items and those of foreign queues: four words
+                        // per workgroup, ordinary vector stores.  tools/mmstream_item_queue.py reads them (mfh_mm_item_stamps).
+#define MMS_STAMP_PARAM , unsigned long long *__restrict__ stamps
+#define MMS_STAMP_ARG , stamps
+#else
+#define MMS_STAMP_PARAM
+#define MMS_STAMP_ARG
+#endif
 __device__ __forceinline__ void mmstream_persistent(const MmsImages &imgs, uint32_t mtiles, uint32_t KS, uint32_t nrows, uint32_t rows_per_chunk,
                                                     const v4i *__restrict__ cdv, int *__restrict__ part, uint32_t ngt, uint32_t ngr, uint32_t map,
                                                     uint64_t cd_stride, uint64_t part_stride, uint32_t nblk /* 32-slot blocks per XCD */, uint32_t nchunks,
-                                                    uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk) {
+                                                    uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk,
+                                                    const MmsQueue &q MMS_STAMP_PARAM) {
+  __shared__ uint32_t claim[2];  // a claimed item: flat index, ordinal of the queue
   const uint32_t xcd = blockIdx.x & 7, cu = blockIdx.x >> 3;
   const uint32_t members = sync_mode == 2 ? 32u : (map ? ngr : ngt);
   uint32_t *ctr = sync + xcd * 32 + (sync_mode == 2 ? 0u : cu / members);
-  uint32_t k = 0;
-  for (uint32_t chunk = 0; chunk < nchunks; chunk++)
-    for (uint32_t slot = cu; slot < nblk * 32; slot += width, k++) {
+  const uint32_t per_chunk = nblk * 32, total = nchunks * per_chunk;
+  uint32_t k = 0, chunk = 0, slot = cu;  // the static walk: round k is (chunk, slot)
+  uint32_t qi = 0;                       // queues exhausted so far
+#ifdef MMS_ITEM_STAMPS
+  unsigned long long t_first = 0, t_left = 0;
+  uint32_t items = 0, foreign = 0;
+#endif
+  for (;;) {
+#ifdef MMS_ITEM_STAMPS
+    if (threadIdx.x == 0) t_left = __builtin_amdgcn_s_memrealtime();
+#endif
+    uint32_t ixcd = xcd, ichunk, islot, from = 0xffu;
+    if (chunk < nchunks && (!q.mode || k < q.prefix)) {
+      ichunk = chunk;
+      islot = slot;
+      slot += width;
+      if (slot >= per_chunk) slot = cu, chunk++;
       if (sync_mode && members > 1) {
         if (threadIdx.x == 0) {
           __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -842,24 +870,76 @@ __device__ __forceinline__ void mmstream_persistent(const MmsImages &imgs, uint3
         }
         __syncthreads();
       }
-      uint32_t grp, tg;
-      mms_item(xcd, slot, ngt, ngr, map, grp, tg);
-      mmstream_body(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, grp, tg, chunk, cd_stride, part_stride, pk);
+      k++;
+    } else if (q.mode) {
+      if (threadIdx.x == 0) {
+        uint32_t flat = total;  // (nothing left)
+        while (qi < 8) {
+          const uint32_t qx = (xcd + q.shift + qi) & 7;
+          const uint32_t n = q.prefix * width + __hip_atomic_fetch_add(q.ctr + qx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (n >= total) {
+            qi++;
+          } else if (mms_slot_valid(qx, n % per_chunk, ngt, ngr, map, q.tgs)) {
+            flat = n;
+            break;
+          }
+        }
+        claim[0] = flat;
+        claim[1] = qi;
+      }
+      __syncthreads();
+      const uint32_t flat = __builtin_amdgcn_readfirstlane(claim[0]);
+      from = __builtin_amdgcn_readfirstlane(claim[1]);
+      __syncthreads();  // (claim[] is read by every wave before thread 0 can write the next one, whatever the item does)
+      if (flat >= total) break;
+      ixcd = (xcd + q.shift + from) & 7;
+      mms_flat(flat, nblk, ichunk, islot);
+    } else
+      break;
+    if (q.log && threadIdx.x == 0 && mms_slot_valid(ixcd, islot, ngt, ngr, map, q.tgs)) {
+      uint32_t *e = q.log + 2 * ((uint64_t)(ichunk * 8 + ixcd) * per_chunk + islot);
+      __hip_atomic_fetch_add(e, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      e[1] = (blockIdx.x + 1) | (from << 16);
     }
+#ifdef MMS_ITEM_STAMPS
+    if (threadIdx.x == 0 && mms_slot_valid(ixcd, islot, ngt, ngr, map, q.tgs)) {
+      if (!items) t_first = t_left;
+      items++;
+      foreign += ixcd != xcd;
+    }
+#endif
+    uint32_t grp, tg;
+    mms_item(ixcd, islot, ngt, ngr, map, grp, tg);
+    mmstream_body(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, grp, tg, ichunk, cd_stride, part_stride, pk);
+  }
+#ifdef MMS_ITEM_STAMPS
+  if (threadIdx.x == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned long long *st = stamps + 4 * (uint64_t)blockIdx.x;
+    st[0] = t_first;
+    st[1] = t_left;
+    st[2] = __builtin_amdgcn_s_memrealtime();
+    st[3] = items | ((unsigned long long)foreign << 32);
+  }
+#endif
 }
 __global__ __launch_bounds__(SW * 64) void k_mmstream_p(MmsImages imgs, uint32_t mtiles, uint32_t KS, uint32_t nrows, uint32_t rows_per_chunk,
                                                         const v4i *__restrict__ cdv, int *__restrict__ part, uint32_t ngt, uint32_t ngr, uint32_t map,
                                                         uint64_t cd_stride, uint64_t part_stride, uint32_t nblk, uint32_t nchunks,
-                                                        uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk) {
-  mmstream_persistent(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, ngt, ngr, map, cd_stride, part_stride, nblk, nchunks, sync, sync_mode, spin_max, width, pk);
+                                                        uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk,
+                                                        MmsQueue q MMS_STAMP_PARAM) {
+  mmstream_persistent(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, ngt, ngr, map, cd_stride, part_stride, nblk, nchunks, sync, sync_mode, spin_max, width, pk,
+                      q MMS_STAMP_ARG);
 }
 // the same grid under another name for the launch that serves b_w of several super-groups (one-byte coefficient columns over the BT+BV image): profiles then show
 // the two launch shapes -- 16 groups x 32768 rows, matrix-core bound; up to 8 groups x 21845 rows -- as two rows
 __global__ __launch_bounds__(SW * 64) void k_mmstream_pb(MmsImages imgs, uint32_t mtiles, uint32_t KS, uint32_t nrows, uint32_t rows_per_chunk,
                                                          const v4i *__restrict__ cdv, int *__restrict__ part, uint32_t ngt, uint32_t ngr, uint32_t map,
                                                          uint64_t cd_stride, uint64_t part_stride, uint32_t nblk, uint32_t nchunks,
-                                                         uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk) {
-  mmstream_persistent(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, ngt, ngr, map, cd_stride, part_stride, nblk, nchunks, sync, sync_mode, spin_max, width, pk);
+                                                         uint32_t *__restrict__ sync, uint32_t sync_mode, uint32_t spin_max, uint32_t width, uint32_t pk,
+                                                         MmsQueue q MMS_STAMP_PARAM) {
+  mmstream_persistent(imgs, mtiles, KS, nrows, rows_per_chunk, cdv, part, ngt, ngr, map, cd_stride, part_stride, nblk, nchunks, sync, sync_mode, spin_max, width, pk,
+                      q MMS_STAMP_ARG);
 }
 
 // ---- k_mmstream_w: the same GEMM with ONE wave per SIMD (round 4) -----------------------------------------------------------------------------------
@@ -1344,6 +1424,16 @@ static uint32_t mms_pk(const mfh_ctx *c, const MmsPlan &P) {
   if (!c->mm_pack || (mms_persistent(c, P) && c->mm_wave1)) return 0;  // (k_mmstream_w writes int32 only)
   return P.ND;
 }
+#ifdef MMS_ITEM_STAMPS  // diagnostic build: 4 words per workgroup (256 at most) and persistent launch, up to 64 launches between two reads (mfh_mm_item_stamps)
+static unsigned long long *g_mms_stamps = nullptr;
+static uint32_t g_mms_stamp_n = 0, g_mms_stamp_kind[64];
+static unsigned long long *mms_stamps_next(uint32_t nd, uint32_t queue) {
+  if (!g_mms_stamps && hipMalloc(&g_mms_stamps, 64 * 256 * 4 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+  if (g_mms_stamp_n == 64) return nullptr;
+  g_mms_stamp_kind[g_mms_stamp_n] = nd | queue << 8;
+  return g_mms_stamps + (size_t)g_mms_stamp_n++ * 256 * 4;
+}
+#endif
 int mms_stream(mfh_ctx *c, const MmsPlan &P) {
   const uint32_t KS = (P.nrows + RT2 - 1) / RT2 * (RT2 / 64), tgs = (P.mtiles + TPW - 1) / TPW;
   const bool will_persist = mms_persistent(c, P);  // (the choice made below)
@@ -1353,19 +1443,45 @@ int mms_stream(mfh_ctx *c, const MmsPlan &P) {
   const uint32_t pk = mms_pk(c, P);  // (mms_finish reads what this launch writes: the same choice)
   if (P.ngt > 1) {
     // slot -> (group, tile group) map and grid shape (mfh_set_mm_stream): see mms_item / k_mmstream_p
-    const uint32_t tgx = (tgs + 7) / 8;  // tile groups per XCD
     const uint32_t map = c->mm_map && 32 % P.ng == 0 ? 1u : 0u;
-    const uint32_t slots = map ? (tgx + 32 / P.ng - 1) / (32 / P.ng) * (P.ngt / P.ng) * 32 : tgx * P.ngt;  // per XCD
+    const uint32_t slots = mms_slots(tgs, P.ngt, P.ng, map);  // per XCD
     const bool persistent = will_persist;
     if (persistent && c->mm_wave1) {
       hipLaunchKernelGGL(k_mmstream_w, dim3(256), dim3(WSW * 64), 0, c->stream, imgs, P.mtiles, KS, P.nrows, P.rpc, (const v4i *)P.cd, P.part, P.ngt, P.ng, map,
                          (uint64_t)(P.cd_bytes / 16), (uint64_t)(P.part_bytes / 4), (slots + 31) / 32, P.nchunks);
     } else if (persistent) {
-      if (!c->mm_sync) HIP_TRY(c, hipMalloc(&c->mm_sync, 8 * 32 * sizeof(uint32_t)));
-      if (c->mm_sync_mode) HIP_TRY(c, hipMemsetAsync(c->mm_sync, 0, 8 * 32 * sizeof(uint32_t), c->stream));  // (the rendezvous counters; unused by default)
+      constexpr size_t SYNC_WORDS = 8 * 32 + 2 * 8;  // the rendezvous counters, then one set of queue counters per workspace (mm_ws_sel)
+      if (!c->mm_sync) HIP_TRY(c, hipMalloc(&c->mm_sync, SYNC_WORDS * sizeof(uint32_t)));
       const uint32_t width = P.ND == 1 ? 32u : c->mm_width;  // (b_w's HBM-bound launch keeps every CU)
+      const uint32_t sync_mode = width == 32 ? c->mm_sync_mode : 0u, nblk = (slots + 31) / 32;
+      // the item queues (mfh_set_mm_queue).  The rendezvous modes keep the static walk: membership of a set is static.  The static prefix has to be whole rounds of the
+      // static walk AND the flat indices below prefix x width, which it is when the grid's width divides a chunk's slots; a start shift (tests) leaves no static prefix.
+      // A launch's counters decide which items run, so no other launch may touch them while it is in flight: a set per workspace.  Two streaming launches of a context
+      // are in flight together only as mfh_prove_batch's S launch on the caller's stream and AS launch on the side stream (snark.hip: OnSide), which is exactly when
+      // they have scratch of their own (ws | ws2 by mm_ws_sel); launches that share a workspace are ordered on one stream, and so are their memsets.
+      uint32_t *qctr = c->mm_sync + 8 * 32 + 8 * (c->mm_ws_sel ? 1 : 0);
+      MmsQueue q{qctr, nullptr, c->mm_queue && !sync_mode ? 1u : 0u, c->mm_queue_shift & 7, 0u, tgs};
+      if (q.mode && !q.shift && nblk * 32 % width == 0) {
+        const uint32_t rounds = P.nchunks * (nblk * 32 / width);
+        q.prefix = c->mm_queue_prefix < 0 ? rounds - std::min(rounds, (uint32_t)-(int64_t)c->mm_queue_prefix) : std::min(rounds, (uint32_t)c->mm_queue_prefix);
+      }
+      // one memset per launch, of what the launch itself uses: the rendezvous counters (speed only: a concurrent launch's memset costs polls, never an item) or its own queues'
+      if (sync_mode) HIP_TRY(c, hipMemsetAsync(c->mm_sync, 0, 8 * 32 * sizeof(uint32_t), c->stream));
+      else if (q.mode) HIP_TRY(c, hipMemsetAsync(qctr, 0, 8 * sizeof(uint32_t), c->stream));
+      if (c->mm_log) {  // (tests) this launch's section of the claim log and what the reader needs to index it
+        const size_t need = (size_t)2 * P.nchunks * 8 * nblk * 32;
+        if (c->mm_log_n == 16 || c->mm_log_used + need > c->mm_log_words) { c->err = "mfh_set_mm_claim_log: the log is too small for the call's launches"; return MFH_EINVAL; }
+        q.log = c->mm_log + c->mm_log_used;
+        const uint32_t desc[12] = {(uint32_t)c->mm_log_used, P.nchunks, nblk, P.ngt, P.ng, map, tgs, width, P.ND, q.mode, q.prefix, q.shift};
+        memcpy(c->mm_log_desc[c->mm_log_n++], desc, sizeof(desc));
+        c->mm_log_used += need;
+      }
+#ifdef MMS_ITEM_STAMPS
+      unsigned long long *stamps = mms_stamps_next(P.ND, q.mode);
+      if (!stamps) { c->err = "MMS_ITEM_STAMPS: no room for another launch"; return MFH_EINVAL; }
+#endif
       hipLaunchKernelGGL(P.ND == 1 ? k_mmstream_pb : k_mmstream_p, dim3(8 * width), dim3(SW * 64), 0, c->stream, imgs, P.mtiles, KS, P.nrows, P.rpc, (const v4i *)P.cd, P.part, P.ngt, P.ng, map,
-                         (uint64_t)(P.cd_bytes / 16), (uint64_t)(P.part_bytes / 4), (slots + 31) / 32, P.nchunks, c->mm_sync, width == 32 ? c->mm_sync_mode : 0u, c->mm_spin, width, pk);
+                         (uint64_t)(P.cd_bytes / 16), (uint64_t)(P.part_bytes / 4), nblk, P.nchunks, c->mm_sync, sync_mode, c->mm_spin, width, pk, q MMS_STAMP_ARG);
     } else {
       hipLaunchKernelGGL(k_mmstream, dim3(slots * 8, P.nchunks), dim3(SW * 64), 0, c->stream, imgs, P.mtiles, KS, P.nrows, P.rpc, (const v4i *)P.cd, P.part, P.ngt, P.ng,
                          map, (uint64_t)(P.cd_bytes / 16), (uint64_t)(P.part_bytes / 4), pk);
@@ -1513,6 +1629,42 @@ int mfh_set_mm_width(mfh_ctx *c, uint32_t per_xcd, int early_chain) {
   c->batch_early_chain = early_chain != 0;
   return MFH_OK;
 }
+int mfh_set_mm_queue(mfh_ctx *c, int mode, uint32_t start_shift, int prefix) {
+  if (!c || mode < 0 || mode > 1 || start_shift > 7) return MFH_EINVAL;
+  c->mm_queue = (uint32_t)mode;
+  c->mm_queue_shift = start_shift;
+  c->mm_queue_prefix = prefix;
+  return MFH_OK;
+}
+int mfh_set_mm_claim_log(mfh_ctx *c, uint32_t *d_log, size_t words) {
+  if (!c || (d_log && !words)) return MFH_EINVAL;
+  c->mm_log = d_log;
+  c->mm_log_words = d_log ? words : 0;
+  c->mm_log_used = 0;
+  c->mm_log_n = 0;
+  return MFH_OK;
+}
+uint32_t mfh_mm_claim_log_launches(const mfh_ctx *c, uint32_t *desc, uint32_t max_launches) {
+  if (!c) return 0;
+  const uint32_t n = std::min(c->mm_log_n, max_launches);
+  if (desc && n) memcpy(desc, c->mm_log_desc, (size_t)n * 12 * sizeof(uint32_t));
+  return c->mm_log_n;
+}
+#ifdef MMS_ITEM_STAMPS
+// diagnostic build only: waits for the device, copies the stamps of the persistent launches since the last call (per launch: {coefficient bytes | queue mode << 8, 0, 0, 0}, then
+// four words per workgroup) into h_out and starts over; returns the number of launches
+uint32_t mfh_mm_item_stamps(unsigned long long *h_out, uint32_t max_launches) {
+  const uint32_t n = std::min(g_mms_stamp_n, max_launches);
+  if (hipDeviceSynchronize() != hipSuccess) return 0;
+  for (uint32_t l = 0; l < n; l++) {
+    unsigned long long *o = h_out + (size_t)l * 257 * 4;
+    o[0] = g_mms_stamp_kind[l], o[1] = o[2] = o[3] = 0;
+    if (hipMemcpy(o + 4, g_mms_stamps + (size_t)l * 256 * 4, 256 * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  }
+  g_mms_stamp_n = 0;
+  return n;
+}
+#endif
 int mfh_set_mm_pack(mfh_ctx *c, int on) {
   if (!c) return MFH_EINVAL;
   c->mm_pack = on != 0;

@@ -859,6 +859,23 @@ int mfh_set_mm_stream(mfh_ctx *ctx, int map, int persistent, int sync_mode, uint
  * mfh_prove_batch then queues the chain of super-group k + 1 and the epilogue of super-group k on side streams beside the streaming launches instead of between them
  * (the round-5 experiment on the power finding, EXPERIMENTS.md).  Tuning; results do not depend on it. */
 int mfh_set_mm_width(mfh_ctx *ctx, uint32_t per_xcd, int early_chain);
+/* How the workgroups of the persistent grid come by their items (tuning; results do not depend on it).  mode 0: every workgroup walks its fixed list, so a launch
+ * ends when the slowest CU has finished its list.  mode 1 (default): every XCD has a queue over its items in the static walk's order; a workgroup claims from its own XCD's queue
+ * (one atomic add per item) and, when that is exhausted, from the queues of the XCDs x + 1, x + 2, ... (mod 8), and returns after eight exhausted queues -- it never waits
+ * for another workgroup.  prefix: rounds of the static list every workgroup runs before it claims (the claim's latency is then paid for the last items only); >= 0 that
+ * many (at most the whole list), < 0 all but the last -prefix rounds (default -8).  start_shift (0..7, tests): workgroups of XCD x begin in the queue of XCD
+ * (x + start_shift) mod 8 and run no static prefix, so whatever a workgroup takes before its first queue is exhausted is a foreign XCD's item (its own XCD's queue
+ * is its (8 - start_shift)-th).  Every launch has counters of its own: the two launches mfh_prove_batch keeps in flight together (mfh_set_batch_launch, merge_regions 0)
+ * do not share any.  The rendezvous modes of mfh_set_mm_stream and the one-wave body keep
+ * the static walk. */
+int mfh_set_mm_queue(mfh_ctx *ctx, int mode, uint32_t start_shift, int prefix);
+/* Tests: a device array of `words` zeroed 32-bit words in which the persistent launches of the following calls record who ran which item (NULL: none, the default).
+ * Launch l of the calls since this one takes the next 2 x nchunks x 8 x 32 nblk words: per (chunk, XCD, slot) how often the item was taken, and
+ * blockIdx.x + 1 | from << 16 of the workgroup that took it (from: 0xff = its static list, else the ordinal 0..7 of the queue it claimed from).
+ * mfh_mm_claim_log_launches copies 12 words per launch -- first word of its section, nchunks, nblk, groups, groups per region, map, tile groups, workgroups per XCD,
+ * coefficient bytes, queue mode, static prefix, start shift -- for up to max_launches launches and returns how many there were (16 at most per log). */
+int mfh_set_mm_claim_log(mfh_ctx *ctx, uint32_t *d_log, size_t words);
+uint32_t mfh_mm_claim_log_launches(const mfh_ctx *ctx, uint32_t *desc, uint32_t max_launches);
 /* rows per row chunk of the matrix-core launches (mfh_eval_rows_multi, mfh_prove_batch): the int32 accumulators hold at most
  * 131071 rows (the default; 0 restores it); smaller values split every region into more chunks -- same results (tuning, tests). */
 int mfh_set_mm_chunk_rows(mfh_ctx *ctx, uint32_t rows);
