@@ -90,7 +90,7 @@ EXPORTS = [
     "mfh_encrypt_rows", "mfh_decrypt", "mfh_ct_smudge", "mfh_ssp_upload", "mfh_witness_poly", "mfh_version",
     "mfh_workspace_bytes", "mfh_last_kernel_ms", "mfh_set_timing", "mfh_set_overlap", "mfh_eval_rows_multi", "mfh_prove_batch", "mfh_crs_mm_image_bytes", "mfh_crs_expand_mm", "mfh_crs_set_resident_mm", "mfh_witness_poly_multi", "mfh_witness_poly_mm", "mfh_poly_h_multi", "mfh_poly_mul", "mfh_poly_add", "mfh_poly_prepare_t",
     "mfh_ssp_prepare", "mfh_poly_h", "mfh_setup_messages", "mfh_setup", "mfh_setup_image", "mfh_crs_image_set_b", "mfh_prove",
-    "mfh_prove_partial", "mfh_prove_finish", "mfh_ct_to_lanes", "mfh_ct_from_lanes", "mfh_lanes_per_value", "mfh_digest128", "mfh_timing_drain", "mfh_timing_busy_ms", "mfh_timing_work_rows", "mfh_set_batch_image", "mfh_set_batch_slabs", "mfh_set_expand_path", "mfh_set_encrypt_path", "mfh_set_batch_launch", "mfh_set_batch_bw", "mfh_set_mm_chunk_rows", "mfh_set_mm_pack", "mfh_set_poly_exact", "mfh_poly_exact_fallbacks", "mfh_poly_exact_points", "mfh_set_poly_exact_points", "mfh_set_mm_stream", "mfh_add_dotp", "mfh_set_encrypt_chunks", "mfh_set_witness_per", "mfh_set_eval_path", "mfh_set_decrypt_path", "mfh_decrypt_rows",
+    "mfh_prove_partial", "mfh_prove_finish", "mfh_ct_to_lanes", "mfh_ct_from_lanes", "mfh_lanes_per_value", "mfh_digest128", "mfh_timing_drain", "mfh_timing_busy_ms", "mfh_timing_work_rows", "mfh_set_batch_image", "mfh_set_batch_slabs", "mfh_set_expand_path", "mfh_set_expand_periods", "mfh_set_encrypt_path", "mfh_set_batch_launch", "mfh_set_batch_bw", "mfh_set_mm_chunk_rows", "mfh_set_mm_pack", "mfh_set_poly_exact", "mfh_poly_exact_fallbacks", "mfh_poly_exact_points", "mfh_set_poly_exact_points", "mfh_set_mm_stream", "mfh_add_dotp", "mfh_set_encrypt_chunks", "mfh_set_witness_per", "mfh_set_eval_path", "mfh_set_decrypt_path", "mfh_decrypt_rows",
     "mfh_crs_mm_share_bytes", "mfh_crs_expand_mm_share", "mfh_crs_set_resident_mm_share", "mfh_batch_chain", "mfh_batch_witness_cols", "mfh_batch_chain_from_w", "mfh_witness_poly_mm_cols", "mfh_prove_batch_partial", "mfh_prove_batch_finish",
     "mfh_resident_row_bytes", "mfh_crs_expand", "mfh_eval_rows_resident", "mfh_crs_set_resident",
     "mfh_witness_lanes", "mfh_witness_from_lanes", "mfh_prove_partial_w", "mfh_verify",
@@ -115,6 +115,8 @@ OPTIONAL_EXPORTS = {
     "mfh_set_mm_queue": "tuning knob; older builds walk fixed lists",
     "mfh_set_mm_claim_log": "test instrumentation of mfh_set_mm_queue",
     "mfh_mm_claim_log_launches": "test instrumentation of mfh_set_mm_queue",
+    # test knob of the CRS expansion's launch plan: the image does not depend on it, and an older build picks the plan from the row count alone
+    "mfh_set_expand_periods": "test knob; older builds pick the periods per chunk from the row count",
 }
 
 
@@ -214,6 +216,7 @@ def load_library():
         "mfh_set_batch_bw": (i32, [vp, i32]),
         "mfh_set_encrypt_path": (i32, [vp, i32]),
         "mfh_set_expand_path": (i32, [vp, i32]),
+        "mfh_set_expand_periods": (i32, [vp, u32]),
         "mfh_set_batch_slabs": (i32, [vp, u32]),
         "mfh_set_encrypt_chunks": (i32, [vp, u32]),
         "mfh_set_eval_path": (i32, [vp, i32]),
@@ -1195,6 +1198,13 @@ class Context:
     def set_expand_path(self, path=0):
         """crs_expand_mm*: 0 = barrier-free writer (MFMA transposition), 1 = LDS-tile writer"""
         self._chk(self.lib.mfh_set_expand_path(self._h, int(path)))
+
+    def set_expand_periods(self, periods=0):
+        """barrier-free writer of crs_expand_mm* and of prove_batch's transient image: periods of 23 AES blocks per chunk, 0 = picked from the row count, 2 .. 10 forced (tests:
+        the image does not depend on it)"""
+        if not 0 <= int(periods) <= 0xFFFFFFFF:
+            raise MfhError("set_expand_periods: 0 or 2 .. 10")
+        self._chk(self.lib.mfh_set_expand_periods(self._h, int(periods)))
 
     def set_encrypt_path(self, path=0):
         """encrypt_rows / setup: 0 = by batch size, 1 = VALU kernel, 2 = matrix-core kernel (<sk, a> as a Toeplitz int8 GEMM)"""

@@ -120,6 +120,7 @@ struct mfh_ctx {
   bool mm_pack = true;  // the streaming kernels hand their partial products to the epilogue recombined (evalmm.hip: mms_store_packed); mfh_set_mm_pack
   uint32_t mm_chunk_rows = 131071;  // rows per row chunk of the matrix-core launches (int32 accumulators: |A'C'| <= 2^14 per row)
   int expand_path = 0;     // mfh_crs_expand_mm*: 0 = k_expand_mm (lane = row, MFMA transposition, no LDS tile), 1 = k_evalmm16<MODE 1> (LDS tile + byte gathers)
+  uint32_t expand_periods = 0;  // k_expand_mm: periods per chunk, 0 = automatic (expand_plan.hpp), 2 .. 10 = forced (mfh_set_expand_periods; tests)
   int enc_path = 0;        // mfh_encrypt_rows: 0 = pick by batch size, 1 = VALU kernel (k_encrypt), 2 = matrix-core kernel (k_encrypt_mm)
   uint32_t ncu = 256;        // compute units of the device (launch sizing)
   int dec_path = 0;          // mfh_decrypt: 0 = by batch size, 1 = VALU kernel (k_decrypt), 2 = matrix-core kernel (k_decrypt_mm)

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "expand_plan.hpp"
 
 namespace {
 
@@ -35,6 +36,9 @@ constexpr int MACB = 23;                // blocks (= 92 dwords) per period
 template <int LOGQ> struct XG;
 template <> struct XG<736> { static constexpr int DW = 23, SIG = 22, CPM = 4, PPM = 22, MT = 11, CT = 2; };   // dwords per value, significant, coords / pieces per period
 template <> struct XG<1472> { static constexpr int DW = 46, SIG = 46, CPM = 2, PPM = 24, MT = 12, CT = 1; };
+// (4 CPM coordinates are 4 periods: 2 chunks of 2)
+static_assert(expand_plan(4 * XG<736>::CPM - 1, 736, 1, 2).gx == 2 && expand_plan(4 * XG<1472>::CPM - 1, 1472, 1, 2).gx == 2, "expand_plan.hpp counts the periods of XG");
+static_assert(MACB * (int)EXPAND_MAX_PERIODS + 1 <= 256, "a chunk's blocks lie in two consecutive spans");
 
 // Compile-time plan of block position T of a period: which registers form the pieces emitted after this block and what stays pending.
 // Codes: 0..2 = pending dword, 3..6 = new dword 0..3, 7 = padding.
@@ -225,15 +229,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 int expand_mm_region(mfh_ctx *c, uint64_t off, uint32_t nrows, const uint8_t *c8, uint8_t *image) {
   const uint32_t n = c->P.n;
   const bool q736 = c->P.logq == 736;
-  const uint32_t ct = q736 ? XG<736>::CT : XG<1472>::CT, mt = q736 ? XG<736>::MT : XG<1472>::MT, cpm = q736 ? XG<736>::CPM : XG<1472>::CPM;
+  const uint32_t ct = q736 ? XG<736>::CT : XG<1472>::CT, mt = q736 ? XG<736>::MT : XG<1472>::MT;
   const uint32_t mtiles = (n + 1 + ct - 1) / ct * mt;
   const uint32_t KS = (nrows + 255) / 256 * 4;  // 64-row k-steps of the region, padded to the streaming kernel's 256-row stages
-  const uint32_t ksteps = (nrows + 63) / 64, nper = (n + 1 + cpm - 1) / cpm;
-  // chunks of at most 10 periods (the counter-mode shortcut's two spans), sized for about eight rounds of the 512 workgroup slots
-  const uint32_t gy = (ksteps + 15) / 16;
-  uint32_t ppc = 10;
-  while (ppc > 2 && (uint64_t)gy * ((nper + ppc - 1) / ppc) < 4096) ppc--;
-  const uint32_t gx = (nper + ppc - 1) / ppc;
+  // chunks of at most 10 periods (the counter-mode shortcut's two spans), sized for about eight rounds of the 512 workgroup slots (expand_plan.hpp)
+  const ExpandPlan pl = expand_plan(n, c->P.logq, nrows, c->expand_periods);
+  const uint32_t ppc = pl.ppc, gx = pl.gx, gy = pl.gy;
   mf::AesKey keyx = c->key;
   for (int i = 56; i < 60; i++) keyx.rk[i] ^= 0x80808080u;
   if (q736)

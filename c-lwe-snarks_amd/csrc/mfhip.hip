@@ -42,6 +42,7 @@ struct PS {
 };
 
 #include "ctx.hpp"
+#include "expand_plan.hpp"
 
 static void upload_free(mfh_ctx *c);  // (mfh_ssp_upload's staging lanes, below)
 
@@ -1054,6 +1055,12 @@ int mfh_set_overlap(mfh_ctx *c, int en) {
 int mfh_set_expand_path(mfh_ctx *c, int path) {
   if (!c || path < 0 || path > 1) return MFH_EINVAL;
   c->expand_path = path;
+  return MFH_OK;
+}
+
+int mfh_set_expand_periods(mfh_ctx *c, uint32_t periods) {
+  if (!c || (periods && (periods < EXPAND_MIN_PERIODS || periods > EXPAND_MAX_PERIODS))) return MFH_EINVAL;
+  c->expand_periods = periods;
   return MFH_OK;
 }
 

@@ -818,6 +818,10 @@ int mfh_crs_set_resident_mm(mfh_ctx *ctx, const uint8_t *d_image);
 /* Which kernel writes the image (same bytes for every row tile and row that exists; tuning / A-B): 0 (default) the barrier-free writer
  * (lane = row, 16 x 16 byte transposition on the matrix cores, csrc/expandmm.hip), 1 the LDS-tile writer (k_evalmm16<MODE 1>). */
 int mfh_set_expand_path(mfh_ctx *ctx, int path);
+/* Periods (of 23 AES blocks) a workgroup of the barrier-free writer walks per chunk: 0 (default) picked from the region's row count, 2 .. 10 forced; anything else is
+ * MFH_EINVAL.  The image's bytes do not depend on it (tests: regions small enough for a test select 2 on their own).  Holds for every expansion of the context, the
+ * transient image of mfh_prove_batch included. */
+int mfh_set_expand_periods(mfh_ctx *ctx, uint32_t periods);
 /* prover() for nproofs statements under ONE CRS and SSP.  The S and AS regions are expanded (or streamed from the image, below) once per group of up to 31 proofs, the
  * BT+BV region once per up to 255 (the S / AS launches of the streaming regime: 255 proofs per two passes over a region), and the multiply-accumulate of the coefficient vectors runs on the matrix cores (mfh_eval_rows_multi); proof b is bit-identical to
  * mfh_prove(witness b, delta b, smudging b).  h_witness_bits: nproofs bit strings, bits_stride bytes apart; h_delta: nproofs values

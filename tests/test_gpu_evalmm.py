@@ -253,7 +253,9 @@ def test_expansion_kernels_write_the_same_image(gpu_ctx_factory, logq, d, m):
     """mfh_crs_expand_mm through the barrier-free writer (k_expand_mm: lane = row, 16 x 16 byte transposition on the matrix cores) and
     through the LDS-tile writer (k_evalmm16<MODE 1>): the same bytes for every row tile, byte position and row that exists, in all three
     regions (S and AS start at byte 0 / 8 of an AES block by row parity; BT+BV has m rows: not a multiple of 64), and for a rank's shares.
-    (Row tiles past the b coordinate and rows past the region are never read back and are left to each kernel.)"""
+    (Row tiles past the b coordinate and rows past the region are never read back and are left to each kernel.)
+    This compares two kernels that share their AES and their geometry; what the bytes must BE is stated independently in tests/expand_mm_ref.py and held against both
+    kernels in tests/test_gpu_expand_mm.py (the masks below are that reference's DATA class: tests/test_expand_mm_ref_cpu.py::test_the_tile_of_the_last_bytes_of_b)."""
     import c_lwe_snarks_amd as mf
 
     p = mf.Params(logq=logq, d=d, m=m)

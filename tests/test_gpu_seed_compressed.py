@@ -9,7 +9,8 @@ C. stream block 2^32 (byte 2^36, where the counter's high word changes and the t
    exactly at a row start, through every call that builds span constants: mfh_encrypt_rows (both kernels), mfh_decrypt_rows, mfh_keystream,
    mfh_sample_rows, mfh_eval_rows (both kernels), mfh_eval_rows_multi (both layouts) and mfh_crs_expand + mfh_eval_rows_resident.
 
-Not covered here: mfh_crs_expand_mm takes no stream offset and reaches byte 2^36 only from about 508 000 rows on, so k_expand_mm is not run at the boundary.
+Not covered here: k_expand_mm.  mfh_crs_expand_mm takes no stream offset, but a small share of a large d reaches byte 2^36 through mfh_crs_expand_mm_share:
+tests/test_gpu_expand_mm.py::test_counter_block_two_to_the_32 runs the kernel at the boundary.
 """
 import ctypes
 
