@@ -105,6 +105,7 @@ EXPORTS = [
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
     "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
+    "mfh_merkle_load_keys", "mfh_merkle_check_table",
 ]
 
 
@@ -274,6 +275,8 @@ def load_library():
         "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
         "mfh_merkle_range_rows": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
         "mfh_merkle_range_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "mfh_merkle_load_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, vp, u32, vp]),
+        "mfh_merkle_check_table": (i32, [vp, vp, vp, sz, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
@@ -1101,6 +1104,78 @@ class MerkleTree:
         c._chk(c.lib.mfh_merkle_balance_sum(c._h, self._h, _ptr(tab), tstride, length, int(key_bytes), int(amount_bytes), total, ctypes.byref(live)))
         self._keep = []
         return int(total[0]) | int(total[1]) << 64, int(live.value)
+
+    def _packed(self, what, who, name, none_ok=False, pad=False):
+        """(tensor or None, n, width) of the packed keys or payloads of load_keys: a contiguous uint8 [n, width] device tensor taken as it is, or a host array / list
+        uploaded (words._keys_array parses keys; pad=True: a list of payloads, zero-padded to the longest)"""
+        from .words import CircuitError, _keys_array
+
+        c = self._ctx
+        if what is None and none_ok:
+            return None, None, 0
+        if isinstance(what, c.torch.Tensor):
+            if what.dtype != c.torch.uint8 or what.device != c.device or what.dim() != 2 or not what.is_contiguous():
+                raise MfhError(f"{who}: a device tensor of {name} is contiguous uint8 [n, width] on the context's device")
+            return what, int(what.shape[0]), int(what.shape[1])
+        if pad and not isinstance(what, np.ndarray):
+            items = [bytes(p) for p in what]
+            width = max((len(p) for p in items), default=0)
+            a = np.zeros((len(items), width), dtype=np.uint8)
+            for i, p in enumerate(items):
+                a[i, : len(p)] = np.frombuffer(p, dtype=np.uint8)
+        elif pad:
+            a = np.ascontiguousarray(what)
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise CircuitError(f"{who}: payloads are uint8 [n, payload_bytes]")
+        else:
+            a = np.ascontiguousarray(_keys_array(what, who))
+        n, width = a.shape
+        return (c.to_device(a) if a.size else None), n, width
+
+    def load_keys(self, table, keys, payloads=None):
+        """(status, where): the WHOLE indexed table of the set `keys` and this tree, built on the device (mfh_merkle_load_keys: a device sort of the keys, one
+        launch that writes every record, the tree as set_records(0, table) makes it; waits for the stream once, for the status).  On status 0 (where = None)
+        the table holds the bytes of words.indexed_records(keys, depth, length, payloads).  Status 2, where = the lowest index of a key that is all-zero or
+        all-0xFF; status 1, where = (i, j), the two lowest indices of the smallest key given twice; with either NOTHING of table or tree is written.
+        table: under update_records' rules, MODIFIED IN PLACE (bytes behind `length` in a wider stride stay).  keys: np.uint8 [n, key_bytes] or a list of
+        bytes-likes of one length (words._keys_array), in any order, uploaded; or a contiguous torch uint8 [n, key_bytes] tensor on the context's device, taken
+        as it is.  payloads: None (all zero), np.uint8 [n, payload_bytes], a list of bytes-likes (zero-padded to the longest), or a device tensor, in the
+        order of the keys.  CircuitError / MfhError with the library's text for more than 2^depth - 1 keys, key_bytes outside [1, 32] or 2 key_bytes +
+        payload_bytes > length."""
+        c = self._ctx
+        who = "load_keys"
+        tab, tstride, length = self._table(table, who)
+        k, nk, kb = self._packed(keys, who, "keys")
+        pay, npay, pb = self._packed(payloads, who, "payloads", none_ok=True, pad=True)
+        if pay is None or pb == 0:
+            pay, pb = None, 0  # (no payload bytes at all is no payload)
+        elif npay != nk:
+            raise MfhError(f"{who}: one payload per key, in the order of the keys")
+        status = (ctypes.c_uint32 * 3)()
+        c._chk(c.lib.mfh_merkle_load_keys(c._h, self._h, _ptr(tab), tstride, length, kb, nk, _ptr(k), _ptr(pay), pb, status))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        else:
+            self._keep += [x for x in (k, pay) if x is not None]
+        st = int(status[0])
+        return st, (None if st == 0 else int(status[1]) if st == 2 else (int(status[1]), int(status[2])))
+
+    def check_table(self, table, key_bytes):
+        """(status, live, where): does the indexed table still have the invariant every key statement is sound relative to, and does this tree belong to it
+        (mfh_merkle_check_table: only reads; waits for the stream)?  live = the number of live records.  Status 0 (where = None): all good.  1: the chain of
+        the live records sorted by (lo, slot) breaks, where = the slot words.indexed_check reports (0xFFFFFFFF without any live record).  2: where = the lowest
+        slot whose record does not hash to its leaf.  3: where = (level, index) of the lowest wrong inner node, the leaves' parents being level 1.  A defect of
+        a lower status hides those of a higher one.  table: under update_records' rules, only read."""
+        c = self._ctx
+        who = "check_table"
+        tab, tstride, length = self._table(table, who)
+        if not isinstance(key_bytes, (int, np.integer)) or not 1 <= key_bytes <= 32 or length < 2 * key_bytes:
+            raise MfhError(f"{who}: 1 <= key_bytes <= 32 and 2 key_bytes <= length")
+        out = (ctypes.c_uint32 * 4)()
+        c._chk(c.lib.mfh_merkle_check_table(c._h, self._h, _ptr(tab), tstride, length, int(key_bytes), out))
+        self._keep = []
+        st = int(out[0])
+        return st, int(out[1]), (None if st == 0 else (int(out[2]), int(out[3])) if st == 3 else int(out[2]))
 
 
 class Context:

@@ -37,6 +37,9 @@
 // k_insert_records, k_remove_records, k_transfer_records: what a batch of key steps ends with -- all 2 nk new records built in one launch from the step's plan,
 // then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
 // (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
+// k_sort_tiles, k_sort_merge: key_sort, the device sort of multi-word keys with a tag (tiles in LDS, then merge passes over a merge-path partition:
+// merkle_sort.hpp).  k_load_entries, k_load_dups, k_load_dup_tags, k_load_records: mfh_merkle_load_keys, a whole indexed table and its tree out of a key set on
+// the device.  k_check_entries, k_chain_check, k_leaf_check, k_node_check: mfh_merkle_check_table, the table's invariant and the tree over it, read only.
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
 #include <functional>
@@ -53,6 +56,7 @@
 #include "merkle_remove.hpp"
 #include "merkle_rows.hpp"
 #include "merkle_sched.hpp"
+#include "merkle_sort.hpp"
 #include "merkle_transfer.hpp"
 #include "sha256_dev.hpp"
 
@@ -691,6 +695,247 @@ __global__ __launch_bounds__(256) void k_insert_records(const uint8_t *__restric
     }
   }
   fresh[g] = out;
+}
+
+// ---- key_sort: n entries of KW key words and a tag into (words, tag) order -- the whole-table order that k_range_order, quadratic, cannot give
+// (merkle_sort.hpp has entries, the order, the partition and the scratch).  Two kernels, no atomics; the result is the one sorted permutation whatever order
+// threads or workgroups run in.
+//   k_sort_tiles<KW>  one workgroup of 256 threads a tile of kSortTile = 1 024 entries: the tile goes into LDS word-plane by word-plane (plane j = word j of
+//                     every entry, 4 KiB: lanes reading one word of consecutive entries hit consecutive banks), a ragged last tile padded with entries of
+//                     all-ones words and tag 0xFFFFFFFF, above every real entry (a real tag is an index below 2^24).  A bitonic network of 55 steps, two
+//                     compare-exchanges a thread and step, then the tile's real entries go back IN PLACE.
+//   k_sort_merge<KW>  one merge pass a launch, from `src` into `dst`: workgroup g owns outputs [1 024 g, 1 024 g + count) (mf::merge_slice), finds its
+//                     slices of the two runs by mf::merge_path on both diagonals -- the even lanes of every wave search one, the odd lanes the other, no barrier -- stages
+//                     them in LDS, and ranks every staged entry in the OTHER slice by a binary search: an entry of a goes behind the entries of b below it,
+//                     an entry of b behind those of a not above it, so the ranks are a permutation of [0, count).  A pass reads and writes (KW + 1) 4 n bytes.
+template <int KW>
+__device__ __forceinline__ bool planes_less(const uint32_t *pl, uint32_t x, uint32_t y) {  // entry x < entry y of a tile in word planes
+#pragma unroll
+  for (int j = 0; j <= KW; j++) {
+    const uint32_t a = pl[j * mf::kSortTile + x], b = pl[j * mf::kSortTile + y];
+    if (a != b) return a < b;
+  }
+  return false;
+}
+
+// BARRIERS: every thread of a workgroup runs the same 55 steps and the barrier of each, whatever n: the loops' bounds are constants, and a tile's padding
+// is data, not a branch.  No `return` stands in front of a barrier.  The grid is sort_tiles(n) workgroups, so every workgroup has at least one real entry.
+// Reads and writes ent[e] for t0 <= e < min(t0 + 1 024, n) only.
+template <int KW>
+__global__ __launch_bounds__(256) void k_sort_tiles(uint32_t *__restrict__ ent, uint32_t n) {
+  __shared__ uint32_t pl[(KW + 1) * mf::kSortTile];
+  const uint32_t t0 = blockIdx.x * mf::kSortTile, fill = min(mf::kSortTile, n - t0);
+  for (uint32_t e = threadIdx.x; e < mf::kSortTile; e += 256) {
+#pragma unroll
+    for (int j = 0; j <= KW; j++) pl[j * mf::kSortTile + e] = e < fill ? ent[(size_t)(t0 + e) * (KW + 1) + j] : 0xFFFFFFFFu;
+  }
+  __syncthreads();
+  for (uint32_t k = 2; k <= mf::kSortTile; k <<= 1) {
+    for (uint32_t j = k >> 1; j; j >>= 1) {
+#pragma unroll
+      for (uint32_t h = 0; h < mf::kSortTile / 512; h++) {
+        const uint32_t p = h * 256 + threadIdx.x, lo = 2 * p - (p & (j - 1)), hi = lo | j;  // the p-th pair of this step: lo has bit j clear
+        const bool up = !(lo & k);  // (k = 1 024: bit 10 of lo < 1 024 is clear, the last merge ascends)
+        if (planes_less<KW>(pl, hi, lo) == up) {  // out of order for this direction (entries differ: tags do, or both are padding)
+#pragma unroll
+          for (int w = 0; w <= KW; w++) {
+            const uint32_t a = pl[w * mf::kSortTile + lo];
+            pl[w * mf::kSortTile + lo] = pl[w * mf::kSortTile + hi];
+            pl[w * mf::kSortTile + hi] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t e = threadIdx.x; e < fill; e += 256) {
+#pragma unroll
+    for (int j = 0; j <= KW; j++) ent[(size_t)(t0 + e) * (KW + 1) + j] = pl[j * mf::kSortTile + e];
+  }
+}
+
+// BARRIERS: ONE barrier, between the staging and the ranking, reached by every thread: the slice is a function of (n, run, blockIdx) alone and the staging
+// loop only skips entries past `count`.  No `return` stands in front of it.  The grid is sort_tiles(n) workgroups: count >= 1 everywhere.
+// Reads src[e] for e inside the pair of runs (below n); writes dst[s.out0 + q] for every q < count exactly once.
+template <int KW>
+__global__ __launch_bounds__(256) void k_sort_merge(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, uint32_t n, uint32_t run) {
+  __shared__ uint32_t pl[(KW + 1) * mf::kSortTile];
+  const mf::MergeSlice s = mf::merge_slice(n, run, blockIdx.x);
+  const uint32_t *a = src + (size_t)s.a_at * (KW + 1), *b = a + (size_t)s.na * (KW + 1);
+  // the two diagonals side by side: even lanes search d0 and odd lanes d0 + count, so the two chains of dependent loads overlap; lanes 0 and 1 hold the answers
+  const uint32_t found = mf::merge_path<KW>(a, s.na, b, s.nb, s.d0 + (threadIdx.x & 1 ? s.count : 0u));
+  const uint32_t a0 = __shfl(found, 0), a1 = __shfl(found, 1);
+  const uint32_t b0 = s.d0 - a0, ca = a1 - a0;  // staged: a[a0, a1) at [0, ca), b[b0, b0 + count - ca) at [ca, count)
+  for (uint32_t e = threadIdx.x; e < s.count; e += 256) {
+    const uint32_t *from = e < ca ? a + (size_t)(a0 + e) * (KW + 1) : b + (size_t)(b0 + e - ca) * (KW + 1);
+#pragma unroll
+    for (int j = 0; j <= KW; j++) pl[j * mf::kSortTile + e] = from[j];
+  }
+  __syncthreads();
+  for (uint32_t e = threadIdx.x; e < s.count; e += 256) {
+    const bool of_a = e < ca;
+    uint32_t l = of_a ? ca : 0, r = of_a ? s.count : ca;  // the other slice
+    while (l < r) {
+      const uint32_t m = l + (r - l) / 2;
+      // of a: the first entry of b not below e.  of b: the first entry of a above e
+      const bool right = of_a ? planes_less<KW>(pl, m, e) : !planes_less<KW>(pl, e, m);
+      if (right) l = m + 1; else r = m;
+    }
+    const uint32_t q = of_a ? e + (l - ca) : (e - ca) + l;
+#pragma unroll
+    for (int j = 0; j <= KW; j++) dst[(size_t)(s.out0 + q) * (KW + 1) + j] = pl[j * mf::kSortTile + e];
+  }
+}
+
+// ---- mfh_merkle_load_keys: a whole indexed table out of a key set on the device.
+//   k_load_entries<KW>  one thread per key i < n: its words through load_key_words (packed keys at any alignment, nothing outside [keys, keys + n K)) and the
+//                       tag i; a sentinel key (all-zero or all-0xFF over its bytes) reports status[0] <- min(status[0], i), an atomic minimum as k_key_locate's:
+//                       the lowest index, whatever order the threads run in.
+//   k_load_dups<KW>     one thread per sorted neighbour pair r, r + 1: equal keys report status[1] <- min(status[1], r); k_load_dup_tags, one thread behind it,
+//                       leaves the two tags of that rank in status[2], status[3] -- the two lowest input indices of the smallest duplicated key, as equal keys
+//                       stand in tag order.  The host reads the four words in ONE copy.
+//   k_load_records      one item per record r < 2^depth and 16-byte window of the DESTINATION's dword grid, k_record_store's items: record 0 = (00..00 | key of
+//                       sorted entry 0), record r = (key r - 1 | key r | payload of tag r - 1) for r <= n, the last hi FF..FF, records above n all zero.  The
+//                       keys' bytes come from the caller's packed keys at tag * K and the payloads from tag * P, through load_unit_within and merge_unit as
+//                       k_insert_records merges its three ranges; bytes [2K + P, length) are zero.
+//                       Reads: the tags of sorted entries r - 1 and r, nothing outside [keys, keys + n K) and [pay, pay + n P).  Writes: bytes [0, length) of
+//                       every record and nothing else -- no gap byte of a wider stride, nothing before the table or behind its last record.
+template <int KW>
+__global__ __launch_bounds__(256) void k_load_entries(const uint8_t *__restrict__ keys, uint32_t key_bytes, uint32_t n, uint32_t *__restrict__ ent,
+                                                      uint32_t *__restrict__ status) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[KW];
+  load_key_words<KW>(keys, (int64_t)i * key_bytes, key_bytes, (int64_t)n * key_bytes, w);
+  const uint32_t last = key_bytes & 3 ? ~0u << (8 * (4 - (key_bytes & 3))) : ~0u;  // the all-0xFF key's last word
+  bool zero = true, ones = true;
+#pragma unroll
+  for (int j = 0; j < KW; j++) {
+    ent[(size_t)i * (KW + 1) + j] = w[j];
+    zero = zero && w[j] == 0;
+    ones = ones && w[j] == (j == KW - 1 ? last : ~0u);
+  }
+  ent[(size_t)i * (KW + 1) + KW] = i;
+  if (zero || ones) atomicMin(status, i);
+}
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_load_dups(const uint32_t *__restrict__ ent, uint32_t n, uint32_t *__restrict__ status) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r + 1 >= n) return;
+  bool same = true;
+#pragma unroll
+  for (int j = 0; j < KW; j++) same = same && ent[(size_t)r * (KW + 1) + j] == ent[(size_t)(r + 1) * (KW + 1) + j];
+  if (same) atomicMin(status + 1, r);
+}
+
+__global__ void k_load_dup_tags(const uint32_t *__restrict__ ent, uint32_t kw, uint32_t *__restrict__ status) {
+  const uint32_t r = status[1];
+  if (threadIdx.x || r == mf::kNoRecord) return;
+  status[2] = ent[(size_t)r * (kw + 1) + kw];
+  status[3] = ent[(size_t)(r + 1) * (kw + 1) + kw];
+}
+
+__global__ __launch_bounds__(256) void k_load_records(uint8_t *__restrict__ table, size_t table_stride, uint32_t records, const uint32_t *__restrict__ ent,
+                                                      uint32_t kw, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ pay, uint32_t key_bytes,
+                                                      uint32_t pay_bytes, uint32_t length, uint32_t n) {
+  const uint32_t units = (length + 18) / 16;
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;  // (records * units < 2^32: checked by the host)
+  if (g >= (uint64_t)records * units) return;
+  const uint32_t r = (uint32_t)(g / units), u = (uint32_t)(g - (uint64_t)r * units);
+  uint8_t *dst = table + (size_t)r * table_stride;
+  const int64_t s = (int64_t)16 * u - (int64_t)(reinterpret_cast<uintptr_t>(dst) & 3);  // the window's first byte, as an offset in the record
+  const int64_t end = min(s + 16, (int64_t)length);
+  if (end <= max(s, (int64_t)0)) return;
+  const int64_t K = key_bytes, P = pay_bytes, keys_span = (int64_t)n * K, pay_span = (int64_t)n * P;
+  uint4 out = make_uint4(0, 0, 0, 0);
+  // (merge_unit is handed the window and the ranges moved up by 4: s is as low as -3 here, and every other caller's offset is >= 0 -- the compiler specialises
+  // the shared helper on that, so a negative offset here would change THEIR code)
+  if (r <= n) {
+    const int64_t lo_key = r ? (int64_t)ent[(size_t)(r - 1) * (kw + 1) + kw] : -1, hi_key = r < n ? (int64_t)ent[(size_t)r * (kw + 1) + kw] : -1;
+    if (s < K && lo_key >= 0)  // lo (record 0: the all-zero sentinel)
+      out = merge_unit(out, load_unit_within(keys, lo_key * K + s, lo_key * K + min(s + 16, K), keys_span), s + 4, 4, K + 4);
+    if (s < 2 * K && s + 16 > K) {  // hi (record n: the all-0xFF sentinel)
+      const uint4 v = hi_key >= 0 ? load_unit_within(keys, hi_key * K + s - K, hi_key * K + min(s + 16, 2 * K) - K, keys_span) : make_uint4(~0u, ~0u, ~0u, ~0u);
+      out = merge_unit(out, v, s + 4, K + 4, 2 * K + 4);
+    }
+    if (s + 16 > 2 * K && s < 2 * K + P && pay && lo_key >= 0)  // the payload
+      out = merge_unit(out, load_unit_within(pay, lo_key * P + s - 2 * K, lo_key * P + min(s + 16, 2 * K + P) - 2 * K, pay_span), s + 4, 2 * K + 4, 2 * K + P + 4);
+  }
+  const uint32_t w[4] = {out.x, out.y, out.z, out.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int64_t o = s + 4 * j;
+    if (o >= 0 && o + 4 <= (int64_t)length) {
+      *reinterpret_cast<uint32_t *>(dst + o) = w[j];
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+        if (o + b >= 0 && o + b < (int64_t)length) dst[o + b] = (uint8_t)(w[j] >> (8 * b));
+    }
+  }
+}
+
+// ---- mfh_merkle_check_table: does a table still have its invariant, and does the tree belong to it?  The live records are selected and their keys made dense
+// by the range reads' kernels (k_range_flags with the bounds 00..00 and FF..FF, k_inert_scan, k_inert_select, k_range_keys: every live record is a link of the
+// whole key space), then
+//   k_check_entries<KW>  one thread per live record r < n: entry r <- (lo of dense[r], tag r).  The slots stand in table order, so the tag orders equal lo by slot.
+//   k_chain_check<KW>    one thread per SORTED record i: lo_0 == 00..00 (fails at 0), hi_i == lo_i+1 (fails at i + 1), hi_n-1 == FF..FF (fails at n - 1), hi_i
+//                        being dense[tag_i]'s.  A failure reports chain <- min(chain, rank << 32 | slot), ONE 64-bit atomic minimum: the first failure in
+//                        sorted order with its slot, whatever order the threads run in (mf::range_status' convention).
+//   k_leaf_check         one thread per slot: the digest k_sha256_records left in scratch against the tree's leaf; leaf <- min(leaf, slot).
+//   k_node_check         one launch per level l = 1 .. depth, one thread per node j: the stored node against compress(IV, its two stored children), k_merkle_level's
+//                        loads; node <- min(node, l << 32 | j): the lowest level with a wrong node and the lowest index there.
+// Nothing is written but the call's scratch.
+template <int KW>
+__global__ __launch_bounds__(256) void k_check_entries(const uint32_t *__restrict__ dense, uint32_t n, uint32_t *__restrict__ ent) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+#pragma unroll
+  for (int j = 0; j < KW; j++) ent[(size_t)r * (KW + 1) + j] = dense[(size_t)r * 2 * KW + j];
+  ent[(size_t)r * (KW + 1) + KW] = r;
+}
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_chain_check(const uint32_t *__restrict__ ent, uint32_t n, const uint32_t *__restrict__ dense,
+                                                     const uint32_t *__restrict__ slots, uint32_t key_bytes, unsigned long long *__restrict__ chain) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t tag = ent[(size_t)i * (KW + 1) + KW];
+  const uint32_t last = key_bytes & 3 ? ~0u << (8 * (4 - (key_bytes & 3))) : ~0u;
+  bool lo_zero = true, hi_ones = true, joins = true;
+#pragma unroll
+  for (int j = 0; j < KW; j++) {
+    const uint32_t hi = dense[(size_t)tag * 2 * KW + KW + j];
+    lo_zero = lo_zero && ent[(size_t)i * (KW + 1) + j] == 0;
+    hi_ones = hi_ones && hi == (j == KW - 1 ? last : ~0u);
+    if (i + 1 < n) joins = joins && hi == ent[(size_t)(i + 1) * (KW + 1) + j];
+  }
+  if (i == 0 && !lo_zero) atomicMin(chain, (unsigned long long)slots[tag]);  // rank 0
+  if (i + 1 < n && !joins) atomicMin(chain, (unsigned long long)(i + 1) << 32 | slots[ent[(size_t)(i + 1) * (KW + 1) + KW]]);
+  if (i + 1 == n && !hi_ones) atomicMin(chain, (unsigned long long)i << 32 | slots[tag]);
+}
+
+__global__ __launch_bounds__(256) void k_leaf_check(const uint4 *__restrict__ dig, const uint4 *__restrict__ leaves, uint32_t n, uint32_t *__restrict__ leaf) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint4 a0 = dig[2 * (size_t)i], a1 = dig[2 * (size_t)i + 1], b0 = leaves[2 * (size_t)i], b1 = leaves[2 * (size_t)i + 1];
+  if (a0.x != b0.x || a0.y != b0.y || a0.z != b0.z || a0.w != b0.w || a1.x != b1.x || a1.y != b1.y || a1.z != b1.z || a1.w != b1.w) atomicMin(leaf, i);
+}
+
+// nodes [p0, p0 + n) in heap order, the level l: p0 = 2^(depth - l)
+__global__ __launch_bounds__(256) void k_node_check(const uint4 *__restrict__ nodes, uint32_t p0, uint32_t n, uint32_t l, unsigned long long *__restrict__ node) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t k = (size_t)p0 + i;
+  const uint4 *ch = nodes + 4 * k;
+  const uint4 c0 = bswap4(ch[0]), c1 = bswap4(ch[1]), c2 = bswap4(ch[2]), c3 = bswap4(ch[3]);
+  uint32_t w[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+  uint32_t h[8] = MF_SHA256_IV;
+  mf::sha256_compress(h, w);
+  const uint4 s0 = bswap4(nodes[2 * k]), s1 = bswap4(nodes[2 * k + 1]);
+  if (s0.x != h[0] || s0.y != h[1] || s0.z != h[2] || s0.w != h[3] || s1.x != h[4] || s1.y != h[5] || s1.z != h[6] || s1.w != h[7])
+    atomicMin(node, (unsigned long long)l << 32 | i);
 }
 
 // ---- mfh_merkle_remove_keys: where the keys of a batch of removes stand in an indexed table, and the 2 nk new records of the batch.
@@ -2313,6 +2558,210 @@ int mfh_merkle_remove_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size
   if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
   const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
   return remove_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- key_sort and the two calls on it, mfh_merkle_load_keys and mfh_merkle_check_table (k_sort_tiles, k_load_entries and k_check_entries have the kernels,
+// merkle_sort.hpp the scratch)
+
+// n entries of buf0 into (words, tag) order: the tile sort in place, then sort_passes(n) merge passes between buf0 and buf1; the buffer that holds the
+// result.  1 + sort_passes(n) launches of the kind "merkle_sort" (mfhip.hip: timing_kind), none for n = 0
+template <int W>
+uint32_t *key_sort(mfh_ctx *c, uint32_t n, uint32_t *buf0, uint32_t *buf1) {
+  if (!n) return buf0;
+  const dim3 grid(mf::sort_tiles(n));
+  {
+    Timer tm(c, 44, n);
+    hipLaunchKernelGGL(k_sort_tiles<W>, grid, dim3(256), 0, c->stream, buf0, n);
+  }
+  uint32_t *src = buf0, *dst = buf1;
+  for (uint32_t p = 0; p < mf::sort_passes(n); p++) {
+    Timer tm(c, 44, n);
+    hipLaunchKernelGGL(k_sort_merge<W>, grid, dim3(256), 0, c->stream, (const uint32_t *)src, dst, n, mf::kSortTile << p);
+    std::swap(src, dst);
+  }
+  return src;
+}
+
+// what the two calls ask of the table's shape, mfh_merkle_absent_rows' texts; `tail`: the bytes a record needs behind its two keys
+const char *table_refused(size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t tail, const char *short_length) {
+  if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return "key_bytes must be in [1, 32]";
+  if ((uint64_t)length < (uint64_t)2 * key_bytes + tail) return short_length;
+  return records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_load_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk, const uint8_t *d_keys,
+                         const uint8_t *d_payloads, uint32_t payload_bytes, uint32_t h_status[3]) {
+  const char *who = "mfh_merkle_load_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  const uint32_t depth = t->depth, records = 1u << depth, units = (length + 18) / 16;
+  if (nk > records - 1) return fail(c, who, "more keys than the 2^depth - 1 slots behind the sentinel record");
+  if (const char *what = table_refused(table_stride, length, key_bytes, payload_bytes, "length shorter than the two keys and the payload, 2 key_bytes + payload_bytes bytes"))
+    return fail(c, who, what);
+  if ((uint64_t)records * units >> 32) return fail(c, who, "the table's records exceed 2^32 units of 16 bytes");
+  if (!d_table) return fail(c, who, "a load without d_table");
+  if (nk && !d_keys) return fail(c, who, "keys without d_keys");
+  if (d_payloads && !payload_bytes) return fail(c, who, "d_payloads with payload_bytes = 0");
+  if (!h_status) return fail(c, who, "a load without h_status");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t kw = mf::key_words(key_bytes);
+  const mf::LoadScratch s = mf::load_scratch(depth, nk, key_bytes);
+  if (int rc = work_reserve(c, c->circ_io, s.bytes)) return rc;
+  uint8_t *d_work = c->circ_io.as<uint8_t>();
+  uint32_t *d_ent0 = reinterpret_cast<uint32_t *>(d_work + s.ent0_at), *d_ent1 = reinterpret_cast<uint32_t *>(d_work + s.ent1_at),
+           *d_status = reinterpret_cast<uint32_t *>(d_work + s.status_at);
+  const uint32_t *d_sorted = d_ent0;
+  if (nk) {
+    HIP_TRY(c, hipMemsetAsync(d_status, 0xFF, 16, c->stream));
+    const dim3 grid((nk + 255) / 256);
+    with_key_words(kw, [&](auto KW) {
+      constexpr int W = decltype(KW)::value;
+      {
+        Timer tm(c, 45, nk);  // "merkle_load" (mfhip.hip: timing_kind): the entries and the sentinel check ...
+        hipLaunchKernelGGL(k_load_entries<W>, grid, dim3(256), 0, c->stream, d_keys, key_bytes, nk, d_ent0, d_status);
+      }
+      d_sorted = key_sort<W>(c, nk, d_ent0, d_ent1);
+      {
+        Timer tm(c, 45, nk);  // ... the duplicate check on sorted neighbours ...
+        hipLaunchKernelGGL(k_load_dups<W>, grid, dim3(256), 0, c->stream, d_sorted, nk, d_status);
+      }
+    });
+    {
+      Timer tm(c, 45, 0);  // ... and its two tags
+      hipLaunchKernelGGL(k_load_dup_tags, dim3(1), dim3(64), 0, c->stream, d_sorted, kw, d_status);
+    }
+    HIP_TRY(c, hipGetLastError());
+    uint32_t *pin = (uint32_t *)pin_acquire(c, c->pin_cw, 16);
+    if (!pin) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin, d_status, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (pin[0] != mf::kNoRecord || pin[1] != mf::kNoRecord) {  // a sentinel key goes before a duplicate
+      const bool sentinel = pin[0] != mf::kNoRecord;
+      h_status[0] = sentinel ? 2 : 1;
+      h_status[1] = sentinel ? pin[0] : pin[2];
+      h_status[2] = sentinel ? mf::kNoRecord : pin[3];
+      return MFH_OK;
+    }
+  }
+  {
+    Timer tm(c, 45, records);  // the build launch: every record of the table
+    hipLaunchKernelGGL(k_load_records, dim3((uint32_t)(((uint64_t)records * units + 255) / 256)), dim3(256), 0, c->stream, d_table, table_stride, records, d_sorted, kw,
+                       d_keys, d_payloads, key_bytes, payload_bytes, length, nk);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (int rc = sha256_records(c, d_table, table_stride, length, records, t->level(0))) return rc;  // mfh_merkle_set_records' two steps
+  if (int rc = merkle_update(c, t, 0, records)) return rc;
+  h_status[0] = 0;
+  h_status[1] = h_status[2] = mf::kNoRecord;
+  return MFH_OK;
+}
+
+int mfh_merkle_check_table(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t h_out[4]) {
+  const char *who = "mfh_merkle_check_table";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (const char *what = table_refused(table_stride, length, key_bytes, 0, "length shorter than the two keys' 2 key_bytes bytes")) return fail(c, who, what);
+  if (!d_table) return fail(c, who, "a check without d_table");
+  if (!h_out) return fail(c, who, "a check without h_out");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t depth = t->depth, records = 1u << depth, kw = mf::key_words(key_bytes);
+  const int64_t span = (int64_t)(((size_t)records - 1) * table_stride + length);
+  const mf::CheckScratch s = mf::check_scratch(depth, records, key_bytes);
+  if (int rc = work_reserve(c, c->circ_io, s.bytes)) return rc;
+  uint8_t *d_work = c->circ_io.as<uint8_t>();
+  auto words = [&](size_t at) { return reinterpret_cast<uint32_t *>(d_work + at); };
+  unsigned long long *d_mask = reinterpret_cast<unsigned long long *>(d_work + s.mask_at);
+  uint32_t *d_count = words(s.count_at), *d_slots = words(s.slots_at), *d_dense = words(s.dense_at), *d_total = words(s.total_at), *d_ent0 = words(s.ent0_at),
+           *d_ent1 = words(s.ent1_at), *d_result = words(s.result_at);
+  uint4 *d_digests = reinterpret_cast<uint4 *>(d_work + s.digests_at);
+  HIP_TRY(c, hipMemsetAsync(d_result, 0xFF, 32, c->stream));
+  RangeBounds bounds{};  // a = 00..00, b = FF..FF: every live record is a link
+  const uint8_t ones[mf::kMaxKeyBytes] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF,
+                                          0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
+  mf::key_to_words(ones, key_bytes, bounds.b);
+  const dim3 all((records + 255) / 256);
+  with_key_words(kw, [&](auto KW) {
+    constexpr int W = decltype(KW)::value;
+    {
+      Timer tm(c, 46, records);  // "merkle_check" (mfhip.hip: timing_kind): the live records' flags ...
+      hipLaunchKernelGGL(k_range_flags<W>, dim3(s.nb), dim3(256), 0, c->stream, d_table, table_stride, span, key_bytes, records, bounds, d_mask, d_count);
+    }
+    {
+      Timer tm(c, 46, 0);  // ... their scan ...
+      hipLaunchKernelGGL(k_inert_scan, dim3(1), dim3(256), 0, c->stream, d_count, s.nb, d_total);
+    }
+    {
+      Timer tm(c, 46, 0);  // ... their slots in table order ...
+      hipLaunchKernelGGL(k_inert_select, dim3((4 * s.nb + 255) / 256), dim3(256), 0, c->stream, (const unsigned long long *)d_mask, (const uint32_t *)d_count, 4 * s.nb,
+                         records, d_slots);
+    }
+    {
+      Timer tm(c, 46, records);  // ... and their keys
+      hipLaunchKernelGGL(k_range_keys<W>, all, dim3(256), 0, c->stream, d_table, table_stride, span, key_bytes, (const uint32_t *)d_total, records,
+                         (const uint32_t *)d_slots, d_dense);
+    }
+  });
+  HIP_TRY(c, hipGetLastError());
+  uint32_t *pin = (uint32_t *)pin_acquire(c, c->pin_cw, 32);
+  if (!pin) return MFH_ENOMEM;
+  HIP_TRY(c, hipMemcpyAsync(pin, d_total, 4, hipMemcpyDeviceToHost, c->stream));  // the sort's grids and passes are the host's: it needs the count
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t live = pin[0];
+  h_out[1] = live;
+  h_out[2] = h_out[3] = mf::kNoRecord;
+  if (!live) {
+    h_out[0] = 1;
+    return MFH_OK;
+  }
+  with_key_words(kw, [&](auto KW) {
+    constexpr int W = decltype(KW)::value;
+    const dim3 grid((live + 255) / 256);
+    {
+      Timer tm(c, 46, live);  // the entries (lo, rank in table order) ...
+      hipLaunchKernelGGL(k_check_entries<W>, grid, dim3(256), 0, c->stream, (const uint32_t *)d_dense, live, d_ent0);
+    }
+    const uint32_t *d_sorted = key_sort<W>(c, live, d_ent0, d_ent1);
+    {
+      Timer tm(c, 46, live);  // ... and the chain over them in key order
+      hipLaunchKernelGGL(k_chain_check<W>, grid, dim3(256), 0, c->stream, d_sorted, live, (const uint32_t *)d_dense, (const uint32_t *)d_slots, key_bytes,
+                         reinterpret_cast<unsigned long long *>(d_result + 2));
+    }
+  });
+  if (int rc = sha256_records(c, d_table, table_stride, length, records, reinterpret_cast<uint8_t *>(d_digests))) return rc;
+  {
+    Timer tm(c, 46, records);  // the leaves
+    hipLaunchKernelGGL(k_leaf_check, all, dim3(256), 0, c->stream, (const uint4 *)d_digests, reinterpret_cast<const uint4 *>(t->level(0)), records, d_result + 1);
+  }
+  for (uint32_t l = 1; l <= depth; l++) {
+    const uint32_t n = 1u << (depth - l);
+    Timer tm(c, 46, n);  // the nodes of level l
+    hipLaunchKernelGGL(k_node_check, dim3((n + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(t->mem), n, n, l,
+                       reinterpret_cast<unsigned long long *>(d_result + 4));
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(pin, d_result, 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint64_t chain = (uint64_t)pin[3] << 32 | pin[2], node = (uint64_t)pin[5] << 32 | pin[4];
+  if (chain != ~0ull) {
+    h_out[0] = 1;
+    h_out[2] = (uint32_t)chain;
+  } else if (pin[1] != mf::kNoRecord) {
+    h_out[0] = 2;
+    h_out[2] = pin[1];
+  } else if (node != ~0ull) {
+    h_out[0] = 3;
+    h_out[2] = (uint32_t)(node >> 32);
+    h_out[3] = (uint32_t)node;
+  } else {
+    h_out[0] = 0;
+  }
+  return MFH_OK;
 }
 
 }  // extern "C"

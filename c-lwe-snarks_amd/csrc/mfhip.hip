@@ -1164,6 +1164,9 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_range_order")) return 41;  // k_range_keys, k_range_order of the range reads: two per call with max_links > 0; rows = max_links, the grids' bound (the links n are on the device at launch; n when the count was asked first)
   if (!strcmp(which, "merkle_adjust_records")) return 42;  // k_adjust_records of mfh_merkle_adjust_keys (merkle.hip): one per call; rows = the nk new records
   if (!strcmp(which, "merkle_balance_sum")) return 43;  // k_balance_sum, k_balance_fold of mfh_merkle_balance_sum: two per call; rows = the table's 2^depth records on the first, 0 on the fold
+  if (!strcmp(which, "merkle_sort")) return 44;  // k_sort_tiles, k_sort_merge of key_sort (merkle.hip): 1 + ceil(log2(ceil(n / 1024))) per sort of n > 0 entries; rows = n on each
+  if (!strcmp(which, "merkle_load")) return 45;  // k_load_entries, k_load_dups, k_load_dup_tags, k_load_records of mfh_merkle_load_keys: three in front of the wait (nk > 0) and the build launch behind it; rows = nk, nk, 0 and the table's 2^depth records
+  if (!strcmp(which, "merkle_check")) return 46;  // mfh_merkle_check_table: flags, scan, select, keys (4), entries and chain (2, live > 0), leaves (1), nodes (depth); rows = the records, live records or nodes each covers
   return -1;
 }
 

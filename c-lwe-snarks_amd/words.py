@@ -1626,6 +1626,38 @@ def indexed_range(table, key_bytes: int, lo: bytes, hi: bytes):
     return [int(s) for _, s in sorted((rlo[s].tobytes(), int(s)) for s in slots)]
 
 
+def indexed_check(table, key_bytes: int):
+    """(status, live, where): the CHAIN part of the invariant of an indexed table (a uint8 array [n, length]) -- the live records (lo < hi), sorted by (lo,
+    slot), tile the key space from 00..00 to FF..FF.  live is their number.  Status 0 (where = None): they do.  Status 1: where is the slot of the first
+    record in sorted order at which the chain breaks -- sorted record 0 when its lo is not 00..00, sorted record i + 1 at the lowest i with hi_i != lo_i+1,
+    the last record when its hi is not FF..FF --, 0xFFFFFFFF when no record is live.  The host reference of MerkleTree.check_table's status 1.
+    CircuitError for a table that is not uint8 [n, length >= 2 key_bytes] or a key_bytes outside [1, 32]."""
+    K = key_bytes
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= 32 or not isinstance(table, np.ndarray) or table.dtype != np.uint8 or table.ndim != 2 \
+            or table.shape[1] < 2 * K:
+        raise CircuitError("indexed_check: a uint8 table [n, length], length at least 2 key_bytes, key_bytes in [1, 32]")
+    rlo, rhi = table[:, :K], table[:, K: 2 * K]
+    live, open_ = np.zeros(len(table), dtype=bool), np.ones(len(table), dtype=bool)
+    for j in range(K):  # lo < hi per row, big-endian: the first byte that differs decides
+        live |= open_ & (rlo[:, j] < rhi[:, j])
+        open_ &= rlo[:, j] == rhi[:, j]
+    slots = np.flatnonzero(live)
+    n = len(slots)
+    if not n:
+        return 1, 0, 0xFFFFFFFF
+    order = np.lexsort((slots,) + tuple(rlo[slots, j] for j in range(K - 1, -1, -1)))  # (lexsort: the LAST key is the primary one)
+    s = slots[order]
+    lo, hi = rlo[s], rhi[s]
+    if lo[0].any():
+        return 1, n, int(s[0])
+    breaks = np.flatnonzero((hi[:-1] != lo[1:]).any(axis=1))
+    if len(breaks):
+        return 1, n, int(s[breaks[0] + 1])
+    if (hi[-1] != 0xFF).any():
+        return 1, n, int(s[-1])
+    return 0, n, None
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.

@@ -709,6 +709,46 @@ int mfh_merkle_adjust_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, si
  * Kernel timing kind: "merkle_balance_sum" (2 per call, rows = 2^depth on the first and 0 on the fold). */
 int mfh_merkle_balance_sum(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes,
                            uint32_t amount_bytes, uint64_t h_sum[2], uint32_t *h_live);
+/* LOAD a whole indexed table from a key set that is on the device, and its tree: the genesis of a ledger, where mfh_merkle_insert_keys is for increments.
+ * d_keys: nk x key_bytes packed bytes, in ANY order; d_payloads: nk x payload_bytes packed bytes in the order of the keys, or NULL (zero payloads).
+ * On status 0 the WHOLE table and the WHOLE tree are written: slot 0 <- the sentinel record (00..00 | the smallest key), slots 1 .. nk <- one record (key |
+ * next larger key | payload, zero-padded to length) per member in ascending key order, the last with hi = FF..FF, slots nk + 1 .. 2^depth - 1 <- all zero;
+ * bytes [length, table_stride) of a slot are left as they were; the tree <- what mfh_merkle_set_records(t, 0, 2^depth, d_table, table_stride, length) gives.
+ * nk = 0 gives the single record (00..00 | FF..FF).  h_status = {status, where0, where1}:
+ *   0  loaded (where0 = where1 = 0xFFFFFFFF)
+ *   2  a key is a sentinel, all-zero or all-0xFF over its bytes: where0 = the lowest input index of such a key.  Goes before status 1
+ *   1  a key is given twice: where0 < where1 = the two lowest input indices of the SMALLEST duplicated key
+ * and with a status other than 0 NOTHING of the table or the tree is written.
+ *   how        k_load_entries (the keys' words and the tag = input index; the sentinel check), key_sort -- k_sort_tiles (tiles of 1 024 entries sorted in LDS)
+ *              and ceil(log2(ceil(nk / 1024))) launches of k_sort_merge (merge-path partition, one pass a launch between two buffers), no atomics, ONE
+ *              permutation whatever the scheduling --, k_load_dups and k_load_dup_tags on the sorted neighbours, ONE wait for 16 bytes of status, then
+ *              k_load_records (every record of the table, at any byte alignment and stride), k_sha256_records and the depth launches of k_merkle_level.
+ *              Scratch: two buffers of nk (ceil(key_bytes / 4) + 1) words in the context's growable scratch.  Queued on the context's stream behind whatever
+ *              produced d_keys there.
+ * MFH_EINVAL with the function's name in mfh_last_error, nothing launched and nothing written: a null tree; a tree of another device; nk > 2^depth - 1;
+ * key_bytes 0 or above 32; length < 2 key_bytes + payload_bytes or > 2^20; table_stride < length; d_table null; d_keys null with nk > 0; d_payloads given
+ * with payload_bytes = 0; h_status null.
+ * Kernel timing kinds: "merkle_sort" (1 + the merge passes; rows = nk each), "merkle_load" (3 in front of the wait, none for nk = 0, and the build launch,
+ * rows = 2^depth), then "sha256_records" (1) and "merkle_level" (depth). */
+int mfh_merkle_load_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t nk,
+                         const uint8_t *d_keys, const uint8_t *d_payloads, uint32_t payload_bytes, uint32_t h_status[3]);
+/* CHECK the invariant every key statement is sound relative to: the live records (lo < hi) of the 2^depth records at d_table tile the key space in ONE chain
+ * from 00..00 to FF..FF, the tree's leaves are the records' SHA-256 and every node is the compression of its children.  Only reads table and tree.
+ * h_out = {status, live, where0, where1}, live = the number of live records:
+ *   0  all good
+ *   1  the chain: with the live records sorted by (lo, slot), where0 = the slot of the first record at which it breaks -- sorted record 0 when its lo is not
+ *      00..00, sorted record i + 1 at the lowest i with hi_i != lo_i+1, the last record when its hi is not FF..FF --, 0xFFFFFFFF when no record is live
+ *   2  the leaves (the chain is good): where0 = the lowest slot whose record does not hash to its leaf, inert slots included
+ *   3  the nodes (chain and leaves are good): where0 = the lowest level with a wrong node, the leaves' parents being level 1, where1 = the lowest index there
+ *   how        k_range_flags (bounds 00..00 and FF..FF), k_inert_scan, k_inert_select, k_range_keys with max_links = 2^depth; one wait for the count; then
+ *              k_check_entries, key_sort of (lo, rank in table order), k_chain_check, k_sha256_records into scratch, k_leaf_check and one k_node_check a
+ *              level, all queued whatever the chain says, and ONE wait for 32 bytes of results.  Scratch: the range reads' with max_links = 2^depth, the
+ *              sort's two buffers and 32 bytes a slot of digests.
+ * MFH_EINVAL as above: a null tree; a tree of another device; key_bytes 0 or above 32; length < 2 key_bytes or > 2^20; table_stride < length; d_table or
+ * h_out null.
+ * Kernel timing kinds: "merkle_check" (4, and with a live record 3 + depth more), "merkle_sort" (as above, n = live), "sha256_records" (1). */
+int mfh_merkle_check_table(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes,
+                           uint32_t h_out[4]);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
