@@ -105,7 +105,7 @@ EXPORTS = [
     "mfh_merkle_absent_rows", "mfh_merkle_insert_keys", "mfh_merkle_update_rows_cut", "mfh_merkle_update_records_cut", "mfh_merkle_insert_keys_cut",
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
     "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
-    "mfh_merkle_load_keys", "mfh_merkle_check_table",
+    "mfh_merkle_load_keys", "mfh_merkle_check_table", "mfh_merkle_grow", "mfh_merkle_grow_leaves",
 ]
 
 
@@ -277,6 +277,8 @@ def load_library():
         "mfh_merkle_range_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]),
         "mfh_merkle_load_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, vp, u32, vp]),
         "mfh_merkle_check_table": (i32, [vp, vp, vp, sz, u32, u32, vp]),
+        "mfh_merkle_grow": (i32, [vp, vp, u32, vp, sz, u32, vp, sz, vp, vp]),
+        "mfh_merkle_grow_leaves": (i32, [vp, vp, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
@@ -1176,6 +1178,55 @@ class MerkleTree:
         self._keep = []
         st = int(out[0])
         return st, int(out[1]), (None if st == 0 else (int(out[2]), int(out[3])) if st == 3 else int(out[2]))
+
+    def grow(self, new_depth, table=None, length=None, out=None, roots=False):
+        """a NEW MerkleTree of new_depth > depth whose leftmost subtree is this tree and whose other leaves are all inert, and with `table` the grown table
+        (mfh_merkle_grow, mfh_merkle_grow_leaves: copies, constants and new_depth - depth compressions -- no record is hashed and no level rebuilt).  This
+        tree and `table` are only read and stay valid.  The new root is words.grown_root(root, depth, new_depth, length): a public function of the old one.
+        table: the table of this tree under update_records' rules; the result is then (tree, new_table), new_table a uint8 [2^new_depth, length] tensor
+        holding words.indexed_grow(table, new_depth): the old records, then all-zero (inert) ones.  out: that tensor preallocated, uint8 [2^new_depth, >=
+        length] under the same rules (a wider stride, a column slice of a wider table; bytes behind `length` stay as they were); it must not overlap
+        `table`.  Without `out` a contiguous one is allocated.
+        table=None, length=L: the tree of L-byte records alone, for a table kept elsewhere.  Neither: a tree of leaves (set_leaves; the inert leaf is 32
+        zero bytes).  roots=True appends (R, R'), the old and the new root as bytes, to the result, and waits for the stream once; without it the call only
+        queues work on the context's stream."""
+        c = self._ctx
+        who = "grow"
+        if not isinstance(new_depth, (int, np.integer)):
+            raise MfhError(f"{who}: new_depth is an integer")
+        new_depth = int(new_depth)
+        h = ctypes.c_void_p()
+        r = (ctypes.c_uint8 * 64)() if roots else None
+        new = None
+        if table is None and length is None:
+            if out is not None:
+                raise MfhError(f"{who}: out goes with a table")
+            c._chk(c.lib.mfh_merkle_grow_leaves(c._h, self._h, new_depth, ctypes.byref(h), r))
+        elif table is None:
+            if out is not None:
+                raise MfhError(f"{who}: out goes with a table")
+            if not isinstance(length, (int, np.integer)) or length < 0:
+                raise MfhError(f"{who}: length is the records' length in bytes")
+            c._chk(c.lib.mfh_merkle_grow(c._h, self._h, new_depth, None, 0, int(length), None, 0, ctypes.byref(h), r))
+        else:
+            tab, tstride, tlength = self._table(table, who)
+            if length is not None and length != tlength:
+                raise MfhError(f"{who}: length is the table's")
+            if not self.depth < new_depth <= 24:
+                raise MfhError(f"{who}: new_depth must be above the tree's depth and at most 24")
+            if out is None:
+                new, nstride = c.empty((tlength << new_depth)).reshape(1 << new_depth, tlength), tlength
+            else:
+                wide, nstride, olength, nrec, _ = _records(c, out, who) if isinstance(out, c.torch.Tensor) else (None, 0, 0, 0, False)
+                if wide is None or nrec != 1 << new_depth or olength < tlength:
+                    raise MfhError(f"{who}: out is a torch uint8 [2^new_depth, >= length] tensor on the context's device")
+                new = wide[:, :tlength]
+            c._chk(c.lib.mfh_merkle_grow(c._h, self._h, new_depth, _ptr(tab), tstride, tlength, _ptr(new), nstride, ctypes.byref(h), r))
+        if roots:
+            self._keep = []  # (the call waited for the stream)
+        tree = MerkleTree(c, new_depth, h)
+        res = (tree,) + ((new,) if table is not None else ()) + (((bytes(r[:32]), bytes(r[32:])),) if roots else ())
+        return res[0] if len(res) == 1 else res
 
 
 class Context:

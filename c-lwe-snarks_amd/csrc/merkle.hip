@@ -40,6 +40,8 @@
 // k_sort_tiles, k_sort_merge: key_sort, the device sort of multi-word keys with a tag (tiles in LDS, then merge passes over a merge-path partition:
 // merkle_sort.hpp).  k_load_entries, k_load_dups, k_load_dup_tags, k_load_records: mfh_merkle_load_keys, a whole indexed table and its tree out of a key set on
 // the device.  k_check_entries, k_chain_check, k_leaf_check, k_node_check: mfh_merkle_check_table, the table's invariant and the tree over it, read only.
+// k_grow_nodes, k_grow_spine, k_grow_table: mfh_merkle_grow, a tree and its table as the leftmost part of a deeper tree and a larger table whose new slots are
+// inert -- copies, constants and new_depth - depth compressions, no record hashed (merkle_grow.hpp).
 // The one layout of all these rows, their sizes and the host's splice of staged rows and gathered records: merkle_rows.hpp.
 #include <algorithm>
 #include <functional>
@@ -50,6 +52,7 @@
 
 #include "ctx.hpp"
 #include "merkle_adjust.hpp"
+#include "merkle_grow.hpp"
 #include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
 #include "merkle_range.hpp"
@@ -1146,6 +1149,91 @@ __global__ __launch_bounds__(256) void k_balance_fold(const unsigned long long *
   }
 }
 
+// ---- mfh_merkle_grow: a tree of depth d and its table become the leftmost subtree and the first 2^d records of a tree of depth D and its table, every new
+// slot inert (merkle_grow.hpp has the placement and the constants E_l, computed by the host and handed over as a kernel argument).  Three kernels, no
+// atomics, no LDS, no record hashed:
+//   k_grow_nodes  ONE launch over the whole memory of the new tree, one 16-byte unit (half a node) a lane: mf::grow_node of the unit's position says whether
+//                 it is a copy of an old node (one 16-byte load, one 16-byte store), the constant E_l (a store) or left alone (the spine: k_grow_spine's; the
+//                 unused position 0: a memset).  Consecutive lanes take consecutive units and, inside a level's copied part, consecutive units of the old
+//                 tree.  Reads: old units [2, 4 << d) only.  Writes: units below 4 << D only.  Streaming: 64 (2^d + 2^D) bytes of HBM traffic.
+//   k_grow_spine  one thread: S_d = the old root, S_l+1 = compress(IV, S_l || E_l) for d <= l < D, stored at position 2^(D - l - 1).  It reads the OLD tree and
+//                 E alone, so it does not depend on k_grow_nodes, and no position is written by both.  D - d dependent compressions: latency, not bandwidth.
+//   k_grow_table  one item per ROW r < rows and 16-byte window of the DESTINATION's dword grid, k_record_store's items: bytes [0, copy_length) of row r <-
+//                 those of the source's row r (through load_unit_within: any alignment and stride on either side) for r < old_rows, every other byte of
+//                 [0, length) <- zero.  A window inside its row is ONE 16-byte store at a 4-byte aligned address; one across the row's head or tail is
+//                 k_record_store's dword and byte stores.  The host picks the rows (merkle_grow, below): a row is a record (rows = 2^D, old_rows = 2^d,
+//                 copy_length = length), or, where both tables are packed (stride = length), the WHOLE table is one row of 2^D length bytes whose first 2^d
+//                 length are copied -- no window then straddles two records and all but two stores are whole.
+//                 Reads: nothing outside [src, src + src_span), src_span = (2^d - 1) src_stride + the records' length.  Writes: bytes [0, length) of every
+//                 row and nothing else -- no gap byte of a wider stride, nothing before the table or behind its last record.
+__global__ __launch_bounds__(256) void k_grow_nodes(const uint4 *__restrict__ from, uint4 *__restrict__ nodes, uint32_t depth, uint32_t new_depth,
+                                                    const mf::GrowRoots roots) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;  // (at most 4 << 24 units)
+  if (g >= mf::grow_units(new_depth)) return;
+  const uint32_t half = g & 1;
+  const mf::GrowNode n = mf::grow_node(depth, new_depth, g >> 1);
+  if (n.kind == mf::kGrowCopy) {
+    nodes[g] = from[2 * (size_t)n.from + half];
+  } else if (n.kind == mf::kGrowInert) {
+    const uint32_t *e = roots.w + 8 * n.level + 4 * half;
+    nodes[g] = make_uint4(e[0], e[1], e[2], e[3]);
+  }
+}
+
+__global__ void k_grow_spine(const uint4 *__restrict__ from, uint4 *__restrict__ nodes, uint32_t depth, uint32_t new_depth, const mf::GrowRoots roots) {
+  if (threadIdx.x || blockIdx.x) return;
+  const uint4 r0 = bswap4(from[2]), r1 = bswap4(from[3]);  // the old root: position 1
+  uint32_t cur[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+  for (uint32_t l = depth; l < new_depth; l++) {
+    uint32_t w[16], h[8] = MF_SHA256_IV;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      w[j] = cur[j];
+      w[8 + j] = __builtin_bswap32(roots.w[8 * l + j]);
+    }
+    mf::sha256_compress(h, w);
+#pragma unroll
+    for (int j = 0; j < 8; j++) cur[j] = h[j];
+    const size_t k = (size_t)1 << (new_depth - l - 1);  // node 0 of level l + 1
+    nodes[2 * k] = bswap4(make_uint4(h[0], h[1], h[2], h[3]));
+    nodes[2 * k + 1] = bswap4(make_uint4(h[4], h[5], h[6], h[7]));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_grow_table(uint8_t *__restrict__ table, size_t table_stride, const uint8_t *__restrict__ src, size_t src_stride,
+                                                    int64_t src_span, uint32_t length, uint32_t copy_length, uint32_t old_rows, uint32_t rows) {
+  const uint32_t units = (length + 18) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (rows * units < 2^32: checked by the host, so the division is a 32-bit one)
+  if (g >= rows * units) return;
+  const uint32_t r = g / units, u = g - r * units;
+  uint8_t *dst = table + (size_t)r * table_stride;
+  const int64_t s = (int64_t)16 * u - (int64_t)(reinterpret_cast<uintptr_t>(dst) & 3);  // the window's first byte, as an offset in the row
+  const int64_t hi = min(s + 16, (int64_t)length);
+  if (hi <= max(s, (int64_t)0)) return;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (r < old_rows && s < (int64_t)copy_length) {
+    const int64_t a = (int64_t)((size_t)r * src_stride);
+    v = load_unit_within(src, a + s, a + min(hi, (int64_t)copy_length), src_span);
+    // (a window across the end of the copied part: its bytes behind are zero.  Window and range go to merge_unit moved up by 4, as in k_load_records)
+    if (hi > (int64_t)copy_length) v = merge_unit(make_uint4(0, 0, 0, 0), v, s + 4, 4, (int64_t)copy_length + 4);
+  }
+  if (s >= 0 && s + 16 <= (int64_t)length) {  // the window lies inside the row, as all but its first and last do: ONE 16-byte store at a 4-byte aligned address
+    __builtin_memcpy(__builtin_assume_aligned(dst + s, 4), &v, 16);
+    return;
+  }
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int64_t o = s + 4 * j;
+    if (o >= 0 && o + 4 <= (int64_t)length) {
+      *reinterpret_cast<uint32_t *>(dst + o) = w[j];
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+        if (o + b >= 0 && o + b < (int64_t)length) dst[o + b] = (uint8_t)(w[j] >> (8 * b));
+    }
+  }
+}
+
 }  // namespace
 
 struct mfh_merkle {
@@ -1168,6 +1256,23 @@ int tree_refused(mfh_ctx *c, const mfh_merkle *t, const char *who) {
   if (!c) return MFH_EINVAL;
   if (!t) return fail(c, who, "the tree is null");
   if (t->device != c->device) return fail(c, who, "the tree belongs to another device");
+  return MFH_OK;
+}
+
+// a tree of `depth` on the context's device (set by the caller) whose 2^(depth + 1) nodes are allocated and NOT written: nothing is queued, nothing waited
+// for.  mfh_merkle_create fills them with the tree of zero leaves, mfh_merkle_grow with the grown tree.  MFH_ENOMEM with `who`'s text
+int tree_alloc(mfh_ctx *c, uint32_t depth, const char *who, mfh_merkle **out) {
+  mfh_merkle *t = new mfh_merkle();
+  t->owner = c;
+  t->device = c->device;
+  t->depth = depth;
+  if (hipMalloc(&t->mem, (size_t)64 << depth) != hipSuccess) {
+    (void)hipGetLastError();
+    delete t;
+    c->err = std::string(who) + ": no memory for the nodes";
+    return MFH_ENOMEM;
+  }
+  *out = t;
   return MFH_OK;
 }
 
@@ -1483,17 +1588,9 @@ int mfh_merkle_create(mfh_ctx *c, uint32_t depth, mfh_merkle **out) {
   if (!out) return fail(c, "mfh_merkle_create", "out is null");
   if (depth < 1 || depth > kMaxDepth) return fail(c, "mfh_merkle_create", "depth must be in [1, 24]");
   HIP_TRY(c, hipSetDevice(c->device));
-  mfh_merkle *t = new mfh_merkle();
-  t->owner = c;
-  t->device = c->device;
-  t->depth = depth;
+  mfh_merkle *t = nullptr;
+  if (int rc = tree_alloc(c, depth, "mfh_merkle_create", &t)) return rc;
   const size_t bytes = (size_t)64 << depth;
-  if (hipMalloc(&t->mem, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    delete t;
-    c->err = "mfh_merkle_create: no memory for the nodes";
-    return MFH_ENOMEM;
-  }
   // all-zero leaves with every level computed: every later state is well defined
   int rc = hipMemsetAsync(t->mem, 0, bytes, c->stream) == hipSuccess ? merkle_update(c, t, 0, 1u << depth) : MFH_EDEVICE;
   if (rc == MFH_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = MFH_EDEVICE;
@@ -2762,6 +2859,104 @@ int mfh_merkle_check_table(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
     h_out[0] = 0;
   }
   return MFH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- mfh_merkle_grow, mfh_merkle_grow_leaves: one driver (k_grow_nodes has the kernels, merkle_grow.hpp the placement and the constants)
+static_assert(mf::kGrowMaxDepth == kMaxDepth, "the constants E_l of a growth reach the deepest tree");
+
+// records: E_0 = SHA-256 of `length` zero bytes and the tables (both or neither); else E_0 = 32 zero bytes and no table.  Queue-only without h_roots
+int merkle_grow(mfh_ctx *c, const mfh_merkle *t, uint32_t new_depth, const char *who, bool records, const uint8_t *d_table, size_t table_stride, uint32_t length,
+                uint8_t *d_new_table, size_t new_stride, mfh_merkle **out, uint8_t *h_roots) {
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!out) return fail(c, who, "out is null");
+  const uint32_t depth = t->depth;
+  if (new_depth <= depth || new_depth > kMaxDepth) return fail(c, who, "new_depth must be above the tree's depth and at most 24");
+  const uint32_t old_records = 1u << depth, new_records = 1u << new_depth;
+  const bool tables = d_table || d_new_table;
+  // k_grow_table's rows, set behind the refusals: the records, or -- both tables packed and the whole new table below 2^32 bytes -- ONE row, the table
+  uint32_t rows = new_records, old_rows = old_records, row_length = length, copy_length = length;
+  int64_t old_span = 0;
+  if (records) {
+    if (length > kMaxRecordLength) return fail(c, who, "length above 2^20 bytes");
+    if (!d_table != !d_new_table) return fail(c, who, "d_table and d_new_table are given together, or neither");
+    if (tables) {
+      if (table_stride < length) return fail(c, who, "table_stride shorter than length");
+      if (new_stride < length) return fail(c, who, "new_stride shorter than length");
+      if (length && table_stride == length && new_stride == length && !(((uint64_t)new_records * length + 18) >> 32)) {
+        rows = old_rows = 1;
+        row_length = new_records * length;
+        copy_length = old_records * length;
+      }
+      if ((uint64_t)rows * ((row_length + 18) / 16) >> 32) return fail(c, who, "the new table's records exceed 2^32 units of 16 bytes");
+      old_span = (int64_t)(((size_t)old_records - 1) * table_stride + length);
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_table), b0 = reinterpret_cast<uintptr_t>(d_new_table);
+      const uintptr_t a1 = a0 + (uintptr_t)old_span, b1 = b0 + ((size_t)new_records - 1) * new_stride + length;
+      if (a0 < b1 && b0 < a1) return fail(c, who, "the new table overlaps the old one");
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  mf::GrowRoots roots;
+  mf::grow_inert_roots(records, length, new_depth, roots);  // (host: microseconds; the kernels take them as an argument, no copy and no wait)
+  const uint32_t units = (row_length + 18) / 16;  // (of a row of k_grow_table)
+  mfh_merkle *g = nullptr;
+  if (int rc = tree_alloc(c, new_depth, who, &g)) return rc;
+  auto queue = [&]() -> int {
+    HIP_TRY(c, hipMemsetAsync(g->mem, 0, 32, c->stream));  // the unused position 0
+    const uint4 *from = reinterpret_cast<const uint4 *>(t->mem);
+    uint4 *nodes = reinterpret_cast<uint4 *>(g->mem);
+    {
+      Timer tm(c, 47, (uint64_t)2 << new_depth);  // "merkle_grow" (mfhip.hip: timing_kind): every node off the spine ...
+      hipLaunchKernelGGL(k_grow_nodes, dim3((mf::grow_units(new_depth) + 255) / 256), dim3(256), 0, c->stream, from, nodes, depth, new_depth, roots);
+    }
+    {
+      Timer tm(c, 47, new_depth - depth);  // ... the spine ...
+      hipLaunchKernelGGL(k_grow_spine, dim3(1), dim3(64), 0, c->stream, from, nodes, depth, new_depth, roots);
+    }
+    if (tables) {
+      Timer tm(c, 47, new_records);  // ... and the table
+      hipLaunchKernelGGL(k_grow_table, dim3((uint32_t)(((uint64_t)rows * units + 255) / 256)), dim3(256), 0, c->stream, d_new_table, new_stride, d_table,
+                         table_stride, old_span, row_length, copy_length, old_rows, rows);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (h_roots) {
+      uint8_t *pin = (uint8_t *)pin_acquire(c, c->pin_cw, 64);
+      if (!pin) {
+        c->err = std::string(who) + ": no pinned memory for the roots";
+        return MFH_ENOMEM;
+      }
+      HIP_TRY(c, hipMemcpyAsync(pin, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(pin + 32, g->level(new_depth), 32, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      memcpy(h_roots, pin, 64);
+    }
+    return MFH_OK;
+  };
+  if (int rc = queue()) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);  // (a launch of this call may be in flight on the nodes)
+    hipFree(g->mem);
+    delete g;
+    return rc;
+  }
+  *out = g;
+  return MFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfh_merkle_grow(mfh_ctx *c, const mfh_merkle *t, uint32_t new_depth, const uint8_t *d_table, size_t table_stride, uint32_t length, uint8_t *d_new_table,
+                    size_t new_stride, mfh_merkle **out, uint8_t *h_roots) {
+  return merkle_grow(c, t, new_depth, "mfh_merkle_grow", true, d_table, table_stride, length, d_new_table, new_stride, out, h_roots);
+}
+
+int mfh_merkle_grow_leaves(mfh_ctx *c, const mfh_merkle *t, uint32_t new_depth, mfh_merkle **out, uint8_t *h_roots) {
+  return merkle_grow(c, t, new_depth, "mfh_merkle_grow_leaves", false, nullptr, 0, 0, nullptr, 0, out, h_roots);
 }
 
 }  // extern "C"

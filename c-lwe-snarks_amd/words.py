@@ -1658,6 +1658,71 @@ def indexed_check(table, key_bytes: int):
     return 0, n, None
 
 
+def merkle_node(left: bytes, right: bytes) -> bytes:
+    """MerklePath's node function on the host: compress(IV, left || right), ONE SHA-256 compression of the 64 bytes with no padding block (FIPS 180-4 6.2.2;
+    hashlib does not expose it).  What a verifier needs to evaluate grown_root."""
+    left, right = bytes(left), bytes(right)
+    if len(left) != 32 or len(right) != 32:
+        raise CircuitError("merkle_node: two nodes of 32 bytes")
+    rotr = lambda x, n: (x >> n | x << (32 - n)) & MASK
+    w = [int.from_bytes((left + right)[4 * t: 4 * t + 4], "big") for t in range(16)]
+    for t in range(16, 64):
+        s0 = rotr(w[t - 15], 7) ^ rotr(w[t - 15], 18) ^ w[t - 15] >> 3
+        s1 = rotr(w[t - 2], 17) ^ rotr(w[t - 2], 19) ^ w[t - 2] >> 10
+        w.append((w[t - 16] + s0 + w[t - 7] + s1) & MASK)
+    a, b, c, d, e, f, g, h = SHA256_IV
+    for t in range(64):
+        t1 = (h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + (e & f ^ ~e & g & MASK) + SHA256_K[t] + w[t]) & MASK
+        t2 = ((rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + (a & b ^ a & c ^ b & c)) & MASK
+        a, b, c, d, e, f, g, h = (t1 + t2) & MASK, a, b, c, (d + t1) & MASK, e, f, g
+    return b"".join(((x + y) & MASK).to_bytes(4, "big") for x, y in zip(SHA256_IV, (a, b, c, d, e, f, g, h)))
+
+
+GROW_MAX_DEPTH = 24  # the deepest tree (mfh_merkle_create)
+
+
+def inert_roots(depth: int, length=None):
+    """[E_0 .. E_depth], 32 bytes each: the root E_l of a subtree of height l whose leaves are all inert, E_l+1 = merkle_node(E_l, E_l).  With a `length`
+    E_0 = SHA-256 of `length` zero bytes, the leaf of an all-zero record (lo >= hi: an inert slot of an indexed table); with length=None E_0 is 32 zero
+    bytes, the leaf of a fresh tree of leaves, whose root at depth D is inert_roots(D)[-1].  CircuitError unless 0 <= depth <= 24 and 0 <= length <= 2^20."""
+    if not isinstance(depth, (int, np.integer)) or not 0 <= depth <= GROW_MAX_DEPTH:
+        raise CircuitError("inert_roots: a depth in [0, 24]")
+    if length is not None and (not isinstance(length, (int, np.integer)) or not 0 <= length <= 1 << 20):
+        raise CircuitError("inert_roots: a length in [0, 2^20], or None for a tree of leaves")
+    e = [bytes(32) if length is None else hashlib.sha256(bytes(int(length))).digest()]
+    for _ in range(int(depth)):
+        e.append(merkle_node(e[-1], e[-1]))
+    return e
+
+
+def grown_root(root: bytes, depth: int, new_depth: int, length=None) -> bytes:
+    """the root R' of the tree of `new_depth` whose leftmost subtree of height `depth` has the root R = `root` and whose other leaves are all inert (what
+    MerkleTree.grow makes): S_depth = R, S_l+1 = merkle_node(S_l, E_l) with E = inert_roots(.., length), R' = S_new_depth.  new_depth - depth compressions of
+    public values: a verifier who follows a chain of roots evaluates this to accept the jump R -> R'; there is nothing to prove.  Growing depth -> m -> new_depth
+    gives what depth -> new_depth gives.  CircuitError unless 1 <= depth < new_depth <= 24 and the root is 32 bytes."""
+    if not all(isinstance(x, (int, np.integer)) for x in (depth, new_depth)) or not 1 <= depth < new_depth <= GROW_MAX_DEPTH:
+        raise CircuitError("grown_root: 1 <= depth < new_depth <= 24")
+    if not isinstance(root, (bytes, bytearray, memoryview, np.ndarray)) or len(bytes(root)) != 32:
+        raise CircuitError("grown_root: the root is 32 bytes")
+    e = inert_roots(int(new_depth) - 1, length)
+    s = bytes(root)
+    for l in range(int(depth), int(new_depth)):
+        s = merkle_node(s, e[l])
+    return s
+
+
+def indexed_grow(table, new_depth: int):
+    """np.uint8 [2^new_depth, length]: the host table (a uint8 array [2^depth, length]) with all-zero rows appended -- inert slots (lo >= hi), so
+    indexed_check gives the grown table the answer it gave the original.  The model of the table MerkleTree.grow writes.  CircuitError unless the table has
+    2^depth rows, depth >= 1, and depth < new_depth <= 24."""
+    if not isinstance(table, np.ndarray) or table.dtype != np.uint8 or table.ndim != 2 or len(table) < 2 or len(table) & (len(table) - 1):
+        raise CircuitError("indexed_grow: a uint8 table [2^depth, length], depth >= 1")
+    depth = len(table).bit_length() - 1
+    if not isinstance(new_depth, (int, np.integer)) or not depth < new_depth <= GROW_MAX_DEPTH:
+        raise CircuitError("indexed_grow: depth < new_depth <= 24")
+    return np.concatenate([table, np.zeros(((1 << int(new_depth)) - len(table), table.shape[1]), dtype=np.uint8)])
+
+
 # (wires, rows) of Sha256Message by length in bytes, as compile counts them; 0 .. 55 bytes are one block and fit Params(d=1 << 16, m=43690) and the LDS
 # witness kernel, 56 .. 119 are two blocks and fit Params(d=1 << 17, m=87381).  A constant zero bit of the padding is left out of the sums it would enter
 # (Words.sum), which can shorten a weighted-sum gate: an all-padding block costs a few wires less than a block of message bits.

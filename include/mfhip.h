@@ -749,6 +749,31 @@ int mfh_merkle_load_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t t
  * Kernel timing kinds: "merkle_check" (4, and with a live record 3 + depth more), "merkle_sort" (as above, n = live), "sha256_records" (1). */
 int mfh_merkle_check_table(mfh_ctx *ctx, const mfh_merkle *t, const uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes,
                            uint32_t h_out[4]);
+/* GROW a tree and its table: *out <- a NEW tree of new_depth > depth whose leftmost subtree of height depth is t and whose other leaves are all the inert
+ * leaf E_0 = SHA-256 of `length` zero bytes; records [0, 2^depth) of d_new_table <- those of d_table and records [2^depth, 2^new_depth) <- all zero (bytes
+ * [0, length) of each; bytes [length, new_stride) and everything outside the new table's span are left as they were).  An all-zero record has lo >= hi: the
+ * new slots are inert, the grown pair has the invariant of mfh_merkle_check_table exactly when the old pair had it, and every key call and cut call runs on
+ * it unchanged.  No record is hashed: with E_l+1 = node(E_l, E_l), the root of every subtree of height l right of the old tree is the constant E_l, and the
+ * nodes above the old root R are S_depth = R, S_l+1 = node(S_l, E_l) -- the new root R' = S_new_depth is new_depth - depth compressions of PUBLIC values, which
+ * a verifier following a chain of roots evaluates himself (words.grown_root): the jump R -> R' needs no proof.
+ * t and d_table are only read and stay valid and unchanged; *out is destroyed by mfh_merkle_destroy like a created tree.
+ * d_table and d_new_table may BOTH be NULL: the tree alone is grown, for a table kept elsewhere (the strides are then unused).
+ * h_roots: NULL, or 64 bytes <- R | R'.  With NULL the call is queue-only on the context's stream and does not wait; with h_roots it waits once.
+ *   how        the host computes E_0 .. E_new_depth (csrc/merkle_grow.hpp: microseconds) and hands them to the kernels as an argument; the nodes are
+ *              allocated and NOT built as a zero tree first; k_grow_nodes (one launch over the whole memory of the new tree, a 16-byte unit a lane: a copy of
+ *              an old node or a constant), k_grow_spine (one thread: the new_depth - depth nodes above the old root, from the old tree and the constants
+ *              alone) and k_grow_table (16-byte windows of the destination's dword grid: any byte alignment and stride on either side); no atomics, no LDS,
+ *              no scratch.
+ * MFH_EINVAL with the function's name in mfh_last_error, nothing queued and *out untouched: a null tree; a tree of another device; out null; new_depth <=
+ * depth or > 24; length > 2^20; table_stride or new_stride < length; one of d_table, d_new_table without the other; a new table whose span [d_new_table,
+ * d_new_table + (2^new_depth - 1) new_stride + length) overlaps the old table's; 2^new_depth ceil((length + 3) / 16) >= 2^32.  MFH_ENOMEM: no memory for the
+ * nodes.
+ * Kernel timing kind: "merkle_grow" (3 per call with the tables, 2 without; rows = the 2^(new_depth + 1) nodes, the new_depth - depth spine nodes, the
+ * 2^new_depth records); no "sha256_records" and no "merkle_level" launch. */
+int mfh_merkle_grow(mfh_ctx *ctx, const mfh_merkle *t, uint32_t new_depth, const uint8_t *d_table, size_t table_stride, uint32_t length,
+                    uint8_t *d_new_table, size_t new_stride, mfh_merkle **out, uint8_t *h_roots);
+/* ... the same for a tree of LEAVES (mfh_merkle_set_leaves): E_0 = 32 zero bytes, the leaf of mfh_merkle_create, whose fresh root of depth D is E_D. */
+int mfh_merkle_grow_leaves(mfh_ctx *ctx, const mfh_merkle *t, uint32_t new_depth, mfh_merkle **out, uint8_t *h_roots);
 
 /* ---- L3/L4: polynomial step, setup, prover ------------------------------------------------------------ */
 /* c = a*b over F_p[x] (la+lb-1 canonical coefficients).  What nmod_poly_mul/pow compute (src/snark.c:167).
