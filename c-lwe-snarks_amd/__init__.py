@@ -90,7 +90,7 @@ EXPORTS = [
     "mfh_encrypt_rows", "mfh_decrypt", "mfh_ct_smudge", "mfh_ssp_upload", "mfh_witness_poly", "mfh_version",
     "mfh_workspace_bytes", "mfh_last_kernel_ms", "mfh_set_timing", "mfh_set_overlap", "mfh_eval_rows_multi", "mfh_prove_batch", "mfh_crs_mm_image_bytes", "mfh_crs_expand_mm", "mfh_crs_set_resident_mm", "mfh_witness_poly_multi", "mfh_witness_poly_mm", "mfh_poly_h_multi", "mfh_poly_mul", "mfh_poly_add", "mfh_poly_prepare_t",
     "mfh_ssp_prepare", "mfh_poly_h", "mfh_setup_messages", "mfh_setup", "mfh_setup_image", "mfh_crs_image_set_b", "mfh_prove",
-    "mfh_prove_partial", "mfh_prove_finish", "mfh_ct_to_lanes", "mfh_ct_from_lanes", "mfh_lanes_per_value", "mfh_digest128", "mfh_timing_drain", "mfh_timing_busy_ms", "mfh_timing_work_rows", "mfh_set_batch_image", "mfh_set_batch_slabs", "mfh_set_expand_path", "mfh_set_expand_periods", "mfh_set_encrypt_path", "mfh_set_batch_launch", "mfh_set_batch_bw", "mfh_set_mm_chunk_rows", "mfh_set_mm_pack", "mfh_set_poly_exact", "mfh_poly_exact_fallbacks", "mfh_poly_exact_points", "mfh_set_poly_exact_points", "mfh_set_mm_stream", "mfh_add_dotp", "mfh_set_encrypt_chunks", "mfh_set_witness_per", "mfh_set_eval_path", "mfh_set_decrypt_path", "mfh_decrypt_rows",
+    "mfh_prove_partial", "mfh_prove_finish", "mfh_ct_to_lanes", "mfh_ct_from_lanes", "mfh_lanes_per_value", "mfh_digest128", "mfh_timing_drain", "mfh_timing_busy_ms", "mfh_timing_work_rows", "mfh_set_batch_image", "mfh_set_batch_slabs", "mfh_set_expand_path", "mfh_set_expand_periods", "mfh_set_encrypt_path", "mfh_set_batch_launch", "mfh_set_batch_bw", "mfh_set_batch_witness", "mfh_witness_poly_stream", "mfh_set_mm_chunk_rows", "mfh_set_mm_pack", "mfh_set_poly_exact", "mfh_poly_exact_fallbacks", "mfh_poly_exact_points", "mfh_set_poly_exact_points", "mfh_set_mm_stream", "mfh_add_dotp", "mfh_set_encrypt_chunks", "mfh_set_witness_per", "mfh_set_eval_path", "mfh_set_decrypt_path", "mfh_decrypt_rows",
     "mfh_crs_mm_share_bytes", "mfh_crs_expand_mm_share", "mfh_crs_set_resident_mm_share", "mfh_batch_chain", "mfh_batch_witness_cols", "mfh_batch_chain_from_w", "mfh_witness_poly_mm_cols", "mfh_prove_batch_partial", "mfh_prove_batch_finish",
     "mfh_resident_row_bytes", "mfh_crs_expand", "mfh_eval_rows_resident", "mfh_crs_set_resident",
     "mfh_witness_lanes", "mfh_witness_from_lanes", "mfh_prove_partial_w", "mfh_verify",
@@ -118,6 +118,9 @@ OPTIONAL_EXPORTS = {
     "mfh_mm_claim_log_launches": "test instrumentation of mfh_set_mm_queue",
     # test knob of the CRS expansion's launch plan: the image does not depend on it, and an older build picks the plan from the row count alone
     "mfh_set_expand_periods": "test knob; older builds pick the periods per chunk from the row count",
+    # the batch prover's streamed witness pass: the proofs do not depend on the route, and an older build runs k_witness_mm8q per super-group
+    "mfh_set_batch_witness": "tuning knob; older builds run the witness pass per super-group",
+    "mfh_witness_poly_stream": "the streamed pass alone (tests); older builds have mfh_witness_poly_mm only",
 }
 
 
@@ -159,6 +162,7 @@ def load_library():
         "mfh_poly_h_multi": (i32, [vp, vp, vp, u32]),
         "mfh_witness_poly_mm": (i32, [vp, vp, u32, ctypes.c_char_p, sz, vp, vp]),
         "mfh_witness_poly_multi": (i32, [vp, vp, u32, ctypes.c_char_p, sz, vp, vp]),
+        "mfh_witness_poly_stream": (i32, [vp, vp, u32, ctypes.c_char_p, sz, vp, vp]),
         "mfh_crs_mm_image_bytes": (sz, [vp]),
         "mfh_crs_expand_mm": (i32, [vp, vp, vp]),
         "mfh_crs_set_resident_mm": (i32, [vp, vp]),
@@ -215,6 +219,7 @@ def load_library():
         "mfh_set_mm_stream": (i32, [vp, i32, i32, i32, u32]),
         "mfh_set_batch_launch": (i32, [vp, u32, i32]),
         "mfh_set_batch_bw": (i32, [vp, i32]),
+        "mfh_set_batch_witness": (i32, [vp, i32]),
         "mfh_set_encrypt_path": (i32, [vp, i32]),
         "mfh_set_expand_path": (i32, [vp, i32]),
         "mfh_set_expand_periods": (i32, [vp, u32]),
@@ -1356,6 +1361,10 @@ class Context:
         """b_w of all super-groups of a call in one streaming launch per 8 of them (default) or one launch per super-group"""
         self._chk(self.lib.mfh_set_batch_bw(self._h, 1 if merged else 0))
 
+    def set_batch_witness(self, streamed=True):
+        """the witness pass of a streaming prove_batch call as one streaming launch over the SSP image (default) or k_witness_mm8q per super-group"""
+        self._chk(self.lib.mfh_set_batch_witness(self._h, 1 if streamed else 0))
+
     def set_mm_stream(self, map=0, persistent=False, sync_mode=0, spin_max=64):
         """layout of a streaming launch with several groups: slot map (0 | 1), persistent one-workgroup-per-CU grid, rendezvous of the sharers (0 | 1 | 2)"""
         self._chk(self.lib.mfh_set_mm_stream(self._h, int(map), int(persistent), int(sync_mode), int(spin_max)))
@@ -1713,14 +1722,15 @@ class Context:
         self._chk(self.lib.mfh_crs_set_resident_mm(self._h, _ptr(image)))
 
     def witness_poly_many(self, d_ssp, witness_bits_list, deltas, mm=True):
-        """w polynomials of up to 256 (mm) / 12 statements in one read of the SSP -> len x d uint32 on the device"""
+        """w polynomials of up to 256 (mm) / 12 statements in one read of the SSP, or of any number by the batch prover's streamed pass (mm="stream")
+        -> len x d uint32 on the device"""
         p = self.params
         nb = len(witness_bits_list)
         stride = (p.m + 6) // 8
         bits = b"".join(bytes(w[:stride]).ljust(stride, b"\0") for w in witness_bits_list)
         dl = (ctypes.c_uint32 * nb)(*[int(x) for x in deltas])
         out = self.empty(nb * p.d * 4)
-        fn = self.lib.mfh_witness_poly_mm if mm else self.lib.mfh_witness_poly_multi
+        fn = self.lib.mfh_witness_poly_stream if mm == "stream" else self.lib.mfh_witness_poly_mm if mm else self.lib.mfh_witness_poly_multi
         self._chk(fn(self._h, _ptr(d_ssp), nb, bits, stride, ctypes.cast(dl, ctypes.c_void_p), _ptr(out)))
         return out
 

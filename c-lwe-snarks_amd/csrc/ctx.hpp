@@ -95,6 +95,13 @@ struct mfh_ctx {
   size_t mm_base[3] = {0, 0, 0};
   DevBuf ssp_frag;  // the dense SSP in MFMA B-fragment order (witness.hip: witness pass of the batch prover); built lazily
   const uint32_t *ssp_frag_src = nullptr;  // the d_ssp it was built from; mfh_ssp_prepare / mfh_ssp_upload / mfh_ssp_from_rows reset it
+  // the dense SSP in MFMA A-fragment order, the layout k_mmstream reads (witness.hip: k_ssp_image; the batch prover's streamed witness pass); built lazily, and
+  // only when that route is taken.  ssp_img_src: the d_ssp it was built from, reset wherever ssp_frag_src is (ssp_images_stale)
+  DevBuf ssp_img;
+  const uint32_t *ssp_img_src = nullptr;
+  DevBuf wstream;  // mfh_prove_batch, streamed witness pass: b_w's digit fragments and partial products | the pass's partial products | W | V of every super-group
+  hipEvent_t ev_wstage = nullptr, ev_wdigits = nullptr;  // ... the host's inputs are staged / the digit fragments both launches read are built
+  int batch_witness = 1;  // mfh_prove_batch: the witness pass of a whole call as ONE streaming launch over the SSP image (mfh_set_batch_witness); 0: k_witness_mm8q per super-group
   SspInterp *interp = nullptr;  // mfh_ssp_from_rows (ssp_interp.hip): the seed table (d alone, built on first use) and per-call staging; t and the weights are rows_tree's
   DevBuf circ_io;  // mfh_circuit_assign (circuit_eval.hip): input rows | witness rows | holds of one chunk of statements; mfh_merkle_paths (merkle.hip): rows | indices of one chunk; mfh_merkle_update_rows: node values | rows | schedule of one chunk; mfh_merkle_absent_rows: query words | results, then path rows | heads | indices of one chunk; mfh_merkle_insert_keys: new records | plan | keys | payloads, then the search's and mfh_merkle_update_rows' scratch; mfh_merkle_remove_keys: new records | plan | keys, then the same
   DevBuf circ_state;  // mfh_circuit_assign of a mfh_circuit_create_global program: the wire words of one chunk, one column per 32 statements
@@ -157,6 +164,8 @@ struct mfh_ctx {
   bool resident_sharded = false;           // image holds only rank res_rank's shares: S share | AS share | BT+BV share
   uint32_t res_rank = 0, res_world = 1;
 };
+
+inline void ssp_images_stale(mfh_ctx *c) { c->ssp_frag_src = c->ssp_img_src = nullptr; }  // a (new) SSP is being registered: derived images are stale
 
 struct Timer {  // brackets one launch with events when timing is on; never synchronises
   mfh_ctx *c;
@@ -354,6 +363,8 @@ bool mm_image_covers(const mfh_ctx *c, uint64_t off, size_t nrows);
 // the phases of such a launch (evalmm.hip), for callers that queue them on different streams
 struct MmsPlan {
   uint32_t ng, ngt, ND, nrows, nchunks, rpc, rpad, ntiles, mtiles;
+  uint32_t ssp = 0;  // 1: the SSP geometry (mms_plan_ssp): img[0] is the SSP image, mtiles = 4 d / 16, packed one-byte records, no ciphertext epilogue (mms_witness_finish)
+  bool nolog = false;  // the launch stays out of the claim log (mfh_set_mm_claim_log): mfh_prove_batch's witness launch, so that a call's log lists its b_w / S / AS launches as before
   size_t cd_bytes, part_bytes;
   const uint8_t *img[2];
   int8_t *cd;
@@ -366,3 +377,14 @@ void mms_bind(MmsPlan &P, void *ws);              // the launch's digit fragment
 int mms_digits(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs);
 int mms_stream(mfh_ctx *c, const MmsPlan &P);
 int mms_finish(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs, int accumulate);
+// The second geometry: the witness pass of ng groups of up to 255 statements as one such launch over the SSP image (witness.hip: ssp_image) -- row r of the
+// K dimension is SSP slot r + 1, byte position 4 k + w is byte w of coefficient k -- with the digit fragments and column sums of b_w's launch over the same
+// statements (mms_digits with MmIo::bits: row 0 -> coefficient 0, row r -> bit r - 1, which is v_0 not selected and v_r selected by bit r - 1).
+bool mms_ssp_ok(const mfh_ctx *c);                // the packed one-byte records are what the launches write (mfh_set_mm_pack, mfh_set_mm_stream)
+bool mms_plan_ssp(mfh_ctx *c, const uint8_t *image, uint32_t ng, MmsPlan &P);  // row chunks as mms_plan cuts m rows: b_w's digit fragments fit
+// w_b[k] = (S mod p + delta_b t[k]) mod p for the statements of every group, from the packed records of all row chunks: d_delta[g] = the group's deltas on the
+// device, W[g] = its nvecs[g] x d coefficients; d_v0 != nullptr: v_b[k] = (w_b[k] + d_v0[k]) mod p as well, into V[g] (the chain's V step)
+int mms_witness_finish(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs, const uint32_t *d_t, const uint32_t *const *d_delta, uint32_t *const *W,
+                       const uint32_t *d_v0 = nullptr, uint32_t *const *V = nullptr);
+// witness.hip: the image of the dense SSP d_ssp, built on first use per SSP on c->stream (and awaited); nullptr when there is no room for it (no c->err)
+const uint8_t *ssp_image(mfh_ctx *c, const uint32_t *d_ssp);

@@ -1216,6 +1216,52 @@ __global__ __launch_bounds__(256) void k_evalmm_finish_groups(const int *__restr
                                   part + lender * part_stride, ND * A.nvec[lender]);
 }
 
+// The epilogue of the streamed witness pass (mms_plan_ssp): byte position 4 k + w of the SSP image is byte w of coefficient k, so the packed record (pk = 1) of byte-
+// position quad k and digit column b is T = sum_w G'[4 k + w][b] 2^(8 w) -- the integer sum_r bit_b[r] v_r[k] up to the corrections evalmm_finish_body<1, .., true>
+// applies per word: S = sum over the row chunks of (T + 128 T_ones) + (128 sc[b] + 16384 rows) 0x01010101, 0 <= S <= (m - 1)(2^32 - 1), and
+//     w_b[k] = (S mod p + delta_b t[k] mod p) mod p,
+// and with v0 the chain's V step on the way out: v_b[k] = (w_b[k] + v_0[k]) mod p (snark.hip: k_add_slot_multi, a pass over W and V per super-group otherwise).
+// blockIdx.x = 32 coefficients, blockIdx.y = group; thread = digit column (a record row of 2 KiB per coefficient is read by the 256 threads side by side), results
+// turned through LDS so that a statement's 32 coefficients are written as one 128-byte line.
+constexpr int WFK = 32;
+struct WfinArgs {  // per group of the launch
+  const int64_t *sc[16];
+  const uint32_t *delta[16];
+  uint32_t *w[16];
+  uint32_t *v[16];  // with v0
+  uint32_t nvec[16];
+};
+__global__ __launch_bounds__(N2) void k_witness_stream_finish(const long long *__restrict__ part, uint64_t part_stride /* records */, uint32_t nchunks, uint32_t nrows,
+                                                              uint32_t d, const uint32_t *__restrict__ t, const uint32_t *__restrict__ v0, WfinArgs A) {
+  __shared__ uint32_t tile[N2][WFK + 1];
+  const uint32_t g = blockIdx.y, b = threadIdx.x, k0 = blockIdx.x * WFK, nvec = A.nvec[g];
+  const long long *pg = part + g * part_stride;
+  if (b < nvec) {
+    const uint64_t corr = (uint64_t)(128 * A.sc[g][b] + 16384ll * nrows) * 0x01010101ull;  // (>= 0: sc >= -128 rows)
+    const uint64_t delta = A.delta[g][b], P = MFH_P;
+#pragma unroll 4
+    for (int kk = 0; kk < WFK; kk++) {
+      long long U = 0, SA = 0;
+      for (uint32_t ch = 0; ch < nchunks; ch++) {
+        const long long *row = pg + ((uint64_t)ch * d + k0 + kk) * N2;
+        U += row[b];
+        SA += row[nvec];  // the ones column
+      }
+      const uint64_t S = (uint64_t)(U + 128 * SA) + corr;
+      tile[b][kk] = (uint32_t)((S % P + (uint64_t)t[k0 + kk] * delta % P) % P);
+    }
+  }
+  __syncthreads();
+  uint32_t *wg = A.w[g], *vg = A.v[g];
+  const uint32_t v0k = v0 ? v0[k0 + threadIdx.x % WFK] : 0u;  // (N2 is a multiple of WFK: a thread keeps its coefficient through the loop)
+  for (uint32_t i = threadIdx.x; i < nvec * WFK; i += N2) {
+    const uint32_t w = tile[i / WFK][i % WFK];
+    const uint64_t at = (uint64_t)(i / WFK) * d + k0 + i % WFK;
+    wg[at] = w;
+    if (v0) vg[at] = (uint32_t)(((uint64_t)w + v0k) % MFH_P);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1437,7 +1483,8 @@ static unsigned long long *mms_stamps_next(uint32_t nd, uint32_t queue) {
 int mms_stream(mfh_ctx *c, const MmsPlan &P) {
   const uint32_t KS = (P.nrows + RT2 - 1) / RT2 * (RT2 / 64), tgs = (P.mtiles + TPW - 1) / TPW;
   const bool will_persist = mms_persistent(c, P);  // (the choice made below)
-  Timer t(c, P.ngt > 1 ? (P.ND == 1 ? 14 : 10) : 8, P.nrows, (uint64_t)P.nrows * P.ngt, will_persist ? 1 : 0);  // kind 10 ("mmstream_rounds"): several groups per launch; 14 ("mmstream_bw"): b_w of several super-groups
+  // kind 10 ("mmstream_rounds"): several groups per launch; 14 ("mmstream_bw"): b_w of several super-groups; 48 ("mmstream_witness"): the witness pass over the SSP image
+  Timer t(c, P.ssp ? 48 : P.ngt > 1 ? (P.ND == 1 ? 14 : 10) : 8, P.nrows, (uint64_t)P.nrows * P.ngt, will_persist ? 1 : 0);
   MmsImages imgs{};
   for (uint32_t g = 0; g < P.ngt; g++) imgs.image[g] = (const v4i *)P.img[g / P.ng];
   const uint32_t pk = mms_pk(c, P);  // (mms_finish reads what this launch writes: the same choice)
@@ -1468,7 +1515,7 @@ int mms_stream(mfh_ctx *c, const MmsPlan &P) {
       // one memset per launch, of what the launch itself uses: the rendezvous counters (speed only: a concurrent launch's memset costs polls, never an item) or its own queues'
       if (sync_mode) HIP_TRY(c, hipMemsetAsync(c->mm_sync, 0, 8 * 32 * sizeof(uint32_t), c->stream));
       else if (q.mode) HIP_TRY(c, hipMemsetAsync(qctr, 0, 8 * sizeof(uint32_t), c->stream));
-      if (c->mm_log) {  // (tests) this launch's section of the claim log and what the reader needs to index it
+      if (c->mm_log && !P.nolog) {  // (tests) this launch's section of the claim log and what the reader needs to index it
         const size_t need = (size_t)2 * P.nchunks * 8 * nblk * 32;
         if (c->mm_log_n == 16 || c->mm_log_used + need > c->mm_log_words) { c->err = "mfh_set_mm_claim_log: the log is too small for the call's launches"; return MFH_EINVAL; }
         q.log = c->mm_log + c->mm_log_used;
@@ -1517,6 +1564,50 @@ int mms_finish(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nv
   HIP_TRY(c, hipGetLastError());
   return MFH_OK;
 }
+// ---- the second geometry: the witness pass over the SSP image (ctx.hpp) ---------------------------------------------------------------------------------
+bool mms_ssp_ok(const mfh_ctx *c) { return c->mm_pack && !c->mm_wave1; }  // (mms_pk: what mms_witness_finish reads is what every launch shape then writes)
+bool mms_plan_ssp(mfh_ctx *c, const uint8_t *image, uint32_t ng, MmsPlan &P) {
+  if (!c || !image || !ng || ng > 16) return false;
+  const uint32_t d = c->P.d, m = c->P.m;
+  if (d % 64 || m < 2 || m > 0xffffffffu - 256 || !mms_ssp_ok(c)) return false;
+  P = MmsPlan{};
+  P.ssp = 1;
+  P.img[0] = image;
+  P.img[1] = nullptr;
+  P.ng = P.ngt = ng;
+  P.ND = 1;
+  P.nrows = m;
+  P.ntiles = 0;          // (no ciphertext epilogue)
+  P.mtiles = d / 4;      // 4 d byte positions in row tiles of 16: d / 64 tile groups, whole ones
+  // the row chunks of mms_plan for the same m rows, so that b_w's digit fragments serve this launch as they are
+  const uint32_t lim = std::max<uint32_t>(RT2, c->mm_chunk_rows / RT2 * RT2);
+  const uint32_t nchunks = (m + lim - 1) / lim;
+  P.rpc = ((m + nchunks - 1) / nchunks + RT2 - 1) / RT2 * RT2;
+  P.nchunks = (m + P.rpc - 1) / P.rpc;
+  P.rpad = P.nchunks * P.rpc;
+  P.cd_bytes = ((size_t)N2 * P.rpad + 255) & ~(size_t)255;
+  P.part_bytes = (size_t)P.nchunks * d * N2 * 8;  // one int64 record per (chunk, coefficient, digit column)
+  P.cd = nullptr;
+  P.part = nullptr;
+  return true;
+}
+int mms_witness_finish(mfh_ctx *c, const MmsPlan &P, const MmIo *ios, const uint32_t *nvecs, const uint32_t *d_t, const uint32_t *const *d_delta, uint32_t *const *W,
+                       const uint32_t *d_v0, uint32_t *const *V) {
+  if (!P.ssp || P.ngt > 16) return MFH_EINVAL;
+  WfinArgs A{};
+  for (uint32_t g = 0; g < P.ngt; g++) {
+    A.sc[g] = ios[g].sc_zeroed;
+    A.delta[g] = d_delta[g];
+    A.w[g] = W[g];
+    A.v[g] = d_v0 ? V[g] : nullptr;
+    A.nvec[g] = nvecs[g];
+  }
+  hipLaunchKernelGGL(k_witness_stream_finish, dim3(c->P.d / WFK, P.ngt), dim3(N2), 0, c->stream, (const long long *)P.part, (uint64_t)(P.part_bytes / 8), P.nchunks, P.nrows,
+                     c->P.d, d_t, d_v0, A);
+  HIP_TRY(c, hipGetLastError());
+  return MFH_OK;
+}
+
 int eval_rows_multi_io_regions(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, size_t nrows, const MmIo *ios, const uint32_t *nvecs, uint32_t ng,
                                uint32_t coeff_bytes, int accumulate) {
   if (!c || !regs || !ios || !nvecs || !ng || !nreg || nreg * ng > 16) return MFH_EINVAL;

@@ -1009,11 +1009,13 @@ void mfh_ctx_destroy(mfh_ctx *c) {
   if (c->ev_join) hipEventDestroy(c->ev_join);
   if (c->ev_chain) hipEventDestroy(c->ev_chain);
   if (c->ev_chain_done) hipEventDestroy(c->ev_chain_done);
+  if (c->ev_wstage) hipEventDestroy(c->ev_wstage);
+  if (c->ev_wdigits) hipEventDestroy(c->ev_wdigits);
   if (c->side) hipStreamDestroy(c->side);
   if (c->side2) hipStreamDestroy(c->side2);
   // every grow-only scratch, in one place: behind all the waits above and the side streams' end, so none goes earlier than it used to
   for (DevBuf *b : {&c->ws, &c->ws2, &c->ws3, &c->wws, &c->lazy, &c->aux, &c->d_msg, &c->d_prover, &c->d_pub, &c->d_batch, &c->batch_img, &c->circ_io,
-                    &c->circ_state, &c->ssp_frag, &c->sample_tmp})
+                    &c->circ_state, &c->ssp_frag, &c->ssp_img, &c->wstream, &c->sample_tmp})
     dev_free(*b);
   if (c->d_t0) hipFree(c->d_t0);
   for (auto &t : c->timed) { hipEventDestroy(t.e0); hipEventDestroy(t.e1); }
@@ -1104,6 +1106,12 @@ int mfh_set_batch_bw(mfh_ctx *c, int merged) {
   return MFH_OK;
 }
 
+int mfh_set_batch_witness(mfh_ctx *c, int streamed) {
+  if (!c) return MFH_EINVAL;
+  c->batch_witness = streamed != 0;
+  return MFH_OK;
+}
+
 int mfh_set_batch_image(mfh_ctx *c, int en) {
   if (!c) return MFH_EINVAL;
   c->batch_image = en != 0;
@@ -1133,6 +1141,7 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "mmstream_rounds")) return 10;  // the streaming launches that serve several groups (a subset of "evalmm_resident")
   if (!strcmp(which, "mmstream_rounds_persistent")) return 110;  // ... those of them that ran the persistent one-workgroup-per-CU grid (k_mmstream_p / k_mmstream_w)
   if (!strcmp(which, "mmstream_bw_persistent")) return 114;      // ... and of "mmstream_bw" (k_mmstream_pb)
+  if (!strcmp(which, "mmstream_witness")) return 48;  // the streaming launch of the batch prover's witness pass over the SSP image (mfh_set_batch_witness)
   if (!strcmp(which, "ssp_interp")) return 15;  // the gather launches of mfh_ssp_from_rows (k_interp + k_interp_sum)
   // mfh_circuit_assign (circuit_eval.hip): 16 + 2 * tier + global; tier 0 not extended, 1 extended, 2 with outputs, 3 with a WSUM gate; global = wire state in
   // device memory (k_circuit_eval_global) instead of LDS (k_circuit_eval)
@@ -1177,6 +1186,7 @@ int mfh_timing_drain(mfh_ctx *c, const char *which, uint64_t *count, double *tot
   if (kind < 0) return MFH_EINVAL;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->side) HIP_TRY(c, hipStreamSynchronize(c->side));
+  if (c->side2) HIP_TRY(c, hipStreamSynchronize(c->side2));  // ("mmstream_witness": the batch prover's witness launch runs on the chain stream)
   uint64_t n = 0, rows = 0, work = 0;
   double tot = 0;
   float last = -1.f;
@@ -1741,7 +1751,7 @@ static void upload_free(mfh_ctx *c) {
 }
 int mfh_ssp_upload(mfh_ctx *c, const void *h_ssp_u64, uint32_t *d_ssp, size_t first_slot, size_t nslots) {
   if (!c || !h_ssp_u64 || !d_ssp) return MFH_EINVAL;
-  c->ssp_frag_src = nullptr;  // derived images of the SSP are stale
+  ssp_images_stale(c);  // derived images of the SSP are stale
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t d = c->P.d;
   const size_t total = nslots * d * 8;  // bytes of uint64 coefficients

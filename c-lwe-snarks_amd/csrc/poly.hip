@@ -1058,7 +1058,7 @@ int mfh_poly_mul(mfh_ctx *c, const uint32_t *d_a, size_t la, const uint32_t *d_b
 
 int mfh_poly_prepare_t(mfh_ctx *c, const uint32_t *d_t) {
   if (!c) return MFH_EINVAL;
-  c->ssp_frag_src = nullptr;  // a (new) SSP is being prepared: derived images are stale
+  ssp_images_stale(c);  // a (new) SSP is being prepared: derived images are stale
   if (c->poly) {  // ... and so is the t prepared before: a call that fails below must not leave it in place for mfh_poly_h*
     c->poly->have_t = false;
     c->poly->cyc = false;

@@ -717,6 +717,10 @@ int batch_streams(mfh_ctx *c) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_chain, hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_chain_done, hipEventDisableTiming));
   }
+  if (!c->ev_wstage) {
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_wstage, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_wdigits, hipEventDisableTiming));
+  }
   return MFH_OK;
 }
 
@@ -1020,6 +1024,66 @@ int batch_transient_image(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nproofs,
   return MFH_OK;
 }
 
+// The witness pass of a whole call and its b_w, for ng = 2 .. 8 super-groups (mfh_set_batch_witness).  Both are products of the same digit matrix -- the statements' witness
+// bits as one-byte columns, row 0 -> 0, row r -> bit r - 1 -- with an image of m rows: b_w with the BT+BV region of the CRS image (129 536 byte positions at the default
+// size), the witness pass with the SSP image (4 d = 131 072).  So the digit fragments and column sums are built ONCE, on the chain stream as soon as the host's inputs are
+// staged (c->ev_wstage); the pass is one streaming launch there, beside the CRS expansion, followed by its epilogue (W and V = W + v_0 of every super-group, ng x BSG x d
+// coefficients each at Wall and Vall: the chain's k_add_slot_multi would read W and write V once more per super-group), and b_w's launch and epilogue follow the expansion on the caller's stream as before, behind the digits (c->ev_wdigits).  The two launches can be in flight
+// together: the witness launch claims from the queue counters of the side workspace (OnSide), b_w's from the caller's.  ios / nvs: b_w's operands, d_delta[g] = the
+// group's deltas on the device.  taken = false, and nothing queued: no room for the SSP image or the scratch -- the caller keeps k_witness_mm8q per super-group.
+int batch_witness_stream(mfh_ctx *c, const uint32_t *d_ssp, const MmRegion &reg, const MmIo *ios, const uint32_t *nvs, uint32_t ng, const uint32_t *const *d_delta,
+                         hipStream_t chain_stream, uint32_t *&Wall, uint32_t *&Vall, bool &taken) {
+  taken = false;
+  const uint32_t d = c->P.d, m = c->P.m;
+  hipStream_t const main_stream = c->stream;
+  MmsPlan BP, WP;
+  if (ng > 8 || !mms_plan(c, &reg, 1, m, ios, nvs, ng, 1, BP)) return MFH_OK;
+  const uint8_t *img;
+  {
+    OnStream chain(c, chain_stream);
+    img = ssp_image(c, d_ssp);
+  }
+  if (!img || !mms_plan_ssp(c, img, ng, WP) || WP.cd_bytes != BP.cd_bytes || WP.rpc != BP.rpc || WP.nchunks != BP.nchunks) return MFH_OK;
+  const size_t bw_b = (mms_ws_bytes(BP) + 255) & ~(size_t)255, wp_b = (size_t)ng * WP.part_bytes, w_b = (size_t)ng * BSG * d * 4;
+  if (c->wstream.cap < bw_b + wp_b + 2 * w_b) {  // (both streams read it: the whole device is awaited before it goes)
+    if (c->wstream.p) {
+      (void)hipDeviceSynchronize();
+      dev_free(c->wstream);
+    }
+    if (!dev_alloc(c->wstream, (bw_b + wp_b + 2 * w_b + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1))) {
+      (void)hipGetLastError();
+      return MFH_OK;
+    }
+  }
+  uint8_t *base = c->wstream.as<uint8_t>();
+  mms_bind(BP, base);
+  WP.cd = BP.cd;
+  WP.part = (int *)(base + bw_b);
+  WP.nolog = true;
+  Wall = (uint32_t *)(base + bw_b + wp_b);
+  Vall = (uint32_t *)(base + bw_b + wp_b + w_b);
+  int rc;
+  {
+    OnSide chain(c, chain_stream);
+    HIP_TRY(c, hipStreamWaitEvent(chain_stream, c->ev_wstage, 0));
+    rc = mms_digits(c, BP, ios, nvs);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_wdigits, chain_stream));
+    rc = mms_stream(c, WP);
+    if (rc) return rc;
+    uint32_t *W[8], *V[8];
+    for (uint32_t g = 0; g < ng; g++) W[g] = Wall + (size_t)g * BSG * d, V[g] = Vall + (size_t)g * BSG * d;
+    rc = mms_witness_finish(c, WP, ios, nvs, d_ssp, d_delta, W, d_ssp + d /* slot 1 = v_0 */, V);
+    if (rc) return rc;
+  }
+  HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_wdigits, 0));
+  rc = mms_stream(c, BP);
+  if (!rc) rc = mms_finish(c, BP, ios, nvs, 0);
+  if (rc) return rc;
+  taken = true;
+  return MFH_OK;
+}
+
 // mfh_prove_batch, and with pub != nullptr mfh_prove_batch_public (h_witness_bits then without the statement bits)
 int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
                      size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
@@ -1111,10 +1175,15 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     c->ev_wdone.push_back(e2);
   }
   hipStream_t const main_stream = c->stream, chain_stream = c->side2;
+  // The streamed witness pass (batch_witness_stream): W and V of EVERY super-group are written by one launch and its epilogue at the head of the call, into areas of their
+  // own (WSTREAM, VSTREAM); H keeps the two areas, and a chain is then the polynomial step only.
+  bool wroute = false;
+  uint32_t *WSTREAM = nullptr, *VSTREAM = nullptr;
   auto whv_of = [&](uint32_t sgi, uint32_t *&W, uint32_t *&H, uint32_t *&V) {
     W = B.WHV + (size_t)(sgi % nbuf) * 3 * BSG * d;
     H = W + (size_t)BSG * d;
     V = H + (size_t)BSG * d;
+    if (wroute) W = WSTREAM + (size_t)sgi * BSG * d, V = VSTREAM + (size_t)sgi * BSG * d;
   };
   auto launch_chain = [&](uint32_t sgi) -> int {  // the chain stream has been told what to wait for
     const uint32_t s0 = sgi * SG, sg = std::min(SG, nproofs - s0);
@@ -1122,16 +1191,25 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     whv_of(sgi, WALL, HALL, VALL);
     OnStream chain(c, chain_stream);
     const PubBatch psg = pub ? pub->at(s0) : PubBatch{};
-    int r = batch_chain_launch(c, src, d_ssp, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0, WALL, HALL, VALL, c->ev_wdone[sgi % nbuf],
-                               pub ? &psg : nullptr);
+    int r;
+    if (wroute)
+      r = mfh_poly_h_multi(c, VALL, HALL, sg);
+    else
+      r = batch_chain_launch(c, src, d_ssp, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0, WALL, HALL, VALL, c->ev_wdone[sgi % nbuf],
+                             pub ? &psg : nullptr);
     if (r) return r;
     HIP_TRY(c, hipEventRecord(c->ev_cdone[sgi % nbuf], chain_stream));
     return MFH_OK;
   };
   HIP_TRY(c, hipEventRecord(c->ev_chain, main_stream));  // what the caller's stream has been given so far no longer reads the scratch
   HIP_TRY(c, hipStreamWaitEvent(chain_stream, c->ev_chain, 0));
-  rc = launch_chain(0);
-  if (rc) return rc;
+  // what the streamed witness pass asks of the call, as far as it can be told before the image question is settled: then the first chain waits for that answer
+  const bool try_ws = c->batch_witness && nsl == 1 && will_stream && !pub && d_ssp && src.dense && d % 64 == 0 && m >= 2 && nsg >= 2 && nsg <= 8 && c->batch_bw_merged &&
+                      mms_ssp_ok(c);
+  if (!try_ws) {
+    rc = launch_chain(0);
+    if (rc) return rc;
+  }
   if (nsl > 1) {
     for (uint32_t k = 1; k < nsg; k++) {
       rc = launch_chain(k);
@@ -1182,10 +1260,15 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     return MFH_OK;
   }
   ImageGuard transient{c, false};
+  if (try_ws) {  // the host's inputs first: the witness launch needs them and runs beside the expansion
+    rc = batch_stage_host(c, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_wstage, main_stream));
+  }
   rc = batch_transient_image(c, d_crs_c8, nproofs, 0, 1, transient);
   if (rc) return rc;
   // everything the host contributes, in one copy (no host-side wait between the super-groups), staged while the GPU expands the CRS
-  rc = batch_stage_host(c, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
+  if (!try_ws) rc = batch_stage_host(c, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
   if (rc) return rc;
   rc = batch_ct_t(c, d_crs_c8, B);
   if (rc) return rc;
@@ -1213,10 +1296,21 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
         ios[k].add_scale = (const uint32_t *)(d_cw + B.cw_delta_off);
         nvs[k] = sg;
       }
+      if (try_ws) {  // (nsg <= 8: the one round of this loop)
+        const uint32_t *dl[8];
+        for (uint32_t k = 0; k < ng; k++) dl[k] = ios[k].add_scale;
+        rc = batch_witness_stream(c, d_ssp, reg, ios, nvs, ng, dl, chain_stream, WSTREAM, VSTREAM, wroute);
+        if (rc) return rc;
+        if (wroute) continue;
+      }
       rc = ng > 1 ? eval_rows_multi_io_regions(c, &reg, 1, m, ios, nvs, ng, 1, 0) : eval_rows_multi_io(c, reg.off, m, reg.c8, ios[0], nvs[0], 1, 0);
       if (rc) return rc;
     }
     bw_done = true;
+  }
+  if (try_ws) {  // the first chain: the polynomial step behind the witness launch and its epilogue, or -- the pass was not taken -- the whole chain as before
+    rc = launch_chain(0);
+    if (rc) return rc;
   }
   // early mode (mfh_set_mm_width(ctx, w < 32, 1): the persistent streaming launch leaves CUs of every XCD free): the chain of super-group k + 1 is queued BESIDE the
   // row work of super-group k (its w | h | v area was last read by k - 1) and the epilogues + smudging of k beside the row work of k + 1, instead of between them
@@ -1238,7 +1332,7 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     if (early && sgi >= 2) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_sgdone[sgi - 2], 0));
     // b_w's pass over the BT+BV image is HBM-bound like the chain's witness pass, and the chain is what the S / AS launches wait for: b_w
     // starts when the witness pass is over and runs beside the polynomial step (NTT: VALU / LDS)
-    HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_wdone[sgi % nbuf], 0));
+    if (!wroute) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_wdone[sgi % nbuf], 0));
     // the multi-vector launches read their coefficient vectors where the polynomial step left them and write the proof structs in place (MmIo)
     bool on_side = false;
     rc = batch_rows_supergroup(c, d_crs_c8, 0, 1, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, sproofs, B, slot, h_delta + s0,

@@ -214,7 +214,7 @@ int mfh_ssp_from_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, con
   if (ncut)
     if (int rc = work_reserve(c, s->scratch, (size_t)ncut * d * 4)) return rc;
 
-  c->ssp_frag_src = nullptr;  // derived images of the SSP are stale
+  ssp_images_stale(c);  // derived images of the SSP are stale
   HIP_TRY(c, hipMemcpyAsync(s->buf.p, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   const uint2 *d_nz = s->buf.as<const uint2>();
   const uint4 *d_parts = (const uint4 *)(s->buf.as<uint32_t>() + nz_words), *d_splits = d_parts + nparts;

@@ -446,7 +446,7 @@ int mfh_ssp_set_rows(mfh_ctx *c, uint32_t nrows, const uint32_t *h_row_ptr, cons
   c->rows_lu_max = lu_max;
   c->prg_on = false;
   c->prg_t = nullptr;
-  c->ssp_frag_src = nullptr;
+  ssp_images_stale(c);
   return MFH_OK;
 }
 

@@ -1,13 +1,15 @@
 // witness.hip -- the witness pass (reference src/snark.c:141,147-155), the first step of every prover entry point:
 //     w_b[k] = delta_b t[k] + sum_i bit_b[i] v_i[k]  (mod p),   k = 0 .. d - 1,
 // over the SSP's wire polynomials v_i (slot i + 1; slot 0 = t): a dense uint32 image or the generator of ssp_prg.hpp.  (The row SSP has no
-// v_i to sum: the entry points hand it to ssp_rows.hip.)  Three forms, all staging the bits through pinned memory into c->wws, on c->stream:
+// v_i to sum: the entry points hand it to ssp_rows.hip.)  Four forms, all staging the bits through pinned memory into c->wws, on c->stream:
 //   VALU, one statement   k_witness_partial[_prg] sums the selected rows in G shares, k_witness_finish adds delta t: mfh_witness_poly (mfh_prove);
 //                         mfh_witness_lanes / _from_lanes (a rank's share of the rows); mfh_ssp_prg_make_t (t of a generated SSP is such a sum)
 //   VALU, 12 statements   k_witness_partial_multi[_prg]<12>, a row read or generated once per 12: mfh_witness_poly_multi (batch chain, d % 128 != 0)
 //   GEMM, <= 256          bits x SSP bytes on the matrix cores, the rows read once (k_witness_mm<MT> / k_witness_mm8q: B fragments from the image
 //                         k_ssp_frag builds per SSP) or generated once (k_witness_mm_prg<MT> / k_witness_mm8q_prg: B fragments hashed in the
 //                         kernel): mfh_witness_poly_mm (batch chain), mfh_witness_poly_mm_cols (a rank's coefficient range, row-sharded prover)
+//   GEMM, a whole call    SSP bytes x bits, the batch prover's streaming launch (evalmm.hip: mms_plan_ssp) over the A-fragment image k_ssp_image builds per SSP, in groups
+//                         of 255 statements: mfh_witness_poly_stream; mfh_prove_batch (snark.hip: batch_witness_stream) shares b_w's digit fragments with it
 #include <algorithm>
 #include <type_traits>
 
@@ -173,6 +175,30 @@ __global__ void k_ssp_frag(const uint32_t *__restrict__ ssp, uint32_t nrowsel, u
   for (int e = 0; e < 4; e++) x[e] = rb + e < nrowsel ? ssp[(uint64_t)(rb + e + 2) * d + k] ^ 0x80808080u : 0u;  // row r = v_{r+1} = slot r + 2
 #pragma unroll
   for (int w = 0; w < 4; w++) frag[(((((uint64_t)kt * KSt + K) * 4 + w) * 64 + lane) << 2) + eg] = byte_plane(x[0], x[1], x[2], x[3], w);
+}
+// A third image of the SSP, in the A-fragment order k_mmstream reads (header of expandmm.hip), for the batch prover's streamed witness pass (evalmm.hip:
+// mms_plan_ssp): the SSP as the MATRIX of that GEMM and the witness bits as its digit columns -- b_w's own product over the BT+BV image with the SSP in the
+// image's place.  "Row" r = 0 .. m - 1 of the K dimension is slot r + 1 (r = 0: v_0, whose digit column holds coefficient 0; r >= 1: v_r, selected by bit
+// r - 1: exactly the digit matrix k_mm_digits builds for b_w), "byte position" 4 k + w is byte w of coefficient k, so that a lane's packed record (pk = 1: four
+// consecutive byte positions, sum_e acc[e] 2^(8 e)) is the integer sum_r bit_r v_r[k] itself up to the -128 corrections.  For row tile P (16 byte positions =
+// coefficients 4 P .. 4 P + 3) and 64-row k-step ks:
+//     img[((P * KS + ks) * 64 + lane) * 16 + e] = byte (lane & 3) of v_r[4 P + ((lane & 15) >> 2)] ^ 0x80,   r = 64 ks + 16 (lane >> 4) + e,
+// KS = the k-steps of m rows padded to 256-row stages; rows >= m hold 0x80 (A = 0; their digits are zero as well).  (d / 4) x KS KiB: the size of the uint32
+// SSP, rounded up to whole stages.  One thread = 16 rows x 1 coefficient -> the 16-byte elements of the four lanes that hold the coefficient's four bytes
+// (64 contiguous bytes); consecutive threads take consecutive coefficients, so the reads of a row are coalesced.  d % 64 == 0: a wave has one (ks, lane >> 4).
+__global__ __launch_bounds__(256) void k_ssp_image(const uint32_t *__restrict__ ssp, uint32_t m, uint32_t d, uint32_t KS, uint4 *__restrict__ img) {
+  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t k = (uint32_t)(gid % d), rest = (uint32_t)(gid / d), g4 = rest & 3, ks = rest >> 2;
+  if (ks >= KS) return;
+  const uint32_t r0 = 64 * ks + 16 * g4;
+  uint32_t x[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) x[e] = (r0 + e < m ? ssp[(uint64_t)(r0 + e + 1) * d + k] : 0u) ^ 0x80808080u;
+  uint4 *o = img + (((uint64_t)(k >> 2) * KS + ks) * 64 + 16 * g4 + 4 * (k & 3));
+#pragma unroll
+  for (int w = 0; w < 4; w++)
+    o[w] = uint4{byte_plane(x[0], x[1], x[2], x[3], w), byte_plane(x[4], x[5], x[6], x[7], w), byte_plane(x[8], x[9], x[10], x[11], w),
+                 byte_plane(x[12], x[13], x[14], x[15], w)};
 }
 // The witness kernels work on a RANGE of coefficients [col0, col0 + d) of the polynomials (the whole polynomial: col0 = 0, d = the SSP's
 // d; a rank of the row-sharded batch prover computes its slice of every statement's w: mfh_witness_poly_mm_cols): `d` below is the width
@@ -682,7 +708,86 @@ template <class F> void with_mt(uint32_t MT, F &&f) {
 
 }  // namespace
 
+// The SSP image of k_ssp_image, built where ssp_frag is built -- on first use per SSP -- and stale where ssp_frag_src is (ssp_images_stale).  Any stream may read it
+// afterwards, so the build is awaited here, once per SSP.  No room: nullptr and no error, the caller keeps k_witness_mm8q (as batch_transient_image's callers
+// regenerate the keystream).
+const uint8_t *ssp_image(mfh_ctx *c, const uint32_t *d_ssp) {
+  const uint32_t d = c->P.d, m = c->P.m;
+  if (!d_ssp || d % 64 || m < 2) return nullptr;
+  const uint32_t KS = (m + 255) / 256 * 4;  // 64-row k-steps, whole 256-row stages (mms_stream)
+  const size_t bytes = (size_t)(d / 4) * KS * 1024;
+  if (c->ssp_img_src == d_ssp && c->ssp_img.cap >= bytes) return c->ssp_img.as<uint8_t>();
+  c->ssp_img_src = nullptr;
+  if (c->ssp_img.cap < bytes) {
+    if (c->ssp_img.p) {
+      (void)hipDeviceSynchronize();
+      dev_free(c->ssp_img);
+    }
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = 0;
+    if (bytes > mem_free / 4 * 3 || !dev_alloc(c->ssp_img, bytes)) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+  }
+  hipLaunchKernelGGL(k_ssp_image, dim3((uint32_t)((uint64_t)d * KS * 4 / 256)), dim3(256), 0, c->stream, d_ssp, m, d, KS, c->ssp_img.as<uint4>());
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
+  c->ssp_img_src = d_ssp;
+  return c->ssp_img.as<uint8_t>();
+}
+
 extern "C" {
+
+// mfh_witness_poly_mm's results for ANY number of statements by the batch prover's streamed pass (evalmm.hip: mms_plan_ssp): groups of 255 statements, up to
+// 8 groups per streaming launch over the SSP image -- k_mmstream1 for one group, the persistent grid k_mmstream_pb for 2, 4 or 8, k_mmstream otherwise --, the
+// digit fragments built here (mfh_prove_batch shares b_w's).  Dense SSPs with d % 64 == 0; MFH_EUNSUPPORTED otherwise, MFH_ENOMEM without room for the image.
+int mfh_witness_poly_stream(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta, uint32_t *d_w) {
+  if (!witness_args_ok(c, nstmt, 0xffffffffu, h_bits, h_delta, d_w)) return MFH_EINVAL;
+  const uint32_t d = c->P.d, m = c->P.m;
+  if (!d_ssp || d % 64 || m < 2 || !mms_ssp_ok(c)) { c->err = "mfh_witness_poly_stream: a dense SSP, d a multiple of 64 and packed partial products"; return MFH_EUNSUPPORTED; }
+  const uint32_t bstride = (m + 6) / 8;
+  if (bits_stride < bstride) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  if (int rc = witness_deltas(c, nstmt, h_delta)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint8_t *img = ssp_image(c, d_ssp);
+  if (!img) { c->err = "mfh_witness_poly_stream: no room for the SSP image"; return MFH_ENOMEM; }
+  constexpr uint32_t SG = 255, NG = 8;  // statements per group (one digit column each + the ones column), groups per launch
+  for (uint32_t s0 = 0; s0 < nstmt; s0 += SG * NG) {
+    const uint32_t cnt = std::min(SG * NG, nstmt - s0), ng = (cnt + SG - 1) / SG;
+    MmsPlan P;
+    if (!mms_plan_ssp(c, img, ng, P)) return MFH_EINVAL;
+    // per group the packed bits and the deltas, staged in one copy | the groups' column sums | digit fragments | partial products
+    const size_t head_g = up256((size_t)SG * bstride + 3) + up256((size_t)SG * 4), delta_off = up256((size_t)SG * bstride + 3);
+    const WwsCarve<4> ws({head_g * ng, (size_t)ng * 2048, P.cd_bytes * ng, P.part_bytes * ng});
+    if (int rc = ws.reserve(c)) return rc;
+    PinBuf &wpin = c->pin_wring[c->pin_wnext++ % 8];
+    uint8_t *stage = (uint8_t *)pin_acquire(c, wpin, head_g * ng);
+    if (!stage) return MFH_ENOMEM;
+    uint8_t *dev = ws.at<uint8_t>(c, 0);
+    MmIo ios[NG];
+    uint32_t nvs[NG], *W[NG];
+    const uint32_t *dl[NG];
+    for (uint32_t g = 0; g < ng; g++) {
+      const uint32_t b0 = s0 + g * SG, sg = std::min(SG, nstmt - b0);
+      for (uint32_t b = 0; b < sg; b++) memcpy(stage + g * head_g + (size_t)b * bstride, h_bits + (size_t)(b0 + b) * bits_stride, bstride);
+      memcpy(stage + g * head_g + delta_off, h_delta + b0, (size_t)sg * 4);
+      ios[g] = MmIo{{nullptr, nullptr}, sg, {nullptr, nullptr}, sg, 0, dev + g * head_g, bstride, ws.at<int64_t>(c, 1) + 256 * g};
+      nvs[g] = sg;
+      dl[g] = (const uint32_t *)(dev + g * head_g + delta_off);
+      W[g] = d_w + (size_t)b0 * d;
+    }
+    HIP_TRY(c, hipMemcpyAsync(dev, stage, head_g * ng, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, wpin);
+    HIP_TRY(c, hipMemsetAsync(ws.at<uint8_t>(c, 1), 0, (size_t)ng * 2048, c->stream));
+    P.cd = ws.at<int8_t>(c, 2);
+    P.part = ws.at<int>(c, 3);
+    int rc = mms_digits(c, P, ios, nvs);
+    if (!rc) rc = mms_stream(c, P);
+    if (!rc) rc = mms_witness_finish(c, P, ios, nvs, d_ssp, dl, W);
+    if (rc) return rc;
+  }
+  return MFH_OK;
+}
 
 int mfh_ssp_set_prg(mfh_ctx *c, uint64_t seed, const uint32_t *d_t) {
   if (!c) return MFH_EINVAL;

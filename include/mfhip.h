@@ -918,6 +918,11 @@ int mfh_set_batch_launch(mfh_ctx *ctx, uint32_t groups_per_launch, int merge_reg
 /* b_w (src/snark.c:143-155) of all super-groups of a streaming mfh_prove_batch call in ONE launch per up to 8 super-groups over the BT+BV image (default), or one
  * launch per super-group (0; rounds 1 - 3).  Tuning; results do not depend on it. */
 int mfh_set_batch_bw(mfh_ctx *ctx, int merged);
+/* The witness pass of a streaming mfh_prove_batch call (single GPU, dense SSP, d % 64 == 0, no public inputs, no row slabs, 2 .. 8 super-groups with b_w merged) as ONE
+ * streaming launch over an image of the SSP in the CRS image's fragment order (mfh_witness_poly_stream below), sharing b_w's digit fragments (default), or
+ * k_witness_mm8q once per super-group (0; every other caller's pass).  The image is a per-SSP constant the size of the SSP, built on first use and rebuilt after
+ * mfh_ssp_upload / mfh_ssp_prepare; without room for it the call keeps the per-super-group pass.  Tuning; results do not depend on it. */
+int mfh_set_batch_witness(mfh_ctx *ctx, int streamed);
 /* how a streaming launch with several groups is laid out on the chip (tuning; results do not depend on it).  map: 0 = a tile group's workgroups for all
  * groups of both regions are neighbours, 1 = the 32 workgroups an XCD runs at a time are 32 / g tile groups x the g groups of ONE region (a group's digit
  * fragments are then shared by twice as many workgroups of the XCD).  persistent: 1 = one workgroup per CU looping over its XCD's items instead of one workgroup
@@ -1023,6 +1028,11 @@ int mfh_witness_poly_mm(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t nstmt, con
  * multiples of 128, else MFH_EUNSUPPORTED).  The cost is the range's share of the read / generation of the selected rows. */
 int mfh_witness_poly_mm_cols(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                              uint32_t col0, uint32_t ncols, uint32_t *d_w, size_t w_stride);
+/* mfh_witness_poly_mm for ANY number of statements of a dense SSP with d a multiple of 64, as the batch prover's streaming GEMM (SSP bytes x witness-bit digit columns, exact):
+ * groups of 255 statements, up to 8 groups per launch over a third image of the SSP, in the CRS image's A-fragment order (same size, built on first use and rebuilt
+ * after mfh_ssp_upload / mfh_ssp_prepare).  MFH_EUNSUPPORTED for other SSPs or with mfh_set_mm_pack(ctx, 0); MFH_ENOMEM without room for the image. */
+int mfh_witness_poly_stream(mfh_ctx *ctx, const uint32_t *d_ssp, uint32_t nstmt, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
+                            uint32_t *d_w);
 /* Optional second exchange that also shards the witness polynomial (the SSP pass, 1.4 GB per proof at the default size):
  * mfh_witness_lanes = this rank's share of sum_{bit} v_i as d uint64 lanes (each < p) -> all-reduce (sum) ->
  * mfh_prove_partial_w takes the summed lanes instead of recomputing w on every rank.  mfh_witness_from_lanes: w = delta t + lanes mod p. */
