@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aes_dev.hpp"
+#include "batch_plan.hpp"
 #include "mfhip.h"
 #include "ssp_prg.hpp"
 
@@ -273,9 +274,34 @@ inline int lazy_reserve(mfh_ctx *c, size_t bytes) {
   return MFH_OK;
 }
 inline int ws_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->ws, bytes); }
+inline DevBuf &mm_ws(mfh_ctx *c) { return c->mm_ws_sel ? c->ws2 : c->ws; }  // the multi-vector launches' workspace: the side stream's launch has its own (OnSide, snark.hip)
 inline int wws_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->wws, bytes); }
 inline int ws2_reserve(mfh_ctx *c, size_t bytes) { return work_reserve(c, c->ws2, bytes); }
 inline int aux_reserve(mfh_ctx *c, size_t bytes) { return dev_reserve(c, c->aux, bytes); }
+
+// vec holds at least n events (no timing), created as needed
+inline int events_grow(mfh_ctx *c, std::vector<hipEvent_t> &vec, size_t n) {
+  while (vec.size() < n) {
+    hipEvent_t e;
+    HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    vec.push_back(e);
+  }
+  return MFH_OK;
+}
+
+// the ciphertext geometry of the context's parameters (batch_plan.hpp), and the checks the batch entry points share on what the host hands them: bits_stride covers a
+// statement's m - 1 witness bits (kNoStride: the entry point takes no bits), the ndelta deltas are < p (h_delta may be null: none), a smudging magnitude of maglen bytes
+// times p fits the KW words of a term (0: the entry point does not smudge)
+inline mf::CtGeom ct_geom(const mfh_ctx *c) { return mf::CtGeom(c->P.n, c->P.logq, c->P.m); }
+static_assert(mf::PLAN_P == MFH_P, "batch_plan.hpp restates p");
+constexpr size_t kNoStride = ~(size_t)0;
+inline int batch_args_check(mfh_ctx *c, const mf::CtGeom &g, size_t bits_stride, const uint32_t *h_delta, uint32_t ndelta, size_t maglen) {
+  if (bits_stride < g.bstride) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  for (uint32_t b = 0; h_delta && b < ndelta; b++)
+    if (h_delta[b] >= MFH_P) { c->err = "delta must be < p"; return MFH_EINVAL; }
+  if (maglen + 4 > (size_t)g.KW * 4) { c->err = "smudge magnitude too wide"; return MFH_EINVAL; }
+  return MFH_OK;
+}
 
 // resolves the d_ssp argument of an entry point: a dense image, or (NULL) the registered row SSP or generator-defined SSP.  The row SSP is only
 // handed to callers that say they handle it (rows_ok): its `dense` is the prefix of slots [0, prefix), and a kernel that reads further would run
@@ -359,7 +385,14 @@ int eval_rows_multi_io_set(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t
 struct MmRegion { uint64_t off; const uint8_t *c8; };
 int eval_rows_multi_io_regions(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, size_t nrows, const MmIo *ios, const uint32_t *nvecs, uint32_t ng,
                                uint32_t coeff_bytes, int accumulate);
-bool mm_image_covers(const mfh_ctx *c, uint64_t off, size_t nrows);
+// the region of the registered matrix-core image that was expanded from exactly these rows (stream offset, count > 0), or nullptr: regenerate the keystream
+inline const uint8_t *mm_image_region(const mfh_ctx *c, uint64_t off, size_t nrows) {
+  for (int r = 0; r < 3 && c->mm_image && nrows; r++)
+    if (c->mm_off[r] == off && c->mm_rows[r] == nrows) return c->mm_image + c->mm_base[r];
+  return nullptr;
+}
+// true when mfh_eval_rows_multi over nrows rows at stream offset off would stream the registered image
+inline bool mm_image_covers(const mfh_ctx *c, uint64_t off, size_t nrows) { return mm_image_region(c, off, nrows) != nullptr; }
 // the phases of such a launch (evalmm.hip), for callers that queue them on different streams
 struct MmsPlan {
   uint32_t ng, ngt, ND, nrows, nchunks, rpc, rpad, ntiles, mtiles;

@@ -1301,9 +1301,7 @@ int eval_rows_multi_io(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t *d_
   // 128 digit columns: k_evalmm (32x32x32 MFMA, 4-coordinate tiles, logq = 736 only); up to 256: k_evalmm16 (16x16x64, 2- or
   // 1-coordinate tiles), which needs every row segment to start at byte 0 or 8 of an AES block: stream offset and row length multiples of 8.
   // A registered matrix-core CRS image (mfh_crs_set_resident_mm) serves the region it was expanded from: always the 256-column layout.
-  const uint8_t *img_region = nullptr;
-  for (int r = 0; r < 3 && c->mm_image; r++)
-    if (c->mm_off[r] == off && c->mm_rows[r] == nrows && nrows) img_region = c->mm_image + c->mm_base[r];
+  const uint8_t *const img_region = mm_image_region(c, off, nrows);
   const bool wide = img_region || !q736 || nvec * ND + 1 > 128;
   if (nvec * ND + 1 > 256) { c->err = "mfh_eval_rows_multi: at most 63 four-byte (255 one-byte) coefficient vectors per call (256 digit columns)"; return MFH_EINVAL; }
   if (wide && ((off & 7) || (((uint64_t)n * wg.vby) & 7))) {
@@ -1329,20 +1327,14 @@ int eval_rows_multi_io(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t *d_
   // row chunks: 368 column tiles x 2 chunks = 736 workgroups = 2.9 rounds of the 256 CUs (one workgroup per CU at a time); an int32
   // accumulator holds 131 071 rows
   // (the 256-column kernels have 736 (1471) column tiles / 506 workgroups of row-tile pairs: one chunk already fills the CUs as evenly)
-  uint32_t nchunks = (!wide && nrows >= 8 * rt) ? 2 : 1;
-  // (the limit rounded DOWN to whole units first: rounding a chunk of <= 131 071 rows up to a unit afterwards could reach 131 072)
-  const uint32_t lim = std::max(rt, c->mm_chunk_rows / rt * rt);
-  nchunks = std::max<uint32_t>(nchunks, ((uint32_t)nrows + lim - 1) / lim);
-  uint32_t rpc = ((uint32_t)nrows + nchunks - 1) / nchunks;
-  rpc = (rpc + rt - 1) / rt * rt;  // <= lim
-  nchunks = ((uint32_t)nrows + rpc - 1) / rpc;
-  const uint32_t rpad = nchunks * rpc;  // a multiple of the unit: digit rows past nrows are zero
+  const mf::RowChunks ch = mf::row_chunks((uint32_t)nrows, rt, c->mm_chunk_rows, (!wide && nrows >= 8 * rt) ? 2 : 1);
+  const uint32_t nchunks = ch.nchunks, rpc = ch.rpc, rpad = ch.rpad;
   const size_t cd_bytes = ((size_t)N * rpad + 255) & ~(size_t)255;
   const size_t sc_bytes = 256 * 8;
   const size_t part_bytes = (size_t)nchunks * ntiles * mb * N * 4;
-  int rc = c->mm_ws_sel ? ws2_reserve(c, cd_bytes + sc_bytes + part_bytes) : ws_reserve(c, cd_bytes + sc_bytes + part_bytes);
+  int rc = work_reserve(c, mm_ws(c), cd_bytes + sc_bytes + part_bytes);
   if (rc) return rc;
-  uint8_t *wsp = (c->mm_ws_sel ? c->ws2 : c->ws).as<uint8_t>();  // the launch on the side stream of mfh_prove_batch has its own scratch
+  uint8_t *wsp = mm_ws(c).as<uint8_t>();  // the launch on the side stream of mfh_prove_batch has its own scratch
   int8_t *cd = (int8_t *)wsp;
   int64_t *sc = io.sc_zeroed ? io.sc_zeroed : (int64_t *)(wsp + cd_bytes);
   int *part = (int *)(wsp + cd_bytes + sc_bytes);
@@ -1395,12 +1387,7 @@ bool mms_plan(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, size_t nrows, con
               MmsPlan &P) {
   if (!c || !regs || !ios || !nvecs || !ng || !nreg || nreg > 2 || nreg * ng > 16) return false;
   bool ok = nreg * ng > 1 && c->have_seed && nrows && nrows <= 0xffffffffu - 256;
-  for (uint32_t q = 0; q < nreg && ok; q++) {
-    P.img[q] = nullptr;
-    for (int r = 0; r < 3 && c->mm_image; r++)
-      if (c->mm_off[r] == regs[q].off && c->mm_rows[r] == nrows) P.img[q] = c->mm_image + c->mm_base[r];
-    ok = P.img[q] != nullptr;
-  }
+  for (uint32_t q = 0; q < nreg && ok; q++) ok = (P.img[q] = mm_image_region(c, regs[q].off, nrows)) != nullptr;
   P.ng = ng;
   P.ngt = nreg * ng;
   for (uint32_t g = 0; g < P.ngt && ok; g++) {
@@ -1418,12 +1405,8 @@ bool mms_plan(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, size_t nrows, con
   P.ntiles = (c->P.n + 1 + wg.ct - 1) / wg.ct;
   P.mtiles = P.ntiles * wg.mt;
   // row chunks: an int32 accumulator holds 131 071 rows (a rank's share of a 2^20-row region is 131 072)
-  // (the limit rounded down to whole stages first, so that the rounded-up chunk cannot exceed it: 2 x 131 071 rows are three chunks)
-  const uint32_t lim = std::max<uint32_t>(RT2, c->mm_chunk_rows / RT2 * RT2);
-  uint32_t nchunks = ((uint32_t)nrows + lim - 1) / lim;
-  P.rpc = (((uint32_t)nrows + nchunks - 1) / nchunks + RT2 - 1) / RT2 * RT2;  // <= lim
-  P.nchunks = ((uint32_t)nrows + P.rpc - 1) / P.rpc;
-  P.rpad = P.nchunks * P.rpc;
+  const mf::RowChunks ch = mf::row_chunks(P.nrows, RT2, c->mm_chunk_rows);
+  P.nchunks = ch.nchunks, P.rpc = ch.rpc, P.rpad = ch.rpad;
   P.cd_bytes = ((size_t)N2 * P.rpad + 255) & ~(size_t)255;
   P.part_bytes = ((size_t)P.nchunks * P.ntiles * wg.mbp * N2 * 4 + 255) & ~(size_t)255;
   P.cd = nullptr;
@@ -1579,12 +1562,9 @@ bool mms_plan_ssp(mfh_ctx *c, const uint8_t *image, uint32_t ng, MmsPlan &P) {
   P.nrows = m;
   P.ntiles = 0;          // (no ciphertext epilogue)
   P.mtiles = d / 4;      // 4 d byte positions in row tiles of 16: d / 64 tile groups, whole ones
-  // the row chunks of mms_plan for the same m rows, so that b_w's digit fragments serve this launch as they are
-  const uint32_t lim = std::max<uint32_t>(RT2, c->mm_chunk_rows / RT2 * RT2);
-  const uint32_t nchunks = (m + lim - 1) / lim;
-  P.rpc = ((m + nchunks - 1) / nchunks + RT2 - 1) / RT2 * RT2;
-  P.nchunks = (m + P.rpc - 1) / P.rpc;
-  P.rpad = P.nchunks * P.rpc;
+  // the row chunks of mms_plan for the same m rows (mf::row_chunks), so that b_w's digit fragments serve this launch as they are
+  const mf::RowChunks ch = mf::row_chunks(m, RT2, c->mm_chunk_rows);
+  P.nchunks = ch.nchunks, P.rpc = ch.rpc, P.rpad = ch.rpad;
   P.cd_bytes = ((size_t)N2 * P.rpad + 255) & ~(size_t)255;
   P.part_bytes = (size_t)P.nchunks * d * N2 * 8;  // one int64 record per (chunk, coefficient, digit column)
   P.cd = nullptr;
@@ -1621,9 +1601,9 @@ int eval_rows_multi_io_regions(mfh_ctx *c, const MmRegion *regs, uint32_t nreg, 
     return MFH_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = c->mm_ws_sel ? ws2_reserve(c, mms_ws_bytes(P)) : ws_reserve(c, mms_ws_bytes(P));
+  int rc = work_reserve(c, mm_ws(c), mms_ws_bytes(P));
   if (rc) return rc;
-  mms_bind(P, (c->mm_ws_sel ? c->ws2 : c->ws).p);
+  mms_bind(P, mm_ws(c).p);
   rc = mms_digits(c, P, ios, nvecs);
   if (!rc) rc = mms_stream(c, P);
   if (!rc) rc = mms_finish(c, P, ios, nvecs, accumulate);
@@ -1633,12 +1613,6 @@ int eval_rows_multi_io_set(mfh_ctx *c, uint64_t off, size_t nrows, const uint8_t
                            uint32_t coeff_bytes) {
   const MmRegion reg = {off, d_c8};
   return eval_rows_multi_io_regions(c, &reg, 1, nrows, ios, nvecs, ng, coeff_bytes, 0);
-}
-// true when mfh_eval_rows_multi over nrows rows at stream offset off would stream the registered image
-bool mm_image_covers(const mfh_ctx *c, uint64_t off, size_t nrows) {
-  for (int r = 0; r < 3 && c->mm_image; r++)
-    if (c->mm_off[r] == off && c->mm_rows[r] == nrows && nrows) return true;
-  return false;
 }
 
 extern "C" {
@@ -1652,9 +1626,9 @@ static size_t mm_region_bytes(const mfh_ctx *c, uint64_t rows) {  // row tiles x
 // the three row ranges (absolute stream rows) of rank `rank`'s shares: S share | AS share | BT+BV share (the whole regions when world == 1)
 struct MmShare { uint64_t row0[3], rows[3]; };
 static MmShare mm_share(const mfh_ctx *c, uint32_t rank, uint32_t world) {
-  const uint64_t d = c->P.d, m = c->P.m;
-  const uint64_t loS = d * rank / world, cS = d * (rank + 1) / world - loS, lo = m * rank / world, cnt = m * (rank + 1) / world - lo;
-  return MmShare{{loS, d + loS, 2 * d + lo}, {cS, cS, cnt}};
+  const uint64_t d = c->P.d;
+  const mf::Share S = mf::row_share(d, rank, world), B = mf::row_share(c->P.m, rank, world);
+  return MmShare{{S.lo, d + S.lo, 2 * d + B.lo}, {S.cnt, S.cnt, B.cnt}};
 }
 size_t mfh_crs_mm_share_bytes(const mfh_ctx *c, uint32_t rank, uint32_t world) {
   if (!c || !world || rank >= world) return 0;

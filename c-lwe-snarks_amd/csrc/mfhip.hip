@@ -1562,17 +1562,9 @@ int mfh_crs_set_resident_prefix(mfh_ctx *c, const void *d_rows, size_t nrows_res
   return MFH_OK;
 }
 
-static void row_share(uint32_t rows, uint32_t rank, uint32_t world, uint32_t &lo, uint32_t &cnt) {
-  lo = (uint32_t)((uint64_t)rows * rank / world);
-  cnt = (uint32_t)((uint64_t)rows * (rank + 1) / world) - lo;
-}
-
 size_t mfh_resident_share_rows(const mfh_ctx *c, uint32_t rank, uint32_t world) {
   if (!c || !world || rank >= world) return 0;
-  uint32_t lo, cs, cb;
-  row_share(c->P.d, rank, world, lo, cs);
-  row_share(c->P.m, rank, world, lo, cb);
-  return (size_t)2 * cs + cb;
+  return (size_t)(2 * mf::row_share(c->P.d, rank, world).cnt + mf::row_share(c->P.m, rank, world).cnt);
 }
 
 int mfh_crs_expand_share(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world, void *d_image) {
@@ -1580,9 +1572,8 @@ int mfh_crs_expand_share(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, uin
   const uint32_t d = c->P.d, m = c->P.m, ctb = c->P.logq / 8;
   const uint64_t ctr_ct = (uint64_t)ctb * c->P.n;
   const size_t rb = mfh_resident_row_bytes(c);
-  uint32_t loS, cS, loB, cB;
-  row_share(d, rank, world, loS, cS);
-  row_share(m, rank, world, loB, cB);
+  const mf::Share S = mf::row_share(d, rank, world), B = mf::row_share(m, rank, world);
+  const uint32_t loS = (uint32_t)S.lo, cS = (uint32_t)S.cnt, loB = (uint32_t)B.lo, cB = (uint32_t)B.cnt;
   uint8_t *img = (uint8_t *)d_image;
   int rc = mfh_crs_expand(c, ctr_ct * loS, cS, d_crs_c8 + (size_t)loS * ctb, img);                                   // S share
   if (rc) return rc;
@@ -1686,25 +1677,15 @@ int mfh_add_dotp(mfh_ctx *c, uint64_t *d_rop, const uint64_t *d_a, const uint64_
 int mfh_ct_smudge(mfh_ctx *c, uint64_t *d_cts, size_t count, const uint8_t *h_mag, size_t maglen, const uint8_t *h_sign) {
   if (!c || (count && (!d_cts || !h_mag || !h_sign))) return MFH_EINVAL;
   if (!count) return MFH_OK;
-  const uint32_t KW = 2 * (c->P.logq / 64);
-  if (maglen + 4 > (size_t)KW * 4) { c->err = "smudge magnitude too wide"; return MFH_EINVAL; }
+  const uint32_t KW = ct_geom(c).KW;
+  if (int rc0 = batch_args_check(c, ct_geom(c), kNoStride, nullptr, 0, maglen)) return rc0;
   HIP_TRY(c, hipSetDevice(c->device));
   // u*p on the host (count is 5 per proof): schoolbook by 32-bit words, staged through pinned memory
   const size_t ub = (size_t)count * KW * 4;
   uint8_t *stage = (uint8_t *)pin_acquire(c, c->pin_smudge, ub + count);
   if (!stage) return MFH_ENOMEM;
   uint32_t *up = (uint32_t *)stage;
-  for (size_t i = 0; i < count; i++) {
-    uint64_t carry = 0;
-    for (uint32_t l = 0; l < KW; l++) {
-      uint32_t w = 0;
-      const size_t o = (size_t)l * 4;
-      if (o < maglen) memcpy(&w, h_mag + i * maglen + o, std::min<size_t>(4, maglen - o));
-      uint64_t t = (uint64_t)w * MFH_P + carry;
-      up[i * KW + l] = (uint32_t)t;
-      carry = t >> 32;
-    }
-  }
+  for (size_t i = 0; i < count; i++) mf::smudge_term(h_mag + i * maglen, maglen, KW, up + i * KW);
   memcpy(stage + ub, h_sign, count);
   int rc = aux_reserve(c, ub + count);
   if (rc) return rc;

@@ -368,7 +368,7 @@ uint32_t mfh_lanes_per_value(const mfh_ctx *c) { return c ? (64 * (c->P.logq / 6
 int mfh_ct_to_lanes(mfh_ctx *c, const uint64_t *d_cts, size_t count, uint64_t *d_lanes) {
   if (!c || !d_cts || !d_lanes) return MFH_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t L = (c->P.logq + 63) / 64, K = c->P.logq / 64, NL = mfh_lanes_per_value(c);
+  const uint32_t L = ct_geom(c).L, K = c->P.logq / 64, NL = mfh_lanes_per_value(c);
   const uint64_t nvalues = (uint64_t)count * (c->P.n + 1);
   if (!nvalues) return MFH_OK;
   hipLaunchKernelGGL(k_ct_to_lanes, dim3((uint32_t)((nvalues * NL + 255) / 256)), dim3(256), 0, c->stream, d_cts, nvalues, L, K, NL, d_lanes);
@@ -379,7 +379,7 @@ int mfh_ct_to_lanes(mfh_ctx *c, const uint64_t *d_cts, size_t count, uint64_t *d
 int mfh_ct_from_lanes(mfh_ctx *c, const uint64_t *d_lanes, size_t count, uint64_t *d_cts) {
   if (!c || !d_cts || !d_lanes) return MFH_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t L = (c->P.logq + 63) / 64, K = c->P.logq / 64, NL = mfh_lanes_per_value(c);
+  const uint32_t L = ct_geom(c).L, K = c->P.logq / 64, NL = mfh_lanes_per_value(c);
   const uint64_t nvalues = (uint64_t)count * (c->P.n + 1);
   if (!nvalues) return MFH_OK;
   hipLaunchKernelGGL(k_ct_from_lanes, dim3((uint32_t)((nvalues + 255) / 256)), dim3(256), 0, c->stream, d_lanes, nvalues, L, K, NL, d_cts);
@@ -396,7 +396,7 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
   std::vector<uint8_t> priv;  // the witness bits with the statement's cleared
   const uint8_t *const h_stmt = h_witness_bits;
   if (lu) {
-    priv.assign(h_witness_bits, h_witness_bits + (c->P.m + 6) / 8);
+    priv.assign(h_witness_bits, h_witness_bits + ct_geom(c).bstride);
     for (uint32_t i = 0; i < lu; i++) priv[i >> 3] &= (uint8_t) ~(1u << (i & 7));
     h_witness_bits = priv.data();
   }
@@ -406,9 +406,10 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
     if (rc0) return rc0;
     if ((rc0 = ssp_rows_lu_check(c, d_ssp, lu))) return rc0;
   }
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  const uint32_t L = (c->P.logq + 63) / 64, ctb = c->P.logq / 8;
-  const size_t ctl = (size_t)(n + 1) * L;
+  const uint32_t d = c->P.d, m = c->P.m;
+  const mf::CtGeom G = ct_geom(c);
+  const uint32_t ctb = G.ctb;
+  const size_t ctl = G.ctl;
   HIP_TRY(c, hipSetDevice(c->device));
   // prover scratch: w, v, h (d each), cw (m), the statement bits (lu < m bits)
   const size_t pwords = (size_t)3 * d + m + (m + 31) / 32;
@@ -419,8 +420,8 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
            *pi_b_w = d_partial + 4 * ctl;
   // this rank's contiguous share of each region's rows
   auto share = [&](uint32_t rows, uint32_t &lo, uint32_t &cnt) {
-    lo = (uint32_t)((uint64_t)rows * rank / world);
-    cnt = (uint32_t)((uint64_t)rows * (rank + 1) / world) - lo;
+    const mf::Share sh = mf::row_share(rows, rank, world);
+    lo = (uint32_t)sh.lo, cnt = (uint32_t)sh.cnt;
   };
 
   // The witness pass (HBM-bound over the SSP) and the polynomial step (a chain of short launches) do not depend on b_w, and b_w's
@@ -455,7 +456,7 @@ static int prove_partial_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_
   for (uint32_t i = 1; i < m; i++) h_cw[i] = (h_witness_bits[(i - 1) >> 3] >> ((i - 1) & 7)) & 1;
   HIP_TRY(c, hipMemcpyAsync(cw, h_cw, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_cw);
-  const uint64_t ctr_ct = (uint64_t)ctb * n;
+  const uint64_t ctr_ct = G.ctr_ct;
   uint32_t lo, cnt;
   share(m, lo, cnt);
   const void *res = c->resident_rows;
@@ -537,7 +538,7 @@ int mfh_prove_partial_w(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_s
 
 int mfh_prove_finish(mfh_ctx *c, uint64_t *d_proof, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign) {
   if (!c || !d_proof || !h_smudge_mag || !h_smudge_sign) return MFH_EINVAL;
-  const size_t ctl = (size_t)(c->P.n + 1) * ((c->P.logq + 63) / 64);
+  const size_t ctl = ct_geom(c).ctl;
   // smudging: h, hat_h, hat_v, v_w, then v_w AGAIN; b_w is never smudged (src/snark.c:185-189)
   int rc = mfh_ct_smudge(c, d_proof, 4, h_smudge_mag, maglen, h_smudge_sign);
   if (rc) return rc;
@@ -610,17 +611,17 @@ struct BatchScratch {
   int64_t *SCZ;
   size_t nslots;
 };
-int batch_scratch(mfh_ctx *c, uint32_t nproofs, uint32_t whv /* w | h | v areas of a super-group */, BatchScratch &B, uint32_t ncw = 1,
+int batch_scratch(mfh_ctx *c, const mf::CtGeom &G, uint32_t nproofs, uint32_t whv /* w | h | v areas of a super-group */, BatchScratch &B, uint32_t ncw = 1,
                   uint32_t nsmudge = 0 /* proofs whose smudging terms are staged */) {
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
+  const uint32_t d = c->P.d;
+  const size_t ctl = G.ctl;
   const size_t nsg = ((size_t)nproofs + BSG_REGEN - 1) / BSG_REGEN;  // (the smaller super-group size: never fewer slots than a call uses)
   B.nslots = nsg * (2 + 2 * ((BSG + BG - 1) / BG));  // multi-vector launches of the call
   const size_t whv_b = (size_t)whv * 3 * BSG * d * 4;
-  const size_t packed = ((size_t)BSG * ((m + 6) / 8) + 3) & ~(size_t)3;
+  const size_t packed = ((size_t)BSG * G.bstride + 3) & ~(size_t)3;
   const size_t cw_b = packed + (size_t)BSG * 4;
   const size_t cw_pad = (cw_b + 255) & ~(size_t)255;
-  const size_t KW = 2 * (c->P.logq / 64);
+  const size_t KW = G.KW;
   const size_t sm_b = ((size_t)nsmudge * 5 * (KW * 4 + 1) + 255) & ~(size_t)255;
   const size_t need = whv_b + cw_pad * ncw + sm_b + 256 + ctl * 8 + B.nslots * 2048;
   if (int rc = dev_reserve(c, c->d_batch, need, DevWait::device)) return rc;
@@ -639,11 +640,11 @@ int batch_scratch(mfh_ctx *c, uint32_t nproofs, uint32_t whv /* w | h | v areas 
 // Everything the host contributes to a call, staged in one pinned buffer and copied once, on c->stream: per super-group the packed
 // witness bits (the m - 1 bits of a statement repacked densely) and the deltas, then the smudging terms u p of all five draws of every
 // proof (schoolbook by 32-bit words: src/lwe.c:65-76) and their signs.  B was sized with ncw = super-groups, nsmudge = nproofs.
-int batch_stage_host(mfh_ctx *c, const BatchScratch &B, uint32_t nproofs, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
+// (maglen: checked by the caller, batch_args_check)
+int batch_stage_host(mfh_ctx *c, const mf::CtGeom &G, const BatchScratch &B, uint32_t nproofs, const uint8_t *h_bits, size_t bits_stride, const uint32_t *h_delta,
                      const uint8_t *h_mag, size_t maglen, const uint8_t *h_sign, uint32_t SG) {
-  const uint32_t m = c->P.m, nsg = (nproofs + SG - 1) / SG;
-  const uint32_t bstride = (m + 6) / 8, KW = 2 * (c->P.logq / 64);
-  if (maglen + 4 > (size_t)KW * 4) { c->err = "smudge magnitude too wide"; return MFH_EINVAL; }
+  const uint32_t nsg = (nproofs + SG - 1) / SG;
+  const uint32_t bstride = G.bstride, KW = G.KW;
   const size_t total = (size_t)((uint8_t *)B.SMS - B.CW) + (size_t)nproofs * 5;
   uint8_t *st = (uint8_t *)pin_acquire(c, c->pin_cw, total);
   if (!st) return MFH_ENOMEM;
@@ -654,17 +655,7 @@ int batch_stage_host(mfh_ctx *c, const BatchScratch &B, uint32_t nproofs, const 
     memcpy(a + B.cw_delta_off, h_delta + s0, (size_t)sg * 4);
   }
   uint32_t *up = (uint32_t *)(st + ((uint8_t *)B.SMU - B.CW));
-  for (size_t i = 0; i < (size_t)nproofs * 5; i++) {
-    uint64_t carry = 0;
-    for (uint32_t l = 0; l < KW; l++) {
-      uint32_t w = 0;
-      const size_t o = (size_t)l * 4;
-      if (o < maglen) memcpy(&w, h_mag + i * maglen + o, std::min<size_t>(4, maglen - o));
-      const uint64_t t = (uint64_t)w * P32 + carry;
-      up[i * KW + l] = (uint32_t)t;
-      carry = t >> 32;
-    }
-  }
+  for (size_t i = 0; i < (size_t)nproofs * 5; i++) mf::smudge_term(h_mag + i * maglen, maglen, KW, up + i * KW);
   memcpy(st + ((uint8_t *)B.SMS - B.CW), h_sign, (size_t)nproofs * 5);
   HIP_TRY(c, hipMemcpyAsync(B.CW, st, total, hipMemcpyHostToDevice, c->stream));
   pin_release(c, c->pin_cw);
@@ -697,8 +688,8 @@ __global__ void k_smudge_batch(uint64_t *cts, uint32_t n, uint32_t L, uint32_t K
   }
   for (uint32_t l = KW; l < 2 * L; l++) b[l] = 0;
 }
-int batch_smudge_staged(mfh_ctx *c, const BatchScratch &B, uint64_t *sproofs, uint32_t s0, uint32_t sg) {
-  const uint32_t L = (c->P.logq + 63) / 64, KW = 2 * (c->P.logq / 64);
+int batch_smudge_staged(mfh_ctx *c, const mf::CtGeom &G, const BatchScratch &B, uint64_t *sproofs, uint32_t s0, uint32_t sg) {
+  const uint32_t L = G.L, KW = G.KW;
   const uint32_t *up = B.SMU + (size_t)s0 * 5 * KW;
   const uint8_t *sn = B.SMS + (size_t)s0 * 5;
   hipLaunchKernelGGL(k_smudge_batch, dim3((sg * 4 + 63) / 64), dim3(64), 0, c->stream, sproofs, c->P.n, L, KW, up, sn, sg * 4, 4u, 0u, 0u);
@@ -802,16 +793,14 @@ struct BatchCoef {
 // proof: the term is added once, after the ranks' shares have been summed).  wait_ev: awaited before the S / AS launches (the chain).
 // accumulate: add onto what sproofs holds (mod 2^(64K)) -- the row slabs of mfh_prove_batch when the image does not fit HBM.
 // b_w of a super-group on c->stream from the staged area d_cw (packed bits, then -- has_delta -- the deltas at B.cw_delta_off)
-int batch_bw(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world, uint32_t sg, const uint8_t *d_cw, bool has_delta, uint64_t *sproofs,
-             const BatchScratch &B, size_t &slot, int accumulate) {
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  const uint32_t ctb = c->P.logq / 8;
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
-  const uint64_t ctr_ct = (uint64_t)ctb * n;
-  const uint64_t pstride = 5 * ctl;
-  const uint32_t lo = (uint32_t)((uint64_t)m * rank / world), cnt = (uint32_t)((uint64_t)m * (rank + 1) / world) - lo;
-  const uint32_t bstride = (m + 6) / 8;
-  MmIo io_bw = {{nullptr, nullptr}, sg, {sproofs + 4 * ctl, nullptr}, sg, pstride, d_cw, bstride, B.SCZ + 256 * slot++};
+int batch_bw(mfh_ctx *c, const mf::CtGeom &G, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world, uint32_t sg, const uint8_t *d_cw, bool has_delta,
+             uint64_t *sproofs, const BatchScratch &B, size_t &slot, int accumulate) {
+  const uint32_t d = c->P.d;
+  const uint32_t ctb = G.ctb;
+  const uint64_t ctr_ct = G.ctr_ct;
+  const mf::Share sh = mf::row_share(c->P.m, rank, world);
+  const uint32_t lo = (uint32_t)sh.lo, cnt = (uint32_t)sh.cnt;
+  MmIo io_bw = {{nullptr, nullptr}, sg, {sproofs + 4 * G.ctl, nullptr}, sg, G.pstride, d_cw, G.bstride, B.SCZ + 256 * slot++};
   io_bw.bits_row0 = lo;
   if (has_delta) {  // + delta_b ct_t (src/snark.c:143-145) in the launch's epilogue
     io_bw.add_ct = B.CT_T;
@@ -820,23 +809,24 @@ int batch_bw(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world,
   return eval_rows_multi_io(c, ctr_ct * ((uint64_t)2 * d + lo), cnt, d_crs_c8 + ((size_t)2 * d + lo) * ctb, io_bw, sg, 1, accumulate);
 }
 // d_cw: the super-group's staged area (batch_stage_host), or nullptr: staged here from h_bits / h_delta.
-int batch_rows_supergroup(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world, uint32_t sg, const uint8_t *h_bits,
+int batch_rows_supergroup(mfh_ctx *c, const mf::CtGeom &G, const uint8_t *d_crs_c8, uint32_t rank, uint32_t world, uint32_t sg, const uint8_t *h_bits,
                           size_t bits_stride, const BatchCoef &co, uint64_t *sproofs, const BatchScratch &B, size_t &slot,
                           const uint32_t *h_delta, hipEvent_t wait_ev, int accumulate = 0, const uint8_t *d_cw = nullptr, bool bw_done = false,
                           uint32_t ws_slot = 0 /* early mode: which half of ws3 */, bool *tail_on_side = nullptr /* early mode: the epilogues were queued on c->side, not joined */) {
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  const uint32_t ctb = c->P.logq / 8;
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
-  const uint64_t ctr_ct = (uint64_t)ctb * n;
-  const uint64_t pstride = 5 * ctl;  // component `slot` of consecutive proofs (struct order h | hat_h | hat_v | v_w | b_w)
+  const uint32_t d = c->P.d;
+  const uint32_t ctb = G.ctb;
+  const size_t ctl = G.ctl;
+  const uint64_t ctr_ct = G.ctr_ct;
+  const uint64_t pstride = G.pstride;  // component `slot` of consecutive proofs (struct order h | hat_h | hat_v | v_w | b_w)
   hipStream_t const main_stream = c->stream, side_stream = c->side;
-  const uint32_t loS = (uint32_t)((uint64_t)d * rank / world), cS = (uint32_t)((uint64_t)d * (rank + 1) / world) - loS;
+  const mf::Share shS = mf::row_share(d, rank, world);
+  const uint32_t loS = (uint32_t)shS.lo, cS = (uint32_t)shS.cnt;
   int rc = MFH_OK;
   if (!bw_done) {
     if (!d_cw) {
       // ---- b_w: the packed bits travel as they are (2.7 KB per statement at the default size; the digit kernel unpacks them), the deltas
       // behind them, through one pinned staging buffer and one copy
-      const uint32_t bstride = (m + 6) / 8;  // the m - 1 bits of a statement, repacked densely
+      const uint32_t bstride = G.bstride;  // the m - 1 bits of a statement, repacked densely
       const size_t staged = B.cw_delta_off + (h_delta ? (size_t)sg * 4 : 0);
       uint8_t *h_cw = (uint8_t *)pin_acquire(c, c->pin_cw, staged);
       if (!h_cw) return MFH_ENOMEM;
@@ -846,7 +836,7 @@ int batch_rows_supergroup(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, ui
       pin_release(c, c->pin_cw);
       d_cw = B.CW;
     }
-    rc = batch_bw(c, d_crs_c8, rank, world, sg, d_cw, h_delta != nullptr, sproofs, B, slot, accumulate);
+    rc = batch_bw(c, G, d_crs_c8, rank, world, sg, d_cw, h_delta != nullptr, sproofs, B, slot, accumulate);
     if (rc) return rc;
   }
   if (wait_ev) HIP_TRY(c, hipStreamWaitEvent(main_stream, wait_ev, 0));
@@ -921,11 +911,8 @@ int batch_rows_supergroup(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, ui
       rc = mms_stream(c, plan[r]);
       if (rc) return rc;
       if (early) {  // epilogue on the side stream, behind this round's launch only
-        while (c->ev_round.size() <= r) {
-          hipEvent_t e;
-          HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          c->ev_round.push_back(e);
-        }
+        rc = events_grow(c, c->ev_round, r + 1);
+        if (rc) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_round[r], main_stream));
         HIP_TRY(c, hipStreamWaitEvent(side_stream, c->ev_round[r], 0));
         OnStream side(c, side_stream);
@@ -992,10 +979,10 @@ int batch_smudge(mfh_ctx *c, uint64_t *sproofs, uint32_t sg, const uint8_t *h_sm
 }
 
 // ct_t = the BT row as a ciphertext (eval_poly of one row with coefficient 1): b_w's delta * ct_t term (src/snark.c:143-145)
-int batch_ct_t(mfh_ctx *c, const uint8_t *d_crs_c8, const BatchScratch &B) {
-  const uint32_t d = c->P.d, ctb = c->P.logq / 8;
+int batch_ct_t(mfh_ctx *c, const mf::CtGeom &G, const uint8_t *d_crs_c8, const BatchScratch &B) {
+  const uint32_t d = c->P.d;
   HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)B.ONE, 1, 1, c->stream));
-  return mfh_eval_rows(c, (uint64_t)ctb * c->P.n * 2 * d, 1, d_crs_c8 + (size_t)2 * d * ctb, B.ONE, nullptr, B.CT_T, nullptr, 0);
+  return mfh_eval_rows(c, G.ctr_ct * 2 * d, 1, d_crs_c8 + (size_t)2 * d * G.ctb, B.ONE, nullptr, B.CT_T, nullptr, 0);
 }
 
 // More than one group and no image registered: expand this rank's row shares of the CRS once for the whole call into a transient image in
@@ -1006,8 +993,7 @@ struct ImageGuard {
   ~ImageGuard() { if (on) mfh_crs_set_resident_mm(c, nullptr); }
 };
 int batch_transient_image(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nproofs, uint32_t rank, uint32_t world, ImageGuard &guard) {
-  const uint32_t ctb = c->P.logq / 8;
-  if (c->mm_image || !c->batch_image || nproofs <= BG || (((uint64_t)c->P.n * ctb) & 7)) return MFH_OK;
+  if (!mf::batch_transient(c->mm_image != nullptr, c->batch_image != 0, nproofs, BG, c->P.n, c->P.logq)) return MFH_OK;
   const size_t ib = mfh_crs_mm_share_bytes(c, rank, world);
   if (c->batch_img.cap < ib) {
     (void)batch_img_drop(c);
@@ -1043,7 +1029,8 @@ int batch_witness_stream(mfh_ctx *c, const uint32_t *d_ssp, const MmRegion &reg,
     OnStream chain(c, chain_stream);
     img = ssp_image(c, d_ssp);
   }
-  if (!img || !mms_plan_ssp(c, img, ng, WP) || WP.cd_bytes != BP.cd_bytes || WP.rpc != BP.rpc || WP.nchunks != BP.nchunks) return MFH_OK;
+  // (WP's row chunks are BP's: both cut the same m rows by mf::row_chunks with the same unit and limit, which is what lets the launches share one set of digit fragments)
+  if (!img || !mms_plan_ssp(c, img, ng, WP)) return MFH_OK;
   const size_t bw_b = (mms_ws_bytes(BP) + 255) & ~(size_t)255, wp_b = (size_t)ng * WP.part_bytes, w_b = (size_t)ng * BSG * d * 4;
   if (c->wstream.cap < bw_b + wp_b + 2 * w_b) {  // (both streams read it: the whole device is awaited before it goes)
     if (c->wstream.p) {
@@ -1084,108 +1071,46 @@ int batch_witness_stream(mfh_ctx *c, const uint32_t *d_ssp, const MmRegion &reg,
   return MFH_OK;
 }
 
-// mfh_prove_batch, and with pub != nullptr mfh_prove_batch_public (h_witness_bits then without the statement bits)
-int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
-                     size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
-                     uint64_t *d_proofs, const PubBatch *pub) {
-  if (!c) return MFH_EINVAL;
-  if (!nproofs) return MFH_OK;
-  if (!d_crs_c8 || !h_witness_bits || !h_delta || !h_smudge_mag || !h_smudge_sign || !d_proofs) return MFH_EINVAL;
-  if (c->resident_rows) { c->err = "mfh_prove_batch regenerates the keystream: clear the resident CRS image first"; return MFH_EUNSUPPORTED; }
-  if (c->mm_image && c->mm_world != 1) { c->err = "mfh_prove_batch: the registered matrix-core image holds one rank's row shares (use mfh_prove_batch_partial)"; return MFH_EINVAL; }
+int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits, size_t bits_stride,
+                     const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign, uint64_t *d_proofs, const PubBatch *pub);
+
+// One mfh_prove_batch call: its arguments, what is decided before anything is queued (G, R: batch_plan.hpp), its scratch and streams, and the three regimes, of which
+// a call runs exactly one:
+//   prove_batch_subcalls   the w | h | v areas of the whole call would not fit beside the row slabs: the call again, per R.sub_sg super-groups
+//   prove_batch_slabs      the image does not fit HBM (or mfh_set_batch_slabs): all chains first, then the CRS rows slab by slab for every super-group
+//   prove_batch_resident   the image (the caller's, or the call's transient one) is in HBM, or every group regenerates the keystream: super-group by super-group
+struct BatchCall {
+  mfh_ctx *c;
+  const uint8_t *d_crs_c8;
+  const uint32_t *d_ssp;
+  uint32_t nproofs;
+  const uint8_t *h_witness_bits;
+  size_t bits_stride;
+  const uint32_t *h_delta;
+  const uint8_t *h_smudge_mag;
+  size_t maglen;
+  const uint8_t *h_smudge_sign;
+  uint64_t *d_proofs;
+  const PubBatch *pub;
+  mf::CtGeom G;
   mf::SspSrc src;
-  {
-    int rc0 = ssp_src(c, d_ssp, src, true);  // (the row SSP: batch_chain_launch's witness pass interpolates)
-    if (rc0) return rc0;
-    if (pub && (rc0 = ssp_rows_lu_check(c, d_ssp, pub->lu))) return rc0;
-  }
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  if (bits_stride < (m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
-  for (uint32_t b = 0; b < nproofs; b++)
-    if (h_delta[b] >= P32) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  // (checked before any GPU work in every regime: the row-slab path smudges only after all its launches)
-  if (maglen + 4 > (size_t)(c->P.logq / 64) * 8) { c->err = "smudge magnitude too wide"; return MFH_EINVAL; }
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
-  HIP_TRY(c, hipSetDevice(c->device));
-  // The chain (witness pass + polynomial step) of a super-group runs on its own stream: the first one beside the CRS expansion, the chain
-  // of super-group k + 1 after the row work of super-group k (beside its smudging), into the other of two w | h | v areas.  Queued further
-  // ahead (one area per super-group, chains beside the previous super-groups' streaming launches) the call takes the same time --
-  // measured with 2, 3, 4, 8 areas: 88.2, 88.7, 89.4, 89.9 ms per 992 statements -- because every kernel of the call fills the CUs it
-  // gets (one k_mmstream workgroup owns a CU's registers and LDS, k_expand_mm runs 8 waves per SIMD): concurrent streams time-share
-  // the GPU and the work is conserved.  In turn keeps the streaming launches' durations clean.
-  // super-group size: 255 statements when the row work streams an image (the caller's, or the call's transient one: groups of 63 / 64 coefficient vectors
-  // with a shared ones column), 248 = 8 x 31 when every group regenerates the keystream
-  const bool will_stream = c->mm_image || (c->batch_image && nproofs > BG && (((uint64_t)n * (c->P.logq / 8)) & 7) == 0);
-  const uint32_t SG = will_stream ? BSG : BSG_REGEN;
-  const uint32_t nsg = (nproofs + SG - 1) / SG;
-  // Row slabs.  When the call would stream an image that does not fit HBM (363 GB at 2^20 constraints), the CRS rows are cut into
-  // `nsl` slabs -- exactly the row shares of the multi-GPU prover, one after the other on this GPU: a slab's image is expanded once and
-  // streamed for EVERY group of the call (results accumulated mod 2^(64K)), so the keystream is generated once per call instead of
-  // once per group of 31 proofs.  All chains run first (one w | h | v area per super-group).
-  uint32_t nsl = 1;
-  const uint32_t ctb0 = c->P.logq / 8;
-  const bool slabs_ok = !c->mm_image && c->batch_image && nproofs > BG && (((uint64_t)n * ctb0) & 7) == 0;
-  if (slabs_ok && c->batch_slabs) nsl = std::min(c->batch_slabs, std::max(1u, std::min(d, m)));  // forced (tests, tuning)
-  else if (slabs_ok) {
-    size_t mem_free = 0, mem_total = 0;
-    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-      const size_t ib = mfh_crs_mm_image_bytes(c), avail = mem_free + c->batch_img.cap + c->d_batch.cap;  // (what the context holds is re-used)
-      if (ib > avail / 4 * 3) {
-        const size_t budget = std::max<size_t>(avail / 3, (size_t)1 << 30);
-        nsl = (uint32_t)std::min<size_t>(256, (ib + budget - 1) / budget);
-        const size_t area = (size_t)3 * BSG * d * 4, maxsg = std::max<size_t>(1, avail / 4 / area);
-        if (nsg > maxsg) {  // the w | h | v areas of the whole call would not fit: sub-calls of maxsg super-groups
-          const size_t ctl0 = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
-          for (uint32_t s0 = 0; s0 < nproofs; s0 += (uint32_t)maxsg * SG) {
-            const uint32_t cnt = std::min<uint32_t>((uint32_t)maxsg * SG, nproofs - s0);
-            const PubBatch sub = pub ? pub->at(s0) : PubBatch{};
-            int r = prove_batch_impl(c, d_crs_c8, d_ssp, cnt, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0,
-                                     h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5, d_proofs + (size_t)s0 * 5 * ctl0,
-                                     pub ? &sub : nullptr);
-            if (r) return r;
-          }
-          c->last_batch_sg = 0;  // (several sub-calls: no per-super-group completion to hand out; a caller drains after mfh_sync)
-          return MFH_OK;
-        }
-      }
-    }
-  }
-  const uint32_t nbuf = nsl > 1 ? nsg : 2;
-  // one completion event per super-group (mfh_prove_batch_stream_wait: a caller's copy stream drains super-group k while k + 1 runs)
-  while (c->ev_sgdone.size() < nsg) {
-    hipEvent_t e;
-    HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->ev_sgdone.push_back(e);
-  }
-  c->last_batch_sg = 0;  // (set when the whole call has been queued)
+  mf::BatchRoute R;
   BatchScratch B;
-  int rc = batch_scratch(c, nproofs, nbuf, B, nsl > 1 ? 1 : nsg, nsl > 1 ? 0 : nproofs);
-  if (rc) return rc;
-  size_t slot = 0;
-  HIP_TRY(c, hipMemsetAsync(B.SCZ, 0, B.nslots * 2048, c->stream));
-  rc = batch_streams(c);
-  if (rc) return rc;
-  while (c->ev_cdone.size() < nbuf) {
-    hipEvent_t e0, e1, e2;
-    HIP_TRY(c, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-    c->ev_cdone.push_back(e0);
-    c->ev_rdone.push_back(e1);
-    c->ev_wdone.push_back(e2);
-  }
-  hipStream_t const main_stream = c->stream, chain_stream = c->side2;
+  hipStream_t main_stream, chain_stream;
   // The streamed witness pass (batch_witness_stream): W and V of EVERY super-group are written by one launch and its epilogue at the head of the call, into areas of their
   // own (WSTREAM, VSTREAM); H keeps the two areas, and a chain is then the polynomial step only.
-  bool wroute = false;
-  uint32_t *WSTREAM = nullptr, *VSTREAM = nullptr;
-  auto whv_of = [&](uint32_t sgi, uint32_t *&W, uint32_t *&H, uint32_t *&V) {
-    W = B.WHV + (size_t)(sgi % nbuf) * 3 * BSG * d;
+  bool wroute;
+  uint32_t *WSTREAM, *VSTREAM;
+
+  void whv_of(uint32_t sgi, uint32_t *&W, uint32_t *&H, uint32_t *&V) const {
+    const uint32_t d = c->P.d;
+    W = B.WHV + (size_t)(sgi % R.nbuf) * 3 * BSG * d;
     H = W + (size_t)BSG * d;
     V = H + (size_t)BSG * d;
     if (wroute) W = WSTREAM + (size_t)sgi * BSG * d, V = VSTREAM + (size_t)sgi * BSG * d;
-  };
-  auto launch_chain = [&](uint32_t sgi) -> int {  // the chain stream has been told what to wait for
+  }
+  int launch_chain(uint32_t sgi) const {  // the chain stream has been told what to wait for
+    const uint32_t SG = R.SG, nbuf = R.nbuf;
     const uint32_t s0 = sgi * SG, sg = std::min(SG, nproofs - s0);
     uint32_t *WALL, *HALL, *VALL;
     whv_of(sgi, WALL, HALL, VALL);
@@ -1200,77 +1125,110 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     if (r) return r;
     HIP_TRY(c, hipEventRecord(c->ev_cdone[sgi % nbuf], chain_stream));
     return MFH_OK;
-  };
-  HIP_TRY(c, hipEventRecord(c->ev_chain, main_stream));  // what the caller's stream has been given so far no longer reads the scratch
-  HIP_TRY(c, hipStreamWaitEvent(chain_stream, c->ev_chain, 0));
+  }
+  int prove_batch_subcalls() const;
+  int prove_batch_slabs();
+  int prove_batch_resident();
+};
+
+int BatchCall::prove_batch_subcalls() const {
+  const uint32_t SG = R.SG;
+  const size_t maxsg = R.sub_sg;
+  for (uint32_t s0 = 0; s0 < nproofs; s0 += (uint32_t)maxsg * SG) {
+    const uint32_t cnt = std::min<uint32_t>((uint32_t)maxsg * SG, nproofs - s0);
+    const PubBatch sub = pub ? pub->at(s0) : PubBatch{};
+    int r = prove_batch_impl(c, d_crs_c8, d_ssp, cnt, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0,
+                             h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5, d_proofs + (size_t)s0 * 5 * G.ctl,
+                             pub ? &sub : nullptr);
+    if (r) return r;
+  }
+  c->last_batch_sg = 0;  // (several sub-calls: no per-super-group completion to hand out; a caller drains after mfh_sync)
+  return MFH_OK;
+}
+
+// Row slabs.  When the call would stream an image that does not fit HBM (363 GB at 2^20 constraints), the CRS rows are cut into
+// `nsl` slabs -- exactly the row shares of the multi-GPU prover, one after the other on this GPU: a slab's image is expanded once and
+// streamed for EVERY group of the call (results accumulated mod 2^(64K)), so the keystream is generated once per call instead of
+// once per group of 31 proofs.  All chains run first (one w | h | v area per super-group).
+int BatchCall::prove_batch_slabs() {
+  const uint32_t d = c->P.d, m = c->P.m, SG = R.SG, nsg = R.nsg, nbuf = R.nbuf;
+  const size_t ctl = G.ctl;
+  uint32_t nsl = R.nsl;
+  size_t slot = 0;
+  int rc = launch_chain(0);
+  if (rc) return rc;
+  for (uint32_t k = 1; k < nsg; k++) {
+    rc = launch_chain(k);
+    if (rc) return rc;
+  }
+  // The slab count was sized from the free memory BEFORE this call's own scratch (w | h | v areas of every super-group, digit and partial-product areas) was
+  // reserved; when the slab image then does not fit, halve the slabs (twice as many, up to 256) instead of giving up: the result does not depend on the count.
+  for (;;) {
+    size_t ib = 0;
+    for (uint32_t r = 0; r < nsl; r++) ib = std::max(ib, mfh_crs_mm_share_bytes(c, r, nsl));
+    if (c->batch_img.cap >= ib) break;
+    (void)batch_img_drop(c);
+    size_t mem_free = 0, mem_total = 0;
+    const bool fits = hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || ib + ((size_t)8 << 30) <= mem_free;  // (leave room for the launches' workspaces)
+    if (fits && dev_alloc(c->batch_img, ib)) break;
+    (void)hipGetLastError();
+    const uint32_t cap = std::min<uint32_t>(256u, std::max(1u, std::min(d, m)));
+    if (nsl >= cap || c->batch_slabs) { c->err = "mfh_prove_batch: no room for a row slab of the CRS image"; return MFH_ENOMEM; }
+    nsl = std::min(cap, nsl * 2);
+  }
+  rc = batch_ct_t(c, G, d_crs_c8, B);
+  if (rc) return rc;
+  ImageGuard slab{c, true};
+  for (uint32_t r = 0; r < nsl; r++) {
+    rc = mfh_crs_expand_mm_share(c, d_crs_c8, r, nsl, c->batch_img.as<uint8_t>());  // (queued behind the previous slab's launches on the caller's stream)
+    if (rc) return rc;
+    mfh_crs_set_resident_mm_share(c, c->batch_img.as<uint8_t>(), r, nsl);
+    HIP_TRY(c, hipMemsetAsync(B.SCZ, 0, B.nslots * 2048, c->stream));
+    slot = 0;
+    const uint32_t loS = (uint32_t)mf::row_share(d, r, nsl).lo;
+    for (uint32_t s0 = 0, sgi = 0; s0 < nproofs; s0 += SG, sgi++) {
+      const uint32_t sg = std::min(SG, nproofs - s0);
+      uint32_t *WALL, *HALL, *VALL;
+      whv_of(sgi, WALL, HALL, VALL);
+      const BatchCoef co = {WALL + loS, HALL + loS, VALL + loS, d};
+      rc = batch_rows_supergroup(c, G, d_crs_c8, r, nsl, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, d_proofs + (size_t)s0 * 5 * ctl, B, slot,
+                                 r == 0 ? h_delta + s0 : nullptr, r == 0 ? c->ev_cdone[sgi % nbuf] : nullptr, r > 0);
+      if (rc) return rc;
+    }
+  }
+  for (uint32_t s0 = 0; s0 < nproofs; s0 += SG) {
+    rc = batch_smudge(c, d_proofs + (size_t)s0 * 5 * ctl, std::min(SG, nproofs - s0), h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_sgdone[s0 / SG], c->stream));  // (every slab touches every proof: all super-groups complete together, at the end)
+  }
+  c->last_batch_sg = SG;
+  c->last_batch_n = nproofs;
+  return MFH_OK;
+}
+
+int BatchCall::prove_batch_resident() {
+  const uint32_t d = c->P.d, m = c->P.m, SG = R.SG, nsg = R.nsg, nbuf = R.nbuf;
+  const size_t ctl = G.ctl;
   // what the streamed witness pass asks of the call, as far as it can be told before the image question is settled: then the first chain waits for that answer
-  const bool try_ws = c->batch_witness && nsl == 1 && will_stream && !pub && d_ssp && src.dense && d % 64 == 0 && m >= 2 && nsg >= 2 && nsg <= 8 && c->batch_bw_merged &&
-                      mms_ssp_ok(c);
+  const bool try_ws = R.try_ws && d_ssp && d % 64 == 0;
+  size_t slot = 0;
+  int rc;
   if (!try_ws) {
     rc = launch_chain(0);
     if (rc) return rc;
   }
-  if (nsl > 1) {
-    for (uint32_t k = 1; k < nsg; k++) {
-      rc = launch_chain(k);
-      if (rc) return rc;
-    }
-    // The slab count was sized from the free memory BEFORE this call's own scratch (w | h | v areas of every super-group, digit and partial-product areas) was
-    // reserved; when the slab image then does not fit, halve the slabs (twice as many, up to 256) instead of giving up: the result does not depend on the count.
-    for (;;) {
-      size_t ib = 0;
-      for (uint32_t r = 0; r < nsl; r++) ib = std::max(ib, mfh_crs_mm_share_bytes(c, r, nsl));
-      if (c->batch_img.cap >= ib) break;
-      (void)batch_img_drop(c);
-      size_t mem_free = 0, mem_total = 0;
-      const bool fits = hipMemGetInfo(&mem_free, &mem_total) != hipSuccess || ib + ((size_t)8 << 30) <= mem_free;  // (leave room for the launches' workspaces)
-      if (fits && dev_alloc(c->batch_img, ib)) break;
-      (void)hipGetLastError();
-      const uint32_t cap = std::min<uint32_t>(256u, std::max(1u, std::min(d, m)));
-      if (nsl >= cap || c->batch_slabs) { c->err = "mfh_prove_batch: no room for a row slab of the CRS image"; return MFH_ENOMEM; }
-      nsl = std::min(cap, nsl * 2);
-    }
-    rc = batch_ct_t(c, d_crs_c8, B);
-    if (rc) return rc;
-    ImageGuard slab{c, true};
-    for (uint32_t r = 0; r < nsl; r++) {
-      rc = mfh_crs_expand_mm_share(c, d_crs_c8, r, nsl, c->batch_img.as<uint8_t>());  // (queued behind the previous slab's launches on the caller's stream)
-      if (rc) return rc;
-      mfh_crs_set_resident_mm_share(c, c->batch_img.as<uint8_t>(), r, nsl);
-      HIP_TRY(c, hipMemsetAsync(B.SCZ, 0, B.nslots * 2048, c->stream));
-      slot = 0;
-      const uint32_t loS = (uint32_t)((uint64_t)d * r / nsl);
-      for (uint32_t s0 = 0, sgi = 0; s0 < nproofs; s0 += SG, sgi++) {
-        const uint32_t sg = std::min(SG, nproofs - s0);
-        uint32_t *WALL, *HALL, *VALL;
-        whv_of(sgi, WALL, HALL, VALL);
-        const BatchCoef co = {WALL + loS, HALL + loS, VALL + loS, d};
-        rc = batch_rows_supergroup(c, d_crs_c8, r, nsl, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, d_proofs + (size_t)s0 * 5 * ctl, B, slot,
-                                   r == 0 ? h_delta + s0 : nullptr, r == 0 ? c->ev_cdone[sgi % nbuf] : nullptr, r > 0);
-        if (rc) return rc;
-      }
-    }
-    for (uint32_t s0 = 0; s0 < nproofs; s0 += SG) {
-      rc = batch_smudge(c, d_proofs + (size_t)s0 * 5 * ctl, std::min(SG, nproofs - s0), h_smudge_mag + (size_t)s0 * 5 * maglen, maglen, h_smudge_sign + (size_t)s0 * 5);
-      if (rc) return rc;
-      HIP_TRY(c, hipEventRecord(c->ev_sgdone[s0 / SG], c->stream));  // (every slab touches every proof: all super-groups complete together, at the end)
-    }
-    c->last_batch_sg = SG;
-    c->last_batch_n = nproofs;
-    return MFH_OK;
-  }
   ImageGuard transient{c, false};
   if (try_ws) {  // the host's inputs first: the witness launch needs them and runs beside the expansion
-    rc = batch_stage_host(c, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
+    rc = batch_stage_host(c, G, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
     if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_wstage, main_stream));
   }
   rc = batch_transient_image(c, d_crs_c8, nproofs, 0, 1, transient);
   if (rc) return rc;
   // everything the host contributes, in one copy (no host-side wait between the super-groups), staged while the GPU expands the CRS
-  if (!try_ws) rc = batch_stage_host(c, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
+  if (!try_ws) rc = batch_stage_host(c, G, B, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, SG);
   if (rc) return rc;
-  rc = batch_ct_t(c, d_crs_c8, B);
+  rc = batch_ct_t(c, G, d_crs_c8, B);
   if (rc) return rc;
   // (b_w needs nothing of the chain and nothing needs b_w before the call ends, so all b_w launches of a call -- HBM-bound passes over the
   // BT+BV image -- could run in the background under the matrix-core bound S / AS launches.  Built and measured: on an unrestricted side
@@ -1280,10 +1238,8 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
   // for its super-group's turn, and 4 - 8 groups over the BT+BV image share its fragments in the XCDs' L2s like the S / AS groups of a super-group do (one group
   // per launch is HBM-bound at 3.4 TB/s: 0.9 ms per super-group).  mfh_set_batch_bw(ctx, 0) restores one launch per super-group.
   bool bw_done = false;
-  if (c->batch_bw_merged && nsg > 1 && mm_image_covers(c, (uint64_t)ctb0 * n * 2 * d, m)) {
-    const uint64_t ctr_ct = (uint64_t)ctb0 * n, pstride = 5 * ctl;
-    const uint32_t bstride = (m + 6) / 8;
-    const MmRegion reg = {ctr_ct * 2 * d, d_crs_c8 + (size_t)2 * d * ctb0};
+  if (c->batch_bw_merged && nsg > 1 && mm_image_covers(c, G.ctr_ct * 2 * d, m)) {
+    const MmRegion reg = {G.ctr_ct * 2 * d, d_crs_c8 + (size_t)2 * d * G.ctb};
     for (uint32_t g0 = 0; g0 < nsg; g0 += 8) {
       MmIo ios[8];
       uint32_t nvs[8];
@@ -1291,7 +1247,7 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
       for (uint32_t k = 0; k < ng; k++) {
         const uint32_t sgi = g0 + k, s0 = sgi * SG, sg = std::min(SG, nproofs - s0);
         const uint8_t *d_cw = B.CW + (size_t)sgi * B.cw_stride;
-        ios[k] = MmIo{{nullptr, nullptr}, sg, {d_proofs + (size_t)s0 * 5 * ctl + 4 * ctl, nullptr}, sg, pstride, d_cw, bstride, B.SCZ + 256 * slot++};
+        ios[k] = MmIo{{nullptr, nullptr}, sg, {d_proofs + (size_t)s0 * 5 * ctl + 4 * ctl, nullptr}, sg, G.pstride, d_cw, G.bstride, B.SCZ + 256 * slot++};
         ios[k].add_ct = B.CT_T;  // + delta_b ct_t (src/snark.c:143-145) in the epilogue
         ios[k].add_scale = (const uint32_t *)(d_cw + B.cw_delta_off);
         nvs[k] = sg;
@@ -1335,7 +1291,7 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     if (!wroute) HIP_TRY(c, hipStreamWaitEvent(main_stream, c->ev_wdone[sgi % nbuf], 0));
     // the multi-vector launches read their coefficient vectors where the polynomial step left them and write the proof structs in place (MmIo)
     bool on_side = false;
-    rc = batch_rows_supergroup(c, d_crs_c8, 0, 1, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, sproofs, B, slot, h_delta + s0,
+    rc = batch_rows_supergroup(c, G, d_crs_c8, 0, 1, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, sproofs, B, slot, h_delta + s0,
                                c->ev_cdone[sgi % nbuf], 0, B.CW + (size_t)sgi * B.cw_stride, bw_done, sgi, early ? &on_side : nullptr);
     if (rc) return rc;
     if (early) HIP_TRY(c, hipEventRecord(c->ev_rdone[sgi % nbuf], main_stream));  // (the digit kernels were the last readers of the area)
@@ -1347,7 +1303,7 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
     }
     {
       OnStream tail(c, on_side ? c->side : main_stream);
-      rc = batch_smudge_staged(c, B, sproofs, s0, sg);
+      rc = batch_smudge_staged(c, G, B, sproofs, s0, sg);
       if (rc) return rc;
       HIP_TRY(c, hipEventRecord(c->ev_sgdone[sgi], c->stream));  // this super-group's proofs are final (b_w was written before the loop or by batch_rows_supergroup)
     }
@@ -1360,6 +1316,68 @@ int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp,
   c->last_batch_sg = SG;
   c->last_batch_n = nproofs;
   return MFH_OK;
+}
+
+// mfh_prove_batch, and with pub != nullptr mfh_prove_batch_public (h_witness_bits then without the statement bits): check, route, scratch and events, one regime
+int prove_batch_impl(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *d_ssp, uint32_t nproofs, const uint8_t *h_witness_bits,
+                     size_t bits_stride, const uint32_t *h_delta, const uint8_t *h_smudge_mag, size_t maglen, const uint8_t *h_smudge_sign,
+                     uint64_t *d_proofs, const PubBatch *pub) {
+  if (!c) return MFH_EINVAL;
+  if (!nproofs) return MFH_OK;
+  if (!d_crs_c8 || !h_witness_bits || !h_delta || !h_smudge_mag || !h_smudge_sign || !d_proofs) return MFH_EINVAL;
+  if (c->resident_rows) { c->err = "mfh_prove_batch regenerates the keystream: clear the resident CRS image first"; return MFH_EUNSUPPORTED; }
+  if (c->mm_image && c->mm_world != 1) { c->err = "mfh_prove_batch: the registered matrix-core image holds one rank's row shares (use mfh_prove_batch_partial)"; return MFH_EINVAL; }
+  mf::SspSrc src;
+  {
+    int rc0 = ssp_src(c, d_ssp, src, true);  // (the row SSP: batch_chain_launch's witness pass interpolates)
+    if (rc0) return rc0;
+    if (pub && (rc0 = ssp_rows_lu_check(c, d_ssp, pub->lu))) return rc0;
+  }
+  BatchCall k{c, d_crs_c8, d_ssp, nproofs, h_witness_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs, pub, ct_geom(c), src};
+  // (the magnitudes are checked before any GPU work in every regime: the row-slab path smudges only after all its launches)
+  if (int rc0 = batch_args_check(c, k.G, bits_stride, h_delta, nproofs, maglen)) return rc0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // The chain (witness pass + polynomial step) of a super-group runs on its own stream: the first one beside the CRS expansion, the chain
+  // of super-group k + 1 after the row work of super-group k (beside its smudging), into the other of two w | h | v areas.  Queued further
+  // ahead (one area per super-group, chains beside the previous super-groups' streaming launches) the call takes the same time --
+  // measured with 2, 3, 4, 8 areas: 88.2, 88.7, 89.4, 89.9 ms per 992 statements -- because every kernel of the call fills the CUs it
+  // gets (one k_mmstream workgroup owns a CU's registers and LDS, k_expand_mm runs 8 waves per SIMD): concurrent streams time-share
+  // the GPU and the work is conserved.  In turn keeps the streaming launches' durations clean.
+  // The route (mf::batch_route).  Super-group size: 255 statements when the row work streams an image (the caller's, or the call's transient one: groups of 63 / 64
+  // coefficient vectors with a shared ones column), 248 = 8 x 31 when every group regenerates the keystream.  Free memory is asked only where the route looks at it.
+  mf::BatchRouteIn in{};
+  in.nproofs = nproofs, in.d = c->P.d, in.m = c->P.m, in.n = c->P.n, in.logq = c->P.logq;
+  in.has_mm_image = c->mm_image != nullptr, in.batch_image = c->batch_image != 0, in.batch_slabs = c->batch_slabs;
+  in.batch_witness = c->batch_witness != 0, in.batch_bw_merged = c->batch_bw_merged != 0, in.has_pub = pub != nullptr, in.ssp_dense = src.dense != nullptr;
+  in.mms_ssp_ok = mms_ssp_ok(c);
+  in.BG = BG, in.BSG = BSG, in.BSG_REGEN = BSG_REGEN;
+  if (!c->batch_slabs && mf::batch_transient(in.has_mm_image, in.batch_image, nproofs, BG, in.n, in.logq)) {
+    size_t mem_free = 0, mem_total = 0;
+    in.mem_ok = hipMemGetInfo(&mem_free, &mem_total) == hipSuccess;
+    in.image_bytes = mfh_crs_mm_image_bytes(c);
+    in.avail = mem_free + c->batch_img.cap + c->d_batch.cap;  // (what the context holds is re-used)
+  }
+  k.R = mf::batch_route(in);
+  if (k.R.sub_sg) return k.prove_batch_subcalls();
+  const uint32_t nsg = k.R.nsg, nsl = k.R.nsl, nbuf = k.R.nbuf;
+  // one completion event per super-group (mfh_prove_batch_stream_wait: a caller's copy stream drains super-group k while k + 1 runs)
+  int rc = events_grow(c, c->ev_sgdone, nsg);
+  if (rc) return rc;
+  c->last_batch_sg = 0;  // (set when the whole call has been queued)
+  rc = batch_scratch(c, k.G, nproofs, nbuf, k.B, nsl > 1 ? 1 : nsg, nsl > 1 ? 0 : nproofs);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(k.B.SCZ, 0, k.B.nslots * 2048, c->stream));
+  rc = batch_streams(c);
+  if (rc) return rc;
+  // per w | h | v area: its chain done / the area read / its witness pass done
+  rc = events_grow(c, c->ev_cdone, nbuf);
+  if (!rc) rc = events_grow(c, c->ev_rdone, nbuf);
+  if (!rc) rc = events_grow(c, c->ev_wdone, nbuf);
+  if (rc) return rc;
+  k.main_stream = c->stream, k.chain_stream = c->side2;
+  HIP_TRY(c, hipEventRecord(c->ev_chain, k.main_stream));  // what the caller's stream has been given so far no longer reads the scratch
+  HIP_TRY(c, hipStreamWaitEvent(k.chain_stream, c->ev_chain, 0));
+  return nsl > 1 ? k.prove_batch_slabs() : k.prove_batch_resident();
 }
 
 }  // namespace
@@ -1380,8 +1398,8 @@ int mfh_prove_batch_public(mfh_ctx *c, const uint8_t *d_crs_c8, const uint32_t *
   if (!lu) return mfh_prove_batch(c, d_crs_c8, d_ssp, nproofs, h_bits, bits_stride, h_delta, h_smudge_mag, maglen, h_smudge_sign, d_proofs);
   if (!nproofs) return MFH_OK;
   if (!h_bits) return MFH_EINVAL;
-  const uint32_t m = c->P.m, bstride = (m + 6) / 8, ub = (lu + 7) / 8;
-  if (bits_stride < bstride) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  const uint32_t bstride = ct_geom(c).bstride, ub = (lu + 7) / 8;
+  if (int rc0 = batch_args_check(c, ct_geom(c), bits_stride, nullptr, 0, 0)) return rc0;
   // the private witness (statement bits cleared): what the witness GEMM and the b_w launches see, staged as mfh_prove_batch stages its bits
   std::vector<uint8_t> priv((size_t)nproofs * bstride), pubb;
   std::vector<uint32_t> zero;
@@ -1432,10 +1450,8 @@ int mfh_batch_chain(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, const uin
   mf::SspSrc src;
   int rc = ssp_src(c, d_ssp, src, true);
   if (rc) return rc;
-  const uint32_t d = c->P.d, m = c->P.m;
-  if (bits_stride < (m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
-  for (uint32_t b = 0; b < nstmt; b++)
-    if (h_delta[b] >= P32) { c->err = "delta must be < p"; return MFH_EINVAL; }
+  const uint32_t d = c->P.d;
+  if ((rc = batch_args_check(c, ct_geom(c), bits_stride, h_delta, nstmt, 0))) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   for (uint32_t s0 = 0; s0 < nstmt; s0 += BSG) {
     const size_t o = (size_t)s0 * d;
@@ -1454,7 +1470,7 @@ int mfh_batch_witness_cols(mfh_ctx *c, const uint32_t *d_ssp, uint32_t nstmt, co
   if (!c) return MFH_EINVAL;
   if (!nstmt || !ncols) return MFH_OK;
   if (!h_witness_bits || !h_delta || !d_w) return MFH_EINVAL;
-  if (bits_stride < (c->P.m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
+  if (int rc0 = batch_args_check(c, ct_geom(c), bits_stride, nullptr, 0, 0)) return rc0;
   for (uint32_t s0 = 0; s0 < nstmt; s0 += BSG) {
     int rc = mfh_witness_poly_mm_cols(c, d_ssp, std::min(BSG, nstmt - s0), h_witness_bits + (size_t)s0 * bits_stride, bits_stride, h_delta + s0, col0, ncols,
                                       d_w + (size_t)s0 * w_stride, w_stride);
@@ -1493,14 +1509,13 @@ int mfh_prove_batch_partial(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, 
     c->err = "the registered matrix-core image holds the row shares of a different (rank, world)";
     return MFH_EINVAL;
   }
-  const uint32_t d = c->P.d, m = c->P.m, n = c->P.n;
-  const uint32_t cS = (uint32_t)((uint64_t)d * (rank + 1) / world) - (uint32_t)((uint64_t)d * rank / world);
-  if (bits_stride < (m + 6) / 8) { c->err = "bits_stride shorter than the m - 1 witness bits"; return MFH_EINVAL; }
-  if (coef_stride < cS) { c->err = "coef_stride shorter than the rank's share of the S / AS rows"; return MFH_EINVAL; }
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
+  const mf::CtGeom G = ct_geom(c);
+  if (int rc0 = batch_args_check(c, G, bits_stride, nullptr, 0, 0)) return rc0;
+  if (coef_stride < mf::row_share(c->P.d, rank, world).cnt) { c->err = "coef_stride shorter than the rank's share of the S / AS rows"; return MFH_EINVAL; }
+  const size_t ctl = G.ctl;
   HIP_TRY(c, hipSetDevice(c->device));
   BatchScratch B;
-  int rc = batch_scratch(c, nstmt, 0, B);
+  int rc = batch_scratch(c, G, nstmt, 0, B);
   if (rc) return rc;
   size_t slot = 0;
   HIP_TRY(c, hipMemsetAsync(B.SCZ, 0, B.nslots * 2048, c->stream));
@@ -1513,7 +1528,7 @@ int mfh_prove_batch_partial(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t rank, 
     const uint32_t sg = std::min(BSG, nstmt - s0);
     const uint64_t o = (uint64_t)s0 * coef_stride;
     const BatchCoef co = {d_w + o, d_h + o, d_v + o, coef_stride};
-    rc = batch_rows_supergroup(c, d_crs_c8, rank, world, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, d_partial + (size_t)s0 * 5 * ctl, B,
+    rc = batch_rows_supergroup(c, G, d_crs_c8, rank, world, sg, h_witness_bits + (size_t)s0 * bits_stride, bits_stride, co, d_partial + (size_t)s0 * 5 * ctl, B,
                                slot, nullptr, nullptr);
     if (rc) return rc;
   }
@@ -1525,17 +1540,16 @@ int mfh_prove_batch_finish(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nstmt, 
   if (!c) return MFH_EINVAL;
   if (!nstmt) return MFH_OK;
   if (!d_crs_c8 || !h_delta || !h_smudge_mag || !h_smudge_sign || !d_proofs) return MFH_EINVAL;
-  for (uint32_t b = 0; b < nstmt; b++)
-    if (h_delta[b] >= P32) { c->err = "delta must be < p"; return MFH_EINVAL; }
-  if (maglen + 4 > (size_t)(c->P.logq / 64) * 8) { c->err = "smudge magnitude too wide"; return MFH_EINVAL; }  // before delta ct_t is added
-  const uint32_t n = c->P.n, KW = 2 * (c->P.logq / 64);
-  const size_t ctl = (size_t)(n + 1) * ((c->P.logq + 63) / 64);
+  const mf::CtGeom G = ct_geom(c);
+  if (int rc0 = batch_args_check(c, G, kNoStride, h_delta, nstmt, maglen)) return rc0;  // (the magnitudes too: before delta ct_t is added)
+  const uint32_t n = c->P.n, KW = G.KW;
+  const size_t ctl = G.ctl;
   HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t cap = std::min(nstmt, BSG);
   BatchScratch B;
-  int rc = batch_scratch(c, cap, 0, B, 1, cap);
+  int rc = batch_scratch(c, G, cap, 0, B, 1, cap);
   if (rc) return rc;
-  rc = batch_ct_t(c, d_crs_c8, B);
+  rc = batch_ct_t(c, G, d_crs_c8, B);
   if (rc) return rc;
   // Everything the host contributes to the call -- per chunk of up to BSG statements the deltas, the smudging terms u p of all five draws (schoolbook by 32-bit words,
   // src/lwe.c:65-76) and their signs -- is staged in ONE pinned buffer taken once, so the call queues its copies and kernels and returns: the host does not wait for
@@ -1551,27 +1565,16 @@ int mfh_prove_batch_finish(mfh_ctx *c, const uint8_t *d_crs_c8, uint32_t nstmt, 
     uint32_t *h_dl = (uint32_t *)(st + at), *up = h_dl + sg;
     uint8_t *sn = (uint8_t *)(up + (size_t)sg * 5 * KW);
     memcpy(h_dl, h_delta + s0, (size_t)sg * 4);
-    for (size_t i = 0; i < (size_t)sg * 5; i++) {
-      const uint8_t *mag = h_smudge_mag + ((size_t)s0 * 5 + i) * maglen;
-      uint64_t carry = 0;
-      for (uint32_t l = 0; l < KW; l++) {
-        uint32_t w = 0;
-        const size_t o = (size_t)l * 4;
-        if (o < maglen) memcpy(&w, mag + o, std::min<size_t>(4, maglen - o));
-        const uint64_t t = (uint64_t)w * P32 + carry;
-        up[i * KW + l] = (uint32_t)t;
-        carry = t >> 32;
-      }
-    }
+    for (size_t i = 0; i < (size_t)sg * 5; i++) mf::smudge_term(h_smudge_mag + ((size_t)s0 * 5 + i) * maglen, maglen, KW, up + i * KW);
     memcpy(sn, h_smudge_sign + (size_t)s0 * 5, (size_t)sg * 5);
     at += ((size_t)sg * per + 3) & ~(size_t)3;
     HIP_TRY(c, hipMemcpyAsync(B.CW, h_dl, (size_t)sg * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(B.SMU, up, (size_t)sg * 5 * KW * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(B.SMS, sn, (size_t)sg * 5, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_bw_add_delta_ct, dim3((n + 1 + 255) / 256, sg), dim3(256), 0, c->stream, sproofs, B.CT_T, (const uint32_t *)B.CW, n + 1,
-                       (c->P.logq + 63) / 64, 2 * (c->P.logq / 64));
+                       G.L, G.KW);
     HIP_TRY(c, hipGetLastError());
-    rc = batch_smudge_staged(c, B, sproofs, 0, sg);
+    rc = batch_smudge_staged(c, G, B, sproofs, 0, sg);
     if (rc) break;
   }
   pin_release(c, c->pin_smudge);

@@ -665,8 +665,8 @@ template <class F> int witness_partials(mfh_ctx *c, const mf::SspSrc &src, const
   uint32_t nall = 0;
   for (uint32_t i = 1; i < m; i++)
     if (witness_bit(h_bits, i)) rows[nall++] = i + 1;  // slot of v_i
-  const uint32_t lo = (uint32_t)((uint64_t)nall * rank / world), hi = (uint32_t)((uint64_t)nall * (rank + 1) / world);  // contiguous share of the selected rows
-  const uint32_t nsel = hi - lo, G = std::max(1u, std::min(64u, nsel / 8 + 1));
+  const mf::Share sel = mf::row_share(nall, rank, world);  // contiguous share of the selected rows
+  const uint32_t lo = (uint32_t)sel.lo, nsel = (uint32_t)sel.cnt, G = std::max(1u, std::min(64u, nsel / 8 + 1));
   const WwsCarve<2> ws({up256((size_t)m * 4), (size_t)G * d * 8});
   if (int rc = ws.reserve(c)) return rc;
   uint32_t *d_rows = ws.at<uint32_t>(c, 0);  // the selected rows | the partials
