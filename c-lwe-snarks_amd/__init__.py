@@ -106,6 +106,7 @@ EXPORTS = [
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
     "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
     "mfh_merkle_load_keys", "mfh_merkle_check_table", "mfh_merkle_grow", "mfh_merkle_grow_leaves",
+    "mfh_merkle_write_keys", "mfh_merkle_write_keys_cut",
 ]
 
 
@@ -276,6 +277,8 @@ def load_library():
         "mfh_merkle_adjust_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
         "mfh_merkle_adjust_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, sz, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_balance_sum": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, vp]),
+        "mfh_merkle_write_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, u32, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+        "mfh_merkle_write_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, u32, vp, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
         "mfh_merkle_paths_cut": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
         "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
         "mfh_merkle_range_rows": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
@@ -1093,6 +1096,94 @@ class MerkleTree:
         """adjust_key_segments with every segment's rows as 0 / 1 arrays"""
         out = self.adjust_key_segments(table, keys, amounts, cuts, sides, amount_bytes)
         head = 64 + np.ascontiguousarray(keys).shape[1] + int(amount_bytes) + 1 + int(table.shape[1])
+        return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 257 * c0),) + tuple(out[1:])
+
+    # ---- writes by key, plain and compare-and-set: the put of the keyed store
+    @staticmethod
+    def _field_values(who, what, values, nk, F):
+        """np.uint8 [nk, F], contiguous: an array of that shape, or nk bytes-likes of F bytes"""
+        try:
+            if isinstance(values, np.ndarray):
+                v = values
+            else:
+                items = [bytes(x) for x in values]
+                v = np.frombuffer(b"".join(items), dtype=np.uint8).reshape(len(items), F) if all(len(x) == F for x in items) else None
+        except (TypeError, ValueError):
+            v = None
+        if v is None or v.dtype != np.uint8 or v.shape != (nk, F):
+            raise MfhError(f"{who}: {what} are np.uint8 [nk, hi - lo] or nk bytes-likes of hi - lo bytes, one a step")
+        return np.ascontiguousarray(v)
+
+    def _write(self, who, table, keys, values, field, expect, roots=False, cut=False, cuts=None):
+        """the body of write_keys and, with cut=True, write_key_segments: mfh_merkle_write_keys[_cut] with rows, index, status and roots allocated here"""
+        c = self._ctx
+        tab, tstride, length, k = self._keys(table, keys, who)
+        nk, kb = k.shape
+        vp = ctypes.c_void_p
+        try:
+            lo, hi = field
+        except (TypeError, ValueError):
+            lo = hi = None
+        if not all(isinstance(x, (int, np.integer)) for x in (lo, hi)) or not 2 * kb <= lo < hi <= length:
+            raise MfhError(f"{who}: the field is (lo, hi) with 2 key_bytes <= lo < hi <= length")
+        lo, hi = int(lo), int(hi)
+        F = hi - lo
+        val = self._field_values(who, "values", values, nk, F)
+        exp = None if expect is None else self._field_values(who, "expectations", expect, nk, F)
+        head = 64 + kb + (F if exp is None else 2 * F) + length
+        if not cut:
+            rows = np.zeros((nk, head + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
+            out = (vp(rows.ctypes.data), rows.shape[1])
+        else:
+            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 32 * c0 + (c0 + 7) // 8, nk)
+        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots or cut else None
+        index = np.zeros(nk, dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        call = c.lib.mfh_merkle_write_keys_cut if cut else c.lib.mfh_merkle_write_keys
+        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, lo, hi, nk, vp(k.ctypes.data), kb, vp(val.ctypes.data), F,
+                    vp(exp.ctypes.data) if exp is not None else None, F, *out, vp(r.ctypes.data) if r is not None else None, vp(index.ctypes.data),
+                    vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif r is not None:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        if not cut:
+            return (rows, index, r) if roots else (rows, index)
+        return rows, self._cut_nodes(rows, r), index
+
+    def write_keys(self, table, keys, values, field, expect=None, roots=False):
+        """(rows, index): nk sequential WRITES BY KEY on an INDEXED table and this tree in one call (mfh_merkle_write_keys; waits for the stream).  Step j sets
+        bytes [lo, hi) = field of the record whose own key is keys[j] to values[j]; with `expect` only if those bytes are expect[j] at that step (compare-and-
+        set), else the whole call is refused.  A key may occur in any number of steps, and a step sees what the earlier steps left: an expectation may be one
+        that only an earlier write of the batch satisfies.  rows is np.uint8 [nk, 64 + key_bytes + F (2 F with expect) + length + 32 depth + ceil(depth / 8)],
+        F = hi - lo: row j is the packed input row of words.MerkleWrite(key_bytes, length, depth, field, expect is not None) taken from table and tree as they
+        stood before step j.  index is np.uint32 [nk]: the record's slot.  With roots=True a triple whose last element is np.uint8 [nk + 1, 32], the roots R_0 ..
+        R_nk: statement j is MerkleWrite.statement(R_j, R_j+1, keys[j], [expect[j],] values[j]).
+        table: under update_records' rules, MODIFIED IN PLACE.  keys: np.uint8 [nk, key_bytes] under locate_keys' rules, repeats allowed.  values, expect:
+        np.uint8 [nk, F] or nk bytes-likes of F bytes.  field: 2 key_bytes <= lo < hi <= length, the keys are never writable.  MfhError with the library's text,
+        table and tree untouched, when a key is not a member or a field is not what was expected at its step."""
+        return self._write("write_keys", table, keys, values, field, expect, roots)
+
+    def write_bits(self, table, keys, values, field, expect=None, roots=False):
+        """write_keys with the rows as np.uint8 [nk, 512 + 8 (key_bytes + F [+ F]) + 8 length + 257 depth] of 0 / 1: what Context.circuit_assign(prog, bits)
+        takes for words.MerkleWrite(key_bytes, length, depth, field, expect is not None)"""
+        out = self.write_keys(table, keys, values, field, expect, roots)
+        head = out[0].shape[1] - 64 - 32 * self.depth - (self.depth + 7) // 8
+        return (self._unpack(out[0], 64, head),) + tuple(out[1:])
+
+    def write_key_segments(self, table, keys, values, field, cuts, expect=None):
+        """write_keys with the path cut at levels `cuts` (mfh_merkle_write_keys_cut).  Returns (rows, nodes, index), rows and nodes shaped as
+        update_record_segments returns them: rows[0][j] is the packed input row of words.MerkleWrite(key_bytes, length, c_0, field, expect is not None) of
+        step j -- the statement itself over the subtree of height c_0, it has one pair of tops -- and rows[g][j], g >= 1, that of words.MerkleSegment(c_g -
+        c_g-1); nodes is np.uint8 [nk, G + 1, 2, 32], the published pairs of every step, (X_G, X_G') = (R_j, R_j+1): segment 0's statement is
+        MerkleWrite.statement(*nodes[j, 0], keys[j], [expect[j],] values[j]), the upper ones MerkleSegment.chain(nodes[j]).  index as write_keys gives it."""
+        return self._write("write_key_segments", table, keys, values, field, expect, cut=True, cuts=cuts)
+
+    def write_key_segment_bits(self, table, keys, values, field, cuts, expect=None):
+        """write_key_segments with every segment's rows as 0 / 1 arrays"""
+        out = self.write_key_segments(table, keys, values, field, cuts, expect)
+        lo, hi = field
+        head = 64 + np.ascontiguousarray(keys).shape[1] + (1 if expect is None else 2) * (int(hi) - int(lo)) + int(table.shape[1])
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 257 * c0),) + tuple(out[1:])
 
     def total_balance(self, table, key_bytes, amount_bytes=8):

@@ -34,6 +34,8 @@
 // the located records' balances read behind the search, then the steps below (the host's plan: merkle_transfer.hpp).
 // k_adjust_records: mfh_merkle_adjust_keys, a batch of sequential deposits and withdrawals in one call -- the search and the balances as for the transfers, ONE
 // new record a step (the host's plan: merkle_adjust.hpp), then the record updates above.  k_balance_sum, k_balance_fold: mfh_merkle_balance_sum, the supply.
+// k_field_gather, k_write_records: mfh_merkle_write_keys, a batch of sequential writes by key, plain or compare-and-set, in one call -- the search as above, for
+// the conditional form the located records' field behind it, ONE new record a step (the host's plan: merkle_write.hpp), then the record updates above.
 // k_insert_records, k_remove_records, k_transfer_records: what a batch of key steps ends with -- all 2 nk new records built in one launch from the step's plan,
 // then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
 // (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
@@ -61,6 +63,7 @@
 #include "merkle_sched.hpp"
 #include "merkle_sort.hpp"
 #include "merkle_transfer.hpp"
+#include "merkle_write.hpp"
 #include "sha256_dev.hpp"
 
 namespace {
@@ -1027,17 +1030,17 @@ __global__ __launch_bounds__(256) void k_balance_gather(const uint8_t *__restric
   balance[u] = value;
 }
 
-// unit u of a new record that differs from a table record in its balance alone (k_transfer_records, k_adjust_records): the record at byte `rec` of the table
-// as it stood before the batch, with bytes [2K, 2K + A) <- the A bytes of slot `slot` of the uploaded balances `bal` (bal_span bytes).  Bytes at or past
-// `length`: zero
-__device__ __forceinline__ uint4 rebalanced_unit(const uint8_t *__restrict__ table, int64_t rec, int64_t table_span, const uint8_t *__restrict__ bal, int64_t slot,
-                                                 int64_t bal_span, uint32_t u, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length) {
-  const int64_t o = 16 * (int64_t)u, f0 = 2 * (int64_t)key_bytes, f1 = f0 + amount_bytes;
-  const uint4 v = load_unit_within(table, rec + o, rec + min(o + 16, (int64_t)length), table_span);  // the keys and the payload behind the balance
+// unit u of a new record that differs from a table record in ONE field (k_transfer_records, k_adjust_records: the balance; k_write_records: the written
+// bytes): the record at byte `rec` of the table as it stood before the batch, with bytes [f0, f1) <- the f1 - f0 bytes at slot * pitch of the uploaded source
+// `src` (src_span bytes).  Bytes at or past `length`: zero
+__device__ __forceinline__ uint4 refielded_unit(const uint8_t *__restrict__ table, int64_t rec, int64_t table_span, const uint8_t *__restrict__ src, int64_t slot,
+                                                 int64_t pitch, int64_t src_span, uint32_t u, int64_t f0, int64_t f1, uint32_t length) {
+  const int64_t o = 16 * (int64_t)u;
+  const uint4 v = load_unit_within(table, rec + o, rec + min(o + 16, (int64_t)length), table_span);  // what stands before and behind the field
   uint4 out = merge_unit(merge_unit(make_uint4(0, 0, 0, 0), v, o, 0, f0), v, o, f1, length);
-  if (o < f1 && o + 16 > f0) {  // the balance
-    const int64_t at = slot * amount_bytes - f0;  // the record's byte x is bal's byte at + x
-    out = merge_unit(out, load_unit_within(bal, at + o, at + min(o + 16, f1), bal_span), o, f0, f1);
+  if (o < f1 && o + 16 > f0) {  // the field
+    const int64_t at = slot * pitch - f0;  // the record's byte x is src's byte at + x
+    out = merge_unit(out, load_unit_within(src, at + o, at + min(o + 16, f1), src_span), o, f0, f1);
   }
   return out;
 }
@@ -1059,7 +1062,7 @@ __global__ __launch_bounds__(256) void k_transfer_records(const uint8_t *__restr
   if (g >= 2 * nk * units) return;
   const uint32_t r = g / units, u = g - r * units;
   const int64_t rec = (int64_t)((size_t)(uint32_t)plan[3 * (r >> 1) + (r & 1)] * table_stride);
-  fresh[g] = rebalanced_unit(table, rec, table_span, bal, r, (int64_t)2 * nk * amount_bytes, u, key_bytes, amount_bytes, length);
+  fresh[g] = refielded_unit(table, rec, table_span, bal, r, amount_bytes, (int64_t)2 * nk * amount_bytes, u, 2 * (int64_t)key_bytes, 2 * (int64_t)key_bytes + amount_bytes, length);
 }
 
 // ---- mfh_merkle_adjust_keys: the nk new records of a batch of deposits and withdrawals (merkle_adjust.hpp), and mfh_merkle_balance_sum: the table's supply.
@@ -1068,7 +1071,7 @@ __global__ __launch_bounds__(256) void k_transfer_records(const uint8_t *__restr
 // aligned).  One item per record j and 16-byte unit u; the store is the whole unit.  Record j is the table's record plan[j] as it stood before the batch, with
 // bytes [2K, 2K + A) <- the account's balance right after step j, bal[j A ..] (the plan's running balance, big-endian).  An adjust changes nothing else of a
 // record, so every source is the table as it stood BEFORE the batch or the uploaded balances -- one launch, no ordering among the items, and the table is only
-// read, even where an account occurs in many steps.  The unit is k_transfer_records' (rebalanced_unit): load_unit_within fetches the 16 bytes of a source that
+// read, even where an account occurs in many steps.  The unit is k_transfer_records' (refielded_unit): load_unit_within fetches the 16 bytes of a source that
 // line up with the unit, merge_unit takes each range's bytes under per-dword byte masks, for any alignment, stride, K and A.  Bytes at or past `length`: zero.
 // Reads: nothing outside [table, table + table_span), [bal, bal + nk A) and the plan.
 __global__ __launch_bounds__(256) void k_adjust_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ bal,
@@ -1078,7 +1081,44 @@ __global__ __launch_bounds__(256) void k_adjust_records(const uint8_t *__restric
   if (g >= nk * units) return;
   const uint32_t r = g / units, u = g - r * units;
   const int64_t rec = (int64_t)((size_t)(uint32_t)plan[r] * table_stride);
-  fresh[g] = rebalanced_unit(table, rec, table_span, bal, r, (int64_t)nk * amount_bytes, u, key_bytes, amount_bytes, length);
+  fresh[g] = refielded_unit(table, rec, table_span, bal, r, amount_bytes, (int64_t)nk * amount_bytes, u, 2 * (int64_t)key_bytes, 2 * (int64_t)key_bytes + amount_bytes, length);
+}
+
+// ---- mfh_merkle_write_keys: the located records' field before the batch (for the compare-and-set form alone), and the nk new records of a batch of writes
+// (merkle_write.hpp).  The field is the record's bytes [f0, f1), 2K <= f0 < f1 <= length, F = f1 - f0 of them.
+//
+// k_field_gather, ONE launch per call WITH expectations, behind k_key_locate on the same stream: one item per UNIQUE key q < nu and 16-byte unit s of its slot of
+// ceil(F / 16) units.  present[q] is the search's result word on the device, the record whose own key is key q (0xFFFFFFFF: not a member).  Unit s holds the
+// field's bytes [16 s, 16 s + 16), through load_unit_within -- any alignment of the table, any stride, the field anywhere across the record's units -- with zero
+// behind F, and all zero for a key that is not a member (or a record index that is not below n, which the search never leaves).  The store is the whole unit.
+// Reads: nothing outside [table, table + span) and present.
+__global__ __launch_bounds__(256) void k_field_gather(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t f0, uint32_t f1, uint32_t n,
+                                                      const uint32_t *__restrict__ present, uint32_t nu, uint4 *__restrict__ field) {
+  const uint32_t units = (f1 - f0 + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nu units < 2^32: the host checks nk units of a whole record)
+  if (g >= nu * units) return;
+  const uint32_t q = g / units, s = g - q * units, rec = present[q];
+  uint4 out = make_uint4(0, 0, 0, 0);
+  if (rec < n) {
+    const int64_t o = 16 * (int64_t)s, F = (int64_t)f1 - f0, a = (int64_t)((size_t)rec * stride) + f0 + o;
+    out = merge_unit(out, load_unit_within(table, a, a + min((int64_t)16, F - o), span), o, 0, F);
+  }
+  field[g] = out;
+}
+
+// k_write_records, ONE launch per call: all nk new records of the batch into `fresh`, record j at j * pitch bytes (pitch = ceil(length / 16) units, 16-byte
+// aligned).  One item per record j and 16-byte unit u; the store is the whole unit.  Record j is the table's record plan[j] as it stood BEFORE the batch with
+// bytes [f0, f1) <- val[j F ..], the step's value.  A write overwrites the WHOLE field and nothing else of a record, so even where a key occurs in many steps
+// every source is the table before the batch or the uploaded values -- one launch, no ordering among the items, and the table is only read.  The unit is
+// k_transfer_records' and k_adjust_records' (refielded_unit), for any alignment, stride, K and field.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [val, val + nk F) and the plan.
+__global__ __launch_bounds__(256) void k_write_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ val,
+                                                       const int32_t *__restrict__ plan, uint32_t f0, uint32_t f1, uint32_t length, uint32_t nk,
+                                                       uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nk units < 2^32: checked by the host)
+  if (g >= nk * units) return;
+  const uint32_t r = g / units, u = g - r * units;
+  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[r] * table_stride), F = (int64_t)f1 - f0;
+  fresh[g] = refielded_unit(table, rec, table_span, val, r, F, (int64_t)nk * F, u, f0, f1, length);
 }
 
 // The supply: the sum of the balances of all LIVE records and their number, two launches, no atomics (integer addition: the result does not depend on the
@@ -2540,9 +2580,125 @@ int adjust_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
   return record_updates(c, t, nk, k.h_index, d_table, k.table_stride, length, d_fresh, hp, k.h_roots, rowb, &chunks, rows_out, k.cuts);
 }
 
+// the field and the step values of a batch of writes: bytes [lo, hi) of a record, value j the hi - lo bytes at values + j * value_stride, and with `expect` the
+// bytes the field must hold at step j (null: plain writes)
+struct WriteArgs {
+  uint32_t lo, hi;
+  const uint8_t *values;
+  size_t value_stride;
+  const uint8_t *expect;
+  size_t expect_stride;
+};
+
+// mfh_merkle_write_keys (k.cuts = null: one row of the whole depth a step) and mfh_merkle_write_keys_cut (segment 0's row a write over c_0 levels to
+// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  adjust_keys' one-record driver: the front of the
+// scratch, kept for the whole call, is fresh = the nk new records at a pitch of record_head_pitch(length) | the plan, one word a step | the nk values, F bytes
+// each; behind its bytes rounded up to 16 the search, with expectations the nu field slots behind it, then per chunk update_rows' scratch.
+int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const WriteArgs &w) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes;  // d0: the levels of the write's own row
+  const uint32_t F = w.hi > w.lo ? w.hi - w.lo : 0;
+  const size_t pub = (size_t)K + (w.expect ? 2 : 1) * (size_t)F, rowb = mf::row_bytes(64, pub + length, d0);
+  const std::string what = keys_refused(k, depth, "writes", true, [&]() -> const char * {
+    if (w.lo < 2 * K) return "field_lo below the two keys' 2 key_bytes bytes: the keys are not writable";
+    if (w.hi <= w.lo) return "field_hi must be above field_lo";
+    if (w.hi > length) return "field_hi above length";
+    if (w.value_stride < F) return "value_stride shorter than the field's field_hi - field_lo bytes";
+    if (w.expect && w.expect_stride < F) return "expect_stride shorter than the field's field_hi - field_lo bytes";
+    if (k.cuts) return cuts_refused(nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
+    return k.h_inputs && k.in_stride < rowb ? "in_stride shorter than the row's 64 + key_bytes + the field's bytes (twice with h_expect) + length + 32 depth + ceil(depth / 8) bytes"
+                                            : nullptr;
+  }, false);
+  if (!what.empty()) return fail(c, k.who, what.c_str());
+  if (nk && !w.values) return fail(c, k.who, "writes without h_values");
+  if (!nk) return MFH_OK;
+  mf::KeyPlan keys;
+  mf::keys_prepare(k.h_keys, k.key_stride, K, nk, keys);
+  const uint32_t nu = keys.nu, n = 1u << depth;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hp = mf::record_head_pitch(length), fresh_bytes = (size_t)nk * hp, plan_bytes = (size_t)nk * 4, val_bytes = (size_t)nk * F;
+  const size_t skip = (fresh_bytes + plan_bytes + val_bytes + 15) & ~(size_t)15;
+  const size_t slot = mf::field_slot_bytes(F), gather_bytes = w.expect ? (size_t)nu * slot : 0;
+  const uint32_t ch = mf::update_chunk(nk, rowb + (k.cuts ? mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, skip + std::max(key_search_tail_at(nu, K) + gather_bytes, update_rows_bytes(depth, ch, 2 * hp, 1, k.cuts)))) return rc;
+  std::vector<uint32_t> rec(nu);
+  std::vector<uint8_t> field(gather_bytes);
+  {  // a. the search, against the table before the batch; with expectations the located records' field behind it, under the same wait
+    const SearchTail gather{gather_bytes, [&](const uint32_t *d_res, uint8_t *d_out) {
+      Timer tm(c, 49, nu);  // "merkle_fields" (mfhip.hip: timing_kind)
+      const uint64_t items = (uint64_t)nu * (slot / 16);
+      hipLaunchKernelGGL(k_field_gather, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), w.lo, w.hi, n, d_res + nu, nu,
+                         reinterpret_cast<uint4 *>(d_out));
+    }};
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + skip, &res, w.expect ? &gather : nullptr)) return rc;
+    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
+    if (gather_bytes) memcpy(field.data(), res + (size_t)2 * nu, gather_bytes);
+  }
+  // b. the plan: the running field of every key through the steps in order
+  mf::WritePlan plan;
+  mf::write_plan(nk, keys.slot.data(), rec.data(), F, w.values, w.value_stride, w.expect, w.expect_stride, field.data(), slot, plan);
+  memcpy(k.h_index, plan.idx.data(), (size_t)nk * 4);
+  memcpy(k.h_status, plan.status.data(), nk);
+  if (plan.failed)
+    return fail(c, k.who, plan.status[plan.first] == 1 ? "a key is not a member of the set (h_status 1)" : "a field is not what was expected at that step (h_status 5)");
+  // c. the plan's words and the nk values go up; ONE launch builds the nk new records
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_val = d_plan + plan_bytes;
+  {
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, plan_bytes + val_bytes);
+    if (!pin_up) return MFH_ENOMEM;
+    memcpy(pin_up, plan.idx.data(), plan_bytes);
+    for (uint32_t j = 0; j < nk; j++) memcpy(pin_up + plan_bytes + (size_t)j * F, w.values + (size_t)j * w.value_stride, F);
+    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, plan_bytes + val_bytes, hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {
+    Timer tm(c, 50, nk);  // "merkle_write_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nk * (hp / 16);
+    hipLaunchKernelGGL(k_write_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), (const uint8_t *)d_val,
+                       (const int32_t *)d_plan, w.lo, w.hi, length, nk, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  // d. the nk record updates; a row: k | [e |] v | the old record
+  const Pairs chunks{ch, skip, true};
+  ChunkFn rows_out;
+  if (k.h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b < u.k; b++) {
+        const uint32_t j = u.b0 + b;
+        const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs;
+        uint8_t *row = k.h_inputs + (size_t)j * k.in_stride;
+        const mf::RowPiece e{w.expect ? w.expect + (size_t)j * w.expect_stride : nullptr, w.expect ? F : 0};
+        mf::splice_row(row, 64, {{k.key(j), K}, e, {w.values + (size_t)j * w.value_stride, F}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
+        if (k.cuts) mf::splice_cut_tail(row + 64 + pub + length, staged, d0, k.h_index[j]);
+      }
+    };
+  return record_updates(c, t, nk, k.h_index, d_table, k.table_stride, length, d_fresh, hp, k.h_roots, rowb, &chunks, rows_out, k.cuts);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mfh_merkle_write_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t field_lo, uint32_t field_hi,
+                          uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint8_t *h_values, size_t value_stride, const uint8_t *h_expect, size_t expect_stride,
+                          uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_write_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return write_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_inputs, in_stride, h_index, h_status, h_roots, nullptr}, d_table,
+                    {field_lo, field_hi, h_values, value_stride, h_expect, expect_stride});
+}
+
+int mfh_merkle_write_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t field_lo, uint32_t field_hi,
+                              uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint8_t *h_values, size_t value_stride, const uint8_t *h_expect,
+                              size_t expect_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots,
+                              uint32_t *h_index, uint8_t *h_status) {
+  const char *who = "mfh_merkle_write_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return write_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table,
+                    {field_lo, field_hi, h_values, value_stride, h_expect, expect_stride});
+}
 
 int mfh_merkle_adjust_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
                            const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots,

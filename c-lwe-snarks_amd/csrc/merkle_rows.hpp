@@ -18,6 +18,9 @@
 //                                                 tails as the insert's                           pair_row_bytes(2 key_bytes + amount_bytes, 2, length, depth)
 //   words.MerkleAdjust(key_bytes, length, depth, amount_bytes)   ONE record and one tail behind three public pieces: Z = 64, head = the key | the amount as
 //                                                 amount_bytes big-endian bytes | the side byte | the old record    row_bytes(64, key_bytes + amount_bytes + 1 + length, depth)
+//   words.MerkleWrite(key_bytes, length, depth, field, expect)   ONE record and one tail behind the key and the F = hi - lo bytes of the value, with expect=True the
+//                                                 F expected bytes in front of it: Z = 64, head = the key | [e |] v | the old record
+//                                                                                                 row_bytes(64, key_bytes + F [+ F] + length, depth)
 //   words.MerkleSegment(levels)                   the GIVEN nodes stand in front of the computed tops: old node as words | new node as words | 64 zero
 //                                                 bytes | levels siblings as words | ceil(levels / 8) index bytes      segment_row_bytes(levels)
 //   words.MerkleClimb(levels)                     the GIVEN node stands in front of the computed top: the node as words | 32 zero bytes | levels siblings as

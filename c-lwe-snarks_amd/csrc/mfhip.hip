@@ -1177,6 +1177,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_load")) return 45;  // k_load_entries, k_load_dups, k_load_dup_tags, k_load_records of mfh_merkle_load_keys: three in front of the wait (nk > 0) and the build launch behind it; rows = nk, nk, 0 and the table's 2^depth records
   if (!strcmp(which, "merkle_check")) return 46;  // mfh_merkle_check_table: flags, scan, select, keys (4), entries and chain (2, live > 0), leaves (1), nodes (depth); rows = the records, live records or nodes each covers
   if (!strcmp(which, "merkle_grow")) return 47;  // k_grow_nodes, k_grow_spine, k_grow_table of mfh_merkle_grow / mfh_merkle_grow_leaves (merkle.hip): 3 per call with a table and 2 without; rows = the new tree's 2^(new_depth + 1) nodes, the new_depth - depth spine nodes and the new table's 2^new_depth records
+  if (!strcmp(which, "merkle_fields")) return 49;  // k_field_gather of mfh_merkle_write_keys with expectations (merkle.hip): one per call, none for plain writes; rows = the unique keys
+  if (!strcmp(which, "merkle_write_records")) return 50;  // k_write_records of mfh_merkle_write_keys: one per call; rows = the nk new records
   return -1;
 }
 

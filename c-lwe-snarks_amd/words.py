@@ -61,6 +61,9 @@ Whole statements built from that compression, the result 256 computed public out
                             withdrawal), and that alone takes the tree from R to R'": ONE live record whose balance becomes b + v or b - v through one ripple
                             with the side as carry in, the carry out tied to the side; lu = 512 + 8 (key_bytes + amount_bytes + 1); MerkleRecordUpdate's
                             depth range, (8, 55, 9, 8) fits d = 2^20.
+    MerkleWrite(key_bytes, length, depth, field, expect=False)   "bytes [lo, hi) of the record of key k were set to v [, having been e], and that alone takes
+                            the tree from R to R'": the put, plain or compare-and-set; ONE live record whose field's wires are replaced by v's; lu = 512 +
+                            8 (key_bytes + F), 8 F more with expect=True; (8, 55, 9, (16, 55), True) fits d = 2^20.
     MerkleSegment(levels)   "one node changed from X to X', and that alone takes its ancestor `levels` levels up from Y to Y'" (lu = 1024, the two nodes
                             given, the two tops computed): one level range of a path cut by segment_levels(depth, cuts); MerkleUpdate's sizes, 10 levels
                             fit d = 2^20.  chain(nodes) turns the published node pairs of a transition into the upper segments' statements.
@@ -1460,6 +1463,103 @@ class MerkleAdjust(_TwoRoots):
                 + self._public(key, amount, side))
 
 
+def _field_arg(who: str, field, key_bytes: int, length: int):
+    """(lo, hi) of a written field, checked: two integers with 2 key_bytes <= lo < hi <= length"""
+    try:
+        lo, hi = field
+    except (TypeError, ValueError):
+        lo = hi = None
+    if not all(isinstance(x, (int, np.integer)) for x in (lo, hi)) or not 2 * key_bytes <= lo < hi <= length:
+        raise CircuitError(f"{who}: the field is (lo, hi) with 2 key_bytes <= lo < hi <= length -- the keys are never writable")
+    return int(lo), int(hi)
+
+
+class MerkleWrite(_TwoRoots):
+    """The statement "bytes [lo, hi) of the record of key k were set to v, and that alone takes the tree from root R to root R'" -- with expect=True "... were
+    set to v, having been e": the PUT of the indexed table as a keyed store, plain or compare-and-set.  ONE record update, beside MerkleAdjust.
+
+    field = (lo, hi) with 2K <= lo < hi <= length, F = hi - lo: the keys are never writable, the whole payload is.
+    Public wires, in this order: R as 256 computed outputs at statement bits [0, 256), R' at [256, 512), the 8K given bits of k, with expect=True the 8F bits
+    of e, the field's old bytes, then the 8F bits of v.  The values are bytes, not integers: byte j's bit b (LSB first) at 8 j + b, the record's own bit
+    order.  lu = 512 + 8 (K + F), with expect=True 512 + 8 (K + 2F).  statement(R, R', k, v) or statement(R, R', k, e, v) is MerkleUpdate.statement's 64
+    bytes, then k, [e,] v.
+    Private inputs, in this order: the old record (8 * length bits, byte j's bit b at 8 j + b); `depth` siblings of 8 words from the leaf's level up;
+    `depth` direction bits -- _tail_wires, as MerkleAdjust has them.  nin = lu + 8 length + 257 depth.  The packed row: 64 zero bytes | k | [e |] v | old
+    record | depth siblings as words | ceil(depth / 8) index bytes.
+    The body.  The new record is not an input: it is the old record's wires with the field's 8F wires replaced by v's.  Two record chains (_message_chain)
+    and MerkleUpdate's two level chains over the shared tail (_root_outputs).  assert_same: k = old[0, K); with expect=True e = old[lo, hi).  One comparator:
+    less_than(lo_key, hi_key) = 1, the record is live.  The sentinel keys are refused as for members.
+    Soundness.  Keys and the rest of the payload are the old record's wires, so every record's lo and hi are what they were: the table's invariant
+    (MerkleAbsent) is kept.  By the invariant k is the lo of at most one live record, so the record opened is the record of k and no other.  v equal to the
+    field's old bytes is a no-op with R' = R.  What it does not cover: like MerkleInsert, the records it does not open.
+    MerkleTree.write_keys / write_bits perform a batch of writes on a device table and give the input rows; statement j is (R_j, R_j+1, k_j, [e_j,] v_j).  A
+    key may occur in many steps of a batch, and an expectation may be one that only an earlier step of the batch satisfies.
+    Sizes (MERKLE_WRITE_SIZES): MerkleAdjust's without the ripple; (8, 55, 9, (16, 55), True), the whole payload, fits Params(d=1 << 20, m=699050), depth 10
+    does not.
+    Cut form.  There is no `joined` parameter: the statement has one pair of tops, so segment 0 of a cut write (segment_levels) is MerkleWrite(K, length,
+    c_0, field, expect) itself over the record's subtree of height c_0, and the upper ranges are MerkleSegment rows (MerkleTree.write_key_segments)."""
+
+    def __init__(self, key_bytes: int, length: int, depth: int, field, expect=False):
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = length = self._arg(length, 2 * K + 1, None, "the length is at least 2 key_bytes + 1 bytes")
+        self.depth = self._depth_arg(depth)
+        self.field = lo, hi = _field_arg("MerkleWrite", field, K, length)
+        if not isinstance(expect, (bool, np.bool_)):
+            raise CircuitError("MerkleWrite: expect is True or False")
+        self.expect = bool(expect)
+        self.field_bytes = F = hi - lo
+        self.w = w = Words()
+        self.old_record = w.c.private(8 * length)
+        self._tail_wires()
+        # the public pieces are read by the new record's chain, so they are declared here and moved behind the roots below
+        self.key = w.c.public(8 * K)
+        self.expected = w.c.public(8 * F) if self.expect else []
+        self.value = w.c.public(8 * F)
+        self.new_record = self.old_record[: 8 * lo] + self.value + self.old_record[8 * hi:]
+        self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
+        self.new_leaf, _ = _message_chain(w, self.new_record, length)
+        self._root_outputs(self.old_leaf, self.new_leaf)
+        w.c.public_last(self.key + self.expected + self.value)
+        for x, y in zip(self.key, self.old_record[: 8 * K]):
+            w.c.assert_same(x, y)
+        for x, y in zip(self.expected, self.old_record[8 * lo: 8 * hi]):
+            w.c.assert_same(x, y)
+        lo_key, hi_key = (_key_bits_lsb_first(part, K) for part in (self.old_record[: 8 * K], self.old_record[8 * K: 16 * K]))
+        w.c.assert_equal(w.less_than(lo_key, hi_key), 1)
+
+    @property
+    def lu(self) -> int:
+        return 512 + 8 * (self.key_bytes + (2 if self.expect else 1) * self.field_bytes)
+
+    def _public(self, key, values) -> bytes:
+        """the checked K + F [+ F] bytes of the public pieces behind the roots; values = (v,) or (e, v)"""
+        if len(values) != (2 if self.expect else 1):
+            raise CircuitError("MerkleWrite: the public values are (e, v) with expect=True and v alone without")
+        values = [bytes(x) for x in values]
+        if any(len(x) != self.field_bytes for x in values):
+            raise CircuitError(f"MerkleWrite: a value is the field's {self.field_bytes} bytes")
+        return _checked_key("MerkleWrite", self.key_bytes, key, "members") + b"".join(values)
+
+    def bits(self, key: bytes, *values_record_siblings_index):
+        """bits(key, [expected,] value, old_record, siblings, index): one statement's input bits, public then private -- 512 zeros where the two roots are
+        computed, the bits of k, of e with expect=True and of v, the old record's bits, the siblings from the leaf's level up, then the direction bits.  (A
+        witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
+        who = "MerkleWrite"
+        nv = 2 if self.expect else 1
+        if len(values_record_siblings_index) != nv + 3:
+            raise CircuitError(f"{who}: bits(key, {'expected, ' if self.expect else ''}value, old_record, siblings, index)")
+        *values, old_record, siblings, index = values_record_siblings_index
+        public = np.unpackbits(np.frombuffer(self._public(key, values), dtype=np.uint8), bitorder="little")
+        return _input_bits(512, public, _record_bits(who, self.length, old_record), _tail_bits(who, self.depth, siblings, index))
+
+    def statement(self, old_root: bytes, new_root: bytes, key: bytes, *values) -> bytes:
+        """statement(R, R', key, value) or, with expect=True, statement(R, R', key, expected, value): the 64 + K + F [+ F] statement bytes (what
+        verify_public takes, bits [0, lu) of a witness row) that say "the write of `value` under `key` [over `expected`] took old_root to new_root":
+        MerkleUpdate.statement's bytes, then the key, [the expected bytes,] the value"""
+        return (_statement_of(old_root, "MerkleWrite: the old root") + _statement_of(new_root, "MerkleWrite: the new root")
+                + self._public(key, values))
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):
@@ -1599,6 +1699,29 @@ def indexed_adjust(record, amount: int, side: int, key_bytes: int, amount_bytes=
         raise CircuitError(f"indexed_adjust: the balance would exceed 2^{8 * A} - 1")
     fresh = b - int(amount) if side else b + int(amount)
     return np.frombuffer(record[: 2 * K] + fresh.to_bytes(A, "big") + record[2 * K + A:], dtype=np.uint8).copy()
+
+
+def indexed_write(record, field, value, key_bytes: int, expect=None):
+    """the new record, np.uint8 [length]: `record`, a live record of an indexed table, with its bytes [lo, hi) = field set to `value` (MerkleWrite has the
+    statement); nothing else of it changes.  expect: the hi - lo bytes the field must hold now (None: a plain write).  CircuitError on a record that is not
+    live (lo < hi), a field outside [2 key_bytes, length], a value that is not hi - lo bytes, or an expectation the record does not meet."""
+    record = bytes(record)
+    K, length = key_bytes, len(record)
+    if not isinstance(K, (int, np.integer)) or not 1 <= K <= 32 or length < 2 * K + 1:
+        raise CircuitError("indexed_write: a record of at least 2 key_bytes + 1 bytes, key_bytes in [1, 32]")
+    lo, hi = _field_arg("indexed_write", field, K, length)
+    value = bytes(value)
+    if len(value) != hi - lo:
+        raise CircuitError(f"indexed_write: the value is the field's {hi - lo} bytes")
+    if not record[:K] < record[K: 2 * K]:
+        raise CircuitError("indexed_write: the record is not live (lo < hi)")
+    if expect is not None:
+        expect = bytes(expect)
+        if len(expect) != hi - lo:
+            raise CircuitError(f"indexed_write: the expected value is the field's {hi - lo} bytes")
+        if record[lo:hi] != expect:
+            raise CircuitError("indexed_write: the field is not what was expected")
+    return np.frombuffer(record[:lo] + value + record[hi:], dtype=np.uint8).copy()
 
 
 def indexed_range(table, key_bytes: int, lo: bytes, hi: bytes):
@@ -1785,3 +1908,13 @@ MERKLE_TRANSFER_SPLIT_SIZES = {(4, 16, 1, 8): (225209, 400576), (8, 55, 1, 8): (
 # fits Params(d=1 << 18, m=174762); (8, 55, 9, 8) is the deepest one-block statement that fits Params(d=1 << 20, m=699050): (8, 55, 10, 8) would be 1 114 167 rows
 MERKLE_ADJUST_SIZES = {(4, 16, 1, 8): (112677, 200400), (4, 16, 1, 1): (112453, 200008), (4, 16, 1, 3): (112517, 200120), (8, 55, 1, 8): (113091, 200910),
                        (4, 16, 2, 8): (169670, 301873), (8, 55, 9, 8): (569035, 1012694)}
+# ... and of MerkleWrite by (key_bytes, length, depth, field, expect), F = hi - lo: MerkleAdjust(key_bytes, length, depth, F)'s two record chains and two level
+# chains with ONE input record, without the side byte, the carry's equality and the ripple, the field's wires of the new record being v's own public wires: plain
+# it is 8 + 24 F wires and 16 + 48 F rows BELOW MerkleAdjust with amount_bytes = F ((4, 16, 1, (8, 16)) is (200, 400) below (4, 16, 1, 8), (8, 55, 1, (16, 24))
+# the same below (8, 55, 1, 8)).  A field byte costs 8 wires and 8 rows; expect=True adds 8 F wires and 16 F rows (e's public wires and its equalities:
+# (4, 16, 1, (8, 16), True) less (4, 16, 1, (9, 10), True) is 7 x (16, 24)).  A level costs 56 993 wires and 101 473 rows, MerkleUpdate's.  (4, 16, 1, ..) fits
+# Params(d=1 << 18, m=174762); (8, 55, 9, (16, 55), True), the whole payload under compare-and-set, is the deepest that fits Params(d=1 << 20, m=699050):
+# (8, 55, 10, (16, 55), True) would be 1 114 639 rows
+MERKLE_WRITE_SIZES = {(4, 16, 1, (8, 16), False): (112477, 200000), (4, 16, 1, (8, 16), True): (112541, 200128), (4, 16, 1, (9, 10), True): (112429, 199960),
+                      (4, 16, 2, (8, 16), True): (169534, 301601), (8, 55, 1, (16, 24), False): (112891, 200510), (8, 55, 1, (16, 24), True): (112955, 200638),
+                      (8, 55, 9, (16, 55), True): (569395, 1013166)}

@@ -698,6 +698,46 @@ int mfh_merkle_adjust_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, si
                                uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides, uint32_t ncuts,
                                const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index,
                                uint8_t *h_status);
+/* nk sequential WRITES BY KEY on an indexed table and its tree in ONE call, plain or compare-and-set, and the packed input row of
+ * words.MerkleWrite(key_bytes, length, depth, (field_lo, field_hi), expect) of every step -- "bytes [field_lo, field_hi) of the record of key k_j were set to
+ * v_j [, having been e_j], and that alone takes the tree from R_j to R_j+1".  The put of the keyed store: the field is any part of the payload, 2 key_bytes <=
+ * field_lo < field_hi <= length, F = field_hi - field_lo bytes, one field for the whole call; the keys are never writable.
+ *   semantics  byte for byte what this gives, run once per step in order: find the lowest live record whose own key (lo) is k_j; if expectations are given and
+ *              its field is not e_j the step fails; else that record with the field set to v_j, through mfh_merkle_update_records.  That covers the table in
+ *              place, every node of the tree, the roots and row j, which describes table and tree as they stood before step j.  A key may occur in ANY number
+ *              of steps, and a step sees what the earlier steps of the batch left: an expectation may be met by an earlier write alone, or broken by one.
+ *   arguments  key j is the key_bytes bytes at h_keys + j * key_stride, v_j the F bytes at h_values + j * value_stride, e_j the F bytes at h_expect + j *
+ *              expect_stride.  h_expect = NULL: every step is unconditional (expect_stride is ignored); a call is all-conditional or all-plain, as a circuit
+ *              is.  h_inputs = NULL: write, no rows.  h_roots (may be NULL) receives the nk + 1 roots R_0 .. R_nk.  h_index receives the nk records, 0xFFFFFFFF
+ *              for a key that is no member.  h_status receives per step the first that applies: 0 = fine; 1 = the key is not a member; 5 = the field is not
+ *              what was expected AT THAT STEP (2 to 4 are unused: the numbers keep their meaning across the key calls).  A step with a status is left out of
+ *              the values the later steps are judged by.
+ *   rows       row j (at h_inputs + j * in_stride): 64 zero bytes where the roots are computed | k_j | with h_expect e_j | v_j | the old record | the 32 depth
+ *              sibling bytes | ceil(depth / 8) index bytes.  Exactly 64 + key_bytes + F (2 F with h_expect) + length + 32 depth + ceil(depth / 8) bytes are
+ *              written.
+ *   how        ONE launch of k_key_locate over the sorted unique keys; with h_expect, behind it on the stream, ONE launch of k_field_gather (a slot of
+ *              ceil(F / 16) 16-byte units per unique key); the results come back under ONE wait.  The host walks the steps in order over a running field value
+ *              per unique key (merkle_write.hpp); ONE launch of k_write_records builds the nk new records from the table before the batch and the uploaded
+ *              values; they go through mfh_merkle_update_records' machinery in its chunks (the most updates whose rows fit 64 MiB, at least one).  The call
+ *              synchronises the stream behind the search and every chunk.
+ * mfh_merkle_write_keys_cut is the same with the path cut (above), exactly as mfh_merkle_adjust_keys_cut: segment 0's row is that of MerkleWrite(key_bytes,
+ * length, c_0, field, expect) -- 64 zero bytes | k | [e |] v | old record | c_0 siblings | ceil(c_0 / 8) index bytes of the record mod 2^c_0 -- every upper
+ * segment has ONE MerkleSegment row per step, and h_roots (may be NULL) receives the nk + 1 roots; it has no "no rows" mode.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: what mfh_merkle_adjust_keys refuses of the arguments the two share;
+ * field_lo < 2 key_bytes; field_hi <= field_lo; field_hi > length; value_stride < F; expect_stride < F with h_expect; nk > 0 with h_values null; in_stride
+ * below the row's bytes when h_inputs is given; for the cut call, what the cut calls above refuse.
+ * MFH_EINVAL after the search, with h_status and h_index filled, table and tree unwritten and no record or tree kernel launched: any step with a status
+ * other than 0.  The call is all or nothing.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call, rows = 2^depth), "merkle_fields" (1 per call with h_expect, none without; rows = the unique keys),
+ * "merkle_write_records" (1 per call, rows = nk), then per chunk as mfh_merkle_adjust_keys. */
+int mfh_merkle_write_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t field_lo,
+                          uint32_t field_hi, uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint8_t *h_values, size_t value_stride,
+                          const uint8_t *h_expect, size_t expect_stride, uint8_t *h_inputs, size_t in_stride, uint8_t *h_roots, uint32_t *h_index,
+                          uint8_t *h_status);
+int mfh_merkle_write_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t field_lo,
+                              uint32_t field_hi, uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint8_t *h_values, size_t value_stride,
+                              const uint8_t *h_expect, size_t expect_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                              const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
 /* The SUPPLY of such a table: h_sum[0] | h_sum[1] << 64 = the sum of the balances (bytes [2 key_bytes, 2 key_bytes + amount_bytes), big-endian) of all LIVE
  * records (lo < hi) of the 2^depth records at d_table, *h_live (may be NULL) their number.  What is in the balance bytes of a record that is not live does
  * not count.  The table is only read; the tree is used for its depth alone.  Transfers leave the sum as it is, a batch of adjusts changes it by its deposits
