@@ -1022,10 +1022,36 @@ class MerkleTree:
         head = self._step_head(table, from_keys, 2, 128) + np.ascontiguousarray(from_keys).shape[1] + int(amount_bytes)
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 514 * c0),) + tuple(out[1:])
 
+    # ---- one-record steps by key: deposits and withdrawals, writes
+    def _record_step(self, who, name, table, nk, pub, args, roots, cut, cuts):
+        """what _adjust and _write end with: mfh_merkle_<name>[_cut] with rows (`pub` bytes of public pieces in a row's head), index, status and roots allocated
+        here.  table: what _keys made of it; args: the call's arguments between `length` and the rows, whose arrays stay alive in the caller"""
+        c = self._ctx
+        tab, tstride, length = table
+        vp = ctypes.c_void_p
+        head = 64 + pub + length
+        if not cut:
+            rows = np.zeros((nk, head + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
+            out = (vp(rows.ctypes.data), rows.shape[1])
+        else:
+            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 32 * c0 + (c0 + 7) // 8, nk)
+        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots or cut else None
+        index = np.zeros(nk, dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        call = getattr(c.lib, f"mfh_merkle_{name}_cut" if cut else f"mfh_merkle_{name}")
+        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, *args, *out, vp(r.ctypes.data) if r is not None else None, vp(index.ctypes.data),
+                    vp(status.ctypes.data)))
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        elif r is not None:
+            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        if not cut:
+            return (rows, index, r) if roots else (rows, index)
+        return rows, self._cut_nodes(rows, r), index
+
     # ---- deposits and withdrawals: what funds and drains the ledger, and its supply
     def _adjust(self, who, table, keys, amounts, sides, amount_bytes, roots=False, cut=False, cuts=None):
-        """the body of adjust_keys and, with cut=True, adjust_key_segments: mfh_merkle_adjust_keys[_cut] with rows, index, status and roots allocated here"""
-        c = self._ctx
+        """the body of adjust_keys and, with cut=True, adjust_key_segments: its argument checks, then _record_step"""
         tab, tstride, length, k = self._keys(table, keys, who)
         nk, kb = k.shape
         vp = ctypes.c_void_p
@@ -1043,25 +1069,8 @@ class MerkleTree:
             raise MfhError(f"{who}: sides are nk values 0 (a deposit) or 1 (a withdrawal), one a step")
         amt = np.array(values, dtype=np.uint64).reshape(nk)
         side = np.array(dirs, dtype=np.uint8).reshape(nk)
-        head = 64 + kb + int(ab) + 1 + length
-        if not cut:
-            rows = np.zeros((nk, head + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
-            out = (vp(rows.ctypes.data), rows.shape[1])
-        else:
-            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 32 * c0 + (c0 + 7) // 8, nk)
-        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots or cut else None
-        index = np.zeros(nk, dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        call = c.lib.mfh_merkle_adjust_keys_cut if cut else c.lib.mfh_merkle_adjust_keys
-        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, int(ab), nk, vp(k.ctypes.data), kb, vp(amt.ctypes.data), vp(side.ctypes.data) if sides is not None else None,
-                    *out, vp(r.ctypes.data) if r is not None else None, vp(index.ctypes.data), vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        elif r is not None:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        if not cut:
-            return (rows, index, r) if roots else (rows, index)
-        return rows, self._cut_nodes(rows, r), index
+        args = (kb, int(ab), nk, vp(k.ctypes.data), kb, vp(amt.ctypes.data), vp(side.ctypes.data) if sides is not None else None)
+        return self._record_step(who, "adjust_keys", (tab, tstride, length), nk, kb + int(ab) + 1, args, roots, cut, cuts)
 
     def adjust_keys(self, table, keys, amounts, sides=None, amount_bytes=8, roots=False):
         """(rows, index): nk sequential DEPOSITS and WITHDRAWALS on the accounts of an INDEXED table whose records carry a balance (words.MerkleTransfer has the
@@ -1115,8 +1124,7 @@ class MerkleTree:
         return np.ascontiguousarray(v)
 
     def _write(self, who, table, keys, values, field, expect, roots=False, cut=False, cuts=None):
-        """the body of write_keys and, with cut=True, write_key_segments: mfh_merkle_write_keys[_cut] with rows, index, status and roots allocated here"""
-        c = self._ctx
+        """the body of write_keys and, with cut=True, write_key_segments: its argument checks, then _record_step"""
         tab, tstride, length, k = self._keys(table, keys, who)
         nk, kb = k.shape
         vp = ctypes.c_void_p
@@ -1130,26 +1138,8 @@ class MerkleTree:
         F = hi - lo
         val = self._field_values(who, "values", values, nk, F)
         exp = None if expect is None else self._field_values(who, "expectations", expect, nk, F)
-        head = 64 + kb + (F if exp is None else 2 * F) + length
-        if not cut:
-            rows = np.zeros((nk, head + 32 * self.depth + (self.depth + 7) // 8), dtype=np.uint8)
-            out = (vp(rows.ctypes.data), rows.shape[1])
-        else:
-            rows, out, keep = self._cut(cuts, who, nk, lambda c0: head + 32 * c0 + (c0 + 7) // 8, nk)
-        r = np.zeros((nk + 1, 32), dtype=np.uint8) if roots or cut else None
-        index = np.zeros(nk, dtype=np.uint32)
-        status = np.zeros(nk, dtype=np.uint8)
-        call = c.lib.mfh_merkle_write_keys_cut if cut else c.lib.mfh_merkle_write_keys
-        c._chk(call(c._h, self._h, _ptr(tab), tstride, length, kb, lo, hi, nk, vp(k.ctypes.data), kb, vp(val.ctypes.data), F,
-                    vp(exp.ctypes.data) if exp is not None else None, F, *out, vp(r.ctypes.data) if r is not None else None, vp(index.ctypes.data),
-                    vp(status.ctypes.data)))
-        if nk:
-            self._keep = []  # (the call waited for the stream)
-        elif r is not None:
-            r[0] = np.frombuffer(self.root(), dtype=np.uint8)
-        if not cut:
-            return (rows, index, r) if roots else (rows, index)
-        return rows, self._cut_nodes(rows, r), index
+        args = (kb, lo, hi, nk, vp(k.ctypes.data), kb, vp(val.ctypes.data), F, vp(exp.ctypes.data) if exp is not None else None, F)
+        return self._record_step(who, "write_keys", (tab, tstride, length), nk, kb + (F if exp is None else 2 * F), args, roots, cut, cuts)
 
     def write_keys(self, table, keys, values, field, expect=None, roots=False):
         """(rows, index): nk sequential WRITES BY KEY on an INDEXED table and this tree in one call (mfh_merkle_write_keys; waits for the stream).  Step j sets

@@ -32,13 +32,14 @@
 // one pass, then the steps below (the host's plan: merkle_remove.hpp).
 // k_balance_gather: mfh_merkle_transfer_keys, a batch of sequential transfers between the accounts of an indexed table in one call -- the keys located as above,
 // the located records' balances read behind the search, then the steps below (the host's plan: merkle_transfer.hpp).
-// k_adjust_records: mfh_merkle_adjust_keys, a batch of sequential deposits and withdrawals in one call -- the search and the balances as for the transfers, ONE
-// new record a step (the host's plan: merkle_adjust.hpp), then the record updates above.  k_balance_sum, k_balance_fold: mfh_merkle_balance_sum, the supply.
-// k_field_gather, k_write_records: mfh_merkle_write_keys, a batch of sequential writes by key, plain or compare-and-set, in one call -- the search as above, for
-// the conditional form the located records' field behind it, ONE new record a step (the host's plan: merkle_write.hpp), then the record updates above.
-// k_insert_records, k_remove_records, k_transfer_records: what a batch of key steps ends with -- all 2 nk new records built in one launch from the step's plan,
-// then the record updates above.  The host side of the key calls is one preamble (keys_refused), one search (key_search), one driver of the steps
-// (pair_reserve, pair_updates); a call states its refusals, its plan, its build launch and its row.
+// mfh_merkle_adjust_keys, a batch of sequential deposits and withdrawals in one call -- the search and the balances as for the transfers, ONE new record a
+// step (the host's plan: merkle_adjust.hpp), then the steps below.  k_balance_sum, k_balance_fold: mfh_merkle_balance_sum, the supply.
+// k_field_gather: mfh_merkle_write_keys, a batch of sequential writes by key, plain or compare-and-set, in one call -- the search as above, for the conditional
+// form the located records' field behind it, ONE new record a step (the host's plan: merkle_write.hpp), then the steps below.
+// k_insert_records, k_remove_records, k_refield_records (transfers, adjusts and writes: one field of a record changes): what a batch of steps ends with -- all
+// R nk new records (R = 2 a key step, 1 an adjust or a write) built in one launch from the step's plan, then the record updates above.  The host side of the
+// key calls is one preamble (keys_refused), one search (key_search), one driver of the steps (step_reserve, step_updates); a call states its refusals, its
+// plan, its build launch and its row.
 // k_sort_tiles, k_sort_merge: key_sort, the device sort of multi-word keys with a tag (tiles in LDS, then merge passes over a merge-path partition:
 // merkle_sort.hpp).  k_load_entries, k_load_dups, k_load_dup_tags, k_load_records: mfh_merkle_load_keys, a whole indexed table and its tree out of a key set on
 // the device.  k_check_entries, k_chain_check, k_leaf_check, k_node_check: mfh_merkle_check_table, the table's invariant and the tree over it, read only.
@@ -1008,31 +1009,33 @@ __global__ __launch_bounds__(256) void k_remove_records(const uint8_t *__restric
   fresh[g] = out;
 }
 
-// ---- mfh_merkle_transfer_keys: the balances of a batch's accounts before the batch, and the 2 nk new records of the batch.  A record's balance is its bytes
-// [2K, 2K + A), an unsigned big-endian integer, A = amount_bytes in [1, 8] (merkle_transfer.hpp).
-//
+// ---- The balances and the new records of the calls that change ONE field of a record: mfh_merkle_transfer_keys and mfh_merkle_adjust_keys (the balance) and
+// mfh_merkle_write_keys (any field behind the keys).  A record's balance is its bytes [2K, 2K + A), an unsigned big-endian integer, A = amount_bytes in [1, 8]
+// (merkle_transfer.hpp).
+
+// the balance that starts at byte `at` of the table (a record's byte 2K): its A bytes through load_unit_within -- any alignment of the table, any stride, the
+// field anywhere across a 16-byte unit; nothing outside the table's span is read -- as one uint64
+__device__ __forceinline__ unsigned long long balance_at(const uint8_t *__restrict__ table, int64_t at, uint32_t amount_bytes, int64_t span) {
+  const uint4 v = load_unit_within(table, at, at + amount_bytes, span);
+  const unsigned long long be = (unsigned long long)__builtin_bswap32(v.x) << 32 | __builtin_bswap32(v.y);  // byte 0 in the top 8 bits
+  return be >> (8 * (8 - amount_bytes));  // (the bytes at and past A, unspecified, leave here)
+}
+
 // k_balance_gather, ONE launch per call behind k_key_locate on the same stream, one thread per UNIQUE key u < nu: present[u] is the search's result word on the
-// device, the record whose own key is key u (0xFFFFFFFF: not a member).  The A balance bytes come through load_unit_within -- any alignment of the table, any
-// stride, the field anywhere across a 16-byte unit; nothing outside the table's span is read -- and balance[u] <- their value as one uint64, 0 for a key that
-// is not a member (or a record index that is not below n, which the search never leaves).
+// device, the record whose own key is key u (0xFFFFFFFF: not a member).  balance[u] <- that record's balance, 0 for a key that is not a member (or a record
+// index that is not below n, which the search never leaves).
 __global__ __launch_bounds__(256) void k_balance_gather(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t key_bytes, uint32_t amount_bytes,
                                                         uint32_t n, const uint32_t *__restrict__ present, uint32_t nu, unsigned long long *__restrict__ balance) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   if (u >= nu) return;
   const uint32_t rec = present[u];
   unsigned long long value = 0;
-  if (rec < n) {
-    const int64_t a = (int64_t)((size_t)rec * stride) + 2 * (int64_t)key_bytes;
-    const uint4 v = load_unit_within(table, a, a + amount_bytes, span);
-    const unsigned long long be = (unsigned long long)__builtin_bswap32(v.x) << 32 | __builtin_bswap32(v.y);  // byte 0 in the top 8 bits
-    value = be >> (8 * (8 - amount_bytes));  // (the bytes at and past A, unspecified, leave here)
-  }
+  if (rec < n) value = balance_at(table, (int64_t)((size_t)rec * stride) + 2 * (int64_t)key_bytes, amount_bytes, span);
   balance[u] = value;
 }
 
-// unit u of a new record that differs from a table record in ONE field (k_transfer_records, k_adjust_records: the balance; k_write_records: the written
-// bytes): the record at byte `rec` of the table as it stood before the batch, with bytes [f0, f1) <- the f1 - f0 bytes at slot * pitch of the uploaded source
-// `src` (src_span bytes).  Bytes at or past `length`: zero
+// unit u of a new record that differs from a table record in ONE field: the record at byte `rec` of the table as it stood before the batch, with bytes
+// [f0, f1) <- the f1 - f0 bytes at slot * pitch of the uploaded source `src` (src_span bytes).  Bytes at or past `length`: zero
 __device__ __forceinline__ uint4 refielded_unit(const uint8_t *__restrict__ table, int64_t rec, int64_t table_span, const uint8_t *__restrict__ src, int64_t slot,
                                                  int64_t pitch, int64_t src_span, uint32_t u, int64_t f0, int64_t f1, uint32_t length) {
   const int64_t o = 16 * (int64_t)u;
@@ -1045,43 +1048,25 @@ __device__ __forceinline__ uint4 refielded_unit(const uint8_t *__restrict__ tabl
   return out;
 }
 
-// k_transfer_records, ONE launch per call: all 2 nk new records of the batch into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte
-// aligned).  One item per record r and 16-byte unit u; the store is the whole unit.  With (p, s, spare) = plan[3 j ..] of transfer j (merkle_transfer.hpp):
-//   record 2 j      the table's record p as it stood before the batch, with bytes [2K, 2K + A) <- the sender's new balance, bal[2 j A ..]
-//   record 2 j + 1  the table's record s, with those bytes <- the receiver's new balance, bal[(2 j + 1) A ..]
-// The new balances are the host's (the plan's running balances, big-endian), and a transfer changes nothing else of a record, so every source is the table as
-// it stood BEFORE the batch or the uploaded balances -- one launch, no ordering among the items, and the table is only read, even where an account occurs in
-// many steps.  K and A are any, the table sits at any byte alignment, so a unit may straddle the three ranges anywhere: as in k_insert_records,
-// load_unit_within fetches the 16 bytes of a source that line up with the unit and merge_unit takes each range's bytes under per-dword byte masks.  Bytes at
-// or past `length`: zero.
-// Reads: nothing outside [table, table + table_span), [bal, bal + 2 nk A) and the plan.
-__global__ __launch_bounds__(256) void k_transfer_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ bal,
-                                                          const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t nk,
-                                                          uint4 *__restrict__ fresh) {
-  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (2 nk units < 2^32: checked by the host)
-  if (g >= 2 * nk * units) return;
+// k_refield_records, ONE launch per call: all nrec new records of a batch of transfers (nrec = 2 nk, the field the balance), of adjusts (nrec = nk, the
+// balance) or of writes (nrec = nk, the written field) into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units, 16-byte aligned).  One item
+// per record r and 16-byte unit u; the store is the whole unit.  Record r is the table's record plan[(r / per) * words + r % per] as it stood BEFORE the batch,
+// with bytes [f0, f1) <- src[r (f1 - f0) ..]: a step is `per` records (1 or 2) and `words` plan words, the records' indices first -- (p, s, spare) a transfer
+// (merkle_transfer.hpp), (2, 3); the one index of an adjust or a write (merkle_adjust.hpp, merkle_write.hpp), (1, 1).  The field's new bytes are the host's
+// (the plan's running balances, big-endian; the step's value), and a step changes nothing else of a record, so every source is the table as it stood before
+// the batch or the uploaded bytes -- one launch, no ordering among the items, and the table is only read, even where a key occurs in many steps.  K, the field
+// and the table's alignment and stride are any, so a unit may straddle the three ranges anywhere: as in k_insert_records, load_unit_within fetches the 16
+// bytes of a source that line up with the unit and merge_unit takes each range's bytes under per-dword byte masks.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [src, src + nrec (f1 - f0)) and the plan.
+__global__ __launch_bounds__(256) void k_refield_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ src,
+                                                         const int32_t *__restrict__ plan, uint32_t per, uint32_t words, uint32_t f0, uint32_t f1, uint32_t length,
+                                                         uint32_t nrec, uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nrec units < 2^32: checked by the host)
+  if (g >= nrec * units) return;
   const uint32_t r = g / units, u = g - r * units;
-  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[3 * (r >> 1) + (r & 1)] * table_stride);
-  fresh[g] = refielded_unit(table, rec, table_span, bal, r, amount_bytes, (int64_t)2 * nk * amount_bytes, u, 2 * (int64_t)key_bytes, 2 * (int64_t)key_bytes + amount_bytes, length);
-}
-
-// ---- mfh_merkle_adjust_keys: the nk new records of a batch of deposits and withdrawals (merkle_adjust.hpp), and mfh_merkle_balance_sum: the table's supply.
-//
-// k_adjust_records, ONE launch per call: all nk new records of the batch into `fresh`, record j at j * pitch bytes (pitch = ceil(length / 16) units, 16-byte
-// aligned).  One item per record j and 16-byte unit u; the store is the whole unit.  Record j is the table's record plan[j] as it stood before the batch, with
-// bytes [2K, 2K + A) <- the account's balance right after step j, bal[j A ..] (the plan's running balance, big-endian).  An adjust changes nothing else of a
-// record, so every source is the table as it stood BEFORE the batch or the uploaded balances -- one launch, no ordering among the items, and the table is only
-// read, even where an account occurs in many steps.  The unit is k_transfer_records' (refielded_unit): load_unit_within fetches the 16 bytes of a source that
-// line up with the unit, merge_unit takes each range's bytes under per-dword byte masks, for any alignment, stride, K and A.  Bytes at or past `length`: zero.
-// Reads: nothing outside [table, table + table_span), [bal, bal + nk A) and the plan.
-__global__ __launch_bounds__(256) void k_adjust_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ bal,
-                                                        const int32_t *__restrict__ plan, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t nk,
-                                                        uint4 *__restrict__ fresh) {
-  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nk units < 2^32: checked by the host)
-  if (g >= nk * units) return;
-  const uint32_t r = g / units, u = g - r * units;
-  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[r] * table_stride);
-  fresh[g] = refielded_unit(table, rec, table_span, bal, r, amount_bytes, (int64_t)nk * amount_bytes, u, 2 * (int64_t)key_bytes, 2 * (int64_t)key_bytes + amount_bytes, length);
+  const uint32_t word = (r >> (per - 1)) * words + (r & (per - 1));  // (per is 1 or 2: r / per and r % per)
+  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[word] * table_stride), F = (int64_t)f1 - f0;
+  fresh[g] = refielded_unit(table, rec, table_span, src, r, F, (int64_t)nrec * F, u, f0, f1, length);
 }
 
 // ---- mfh_merkle_write_keys: the located records' field before the batch (for the compare-and-set form alone), and the nk new records of a batch of writes
@@ -1103,22 +1088,6 @@ __global__ __launch_bounds__(256) void k_field_gather(const uint8_t *__restrict_
     out = merge_unit(out, load_unit_within(table, a, a + min((int64_t)16, F - o), span), o, 0, F);
   }
   field[g] = out;
-}
-
-// k_write_records, ONE launch per call: all nk new records of the batch into `fresh`, record j at j * pitch bytes (pitch = ceil(length / 16) units, 16-byte
-// aligned).  One item per record j and 16-byte unit u; the store is the whole unit.  Record j is the table's record plan[j] as it stood BEFORE the batch with
-// bytes [f0, f1) <- val[j F ..], the step's value.  A write overwrites the WHOLE field and nothing else of a record, so even where a key occurs in many steps
-// every source is the table before the batch or the uploaded values -- one launch, no ordering among the items, and the table is only read.  The unit is
-// k_transfer_records' and k_adjust_records' (refielded_unit), for any alignment, stride, K and field.  Bytes at or past `length`: zero.
-// Reads: nothing outside [table, table + table_span), [val, val + nk F) and the plan.
-__global__ __launch_bounds__(256) void k_write_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ val,
-                                                       const int32_t *__restrict__ plan, uint32_t f0, uint32_t f1, uint32_t length, uint32_t nk,
-                                                       uint4 *__restrict__ fresh) {
-  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nk units < 2^32: checked by the host)
-  if (g >= nk * units) return;
-  const uint32_t r = g / units, u = g - r * units;
-  const int64_t rec = (int64_t)((size_t)(uint32_t)plan[r] * table_stride), F = (int64_t)f1 - f0;
-  fresh[g] = refielded_unit(table, rec, table_span, val, r, F, (int64_t)nk * F, u, f0, f1, length);
 }
 
 // The supply: the sum of the balances of all LIVE records and their number, two launches, no atomics (integer addition: the result does not depend on the
@@ -1162,10 +1131,7 @@ __global__ __launch_bounds__(256) void k_balance_sum(const uint8_t *__restrict__
   if (i < n) {
     uint32_t lo[KW], hi[KW];
     if (load_record_keys<KW>(table, stride, span, key_bytes, i, lo, hi)) {
-      const int64_t a = (int64_t)((size_t)i * stride) + 2 * (int64_t)key_bytes;
-      const uint4 v = load_unit_within(table, a, a + amount_bytes, span);
-      const unsigned long long be = (unsigned long long)__builtin_bswap32(v.x) << 32 | __builtin_bswap32(v.y);  // byte 0 in the top 8 bits
-      s.lo = be >> (8 * (8 - amount_bytes));
+      s.lo = balance_at(table, (int64_t)((size_t)i * stride) + 2 * (int64_t)key_bytes, amount_bytes, span);
       s.live = 1;
     }
   }
@@ -1419,7 +1385,7 @@ int path_rows(mfh_ctx *c, const mfh_merkle *t, uint32_t n, const uint32_t *h_ind
 // k_merkle_update_level and the tree's write-back, `after` (if any) queues what has to follow that, the level rows, the heads and the roots come back, and
 // `rows_out` takes them from the pinned buffer with the stream idle.  On the device: V[0] (own leaves only) | V[1 .. depth], slots of ch nodes | level rows |
 // heads | the schedule (idx | last | same0 | sib[depth]).  Pinned: level rows | heads | R_b0, the chunk's new roots
-// A batch of key steps (pair_updates) drives the same body with `pairs`: chunks of whole steps (mf::pair_chunk: an even number of updates), the first
+// A batch of steps (step_updates) drives the same body with `pairs`: chunks of whole steps (mf::step_layout: a multiple of the step's updates), the first
 // `skip` bytes of the scratch (a multiple of 16, reserved by the caller with update_rows_bytes behind them) left to the caller, h_roots given every second root,
 // and rows_out = null for "no rows": then nothing but the roots comes back.
 // A cut call (mfh_merkle_*_cut) drives the same body with `cuts`: the schedule carries same_cut behind sib, k_merkle_cut_rows runs between the last level and the
@@ -1943,75 +1909,100 @@ int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch 
   return MFH_OK;
 }
 
-// What a batch of nk key steps keeps at the front of the scratch for the whole call: fresh = the 2 nk new records at a pitch of record_head_pitch(length) | the
-// plan, three words a step (its build kernel says which) | the keys, packed | the payloads, packed.  skip = their bytes rounded up to 16: behind them, one after the
-// other, the call's searches and per chunk update_rows' scratch.  ch: the updates a chunk -- whole steps, all segments' rows together
-struct PairScratch {
-  size_t fresh_bytes, plan_bytes, keys_bytes, pay_bytes, skip, rowb;
-  uint32_t ch;
-  size_t up_bytes() const { return plan_bytes + keys_bytes + pay_bytes; }
-};
+// The search of a batch of balance steps (transfers, adjusts), against the table before the batch, and the located records' balances behind it under the same
+// wait: rec[u] <- the record whose own key is unique key u, or kNoRecord, and balance[u] <- its balance (0 for no record).  At d_work: balance_search_bytes
+size_t balance_search_bytes(uint32_t nu, uint32_t key_bytes) { return key_search_tail_at(nu, key_bytes) + (size_t)nu * 8; }
 
-// lays that scratch out for rows of rowb bytes and payloads of plen bytes (0: none go up) and reserves it, with the larger of search_bytes -- the most any of
-// the caller's searches needs -- and update_rows' scratch behind the front
-int pair_reserve(mfh_ctx *c, const KeyCall &k, uint32_t depth, size_t rowb, size_t plen, size_t search_bytes, PairScratch &s) {
-  s.fresh_bytes = (size_t)2 * k.nk * mf::record_head_pitch(k.length);
-  s.plan_bytes = (size_t)k.nk * 3 * 4;
-  s.keys_bytes = (size_t)k.nk * k.key_bytes;
-  s.pay_bytes = (size_t)k.nk * plen;
-  s.skip = (s.fresh_bytes + s.up_bytes() + 15) & ~(size_t)15;
-  s.rowb = rowb;
-  s.ch = mf::pair_chunk(k.nk, rowb + (k.cuts ? 2 * mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
+int balance_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, uint32_t depth, uint32_t amount_bytes, uint8_t *d_work, std::vector<uint32_t> &rec,
+                   std::vector<uint64_t> &balance) {
+  const uint32_t nu = keys.nu;
+  const SearchTail gather{(size_t)nu * 8, [&](const uint32_t *d_res, uint8_t *d_out) {
+    Timer tm(c, 37, nu);  // "merkle_balances" (mfhip.hip: timing_kind)
+    hipLaunchKernelGGL(k_balance_gather, dim3((nu + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), k.key_bytes, amount_bytes, 1u << depth,
+                       d_res + nu, nu, reinterpret_cast<unsigned long long *>(d_out));
+  }};
+  const uint32_t *res;
+  if (int rc = key_search(c, k, keys, kLocate, depth, d_work, &res, &gather)) return rc;
+  rec.assign(res + nu, res + (size_t)2 * nu);
+  balance.resize(nu);
+  memcpy(balance.data(), res + (size_t)2 * nu, (size_t)nu * 8);
+  return MFH_OK;
+}
+
+// what the calls with a balance ask of amount_bytes and of the record's length
+const char *balance_refused(uint32_t length, uint32_t key_bytes, uint32_t amount_bytes) {
+  if (amount_bytes < 1 || amount_bytes > mf::kMaxAmountBytes) return "amount_bytes must be in [1, 8]";
+  if (length < 2 * key_bytes + amount_bytes) return "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes";
+  return nullptr;
+}
+
+// lays out the front of the scratch of a batch of nk steps of R record updates each (mf::step_layout: fresh | the plan, `words` words a step | the keys, if
+// they go up | payloads of plen bytes a step, 0: none) for rows of rowb bytes and reserves it, with the larger of search_bytes -- the most any of the caller's
+// searches needs -- and update_rows' scratch behind the front
+int step_reserve(mfh_ctx *c, const KeyCall &k, uint32_t depth, uint32_t R, uint32_t words, bool keys_up, size_t rowb, size_t plen, size_t search_bytes, mf::StepLayout &s) {
+  s = mf::step_layout(R, words, k.nk, k.length, keys_up ? k.key_bytes : 0, plen, rowb, depth, k.cuts ? k.cuts->ncuts : 0, k.cuts ? k.cuts->cuts : nullptr, kPathStageBytes);
   return work_reserve(c, c->circ_io, s.skip + std::max(search_bytes, update_rows_bytes(depth, s.ch, 2 * mf::record_head_pitch(k.length), 1, k.cuts)));
 }
 
-// the caller's splice of step j's row out of the pinned buffer: the heads (old | new record at a pitch of record_head_pitch) and the level rows of its updates p, s
-using PairSplice = std::function<void(uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s)>;
+// step j's pieces in the pinned buffer, for the caller's splice of its row: record update r < R of the step has its head (old | new record at a pitch of
+// record_head_pitch) and its level row
+struct StepRows {
+  uint32_t j;
+  const uint8_t *heads, *staged;
+  size_t hs, rs;
+  const uint8_t *head(uint32_t r) const { return heads + r * hs; }
+  const uint8_t *level_row(uint32_t r) const { return staged + r * rs; }
+};
+using StepSplice = std::function<void(const StepRows &)>;
 
-// the caller's build kernel, launched on the context's stream over `grid` workgroups of 256: the 2 nk new records into d_fresh from the plan, the packed keys
-// and payloads (d_pay = null: none went up) and the table before the batch
-using PairBuild = std::function<void(dim3 grid, const int32_t *d_plan, const uint8_t *d_keys, const uint8_t *d_pay, uint4 *d_fresh)>;
+// the caller's build kernel, launched on the context's stream over `grid` workgroups of 256: the R nk new records into d_fresh from the plan, the packed keys
+// (if they went up) and payloads (d_pay = null: none went up) and the table before the batch
+using StepBuild = std::function<void(dim3 grid, const int32_t *d_plan, const uint8_t *d_keys, const uint8_t *d_pay, uint4 *d_fresh)>;
 
-// What follows the plan in a batch of key steps.  The plan (three words a step), the keys and the payloads go up packed; the caller's build kernel, ONE launch
-// under the caller's timing kind, builds the 2 nk new records from the table before the batch; then the 2 nk record updates idx, a chunk of whole steps at a
-// time, row b of a chunk spliced out of the heads and the level rows of its updates 2 b and 2 b + 1
-int pair_updates(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const PairScratch &s, int build_kind, const PairBuild &build,
-                 const std::vector<int32_t> &plan, const std::vector<uint32_t> &idx, const uint8_t *h_payloads, size_t payload_stride, const PairSplice &splice) {
-  const uint32_t nk = k.nk, nupd = 2 * nk;
-  const size_t hp = mf::record_head_pitch(k.length), plen = s.pay_bytes / nk;
+// What follows the plan in a batch of steps.  The plan's words, the keys and the payloads go up packed; the caller's build kernel, ONE launch under the
+// caller's timing kind, builds the R nk new records from the table before the batch; then the R nk record updates idx, a chunk of whole steps at a time, step
+// b of a chunk spliced out of the heads and the level rows of its updates R b .. R b + R - 1
+int step_updates(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const mf::StepLayout &s, int build_kind, const StepBuild &build, const void *plan,
+                 const uint32_t *idx, const uint8_t *h_payloads, size_t payload_stride, const StepSplice &splice) {
+  const uint32_t nk = k.nk, R = s.R, nupd = R * nk;
+  const size_t hp = mf::record_head_pitch(k.length), klen = s.keys_bytes / nk, plen = s.pay_bytes / nk;
   uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + s.fresh_bytes, *d_keys = d_plan + s.plan_bytes, *d_pay = s.pay_bytes ? d_keys + s.keys_bytes : nullptr;
   {
     uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, s.up_bytes());
     if (!pin_up) return MFH_ENOMEM;
-    memcpy(pin_up, plan.data(), s.plan_bytes);
+    memcpy(pin_up, plan, s.plan_bytes);
     for (uint32_t j = 0; j < nk; j++) {
-      memcpy(pin_up + s.plan_bytes + (size_t)j * k.key_bytes, k.key(j), k.key_bytes);
+      if (klen) memcpy(pin_up + s.plan_bytes + (size_t)j * klen, k.key(j), klen);
       if (plen) memcpy(pin_up + s.plan_bytes + s.keys_bytes + (size_t)j * plen, h_payloads + (size_t)j * payload_stride, plen);
     }
     HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, s.up_bytes(), hipMemcpyHostToDevice, c->stream));
     pin_release(c, c->pin_rows);
   }
   {
-    Timer tm(c, build_kind, nupd);  // "merkle_insert_records", "merkle_remove_records" or "merkle_transfer_records" (mfhip.hip: timing_kind)
+    Timer tm(c, build_kind, nupd);  // "merkle_insert_records", "merkle_remove_records", "merkle_transfer_records", "merkle_adjust_records" or "merkle_write_records"
     const uint64_t items = (uint64_t)nupd * (hp / 16);
     build(dim3((uint32_t)((items + 255) / 256)), (const int32_t *)d_plan, d_keys, d_pay, reinterpret_cast<uint4 *>(d_fresh));
   }
   HIP_TRY(c, hipGetLastError());
-  const Pairs chunks{s.ch, s.skip, k.cuts != nullptr};
+  const Pairs chunks{s.ch, s.skip, k.cuts != nullptr || R == 1};
   ChunkFn rows_out;
   if (k.h_inputs)
     rows_out = [&](const Chunk &u) {
-      for (uint32_t b = 0; b + 1 < u.k; b += 2) {
-        const uint8_t *head_p = u.pin_heads + (size_t)b * u.hs, *staged_p = u.pin_rows + (size_t)b * u.rs;
-        splice((u.b0 + b) / 2, head_p, head_p + u.hs, staged_p, staged_p + u.rs);
-      }
+      for (uint32_t b = 0; b + R <= u.k; b += R) splice({(u.b0 + b) / R, u.pin_heads + (size_t)b * u.hs, u.pin_rows + (size_t)b * u.rs, u.hs, u.rs});
     };
-  return record_updates(c, t, nupd, idx.data(), d_table, k.table_stride, k.length, d_fresh, hp, k.h_roots, s.rowb, &chunks, rows_out, k.cuts);
+  return record_updates(c, t, nupd, idx, d_table, k.table_stride, k.length, d_fresh, hp, k.h_roots, s.rowb, &chunks, rows_out, k.cuts);
 }
 
-// the two refusals a batch of key steps shares behind keys_refused: the caller's own row checks, uncut (in_stride, with its text) or cut (segment 0 has nk
-// rows, the upper segments 2 nk: a null pointer is refused for either count)
-const char *pair_rows_refused(const KeyCall &k, uint32_t depth, size_t rowb, const char *short_stride) {
+// the one build launch of the steps that change one field [f0, f1) of a record, whose plan words start with a step's `per` record indices: k_refield_records
+StepBuild refield_build(mfh_ctx *c, const KeyCall &k, uint32_t depth, uint32_t per, uint32_t words, uint32_t f0, uint32_t f1) {
+  return [=, &k](dim3 grid, const int32_t *d_plan, const uint8_t *, const uint8_t *d_pay, uint4 *d_fresh) {
+    hipLaunchKernelGGL(k_refield_records, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), d_pay, d_plan, per, words, f0, f1, k.length, per * k.nk, d_fresh);
+  };
+}
+
+// the two refusals a batch of steps shares behind keys_refused: the caller's own row checks, uncut (in_stride, with its text) or cut (segment 0 has nk rows,
+// the upper segments R nk: a null pointer is refused for either count)
+const char *step_rows_refused(const KeyCall &k, uint32_t depth, size_t rowb, const char *short_stride) {
   if (k.cuts) return cuts_refused(k.nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
   return k.h_inputs && k.in_stride < rowb ? short_stride : nullptr;
 }
@@ -2267,7 +2258,7 @@ int insert_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
   const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(k.key_bytes, 3, length, d0, zeros);
   const std::string what = keys_refused(k, depth, "inserts", true, [&]() -> const char * {
     if (h_payloads && payload_stride < length - 2 * k.key_bytes) return "payload_stride shorter than the payload's length - 2 key_bytes bytes";
-    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
+    return step_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 3 length + 64 depth + ceil(2 depth / 8) bytes");
   });
   if (!what.empty()) return fail(c, k.who, what.c_str());
   if (!nk) return MFH_OK;
@@ -2278,8 +2269,8 @@ int insert_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
   // behind the batch's front, one after the other: the search, the inert search (mask words | count[nb] | total | slots[nk]), update_rows' scratch
   const uint32_t n = 1u << depth, nb = (n + 255) / 256;
   const size_t mask_bytes = (size_t)nb * 4 * 8, inert_bytes = mask_bytes + ((size_t)nb + 1 + nk) * 4;
-  PairScratch s;
-  if (int rc = pair_reserve(c, k, depth, rowb, h_payloads ? length - 2 * k.key_bytes : 0, std::max(key_search_bytes(nk, k.key_bytes), inert_bytes), s)) return rc;
+  mf::StepLayout s;
+  if (int rc = step_reserve(c, k, depth, 2, 3, true, rowb, h_payloads ? length - 2 * k.key_bytes : 0, std::max(key_search_bytes(nk, k.key_bytes), inert_bytes), s)) return rc;
   uint8_t *d_work = c->circ_io.as<uint8_t>() + s.skip;
   std::vector<uint32_t> located(nk), slots(nk);
   {  // a. the search: mfh_merkle_absent_rows', against the table before the batch
@@ -2338,10 +2329,9 @@ int insert_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
   // d. the 2 nk new records and their updates; a row: the key | old record of p | old record of s | new record of s
   const size_t hp = mf::record_head_pitch(length);
   const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
-  return pair_updates(c, t, k, d_table, s, 33, build, words, plan.idx, h_payloads, payload_stride,
-                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
-    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros, {{k.key(j), k.key_bytes}, {head_p, length}, {head_s, length}, {head_s + hp, length}}, staged_p, staged_s, d0,
-                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  return step_updates(c, t, k, d_table, s, 33, build, words.data(), plan.idx.data(), h_payloads, payload_stride, [&](const StepRows &u) {
+    mf::splice_pair_row(k.h_inputs + (size_t)u.j * k.in_stride, zeros, {{k.key(u.j), k.key_bytes}, {u.head(0), length}, {u.head(1), length}, {u.head(1) + hp, length}},
+                        u.level_row(0), u.level_row(1), d0, k.h_index[2 * (size_t)u.j] & low, k.h_index[2 * (size_t)u.j + 1] & low);
   });
 }
 
@@ -2351,7 +2341,7 @@ int remove_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table) {
   const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length;  // d0: the levels of the remove's own row
   const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(k.key_bytes, 2, length, d0, zeros);
   const std::string what = keys_refused(k, depth, "removes", true, [&] {
-    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
+    return step_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
   });
   if (!what.empty()) return fail(c, k.who, what.c_str());
   if (!nk) return MFH_OK;
@@ -2359,8 +2349,8 @@ int remove_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table) {
   mf::keys_prepare(k.h_keys, k.key_stride, k.key_bytes, nk, keys);
   if (keys.nu != nk) return fail(c, k.who, "a key is given twice");
   HIP_TRY(c, hipSetDevice(c->device));
-  PairScratch s;  // behind the batch's front: the search, then update_rows' scratch
-  if (int rc = pair_reserve(c, k, depth, rowb, 0, key_search_bytes(nk, k.key_bytes), s)) return rc;
+  mf::StepLayout s;  // behind the batch's front: the search, then update_rows' scratch
+  if (int rc = step_reserve(c, k, depth, 2, 3, true, rowb, 0, key_search_bytes(nk, k.key_bytes), s)) return rc;
   std::vector<uint32_t> own(nk), prev(nk);
   {  // a. the search, against the table before the batch: own | prev per UNIQUE sorted key, back to the caller's order
     const uint32_t *res;
@@ -2394,10 +2384,9 @@ int remove_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table) {
   };
   // c. the 2 nk new records and their updates; a row: the key | old record of P | old record of s
   const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
-  return pair_updates(c, t, k, d_table, s, 36, build, words, plan.idx, nullptr, 0,
-                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
-    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros, {{k.key(j), k.key_bytes}, {head_p, length}, {head_s, length}}, staged_p, staged_s, d0,
-                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  return step_updates(c, t, k, d_table, s, 36, build, words.data(), plan.idx.data(), nullptr, 0, [&](const StepRows &u) {
+    mf::splice_pair_row(k.h_inputs + (size_t)u.j * k.in_stride, zeros, {{k.key(u.j), k.key_bytes}, {u.head(0), length}, {u.head(1), length}}, u.level_row(0), u.level_row(1), d0,
+                        k.h_index[2 * (size_t)u.j] & low, k.h_index[2 * (size_t)u.j + 1] & low);
   });
 }
 
@@ -2407,9 +2396,8 @@ int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table,
   const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes, A = amount_bytes;  // d0: the levels of the transfer's own row
   const size_t zeros = k.cuts ? 128 : 64, rowb = mf::pair_row_bytes(2 * K + A, 2, length, d0, zeros);
   const std::string what = keys_refused(k, depth, "transfers", true, [&]() -> const char * {
-    if (A < 1 || A > mf::kMaxAmountBytes) return "amount_bytes must be in [1, 8]";
-    if (length < 2 * K + A) return "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes";
-    return pair_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + 2 key_bytes + amount_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
+    if (const char *what = balance_refused(length, K, A)) return what;
+    return step_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + 2 key_bytes + amount_bytes + 2 length + 64 depth + ceil(2 depth / 8) bytes");
   }, false);  // (2 nk below 2^32 by the check of the new records' units)
   if (!what.empty()) return fail(c, k.who, what.c_str());
   if (nk && (!h_to || !h_amounts)) return fail(c, k.who, !h_to ? "transfers without h_to" : "transfers without h_amounts");
@@ -2429,23 +2417,14 @@ int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table,
   }
   mf::KeyPlan keys;
   mf::keys_prepare(both.data(), K, K, 2 * nk, keys);
-  const uint32_t nu = keys.nu, n = 1u << depth;
+  const uint32_t nu = keys.nu;
   HIP_TRY(c, hipSetDevice(c->device));
-  PairScratch s;  // behind the batch's front: the search and the nu balances behind it, then update_rows' scratch
-  if (int rc = pair_reserve(c, k, depth, rowb, 2 * A, key_search_tail_at(nu, K) + (size_t)nu * 8, s)) return rc;
-  std::vector<uint32_t> rec(nu), from(nk), to(nk);
-  std::vector<uint64_t> balance(nu);
-  {  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
-    const SearchTail gather{(size_t)nu * 8, [&](const uint32_t *d_res, uint8_t *d_out) {
-      Timer tm(c, 37, nu);  // "merkle_balances" (mfhip.hip: timing_kind)
-      hipLaunchKernelGGL(k_balance_gather, dim3((nu + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), K, A, n, d_res + nu, nu,
-                         reinterpret_cast<unsigned long long *>(d_out));
-    }};
-    const uint32_t *res;
-    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + s.skip, &res, &gather)) return rc;
-    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
-    memcpy(balance.data(), res + (size_t)2 * nu, (size_t)nu * 8);
-  }
+  mf::StepLayout s;  // behind the batch's front: the search and the nu balances behind it, then update_rows' scratch
+  if (int rc = step_reserve(c, k, depth, 2, 3, true, rowb, 2 * A, balance_search_bytes(nu, K), s)) return rc;
+  std::vector<uint32_t> rec, from(nk), to(nk);
+  std::vector<uint64_t> balance;
+  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
+  if (int rc = balance_search(c, k, keys, depth, A, c->circ_io.as<uint8_t>() + s.skip, rec, balance)) return rc;
   // b. the plan: the running balance of every account through the steps in order -- (p, s) and the two new balances of every transfer, its status
   for (uint32_t j = 0; j < nk; j++) {
     from[j] = keys.slot[2 * (size_t)j];
@@ -2466,7 +2445,7 @@ int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table,
                                       "a transfer takes its receiver's balance past 2^(8 amount_bytes) - 1 (h_status 4)"};
     return fail(c, k.who, why[plan.status[first]]);
   }
-  // what k_transfer_records reads: (p, s, spare) a transfer, and in the payloads' place the two new balances, A big-endian bytes each
+  // what k_refield_records reads: (p, s, spare) a transfer, and in the payloads' place the two new balances, A big-endian bytes each
   std::vector<int32_t> words((size_t)3 * nk);
   std::vector<uint8_t> fresh((size_t)2 * nk * A);
   for (uint32_t j = 0; j < nk; j++) {
@@ -2476,32 +2455,24 @@ int transfer_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table,
     mf::balance_bytes(plan.fresh[2 * (size_t)j], A, fresh.data() + (size_t)2 * j * A);
     mf::balance_bytes(plan.fresh[2 * (size_t)j + 1], A, fresh.data() + ((size_t)2 * j + 1) * A);
   }
-  auto build = [&](dim3 grid, const int32_t *d_plan, const uint8_t *, const uint8_t *d_pay, uint4 *d_fresh) {
-    hipLaunchKernelGGL(k_transfer_records, grid, dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), d_pay, d_plan, K, A, length, nk, d_fresh);
-  };
   // c. the 2 nk new records and their updates; a row: k_from | k_to | v | old record of p | old record of s
   const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: both indices mod 2^d0
-  return pair_updates(c, t, k, d_table, s, 38, build, words, plan.idx, fresh.data(), (size_t)2 * A,
-                      [&](uint32_t j, const uint8_t *head_p, const uint8_t *head_s, const uint8_t *staged_p, const uint8_t *staged_s) {
-    mf::splice_pair_row(k.h_inputs + (size_t)j * k.in_stride, zeros,
-                        {{k.key(j), K}, {h_to + (size_t)j * k.key_stride, K}, {amounts.data() + (size_t)j * A, A}, {head_p, length}, {head_s, length}}, staged_p, staged_s, d0,
-                        k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+  return step_updates(c, t, k, d_table, s, 38, refield_build(c, k, depth, 2, 3, 2 * K, 2 * K + A), words.data(), plan.idx.data(), fresh.data(), (size_t)2 * A, [&](const StepRows &u) {
+    mf::splice_pair_row(k.h_inputs + (size_t)u.j * k.in_stride, zeros,
+                        {{k.key(u.j), K}, {h_to + (size_t)u.j * k.key_stride, K}, {amounts.data() + (size_t)u.j * A, A}, {u.head(0), length}, {u.head(1), length}}, u.level_row(0),
+                        u.level_row(1), d0, k.h_index[2 * (size_t)u.j] & low, k.h_index[2 * (size_t)u.j + 1] & low);
   });
 }
 
 // mfh_merkle_adjust_keys (k.cuts = null: one row of the whole depth a step) and mfh_merkle_adjust_keys_cut (segment 0's row an adjust over c_0 levels to
-// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  A step is ONE record update, so this is the
-// one-record driver beside pair_reserve / pair_updates, whose scratch, chunks and launches stay what they are.  The front of the scratch, kept for the whole
-// call: fresh = the nk new records at a pitch of record_head_pitch(length) | the plan, one word a step | the nk new balances, A bytes each; behind its bytes
-// rounded up to 16 the search with the nu balances behind it, then per chunk update_rows' scratch.
+// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  A step is ONE record update: the step driver with
+// R = 1, one plan word a step, no keys on the device and the nk new balances, A bytes each, as the payloads.
 int adjust_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const uint64_t *h_amounts, const uint8_t *h_sides, uint32_t amount_bytes) {
   const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes, A = amount_bytes;  // d0: the levels of the adjust's own row
   const size_t rowb = mf::row_bytes(64, (size_t)K + A + 1 + length, d0);
   const std::string what = keys_refused(k, depth, "adjusts", true, [&]() -> const char * {
-    if (A < 1 || A > mf::kMaxAmountBytes) return "amount_bytes must be in [1, 8]";
-    if (length < 2 * K + A) return "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes";
-    if (k.cuts) return cuts_refused(nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
-    return k.h_inputs && k.in_stride < rowb ? "in_stride shorter than the row's 64 + key_bytes + amount_bytes + 1 + length + 32 depth + ceil(depth / 8) bytes" : nullptr;
+    if (const char *what = balance_refused(length, K, A)) return what;
+    return step_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + amount_bytes + 1 + length + 32 depth + ceil(depth / 8) bytes");
   }, false);
   if (!what.empty()) return fail(c, k.who, what.c_str());
   if (nk && !h_amounts) return fail(c, k.who, "adjusts without h_amounts");
@@ -2512,25 +2483,13 @@ int adjust_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
   if (!nk) return MFH_OK;
   mf::KeyPlan keys;
   mf::keys_prepare(k.h_keys, k.key_stride, K, nk, keys);
-  const uint32_t nu = keys.nu, n = 1u << depth;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t hp = mf::record_head_pitch(length), fresh_bytes = (size_t)nk * hp, plan_bytes = (size_t)nk * 4, bal_bytes = (size_t)nk * A;
-  const size_t skip = (fresh_bytes + plan_bytes + bal_bytes + 15) & ~(size_t)15;
-  const uint32_t ch = mf::update_chunk(nk, rowb + (k.cuts ? mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
-  if (int rc = work_reserve(c, c->circ_io, skip + std::max(key_search_tail_at(nu, K) + (size_t)nu * 8, update_rows_bytes(depth, ch, 2 * hp, 1, k.cuts)))) return rc;
-  std::vector<uint32_t> rec(nu);
-  std::vector<uint64_t> balance(nu);
-  {  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
-    const SearchTail gather{(size_t)nu * 8, [&](const uint32_t *d_res, uint8_t *d_out) {
-      Timer tm(c, 37, nu);  // "merkle_balances" (mfhip.hip: timing_kind)
-      hipLaunchKernelGGL(k_balance_gather, dim3((nu + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), K, A, n, d_res + nu, nu,
-                         reinterpret_cast<unsigned long long *>(d_out));
-    }};
-    const uint32_t *res;
-    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + skip, &res, &gather)) return rc;
-    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
-    memcpy(balance.data(), res + (size_t)2 * nu, (size_t)nu * 8);
-  }
+  mf::StepLayout s;  // behind the batch's front: the search and the nu balances behind it, then update_rows' scratch
+  if (int rc = step_reserve(c, k, depth, 1, 1, false, rowb, A, balance_search_bytes(keys.nu, K), s)) return rc;
+  std::vector<uint32_t> rec;
+  std::vector<uint64_t> balance;
+  // a. the search, against the table before the batch, and the located records' balances behind it: one wait for both
+  if (int rc = balance_search(c, k, keys, depth, A, c->circ_io.as<uint8_t>() + s.skip, rec, balance)) return rc;
   // b. the plan: the running balance of every account through the steps in order
   mf::AdjustPlan plan;
   mf::adjust_plan(nk, keys.slot.data(), h_amounts, h_sides, A, rec.data(), balance.data(), plan);
@@ -2543,41 +2502,19 @@ int adjust_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, c
     while (!plan.status[first]) first++;
     return fail(c, k.who, why[plan.status[first]]);
   }
-  // c. the plan's words and the nk new balances go up; ONE launch builds the nk new records
-  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_bal = d_plan + plan_bytes;
-  std::vector<uint8_t> amounts((size_t)nk * A);
-  {
-    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, plan_bytes + bal_bytes);
-    if (!pin_up) return MFH_ENOMEM;
-    memcpy(pin_up, plan.idx.data(), plan_bytes);
-    for (uint32_t j = 0; j < nk; j++) {
-      mf::balance_bytes(plan.fresh[j], A, pin_up + plan_bytes + (size_t)j * A);
-      mf::balance_bytes(h_amounts[j], A, amounts.data() + (size_t)j * A);
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, plan_bytes + bal_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
+  // c. what k_refield_records reads: the record of every step, and in the payloads' place its account's balance right after it, A big-endian bytes
+  std::vector<uint8_t> fresh((size_t)nk * A), amounts((size_t)nk * A);
+  for (uint32_t j = 0; j < nk; j++) {
+    mf::balance_bytes(plan.fresh[j], A, fresh.data() + (size_t)j * A);
+    mf::balance_bytes(h_amounts[j], A, amounts.data() + (size_t)j * A);
   }
-  {
-    Timer tm(c, 42, nk);  // "merkle_adjust_records" (mfhip.hip: timing_kind)
-    const uint64_t items = (uint64_t)nk * (hp / 16);
-    hipLaunchKernelGGL(k_adjust_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), (const uint8_t *)d_bal,
-                       (const int32_t *)d_plan, K, A, length, nk, reinterpret_cast<uint4 *>(d_fresh));
-  }
-  HIP_TRY(c, hipGetLastError());
-  // d. the nk record updates; a row: k | v | side | the old record
-  const Pairs chunks{ch, skip, true};
-  ChunkFn rows_out;
-  if (k.h_inputs)
-    rows_out = [&](const Chunk &u) {
-      for (uint32_t b = 0; b < u.k; b++) {
-        const uint32_t j = u.b0 + b;
-        const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs, side = h_sides ? h_sides[j] : (uint8_t)0;
-        uint8_t *row = k.h_inputs + (size_t)j * k.in_stride;
-        mf::splice_row(row, 64, {{k.key(j), K}, {amounts.data() + (size_t)j * A, A}, {&side, 1}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
-        if (k.cuts) mf::splice_cut_tail(row + 64 + K + A + 1 + (size_t)length, staged, d0, k.h_index[j]);
-      }
-    };
-  return record_updates(c, t, nk, k.h_index, d_table, k.table_stride, length, d_fresh, hp, k.h_roots, rowb, &chunks, rows_out, k.cuts);
+  // d. the nk new records and their updates; a row: k | v | side | the old record
+  return step_updates(c, t, k, d_table, s, 42, refield_build(c, k, depth, 1, 1, 2 * K, 2 * K + A), plan.idx.data(), plan.idx.data(), fresh.data(), A, [&](const StepRows &u) {
+    const uint8_t side = h_sides ? h_sides[u.j] : (uint8_t)0;
+    uint8_t *row = k.h_inputs + (size_t)u.j * k.in_stride;
+    mf::splice_row(row, 64, {{k.key(u.j), K}, {amounts.data() + (size_t)u.j * A, A}, {&side, 1}, {u.head(0), length}}, k.cuts ? nullptr : u.level_row(0), 128, depth);
+    if (k.cuts) mf::splice_cut_tail(row + 64 + K + A + 1 + (size_t)length, u.level_row(0), d0, k.h_index[u.j]);
+  });
 }
 
 // the field and the step values of a batch of writes: bytes [lo, hi) of a record, value j the hi - lo bytes at values + j * value_stride, and with `expect` the
@@ -2591,9 +2528,8 @@ struct WriteArgs {
 };
 
 // mfh_merkle_write_keys (k.cuts = null: one row of the whole depth a step) and mfh_merkle_write_keys_cut (segment 0's row a write over c_0 levels to
-// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  adjust_keys' one-record driver: the front of the
-// scratch, kept for the whole call, is fresh = the nk new records at a pitch of record_head_pitch(length) | the plan, one word a step | the nk values, F bytes
-// each; behind its bytes rounded up to 16 the search, with expectations the nu field slots behind it, then per chunk update_rows' scratch.
+// cuts->h_rows[0] = k.h_inputs, ONE MerkleSegment row a step and upper segment); nk + 1 roots either way.  A step is ONE record update: the step driver with
+// R = 1, one plan word a step, no keys on the device and the nk values, F bytes each, as the payloads.
 int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const WriteArgs &w) {
   const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes;  // d0: the levels of the write's own row
   const uint32_t F = w.hi > w.lo ? w.hi - w.lo : 0;
@@ -2604,9 +2540,7 @@ int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, co
     if (w.hi > length) return "field_hi above length";
     if (w.value_stride < F) return "value_stride shorter than the field's field_hi - field_lo bytes";
     if (w.expect && w.expect_stride < F) return "expect_stride shorter than the field's field_hi - field_lo bytes";
-    if (k.cuts) return cuts_refused(nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, rowb);
-    return k.h_inputs && k.in_stride < rowb ? "in_stride shorter than the row's 64 + key_bytes + the field's bytes (twice with h_expect) + length + 32 depth + ceil(depth / 8) bytes"
-                                            : nullptr;
+    return step_rows_refused(k, depth, rowb, "in_stride shorter than the row's 64 + key_bytes + the field's bytes (twice with h_expect) + length + 32 depth + ceil(depth / 8) bytes");
   }, false);
   if (!what.empty()) return fail(c, k.who, what.c_str());
   if (nk && !w.values) return fail(c, k.who, "writes without h_values");
@@ -2615,11 +2549,9 @@ int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, co
   mf::keys_prepare(k.h_keys, k.key_stride, K, nk, keys);
   const uint32_t nu = keys.nu, n = 1u << depth;
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t hp = mf::record_head_pitch(length), fresh_bytes = (size_t)nk * hp, plan_bytes = (size_t)nk * 4, val_bytes = (size_t)nk * F;
-  const size_t skip = (fresh_bytes + plan_bytes + val_bytes + 15) & ~(size_t)15;
   const size_t slot = mf::field_slot_bytes(F), gather_bytes = w.expect ? (size_t)nu * slot : 0;
-  const uint32_t ch = mf::update_chunk(nk, rowb + (k.cuts ? mf::cut_rows_bytes(depth, k.cuts->ncuts, k.cuts->cuts) : 0), kPathStageBytes);
-  if (int rc = work_reserve(c, c->circ_io, skip + std::max(key_search_tail_at(nu, K) + gather_bytes, update_rows_bytes(depth, ch, 2 * hp, 1, k.cuts)))) return rc;
+  mf::StepLayout s;  // behind the batch's front: the search, with expectations the nu field slots behind it, then update_rows' scratch
+  if (int rc = step_reserve(c, k, depth, 1, 1, false, rowb, F, key_search_tail_at(nu, K) + gather_bytes, s)) return rc;
   std::vector<uint32_t> rec(nu);
   std::vector<uint8_t> field(gather_bytes);
   {  // a. the search, against the table before the batch; with expectations the located records' field behind it, under the same wait
@@ -2630,7 +2562,7 @@ int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, co
                          reinterpret_cast<uint4 *>(d_out));
     }};
     const uint32_t *res;
-    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + skip, &res, w.expect ? &gather : nullptr)) return rc;
+    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + s.skip, &res, w.expect ? &gather : nullptr)) return rc;
     memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
     if (gather_bytes) memcpy(field.data(), res + (size_t)2 * nu, gather_bytes);
   }
@@ -2641,38 +2573,14 @@ int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, co
   memcpy(k.h_status, plan.status.data(), nk);
   if (plan.failed)
     return fail(c, k.who, plan.status[plan.first] == 1 ? "a key is not a member of the set (h_status 1)" : "a field is not what was expected at that step (h_status 5)");
-  // c. the plan's words and the nk values go up; ONE launch builds the nk new records
-  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_plan = d_fresh + fresh_bytes, *d_val = d_plan + plan_bytes;
-  {
-    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, plan_bytes + val_bytes);
-    if (!pin_up) return MFH_ENOMEM;
-    memcpy(pin_up, plan.idx.data(), plan_bytes);
-    for (uint32_t j = 0; j < nk; j++) memcpy(pin_up + plan_bytes + (size_t)j * F, w.values + (size_t)j * w.value_stride, F);
-    HIP_TRY(c, hipMemcpyAsync(d_plan, pin_up, plan_bytes + val_bytes, hipMemcpyHostToDevice, c->stream));
-    pin_release(c, c->pin_rows);
-  }
-  {
-    Timer tm(c, 50, nk);  // "merkle_write_records" (mfhip.hip: timing_kind)
-    const uint64_t items = (uint64_t)nk * (hp / 16);
-    hipLaunchKernelGGL(k_write_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), (const uint8_t *)d_val,
-                       (const int32_t *)d_plan, w.lo, w.hi, length, nk, reinterpret_cast<uint4 *>(d_fresh));
-  }
-  HIP_TRY(c, hipGetLastError());
-  // d. the nk record updates; a row: k | [e |] v | the old record
-  const Pairs chunks{ch, skip, true};
-  ChunkFn rows_out;
-  if (k.h_inputs)
-    rows_out = [&](const Chunk &u) {
-      for (uint32_t b = 0; b < u.k; b++) {
-        const uint32_t j = u.b0 + b;
-        const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs;
-        uint8_t *row = k.h_inputs + (size_t)j * k.in_stride;
-        const mf::RowPiece e{w.expect ? w.expect + (size_t)j * w.expect_stride : nullptr, w.expect ? F : 0};
-        mf::splice_row(row, 64, {{k.key(j), K}, e, {w.values + (size_t)j * w.value_stride, F}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
-        if (k.cuts) mf::splice_cut_tail(row + 64 + pub + length, staged, d0, k.h_index[j]);
-      }
-    };
-  return record_updates(c, t, nk, k.h_index, d_table, k.table_stride, length, d_fresh, hp, k.h_roots, rowb, &chunks, rows_out, k.cuts);
+  // c. the nk new records (k_refield_records reads the record of every step and, in the payloads' place, its value) and their updates; a row: k | [e |] v | the
+  // old record
+  return step_updates(c, t, k, d_table, s, 50, refield_build(c, k, depth, 1, 1, w.lo, w.hi), plan.idx.data(), plan.idx.data(), w.values, w.value_stride, [&](const StepRows &u) {
+    uint8_t *row = k.h_inputs + (size_t)u.j * k.in_stride;
+    const mf::RowPiece e{w.expect ? w.expect + (size_t)u.j * w.expect_stride : nullptr, w.expect ? F : 0};
+    mf::splice_row(row, 64, {{k.key(u.j), K}, e, {w.values + (size_t)u.j * w.value_stride, F}, {u.head(0), length}}, k.cuts ? nullptr : u.level_row(0), 128, depth);
+    if (k.cuts) mf::splice_cut_tail(row + 64 + pub + length, u.level_row(0), d0, k.h_index[u.j]);
+  });
 }
 
 }  // namespace
@@ -2725,8 +2633,7 @@ int mfh_merkle_balance_sum(mfh_ctx *c, const mfh_merkle *t, const uint8_t *d_tab
   const char *who = "mfh_merkle_balance_sum";
   if (int rc = tree_refused(c, t, who)) return rc;
   if (key_bytes < 1 || key_bytes > mf::kMaxKeyBytes) return fail(c, who, "key_bytes must be in [1, 32]");
-  if (amount_bytes < 1 || amount_bytes > mf::kMaxAmountBytes) return fail(c, who, "amount_bytes must be in [1, 8]");
-  if (length < 2 * key_bytes + amount_bytes) return fail(c, who, "length shorter than the two keys and the balance, 2 key_bytes + amount_bytes bytes");
+  if (const char *what = balance_refused(length, key_bytes, amount_bytes)) return fail(c, who, what);
   if (const char *what = records_refused(nullptr, table_stride, length, 0, "table_stride shorter than length")) return fail(c, who, what);
   if (!d_table) return fail(c, who, "a sum without d_table");
   if (!h_sum) return fail(c, who, "a sum without h_sum");

@@ -135,6 +135,31 @@ inline ClimbPlan climb_plan(uint32_t depth, uint32_t ncuts, const uint32_t *cuts
 // even, so both updates of a step are in one chunk even when one row alone exceeds the stage
 inline uint32_t pair_chunk(uint32_t nk, size_t row_bytes, size_t stage_bytes) { return 2 * update_chunk(nk, row_bytes, stage_bytes); }
 
+// What a batch of nk steps of R record updates each (R = 2: insert, remove, transfer; R = 1: adjust, write) keeps at the front of the device scratch for the
+// whole call: fresh = the R nk new records at a pitch of record_head_pitch(length) | the plan, `words` words a step (the step's build kernel says which) | the
+// keys, key_bytes a step, packed (0: none go up) | the payloads, pay a step, packed (0: none).  skip = their bytes rounded up to 16: behind them, one after the
+// other, the call's searches and per chunk the updates' scratch.  ch: the updates a chunk -- whole steps whose rows of rowb bytes and, of a path cut at
+// cuts[0 .. ncuts) (ncuts = 0: uncut), R MerkleSegment rows an upper segment fit the stage together, at least one step
+struct StepLayout {
+  uint32_t R, ch;
+  size_t fresh_bytes, plan_bytes, keys_bytes, pay_bytes, skip, rowb;
+  size_t up_bytes() const { return plan_bytes + keys_bytes + pay_bytes; }  // what goes up: all but fresh, which the build kernel writes
+};
+
+inline StepLayout step_layout(uint32_t R, uint32_t words, uint32_t nk, uint32_t length, size_t key_bytes, size_t pay, size_t rowb, uint32_t depth, uint32_t ncuts,
+                              const uint32_t *cuts, size_t stage_bytes) {
+  StepLayout s{};
+  s.R = R;
+  s.fresh_bytes = (size_t)R * nk * record_head_pitch(length);
+  s.plan_bytes = (size_t)nk * words * 4;
+  s.keys_bytes = (size_t)nk * key_bytes;
+  s.pay_bytes = (size_t)nk * pay;
+  s.skip = (s.fresh_bytes + s.up_bytes() + 15) & ~(size_t)15;
+  s.rowb = rowb;
+  s.ch = R * update_chunk(nk, rowb + R * cut_rows_bytes(depth, ncuts, cuts), stage_bytes);
+  return s;
+}
+
 struct RowPiece {
   const uint8_t *p;
   size_t bytes;

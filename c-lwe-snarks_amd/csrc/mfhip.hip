@@ -1167,18 +1167,18 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_owners")) return 35;  // k_key_owners of mfh_merkle_remove_keys (merkle.hip): one per call; rows = the table's 2^depth records
   if (!strcmp(which, "merkle_remove_records")) return 36;  // k_remove_records of mfh_merkle_remove_keys: one per call; rows = the 2 nk new records
   if (!strcmp(which, "merkle_balances")) return 37;  // k_balance_gather of mfh_merkle_transfer_keys (merkle.hip): one per call; rows = the batch's unique keys
-  if (!strcmp(which, "merkle_transfer_records")) return 38;  // k_transfer_records of mfh_merkle_transfer_keys: one per call; rows = the 2 nk new records
+  if (!strcmp(which, "merkle_transfer_records")) return 38;  // k_refield_records of mfh_merkle_transfer_keys (merkle.hip): one per call; rows = the 2 nk new records
   if (!strcmp(which, "merkle_climb_rows")) return 39;  // k_merkle_climb_rows of the cut reads (mfh_merkle_paths_cut, mfh_merkle_absent_rows_cut): one per chunk; rows = the chunk's statements x segments
   if (!strcmp(which, "merkle_range")) return 40;  // k_range_flags, k_inert_scan, k_inert_select of the range reads (mfh_merkle_range_rows, _cut): three per call, two for the count query; rows = the table's 2^depth records on the first
   if (!strcmp(which, "merkle_range_order")) return 41;  // k_range_keys, k_range_order of the range reads: two per call with max_links > 0; rows = max_links, the grids' bound (the links n are on the device at launch; n when the count was asked first)
-  if (!strcmp(which, "merkle_adjust_records")) return 42;  // k_adjust_records of mfh_merkle_adjust_keys (merkle.hip): one per call; rows = the nk new records
+  if (!strcmp(which, "merkle_adjust_records")) return 42;  // k_refield_records of mfh_merkle_adjust_keys (merkle.hip): one per call; rows = the nk new records
   if (!strcmp(which, "merkle_balance_sum")) return 43;  // k_balance_sum, k_balance_fold of mfh_merkle_balance_sum: two per call; rows = the table's 2^depth records on the first, 0 on the fold
   if (!strcmp(which, "merkle_sort")) return 44;  // k_sort_tiles, k_sort_merge of key_sort (merkle.hip): 1 + ceil(log2(ceil(n / 1024))) per sort of n > 0 entries; rows = n on each
   if (!strcmp(which, "merkle_load")) return 45;  // k_load_entries, k_load_dups, k_load_dup_tags, k_load_records of mfh_merkle_load_keys: three in front of the wait (nk > 0) and the build launch behind it; rows = nk, nk, 0 and the table's 2^depth records
   if (!strcmp(which, "merkle_check")) return 46;  // mfh_merkle_check_table: flags, scan, select, keys (4), entries and chain (2, live > 0), leaves (1), nodes (depth); rows = the records, live records or nodes each covers
   if (!strcmp(which, "merkle_grow")) return 47;  // k_grow_nodes, k_grow_spine, k_grow_table of mfh_merkle_grow / mfh_merkle_grow_leaves (merkle.hip): 3 per call with a table and 2 without; rows = the new tree's 2^(new_depth + 1) nodes, the new_depth - depth spine nodes and the new table's 2^new_depth records
   if (!strcmp(which, "merkle_fields")) return 49;  // k_field_gather of mfh_merkle_write_keys with expectations (merkle.hip): one per call, none for plain writes; rows = the unique keys
-  if (!strcmp(which, "merkle_write_records")) return 50;  // k_write_records of mfh_merkle_write_keys: one per call; rows = the nk new records
+  if (!strcmp(which, "merkle_write_records")) return 50;  // k_refield_records of mfh_merkle_write_keys (merkle.hip): one per call; rows = the nk new records
   return -1;
 }
 

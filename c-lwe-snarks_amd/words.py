@@ -1370,7 +1370,56 @@ class MerkleTransfer(_KeyStep):
         return self._step_bits((k_from, k_to, amount), (old_p, old_s), siblings_p, index_p, siblings_s, index_s)
 
 
-class MerkleAdjust(_TwoRoots):
+class _RecordStep(_TwoRoots):
+    """Private base of MerkleAdjust and MerkleWrite: ONE record update by key under a pair of roots, the new record the old one's wires with one field
+    replaced, the key and the step's other public pieces (self.public; _public) behind the roots.  A subclass's __init__ is _open, its further public pieces
+    and its new record, _close, then its own assertions with _assert_key and _assert_live among them in ITS order: that of the compiled program's."""
+
+    def _open(self, key_bytes, length, depth, least: int):
+        """the checks of key_bytes, length (the two keys and `least` bytes) and depth; the private wires (the old record, _tail_wires); the key's public wires.
+        The public pieces are read by the new record's gates: the subclass declares its others next, and _close moves them all behind the roots"""
+        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
+        self.length = self._arg(length, 2 * K + least, None, f"the length is at least 2 key_bytes + {least} bytes")
+        self.depth = self._depth_arg(depth)
+        self.w = w = Words()
+        self.old_record = w.c.private(8 * self.length)
+        self._tail_wires()
+        self.key = w.c.public(8 * K)
+        return w
+
+    def _close(self, new_record, *pieces):
+        """the two record chains, MerkleUpdate's two level chains over the shared tail and the roots' outputs; the key and then `pieces` go behind the roots"""
+        self.new_record = new_record
+        self.old_leaf, self.blocks = _message_chain(self.w, self.old_record, self.length)
+        self.new_leaf, _ = _message_chain(self.w, self.new_record, self.length)
+        self._root_outputs(self.old_leaf, self.new_leaf)
+        self.public = [x for piece in (self.key,) + pieces for x in piece]
+        self.w.c.public_last(self.public)
+
+    def _assert_key(self):  # k = old[0, K)
+        for x, y in zip(self.key, self.old_record[: 8 * self.key_bytes]):
+            self.w.c.assert_same(x, y)
+
+    def _assert_live(self):  # less_than(lo, hi) = 1: the record is live
+        K = self.key_bytes
+        lo, hi = (_key_bits_lsb_first(part, K) for part in (self.old_record[: 8 * K], self.old_record[8 * K: 16 * K]))
+        self.w.c.assert_equal(self.w.less_than(lo, hi), 1)
+
+    @property
+    def lu(self) -> int:
+        return 512 + len(self.public)
+
+    def _step_bits(self, public: bytes, old_record, siblings, index):  # the bits of: 64 zero bytes | the checked public bytes | the old record | the tail
+        who = type(self).__name__
+        return _input_bits(512, np.unpackbits(np.frombuffer(public, dtype=np.uint8), bitorder="little"), _record_bits(who, self.length, old_record),
+                           _tail_bits(who, self.depth, siblings, index))
+
+    def statement(self, old_root: bytes, new_root: bytes, *pieces) -> bytes:
+        """the lu / 8 statement bytes (what verify_public takes, bits [0, lu) of a witness row): MerkleUpdate.statement's, then the pieces' checked bytes"""
+        return super().statement(old_root, new_root) + self._public(*pieces)
+
+
+class MerkleAdjust(_RecordStep):
     """The statement "the balance of the account with key k went up by v (side 0, a deposit) or down by v (side 1, a withdrawal), and that alone takes the
     tree from root R to root R'": ONE record update of the indexed table with balances -- what funds and drains the ledger that MerkleTransfer moves
     value within.
@@ -1405,14 +1454,8 @@ class MerkleAdjust(_TwoRoots):
 
     def __init__(self, key_bytes: int, length: int, depth: int, amount_bytes=8):
         self.amount_bytes = A = self._arg(amount_bytes, 1, 8, "amount_bytes is in [1, 8]")
-        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
-        self.length = length = self._arg(length, 2 * K + A, None, f"the length is at least 2 key_bytes + {A} bytes")
-        self.depth = self._depth_arg(depth)
-        self.w = w = Words()
-        self.old_record = w.c.private(8 * length)
-        self._tail_wires()
-        # the public pieces are read by the balance's gates, so they are declared here and moved behind the roots below
-        self.key, self.amount, self.side = w.c.public(8 * K), w.c.public(8 * A), w.c.public(8)
+        w, K = self._open(key_bytes, length, depth, A), self.key_bytes
+        self.amount, self.side = w.c.public(8 * A), w.c.public(8)
         field = slice(16 * K, 16 * K + 8 * A)
         v, b = _key_bits_lsb_first(self.amount, A), _key_bits_lsb_first(self.old_record[field], A)
         side = self.side[0]
@@ -1422,22 +1465,13 @@ class MerkleAdjust(_TwoRoots):
             bits.append(s)
         self.carry = carry
         # `bits` least significant first, back into the record's byte order
-        self.new_record = self.old_record[: field.start] + [bits[8 * (A - 1 - j) + i] for j in range(A) for i in range(8)] + self.old_record[field.stop:]
-        self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
-        self.new_leaf, _ = _message_chain(w, self.new_record, length)
-        self._root_outputs(self.old_leaf, self.new_leaf)
-        w.c.public_last(self.key + self.amount + self.side)
+        self._close(self.old_record[: field.start] + [bits[8 * (A - 1 - j) + i] for j in range(A) for i in range(8)] + self.old_record[field.stop:],
+                    self.amount, self.side)
         w.c.assert_same(self.carry, side)
         for x in self.side[1:]:
             w.c.assert_equal(x, 0)
-        for x, y in zip(self.key, self.old_record[: 8 * K]):
-            w.c.assert_same(x, y)
-        lo, hi = (_key_bits_lsb_first(part, K) for part in (self.old_record[: 8 * K], self.old_record[8 * K: 16 * K]))
-        w.c.assert_equal(w.less_than(lo, hi), 1)
-
-    @property
-    def lu(self) -> int:
-        return 512 + 8 * (self.key_bytes + self.amount_bytes + 1)
+        self._assert_key()
+        self._assert_live()
 
     def _public(self, key, amount, side) -> bytes:
         """the checked K + A + 1 bytes of the public pieces behind the roots"""
@@ -1452,15 +1486,7 @@ class MerkleAdjust(_TwoRoots):
         """one statement's input bits, public then private: 512 zeros where the two roots are computed, the bits of k, of the amount's A big-endian bytes
         and of the side byte, the old record's bits, the siblings from the leaf's level up, then the direction bits.  (A witness that breaks a constraint
         is not refused here: Circuit.holds / circuit_assign say so.)"""
-        who = "MerkleAdjust"
-        public = np.unpackbits(np.frombuffer(self._public(key, amount, side), dtype=np.uint8), bitorder="little")
-        return _input_bits(512, public, _record_bits(who, self.length, old_record), _tail_bits(who, self.depth, siblings, index))
-
-    def statement(self, old_root: bytes, new_root: bytes, key: bytes, amount: int, side: int) -> bytes:
-        """the 64 + K + A + 1 statement bytes (what verify_public takes, bits [0, lu) of a witness row) that say "the adjust of `key` by `amount` in the
-        direction `side` took old_root to new_root": MerkleUpdate.statement's bytes, then the key, the amount as A big-endian bytes, the side byte"""
-        return (_statement_of(old_root, "MerkleAdjust: the old root") + _statement_of(new_root, "MerkleAdjust: the new root")
-                + self._public(key, amount, side))
+        return self._step_bits(self._public(key, amount, side), old_record, siblings, index)
 
 
 def _field_arg(who: str, field, key_bytes: int, length: int):
@@ -1474,7 +1500,7 @@ def _field_arg(who: str, field, key_bytes: int, length: int):
     return int(lo), int(hi)
 
 
-class MerkleWrite(_TwoRoots):
+class MerkleWrite(_RecordStep):
     """The statement "bytes [lo, hi) of the record of key k were set to v, and that alone takes the tree from root R to root R'" -- with expect=True "... were
     set to v, having been e": the PUT of the indexed table as a keyed store, plain or compare-and-set.  ONE record update, beside MerkleAdjust.
 
@@ -1500,38 +1526,21 @@ class MerkleWrite(_TwoRoots):
     c_0, field, expect) itself over the record's subtree of height c_0, and the upper ranges are MerkleSegment rows (MerkleTree.write_key_segments)."""
 
     def __init__(self, key_bytes: int, length: int, depth: int, field, expect=False):
-        self.key_bytes = K = self._arg(key_bytes, 1, 32, "key_bytes is in [1, 32]")
-        self.length = length = self._arg(length, 2 * K + 1, None, "the length is at least 2 key_bytes + 1 bytes")
-        self.depth = self._depth_arg(depth)
-        self.field = lo, hi = _field_arg("MerkleWrite", field, K, length)
+        w = self._open(key_bytes, length, depth, 1)
+        self.field = lo, hi = _field_arg("MerkleWrite", field, self.key_bytes, self.length)
         if not isinstance(expect, (bool, np.bool_)):
             raise CircuitError("MerkleWrite: expect is True or False")
         self.expect = bool(expect)
         self.field_bytes = F = hi - lo
-        self.w = w = Words()
-        self.old_record = w.c.private(8 * length)
-        self._tail_wires()
-        # the public pieces are read by the new record's chain, so they are declared here and moved behind the roots below
-        self.key = w.c.public(8 * K)
         self.expected = w.c.public(8 * F) if self.expect else []
         self.value = w.c.public(8 * F)
-        self.new_record = self.old_record[: 8 * lo] + self.value + self.old_record[8 * hi:]
-        self.old_leaf, self.blocks = _message_chain(w, self.old_record, length)
-        self.new_leaf, _ = _message_chain(w, self.new_record, length)
-        self._root_outputs(self.old_leaf, self.new_leaf)
-        w.c.public_last(self.key + self.expected + self.value)
-        for x, y in zip(self.key, self.old_record[: 8 * K]):
-            w.c.assert_same(x, y)
+        self._close(self.old_record[: 8 * lo] + self.value + self.old_record[8 * hi:], self.expected, self.value)
+        self._assert_key()
         for x, y in zip(self.expected, self.old_record[8 * lo: 8 * hi]):
             w.c.assert_same(x, y)
-        lo_key, hi_key = (_key_bits_lsb_first(part, K) for part in (self.old_record[: 8 * K], self.old_record[8 * K: 16 * K]))
-        w.c.assert_equal(w.less_than(lo_key, hi_key), 1)
+        self._assert_live()
 
-    @property
-    def lu(self) -> int:
-        return 512 + 8 * (self.key_bytes + (2 if self.expect else 1) * self.field_bytes)
-
-    def _public(self, key, values) -> bytes:
+    def _public(self, key, *values) -> bytes:
         """the checked K + F [+ F] bytes of the public pieces behind the roots; values = (v,) or (e, v)"""
         if len(values) != (2 if self.expect else 1):
             raise CircuitError("MerkleWrite: the public values are (e, v) with expect=True and v alone without")
@@ -1544,20 +1553,10 @@ class MerkleWrite(_TwoRoots):
         """bits(key, [expected,] value, old_record, siblings, index): one statement's input bits, public then private -- 512 zeros where the two roots are
         computed, the bits of k, of e with expect=True and of v, the old record's bits, the siblings from the leaf's level up, then the direction bits.  (A
         witness that breaks a constraint is not refused here: Circuit.holds / circuit_assign say so.)"""
-        who = "MerkleWrite"
-        nv = 2 if self.expect else 1
-        if len(values_record_siblings_index) != nv + 3:
-            raise CircuitError(f"{who}: bits(key, {'expected, ' if self.expect else ''}value, old_record, siblings, index)")
+        if len(values_record_siblings_index) != (5 if self.expect else 4):
+            raise CircuitError(f"MerkleWrite: bits(key, {'expected, ' if self.expect else ''}value, old_record, siblings, index)")
         *values, old_record, siblings, index = values_record_siblings_index
-        public = np.unpackbits(np.frombuffer(self._public(key, values), dtype=np.uint8), bitorder="little")
-        return _input_bits(512, public, _record_bits(who, self.length, old_record), _tail_bits(who, self.depth, siblings, index))
-
-    def statement(self, old_root: bytes, new_root: bytes, key: bytes, *values) -> bytes:
-        """statement(R, R', key, value) or, with expect=True, statement(R, R', key, expected, value): the 64 + K + F [+ F] statement bytes (what
-        verify_public takes, bits [0, lu) of a witness row) that say "the write of `value` under `key` [over `expected`] took old_root to new_root":
-        MerkleUpdate.statement's bytes, then the key, [the expected bytes,] the value"""
-        return (_statement_of(old_root, "MerkleWrite: the old root") + _statement_of(new_root, "MerkleWrite: the new root")
-                + self._public(key, values))
+        return self._step_bits(self._public(key, *values), old_record, siblings, index)
 
 
 def _keys_array(keys, who: str):

@@ -632,7 +632,7 @@ int mfh_merkle_remove_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, si
  *              ceil(2 depth / 8) bytes are written.
  *   how        ONE launch of k_key_locate over the sorted unique keys of all 2 nk senders and receivers and, behind it on the stream, ONE launch of
  *              k_balance_gather (one thread per unique key: the located record's balance as a uint64); 2 words and one balance per unique key come back under
- *              ONE wait.  The host walks the steps in order over a running balance per account (merkle_transfer.hpp); ONE launch of k_transfer_records
+ *              ONE wait.  The host walks the steps in order over a running balance per account (merkle_transfer.hpp); ONE launch of k_refield_records
  *              builds the 2 nk new records from the table before the batch and the uploaded new balances; they go through mfh_merkle_update_records'
  *              machinery in chunks of whole transfers (the most whose rows fit 64 MiB, at least one).  The call synchronises the stream behind the search
  *              and every chunk.
@@ -676,7 +676,7 @@ int mfh_merkle_transfer_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, 
  *              32 depth + ceil(depth / 8) bytes are written.
  *   how        ONE launch of k_key_locate over the sorted unique keys and, behind it on the stream, ONE launch of k_balance_gather; 2 words and one balance
  *              per unique key come back under ONE wait.  The host walks the steps in order over a running balance per account (merkle_adjust.hpp); ONE launch
- *              of k_adjust_records builds the nk new records from the table before the batch and the uploaded new balances; they go through
+ *              of k_refield_records builds the nk new records from the table before the batch and the uploaded new balances; they go through
  *              mfh_merkle_update_records' machinery in its chunks (the most updates whose rows fit 64 MiB, at least one).  The call synchronises the stream
  *              behind the search and every chunk.
  * mfh_merkle_adjust_keys_cut is the same with the path cut (above), exactly as mfh_merkle_update_records_cut for nk updates: segment 0's row is that of
@@ -717,7 +717,7 @@ int mfh_merkle_adjust_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, si
  *              written.
  *   how        ONE launch of k_key_locate over the sorted unique keys; with h_expect, behind it on the stream, ONE launch of k_field_gather (a slot of
  *              ceil(F / 16) 16-byte units per unique key); the results come back under ONE wait.  The host walks the steps in order over a running field value
- *              per unique key (merkle_write.hpp); ONE launch of k_write_records builds the nk new records from the table before the batch and the uploaded
+ *              per unique key (merkle_write.hpp); ONE launch of k_refield_records builds the nk new records from the table before the batch and the uploaded
  *              values; they go through mfh_merkle_update_records' machinery in its chunks (the most updates whose rows fit 64 MiB, at least one).  The call
  *              synchronises the stream behind the search and every chunk.
  * mfh_merkle_write_keys_cut is the same with the path cut (above), exactly as mfh_merkle_adjust_keys_cut: segment 0's row is that of MerkleWrite(key_bytes,

@@ -27,6 +27,11 @@ STATEMENTS = {
     "MerkleAbsent(8, 16, 1)": lambda: W.MerkleAbsent(8, 16, 1),
     "Sha256Message(0)": lambda: W.Sha256Message(0),
     "Sha256Message(56)": lambda: W.Sha256Message(56),
+    "MerkleAdjust(4, 16, 1, 8)": lambda: W.MerkleAdjust(4, 16, 1, 8),
+    "MerkleAdjust(4, 16, 1, 3)": lambda: W.MerkleAdjust(4, 16, 1, 3),
+    "MerkleWrite(4, 16, 1, (8, 16))": lambda: W.MerkleWrite(4, 16, 1, (8, 16)),
+    "MerkleWrite(4, 16, 1, (8, 16), True)": lambda: W.MerkleWrite(4, 16, 1, (8, 16), True),
+    "MerkleWrite(4, 16, 1, (9, 10), True)": lambda: W.MerkleWrite(4, 16, 1, (9, 10), True),
 }
 # compiled against P19; the entries above stay on P18, so their digests do not move
 STATEMENTS_P19 = {
@@ -35,6 +40,7 @@ STATEMENTS_P19 = {
     "MerkleRemove(4, 8, 1)": lambda: W.MerkleRemove(4, 8, 1),
     "MerkleRemove(5, 11, 1, joined=False)": lambda: W.MerkleRemove(5, 11, 1, joined=False),
     "MerkleSegment(2)": lambda: W.MerkleSegment(2),
+    "MerkleTransfer(4, 16, 1, 8)": lambda: W.MerkleTransfer(4, 16, 1, 8),
 }
 STATEMENTS.update(STATEMENTS_P19)
 
