@@ -106,7 +106,7 @@ EXPORTS = [
     "mfh_merkle_remove_keys", "mfh_merkle_remove_keys_cut", "mfh_merkle_transfer_keys", "mfh_merkle_transfer_keys_cut",
     "mfh_merkle_paths_cut", "mfh_merkle_absent_rows_cut", "mfh_merkle_range_rows", "mfh_merkle_range_rows_cut",
     "mfh_merkle_load_keys", "mfh_merkle_check_table", "mfh_merkle_grow", "mfh_merkle_grow_leaves",
-    "mfh_merkle_write_keys", "mfh_merkle_write_keys_cut",
+    "mfh_merkle_write_keys", "mfh_merkle_write_keys_cut", "mfh_merkle_block_keys", "mfh_merkle_block_keys_cut", "mfh_merkle_block_row_bytes",
 ]
 
 
@@ -279,6 +279,10 @@ def load_library():
         "mfh_merkle_balance_sum": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, vp]),
         "mfh_merkle_write_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, u32, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
         "mfh_merkle_write_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, u32, vp, sz, vp, sz, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_block_keys": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, vp, vp, vp, vp, vp, vp]),
+        "mfh_merkle_block_keys_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, u32, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp, vp,
+                                            vp]),
+        "mfh_merkle_block_row_bytes": (sz, [u32, u32, u32, u32, u32, u32, u32, u32, u32]),
         "mfh_merkle_paths_cut": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
         "mfh_merkle_absent_rows_cut": (i32, [vp, vp, vp, sz, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp]),
         "mfh_merkle_range_rows": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
@@ -373,6 +377,52 @@ def _records(ctx, records, who):
         raise MfhError(f"{who}: records are a uint8 array [n, length]")
     n, length = a.shape
     return ctx.to_device(a).reshape(n, length), length, length, n, True
+
+
+class BlockResult:
+    """what MerkleTree.apply_block / apply_block_segments return.  rows: one 1-D np.uint8 view per step, its packed input row (None for a skipped step);
+    index np.uint32 [nk, 2]; status np.uint8 [nk]; roots np.uint8 [nk + 1, 32]; first_update np.uint32 [nk + 1]; update_roots np.uint8 [nupd + 1, 32], the
+    root behind every update; a cut call's segments and nodes (apply_block_segments)."""
+
+    def __init__(self, tree, block, length, levels, cut, buf, row_at, index, status, r_all, first_update):
+        self.block, self.length, self.levels, self.cut = block, length, levels, cut
+        self.index, self.status, self.first_update = index, status, first_update
+        self.update_roots = r_all[: int(first_update[-1]) + 1]
+        self.roots = r_all[first_update]
+        self._buf, self._row_at, self._rows = buf, row_at, None
+        self.segments, self.nodes = None, None
+
+    @property
+    def rows(self):
+        if self._rows is None:  # (views, made when first asked for)
+            at = [int(x) for x in self._row_at]
+            self._rows = [None if st else self._buf[at[j]: at[j + 1]] for j, st in enumerate(self.status)]
+        return self._rows
+
+    def rows_of(self, kind, field=None, expect=False):
+        """(steps, rows [n, width]): the applied steps of one statement -- kind is Block.TRANSFER, Block.ADJUST or Block.WRITE, and for writes the field
+        (lo, hi) and whether they carry an expectation -- and their rows stacked, ready for the _unpack and circuit_assign of that statement's program"""
+        from .words import Block
+
+        if kind not in (Block.TRANSFER, Block.ADJUST, Block.WRITE):
+            raise MfhError("rows_of: kind is Block.TRANSFER, Block.ADJUST or Block.WRITE")
+        if kind == Block.WRITE and field is None:
+            raise MfhError("rows_of: a write's rows are those of one field (lo, hi)")
+        steps = [j for j, s in enumerate(self.block.steps) if s[0] == kind and self.rows[j] is not None
+                 and (kind != Block.WRITE or (tuple(s[2]) == tuple(int(x) for x in field) and (s[4] is not None) == bool(expect)))]
+        rows = np.stack([self.rows[j] for j in steps]) if steps else np.zeros((0, 0), dtype=np.uint8)
+        return steps, rows
+
+    def bits_of(self, kind, field=None, expect=False):
+        """rows_of with the rows as 0 / 1 arrays of the statement's nin bits: what Context.circuit_assign(prog, bits) takes"""
+        from .words import Block
+
+        steps, rows = self.rows_of(kind, field, expect)
+        if not steps:
+            return steps, rows
+        ndir = (2 if kind == Block.TRANSFER else 1) * self.levels  # the direction bits: the last ceil(ndir / 8) bytes of a row
+        nbits = 8 * (rows.shape[1] - (ndir + 7) // 8) + ndir
+        return steps, np.unpackbits(rows, axis=1, bitorder="little")[:, :nbits]
 
 
 class MerkleTree:
@@ -1175,6 +1225,87 @@ class MerkleTree:
         lo, hi = field
         head = 64 + np.ascontiguousarray(keys).shape[1] + (1 if expect is None else 2) * (int(hi) - int(lo)) + int(table.shape[1])
         return (self._cut_unpack(out[0], cuts, lambda c0: 8 * head + 257 * c0),) + tuple(out[1:])
+
+    # ---- blocks: transfers, adjusts and writes in any order in one call
+    def _block(self, who, table, block, skip_failed, cut=False, cuts=None):
+        """the body of apply_block and, with cut=True, apply_block_segments: the argument checks, the block's arrays, mfh_merkle_block_keys[_cut]"""
+        from .words import Block
+
+        c = self._ctx
+        vp = ctypes.c_void_p
+        tab, tstride, length = self._table(table, who)
+        if not isinstance(block, Block):
+            raise MfhError(f"{who}: the block is a words.Block")
+        K, A, nk = block.key_bytes, block.amount_bytes, len(block)
+        if length < 2 * K + A:
+            raise MfhError(f"{who}: 2 key_bytes + amount_bytes <= length")
+        col = block.columns()  # (made once a block, in one pass over its steps)
+        if col["field_hi"] > length:
+            raise MfhError(f"{who}: a write's field is (lo, hi) with 2 key_bytes <= lo < hi <= length")
+        kinds, keys, keys_to, amounts, sides, fields = (col[x] for x in ("kinds", "keys", "keys_to", "amounts", "sides", "fields"))
+        value_at, expect_at, values, expect = (col[x] for x in ("value_at", "expect_at", "values", "expect"))
+        if cut:
+            rows_g, cut_args, keep = self._cut(cuts, who, 0, lambda c0: 0, col["updates"])
+            d0 = int(keep[0])
+        else:
+            d0 = self.depth
+        # every step's row bytes (csrc/merkle_rows.hpp; mfh_merkle_block_row_bytes says the same of one step), by kind
+        one = 64 + K + length + 32 * d0 + (d0 + 7) // 8
+        written = (fields[:, 1] - fields[:, 0]).astype(np.uint64) * np.where(expect_at != 0xFFFFFFFFFFFFFFFF, 2, 1).astype(np.uint64)
+        rowb = np.where(kinds == Block.TRANSFER, (128 if cut else 64) + 2 * K + A + 2 * length + 64 * d0 + (2 * d0 + 7) // 8,
+                        np.where(kinds == Block.ADJUST, one + A + 1, one + written)).astype(np.uint64)
+        row_at = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(rowb, dtype=np.uint64)])
+        buf = np.zeros(int(row_at[-1]) or 1, dtype=np.uint8)
+        r_all = np.zeros((2 * nk + 1, 32), dtype=np.uint8)
+        index = np.full((nk, 2), 0xFFFFFFFF, dtype=np.uint32)
+        status = np.zeros(nk, dtype=np.uint8)
+        first_update = np.zeros(nk + 1, dtype=np.uint32)
+        args = (c._h, self._h, _ptr(tab), tstride, length, K, A, nk, vp(kinds.ctypes.data), vp(keys.ctypes.data), vp(keys_to.ctypes.data), K, vp(amounts.ctypes.data),
+                vp(sides.ctypes.data), vp(fields.ctypes.data), vp(value_at.ctypes.data), vp(values.ctypes.data), col["values_bytes"], vp(expect_at.ctypes.data),
+                vp(expect.ctypes.data), col["expect_bytes"], int(bool(skip_failed)))
+        outs = (vp(row_at.ctypes.data), vp(r_all.ctypes.data), vp(index.ctypes.data), vp(status.ctypes.data), vp(first_update.ctypes.data))
+        try:
+            if cut:
+                rows_g[0] = buf.reshape(1, -1)
+                ncuts, h_cuts, _, _ = cut_args
+                ptrs = (vp * len(rows_g))(*[r.ctypes.data for r in rows_g])
+                strides = (ctypes.c_size_t * len(rows_g))(*[r.shape[1] for r in rows_g])
+                c._chk(c.lib.mfh_merkle_block_keys_cut(*args, ncuts, h_cuts, ptrs, strides, *outs))
+            else:
+                c._chk(c.lib.mfh_merkle_block_keys(*args, vp(buf.ctypes.data), *outs))
+        except MfhError as e:
+            e.status, e.index = status, index  # (filled when the refusal came behind the search)
+            raise
+        if nk:
+            self._keep = []  # (the call waited for the stream)
+        else:
+            r_all[0] = np.frombuffer(self.root(), dtype=np.uint8)
+        res = BlockResult(self, block, length, d0, cut, buf, row_at, index, status, r_all, first_update)
+        if cut:
+            nupd = int(first_update[nk])
+            res.segments = [r[:nupd] for r in rows_g[1:]]
+            res.nodes = self._cut_nodes([None] + res.segments, r_all[: nupd + 1])
+        return res
+
+    def apply_block(self, table, block, skip_failed=False):
+        """a BlockResult: the steps of a words.Block -- transfers, adjusts and writes in any order -- applied in order to an INDEXED table whose records
+        carry a balance and to this tree in ONE call (mfh_merkle_block_keys: one search, one build launch; waits for the stream).  Byte for byte what
+        transfer_keys, adjust_keys and write_keys give when run once per step: result.rows[j] is step j's packed input row, that of its kind's statement,
+        taken from table and tree as they stood before step j; result.index is np.uint32 [nk, 2], (the sender's slot, the receiver's) or (the slot,
+        0xFFFFFFFF); result.status np.uint8 [nk]; result.roots np.uint8 [nk + 1, 32], R_0 .. R_nk: block.statements(length, depth, result.roots,
+        result.status) are the statements.  table: under update_records' rules, MODIFIED IN PLACE.
+        skip_failed=False: MfhError with the library's text, table and tree untouched, when any step has a status -- 1 the key (a sender) is no member, 2 a
+        receiver is none, 3 an overdraft and 4 an overflow of the running balance, 5 the running field is not what the step expects; the error carries
+        .status and .index.  skip_failed=True: the steps with a status are left out (no row: result.rows[j] is None; R_j+1 = R_j) and the rest applied as
+        if the block had been given without them."""
+        return self._block("apply_block", table, block, skip_failed)
+
+    def apply_block_segments(self, table, block, cuts, skip_failed=False):
+        """apply_block with the path cut at levels `cuts` (mfh_merkle_block_keys_cut).  result.rows[j] is step j's segment-0 row -- that of
+        words.MerkleTransfer(.., c_0, joined=False), or MerkleAdjust / MerkleWrite at depth c_0; result.segments[g - 1] is np.uint8 [nupd, ..], one
+        words.MerkleSegment row per UPDATE for the level range g >= 1; result.nodes np.uint8 [nupd, G + 1, 2, 32], the published pairs of every update;
+        result.first_update np.uint32 [nk + 1]: step j's updates are [first_update[j], first_update[j + 1]), two of a transfer, none of a skipped step."""
+        return self._block("apply_block_segments", table, block, skip_failed, cut=True, cuts=cuts)
 
     def total_balance(self, table, key_bytes, amount_bytes=8):
         """(sum, live): the SUPPLY of an indexed table whose records carry a balance -- the sum, a Python int, of the balances (bytes [2 key_bytes, 2 key_bytes

@@ -36,6 +36,9 @@
 // step (the host's plan: merkle_adjust.hpp), then the steps below.  k_balance_sum, k_balance_fold: mfh_merkle_balance_sum, the supply.
 // k_field_gather: mfh_merkle_write_keys, a batch of sequential writes by key, plain or compare-and-set, in one call -- the search as above, for the conditional
 // form the located records' field behind it, ONE new record a step (the host's plan: merkle_write.hpp), then the steps below.
+// k_window_gather, k_window_records: mfh_merkle_block_keys, a block of transfers, adjusts and writes in any order in one call -- one search, a window of
+// its own per unique key gathered behind it, all new records in one launch from per-update descriptors (the host's plan: merkle_block.hpp), then the record
+// updates above.
 // k_insert_records, k_remove_records, k_refield_records (transfers, adjusts and writes: one field of a record changes): what a batch of steps ends with -- all
 // R nk new records (R = 2 a key step, 1 an adjust or a write) built in one launch from the step's plan, then the record updates above.  The host side of the
 // key calls is one preamble (keys_refused), one search (key_search), one driver of the steps (step_reserve, step_updates); a call states its refusals, its
@@ -55,6 +58,7 @@
 
 #include "ctx.hpp"
 #include "merkle_adjust.hpp"
+#include "merkle_block.hpp"
 #include "merkle_grow.hpp"
 #include "merkle_insert.hpp"
 #include "merkle_keys.hpp"
@@ -1090,6 +1094,50 @@ __global__ __launch_bounds__(256) void k_field_gather(const uint8_t *__restrict_
   field[g] = out;
 }
 
+// ---- mfh_merkle_block_keys: a block of steps of mixed kinds (merkle_block.hpp).  Every unique key has a WINDOW of its own, every update a window and a
+// source of its own: the two kernels are k_field_gather's and k_refield_records' bodies with the geometry read per item, where those take one field as launch
+// arguments.
+//
+// k_window_gather, ONE launch per call behind k_key_locate on the same stream: one item per UNIQUE key q < nu and 16-byte unit of its slot.  win[q] = (f0, f1,
+// first, 0): the key's window is its record's bytes [f0, f1) and its slot the units [first, first + ceil((f1 - f0) / 16)) of `out`; win[nu].z = the units of
+// all slots.  Item g finds its key by bisection over the first units (ascending; a key's slot has at least one unit).  present[q] is the search's result word
+// on the device.  Unit s of a slot holds the window's bytes [16 s, 16 s + 16) through load_unit_within -- any alignment of the table, any stride, the window
+// anywhere across the record's units -- with zero behind the window, and all zero for a key that is not a member.  The store is the whole unit.
+// Reads: nothing outside [table, table + span), win and present.
+__global__ __launch_bounds__(256) void k_window_gather(const uint8_t *__restrict__ table, size_t stride, int64_t span, uint32_t n, const uint32_t *__restrict__ present,
+                                                       uint32_t nu, const uint4 *__restrict__ win, uint4 *__restrict__ out) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= win[nu].z) return;
+  uint32_t lo = 0, hi = nu;  // the key: the last q with first[q] <= g
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (win[mid].z <= g) lo = mid;
+    else hi = mid;
+  }
+  const uint4 w = win[lo];
+  const uint32_t rec = present[lo];
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (rec < n) {
+    const int64_t o = 16 * (int64_t)(g - w.z), F = (int64_t)w.y - w.x, a = (int64_t)((size_t)rec * stride) + w.x + o;
+    v = merge_unit(v, load_unit_within(table, a, a + min((int64_t)16, F - o), span), o, 0, F);
+  }
+  out[g] = v;
+}
+
+// k_window_records, ONE launch per call: all nupd new records of a block into `fresh`, record r at r * pitch bytes (pitch = ceil(length / 16) units).  One item
+// per update r and 16-byte unit u; the store is the whole unit.  desc[r] = (the table record, f0, f1, at): new record r is the table's record as it stood
+// BEFORE the block with bytes [f0, f1) <- src[at .. at + f1 - f0), the bytes the host's plan left in the key's window right after the step.  Every source is
+// the old table or the upload: one launch, no ordering among the items, no atomics, no LDS, and the table is only read.  Bytes at or past `length`: zero.
+// Reads: nothing outside [table, table + table_span), [src, src + src_span) and desc.
+__global__ __launch_bounds__(256) void k_window_records(const uint8_t *__restrict__ table, size_t table_stride, int64_t table_span, const uint8_t *__restrict__ src,
+                                                        int64_t src_span, const uint4 *__restrict__ desc, uint32_t length, uint32_t nupd, uint4 *__restrict__ fresh) {
+  const uint32_t units = (length + 15) / 16, g = blockIdx.x * 256 + threadIdx.x;  // (nupd units < 2^32: checked by the host)
+  if (g >= nupd * units) return;
+  const uint32_t r = g / units, u = g - r * units;
+  const uint4 d = desc[r];
+  fresh[g] = refielded_unit(table, (int64_t)((size_t)d.x * table_stride), table_span, src, d.w, 1, src_span, u, d.y, d.z, length);
+}
+
 // The supply: the sum of the balances of all LIVE records and their number, two launches, no atomics (integer addition: the result does not depend on the
 // order anyway).  The sum is 128 bits, two 64-bit words with the carry out of the low word: 2^depth balances below 2^64 stay below 2^(64 + depth) <= 2^88.
 //   k_balance_sum<KW>  one thread per record i < n, 256 a workgroup: lo | hi through load_record_keys (any alignment and stride, nothing outside the table's span),
@@ -1867,9 +1915,13 @@ size_t key_search_bytes(uint32_t nu, uint32_t key_bytes) { return (size_t)nu * (
 // An optional second kernel behind the search, on the same stream and under the same wait: launch(d_res, d_out) reads the search's 2 nu result words on the
 // device and writes `bytes` bytes at d_out = d_work + key_search_bytes rounded up to 16 (the caller reserves both); they come back behind the results, at
 // *res + 2 nu words.  A call without one queues and waits for exactly what it always has
+// `up`: up_bytes bytes the tail's kernel reads, which go up with the keys' words (the same pinned buffer, a copy of their own) to d_out + bytes (bytes a
+// multiple of 16 then; the caller reserves them too); 0: nothing more is queued
 struct SearchTail {
   size_t bytes;
   std::function<void(const uint32_t *d_res, uint8_t *d_out)> launch;
+  const void *up = nullptr;
+  size_t up_bytes = 0;
 };
 
 size_t key_search_tail_at(uint32_t nu, uint32_t key_bytes) { return (key_search_bytes(nu, key_bytes) + 15) & ~(size_t)15; }
@@ -1881,10 +1933,16 @@ int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch 
   const uint32_t nu = keys.nu, kw = mf::key_words(k.key_bytes), n = 1u << depth;
   const size_t words_bytes = (size_t)nu * kw * 4, res_bytes = (size_t)2 * nu * 4;
   uint32_t *d_qw = reinterpret_cast<uint32_t *>(d_work), *d_res = d_qw + (size_t)nu * kw;
-  uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes);
+  const size_t up_bytes = tail ? tail->up_bytes : 0;
+  uint8_t *d_tail = tail ? d_work + key_search_tail_at(nu, k.key_bytes) : nullptr;
+  uint32_t *pin_qw = (uint32_t *)pin_acquire(c, c->pin_rows, words_bytes + up_bytes);
   if (!pin_qw) return MFH_ENOMEM;
   memcpy(pin_qw, keys.words.data(), words_bytes);
   HIP_TRY(c, hipMemcpyAsync(d_qw, pin_qw, words_bytes, hipMemcpyHostToDevice, c->stream));
+  if (up_bytes) {
+    memcpy(pin_qw + (size_t)nu * kw, tail->up, up_bytes);
+    HIP_TRY(c, hipMemcpyAsync(d_tail + tail->bytes, pin_qw + (size_t)nu * kw, up_bytes, hipMemcpyHostToDevice, c->stream));
+  }
   pin_release(c, c->pin_rows);
   HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, res_bytes, c->stream));
   KeyKernel kernel = nullptr;
@@ -1895,7 +1953,6 @@ int key_search(mfh_ctx *c, const KeyCall &k, const mf::KeyPlan &keys, KeySearch 
                        d_res + nu);
   }
   HIP_TRY(c, hipGetLastError());
-  uint8_t *d_tail = tail ? d_work + key_search_tail_at(nu, k.key_bytes) : nullptr;
   if (tail) {
     tail->launch(d_res, d_tail);
     HIP_TRY(c, hipGetLastError());
@@ -2583,6 +2640,216 @@ int write_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, co
   });
 }
 
+// what a block has beside the key calls' shared arguments (include/mfhip.h says what each is).  k.h_keys are the steps' first keys (a transfer's sender),
+// k.h_inputs the one buffer of the steps' rows (segment 0's in a cut call), k.h_index nk pairs
+struct BlockArgs {
+  uint32_t amount_bytes;
+  const uint8_t *kinds, *keys_to;
+  const uint64_t *amounts;
+  const uint8_t *sides;
+  const uint32_t *fields;
+  const uint64_t *value_at;
+  const uint8_t *values;
+  size_t values_bytes;
+  const uint64_t *expect_at;
+  const uint8_t *expect;
+  size_t expect_bytes;
+  const uint64_t *row_at;
+  bool skip_failed;
+  uint32_t *first_update;
+  const uint8_t *to(uint32_t j, size_t key_stride) const { return keys_to + (size_t)j * key_stride; }
+  bool expects(uint32_t j) const { return expect_at && expect_at[j] != MFH_BLOCK_NO_EXPECT; }
+};
+
+// mfh_merkle_block_keys (k.cuts = null: every step's row is its kind's row of the whole depth) and mfh_merkle_block_keys_cut (segment 0's rows the kinds' rows
+// over c_0 levels, ONE MerkleSegment row an UPDATE and upper segment); nupd + 1 roots either way, one behind every update.  Not the step driver: a block's
+// steps have 0, 1 or 2 updates, so the chunks of record_updates are uniform in UPDATES and a transfer's two may lie in two chunks -- its row is then spliced
+// from a host copy of its first update's head and level row, kept across the seam.
+int block_keys(mfh_ctx *c, mfh_merkle *t, const KeyCall &k, uint8_t *d_table, const BlockArgs &a) {
+  const uint32_t depth = t->depth, d0 = k.cuts ? k.cuts->cuts[0] : depth, nk = k.nk, length = k.length, K = k.key_bytes, A = a.amount_bytes;  // d0: the levels of a step's own row
+  const std::string what = keys_refused(k, depth, "steps", true, [&]() -> const char * {
+    if (const char *what = balance_refused(length, K, A)) return what;
+    return k.cuts ? cuts_refused(nk, k.cuts->ncuts, k.cuts->cuts, depth, k.cuts->h_rows, k.cuts->strides, 0) : nullptr;
+  }, false);  // (the updates, at most 2 nk, below 2^32 by the check of the new records' units)
+  if (!what.empty()) return fail(c, k.who, what.c_str());
+  if (nk && !a.kinds) return fail(c, k.who, "steps without h_kinds");
+  if (nk && !a.first_update) return fail(c, k.who, "steps without h_first_update");
+  if (nk && k.h_inputs && !a.row_at) return fail(c, k.who, "rows without h_row_at");
+  size_t rowb = 0;  // the most row bytes an update of any step stands for
+  for (uint32_t j = 0; j < nk; j++) {
+    const uint8_t kind = a.kinds[j];
+    if (kind > mf::kBlockWrite) return fail(c, k.who, "a kind is none of 0 (a transfer), 1 (an adjust), 2 (a write)");
+    uint32_t lo = 0, hi = 0;
+    if (kind == mf::kBlockWrite) {
+      if (!a.fields || !a.value_at || !a.values) return fail(c, k.who, !a.fields ? "writes without h_fields" : !a.value_at ? "writes without h_value_at" : "writes without h_values");
+      lo = a.fields[2 * (size_t)j];
+      hi = a.fields[2 * (size_t)j + 1];
+      if (lo < 2 * K) return fail(c, k.who, "a field's lo below the two keys' 2 key_bytes bytes: the keys are not writable");
+      if (hi <= lo) return fail(c, k.who, "a field's hi must be above its lo");
+      if (hi > length) return fail(c, k.who, "a field's hi above length");
+      if (a.value_at[j] > a.values_bytes || a.values_bytes - a.value_at[j] < hi - lo) return fail(c, k.who, "a value's bytes lie outside h_values");
+      if (a.expects(j) && (!a.expect || a.expect_at[j] > a.expect_bytes || a.expect_bytes - a.expect_at[j] < hi - lo))
+        return fail(c, k.who, "an expectation's bytes lie outside h_expect");
+    } else {
+      if (!a.amounts) return fail(c, k.who, "transfers or adjusts without h_amounts");
+      if (a.amounts[j] > mf::balance_limit(A)) return fail(c, k.who, "an amount does not fit amount_bytes bytes");
+      if (kind == mf::kBlockAdjust && a.sides && a.sides[j] > 1) return fail(c, k.who, "a side is neither 0 (a deposit) nor 1 (a withdrawal)");
+    }
+    if (kind == mf::kBlockTransfer) {
+      if (!a.keys_to) return fail(c, k.who, "transfers without h_keys_to");
+      if (mf::key_is_sentinel(a.to(j, k.key_stride), K)) return fail(c, k.who, "a key is the all-zero or the all-0xFF key");
+      if (!memcmp(k.key(j), a.to(j, k.key_stride), K)) return fail(c, k.who, "a transfer from an account to itself");
+    }
+    const size_t rowb_j = mf::block_row_bytes(kind, K, A, length, d0, lo, hi, kind == mf::kBlockWrite && a.expects(j), k.cuts != nullptr);
+    if (k.h_inputs && (a.row_at[j + 1] < a.row_at[j] || a.row_at[j + 1] - a.row_at[j] < rowb_j)) return fail(c, k.who, "a row's slot in h_rows is shorter than the step's row");
+    rowb = std::max(rowb, (rowb_j + mf::block_step_updates(kind) - 1) / mf::block_step_updates(kind));
+  }
+  if (!nk) return MFH_OK;
+  // the keys: the unique keys of all senders, receivers, accounts and written keys.  A key may occur in many steps of any kind
+  std::vector<uint8_t> all;
+  std::vector<uint32_t> key_of((size_t)nk + 1, 0);  // step j's keys are all[key_of[j] ..]
+  for (uint32_t j = 0; j < nk; j++) {
+    all.insert(all.end(), k.key(j), k.key(j) + K);
+    if (a.kinds[j] == mf::kBlockTransfer) all.insert(all.end(), a.to(j, k.key_stride), a.to(j, k.key_stride) + K);
+    key_of[(size_t)j + 1] = (uint32_t)(all.size() / K);
+  }
+  mf::KeyPlan keys;
+  mf::keys_prepare(all.data(), K, K, key_of[nk], keys);
+  const uint32_t nu = keys.nu, n = 1u << depth;
+  std::vector<mf::BlockStep> steps(nk);
+  std::vector<uint8_t> amounts((size_t)nk * A);
+  for (uint32_t j = 0; j < nk; j++) {
+    mf::BlockStep &s = steps[j];
+    s = mf::BlockStep{};
+    s.kind = a.kinds[j];
+    s.a = keys.slot[key_of[j]];
+    if (s.kind == mf::kBlockTransfer) s.b = keys.slot[key_of[j] + 1];
+    if (s.kind == mf::kBlockWrite) {
+      s.lo = a.fields[2 * (size_t)j];
+      s.hi = a.fields[2 * (size_t)j + 1];
+      s.value = a.values + a.value_at[j];
+      s.expect = a.expects(j) ? a.expect + a.expect_at[j] : nullptr;
+    } else {
+      s.amount = a.amounts[j];
+      s.side = s.kind == mf::kBlockAdjust && a.sides ? a.sides[j] : (uint8_t)0;
+      mf::balance_bytes(s.amount, A, amounts.data() + (size_t)j * A);
+    }
+  }
+  mf::BlockWindows w;
+  mf::block_windows(nk, steps.data(), nu, K, A, w);
+  // (the slots' units stay below 2^32 by keys_refused's check of the new records' units: at most 2 nk unique keys, a window no longer than a record.)  An update's
+  // descriptor holds where its window's bytes stand among the source bytes as 32 bits
+  if (w.max_src >> 32) return fail(c, k.who, "the updates' window bytes, one window an update, reach 2^32");
+  const uint32_t units = (uint32_t)w.units, max_updates = (uint32_t)w.max_updates;
+  std::vector<uint32_t> win_desc((size_t)4 * (nu + 1), 0);  // what k_window_gather reads per key: (f0, f1, first, 0); [nu]: first = all units
+  for (uint32_t u = 0; u <= nu; u++) {
+    if (u < nu) win_desc[4 * (size_t)u] = w.f0[u], win_desc[4 * (size_t)u + 1] = w.f1[u];
+    win_desc[4 * (size_t)u + 2] = w.first[u];
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t hp = mf::record_head_pitch(length), gather_bytes = (size_t)units * 16, desc_bytes = (size_t)(nu + 1) * 16;
+  const mf::BlockLayout s = mf::block_layout(max_updates, (size_t)w.max_src, length, rowb, depth, k.cuts ? k.cuts->ncuts : 0, k.cuts ? k.cuts->cuts : nullptr, kPathStageBytes);
+  if (int rc = work_reserve(c, c->circ_io, s.skip + std::max(key_search_tail_at(nu, K) + gather_bytes + desc_bytes, update_rows_bytes(depth, s.ch, 2 * hp, 1, k.cuts)))) return rc;
+  std::vector<uint32_t> rec(nu);
+  std::vector<uint8_t> win(gather_bytes);
+  {  // a. ONE search for all steps, against the table before the block, and the unique keys' windows behind it under the same wait
+    SearchTail gather{gather_bytes, [&](const uint32_t *d_res, uint8_t *d_out) {
+      Timer tm(c, 51, nu);  // "merkle_block_windows" (mfhip.hip: timing_kind)
+      hipLaunchKernelGGL(k_window_gather, dim3((units + 255) / 256), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), n, d_res + nu, nu,
+                         reinterpret_cast<const uint4 *>(d_out + gather_bytes), reinterpret_cast<uint4 *>(d_out));
+    }};
+    gather.up = win_desc.data();
+    gather.up_bytes = desc_bytes;
+    const uint32_t *res;
+    if (int rc = key_search(c, k, keys, kLocate, depth, c->circ_io.as<uint8_t>() + s.skip, &res, &gather)) return rc;
+    memcpy(rec.data(), res + nu, (size_t)nu * 4);  // the record whose own key it is, or kNoRecord
+    memcpy(win.data(), res + (size_t)2 * nu, gather_bytes);
+  }
+  // b. the plan: the running window bytes of every key through the steps in order, and the policy
+  mf::BlockPlan plan;
+  mf::block_plan(nk, steps.data(), K, A, w, rec.data(), win.data(), a.skip_failed, plan);
+  memcpy(k.h_index, plan.index.data(), (size_t)2 * nk * 4);
+  memcpy(k.h_status, plan.status.data(), nk);
+  memcpy(a.first_update, plan.first_update.data(), ((size_t)nk + 1) * 4);
+  if (plan.failed && !a.skip_failed) {
+    static const char *const why[] = {"", "a key is not a member of the set (h_status 1)", "a receiver is not a member of the set (h_status 2)",
+                                      "a step overdraws its account's balance at that step (h_status 3)",
+                                      "a step takes its account's balance past 2^(8 amount_bytes) - 1 (h_status 4)",
+                                      "a field is not what was expected at that step (h_status 5)"};
+    return fail(c, k.who, why[plan.status[plan.first]]);
+  }
+  const uint32_t nupd = (uint32_t)plan.upd.size();
+  if (!nupd) {  // every step skipped: R_0 alone
+    if (!k.h_roots) return MFH_OK;
+    uint8_t *pin = (uint8_t *)pin_acquire(c, c->pin_cw, 32);
+    if (!pin) return MFH_ENOMEM;
+    HIP_TRY(c, hipMemcpyAsync(pin, t->level(depth), 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(k.h_roots, pin, 32);
+    return MFH_OK;
+  }
+  // c. the update descriptors and the source bytes go up; ONE launch builds all nupd new records from the table before the block
+  uint8_t *d_fresh = c->circ_io.as<uint8_t>(), *d_desc = d_fresh + s.fresh_bytes, *d_src = d_desc + s.desc_bytes;
+  {
+    const size_t db = (size_t)nupd * 16;
+    uint8_t *pin_up = (uint8_t *)pin_acquire(c, c->pin_rows, db + plan.src.size());
+    if (!pin_up) return MFH_ENOMEM;
+    memcpy(pin_up, plan.upd.data(), db);
+    memcpy(pin_up + db, plan.src.data(), plan.src.size());
+    HIP_TRY(c, hipMemcpyAsync(d_desc, pin_up, db, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_src, pin_up + db, plan.src.size(), hipMemcpyHostToDevice, c->stream));
+    pin_release(c, c->pin_rows);
+  }
+  {
+    Timer tm(c, 52, nupd);  // "merkle_block_records" (mfhip.hip: timing_kind)
+    const uint64_t items = (uint64_t)nupd * (hp / 16);
+    hipLaunchKernelGGL(k_window_records, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, c->stream, k.d_table, k.table_stride, k.span(depth), (const uint8_t *)d_src,
+                       (int64_t)plan.src.size(), reinterpret_cast<const uint4 *>(d_desc), length, nupd, reinterpret_cast<uint4 *>(d_fresh));
+  }
+  HIP_TRY(c, hipGetLastError());
+  // d. the nupd record updates, a root behind every one, and every applied step's row by the splice of its kind
+  std::vector<uint32_t> idx(nupd), step_of(nupd);
+  for (uint32_t j = 0; j < nk; j++)
+    for (uint32_t r = plan.first_update[j]; r < plan.first_update[(size_t)j + 1]; r++) {
+      idx[r] = plan.upd[r].rec;
+      step_of[r] = j;
+    }
+  const uint32_t low = (uint32_t)(((uint64_t)1 << d0) - 1);  // a cut row's subtree has height d0: indices mod 2^d0
+  std::vector<uint8_t> seam_head, seam_row;  // a transfer's first update, when its second lies in the next chunk
+  const Pairs chunks{s.ch, s.skip, true};
+  ChunkFn rows_out;
+  if (k.h_inputs)
+    rows_out = [&](const Chunk &u) {
+      for (uint32_t b = 0; b < u.k; b++) {
+        const uint32_t r = u.b0 + b, j = step_of[r];
+        const mf::BlockStep &st = steps[j];
+        const uint8_t *head = u.pin_heads + (size_t)b * u.hs, *staged = u.pin_rows + (size_t)b * u.rs;
+        uint8_t *row = k.h_inputs + a.row_at[j];
+        if (st.kind == mf::kBlockTransfer) {
+          if (r == plan.first_update[j]) {  // the sender's update: the row is spliced at the receiver's
+            if (b + 1 == u.k) {
+              seam_head.assign(head, head + u.hs);
+              seam_row.assign(staged, staged + u.rs);
+            }
+            continue;
+          }
+          const uint8_t *head_p = b ? head - u.hs : seam_head.data(), *staged_p = b ? staged - u.rs : seam_row.data();
+          mf::splice_pair_row(row, k.cuts ? 128 : 64, {{k.key(j), K}, {a.to(j, k.key_stride), K}, {amounts.data() + (size_t)j * A, A}, {head_p, length}, {head, length}}, staged_p,
+                              staged, d0, k.h_index[2 * (size_t)j] & low, k.h_index[2 * (size_t)j + 1] & low);
+        } else if (st.kind == mf::kBlockAdjust) {
+          mf::splice_row(row, 64, {{k.key(j), K}, {amounts.data() + (size_t)j * A, A}, {&st.side, 1}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
+          if (k.cuts) mf::splice_cut_tail(row + 64 + K + A + 1 + (size_t)length, staged, d0, k.h_index[2 * (size_t)j]);
+        } else {
+          const uint32_t F = st.hi - st.lo;
+          const mf::RowPiece e{st.expect, st.expect ? F : 0};
+          mf::splice_row(row, 64, {{k.key(j), K}, e, {st.value, F}, {head, length}}, k.cuts ? nullptr : staged, 128, depth);
+          if (k.cuts) mf::splice_cut_tail(row + 64 + K + (st.expect ? 2 : 1) * (size_t)F + length, staged, d0, k.h_index[2 * (size_t)j]);
+        }
+      }
+    };
+  return record_updates(c, t, nupd, idx.data(), d_table, k.table_stride, length, d_fresh, hp, k.h_roots, s.rowb, &chunks, rows_out, k.cuts);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2606,6 +2873,38 @@ int mfh_merkle_write_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_
   const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
   return write_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], h_strides[0], h_index, h_status, h_roots, &cuts}, d_table,
                     {field_lo, field_hi, h_values, value_stride, h_expect, expect_stride});
+}
+
+int mfh_merkle_block_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                          const uint8_t *h_kinds, const uint8_t *h_keys, const uint8_t *h_keys_to, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides,
+                          const uint32_t *h_fields, const uint64_t *h_value_at, const uint8_t *h_values, size_t values_bytes, const uint64_t *h_expect_at,
+                          const uint8_t *h_expect, size_t expect_bytes, uint32_t skip_failed, uint8_t *h_rows, const uint64_t *h_row_at, uint8_t *h_roots, uint32_t *h_index,
+                          uint8_t *h_status, uint32_t *h_first_update) {
+  const char *who = "mfh_merkle_block_keys";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  return block_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows, 0, h_index, h_status, h_roots, nullptr}, d_table,
+                    {amount_bytes, h_kinds, h_keys_to, h_amounts, h_sides, h_fields, h_value_at, h_values, values_bytes, h_expect_at, h_expect, expect_bytes, h_row_at,
+                     skip_failed != 0, h_first_update});
+}
+
+int mfh_merkle_block_keys_cut(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,
+                              const uint8_t *h_kinds, const uint8_t *h_keys, const uint8_t *h_keys_to, size_t key_stride, const uint64_t *h_amounts, const uint8_t *h_sides,
+                              const uint32_t *h_fields, const uint64_t *h_value_at, const uint8_t *h_values, size_t values_bytes, const uint64_t *h_expect_at,
+                              const uint8_t *h_expect, size_t expect_bytes, uint32_t skip_failed, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
+                              const size_t *h_strides, const uint64_t *h_row_at, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status, uint32_t *h_first_update) {
+  const char *who = "mfh_merkle_block_keys_cut";
+  if (int rc = tree_refused(c, t, who)) return rc;
+  if (!ncuts || !h_cuts || !h_rows || !h_strides) return fail(c, who, cuts_refused(nk, ncuts, h_cuts, t->depth, h_rows, h_strides, 0));
+  const Cuts cuts{ncuts, h_cuts, h_rows, h_strides};
+  return block_keys(c, t, {who, d_table, table_stride, length, key_bytes, nk, h_keys, key_stride, h_rows[0], 0, h_index, h_status, h_roots, &cuts}, d_table,
+                    {amount_bytes, h_kinds, h_keys_to, h_amounts, h_sides, h_fields, h_value_at, h_values, values_bytes, h_expect_at, h_expect, expect_bytes, h_row_at,
+                     skip_failed != 0, h_first_update});
+}
+
+size_t mfh_merkle_block_row_bytes(uint32_t kind, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t depth, uint32_t field_lo, uint32_t field_hi,
+                                  uint32_t expect, uint32_t cut) {
+  if (kind > mf::kBlockWrite) return 0;
+  return mf::block_row_bytes((uint8_t)kind, key_bytes, amount_bytes, length, depth, field_lo, field_hi, expect != 0, cut != 0);
 }
 
 int mfh_merkle_adjust_keys(mfh_ctx *c, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes, uint32_t nk,

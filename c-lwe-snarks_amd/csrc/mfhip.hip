@@ -1179,6 +1179,8 @@ static int timing_kind(const char *which) {
   if (!strcmp(which, "merkle_grow")) return 47;  // k_grow_nodes, k_grow_spine, k_grow_table of mfh_merkle_grow / mfh_merkle_grow_leaves (merkle.hip): 3 per call with a table and 2 without; rows = the new tree's 2^(new_depth + 1) nodes, the new_depth - depth spine nodes and the new table's 2^new_depth records
   if (!strcmp(which, "merkle_fields")) return 49;  // k_field_gather of mfh_merkle_write_keys with expectations (merkle.hip): one per call, none for plain writes; rows = the unique keys
   if (!strcmp(which, "merkle_write_records")) return 50;  // k_refield_records of mfh_merkle_write_keys (merkle.hip): one per call; rows = the nk new records
+  if (!strcmp(which, "merkle_block_windows")) return 51;  // k_window_gather of mfh_merkle_block_keys (merkle.hip): one per call; rows = the block's unique keys
+  if (!strcmp(which, "merkle_block_records")) return 52;  // k_window_records of mfh_merkle_block_keys (merkle.hip): one per call with an update; rows = the applied steps' updates
   return -1;
 }
 

@@ -1559,6 +1559,137 @@ class MerkleWrite(_RecordStep):
         return self._step_bits(self._public(key, *values), old_record, siblings, index)
 
 
+class Block:
+    """A BLOCK of a keyed ledger: transfers, adjusts and writes in any order, built step by step and applied in that order by MerkleTree.apply_block /
+    apply_block_segments in one device call.  key_bytes = K and amount_bytes = A hold for the whole block; a write's field is per step.  A step's statement is
+    an existing one -- MerkleTransfer, MerkleAdjust or MerkleWrite over (R_j, R_j+1) -- and a step may spend what the step before it delivered; a write may
+    cover balance bytes.  Inserts and removes are no steps of a block: they change membership.
+
+    .transfer(k_from, k_to, v), .adjust(k, v, side=0), .write(k, (lo, hi), value, expect=None) append one step and return the block; len(block) is the
+    number of steps; .steps is the list of (kind, ...) tuples: (Block.TRANSFER, k_from, k_to, v), (Block.ADJUST, k, v, side), (Block.WRITE, k, (lo, hi),
+    value, expect or None).  What needs the record's length (a field's upper end, the balance's room) is judged where the block is applied."""
+
+    TRANSFER, ADJUST, WRITE = 0, 1, 2
+
+    def __init__(self, key_bytes: int, amount_bytes=8):
+        if not isinstance(key_bytes, (int, np.integer)) or not 1 <= key_bytes <= 32:
+            raise CircuitError("Block: key_bytes is in [1, 32]")
+        if not isinstance(amount_bytes, (int, np.integer)) or not 1 <= amount_bytes <= 8:
+            raise CircuitError("Block: amount_bytes is in [1, 8]")
+        self.key_bytes, self.amount_bytes = int(key_bytes), int(amount_bytes)
+        self.steps = []
+
+    def __len__(self):
+        return len(self.steps)
+
+    def _key(self, key) -> bytes:
+        return _checked_key("Block", self.key_bytes, key, "members")
+
+    def _amount(self, v) -> int:
+        if not isinstance(v, (int, np.integer)) or not 0 <= v < 1 << (8 * self.amount_bytes):
+            raise CircuitError(f"Block: the amount is an integer in [0, 2^{8 * self.amount_bytes})")
+        return int(v)
+
+    def transfer(self, k_from, k_to, v):
+        k_from, k_to = self._key(k_from), self._key(k_to)
+        if k_from == k_to:
+            raise CircuitError("Block: a transfer from an account to itself")
+        self.steps.append((self.TRANSFER, k_from, k_to, self._amount(v)))
+        return self
+
+    def adjust(self, k, v, side=0):
+        if not isinstance(side, (int, np.integer)) or side not in (0, 1):
+            raise CircuitError("Block: the side is 0 (a deposit) or 1 (a withdrawal)")
+        self.steps.append((self.ADJUST, self._key(k), self._amount(v), int(side)))
+        return self
+
+    def write(self, k, field, value, expect=None):
+        lo, hi = _field_arg("Block", field, self.key_bytes, 1 << 20)
+        value = bytes(value)
+        expect = None if expect is None else bytes(expect)
+        if len(value) != hi - lo or (expect is not None and len(expect) != hi - lo):
+            raise CircuitError(f"Block: a value is the field's {hi - lo} bytes")
+        self.steps.append((self.WRITE, self._key(k), (lo, hi), value, expect))
+        return self
+
+    def columns(self):
+        """the steps as the arrays mfh_merkle_block_keys takes, made in one pass and kept for as long as `steps` holds the same steps (compared step by step at every call, so an appended, assigned or replaced step makes them anew): a dict of kinds np.uint8 [nk], keys and keys_to
+        np.uint8 [nk, K] (keys_to: zero for a step that is no transfer), amounts np.uint64 [nk], sides np.uint8 [nk], fields np.uint32 [nk, 2], value_at and
+        expect_at np.uint64 [nk] (offsets into values and expect; 2^64 - 1: no expectation), values and expect np.uint8 (at least one byte each), updates
+        (the record updates of all steps) and field_hi, the largest hi of a written field (0: no write)"""
+        now = tuple(self.steps)  # (a step is an immutable tuple, so the steps are what they were exactly when this tuple is: appended to, assigned, or edited in place)
+        cached = getattr(self, "_columns", None)
+        if cached is not None and cached[0] == now:
+            return cached[1]
+        K, nk = self.key_bytes, len(self.steps)
+        kinds, keys, keys_to, amounts, sides, fields, value_at, expect_at = [], bytearray(), bytearray(), [], [], [], [], []
+        values, expect, none, field_hi = bytearray(), bytearray(), bytes(K), 0
+        for s in self.steps:
+            kinds.append(s[0])
+            keys += s[1]
+            if s[0] == self.WRITE:
+                keys_to += none
+                amounts.append(0)
+                sides.append(0)
+                fields += s[2]
+                field_hi = max(field_hi, s[2][1])
+                value_at.append(len(values))
+                values += s[3]
+                expect_at.append(0xFFFFFFFFFFFFFFFF if s[4] is None else len(expect))
+                if s[4] is not None:
+                    expect += s[4]
+            else:
+                transfer = s[0] == self.TRANSFER
+                keys_to += s[2] if transfer else none
+                amounts.append(s[3] if transfer else s[2])
+                sides.append(0 if transfer else s[3])
+                fields += (0, 0)
+                value_at.append(0)
+                expect_at.append(0xFFFFFFFFFFFFFFFF)
+        cols = {"kinds": np.array(kinds, dtype=np.uint8).reshape(nk), "keys": np.frombuffer(bytes(keys), dtype=np.uint8).reshape(nk, K),
+                "keys_to": np.frombuffer(bytes(keys_to), dtype=np.uint8).reshape(nk, K), "amounts": np.array(amounts, dtype=np.uint64).reshape(nk),
+                "sides": np.array(sides, dtype=np.uint8).reshape(nk), "fields": np.array(fields, dtype=np.uint32).reshape(nk, 2),
+                "value_at": np.array(value_at, dtype=np.uint64).reshape(nk), "expect_at": np.array(expect_at, dtype=np.uint64).reshape(nk),
+                "values": np.frombuffer(bytes(values) or b"\0", dtype=np.uint8), "expect": np.frombuffer(bytes(expect) or b"\0", dtype=np.uint8),
+                "values_bytes": len(values), "expect_bytes": len(expect), "updates": nk + kinds.count(self.TRANSFER), "field_hi": field_hi}
+        self._columns = (now, cols)
+        return cols
+
+    def statement_key(self, j: int, length: int, depth: int):
+        """what names step j's statement object, the class and its arguments: ("MerkleTransfer", K, length, depth, A), ("MerkleAdjust", K, length, depth, A)
+        or ("MerkleWrite", K, length, depth, (lo, hi), expect) -- getattr(words, key[0])(*key[1:]) builds it"""
+        step = self.steps[j]
+        if step[0] == self.WRITE:
+            return ("MerkleWrite", self.key_bytes, int(length), int(depth), step[2], step[4] is not None)
+        return ("MerkleTransfer" if step[0] == self.TRANSFER else "MerkleAdjust", self.key_bytes, int(length), int(depth), self.amount_bytes)
+
+    def statements(self, length: int, depth: int, roots, status=None):
+        """one entry a step: (statement_key(j, length, depth), the statement bytes for (R_j, R_j+1) = roots[j], roots[j + 1]) -- the existing classes'
+        .statement(..) on a stand-in that has the sizes and no circuit, so nothing is compiled here.  roots: the nk + 1 roots of 32 bytes.  status (nk values,
+        as apply_block gives them): a step with a status other than 0 was skipped and gives None"""
+        if len(roots) != len(self.steps) + 1:
+            raise CircuitError("Block: statements takes the nk + 1 roots R_0 .. R_nk")
+        if status is not None and len(status) != len(self.steps):
+            raise CircuitError("Block: status has one value a step")
+        out = []
+        for j, step in enumerate(self.steps):
+            if status is not None and int(status[j]):
+                out.append(None)
+                continue
+            key = self.statement_key(j, length, depth)
+            st = object.__new__(globals()[key[0]])
+            st.key_bytes, st.length, st.depth = key[1:4]
+            old, new = bytes(roots[j]), bytes(roots[j + 1])
+            if step[0] == self.WRITE:
+                st.field, st.field_bytes, st.expect = step[2], step[2][1] - step[2][0], step[4] is not None
+                pieces = (step[1],) + ((step[4],) if st.expect else ()) + (step[3],)
+            else:
+                st.amount_bytes = self.amount_bytes
+                pieces = step[1:]
+            out.append((key, st.statement(old, new, *pieces)))
+        return out
+
+
 def _keys_array(keys, who: str):
     """keys as np.uint8 [n, K]: an array of that shape, or n bytes-likes of one length K >= 1"""
     if isinstance(keys, np.ndarray):

@@ -738,6 +738,68 @@ int mfh_merkle_write_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, siz
                               uint32_t field_hi, uint32_t nk, const uint8_t *h_keys, size_t key_stride, const uint8_t *h_values, size_t value_stride,
                               const uint8_t *h_expect, size_t expect_stride, uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows,
                               const size_t *h_strides, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status);
+/* A BLOCK: nk sequential steps of MIXED kinds -- transfers, adjusts and writes in any order -- on an indexed table whose records carry a balance and its tree
+ * in ONE call, and every step's packed input row: that of words.MerkleTransfer, words.MerkleAdjust or words.MerkleWrite, as the three calls above write it.
+ * key_bytes and amount_bytes hold for the whole call; a write's field is PER STEP.  A write may cover balance bytes: a later transfer or adjust of the block
+ * then reads the balance those bytes spell.  No step changes membership (inserts and removes are no kinds of a block), so one search serves all steps.
+ *   semantics  byte for byte what the three calls give, run once per step in order on the same table and tree: the table's whole allocation, every node of
+ *              the tree, the roots and row j, which describes table and tree as they stood before step j.  A key may occur in ANY number of steps of any
+ *              kind, and a step sees what the earlier steps of the block left.
+ *   arguments  h_kinds[j]: 0 = a transfer, 1 = an adjust, 2 = a write.  Key j, the key_bytes bytes at h_keys + j * key_stride, is the sender, the account or
+ *              the written key; h_keys_to + j * key_stride is a transfer's receiver (read for transfers only; NULL in a block without one).  h_amounts[j]
+ *              (transfers and adjusts; NULL in a block of writes) is below 2^(8 amount_bytes); h_sides[j] (adjusts) is 0 = a deposit or 1 = a withdrawal,
+ *              h_sides = NULL: all deposits.  A write's field is bytes [h_fields[2 j], h_fields[2 j + 1]) of the record, 2 key_bytes <= lo < hi <= length,
+ *              its value the hi - lo bytes at h_values + h_value_at[j] (inside the buffer's values_bytes bytes) and its expectation, if it has one, those
+ *              at h_expect + h_expect_at[j] (inside expect_bytes); h_expect_at[j] = MFH_BLOCK_NO_EXPECT or h_expect_at = NULL: a plain write.  These
+ *              arrays have nk entries each and are read at the steps of their kinds alone.  skip_failed: the policy, below.
+ *   outputs    h_rows (may be NULL: no rows) is ONE buffer: row j is written at h_rows + h_row_at[j], and h_row_at has nk + 1 entries, the slot of row j
+ *              being [h_row_at[j], h_row_at[j + 1]) -- at least mfh_merkle_block_row_bytes of the step.  h_index receives nk PAIRS: (the sender's
+ *              record, the receiver's) of a transfer, (the record, 0xFFFFFFFF) of a one-record step, 0xFFFFFFFF for a key that is no member.  h_status
+ *              receives per step the first that applies, with the numbers of the three calls: 0 = fine; 1 = the key (a transfer's sender) is not a member; 2 =
+ *              a transfer's receiver is not a member; 3 = an overdraft against the RUNNING balance; 4 = an overflow of the running balance; 5 = the RUNNING
+ *              field is not what the step expects.  A step with a status is not applied, and the steps behind it are judged without it.
+ *              h_first_update receives nk + 1 entries: step j's record updates are [h_first_update[j], h_first_update[j + 1]), none, one or two, and nupd =
+ *              h_first_update[nk].  h_roots (may be NULL; room for 2 nk + 1 roots) receives the nupd + 1 roots, one behind EVERY update: the root before
+ *              step j is root h_first_update[j], the root behind it root h_first_update[j + 1].
+ *   policy     skip_failed = 0, fail-fast: any status other than 0 returns MFH_EINVAL after the search with h_status, h_index and h_first_update (all zero)
+ *              filled, table and tree unwritten and no record or tree kernel launched.  skip_failed = 1: the steps with a status are left out -- no update,
+ *              their row's slot is not touched, R_j+1 = R_j -- every other step is applied as if the block had been given without them, and the call
+ *              returns MFH_OK with the statuses.
+ *   how        ONE launch of k_key_locate over the sorted unique keys of all steps and behind it ONE of k_window_gather: unique key u has a WINDOW of its
+ *              record, the hull of what its steps touch (the balance field for transfers and adjusts, every written field), gathered into a slot of
+ *              ceil(window bytes / 16) 16-byte units; both come back under ONE wait.  The host walks the steps in order over the running window bytes
+ *              (merkle_block.hpp); ONE launch of k_window_records builds all nupd new records from the table before the block, per-update descriptors and
+ *              the uploaded window bytes; they go through mfh_merkle_update_records' machinery in uniform chunks of updates (the most whose rows fit 64 MiB
+ *              when every update is charged the most row bytes an update of any step stands for, at least one).  A transfer whose two updates fall into two
+ *              chunks is spliced from a host copy of its first update's pieces.  The call synchronises the stream behind the search and every chunk.
+ * mfh_merkle_block_keys_cut is the same with the path cut (above): h_rows[0] is the one buffer of the segment-0 rows, addressed through h_row_at -- a
+ * transfer's is that of MerkleTransfer(.., c_0, joined=False), 128 zero bytes in front, an adjust's and a write's the statement's own at depth c_0 -- and
+ * h_strides[0] is not read; every upper segment g has ONE MerkleSegment row per UPDATE, update r's at h_rows[g] + r * h_strides[g], so its array has room
+ * for the updates of all steps.  It has no "no rows" mode.
+ * MFH_EINVAL, with its own mfh_last_error text naming the function and nothing queued: what mfh_merkle_adjust_keys refuses of the table, the keys and
+ * amount_bytes; nk > 0 with h_kinds, h_first_update or, with rows, h_row_at null; a kind above 2; a transfer without h_keys_to, with a sentinel receiver or
+ * to its own sender; a transfer or an adjust without h_amounts or with an amount above 2^(8 amount_bytes) - 1; a side above 1; a write without h_fields,
+ * h_value_at or h_values, with lo < 2 key_bytes, hi <= lo or hi > length, with a value outside h_values or an expectation outside h_expect; a row slot
+ * shorter than the step's row; 2^32 or more window bytes summed over the updates of all steps, one window of its key an update (the new records' units are
+ * bounded as in mfh_merkle_adjust_keys, which bounds the gather's units too); for the cut call, what the cut calls above refuse.  nk = 0 does nothing.
+ * Kernel timing kinds: "merkle_locate" (1 per call, rows = 2^depth), "merkle_block_windows" (1 per call, rows = the unique keys), "merkle_block_records" (1
+ * per call with an update, rows = nupd), then per chunk as mfh_merkle_adjust_keys on nupd updates. */
+#define MFH_BLOCK_NO_EXPECT (~(uint64_t)0)
+int mfh_merkle_block_keys(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                          uint32_t nk, const uint8_t *h_kinds, const uint8_t *h_keys, const uint8_t *h_keys_to, size_t key_stride, const uint64_t *h_amounts,
+                          const uint8_t *h_sides, const uint32_t *h_fields, const uint64_t *h_value_at, const uint8_t *h_values, size_t values_bytes,
+                          const uint64_t *h_expect_at, const uint8_t *h_expect, size_t expect_bytes, uint32_t skip_failed, uint8_t *h_rows,
+                          const uint64_t *h_row_at, uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status, uint32_t *h_first_update);
+int mfh_merkle_block_keys_cut(mfh_ctx *ctx, mfh_merkle *t, uint8_t *d_table, size_t table_stride, uint32_t length, uint32_t key_bytes, uint32_t amount_bytes,
+                              uint32_t nk, const uint8_t *h_kinds, const uint8_t *h_keys, const uint8_t *h_keys_to, size_t key_stride,
+                              const uint64_t *h_amounts, const uint8_t *h_sides, const uint32_t *h_fields, const uint64_t *h_value_at, const uint8_t *h_values,
+                              size_t values_bytes, const uint64_t *h_expect_at, const uint8_t *h_expect, size_t expect_bytes, uint32_t skip_failed,
+                              uint32_t ncuts, const uint32_t *h_cuts, uint8_t *const *h_rows, const size_t *h_strides, const uint64_t *h_row_at,
+                              uint8_t *h_roots, uint32_t *h_index, uint8_t *h_status, uint32_t *h_first_update);
+/* the bytes of a block step's row: kind as h_kinds has it, a write's field (field_lo, field_hi) and whether it has an expectation (both ignored for the other
+ * kinds), over `depth` levels; cut != 0: a segment-0 row of a cut call, depth = c_0.  0 for a kind above 2 */
+size_t mfh_merkle_block_row_bytes(uint32_t kind, uint32_t key_bytes, uint32_t amount_bytes, uint32_t length, uint32_t depth, uint32_t field_lo,
+                                  uint32_t field_hi, uint32_t expect, uint32_t cut);
 /* The SUPPLY of such a table: h_sum[0] | h_sum[1] << 64 = the sum of the balances (bytes [2 key_bytes, 2 key_bytes + amount_bytes), big-endian) of all LIVE
  * records (lo < hi) of the 2^depth records at d_table, *h_live (may be NULL) their number.  What is in the balance bytes of a record that is not live does
  * not count.  The table is only read; the tree is used for its depth alone.  Transfers leave the sum as it is, a batch of adjusts changes it by its deposits
